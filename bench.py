@@ -7,6 +7,9 @@ top_k=40, Lx=80 phonemes, 150 prompt frames -> 650 generated frames (the referen
 cap ends generation).  codec tokens = K * generated frames.
 
   python bench.py --gpus 1 --steps 3 --warmup 1
+  python bench.py --gpus 1 --steps 3 --warmup 1 --full   (+ the blocks below the headline: kernel rooflines, A/Bs, the
+                                                          other BASELINE configs, ragged batches, codec, CPU baseline)
+  python bench.py ... --dump-outputs DIR                  (the last timed step's outputs as DIR/<name>.npy, float32)
   python bench.py --gpus N ...            (no launcher: starts its own N ranks through torch.distributed.run)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
@@ -64,6 +67,13 @@ def parse():
                         "reported as the `ab` object of the JSON line.  auto (default, N = 1 only): the default-ON launch-shape feature "
                         "of this run's step - fr_one=0:1 at one row per step, finished_rows=0:16 at 2..16 rows, wide_gemm=0:1 above; none: skip")
     p.add_argument("--ab-pairs", type=int, default=7)
+    p.add_argument("--full", action="store_true",
+                   help="everything besides the headline: box probe, kernel microbenchmarks and rooflines, sampler stamps, one_sample, "
+                        "the A/Bs, the other BASELINE configs, ragged batches, codec and CPU baseline.  Off: set up, warm up, time the "
+                        "steps, print the result line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float32; "
+                        "token ids are exact in it), at most 64 MB in all")
     return p.parse_args()
 
 
@@ -438,17 +448,21 @@ class Workload:
         if self.edit:
             mi = torch.tensor([[list(self.span)]], dtype=torch.int64)
             res = eng.inference(self.xs[0], self.xls[0], self.ys[0], mi, silence_tokens=[1388, 1898, 131], _seed=seed, **self.knobs)
+            self.last_outputs = {"u0_res": res}
             return [None], (int(res.shape[2]) - (self.prompt_frames - (self.span[1] - self.span[0]))) * K
         if self.best_of > 1:      # the reference's front-ends run this mode (gradio_app.py:506 sample_batch_size = 3): the kept sample's frames count
             res, gen = eng.inference_tts_batch(self.xs[0], self.xls[0], self.ys[0], kvcache=1, batch_size=self.best_of,
                                                silence_tokens=[1388, 1898, 131], _seed=seed, **self.knobs)
             gens = [gen]
+            self.last_outputs = {"u0_res": res, "u0_gen": gen}
         elif self.B == 1:
             res, gen = eng.inference_tts(self.xs[0], self.xls[0], self.ys[0], kvcache=1, silence_tokens=[1388, 1898, 131], _seed=seed, **self.knobs)
             gens = [gen]
+            self.last_outputs = {"u0_res": res, "u0_gen": gen}
         else:
             outs = eng.inference_tts_multi([x[0] for x in self.xs], [y[0] for y in self.ys], silence_tokens=[1388, 1898, 131], _seed=seed, **self.knobs)
             gens = [o[1] for o in outs]
+            self.last_outputs = {f"u{u}_{n}": t for u, o in enumerate(outs) for n, t in zip(("res", "gen"), o)}
         return gens, sum(int(g.shape[2]) * K for g in gens)
 
     def label(self, use_graph=True):
@@ -636,6 +650,25 @@ def cpu_only(args):
             json.dump(j, f, indent=1, sort_keys=True)
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """`--dump-outputs DIR`: every array the last timed step returned to its caller, as DIR/<name>.npy in float32 (token ids
+    < 2**24 are exact in it), so that two builds can be compared output for output.  Over 64 MB in all, each array is cut to a
+    fixed, seeded sample of its flattened elements (the same indices in every run of the same arguments)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {n: t.detach().cpu().numpy().astype(np.float32) for n, t in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    for n, v in sorted(arrays.items()):
+        if total > DUMP_CAP_BYTES:
+            keep = max(1, int(v.size * DUMP_CAP_BYTES // total))
+            idx = np.sort(np.random.RandomState(0).choice(v.size, keep, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{n}.npy"), v)
+
+
 def spawn_command(gpus, argv, port):
     """`python bench.py --gpus N` outside a launcher: the command that starts the N ranks (one process per GPU, rendezvous on
     127.0.0.1) with this very argument list - the form the driver itself uses for N > 1."""
@@ -692,7 +725,7 @@ def main():
     assert args.gpus == n_gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}"
 
     from voicecraft_amd import dist as vdist
-    box = box_block(dev) if (rank == 0 and world == 1) else None
+    box = box_block(dev) if (args.full and rank == 0 and world == 1) else None
     wl = Workload(args.preset, args.mode, args.batch, args.lx, args.prompt_frames, args.top_k, args.dtype, dev,
                   use_graph=not args.no_graph, rank=rank, world=world)
     a, sd, eng, K, B, edit, span, Tg, prompts = wl.a, wl.sd, wl.eng, wl.K, wl.B, wl.edit, wl.span, wl.Tg, wl.prompts
@@ -741,89 +774,15 @@ def main():
         import numpy as np
         merged = vdist.merge_in_utterance_order(gathered)
         np.savez(args.dump, **{f"u{u}": m.cpu().numpy() for u, m in enumerate(merged)})
+    if rank == 0 and args.dump_outputs:      # this rank's own outputs, and with N > 1 the token blocks the gather handed it
+        outs = dict(wl.last_outputs)
+        if gathered:
+            outs.update({f"gathered_u{u}": m for u, m in enumerate(vdist.merge_in_utterance_order(gathered))})
+        dump_outputs(args.dump_outputs, outs)
     if rank == 0:
         frames = tokens / K
         value = tokens / dt
         step_bytes = step_alg_bytes(a, args.dtype, B, wl.s_mean())      # weights (once per step) + KV read + KV write of each of the B sequences
-        # dominant kernel = the largest share of a step's kernel time.  Every decode kernel runs once per layer, so it is the one with the
-        # longest launch: each is timed in isolation here (layers rotate: cold caches), the longest becomes the `roofline` object - the
-        # FFN up-projection since round 5 (profiles/r05d_rocprof_kernel_stats.txt: 23.4 % against 20.4 % for the down-projection, which
-        # was the dominant one through round 4), and `in_situ` carries the committed rocprof average of the same kernel
-        mb_rows = min(B, 16)       # the kernel microbenchmarks drive the <=16-row decode kernels
-        c0 = eng.launch_counts()
-        step_ms, _ = eng.bench_kernel("step", n_rows=mb_rows, iters=8)
-        kernels, kraw = {}, {}
-        for kn in ("qkv", "attn", "oproj", "ffn1", "ffn2", "qkv_hot", "oproj_hot", "ffn1_hot", "ffn2_hot"):
-            # (a short untimed run first, then the better of two: the first microbenchmark after the step used to catch the chip in
-            # transition - the same kernel read 6.3 / 6.7 / 7.8 us on three boxes while its in-situ average stayed at 6.4-6.5)
-            eng.bench_kernel(kn, n_rows=mb_rows, iters=8)
-            ms_, by_ = min(eng.bench_kernel(kn, n_rows=mb_rows, iters=64), eng.bench_kernel(kn, n_rows=mb_rows, iters=64))
-            kraw[kn] = (ms_, by_)
-        for kn in list(kraw):      # a second sweep, the better of the two kept: the first kernel timed after the whole-step microbenchmark has
-            ms_, by_ = min(kraw[kn], eng.bench_kernel(kn, n_rows=mb_rows, iters=64))      # read 7.4-8.8 us for a launch that takes 6.5 in situ (r06b / r06d)
-            kraw[kn] = (ms_, by_)
-            kernels[kn] = {"avg_us": round(ms_ * 1e3, 2), "GB/s": round(by_ / (ms_ * 1e-3) / 1e9, 1)}
-        c1 = eng.launch_counts()
-        fr1_form = c1["row_gemm_fr1"] > c0["row_gemm_fr1"]      # which forms the microbenchmarks (= the step) really launched
-        fr_form = c1["rows_gemm_fr"] > c0["rows_gemm_fr"]
-        # ... decided by the committed in-situ trace of this very configuration where there is one (what a reader of profiles/ computes),
-        # by the isolated times otherwise
-        ins = {k: in_situ(k, args) for k in ("ffn1", "ffn2", "qkv")}
-        if all(v and v.get("avg_us") for v in ins.values()):
-            dom = max(ins, key=lambda k: ins[k]["avg_us"])
-        else:
-            dom = max(("ffn1", "ffn2", "qkv"), key=lambda k: kraw[k][0])
-        k_ms, k_bytes = kraw[dom]
-        what = {"ffn1": "FFN up-projection", "ffn2": "FFN down-projection", "qkv": "QKV projection"}[dom]
-        if fr_form:
-            form = {"ffn2": "rows_gemm_fr_k<plain> (finished rows: 8-channel tiles over the whole K)", "ffn1": "rows_gemm_k<LayerNorm fold of finished rows, ReLU>",
-                    "qkv": "rows_gemm_k<LayerNorm fold of finished rows, QKV>"}[dom] + ("" if B <= 16 else f"; microbenchmarked at 16 rows - this run's {B}-row steps use the wide-decode kernel rows_gemm_mt_k")
-        elif fr1_form:
-            form = {"ffn2": "row_gemm_fr1_k<plain, residual> (finished row: 8-channel tiles over the whole K, two k-tiles per MFMA fragment)",
-                    "ffn1": "rows_gemm_k<LayerNorm fold of h + 2 slabs, ReLU> (16-channel tiles)",
-                    "qkv": "row_gemm_fr1_k<LayerNorm fold, QKV> (8-channel tiles, two k-tiles per MFMA fragment)"}[dom]
-        else:
-            form = {"ffn2": "rows_gemm_k<plain, split-K slabs>", "ffn1": "rows_gemm_k<LayerNorm fold, ReLU>", "qkv": "rows_gemm_k<LayerNorm fold, QKV>"}[dom]
-        # `achieved` / `frac`: the IN-SITU figure (every launch of the decode loop under rocprofv3, caches as the step leaves them) when the
-        # committed trace belongs to this configuration and this build; otherwise the isolated microbenchmark of this run, which comes out
-        # ~3-5 % higher (a quiet chip) and always rides along as `isolated_*`
-        iso_gbs = k_bytes / (k_ms * 1e-3) / 1e9
-        ins_dom = in_situ(dom, args)
-        tr = pmc_traffic(dom, args)
-        if ins_dom and ins_dom.get("frac"):
-            ach_us, measured = ins_dom["avg_us"], f"in situ: rocprofv3 --kernel-trace average over {ins_dom['calls']} launches of the decode loop, committed trace of this build ({ins_dom['source']})"
-        else:
-            ach_us, measured = k_ms * 1e3, "isolated: the kernel back to back over rotating layers, HIP events on the launch stream (vc_bench_kernel); no in-situ trace of this build and configuration is on file"
-        ach_gbs = k_bytes / (ach_us * 1e-6) / 1e9
-        roof = {"bound": "hbm", "kernel": f"{form} ({what}; the longest of the step's per-layer launches)",
-                "achieved": round(ach_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(ach_gbs / HBM_PEAK_GBS, 4), "traffic": tr["bytes"] if tr else None,
-                "traffic_source": ({k: tr[k] for k in ("source", "box", "lib_stamp")} if tr else None),
-                "bytes_per_launch": k_bytes, "avg_launch_us": round(ach_us, 2),
-                "measured": measured,
-                "isolated_frac": round(iso_gbs / HBM_PEAK_GBS, 4), "isolated_avg_launch_us": round(k_ms * 1e3, 2), "isolated_achieved": round(iso_gbs, 1),
-                "in_situ": ins_dom, "lib_stamp": lib_stamp(),
-                "per_layer_launches": {k: {"isolated_us": kernels[k]["avg_us"], "in_situ": in_situ(k, args)} for k in ("qkv", "attn", "oproj", "ffn1", "ffn2")}}
-        # the prefill is GEMM-shaped: MFMA rooflines of its widest block GEMM (FFN up-projection) at the run's own pass
-        # size and at a full 512-row pass, and of the MFMA tile attention
-        own_rows = min(512, B * ((args.lx + (args.prompt_frames + 1 if not edit else args.prompt_frames - (span[1] - span[0]) + 2 * K + 4) + 15) // 16 * 16))
-        pk = MFMA_PEAK_TF[args.dtype]
-
-        def mfma_obj(which, rows, label):
-            ms_, fl_ = eng.bench_kernel(which, n_rows=rows, iters=32)
-            return {"bound": "mfma", "kernel": label, "achieved": round(fl_ / (ms_ * 1e-3) / 1e12, 1), "peak": pk, "unit": "TFLOP/s",
-                    "frac": round(fl_ / (ms_ * 1e-3) / 1e12 / pk, 4), "traffic": None, "flops_per_launch": fl_, "avg_launch_us": round(ms_ * 1e3, 2)}
-        mfma = mfma_obj("pf_ffn1", 512, "rows_gemm_blk_k<ReLU> (prefill FFN up-projection, 512 rows)")
-        mfma["at_run_rows"] = mfma_obj("pf_ffn1", own_rows, f"rows_gemm_blk_k<ReLU> (prefill FFN up-projection, this run's {own_rows}-row pass)")
-        mfma["at_2048_rows"] = mfma_obj("pf_ffn1", 2048, "rows_gemm_big_k<ReLU> (prefill FFN up-projection, a 2048-row stream: 256 x 256 tiles, LDS-DMA)")
-        mfma["attention"] = mfma_obj("pf_attn", 512, "tile_attn_k (prefill attention, 512 causal rows of one sequence, all heads)")
-        try:      # the second kernel (prompts of >= 768 rows): as many rows as this engine's cache holds, 1024 by default
-            rows_long = min(2048, eng.max_positions) // 64 * 64
-            if rows_long >= 768:
-                mfma["attention"]["long_prompt"] = mfma_obj("pf_attn", rows_long, f"tile_attn64_k (prefill attention, {rows_long} causal rows of one sequence, all heads: "
-                                                            "64 query rows per workgroup, P in registers)")
-        except Exception as e:   # reporting only
-            mfma["attention"]["long_prompt"] = {"error": str(e)}
         # per step TAKEN: the timed region also covers the (graph-rounded) tail of replayed no-op steps after the last sequence
         # retired, so this slightly OVERstates the step (never understates it); the launched count is kept as an annotation
         dec_step_ms = dec_ms / max(1, steps_run)
@@ -836,11 +795,91 @@ def main():
             "rtf": round(dt / (frames / 50.0), 4),
             "decode_ms_per_token_step": round(dec_step_ms, 4), "prefill_ms": round(pre_ms / args.steps, 2),
             "decode_steps": {"taken": steps_run // max(1, args.steps), "launched": steps_launched // max(1, args.steps)},
-            "decode_step": {"alg_bytes": int(step_bytes), "isolated_step_ms": round(step_ms, 4),
+            "decode_step": {"alg_bytes": int(step_bytes),
                             "hbm_frac_in_loop": round(step_bytes / (dec_step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if dec_step_ms > 0 else None},
-            "roofline": roof, "kernels": kernels,
         }
-        out["prefill_roofline"] = mfma
+        if args.full:
+            # dominant kernel = the largest share of a step's kernel time.  Every decode kernel runs once per layer, so it is the one with the
+            # longest launch: each is timed in isolation here (layers rotate: cold caches), the longest becomes the `roofline` object - the
+            # FFN up-projection since round 5 (profiles/r05d_rocprof_kernel_stats.txt: 23.4 % against 20.4 % for the down-projection, which
+            # was the dominant one through round 4), and `in_situ` carries the committed rocprof average of the same kernel
+            mb_rows = min(B, 16)       # the kernel microbenchmarks drive the <=16-row decode kernels
+            c0 = eng.launch_counts()
+            step_ms, _ = eng.bench_kernel("step", n_rows=mb_rows, iters=8)
+            kernels, kraw = {}, {}
+            for kn in ("qkv", "attn", "oproj", "ffn1", "ffn2", "qkv_hot", "oproj_hot", "ffn1_hot", "ffn2_hot"):
+                # (a short untimed run first, then the better of two: the first microbenchmark after the step used to catch the chip in
+                # transition - the same kernel read 6.3 / 6.7 / 7.8 us on three boxes while its in-situ average stayed at 6.4-6.5)
+                eng.bench_kernel(kn, n_rows=mb_rows, iters=8)
+                ms_, by_ = min(eng.bench_kernel(kn, n_rows=mb_rows, iters=64), eng.bench_kernel(kn, n_rows=mb_rows, iters=64))
+                kraw[kn] = (ms_, by_)
+            for kn in list(kraw):      # a second sweep, the better of the two kept: the first kernel timed after the whole-step microbenchmark has
+                ms_, by_ = min(kraw[kn], eng.bench_kernel(kn, n_rows=mb_rows, iters=64))      # read 7.4-8.8 us for a launch that takes 6.5 in situ (r06b / r06d)
+                kraw[kn] = (ms_, by_)
+                kernels[kn] = {"avg_us": round(ms_ * 1e3, 2), "GB/s": round(by_ / (ms_ * 1e-3) / 1e9, 1)}
+            c1 = eng.launch_counts()
+            fr1_form = c1["row_gemm_fr1"] > c0["row_gemm_fr1"]      # which forms the microbenchmarks (= the step) really launched
+            fr_form = c1["rows_gemm_fr"] > c0["rows_gemm_fr"]
+            # ... decided by the committed in-situ trace of this very configuration where there is one (what a reader of profiles/ computes),
+            # by the isolated times otherwise
+            ins = {k: in_situ(k, args) for k in ("ffn1", "ffn2", "qkv")}
+            if all(v and v.get("avg_us") for v in ins.values()):
+                dom = max(ins, key=lambda k: ins[k]["avg_us"])
+            else:
+                dom = max(("ffn1", "ffn2", "qkv"), key=lambda k: kraw[k][0])
+            k_ms, k_bytes = kraw[dom]
+            what = {"ffn1": "FFN up-projection", "ffn2": "FFN down-projection", "qkv": "QKV projection"}[dom]
+            if fr_form:
+                form = {"ffn2": "rows_gemm_fr_k<plain> (finished rows: 8-channel tiles over the whole K)", "ffn1": "rows_gemm_k<LayerNorm fold of finished rows, ReLU>",
+                        "qkv": "rows_gemm_k<LayerNorm fold of finished rows, QKV>"}[dom] + ("" if B <= 16 else f"; microbenchmarked at 16 rows - this run's {B}-row steps use the wide-decode kernel rows_gemm_mt_k")
+            elif fr1_form:
+                form = {"ffn2": "row_gemm_fr1_k<plain, residual> (finished row: 8-channel tiles over the whole K, two k-tiles per MFMA fragment)",
+                        "ffn1": "rows_gemm_k<LayerNorm fold of h + 2 slabs, ReLU> (16-channel tiles)",
+                        "qkv": "row_gemm_fr1_k<LayerNorm fold, QKV> (8-channel tiles, two k-tiles per MFMA fragment)"}[dom]
+            else:
+                form = {"ffn2": "rows_gemm_k<plain, split-K slabs>", "ffn1": "rows_gemm_k<LayerNorm fold, ReLU>", "qkv": "rows_gemm_k<LayerNorm fold, QKV>"}[dom]
+            # `achieved` / `frac`: the IN-SITU figure (every launch of the decode loop under rocprofv3, caches as the step leaves them) when the
+            # committed trace belongs to this configuration and this build; otherwise the isolated microbenchmark of this run, which comes out
+            # ~3-5 % higher (a quiet chip) and always rides along as `isolated_*`
+            iso_gbs = k_bytes / (k_ms * 1e-3) / 1e9
+            ins_dom = in_situ(dom, args)
+            tr = pmc_traffic(dom, args)
+            if ins_dom and ins_dom.get("frac"):
+                ach_us, measured = ins_dom["avg_us"], f"in situ: rocprofv3 --kernel-trace average over {ins_dom['calls']} launches of the decode loop, committed trace of this build ({ins_dom['source']})"
+            else:
+                ach_us, measured = k_ms * 1e3, "isolated: the kernel back to back over rotating layers, HIP events on the launch stream (vc_bench_kernel); no in-situ trace of this build and configuration is on file"
+            ach_gbs = k_bytes / (ach_us * 1e-6) / 1e9
+            roof = {"bound": "hbm", "kernel": f"{form} ({what}; the longest of the step's per-layer launches)",
+                    "achieved": round(ach_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(ach_gbs / HBM_PEAK_GBS, 4), "traffic": tr["bytes"] if tr else None,
+                    "traffic_source": ({k: tr[k] for k in ("source", "box", "lib_stamp")} if tr else None),
+                    "bytes_per_launch": k_bytes, "avg_launch_us": round(ach_us, 2),
+                    "measured": measured,
+                    "isolated_frac": round(iso_gbs / HBM_PEAK_GBS, 4), "isolated_avg_launch_us": round(k_ms * 1e3, 2), "isolated_achieved": round(iso_gbs, 1),
+                    "in_situ": ins_dom, "lib_stamp": lib_stamp(),
+                    "per_layer_launches": {k: {"isolated_us": kernels[k]["avg_us"], "in_situ": in_situ(k, args)} for k in ("qkv", "attn", "oproj", "ffn1", "ffn2")}}
+            # the prefill is GEMM-shaped: MFMA rooflines of its widest block GEMM (FFN up-projection) at the run's own pass
+            # size and at a full 512-row pass, and of the MFMA tile attention
+            own_rows = min(512, B * ((args.lx + (args.prompt_frames + 1 if not edit else args.prompt_frames - (span[1] - span[0]) + 2 * K + 4) + 15) // 16 * 16))
+            pk = MFMA_PEAK_TF[args.dtype]
+
+            def mfma_obj(which, rows, label):
+                ms_, fl_ = eng.bench_kernel(which, n_rows=rows, iters=32)
+                return {"bound": "mfma", "kernel": label, "achieved": round(fl_ / (ms_ * 1e-3) / 1e12, 1), "peak": pk, "unit": "TFLOP/s",
+                        "frac": round(fl_ / (ms_ * 1e-3) / 1e12 / pk, 4), "traffic": None, "flops_per_launch": fl_, "avg_launch_us": round(ms_ * 1e3, 2)}
+            mfma = mfma_obj("pf_ffn1", 512, "rows_gemm_blk_k<ReLU> (prefill FFN up-projection, 512 rows)")
+            mfma["at_run_rows"] = mfma_obj("pf_ffn1", own_rows, f"rows_gemm_blk_k<ReLU> (prefill FFN up-projection, this run's {own_rows}-row pass)")
+            mfma["at_2048_rows"] = mfma_obj("pf_ffn1", 2048, "rows_gemm_big_k<ReLU> (prefill FFN up-projection, a 2048-row stream: 256 x 256 tiles, LDS-DMA)")
+            mfma["attention"] = mfma_obj("pf_attn", 512, "tile_attn_k (prefill attention, 512 causal rows of one sequence, all heads)")
+            try:      # the second kernel (prompts of >= 768 rows): as many rows as this engine's cache holds, 1024 by default
+                rows_long = min(2048, eng.max_positions) // 64 * 64
+                if rows_long >= 768:
+                    mfma["attention"]["long_prompt"] = mfma_obj("pf_attn", rows_long, f"tile_attn64_k (prefill attention, {rows_long} causal rows of one sequence, all heads: "
+                                                                "64 query rows per workgroup, P in registers)")
+            except Exception as e:   # reporting only
+                mfma["attention"]["long_prompt"] = {"error": str(e)}
+            out["decode_step"]["isolated_step_ms"] = round(step_ms, 4)
+            out["roofline"], out["kernels"], out["prefill_roofline"] = roof, kernels, mfma
         # launch-shape options in force (prefetch roles of latency-bound launches, finished-row form, ...): additional work
         # inside the timed region where they add any, nothing skipped
         out["config"]["engine_options"] = options_object(eng.options())
@@ -854,7 +893,7 @@ def main():
                     out["sampler"] = sampler_block(wl, box)
                 except Exception as e:   # reporting only
                     out["sampler"] = {"error": str(e)}
-        if n_gpus == 1 and B == 1 and not edit and not args.no_codec:
+        if args.full and n_gpus == 1 and B == 1 and not edit and not args.no_codec:
             try:
                 out["one_sample"] = one_sample_block(eng, a, dev, args)
             except Exception as e:   # reporting only
@@ -866,7 +905,7 @@ def main():
             ab = ("fr_one=0:1" if B == 1 else "finished_rows=0:16" if B <= 16 else "wide_gemm=0:1")
             if B == 1:
                 more = ["qkv_p8=0:1"]
-        if n_gpus == 1 and ab and ab != "none":
+        if args.full and n_gpus == 1 and ab and ab != "none":
             try:
                 out["ab"] = ab_block(eng, one_step, ab, max(3, args.ab_pairs))
             except Exception as e:   # reporting only
@@ -879,17 +918,17 @@ def main():
                     out["ab_more"].append(r)
                 except Exception as e:   # reporting only
                     out["ab_more"].append({"knob": spec, "error": str(e)})
-        if n_gpus == 1 and B == 1 and not edit and args.preset == "giga830M" and not args.no_configs:
+        if args.full and n_gpus == 1 and B == 1 and not edit and args.preset == "giga830M" and not args.no_configs:
             # the other BASELINE configurations on their own engines (after the headline's timed region; ~20 s)
             del eng, wl
             out["configs"] = configs_block(args, dev, sd)
             out["ragged"] = ragged_block(args, dev, sd)
-        if n_gpus == 1 and not args.no_codec:
+        if args.full and n_gpus == 1 and not args.no_codec:
             try:
                 out["codec"] = codec_block(dev)
             except Exception as e:   # reporting only
                 out["codec"] = {"error": str(e)}
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, sd, a, prompts[0][0], prompts[0][1], prompts[0][2])
             except Exception as e:   # the baseline is reporting only; never lose the GPU number to it

@@ -101,3 +101,23 @@ def test_plain_multi_gpu_entry_builds_the_launcher_command_and_refuses_a_box_wit
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
     assert r.returncode != 0 and f"--gpus {n} but only" in r.stdout, r.stdout[-2000:]
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_dump_outputs_writes_float32_arrays_and_a_fixed_sample_over_the_cap(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: one float32 .npy per returned array (token ids exact); over the size cap a seeded sample of the flattened
+    elements, the same one in every run."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    bench.dump_outputs(str(tmp_path / "a"), {"u0_res": torch.arange(12).view(1, 4, 3), "u0_gen": torch.full((1, 4, 2), 2051)})
+    got = np.load(tmp_path / "a" / "u0_res.npy")
+    assert got.dtype == np.float32 and got.shape == (1, 4, 3) and np.array_equal(got, np.arange(12).reshape(1, 4, 3))
+    assert np.array_equal(np.load(tmp_path / "a" / "u0_gen.npy"), np.full((1, 4, 2), 2051.0))
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 64)
+    big = {"x": torch.arange(100), "y": torch.arange(60)}
+    bench.dump_outputs(str(tmp_path / "b"), big)
+    bench.dump_outputs(str(tmp_path / "c"), big)
+    x, y = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert x.nbytes + y.nbytes <= 64 and len(set(x.tolist())) == x.size and set(y.tolist()) <= set(range(60))
+    assert np.array_equal(x, np.load(tmp_path / "c" / "x.npy")) and np.array_equal(y, np.load(tmp_path / "c" / "y.npy"))

@@ -83,3 +83,33 @@ def test_plain_entry_refuses_more_gpus_than_the_box_has():
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
 def test_two_gpu_bench_gathers_what_one_engine_generates(tmp_path):
     _check_against_one_engine(_two_rank_bench(tmp_path, "nccl", share=False))
+
+
+def test_plain_bench_line_is_lean_and_dumps_what_the_last_step_returned(tmp_path):
+    """`python bench.py --gpus 1` without --full: the headline fields and nothing measured besides; --dump-outputs holds what the last
+    timed call returned (seed 1000 + steps - 1), equal to what one engine returns for the same call."""
+    import json
+    out = tmp_path / "outs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--preset", "tiny128",
+                        "--lx", "8", "--prompt-frames", "20", "--batch", "2", "--dump-outputs", str(out)],
+                       cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    assert j["metric"] == "codec_tokens_per_sec" and j["unit"] == "codec-tokens/s" and j["higher_is_better"] is True and j["dtype"] == "bf16"
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0
+    assert not {"roofline", "kernels", "prefill_roofline", "ab", "configs", "ragged", "codec", "cpu_baseline", "box"} & set(j), sorted(j)
+    assert sorted(os.listdir(out)) == ["u0_gen.npy", "u0_res.npy", "u1_gen.npy", "u1_res.npy"]
+    from voicecraft_amd import synth
+    from voicecraft_amd.engine import VoiceCraftEngine
+    a = synth.make_args("tiny128")
+    sd = synth.make_state_dict(a, seed=0, perturb=False, mute_eos=True, fast=True)
+    eng = VoiceCraftEngine(a, sd, device="cuda:0", dtype="bf16", max_seqs=2, max_positions=1024)
+    prompts = [synth.random_prompt(a, 8, 20, seed=1 + u) for u in range(2)]
+    outs = eng.inference_tts_multi([p[0][0] for p in prompts], [p[2][0] for p in prompts], top_k=40, top_p=1.0, temperature=1.0,
+                                   stop_repetition=3, silence_tokens=[1388, 1898, 131], _seed=1002)
+    for u in range(2):
+        for n, t in zip(("res", "gen"), outs[u]):
+            got = np.load(out / f"u{u}_{n}.npy")
+            assert got.dtype == np.float32 and np.array_equal(got, t.cpu().numpy().astype(np.float32)), (u, n)

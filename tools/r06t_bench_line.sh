@@ -1,7 +1,7 @@
 set -u
 export TMPDIR=/tmp
 O=gpurun_out
-( time python bench.py 2>/dev/null | tail -1 > $O/r06t_bench.json.log ) 2>&1 | grep real
+( time python bench.py --full 2>/dev/null | tail -1 > $O/r06t_bench.json.log ) 2>&1 | grep real
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r06t_bench.json.log").read())

@@ -10,7 +10,7 @@ export TAG
 echo "== probe"; timeout 200 python tools/box_probe.py 2>&1 | grep -v amdgpu.ids | tee $O/${TAG}_box_probe.log
 echo "== whole GPU suite"; timeout 700 python -m pytest tests -m gpu -q 2>&1 | tail -25 | tee $O/${TAG}_pytest_gpu.log
 echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | grep -v amdgpu.ids | tail -3 | tee $O/${TAG}_smoke.log
-echo "== default bench line"; timeout 900 python bench.py 2>/dev/null | tail -1 > $O/${TAG}_bench.json.log; python - <<'PY'
+echo "== default bench line"; timeout 900 python bench.py --full 2>/dev/null | tail -1 > $O/${TAG}_bench.json.log; python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/" + __import__("os").environ.get("TAG", "chk") + "_bench.json.log").read())
 print({k:d[k] for k in ("value","ms_per_step","decode_ms_per_token_step","prefill_ms")}, d["roofline"]["frac"], d["roofline"]["kernel"][:60], d["roofline"]["in_situ"], d["decode_step"])

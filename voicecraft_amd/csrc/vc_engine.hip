@@ -83,7 +83,8 @@ struct vc_engine {
   int gen_cap = 0;
   // pinned host staging
   SeqState *h_st = nullptr, *h_st2 = nullptr;
-  int *h_flag = nullptr;                // [0] error/poll word, [1] staging, [8] "sequences still active" written by the device
+  int *h_flag = nullptr;                // [0] error/poll word, [1] staging, [8] "sequences still active" written by the device,
+                                        // [9..10] SampleArgs.host_live, [11] the decode loop's live steps (step_ctr, after a re-packed call)
   SampleDyn *h_dyn = nullptr, *d_dyn = nullptr;   // per-call sampler values (vc_common.h)
   // captured decode steps, kept across calls: key = (sequences, rows per sequence, best-of-N)
   // ... and by the option state they were captured under (vc_set_option): toggling an option back and forth reuses the captures
@@ -91,6 +92,7 @@ struct vc_engine {
   std::string opt_state;                // canonical text of every option that shapes a decode step
   int steps_per_graph = 8;              // VC_GRAPH_STEPS: decode steps captured into one graph launch
   hipEvent_t ev_pace[2]{};
+  std::vector<int> repack_at;           // decode_loop: the batch index before which each re-pack of the last call was queued
 
   hipStream_t own_stream = nullptr;     // used when the caller passes the null stream (not capturable)
   // Non-temporal weight loads of the decode kernels, per matrix: bit 0 QKV, 1 out-projection, 2 FFN-up, 3 FFN-down, 4 heads-1, 5 heads-2.
@@ -954,6 +956,7 @@ int decode_loop(vc_engine* e, const SampleArgs& sa0, int B0, int rps, bool group
   }
   const double t1 = now_ms();
   HIPCHK(e, hipMemsetAsync(e->step_ctr, 0, sizeof(int), s));      // the loop's first step is step 0 of batch 0 (SampleArgs.host_live slots)
+  e->repack_at.clear();
   volatile int* live = e->h_flag + 8;
   volatile int* live_n = e->h_flag + 9;                   // two slots: sequences still live as the LAST step of a batch of G steps found them
   int launched = 0, rc = VC_OK, batch = 0;
@@ -975,7 +978,7 @@ int decode_loop(vc_engine* e, const SampleArgs& sa0, int B0, int rps, bool group
           hipError_t re = vc_launch_repack(ra, s);
           if (re != hipSuccess) { rc = fail(e, VC_EHIP, "re-pack launch: %s", hipGetErrorString(re)); break; }
           B = w; sa = make_sample_args(e, w, rps);
-          e->host_ms[6] += 1;                             // re-packs of this call
+          e->repack_at.push_back(batch);                  // counted in host_ms[6] once the call knows its live steps (tts_run)
         }
       }
     }
@@ -1538,6 +1541,7 @@ int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const 
   rc = decode_loop(e, sa, B, 1, grouped, sc, max_steps, &steps_run, s);
   if (rc) return rc;
   HIPCHK(e, hipEventRecord(e->ev[2], s));
+  if (!e->repack_at.empty()) HIPCHK(e, hipMemcpyAsync(e->h_flag + 11, e->step_ctr, sizeof(int), hipMemcpyDeviceToHost, s));
   if (e->cur_rows == B) {
     HIPCHK(e, hipMemcpyAsync(e->h_st, e->st, sizeof(SeqState) * B, hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
@@ -1553,6 +1557,11 @@ int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const 
     rc = check_err_flag(e, s);
     if (rc) return rc;
   }
+  // re-packs of this call: those that moved live sequences, i.e. the one queued before batch k counts when the loop's live steps
+  // (step_ctr stops at the last one) reach into batch k.  Whether the host queues one more after the last sequence has retired
+  // depends on how far it trails the device, so that one is not counted and the figure is the same in every run
+  for (int k : e->repack_at)
+    if (e->h_flag[11] > k * std::max(1, e->steps_per_graph)) e->host_ms[6] += 1;
   HIPCHK(e, hipEventElapsedTime(&e->ms[0], e->ev[0], e->ev[1]));
   HIPCHK(e, hipEventElapsedTime(&e->ms[1], e->ev[1], e->ev[2]));
   e->ms[2] = e->ms[0] + e->ms[1];
