@@ -103,18 +103,14 @@ struct vc_engine {
   // (in-process A/Bs, profiles/r04d_bench_*attn_nt*: one row +0.3 % +- 0.09 - there the launch is latency-bound and carries the prefetch
   // role -, 8 rows -4.8 % +- 0.05, 32 rows -6.5 % +- 0.05: several caches stream 58-230 MB per layer through L2 otherwise)
   int attn_nt = 2;
-  static constexpr int ln_split_rows = 3;      // slab-form passes with at least this many rows run LayerNorm as its own launch (was an option through round 5)
-  // finished-row form of decode passes of 2..fr_rows rows (forward_rows_fr): 0 = off.  VC_FINISHED_ROWS / option "finished_rows"
+  // finished-row form of passes of 2..fr_rows rows (plan_pass): 0 = off.  VC_FINISHED_ROWS / option "finished_rows"
   int fr_rows = VC_ROWS;
-  // (weight tiles per workgroup of the finished-row consumers (QKV, FFN-up): two from 5 rows up - in-process A/Bs of round 4,
-  // profiles/r04b_bench_batch*.json.log: 8 rows -3.4 % +- 0.1 with two, 4 rows +0.5 % +- 0.05 - lnw_two(); an option through round 5)
   // option "tile_attn": prefill attention kernel - 1 = tile_attn_k (16 query rows per wave, keys split over the waves), 2 =
   // tile_attn64_k (64 query rows per workgroup, transposed score product, P in registers; bf16 / head_dim 128 only, prompts are then
   // laid out on 64-row boundaries)
   // Default 2 when the call's longest prompt has at least 768 rows ("tile_attn" = "k[,min_rows]"): measured on one layer of giga830M (profiles/r04o_attn64_probe.log)
   // 512 / 800 / 2048 causal rows: 14.3 / 24.6 / 86.7 us (first kernel) against 15.5 / 21.0 / 52.5 us (second).
   int tile_attn = 2, tile_attn_min_rows = 768;
-  static constexpr int fr_split_rows = VC_FR_MAX_ROWS;   // finished-row passes of more rows run the attention unsplit (it normalises itself, plain out-projection prologue; unsplit from 5 rows measured +1.7..+4.5 %, r04j)
   // option "fr_one" (round 5): ONE-row steps - the FFN down-projection finishes its row (row_gemm_fr1_k: 8-channel tiles over the whole K,
   // two k-tiles per MFMA fragment, residual + bias added) instead of leaving 4 split-K slabs, so the next layer's QKV projection (and
   // heads-1) reads one 8 KB row instead of h + bias + 4 slabs = 40 KB in each of its 512 workgroups; 0 = off
@@ -145,8 +141,9 @@ struct vc_engine {
   // narrower step (the next power of two >= the live count: 64 -> 32 -> 16 -> 8 -> 4 -> 2 -> 1) instead of keeping its launch form until
   // the longest sequence ends; 0 = the fixed width of rounds 1-5.  Results do not depend on it: everything per sequence is indexed by its slot.
   int shrink = 1;
+  // weight images vc_finalize_weights packed: Layer.Wo8 / W28, Layer.Wqkv8, Layer.Wqkv16 (the forms that read one, plan_pass)
+  bool has_fr8 = false, has_qkv8 = false, has_qkv16 = false;
   int cur_rows = 0;                     // rows per step the last decode loop ended on (tts_run reads the states back accordingly)
-  int h_parts = 0;                      // split-K slabs the last pass left pending on hB (what the heads' LayerNorm has to sum)
   // option "attn_fast": decode attention with the wave's maximum taken before any exponential (no online rescaling inside a wave) and,
   // in bf16 mode, hardware exp2 (v_exp_f32) instead of expf
   int attn_fast = 1;
@@ -157,8 +154,6 @@ struct vc_engine {
   void *hqA = nullptr, *hqB = nullptr;  // centred copies of hA / hB, WT [VC_ROWS][d]
   float* row_mu[2] = {nullptr, nullptr};       // [VC_ROWS] each: ping-pong of the rows' means
   float* mu_zero = nullptr;             // [VC_ROWS] zeros: GemmArgs.row_mu of every launch that centres nothing
-  int mu_cur = 0;                       // which row_mu buffer holds the means of the rows in hB (run_heads16 reads it behind forward_rows_fr)
-  bool hq_h = false;                    // hqB holds the centred copy of the finished rows in hB
   // option "att_p16" (round 6; bf16 mode): finished-row passes of 2..8 rows hand the attention's split partials to the out-projection as
   // bf16 (131 -> 66 KB per out-projection workgroup at 8 rows; the merged row is rounded to bf16 for the MFMA anyway)
   int att_p16 = 1;
@@ -168,7 +163,6 @@ struct vc_engine {
   float ms[3]{0, 0, 0};
   double host_ms[8]{};                  // host wall clock of the last call's phases (vc_debug_read "host_ms")
   double bytes_total = 0;               // HBM bytes owned by the engine
-  bool finished_rows_h = false;         // run_heads16: hB holds the finished residual (no slabs, no pending bias)
   // training objective (vc_eval_forward), allocated on first use
   int *ce_tgt = nullptr, *ce_hit = nullptr;
   float *ce_nll = nullptr;
@@ -296,32 +290,15 @@ int keep_vec(vc_engine* e, const std::string& key, int n, float** out) {
   return VC_OK;
 }
 
-// ---------------------------------------------------------------- one forward pass over <= 16 rows
+// ---------------------------------------------------------------- one forward pass
 struct RowSrc {
   const float* h_in;
   const int* row_seq;
   const int* row_pos;
   int n_rows;       // rows carried
-  int nsplit;
   const int* n_active;
   int nt;           // force the streaming-load policy (microbenchmarks)
-  int tiled;        // 1: every 16-row tile holds consecutive positions of ONE sequence (prefill_batch): MFMA attention
 };
-
-// The consumers of 2..16 finished rows fold the producers' centred copy of the rows (PRO_LNQ) when a row of it is whole 1 KB requests of a
-// wave (64 lanes x 16 bytes: d a multiple of 512 in bf16, of 256 in fp32); other widths keep the fp32 rows (PRO_LNW).
-bool hq_on(const vc_engine* e) {
-  const int bytes = e->d * (e->dtype == VC_DTYPE_BF16 ? 2 : 4);
-  return e->hq != 0 && bytes % 1024 == 0 && bytes <= 8192;
-}
-
-// Option "qkv_p8" = 2: behind a centred copy, the QKV projection of 2..8 finished rows runs on the 8-channel image with two k-tiles per
-// fragment (rows_gemm_qp_k: every lane of every weight request a weight) instead of the 12-channel tiles of rows_gemm_k.
-// Measured (profiles/r06i_ab_qp.log, per step): giga830M 2 / 4 / 6 / 8 rows -2.0 / -1.1 / -0.3 / +0.5 %, giga330M 8 rows -1.3 %: at d >= 2048 the form
-// stops at 6 rows (the 8-row launch itself: 7.42 us against 7.33 us of the 12-channel tiles).
-bool qp_on(const vc_engine* e, const Layer& ly, int rows) {
-  return e->qkv_p8 >= 2 && hq_on(e) && ly.Wqkv8 != nullptr && rows <= (e->d >= 2048 ? 6 : 8) && vc_gemm_qp_ok(rows, 3 * e->d, e->d, e->dtype) != 0;
-}
 
 GemmArgs base_args(vc_engine* e, const RowSrc& rs, const Plan& p, int N, int Kdim) {
   GemmArgs g;
@@ -341,20 +318,11 @@ GemmArgs base_args(vc_engine* e, const RowSrc& rs, const Plan& p, int N, int Kdi
   return g;
 }
 
-// ONE-row steps whose FFN down-projection finishes the row (option "fr_one" bit 0): the launcher's own statement of what it takes
-// fr_one != 0: wherever the kernel can run.  (The first build - FFN-down alone - gained 2.1 % at giga830M and LOST 1.5 % at giga330M,
-// whose d / 8 = 128 workgroups fill half the chip; together with the paired QKV projection it takes along the form gains there
-// too: -0.5 % +- 0.1 / -0.9 % +- 0.09 on two boxes, profiles/r05e_ab_330M.log, r05f_ab_330M.log.)
-inline bool fd_one(const vc_engine* e, int rows) {
-  if (rows != 1 || e->fr_one == 0) return false;
-  return !e->layers.empty() && e->layers[0].W28 != nullptr && vc_gemm_fr1_ok(e->d, 4 * e->d, e->dtype, VC_FR_WAVES) != 0;
-}
-
 inline int attn_nt_for(const vc_engine* e, int rows) { return e->attn_nt == 1 || (e->attn_nt == 2 && rows >= 2); }
 enum { NT_QKV = 1, NT_O = 2, NT_F1 = 4, NT_F2 = 8, NT_H1 = 16, NT_H2 = 32 };
 inline void nt_bit(const vc_engine* e, GemmArgs& g, int bit) { if (!(e->nt_decode & bit)) g.nt = 0; }
 
-int attn_nsplit(vc_engine* e, int rows) {
+int attn_nsplit(const vc_engine* e, int rows) {
   // 8-wave blocks: one decode row is covered by ~256 of them; several rows get ~512 (two per CU), which
   // halves the positions each block walks while the merge in the out-projection stays <= 4 partials
   int ns = (rows > 1 ? e->attn_blocks_multi : e->attn_blocks_one) / std::max(1, rows * e->H);   // (fewer splits = a cheaper merge in the out-projection)
@@ -370,304 +338,6 @@ int fr_max_rows(const vc_engine* e) {
   while (r >= 2 && vc_gemm_fr_form(r, e->d, 4 * e->d, e->dtype, PRO_PLAIN, 1) == 0) --r;
   return r >= 2 ? r : 0;
 }
-bool lnw_two(const vc_engine*, int rows) { return rows >= 5; }
-// splits of the decode attention in the finished-row form: the out-projection merges rows x splits <= 16 partials per thread in
-// one batch of loads; from 9 rows up the attention is unsplit (rows x heads >= 144 workgroups) and normalises itself
-int fr_nsplit(vc_engine* e, int rows) {
-  if (rows > std::min(e->fr_split_rows, VC_FR_MAX_ROWS)) return 1;
-  int ns = std::min(attn_nsplit(e, rows), 16 / rows);
-  int p = 1;
-  while (p * 2 <= ns) p *= 2;
-  return std::max(2, p);
-}
-
-// The same pass in the finished-row form (2..fr_max_rows rows): five launches per layer, no split-K slabs, no LayerNorm
-// launch.  The residual stream is a whole row at every launch boundary: QKV and FFN-up fold the LayerNorm of finished rows
-// (PRO_LNW, one wave per row), the out-projection and the FFN down-projection own 8 output channels over the whole K and
-// add residual + bias in their epilogue (rows_gemm_fr_k).  Leaves the finished rows in hB.
-int forward_rows_fr(vc_engine* e, const RowSrc& rs, hipStream_t s) {
-  const int d = e->d;
-  // option "hq": the producers leave a centred copy of their rows in the compute dtype and the consumers fold THAT (PRO_LNQ).  `cur` names
-  // the row_mu buffer with the latest means: a consumer reads its producer's constant there and leaves the row's new mean in the other one.
-  const bool hq = hq_on(e);
-  int cur = 0;
-  for (int l = 0; l < e->L; ++l) {
-    Layer& ly = e->layers[l];
-    const float* h_res = (l == 0) ? rs.h_in : e->hB;      // residual entering the layer
-    {  // q,k,v = Wqkv LN1(h) + b ; K/V go straight into the cache
-      GemmArgs g = base_args(e, rs, e->p_qkv, 3 * d, d);
-      g.Wp = ly.Wqkv; nt_bit(e, g, NT_QKV); g.bias = ly.bqkv; g.wg = ly.wg_qkv;
-      g.h_in = h_res;
-      g.q_out = e->q; g.kcache = ly.kc; g.vcache = ly.vc;
-      g.mt = rs.n_rows > VC_FR_MAX_ROWS ? 4 : lnw_two(e, rs.n_rows) ? 3 : 0;
-      if (hq) g.row_mu_out = e->row_mu[cur ^ 1];
-      if (hq && l > 0) {       // the previous layer's FFN down-projection left hqB = WT(hB - row_mu[cur])
-        g.x_in = e->hqB; g.x_ld = d; g.row_mu = e->row_mu[cur];
-        if (qp_on(e, ly, rs.n_rows)) { g.Wp = ly.Wqkv8; HIPCHK(e, vc_launch_gemm_qp(g, e->dtype, s)); }
-        else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNQ, EPI_QKV, 1, 1, s));
-      } else {
-        HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNW, EPI_QKV, 1, 1, s));
-      }
-      cur ^= 1;
-    }
-    {
-      AttnArgs a;
-      memset(&a, 0, sizeof a);
-      a.q = e->q; a.kcache = ly.kc; a.vcache = ly.vc;
-      a.cache_seq_stride = (long)e->H * e->S_max * e->hd;
-      a.S_max = e->S_max; a.H = e->H; a.hd = e->hd; a.hd_shift = e->hd == 32 ? 5 : e->hd == 64 ? 6 : 7; a.d = d; a.nsplit = rs.nsplit;
-      a.scale = 1.0f / sqrtf((float)e->hd);
-      a.row_seq = rs.row_seq; a.row_pos = rs.row_pos; a.n_rows = rs.n_rows;
-      a.n_active = rs.n_active ? rs.n_active : e->one; a.dbg_ts = e->dbg_ts;
-      a.att_o = e->att_o; a.att_ml = e->att_ml; a.share_len = e->share_len;
-      a.nt = (rs.n_active != nullptr || rs.nt) ? attn_nt_for(e, rs.n_rows) : 0;
-      a.fast = e->attn_fast;
-      a.part16 = (e->att_p16 && e->dtype == VC_DTYPE_BF16 && rs.nsplit > 1) ? 1 : 0;
-      if (rs.nsplit == 1) a.x_out = e->xn;        // unsplit (9..16 rows): the workgroup saw every position and normalises itself
-      HIPCHK(e, vc_launch_attn(a, e->dtype, rs.n_rows, s));
-    }
-    {  // h' = h + bo + Wo merge(attention partials of all heads)
-      GemmArgs g = base_args(e, rs, e->p_o, d, d);
-      g.Wp = ly.Wo8; g.bias = ly.bo;
-      g.h_in = h_res; g.h_out = e->hA;
-      if (hq) { g.hq_out = e->hqA; g.row_mu = e->row_mu[cur]; }      // centred on the mean the QKV consumer found for h
-      if (rs.nsplit == 1) {
-        g.x_in = e->xn; g.x_ld = d;
-        HIPCHK(e, vc_launch_gemm_fr(g, e->dtype, PRO_PLAIN, s));
-      } else {
-        g.att_o = e->att_o; g.att_ml = e->att_ml; g.nsplit = rs.nsplit;
-        g.att_p16 = (e->att_p16 && e->dtype == VC_DTYPE_BF16) ? 1 : 0;
-        HIPCHK(e, vc_launch_gemm_fr(g, e->dtype, PRO_ATT, s));
-      }
-    }
-    {  // a = relu(W1 LN2(h') + b1)
-      GemmArgs g = base_args(e, rs, e->p_f1, 4 * d, d);
-      g.Wp = ly.W1; nt_bit(e, g, NT_F1); g.bias = ly.b1; g.wg = ly.wg_1;
-      g.h_in = e->hA;
-      g.out = e->act; g.out_ld = 4 * d;
-      g.mt = rs.n_rows > VC_FR_MAX_ROWS ? 4 : lnw_two(e, rs.n_rows) ? 3 : 0;
-      if (hq) {
-        g.x_in = e->hqA; g.x_ld = d; g.row_mu = e->row_mu[cur]; g.row_mu_out = e->row_mu[cur ^ 1];
-        HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNQ, EPI_RELU, 1, 1, s));
-        cur ^= 1;
-      } else {
-        HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNW, EPI_RELU, 1, 1, s));
-      }
-    }
-    {  // h'' = h' + b2 + W2 a
-      GemmArgs g = base_args(e, rs, e->p_f2, d, 4 * d);
-      g.Wp = ly.W28; g.bias = ly.b2;
-      g.x_in = e->act; g.x_ld = 4 * d;
-      g.h_in = e->hA; g.h_out = e->hB;
-      if (hq) { g.hq_out = e->hqB; g.row_mu = e->row_mu[cur]; }      // centred on the mean the FFN-up consumer found for h'
-      if (e->fr_pair && vc_gemm_frp_ok(rs.n_rows, d, 4 * d, e->dtype)) HIPCHK(e, vc_launch_gemm_frp(g, e->dtype, s));      // 2..8 rows: two k-tiles per fragment
-      else HIPCHK(e, vc_launch_gemm_fr(g, e->dtype, PRO_PLAIN, s));
-    }
-  }
-  e->hq_h = hq;
-  e->mu_cur = cur;
-  return VC_OK;
-}
-
-// One pass of up to 16 rows through every layer (decode step, 3-row span switch, short prompts).
-int forward_rows(vc_engine* e, const RowSrc& rs, hipStream_t s) {
-  const int d = e->d;
-  e->finished_rows_h = false;
-  e->hq_h = false;
-  if (rs.n_rows >= 2 && rs.n_rows <= fr_max_rows(e)) {
-    RowSrc fr = rs;
-    fr.nsplit = fr_nsplit(e, rs.n_rows);
-    e->finished_rows_h = true;            // tells run_heads16 (the caller's next step) that hB holds finished rows
-    return forward_rows_fr(e, fr, s);
-  }
-  // The in-GEMM LayerNorm prologue walks the rows one after the other (each a dependent round trip
-  // in every one of the 384-512 workgroups): from ln_split_rows rows on, a per-row LayerNorm launch
-  // plus the plain prologue is cheaper (measured: 8 rows 20 us -> ~12 us per GEMM).
-  const bool split_ln = rs.n_rows >= e->ln_split_rows;
-  // one row, option fr_one: the FFN down-projection writes the FINISHED residual row into hB (row_gemm_fr1_k), so the row entering a
-  // layer is whole: the QKV prologue reads it alone and writes nothing, the FFN-up prologue adds the out-projection's two slabs to
-  // it and leaves h' in hA for the down-projection's epilogue
-  const bool fd = fd_one(e, rs.n_rows);
-  e->finished_rows_h = fd;
-  e->h_parts = e->p_f2.ksplit;
-  for (int l = 0; l < e->L; ++l) {
-    Layer& ly = e->layers[l];
-    const float* h_res = (l == 0) ? rs.h_in : e->hB;
-    {  // x = LN1(h); q,k,v = Wqkv x + b ; K/V go straight into the cache
-      GemmArgs g = base_args(e, rs, e->p_qkv, 3 * d, d);
-      g.Wp = ly.Wqkv; nt_bit(e, g, NT_QKV); g.bias = ly.bqkv;
-      g.h_in = h_res;
-      g.h_out = fd ? nullptr : e->hA;
-      g.parts = e->parts;
-      g.n_parts = (l == 0 || fd) ? 0 : e->p_f2.ksplit;
-      g.prev_bias = (l == 0) ? ly.bo : e->layers[l - 1].b2;    // (any readable [d] vector when unused)
-      g.has_prev_bias = (l == 0 || fd) ? 0 : 1;
-      g.wg = ly.wg_qkv;
-      g.q_out = e->q; g.kcache = ly.kc; g.vcache = ly.vc;
-      if (fd && e->qkv_p8 && ly.Wqkv8 && !split_ln) {
-        // the row entering the layer is finished (layer 0: the sampler's dec_h row): 8-channel tiles, two k-tiles per fragment
-        g.Wp = ly.Wqkv8;
-        HIPCHK(e, vc_launch_gemm_fr1(g, e->dtype, PRO_LN, EPI_QKV, s));
-      } else if (split_ln) {   // several rows: LayerNorm once per row, then the plain-prologue GEMM
-        g.x_out = e->xn;
-        HIPCHK(e, vc_launch_ln_rows(g, e->dtype, s));
-        g.x_in = e->xn; g.x_ld = d;
-        HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_QKV, 1, 1, s));
-      } else {
-        HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LN, EPI_QKV, 1, 1, s));
-      }
-    }
-    {  //                                                                 
-      AttnArgs a;
-      memset(&a, 0, sizeof a);
-      a.q = e->q; a.kcache = ly.kc; a.vcache = ly.vc;
-      a.cache_seq_stride = (long)e->H * e->S_max * e->hd;
-      a.S_max = e->S_max; a.H = e->H; a.hd = e->hd; a.hd_shift = e->hd == 32 ? 5 : e->hd == 64 ? 6 : 7; a.d = d; a.nsplit = rs.nsplit;
-      a.scale = 1.0f / sqrtf((float)e->hd);
-      a.row_seq = rs.row_seq; a.row_pos = rs.row_pos; a.n_rows = rs.n_rows;
-      a.n_active = rs.n_active ? rs.n_active : e->one; a.dbg_ts = e->dbg_ts;
-      a.att_o = e->att_o; a.att_ml = e->att_ml; a.share_len = e->share_len;
-      a.nt = (rs.n_active != nullptr || rs.nt) ? attn_nt_for(e, rs.n_rows) : 0;
-      a.fast = e->attn_fast;
-      HIPCHK(e, vc_launch_attn(a, e->dtype, rs.n_rows, s));
-    }
-    {  // out-projection of the merged attention output -> split-K partial slabs
-      GemmArgs g = base_args(e, rs, e->p_o, d, d);
-      g.Wp = ly.Wo; nt_bit(e, g, NT_O);
-      g.att_o = e->att_o; g.att_ml = e->att_ml; g.nsplit = rs.nsplit;
-      g.part_out = e->parts;
-      HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_ATT, EPI_PART, e->p_o.ksplit, 1, s));
-    }
-    {  // h' = h + attn + bo ; a = relu(W1 LN2(h') + b1)                  
-      GemmArgs g = base_args(e, rs, e->p_f1, 4 * d, d);
-      g.Wp = ly.W1; nt_bit(e, g, NT_F1); g.bias = ly.b1;
-      g.h_in = fd ? h_res : e->hA; g.h_out = fd ? e->hA : e->hB;
-      g.parts = e->parts; g.n_parts = e->p_o.ksplit; g.prev_bias = ly.bo; g.has_prev_bias = 1;
-      g.wg = ly.wg_1;
-      g.out = e->act; g.out_ld = 4 * d;
-      if (split_ln) {
-        g.x_out = e->xn;
-        HIPCHK(e, vc_launch_ln_rows(g, e->dtype, s));
-        g.x_in = e->xn; g.x_ld = d;
-        HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_RELU, 1, 1, s));
-      } else {
-        HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LN, EPI_RELU, 1, 1, s));
-      }
-    }
-    if (fd) {  // h'' = h' + b2 + W2 a: the finished row (one row, row_gemm_fr1_k)
-      GemmArgs g = base_args(e, rs, e->p_f2, d, 4 * d);
-      g.Wp = ly.W28; g.bias = ly.b2;
-      g.x_in = e->act; g.x_ld = 4 * d;
-      g.h_in = e->hA; g.h_out = e->hB;
-      HIPCHK(e, vc_launch_gemm_fr1(g, e->dtype, PRO_PLAIN, EPI_RES, s));
-    } else {  // W2 a -> partial slabs, folded into the next LayerNorm prologue together with b2
-      GemmArgs g = base_args(e, rs, e->p_f2, d, 4 * d);
-      g.Wp = ly.W2; nt_bit(e, g, NT_F2);
-      g.x_in = e->act; g.x_ld = 4 * d;
-      g.part_out = e->parts;
-      HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_PART, e->p_f2.ksplit, 1, s));
-    }
-  }
-  return VC_OK;
-}
-
-// final LayerNorm + the K prediction heads (voicecraft.py:181-185, :1084-1086) for n rows;
-// row r reads hidden row gather[r] (or in_row0 + r) and writes logits row (out_row0 + r).
-int run_heads16(vc_engine* e, const int* gather, int n, int in_row0, int out_row0, const int* n_active, hipStream_t s) {
-  if (gather && n > 1) return fail(e, VC_EINVAL, "internal: a gathered head pass carries one row");
-  RowSrc rs{};
-  rs.n_rows = n; rs.n_active = n_active;
-  {  //                                                                   
-    GemmArgs g = base_args(e, rs, e->p_h1, e->K * e->P, e->d);
-    g.Wp = e->Wh1; nt_bit(e, g, NT_H1); g.bias = e->bh1;
-    g.h_in = e->hB + (size_t)in_row0 * e->d; g.h_out = nullptr;
-    g.parts = e->parts + (size_t)in_row0 * e->d; g.n_parts = e->h_parts; g.prev_bias = e->layers[e->L - 1].b2; g.has_prev_bias = 1;
-    if (e->finished_rows_h) { g.n_parts = 0; g.has_prev_bias = 0; }       // the finished-row form left the whole residual in hB
-    g.wg = e->wg_h1; g.gather_rows = gather;
-    g.out = (char*)e->hh + (size_t)out_row0 * e->K * e->P * e->esz; g.out_ld = e->K * e->P;
-    if (e->finished_rows_h && !gather && n >= 2 && n <= VC_FR_MAX_ROWS) {     // finished rows: LayerNorm fold per wave, no extra launch
-      if (e->hq_h && in_row0 == 0) {      // ... on the last FFN down-projection's centred copy
-        g.x_in = e->hqB; g.x_ld = e->d; g.row_mu = e->row_mu[e->mu_cur];
-        HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNQ, EPI_GELU, 1, 1, s));
-      } else {
-        HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNW, EPI_GELU, 1, 1, s));
-      }
-    } else if (!gather && n >= e->ln_split_rows) {
-      g.x_out = e->xn;
-      HIPCHK(e, vc_launch_ln_rows(g, e->dtype, s));
-      g.x_in = e->xn; g.x_ld = e->d;
-      HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_GELU, 1, 1, s));
-    } else {
-      HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LN, EPI_GELU, 1, 1, s));
-    }
-  }
-  {  //                                                                          
-    GemmArgs g = base_args(e, rs, e->p_h2, e->V, e->P);
-    g.Wp = e->Wh2; nt_bit(e, g, NT_H2); g.bias = e->bh2;
-    g.w_group_stride = e->wh2_group_stride; g.bias_group_stride = e->V;
-    g.x_in = (char*)e->hh + (size_t)out_row0 * e->K * e->P * e->esz; g.x_ld = e->K * e->P; g.x_group_stride = e->P;
-    g.out = e->logits + (size_t)out_row0 * e->K * e->V;
-    HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_LOGITS, 1, e->K, s));
-  }
-  return VC_OK;
-}
-// 17..64 rows (wide decode steps): the final LayerNorm once per row (ln_rows_k), then both head matrices on the weight-stationary
-// kernel of those steps (rows_gemm_mt_k: every weight read ONCE per step) instead of once per 16 rows - at 64 rows the 16-row passes
-// streamed the 33.6 MB of head weights four times (option "wide_heads").
-bool use_wd(const vc_engine* e, int rows);
-int run_heads_wide(vc_engine* e, int n, const int* n_active, hipStream_t s) {
-  RowSrc rs{};
-  rs.n_rows = n; rs.n_active = n_active;
-  const bool wd = use_wd(e, n);
-  {
-    GemmArgs g = base_args(e, rs, e->p_h1, e->K * e->P, e->d);
-    g.Wp = e->Wh1; nt_bit(e, g, NT_H1); g.bias = e->bh1;
-    g.h_in = e->hB; g.h_out = nullptr;
-    g.parts = e->parts; g.n_parts = e->h_parts; g.prev_bias = e->layers[e->L - 1].b2; g.has_prev_bias = 1;
-    g.wg = e->wg_h1;
-    g.out = e->hh; g.out_ld = e->K * e->P;
-    g.x_out = e->xn;
-    HIPCHK(e, vc_launch_ln_rows(g, e->dtype, s));
-    g.x_in = e->xn; g.x_ld = e->d; g.mt = 2;
-    if (wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_GELU, 1, 1, s));
-    else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_GELU, 1, 1, s));
-  }
-  {
-    GemmArgs g = base_args(e, rs, e->p_h2, e->V, e->P);
-    g.Wp = e->Wh2; nt_bit(e, g, NT_H2); g.bias = e->bh2;
-    g.w_group_stride = e->wh2_group_stride; g.bias_group_stride = e->V;
-    g.x_in = e->hh; g.x_ld = e->K * e->P; g.x_group_stride = e->P;
-    g.out = e->logits; g.mt = 2;
-    if (wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_LOGITS, 1, e->K, s));
-    else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_LOGITS, 1, e->K, s));
-  }
-  return VC_OK;
-}
-int run_heads(vc_engine* e, const int* gather, int n, int out_row0, const int* n_active, hipStream_t s) {
-  if (e->wide_heads && !gather && out_row0 == 0 && n > VC_ROWS && n <= VC_MAX_SEQS && n_active != nullptr && !e->finished_rows_h)
-    return run_heads_wide(e, n, n_active, s);
-  for (int r0 = 0; r0 < n; r0 += VC_ROWS) {       // wide batches: the heads run 16 rows at a time
-    int rc = run_heads16(e, gather, std::min(VC_ROWS, n - r0), r0, out_row0 + r0, n_active, s);
-    if (rc) return rc;
-  }
-  return VC_OK;
-}
-
-// Prefill pass over up to VC_MAX_ROWS prompt rows: LayerNorm once per row (ln_rows_k), then the
-// multi-tile rows-GEMM (weights streamed once per pass).  Same buffers and slabs as the decode pass.
-// Which image of the QKV matrix a many-row pass reads (option "qkv16").  The 16-channel image has 3/4 of the 12-channel image's tiles,
-// and the block GEMM picks its workgroup tile from the tile count (vc_gemm_pf.hip launch_blk_e: 128-channel tiles from 240 workgroups):
-// where the smaller count would push a pass back to the 64-channel form the 12-channel image stays (giga830M, 385..512 rows: 24.0 us
-// against 34.0, profiles/r05j_qkv16_probe.log); everywhere else the full fragments win or tie (240 rows -6.7 %, 800 rows -1.7 %,
-// 1 280 rows -26.7 % - there the pass also leaves the 256 x 256 kernel, whose 160 workgroups fill 5/8 of the chip -, 32-row decode
-// steps -1.8 % per step).
-bool use_qkv16(const vc_engine* e, int rows, int mtv) {
-  if (!e->qkv16 || e->layers.empty() || !e->layers[0].Wqkv16) return false;
-  if (mtv == 2) return true;                          // wide decode passes: a weight stream, fewer instructions per byte
-  const long blk = (rows + 127) / 128;
-  const long w12 = (long)(e->p_qkv.n_tiles / 8) * blk, w16 = (long)(e->p_qkv16.n_tiles / 8) * blk;
-  return !(w12 >= 240 && w16 < 240);
-}
 
 // K slices of a split-K producer on the wide-decode kernel (rows_gemm_wd_k: two 16-channel tiles per workgroup, the slice split over
 // 8 waves): the fewest slices that put a workgroup on every CU, among those the kernel has a form for; 0 = none.
@@ -681,86 +351,360 @@ int wd_ksplit(const vc_engine* e, int N, int Kdim) {
   }
   return best;
 }
-// Does a pass of `rows` rows run its linear layers on rows_gemm_wd_k?  (Every matrix of the layer must have a form - the QKV projection
-// needs the 16-channel image.)
-bool use_wd(const vc_engine* e, int rows) {
-  if (!e->wide_gemm || rows <= VC_ROWS || rows > VC_MAX_SEQS || e->layers.empty() || !e->layers[0].Wqkv16 || !e->qkv16) return false;
-  const int d = e->d;
-  return vc_gemm_wd_kpw(d, e->dtype, 1) && wd_ksplit(e, d, d) && wd_ksplit(e, d, 4 * d) && vc_gemm_wd_kpw(e->P, e->dtype, 1);
-}
 
-int prefill_rows(vc_engine* e, const RowSrc& rs, hipStream_t s) {
+// The forms of a pass.  Slab: 1 row, and 3..16 rows where the finished-row form cannot run - the producers leave split-K slabs that
+// the next LayerNorm sums.  Finished rows (2..fr_max_rows rows): five launches per layer, no slabs, no LayerNorm launch - QKV and
+// FFN-up fold the LayerNorm of whole rows (PRO_LNW / PRO_LNQ), the out-projection and FFN-down own 8 output channels over the whole K
+// and add residual + bias (rows_gemm_fr_k).  Wide: decode steps of 17..64 rows, weight streams on rows_gemm_wd_k / rows_gemm_mt_k.
+// Block: prefill passes of more rows, the MFMA block GEMM.  Wide and block passes normalise every row in ln_rows_k.
+enum { FORM_SLAB = 0, FORM_FR = 1, FORM_WIDE = 2, FORM_BLOCK = 3 };   // (values: vc_debug_plan out[1])
+enum { ATT_ROWS = 0, ATT_TILE = 1, ATT_TILE64 = 2 };                 // rows_attn_k, tile_attn_k, tile_attn64_k
+// The in-GEMM LayerNorm prologue walks the rows one after the other (each a dependent round trip in every one of the 384-512
+// workgroups): from this many rows on, a per-row LayerNorm launch plus the plain prologue is cheaper (8 rows 20 us -> ~12 us per GEMM).
+constexpr int ln_split_rows = 3;
+
+// Every launch decision of a pass of `rows` rows: plan_pass below is the one place they are made.
+struct PassPlan {
+  int form;         // FORM_*
+  int attn;         // ATT_*
+  int nsplit;       // attention splits
+  bool att_x;       // the attention is unsplit and normalises its rows into xn; the out-projection takes them with the plain prologue
+  bool part16;      // the split partials in bf16 (option att_p16)
+  bool ln_launch;   // QKV / FFN-up: LayerNorm as its own per-row launch (ln_rows_k) + the plain prologue, else in the GEMM prologue
+  bool hq;          // finished rows: the consumers fold the producers' centred copy (PRO_LNQ) instead of the fp32 rows (PRO_LNW)
+  int mt;           // GemmArgs.mt of the consumers: 0 / 3 / 4 finished rows, 2 wide, 1 block
+  bool fd;          // one row: the FFN down-projection finishes its row (row_gemm_fr1_k, option fr_one)
+  bool qkv_fr1;     // ... and the QKV projection behind it pairs k-tiles on the 8-channel image (option qkv_p8)
+  bool qp;          // 2..8 finished rows: the QKV projection of layers 1.. on rows_gemm_qp_k (qkv_p8 = 2)
+  bool frp;         // finished rows: the FFN down-projection on rows_gemm_frp_k (option fr_pair)
+  bool qkv16;       // wide and block: the QKV projection on the 16-channel image (option qkv16)
+  bool wd;          // wide: the linear layers on rows_gemm_wd_k (option wide_gemm)
+  int ks_o, ks_f2;  // split-K slabs the out-projection / FFN down-projection leave (slab, wide and block forms)
+  bool heads_wide;  // the heads run once over all rows on the wide-step kernels (option wide_heads)
+  bool heads_fold;  // heads-1 folds the finished rows itself (no LayerNorm launch)
+};
+
+// decode: a decode step (n_active set).  tiled: a prefill pass whose 16-row tiles (1) or 64-row blocks (2) each hold consecutive
+// positions of ONE sequence (prefill_batch): MFMA attention; 0 for passes of up to VC_ROWS rows.
+PassPlan plan_pass(const vc_engine* e, int rows, bool decode, int tiled) {
+  PassPlan p{};
   const int d = e->d;
-  e->finished_rows_h = false;           // this pass leaves h + split-K slabs
-  e->hq_h = false;
-  // prefill passes run on the block GEMM (mt = 1); decode passes of 17..64 rows (n_active set) are still weight
-  // streams: they take the weight-stationary multi-tile kernel (mt = 2), which reads every weight once at the decode rate
-  const int mtv = (rs.n_active != nullptr && rs.n_rows <= VC_MAX_SEQS && !getenv("VC_WIDE_BLK")) ? 2 : 1;
-  const bool wd = mtv == 2 && use_wd(e, rs.n_rows);                 // wide decode step on rows_gemm_wd_k
-  const int ks_o = wd ? wd_ksplit(e, d, d) : e->p_o.ksplit, ks_f2 = wd ? wd_ksplit(e, d, 4 * d) : e->p_f2.ksplit;
-  e->h_parts = ks_f2;
-  for (int l = 0; l < e->L; ++l) {
-    Layer& ly = e->layers[l];
-    {
-      GemmArgs g = base_args(e, rs, e->p_qkv, 3 * d, d);
-      g.h_in = (l == 0) ? rs.h_in : e->hB; g.h_out = e->hA; g.parts = e->parts;
-      g.n_parts = (l == 0) ? 0 : ks_f2;
-      g.prev_bias = (l == 0) ? ly.bo : e->layers[l - 1].b2; g.has_prev_bias = (l == 0) ? 0 : 1;
-      g.x_out = e->xn;
-      HIPCHK(e, vc_launch_ln_rows(g, e->dtype, s));
-      g.Wp = ly.Wqkv; nt_bit(e, g, NT_QKV); g.bias = ly.bqkv; g.x_in = e->xn; g.x_ld = d; g.mt = mtv;
-      g.q_out = e->q; g.kcache = ly.kc; g.vcache = ly.vc;
-      if (use_qkv16(e, rs.n_rows, mtv)) {     // every A lane a weight: the 16-channel image
-        g.Wp = ly.Wqkv16; g.n_tiles = e->p_qkv16.n_tiles; g.KT = e->p_qkv16.KT; g.nchunk = e->p_qkv16.nchunk;
-        if (wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_QKV16, 1, 1, s));
-        else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_QKV16, 1, 1, s));
-      } else {
-        HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_QKV, 1, 1, s));
-      }
+  const bool bf16 = e->dtype == VC_DTYPE_BF16;
+  if (rows <= VC_ROWS && !tiled) p.form = rows >= 2 && rows <= fr_max_rows(e) ? FORM_FR : FORM_SLAB;
+  else p.form = decode && rows <= VC_MAX_SEQS ? FORM_WIDE : FORM_BLOCK;
+  p.attn = p.form == FORM_BLOCK && tiled ? (tiled == 2 ? ATT_TILE64 : ATT_TILE) : ATT_ROWS;
+  p.ks_o = e->p_o.ksplit; p.ks_f2 = e->p_f2.ksplit;
+  if (p.form == FORM_SLAB) {
+    p.nsplit = attn_nsplit(e, rows);
+    p.ln_launch = rows >= ln_split_rows;
+    // one row, option fr_one: the FFN down-projection writes the FINISHED residual row into hB (row_gemm_fr1_k), so the row entering a
+    // layer is whole: the QKV prologue reads it alone and writes nothing, the FFN-up prologue adds the out-projection's two slabs to it
+    // and leaves h' in hA for the down-projection's epilogue.  (The first build - FFN-down alone - gained 2.1 % at giga830M and LOST
+    // 1.5 % at giga330M, whose d / 8 = 128 workgroups fill half the chip; together with the paired QKV projection it takes along the
+    // form gains there too: -0.5 % +- 0.1 / -0.9 % +- 0.09 on two boxes, profiles/r05e_ab_330M.log, r05f_ab_330M.log.)
+    p.fd = rows == 1 && e->fr_one && e->has_fr8 && vc_gemm_fr1_ok(d, 4 * d, e->dtype, VC_FR_WAVES);
+    p.qkv_fr1 = p.fd && e->qkv_p8 && e->has_qkv8 && !p.ln_launch;
+  } else if (p.form == FORM_FR) {
+    // splits of the decode attention: the out-projection merges rows x splits <= 16 partials per thread in one batch of loads; past
+    // VC_FR_MAX_ROWS rows the attention is unsplit (rows x heads >= 144 workgroups) and normalises itself (unsplit from 5 rows measured
+    // +1.7..+4.5 %, r04j)
+    if (rows > VC_FR_MAX_ROWS) {
+      p.nsplit = 1;
+    } else {
+      const int ns = std::min(attn_nsplit(e, rows), 16 / rows);
+      p.nsplit = 1;
+      while (p.nsplit * 2 <= ns) p.nsplit *= 2;
+      p.nsplit = std::max(2, p.nsplit);
     }
-    {
-      AttnArgs a;
-      memset(&a, 0, sizeof a);
-      a.q = e->q; a.kcache = ly.kc; a.vcache = ly.vc; a.cache_seq_stride = (long)e->H * e->S_max * e->hd;
-      a.S_max = e->S_max; a.H = e->H; a.hd = e->hd; a.hd_shift = e->hd == 32 ? 5 : e->hd == 64 ? 6 : 7; a.d = d; a.nsplit = rs.nsplit; a.scale = 1.0f / sqrtf((float)e->hd);
-      a.row_seq = rs.row_seq; a.row_pos = rs.row_pos; a.n_rows = rs.n_rows; a.att_o = e->att_o; a.att_ml = e->att_ml;
-      a.n_active = rs.n_active ? rs.n_active : e->one; a.dbg_ts = e->dbg_ts; a.share_len = e->share_len;
-      a.nt = rs.n_active != nullptr ? attn_nt_for(e, rs.n_rows) : 0;      // wide decode passes stream their K/V once, prefill passes re-read it
-      a.fast = e->attn_fast;
-      if (rs.nsplit == 1) a.x_out = e->xn;    // xn is free between the QKV GEMM and the FFN LayerNorm
-      if (rs.tiled == 2 && rs.nsplit == 1) HIPCHK(e, vc_launch_tile_attn64(a, s));
-      else if (rs.tiled && rs.nsplit == 1) HIPCHK(e, vc_launch_tile_attn(a, e->dtype, s));
-      else HIPCHK(e, vc_launch_attn(a, e->dtype, rs.n_rows, s));
-    }
-    {
-      GemmArgs g = base_args(e, rs, e->p_o, d, d);
-      g.Wp = ly.Wo; nt_bit(e, g, NT_O); g.part_out = e->parts; g.mt = mtv;
-      if (rs.nsplit == 1) {
-        g.x_in = e->xn; g.x_ld = d;
-        if (wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_PART, ks_o, 1, s));
-        else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_PART, e->p_o.ksplit, 1, s));
-      } else {
-        g.att_o = e->att_o; g.att_ml = e->att_ml; g.nsplit = rs.nsplit;
-        HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_ATT, EPI_PART, e->p_o.ksplit, 1, s));
-      }
-    }
-    {
-      GemmArgs g = base_args(e, rs, e->p_f1, 4 * d, d);
-      g.h_in = e->hA; g.h_out = e->hB; g.parts = e->parts; g.n_parts = ks_o; g.prev_bias = ly.bo; g.has_prev_bias = 1;
-      g.x_out = e->xn;
-      HIPCHK(e, vc_launch_ln_rows(g, e->dtype, s));
-      g.Wp = ly.W1; nt_bit(e, g, NT_F1); g.bias = ly.b1; g.x_in = e->xn; g.x_ld = d; g.out = e->act; g.out_ld = 4 * d; g.mt = mtv;
-      if (wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_RELU, 1, 1, s));
-      else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_RELU, 1, 1, s));
-    }
-    {
-      GemmArgs g = base_args(e, rs, e->p_f2, d, 4 * d);
-      g.Wp = ly.W2; nt_bit(e, g, NT_F2); g.x_in = e->act; g.x_ld = 4 * d; g.part_out = e->parts; g.mt = mtv;
-      if (wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_PART, ks_f2, 1, s));
-      else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_PART, e->p_f2.ksplit, 1, s));
+    p.att_x = p.nsplit == 1;
+    p.part16 = e->att_p16 && bf16 && p.nsplit > 1;
+    // the centred copy when a row of it is whole 1 KB requests of a wave (64 lanes x 16 bytes: d a multiple of 512 in bf16, of 256 in
+    // fp32); other widths keep the fp32 rows
+    const int row_bytes = d * (bf16 ? 2 : 4);
+    p.hq = e->hq != 0 && row_bytes % 1024 == 0 && row_bytes <= 8192;
+    // weight tiles per consumer workgroup: two from 5 rows up (8 rows -3.4 % +- 0.1, 4 rows +0.5 % +- 0.05, profiles/r04b_bench_batch*),
+    // and two rows per wave past VC_FR_MAX_ROWS
+    p.mt = rows > VC_FR_MAX_ROWS ? 4 : rows >= 5 ? 3 : 0;
+    // the 8-channel QKV image behind a centred copy (profiles/r06i_ab_qp.log, per step: giga830M 2 / 4 / 6 / 8 rows -2.0 / -1.1 / -0.3 /
+    // +0.5 %, giga330M 8 rows -1.3 %): at d >= 2048 the form stops at 6 rows (the 8-row launch itself: 7.42 us against 7.33 us)
+    p.qp = e->qkv_p8 >= 2 && p.hq && e->has_qkv8 && rows <= (d >= 2048 ? 6 : 8) && vc_gemm_qp_ok(rows, 3 * d, d, e->dtype) != 0;
+    p.frp = e->fr_pair && vc_gemm_frp_ok(rows, d, 4 * d, e->dtype);
+  } else {
+    p.nsplit = 1;                      // attention one workgroup per (row, head), no split partials
+    p.att_x = true;
+    p.ln_launch = true;
+    p.mt = p.form == FORM_WIDE ? 2 : 1;
+    // The 16-channel QKV image has 3/4 of the 12-channel image's tiles, and the block GEMM picks its workgroup tile from the tile count
+    // (vc_gemm_pf.hip launch_blk_e: 128-channel tiles from 240 workgroups): where the smaller count would push a pass back to the
+    // 64-channel form the 12-channel image stays (giga830M, 385..512 rows: 24.0 us against 34.0, profiles/r05j_qkv16_probe.log);
+    // everywhere else the full fragments win or tie (240 rows -6.7 %, 800 rows -1.7 %, 1 280 rows -26.7 %, 32-row decode steps -1.8 %).
+    const long blk = (rows + 127) / 128;
+    const bool tiles_ok = !((long)(e->p_qkv.n_tiles / 8) * blk >= 240 && (long)(e->p_qkv16.n_tiles / 8) * blk < 240);
+    p.qkv16 = e->qkv16 && e->has_qkv16 && (p.form == FORM_WIDE || tiles_ok);
+    if (p.form == FORM_WIDE && e->wide_gemm && p.qkv16) {      // every matrix of the layer needs a form on rows_gemm_wd_k
+      const int ko = wd_ksplit(e, d, d), kf = wd_ksplit(e, d, 4 * d);
+      p.wd = vc_gemm_wd_kpw(d, e->dtype, 1) && ko && kf && vc_gemm_wd_kpw(e->P, e->dtype, 1);
+      if (p.wd) { p.ks_o = ko; p.ks_f2 = kf; }
     }
   }
+  p.heads_wide = p.form == FORM_WIDE && e->wide_heads;
+  p.heads_fold = p.form == FORM_FR && rows <= VC_FR_MAX_ROWS;
+  return p;
+}
+
+// The rows a LayerNorm reads (a launch, or a GEMM prologue): h_in + prev_bias + n_parts split-K slabs; their sum goes to h_out (may be null).
+struct Resid { const float* h_in; float* h_out; int n_parts; const float* prev_bias; };
+void set_resid(vc_engine* e, GemmArgs& g, const Resid& r) {
+  g.h_in = r.h_in; g.h_out = r.h_out; g.parts = e->parts; g.n_parts = r.n_parts;
+  g.prev_bias = r.prev_bias; g.has_prev_bias = r.n_parts > 0 ? 1 : 0;      // (prev_bias: any readable [d] vector when unused)
+}
+// In front of QKV: h = the residual entering the layer, prev = the layer before (null: layer 0, no slabs).  Behind a finished row the
+// prologue reads it alone and writes nothing.
+Resid qkv_in(vc_engine* e, const PassPlan& p, const Layer& ly, const float* h, const Layer* prev) {
+  return {h, p.fd ? nullptr : e->hA, prev && !p.fd ? p.ks_f2 : 0, prev ? prev->b2 : ly.bo};
+}
+// In front of FFN-up: h + bo + the out-projection's slabs.
+Resid ffn_in(vc_engine* e, const PassPlan& p, const Layer& ly, const float* h) {
+  return p.fd ? Resid{h, e->hA, p.ks_o, ly.bo} : Resid{e->hA, e->hB, p.ks_o, ly.bo};
+}
+
+// ---- the launch sites of a layer.  h = the residual entering the layer.
+int site_ln(vc_engine* e, const RowSrc& rs, const Resid& r, hipStream_t s) {
+  GemmArgs g = base_args(e, rs, e->p_f1, 4 * e->d, e->d);
+  set_resid(e, g, r);
+  g.x_out = e->xn;
+  HIPCHK(e, vc_launch_ln_rows(g, e->dtype, s));
   return VC_OK;
+}
+
+// The finished-row consumers' `row_mu` ping-pong: QKV reads the means in row_mu[0] and leaves the rows' new means in row_mu[1], which
+// the out-projection centres its copy on; FFN-up reads row_mu[1] and leaves row_mu[0] for the FFN down-projection and the heads.
+// q,k,v = Wqkv LN1(h) + b ; K/V go straight into the cache.  first: layer 0 (no centred copy of its input rows).
+int site_qkv(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly, const Resid& r, bool first, hipStream_t s) {
+  const int d = e->d;
+  GemmArgs g = base_args(e, rs, e->p_qkv, 3 * d, d);
+  g.Wp = ly.Wqkv; nt_bit(e, g, NT_QKV); g.bias = ly.bqkv; g.wg = ly.wg_qkv;
+  g.q_out = e->q; g.kcache = ly.kc; g.vcache = ly.vc; g.mt = p.mt;
+  if (p.form == FORM_FR) {
+    g.h_in = r.h_in;
+    if (p.hq) g.row_mu_out = e->row_mu[1];
+    if (p.hq && !first) {      // the previous layer's FFN down-projection left hqB = WT(hB - row_mu[0])
+      g.x_in = e->hqB; g.x_ld = d; g.row_mu = e->row_mu[0];
+      if (p.qp) { g.Wp = ly.Wqkv8; HIPCHK(e, vc_launch_gemm_qp(g, e->dtype, s)); }
+      else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNQ, EPI_QKV, 1, 1, s));
+    } else {
+      HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNW, EPI_QKV, 1, 1, s));
+    }
+    return VC_OK;
+  }
+  set_resid(e, g, r);
+  if (p.qkv_fr1) {         // the row entering the layer is finished (layer 0: the sampler's dec_h row): 8-channel tiles, two k-tiles per fragment
+    g.Wp = ly.Wqkv8;
+    HIPCHK(e, vc_launch_gemm_fr1(g, e->dtype, PRO_LN, EPI_QKV, s));
+  } else if (!p.ln_launch) {
+    HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LN, EPI_QKV, 1, 1, s));
+  } else if (p.qkv16) {    // every A lane a weight: the 16-channel image
+    g.x_in = e->xn; g.x_ld = d;
+    g.Wp = ly.Wqkv16; g.n_tiles = e->p_qkv16.n_tiles; g.KT = e->p_qkv16.KT; g.nchunk = e->p_qkv16.nchunk;
+    if (p.wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_QKV16, 1, 1, s));
+    else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_QKV16, 1, 1, s));
+  } else {
+    g.x_in = e->xn; g.x_ld = d;
+    HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_QKV, 1, 1, s));
+  }
+  return VC_OK;
+}
+
+int site_attn(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly, hipStream_t s) {
+  AttnArgs a;
+  memset(&a, 0, sizeof a);
+  a.q = e->q; a.kcache = ly.kc; a.vcache = ly.vc;
+  a.cache_seq_stride = (long)e->H * e->S_max * e->hd;
+  a.S_max = e->S_max; a.H = e->H; a.hd = e->hd; a.hd_shift = e->hd == 32 ? 5 : e->hd == 64 ? 6 : 7; a.d = e->d; a.nsplit = p.nsplit;
+  a.scale = 1.0f / sqrtf((float)e->hd);
+  a.row_seq = rs.row_seq; a.row_pos = rs.row_pos; a.n_rows = rs.n_rows;
+  a.n_active = rs.n_active ? rs.n_active : e->one; a.dbg_ts = e->dbg_ts;
+  a.att_o = e->att_o; a.att_ml = e->att_ml; a.share_len = e->share_len;
+  a.nt = (rs.n_active != nullptr || rs.nt) ? attn_nt_for(e, rs.n_rows) : 0;   // decode passes stream their K/V once, prefill passes re-read it
+  a.fast = e->attn_fast;
+  a.part16 = p.part16 ? 1 : 0;
+  if (p.att_x) a.x_out = e->xn;        // xn is free between the QKV GEMM and the FFN LayerNorm
+  if (p.attn == ATT_TILE64) HIPCHK(e, vc_launch_tile_attn64(a, s));
+  else if (p.attn == ATT_TILE) HIPCHK(e, vc_launch_tile_attn(a, e->dtype, s));
+  else HIPCHK(e, vc_launch_attn(a, e->dtype, rs.n_rows, s));
+  return VC_OK;
+}
+
+// h' = h + bo + Wo attn: finished rows into hA, or split-K slabs
+int site_oproj(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly, const float* h, hipStream_t s) {
+  const int d = e->d;
+  GemmArgs g = base_args(e, rs, e->p_o, d, d);
+  if (p.form == FORM_FR) {
+    g.Wp = ly.Wo8; g.bias = ly.bo;
+    g.h_in = h; g.h_out = e->hA;
+    if (p.hq) { g.hq_out = e->hqA; g.row_mu = e->row_mu[1]; }      // centred on the mean the QKV consumer found for h
+    if (p.att_x) {
+      g.x_in = e->xn; g.x_ld = d;
+      HIPCHK(e, vc_launch_gemm_fr(g, e->dtype, PRO_PLAIN, s));
+    } else {
+      g.att_o = e->att_o; g.att_ml = e->att_ml; g.nsplit = p.nsplit; g.att_p16 = p.part16 ? 1 : 0;
+      HIPCHK(e, vc_launch_gemm_fr(g, e->dtype, PRO_ATT, s));
+    }
+    return VC_OK;
+  }
+  g.Wp = ly.Wo; nt_bit(e, g, NT_O); g.part_out = e->parts; g.mt = p.mt;
+  if (p.att_x) {
+    g.x_in = e->xn; g.x_ld = d;
+    if (p.wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_PART, p.ks_o, 1, s));
+    else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_PART, p.ks_o, 1, s));
+  } else {                 // merge the attention partials of all heads
+    g.att_o = e->att_o; g.att_ml = e->att_ml; g.nsplit = p.nsplit;
+    HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_ATT, EPI_PART, p.ks_o, 1, s));
+  }
+  return VC_OK;
+}
+
+// a = relu(W1 LN2(h') + b1)
+int site_ffn_up(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly, const Resid& r, hipStream_t s) {
+  const int d = e->d;
+  GemmArgs g = base_args(e, rs, e->p_f1, 4 * d, d);
+  g.Wp = ly.W1; nt_bit(e, g, NT_F1); g.bias = ly.b1; g.wg = ly.wg_1;
+  g.out = e->act; g.out_ld = 4 * d; g.mt = p.mt;
+  if (p.form == FORM_FR) {
+    g.h_in = r.h_in;
+    if (p.hq) {
+      g.x_in = e->hqA; g.x_ld = d; g.row_mu = e->row_mu[1]; g.row_mu_out = e->row_mu[0];
+      HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNQ, EPI_RELU, 1, 1, s));
+    } else {
+      HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNW, EPI_RELU, 1, 1, s));
+    }
+    return VC_OK;
+  }
+  set_resid(e, g, r);
+  if (!p.ln_launch) {
+    HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LN, EPI_RELU, 1, 1, s));
+    return VC_OK;
+  }
+  g.x_in = e->xn; g.x_ld = d;
+  if (p.wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_RELU, 1, 1, s));
+  else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_RELU, 1, 1, s));
+  return VC_OK;
+}
+
+// h'' = h' + b2 + W2 a: finished rows into hB, or split-K slabs folded into the next LayerNorm together with b2
+int site_ffn_down(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly, hipStream_t s) {
+  const int d = e->d;
+  GemmArgs g = base_args(e, rs, e->p_f2, d, 4 * d);
+  g.x_in = e->act; g.x_ld = 4 * d;
+  if (p.form == FORM_FR || p.fd) {
+    g.Wp = ly.W28; g.bias = ly.b2;
+    g.h_in = e->hA; g.h_out = e->hB;
+    if (p.hq) { g.hq_out = e->hqB; g.row_mu = e->row_mu[0]; }      // centred on the mean the FFN-up consumer found for h'
+    if (p.fd) HIPCHK(e, vc_launch_gemm_fr1(g, e->dtype, PRO_PLAIN, EPI_RES, s));
+    else if (p.frp) HIPCHK(e, vc_launch_gemm_frp(g, e->dtype, s));      // 2..8 rows: two k-tiles per fragment
+    else HIPCHK(e, vc_launch_gemm_fr(g, e->dtype, PRO_PLAIN, s));
+    return VC_OK;
+  }
+  g.Wp = ly.W2; nt_bit(e, g, NT_F2); g.part_out = e->parts; g.mt = p.mt;
+  if (p.wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_PART, p.ks_f2, 1, s));
+  else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_PART, p.ks_f2, 1, s));
+  return VC_OK;
+}
+
+// What a pass leaves for the heads in hB: finished rows (n_parts = 0; hq: their centred copy, on the means in mu) or rows whose
+// n_parts split-K slabs and last FFN-down bias are still to be added.
+struct PassOut { int n_parts; const void* hq; const float* mu; };
+
+// One pass of rs.n_rows rows through every layer, in the form `p` plans.
+int run_pass(vc_engine* e, const PassPlan& p, const RowSrc& rs, PassOut* out, hipStream_t s) {
+  for (int l = 0; l < e->L; ++l) {
+    const Layer& ly = e->layers[l];
+    const Layer* prev = l > 0 ? &e->layers[l - 1] : nullptr;
+    const float* h = prev ? e->hB : rs.h_in;
+    const Resid rq = qkv_in(e, p, ly, h, prev), rf = ffn_in(e, p, ly, h);
+    int rc;
+    if ((p.ln_launch && (rc = site_ln(e, rs, rq, s))) || (rc = site_qkv(e, p, rs, ly, rq, !prev, s)) || (rc = site_attn(e, p, rs, ly, s)) ||
+        (rc = site_oproj(e, p, rs, ly, h, s)) || (p.ln_launch && (rc = site_ln(e, rs, rf, s))) || (rc = site_ffn_up(e, p, rs, ly, rf, s)) ||
+        (rc = site_ffn_down(e, p, rs, ly, s)))
+      return rc;
+  }
+  const bool finished = p.form == FORM_FR || p.fd;
+  *out = {finished ? 0 : p.ks_f2, p.hq ? e->hqB : nullptr, e->row_mu[0]};
+  return VC_OK;
+}
+
+// final LayerNorm + heads-1 for n rows; row r reads hidden row gather[r] (or in_row0 + r) and writes hh row (out_row0 + r).  wide: all
+// rows of a 17..64-row step at once on the weight-stationary kernel of those steps (LayerNorm launch + rows_gemm_wd_k / rows_gemm_mt_k)
+int site_heads1(vc_engine* e, const PassPlan& p, const PassOut& po, bool wide, const int* gather, int n, int in_row0, int out_row0,
+                const int* n_active, hipStream_t s) {
+  if (gather && n > 1) return fail(e, VC_EINVAL, "internal: a gathered head pass carries one row");
+  RowSrc rs{};
+  rs.n_rows = n; rs.n_active = n_active;
+  const int d = e->d;
+  GemmArgs g = base_args(e, rs, e->p_h1, e->K * e->P, d);
+  g.Wp = e->Wh1; nt_bit(e, g, NT_H1); g.bias = e->bh1; g.wg = e->wg_h1; g.gather_rows = gather;
+  g.h_in = e->hB + (size_t)in_row0 * d; g.parts = e->parts + (size_t)in_row0 * d; g.n_parts = po.n_parts;
+  g.prev_bias = e->layers[e->L - 1].b2; g.has_prev_bias = po.n_parts > 0 ? 1 : 0;
+  g.out = (char*)e->hh + (size_t)out_row0 * e->K * e->P * e->esz; g.out_ld = e->K * e->P;
+  if (p.heads_fold && !gather) {                  // finished rows: LayerNorm fold per wave, no extra launch
+    if (po.hq && in_row0 == 0) {                  // ... on the last FFN down-projection's centred copy
+      g.x_in = po.hq; g.x_ld = d; g.row_mu = po.mu;
+      HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNQ, EPI_GELU, 1, 1, s));
+    } else {
+      HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNW, EPI_GELU, 1, 1, s));
+    }
+  } else if (!gather && n >= ln_split_rows) {      // (wide: always)
+    g.x_out = e->xn;
+    HIPCHK(e, vc_launch_ln_rows(g, e->dtype, s));
+    g.x_in = e->xn; g.x_ld = d;
+    if (wide) g.mt = 2;
+    if (wide && p.wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_GELU, 1, 1, s));
+    else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_GELU, 1, 1, s));
+  } else {
+    HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LN, EPI_GELU, 1, 1, s));
+  }
+  return VC_OK;
+}
+// heads-2: the K codebook logits of hh rows out_row0.. (one group per codebook)
+int site_heads2(vc_engine* e, const PassPlan& p, bool wide, int n, int out_row0, const int* n_active, hipStream_t s) {
+  RowSrc rs{};
+  rs.n_rows = n; rs.n_active = n_active;
+  GemmArgs g = base_args(e, rs, e->p_h2, e->V, e->P);
+  g.Wp = e->Wh2; nt_bit(e, g, NT_H2); g.bias = e->bh2;
+  g.w_group_stride = e->wh2_group_stride; g.bias_group_stride = e->V;
+  g.x_in = (char*)e->hh + (size_t)out_row0 * e->K * e->P * e->esz; g.x_ld = e->K * e->P; g.x_group_stride = e->P;
+  g.out = e->logits + (size_t)out_row0 * e->K * e->V;
+  if (wide) g.mt = 2;
+  if (wide && p.wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_LOGITS, 1, e->K, s));
+  else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_LOGITS, 1, e->K, s));
+  return VC_OK;
+}
+// The prediction heads (voicecraft.py:181-185, :1084-1086) behind pass `p`: at 17..64 rows once over the step (option wide_heads: the
+// 16-row passes streamed the 33.6 MB of head weights four times at 64 rows), otherwise 16 rows at a time.
+int run_heads(vc_engine* e, const PassPlan& p, const PassOut& po, const int* gather, int n, int in_row0, int out_row0,
+              const int* n_active, hipStream_t s) {
+  const bool wide = p.heads_wide && !gather;
+  const int step = wide ? n : VC_ROWS;
+  for (int r0 = 0; r0 < n; r0 += step) {
+    const int m = std::min(step, n - r0);
+    int rc;
+    if ((rc = site_heads1(e, p, po, wide, gather, m, in_row0 + r0, out_row0 + r0, n_active, s)) ||
+        (rc = site_heads2(e, p, wide, m, out_row0 + r0, n_active, s)))
+      return rc;
+  }
+  return VC_OK;
+}
+
+// Prefill attention of a call whose longest prompt has `longest` rows: 2 = tile_attn64_k on 64-row blocks, 1 = tile_attn_k on 16-row tiles.
+// (tile_attn64_k's gain grows with the sequence - 800 rows -15 %, 2048 rows -39 % of the attention launch; 512 rows +8 % -, while the 64-row
+// layout costs up to 48 padding rows per prompt in every GEMM of the pass: config 5's eight 231-row prompts would pay 6.7 % more GEMM rows
+// for no attention gain (measured neutral: prefill 5.2 ms either way, profiles/r04p_default_attn64.log), so they stay on the first kernel
+// and 16-row boundaries.  And only when the passes are cut on 64-row boundaries: with a `prefill_rows` option that is not a multiple of
+// 64 a block of a later pass would straddle one prompt's tail padding and the next prompt's first rows - ADVICE r04.)
+int prefill_tiled(const vc_engine* e, long longest) {
+  const bool attn64 = e->tile_attn == 2 && e->dtype == VC_DTYPE_BF16 && e->hd == 128 && longest >= e->tile_attn_min_rows &&
+                      e->prefill_rows_per_pass % 64 == 0;
+  return attn64 ? 2 : 1;
 }
 
 // Prefill of one or several prompts as ONE row stream: the prompts' rows are laid back to back in `emb`
@@ -777,18 +721,11 @@ int prefill_batch(vc_engine* e, std::vector<PromptArgs>& pas, const std::vector<
     // attention of the prefill works on such tiles; the padding rows are inactive, row_pos = -1)
     size_t i1 = i0;
     int R = 0;
-    // (tile_attn64_k works on 64-row blocks of one sequence: prompts then start on multiples of 64 rows)
-    // ... and only when the call holds a LONG prompt: the kernel's gain grows with the sequence (800 rows -15 %, 2048 rows -39 %
-    // of the attention launch; 512 rows +8 %), while the 64-row layout costs up to 48 padding rows per prompt in every GEMM of the
-    // pass - config 5's eight 231-row prompts would pay 6.7 % more GEMM rows for no attention gain (measured neutral: prefill 5.2 ms
-    // either way, profiles/r04p_default_attn64.log), so they stay on the first kernel and 16-row boundaries
+    // (tile_attn64_k works on 64-row blocks of one sequence: prompts then start on multiples of 64 rows; prefill_tiled)
     long longest = 0;
     for (const PromptArgs& pa : pas) longest = std::max<long>(longest, pa.Lx + pa.n_cols - pa.skip);
-    // (... and only when the passes are cut on 64-row boundaries: with a `prefill_rows` option that is not a multiple of 64 a block of
-    // a later pass would straddle one prompt's tail padding and the next prompt's first rows - ADVICE r04)
-    const bool attn64 = e->tile_attn == 2 && e->dtype == VC_DTYPE_BF16 && e->hd == 128 && longest >= e->tile_attn_min_rows && chunk % 64 == 0 &&
-                        !getenv("VC_NO_TILE_ATTN");
-    const int al = attn64 ? 64 : 16;
+    const int tiled = prefill_tiled(e, longest);
+    const int al = tiled == 2 ? 64 : 16;
     auto rows_of = [al](const PromptArgs& pa) { return ((pa.Lx + pa.n_cols - pa.skip) + al - 1) & ~(al - 1); };
     while (i1 < pas.size() && (i1 == i0 || R + rows_of(pas[i1]) <= e->emb_cap)) {
       R += rows_of(pas[i1]);
@@ -816,13 +753,13 @@ int prefill_batch(vc_engine* e, std::vector<PromptArgs>& pas, const std::vector<
       rs.h_in = e->emb + (size_t)r0 * e->d;
       rs.row_seq = e->pre_row_seq + r0; rs.row_pos = e->pre_row_pos + r0;
       rs.n_rows = std::min(chunk, R - r0);
-      int rc;
-      if (rs.n_rows > VC_ROWS) { rs.nsplit = 1; rs.tiled = getenv("VC_NO_TILE_ATTN") ? 0 : (attn64 ? 2 : 1); rc = prefill_rows(e, rs, s); }
-      else { rs.nsplit = attn_nsplit(e, rs.n_rows); rc = forward_rows(e, rs, s); }
+      const PassPlan p = plan_pass(e, rs.n_rows, false, rs.n_rows > VC_ROWS ? tiled : 0);
+      PassOut po;
+      int rc = run_pass(e, p, rs, &po, s);
       if (rc) return rc;
       for (size_t i = i0; i < i1; ++i)
         if (last[i - i0] >= r0 && last[i - i0] < r0 + rs.n_rows)
-          if ((rc = run_heads(e, e->logit_row + slots[i], 1, slots[i], nullptr, s))) return rc;
+          if ((rc = run_heads(e, p, po, e->logit_row + slots[i], 1, 0, slots[i], nullptr, s))) return rc;
     }
     i0 = i1;
   }
@@ -876,17 +813,13 @@ int push_sample_dyn(vc_engine* e, const vc_sample_cfg* sc, const int64_t* forced
 int decode_step(vc_engine* e, const SampleArgs& sa, int B, int rps, bool grouped, hipStream_t s) {
   RowSrc rs{};
   rs.h_in = e->dec_h; rs.row_seq = e->dec_row_seq; rs.row_pos = e->dec_row_pos;
-  rs.n_rows = B * rps; rs.nsplit = attn_nsplit(e, B * rps); rs.n_active = e->n_active;
-  int rc;
-  if (rs.n_rows > VC_ROWS) {             // more than one MFMA row tile: the step runs on the block GEMM (per-row LayerNorm launch,
-    rs.nsplit = 1;                // attention one workgroup per (row, head), no split partials)
-    rc = prefill_rows(e, rs, s);
-  } else {
-    rc = forward_rows(e, rs, s);
-  }
+  rs.n_rows = B * rps; rs.n_active = e->n_active;
+  const PassPlan p = plan_pass(e, rs.n_rows, true, 0);
+  PassOut po;
+  int rc = run_pass(e, p, rs, &po, s);
   if (rc) return rc;
   // rps == 1: logit_row[b] == b (vc_tokens.hip advance_phase); the 3-row span switch is single-sequence
-  rc = run_heads(e, rps == 1 ? nullptr : e->logit_row, B, 0, e->n_active, s);
+  rc = run_heads(e, p, po, rps == 1 ? nullptr : e->logit_row, B, 0, 0, e->n_active, s);
   if (rc) return rc;
   HIPCHK(e, vc_launch_sample(sa, grouped, s));
   return VC_OK;
@@ -1056,13 +989,13 @@ int apply_option(vc_engine* e, const std::string& name, const char* value) {
     e->tile_attn = v0 == 2 ? 2 : 1;
     if (n >= 2) e->tile_attn_min_rows = std::max(64, v1);
   } else if (name == "finished_rows" || name == "fr_one") {
-    if (v0 > 0 && !e->layers.empty() && !e->layers[0].W28)
+    if (v0 > 0 && !e->has_fr8)
       return fail(e, VC_ESTATE, "option '%s': this engine was created with VC_FINISHED_ROWS=0 and VC_FR_ONE=0 and holds no 8-channel weight images", name.c_str());
     if (name == "fr_one") e->fr_one = std::max(0, std::min(v0, 2));
     else e->fr_rows = std::max(0, std::min(v0, VC_ROWS));
   } else if (name == "fr_pair") { e->fr_pair = v0 ? 1 : 0;
   } else if (name == "qkv_p8") {
-    if (v0 && !e->layers.empty() && !e->layers[0].Wqkv8 && vc_gemm_fr1_ok(3 * e->d, e->d, e->dtype, 4))
+    if (v0 && !e->has_qkv8 && vc_gemm_fr1_ok(3 * e->d, e->d, e->dtype, 4))
       return fail(e, VC_ESTATE, "option 'qkv_p8': this engine was created with VC_QKV_P8=0 or VC_FR_ONE=0 and holds no 8-channel image of the QKV matrix");
     e->qkv_p8 = std::max(0, std::min(v0, 2));      // 2: steps of 2..8 finished rows as well (rows_gemm_qp_k)
   } else if (name == "wide_heads") { e->wide_heads = v0 ? 1 : 0;
@@ -1070,7 +1003,7 @@ int apply_option(vc_engine* e, const std::string& name, const char* value) {
   } else if (name == "shrink") { e->shrink = v0 ? 1 : 0;
   } else if (name == "wd_stage") { e->wd_stage = v0 ? 1 : 0;
   } else if (name == "qkv16") {
-    if (v0 && !e->layers.empty() && !e->layers[0].Wqkv16)
+    if (v0 && !e->has_qkv16)
       return fail(e, VC_ESTATE, "option 'qkv16': this engine holds no 16-channel image of the QKV matrix (packed for max_seqs > 16, or with VC_QKV16=1 at creation)");
     e->qkv16 = v0 ? 1 : 0;
   } else if (name == "attn_fast") { e->attn_fast = v0 ? 1 : 0;
@@ -1101,34 +1034,35 @@ void refresh_opt_state(vc_engine* e) {
 extern "C" int vc_debug_plan(const vc_model_cfg* c, int compute_dtype, int rows, int32_t out[16]) {
   if (!c || !out || rows < 1 || rows > VC_MAX_SEQS || c->d_model <= 0 || c->nhead <= 0 || c->d_model % c->nhead) return VC_EINVAL;
   if (compute_dtype != VC_DTYPE_BF16 && compute_dtype != VC_DTYPE_F32) return VC_EINVAL;
-  vc_engine e;
-  e.cfg = *c; e.d = c->d_model; e.H = c->nhead; e.hd = c->d_model / c->nhead; e.dtype = compute_dtype;
-  const int d = e.d, frmax = fr_max_rows(&e);
-  const bool fr = rows >= 2 && rows <= VC_ROWS && rows <= frmax;
-  const int ns = fr ? fr_nsplit(&e, rows) : attn_nsplit(&e, rows);
-  out[0] = frmax;
-  out[1] = rows > VC_ROWS ? 2 : fr ? 1 : 0;                                   // 0 slab form (rows-GEMM), 1 finished-row form, 2 wide decode
-  out[2] = rows > VC_ROWS ? 1 : ns;                                           // attention splits
-  out[3] = fr ? (rows > VC_FR_MAX_ROWS ? 4 : lnw_two(&e, rows) ? 3 : 0) : -1; // consumers: GemmArgs.mt (0 one tile, 3 two tiles, 4 two tiles x two rows per wave)
-  out[4] = fr ? vc_gemm_fr_form(rows, d, d, compute_dtype, ns == 1 ? PRO_PLAIN : PRO_ATT, ns) : -1;    // out-projection producer form
-  out[5] = fr ? vc_gemm_fr_form(rows, d, 4 * d, compute_dtype, PRO_PLAIN, 1) : -1;                      // FFN-down producer form
-  out[6] = fr && rows <= VC_FR_MAX_ROWS ? 1 : 0;                              // heads-1 folds finished rows itself (else LayerNorm launch)
+  vc_engine e;      // default options, the weight images vc_finalize_weights packs for an engine that takes wide steps
+  e.cfg = *c; e.d = c->d_model; e.H = c->nhead; e.hd = c->d_model / c->nhead; e.P = c->head_hidden; e.dtype = compute_dtype;
+  const int d = e.d;
+  e.has_fr8 = e.has_qkv16 = true;
+  e.has_qkv8 = vc_gemm_fr1_ok(3 * d, d, compute_dtype, 4) != 0;
+  const PassPlan p = plan_pass(&e, rows, true, 0);
+  const bool fr = p.form == FORM_FR;
+  out[0] = fr_max_rows(&e);
+  out[1] = p.form;                                                            // 0 slab form (rows-GEMM), 1 finished-row form, 2 wide decode
+  out[2] = p.nsplit;                                                          // attention splits
+  out[3] = fr ? p.mt : -1;                                                    // consumers: GemmArgs.mt (0 one tile, 3 two tiles, 4 two tiles x two rows per wave)
+  out[4] = fr ? vc_gemm_fr_form(rows, d, d, compute_dtype, p.att_x ? PRO_PLAIN : PRO_ATT, p.nsplit) : -1;   // out-projection producer form
+  out[5] = fr ? vc_gemm_fr_form(rows, d, 4 * d, compute_dtype, PRO_PLAIN, 1) : -1;                       // FFN-down producer form
+  out[6] = p.heads_fold ? 1 : 0;                                              // heads-1 folds finished rows itself (else LayerNorm launch)
   out[7] = (3 * d / VC_TH_QKV) % 2 == 0 && (4 * d / 16) % 2 == 0 ? 1 : 0;     // the consumers' tile counts are even (two tiles per workgroup)
-  // the default forms of rounds 5-6, from the launchers' own predicates
+  // the default forms of rounds 5-6
   for (int i = 8; i < 16; ++i) out[i] = -1;
   if (rows == 1) {
-    out[8] = vc_gemm_fr1_ok(d, 4 * d, compute_dtype, VC_FR_WAVES) ? 1 : 0;                       // fr_one: FFN-down finishes its row
-    out[9] = out[8] && vc_gemm_fr1_ok(3 * d, d, compute_dtype, 4) ? 1 : 0;                       // qkv_p8: the paired QKV projection behind it
+    out[8] = p.fd ? 1 : 0;                                                    // fr_one: FFN-down finishes its row
+    out[9] = p.qkv_fr1 ? 1 : 0;                                               // qkv_p8: the paired QKV projection behind it
   }
-  if (fr && rows <= VC_FR_MAX_ROWS) out[10] = vc_gemm_frp_ok(rows, d, 4 * d, compute_dtype) ? 1 : 0;   // fr_pair
-  if (fr && rows <= VC_FR_MAX_ROWS)       // qkv_p8 = 2: layers 1.. run the QKV projection on the 8-channel image (rows_gemm_qp_k) - the image's packing rule, qp_on's row rule
-    out[9] = (hq_on(&e) && vc_gemm_fr1_ok(3 * d, d, compute_dtype, 4) && rows <= (d >= 2048 ? 6 : 8) && vc_gemm_qp_ok(rows, 3 * d, d, compute_dtype)) ? 2 : 0;
+  if (fr && rows <= VC_FR_MAX_ROWS) {
+    out[10] = p.frp ? 1 : 0;                                                  // fr_pair
+    out[9] = p.qp ? 2 : 0;                                                    // qkv_p8 = 2: layers 1.. run the QKV projection on rows_gemm_qp_k
+  }
   if (rows > VC_ROWS) {
-    e.P = c->head_hidden;
-    const int ko = wd_ksplit(&e, d, d), kf = wd_ksplit(&e, d, 4 * d);
-    out[12] = ko; out[13] = kf;
+    out[11] = p.wd ? 1 : 0;                                                   // the wide step on rows_gemm_wd_k, and the launcher's forms it needs:
+    out[12] = wd_ksplit(&e, d, d); out[13] = wd_ksplit(&e, d, 4 * d);
     out[14] = vc_gemm_wd_kpw(d, compute_dtype, 1); out[15] = vc_gemm_wd_kpw(c->head_hidden, compute_dtype, 1);
-    out[11] = (ko && kf && out[14] && out[15]) ? 1 : 0;
   }
   return VC_OK;
 }
@@ -1267,6 +1201,11 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
   const char* env_q16 = getenv("VC_QKV16");
   const bool want_qkv16 = env_q16 ? atoi(env_q16) != 0 : e->B_max > VC_ROWS;
   if (!want_qkv16) e->qkv16 = 0;
+  const char* env_p8 = getenv("VC_QKV_P8");
+  const bool want_p8 = !(env_p8 && atoi(env_p8) == 0) && !(env_f1 && atoi(env_f1) == 0);
+  e->has_fr8 = want_fr8;
+  e->has_qkv8 = want_fr8 && want_p8 && vc_gemm_fr1_ok(3 * d, d, e->dtype, 4);
+  e->has_qkv16 = want_qkv16;
   e->layers.resize(L);
   for (int l = 0; l < L; ++l) {
     const std::string pre = "decoder.layers." + std::to_string(l) + ".";
@@ -1291,9 +1230,7 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
       if ((rc = pack_matrix(e, pre + "linear2.weight", d, 4 * d, &ly.W28, VC_TH_RES))) return rc;
       // (the one-row paired QKV kernel reads the folded matrix in 8-channel tiles: only where its form can run, i.e. behind fr_one)
       // (not packed when either of the two options it serves is preset off - VC_QKV_P8=0 / VC_FR_ONE=0 -: 0.4 GB at giga830M)
-      const char* env_p8 = getenv("VC_QKV_P8");
-      const bool want_p8 = !(env_p8 && atoi(env_p8) == 0) && !(env_f1 && atoi(env_f1) == 0);
-      if (want_p8 && vc_gemm_fr1_ok(3 * d, d, e->dtype, 4)) {
+      if (e->has_qkv8) {
         const RawTensor* tg1;
         if ((rc = need(e, pre + "norm1.weight", {d}, &tg1))) return rc;
         if ((rc = pack_matrix(e, pre + "self_attn.in_proj_weight", 3 * d, d, &ly.Wqkv8, VC_TH_RES, tg1->dev))) return rc;
@@ -1897,12 +1834,12 @@ extern "C" int vc_eval_forward(vc_engine* e, int B, const int64_t* x_dev, const 
       rs.h_in = e->emb + (size_t)r0 * e->d;
       rs.row_seq = e->pre_row_seq + r0; rs.row_pos = e->pre_row_pos + r0;
       rs.n_rows = std::min(chunk, R - r0);
-      if (rs.n_rows > VC_ROWS) { rs.nsplit = 1; rs.tiled = getenv("VC_NO_TILE_ATTN") ? 0 : 1; rc = prefill_rows(e, rs, s); }
-      else { rs.nsplit = attn_nsplit(e, rs.n_rows); rc = forward_rows(e, rs, s); }
-      if (rc) return rc;
+      const PassPlan p = plan_pass(e, rs.n_rows, false, rs.n_rows > VC_ROWS ? 1 : 0);      // 16-row tiles only
+      PassOut po;
+      if ((rc = run_pass(e, p, rs, &po, s))) return rc;
       for (int g0 = 0; g0 < rs.n_rows; g0 += VC_ROWS) {
         const int n = std::min(VC_ROWS, rs.n_rows - g0);
-        if ((rc = run_heads16(e, nullptr, n, g0, 0, nullptr, s))) return rc;
+        if ((rc = run_heads(e, p, po, nullptr, n, g0, 0, nullptr, s))) return rc;
         CeArgs ca;
         memset(&ca, 0, sizeof ca);
         ca.logits = e->logits; ca.y = y_dev; ca.tgt = e->ce_tgt + (size_t)(r0 + g0) * K;
@@ -2000,8 +1937,8 @@ extern "C" int vc_last_timing(const vc_engine* e, float ms[3]) {
   return VC_OK;
 }
 
-// Times one kernel of the decode step in isolation (HIP events on the launch stream).
-//   which = "ffn1" | "ffn2" | "qkv" | "oproj" : the rows-GEMM of layer (i % L), n_rows rows
+// Times one launch site of a pass in isolation (HIP events on the launch stream), on the weights of layer (i % L) (layer 0: _hot).
+//   which = "ffn1" | "ffn2" | "qkv" | "oproj" | "attn" : a step of n_rows <= 16 rows; "wd_*" (also "wd_ln"): 17..64 rows; "pf_*": a prefill pass
 //   which = "step" : one whole decode step (forward + heads, sampler excluded) for n_rows sequences
 extern "C" int vc_bench_kernel(vc_engine* e, const char* which, int n_rows, int iters, float* avg_ms,
                                double* alg_bytes, void* stream) {
@@ -2048,171 +1985,38 @@ extern "C" int vc_bench_kernel(vc_engine* e, const char* which, int n_rows, int 
   HIPCHK(e, hipMemsetAsync(e->att_o, 0, (size_t)VC_ROWS * e->H * VC_MAX_NSPLIT * e->hd * 4, s));
   HIPCHK(e, hipMemsetAsync(e->att_ml, 0, (size_t)VC_ROWS * e->H * VC_MAX_NSPLIT * 2 * 4, s));
   HIPCHK(e, hipMemsetAsync(e->logit_row, 0, VC_ROWS * 4, s));
-  RowSrc rs{};
-  rs.h_in = e->dec_h; rs.row_seq = e->dec_row_seq; rs.row_pos = e->dec_row_pos;
-  rs.n_rows = n_rows; rs.nsplit = attn_nsplit(e, n_rows); rs.nt = 1;
-  if (n_rows >= 2 && n_rows <= fr_max_rows(e)) rs.nsplit = fr_nsplit(e, n_rows);
   bool hot = false;
   std::string w2 = w;
   if (w.size() > 4 && w.substr(w.size() - 4) == "_hot") { hot = true; w2 = w.substr(0, w.size() - 4); }
+  // The launch site a name times, in the form a pass of n_rows rows launches it at a layer > 0 (wd_*: a 17..64-row decode step; pf_*: a
+  // prefill pass, the attention kernel a prompt of n_rows rows gets).  The LayerNorm launch in front of a GEMM is a site of its own.
+  const std::string site = (wide || pf) ? w2.substr(3) : w2;
+  const bool known = wide ? (site == "ffn1" || site == "ffn2" || site == "oproj" || site == "qkv" || site == "ln" || site == "attn")
+                     : pf ? (site == "ffn1" || site == "qkv" || site == "attn")
+                          : (site == "ffn1" || site == "ffn2" || site == "oproj" || site == "qkv" || site == "attn" || site == "step");
+  if (!known) return fail(e, VC_EINVAL, "unknown kernel '%s'", which);
+  const PassPlan p = plan_pass(e, n_rows, wide, pf ? prefill_tiled(e, n_rows) : 0);
+  RowSrc rs{};
+  rs.h_in = e->dec_h; rs.row_seq = pf ? e->pre_row_seq : e->dec_row_seq; rs.row_pos = pf ? e->pre_row_pos : e->dec_row_pos;
+  rs.n_rows = n_rows; rs.n_active = wide ? e->one : nullptr; rs.nt = 1;
   auto one = [&](int i) -> int {
-    Layer& ly = e->layers[hot ? 0 : i % e->L];   // _hot: the same 8-34 MB every launch (cache-resident)
-    const std::string& w = w2;
-    const bool split_ln = n_rows >= e->ln_split_rows;   // the engine then normalises in ln_rows_k and takes the plain prologue
-    if (wide) {      // one linear layer of a 17..64-row step, in the form prefill_rows launches it there (options wide_gemm / wd_stage / qkv16)
-      const bool wd = use_wd(e, n_rows);
-      RowSrc rw = rs;
-      rw.n_active = e->one; rw.nsplit = 1;
-      if (w == "wd_ffn1") {
-        GemmArgs g = base_args(e, rw, e->p_f1, 4 * d, d);
-        g.Wp = ly.W1; nt_bit(e, g, NT_F1); g.bias = ly.b1; g.x_in = e->xn; g.x_ld = d; g.out = e->act; g.out_ld = 4 * d; g.mt = 2;
-        if (wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_RELU, 1, 1, s));
-        else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_RELU, 1, 1, s));
-      } else if (w == "wd_ffn2") {
-        GemmArgs g = base_args(e, rw, e->p_f2, d, 4 * d);
-        g.Wp = ly.W2; nt_bit(e, g, NT_F2); g.x_in = e->act; g.x_ld = 4 * d; g.part_out = e->parts; g.mt = 2;
-        if (wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_PART, wd_ksplit(e, d, 4 * d), 1, s));
-        else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_PART, e->p_f2.ksplit, 1, s));
-      } else if (w == "wd_oproj") {
-        GemmArgs g = base_args(e, rw, e->p_o, d, d);
-        g.Wp = ly.Wo; nt_bit(e, g, NT_O); g.x_in = e->xn; g.x_ld = d; g.part_out = e->parts; g.mt = 2;
-        if (wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_PART, wd_ksplit(e, d, d), 1, s));
-        else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_PART, e->p_o.ksplit, 1, s));
-      } else if (w == "wd_qkv") {
-        GemmArgs g = base_args(e, rw, e->p_qkv, 3 * d, d);
-        g.Wp = ly.Wqkv; nt_bit(e, g, NT_QKV); g.bias = ly.bqkv; g.x_in = e->xn; g.x_ld = d; g.mt = 2;
-        g.q_out = e->q; g.kcache = ly.kc; g.vcache = ly.vc;
-        if (use_qkv16(e, n_rows, 2)) {
-          g.Wp = ly.Wqkv16; g.n_tiles = e->p_qkv16.n_tiles; g.KT = e->p_qkv16.KT; g.nchunk = e->p_qkv16.nchunk;
-          if (wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_QKV16, 1, 1, s));
-          else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_QKV16, 1, 1, s));
-        } else {
-          HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_QKV, 1, 1, s));
-        }
-      } else if (w == "wd_ln") {      // the per-row LayerNorm launch in front of the FFN up-projection (h + bias + the out-projection's slabs)
-        GemmArgs g = base_args(e, rw, e->p_f1, 4 * d, d);
-        g.h_in = e->hA; g.h_out = e->hB; g.parts = e->parts; g.n_parts = wd ? wd_ksplit(e, d, d) : e->p_o.ksplit; g.prev_bias = ly.bo; g.has_prev_bias = 1;
-        g.x_out = e->xn;
-        HIPCHK(e, vc_launch_ln_rows(g, e->dtype, s));
-      } else if (w == "wd_attn") {    // the decode attention of that step: n_rows rows of ONE sequence slot at its last position (timing only)
-        AttnArgs a;
-        memset(&a, 0, sizeof a);
-        a.q = e->q; a.kcache = ly.kc; a.vcache = ly.vc; a.cache_seq_stride = (long)e->H * e->S_max * e->hd;
-        a.S_max = e->S_max; a.H = e->H; a.hd = e->hd; a.hd_shift = e->hd == 32 ? 5 : e->hd == 64 ? 6 : 7; a.d = d; a.nsplit = 1; a.scale = 1.0f / sqrtf((float)e->hd);
-        a.row_seq = rs.row_seq; a.row_pos = rs.row_pos; a.n_rows = n_rows; a.att_o = e->att_o; a.att_ml = e->att_ml;
-        a.n_active = e->one; a.dbg_ts = e->dbg_ts; a.share_len = e->share_len; a.nt = attn_nt_for(e, n_rows); a.x_out = e->xn;
-        a.fast = e->attn_fast;
-        HIPCHK(e, vc_launch_attn(a, e->dtype, n_rows, s));
-      } else {
-        return fail(e, VC_EINVAL, "unknown kernel '%s'", which);
-      }
-      return VC_OK;
+    const Layer& ly = e->layers[hot ? 0 : i % e->L];   // _hot: the same 8-34 MB every launch (cache-resident)
+    const Resid rq = qkv_in(e, p, ly, e->hB, &ly), rf = ffn_in(e, p, ly, e->hB);
+    if (site == "qkv") return site_qkv(e, p, rs, ly, rq, false, s);
+    if (site == "attn") return site_attn(e, p, rs, ly, s);
+    if (site == "oproj") return site_oproj(e, p, rs, ly, e->hB, s);
+    if (site == "ln") return site_ln(e, rs, rf, s);         // the per-row LayerNorm launch in front of the FFN up-projection
+    if (site == "ffn2") return site_ffn_down(e, p, rs, ly, s);
+    if (site == "ffn1") {
+      const char* dbg_env = pf ? getenv("VC_BLK_DBG") : nullptr;        // tools/blk_probe.py: wrong results by design, timing only
+      if (pf) vc_blk_dbg_mask = dbg_env ? atoi(dbg_env) : 0;
+      const int r = site_ffn_up(e, p, rs, ly, rf, s);
+      if (pf) vc_blk_dbg_mask = 0;
+      return r;
     }
-    if (n_rows >= 2 && n_rows <= fr_max_rows(e) && (w == "ffn1" || w == "ffn2" || w == "qkv" || w == "oproj")) {
-      // the forms a step of this many rows really launches (forward_rows_fr): finished rows in, finished rows out
-      if (w == "ffn1") {
-        GemmArgs g = base_args(e, rs, e->p_f1, 4 * d, d);
-        g.Wp = ly.W1; nt_bit(e, g, NT_F1); g.bias = ly.b1; g.wg = ly.wg_1; g.h_in = e->hA; g.out = e->act; g.out_ld = 4 * d;
-        g.mt = rs.n_rows > VC_FR_MAX_ROWS ? 4 : lnw_two(e, rs.n_rows) ? 3 : 0;
-        if (hq_on(e)) { g.x_in = e->hqA; g.x_ld = d; g.row_mu = e->row_mu[0]; g.row_mu_out = e->row_mu[1]; }     // the form forward_rows_fr launches
-        HIPCHK(e, vc_launch_gemm(g, e->dtype, hq_on(e) ? PRO_LNQ : PRO_LNW, EPI_RELU, 1, 1, s));
-      } else if (w == "qkv") {
-        GemmArgs g = base_args(e, rs, e->p_qkv, 3 * d, d);
-        g.Wp = ly.Wqkv; nt_bit(e, g, NT_QKV); g.bias = ly.bqkv; g.wg = ly.wg_qkv; g.h_in = e->hB; g.q_out = e->q; g.kcache = ly.kc; g.vcache = ly.vc;
-        g.mt = rs.n_rows > VC_FR_MAX_ROWS ? 4 : lnw_two(e, rs.n_rows) ? 3 : 0;
-        if (hq_on(e)) { g.x_in = e->hqB; g.x_ld = d; g.row_mu = e->row_mu[0]; g.row_mu_out = e->row_mu[1]; }
-        if (qp_on(e, ly, n_rows)) { g.Wp = ly.Wqkv8; HIPCHK(e, vc_launch_gemm_qp(g, e->dtype, s)); }
-        else HIPCHK(e, vc_launch_gemm(g, e->dtype, hq_on(e) ? PRO_LNQ : PRO_LNW, EPI_QKV, 1, 1, s));
-      } else if (w == "ffn2") {
-        GemmArgs g = base_args(e, rs, e->p_f2, d, 4 * d);
-        g.Wp = ly.W28; g.bias = ly.b2; g.x_in = e->act; g.x_ld = 4 * d; g.h_in = e->hA; g.h_out = e->hB;
-        if (e->fr_pair && vc_gemm_frp_ok(n_rows, d, 4 * d, e->dtype)) HIPCHK(e, vc_launch_gemm_frp(g, e->dtype, s));
-        else HIPCHK(e, vc_launch_gemm_fr(g, e->dtype, PRO_PLAIN, s));
-      } else {
-        GemmArgs g = base_args(e, rs, e->p_o, d, d);
-        g.Wp = ly.Wo8; g.bias = ly.bo; g.h_in = e->hB; g.h_out = e->hA;
-        if (fr_nsplit(e, n_rows) == 1) { g.x_in = e->xn; g.x_ld = d; HIPCHK(e, vc_launch_gemm_fr(g, e->dtype, PRO_PLAIN, s)); }
-        else { g.att_o = e->att_o; g.att_ml = e->att_ml; g.nsplit = fr_nsplit(e, n_rows); g.att_p16 = (e->att_p16 && e->dtype == VC_DTYPE_BF16) ? 1 : 0; HIPCHK(e, vc_launch_gemm_fr(g, e->dtype, PRO_ATT, s)); }
-      }
-      return VC_OK;
-    }
-    if (w == "ffn1") {
-      GemmArgs g = base_args(e, rs, e->p_f1, 4 * d, d);
-      g.Wp = ly.W1; nt_bit(e, g, NT_F1); g.bias = ly.b1; g.h_in = e->hA; g.h_out = e->hB; g.parts = e->parts; g.n_parts = e->p_o.ksplit;
-      g.prev_bias = ly.bo; g.has_prev_bias = 1; g.wg = ly.wg_1; g.out = e->act; g.out_ld = 4 * d;
-      if (split_ln) { g.x_in = e->xn; g.x_ld = d; HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_RELU, 1, 1, s)); }
-      else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LN, EPI_RELU, 1, 1, s));
-    } else if (w == "ffn2" && fd_one(e, n_rows)) {     // one row, finished by the producer (forward_rows, option fr_one)
-      GemmArgs g = base_args(e, rs, e->p_f2, d, 4 * d);
-      g.Wp = ly.W28; g.bias = ly.b2; g.x_in = e->act; g.x_ld = 4 * d; g.h_in = e->hA; g.h_out = e->hB;
-      HIPCHK(e, vc_launch_gemm_fr1(g, e->dtype, PRO_PLAIN, EPI_RES, s));
-    } else if (w == "ffn2") {
-      GemmArgs g = base_args(e, rs, e->p_f2, d, 4 * d);
-      g.Wp = ly.W2; nt_bit(e, g, NT_F2); g.x_in = e->act; g.x_ld = 4 * d; g.part_out = e->parts;
-      HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_PART, e->p_f2.ksplit, 1, s));
-    } else if (w == "qkv") {
-      GemmArgs g = base_args(e, rs, e->p_qkv, 3 * d, d);
-      g.Wp = ly.Wqkv; nt_bit(e, g, NT_QKV); g.bias = ly.bqkv; g.h_in = e->hB; g.h_out = e->hA; g.parts = e->parts; g.n_parts = e->p_f2.ksplit;
-      g.prev_bias = ly.b2; g.has_prev_bias = 1; g.wg = ly.wg_qkv; g.q_out = e->q; g.kcache = ly.kc; g.vcache = ly.vc;
-      if (fd_one(e, n_rows)) { g.h_out = nullptr; g.n_parts = 0; g.has_prev_bias = 0; }       // the row in hB is finished
-      if (fd_one(e, n_rows) && e->qkv_p8 && ly.Wqkv8 && !split_ln) {                          // ... and the step runs the paired 8-channel form
-        g.Wp = ly.Wqkv8;
-        HIPCHK(e, vc_launch_gemm_fr1(g, e->dtype, PRO_LN, EPI_QKV, s));
-        return VC_OK;
-      }
-      if (split_ln) { g.x_in = e->xn; g.x_ld = d; HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_QKV, 1, 1, s)); }
-      else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LN, EPI_QKV, 1, 1, s));
-    } else if (w == "oproj") {
-      GemmArgs g = base_args(e, rs, e->p_o, d, d);
-      g.Wp = ly.Wo; nt_bit(e, g, NT_O); g.att_o = e->att_o; g.att_ml = e->att_ml; g.nsplit = rs.nsplit; g.part_out = e->parts;
-      HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_ATT, EPI_PART, e->p_o.ksplit, 1, s));
-    } else if (w == "attn") {
-      AttnArgs a;
-      memset(&a, 0, sizeof a);
-      a.q = e->q; a.kcache = ly.kc; a.vcache = ly.vc; a.cache_seq_stride = (long)e->H * e->S_max * e->hd;
-      a.S_max = e->S_max; a.H = e->H; a.hd = e->hd; a.hd_shift = e->hd == 32 ? 5 : e->hd == 64 ? 6 : 7; a.d = d; a.nsplit = rs.nsplit; a.scale = 1.0f / sqrtf((float)e->hd);
-      a.row_seq = rs.row_seq; a.row_pos = rs.row_pos; a.n_rows = rs.n_rows; a.att_o = e->att_o; a.att_ml = e->att_ml;
-      a.n_active = e->one; a.dbg_ts = e->dbg_ts; a.share_len = e->share_len; a.nt = attn_nt_for(e, rs.n_rows);
-      a.fast = e->attn_fast;
-      a.part16 = (e->att_p16 && e->dtype == VC_DTYPE_BF16 && n_rows >= 2 && n_rows <= fr_max_rows(e) && rs.nsplit > 1) ? 1 : 0;    // as forward_rows_fr launches it
-      HIPCHK(e, vc_launch_attn(a, e->dtype, rs.n_rows, s));
-    } else if (w == "pf_ffn1") {      // the prefill pass's FFN up-projection on the MFMA block GEMM (X = xn, n_rows rows)
-      GemmArgs g = base_args(e, rs, e->p_f1, 4 * d, d);
-      g.Wp = ly.W1; nt_bit(e, g, NT_F1); g.bias = ly.b1; g.x_in = e->xn; g.x_ld = d; g.out = e->act; g.out_ld = 4 * d; g.mt = 1;
-      const char* dbg_env = getenv("VC_BLK_DBG");        // tools/blk_probe.py: wrong results by design, timing only
-      vc_blk_dbg_mask = dbg_env ? atoi(dbg_env) : 0;
-      hipError_t le = vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_RELU, 1, 1, s);
-      vc_blk_dbg_mask = 0;
-      HIPCHK(e, le);
-    } else if (w == "pf_qkv") {       // the prefill pass's QKV projection (X = xn; the image option "qkv16" selects)
-      GemmArgs g = base_args(e, rs, e->p_qkv, 3 * d, d);
-      g.Wp = ly.Wqkv; nt_bit(e, g, NT_QKV); g.bias = ly.bqkv; g.x_in = e->xn; g.x_ld = d; g.mt = 1;
-      g.q_out = e->q; g.kcache = ly.kc; g.vcache = ly.vc;
-      g.row_seq = e->pre_row_seq; g.row_pos = e->pre_row_pos;        // sequence 0, positions 0 .. n_rows - 1
-      if (use_qkv16(e, n_rows, 1)) {
-        g.Wp = ly.Wqkv16; g.n_tiles = e->p_qkv16.n_tiles; g.KT = e->p_qkv16.KT; g.nchunk = e->p_qkv16.nchunk;
-        HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_QKV16, 1, 1, s));
-      } else {
-        HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_QKV, 1, 1, s));
-      }
-    } else if (w == "pf_attn") {      // the prefill's MFMA tile attention: n_rows consecutive positions of sequence 0 (16-row tiles)
-      AttnArgs a;
-      memset(&a, 0, sizeof a);
-      a.q = e->q; a.kcache = ly.kc; a.vcache = ly.vc; a.cache_seq_stride = (long)e->H * e->S_max * e->hd;
-      a.S_max = e->S_max; a.H = e->H; a.hd = e->hd; a.hd_shift = e->hd == 32 ? 5 : e->hd == 64 ? 6 : 7; a.d = d; a.nsplit = 1; a.scale = 1.0f / sqrtf((float)e->hd);
-      a.row_seq = e->pre_row_seq; a.row_pos = e->pre_row_pos; a.n_rows = n_rows; a.att_o = e->att_o; a.att_ml = e->att_ml;
-      a.n_active = e->one; a.dbg_ts = e->dbg_ts; a.share_len = e->share_len; a.x_out = e->xn;
-      // (the kernel a prompt of this many rows would get: prefill_batch's rule)
-      if (e->tile_attn == 2 && e->dtype == VC_DTYPE_BF16 && e->hd == 128 && n_rows >= e->tile_attn_min_rows) HIPCHK(e, vc_launch_tile_attn64(a, s));
-      else HIPCHK(e, vc_launch_tile_attn(a, e->dtype, s));
-    } else if (w == "step") {
-      int r = forward_rows(e, rs, s);
-      if (r) return r;
-      return run_heads(e, nullptr, n_rows, 0, nullptr, s);
-    } else {
-      return fail(e, VC_EINVAL, "unknown kernel '%s'", which);
-    }
-    return VC_OK;
+    PassOut po;                                              // "step": forward + heads, sampler excluded
+    const int r = run_pass(e, p, rs, &po, s);
+    return r ? r : run_heads(e, p, po, nullptr, n_rows, 0, 0, nullptr, s);
   };
   for (int i = 0; i < 3; ++i) { rc = one(i); if (rc) return rc; }
   HIPCHK(e, hipEventRecord(e->ev[0], s));
@@ -2227,10 +2031,10 @@ extern "C" int vc_bench_kernel(vc_engine* e, const char* which, int n_rows, int 
     const std::string& w = w2;
     double b = 0;
     if (w == "wd_ffn1") b = 4.0 * d * d * es + n_rows * (d * es + 4.0 * d * es);
-    else if (w == "wd_ffn2") b = 4.0 * d * d * es + n_rows * (4.0 * d * es + d * 4.0 * (use_wd(e, n_rows) ? wd_ksplit(e, d, 4 * d) : e->p_f2.ksplit));
+    else if (w == "wd_ffn2") b = 4.0 * d * d * es + n_rows * (4.0 * d * es + d * 4.0 * p.ks_f2);
     else if (w == "wd_qkv") b = 3.0 * d * d * es + n_rows * (d * es + d * 4.0 + 2.0 * d * es);
-    else if (w == "wd_oproj") b = 1.0 * d * d * es + n_rows * (d * es + d * 4.0 * (use_wd(e, n_rows) ? wd_ksplit(e, d, d) : e->p_o.ksplit));
-    else if (w == "wd_ln") b = n_rows * (d * 4.0 * (2 + (use_wd(e, n_rows) ? wd_ksplit(e, d, d) : e->p_o.ksplit)) + d * es);
+    else if (w == "wd_oproj") b = 1.0 * d * d * es + n_rows * (d * es + d * 4.0 * p.ks_o);
+    else if (w == "wd_ln") b = n_rows * (d * 4.0 * (2 + p.ks_o) + d * es);
     else if (w == "wd_attn") b = n_rows * 2.0 * d * es * (std::min(e->S_max - 1, 883) + 1);
     else if (w == "ffn1") b = 4.0 * d * d * es + n_rows * (d * 4.0 + 4.0 * d * es);
     else if (w == "ffn2") b = 4.0 * d * d * es + n_rows * (4.0 * d * es + d * 4.0);

@@ -447,10 +447,10 @@ class VoiceCraftEngine:
         check(self.lib.vc_set_option(self._h, str(name).encode(), str(value).encode()), self._h, f"vc_set_option({name})")
 
     def options(self) -> str:
-        """The engine's option state as text, `key=v,v,...|key=...`: g = steps per graph, ls = ln_split_rows, ab = attention workgroups
-        aimed at (several rows, one row), nt = (weight mask, K/V rows), fr = finished-row form (max rows, consumer tiles, split rows,
-        paired producer), ta = prefill attention (kernel, min rows), r1 = one-row step (fr_one, ln_trim, attn_fast, qkv_p8), q16 = many-row
-        steps (qkv16, wide_heads, mt_tiles, wide_gemm, wd_stage), sh = shrink.  bench.py turns it into a JSON object (`config.engine_options`)."""
+        """The engine's option state as text, `key=v,v,...|key=...`: g = graph_steps, nt = (weight mask, K/V loads), fr = finished-row
+        forms (finished_rows, fr_pair, att_p16, hq), ta = tile_attn (kernel, min rows), r1 = one-row and attention forms (fr_one,
+        attn_fast, qkv_p8), q16 = many-row steps (qkv16, wide_heads, wide_gemm, wd_stage), sh = shrink.  bench.py turns it into a JSON
+        object (`config.engine_options`)."""
         return bytes(self.debug_read("options", (256,), torch.uint8).tolist()).split(b"\0")[0].decode()
 
     def last_timing_ms(self):
