@@ -189,6 +189,23 @@ int vc_edit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, in
             int64_t* res_dev, int res_cap, int* res_len, float* logits_dev, int logit_steps,
             int* n_steps, void* stream);
 
+/* ---- batched speech editing: B independent inference requests (each with its own text, audio and 1..max_n_spans
+ * spans) decoded as one batch; each request follows vc_edit exactly.  One prefill over all prompts, then ONE decode row
+ * per request: a span switch is fed over three one-row steps instead of vc_edit's 3-row step, so the step stays B rows
+ * wide and shrinks as requests retire (option "shrink").  Sampling config shared by the whole call.
+ *   x_dev int64 [sum Lx], y_dev int64 [sum T][K] concatenated; x_off / y_off host int32 [B+1] (as vc_tts_multi)
+ *   mask_intervals host int32 [sum M_i][2], span_off host int32 [B+1]; request i's 2*M_i mask values start at
+ *     mask_values + 2*span_off[i] (as vc_eval_forward's spans)
+ *   res_dev int64 [B][K][res_cap]; res_len host [B]
+ *   forced_dev / logits_dev: [step][B][K](...), indexed by each request's own sampled steps (feed steps are not steps)
+ *   B > max_seqs: VC_ECAP.  A request's bad input fails the call with a message naming the request ("request 2: ..."). */
+int vc_edit_multi(vc_engine* e, int B, const int64_t* x_dev, const int32_t* x_off,
+                  const int64_t* y_dev, const int32_t* y_off,
+                  const int32_t* mask_intervals, const int32_t* span_off, const int32_t* mask_values,
+                  const vc_sample_cfg* sc, const int64_t* forced_dev, int n_forced,
+                  int64_t* res_dev, int res_cap, int* res_len, float* logits_dev, int logit_steps,
+                  int* n_steps, void* stream);
+
 /* ---- the training objective, teacher-forced: VoiceCraft.forward (models/voicecraft.py:472-559) for B utterances
  * whose mask intervals are GIVEN (the reference draws them at random, :198-237): rearrange / delay-shift / mask
  * placeholders (:239-320), one non-cached decoder pass over [text ; rearranged audio] of every utterance (:501-512;

@@ -186,6 +186,9 @@ struct SeqState {
   int mask_value[VC_MAX_SPANS];   // mask_embedding row inserted before span i (i >= 1)
   int slot;          // the sequence's index in the CALL (= its KV-cache slot, its rows of the gen / forced / logits_out buffers, its Philox
                      // stream); equal to its state's index until a wide batch is re-packed onto fewer rows (vc_tokens.hip repack_k)
+  int feed_switch;   // 1: a span switch is fed as three ONE-row steps (vc_edit_multi, one row per sequence); 0: one 3-row step (vc_edit)
+  int feed;          // rows of the current span switch still to be fed (2: the mask_embedding row, 1: the all-empty column); the
+                     // sampler block of such a step draws nothing and logs nothing (vc_tokens.hip advance_phase)
 };
 
 // ---------------------------------------------------------------- kernel argument blocks

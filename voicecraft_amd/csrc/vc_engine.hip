@@ -1385,6 +1385,33 @@ namespace {
 
 struct TtsJob { const int64_t* x; int Lx; const int64_t* y; int T; };
 
+// After a one-row-per-sequence decode loop: the final states by slot into h_st[0, B) and the call's re-pack count (host_ms[6]).
+// Shared by tts_run and vc_edit_multi.
+int collect_states(vc_engine* e, int B, hipStream_t s) {
+  if (!e->repack_at.empty()) HIPCHK(e, hipMemcpyAsync(e->h_flag + 11, e->step_ctr, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (e->cur_rows == B) {
+    HIPCHK(e, hipMemcpyAsync(e->h_st, e->st, sizeof(SeqState) * B, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+  } else {      // the batch was re-packed onto fewer rows on the way: final states = the parked ones + the rows of the last layout, by slot
+    const int Bc = e->cur_rows;
+    HIPCHK(e, hipMemcpyAsync(e->h_st, e->st_fin, sizeof(SeqState) * B, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(e->h_st2, e->st, sizeof(SeqState) * Bc, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    for (int r = 0; r < Bc; ++r) {
+      const int slot = e->h_st2[r].slot;
+      if (slot >= 0 && slot < B) e->h_st[slot] = e->h_st2[r];
+    }
+    const int rc = check_err_flag(e, s);
+    if (rc) return rc;
+  }
+  // re-packs of this call: those that moved live sequences, i.e. the one queued before batch k counts when the loop's live steps
+  // (step_ctr stops at the last one) reach into batch k.  Whether the host queues one more after the last sequence has retired
+  // depends on how far it trails the device, so that one is not counted and the figure is the same in every run
+  for (int k : e->repack_at)
+    if (e->h_flag[11] > k * std::max(1, e->steps_per_graph)) e->host_ms[6] += 1;
+  return VC_OK;
+}
+
 // Shared by vc_tts (one prompt, n_samples >= 1) and vc_tts_multi (B prompts).
 int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const vc_sample_cfg* sc,
             const int64_t* forced, int n_forced, float* logits_out, int logit_steps, int* steps_out,
@@ -1478,27 +1505,8 @@ int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const 
   rc = decode_loop(e, sa, B, 1, grouped, sc, max_steps, &steps_run, s);
   if (rc) return rc;
   HIPCHK(e, hipEventRecord(e->ev[2], s));
-  if (!e->repack_at.empty()) HIPCHK(e, hipMemcpyAsync(e->h_flag + 11, e->step_ctr, sizeof(int), hipMemcpyDeviceToHost, s));
-  if (e->cur_rows == B) {
-    HIPCHK(e, hipMemcpyAsync(e->h_st, e->st, sizeof(SeqState) * B, hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-  } else {      // the batch was re-packed onto fewer rows on the way: final states = the parked ones + the rows of the last layout, by slot
-    const int Bc = e->cur_rows;
-    HIPCHK(e, hipMemcpyAsync(e->h_st, e->st_fin, sizeof(SeqState) * B, hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipMemcpyAsync(e->h_st2, e->st, sizeof(SeqState) * Bc, hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-    for (int r = 0; r < Bc; ++r) {
-      const int slot = e->h_st2[r].slot;
-      if (slot >= 0 && slot < B) e->h_st[slot] = e->h_st2[r];
-    }
-    rc = check_err_flag(e, s);
-    if (rc) return rc;
-  }
-  // re-packs of this call: those that moved live sequences, i.e. the one queued before batch k counts when the loop's live steps
-  // (step_ctr stops at the last one) reach into batch k.  Whether the host queues one more after the last sequence has retired
-  // depends on how far it trails the device, so that one is not counted and the figure is the same in every run
-  for (int k : e->repack_at)
-    if (e->h_flag[11] > k * std::max(1, e->steps_per_graph)) e->host_ms[6] += 1;
+  rc = collect_states(e, B, s);
+  if (rc) return rc;
   HIPCHK(e, hipEventElapsedTime(&e->ms[0], e->ev[0], e->ev[1]));
   HIPCHK(e, hipEventElapsedTime(&e->ms[1], e->ev[1], e->ev[2]));
   e->ms[2] = e->ms[0] + e->ms[1];
@@ -1584,38 +1592,44 @@ extern "C" int vc_tts_multi(vc_engine* e, int B, const int64_t* x_dev, const int
 }
 
 // ------------------------------------------------------------------------------------- editing
-extern "C" int vc_edit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
-                       const int32_t* mask_intervals, int M, const int32_t* mask_values,
-                       const vc_sample_cfg* sc, const int64_t* forced_dev, int n_forced,
-                       int64_t* res_dev, int res_cap, int* res_len, float* logits_dev, int logit_steps,
-                       int* n_steps, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
-  if (!x_dev || !y_dev || !mask_intervals || !mask_values || !sc || !res_dev || !res_len)
-    return fail(e, VC_EINVAL, "null argument to vc_edit");
-  if (M < 1 || M > e->cfg.max_n_spans || 2 * M + 1 > VC_MAX_SPANS * 2 + 1)
-    return fail(e, VC_EINVAL, "number of spans %d outside [1,%d]", M, e->cfg.max_n_spans);
-  if (Lx < 1 || T < 1) return fail(e, VC_EINVAL, "empty text or audio");
-  hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
-  const int K = e->K;
+namespace {
+
+// One editing request: its inputs, the prefill's segment table (PromptArgs) and its budget of sampled steps.
+struct EditJob {
+  const int64_t* x; int Lx; const int64_t* y; int T;
+  const int32_t* iv; int M; const int32_t* mv;     // mask intervals [M][2], mask values [2M]
+  std::vector<int> ns, ne;                          // the M + 1 non-masked pieces
+  PromptArgs pa;
+  int max_steps;
+};
+
+// Validation, segment table and step budget of one request (vc_edit, vc_edit_multi; `who` prefixes every message).
+int edit_prepare(vc_engine* e, EditJob& j, const char* who) {
+  const int K = e->K, M = j.M, Lx = j.Lx, T = j.T;
   const vc_model_cfg& c = e->cfg;
-  if (c.eos > 0 && !c.reduced_eog) return fail(e, VC_EINVAL, "eos > 0 requires reduced_eog (voicecraft.py:244)");
+  if (M < 1 || M > c.max_n_spans || 2 * M + 1 > VC_MAX_SPANS * 2 + 1)
+    return fail(e, VC_EINVAL, "%snumber of spans %d outside [1,%d]", who, M, c.max_n_spans);
+  if (Lx < 1 || T < 1) return fail(e, VC_EINVAL, "%sempty text or audio", who);
+  if (c.eos > 0 && !c.reduced_eog) return fail(e, VC_EINVAL, "%seos > 0 requires reduced_eog (voicecraft.py:244)", who);
   // non-mask intervals (voicecraft.py:620-628)
-  std::vector<int> ns(M + 1), ne(M + 1);
+  std::vector<int>& ns = j.ns;
+  std::vector<int>& ne = j.ne;
+  ns.assign(M + 1, 0); ne.assign(M + 1, 0);
   for (int i = 0; i <= M; ++i) {
-    ns[i] = (i == 0) ? 0 : mask_intervals[2 * (i - 1) + 1];
-    ne[i] = (i == M) ? T : mask_intervals[2 * i];
-    if (ns[i] < 0 || ne[i] > T || ne[i] < ns[i]) return fail(e, VC_EINVAL, "mask intervals must be ordered, disjoint and inside [0,%d]", T);
+    ns[i] = (i == 0) ? 0 : j.iv[2 * (i - 1) + 1];
+    ne[i] = (i == M) ? T : j.iv[2 * i];
+    if (ns[i] < 0 || ne[i] > T || ne[i] < ns[i])
+      return fail(e, VC_EINVAL, "%smask intervals must be ordered, disjoint and inside [0,%d]", who, T);
   }
   for (int i = 0; i < M; ++i)
-    if (mask_intervals[2 * i + 1] < mask_intervals[2 * i]) return fail(e, VC_EINVAL, "mask interval %d is reversed", i);
+    if (j.iv[2 * i + 1] < j.iv[2 * i]) return fail(e, VC_EINVAL, "%smask interval %d is reversed", who, i);
   for (int i = 0; i < 2 * M; ++i)
-    if (mask_values[i] < 0 || mask_values[i] >= c.max_n_spans) return fail(e, VC_EINVAL, "mask value out of range");
+    if (j.mv[i] < 0 || j.mv[i] >= c.max_n_spans) return fail(e, VC_EINVAL, "%smask value out of range", who);
   // segments of the prefill: every non-mask piece (delay-shifted, K extra columns), a mask
   // placeholder after each of them, and the first all-empty column of the first masked piece
   // (rearrange :239-252, shift :254-262, insert_mask :264-288, the cut at :672-679)
-  PromptArgs pa;
-  fill_prompt_common(e, pa, x_dev, Lx, y_dev, T);
+  PromptArgs& pa = j.pa;
+  fill_prompt_common(e, pa, j.x, Lx, j.y, T);
   int col = 0, nseg = 0;
   for (int i = 0; i <= M; ++i) {
     int term = -1;
@@ -1624,10 +1638,10 @@ extern "C" int vc_edit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t
     else term = c.eog;
     const int n = (ne[i] - ns[i]) + (term >= 0 ? 1 : 0);
     if (n <= 0)   // the reference raises IndexError here (codebooks_patterns.py:174 on a zero-length piece)
-      return fail(e, VC_EINVAL, "non-masked piece %d is empty (a span may not start at frame 0)", i);
+      return fail(e, VC_EINVAL, "%snon-masked piece %d is empty (a span may not start at frame 0)", who, i);
     pa.seg[nseg++] = Segment{col, n + K, ns[i], ne[i] - ns[i], term, -1};
     col += n + K;
-    pa.seg[nseg++] = Segment{col, 1, 0, 0, -1, mask_values[i]};
+    pa.seg[nseg++] = Segment{col, 1, 0, 0, -1, j.mv[i]};
     col += 1;
   }
   pa.seg[nseg++] = Segment{col, 1, 0, 0, -1, -1};   // s = 0 of the first masked piece: all `empty`
@@ -1638,22 +1652,71 @@ extern "C" int vc_edit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t
   {   // as in tts_run: clamp to the room there is; running out of it is reported after the loop
     const int room = e->S_max - (Lx + col) - 3 * M - 1;
     if (room < M * (K + 1))
-      return fail(e, VC_ECAP, "editing: the rearranged prompt alone takes %d of max_positions %d", Lx + col, e->S_max);
+      return fail(e, VC_ECAP, "%sediting: the rearranged prompt alone takes %d of max_positions %d", who, Lx + col, e->S_max);
     max_steps = std::min(std::min(max_steps, room), e->gen_cap);
   }
+  j.max_steps = max_steps;
+  return VC_OK;
+}
+
+// The request's first state: more_mask_value (:676) per span switch.
+SeqState edit_state(vc_engine* e, const EditJob& j) {
+  SeqState st = init_state(e, j.Lx, j.pa.n_cols, false, j.M);
+  for (int i = 1; i < j.M; ++i) st.mask_value[i] = j.mv[j.M + i];
+  return st;
+}
+
+// res = nonmask_0, gen_0, nonmask_1, gen_1, ..., nonmask_M (voicecraft.py:890-898) from the request's final state and gen rows.
+int edit_assemble(vc_engine* e, const EditJob& j, const SeqState& fs, const int* gen, int64_t* res, int res_cap, int* res_len,
+                  hipStream_t s, const char* who) {
+  const int K = e->K, M = j.M;
+  if (!fs.done || fs.span < M)
+    return fail(e, VC_ECAP, "%sediting ran out of room before it terminated (max_positions %d): raise max_positions", who, e->S_max);
+  AssembleArgs a;
+  memset(&a, 0, sizeof a);
+  a.y = j.y; a.gen = gen; a.K = K; a.T = j.T; a.res_cap = res_cap; a.res = res;
+  int dst = 0, g0 = 0;
+  for (int i = 0; i <= M; ++i) {
+    if (j.ne[i] > j.ns[i]) { int p = a.n_piece++; a.kind[p] = 0; a.src0[p] = j.ns[i]; a.len[p] = j.ne[i] - j.ns[i]; a.dst0[p] = dst; dst += j.ne[i] - j.ns[i]; }
+    if (i < M) {
+      const int N = fs.span_steps[i], Tg = N - K;
+      if (Tg < 0) return fail(e, VC_ESTATE, "%sinternal: span of %d steps", who, N);
+      if (Tg > 0) { int p = a.n_piece++; a.kind[p] = 1; a.src0[p] = g0; a.len[p] = Tg; a.dst0[p] = dst; dst += Tg; }
+      g0 += N;
+    }
+  }
+  if (dst > res_cap) return fail(e, VC_ECAP, "%sres capacity %d < %d", who, res_cap, dst);
+  HIPCHK(e, vc_launch_assemble(a, s));
+  *res_len = dst;
+  return VC_OK;
+}
+
+}  // namespace
+
+extern "C" int vc_edit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
+                       const int32_t* mask_intervals, int M, const int32_t* mask_values,
+                       const vc_sample_cfg* sc, const int64_t* forced_dev, int n_forced,
+                       int64_t* res_dev, int res_cap, int* res_len, float* logits_dev, int logit_steps,
+                       int* n_steps, void* stream) {
+  int rc = check_ready(e);
+  if (rc) return rc;
+  if (!x_dev || !y_dev || !mask_intervals || !mask_values || !sc || !res_dev || !res_len)
+    return fail(e, VC_EINVAL, "null argument to vc_edit");
+  EditJob j{x_dev, Lx, y_dev, T, mask_intervals, M, mask_values};
+  if ((rc = edit_prepare(e, j, ""))) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+  const int max_steps = j.max_steps;
   {   // decode graphs of a first call of this shape: captured ahead of both timers (as in tts_run)
     SampleArgs sa0 = make_sample_args(e, 1, (M > 1) ? 3 : 1);
     if ((rc = decode_loop(e, sa0, 1, (M > 1) ? 3 : 1, false, sc, max_steps, nullptr, s, true))) return rc;
   }
   HIPCHK(e, hipEventRecord(e->ev[0], s));
   {
-    std::vector<PromptArgs> pas(1, pa);
+    std::vector<PromptArgs> pas(1, j.pa);
     rc = prefill_batch(e, pas, std::vector<int>(1, 0), s);
     if (rc) return rc;
   }
-  SeqState st = init_state(e, Lx, col, false, M);
-  for (int i = 1; i < M; ++i) st.mask_value[i] = mask_values[M + i];   // more_mask_value (:676)
-  e->h_st[0] = st;
+  e->h_st[0] = edit_state(e, j);
   HIPCHK(e, hipMemcpyAsync(e->st, e->h_st, sizeof(SeqState), hipMemcpyHostToDevice, s));
   e->h_flag[1] = 1;
   e->h_flag[8] = 1;
@@ -1677,27 +1740,94 @@ extern "C" int vc_edit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t
   e->ms[2] = e->ms[0] + e->ms[1];
   if (n_steps) *n_steps = e->h_st[0].total_steps;
   (void)steps_run;
-  const SeqState& fs = e->h_st[0];
-  if (!fs.done || fs.span < M)
-    return fail(e, VC_ECAP, "editing ran out of room before it terminated (max_positions %d): raise max_positions", e->S_max);
-  // res = nonmask_0, gen_0, nonmask_1, gen_1, ..., nonmask_M (voicecraft.py:890-898)
-  AssembleArgs a;
-  memset(&a, 0, sizeof a);
-  a.y = y_dev; a.gen = e->gen; a.K = K; a.T = T; a.res_cap = res_cap; a.res = res_dev;
-  int dst = 0, g0 = 0;
-  for (int i = 0; i <= M; ++i) {
-    if (ne[i] > ns[i]) { int p = a.n_piece++; a.kind[p] = 0; a.src0[p] = ns[i]; a.len[p] = ne[i] - ns[i]; a.dst0[p] = dst; dst += ne[i] - ns[i]; }
-    if (i < M) {
-      const int N = fs.span_steps[i], Tg = N - K;
-      if (Tg < 0) return fail(e, VC_ESTATE, "internal: span of %d steps", N);
-      if (Tg > 0) { int p = a.n_piece++; a.kind[p] = 1; a.src0[p] = g0; a.len[p] = Tg; a.dst0[p] = dst; dst += Tg; }
-      g0 += N;
-    }
-  }
-  if (dst > res_cap) return fail(e, VC_ECAP, "res capacity %d < %d", res_cap, dst);
-  HIPCHK(e, vc_launch_assemble(a, s));
+  rc = edit_assemble(e, j, e->h_st[0], e->gen, res_dev, res_cap, res_len, s, "");
+  if (rc) return rc;
   HIPCHK(e, hipStreamSynchronize(s));
-  *res_len = dst;
+  return VC_OK;
+}
+
+// B editing requests as one batch: ONE prefill over all their prompts, then one decode row per request.  A span switch is fed as
+// three one-row steps (SeqState.feed_switch, vc_tokens.hip advance_phase) instead of vc_edit's 3-row step, so a step stays B rows
+// wide and the batch re-packs onto narrower steps as requests retire, as in vc_tts_multi.
+extern "C" int vc_edit_multi(vc_engine* e, int B, const int64_t* x_dev, const int32_t* x_off,
+                             const int64_t* y_dev, const int32_t* y_off,
+                             const int32_t* mask_intervals, const int32_t* span_off, const int32_t* mask_values,
+                             const vc_sample_cfg* sc, const int64_t* forced_dev, int n_forced,
+                             int64_t* res_dev, int res_cap, int* res_len, float* logits_dev, int logit_steps,
+                             int* n_steps, void* stream) {
+  int rc = check_ready(e);
+  if (rc) return rc;
+  if (B < 1 || !x_dev || !x_off || !y_dev || !y_off || !mask_intervals || !span_off || !mask_values || !sc || !res_dev || !res_len)
+    return fail(e, VC_EINVAL, "null/invalid argument to vc_edit_multi");
+  if (B > e->B_max) return fail(e, VC_ECAP, "%d requests, the engine was created for max_seqs %d", B, e->B_max);
+  const int K = e->K;
+  std::vector<EditJob> jobs(B);
+  std::vector<std::string> who(B);
+  int loop_steps = 0;
+  for (int b = 0; b < B; ++b) {
+    char buf[32];
+    snprintf(buf, sizeof buf, "request %d: ", b);
+    who[b] = buf;
+    if (x_off[b] < 0 || y_off[b] < 0 || span_off[b] < 0) return fail(e, VC_EINVAL, "%snegative offset", buf);
+    EditJob& j = jobs[b];
+    j.x = x_dev + x_off[b]; j.Lx = x_off[b + 1] - x_off[b];
+    j.y = y_dev + (size_t)y_off[b] * K; j.T = y_off[b + 1] - y_off[b];
+    j.iv = mask_intervals + 2 * (size_t)span_off[b]; j.M = span_off[b + 1] - span_off[b];
+    j.mv = mask_values + 2 * (size_t)span_off[b];
+    if ((rc = edit_prepare(e, j, buf))) return rc;
+    loop_steps = std::max(loop_steps, j.max_steps + 2 * (j.M - 1));     // + the two feed steps of every span switch
+  }
+  hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+  {   // decode graphs (width B and the narrower widths a shrinking batch passes through): ahead of both timers, as in tts_run
+    SampleArgs sa0 = make_sample_args(e, B, 1);
+    if ((rc = decode_loop(e, sa0, B, 1, false, sc, loop_steps, nullptr, s, true))) return rc;
+  }
+  HIPCHK(e, hipEventRecord(e->ev[0], s));
+  {
+    std::vector<PromptArgs> pas(B);
+    std::vector<int> slots(B);
+    for (int b = 0; b < B; ++b) { pas[b] = jobs[b].pa; slots[b] = b; }
+    rc = prefill_batch(e, pas, slots, s);
+    if (rc) return rc;
+  }
+  for (int b = 0; b < B; ++b) {
+    e->h_st[b] = edit_state(e, jobs[b]);
+    e->h_st[b].slot = b;
+    e->h_st[b].feed_switch = 1;
+  }
+  HIPCHK(e, hipMemcpyAsync(e->st, e->h_st, sizeof(SeqState) * B, hipMemcpyHostToDevice, s));
+  HIPCHK(e, hipMemsetAsync(e->st_fin, 0, sizeof(SeqState) * B, s));
+  e->h_flag[1] = B;
+  e->h_flag[8] = B;
+  e->h_flag[9] = B; e->h_flag[10] = B;        // the two slots of "sequences still live" (SampleArgs.host_live)
+  e->host_ms[6] = 0;
+  HIPCHK(e, hipMemcpyAsync(e->n_active, e->h_flag + 1, sizeof(int), hipMemcpyHostToDevice, s));
+  rc = push_sample_dyn(e, sc, forced_dev, n_forced, logits_dev, logit_steps, B, s);
+  if (rc) return rc;
+  rc = check_err_flag(e, s);
+  if (rc) return rc;
+  SampleArgs sa = make_sample_args(e, B, 1);
+  HIPCHK(e, vc_launch_sample(sa, false, s));
+  HIPCHK(e, hipEventRecord(e->ev[1], s));
+  rc = decode_loop(e, sa, B, 1, false, sc, loop_steps, nullptr, s);
+  if (rc) return rc;
+  HIPCHK(e, hipEventRecord(e->ev[2], s));
+  rc = collect_states(e, B, s);
+  if (rc) return rc;
+  HIPCHK(e, hipEventElapsedTime(&e->ms[0], e->ev[0], e->ev[1]));
+  HIPCHK(e, hipEventElapsedTime(&e->ms[1], e->ev[1], e->ev[2]));
+  e->ms[2] = e->ms[0] + e->ms[1];
+  if (n_steps) {   // sampled steps of the longest request (feed steps not counted)
+    int m = 0;
+    for (int b = 0; b < B; ++b) m = std::max(m, e->h_st[b].total_steps);
+    *n_steps = m;
+  }
+  for (int b = 0; b < B; ++b) {
+    rc = edit_assemble(e, jobs[b], e->h_st[b], e->gen + (size_t)b * e->gen_cap * K, res_dev + (size_t)b * K * res_cap, res_cap,
+                       &res_len[b], s, who[b].c_str());
+    if (rc) return rc;
+  }
+  HIPCHK(e, hipStreamSynchronize(s));
   return VC_OK;
 }
 

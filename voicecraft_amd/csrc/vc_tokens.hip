@@ -332,8 +332,8 @@ __device__ __forceinline__ void sample_phase(const SampleArgs& a, const SampleDy
   // the fields this phase reads, fetched from LDS in one go
   const int st_done = sp->done, step = sp->total_steps, term = sp->term_token, kill = sp->kill_token, n_eog = sp->n_eog;
   const int min_gen = sp->min_gen, cur_num_gen = sp->cur_num_gen, prev_token = sp->prev_token, consec = sp->consec_silence;
-  const int y_len = sp->y_len, cap_len = sp->cap_len, slot = sp->slot;
-  if (st_done) return;
+  const int y_len = sp->y_len, cap_len = sp->cap_len, slot = sp->slot, feed = sp->feed;
+  if (st_done || feed) return;              // (a feed step of a span switch: the reference does not sample those logits)
   const int V = a.V;
   const int VP = ((V + 63) >> 6) << 6;
   for (int k = wave; k < a.K; k += 4) {
@@ -410,7 +410,7 @@ __device__ __forceinline__ void sample_phase(const SampleArgs& a, const SampleDy
 // the next decode rows (embedding sum + position, voicecraft.py:1102-1116; span switch :838-858).
 __device__ void advance_phase(const SampleArgs& a, const SampleDyn& dy, int b, bool grouped, SeqState* sp, const int* xs) {
   __shared__ int s_tok[VC_MAX_CODEBOOKS];
-  __shared__ int s_mode;     // 0: row inactive, 1: one new row, 3: span switch (three rows)
+  __shared__ int s_mode;     // 0: row inactive, 1: one new row, 3: span switch (three rows), 4 / 5: a feed step of a switch (SeqState.feed)
   __shared__ int s_ylen, s_mask, s_Lx;
   const int tid = threadIdx.x;
   const int K = a.K;
@@ -419,8 +419,16 @@ __device__ void advance_phase(const SampleArgs& a, const SampleDyn& dy, int b, b
     const int done0 = sp->done, Lx = sp->Lx, term = sp->term_token, group = sp->group, n_spans = sp->n_spans, slot = sp->slot;
     int n_eog = sp->n_eog, cur = sp->cur_num_gen, prev = sp->prev_token, consec = sp->consec_silence;
     int span = sp->span, total = sp->total_steps, y_len = sp->y_len;
+    const int feed = sp->feed;
     int mode = 0, mask = 0, ylen_row = y_len;
-    if (!done0) {
+    if (!done0 && feed) {
+      // rows 2 and 3 of a span switch fed on steps of their own (the state already counts all three positions): the
+      // mask_embedding row of the new span, then the all-empty column.  Nothing was drawn: no gen row, no counter moves
+      mode = 6 - feed;
+      mask = sp->mask_value[span];
+      ylen_row = y_len - feed;
+      sp->feed = feed - 1;
+    } else if (!done0) {
       int tok[VC_MAX_CODEBOOKS];
 #pragma unroll
       for (int k = 0; k < VC_MAX_CODEBOOKS; ++k) tok[k] = (k < K) ? xs[k] : 0;
@@ -488,6 +496,7 @@ __device__ void advance_phase(const SampleArgs& a, const SampleDyn& dy, int b, b
           y_len += 3;
           prev = -1;
           consec = 0;
+          if (sp->feed_switch) { mode = 1; sp->feed = 2; }   // one row per sequence: the other two rows follow on the next two steps
         }
       } else if (total >= dy.max_steps || Lx + y_len + 1 > a.max_positions) {   // capacity guard (never hit when sized right)
         done = 1;
@@ -524,7 +533,7 @@ __device__ void advance_phase(const SampleArgs& a, const SampleDyn& dy, int b, b
   const float* pe0 = a.pe + (long)ylen * d;
   const int nq = d >> 2;
   // two columns per thread and pass (d = 2048: the whole row in ONE round trip instead of two dependent ones)
-  for (int i = tid; i < nq; i += 2 * blockDim.x) {
+  for (int i = tid; i < nq && mode <= 3; i += 2 * blockDim.x) {
     const int i2 = i + blockDim.x;
     const bool two = i2 < nq;
     const int j2 = two ? i2 : i;
@@ -555,11 +564,13 @@ __device__ void advance_phase(const SampleArgs& a, const SampleDyn& dy, int b, b
     *reinterpret_cast<float4*>(h0 + i * 4) = va;
     if (two) *reinterpret_cast<float4*>(h0 + i2 * 4) = vb;
   }
-  if (mode == 3) {   // span switch: [last token, mask_embedding[next span], all-empty column] (voicecraft.py:838-858)
+  if (mode >= 3) {   // span switch: [last token, mask_embedding[next span], all-empty column] (voicecraft.py:838-858)
+    // (a feed step, mode 4 / 5, writes the second / the third of these rows as its only row)
+    const int o_m = (mode == 3) ? d : 0, o_e = (mode == 3) ? 2 * d : 0;
     for (int i = tid; i < nq; i += blockDim.x) {
       const float4 mk = *reinterpret_cast<const float4*>(a.mask_emb + (long)s_mask * d + i * 4);
-      const float4 p1 = *reinterpret_cast<const float4*>(pe0 + d + i * 4);
-      const float4 p2 = *reinterpret_cast<const float4*>(pe0 + 2 * d + i * 4);
+      const float4 p1 = *reinterpret_cast<const float4*>(pe0 + o_m + i * 4);
+      const float4 p2 = *reinterpret_cast<const float4*>(pe0 + o_e + i * 4);
       float4 v = *reinterpret_cast<const float4*>(a.audio_emb + ((long)a.empty_token) * d + i * 4);
 #pragma unroll 1
       for (int k = 1; k < K; ++k) {
@@ -569,8 +580,11 @@ __device__ void advance_phase(const SampleArgs& a, const SampleDyn& dy, int b, b
       float4 o1, o2;
       o1.x = mk.x + a.alpha_audio * p1.x; o1.y = mk.y + a.alpha_audio * p1.y; o1.z = mk.z + a.alpha_audio * p1.z; o1.w = mk.w + a.alpha_audio * p1.w;
       o2.x = v.x + a.alpha_audio * p2.x; o2.y = v.y + a.alpha_audio * p2.y; o2.z = v.z + a.alpha_audio * p2.z; o2.w = v.w + a.alpha_audio * p2.w;
-      *reinterpret_cast<float4*>(h0 + d + i * 4) = o1;
-      *reinterpret_cast<float4*>(h0 + 2 * d + i * 4) = o2;
+      // both rows final in registers before the first store (the stores are predicated: a value first consumed inside one would
+      // make that store wait for every load in flight, behind the other store)
+      asm volatile("" : "+v"(o1.x), "+v"(o1.y), "+v"(o1.z), "+v"(o1.w), "+v"(o2.x), "+v"(o2.y), "+v"(o2.z), "+v"(o2.w));
+      if (mode != 5) *reinterpret_cast<float4*>(h0 + o_m + i * 4) = o1;
+      if (mode != 4) *reinterpret_cast<float4*>(h0 + o_e + i * 4) = o2;
     }
   }
 }
@@ -689,7 +703,9 @@ hipError_t vc_launch_sample(const SampleArgs& a, bool grouped, hipStream_t s) {
 // narrower launch form, the host's decode loop queues this kernel between two graphs: the live sequences move - in their order - to rows
 // [0, n_live) (state, next input row, row tables), rows [n_live, B_new) become inactive fillers, and the final states of the retired
 // ones are parked in st_fin[slot].  Everything per-SEQUENCE (KV cache, gen log, forced / logits_out rows, Philox stream) is
-// indexed by SeqState.slot and does not move.  One workgroup; runs a handful of times per call.
+// indexed by SeqState.slot and does not move.  A sequence in the middle of a one-row span switch (vc_edit_multi, SeqState.feed) moves
+// like any other: its pending row and position travel with it, and the rows still to be fed are built from its state alone.
+// One workgroup; runs a handful of times per call.
 __global__ __launch_bounds__(256) void repack_k(const RepackArgs a) {
   __shared__ SeqState s_st[VC_MAX_SEQS];
   __shared__ int s_src[VC_MAX_SEQS], s_pos[VC_MAX_SEQS], s_live;

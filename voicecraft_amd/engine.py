@@ -398,21 +398,9 @@ class VoiceCraftEngine:
         K = self.args.n_codebooks
         ivs = [(int(a), int(b)) for a, b in mask_interval[0].tolist()]
         M = len(ivs)
-        # insert_mask (models/voicecraft.py:264-288): which mask_embedding row each placeholder uses
-        emb_inds = list(range(int(self.args.max_n_spans)))
-        if getattr(self.args, "shuffle_mask_embedding", 0):
-            random.shuffle(emb_inds)
-        use = emb_inds[:M]
-        assert len(use) == M, f"{M} spans but max_n_spans is {self.args.max_n_spans}"
-        mask_value = use + use
-        # a zero-length piece makes the reference raise inside build_pattern_sequence (codebooks_patterns.py:174)
-        starts = [iv[0] for iv in ivs] + [T]
-        ends = [0] + [iv[1] for iv in ivs]
-        eos, reduced = self.args.eos, int(getattr(self.args, "reduced_eog", 0) or 0)
-        for i, (s, e) in enumerate(zip(ends, starts)):
-            has_term = (i == M) if (eos > 0 or reduced) else True
-            if e - s + int(has_term) <= 0:
-                raise IndexError("index is out of bounds for dimension with size 0 (zero-length non-masked piece)")
+        # insert_mask (models/voicecraft.py:264-288): which mask_embedding row each placeholder uses; a zero-length piece
+        # makes the reference raise inside build_pattern_sequence (codebooks_patterns.py:174)
+        mask_value = self._edit_layout(ivs, T)
         sc = self._sample_cfg(top_k, top_p, temperature, stop_repetition, silence_tokens, _seed, _forced_mode)
         flat = [v for iv in ivs for v in iv]
         iv_arr = (C.c_int32 * (2 * M))(*flat)
@@ -438,6 +426,90 @@ class VoiceCraftEngine:
         if logits is not None:
             return out, logits
         return out
+
+    def _edit_layout(self, ivs, T: int, who: str = ""):
+        """The per-request part of `inference`: insert_mask's mask_value list (models/voicecraft.py:264-288; one
+        `shuffle_mask_embedding` draw per call) and the zero-length-piece IndexError of codebooks_patterns.py:174."""
+        M = len(ivs)
+        emb_inds = list(range(int(self.args.max_n_spans)))
+        if getattr(self.args, "shuffle_mask_embedding", 0):
+            random.shuffle(emb_inds)
+        use = emb_inds[:M]
+        assert len(use) == M, f"{who}{M} spans but max_n_spans is {self.args.max_n_spans}"
+        starts = [iv[0] for iv in ivs] + [T]
+        ends = [0] + [iv[1] for iv in ivs]
+        eos, reduced = self.args.eos, int(getattr(self.args, "reduced_eog", 0) or 0)
+        for i, (s, e) in enumerate(zip(ends, starts)):
+            has_term = (i == M) if (eos > 0 or reduced) else True
+            if e - s + int(has_term) <= 0:
+                raise IndexError(f"{who}index is out of bounds for dimension with size 0 (zero-length non-masked piece)")
+        return use + use
+
+    @torch.no_grad()
+    def inference_multi(self, xs, ys, mask_intervals, top_k: int = -100, top_p: float = 1.0, temperature: float = 1.0,
+                        stop_repetition: int = -1, silence_tokens: Iterable[int] = (1388, 1898, 131), _seed=None,
+                        _forced=None, _forced_mode: str = "tokens", _logit_steps: int = 0):
+        """B speech-editing requests as one batch (not in the reference; include/vc_engine.h vc_edit_multi): each follows
+        `inference` exactly.  xs: list of int64 [Lx_i]; ys: list of time-major [T_i,K]; mask_intervals: list of per-request
+        (start, end) pair lists or [1,M_i,2] tensors.  Returns a list of res [1,K,T'_i] (+ the raw head logits [steps,B,K,V]
+        when _logit_steps > 0).  Sampling parameters are shared by the whole call."""
+        B = len(xs)
+        assert B >= 1 and B == len(ys) == len(mask_intervals), (B, len(ys), len(mask_intervals))
+        K = self.args.n_codebooks
+        xl = [torch.as_tensor(v, dtype=torch.int64).reshape(-1) for v in xs]
+        yl = [torch.as_tensor(v, dtype=torch.int64).reshape(-1, K) for v in ys]
+        xcat = torch.cat(xl).to(self.device).contiguous()
+        ycat = torch.cat(yl).to(self.device).contiguous()
+        if self.args.special_first:
+            ycat = ycat + int(self.args.n_special)
+        xo, yo, so, flat, mvals = [0], [0], [0], [], []
+        cap = 0
+        for b, (xv, yv, mi) in enumerate(zip(xl, yl, mask_intervals)):
+            Lx, T = int(xv.numel()), int(yv.shape[0])
+            mi = torch.as_tensor(mi, dtype=torch.int64)
+            if mi.ndim == 3:
+                assert mi.shape[0] == 1 and mi.shape[2] == 2, f"request {b}: mask_interval shape {tuple(mi.shape)}"
+                mi = mi[0]
+            assert mi.ndim == 2 and mi.shape[1] == 2, f"request {b}: mask_interval shape {tuple(mi.shape)}"
+            ivs = [(int(s), int(e)) for s, e in mi.tolist()]
+            mvals += self._edit_layout(ivs, T, who=f"request {b}: ")      # shuffle draws in request order
+            flat += [v for iv in ivs for v in iv]
+            M = len(ivs)
+            xo.append(xo[-1] + Lx)
+            yo.append(yo[-1] + T)
+            so.append(so[-1] + M)
+            n_cols = T + 2 * (M + 1) + (M + 1) * K + 1
+            cap = max(cap, T + self._gen_budget(Lx, n_cols, 10, spans=M))
+        logging.info(f"silence tokens: {list(silence_tokens)}, note that if you are not using the pretrained encodec 6f79c6a8, make sure you specified it yourself, rather than using the default")
+        sc = self._sample_cfg(top_k, top_p, temperature, stop_repetition, silence_tokens, _seed, _forced_mode)
+        x_off = (C.c_int32 * (B + 1))(*xo)
+        y_off = (C.c_int32 * (B + 1))(*yo)
+        span_off = (C.c_int32 * (B + 1))(*so)
+        iv_arr = (C.c_int32 * max(1, len(flat)))(*flat)
+        mv_arr = (C.c_int32 * max(1, len(mvals)))(*mvals)
+        res = torch.empty((B, K, cap), dtype=torch.int64, device=self.device)
+        res_len = (C.c_int * B)()
+        n_steps = C.c_int(0)
+        fd, forced_ptr, n_forced = self._forced_arg(_forced, B)
+        logits = None
+        if _logit_steps > 0:
+            V = self.args.audio_vocab_size + int(self.args.n_special)
+            logits = torch.zeros((_logit_steps, B, K, V), dtype=torch.float32, device=self.device)
+        rc = self.lib.vc_edit_multi(self._h, B, C.c_void_p(xcat.data_ptr()), x_off, C.c_void_p(ycat.data_ptr()), y_off,
+                                    iv_arr, span_off, mv_arr, C.byref(sc), forced_ptr, n_forced, C.c_void_p(res.data_ptr()), cap,
+                                    res_len, C.c_void_p(logits.data_ptr()) if logits is not None else None, int(_logit_steps),
+                                    C.byref(n_steps), self._stream())
+        check(rc, self._h, "vc_edit_multi")
+        self.last_steps = n_steps.value
+        outs = []
+        for b in range(B):
+            r = res[b, :, : res_len[b]].unsqueeze(0)
+            if self.args.special_first:
+                r = r - int(self.args.n_special)
+            outs.append(r)
+        if logits is not None:
+            return outs, logits
+        return outs
 
     # ------------------------------------------------------------------ measurement hooks
     def set_option(self, name: str, value) -> None:
