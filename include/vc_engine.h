@@ -179,6 +179,23 @@ int vc_tts_multi(vc_engine* e, int B, const int64_t* x_dev, const int32_t* x_off
                  const int64_t* forced_dev, int n_forced, int64_t* res_dev, int res_cap, int* gen_len,
                  float* logits_dev, int logit_steps, int* n_steps, void* stream);
 
+/* ---- multi-utterance best-of-N TTS: B utterances x n_samples (N) samples as B*N sequences - every sentence of the reference's
+ * "Long TTS" goes through inference_tts_batch(batch_size = sample_batch_size) (gradio_app.py:249-280, inference_tts_scale.py:61-87),
+ * here all of them in one call.  Sample j of utterance u is the sequence of slot u*N + j and a member of best-of-N group u; each
+ * utterance behaves exactly like vc_tts(..., n_samples = N) on its own prompt (the LAST sample whose first codebook terminates
+ * first is kept, models/voicecraft.py:1296-1302).  vc_tts is the case (1, N) of this call and vc_tts_multi the case (B, 1).
+ *   x_dev / x_off / y_dev / y_off / shared_text_prefix: as vc_tts_multi (positions below the prefix are read from slot 0)
+ *   res_dev int64 [B][K][res_cap]; gen_len host [B]; kept host [B] (may be NULL): the sample index 0..N-1 each utterance kept
+ *   forced_dev int64 [n_forced][B*N][K], logits_dev float [logit_steps][B*N][K][V]: utterance-major, indexed by slot
+ *   The Philox stream is keyed by slot (vc_sample_cfg.seed), so utterance 0's draws are the draws of a lone vc_tts call with the
+ *   same seed; utterance u > 0 draws on the streams of slots u*N .. u*N + N-1.
+ *   B*N > max_seqs: VC_ECAP; n_samples < 1: VC_EINVAL; an utterance none of whose samples terminated within the step budget:
+ *   VC_ECAP ("utterance 3: ..."). */
+int vc_tts_multi_best_of(vc_engine* e, int B, int n_samples, const int64_t* x_dev, const int32_t* x_off,
+                         const int64_t* y_dev, const int32_t* y_off, const vc_sample_cfg* sc, int shared_text_prefix,
+                         const int64_t* forced_dev, int n_forced, int64_t* res_dev, int res_cap, int* gen_len,
+                         int* kept, float* logits_dev, int logit_steps, int* n_steps, void* stream);
+
 /* ---- speech editing: VoiceCraft.inference (models/voicecraft.py:561-906).
  *   mask_intervals host int32 [M][2] (codec-frame units, as mask_interval[0])
  *   mask_values    host int32 [2M]   the reference's mask_value list (insert_mask, :264-288)

@@ -44,6 +44,10 @@ PROTOTYPES = {
     "vc_tts_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32),
                                C.POINTER(SampleCfg), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int),
                                C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "vc_tts_multi_best_of": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p,
+                                       C.POINTER(C.c_int32), C.POINTER(SampleCfg), C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                                       C.c_void_p]),
     "vc_eval_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                   C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64),

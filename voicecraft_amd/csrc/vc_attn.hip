@@ -300,23 +300,29 @@ hipError_t vc_launch_attn(const AttnArgs& a, int dtype, int rows_cap, hipStream_
 
 // ---------------------------------------------------------------- KV replication (best-of-N)
 // inference_tts_batch repeats the prefilled cache batch_size times (voicecraft.py:1329-1343);
-// here the prompt is prefilled once into slot src and its first `len` positions are copied.
-__global__ void copy_kv_k(char* cache, long seq_stride_b, long head_stride_b, long len_b, int H,
-                          int src_seq, int dst_seq0) {
-  const int dst = dst_seq0 + blockIdx.z;
-  const int h = blockIdx.y;
-  const char* s = cache + (long)src_seq * seq_stride_b + (long)h * head_stride_b;
-  char* d = cache + (long)dst * seq_stride_b + (long)h * head_stride_b;
-  for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 16; i < len_b;
-       i += (long)gridDim.x * blockDim.x * 16)
-    *reinterpret_cast<uint4*>(d + i) = *reinterpret_cast<const uint4*>(s + i);
+// here each prompt is prefilled once into its group's first slot and positions [p0, p1) are copied to the other
+// members.  One launch per cache tensor for all groups of a call: blockIdx.z enumerates the destination slots, the
+// table (CopyKvArgs) maps it to its entry.  W: uint4 when every stride is a multiple of 16 bytes, else 4-byte words.
+template <typename W>
+__global__ void copy_kv_k(const CopyKvArgs a) {
+  int z = blockIdx.z, i = 0;
+  while (i < a.n_ent - 1 && z >= a.cnt[i]) z -= a.cnt[i++];
+  if (z >= a.cnt[i]) return;
+  const int dst = a.dst0[i] + z;
+  const long off = (long)blockIdx.y * a.head_stride_b + (long)a.p0[i] * a.pos_b;
+  const long len_b = (long)(a.p1[i] - a.p0[i]) * a.pos_b;
+  const char* s = a.base + (long)a.src[i] * a.seq_stride_b + off;
+  char* d = a.base + (long)dst * a.seq_stride_b + off;
+  for (long o = ((long)blockIdx.x * blockDim.x + threadIdx.x) * (long)sizeof(W); o < len_b;
+       o += (long)gridDim.x * blockDim.x * (long)sizeof(W))
+    *reinterpret_cast<W*>(d + o) = *reinterpret_cast<const W*>(s + o);
 }
-hipError_t vc_launch_copy_kv(void* cache, long seq_stride, int H, int S_max, int hd, int len,
-                             int src_seq, int dst_seq0, int n_dst, int dtype, hipStream_t s) {
-  if (n_dst <= 0 || len <= 0) return hipSuccess;
-  const long esz = dtype == VC_DTYPE_BF16 ? 2 : 4;
-  hipLaunchKernelGGL(copy_kv_k, dim3(8, H, n_dst), dim3(256), 0, s, (char*)cache, seq_stride * esz,
-                     (long)S_max * hd * esz, (long)len * hd * esz, H, src_seq, dst_seq0);
+hipError_t vc_launch_copy_kv(const CopyKvArgs& a, hipStream_t s) {
+  if (a.n_ent <= 0 || a.n_dst <= 0) return hipSuccess;
+  if (a.n_ent > VC_MAX_SEQS || a.H < 1) return hipErrorInvalidValue;
+  const bool v16 = ((a.seq_stride_b | a.head_stride_b | a.pos_b) & 15) == 0 && ((uintptr_t)a.base & 15) == 0;
+  if (v16) hipLaunchKernelGGL(copy_kv_k<uint4>, dim3(8, a.H, a.n_dst), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(copy_kv_k<uint32_t>, dim3(8, a.H, a.n_dst), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

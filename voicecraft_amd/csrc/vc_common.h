@@ -334,6 +334,7 @@ struct SampleDyn {
   int logit_steps;
   int max_steps;            // rows of the gen buffer per sequence this call may fill
   int n_seq;                // sequences of the CALL: row stride of forced / logits_out (the step's row count may have shrunk since)
+  int n_group;              // best-of-N: samples per group; sample j of group u is the sequence of slot u * n_group + j
   uint64_t seed;
   const int64_t* forced;    // [n_forced][B][K] or null
   float* logits_out;        // [logit_steps][B][K][V] or null
@@ -355,6 +356,7 @@ struct SampleArgs {         // engine-constant part (kernel argument)
   int graph_steps;          // slot (step_ctr / graph_steps) & 1: the host reads the slot of a batch of steps it has seen END, so what it re-packs by
                             // does not depend on how far the device has run ahead (same seed, same widths, same tokens in every run)
   int* samp;                // scratch [B][K + 2]
+  int* err;                 // bit 3: a best-of-N group whose members do not sit on consecutive rows in sample order (vc_tokens.hip advance_phase)
   int* gen;                 // [B][gen_stride][K]
   // next-step rows
   int rps;                  // rows per sequence slot (1, or 3 for editing)
@@ -452,5 +454,12 @@ struct CeReduceArgs {      // per codebook: acc[k] += sum over rows, in a fixed 
 hipError_t vc_launch_ce_reduce(const CeReduceArgs& a, hipStream_t s);
 
 hipError_t vc_launch_cast(const float* src, void* dst, long n, int dtype, hipStream_t s);
-hipError_t vc_launch_copy_kv(void* cache, long seq_stride, int H, int S_max, int hd, int len,
-                             int src_seq, int dst_seq0, int n_dst, int dtype, hipStream_t s);
+// Replication of per-sequence data to other slots (best-of-N): entry i copies positions [p0[i], p1[i]) of slot src[i] to the slots
+// dst0[i] .. dst0[i] + cnt[i] - 1.  Layout of `base`: [slot][H][positions] with the given byte strides; pos_b = bytes per position.
+struct CopyKvArgs {
+  char* base;
+  long seq_stride_b, head_stride_b, pos_b;
+  int H, n_ent, n_dst;      // n_dst = sum of cnt
+  int src[VC_MAX_SEQS], dst0[VC_MAX_SEQS], cnt[VC_MAX_SEQS], p0[VC_MAX_SEQS], p1[VC_MAX_SEQS];
+};
+hipError_t vc_launch_copy_kv(const CopyKvArgs& a, hipStream_t s);

@@ -782,6 +782,7 @@ SampleArgs make_sample_args(vc_engine* e, int B, int rps) {
   a.logits = e->logits; a.B = B; a.K = e->K; a.V = e->V; a.d = e->d;
   a.empty_token = e->cfg.empty_token; a.gen_stride = e->gen_cap; a.dyn = e->d_dyn;
   a.st = e->st; a.n_active = e->n_active; a.host_active = e->h_flag + 8; a.host_live = e->h_flag + 9; a.step_ctr = e->step_ctr; a.graph_steps = std::max(1, e->steps_per_graph); a.samp = e->samp;
+  a.err = e->err_flag;
   a.gen = e->gen;
   a.rps = rps; a.dec_h = e->dec_h; a.row_seq = e->dec_row_seq; a.row_pos = e->dec_row_pos;
   a.logit_row = e->logit_row;
@@ -791,7 +792,7 @@ SampleArgs make_sample_args(vc_engine* e, int B, int rps) {
 }
 
 int push_sample_dyn(vc_engine* e, const vc_sample_cfg* sc, const int64_t* forced, int n_forced, float* logits_out,
-                    int logit_steps, int n_seq, hipStream_t s) {
+                    int logit_steps, int n_seq, hipStream_t s, int n_group = 1) {
   SampleDyn& d = *e->h_dyn;
   memset(&d, 0, sizeof d);
   d.top_k = sc->top_k; d.top_p = sc->top_p; d.temperature = sc->temperature;
@@ -805,6 +806,7 @@ int push_sample_dyn(vc_engine* e, const vc_sample_cfg* sc, const int64_t* forced
   d.logits_out = logits_out; d.logit_steps = logits_out ? logit_steps : 0;
   d.max_steps = e->gen_cap;                               // rows of the gen buffer per sequence
   d.n_seq = n_seq;                                        // sequences of the call (row stride of forced / logits_out)
+  d.n_group = n_group;                                    // samples per best-of-N group (advance_phase's keep decision)
   d.dbg_ts = getenv("VC_SAMPLER_TS") ? e->dbg_ts : nullptr;
   HIPCHK(e, hipMemcpyAsync(e->d_dyn, e->h_dyn, sizeof(SampleDyn), hipMemcpyHostToDevice, s));
   return VC_OK;
@@ -834,17 +836,20 @@ int decode_step(vc_engine* e, const SampleArgs& sa, int B, int rps, bool grouped
 // per blocking poll).  Steps replayed after the last sequence retired are no-ops (*n_active == 0).
 void refresh_opt_state(vc_engine* e);
 
-int decode_loop(vc_engine* e, const SampleArgs& sa0, int B0, int rps, bool grouped, const vc_sample_cfg* sc,
+// groups: 0 = independent sequences, else the number of best-of-N groups the B0 sequences form (grouped sampler launches).
+int decode_loop(vc_engine* e, const SampleArgs& sa0, int B0, int rps, int groups, const vc_sample_cfg* sc,
                 int max_steps, int* steps_run, hipStream_t s, bool precapture_only = false) {
   const int G = std::max(1, e->steps_per_graph);
+  const bool grouped = groups > 0;
   const double t0 = now_ms();
   if (precapture_only) e->host_ms[1] = e->host_ms[2] = 0;
   // Rows per step.  A multi-utterance call starts with one row per sequence; when few enough sequences are left (option "shrink") the
   // live ones are re-packed onto the rows of a narrower step - the next power of two >= the live count - and the loop goes on with
-  // that width's captured graph (graphs are keyed by width).  B / sa = the width in force.
+  // that width's captured graph (graphs are keyed by width).  B / sa = the width in force.  Best-of-N calls of two or more groups shrink
+  // too (a decided group keeps one live row); a call of ONE group does not: its step stays N rows wide, as it always has.
   int B = B0;
   SampleArgs sa = sa0;
-  const bool can_shrink = e->shrink && !grouped && rps == 1 && B0 > 1;
+  const bool can_shrink = e->shrink && groups != 1 && rps == 1 && B0 > 1;
   auto width_for = [](int live) { int p = 1; while (p < live) p *= 2; return p; };
   // One captured graph per (rows per step, option state), kept for the life of the engine.
   auto exec_for = [&](hipGraphExec_t* out) -> int {
@@ -974,6 +979,8 @@ int check_err_flag(vc_engine* e, hipStream_t s) {
       return fail(e, VC_EINVAL, "shared_text_prefix: a sequence's text differs from sequence 0's inside the shared prefix");
     if (bits & 4)
       return fail(e, VC_ESTATE, "internal: a re-pack found more live sequences than the narrower step has rows");
+    if (bits & 8)
+      return fail(e, VC_ESTATE, "internal: the samples of a best-of-N group were not on consecutive rows in sample order at their keep decision");
     return fail(e, VC_EINVAL, "token id out of range in x or y (text rows %d, audio vocab %d)", e->cfg.text_rows, e->V);
   }
   return VC_OK;
@@ -1412,16 +1419,24 @@ int collect_states(vc_engine* e, int B, hipStream_t s) {
   return VC_OK;
 }
 
-// Shared by vc_tts (one prompt, n_samples >= 1) and vc_tts_multi (B prompts).
+// The one TTS host path: U prompts (jobs) x n_samples (N) samples each, as U * N sequences.  Sample j of utterance u is the
+// sequence of slot u * N + j and, with N > 1, a member of best-of-N group u.  vc_tts is (1, N), vc_tts_multi (U, 1) and
+// vc_tts_multi_best_of (U, N).
 int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const vc_sample_cfg* sc,
             const int64_t* forced, int n_forced, float* logits_out, int logit_steps, int* steps_out,
             hipStream_t s, int shared_prefix = 0) {
   const int K = e->K;
-  const bool grouped = n_samples > 1;
-  const int B = grouped ? n_samples : (int)jobs.size();
-  if (B > e->B_max) return fail(e, VC_ECAP, "%d sequences requested but max_seqs is %d", B, e->B_max);
+  const int U = (int)jobs.size(), N = n_samples;
+  if (N < 1) return fail(e, VC_EINVAL, "n_samples %d must be at least 1", N);
+  const bool grouped = N > 1;
+  const int B = U * N;
+  if (B > e->B_max) {
+    if (grouped && U > 1)
+      return fail(e, VC_ECAP, "%d sequences requested (%d utterances x %d samples) but max_seqs is %d", B, U, N, e->B_max);
+    return fail(e, VC_ECAP, "%d sequences requested but max_seqs is %d", B, e->B_max);
+  }
   int max_steps = 0;
-  for (int b = 0; b < (int)jobs.size(); ++b) {
+  for (int b = 0; b < U; ++b) {
     const TtsJob& j = jobs[b];
     if (j.Lx < 1 || j.T < 0) return fail(e, VC_EINVAL, "empty text or negative prompt length");
     const int n_cols = j.T + 1;                           // T+K columns minus the K-1 dropped ones (:967)
@@ -1448,23 +1463,23 @@ int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const 
   // ev[1] the host time of capture + instantiation showed up as prefill time of that first call)
   {
     SampleArgs sa0 = make_sample_args(e, B, 1);
-    if (int rc0 = decode_loop(e, sa0, B, 1, grouped, sc, max_steps, nullptr, s, true)) return rc0;
+    if (int rc0 = decode_loop(e, sa0, B, 1, grouped ? U : 0, sc, max_steps, nullptr, s, true)) return rc0;
   }
   HIPCHK(e, hipEventRecord(e->ev[0], s));
-  // ---- prompts + ONE prefill over all of them; best-of-N prefills once and replicates the cache
+  // ---- prompts + ONE prefill over all of them, into the slots of the groups' first samples
   {
-    std::vector<PromptArgs> pas(jobs.size());
-    std::vector<int> slots(jobs.size());
-    for (int b = 0; b < (int)jobs.size(); ++b) {
-      const TtsJob& j = jobs[b];
-      fill_prompt_common(e, pas[b], j.x, j.Lx, j.y, j.T);
-      pas[b].n_seg = 1; pas[b].n_cols = j.T + 1;
-      pas[b].seg[0] = Segment{0, j.T + 1, 0, j.T, -1, -1};
-      pas[b].skip = (b > 0) ? shared_prefix : 0;          // the shared text prefix is prefilled once, in sequence 0
-      pas[b].x_shared = jobs[0].x;                        // ... and checked on the device to be the same text (prompt_k)
-      slots[b] = b;
-      e->h_st[b] = init_state(e, j.Lx, j.T + 1, true, 1);
-      e->h_st[b].slot = b;
+    std::vector<PromptArgs> pas(U);
+    std::vector<int> slots(U);
+    for (int u = 0; u < U; ++u) {
+      const TtsJob& j = jobs[u];
+      fill_prompt_common(e, pas[u], j.x, j.Lx, j.y, j.T);
+      pas[u].n_seg = 1; pas[u].n_cols = j.T + 1;
+      pas[u].seg[0] = Segment{0, j.T + 1, 0, j.T, -1, -1};
+      pas[u].skip = (u > 0) ? shared_prefix : 0;          // the shared text prefix is prefilled once, in sequence 0
+      pas[u].x_shared = jobs[0].x;                        // ... and checked on the device to be the same text (prompt_k)
+      slots[u] = u * N;
+      e->h_st[u * N] = init_state(e, j.Lx, j.T + 1, true, 1);
+      e->h_st[u * N].slot = u * N;
     }
     e->h_flag[2] = shared_prefix;
     HIPCHK(e, hipMemcpyAsync(e->share_len, e->h_flag + 2, sizeof(int), hipMemcpyHostToDevice, s));
@@ -1473,18 +1488,36 @@ int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const 
     if (rc) return rc;
   }
   if (grouped) {
-    const TtsJob& j = jobs[0];
+    // best-of-N prefills once per group and replicates: every sample starts from its prompt's K/V and first-step logits.  Positions
+    // below the shared prefix are read from sequence 0's cache by every sequence, so they are not copied.  One launch per cache tensor
+    // and one for the logits, whatever the number of groups
+    CopyKvArgs kv;
+    memset(&kv, 0, sizeof kv);
+    kv.n_ent = U; kv.n_dst = U * (N - 1);
+    for (int u = 0; u < U; ++u) {
+      kv.src[u] = u * N; kv.dst0[u] = u * N + 1; kv.cnt[u] = N - 1;
+      kv.p0[u] = shared_prefix; kv.p1[u] = jobs[u].Lx + jobs[u].T + 1;
+    }
+    CopyKvArgs lg = kv;
+    const long esz = e->dtype == VC_DTYPE_BF16 ? 2 : 4;
+    kv.H = e->H; kv.head_stride_b = (long)e->S_max * e->hd * esz; kv.pos_b = (long)e->hd * esz;
+    kv.seq_stride_b = (long)e->H * kv.head_stride_b;
     for (int l = 0; l < e->L; ++l) {
-      const long stride = (long)e->H * e->S_max * e->hd;
-      HIPCHK(e, vc_launch_copy_kv(e->layers[l].kc, stride, e->H, e->S_max, e->hd, j.Lx + j.T + 1, 0, 1, B - 1, e->dtype, s));
-      HIPCHK(e, vc_launch_copy_kv(e->layers[l].vc, stride, e->H, e->S_max, e->hd, j.Lx + j.T + 1, 0, 1, B - 1, e->dtype, s));
+      kv.base = (char*)e->layers[l].kc;
+      HIPCHK(e, vc_launch_copy_kv(kv, s));
+      kv.base = (char*)e->layers[l].vc;
+      HIPCHK(e, vc_launch_copy_kv(kv, s));
     }
-    for (int b = 1; b < B; ++b) {   // every sample starts from the same first-step logits
-      HIPCHK(e, hipMemcpyAsync(e->logits + (size_t)b * K * e->V, e->logits, (size_t)K * e->V * 4, hipMemcpyDeviceToDevice, s));
-      e->h_st[b] = e->h_st[0];
-      e->h_st[b].slot = b;
-    }
-    for (int b = 0; b < B; ++b) e->h_st[b].group = 0;
+    lg.base = (char*)e->logits; lg.H = 1; lg.seq_stride_b = lg.pos_b = (long)K * e->V * 4;
+    for (int u = 0; u < U; ++u) { lg.p0[u] = 0; lg.p1[u] = 1; }
+    HIPCHK(e, vc_launch_copy_kv(lg, s));
+    for (int u = 0; u < U; ++u)
+      for (int j = 0; j < N; ++j) {
+        SeqState& st = e->h_st[u * N + j];
+        if (j > 0) st = e->h_st[u * N];
+        st.slot = u * N + j;
+        st.group = u;
+      }
   }
   HIPCHK(e, hipMemcpyAsync(e->st, e->h_st, sizeof(SeqState) * B, hipMemcpyHostToDevice, s));
   HIPCHK(e, hipMemsetAsync(e->st_fin, 0, sizeof(SeqState) * B, s));
@@ -1493,7 +1526,7 @@ int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const 
   e->h_flag[9] = B; e->h_flag[10] = B;        // the two slots of "sequences still live" (SampleArgs.host_live)
   e->host_ms[6] = 0;
   HIPCHK(e, hipMemcpyAsync(e->n_active, e->h_flag + 1, sizeof(int), hipMemcpyHostToDevice, s));
-  int rc = push_sample_dyn(e, sc, forced, n_forced, logits_out, logit_steps, B, s);
+  int rc = push_sample_dyn(e, sc, forced, n_forced, logits_out, logit_steps, B, s, N);
   if (rc) return rc;
   rc = check_err_flag(e, s);   // also orders the pinned-buffer reuse
   if (rc) return rc;
@@ -1502,11 +1535,12 @@ int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const 
   int steps_run = 0;
   HIPCHK(e, vc_launch_sample(sa, grouped, s));
   HIPCHK(e, hipEventRecord(e->ev[1], s));
-  rc = decode_loop(e, sa, B, 1, grouped, sc, max_steps, &steps_run, s);
+  rc = decode_loop(e, sa, B, 1, grouped ? U : 0, sc, max_steps, &steps_run, s);
   if (rc) return rc;
   HIPCHK(e, hipEventRecord(e->ev[2], s));
   rc = collect_states(e, B, s);
   if (rc) return rc;
+  if (grouped && (rc = check_err_flag(e, s))) return rc;      // the keep decisions' row check (advance_phase)
   HIPCHK(e, hipEventElapsedTime(&e->ms[0], e->ev[0], e->ev[1]));
   HIPCHK(e, hipEventElapsedTime(&e->ms[1], e->ev[1], e->ev[2]));
   e->ms[2] = e->ms[0] + e->ms[1];
@@ -1517,6 +1551,16 @@ int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const 
   }
   (void)steps_run;
   return VC_OK;
+}
+
+// The sample utterance u of a tts_run keeps: the member that is kept, done and has its span (-1 if none terminated).
+int kept_sample(const vc_engine* e, int u, int N) {
+  int keep = -1;
+  for (int j = 0; j < N; ++j) {
+    const SeqState& st = e->h_st[u * N + j];
+    if (st.kept && st.done && st.span >= 1) keep = j;
+  }
+  return keep;
 }
 
 int assemble_tts(vc_engine* e, const TtsJob& j, int slot, int64_t* res, int res_cap, int* gen_len, hipStream_t s) {
@@ -1554,12 +1598,40 @@ extern "C" int vc_tts(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t*
   if (rc) return rc;
   int slot = 0;
   if (n_samples > 1) {
-    slot = -1;
-    for (int b = 0; b < n_samples; ++b) if (e->h_st[b].kept && e->h_st[b].done && e->h_st[b].span >= 1) slot = b;
+    slot = kept_sample(e, 0, n_samples);
     if (slot < 0) return fail(e, VC_ECAP, "no sample terminated within the step budget");
   }
   rc = assemble_tts(e, jobs[0], slot, res_dev, res_cap, gen_len, s);
   if (rc) return rc;
+  HIPCHK(e, hipStreamSynchronize(s));
+  return VC_OK;
+}
+
+extern "C" int vc_tts_multi_best_of(vc_engine* e, int B, int n_samples, const int64_t* x_dev, const int32_t* x_off,
+                                    const int64_t* y_dev, const int32_t* y_off, const vc_sample_cfg* sc, int shared_text_prefix,
+                                    const int64_t* forced_dev, int n_forced, int64_t* res_dev, int res_cap, int* gen_len,
+                                    int* kept, float* logits_dev, int logit_steps, int* n_steps, void* stream) {
+  int rc = check_ready(e);
+  if (rc) return rc;
+  if (B < 1 || n_samples < 1 || !x_dev || !x_off || !y_dev || !y_off || !sc || !res_dev || !gen_len)
+    return fail(e, VC_EINVAL, "null/invalid argument to vc_tts_multi (B %d, n_samples %d)", B, n_samples);
+  for (int b = 0; b < B; ++b)
+    if (shared_text_prefix < 0 || shared_text_prefix >= x_off[b + 1] - x_off[b])
+      return fail(e, VC_EINVAL, "shared_text_prefix %d must be shorter than every text (sequence %d has %d tokens)",
+                  shared_text_prefix, b, x_off[b + 1] - x_off[b]);
+  hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+  std::vector<TtsJob> jobs;
+  for (int b = 0; b < B; ++b)
+    jobs.push_back(TtsJob{x_dev + x_off[b], x_off[b + 1] - x_off[b], y_dev + (size_t)y_off[b] * e->K, y_off[b + 1] - y_off[b]});
+  rc = tts_run(e, jobs, n_samples, sc, forced_dev, n_forced, logits_dev, logit_steps, n_steps, s, B > 1 ? shared_text_prefix : 0);
+  if (rc) return rc;
+  for (int b = 0; b < B; ++b) {
+    const int j = n_samples > 1 ? kept_sample(e, b, n_samples) : 0;
+    if (j < 0) return fail(e, VC_ECAP, "utterance %d: no sample terminated within the step budget", b);
+    if (kept) kept[b] = j;
+    rc = assemble_tts(e, jobs[b], b * n_samples + j, res_dev + (size_t)b * e->K * res_cap, res_cap, &gen_len[b], s);
+    if (rc) return rc;
+  }
   HIPCHK(e, hipStreamSynchronize(s));
   return VC_OK;
 }
@@ -1569,26 +1641,8 @@ extern "C" int vc_tts_multi(vc_engine* e, int B, const int64_t* x_dev, const int
                             int shared_text_prefix,
                             const int64_t* forced_dev, int n_forced, int64_t* res_dev, int res_cap, int* gen_len,
                             float* logits_dev, int logit_steps, int* n_steps, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
-  if (B < 1 || !x_dev || !x_off || !y_dev || !y_off || !sc || !res_dev || !gen_len)
-    return fail(e, VC_EINVAL, "null/invalid argument to vc_tts_multi");
-  for (int b = 0; b < B; ++b)
-    if (shared_text_prefix < 0 || shared_text_prefix >= x_off[b + 1] - x_off[b])
-      return fail(e, VC_EINVAL, "shared_text_prefix %d must be shorter than every text (sequence %d has %d tokens)",
-                  shared_text_prefix, b, x_off[b + 1] - x_off[b]);
-  hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
-  std::vector<TtsJob> jobs;
-  for (int b = 0; b < B; ++b)
-    jobs.push_back(TtsJob{x_dev + x_off[b], x_off[b + 1] - x_off[b], y_dev + (size_t)y_off[b] * e->K, y_off[b + 1] - y_off[b]});
-  rc = tts_run(e, jobs, 1, sc, forced_dev, n_forced, logits_dev, logit_steps, n_steps, s, B > 1 ? shared_text_prefix : 0);
-  if (rc) return rc;
-  for (int b = 0; b < B; ++b) {
-    rc = assemble_tts(e, jobs[b], b, res_dev + (size_t)b * e->K * res_cap, res_cap, &gen_len[b], s);
-    if (rc) return rc;
-  }
-  HIPCHK(e, hipStreamSynchronize(s));
-  return VC_OK;
+  return vc_tts_multi_best_of(e, B, 1, x_dev, x_off, y_dev, y_off, sc, shared_text_prefix, forced_dev, n_forced, res_dev, res_cap,
+                              gen_len, nullptr, logits_dev, logit_steps, n_steps, stream);
 }
 
 // ------------------------------------------------------------------------------------- editing
@@ -1708,7 +1762,7 @@ extern "C" int vc_edit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t
   const int max_steps = j.max_steps;
   {   // decode graphs of a first call of this shape: captured ahead of both timers (as in tts_run)
     SampleArgs sa0 = make_sample_args(e, 1, (M > 1) ? 3 : 1);
-    if ((rc = decode_loop(e, sa0, 1, (M > 1) ? 3 : 1, false, sc, max_steps, nullptr, s, true))) return rc;
+    if ((rc = decode_loop(e, sa0, 1, (M > 1) ? 3 : 1, 0, sc, max_steps, nullptr, s, true))) return rc;
   }
   HIPCHK(e, hipEventRecord(e->ev[0], s));
   {
@@ -1730,7 +1784,7 @@ extern "C" int vc_edit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t
   HIPCHK(e, vc_launch_sample(sa, false, s));
   HIPCHK(e, hipEventRecord(e->ev[1], s));
   int steps_run = 0;
-  rc = decode_loop(e, sa, 1, rps, false, sc, max_steps, &steps_run, s);
+  rc = decode_loop(e, sa, 1, rps, 0, sc, max_steps, &steps_run, s);
   if (rc) return rc;
   HIPCHK(e, hipEventRecord(e->ev[2], s));
   HIPCHK(e, hipMemcpyAsync(e->h_st, e->st, sizeof(SeqState), hipMemcpyDeviceToHost, s));
@@ -1780,7 +1834,7 @@ extern "C" int vc_edit_multi(vc_engine* e, int B, const int64_t* x_dev, const in
   hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
   {   // decode graphs (width B and the narrower widths a shrinking batch passes through): ahead of both timers, as in tts_run
     SampleArgs sa0 = make_sample_args(e, B, 1);
-    if ((rc = decode_loop(e, sa0, B, 1, false, sc, loop_steps, nullptr, s, true))) return rc;
+    if ((rc = decode_loop(e, sa0, B, 1, 0, sc, loop_steps, nullptr, s, true))) return rc;
   }
   HIPCHK(e, hipEventRecord(e->ev[0], s));
   {
@@ -1809,7 +1863,7 @@ extern "C" int vc_edit_multi(vc_engine* e, int B, const int64_t* x_dev, const in
   SampleArgs sa = make_sample_args(e, B, 1);
   HIPCHK(e, vc_launch_sample(sa, false, s));
   HIPCHK(e, hipEventRecord(e->ev[1], s));
-  rc = decode_loop(e, sa, B, 1, false, sc, loop_steps, nullptr, s);
+  rc = decode_loop(e, sa, B, 1, 0, sc, loop_steps, nullptr, s);
   if (rc) return rc;
   HIPCHK(e, hipEventRecord(e->ev[2], s));
   rc = collect_states(e, B, s);

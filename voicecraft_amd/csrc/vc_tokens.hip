@@ -411,12 +411,41 @@ __device__ __forceinline__ void sample_phase(const SampleArgs& a, const SampleDy
 __device__ void advance_phase(const SampleArgs& a, const SampleDyn& dy, int b, bool grouped, SeqState* sp, const int* xs) {
   __shared__ int s_tok[VC_MAX_CODEBOOKS];
   __shared__ int s_mode;     // 0: row inactive, 1: one new row, 3: span switch (three rows), 4 / 5: a feed step of a switch (SeqState.feed)
-  __shared__ int s_ylen, s_mask, s_Lx;
+  __shared__ int s_ylen, s_mask, s_Lx, s_keep;
   const int tid = threadIdx.x;
   const int K = a.K;
+  if (grouped) {
+    // best-of-N (voicecraft.py:1296-1302): the LAST sample whose first codebook terminates is kept.  While the group's terminator is
+    // still ahead (n_eog == 0) every member is live and the members sit on consecutive rows in sample order (they start that way and
+    // repack_k keeps the live rows in order), so sample m of this block's group is row b - j + m: one lane per member reads that
+    // row's flag, and the keeper is the highest set bit of the ballot.  Done rows (fillers, dropped samples) carry no flag
+    // (sample_only_k clears theirs) and no group of a live sequence (fillers are group -1)
+    if (tid < 64) {
+      int keep = -1;
+      if (!sp->done && !sp->feed && sp->n_eog == 0) {        // wave-uniform (LDS)
+        const int N = dy.n_group, group = sp->group, slot = sp->slot;
+        const int j = slot - group * N;                       // this block's sample index
+        const int r = b - j + tid;                            // row of sample `tid`
+        bool bad = group < 0 || j < 0 || j >= N || N > 64, flag = false;
+        if (!bad && tid < N) {
+          bad = r < 0 || r >= a.B;
+          if (!bad) {
+            bad = a.st[r].group != group || a.st[r].slot != slot - j + tid;        // immutable during the step
+            flag = a.samp[r * (VC_MAX_CODEBOOKS + 2) + K + 1] != 0;
+          }
+        }
+        const uint64_t fb = __ballot(flag && !bad), bb = __ballot(bad);
+        keep = fb ? 63 - __clzll((long long)fb) : -1;
+        if (tid == 0 && bb) atomicOr(a.err, 8);
+        if (tid == 0 && keep >= 0) keep = (keep == j) ? -2 : keep;   // -2: this block is the keeper
+      }
+      if (tid == 0) s_keep = keep;
+    }
+    __syncthreads();
+  }
   if (tid == 0) {
     // scalar fields in registers (fetched from LDS in one go); only the span arrays are indexed dynamically
-    const int done0 = sp->done, Lx = sp->Lx, term = sp->term_token, group = sp->group, n_spans = sp->n_spans, slot = sp->slot;
+    const int done0 = sp->done, Lx = sp->Lx, term = sp->term_token, n_spans = sp->n_spans, slot = sp->slot;
     int n_eog = sp->n_eog, cur = sp->cur_num_gen, prev = sp->prev_token, consec = sp->consec_silence;
     int span = sp->span, total = sp->total_steps, y_len = sp->y_len;
     const int feed = sp->feed;
@@ -434,14 +463,7 @@ __device__ void advance_phase(const SampleArgs& a, const SampleDyn& dy, int b, b
       for (int k = 0; k < VC_MAX_CODEBOOKS; ++k) tok[k] = (k < K) ? xs[k] : 0;
       int cond = xs[K + 1];
       bool drop = false;
-      if (grouped && n_eog == 0) {
-        // best-of-N (voicecraft.py:1296-1302): the LAST sample whose first codebook terminates is kept
-        int keep = -1;
-        for (int bb = 0; bb < a.B; ++bb)
-          if (a.st[bb].group == group && a.samp[bb * (VC_MAX_CODEBOOKS + 2) + K + 1]) keep = bb;
-        // (group ids are immutable and every member is still alive while n_eog == 0)
-        if (keep >= 0 && keep != b) drop = true;
-      }
+      if (grouped && n_eog == 0 && s_keep >= 0) drop = true;   // another member of the group is kept (s_keep above)
       const int step = total;
       const bool forced = dy.forced && dy.forced_mode == 0 && step < dy.n_forced;
       if (n_eog == 0) {
@@ -670,7 +692,16 @@ __global__ __launch_bounds__(256) void sample_only_k(const SampleArgs a) {
   const SampleDyn dy = *a.dyn;
   __builtin_amdgcn_sched_barrier(0);
   if (active == 0) return;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {      // the step counter and the live count the host shrinks by, as in sample_fused_k
+    const int c = *a.step_ctr;
+    *a.step_ctr = c + 1;
+    __hip_atomic_store(a.host_live + ((c / a.graph_steps) & 1), active, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
   park_state(&s_st, sw);
+  if (s_st.done) {      // a finished row (a dropped sample, a filler after a re-pack) raises no keep flag: its entry may hold a stale one
+    if (threadIdx.x == 0) a.samp[blockIdx.x * (VC_MAX_CODEBOOKS + 2) + a.K + 1] = 0;
+    return;
+  }
   sample_phase(a, dy, blockIdx.x, &s_st, a.samp + blockIdx.x * (VC_MAX_CODEBOOKS + 2), s_dyn, v0);
 }
 __global__ __launch_bounds__(256) void advance_only_k(const SampleArgs a) {
@@ -690,7 +721,7 @@ hipError_t vc_launch_sample(const SampleArgs& a, bool grouped, hipStream_t s) {
   if (!grouped) {
     hipLaunchKernelGGL(sample_fused_k, dim3(a.B), dim3(256), lds, s, a);
   } else {
-    // the keep decision reads every sample's cond flag, so it needs the kernel boundary
+    // the keep decision reads every member's cond flag, so it needs the kernel boundary
     hipLaunchKernelGGL(sample_only_k, dim3(a.B), dim3(256), lds, s, a);
     hipLaunchKernelGGL(advance_only_k, dim3(a.B), dim3(256), 0, s, a);
   }
@@ -735,7 +766,9 @@ __global__ __launch_bounds__(256) void repack_k(const RepackArgs a) {
       if (tid < W) reinterpret_cast<int*>(a.st + r)[tid] = reinterpret_cast<const int*>(s_st + s_src[r])[tid];
       if (tid == 0) { a.row_seq[r] = s_st[s_src[r]].slot; a.row_pos[r] = s_pos[s_src[r]]; a.logit_row[r] = r; }
     } else {       // filler: a finished state that owns no sequence
-      if (tid < W) reinterpret_cast<int*>(a.st + r)[tid] = (tid == (int)(offsetof(SeqState, done) / 4)) ? 1 : (tid == (int)(offsetof(SeqState, slot) / 4)) ? -1 : 0;
+      // (group -1: a filler is no member of any best-of-N group, advance_phase)
+      if (tid < W) reinterpret_cast<int*>(a.st + r)[tid] = (tid == (int)(offsetof(SeqState, done) / 4)) ? 1 :
+                                                           (tid == (int)(offsetof(SeqState, slot) / 4) || tid == (int)(offsetof(SeqState, group) / 4)) ? -1 : 0;
       if (tid == 0) { a.row_seq[r] = 0; a.row_pos[r] = -1; a.logit_row[r] = r; }
     }
   }

@@ -87,6 +87,7 @@ class VoiceCraftEngine:
         check(self.lib.vc_create(C.byref(cfg), index, C.byref(self._h)), None, "vc_create")
         self._load(state_dict)
         self.last_steps = 0
+        self.last_kept: list[int] = []       # inference_tts_multi / _long with batch_size > 1: kept sample per utterance
 
     # ------------------------------------------------------------------ nn.Module look-alikes
     def eval(self):
@@ -222,11 +223,18 @@ class VoiceCraftEngine:
     @torch.no_grad()
     def inference_tts_multi(self, xs, ys, top_k: int = -100, top_p: float = 1.0, temperature: float = 1.0,
                             stop_repetition: int = 3, silence_tokens: Iterable[int] = (1388, 1898, 131), _seed=None,
-                            _forced=None, _forced_mode: str = "tokens", _logit_steps: int = 0, _shared_text_prefix: int = 0):
+                            _forced=None, _forced_mode: str = "tokens", _logit_steps: int = 0, _shared_text_prefix: int = 0,
+                            batch_size: int = 1):
         """B different utterances as one batch (not in the reference: SURVEY.md §8f-1).
         xs: list of int64 [Lx_i]; ys: list of int64 [T_i,K].  Returns list of (res [1,K,T_i+Tg_i], gen)
-        (+ the raw head logits [steps,B,K,V] as a third value when _logit_steps > 0)."""
+        (+ the raw head logits [steps,B*N,K,V] as a second value when _logit_steps > 0).
+        batch_size N > 1: best-of-N per utterance, as inference_tts_batch(batch_size=N) on each prompt
+        (include/vc_engine.h vc_tts_multi_best_of): B*N sequences, sample j of utterance u in slot u*N + j; the kept
+        sample's (res, gen) is returned and self.last_kept lists the kept sample index of every utterance.
+        _forced is [steps][B*N][K], utterance-major."""
         B = len(xs)
+        N = int(batch_size)
+        assert N >= 1, f"batch_size must be at least 1, got {batch_size}"
         assert B == len(ys) and 1 <= B <= self.max_seqs, (B, self.max_seqs)
         K = self.args.n_codebooks
         xcat = torch.cat([torch.as_tensor(v, dtype=torch.int64).reshape(-1) for v in xs]).to(self.device).contiguous()
@@ -245,18 +253,20 @@ class VoiceCraftEngine:
         sc = self._sample_cfg(top_k, top_p, temperature, stop_repetition, silence_tokens, _seed, _forced_mode)
         res = torch.empty((B, K, cap), dtype=torch.int64, device=self.device)
         gen_len = (C.c_int * B)()
+        kept = (C.c_int * B)()
         n_steps = C.c_int(0)
-        fd, forced_ptr, n_forced = self._forced_arg(_forced, B)
+        fd, forced_ptr, n_forced = self._forced_arg(_forced, B * N)
         logits = None
         if _logit_steps > 0:
             V = self.args.audio_vocab_size + int(self.args.n_special)
-            logits = torch.zeros((_logit_steps, B, K, V), dtype=torch.float32, device=self.device)
-        rc = self.lib.vc_tts_multi(self._h, B, C.c_void_p(xcat.data_ptr()), x_off, C.c_void_p(ycat.data_ptr()), y_off,
-                                   C.byref(sc), int(_shared_text_prefix), forced_ptr, n_forced, C.c_void_p(res.data_ptr()), cap, gen_len,
-                                   C.c_void_p(logits.data_ptr()) if logits is not None else None, int(_logit_steps),
-                                   C.byref(n_steps), self._stream())
+            logits = torch.zeros((_logit_steps, B * N, K, V), dtype=torch.float32, device=self.device)
+        rc = self.lib.vc_tts_multi_best_of(self._h, B, N, C.c_void_p(xcat.data_ptr()), x_off, C.c_void_p(ycat.data_ptr()), y_off,
+                                           C.byref(sc), int(_shared_text_prefix), forced_ptr, n_forced, C.c_void_p(res.data_ptr()),
+                                           cap, gen_len, kept, C.c_void_p(logits.data_ptr()) if logits is not None else None,
+                                           int(_logit_steps), C.byref(n_steps), self._stream())
         check(rc, self._h, "vc_tts_multi")
         self.last_steps = n_steps.value
+        self.last_kept = [int(kept[b]) for b in range(B)]
         outs = []
         for b in range(B):
             T, Tg = yo[b + 1] - yo[b], gen_len[b]
@@ -363,7 +373,7 @@ class VoiceCraftEngine:
     @torch.no_grad()
     def inference_tts_long(self, x_prompt, x_sentences, y, top_k: int = -100, top_p: float = 1.0, temperature: float = 1.0,
                            stop_repetition: int = 3, silence_tokens: Iterable[int] = (1388, 1898, 131), reuse_prefix: bool = True,
-                           _seed=None):
+                           _seed=None, batch_size: int = 1):
         """Sentence-chained "Long TTS" (gradio_app.py:231-236, :249-313): the reference synthesises every sentence with
         its own `inference_one_sample` call on the text [transcript of the voice prompt ; sentence] and the SAME audio
         prompt.  Here all sentences are decoded together (chunks of max_seqs: the weights are streamed once per step
@@ -371,19 +381,27 @@ class VoiceCraftEngine:
         transcript prefix are computed once per chunk and read by every sentence (include/vc_engine.h, vc_tts_multi).
 
         x_prompt int64 [Lp] phonemes of the voice prompt's transcript, x_sentences list of int64 [Ls_i],
-        y int64 [1,T,K] (or [T,K]) codes of the voice prompt.  Returns a list of (res [1,K,T+Tg_i], gen [1,K,Tg_i])."""
+        y int64 [1,T,K] (or [T,K]) codes of the voice prompt.  Returns a list of (res [1,K,T+Tg_i], gen [1,K,Tg_i]).
+        batch_size = the app's sample_batch_size (gradio_app.py:506, default 3 there): best-of-N per sentence, as its
+        inference_one_sample -> inference_tts_batch; sentences then go max_seqs // batch_size per call and
+        self.last_kept holds the kept sample index of every sentence."""
+        N = int(batch_size)
+        assert 1 <= N <= self.max_seqs, f"batch_size {batch_size} must be in [1, max_seqs = {self.max_seqs}]"
         xp = torch.as_tensor(x_prompt, dtype=torch.int64).reshape(-1)
         K = self.args.n_codebooks
         yy = torch.as_tensor(y, dtype=torch.int64).reshape(-1, K)
-        outs = []
-        for c0 in range(0, len(x_sentences), self.max_seqs):
-            chunk = x_sentences[c0: c0 + self.max_seqs]
+        outs, kept = [], []
+        per_call = self.max_seqs // N
+        for c0 in range(0, len(x_sentences), per_call):
+            chunk = x_sentences[c0: c0 + per_call]
             xs = [torch.cat([xp, torch.as_tensor(v, dtype=torch.int64).reshape(-1)]) for v in chunk]
             for v in xs:
                 assert v.numel() > xp.numel(), "every sentence needs at least one phoneme"
             share = int(xp.numel()) if (reuse_prefix and len(chunk) > 1) else 0
             outs += self.inference_tts_multi(xs, [yy] * len(chunk), top_k, top_p, temperature, stop_repetition, silence_tokens,
-                                             _seed=None if _seed is None else _seed + c0, _shared_text_prefix=share)
+                                             _seed=None if _seed is None else _seed + c0, _shared_text_prefix=share, batch_size=N)
+            kept += self.last_kept
+        self.last_kept = kept
         return outs
 
     # ------------------------------------------------------------------ editing
