@@ -82,6 +82,44 @@ int vc_codec_encode_batch(vc_codec* c, const float* wav_dev, int B, int n_sample
                           int codes_cap, int* n_frames, void* stream);
 int vc_codec_decode_batch(vc_codec* c, const int64_t* codes_dev, int B, int T, float* wav_dev, int wav_cap,
                           void* stream);
+/* ---- chunked decode: the waveform of a code sequence that is still being produced (one clip; no batch form).
+ * The decoder is an RVQ look-up, one conv over frames, a UNIDIRECTIONAL LSTM and a purely local upsampling stack, so it can
+ * run chunk by chunk with the LSTM's (h, c) carried between calls and a few frames of look-ahead - exactly: the
+ * concatenation of everything a stream emits is, BIT FOR BIT, what vc_codec_decode gives for the concatenation of
+ * everything it was fed, for any split into chunks (chunks of one frame, a total shorter than the look-ahead, an empty
+ * final call).  Every frame passes the look-up, the first conv and the LSTM once; the stack behind the LSTM runs over a
+ * window = the frames to hand out plus the context frames on either side, and only the interior samples leave.
+ *
+ *   vc_codec_stream_geometry (host only, no handle, no GPU), all three in frames, derived from the config (kernel
+ *   sizes, ratios, num_residual_layers, dilation_growth_rate, causal, pad_reflect):
+ *     lookahead_frames     the samples of frame t are final - and emitted - once frame t + lookahead has been fed
+ *                          (right context of the first conv + of the stack behind the LSTM; 0 with causal = 1)
+ *     left_context_frames  behind the LSTM, the output of frame p reaches no sample of frames >= p + left_context
+ *                          (its own frame counts: the window keeps left_context - 1 frames in front of the emitted ones)
+ *     start_frames         (may be NULL) nothing is emitted before this many frames have been fed: reflect padding at
+ *                          the true start mirrors the frames behind it, and a clip no longer than its padding is
+ *                          zero-extended first, so the first conv must know the clip is longer than that.  1 with
+ *                          constant padding.
+ *   After feeding F frames in all, hop * (F >= start_frames ? max(0, F - lookahead_frames) : 0) samples have been
+ *   emitted; the call with last = 1 emits the rest (hop * F in all) and closes the stream.
+ *
+ *   vc_codec_decode_stream_begin  opens the handle's decode stream (zero LSTM state); a second begin restarts it.
+ *   vc_codec_decode_stream        codes_dev int64 [K][n] with row stride `stride` (>= n): the next n frames (n = 0 is
+ *                                 legal, e.g. a final call that only flushes); wav_dev receives *n_samples_out samples
+ *                                 (wav_cap too small: VC_ECAP, nothing consumed).  The call returns with the samples
+ *                                 written (it synchronises `stream`): the activation arenas are shared with the
+ *                                 blocking calls, so vc_codec_encode / vc_codec_decode between two calls of an open
+ *                                 stream are legal and do not disturb it.  What the stream remembers - the (h, c) of
+ *                                 both LSTM layers, the latents in front of the first conv, the LSTM outputs the next
+ *                                 window needs, the frame counters - lives in buffers of its own, sized by the
+ *                                 geometry.  n + the kept context may not exceed the frames max_samples allows per call.
+ *   Errors: bad pointers / n < 0 / stride < n / wav_cap < 0: VC_EINVAL (checked first, NULL handle included); no open
+ *   stream: VC_ESTATE; a failed call closes the stream. */
+int vc_codec_stream_geometry(const vc_codec_cfg* cfg, int* lookahead_frames, int* left_context_frames, int* start_frames);
+int vc_codec_decode_stream_begin(vc_codec* c);
+int vc_codec_decode_stream(vc_codec* c, const int64_t* codes_dev, int stride, int n, int last, float* wav_dev,
+                           int wav_cap, int* n_samples_out, void* stream);
+
 /* Test hooks: the latent before quantisation ([T][hidden], channels-last) of the last encode,
  * and its timing (HIP events on the stream). */
 int vc_codec_debug_latent(vc_codec* c, float* host_dst, int64_t n_floats);

@@ -160,6 +160,34 @@ int vc_tts(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int
            int64_t* res_dev, int res_cap, int* gen_len, float* logits_dev, int logit_steps,
            int* n_steps, void* stream);
 
+/* ---- streaming TTS: vc_tts for ONE utterance and one sample (inference_tts semantics), resumable - the generated frames are
+ * handed out while the decode loop runs instead of after its last step.  The loop is the blocking call's: the same captured graphs,
+ * at most two graph batches queued, the host pacing one batch behind the device; after each pacing wait the host knows that
+ * `graph_steps` more steps are complete and that their rows of the generated-token buffer are final (overrides happen at sampling
+ * time, nothing rewrites a row).  The delay pattern makes frame t complete once step t + K - 1 has run, so after S finished steps
+ * of a live sequence frames < S - (K - 1) are complete; once the sequence has ended the count is its own Tg.  Same tokens, same
+ * number of launched steps, same Philox stream as vc_tts with the same arguments.
+ * Not streamable, and refused: best-of-N (n_samples > 1: the kept sample is unknown until a group terminates), the multi-utterance
+ * calls and editing - they have no stream form.
+ *   begin  does what vc_tts does up to and including the first sample (graphs pre-captured ahead of the timers, prompt, prefill,
+ *          state upload, first sample).  x_dev / y_dev / forced_dev must stay valid until end.  forced_dev: as in vc_tts (B = 1).
+ *   next   queues and paces graph batches exactly as the blocking loop does and returns as soon as at least min_frames new frames
+ *          are complete, or the sequence has ended: frames [first_frame, first_frame + n_frames) un-shifted into codes_dev
+ *          [K][cap] (row stride cap, time-major like res; n_frames <= cap; 1 <= min_frames <= cap).  *done = 1 once every frame
+ *          has been handed out (possibly with n_frames = 0).  The gather runs on a side stream the engine owns and only that
+ *          stream is synchronised: the decode stream gets no synchronisation inside the loop.
+ *   end    drains the loop if frames are still outstanding, assembles the full result exactly as vc_tts does (res_dev, res_cap,
+ *          gen_len, n_steps as there) and fills vc_last_timing.  res_dev = NULL aborts: what is queued is waited for, nothing is
+ *          assembled, the engine is reusable.  Either way the stream is closed.
+ * While a stream is open every other decode entry point, vc_set_option and a second begin return VC_ESTATE; next / end without
+ * an open stream return VC_ESTATE; bad pointers, cap < 1, min_frames < 1 or > cap return VC_EINVAL (checked first).  An error
+ * returned by next leaves the stream open: close it with end (res_dev = NULL, or a buffer to get the same error once more). */
+int vc_tts_stream_begin(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
+                        const vc_sample_cfg* sc, const int64_t* forced_dev, int n_forced, void* stream);
+int vc_tts_stream_next(vc_engine* e, int min_frames, int64_t* codes_dev, int cap,
+                       int* first_frame, int* n_frames, int* done);
+int vc_tts_stream_end(vc_engine* e, int64_t* res_dev, int res_cap, int* gen_len, int* n_steps);
+
 /* ---- multi-utterance TTS (SURVEY.md §8f-1 / BASELINE config 5): B independent
  * (x, y) pairs decoded as one batch; each row follows inference_tts exactly.
  *   x_dev int64 [sum Lx], y_dev int64 [sum T][K] concatenated; *_off host arrays [B+1].

@@ -3,7 +3,8 @@
 Public surface (mirrors the reference's model interface):
     VoiceCraftEngine.inference_tts / inference_tts_batch / inference
     pattern_shift / pattern_revert / pattern_unshift   (delayed-codebook pattern, bit-exact)
-    AudioTokenizer                                     (EnCodec encode/decode)
+    AudioTokenizer                                     (EnCodec encode/decode, .decode_stream())
+    VoiceCraftEngine.inference_tts_stream, stream_tts  (tokens / audio while the decode loop runs)
 Everything computes in libvcengine.so (HIP, gfx950); importing this package does not need a GPU,
 constructing an engine does.
 """
@@ -14,6 +15,9 @@ def __getattr__(name):
     if name in ("VoiceCraftEngine", "pattern_shift", "pattern_revert", "pattern_unshift"):
         from . import engine
         return getattr(engine, name)
+    if name == "stream_tts":
+        from . import stream
+        return stream.stream_tts
     if name == "AudioTokenizer":
         from . import codec
         return codec.AudioTokenizer

@@ -41,6 +41,11 @@ PROTOTYPES = {
     "vc_tts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(SampleCfg), C.c_int,
                          C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_int,
                          C.POINTER(C.c_int), C.c_void_p]),
+    "vc_tts_stream_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(SampleCfg), C.c_void_p,
+                                      C.c_int, C.c_void_p]),
+    "vc_tts_stream_next": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                     C.POINTER(C.c_int)]),
+    "vc_tts_stream_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vc_tts_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32),
                                C.POINTER(SampleCfg), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int),
                                C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]),

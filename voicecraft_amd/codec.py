@@ -46,6 +46,10 @@ PROTOTYPES = {
     "vc_codec_debug_latent": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "vc_codec_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "vc_codec_last_lstm_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
+    "vc_codec_stream_geometry": (C.c_int, [C.POINTER(CodecCfg), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vc_codec_decode_stream_begin": (C.c_int, [C.c_void_p]),
+    "vc_codec_decode_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                         C.POINTER(C.c_int), C.c_void_p]),
 }
 
 # the VoiceCraft codec (README.md:198 of the reference; config.py:51; phonemize_encodec_encode_hf.py:11-13)
@@ -62,6 +66,75 @@ def _bind(lib):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     return lib
+
+
+def make_cfg(cfg: dict | None = None, max_samples: int = 320000, max_batch: int = 1) -> CodecCfg:
+    """The C config of DEFAULT_CFG overridden by `cfg` (transformers.EncodecConfig names)."""
+    cf = dict(DEFAULT_CFG, **(cfg or {}))
+    assert cf["pad_mode"] in ("reflect", "constant"), cf["pad_mode"]
+    c = CodecCfg(sample_rate=cf["sample_rate"], n_filters=cf["n_filters"], n_ratios=len(cf["ratios"]), hidden=cf["hidden"],
+                 n_q=cf["n_q"], codebook_size=cf["codebook_size"], lstm_layers=cf["lstm_layers"], kernel_size=cf["kernel_size"],
+                 last_kernel_size=cf["last_kernel_size"], residual_kernel_size=cf["residual_kernel_size"],
+                 compress=cf["compress"], max_samples=int(max_samples), causal=int(bool(cf["use_causal_conv"])),
+                 pad_reflect=int(cf["pad_mode"] == "reflect"), conv_shortcut=int(bool(cf["use_conv_shortcut"])),
+                 num_residual_layers=int(cf["num_residual_layers"]), dilation_growth_rate=int(cf["dilation_growth_rate"]),
+                 max_batch=int(max_batch))
+    for i, r in enumerate(cf["ratios"]):
+        c.ratios[i] = r
+    return c
+
+
+def stream_geometry(cfg: dict | None = None) -> tuple[int, int, int]:
+    """(lookahead_frames, left_context_frames, start_frames) of the chunked decode for a codec config - host only, no GPU
+    (vc_codec_stream_geometry, include/vc_codec.h)."""
+    lib = _bind(_lib.load())
+    la, lc, st = C.c_int(0), C.c_int(0), C.c_int(0)
+    rc = lib.vc_codec_stream_geometry(C.byref(make_cfg(cfg)), C.byref(la), C.byref(lc), C.byref(st))
+    if rc:
+        raise AssertionError(f"vc_codec_stream_geometry: the config has no stream geometry (code {rc})")
+    return la.value, lc.value, st.value
+
+
+class CodecDecodeStream:
+    """The open decode stream of an AudioTokenizer (one per tokenizer; opening another restarts it).  `feed` takes the
+    next frames and returns the samples that have become final: concatenated, bit for bit `tokenizer.decode` of
+    everything fed.  Blocking `encode` / `decode` calls of the tokenizer between two feeds are legal."""
+
+    def __init__(self, tok: "AudioTokenizer"):
+        self.tok = tok
+        self.lookahead_frames, self.left_context_frames, self.start_frames = stream_geometry(tok.cfg)
+        self.fed = 0
+        self.emitted = 0          # samples
+        self.closed = False
+        self.ms = 0.0             # device time of the chunks so far (vc_codec_last_ms per call, summed)
+        tok._check(tok.lib.vc_codec_decode_stream_begin(tok._h), "vc_codec_decode_stream_begin")
+
+    def ready_frames(self, fed: int) -> int:
+        """Frames whose samples have been emitted once `fed` frames were fed (before the final call)."""
+        return max(0, fed - self.lookahead_frames) if fed >= self.start_frames else 0
+
+    @torch.no_grad()
+    def feed(self, codes: torch.Tensor, last: bool = False) -> torch.Tensor:
+        """codes int64 [1, K, n] (n may be 0) -> wav fp32 [1, 1, m]; `last=True` flushes and closes the stream."""
+        tok = self.tok
+        if self.closed:
+            raise _lib.EngineError("decode stream is closed")
+        assert codes.ndim == 3 and codes.shape[0] == 1 and codes.shape[1] == tok.n_q, codes.shape
+        n = int(codes.shape[2])
+        cd = codes[0].to(tok.device, torch.int64).contiguous()
+        fed = self.fed + n
+        m = (fed if last else self.ready_frames(fed)) * tok.hop - self.emitted
+        wav = torch.empty((max(m, 1),), dtype=torch.float32, device=tok.device)
+        got = C.c_int(0)
+        self.closed = True        # a failed call closes the stream on the C side too
+        tok._check(tok.lib.vc_codec_decode_stream(tok._h, C.c_void_p(cd.data_ptr()) if n else None, n, n, int(bool(last)),
+                                                  C.c_void_p(wav.data_ptr()), m, C.byref(got), tok._stream()),
+                   "vc_codec_decode_stream")
+        self.closed = bool(last)
+        self.fed = fed
+        self.emitted += got.value
+        self.ms += tok.last_ms()
+        return wav[: got.value].reshape(1, 1, -1)
 
 
 def fold_weight_norm(g: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
@@ -186,6 +259,7 @@ class AudioTokenizer:
         self.lib = _bind(_lib.load())
         cf = dict(DEFAULT_CFG, **(cfg or {}))
         assert cf["pad_mode"] in ("reflect", "constant"), cf["pad_mode"]
+        self.cfg = cf
         self.max_batch = int(max_batch)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -198,15 +272,7 @@ class AudioTokenizer:
         for r in cf["ratios"]:
             self.hop *= r
         self.max_samples = int(max_seconds * self.sample_rate)
-        c = CodecCfg(sample_rate=cf["sample_rate"], n_filters=cf["n_filters"], n_ratios=len(cf["ratios"]), hidden=cf["hidden"],
-                     n_q=cf["n_q"], codebook_size=cf["codebook_size"], lstm_layers=cf["lstm_layers"], kernel_size=cf["kernel_size"],
-                     last_kernel_size=cf["last_kernel_size"], residual_kernel_size=cf["residual_kernel_size"],
-                     compress=cf["compress"], max_samples=self.max_samples, causal=int(bool(cf["use_causal_conv"])),
-                     pad_reflect=int(cf["pad_mode"] == "reflect"), conv_shortcut=int(bool(cf["use_conv_shortcut"])),
-                     num_residual_layers=int(cf["num_residual_layers"]), dilation_growth_rate=int(cf["dilation_growth_rate"]),
-                     max_batch=self.max_batch)
-        for i, r in enumerate(cf["ratios"]):
-            c.ratios[i] = r
+        c = make_cfg(cf, self.max_samples, self.max_batch)
         self._h = C.c_void_p()
         self._check(self.lib.vc_codec_create(C.byref(c), index, C.byref(self._h)), "vc_codec_create", None)
         want = expected_keys(cf)
@@ -277,6 +343,10 @@ class AudioTokenizer:
                                                        T * self.hop, self._stream()), "vc_codec_decode_batch")
             outs.append(wav)
         return torch.cat(outs, dim=0).unsqueeze(1)
+
+    def decode_stream(self) -> CodecDecodeStream:
+        """Opens the chunked decode: `.feed(codes [1,K,n], last=False) -> wav [1,1,m]`, `.lookahead_frames`."""
+        return CodecDecodeStream(self)
 
     def last_latent(self, T: int, hidden: int = 128) -> torch.Tensor:
         out = torch.empty((T, hidden), dtype=torch.float32)

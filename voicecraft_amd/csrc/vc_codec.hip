@@ -287,8 +287,10 @@ struct LstmWaveArgs {
   float* out_raw;        // optional [B][T][H]
   float* out_elu;        // optional [B][T][H]
   int H, T, k, B;        // B sequences advance together: the step's weights are read ONCE for all of them
+  const float* h0[2];    // CARRY: [B][H] per layer, h of the step before this launch sequence's first (a chunk of a longer sequence)
 };
-template <int NQ>   // H = 256 * NQ
+// CARRY = the chunked form (vc_codec_decode_stream): step 0 continues from h0 / the cell states the caller left in c instead of zeros
+template <int NQ, bool CARRY = false>   // H = 256 * NQ
 __global__ __launch_bounds__(256) void lstm_wave_k(const LstmWaveArgs a) {
   const int n = blockIdx.y;
   const int t = a.k - n;
@@ -316,7 +318,7 @@ __global__ __launch_bounds__(256) void lstm_wave_k(const LstmWaveArgs a) {
     gb = *reinterpret_cast<const float4*>(a.b1 + 4 * u);
   }
   for (int b = 0; b < a.B; ++b) {
-    const float4* hp = reinterpret_cast<const float4*>(t ? a.hs[n] + b * TH + (long)(t - 1) * H : a.hzero);
+    const float4* hp = reinterpret_cast<const float4*>(t ? a.hs[n] + b * TH + (long)(t - 1) * H : CARRY ? a.h0[n] + (long)b * H : a.hzero);
     float4 hv[NQ], xv[NQ];
 #pragma unroll
     for (int j = 0; j < NQ; ++j) hv[j] = hp[lane + 64 * j];
@@ -395,10 +397,15 @@ struct LstmPersistArgs {
   int H, T, B;
   unsigned epoch;              // != 0, differs from call to call
   int* err;
+  const float* h0[2];          // CARRY: [B][H] per layer, h of the step before step 0 (plain floats, final before the launch)
+  float* hT[2];                // CARRY: [B][H] per layer, receives h of step T - 1 (another buffer than h0: a fast workgroup ends before a slow one starts)
+  int carry;                   // CARRY: 1.  Read at run time so that step 0 keeps the one-shot form's selects and the compiler the same arithmetic to schedule
 };
 #define VC_LSTM_SPIN_LIMIT 400000
 #define VC_LSTM_BG 8            // clips advanced per hand-off round (LDS: 2 parities x BG x {h, x} x H floats = 128 KB at H = 1024)
-template <int NQ>   // H = 256 * NQ
+// CARRY = the chunked form (vc_codec_decode_stream): step 0 takes h from h0 and c from the cell states the last chunk left, and the
+// last step leaves h in hT.  Hand-off, bound and error word are the one-shot form's; so is the order of every sum.
+template <int NQ, bool CARRY = false>   // H = 256 * NQ
 __global__ __launch_bounds__(512) void lstm_persist_k(const LstmPersistArgs a) {
   extern __shared__ __attribute__((aligned(16))) float s_hx[];          // [parity][clip][h_prev | x][H]
   __shared__ int s_abort;
@@ -445,9 +452,17 @@ __global__ __launch_bounds__(512) void lstm_persist_k(const LstmPersistArgs a) {
   for (int b0 = 0; b0 < a.B; b0 += VC_LSTM_BG) {
     const int nb = min(VC_LSTM_BG, a.B - b0);
     for (int t = 0; t < a.T; ++t) {
+      const int tz = CARRY ? (t | a.carry) : t;           // non-zero: the step has a predecessor (in this launch, or carried in)
       float* sbuf = s_hx + (size_t)(t & 1) * (bg * 2 * H);
       // ---- bounded wait for this wave's slices of h_{t-1} (own layer) and, on layer 1, of the lower layer's h_t
       bool ok = true;
+      if (CARRY && t == 0) {   // h_{-1} was final before the launch: parked without a tag check
+#pragma unroll 1
+        for (int bb = 0; bb < nb; ++bb) {
+#pragma unroll
+          for (int q = 0; q < GPL; ++q) sbuf[(size_t)bb * 2 * H + s0 + q] = a.h0[n][(long)(b0 + bb) * H + s0 + q];
+        }
+      }
       if (t || n == 1) {
         ok = false;
         for (int spins = 0; spins < VC_LSTM_SPIN_LIMIT && !ok; ++spins) {
@@ -487,12 +502,12 @@ __global__ __launch_bounds__(512) void lstm_persist_k(const LstmPersistArgs a) {
         float4 hv[NQ], xv[NQ];
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
-          hv[j] = t ? reinterpret_cast<const float4*>(sh)[lane + 64 * j] : make_float4(0.f, 0.f, 0.f, 0.f);
+          hv[j] = tz ? reinterpret_cast<const float4*>(sh)[lane + 64 * j] : make_float4(0.f, 0.f, 0.f, 0.f);
           xv[j] = (n == 1) ? reinterpret_cast<const float4*>(sh + H)[lane + 64 * j] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
         float4 gi = gb;
         if (n == 0) gi = *reinterpret_cast<const float4*>(a.G0 + (b * (long)a.T + t) * 4 * H + 4 * u);
-        const float c_prev = t ? a.c[n][(long)b * H + u] : 0.f;
+        const float c_prev = tz ? a.c[n][(long)b * H + u] : 0.f;
         const float sk = (n == 1 && a.skip) ? a.skip[b * TH + (long)t * H + u] : 0.f;
         float g4[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -523,6 +538,7 @@ __global__ __launch_bounds__(512) void lstm_persist_k(const LstmPersistArgs a) {
           a.c[n][(long)b * H + u] = c;
           __hip_atomic_store(a.hg[n] + b * TH + (long)t * H + u, ((unsigned long long)a.epoch << 32) | (unsigned long long)__float_as_uint(h),
                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (CARRY && t == a.T - 1) a.hT[n][(long)b * H + u] = h;
           if (n == 1 && a.skip) {
             const float y = h + sk;
             if (a.out_raw) a.out_raw[b * TH + (long)t * H + u] = y;
@@ -675,6 +691,20 @@ __global__ void rvq_decode_k(const int64_t* __restrict__ codes, const float* __r
   }
   out[idx] = v;
 }
+// the same look-up for a chunk of a stream: codes [Q][n] with a row stride, out [n][D] (same sum order)
+__global__ void rvq_decode_stream_k(const int64_t* __restrict__ codes, int stride, const float* __restrict__ E, float* __restrict__ out,
+                                    int n, int D, int C, int Q, int* err) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)n * D) return;
+  const int t = (int)(idx / D), i = (int)(idx % D);
+  float v = 0.f;
+  for (int q = 0; q < Q; ++q) {
+    long c = codes[(long)q * stride + t];
+    if (c < 0 || c >= C) { *err = 1; c = 0; }
+    v = v + E[((long)q * C + c) * D + i];
+  }
+  out[idx] = v;
+}
 __global__ void transpose_k(const float* __restrict__ src, float* __restrict__ dst, int R, int Cc) {   // [R][Cc] -> [Cc][R]
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long)R * Cc) return;
@@ -753,6 +783,7 @@ struct vc_codec {
   unsigned long long* hgran = nullptr;   // persistent LSTM: 2 x [B_max][T_max][H] granules, allocated on first use
   unsigned lstm_epoch = 0;
   int persist_ok = -1;                   // -1 not probed, 0 the cooperative grid does not fit, 1 usable
+  int persist_carry_ok = -1;             // the same for the carried-state form (lstm_persist_k<NQ, true>)
   bool persist_used = false;             // a persistent launch is in flight / unchecked (check_lstm_flag)
   int last_lstm_persist = 0;             // 1: the last LSTM ran as the persistent launch, 0: launch per step
   int* err_flag = nullptr;
@@ -763,6 +794,18 @@ struct vc_codec {
   float last_ms = 0, last_lstm_ms = 0;
   hipEvent_t ev_l[2]{};
   hipStream_t own_stream = nullptr;
+  // ---- the open decode stream (vc_codec_decode_stream): everything it remembers between calls, sized by the geometry
+  struct DecStream {
+    bool open = false;
+    int pl = 0, pr = 0;                  // first conv: frames of context to the left / right
+    int left = 0, right = 0, start = 1;  // vc_codec_stream_geometry
+    long fed = 0, proc = 0, emitted = 0; // frames fed / through the LSTM / whose samples were handed out
+    int n_lat = 0, n_y = 0;              // rows kept: latents of frames [fed - n_lat, fed), LSTM outputs of frames [proc - n_y, proc)
+    int lat_cap = 0, y_cap = 0;
+    int hcur = 0;                        // which half of h holds the carried hidden state
+    float *lat = nullptr, *y = nullptr;  // [lat_cap][hidden], [y_cap][top]
+    float *h = nullptr, *c = nullptr;    // [2][layers][top] (ping-pong), [layers][top]
+  } ds;
 };
 
 namespace {
@@ -965,8 +1008,20 @@ int check_lstm_flag(vc_codec* c) {
   return VC_OK;
 }
 // EncodecLSTM: y = lstm(x) + x over [B][T][H]; x is raw, the block output is written raw and/or ELU'd
-int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, float* out_elu, hipStream_t s, int B = 1) {
+// cy != NULL: the chunk of a stream - the recurrence starts from cy->h_in / cy->c and leaves its last step in cy->h_out / cy->c
+struct LstmCarry { const float* h_in[2]; float* h_out[2]; float* c[2]; };
+template <bool CARRY>
+void launch_lstm_wave(int H, const LstmWaveArgs& a, hipStream_t s) {
+  const dim3 grid(H / 4, 2);
+  if (H == 256) hipLaunchKernelGGL((lstm_wave_k<1, CARRY>), grid, dim3(256), 0, s, a);
+  else if (H == 512) hipLaunchKernelGGL((lstm_wave_k<2, CARRY>), grid, dim3(256), 0, s, a);
+  else if (H == 768) hipLaunchKernelGGL((lstm_wave_k<3, CARRY>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((lstm_wave_k<4, CARRY>), grid, dim3(256), 0, s, a);
+}
+int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, float* out_elu, hipStream_t s, int B = 1,
+             const LstmCarry* cy = nullptr) {
   const int H = L.H;
+  if (cy && (B != 1 || L.layers > 2)) return cfail(c, VC_EINVAL, "internal: a carried LSTM state is one sequence of at most two layers");
   const float* in = x;
   float* seq[2] = {c->HS0, c->HS1};
   if (L.layers == 2 && H % 256 == 0 && H <= 1024 && !getenv("VC_LSTM_SEQUENTIAL")) {
@@ -976,9 +1031,18 @@ int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, 
     // one persistent cooperative launch (lstm_persist_k) when its 2 x H/8 workgroups are all resident at once;
     // VC_LSTM_WAVE=1 forces the launch-per-step wavefront (the reference form of the tests)
     if ((H == 512 || H == 1024) && !getenv("VC_LSTM_WAVE")) {
-      const void* kern = H == 512 ? (const void*)lstm_persist_k<2> : (const void*)lstm_persist_k<4>;
+      const void* kern = cy ? (H == 512 ? (const void*)lstm_persist_k<2, true> : (const void*)lstm_persist_k<4, true>)
+                            : (H == 512 ? (const void*)lstm_persist_k<2> : (const void*)lstm_persist_k<4>);
       const long n_wg = 2L * (H / 8);
-      if (c->persist_ok < 0) {
+      if (cy && c->persist_carry_ok < 0) {   // the carried form is a kernel of its own: its own residency probe (one clip: 16 KB of LDS at most)
+        int per_cu = 0, coop = 0;
+        hipDeviceProp_t prop;
+        CCHK(c, hipGetDeviceProperties(&prop, c->device));
+        CCHK(c, hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device));
+        CCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 512, (size_t)2 * 2 * H * sizeof(float)));
+        c->persist_carry_ok = (coop && (long)per_cu * prop.multiProcessorCount >= n_wg) ? 1 : 0;
+      }
+      if (!cy && c->persist_ok < 0) {
         int per_cu = 0, coop = 0;
         hipDeviceProp_t prop;
         CCHK(c, hipGetDeviceProperties(&prop, c->device));
@@ -988,7 +1052,7 @@ int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, 
         CCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 512, lds_max));
         c->persist_ok = (coop && (long)per_cu * prop.multiProcessorCount >= n_wg) ? 1 : 0;
       }
-      if (c->persist_ok) {
+      if (cy ? c->persist_carry_ok : c->persist_ok) {
         if (!c->hgran) {
           int rc2 = calloc_dev(c, &c->hgran, (size_t)2 * c->B_max * c->T_max * H);
           if (rc2) return rc2;
@@ -1000,6 +1064,8 @@ int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, 
         pa.Whh[0] = L.Whh[0]; pa.Whh[1] = L.Whh[1]; pa.Wih1 = L.WihP[1]; pa.b1 = L.bP[1]; pa.G0 = c->G;
         pa.hg[0] = c->hgran; pa.hg[1] = c->hgran + (size_t)c->B_max * c->T_max * H;
         pa.c[0] = c->cstate; pa.c[1] = c->cstate + (size_t)B * H;
+        if (cy)
+          for (int n = 0; n < 2; ++n) { pa.c[n] = cy->c[n]; pa.h0[n] = cy->h_in[n]; pa.hT[n] = cy->h_out[n]; pa.carry = 1; }
         pa.skip = x; pa.out_raw = out_raw; pa.out_elu = out_elu; pa.H = H; pa.T = T; pa.B = B;
         pa.epoch = c->lstm_epoch; pa.err = c->err_flag + 1;      // word 1: a bounded wait gave up
         void* kargs[] = {&pa};
@@ -1013,22 +1079,24 @@ int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, 
       }
     }
     c->last_lstm_persist = 0;
-    CCHK(c, hipMemsetAsync(c->cstate, 0, (size_t)2 * B * H * 4, s));
+    if (!cy) CCHK(c, hipMemsetAsync(c->cstate, 0, (size_t)2 * B * H * 4, s));
     LstmWaveArgs a;
     memset(&a, 0, sizeof a);
     a.Whh[0] = L.Whh[0]; a.Whh[1] = L.Whh[1]; a.Wih1 = L.WihP[1]; a.b1 = L.bP[1]; a.G0 = c->G;
     a.hs[0] = seq[0]; a.hs[1] = seq[1]; a.c[0] = c->cstate; a.c[1] = c->cstate + (size_t)B * H; a.hzero = c->hzero;
     a.skip = x; a.out_raw = out_raw; a.out_elu = out_elu; a.H = H; a.T = T; a.B = B;
-    const dim3 grid(H / 4, 2);
+    if (cy)
+      for (int n = 0; n < 2; ++n) { a.c[n] = cy->c[n]; a.h0[n] = cy->h_in[n]; }
     CCHK(c, hipEventRecord(c->ev_l[0], s));
     for (int k = 0; k <= T; ++k) {
       a.k = k;
-      if (H == 256) hipLaunchKernelGGL(lstm_wave_k<1>, grid, dim3(256), 0, s, a);
-      else if (H == 512) hipLaunchKernelGGL(lstm_wave_k<2>, grid, dim3(256), 0, s, a);
-      else if (H == 768) hipLaunchKernelGGL(lstm_wave_k<3>, grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL(lstm_wave_k<4>, grid, dim3(256), 0, s, a);
+      if (cy) launch_lstm_wave<true>(H, a, s);
+      else launch_lstm_wave<false>(H, a, s);
     }
     CCHK(c, hipGetLastError());
+    if (cy)
+      for (int n = 0; n < 2; ++n)
+        CCHK(c, hipMemcpyAsync(cy->h_out[n], a.hs[n] + (size_t)(T - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, s));
     CCHK(c, hipEventRecord(c->ev_l[1], s));
     return VC_OK;
   }
@@ -1036,14 +1104,14 @@ int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, 
   for (int n = 0; n < L.layers; ++n) {
     int rc = run_conv1x1(c, L.Wih[n], in, T, c->G, s, 1);                        // G = in W_ih^T + b_ih + b_hh
     if (rc) return rc;
-    CCHK(c, hipMemsetAsync(c->cstate, 0, (size_t)H * 4, s));
+    if (!cy) CCHK(c, hipMemsetAsync(c->cstate, 0, (size_t)H * 4, s));
     float* hs = seq[n & 1];
     const bool last = (n == L.layers - 1);
     for (int t = 0; t < T; ++t) {
       LstmArgs a;
       memset(&a, 0, sizeof a);
-      a.Whh = L.Whh[n]; a.G = c->G + (size_t)t * 4 * H; a.h_prev = t ? hs + (size_t)(t - 1) * H : c->hzero;
-      a.c = c->cstate; a.h_out = hs + (size_t)t * H; a.H = H;
+      a.Whh = L.Whh[n]; a.G = c->G + (size_t)t * 4 * H; a.h_prev = t ? hs + (size_t)(t - 1) * H : cy ? cy->h_in[n] : c->hzero;
+      a.c = cy ? cy->c[n] : c->cstate; a.h_out = hs + (size_t)t * H; a.H = H;
       if (last) {
         a.skip = x + (size_t)t * H;
         a.out_raw = out_raw ? out_raw + (size_t)t * H : nullptr;
@@ -1052,8 +1120,78 @@ int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, 
       hipLaunchKernelGGL(lstm_step_k, dim3((H + 3) / 4), dim3(256), (size_t)H * 4, s, a);
     }
     CCHK(c, hipGetLastError());
+    if (cy) CCHK(c, hipMemcpyAsync(cy->h_out[n], hs + (size_t)(T - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, s));
     in = hs;
   }
+  return VC_OK;
+}
+// The decoder behind its LSTM: the upsampling stages and the last conv over L frames of ELU'd LSTM output in B_elu -> wav [B][hop * L].
+// Shared by the one-shot decode (the whole clip) and the stream (a window of frames).
+int run_dec_back(vc_codec* c, int L, float* wav, hipStream_t s, int B) {
+  const vc_codec_cfg& g = c->cfg;
+  int rc, Lo;
+  float* elu = c->B_elu;
+  for (int i = 0; i < g.n_ratios; ++i) {
+    float* nelu = (elu == c->A_elu) ? c->B_elu : c->A_elu;
+    if ((rc = run_convT(c, c->dec_up[i], elu, L, c->A_raw, nelu, &Lo, s, B))) return rc;
+    L = Lo;
+    float* raw = c->A_raw;
+    elu = nelu;
+    if ((rc = run_res_units(c, c->dec_res[i], &raw, &elu, L, false, s, B))) return rc;
+  }
+  {
+    const int Ci = g.n_filters, Kw = g.last_kernel_size;
+    const int pt = Kw - 1;
+    const int pad = g.causal ? pt : pt - pt / 2;
+    const int mp = std::max(pad, pt - pad);
+    hipLaunchKernelGGL(conv_last_k, dim3((L + 255) / 256, B), dim3(256), (size_t)Kw * Ci * 4, s, elu, c->dec_last.w_raw,
+                       c->dec_last.bias, wav, L, Ci, Kw, pad, g.pad_reflect, (g.pad_reflect && L <= mp) ? mp + 1 : L);
+  }
+  CCHK(c, hipGetLastError());
+  return VC_OK;
+}
+
+// Host-only geometry of the chunked decode.  Behind the LSTM the decoder is local: cl / cr = how many output positions at a window's
+// left / right edge differ from the true signal because the window's neighbour is missing there (a transposed conv misses x[-1] /
+// x[L], a conv pads), pushed through every layer at its own resolution.  A conv with pl / pr taps to the left / right widens the
+// two counts by pl / pr; a transposed conv of stride s that trims pl on the left turns them into cl * s + s - pl and cr * s + pl.
+struct StreamGeom { int pl, pr, left, right, start; };
+int stream_geom(const vc_codec_cfg* g, StreamGeom* o) {
+  if (!g || g->n_ratios < 1 || g->n_ratios > VC_CODEC_MAX_RATIOS || g->kernel_size < 1 || g->last_kernel_size < 1 ||
+      g->residual_kernel_size < 1 || g->num_residual_layers < 1 || g->num_residual_layers > 4 || g->dilation_growth_rate < 1 ||
+      g->dilation_growth_rate > 4)
+    return VC_EINVAL;
+  auto left_of = [&](int pt) { return g->causal ? pt : pt - pt / 2; };
+  o->pl = left_of(g->kernel_size - 1);
+  o->pr = g->kernel_size - 1 - o->pl;
+  long cl = 0, cr = 0, hop = 1;
+  long min_rows = 1;      // frames a window at the true start needs so that every layer's reflect padding mirrors positions inside it
+  for (int i = 0; i < g->n_ratios; ++i) {
+    const int st = g->ratios[i];
+    if (st < 1) return VC_EINVAL;
+    const int ptT = st, prT = g->causal ? ptT : ptT / 2, plT = ptT - prT;   // run_convT: kernel 2 * stride
+    cl = cl * st + st - plT;
+    cr = cr * st + plT;
+    hop *= st;
+    int dil = 1;
+    for (int j = 0; j < g->num_residual_layers; ++j) {
+      const int pt = (g->residual_kernel_size - 1) * dil, pl = left_of(pt);
+      cl += pl; cr += pt - pl;
+      min_rows = std::max(min_rows, std::max(pl, pt - pl) / hop + 1);
+      dil *= g->dilation_growth_rate;
+    }
+  }
+  {
+    const int pt = g->last_kernel_size - 1, pl = left_of(pt);
+    cl += pl; cr += pt - pl;
+    min_rows = std::max(min_rows, std::max(pl, pt - pl) / hop + 1);
+  }
+  // in frames: the LSTM output of frame p reaches the samples of frames (p - right) .. (p + left - 1)
+  o->left = 1 + (int)((cl + hop - 1) / hop);
+  o->right = (int)((cr + hop - 1) / hop);
+  // reflect padding at the true start mirrors frames 1..pad, and a clip no longer than its padding is zero-extended first
+  // (run_conv's L_ext): until more frames than that are known the first conv cannot tell which case it is in
+  o->start = g->pad_reflect ? std::max(std::max(o->pl, o->pr) + 1, (int)min_rows + o->pr) : 1;
   return VC_OK;
 }
 }  // namespace
@@ -1204,6 +1342,18 @@ extern "C" int vc_codec_finalize(vc_codec* c) {
   if ((rc = calloc_dev(c, &c->err_flag, (size_t)4))) return rc;
   CCHK(c, hipMemset(c->hzero, 0, (size_t)top * 4));
   CCHK(c, hipMemset(c->err_flag, 0, 16));
+  {   // the decode stream's own buffers
+    StreamGeom sg;
+    if (stream_geom(&g, &sg)) return cfail(c, VC_EINVAL, "codec config has no stream geometry");
+    vc_codec::DecStream& d = c->ds;
+    d.pl = sg.pl; d.pr = sg.pr; d.left = sg.left; d.right = sg.right; d.start = sg.start;
+    d.lat_cap = sg.pl + std::max(sg.pr, sg.start - 1) + 1;
+    d.y_cap = sg.left + sg.right;
+    if ((rc = calloc_dev(c, &d.lat, (size_t)d.lat_cap * D))) return rc;
+    if ((rc = calloc_dev(c, &d.y, (size_t)d.y_cap * top))) return rc;
+    if ((rc = calloc_dev(c, &d.h, (size_t)2 * 2 * top))) return rc;
+    if ((rc = calloc_dev(c, &d.c, (size_t)2 * top))) return rc;
+  }
   CCHK(c, hipHostMalloc((void**)&c->h_flag, 64));
   for (auto& ev : c->ev) CCHK(c, hipEventCreate(&ev));
   for (auto& ev : c->ev_l) CCHK(c, hipEventCreate(&ev));
@@ -1293,24 +1443,7 @@ extern "C" int vc_codec_decode_batch(vc_codec* c, const int64_t* codes_dev, int 
   int rc, Lo, L = T;
   if ((rc = run_conv(c, c->dec_first, c->latent, L, nullptr, c->A_raw, nullptr, &Lo, s, B))) return rc;
   if ((rc = run_lstm(c, c->dec_lstm, c->A_raw, L, nullptr, c->B_elu, s, B))) return rc;
-  float* elu = c->B_elu;
-  for (int i = 0; i < g.n_ratios; ++i) {
-    float* nelu = (elu == c->A_elu) ? c->B_elu : c->A_elu;
-    if ((rc = run_convT(c, c->dec_up[i], elu, L, c->A_raw, nelu, &Lo, s, B))) return rc;
-    L = Lo;
-    float* raw = c->A_raw;
-    elu = nelu;
-    if ((rc = run_res_units(c, c->dec_res[i], &raw, &elu, L, false, s, B))) return rc;
-  }
-  {
-    const int Ci = g.n_filters, Kw = g.last_kernel_size;
-    const int pt = Kw - 1;
-    const int pad = g.causal ? pt : pt - pt / 2;
-    const int mp = std::max(pad, pt - pad);
-    hipLaunchKernelGGL(conv_last_k, dim3((L + 255) / 256, B), dim3(256), (size_t)Kw * Ci * 4, s, elu, c->dec_last.w_raw,
-                       c->dec_last.bias, wav_dev, L, Ci, Kw, pad, g.pad_reflect, (g.pad_reflect && L <= mp) ? mp + 1 : L);
-  }
-  CCHK(c, hipGetLastError());
+  if ((rc = run_dec_back(c, L, wav_dev, s, B))) return rc;
   CCHK(c, hipEventRecord(c->ev[1], s));
   CCHK(c, hipMemcpyAsync(c->h_flag, c->err_flag, 4, hipMemcpyDeviceToHost, s));
   CCHK(c, hipStreamSynchronize(s));
@@ -1323,6 +1456,128 @@ extern "C" int vc_codec_decode_batch(vc_codec* c, const int64_t* codes_dev, int 
 }
 extern "C" int vc_codec_decode(vc_codec* c, const int64_t* codes_dev, int T, float* wav_dev, int wav_cap, void* stream) {
   return vc_codec_decode_batch(c, codes_dev, 1, T, wav_dev, wav_cap, stream);
+}
+
+// ---- chunked decode
+extern "C" int vc_codec_stream_geometry(const vc_codec_cfg* cfg, int* lookahead_frames, int* left_context_frames, int* start_frames) {
+  if (!cfg || !lookahead_frames || !left_context_frames) return VC_EINVAL;
+  StreamGeom sg;
+  if (stream_geom(cfg, &sg)) return VC_EINVAL;
+  *lookahead_frames = sg.pr + sg.right;
+  *left_context_frames = sg.left;
+  if (start_frames) *start_frames = sg.start;
+  return VC_OK;
+}
+
+extern "C" int vc_codec_decode_stream_begin(vc_codec* c) {
+  if (!c) return VC_EINVAL;
+  if (!c->finalized) return cfail(c, VC_ESTATE, "codec not finalized");
+  CCHK(c, hipSetDevice(c->device));
+  vc_codec::DecStream& d = c->ds;
+  const int top = c->dec_lstm.H;
+  // (the null stream: ordered against whatever stream the chunks will run on)
+  CCHK(c, hipMemset(d.h, 0, (size_t)2 * 2 * top * 4));
+  CCHK(c, hipMemset(d.c, 0, (size_t)2 * top * 4));
+  CCHK(c, hipDeviceSynchronize());
+  d.fed = d.proc = d.emitted = 0;
+  d.n_lat = d.n_y = 0; d.hcur = 0;
+  d.open = true;
+  return VC_OK;
+}
+
+extern "C" int vc_codec_decode_stream(vc_codec* c, const int64_t* codes_dev, int stride, int n, int last, float* wav_dev,
+                                      int wav_cap, int* n_samples_out, void* stream) {
+  if (n < 0 || (n > 0 && (!codes_dev || stride < n)) || !wav_dev || wav_cap < 0 || !n_samples_out)
+    return cfail(c, VC_EINVAL, "null/invalid argument to vc_codec_decode_stream");
+  if (!c || !c->finalized) return cfail(c, VC_ESTATE, "codec not finalized");
+  vc_codec::DecStream& d = c->ds;
+  if (!d.open) return cfail(c, VC_ESTATE, "no decode stream is open (call vc_codec_decode_stream_begin)");
+  const vc_codec_cfg& g = c->cfg;
+  const int D = g.hidden, top = c->dec_lstm.H, hop = c->hop;
+  // ---- the plan of this call, on the host: frames through the front half (P), frames handed out (E)
+  const long F = d.fed + n;
+  const int rows_lat = d.n_lat + n;                       // the latent window: frames [w0, F)
+  const long w0 = F - rows_lat;
+  // the first conv of frame t needs frames up to t + pr; at `last` the true end is known and gets the one-shot call's padding
+  const long P = last ? F : (F >= d.start ? std::max(d.proc, F - d.pr) : d.proc);
+  const int np = (int)(P - d.proc);
+  const long E = last ? F : std::max(d.emitted, P - d.right);
+  const int ne = (int)(E - d.emitted);
+  const int rows_y = d.n_y + np;                          // the window of LSTM outputs: frames [y0, P)
+  const long y0 = P - rows_y;
+  if (rows_lat > c->T_max - 1 || rows_y > c->T_max - 1)
+    return cfail(c, VC_ECAP, "chunk of %d frames (+ %d kept) exceeds the codec's capacity of %d frames per call", n, std::max(d.n_lat, d.n_y), c->T_max - 1);
+  if ((long)ne * hop > wav_cap) return cfail(c, VC_ECAP, "wav capacity %d < %ld", wav_cap, (long)ne * hop);
+  CCHK(c, hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->own_stream;
+  d.open = false;                                         // an error below leaves the stream closed; success re-opens it
+  CCHK(c, hipEventRecord(c->ev[0], s));
+  // ---- front half: every frame once.  Latent window = kept rows + the new look-ups
+  if (d.n_lat) CCHK(c, hipMemcpyAsync(c->latent, d.lat, (size_t)d.n_lat * D * 4, hipMemcpyDeviceToDevice, s));
+  if (n > 0) {
+    const long tot = (long)n * D;
+    hipLaunchKernelGGL(rvq_decode_stream_k, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, codes_dev, stride, c->E,
+                       c->latent + (size_t)d.n_lat * D, n, D, g.codebook_size, g.n_q, c->err_flag);
+  }
+  if (d.n_y) CCHK(c, hipMemcpyAsync(c->B_elu, d.y, (size_t)d.n_y * top * 4, hipMemcpyDeviceToDevice, s));
+  int rc;
+  if (np > 0) {
+    // the first conv over frames [proc, P), reading the window: an interior left edge has its pl real neighbours in the window
+    // (pad 0 there), the true start (w0 == 0) and, at `last`, the true end are the window's own edges and are padded as run_conv pads
+    const Conv& cv = c->dec_first;
+    const int lead = (int)(d.proc - w0);                  // window rows in front of the first output frame
+    if (lead > d.pl || (lead < d.pl && w0 != 0)) return cfail(c, VC_ESTATE, "internal: stream window lost its left context");
+    const int mp = std::max(d.pl, d.pr);
+    ConvArgs a;
+    memset(&a, 0, sizeof a);
+    a.x = c->latent; a.Wp = cv.Wp; a.bias = cv.bias; a.out_raw = c->A_raw;
+    a.L_in = rows_lat; a.T = np; a.Ci = cv.Ci; a.Co = cv.Co; a.Kw = cv.Kw;
+    a.s_in = 1; a.dil = 1; a.pad = d.pl - lead; a.reflect = g.pad_reflect;
+    a.L_ext = (g.pad_reflect && w0 == 0 && rows_lat <= mp) ? mp + 1 : rows_lat;     // only a whole clip decoded at `last` is that short
+    a.s_out = 1; a.o_off = 0; a.L_dst = np; a.w_phase_stride = cv.phase_stride;
+    a.nphase = 1; a.x_bstride = (long)rows_lat * cv.Ci; a.o_bstride = (long)np * cv.Co;
+    hipLaunchKernelGGL(conv_gemm_k, dim3((np + 127) / 128, (cv.Co + 31) / 32, 1), dim3(256), 0, s, a);
+    CCHK(c, hipGetLastError());
+    LstmCarry cy;
+    for (int l = 0; l < 2; ++l) {
+      cy.h_in[l] = d.h + ((size_t)d.hcur * 2 + l) * top;
+      cy.h_out[l] = d.h + ((size_t)(d.hcur ^ 1) * 2 + l) * top;
+      cy.c[l] = d.c + (size_t)l * top;
+    }
+    if ((rc = run_lstm(c, c->dec_lstm, c->A_raw, np, nullptr, c->B_elu + (size_t)d.n_y * top, s, 1, &cy))) return rc;
+    d.hcur ^= 1;
+  }
+  // ---- what the next call needs: latents of frames [P - pl, F), LSTM outputs of frames [E - (left - 1), P)
+  int keep_lat = 0, keep_y = 0;
+  if (!last) {
+    const long l0 = std::max(w0, P - d.pl), k0 = std::max(y0, E - (d.left - 1));
+    keep_lat = (int)(F - l0); keep_y = (int)(P - k0);
+    if (keep_lat > d.lat_cap || keep_y > d.y_cap) return cfail(c, VC_ESTATE, "internal: stream context %d / %d rows exceeds %d / %d", keep_lat, keep_y, d.lat_cap, d.y_cap);
+    if (keep_lat) CCHK(c, hipMemcpyAsync(d.lat, c->latent + (size_t)(l0 - w0) * D, (size_t)keep_lat * D * 4, hipMemcpyDeviceToDevice, s));
+    if (keep_y) CCHK(c, hipMemcpyAsync(d.y, c->B_elu + (size_t)(k0 - y0) * top, (size_t)keep_y * top * 4, hipMemcpyDeviceToDevice, s));
+  }
+  // ---- back half over the window of LSTM outputs; only frames [emitted, E) leave.  The window's edges are the true ends of the
+  // signal or lie left - 1 / right frames outside that range, which is as far as a missing neighbour is felt (stream_geom)
+  if (ne > 0) {
+    if (y0 != 0 && d.emitted - y0 < d.left - 1) return cfail(c, VC_ESTATE, "internal: stream window lost its LSTM context");
+    float* tmp = c->H_elu;                                // free once the last residual unit has run
+    if ((rc = run_dec_back(c, rows_y, tmp, s, 1))) return rc;
+    CCHK(c, hipMemcpyAsync(wav_dev, tmp + (size_t)(d.emitted - y0) * hop, (size_t)ne * hop * 4, hipMemcpyDeviceToDevice, s));
+  }
+  CCHK(c, hipEventRecord(c->ev[1], s));
+  CCHK(c, hipMemcpyAsync(c->h_flag, c->err_flag, 4, hipMemcpyDeviceToHost, s));
+  // the arenas are shared with the blocking calls: nothing of this chunk is in flight when the call returns
+  CCHK(c, hipStreamSynchronize(s));
+  CCHK(c, hipEventElapsedTime(&c->last_ms, c->ev[0], c->ev[1]));
+  if (*c->h_flag) {
+    (void)hipMemset(c->err_flag, 0, 4);
+    return cfail(c, VC_EINVAL, "code index outside [0, %d)", g.codebook_size);
+  }
+  if ((rc = check_lstm_flag(c))) return rc;
+  d.fed = F; d.proc = P; d.emitted = E; d.n_lat = keep_lat; d.n_y = keep_y;
+  d.open = !last;
+  *n_samples_out = ne * hop;
+  return VC_OK;
 }
 
 extern "C" int vc_codec_debug_latent(vc_codec* c, float* host_dst, int64_t n_floats) {

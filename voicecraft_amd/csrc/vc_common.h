@@ -429,6 +429,14 @@ struct RepackArgs {
 };
 hipError_t vc_launch_repack(const RepackArgs& a, hipStream_t s);
 hipError_t vc_launch_assemble(const AssembleArgs& a, hipStream_t s);
+struct StreamGatherArgs {   // vc_tts_stream_next: the frames of sequence 0 that `rows` finished rows of its gen buffer make complete
+  const SeqState* st;       // sequence 0's state (later steps may be writing it: only what the finished rows fixed is trusted)
+  const int* gen;           // [max_steps][K]
+  int K, rows, first, cap;  // frames [first, first + n) -> out [K][cap], n <= cap
+  int64_t* out;
+  int* host_n;              // pinned: receives n
+};
+hipError_t vc_launch_stream_gather(const StreamGatherArgs& a, hipStream_t s);
 
 // ---- training objective, teacher-forced (vc_eval_forward; VoiceCraft.forward, models/voicecraft.py:472-559)
 struct CeArgs {            // cross-entropy and top-10 membership of up to VC_ROWS logits rows against their targets

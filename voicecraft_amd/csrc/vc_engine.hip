@@ -95,6 +95,8 @@ struct vc_engine {
   std::vector<int> repack_at;           // decode_loop: the batch index before which each re-pack of the last call was queued
 
   hipStream_t own_stream = nullptr;     // used when the caller passes the null stream (not capturable)
+  hipStream_t side_stream = nullptr;    // vc_tts_stream_next gathers finished frames here: never behind the decode stream's queued graphs
+  struct TtsStream* ts = nullptr;       // the open streaming TTS call (vc_tts_stream_begin .. vc_tts_stream_end), else NULL
   // Non-temporal weight loads of the decode kernels, per matrix: bit 0 QKV, 1 out-projection, 2 FFN-up, 3 FFN-down, 4 heads-1, 5 heads-2.
   // Option "nt" (VC_NT).  Until round 4 the compiled QKV / out-projection / heads-2 kernels carried NO such load whatever this said (the
   // compiler merged the kernel's two load arms and dropped the hint): 28 reproduces that mix, 63 = every matrix (default), 0 = none.
@@ -835,24 +837,38 @@ int decode_step(vc_engine* e, const SampleArgs& sa, int B, int rps, bool grouped
 // always waiting when the running one ends (measured before: ~8 us of idle GPU per graph launch and ~100 us
 // per blocking poll).  Steps replayed after the last sequence retired are no-ops (*n_active == 0).
 void refresh_opt_state(vc_engine* e);
+void drop_tts_stream(vc_engine* e);
 
+// The loop as a resumable object: begin / advance / finish.  The blocking calls drive it to its end in one go (decode_loop); the
+// streaming TTS call (vc_tts_stream_*) keeps it in the engine and advances it from vc_tts_stream_next, reading in between how many
+// steps the pacing has shown to be complete.  One copy of the pacing and of the graph cache.
 // groups: 0 = independent sequences, else the number of best-of-N groups the B0 sequences form (grouped sampler launches).
-int decode_loop(vc_engine* e, const SampleArgs& sa0, int B0, int rps, int groups, const vc_sample_cfg* sc,
-                int max_steps, int* steps_run, hipStream_t s, bool precapture_only = false) {
-  const int G = std::max(1, e->steps_per_graph);
-  const bool grouped = groups > 0;
-  const double t0 = now_ms();
-  if (precapture_only) e->host_ms[1] = e->host_ms[2] = 0;
+struct DecodeLoop {
+  vc_engine* e = nullptr;
+  SampleArgs sa{};
+  vc_sample_cfg sc{};
+  int B0 = 0, B = 0, rps = 1, groups = 0, G = 1, max_steps = 0;
+  bool grouped = false, can_shrink = false;
+  hipStream_t s = nullptr;
+  int launched = 0, batch = 0;
+  int complete = 0;        // decode steps the host KNOWS to have ended (the pacing event behind them was waited for)
+  bool over = false;       // nothing more will be queued: the last sequence retired, or the step budget is used up
+  double t1 = 0;
+
   // Rows per step.  A multi-utterance call starts with one row per sequence; when few enough sequences are left (option "shrink") the
   // live ones are re-packed onto the rows of a narrower step - the next power of two >= the live count - and the loop goes on with
   // that width's captured graph (graphs are keyed by width).  B / sa = the width in force.  Best-of-N calls of two or more groups shrink
   // too (a decided group keeps one live row); a call of ONE group does not: its step stays N rows wide, as it always has.
-  int B = B0;
-  SampleArgs sa = sa0;
-  const bool can_shrink = e->shrink && groups != 1 && rps == 1 && B0 > 1;
-  auto width_for = [](int live) { int p = 1; while (p < live) p *= 2; return p; };
+  void init(vc_engine* e_, const SampleArgs& sa0, int B0_, int rps_, int groups_, const vc_sample_cfg* sc_, int max_steps_, hipStream_t s_) {
+    e = e_; sa = sa0; sc = *sc_; B0 = B = B0_; rps = rps_; groups = groups_; max_steps = max_steps_; s = s_;
+    G = std::max(1, e->steps_per_graph);
+    grouped = groups > 0;
+    can_shrink = e->shrink && groups != 1 && rps == 1 && B0 > 1;
+    launched = batch = complete = 0; over = false;
+  }
+  static int width_for(int live) { int p = 1; while (p < live) p *= 2; return p; }
   // One captured graph per (rows per step, option state), kept for the life of the engine.
-  auto exec_for = [&](hipGraphExec_t* out) -> int {
+  int exec_for(hipGraphExec_t* out) {
     const auto key = std::make_pair(std::make_tuple(B, rps, grouped ? 1 : 0), e->opt_state);
     auto it = e->graphs.find(key);
     int rc = VC_OK;
@@ -879,9 +895,11 @@ int decode_loop(vc_engine* e, const SampleArgs& sa0, int B0, int rps, int groups
       if (graph) (void)hipGraphDestroy(graph);
     }
     return rc;
-  };
-  if (precapture_only) {       // every graph this call can need, captured before the caller starts its decode timer
-    if (!sc->use_graph) return VC_OK;
+  }
+  // every graph this call can need, captured before the caller starts its decode timer
+  int precapture() {
+    e->host_ms[1] = e->host_ms[2] = 0;
+    if (!sc.use_graph) return VC_OK;
     hipGraphExec_t exec = nullptr;
     int rc0 = exec_for(&exec);
     if (can_shrink)            // ... and the narrower widths a shrinking batch passes through
@@ -892,17 +910,23 @@ int decode_loop(vc_engine* e, const SampleArgs& sa0, int B0, int rps, int groups
       }
     return rc0;
   }
-  const double t1 = now_ms();
-  HIPCHK(e, hipMemsetAsync(e->step_ctr, 0, sizeof(int), s));      // the loop's first step is step 0 of batch 0 (SampleArgs.host_live slots)
-  e->repack_at.clear();
-  volatile int* live = e->h_flag + 8;
-  volatile int* live_n = e->h_flag + 9;                   // two slots: sequences still live as the LAST step of a batch of G steps found them
-  int launched = 0, rc = VC_OK, batch = 0;
-  while (launched < max_steps && rc == VC_OK) {
+  int begin() {
+    t1 = now_ms();
+    HIPCHK(e, hipMemsetAsync(e->step_ctr, 0, sizeof(int), s));      // the loop's first step is step 0 of batch 0 (SampleArgs.host_live slots)
+    e->repack_at.clear();
+    over = launched >= max_steps;
+    return VC_OK;
+  }
+  // One turn: wait for the older of the two batches in flight, then queue the next one.  Sets `over` instead when the loop has ended.
+  int advance() {
+    volatile int* live = e->h_flag + 8;
+    volatile int* live_n = e->h_flag + 9;                   // two slots: sequences still live as the LAST step of a batch of G steps found them
+    if (over) return VC_OK;
     if (batch >= 2) {   // pace: at most two batches in flight; the older one must have ended before a third is queued
       hipError_t we = hipEventSynchronize(e->ev_pace[batch & 1]);
-      if (we != hipSuccess) { rc = fail(e, VC_EHIP, "pacing event: %s", hipGetErrorString(we)); break; }
-      if (*live <= 0) break;
+      if (we != hipSuccess) { over = true; return fail(e, VC_EHIP, "pacing event: %s", hipGetErrorString(we)); }
+      complete = (batch - 1) * G;
+      if (*live <= 0) { over = true; return VC_OK; }
       if (can_shrink) {
         // the slot of the batch whose end has just been waited for (launched two iterations ago): the batch still in flight writes
         // the other one, so the width schedule is the same in every run of the same call - and with it, in bf16, every sampled token
@@ -914,32 +938,48 @@ int decode_loop(vc_engine* e, const SampleArgs& sa0, int B0, int rps, int groups
           ra.st = e->st; ra.st_fin = e->st_fin; ra.dec_h = e->dec_h; ra.row_seq = e->dec_row_seq; ra.row_pos = e->dec_row_pos;
           ra.logit_row = e->logit_row; ra.err = e->err_flag; ra.B_old = B; ra.B_new = w; ra.d = e->d;
           hipError_t re = vc_launch_repack(ra, s);
-          if (re != hipSuccess) { rc = fail(e, VC_EHIP, "re-pack launch: %s", hipGetErrorString(re)); break; }
+          if (re != hipSuccess) { over = true; return fail(e, VC_EHIP, "re-pack launch: %s", hipGetErrorString(re)); }
           B = w; sa = make_sample_args(e, w, rps);
           e->repack_at.push_back(batch);                  // counted in host_ms[6] once the call knows its live steps (tts_run)
         }
       }
     }
-    if (sc->use_graph) {
+    int rc = VC_OK;
+    if (sc.use_graph) {
       hipGraphExec_t exec = nullptr;
       rc = exec_for(&exec);
-      if (rc) break;
+      if (rc) { over = true; return rc; }
       hipError_t le = hipGraphLaunch(exec, s);
       if (le != hipSuccess) rc = fail(e, VC_EHIP, "hipGraphLaunch failed: %s", hipGetErrorString(le));
     } else {
       for (int i = 0; i < G && rc == VC_OK; ++i) rc = decode_step(e, sa, B, rps, grouped, s);
     }
-    if (rc) break;
+    if (rc) { over = true; return rc; }
     launched += G;
     hipError_t re = hipEventRecord(e->ev_pace[batch & 1], s);
-    if (re != hipSuccess) { rc = fail(e, VC_EHIP, "hipEventRecord: %s", hipGetErrorString(re)); break; }
+    if (re != hipSuccess) { over = true; return fail(e, VC_EHIP, "hipEventRecord: %s", hipGetErrorString(re)); }
     ++batch;
+    if (launched >= max_steps) over = true;
+    return VC_OK;
   }
-  e->host_ms[3] = now_ms() - t1;
-  e->host_ms[4] = 0;
-  e->host_ms[5] = launched;                               // decode steps LAUNCHED (a multiple of steps_per_graph; the tail are no-ops)
-  e->cur_rows = B;
-  if (steps_run) *steps_run = launched;
+  void finish(int* steps_run) {
+    e->host_ms[3] = now_ms() - t1;
+    e->host_ms[4] = 0;
+    e->host_ms[5] = launched;                               // decode steps LAUNCHED (a multiple of steps_per_graph; the tail are no-ops)
+    e->cur_rows = B;
+    if (steps_run) *steps_run = launched;
+  }
+};
+
+int decode_loop(vc_engine* e, const SampleArgs& sa0, int B0, int rps, int groups, const vc_sample_cfg* sc,
+                int max_steps, int* steps_run, hipStream_t s, bool precapture_only = false) {
+  DecodeLoop L;
+  L.init(e, sa0, B0, rps, groups, sc, max_steps, s);
+  if (precapture_only) return L.precapture();
+  int rc = L.begin();
+  if (rc) return rc;
+  while (rc == VC_OK && !L.over) rc = L.advance();
+  L.finish(steps_run);
   return rc;
 }
 
@@ -967,6 +1007,14 @@ int check_ready(vc_engine* e) {
   if (!e->finalized) return fail(e, VC_ESTATE, "weights are not finalized (call vc_finalize_weights)");
   hipError_t err = hipSetDevice(e->device);
   if (err != hipSuccess) return fail(e, VC_EHIP, "hipSetDevice: %s", hipGetErrorString(err));
+  return VC_OK;
+}
+
+// entry points that decode (or change what a decode step is): not while a streaming TTS call is open
+int check_idle(vc_engine* e) {
+  const int rc = check_ready(e);
+  if (rc) return rc;
+  if (e->ts) return fail(e, VC_ESTATE, "a streaming TTS call is open (vc_tts_stream_end closes it)");
   return VC_OK;
 }
 
@@ -1075,7 +1123,7 @@ extern "C" int vc_debug_plan(const vc_model_cfg* c, int compute_dtype, int rows,
 }
 
 extern "C" int vc_set_option(vc_engine* e, const char* name, const char* value) {
-  int rc = check_ready(e);
+  int rc = check_idle(e);
   if (rc) return rc;
   if (!name || !value) return fail(e, VC_EINVAL, "null argument to vc_set_option");
   rc = apply_option(e, name, value);
@@ -1133,6 +1181,8 @@ extern "C" void vc_destroy(vc_engine* e) {
   for (auto& ev : e->ev_pace) if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
+  if (e->side_stream) (void)hipStreamDestroy(e->side_stream);
+  drop_tts_stream(e);
   delete e;
 }
 
@@ -1369,6 +1419,7 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
   for (auto& ev : e->ev) HIPCHK(e, hipEventCreate(&ev));
   // a blocking stream: implicitly ordered after work the caller queued on the null stream
   HIPCHK(e, hipStreamCreate(&e->own_stream));
+  HIPCHK(e, hipStreamCreateWithFlags(&e->side_stream, hipStreamNonBlocking));
   // ---- options: the VC_* environment variables preset them, vc_set_option changes them at run time
   for (const auto& kv : {std::make_pair("VC_NT", "nt"), std::make_pair("VC_PREFILL_ROWS", "prefill_rows"), 
                          std::make_pair("VC_GRAPH_STEPS", "graph_steps"),
@@ -1422,9 +1473,13 @@ int collect_states(vc_engine* e, int B, hipStream_t s) {
 // The one TTS host path: U prompts (jobs) x n_samples (N) samples each, as U * N sequences.  Sample j of utterance u is the
 // sequence of slot u * N + j and, with N > 1, a member of best-of-N group u.  vc_tts is (1, N), vc_tts_multi (U, 1) and
 // vc_tts_multi_best_of (U, N).
-int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const vc_sample_cfg* sc,
-            const int64_t* forced, int n_forced, float* logits_out, int logit_steps, int* steps_out,
-            hipStream_t s, int shared_prefix = 0) {
+// tts_prepare: everything up to and including the first sample (graphs pre-captured ahead of the timers, prompts, prefill, state
+// upload, sampler values, the sample from the prefill logits); tts_finish: everything behind the decode loop (states, timing).  The
+// blocking calls run prepare - decode_loop - finish back to back (tts_run); the streaming call keeps the loop open in between.
+struct TtsPrep { SampleArgs sa; int B = 0, U = 0, N = 0, max_steps = 0; bool grouped = false; };
+int tts_prepare(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const vc_sample_cfg* sc,
+                const int64_t* forced, int n_forced, float* logits_out, int logit_steps,
+                hipStream_t s, int shared_prefix, TtsPrep* prep, bool* share_armed) {
   const int K = e->K;
   const int U = (int)jobs.size(), N = n_samples;
   if (N < 1) return fail(e, VC_EINVAL, "n_samples %d must be at least 1", N);
@@ -1453,12 +1508,6 @@ int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const 
     max_steps = std::max(max_steps, steps);
   }
   max_steps = std::min(max_steps, e->gen_cap);
-  // the device word share_len is non-zero only inside this call, whichever way it ends (a later vc_eval_forward or
-  // vc_edit would otherwise read positions below it from sequence 0's cache)
-  struct ShareGuard {
-    vc_engine* e; hipStream_t s; bool armed = false;
-    ~ShareGuard() { if (armed) (void)hipMemsetAsync(e->share_len, 0, sizeof(int), s); }
-  } share_guard{e, s};
   // (a first call of this shape / option state captures its decode graphs HERE, ahead of both timers - ADVICE r05: between ev[0] and
   // ev[1] the host time of capture + instantiation showed up as prefill time of that first call)
   {
@@ -1483,7 +1532,7 @@ int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const 
     }
     e->h_flag[2] = shared_prefix;
     HIPCHK(e, hipMemcpyAsync(e->share_len, e->h_flag + 2, sizeof(int), hipMemcpyHostToDevice, s));
-    share_guard.armed = shared_prefix > 0;
+    *share_armed = shared_prefix > 0;
     int rc = prefill_batch(e, pas, slots, s);
     if (rc) return rc;
   }
@@ -1532,13 +1581,17 @@ int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const 
   if (rc) return rc;
   // ---- first sample comes from the prefill logits, then the decode loop
   SampleArgs sa = make_sample_args(e, B, 1);
-  int steps_run = 0;
   HIPCHK(e, vc_launch_sample(sa, grouped, s));
   HIPCHK(e, hipEventRecord(e->ev[1], s));
-  rc = decode_loop(e, sa, B, 1, grouped ? U : 0, sc, max_steps, &steps_run, s);
-  if (rc) return rc;
+  prep->sa = sa; prep->B = B; prep->U = U; prep->N = N; prep->max_steps = max_steps; prep->grouped = grouped;
+  return VC_OK;
+}
+
+int tts_finish(vc_engine* e, const TtsPrep& prep, int* steps_out, hipStream_t s) {
+  const int B = prep.B;
+  const bool grouped = prep.grouped;
   HIPCHK(e, hipEventRecord(e->ev[2], s));
-  rc = collect_states(e, B, s);
+  int rc = collect_states(e, B, s);
   if (rc) return rc;
   if (grouped && (rc = check_err_flag(e, s))) return rc;      // the keep decisions' row check (advance_phase)
   HIPCHK(e, hipEventElapsedTime(&e->ms[0], e->ev[0], e->ev[1]));
@@ -1549,8 +1602,25 @@ int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const 
     for (int b = 0; b < B; ++b) m = std::max(m, e->h_st[b].total_steps);
     *steps_out = m;
   }
-  (void)steps_run;
   return VC_OK;
+}
+
+int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const vc_sample_cfg* sc,
+            const int64_t* forced, int n_forced, float* logits_out, int logit_steps, int* steps_out,
+            hipStream_t s, int shared_prefix = 0) {
+  // the device word share_len is non-zero only inside this call, whichever way it ends (a later vc_eval_forward or
+  // vc_edit would otherwise read positions below it from sequence 0's cache)
+  struct ShareGuard {
+    vc_engine* e; hipStream_t s; bool armed = false;
+    ~ShareGuard() { if (armed) (void)hipMemsetAsync(e->share_len, 0, sizeof(int), s); }
+  } share_guard{e, s};
+  TtsPrep prep;
+  int rc = tts_prepare(e, jobs, n_samples, sc, forced, n_forced, logits_out, logit_steps, s, shared_prefix, &prep, &share_guard.armed);
+  if (rc) return rc;
+  int steps_run = 0;
+  rc = decode_loop(e, prep.sa, prep.B, 1, prep.grouped ? prep.U : 0, sc, prep.max_steps, &steps_run, s);
+  if (rc) return rc;
+  return tts_finish(e, prep, steps_out, s);
 }
 
 // The sample utterance u of a tts_run keeps: the member that is kept, done and has its span (-1 if none terminated).
@@ -1582,13 +1652,140 @@ int assemble_tts(vc_engine* e, const TtsJob& j, int slot, int64_t* res, int res_
   return VC_OK;
 }
 
+// ---- the streaming TTS call: tts_prepare at begin, the DecodeLoop advanced from next, tts_finish + assemble_tts at end
 }  // namespace
+struct TtsStream {
+  TtsJob job{};
+  TtsPrep prep{};
+  DecodeLoop L{};
+  hipStream_t s = nullptr;
+  int emitted = 0;          // frames handed out so far
+  bool finished = false;    // tts_finish has run: h_st[0] holds the final state
+  int finish_rc = VC_OK;
+  int Tg = -1;              // generated frames, known once finished (-1: the sequence did not terminate)
+  int n_steps = 0;
+};
+namespace {
+void drop_tts_stream(vc_engine* e) {
+  delete e->ts;
+  e->ts = nullptr;
+}
+
+// once the loop is over: the blocking call's tail (states, timing); the frame count then comes from the sequence's state
+int stream_finalize(vc_engine* e) {
+  TtsStream& t = *e->ts;
+  if (t.finished) return t.finish_rc;
+  t.L.finish(nullptr);
+  t.finish_rc = tts_finish(e, t.prep, &t.n_steps, t.s);
+  t.finished = true;
+  const SeqState& st = e->h_st[0];
+  if (t.finish_rc == VC_OK && st.done && st.span >= 1) t.Tg = std::max(0, st.span_steps[0] - e->K);
+  return t.finish_rc;
+}
+
+// frames [t.emitted, ...) that `rows` finished rows of the gen buffer hold, un-shifted into the caller's block on the side stream
+int stream_gather(vc_engine* e, int rows, int64_t* codes, int cap, int* n_out) {
+  TtsStream& t = *e->ts;
+  StreamGatherArgs a;
+  memset(&a, 0, sizeof a);
+  a.st = e->st; a.gen = e->gen; a.K = e->K; a.rows = rows; a.first = t.emitted; a.cap = cap; a.out = codes; a.host_n = e->h_flag + 12;
+  e->h_flag[12] = 0;
+  HIPCHK(e, vc_launch_stream_gather(a, e->side_stream));
+  HIPCHK(e, hipStreamSynchronize(e->side_stream));       // the side stream only: the decode stream's queued graphs are not waited for
+  *n_out = e->h_flag[12];
+  return VC_OK;
+}
+}  // namespace
+
+extern "C" int vc_tts_stream_begin(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
+                                   const vc_sample_cfg* sc, const int64_t* forced_dev, int n_forced, void* stream) {
+  if (!x_dev || (!y_dev && T > 0) || !sc || Lx < 1 || T < 0 || n_forced < 0)
+    return fail(e, VC_EINVAL, "null/invalid argument to vc_tts_stream_begin");
+  int rc = check_idle(e);
+  if (rc) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+  std::vector<TtsJob> jobs{TtsJob{x_dev, Lx, y_dev, T}};
+  TtsPrep prep;
+  bool share_armed = false;
+  rc = tts_prepare(e, jobs, 1, sc, forced_dev, n_forced, nullptr, 0, s, 0, &prep, &share_armed);
+  if (rc) return rc;
+  TtsStream* t = new TtsStream();
+  t->job = jobs[0]; t->prep = prep; t->s = s;
+  t->L.init(e, prep.sa, prep.B, 1, 0, sc, prep.max_steps, s);
+  e->ts = t;
+  rc = t->L.begin();
+  if (rc) drop_tts_stream(e);
+  return rc;
+}
+
+extern "C" int vc_tts_stream_next(vc_engine* e, int min_frames, int64_t* codes_dev, int cap, int* first_frame, int* n_frames,
+                                  int* done) {
+  if (!codes_dev || cap < 1 || min_frames < 1 || min_frames > cap || !first_frame || !n_frames || !done)
+    return fail(e, VC_EINVAL, "null/invalid argument to vc_tts_stream_next (min_frames %d, cap %d)", min_frames, cap);
+  if (!e) return VC_EINVAL;
+  if (!e->ts) return fail(e, VC_ESTATE, "no streaming TTS call is open (vc_tts_stream_begin)");
+  HIPCHK(e, hipSetDevice(e->device));
+  TtsStream& t = *e->ts;
+  const int K = e->K;
+  for (;;) {
+    int rc, n = 0;
+    if (t.L.over) {
+      // the sequence has ended (or the step budget has): the count comes from its state, never from the launched multiple of graph_steps
+      if ((rc = stream_finalize(e))) return rc;
+      if (t.Tg > t.emitted && (rc = stream_gather(e, t.Tg + K, codes_dev, cap, &n))) return rc;
+      *first_frame = t.emitted; *n_frames = n;
+      t.emitted += n;
+      *done = t.emitted >= t.Tg;
+      return VC_OK;
+    }
+    // a live sequence: after S finished rows (the first sample + the steps whose pacing event has been waited for), frames
+    // < S - (K - 1) are complete (out[j][t] = rows[j + t][j]).  The kernel clamps the count to the sequence's own state.
+    const int rows = 1 + t.L.complete;
+    if (rows - (K - 1) - t.emitted >= min_frames) {
+      if ((rc = stream_gather(e, rows, codes_dev, cap, &n))) return rc;
+      if (n >= min_frames) {
+        *first_frame = t.emitted; *n_frames = n; *done = 0;
+        t.emitted += n;
+        return VC_OK;
+      }
+    }
+    if ((rc = t.L.advance())) return rc;
+  }
+}
+
+extern "C" int vc_tts_stream_end(vc_engine* e, int64_t* res_dev, int res_cap, int* gen_len, int* n_steps) {
+  if (res_dev && (!gen_len || res_cap < 0)) return fail(e, VC_EINVAL, "null/invalid argument to vc_tts_stream_end");
+  if (!e) return VC_EINVAL;
+  if (!e->ts) return fail(e, VC_ESTATE, "no streaming TTS call is open (vc_tts_stream_begin)");
+  HIPCHK(e, hipSetDevice(e->device));
+  TtsStream& t = *e->ts;
+  int rc = VC_OK;
+  if (!res_dev) {             // abort: wait for what is queued; the next call uploads every state afresh
+    if (!t.finished) {
+      t.L.finish(nullptr);
+      hipError_t se = hipStreamSynchronize(t.s);
+      if (se != hipSuccess) rc = fail(e, VC_EHIP, "hipStreamSynchronize: %s", hipGetErrorString(se));
+    }
+    drop_tts_stream(e);
+    return rc;
+  }
+  while (rc == VC_OK && !t.L.over) rc = t.L.advance();
+  if (rc == VC_OK) rc = stream_finalize(e);
+  if (rc == VC_OK) rc = assemble_tts(e, t.job, 0, res_dev, res_cap, gen_len, t.s);
+  if (rc == VC_OK) {
+    hipError_t se = hipStreamSynchronize(t.s);
+    if (se != hipSuccess) rc = fail(e, VC_EHIP, "hipStreamSynchronize: %s", hipGetErrorString(se));
+  }
+  if (rc == VC_OK && n_steps) *n_steps = t.n_steps;
+  drop_tts_stream(e);
+  return rc;
+}
 
 extern "C" int vc_tts(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
                       const vc_sample_cfg* sc, int n_samples, const int64_t* forced_dev, int n_forced,
                       int64_t* res_dev, int res_cap, int* gen_len, float* logits_dev, int logit_steps,
                       int* n_steps, void* stream) {
-  int rc = check_ready(e);
+  int rc = check_idle(e);
   if (rc) return rc;
   if (!x_dev || (!y_dev && T > 0) || !sc || !res_dev || !gen_len || n_samples < 1)
     return fail(e, VC_EINVAL, "null/invalid argument to vc_tts");
@@ -1611,7 +1808,7 @@ extern "C" int vc_tts_multi_best_of(vc_engine* e, int B, int n_samples, const in
                                     const int64_t* y_dev, const int32_t* y_off, const vc_sample_cfg* sc, int shared_text_prefix,
                                     const int64_t* forced_dev, int n_forced, int64_t* res_dev, int res_cap, int* gen_len,
                                     int* kept, float* logits_dev, int logit_steps, int* n_steps, void* stream) {
-  int rc = check_ready(e);
+  int rc = check_idle(e);
   if (rc) return rc;
   if (B < 1 || n_samples < 1 || !x_dev || !x_off || !y_dev || !y_off || !sc || !res_dev || !gen_len)
     return fail(e, VC_EINVAL, "null/invalid argument to vc_tts_multi (B %d, n_samples %d)", B, n_samples);
@@ -1752,7 +1949,7 @@ extern "C" int vc_edit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t
                        const vc_sample_cfg* sc, const int64_t* forced_dev, int n_forced,
                        int64_t* res_dev, int res_cap, int* res_len, float* logits_dev, int logit_steps,
                        int* n_steps, void* stream) {
-  int rc = check_ready(e);
+  int rc = check_idle(e);
   if (rc) return rc;
   if (!x_dev || !y_dev || !mask_intervals || !mask_values || !sc || !res_dev || !res_len)
     return fail(e, VC_EINVAL, "null argument to vc_edit");
@@ -1809,7 +2006,7 @@ extern "C" int vc_edit_multi(vc_engine* e, int B, const int64_t* x_dev, const in
                              const vc_sample_cfg* sc, const int64_t* forced_dev, int n_forced,
                              int64_t* res_dev, int res_cap, int* res_len, float* logits_dev, int logit_steps,
                              int* n_steps, void* stream) {
-  int rc = check_ready(e);
+  int rc = check_idle(e);
   if (rc) return rc;
   if (B < 1 || !x_dev || !x_off || !y_dev || !y_off || !mask_intervals || !span_off || !mask_values || !sc || !res_dev || !res_len)
     return fail(e, VC_EINVAL, "null/invalid argument to vc_edit_multi");
@@ -1950,7 +2147,7 @@ extern "C" int vc_eval_forward(vc_engine* e, int B, const int64_t* x_dev, const 
                                const int32_t* spans, const int32_t* span_off, const int32_t* mask_values,
                                double* nll_sum, int64_t* hits, int64_t* n_targets,
                                float* nll_dev, int32_t* tgt_dev, int64_t nll_cap, int64_t* n_rows_out, void* stream) {
-  int rc = check_ready(e);
+  int rc = check_idle(e);
   if (rc) return rc;
   if (B < 1 || !x_dev || !x_off || !y_dev || !y_off || !spans || !span_off || !mask_values || !nll_sum || !hits || !n_targets)
     return fail(e, VC_EINVAL, "null/invalid argument to vc_eval_forward");
@@ -2126,7 +2323,7 @@ extern "C" int vc_last_timing(const vc_engine* e, float ms[3]) {
 //   which = "step" : one whole decode step (forward + heads, sampler excluded) for n_rows sequences
 extern "C" int vc_bench_kernel(vc_engine* e, const char* which, int n_rows, int iters, float* avg_ms,
                                double* alg_bytes, void* stream) {
-  int rc = check_ready(e);
+  int rc = check_idle(e);
   if (rc) return rc;
   if (!which || n_rows < 1 || iters < 1 || !avg_ms) return fail(e, VC_EINVAL, "bad argument to vc_bench_kernel");
   const bool pf = std::string(which).rfind("pf_", 0) == 0;      // prefill block GEMM: up to VC_MAX_ROWS rows

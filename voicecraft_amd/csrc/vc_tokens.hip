@@ -959,6 +959,33 @@ hipError_t vc_launch_ce_reduce(const CeReduceArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(ce_reduce_k, dim3(a.K), dim3(256), 0, s, a);
   return hipGetLastError();
 }
+// The frames a streaming call may hand out: out[j][t] = gen[first + j + t][j].  `rows` rows of gen are final (the host waited
+// for the steps that wrote them); frame t needs rows t .. t + K - 1.  Steps still in flight may be updating the state, so it is
+// used only where the finished rows pin it: a sequence that ENDED within them (done, its span's step count <= rows) gives its
+// exact frame count, and rows the sequence never wrote (no-op steps replayed after it retired) are not counted.
+__global__ void stream_gather_k(const StreamGatherArgs a) {
+  __shared__ int s_n;
+  if (threadIdx.x == 0) {
+    const SeqState* sp = a.st;
+    const int rows = min(a.rows, sp->total_steps);
+    const int N = sp->span_steps[0];
+    const bool ended = sp->done && N > 0 && N <= rows;
+    const int avail = ended ? N - a.K : rows - (a.K - 1);
+    const int n = max(0, min(avail - a.first, a.cap));
+    s_n = n;
+    __hip_atomic_store(a.host_n, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  __syncthreads();
+  const int n = s_n;
+  for (int idx = threadIdx.x; idx < a.K * n; idx += blockDim.x) {
+    const int j = idx / n, t = idx - j * n;
+    a.out[(long)j * a.cap + t] = (int64_t)a.gen[(long)(a.first + j + t) * a.K + j];
+  }
+}
+hipError_t vc_launch_stream_gather(const StreamGatherArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(stream_gather_k, dim3(1), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
 hipError_t vc_launch_assemble(const AssembleArgs& a, hipStream_t s) {
   if (a.n_piece <= 0) return hipSuccess;
   hipLaunchKernelGGL(assemble_k, dim3(8, a.n_piece), dim3(256), 0, s, a);

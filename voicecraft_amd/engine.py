@@ -210,6 +210,65 @@ class VoiceCraftEngine:
             return out, gen, (logits[:, 0] if nb == 1 else logits)
         return out, gen
 
+    def inference_tts_stream(self, x, x_lens, y, top_k: int = -100, top_p: float = 1.0, temperature: float = 1.0,
+                             stop_repetition: int = 3, kvcache: int = 1, silence_tokens: Iterable[int] = (1388, 1898, 131),
+                             *kargs, chunk_frames: int = 8, _n_samples: int = 1, _seed=None, _forced=None,
+                             _forced_mode: str = "tokens"):
+        """inference_tts as a generator: yields (first_frame, codes [1, K, n]) while the decode loop runs, every chunk of at
+        least `chunk_frames` frames except the last; the chunks are contiguous from frame 0 and their concatenation is `gen` of
+        inference_tts with the same arguments.  After exhaustion `self.last_stream_result` holds the (res, gen) pair
+        inference_tts would have returned.  Closing the generator early aborts the call and leaves the engine usable.  One
+        utterance, one sample: best-of-N (inference_tts_batch) cannot stream - the kept sample is unknown until it terminates."""
+        if int(_n_samples) != 1:
+            raise AssertionError("inference_tts_stream: best-of-N (n_samples > 1, inference_tts_batch) cannot be streamed: "
+                                 "which sample is kept is unknown until one terminates")
+        assert int(chunk_frames) >= 1, chunk_frames
+        return self._tts_stream(x, x_lens, y, top_k, top_p, temperature, stop_repetition, silence_tokens, int(chunk_frames),
+                                _seed, _forced, _forced_mode)
+
+    @torch.no_grad()
+    def _tts_stream(self, x, x_lens, y, top_k, top_p, temperature, stop_repetition, silence_tokens, chunk, seed, forced, forced_mode):
+        xd, Lx, yd, T = self._prep(x, x_lens, y)
+        K = self.args.n_codebooks
+        sc = self._sample_cfg(top_k, top_p, temperature, stop_repetition, silence_tokens, seed, forced_mode)
+        budget = self._gen_budget(Lx, T + 1, self.args.encodec_sr // 5)
+        cap = T + budget
+        fd, forced_ptr, n_forced = self._forced_arg(forced, 1)
+        shift = int(self.args.n_special) if self.args.special_first else 0
+        self.last_stream_result = None
+        rc = self.lib.vc_tts_stream_begin(self._h, C.c_void_p(xd.data_ptr()), Lx, C.c_void_p(yd.data_ptr()), T, C.byref(sc),
+                                          forced_ptr, n_forced, self._stream())
+        check(rc, self._h, "vc_tts_stream_begin")
+        finished = False
+        side = torch.cuda.Stream(device=self.device) if shift else None
+        try:
+            ccap = max(chunk, budget + K)
+            first, n, done = C.c_int(0), C.c_int(0), C.c_int(0)
+            while not done.value:
+                buf = torch.empty((K, ccap), dtype=torch.int64, device=self.device)
+                check(self.lib.vc_tts_stream_next(self._h, chunk, C.c_void_p(buf.data_ptr()), ccap, C.byref(first), C.byref(n),
+                                                  C.byref(done)), self._h, "vc_tts_stream_next")
+                if n.value or not done.value:
+                    codes = buf[:, : n.value]
+                    if shift:
+                        # not on the null stream: a launch there would wait for the decode batches queued on the engine's stream
+                        with torch.cuda.stream(side):
+                            codes = codes - shift
+                        side.synchronize()
+                    yield first.value, codes.unsqueeze(0)     # final on the device: usable from any stream
+            res = torch.empty((K, cap), dtype=torch.int64, device=self.device)
+            gen_len, n_steps = C.c_int(0), C.c_int(0)
+            finished = True
+            check(self.lib.vc_tts_stream_end(self._h, C.c_void_p(res.data_ptr()), cap, C.byref(gen_len), C.byref(n_steps)),
+                  self._h, "vc_tts_stream_end")
+            self.last_steps = n_steps.value
+            Tg = gen_len.value
+            self.last_stream_result = (res[:, : T + Tg].unsqueeze(0) - shift, res[:, T: T + Tg].unsqueeze(0) - shift)
+        finally:
+            if not finished:      # closed early (or an error): abort, the engine stays usable
+                self.lib.vc_tts_stream_end(self._h, None, 0, None, None)
+            del fd, xd, yd
+
     @torch.no_grad()
     def inference_tts_batch(self, x, x_lens, y, top_k: int = -100, top_p: float = 1.0, temperature: float = 1.0,
                             stop_repetition: int = 3, kvcache: int = 1, batch_size: int = 5,
