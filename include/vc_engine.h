@@ -47,15 +47,24 @@ typedef struct vc_engine vc_engine;
 /* Model hyper-parameters = the fields of the reference's pickled `args` Namespace that
  * the inference path reads (models/voicecraft.py:105-185, config.py:55-84), plus the
  * capacities the engine sizes its HBM arenas with. */
+/* The token side of the model, accepted and tested ranges (tests/test_gpu_codebooks.py, tests/golden/model_*k*.npz):
+ *   n_codebooks K   2..VC_MAX_CODEBOOKS.  K = 1 is refused (VC_EINVAL): the reference's own TTS cuts the shifted prompt with
+ *                   [:, :-(n_codebooks-1)] (voicecraft.py:967, :1217), which drops the WHOLE audio prompt at one codebook, so there is
+ *                   nothing to be equal to.  (The engine-less pattern entry points below keep K = 1.)  Run against the reference
+ *                   at K = 2, 3, 4, 5, 6 and 8.
+ *   V               audio_vocab_size + n_special <= 2176 (64 lanes x 34 logits in the sampler).  Run at V = 515, 1028, 1540, 2051,
+ *                   2052 and 2176; the sampler alone at every V in {1, 2, 63, 64, 65, 2175, 2176} as well.
+ *   head_hidden P   a multiple of 256.  Run at 256, 512, 768 and 1024; 768 has no wide-decode form (steps of 17..64 rows run its
+ *                   heads on the weight-stationary kernel). */
 typedef struct vc_model_cfg {
   int32_t d_model;          /* args.d_model                                   */
   int32_t nhead;            /* args.nhead                                     */
   int32_t num_layers;       /* args.num_decoder_layers                        */
-  int32_t n_codebooks;      /* args.n_codebooks (K)                           */
+  int32_t n_codebooks;      /* args.n_codebooks (K), 2..VC_MAX_CODEBOOKS      */
   int32_t audio_vocab_size; /* args.audio_vocab_size (2048)                   */
-  int32_t n_special;        /* args.n_special; V = audio_vocab_size+n_special */
+  int32_t n_special;        /* args.n_special; V = audio_vocab_size+n_special <= 2176 */
   int32_t text_rows;        /* args.text_vocab_size + 1 (voicecraft.py:129)   */
-  int32_t head_hidden;      /* audio_vocab_size // 2   (voicecraft.py:183)    */
+  int32_t head_hidden;      /* audio_vocab_size // 2   (voicecraft.py:183); a multiple of 256 */
   int32_t empty_token;      /* args.empty_token                               */
   int32_t eog;              /* args.eog                                       */
   int32_t audio_pad_token;  /* args.audio_pad_token                           */

@@ -1,6 +1,7 @@
 """Generates tests/golden/*.npz by running the REAL reference.  TEST INFRASTRUCTURE ONLY.
 
 Run in the build container (needs /root/reference):   python -m oracle.gen_golden
+Named cases only (nothing else is rewritten):          python -m oracle.gen_golden --only tts_k8_greedy fwd_k8 ...
 Every fixture stores the inputs, the reference's outputs and (for model runs) the raw head logits
 of every decode step, sub-sampled, plus the first steps in full.  Checkpoints are not stored: they
 are regenerated from (preset, seed) by voicecraft_amd.synth, which uses a frozen RNG stream.
@@ -21,7 +22,7 @@ from oracle import ref_loader  # noqa: E402
 from voicecraft_amd import synth  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-FULL_STEPS = 3       # steps whose [K,V] logits are stored in full
+FULL_STEPS = 3       # steps whose [K,V] logits are stored in full (a case may lower it: spec["full_steps"])
 STRIDE = 61          # sub-sampling stride over V for all steps
 
 # name -> spec.  `arg_kw` feeds synth.make_args, `knobs` the reference call.
@@ -100,6 +101,37 @@ MODEL_CASES = {
     "edit_sampled_eog": dict(preset="tiny", arg_kw={}, wseed=3, prompt=(8, 60, 39), mode="edit", spans=[(12, 20), (30, 41)], tseed=98,
                              sd_kw=dict(mute_eos=False, boost=[(0, 500, 3.0), (0, 2049, 2.0)]),
                              knobs=dict(top_k=30, top_p=0.8, temperature=1.0, stop_repetition=2, kvcache=1)),
+    # ---- the token side of the model away from K = 4 / V = 2052 / P = 1024: codebook counts 2..8, audio vocabularies 512 / 1024 /
+    # 1536 (head_hidden 256 / 512 / 768) and V at the sampler's cap (2176).  `full_steps` keeps a K = 8 fixture at the size of the others
+    "tts_k8_greedy": dict(preset="tiny", arg_kw=dict(n_codebooks=8), wseed=21, prompt=(5, 17, 41), mode="tts", full_steps=1,
+                          knobs=dict(top_k=1, top_p=1.0, temperature=1.0, stop_repetition=3, kvcache=1)),
+    "tts_k2_greedy": dict(preset="tiny", arg_kw=dict(n_codebooks=2), wseed=22, prompt=(6, 21, 42), mode="tts",
+                          knobs=dict(top_k=1, top_p=1.0, temperature=1.0, stop_repetition=3, kvcache=1)),
+    "tts_k3_sampled_eos": dict(preset="tiny", arg_kw=dict(n_codebooks=3), wseed=23, prompt=(9, 30, 43), mode="tts", tseed=4323,
+                               sd_kw=dict(mute_eos=False, boost=[(0, 2051, 1.5), (0, 131, 4.0)]),
+                               knobs=dict(top_k=40, top_p=0.9, temperature=0.8, stop_repetition=2, kvcache=1)),
+    "tts_k8_sampled_eos": dict(preset="tiny", arg_kw=dict(n_codebooks=8), wseed=24, prompt=(9, 30, 44), mode="tts", tseed=4328,
+                               full_steps=1, sd_kw=dict(mute_eos=False, boost=[(0, 2051, 1.5), (0, 131, 4.0)]),
+                               knobs=dict(top_k=40, top_p=0.9, temperature=0.8, stop_repetition=2, kvcache=1)),
+    "edit_k8_2span": dict(preset="tiny", arg_kw=dict(n_codebooks=8), wseed=25, prompt=(13, 64, 45), mode="edit",   # (Lx 13: the rearranged
+                          # prompt has 8 more columns per piece than at K = 4 and must stay under the reference's 10 * Lx cap, :751)
+                          spans=[(10, 18), (40, 47)], full_steps=1, sd_kw=dict(mute_eos=False, boost=[(0, 2049, 0.35)]),
+                          knobs=dict(top_k=1, top_p=1.0, temperature=1.0, stop_repetition=2, kvcache=1)),
+    "edit_k2_sampled_eog": dict(preset="tiny", arg_kw=dict(n_codebooks=2), wseed=26, prompt=(8, 60, 46), mode="edit",
+                                spans=[(12, 20), (30, 41)], tseed=97,
+                                sd_kw=dict(mute_eos=False, boost=[(0, 500, 3.0), (0, 2049, 2.0)]),
+                                knobs=dict(top_k=30, top_p=0.8, temperature=1.0, stop_repetition=2, kvcache=1)),
+    "tts_batch3_k6_av1536": dict(preset="tiny", arg_kw=dict(n_codebooks=6, audio_vocab_size=1536), wseed=27, prompt=(8, 25, 47),
+                                 mode="tts_batch", tseed=779, full_steps=1,
+                                 sd_kw=dict(mute_eos=False, boost=[(0, 700, 4.0), (0, 1539, 2.2)]),
+                                 knobs=dict(top_k=20, top_p=1.0, temperature=1.3, stop_repetition=3, kvcache=1, batch_size=3)),
+    "tts_k5_av1024_hd128": dict(preset="tiny128", arg_kw=dict(n_codebooks=5, audio_vocab_size=1024), wseed=28, prompt=(5, 17, 48),
+                                mode="tts", knobs=dict(top_k=1, top_p=1.0, temperature=1.0, stop_repetition=-1, kvcache=1)),
+    "tts_av512_oldscheme": dict(preset="tiny", arg_kw=dict(audio_vocab_size=512, eos=-1, n_special=3, reduced_eog=0), wseed=29,
+                                prompt=(6, 19, 49), mode="tts",
+                                knobs=dict(top_k=1, top_p=1.0, temperature=1.0, stop_repetition=3, kvcache=1)),
+    "tts_vcap": dict(preset="tiny", arg_kw=dict(n_special=128), wseed=30, prompt=(6, 21, 50), mode="tts", full_steps=2,   # V = 2176 = 64 x 34
+                     knobs=dict(top_k=1, top_p=1.0, temperature=1.0, stop_repetition=3, kvcache=1)),
 }
 
 
@@ -123,6 +155,12 @@ FORWARD_CASES = {
     "fwd_hd128": dict(preset="tiny128", arg_kw={}, wseed=14, sd_kw=dict(mute_eos=False, boost=_BOOST12),
                       samples=[(10, 70, 27), (6, 52, 28)], spans=[[(1, 6), (30, 44)], [(26, 51)]],
                       codebook_weight="[5,1,0.5,0.1]"),
+    "fwd_k8": dict(preset="tiny", arg_kw=dict(n_codebooks=8), wseed=15, sd_kw=dict(mute_eos=False, boost=_BOOST12),
+                   samples=[(9, 44, 29), (6, 31, 30)], spans=[[(8, 15), (30, 36)], [(10, 22)]],
+                   codebook_weight="[5,1,0.5,0.1,2,0.25,1,3]"),
+    "fwd_k2_av1024": dict(preset="tiny", arg_kw=dict(n_codebooks=2, audio_vocab_size=1024), wseed=16,
+                          sd_kw=dict(mute_eos=False, boost=_BOOST12),
+                          samples=[(11, 52, 31), (7, 38, 32)], spans=[[(14, 27)], [(4, 9), (20, 28)]], codebook_weight="[5,1]"),
 }
 
 
@@ -217,7 +255,7 @@ def run_reference_case(spec):
     steps = len(captured) // K
     lg = torch.stack([torch.stack([captured[s * K + k] for k in range(K)], dim=0) for s in range(steps)], dim=0)
     lg = lg.reshape(steps, K, -1, lg.shape[-1])          # [steps,K,B,V]
-    out["logits_full"] = lg[:FULL_STEPS, :, 0].numpy().astype(np.float32)
+    out["logits_full"] = lg[:spec.get("full_steps", FULL_STEPS), :, 0].numpy().astype(np.float32)
     out["logits_sub"] = lg[:, :, 0, ::STRIDE].numpy().astype(np.float32)
     out["n_steps"] = np.int64(steps)
     out["x"], out["y"] = x.numpy(), y.numpy()
@@ -265,9 +303,29 @@ def gen_sampler():
     print("sampler.npz:", len(out), "arrays")
 
 
+def _write_model(name):
+    out = run_reference_case(MODEL_CASES[name])
+    np.savez_compressed(os.path.join(GOLDEN, f"model_{name}.npz"), **out)
+    print(f"model_{name}.npz: steps={int(out['n_steps'])} res={out['res'].shape}")
+
+
+def _write_forward(name):
+    out = run_reference_forward(FORWARD_CASES[name])
+    np.savez_compressed(os.path.join(GOLDEN, f"{name}.npz"), **out)
+    print(f"{name}.npz: loss={float(out['loss']):.4f} top10={out['top10acc_by_codebook']} ntoken={int(out['effective_ntoken'])}")
+
+
 def main():
     os.makedirs(GOLDEN, exist_ok=True)
     torch.set_num_threads(8)
+    if "--only" in sys.argv:                    # python -m oracle.gen_golden --only NAME ...: these cases, nothing else is rewritten
+        names = sys.argv[sys.argv.index("--only") + 1:]
+        unknown = [n for n in names if n not in MODEL_CASES and n not in FORWARD_CASES]
+        if unknown or not names:
+            sys.exit(f"--only: unknown case(s) {unknown}" if unknown else "--only needs at least one case name")
+        for n in names:
+            _write_model(n) if n in MODEL_CASES else _write_forward(n)
+        return
     if "--forward-only" in sys.argv:            # the training-objective fixtures only (the others are unchanged)
         for name, spec in FORWARD_CASES.items():
             out = run_reference_forward(spec)

@@ -80,6 +80,51 @@ def test_bad_config_is_rejected(lib):
     assert b"d_model" in lib.vc_last_error(None)
 
 
+def _cfg(**kw):
+    from voicecraft_amd._lib import ModelCfg
+    base = dict(d_model=256, nhead=4, num_layers=1, n_codebooks=4, audio_vocab_size=2048, n_special=4, text_rows=101,
+                head_hidden=1024, empty_token=2048, eog=2049, audio_pad_token=2050, eos=2051, reduced_eog=1,
+                encodec_sr=50, max_n_spans=3, max_seqs=1, max_positions=256)
+    base.update(kw)
+    return ModelCfg(**base)
+
+
+def test_one_codebook_is_refused_with_the_reason(lib):
+    """K = 1: the reference's TTS cuts the shifted prompt with [:, :-(n_codebooks-1)] = [:, :-0] and so drops the whole audio
+    prompt (models/voicecraft.py:967, :1217); the engine keeps it, so there is no parity to offer.  vc_create and the Python
+    mirror refuse; the engine-less pattern entry points keep K = 1 (their argument checks still pass for it)."""
+    h = C.c_void_p()
+    assert lib.vc_create(C.byref(_cfg(n_codebooks=1)), 0, C.byref(h)) == -1 and not h.value
+    msg = lib.vc_last_error(None)
+    assert b"n_codebooks 1" in msg and b"prompt" in msg, msg
+    assert lib.vc_create(C.byref(_cfg(n_codebooks=0)), 0, C.byref(h)) == -1 and not h.value
+    assert lib.vc_create(C.byref(_cfg(n_codebooks=9)), 0, C.byref(h)) == -1 and not h.value
+    assert b"n_codebooks 9" in lib.vc_last_error(None)
+    from voicecraft_amd import synth
+    from voicecraft_amd.engine import VoiceCraftEngine
+    with pytest.raises(AssertionError, match="n_codebooks 1 unsupported.*prompt"):
+        VoiceCraftEngine(synth.make_args("tiny", n_codebooks=1), {}, device="cuda:0")
+    assert lib.vc_pattern_unshift(None, 1, 1, None, None) == 0       # N == K == 1: accepted, nothing to write
+    assert lib.vc_pattern_shift(None, 1, 1, 3, 0, None, None) == -1  # (null pointers are what is refused here, not K = 1)
+
+
+def test_vocabulary_and_head_width_limits(lib):
+    """V = audio_vocab_size + n_special may be at most 2176 (64 lanes x 34 logits in the sampler); head_hidden a multiple of 256."""
+    h = C.c_void_p()
+    assert lib.vc_create(C.byref(_cfg(n_special=129)), 0, C.byref(h)) == -1 and not h.value            # V = 2177
+    assert b"2177" in lib.vc_last_error(None) and b"2176" in lib.vc_last_error(None)
+    assert lib.vc_create(C.byref(_cfg(head_hidden=384)), 0, C.byref(h)) == -1 and not h.value
+    assert b"head_hidden 384" in lib.vc_last_error(None)
+    # the limits themselves pass the argument checks: what is left to fail without a GPU is the device, with a GPU nothing
+    for ok in (_cfg(n_special=128), _cfg(head_hidden=768, audio_vocab_size=1536, empty_token=1536, eog=1537, audio_pad_token=1538, eos=1539),
+               _cfg(n_codebooks=2), _cfg(n_codebooks=8)):
+        rc = lib.vc_create(C.byref(ok), 0, C.byref(h))
+        assert rc in (0, -3), (rc, lib.vc_last_error(None))
+        if rc == 0:
+            lib.vc_destroy(h)
+            h = C.c_void_p()
+
+
 def test_pattern_entry_points_validate_arguments(lib):
     assert lib.vc_pattern_shift(None, 1, 4, 3, 0, None, None) == -1
     assert lib.vc_pattern_unshift(None, 2, 4, None, None) == -1      # N < K

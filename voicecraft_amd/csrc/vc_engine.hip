@@ -1145,7 +1145,10 @@ extern "C" int vc_create(const vc_model_cfg* c, int hip_device, vc_engine** out)
   if (hd != 32 && hd != 64 && hd != 128)   // the attention kernel spreads a cached row over 4, 8, 16 or 32 lanes
     return fail(nullptr, VC_EINVAL, "head_dim %d must be 32, 64 or 128", hd);
   if ((hd & (hd - 1)) != 0) return fail(nullptr, VC_EINVAL, "head_dim %d must be a power of two", hd);
-  if (c->n_codebooks < 1 || c->n_codebooks > VC_MAX_CODEBOOKS) return fail(nullptr, VC_EINVAL, "n_codebooks %d unsupported", c->n_codebooks);
+  if (c->n_codebooks < 2)   // voicecraft.py:967, :1217 cut the shifted prompt with [:, :-(n_codebooks-1)]: at K = 1 that is [:, :-0], nothing is left
+    return fail(nullptr, VC_EINVAL, "n_codebooks %d unsupported: the reference's own TTS drops the whole audio prompt at one codebook "
+                "([:, :-(n_codebooks-1)]), so there is nothing to be equal to; 2..%d are supported", c->n_codebooks, VC_MAX_CODEBOOKS);
+  if (c->n_codebooks > VC_MAX_CODEBOOKS) return fail(nullptr, VC_EINVAL, "n_codebooks %d unsupported (max %d)", c->n_codebooks, VC_MAX_CODEBOOKS);
   const int V = c->audio_vocab_size + c->n_special;
   if (V > 64 * VC_VPL) return fail(nullptr, VC_EINVAL, "audio vocabulary %d too large (max %d)", V, 64 * VC_VPL);
   if (c->head_hidden % 256) return fail(nullptr, VC_EINVAL, "head_hidden %d must be a multiple of 256", c->head_hidden);
@@ -2304,6 +2307,13 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
     return VC_OK;
   }
   else if (n == "launch_counts") { host_src = vc_launch_counts; avail = VC_LC_N * 8; }     // process-wide census of kernel forms (vc_common.h)
+  else if (n == "stream") {         // the open streaming TTS call: {finished rows the host knows of, frames handed out, loop over}
+    if (!e->ts) return fail(e, VC_ESTATE, "no streaming TTS call is open (vc_tts_stream_begin)");
+    if (nbytes != 3 * 4) return fail(e, VC_ECAP, "debug buffer 'stream' holds 12 bytes");
+    const int32_t v[3] = {1 + e->ts->L.complete, e->ts->emitted, e->ts->L.over ? 1 : 0};
+    memcpy(host_dst, v, sizeof v);
+    return VC_OK;
+  }
   else return fail(e, VC_EINVAL, "unknown debug buffer '%s'", n.c_str());
   if (nbytes > avail) return fail(e, VC_ECAP, "debug buffer '%s' holds %lld bytes", n.c_str(), (long long)avail);
   if (host_src) { memcpy(host_dst, host_src, (size_t)nbytes); return VC_OK; }

@@ -716,8 +716,27 @@ __global__ __launch_bounds__(256) void advance_only_k(const SampleArgs a) {
   advance_phase(a, dy, blockIdx.x, true, &s_st, a.samp + blockIdx.x * (VC_MAX_CODEBOOKS + 2));
   store_state(a, blockIdx.x, &s_st);
 }
+// Above 64 KB of dynamic LDS a kernel needs its limit raised first (K = 8 with V > 2048: 8 x 2112 x 4 = 67,584 bytes).  Per kernel and
+// device, as the GEMM launchers do.  The static part of these kernels is SeqState + a few dozen words (gfx950 code object metadata:
+// group_segment_fixed_size 224 bytes for sample_fused_k, 144 for sample_only_k), so the largest request, 8 x 2176 x 4 = 69,632 bytes,
+// stays far inside the 160 KB a gfx950 workgroup may own.
+static hipError_t sample_lds_limit(const void* kern, size_t lds, size_t (&granted)[16]) {
+  if (lds <= 64 * 1024) return hipSuccess;
+  int dev = 0;
+  if (hipError_t ge = hipGetDevice(&dev); ge != hipSuccess) return ge;
+  if (dev >= 0 && dev < 16 && lds > granted[dev]) {
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    granted[dev] = lds;
+  }
+  return hipSuccess;
+}
 hipError_t vc_launch_sample(const SampleArgs& a, bool grouped, hipStream_t s) {
+  if (a.K < 1 || a.K > VC_MAX_CODEBOOKS || a.V < 1 || a.V > 64 * VC_VPL) return hipErrorInvalidValue;
   const size_t lds = (size_t)a.K * (((a.V + 63) >> 6) << 6) * sizeof(float);
+  static size_t granted_fused[16] = {0}, granted_only[16] = {0};
+  if (hipError_t e = sample_lds_limit(reinterpret_cast<const void*>(grouped ? sample_only_k : sample_fused_k), lds,
+                                      grouped ? granted_only : granted_fused); e != hipSuccess) return e;
   if (!grouped) {
     hipLaunchKernelGGL(sample_fused_k, dim3(a.B), dim3(256), lds, s, a);
   } else {

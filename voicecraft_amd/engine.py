@@ -67,6 +67,10 @@ class VoiceCraftEngine:
         assert a.audio_pad_token == a.audio_vocab_size + 2, a.audio_pad_token
         if a.eos > 0:
             assert a.eos != a.audio_pad_token and a.eos != a.empty_token, a.eos
+        # vc_create refuses one codebook too: the reference's TTS cuts the shifted prompt with [:, :-(n_codebooks-1)]
+        # (models/voicecraft.py:967, :1217), which at K = 1 is [:, :-0] - the whole audio prompt is dropped, so there is no result to equal
+        assert int(a.n_codebooks) >= 2, (f"n_codebooks {a.n_codebooks} unsupported: the reference's own TTS drops the whole audio prompt "
+                                         "at one codebook ([:, :-(n_codebooks-1)]); 2..8 are supported")
         self.args = a
         self.device = torch.device(device)
         if self.device.type != "cuda":

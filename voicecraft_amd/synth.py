@@ -26,13 +26,19 @@ PRESETS = {
 
 
 def make_args(preset: str = "giga830M", *, eos: int = 2051, n_special: int = 4, reduced_eog: int = 1,
-              n_codebooks: int = 4, max_n_spans: int = 3) -> Namespace:
-    """The `args` Namespace the reference pickles next to a checkpoint (config.py:55-84)."""
+              n_codebooks: int = 4, max_n_spans: int = 3, audio_vocab_size: int = 2048,
+              text_vocab_size: int = 100) -> Namespace:
+    """The `args` Namespace the reference pickles next to a checkpoint (config.py:55-84).
+
+    `empty` / `eog` / `pad` follow the audio vocabulary (voicecraft.py:132-134: V, V+1, V+2).  `eos` keeps its default
+    of 2051 only with the default vocabulary; with another one it becomes audio_vocab_size + 3 unless the caller set it."""
     d, h, l = PRESETS[preset]
+    if audio_vocab_size != 2048 and eos == 2051:
+        eos = audio_vocab_size + 3
     return Namespace(
         d_model=d, nhead=h, num_decoder_layers=l, n_codebooks=n_codebooks, audio_embedding_dim=d,
-        audio_vocab_size=2048, text_vocab_size=100, text_pad_token=100, empty_token=2048, eog=2049,
-        audio_pad_token=2050, eos=eos, n_special=n_special, special_first=0, reduced_eog=reduced_eog,
+        audio_vocab_size=audio_vocab_size, text_vocab_size=text_vocab_size, text_pad_token=text_vocab_size,
+        empty_token=audio_vocab_size, eog=audio_vocab_size + 1, audio_pad_token=audio_vocab_size + 2, eos=eos, n_special=n_special, special_first=0, reduced_eog=reduced_eog,
         max_n_spans=max_n_spans, encodec_sr=50, shuffle_mask_embedding=0,
         text_embedding_dropout=0.0, audio_embedding_dropout=0.0, text_positional_embedding_dropout=0.0,
         audio_positional_embedding_dropout=0.0, trm_dropout=0.0,
