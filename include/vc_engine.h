@@ -197,6 +197,45 @@ int vc_tts_stream_next(vc_engine* e, int min_frames, int64_t* codes_dev, int cap
                        int* first_frame, int* n_frames, int* done);
 int vc_tts_stream_end(vc_engine* e, int64_t* res_dev, int res_cap, int* gen_len, int* n_steps);
 
+/* ---- decode sessions: continuous batching of TTS requests (inference_tts semantics, one sample each).  A session keeps the decode
+ * loop open: requests are submitted at any time, each is prefilled into a free K/V slot between two graph batches and joins the
+ * running batch, and each result can be fetched as soon as its own sequence has ended - the batch is refilled instead of idling
+ * to its longest member.  The step width follows the live count both ways (the next power of two, captured graphs per width).
+ * The sampling controls (top_k, top_p, temperature, stop_repetition, silence_tokens, use_graph) are fixed at open; the seed is per
+ * request: a request draws on the Philox stream (its seed, sequence 0, its own step, codebook) - the stream of a lone vc_tts call with
+ * that seed - whatever slot it lands in.  Exact mode: every request's tokens are those of its own vc_tts call.  bf16: the tokens are a
+ * function of the submissions and of the turn each was made at (the admission schedule is decided from retirements of batches the
+ * host has seen end, never from how far the device runs ahead).
+ * Not part of a session, because they have no per-request form here: editing, best-of-N, a shared text prefix, logits_out and forced
+ * trajectories - the entry points below simply have no such arguments; use the blocking calls.
+ *   open     max_live in [1, max_seqs] slots.  Captures the step graphs of every width the session can pass through (the powers of two
+ *            up to the one for max_live), ahead of any timer.  VC_ESTATE while a streaming call or another session is open.  While a
+ *            session is open every other decode entry point, vc_set_option and vc_tts_stream_begin return VC_ESTATE.
+ *   submit   host-side checks at once, with vc_tts's codes: empty text (VC_EINVAL), a prompt that alone does not fit max_positions
+ *            (VC_ECAP).  The request joins a FIFO; *ticket identifies it.  x_dev / y_dev must stay valid until the ticket is fetched
+ *            or the session closed.
+ *   advance  one turn: wait for the older of the two batches in flight; note what it (or an earlier one) retired; admit from the FIFO
+ *            into the free slots, in order; queue the prefill of the admitted requests, the re-pack to the width now needed, their
+ *            first sample and the next batch.  tickets_out[0 .. *n_finished) = the requests found finished this turn, at most cap of
+ *            them: one there is no room for is reported by a later turn (and holds its slot until then), so cap >= max_live reports
+ *            every request in the turn that finds it.  If the queued work of a turn fails after requests were admitted, the session
+ *            is broken: this and every later submit / advance return the error (VC_ESTATE afterwards) until it is closed.
+ *            *idle = 1 when nothing is live, pending or in flight: an idle session queues nothing, and a later submit restarts it.
+ *   fetch    assembles a finished request exactly as vc_tts does (res_dev [K][res_cap], *gen_len, *n_steps = its own step count) and
+ *            frees its slot; res_dev = NULL drops it.  Unknown ticket: VC_EINVAL; unfinished: VC_ESTATE; ran out of positions before
+ *            its terminator: VC_ECAP, as vc_tts; an out-of-range token id in its x / y: VC_EINVAL naming the ticket.  A finished
+ *            request holds its slot until fetched (the slot's rows of the generated-token log are the result).
+ *   stats    [0] requests admitted, [1] of them admitted while other sequences were live, [2] turns, [3] widenings, [4] narrowings,
+ *            [5] sum over launched steps of the rows that were live (counted at retirement), [6] sum over launched steps of the step
+ *            width, [7] microseconds of decode-stream time spent on admissions (prefill + re-pack + first sample; HIP events).
+ *   close    waits for what is queued, drops everything pending and unfetched; the engine is reusable. */
+int vc_session_open(vc_engine* e, int max_live, const vc_sample_cfg* sc, void* stream);
+int vc_session_submit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T, uint64_t seed, int* ticket);
+int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* n_finished, int* idle);
+int vc_session_fetch(vc_engine* e, int ticket, int64_t* res_dev, int res_cap, int* gen_len, int* n_steps);
+int vc_session_stats(vc_engine* e, int64_t out[8]);
+int vc_session_close(vc_engine* e);
+
 /* ---- multi-utterance TTS (SURVEY.md §8f-1 / BASELINE config 5): B independent
  * (x, y) pairs decoded as one batch; each row follows inference_tts exactly.
  *   x_dev int64 [sum Lx], y_dev int64 [sum T][K] concatenated; *_off host arrays [B+1].

@@ -1,0 +1,130 @@
+"""Decode sessions (continuous batching) against what the blocking API offers for the same work, on ONE engine, interleaved pairs:
+python tools/session_bench.py [--preset giga830M] [--pairs 5] [--sizes 64:8,256:64]
+
+Workload: the ragged utterances of bench.py's ragged_block (giga830M shape, bf16, top-k 40, 150 prompt frames, the synthetic
+checkpoint's terminator muted, so an utterance of Lx phonemes ends at the reference's length cap: 10 Lx - 150 generated frames).  `N:L`
+= N utterances through L slots; utterance u has the phoneme count of ragged_block's utterance u mod L (40 .. 80, evenly spread), so
+every consecutive group of L utterances is exactly that block's batch.
+  * baseline: inference_tts_multi on consecutive groups of L utterances in input order - each call runs until its longest member ends;
+  * session:  inference_tts_queue(max_live = L) - a freed slot is refilled with the next utterance while the others go on decoding.
+Per size one JSON line: codec-tokens/s of both arms (median, min, max over the pairs) and the per-pair ratio; the mean number of live
+rows per launched step and the share of launched rows that were live (session: its own counters; baseline: from the utterances' step
+counts, with the launched rows simulated from the blocking loop's re-pack rule); the decode-stream time per admitted request (prefill +
+re-pack + first sample, HIP events).  Both arms produce the same number of frames per utterance (asserted)."""
+import argparse, json, os, statistics, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch
+from voicecraft_amd import synth
+from voicecraft_amd.engine import VoiceCraftEngine
+
+p = argparse.ArgumentParser()
+p.add_argument("--preset", default="giga830M")
+p.add_argument("--dtype", default="bf16")
+p.add_argument("--lx", type=int, default=80)
+p.add_argument("--lx-min", type=int, default=40)
+p.add_argument("--prompt-frames", type=int, default=150)
+p.add_argument("--top-k", type=int, default=40)
+p.add_argument("--pairs", type=int, default=5)
+p.add_argument("--sizes", default="64:8,256:64")
+args = p.parse_args()
+dev = torch.device("cuda", 0)
+a = synth.make_args(args.preset)
+K = a.n_codebooks
+sd = synth.make_state_dict(a, seed=0, perturb=False, mute_eos=True, fast=True)
+kn = dict(top_k=args.top_k, top_p=1.0, temperature=1.0, stop_repetition=3, silence_tokens=[1388, 1898, 131])
+
+
+def stats(v):
+    v = sorted(v)
+    return dict(median=round(statistics.median(v), 3), min=round(v[0], 3), max=round(v[-1], 3), n=len(v))
+
+
+def width_for(n):
+    w = 1
+    while w < n:
+        w *= 2
+    return w
+
+
+def simulate_blocking_rows(steps, G):
+    """(live row-steps, launched rows, launched steps) of ONE blocking call whose sequences take `steps` samples each: the first sample is
+    outside the loop; batch k of G steps runs at the width the re-pack rule gives from the live count at the end of batch k - 2."""
+    B = len(steps)
+    longest = max(steps) - 1
+    live_rows = sum(s - 1 for s in steps)
+    rows = n = 0
+    w, k = B, 0
+    while k * G < longest:
+        if k >= 2:
+            alive = sum(1 for s in steps if s - 1 > (k - 1) * G)
+            if alive >= 1:
+                w = min(w, width_for(alive))
+        rows += w * G
+        n += G
+        k += 1
+    return live_rows, rows, n
+
+
+for size in args.sizes.split(","):
+    N, L = (int(v) for v in size.split(":"))
+    lxs = [args.lx if L == 1 else args.lx_min + (args.lx - args.lx_min) * (u % L) // (L - 1) for u in range(N)]
+    prompts = [synth.random_prompt(a, lxs[u], args.prompt_frames, seed=1 + u) for u in range(N)]
+    xs = [q[0][0].to(dev) for q in prompts]
+    ys = [q[2][0].to(dev) for q in prompts]
+    eng = VoiceCraftEngine(a, sd, device=dev, dtype=args.dtype, max_seqs=L, max_positions=max(1024, args.lx * 11 + 64))
+    G = int(eng.options().split("g=")[1].split("|")[0].split(",")[0])
+
+    def baseline(seed):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        frames, sim = [], [0, 0, 0]
+        for g0 in range(0, N, L):
+            outs = eng.inference_tts_multi(xs[g0: g0 + L], ys[g0: g0 + L], _seed=seed + g0, **kn)
+            f = [int(gen.shape[2]) for res, gen in outs]
+            frames += f
+            for i, v in enumerate(simulate_blocking_rows([x + K for x in f], G)):
+                sim[i] += v
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        return dict(tok_s=sum(frames) * K / wall, wall_ms=wall * 1e3, frames=frames, live_rows=sim[0], launched_rows=sim[1], steps=sim[2])
+
+    def session(seed):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with eng.open_session(L, **kn) as sess:
+            tickets = [sess.submit(xs[u].reshape(1, -1), torch.tensor([lxs[u]]), ys[u].unsqueeze(0), seed=seed + u) for u in range(N)]
+            done = {t: gen for t, res, gen in sess.drain()}
+            torch.cuda.synchronize()
+            wall = time.perf_counter() - t0
+            st = sess.stats(timing=True)
+        frames = [int(done[t].shape[2]) for t in tickets]
+        return dict(tok_s=sum(frames) * K / wall, wall_ms=wall * 1e3, frames=frames, live_rows=st["live_rows"],
+                    launched_rows=st["launched_rows"], steps=(st["turns"] - 1) * G, admitted=st["admitted"],
+                    admitted_while_live=st["admitted_while_live"], widenings=st["widenings"], narrowings=st["narrowings"],
+                    admission_us=st["admission_us"])
+
+    baseline(0); session(0)                    # graphs captured, allocator warm
+    rows = {"baseline": [], "session": []}
+    for i in range(args.pairs):
+        order = ["baseline", "session"] if i % 2 == 0 else ["session", "baseline"]
+        for arm in order:
+            rows[arm].append(baseline(100 + i) if arm == "baseline" else session(100 + i))
+    for b, s in zip(rows["baseline"], rows["session"]):
+        assert b["frames"] == s["frames"], "both arms generate the same frames per utterance (the length cap ends every sequence)"
+    out = {"workload": f"{args.preset} {args.dtype}, top_k={args.top_k}, {N} utterances through {L} slots, Lx {min(lxs)}..{max(lxs)}, "
+                       f"{args.prompt_frames} prompt frames -> {min(rows['session'][0]['frames'])}..{max(rows['session'][0]['frames'])} generated frames",
+           "pairs": args.pairs, "graph_steps": G, "options": eng.options()}
+    for arm in ("baseline", "session"):
+        r = rows[arm]
+        out[arm] = {"codec_tokens_per_s": stats([v["tok_s"] for v in r]), "wall_ms": stats([v["wall_ms"] for v in r]),
+                    "mean_live_rows_per_launched_step": round(statistics.mean(v["live_rows"] / v["steps"] for v in r), 2),
+                    "live_share_of_launched_rows": round(statistics.mean(v["live_rows"] / v["launched_rows"] for v in r), 4),
+                    "launched_steps": r[0]["steps"]}
+    s0 = rows["session"]
+    out["session"].update({k: s0[0][k] for k in ("admitted", "admitted_while_live", "widenings", "narrowings")})
+    out["session"]["admission_stream_ms_per_request"] = stats([v["admission_us"] / 1e3 / v["admitted"] for v in s0])
+    out["session_vs_baseline_pct"] = stats([100.0 * (s["tok_s"] / b["tok_s"] - 1.0) for b, s in zip(rows["baseline"], rows["session"])])
+    print(json.dumps(out), flush=True)
+    del eng
+    torch.cuda.empty_cache()

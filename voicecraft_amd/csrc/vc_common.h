@@ -339,6 +339,12 @@ struct SampleDyn {
   const int64_t* forced;    // [n_forced][B][K] or null
   float* logits_out;        // [logit_steps][B][K][V] or null
   long long* dbg_ts;        // optional [16] shader-clock stamps of sequence 0 (diagnosis only)
+  // decode sessions only (vc_session_*): read by sample_session_k alone, and last, so that nothing the one-shot kernels read moves
+  const uint64_t* seed_tab; // [max_seqs] Philox key of the request in each slot: a request draws on (its seed, sequence 0, its step, codebook)
+  int* retire_rec;          // pinned host records, VC_SESS_REC ints per slot, written once by the block that retires the slot's sequence
+  const int* batch_id;      // device word: index of the graph batch the step belongs to (set between two batches by session_turn_k)
+  const int* row_base;      // device word: first row of the sequences admitted this turn (their first sample touches rows [*row_base, +grid))
+  const int* adm_slot;      // [grid] slot of each of them = the logits row its prefill left the first-step logits at
 };
 
 struct SampleArgs {         // engine-constant part (kernel argument)
@@ -370,6 +376,9 @@ struct SampleArgs {         // engine-constant part (kernel argument)
   float alpha_audio;
   int max_positions;
 };
+// retirement record of a slot: [0] batch stamp + 1 (0 = none), [1] total steps, [2] spans finished (0 = ran out of positions),
+// [3] steps of span 0, [4] error bits of the request's prompt (prompt_k; written at admission)
+#define VC_SESS_REC 8
 
 struct AssembleArgs {       // writes res [K][res_cap] from y and the generated spans
   const int64_t* y;         // [T][K]
@@ -428,6 +437,32 @@ struct RepackArgs {
   int B_old, B_new, d;
 };
 hipError_t vc_launch_repack(const RepackArgs& a, hipStream_t s);
+// One turn of a decode session, between two graph batches (vc_tokens.hip session_turn_k): stamps the next batch's index and, when the
+// width changes or requests are admitted, re-packs the live rows in order onto rows [0, n_live) of a step of B_new rows - narrower OR
+// wider -, lays the admitted requests' initial states on rows [n_live, n_live + n_new), makes the rest fillers and raises *n_active.
+struct SessTurnArgs {
+  SeqState* st;             // [B_old] in, [B_new] out
+  float* dec_h;
+  int* row_seq;
+  int* row_pos;
+  int* logit_row;
+  int* err;                 // bit 2 raised when the live and the admitted sequences do not fit B_new rows (nothing is moved)
+  int* n_active;
+  int* batch_id;
+  int* row_base;
+  int* adm_slot;            // [max_seqs]
+  uint64_t* seed_tab;       // [max_seqs] by slot
+  int* prompt_err;          // [max_seqs] by slot: prompt_k's error bits of the request prefilled into the slot (cleared here)
+  int* retire_rec;          // pinned host, [max_seqs][VC_SESS_REC]
+  int B_old, B_new, d, batch, repack, n_new;
+  int cap_mult, min_gen, term_token, kill_token;   // init_state of a TTS request (vc_engine.hip)
+  int slot[VC_MAX_SEQS], Lx[VC_MAX_SEQS], n_cols[VC_MAX_SEQS];
+  uint64_t seed[VC_MAX_SEQS];
+};
+hipError_t vc_launch_session_turn(const SessTurnArgs& a, hipStream_t s);
+// The session's sampler launches: first = false, one step of B rows (captured in the session's graphs); first = true, the first sample
+// of the n rows admitted this turn only (the older rows' logits are already consumed).
+hipError_t vc_launch_sample_session(const SampleArgs& a, bool first, int n, hipStream_t s);
 hipError_t vc_launch_assemble(const AssembleArgs& a, hipStream_t s);
 struct StreamGatherArgs {   // vc_tts_stream_next: the frames of sequence 0 that `rows` finished rows of its gen buffer make complete
   const SeqState* st;       // sequence 0's state (later steps may be writing it: only what the finished rows fixed is trusted)

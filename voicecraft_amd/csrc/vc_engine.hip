@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <deque>
 #include <map>
 #include <string>
 #include <tuple>
@@ -97,6 +98,13 @@ struct vc_engine {
   hipStream_t own_stream = nullptr;     // used when the caller passes the null stream (not capturable)
   hipStream_t side_stream = nullptr;    // vc_tts_stream_next gathers finished frames here: never behind the decode stream's queued graphs
   struct TtsStream* ts = nullptr;       // the open streaming TTS call (vc_tts_stream_begin .. vc_tts_stream_end), else NULL
+  struct Session* sess = nullptr;       // the open decode session (vc_session_open .. vc_session_close), else NULL
+  // decode sessions: per-slot Philox keys, the batch index the sampler stamps retirements with, where this turn's admitted rows start and
+  // whose they are, prompt_k's error bits by slot, the prefill's own gather rows (the decode step's logit_row stays the live rows'), and the
+  // pinned retirement records the host reads (vc_common.h VC_SESS_REC)
+  uint64_t* seed_tab = nullptr;
+  int *batch_id = nullptr, *row_base = nullptr, *adm_slot = nullptr, *prompt_err = nullptr, *sess_gather = nullptr;
+  int* h_rec = nullptr;
   // Non-temporal weight loads of the decode kernels, per matrix: bit 0 QKV, 1 out-projection, 2 FFN-up, 3 FFN-down, 4 heads-1, 5 heads-2.
   // Option "nt" (VC_NT).  Until round 4 the compiled QKV / out-projection / heads-2 kernels carried NO such load whatever this said (the
   // compiler merged the kernel's two load arms and dropped the hint): 28 reproduces that mix, 63 = every matrix (default), 0 = none.
@@ -714,7 +722,10 @@ int prefill_tiled(const vc_engine* e, long longest) {
 // prefill_rows_per_pass rows - so the weights are streamed once per pass for all sequences together, not
 // once per sequence - and the heads run on the last row of each prompt as soon as its pass is through.
 // pas[i] describes prompt i (x, y, segments); slots[i] is its sequence slot.
-int prefill_batch(vc_engine* e, std::vector<PromptArgs>& pas, const std::vector<int>& slots, hipStream_t s) {
+// sess: a decode session's admission - the prompts' error bits go to prompt_err[slot] (attributable to a request) and the heads gather
+// through sess_gather, so that nothing the live rows of the running batch own is written.
+int prefill_batch(vc_engine* e, std::vector<PromptArgs>& pas, const std::vector<int>& slots, hipStream_t s, bool sess = false) {
+  int* const gather = sess ? e->sess_gather : e->logit_row;
   const int chunk = e->prefill_rows_per_pass;
   size_t i0 = 0;
   while (i0 < pas.size()) {
@@ -743,9 +754,9 @@ int prefill_batch(vc_engine* e, std::vector<PromptArgs>& pas, const std::vector<
       PromptArgs& pa = pas[i];
       const int rows = pa.Lx + pa.n_cols - pa.skip;
       pa.seq = slots[i]; pa.row0 = row0;
-      pa.emb = e->emb; pa.row_seq = e->pre_row_seq; pa.row_pos = e->pre_row_pos; pa.err = e->err_flag;
+      pa.emb = e->emb; pa.row_seq = e->pre_row_seq; pa.row_pos = e->pre_row_pos; pa.err = sess ? e->prompt_err + slots[i] : e->err_flag;
       last[i - i0] = row0 + rows - 1;
-      pa.logit_row = e->logit_row + slots[i];
+      pa.logit_row = gather + slots[i];
       pa.logit_row_val = last[i - i0] % chunk;            // index of the prompt's last row inside its pass
       HIPCHK(e, vc_launch_prompt(pa, s));
       row0 += (rows + al - 1) & ~(al - 1);
@@ -761,7 +772,7 @@ int prefill_batch(vc_engine* e, std::vector<PromptArgs>& pas, const std::vector<
       if (rc) return rc;
       for (size_t i = i0; i < i1; ++i)
         if (last[i - i0] >= r0 && last[i - i0] < r0 + rs.n_rows)
-          if ((rc = run_heads(e, p, po, e->logit_row + slots[i], 1, 0, slots[i], nullptr, s))) return rc;
+          if ((rc = run_heads(e, p, po, gather + slots[i], 1, 0, slots[i], nullptr, s))) return rc;
     }
     i0 = i1;
   }
@@ -810,11 +821,12 @@ int push_sample_dyn(vc_engine* e, const vc_sample_cfg* sc, const int64_t* forced
   d.n_seq = n_seq;                                        // sequences of the call (row stride of forced / logits_out)
   d.n_group = n_group;                                    // samples per best-of-N group (advance_phase's keep decision)
   d.dbg_ts = getenv("VC_SAMPLER_TS") ? e->dbg_ts : nullptr;
+  d.seed_tab = e->seed_tab; d.retire_rec = e->h_rec; d.batch_id = e->batch_id; d.row_base = e->row_base; d.adm_slot = e->adm_slot;   // (sessions only)
   HIPCHK(e, hipMemcpyAsync(e->d_dyn, e->h_dyn, sizeof(SampleDyn), hipMemcpyHostToDevice, s));
   return VC_OK;
 }
 
-int decode_step(vc_engine* e, const SampleArgs& sa, int B, int rps, bool grouped, hipStream_t s) {
+int decode_step(vc_engine* e, const SampleArgs& sa, int B, int rps, bool grouped, hipStream_t s, bool sess = false) {
   RowSrc rs{};
   rs.h_in = e->dec_h; rs.row_seq = e->dec_row_seq; rs.row_pos = e->dec_row_pos;
   rs.n_rows = B * rps; rs.n_active = e->n_active;
@@ -825,7 +837,8 @@ int decode_step(vc_engine* e, const SampleArgs& sa, int B, int rps, bool grouped
   // rps == 1: logit_row[b] == b (vc_tokens.hip advance_phase); the 3-row span switch is single-sequence
   rc = run_heads(e, p, po, rps == 1 ? nullptr : e->logit_row, B, 0, 0, e->n_active, s);
   if (rc) return rc;
-  HIPCHK(e, vc_launch_sample(sa, grouped, s));
+  if (sess) HIPCHK(e, vc_launch_sample_session(sa, false, B, s));
+  else HIPCHK(e, vc_launch_sample(sa, grouped, s));
   return VC_OK;
 }
 
@@ -838,6 +851,7 @@ int decode_step(vc_engine* e, const SampleArgs& sa, int B, int rps, bool grouped
 // per blocking poll).  Steps replayed after the last sequence retired are no-ops (*n_active == 0).
 void refresh_opt_state(vc_engine* e);
 void drop_tts_stream(vc_engine* e);
+void drop_session(vc_engine* e);
 
 // The loop as a resumable object: begin / advance / finish.  The blocking calls drive it to its end in one go (decode_loop); the
 // streaming TTS call (vc_tts_stream_*) keeps it in the engine and advances it from vc_tts_stream_next, reading in between how many
@@ -849,6 +863,7 @@ struct DecodeLoop {
   vc_sample_cfg sc{};
   int B0 = 0, B = 0, rps = 1, groups = 0, G = 1, max_steps = 0;
   bool grouped = false, can_shrink = false;
+  bool sess = false;       // the steps of a decode session (sample_session_k): graphs of their own
   hipStream_t s = nullptr;
   int launched = 0, batch = 0;
   int complete = 0;        // decode steps the host KNOWS to have ended (the pacing event behind them was waited for)
@@ -869,7 +884,7 @@ struct DecodeLoop {
   static int width_for(int live) { int p = 1; while (p < live) p *= 2; return p; }
   // One captured graph per (rows per step, option state), kept for the life of the engine.
   int exec_for(hipGraphExec_t* out) {
-    const auto key = std::make_pair(std::make_tuple(B, rps, grouped ? 1 : 0), e->opt_state);
+    const auto key = std::make_pair(std::make_tuple(B, rps, sess ? 2 : grouped ? 1 : 0), e->opt_state);
     auto it = e->graphs.find(key);
     int rc = VC_OK;
     if (it != e->graphs.end()) {
@@ -879,7 +894,7 @@ struct DecodeLoop {
       hipGraph_t graph = nullptr;
       hipError_t be = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
       if (be != hipSuccess) rc = fail(e, VC_EHIP, "hipStreamBeginCapture failed: %s", hipGetErrorString(be));
-      for (int i = 0; i < G && rc == VC_OK; ++i) rc = decode_step(e, sa, B, rps, grouped, s);
+      for (int i = 0; i < G && rc == VC_OK; ++i) rc = decode_step(e, sa, B, rps, grouped, s, sess);
       if (be == hipSuccess) {
         hipError_t ce = hipStreamEndCapture(s, &graph);
         if (rc == VC_OK && ce != hipSuccess) rc = fail(e, VC_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
@@ -1015,6 +1030,7 @@ int check_idle(vc_engine* e) {
   const int rc = check_ready(e);
   if (rc) return rc;
   if (e->ts) return fail(e, VC_ESTATE, "a streaming TTS call is open (vc_tts_stream_end closes it)");
+  if (e->sess) return fail(e, VC_ESTATE, "a decode session is open (vc_session_close closes it)");
   return VC_OK;
 }
 
@@ -1186,6 +1202,8 @@ extern "C" void vc_destroy(vc_engine* e) {
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
   if (e->side_stream) (void)hipStreamDestroy(e->side_stream);
   drop_tts_stream(e);
+  drop_session(e);
+  if (e->h_rec) (void)hipHostFree(e->h_rec);
   delete e;
 }
 
@@ -1417,6 +1435,19 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
   HIPCHK(e, hipHostMalloc((void**)&e->h_flag, 64));
   memset(e->h_flag, 0, 64);
   HIPCHK(e, hipHostMalloc((void**)&e->h_dyn, sizeof(SampleDyn)));
+  HIPCHK(e, hipHostMalloc((void**)&e->h_rec, sizeof(int) * VC_SESS_REC * e->NS));
+  memset(e->h_rec, 0, sizeof(int) * VC_SESS_REC * e->NS);
+  if ((rc = dalloc(e, &e->seed_tab, (size_t)e->NS))) return rc;
+  if ((rc = dalloc(e, &e->batch_id, (size_t)4))) return rc;
+  if ((rc = dalloc(e, &e->row_base, (size_t)4))) return rc;
+  if ((rc = dalloc(e, &e->adm_slot, (size_t)e->NS))) return rc;
+  if ((rc = dalloc(e, &e->prompt_err, (size_t)e->NS))) return rc;
+  if ((rc = dalloc(e, &e->sess_gather, (size_t)e->NS))) return rc;
+  HIPCHK(e, hipMemset(e->seed_tab, 0, sizeof(uint64_t) * e->NS));
+  HIPCHK(e, hipMemset(e->batch_id, 0, 16));
+  HIPCHK(e, hipMemset(e->row_base, 0, 16));
+  HIPCHK(e, hipMemset(e->adm_slot, 0, sizeof(int) * e->NS));
+  HIPCHK(e, hipMemset(e->prompt_err, 0, sizeof(int) * e->NS));
   if ((rc = dalloc(e, &e->d_dyn, (size_t)1))) return rc;
   for (auto& ev : e->ev_pace) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   for (auto& ev : e->ev) HIPCHK(e, hipEventCreate(&ev));
@@ -1636,8 +1667,8 @@ int kept_sample(const vc_engine* e, int u, int N) {
   return keep;
 }
 
-int assemble_tts(vc_engine* e, const TtsJob& j, int slot, int64_t* res, int res_cap, int* gen_len, hipStream_t s) {
-  const SeqState& st = e->h_st[slot];
+// (st: the sequence's final state - the blocking calls read it back into h_st, a session rebuilds what is needed from the slot's record)
+int assemble_tts(vc_engine* e, const TtsJob& j, int slot, const SeqState& st, int64_t* res, int res_cap, int* gen_len, hipStream_t s) {
   if (!st.done || st.span < 1)
     return fail(e, VC_ECAP, "generation ran out of room before it terminated (max_positions %d): raise max_positions", e->S_max);
   const int N = st.span_steps[0];
@@ -1653,6 +1684,9 @@ int assemble_tts(vc_engine* e, const TtsJob& j, int slot, int64_t* res, int res_
   HIPCHK(e, vc_launch_assemble(a, s));
   *gen_len = Tg;
   return VC_OK;
+}
+int assemble_tts(vc_engine* e, const TtsJob& j, int slot, int64_t* res, int res_cap, int* gen_len, hipStream_t s) {
+  return assemble_tts(e, j, slot, e->h_st[slot], res, res_cap, gen_len, s);
 }
 
 // ---- the streaming TTS call: tts_prepare at begin, the DecodeLoop advanced from next, tts_finish + assemble_tts at end
@@ -1781,6 +1815,320 @@ extern "C" int vc_tts_stream_end(vc_engine* e, int64_t* res_dev, int res_cap, in
   }
   if (rc == VC_OK && n_steps) *n_steps = t.n_steps;
   drop_tts_stream(e);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------- decode sessions (continuous batching)
+// A session keeps the decode loop open and takes TTS requests at any time (vc_session_submit).  One TURN (vc_session_advance) is one
+// iteration of DecodeLoop::advance with the way in added:
+//   1. wait for the older of the two graph batches in flight;
+//   2. count the retirements stamped with a batch the host has now seen END (the sampler writes one pinned record per slot, stamped
+//      with the batch index session_turn_k laid down in front of that batch);
+//   3. admit from the FIFO into the free slots, in order, as many as fit;
+//   4. queue, on the decode stream: the prompts and ONE prefill of the admitted requests into their K/V slots, session_turn_k (stamp of the
+//      next batch; re-pack of the live rows onto the width now needed, narrower or wider; the admitted requests' initial states behind
+//      them; fillers; n_active raised), the first sample of the admitted rows alone, and the next batch of graph_steps steps.
+// What the host decides - who is admitted when, every width - depends only on the submissions, the turn each was made at and records
+// of batches that have ended: never on how far the device runs ahead.  The same schedule therefore gives the same tokens in bf16 too.
+// Width in force: the next power of two >= live sequences, capped by `top` (that power for max_live where the per-row buffers hold it,
+// else max_live itself, as a blocking call of max_live sequences starts at its own count).
+struct SessReq {
+  TtsJob job{};
+  uint64_t seed = 0;
+  int slot = -1;
+  int state = 0;            // 0 pending, 1 live, 2 finished
+  int total_steps = 0, span = 0, span_steps0 = 0, prompt_err = 0;
+};
+struct Session {
+  DecodeLoop L{};
+  hipStream_t s = nullptr;
+  vc_sample_cfg sc{};
+  int max_live = 0, top = 0;
+  int B = 0;                // rows of the step in force (0: nothing laid out yet)
+  int live = 0;             // admitted and not yet KNOWN to have retired
+  int batch = 0;            // index of the next graph batch (never reset: the retirement stamps are unique for the session's life)
+  int run_start = 0;        // first batch queued since the session was last idle: only batches from there on can be in flight
+  int next_ticket = 1;
+  std::deque<int> fifo;
+  std::map<int, SessReq> reqs;
+  std::vector<int> slot_ticket;      // [max_live] ticket holding the slot (live, or finished and not yet fetched), -1 = free
+  long long stats[8]{};
+  // decode-stream time of each admission (prefill + session_turn_k + first sample): event pairs, read once their batch has ended
+  hipEvent_t ev_adm[4][2]{};
+  int ev_turn[4]{-1, -1, -1, -1};
+  double adm_ms = 0;
+  // a turn whose queued work failed after requests had been admitted on the host: the device and the tables no longer agree, so every
+  // later submit / advance / fetch returns this error and the caller closes the session
+  bool broken = false;
+  std::string broken_msg;
+};
+namespace {
+int session_broken(vc_engine* e, const Session& t) {
+  return fail(e, VC_ESTATE, "the decode session failed in an earlier turn (%s): close it (vc_session_close)", t.broken_msg.c_str());
+}
+void drop_session(vc_engine* e) {
+  if (!e->sess) return;
+  for (auto& pr : e->sess->ev_adm)
+    for (auto& ev : pr) if (ev) (void)hipEventDestroy(ev);
+  delete e->sess;
+  e->sess = nullptr;
+}
+
+int session_width(const Session& t, int live) { return std::min(DecodeLoop::width_for(std::max(1, live)), t.top); }
+
+// the admission timings whose batch the host has seen end (all of them when `all`: the stream was synchronised)
+void session_read_timers(Session& t, int known, bool all) {
+  for (int i = 0; i < 4; ++i) {
+    if (t.ev_turn[i] < 0 || (!all && t.ev_turn[i] > known)) continue;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, t.ev_adm[i][0], t.ev_adm[i][1]) == hipSuccess) t.adm_ms += ms;
+    t.ev_turn[i] = -1;
+  }
+}
+
+// retirements stamped with a batch <= known (stamps are batch + 1 in the record)
+void session_note_retired(vc_engine* e, Session& t, int known, int* tickets_out, int cap, int* n_fin) {
+  for (int slot = 0; slot < t.max_live; ++slot) {
+    const int ticket = t.slot_ticket[slot];
+    if (ticket < 0) continue;
+    SessReq& r = t.reqs[ticket];
+    if (r.state != 1) continue;
+    volatile int* rec = e->h_rec + slot * VC_SESS_REC;
+    const int stamp = rec[0];
+    if (stamp == 0 || stamp - 1 > known) continue;
+    if (*n_fin >= cap) continue;                        // no room to report it: it stays live on the host and is reported by a later turn
+    r.state = 2;
+    r.total_steps = rec[1]; r.span = rec[2]; r.span_steps0 = rec[3]; r.prompt_err = rec[4];
+    t.live -= 1;
+    t.stats[5] += std::max(0, r.total_steps - 1);      // rows of launched steps that were live: every step of the request but its first sample
+    tickets_out[*n_fin] = ticket;
+    *n_fin += 1;
+  }
+}
+}  // namespace
+
+extern "C" int vc_session_open(vc_engine* e, int max_live, const vc_sample_cfg* sc, void* stream) {
+  int rc = check_idle(e);
+  if (rc) return rc;
+  if (!sc) return fail(e, VC_EINVAL, "null argument to vc_session_open");
+  if (max_live < 1 || max_live > e->B_max) return fail(e, VC_EINVAL, "vc_session_open: max_live %d outside [1, max_seqs = %d]", max_live, e->B_max);
+  hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+  Session* t = new Session();
+  t->s = s; t->sc = *sc; t->max_live = max_live;
+  t->top = DecodeLoop::width_for(max_live) <= e->NS ? DecodeLoop::width_for(max_live) : max_live;
+  t->slot_ticket.assign(max_live, -1);
+  auto bail = [&](int code) { e->sess = t; drop_session(e); return code; };
+  for (auto& pr : t->ev_adm)
+    for (auto& ev : pr)
+      if (hipEventCreate(&ev) != hipSuccess) return bail(fail(e, VC_EHIP, "hipEventCreate failed"));
+  // the sampling controls are the session's (one SampleDyn, as per call today); the seed is per request (SampleDyn.seed_tab)
+  if ((rc = push_sample_dyn(e, sc, nullptr, 0, nullptr, 0, max_live, s))) return bail(rc);
+  memset(e->h_rec, 0, sizeof(int) * VC_SESS_REC * e->NS);
+  e->h_flag[1] = 0; e->h_flag[8] = 0; e->h_flag[9] = 0; e->h_flag[10] = 0;
+  hipError_t he = hipMemsetAsync(e->n_active, 0, sizeof(int), s);
+  if (he == hipSuccess) he = hipMemsetAsync(e->step_ctr, 0, sizeof(int), s);
+  if (he == hipSuccess) he = hipMemsetAsync(e->batch_id, 0, sizeof(int), s);
+  if (he == hipSuccess) he = hipMemsetAsync(e->prompt_err, 0, sizeof(int) * e->NS, s);
+  if (he == hipSuccess) he = hipStreamSynchronize(s);       // (orders the reuse of the pinned sampler block, as check_err_flag does in a call)
+  if (he != hipSuccess) return bail(fail(e, VC_EHIP, "vc_session_open: %s", hipGetErrorString(he)));
+  e->repack_at.clear();
+  // every graph the session can pass through, ahead of any timer: the powers of two below `top`, and `top`
+  t->L.init(e, make_sample_args(e, t->top, 1), t->top, 1, 0, sc, 0, s);
+  t->L.sess = true;
+  e->host_ms[1] = e->host_ms[2] = 0;
+  if (sc->use_graph) {
+    hipGraphExec_t exec = nullptr;
+    for (int w = t->top; w >= 1 && rc == VC_OK; w = (w == t->top) ? DecodeLoop::width_for(w) / 2 : w / 2) {
+      t->L.B = w; t->L.sa = make_sample_args(e, w, 1);
+      rc = t->L.exec_for(&exec);
+    }
+    if (rc) return bail(rc);
+  }
+  e->sess = t;
+  return VC_OK;
+}
+
+extern "C" int vc_session_submit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T, uint64_t seed, int* ticket) {
+  if (!e) return VC_EINVAL;
+  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
+  if (e->sess->broken) return session_broken(e, *e->sess);
+  if (!x_dev || (!y_dev && T > 0) || !ticket) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_submit");
+  if (Lx < 1 || T < 0) return fail(e, VC_EINVAL, "empty text or negative prompt length");
+  const int n_cols = T + 1;
+  if (e->S_max - (Lx + n_cols) - 1 < e->K + 1)
+    return fail(e, VC_ECAP, "the prompt alone takes %d of max_positions %d", Lx + n_cols, e->S_max);
+  if (((Lx + n_cols + 63) & ~63) > e->emb_cap)
+    return fail(e, VC_ECAP, "a prompt of %d rows does not fit the prefill arena of %d rows", Lx + n_cols, e->emb_cap);
+  Session& t = *e->sess;
+  SessReq r;
+  r.job = TtsJob{x_dev, Lx, y_dev, T};
+  r.seed = seed;
+  const int id = t.next_ticket++;
+  t.reqs[id] = r;
+  t.fifo.push_back(id);
+  *ticket = id;
+  return VC_OK;
+}
+
+extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* n_finished, int* idle) {
+  if (!e) return VC_EINVAL;
+  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
+  if (!n_finished || !idle || cap < 0 || (cap > 0 && !tickets_out)) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_advance");
+  HIPCHK(e, hipSetDevice(e->device));
+  Session& t = *e->sess;
+  if (t.broken) return session_broken(e, t);
+  hipStream_t s = t.s;
+  const int G = t.L.G;
+  *n_finished = 0; *idle = 0;
+  t.stats[2] += 1;
+  // ---- 1, 2: the older batch in flight, and what it (or an earlier one) retired
+  int known = t.run_start - 1;
+  if (t.batch - t.run_start >= 2) {
+    HIPCHK(e, hipEventSynchronize(e->ev_pace[t.batch & 1]));
+    known = t.batch - 2;
+  }
+  session_note_retired(e, t, known, tickets_out, cap, n_finished);
+  session_read_timers(t, known, false);
+  // ---- 3: admission, FIFO, as many as have a free slot
+  SessTurnArgs ta;
+  memset(&ta, 0, sizeof ta);
+  std::vector<PromptArgs> pas;
+  std::vector<int> slots;
+  const int live_before = t.live;
+  for (int slot = 0; slot < t.max_live && !t.fifo.empty(); ++slot) {
+    if (t.slot_ticket[slot] >= 0) continue;
+    const int id = t.fifo.front();
+    t.fifo.pop_front();
+    SessReq& r = t.reqs[id];
+    r.slot = slot; r.state = 1;
+    t.slot_ticket[slot] = id;
+    const int j = ta.n_new++;
+    ta.slot[j] = slot; ta.Lx[j] = r.job.Lx; ta.n_cols[j] = r.job.T + 1; ta.seed[j] = r.seed;
+    PromptArgs pa;
+    fill_prompt_common(e, pa, r.job.x, r.job.Lx, r.job.y, r.job.T);
+    pa.n_seg = 1; pa.n_cols = r.job.T + 1;
+    pa.seg[0] = Segment{0, r.job.T + 1, 0, r.job.T, -1, -1};
+    pas.push_back(pa);
+    slots.push_back(slot);
+    volatile int* rec = e->h_rec + slot * VC_SESS_REC;      // the slot's record: empty until this request retires
+    for (int i = 0; i < VC_SESS_REC; ++i) rec[i] = 0;
+  }
+  const int n_new = ta.n_new;
+  if (t.live + n_new == 0) {
+    // nothing to decode: what is still queued is steps without a live sequence.  Wait for them and queue nothing more; a later
+    // submit (or the fetch that frees a slot for a pending request) restarts the loop.
+    if (t.batch > t.run_start) {
+      HIPCHK(e, hipStreamSynchronize(s));
+      session_note_retired(e, t, t.batch - 1, tickets_out, cap, n_finished);
+      session_read_timers(t, t.batch - 1, true);
+      t.run_start = t.batch;
+      if (int rc = check_err_flag(e, s)) return rc;        // (session_turn_k's row check; the stream is idle, so this costs nothing)
+    }
+    *idle = t.fifo.empty() ? 1 : 0;
+    return VC_OK;
+  }
+  // ---- 4: prefill of the admitted requests, the turn kernel, their first sample, the next batch.  The requests are admitted on the
+  // host already: if anything below fails the session is marked broken (see Session.broken)
+  const int rc4 = [&]() -> int {
+  const int w = session_width(t, t.live + n_new);
+  const int ei = t.batch & 3;
+  if (n_new > 0) {
+    HIPCHK(e, hipEventRecord(t.ev_adm[ei][0], s));
+    int rc = prefill_batch(e, pas, slots, s, true);
+    if (rc) return rc;
+  }
+  ta.st = e->st; ta.dec_h = e->dec_h; ta.row_seq = e->dec_row_seq; ta.row_pos = e->dec_row_pos; ta.logit_row = e->logit_row;
+  ta.err = e->err_flag; ta.n_active = e->n_active; ta.batch_id = e->batch_id; ta.row_base = e->row_base; ta.adm_slot = e->adm_slot;
+  ta.seed_tab = e->seed_tab; ta.prompt_err = e->prompt_err; ta.retire_rec = e->h_rec;
+  ta.B_old = t.B; ta.B_new = w; ta.d = e->d; ta.batch = t.batch; ta.repack = (n_new > 0 || w != t.B) ? 1 : 0;
+  {
+    const SeqState st0 = init_state(e, 1, 0, true, 1);      // (cap_len of Lx = 1 is the multiplier)
+    ta.cap_mult = st0.cap_len; ta.min_gen = st0.min_gen; ta.term_token = st0.term_token; ta.kill_token = st0.kill_token;
+  }
+  HIPCHK(e, vc_launch_session_turn(ta, s));
+  if (t.B > 0 && w > t.B) t.stats[3] += 1;
+  if (w < t.B) t.stats[4] += 1;
+  t.B = w;
+  t.L.B = w; t.L.sa = make_sample_args(e, w, 1);
+  if (n_new > 0) {
+    HIPCHK(e, vc_launch_sample_session(t.L.sa, true, n_new, s));
+    HIPCHK(e, hipEventRecord(t.ev_adm[ei][1], s));
+    t.ev_turn[ei] = t.batch;
+    t.stats[0] += n_new;
+    if (live_before > 0) t.stats[1] += n_new;
+    t.live += n_new;
+  }
+  int rc = VC_OK;
+  if (t.sc.use_graph) {
+    hipGraphExec_t exec = nullptr;
+    if ((rc = t.L.exec_for(&exec))) return rc;
+    HIPCHK(e, hipGraphLaunch(exec, s));
+  } else {
+    for (int i = 0; i < G && rc == VC_OK; ++i) rc = decode_step(e, t.L.sa, w, 1, false, s, true);
+    if (rc) return rc;
+  }
+  HIPCHK(e, hipEventRecord(e->ev_pace[t.batch & 1], s));
+  t.batch += 1;
+  t.stats[6] += (long long)w * G;
+  return VC_OK;
+  }();
+  if (rc4) { t.broken = true; t.broken_msg = e->err; }
+  return rc4;
+}
+
+extern "C" int vc_session_fetch(vc_engine* e, int ticket, int64_t* res_dev, int res_cap, int* gen_len, int* n_steps) {
+  if (!e) return VC_EINVAL;
+  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
+  Session& t = *e->sess;
+  auto it = t.reqs.find(ticket);
+  if (it == t.reqs.end()) return fail(e, VC_EINVAL, "vc_session_fetch: unknown ticket %d (never issued, or fetched already)", ticket);
+  if (it->second.state != 2) {
+    if (t.broken) return session_broken(e, t);
+    return fail(e, VC_ESTATE, "vc_session_fetch: the request of ticket %d has not finished", ticket);
+  }
+  HIPCHK(e, hipSetDevice(e->device));
+  const SessReq r = it->second;
+  // whatever the outcome the ticket is spent: the slot (its K/V rows, its rows of the generated-token log) is free for the next request
+  t.slot_ticket[r.slot] = -1;
+  t.reqs.erase(it);
+  if (!res_dev) return VC_OK;                               // dropped
+  if (!gen_len || res_cap < 0) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_fetch");
+  if (r.prompt_err & 1)
+    return fail(e, VC_EINVAL, "ticket %d: token id out of range in x or y (text rows %d, audio vocab %d)", ticket, e->cfg.text_rows, e->V);
+  SeqState st;
+  memset(&st, 0, sizeof st);
+  st.done = 1; st.span = r.span; st.span_steps[0] = r.span_steps0; st.total_steps = r.total_steps;
+  // on the side stream: the request's rows of the log are final (its batch has ended), and the decode stream's queued batches are not waited for
+  int rc = assemble_tts(e, r.job, r.slot, st, res_dev, res_cap, gen_len, e->side_stream);
+  if (rc) return rc;
+  HIPCHK(e, hipStreamSynchronize(e->side_stream));
+  if (n_steps) *n_steps = r.total_steps;
+  return VC_OK;
+}
+
+extern "C" int vc_session_stats(vc_engine* e, int64_t out[8]) {
+  if (!e) return VC_EINVAL;
+  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
+  if (!out) return fail(e, VC_EINVAL, "null argument to vc_session_stats");
+  const Session& t = *e->sess;
+  for (int i = 0; i < 7; ++i) out[i] = t.stats[i];
+  out[7] = (int64_t)(t.adm_ms * 1000.0);                    // microseconds of decode-stream time spent on admissions whose batch has ended
+  return VC_OK;
+}
+
+extern "C" int vc_session_close(vc_engine* e) {
+  if (!e) return VC_EINVAL;
+  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
+  HIPCHK(e, hipSetDevice(e->device));
+  Session& t = *e->sess;
+  int rc = VC_OK;
+  // wait for what is queued; the next call uploads every state afresh (vc_tts_stream_end with res_dev = NULL is the model)
+  hipError_t he = hipMemsetAsync(e->n_active, 0, sizeof(int), t.s);
+  if (he == hipSuccess) he = hipStreamSynchronize(t.s);
+  if (he != hipSuccess) rc = fail(e, VC_EHIP, "vc_session_close: %s", hipGetErrorString(he));
+  else rc = check_err_flag(e, t.s);                         // (reads and clears the flag word)
+  e->cur_rows = 0;
+  drop_session(e);
   return rc;
 }
 

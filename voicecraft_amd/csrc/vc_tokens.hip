@@ -246,7 +246,7 @@ __device__ __forceinline__ uint32_t kth_largest(const uint32_t (&key)[VC_VPL], i
 #define VC_TS(i) do { if (dy.dbg_ts && b == 0 && threadIdx.x == 0) dy.dbg_ts[i] = clock64(); } while (0)
 // The logits row of codebook k = wave does not depend on the sequence state: the kernels request it
 // before anything else (v0), so that the state's round trip and the row's overlap.
-__device__ __forceinline__ void preload_row(const SampleArgs& a, int b, float (&v0)[VC_VPL]) {
+__device__ __forceinline__ void preload_row(const SampleArgs& a, int b, float (&v0)[VC_VPL]) {      // b: the row of the logits buffer
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float* row = a.logits + ((long)b * a.K + min(wave, a.K - 1)) * a.V;
 #pragma unroll
@@ -326,8 +326,12 @@ __device__ __forceinline__ int filter_draw(int top_k, float top_p, float tempera
   return __builtin_amdgcn_readlane(tok, __builtin_amdgcn_readfirstlane(src_lane));
 }
 
-__device__ __forceinline__ void sample_phase(const SampleArgs& a, const SampleDyn& dy, int b, const SeqState* sp, int* xs,
-                                             float* s_rows, const float (&v0)[VC_VPL]) {
+// SESS (decode sessions, sample_session_k): the draw's Philox key is the request's own (SampleArgs.seed_tab by slot, sequence 0);
+// lrow = the row of the logits buffer (the step's row b, or, for the first sample of an admitted request, the row its prefill wrote).
+// SESS is a literal at every call site and the phases are inlined, so each kernel is compiled for its own value: the one-shot kernels
+// pass false and lrow = b and keep the code they had without the parameter (they carry no branch on it).
+__device__ __forceinline__ void sample_phase(const SampleArgs& a, const SampleDyn& dy, int b, int lrow, const SeqState* sp, int* xs,
+                                             float* s_rows, const float (&v0)[VC_VPL], const bool SESS) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // the fields this phase reads, fetched from LDS in one go
   const int st_done = sp->done, step = sp->total_steps, term = sp->term_token, kill = sp->kill_token, n_eog = sp->n_eog;
@@ -337,7 +341,7 @@ __device__ __forceinline__ void sample_phase(const SampleArgs& a, const SampleDy
   const int V = a.V;
   const int VP = ((V + 63) >> 6) << 6;
   for (int k = wave; k < a.K; k += 4) {
-    const float* row = a.logits + ((long)b * a.K + k) * V;
+    const float* row = a.logits + ((long)lrow * a.K + k) * V;
     float* sv = s_rows + k * VP;
     float v[VC_VPL];
     if (k == wave) {
@@ -388,7 +392,10 @@ __device__ __forceinline__ void sample_phase(const SampleArgs& a, const SampleDy
       bi = wave_min_i(bi);
     }
     VC_TS(2);
-    const float u = philox_uniform(dy.seed, (uint32_t)slot, (uint32_t)step, (uint32_t)k);
+    uint64_t seed = dy.seed;
+    uint32_t pseq = (uint32_t)slot;
+    if (SESS) { seed = dy.seed_tab[slot]; pseq = 0u; }       // the request's own key, whatever slot it landed in
+    const float u = philox_uniform(seed, pseq, (uint32_t)step, (uint32_t)k);
     int tok = filter_draw(dy.top_k, dy.top_p, dy.temperature, v, bv, V, u);
     if (dy.forced && dy.forced_mode == 1 && step < dy.n_forced)      // replay of recorded reference draws (parity tests)
       tok = (int)dy.forced[((long)step * dy.n_seq + slot) * a.K + k];
@@ -408,7 +415,10 @@ __device__ __forceinline__ void sample_phase(const SampleArgs& a, const SampleDy
 
 // Phase 2 (one block per sequence): advance the state machine, log the step's tokens and build
 // the next decode rows (embedding sum + position, voicecraft.py:1102-1116; span switch :838-858).
-__device__ void advance_phase(const SampleArgs& a, const SampleDyn& dy, int b, bool grouped, SeqState* sp, const int* xs) {
+// SESS (a literal at every call site, as in sample_phase): the block that retires a sequence writes the slot's record for the host
+// (SampleDyn.retire_rec), stamped with the index of the graph batch the step belongs to, next to the n_active update.
+__device__ void advance_phase(const SampleArgs& a, const SampleDyn& dy, int b, bool grouped, SeqState* sp, const int* xs,
+                              const bool SESS) {
   __shared__ int s_tok[VC_MAX_CODEBOOKS];
   __shared__ int s_mode;     // 0: row inactive, 1: one new row, 3: span switch (three rows), 4 / 5: a feed step of a switch (SeqState.feed)
   __shared__ int s_ylen, s_mask, s_Lx, s_keep;
@@ -528,6 +538,15 @@ __device__ void advance_phase(const SampleArgs& a, const SampleDyn& dy, int b, b
       }
       if (done) {
         sp->done = 1;
+        if (SESS) {                            // the host counts the retirement once it has waited for batch `stamp` (vc_engine.hip Session)
+          int* rec = dy.retire_rec + slot * VC_SESS_REC;
+          const int s0 = (span >= 1) ? sp->span_steps[0] : 0;
+          const int stamp = *dy.batch_id;
+          __hip_atomic_store(rec + 1, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          __hip_atomic_store(rec + 2, span, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          __hip_atomic_store(rec + 3, s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          __hip_atomic_store(rec + 0, stamp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
         if (atomicSub(a.n_active, 1) == 1)     // the last live sequence: tell the host loop without a stream operation
           __hip_atomic_store(a.host_active, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
@@ -651,10 +670,10 @@ __global__ __launch_bounds__(256) void sample_fused_k(const SampleArgs a) {
     dy.dbg_ts[32 + 2 * b] = wall_clock64();       // 100 MHz, one counter for the whole chip (clock64 is per XCD); read
   }                                               // after the state fetch (~1.3 us in), only when stamps are requested
   park_state(&s_st, sw);
-  sample_phase(a, dy, blockIdx.x, &s_st, s_xs, s_dyn, v0);
+  sample_phase(a, dy, blockIdx.x, blockIdx.x, &s_st, s_xs, s_dyn, v0, false);
   __syncthreads();
   VC_TS(6);
-  advance_phase(a, dy, blockIdx.x, false, &s_st, s_xs);
+  advance_phase(a, dy, blockIdx.x, false, &s_st, s_xs, false);
   VC_TS(8);
   store_state(a, blockIdx.x, &s_st);
   VC_TS(9);
@@ -702,7 +721,7 @@ __global__ __launch_bounds__(256) void sample_only_k(const SampleArgs a) {
     if (threadIdx.x == 0) a.samp[blockIdx.x * (VC_MAX_CODEBOOKS + 2) + a.K + 1] = 0;
     return;
   }
-  sample_phase(a, dy, blockIdx.x, &s_st, a.samp + blockIdx.x * (VC_MAX_CODEBOOKS + 2), s_dyn, v0);
+  sample_phase(a, dy, blockIdx.x, blockIdx.x, &s_st, a.samp + blockIdx.x * (VC_MAX_CODEBOOKS + 2), s_dyn, v0, false);
 }
 __global__ __launch_bounds__(256) void advance_only_k(const SampleArgs a) {
   __shared__ SeqState s_st;
@@ -713,7 +732,7 @@ __global__ __launch_bounds__(256) void advance_only_k(const SampleArgs a) {
   if (active == 0) return;
   const int b = blockIdx.x;
   park_state(&s_st, sw);
-  advance_phase(a, dy, blockIdx.x, true, &s_st, a.samp + blockIdx.x * (VC_MAX_CODEBOOKS + 2));
+  advance_phase(a, dy, blockIdx.x, true, &s_st, a.samp + blockIdx.x * (VC_MAX_CODEBOOKS + 2), false);
   store_state(a, blockIdx.x, &s_st);
 }
 // Above 64 KB of dynamic LDS a kernel needs its limit raised first (K = 8 with V > 2048: 8 x 2112 x 4 = 67,584 bytes).  Per kernel and
@@ -744,6 +763,46 @@ hipError_t vc_launch_sample(const SampleArgs& a, bool grouped, hipStream_t s) {
     hipLaunchKernelGGL(sample_only_k, dim3(a.B), dim3(256), lds, s, a);
     hipLaunchKernelGGL(advance_only_k, dim3(a.B), dim3(256), 0, s, a);
   }
+  return hipGetLastError();
+}
+
+// ---- decode sessions (vc_session_*): sample_fused_k with the session's three differences as a compile-time form, so that the
+// one-shot kernels keep their code.  FIRST = false: one step of the session's graph (row b = workgroup, logits row b).  FIRST = true:
+// the first sample of the requests admitted this turn - workgroup i takes row *row_base + i (where session_turn_k laid the request's
+// state) and the logits row of its slot (where its prefill left them); the older rows are not touched, and neither are the step
+// counter and the live words, which belong to whole steps.
+template <bool FIRST>
+__global__ __launch_bounds__(256) void sample_session_k(const SampleArgs a) {
+  __shared__ SeqState s_st;
+  __shared__ int s_xs[VC_MAX_CODEBOOKS + 2];
+  int b = blockIdx.x, lrow = blockIdx.x;
+  if (FIRST) { b = *a.dyn->row_base + (int)blockIdx.x; lrow = a.dyn->adm_slot[blockIdx.x]; }
+  float v0[VC_VPL];
+  preload_row(a, lrow, v0);
+  const int sw = fetch_state(a, b);
+  const int active = *a.n_active;
+  const SampleDyn dy = *a.dyn;
+  __builtin_amdgcn_sched_barrier(0);
+  if (active == 0) return;
+  if (!FIRST && blockIdx.x == 0 && threadIdx.x == 0) {
+    const int c = *a.step_ctr;
+    *a.step_ctr = c + 1;
+    __hip_atomic_store(a.host_live + ((c / a.graph_steps) & 1), active, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  park_state(&s_st, sw);
+  sample_phase(a, dy, b, lrow, &s_st, s_xs, s_dyn, v0, true);
+  __syncthreads();
+  advance_phase(a, dy, b, false, &s_st, s_xs, true);
+  store_state(a, b, &s_st);
+}
+hipError_t vc_launch_sample_session(const SampleArgs& a, bool first, int n, hipStream_t s) {
+  if (a.K < 1 || a.K > VC_MAX_CODEBOOKS || a.V < 1 || a.V > 64 * VC_VPL || n < 1 || n > VC_MAX_SEQS) return hipErrorInvalidValue;
+  const size_t lds = (size_t)a.K * (((a.V + 63) >> 6) << 6) * sizeof(float);
+  static size_t granted_step[16] = {0}, granted_first[16] = {0};
+  if (hipError_t e = sample_lds_limit(reinterpret_cast<const void*>(first ? sample_session_k<true> : sample_session_k<false>), lds,
+                                      first ? granted_first : granted_step); e != hipSuccess) return e;
+  if (first) hipLaunchKernelGGL(sample_session_k<true>, dim3(n), dim3(256), lds, s, a);
+  else hipLaunchKernelGGL(sample_session_k<false>, dim3(n), dim3(256), lds, s, a);
   return hipGetLastError();
 }
 
@@ -809,6 +868,91 @@ __global__ __launch_bounds__(256) void repack_k(const RepackArgs a) {
 hipError_t vc_launch_repack(const RepackArgs& a, hipStream_t s) {
   if (a.B_old < 1 || a.B_old > VC_MAX_SEQS || a.B_new < 1 || a.B_new > a.B_old || a.d > 2048) return hipErrorInvalidValue;
   hipLaunchKernelGGL(repack_k, dim3(1), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// ---- decode sessions: repack_k's compaction for a step that may also get WIDER, plus the admission of new requests.  Queued by the
+// session between two graph batches, behind the prefill of the requests it admits; one workgroup.
+__global__ __launch_bounds__(256) void session_turn_k(const SessTurnArgs a) {
+  __shared__ SeqState s_st[VC_MAX_SEQS];
+  __shared__ int s_src[VC_MAX_SEQS], s_pos[VC_MAX_SEQS], s_live;
+  __shared__ int s_slot[VC_MAX_SEQS], s_Lx[VC_MAX_SEQS], s_cols[VC_MAX_SEQS];
+  const int tid = threadIdx.x;
+  constexpr int W = sizeof(SeqState) / 4;
+  if (tid == 0) *a.batch_id = a.batch;
+  if (!a.repack) return;
+  for (int i = tid; i < a.B_old * W; i += blockDim.x) reinterpret_cast<int*>(s_st)[i] = reinterpret_cast<const int*>(a.st)[i];
+  if (tid < a.B_old) s_pos[tid] = a.row_pos[tid];
+  if (tid < a.n_new) { s_slot[tid] = a.slot[tid]; s_Lx[tid] = a.Lx[tid]; s_cols[tid] = a.n_cols[tid]; }
+  __syncthreads();
+  if (tid == 0) {
+    int n = 0;
+    for (int r = 0; r < a.B_old; ++r)
+      if (!s_st[r].done) s_src[n++] = r;
+    s_live = n;
+    if (n + a.n_new > a.B_new) { atomicOr(a.err, 4); *a.row_base = 0; }     // (host logic error: the first-sample launch behind this stays inside the step's rows)
+  }
+  __syncthreads();
+  const int n_live = s_live;
+  if (n_live + a.n_new > a.B_new) return;
+  // states and row tables of the new layout: the live rows in order, then the admitted requests, then fillers
+  for (int r = tid; r < a.B_new; r += blockDim.x) {
+    if (r < n_live) { a.row_seq[r] = s_st[s_src[r]].slot; a.row_pos[r] = s_pos[s_src[r]]; }
+    else { a.row_seq[r] = 0; a.row_pos[r] = -1; }      // (an admitted row gets its tables from its first sample, advance_phase)
+    a.logit_row[r] = r;
+  }
+  for (int i = tid; i < a.B_new * W; i += blockDim.x) {
+    const int r = i / W, w = i - r * W;
+    int v;
+    if (r < n_live) v = reinterpret_cast<const int*>(s_st + s_src[r])[w];
+    else if (r < n_live + a.n_new) {                   // init_state of a TTS request (vc_engine.hip), slot = its K/V slot
+      const int j = r - n_live;
+      v = (w == (int)(offsetof(SeqState, Lx) / 4)) ? s_Lx[j] :
+          (w == (int)(offsetof(SeqState, y_len) / 4)) ? s_cols[j] :
+          (w == (int)(offsetof(SeqState, prev_token) / 4) || w == (int)(offsetof(SeqState, group) / 4)) ? -1 :
+          (w == (int)(offsetof(SeqState, n_spans) / 4) || w == (int)(offsetof(SeqState, kept) / 4)) ? 1 :
+          (w == (int)(offsetof(SeqState, cap_len) / 4)) ? s_Lx[j] * a.cap_mult :
+          (w == (int)(offsetof(SeqState, min_gen) / 4)) ? a.min_gen :
+          (w == (int)(offsetof(SeqState, term_token) / 4)) ? a.term_token :
+          (w == (int)(offsetof(SeqState, kill_token) / 4)) ? a.kill_token :
+          (w == (int)(offsetof(SeqState, slot) / 4)) ? s_slot[j] : 0;
+    } else {                                           // filler: a finished state that owns no sequence (repack_k)
+      v = (w == (int)(offsetof(SeqState, done) / 4)) ? 1 :
+          (w == (int)(offsetof(SeqState, slot) / 4) || w == (int)(offsetof(SeqState, group) / 4)) ? -1 : 0;
+    }
+    reinterpret_cast<int*>(a.st + r)[w] = v;
+  }
+  if (tid < a.n_new) {
+    const int slot = s_slot[tid];
+    a.adm_slot[tid] = slot;
+    a.seed_tab[slot] = a.seed[tid];
+    const int pe = a.prompt_err[slot];
+    a.prompt_err[slot] = 0;
+    __hip_atomic_store(a.retire_rec + slot * VC_SESS_REC + 4, pe, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  if (tid == 0) {
+    *a.row_base = n_live;
+    if (a.n_new > 0) atomicAdd(a.n_active, a.n_new);
+  }
+  // next input rows of the live sequences: source index >= destination and increasing (repack_k)
+  const int nq = a.d >> 2;
+  for (int r = 0; r < n_live; ++r) {
+    const int src = s_src[r];
+    if (src == r) continue;
+    const float4* sp = reinterpret_cast<const float4*>(a.dec_h + (long)src * a.d);
+    float4* dp = reinterpret_cast<float4*>(a.dec_h + (long)r * a.d);
+    float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
+    if (tid < nq) v0 = sp[tid];
+    if (tid + 256 < nq) v1 = sp[tid + 256];
+    if (tid < nq) dp[tid] = v0;
+    if (tid + 256 < nq) dp[tid + 256] = v1;
+    __syncthreads();
+  }
+}
+hipError_t vc_launch_session_turn(const SessTurnArgs& a, hipStream_t s) {
+  if (a.B_old < 0 || a.B_old > VC_MAX_SEQS || a.B_new < 1 || a.B_new > VC_MAX_SEQS || a.n_new < 0 || a.n_new > a.B_new || a.d > 2048)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_turn_k, dim3(1), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

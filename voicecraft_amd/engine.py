@@ -341,6 +341,39 @@ class VoiceCraftEngine:
             return outs, logits
         return outs
 
+    # ---- decode sessions: continuous batching (include/vc_engine.h vc_session_*)
+    def open_session(self, max_live: int | None = None, top_k: int = -100, top_p: float = 1.0, temperature: float = 1.0,
+                     stop_repetition: int = 3, silence_tokens: Iterable[int] = (1388, 1898, 131), **unsupported) -> "DecodeSession":
+        """A decode session over `max_live` K/V slots (default max_seqs): TTS requests with inference_tts semantics, one sample each,
+        submitted at any time, each joining the running batch between two graph batches and handed back as soon as it ends.
+        The sampling controls are the session's; the seed is per request (DecodeSession.submit).  Use it as a context manager.
+        Editing, best-of-N, a shared text prefix, logits_out and forced trajectories are not part of a session and are refused."""
+        if unsupported:
+            raise AssertionError(f"open_session: {sorted(unsupported)} not supported - a decode session takes plain TTS requests, one "
+                                 "sample each (no editing / mask_interval, no best-of-N batch_size, no _shared_text_prefix, no "
+                                 "_logit_steps, no _forced trajectories): use the blocking calls for those")
+        return DecodeSession(self, self.max_seqs if max_live is None else int(max_live),
+                             self._sample_cfg(top_k, top_p, temperature, stop_repetition, silence_tokens, 0))
+
+    @torch.no_grad()
+    def inference_tts_queue(self, xs, ys, max_live: int | None = None, seeds=None, **sampling):
+        """Any number of utterances through `max_live` slots of one decode session (default max_seqs): a freed slot is refilled with
+        the next utterance while the others go on decoding.  xs: list of int64 [Lx_i]; ys: list of int64 [T_i,K]; seeds: one per
+        utterance (default: drawn from torch's generator, as _sample_cfg does).  Returns the list of (res [1,K,T_i+Tg_i], gen) in
+        input order - the return type of inference_tts_multi.  self.last_session_stats holds the session's stats()."""
+        assert len(xs) == len(ys) and len(xs) >= 1, (len(xs), len(ys))
+        assert seeds is None or len(seeds) == len(xs), "one seed per utterance"
+        K = self.args.n_codebooks
+        with self.open_session(max_live, **sampling) as sess:
+            tickets = []
+            for i, (xv, yv) in enumerate(zip(xs, ys)):
+                xv = torch.as_tensor(xv, dtype=torch.int64).reshape(1, -1)
+                yv = torch.as_tensor(yv, dtype=torch.int64).reshape(1, -1, K)
+                tickets.append(sess.submit(xv, torch.tensor([xv.shape[1]]), yv, seed=None if seeds is None else seeds[i]))
+            done = {t: (res, gen) for t, res, gen in sess.drain()}
+            self.last_session_stats = sess.stats()
+        return [done[t] for t in tickets]
+
     # ---- the training objective, teacher-forced (SURVEY §8f-4)
     @torch.no_grad()
     def forward(self, batch, mask_intervals=None, mask_values=None, _per_row: bool = False, mask_sampler=None):
@@ -631,6 +664,153 @@ class VoiceCraftEngine:
         check(self.lib.vc_debug_read(self._h, name.encode(), C.c_void_p(out.data_ptr()), out.numel() * out.element_size()),
               self._h, "vc_debug_read")
         return out
+
+
+class SessionRequestError(EngineError):
+    """Requests of a decode session that finished without a result (DecodeSession.poll / drain): `failed` maps each ticket to the
+    exception its fetch raised - EngineError(VC_ECAP) for a request that ran out of max_positions before its terminator,
+    AssertionError for one whose x / y held an out-of-range token id.  Their slots are free again; the session goes on, and the
+    requests that finished well in the same turn are returned by the next poll() / drain()."""
+
+    def __init__(self, failed: dict):
+        self.failed = dict(failed)
+        super().__init__("decode session: " + "; ".join(f"ticket {t}: {e}" for t, e in sorted(self.failed.items())))
+
+
+class DecodeSession:
+    """An open decode session of a VoiceCraftEngine (VoiceCraftEngine.open_session).  submit() queues a request and returns its
+    ticket; poll() runs one turn of the decode loop and returns the requests that finished; drain() polls until the session is
+    idle.  While a session is open the engine's other decode calls and set_option raise (EngineError, VC_ESTATE)."""
+
+    STATS = ("admitted", "admitted_while_live", "turns", "widenings", "narrowings", "live_rows", "launched_rows", "admission_us")
+
+    def __init__(self, engine: VoiceCraftEngine, max_live: int, sc: SampleCfg):
+        self.engine, self.max_live = engine, int(max_live)
+        self._open = False
+        self._reqs: dict[int, tuple] = {}     # ticket -> (x, y, T, Lx): the device tensors stay alive until the ticket is fetched
+        self._ready: list = []                # (ticket, res, gen) fetched and not yet handed out
+        self.idle = True
+        # uploads and result arithmetic run on a stream of the session's own: a launch on the null stream would wait for the decode
+        # batches queued on the engine's stream (as in _tts_stream)
+        self._side = torch.cuda.Stream(device=engine.device)
+        check(engine.lib.vc_session_open(engine._h, self.max_live, C.byref(sc), engine._stream()), engine._h, "vc_session_open")
+        self._open = True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover
+            pass
+
+    def submit(self, x, x_lens, y, seed=None) -> int:
+        """x [1,Lx'], x_lens [1], y [1,T,K] as inference_tts takes them (same checks, same special_first handling)."""
+        assert self._open, "the session is closed"
+        eng = self.engine
+        Lx = int(x_lens[0])                      # (read on the host before anything is queued)
+        with torch.cuda.stream(self._side):
+            xd, Lx, yd, T = eng._prep(x, torch.tensor([Lx]), y)
+        self._side.synchronize()                 # the prompt is on the device before the prefill that reads it can be queued
+        sd = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+        ticket = C.c_int(0)
+        check(eng.lib.vc_session_submit(eng._h, C.c_void_p(xd.data_ptr()), Lx, C.c_void_p(yd.data_ptr()), T, sd, C.byref(ticket)),
+              eng._h, "vc_session_submit")
+        self._reqs[ticket.value] = (xd, yd, T, Lx)
+        self.idle = False
+        return ticket.value
+
+    def fetch(self, ticket: int):
+        """(res [1,K,T+Tg], gen [1,K,Tg]) of a finished request, the values inference_tts returns; frees its slot."""
+        assert self._open, "the session is closed"
+        eng = self.engine
+        K = eng.args.n_codebooks
+        req = self._reqs.get(int(ticket))
+        xd, yd, T, Lx = req if req is not None else (None, None, 0, 1)
+        cap = T + eng._gen_budget(Lx, T + 1, eng.args.encodec_sr // 5)
+        res = torch.empty((K, cap), dtype=torch.int64, device=eng.device)
+        gen_len, n_steps = C.c_int(0), C.c_int(0)
+        rc = eng.lib.vc_session_fetch(eng._h, int(ticket), C.c_void_p(res.data_ptr()), cap, C.byref(gen_len), C.byref(n_steps))
+        if rc != -2:                           # (an unfinished request keeps its ticket)
+            self._reqs.pop(int(ticket), None)
+        check(rc, eng._h, "vc_session_fetch")
+        eng.last_steps = n_steps.value
+        Tg = gen_len.value
+        out, gen = res[:, : T + Tg].unsqueeze(0), res[:, T: T + Tg].unsqueeze(0)
+        if eng.args.special_first:
+            with torch.cuda.stream(self._side):
+                out, gen = out - int(eng.args.n_special), gen - int(eng.args.n_special)
+            self._side.synchronize()             # final on the device: usable from any stream
+        return out, gen
+
+    @torch.no_grad()
+    def _turn(self) -> None:
+        """One turn of the decode loop.  EVERY request it reports finished is fetched: results go to self._ready; if some finished
+        without a result, SessionRequestError names them once all are fetched (nothing another request produced is lost)."""
+        assert self._open, "the session is closed"
+        eng = self.engine
+        cap = max(1, self.max_live)
+        tickets = (C.c_int * cap)()
+        n, idle = C.c_int(0), C.c_int(0)
+        check(eng.lib.vc_session_advance(eng._h, tickets, cap, C.byref(n), C.byref(idle)), eng._h, "vc_session_advance")
+        self.idle = bool(idle.value)
+        failed = {}
+        for i in range(n.value):
+            t = int(tickets[i])
+            try:
+                self._ready.append((t,) + self.fetch(t))
+            except (EngineError, AssertionError) as ex:
+                failed[t] = ex
+        if failed:
+            raise SessionRequestError(failed)
+
+    def _hand_out(self):
+        out, self._ready = self._ready, []
+        return out
+
+    def poll(self):
+        """One turn of the decode loop; the list of (ticket, res, gen) of the requests that finished since the last call.  Raises
+        SessionRequestError (tickets in `.failed`) when a request finished without a result; the others' results are kept and come
+        with the next call."""
+        self._turn()
+        return self._hand_out()
+
+    def drain(self):
+        """Polls until the session is idle; everything that finished on the way.  After a SessionRequestError call it again: nothing
+        is lost."""
+        self._turn()
+        while not self.idle:
+            self._turn()
+        return self._hand_out()
+
+    def stats(self, timing: bool = False) -> dict:
+        """The session's counters (include/vc_engine.h vc_session_stats): a function of the submission schedule alone, the same in
+        every run of it.  timing=True adds `admission_us`, the decode-stream time spent on admissions so far (HIP events)."""
+        assert self._open, "the session is closed"
+        v = (C.c_int64 * 8)()
+        check(self.engine.lib.vc_session_stats(self.engine._h, v), self.engine._h, "vc_session_stats")
+        return {k: int(v[i]) for i, k in enumerate(self.STATS) if timing or k != "admission_us"}
+
+    def close(self) -> None:
+        if not self._open:
+            return
+        self._open = False
+        try:
+            if self.engine._h:
+                check(self.engine.lib.vc_session_close(self.engine._h), self.engine._h, "vc_session_close")
+        finally:
+            self._reqs.clear()          # the prompts stay valid until the decode stream has been waited for
+            self._ready = []
+
+
+def inference_tts_queue(engine: VoiceCraftEngine, xs, ys, max_live: int | None = None, seeds=None, **sampling):
+    """VoiceCraftEngine.inference_tts_queue as a function: any number of utterances through `max_live` slots of one decode session."""
+    return engine.inference_tts_queue(xs, ys, max_live=max_live, seeds=seeds, **sampling)
 
 
 def debug_sample(logits: torch.Tensor, n_draws: int, top_k: int = -100, top_p: float = 1.0, temperature: float = 1.0,
