@@ -25,28 +25,32 @@ extern "C" {
 typedef struct vc_codec vc_codec;
 
 typedef struct vc_codec_cfg {
+  /* Accepted ranges (vc_codec_create refuses everything else with VC_EINVAL and a message naming the field); the value in
+   * front is the VoiceCraft codec's.  Tested range: DESIGN.md section 6. */
   int32_t sample_rate;          /* 16000 (informational)                               */
-  int32_t n_filters;            /* 64                                                  */
-  int32_t n_ratios;             /* 4                                                   */
-  int32_t ratios[VC_CODEC_MAX_RATIOS]; /* decoder (upsampling) order: 8,5,4,2           */
-  int32_t hidden;               /* 128: latent / codebook dimension                    */
-  int32_t n_q;                  /* 4 quantizers (K)                                    */
-  int32_t codebook_size;        /* 2048                                                */
-  int32_t lstm_layers;          /* 2                                                   */
-  int32_t kernel_size;          /* 7: first conv                                       */
-  int32_t last_kernel_size;     /* 7                                                   */
-  int32_t residual_kernel_size; /* 3                                                   */
-  int32_t compress;             /* 2: residual unit hidden = dim / compress            */
-  int32_t max_samples;          /* capacity: longest waveform (samples) per call       */
+  int32_t n_filters;            /* 64: any positive multiple of 32                     */
+  int32_t n_ratios;             /* 4: 1..VC_CODEC_MAX_RATIOS                            */
+  int32_t ratios[VC_CODEC_MAX_RATIOS]; /* decoder (upsampling) order: 8,5,4,2; each >= 2 (transposed kernel = 2 * ratio) */
+  int32_t hidden;               /* 128: latent / codebook dimension, any positive multiple of 16 (the MFMA search up to 256) */
+  int32_t n_q;                  /* 4 quantizers (K): 1..8                              */
+  int32_t codebook_size;        /* 2048: >= 1 (the MFMA search needs a multiple of 16, else the scalar search runs) */
+  int32_t lstm_layers;          /* 2: >= 1.  Batched calls need 2 layers at an LSTM width (n_filters * 2^n_ratios) that is a
+                                 *    multiple of 256 up to 1024; the decode stream carries at most 2 layers       */
+  int32_t kernel_size;          /* 7: first conv, >= 1 (even sizes pad one more on the left) */
+  int32_t last_kernel_size;     /* 7: >= 1                                             */
+  int32_t residual_kernel_size; /* 3: >= 1                                             */
+  int32_t compress;             /* 2: residual unit hidden = dim / compress (only 2)   */
+  int32_t max_samples;          /* capacity: longest waveform (samples) per encode call, >= 1; a decode call or a stream
+                                 *    window takes up to ceil(max_samples / hop) frames                             */
   /* Architecture switches of the SEANet stacks.  Which values the reference's checkpoint
    * (audiocraft encodec_4cb2048_giga.th, data/tokenizer.py:109-110) was trained with cannot be read from the
    * reference tree, so they are configuration, named as in transformers.EncodecConfig: */
   int32_t causal;               /* use_causal_conv: all padding on the left, transposed convs trimmed on the right */
   int32_t pad_reflect;          /* pad_mode: 1 = "reflect", 0 = "constant" (zeros)     */
   int32_t conv_shortcut;        /* use_conv_shortcut: 1x1 conv on the residual path (else identity) */
-  int32_t num_residual_layers;  /* residual units per stage (1)                        */
-  int32_t dilation_growth_rate; /* unit j dilates its first conv by rate**j (2)        */
-  int32_t max_batch;            /* capacity: clips per vc_codec_encode_batch / decode_batch call */
+  int32_t num_residual_layers;  /* residual units per stage (1): 1..4                  */
+  int32_t dilation_growth_rate; /* unit j dilates its first conv by rate**j (2): 1..4  */
+  int32_t max_batch;            /* capacity: clips per vc_codec_encode_batch / decode_batch call: 1..64 */
 } vc_codec_cfg;
 
 int vc_codec_create(const vc_codec_cfg* cfg, int hip_device, vc_codec** out);
@@ -104,6 +108,7 @@ int vc_codec_decode_batch(vc_codec* c, const int64_t* codes_dev, int B, int T, f
  *   emitted; the call with last = 1 emits the rest (hop * F in all) and closes the stream.
  *
  *   vc_codec_decode_stream_begin  opens the handle's decode stream (zero LSTM state); a second begin restarts it.
+ *                                 A codec with more than 2 LSTM layers has no stream: VC_EINVAL with a message.
  *   vc_codec_decode_stream        codes_dev int64 [K][n] with row stride `stride` (>= n): the next n frames (n = 0 is
  *                                 legal, e.g. a final call that only flushes); wav_dev receives *n_samples_out samples
  *                                 (wav_cap too small: VC_ECAP, nothing consumed).  The call returns with the samples
@@ -126,6 +131,10 @@ int vc_codec_debug_latent(vc_codec* c, float* host_dst, int64_t n_floats);
 int vc_codec_last_ms(const vc_codec* c, float* ms);
 /* Duration of the LSTM recurrence (T+1 wavefront launches) of the last call and the weight bytes one launch reads. */
 int vc_codec_last_lstm_ms(vc_codec* c, float* ms, double* bytes_per_step);
+/* Which kernel forms the last calls took (-1: none yet).  lstm_form: 0 = lstm_step_k layer by layer, 1 = the two-layer
+ * wavefront lstm_wave_k, 2 = the persistent lstm_persist_k (of the last encode, decode or stream chunk);
+ * rvq_form: 0 = rvq_encode_k (scalar), 1 = rvq_encode_mfma_k (of the last encode). */
+int vc_codec_last_forms(const vc_codec* c, int* lstm_form, int* rvq_form);
 
 #ifdef __cplusplus
 }

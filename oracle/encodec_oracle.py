@@ -34,16 +34,52 @@ def build(state_dict: dict[str, torch.Tensor] | None = None, **overrides):
     return m
 
 
+def overrides_from_cfg(cfg: dict | None = None) -> dict:
+    """The dict `voicecraft_amd.codec.AudioTokenizer` takes (names of `codec.DEFAULT_CFG`; missing keys = the VoiceCraft
+    codec shape) as EncodecConfig overrides for `build`.  transformers derives the number of quantizers from
+    target_bandwidths[-1], the frame rate and log2(codebook_size): n_q = int(1000 * bw // (frame_rate * bits)) with
+    frame_rate = ceil(sampling_rate / hop), so bw = n_q * frame_rate * bits / 1000 (+ half a quantizer of margin against
+    rounding) yields n_q.  EncodecModel refuses codebook sizes that are no power of two."""
+    import math
+    from voicecraft_amd.codec import DEFAULT_CFG
+    cf = dict(DEFAULT_CFG, **(cfg or {}))
+    size = int(cf["codebook_size"])
+    bits = int(math.log2(size))
+    assert 2 ** bits == size and bits >= 1, f"EncodecModel needs a power-of-two codebook_size >= 2, not {size}"
+    assert int(cf["compress"]) == 2, cf["compress"]
+    hop = math.prod(int(r) for r in cf["ratios"])
+    frame_rate = math.ceil(int(cf["sample_rate"]) / hop)
+    bw = (int(cf["n_q"]) + 0.5) * frame_rate * bits / 1000.0
+    return dict(target_bandwidths=[bw], sampling_rate=int(cf["sample_rate"]), hidden_size=int(cf["hidden"]),
+                num_filters=int(cf["n_filters"]), upsampling_ratios=[int(r) for r in cf["ratios"]],
+                kernel_size=int(cf["kernel_size"]), last_kernel_size=int(cf["last_kernel_size"]),
+                residual_kernel_size=int(cf["residual_kernel_size"]), num_lstm_layers=int(cf["lstm_layers"]),
+                codebook_size=size, codebook_dim=int(cf["hidden"]), compress=2,
+                num_residual_layers=int(cf["num_residual_layers"]), dilation_growth_rate=int(cf["dilation_growth_rate"]),
+                use_causal_conv=bool(cf["use_causal_conv"]), pad_mode=cf["pad_mode"],
+                use_conv_shortcut=bool(cf["use_conv_shortcut"]))
+
+
+def build_cfg(state_dict: dict[str, torch.Tensor] | None, cfg: dict | None = None):
+    """`build` at the shape of a tokenizer `cfg` dict; checks that the bandwidth gave the wanted number of quantizers."""
+    from voicecraft_amd.codec import DEFAULT_CFG
+    m = build(state_dict, **overrides_from_cfg(cfg))
+    n_q = int(dict(DEFAULT_CFG, **(cfg or {}))["n_q"])
+    assert len(m.quantizer.layers) == n_q and m.quantizer.get_num_quantizers_for_bandwidth(None) == n_q, \
+        (len(m.quantizer.layers), n_q)
+    return m
+
+
 @torch.no_grad()
 def encode(m, wav: torch.Tensor):
-    """wav [1,1,N] -> (codes int64 [K,T], latent fp32 [T,128])"""
-    z = m.encoder(wav)                                   # [1,128,T]
+    """wav [1,1,N] -> (codes int64 [K,T], latent [T,hidden]), T = ceil(N / hop)"""
+    z = m.encoder(wav)                                   # [1,hidden,T]
     codes = m.quantizer.encode(z, None)                  # [K,1,T]
     return codes[:, 0], z[0].transpose(0, 1).contiguous()
 
 
 @torch.no_grad()
 def decode(m, codes: torch.Tensor):
-    """codes int64 [K,T] -> wav fp32 [320*T]"""
-    q = m.quantizer.decode(codes.unsqueeze(1))           # [1,128,T]
+    """codes int64 [K,T] -> wav [hop*T]"""
+    q = m.quantizer.decode(codes.unsqueeze(1))           # [1,hidden,T]
     return m.decoder(q)[0, 0]

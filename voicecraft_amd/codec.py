@@ -46,6 +46,7 @@ PROTOTYPES = {
     "vc_codec_debug_latent": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "vc_codec_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "vc_codec_last_lstm_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
+    "vc_codec_last_forms": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vc_codec_stream_geometry": (C.c_int, [C.POINTER(CodecCfg), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vc_codec_decode_stream_begin": (C.c_int, [C.c_void_p]),
     "vc_codec_decode_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -271,7 +272,7 @@ class AudioTokenizer:
         self.hop = 1
         for r in cf["ratios"]:
             self.hop *= r
-        self.max_samples = int(max_seconds * self.sample_rate)
+        self.max_samples = int(round(max_seconds * self.sample_rate))   # (2.01 s at 16 kHz is 32160 samples, not the 32159 a truncated product gives)
         c = make_cfg(cf, self.max_samples, self.max_batch)
         self._h = C.c_void_p()
         self._check(self.lib.vc_codec_create(C.byref(c), index, C.byref(self._h)), "vc_codec_create", None)
@@ -348,7 +349,9 @@ class AudioTokenizer:
         """Opens the chunked decode: `.feed(codes [1,K,n], last=False) -> wav [1,1,m]`, `.lookahead_frames`."""
         return CodecDecodeStream(self)
 
-    def last_latent(self, T: int, hidden: int = 128) -> torch.Tensor:
+    def last_latent(self, T: int, hidden: int | None = None) -> torch.Tensor:
+        """The latent in front of the quantizer of the last encode, [T, hidden] (first clip of a batch)."""
+        hidden = int(self.cfg["hidden"]) if hidden is None else hidden
         out = torch.empty((T, hidden), dtype=torch.float32)
         self._check(self.lib.vc_codec_debug_latent(self._h, C.c_void_p(out.data_ptr()), out.numel()), "vc_codec_debug_latent")
         return out
@@ -357,6 +360,13 @@ class AudioTokenizer:
         ms, by = C.c_float(0), C.c_double(0)
         self.lib.vc_codec_last_lstm_ms(self._h, C.byref(ms), C.byref(by))
         return ms.value, by.value
+
+    def last_forms(self) -> tuple[int, int]:
+        """(lstm_form, rvq_form) of the last calls (vc_codec_last_forms): LSTM 0 = step kernel per layer, 1 = two-layer
+        wavefront, 2 = persistent launch; RVQ search 0 = scalar, 1 = MFMA; -1 = not run yet."""
+        a, b = C.c_int(-1), C.c_int(-1)
+        self._check(self.lib.vc_codec_last_forms(self._h, C.byref(a), C.byref(b)), "vc_codec_last_forms")
+        return a.value, b.value
 
     def last_ms(self) -> float:
         ms = C.c_float(0)

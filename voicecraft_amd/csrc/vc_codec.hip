@@ -59,7 +59,9 @@ __global__ __launch_bounds__(256) void conv_gemm_k(const ConvArgs a) {
   const int KT = a.Kw * ktpk;
   const float4* wp0 = a.Wp + (long)phase * a.w_phase_stride + ((long)cot0 * KT) * 64 + lane;
   const float4* wp1 = wp0 + (long)KT * 64;
-  const bool two = (cot0 + 1) * 16 < a.Co;               // Co may be a single 16-tile multiple of 32? (always 32-multiples here)
+  // Co is any multiple of 16: an odd tile count (16-channel residual units at n_filters 32, 48 at 96, a latent of 48) leaves the last
+  // pair's second tile empty - it multiplies zeros and the epilogue skips it (co >= Co)
+  const bool two = (cot0 + 1) * 16 < a.Co;
   f32x4 acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -215,12 +217,35 @@ __global__ void conv_last_k(const float* __restrict__ x, const float* __restrict
   out[t] = acc;
 }
 
+// ---- The arithmetic every form of the recurrence shares (lstm_step_k, lstm_wave_k, lstm_persist_k).  Which multiply the compiler
+// fuses into which add under -ffp-contract=fast is its own choice per kernel and per instantiation (lstm_wave_k<1> fused the
+// y product of one gate's pair where lstm_step_k fused the x product: 7e-6 on a waveform), so the forms can be bit-identical
+// only if the rounding is spelled out: contraction is off in here and the one fused multiply-add per pair is written down.
+__device__ __forceinline__ float lstm_dot4(const float4 w, const float4 v) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(w.x, v.x, w.y * v.y) + __builtin_fmaf(w.z, v.z, w.w * v.w);
+}
+// gate pre-activations g4 (the wave sums) + gi (input projection / bias) -> new cell state and hidden value
+__device__ __forceinline__ void lstm_cell(const float g4[4], const float4 gi, const float c_prev, float& c, float& h) {
+#pragma clang fp contract(off)
+  const float ig = 1.f / (1.f + expf(-(g4[0] + gi.x)));
+  const float fg = 1.f / (1.f + expf(-(g4[1] + gi.y)));
+  const float gg = tanhf(g4[2] + gi.z);
+  const float og = 1.f / (1.f + expf(-(g4[3] + gi.w)));
+  c = __builtin_fmaf(fg, c_prev, ig * gg);
+  h = og * tanhf(c);
+}
+
 // ---- LSTM recurrence, one launch per time step (nn.LSTM gate order i,f,g,o; rows re-ordered so the
-// four gates of hidden unit u are rows 4u..4u+3).  gates = G[t] (input projection + both biases,
-// computed for all t by one implicit GEMM) + W_hh h_{t-1}.
+// four gates of hidden unit u are rows 4u..4u+3).  Layer 0: gates = G[t] (input projection + both biases,
+// computed for all t by one implicit GEMM) + W_hh h_{t-1}.  Upper layers fold their input projection into the step,
+// gates = (W_hh h_{t-1} + W_ih x_t) + b, every sum in lstm_wave_k's order: at a width both forms take, codes and waveform
+// of the two are bit-identical (tested), as they are between lstm_wave_k and lstm_persist_k.
 struct LstmArgs {
   const float* Whh;      // [4H][H], rows permuted (unit-major)
-  const float* G;        // [T][4H] permuted the same way
+  const float* G;        // layer 0: row t of [T][4H], permuted the same way; upper layers: [4H] b_ih + b_hh
+  const float* Wih;      // upper layers: [4H][H], unit-major rows (layer 0: NULL)
+  const float* x_in;     // upper layers: [H], the lower layer's h_t
   const float* h_prev;   // [H]
   float* c;              // [H] in/out
   float* h_out;          // [H]: row t of the layer's output sequence
@@ -232,9 +257,11 @@ struct LstmArgs {
 __global__ __launch_bounds__(256) void lstm_step_k(const LstmArgs a) {
   // one wave per hidden unit: its four gate rows (4 x H floats, contiguous after the permutation) are
   // streamed with 16-byte loads, h_{t-1} comes from LDS, each dot product ends in a DPP wave sum.
-  extern __shared__ float s_h[];                         // h_{t-1}
+  extern __shared__ float s_h[];                         // h_{t-1}, behind it (upper layers) the lower layer's h_t
   const int H = a.H;
   for (int i = threadIdx.x; i < H; i += blockDim.x) s_h[i] = a.h_prev[i];
+  if (a.Wih)
+    for (int i = threadIdx.x; i < H; i += blockDim.x) s_h[H + i] = a.x_in[i];
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int u = blockIdx.x * 4 + wave;                   // hidden unit
@@ -248,19 +275,30 @@ __global__ __launch_bounds__(256) void lstm_step_k(const LstmArgs a) {
 #pragma unroll
     for (int gate = 0; gate < 4; ++gate) {
       const float4 ww = w[(long)gate * nq + i];
-      g4[gate] += (ww.x * hh.x + ww.y * hh.y) + (ww.z * hh.z + ww.w * hh.w);
+      g4[gate] += lstm_dot4(ww, hh);
     }
+  }
+  if (a.Wih) {
+    const float4* wi = reinterpret_cast<const float4*>(a.Wih + (long)(4 * u) * H);
+    const float4* xv = hv + nq;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int i = lane; i < nq; i += 64) {
+      const float4 xx = xv[i];
+#pragma unroll
+      for (int gate = 0; gate < 4; ++gate) {
+        const float4 ww = wi[(long)gate * nq + i];
+        acc[gate] += lstm_dot4(ww, xx);
+      }
+    }
+#pragma unroll
+    for (int gate = 0; gate < 4; ++gate) g4[gate] += acc[gate];
   }
 #pragma unroll
   for (int gate = 0; gate < 4; ++gate) g4[gate] = wave_sum(g4[gate]);
   if (lane != 0) return;
   const float4 gi = *reinterpret_cast<const float4*>(a.G + 4 * u);
-  const float ig = 1.f / (1.f + expf(-(g4[0] + gi.x)));
-  const float fg = 1.f / (1.f + expf(-(g4[1] + gi.y)));
-  const float gg = tanhf(g4[2] + gi.z);
-  const float og = 1.f / (1.f + expf(-(g4[3] + gi.w)));
-  const float c = fg * a.c[u] + ig * gg;
-  const float h = og * tanhf(c);
+  float c, h;
+  lstm_cell(g4, gi, a.c[u], c, h);
   a.c[u] = c;
   a.h_out[u] = h;
   if (a.skip) {
@@ -337,7 +375,7 @@ __global__ __launch_bounds__(256) void lstm_wave_k(const LstmWaveArgs a) {
     for (int g = 0; g < 4; ++g) {
 #pragma unroll
       for (int j = 0; j < NQ; ++j)
-        g4[g] += (w[g][j].x * hv[j].x + w[g][j].y * hv[j].y) + (w[g][j].z * hv[j].z + w[g][j].w * hv[j].w);
+        g4[g] += lstm_dot4(w[g][j], hv[j]);
     }
     if (n == 1) {
 #pragma unroll
@@ -345,19 +383,15 @@ __global__ __launch_bounds__(256) void lstm_wave_k(const LstmWaveArgs a) {
         float acc = 0.f;
 #pragma unroll
         for (int j = 0; j < NQ; ++j)
-          acc += (wi[g][j].x * xv[j].x + wi[g][j].y * xv[j].y) + (wi[g][j].z * xv[j].z + wi[g][j].w * xv[j].w);
+          acc += lstm_dot4(wi[g][j], xv[j]);
         g4[g] += acc;
       }
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) g4[g] = wave_sum(g4[g]);
     if (lane == 0) {
-      const float ig = 1.f / (1.f + expf(-(g4[0] + gi.x)));
-      const float fg = 1.f / (1.f + expf(-(g4[1] + gi.y)));
-      const float gg = tanhf(g4[2] + gi.z);
-      const float og = 1.f / (1.f + expf(-(g4[3] + gi.w)));
-      const float c = fg * c_prev + ig * gg;
-      const float h = og * tanhf(c);
+      float c, h;
+      lstm_cell(g4, gi, c_prev, c, h);
       a.c[n][(long)b * H + u] = c;
       a.hs[n][b * TH + (long)t * H + u] = h;
       if (n == 1 && a.skip) {
@@ -514,7 +548,7 @@ __global__ __launch_bounds__(512) void lstm_persist_k(const LstmPersistArgs a) {
         for (int g = 0; g < 4; ++g) {
 #pragma unroll
           for (int j = 0; j < NQ; ++j)
-            g4[g] += (w[g][j].x * hv[j].x + w[g][j].y * hv[j].y) + (w[g][j].z * hv[j].z + w[g][j].w * hv[j].w);
+            g4[g] += lstm_dot4(w[g][j], hv[j]);
         }
         if (n == 1) {
 #pragma unroll
@@ -522,19 +556,15 @@ __global__ __launch_bounds__(512) void lstm_persist_k(const LstmPersistArgs a) {
             float acc = 0.f;
 #pragma unroll
             for (int j = 0; j < NQ; ++j)
-              acc += (wi[g][j].x * xv[j].x + wi[g][j].y * xv[j].y) + (wi[g][j].z * xv[j].z + wi[g][j].w * xv[j].w);
+              acc += lstm_dot4(wi[g][j], xv[j]);
             g4[g] += acc;
           }
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) g4[g] = wave_sum(g4[g]);
         if (lane == 0) {
-          const float ig = 1.f / (1.f + expf(-(g4[0] + gi.x)));
-          const float fg = 1.f / (1.f + expf(-(g4[1] + gi.y)));
-          const float gg = tanhf(g4[2] + gi.z);
-          const float og = 1.f / (1.f + expf(-(g4[3] + gi.w)));
-          const float c = fg * c_prev + ig * gg;
-          const float h = og * tanhf(c);
+          float c, h;
+          lstm_cell(g4, gi, c_prev, c, h);
           a.c[n][(long)b * H + u] = c;
           __hip_atomic_store(a.hg[n] + b * TH + (long)t * H + u, ((unsigned long long)a.epoch << 32) | (unsigned long long)__float_as_uint(h),
                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -592,11 +622,13 @@ __global__ __launch_bounds__(256) void rvq_encode_k(const float* __restrict__ z,
     __syncthreads();
   }
 }
-// The same search on the fp32 MFMA: a workgroup owns 16 frames, stage q is the [2048 codes] x [16 frames] product
+// The same search on the fp32 MFMA (hidden a multiple of 16 up to 256, codebook_size a multiple of 16; anything else takes
+// rvq_encode_k): a workgroup owns 16 frames, stage q is the [C codes] x [16 frames] product
 // E_q R^T (A = codebook rows straight from HBM/L2 - a row IS an A fragment -, B = the residual rows from LDS, loaded
 // once per stage), every wave takes every 4th 16-code tile, a lane keeps the best (distance, index) of the 4 codes x
 // 1 frame it sees per tile, and the 16 candidates per frame (4 lane groups x 4 waves) are settled through LDS with
-// the lowest index winning ties (torch.max returns the first maximum).  dist is evaluated exactly as the reference
+// the lowest index winning ties (torch.max returns the first maximum; a wave without a tile - fewer than four tiles in the
+// codebook - hands in -INFINITY / 0x7fffffff, which never wins).  dist is evaluated exactly as the reference
 // writes it, -((|r|^2 - 2 r.e) + |e|^2).  One block per frame with scalar dot products took 1.5 ms of a 16 s encode.
 __global__ __launch_bounds__(256) void rvq_encode_mfma_k(const float* __restrict__ z, const float* __restrict__ E,
                                                          const float* __restrict__ e2, int64_t* __restrict__ codes,
@@ -610,7 +642,7 @@ __global__ __launch_bounds__(256) void rvq_encode_mfma_k(const float* __restrict
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m = lane & 15, kg = lane >> 4;
   const int f0 = blockIdx.x * 16;
-  const int nks = D >> 4;                                  // 16-dim k-steps (<= 16)
+  const int nks = D >> 4;                                  // 16-dim k-steps: 1..16 (D = 16..256, the launcher's condition)
   for (int i = tid; i < 16 * (D >> 2); i += 256) {         // residual := latent rows (frames past the end: zeros)
     const int fr = i / (D >> 2), c4 = i - fr * (D >> 2);
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -786,6 +818,8 @@ struct vc_codec {
   int persist_carry_ok = -1;             // the same for the carried-state form (lstm_persist_k<NQ, true>)
   bool persist_used = false;             // a persistent launch is in flight / unchecked (check_lstm_flag)
   int last_lstm_persist = 0;             // 1: the last LSTM ran as the persistent launch, 0: launch per step
+  int last_lstm_form = -1;               // vc_codec_last_forms: 0 lstm_step_k per layer, 1 lstm_wave_k, 2 lstm_persist_k
+  int last_rvq_form = -1;                // vc_codec_last_forms: 0 rvq_encode_k, 1 rvq_encode_mfma_k
   int* err_flag = nullptr;
   int* h_flag = nullptr;
   int T_max = 0;
@@ -1075,10 +1109,12 @@ int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, 
         CCHK(c, hipEventRecord(c->ev_l[1], s));
         c->persist_used = true;
         c->last_lstm_persist = 1;
+        c->last_lstm_form = 2;
         return VC_OK;
       }
     }
     c->last_lstm_persist = 0;
+    c->last_lstm_form = 1;
     if (!cy) CCHK(c, hipMemsetAsync(c->cstate, 0, (size_t)2 * B * H * 4, s));
     LstmWaveArgs a;
     memset(&a, 0, sizeof a);
@@ -1101,23 +1137,29 @@ int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, 
     return VC_OK;
   }
   if (B != 1) return cfail(c, VC_EINVAL, "batched LSTM needs the two-layer wavefront (2 layers, hidden a multiple of 256 <= 1024)");
+  c->last_lstm_persist = 0;
+  c->last_lstm_form = 0;
   for (int n = 0; n < L.layers; ++n) {
-    int rc = run_conv1x1(c, L.Wih[n], in, T, c->G, s, 1);                        // G = in W_ih^T + b_ih + b_hh
-    if (rc) return rc;
+    if (n == 0) {
+      int rc = run_conv1x1(c, L.Wih[0], in, T, c->G, s, 1);                      // G = x W_ih^T + b_ih + b_hh
+      if (rc) return rc;
+    }
     if (!cy) CCHK(c, hipMemsetAsync(c->cstate, 0, (size_t)H * 4, s));
     float* hs = seq[n & 1];
     const bool last = (n == L.layers - 1);
     for (int t = 0; t < T; ++t) {
       LstmArgs a;
       memset(&a, 0, sizeof a);
-      a.Whh = L.Whh[n]; a.G = c->G + (size_t)t * 4 * H; a.h_prev = t ? hs + (size_t)(t - 1) * H : cy ? cy->h_in[n] : c->hzero;
+      a.Whh = L.Whh[n]; a.G = n ? L.bP[n] : c->G + (size_t)t * 4 * H;
+      if (n) { a.Wih = L.WihP[n]; a.x_in = in + (size_t)t * H; }                   // upper layers project their input in the step
+      a.h_prev = t ? hs + (size_t)(t - 1) * H : cy ? cy->h_in[n] : c->hzero;
       a.c = cy ? cy->c[n] : c->cstate; a.h_out = hs + (size_t)t * H; a.H = H;
       if (last) {
         a.skip = x + (size_t)t * H;
         a.out_raw = out_raw ? out_raw + (size_t)t * H : nullptr;
         a.out_elu = out_elu ? out_elu + (size_t)t * H : nullptr;
       }
-      hipLaunchKernelGGL(lstm_step_k, dim3((H + 3) / 4), dim3(256), (size_t)H * 4, s, a);
+      hipLaunchKernelGGL(lstm_step_k, dim3((H + 3) / 4), dim3(256), (size_t)2 * H * 4, s, a);
     }
     CCHK(c, hipGetLastError());
     if (cy) CCHK(c, hipMemcpyAsync(cy->h_out[n], hs + (size_t)(T - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, s));
@@ -1202,7 +1244,15 @@ extern "C" int vc_codec_create(const vc_codec_cfg* cfg, int hip_device, vc_codec
   if (!cfg || !out) return cfail(nullptr, VC_EINVAL, "null argument");
   *out = nullptr;
   if (cfg->n_ratios < 1 || cfg->n_ratios > VC_CODEC_MAX_RATIOS) return cfail(nullptr, VC_EINVAL, "n_ratios out of range");
-  if (cfg->n_filters % 32 || cfg->hidden % 16) return cfail(nullptr, VC_EINVAL, "n_filters must be a multiple of 32, hidden of 16");
+  if (cfg->n_filters < 32 || cfg->n_filters % 32) return cfail(nullptr, VC_EINVAL, "n_filters must be a positive multiple of 32 (got %d)", cfg->n_filters);
+  if (cfg->hidden < 16 || cfg->hidden % 16) return cfail(nullptr, VC_EINVAL, "hidden must be a positive multiple of 16 (got %d)", cfg->hidden);
+  for (int i = 0; i < cfg->n_ratios; ++i)   // a ratio of 1 doubles the channels without halving the length: no arena is sized for that
+    if (cfg->ratios[i] < 2) return cfail(nullptr, VC_EINVAL, "ratios[%d] must be at least 2 (got %d)", i, cfg->ratios[i]);
+  if (cfg->lstm_layers < 1) return cfail(nullptr, VC_EINVAL, "lstm_layers must be at least 1 (got %d)", cfg->lstm_layers);
+  if (cfg->codebook_size < 1) return cfail(nullptr, VC_EINVAL, "codebook_size must be at least 1 (got %d)", cfg->codebook_size);
+  if (cfg->kernel_size < 1) return cfail(nullptr, VC_EINVAL, "kernel_size must be at least 1 (got %d)", cfg->kernel_size);
+  if (cfg->residual_kernel_size < 1) return cfail(nullptr, VC_EINVAL, "residual_kernel_size must be at least 1 (got %d)", cfg->residual_kernel_size);
+  if (cfg->last_kernel_size < 1) return cfail(nullptr, VC_EINVAL, "last_kernel_size must be at least 1 (got %d)", cfg->last_kernel_size);
   if (cfg->compress != 2) return cfail(nullptr, VC_EINVAL, "compress must be 2");
   if (cfg->n_q < 1 || cfg->n_q > VC_MAX_CODEBOOKS) return cfail(nullptr, VC_EINVAL, "n_q out of range");
   if (cfg->max_samples < 1) return cfail(nullptr, VC_EINVAL, "max_samples must be positive");
@@ -1326,7 +1376,11 @@ extern "C" int vc_codec_finalize(vc_codec* c) {
   const size_t NB = (size_t)g.max_batch;
   c->B_max = g.max_batch;
   c->T_max = (int)((N + c->hop - 1) / c->hop) + 1;
-  const size_t big = NB * std::max(N * F, (size_t)c->T_max * top) + 1024;
+  // A call carries up to T_max - 1 = ceil(max_samples / hop) frames, and a decode (or a stream window) of that many frames writes
+  // (T_max - 1) * hop positions of F channels in its last stage - more than max_samples when max_samples is no multiple of the hop.
+  // Every other stage holds ceil(n / p) positions of F * 2^i channels with p >= 2^i (every ratio >= 2), which is no more.
+  const size_t N_cap = (size_t)(c->T_max - 1) * c->hop;
+  const size_t big = NB * std::max(N_cap * F, (size_t)c->T_max * top) + 1024;
   if ((rc = calloc_dev(c, &c->A_raw, big))) return rc;
   if ((rc = calloc_dev(c, &c->A_elu, big))) return rc;
   if ((rc = calloc_dev(c, &c->B_elu, big))) return rc;
@@ -1404,9 +1458,11 @@ extern "C" int vc_codec_encode_batch(vc_codec* c, const float* wav_dev, int B, i
   if ((rc = run_conv(c, c->enc_last, c->B_elu, T, nullptr, c->latent, nullptr, &Lo, s, B))) return rc;
   if (g.hidden % 16 == 0 && g.hidden <= 256 && g.codebook_size % 16 == 0 && !getenv("VC_RVQ_SCALAR")) {
     const size_t lds = (size_t)16 * (g.hidden * 4 + 16) + (16 + 256 + 256 + 16) * 4;
+    c->last_rvq_form = 1;
     hipLaunchKernelGGL(rvq_encode_mfma_k, dim3((B * T + 15) / 16), dim3(256), lds, s, c->latent, c->E, c->e2, codes_dev, B * T, T,
                        g.hidden, g.codebook_size, g.n_q);
   } else {
+    c->last_rvq_form = 0;
     hipLaunchKernelGGL(rvq_encode_k, dim3(B * T), dim3(256), (size_t)g.hidden * 4, s, c->latent, c->Et, c->E, c->e2, codes_dev, T,
                        g.hidden, g.codebook_size, g.n_q);
   }
@@ -1473,6 +1529,8 @@ extern "C" int vc_codec_decode_stream_begin(vc_codec* c) {
   if (!c) return VC_EINVAL;
   if (!c->finalized) return cfail(c, VC_ESTATE, "codec not finalized");
   CCHK(c, hipSetDevice(c->device));
+  if (c->dec_lstm.layers > 2)
+    return cfail(c, VC_EINVAL, "the decode stream carries the state of at most 2 LSTM layers (lstm_layers = %d): use vc_codec_decode", c->dec_lstm.layers);
   vc_codec::DecStream& d = c->ds;
   const int top = c->dec_lstm.H;
   // (the null stream: ordered against whatever stream the chunks will run on)
@@ -1588,6 +1646,12 @@ extern "C" int vc_codec_debug_latent(vc_codec* c, float* host_dst, int64_t n_flo
   return VC_OK;
 }
 
+extern "C" int vc_codec_last_forms(const vc_codec* c, int* lstm_form, int* rvq_form) {
+  if (!c || !lstm_form || !rvq_form) return VC_EINVAL;
+  *lstm_form = c->last_lstm_form;
+  *rvq_form = c->last_rvq_form;
+  return VC_OK;
+}
 extern "C" int vc_codec_last_ms(const vc_codec* c, float* ms) {
   if (!c || !ms) return VC_EINVAL;
   *ms = c->last_ms;

@@ -132,9 +132,25 @@ def random_prompt(args: Namespace, Lx: int, T: int, seed: int = 1):
     return x, torch.tensor([Lx], dtype=torch.int64), y
 
 
-def make_codec_state_dict(seed: int = 0, use_conv_shortcut: bool = False, num_residual_layers: int = 1) -> dict[str, torch.Tensor]:
+def make_codec_state_dict(seed: int = 0, use_conv_shortcut: bool | None = None, num_residual_layers: int | None = None,
+                          cfg: dict | None = None) -> dict[str, torch.Tensor]:
     """Synthetic EnCodec weights in transformers.EncodecModel naming (weight-norm g/v pairs, LSTM,
-    codebooks) at the VoiceCraft codec shape.  Magnitudes keep activations O(1) through 16 layers."""
+    codebooks).  Magnitudes keep activations O(1) through the stacks.
+
+    `cfg` is the dict `AudioTokenizer` takes (names of `codec.DEFAULT_CFG`; missing keys = the VoiceCraft codec shape):
+    n_filters, ratios, hidden, n_q, codebook_size, lstm_layers, kernel_size, residual_kernel_size, last_kernel_size,
+    use_conv_shortcut, num_residual_layers.  The two keyword switches override it (the older spelling).  One generator,
+    one draw order: at the default shape the tensors are the ones this function has always made."""
+    from .codec import DEFAULT_CFG
+    cf = dict(DEFAULT_CFG, **(cfg or {}))
+    if use_conv_shortcut is not None:
+        cf["use_conv_shortcut"] = use_conv_shortcut
+    if num_residual_layers is not None:
+        cf["num_residual_layers"] = num_residual_layers
+    use_conv_shortcut, num_residual_layers = bool(cf["use_conv_shortcut"]), int(cf["num_residual_layers"])
+    F, ratios, hidden = int(cf["n_filters"]), [int(r) for r in cf["ratios"]], int(cf["hidden"])
+    k_first, k_res, k_last = int(cf["kernel_size"]), int(cf["residual_kernel_size"]), int(cf["last_kernel_size"])
+    layers, n_q, n_codes = int(cf["lstm_layers"]), int(cf["n_q"]), int(cf["codebook_size"])
     rs = np.random.RandomState(seed)
     sd: dict[str, torch.Tensor] = {}
 
@@ -150,7 +166,7 @@ def make_codec_state_dict(seed: int = 0, use_conv_shortcut: bool = False, num_re
         sd[prefix + ".conv.parametrizations.weight.original1"] = t(v)
         sd[prefix + ".conv.bias"] = t(0.05 * rs.standard_normal(size=(co,)))
 
-    def lstm(prefix, h, layers=2):
+    def lstm(prefix, h):
         for n in range(layers):
             b = h ** -0.5
             sd[f"{prefix}.lstm.weight_ih_l{n}"] = t(rs.uniform(-b, b, size=(4 * h, h)))
@@ -158,11 +174,10 @@ def make_codec_state_dict(seed: int = 0, use_conv_shortcut: bool = False, num_re
             sd[f"{prefix}.lstm.bias_ih_l{n}"] = t(rs.uniform(-b, b, size=(4 * h,)))
             sd[f"{prefix}.lstm.bias_hh_l{n}"] = t(rs.uniform(-b, b, size=(4 * h,)))
 
-    F, ratios, hidden = 64, [8, 5, 4, 2], 128
-    conv("encoder.layers.0", F, 1, 7)
+    conv("encoder.layers.0", F, 1, k_first)
     idx, ch = 1, F
     def res_unit(prefix, dim):
-        conv(prefix + ".block.1", dim // 2, dim, 3)
+        conv(prefix + ".block.1", dim // 2, dim, k_res)
         conv(prefix + ".block.3", dim, dim // 2, 1)
         if use_conv_shortcut:
             conv(prefix + ".shortcut", dim, dim, 1)
@@ -177,8 +192,8 @@ def make_codec_state_dict(seed: int = 0, use_conv_shortcut: bool = False, num_re
         ch *= 2
     lstm(f"encoder.layers.{idx}", ch)
     idx += 2
-    conv(f"encoder.layers.{idx}", hidden, ch, 7)
-    conv("decoder.layers.0", ch, hidden, 7)
+    conv(f"encoder.layers.{idx}", hidden, ch, k_last)
+    conv("decoder.layers.0", ch, hidden, k_first)
     lstm("decoder.layers.1", ch)
     idx = 2
     for r in ratios:
@@ -190,7 +205,7 @@ def make_codec_state_dict(seed: int = 0, use_conv_shortcut: bool = False, num_re
             idx += 1
         ch //= 2
     idx += 1
-    conv(f"decoder.layers.{idx}", 1, F, 7)
-    for q in range(4):
-        sd[f"quantizer.layers.{q}.codebook.embed"] = t(rs.standard_normal(size=(2048, hidden)) * (0.6 ** q))
+    conv(f"decoder.layers.{idx}", 1, F, k_last)
+    for q in range(n_q):
+        sd[f"quantizer.layers.{q}.codebook.embed"] = t(rs.standard_normal(size=(n_codes, hidden)) * (0.6 ** q))
     return sd
