@@ -25,7 +25,13 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 FULL_STEPS = 3       # steps whose [K,V] logits are stored in full (a case may lower it: spec["full_steps"])
 STRIDE = 61          # sub-sampling stride over V for all steps
 
-# name -> spec.  `arg_kw` feeds synth.make_args, `knobs` the reference call.
+# The two settings of synth.trained_stats the stats cases (and tests/test_trained_stats_cpu.py, tests/test_gpu_trained_stats.py) use.
+# A: a large common offset that drifts with every residual update, peaked attention, raw scores past the range of fp32 exp (the bf16
+#    tests lower k_bias to 8: tests/_util.py stats_a).  B: a few massive-activation channels carry a row's sigma.
+STATS_A = dict(seed=1, offset=32.0, drift=4.0, qk_gain=3.0, k_bias=40.0)
+STATS_B = dict(seed=1, offset=4.0, drift=1.0, qk_gain=3.0, n_out=4, out_mag=40.0)
+
+# name -> spec.  `arg_kw` feeds synth.make_args, `knobs` the reference call, `sd_kw` synth.make_state_dict, `stats_kw` synth.trained_stats.
 MODEL_CASES = {
     "tts_greedy": dict(preset="tiny", arg_kw={}, wseed=3, prompt=(6, 21, 11), mode="tts",
                        knobs=dict(top_k=1, top_p=1.0, temperature=1.0, stop_repetition=3, kvcache=1)),
@@ -132,6 +138,14 @@ MODEL_CASES = {
                                 knobs=dict(top_k=1, top_p=1.0, temperature=1.0, stop_repetition=3, kvcache=1)),
     "tts_vcap": dict(preset="tiny", arg_kw=dict(n_special=128), wseed=30, prompt=(6, 21, 50), mode="tts", full_steps=2,   # V = 2176 = 64 x 34
                      knobs=dict(top_k=1, top_p=1.0, temperature=1.0, stop_repetition=3, kvcache=1)),
+    # ---- the value regime of a trained checkpoint (synth.trained_stats; prompt seeds: tests/trained_stats_cases.py): residual rows with |mean| >> sigma, peaked attention whose raw
+    # scores leave the range of fp32 exp (setting A) / a few massive-activation channels that dominate a row's sigma (setting B)
+    "tts_stats_greedy": dict(preset="tiny", arg_kw=dict(num_decoder_layers=4), wseed=3, prompt=(6, 40, 14005), mode="tts",
+                             sd_kw=dict(head_gain=4.0), stats_kw=STATS_A,
+                             knobs=dict(top_k=1, top_p=1.0, temperature=1.0, stop_repetition=3, kvcache=1)),
+    "edit_stats_2span": dict(preset="tiny128", arg_kw=dict(num_decoder_layers=3), wseed=3, prompt=(9, 64, 1017), mode="edit", spans=[(10, 18), (40, 47)],
+                             sd_kw=dict(head_gain=4.0), stats_kw=STATS_B,
+                             knobs=dict(top_k=1, top_p=1.0, temperature=1.0, stop_repetition=-1, kvcache=1)),
 }
 
 
@@ -208,7 +222,10 @@ def case_state_dict(spec, args):
     """The synthetic checkpoint of a golden case (shared with tests/_util.py)."""
     kw = dict(mute_eos=True)
     kw.update(spec.get("sd_kw", {}))
-    return synth.make_state_dict(args, seed=spec["wseed"], perturb=True, **kw)
+    sd = synth.make_state_dict(args, seed=spec["wseed"], perturb=True, **kw)
+    if "stats_kw" in spec:          # the value regime of a trained checkpoint (synth.trained_stats) on top of the same draws
+        sd = synth.trained_stats(sd, args, **spec["stats_kw"])
+    return sd
 
 
 def run_reference_case(spec):

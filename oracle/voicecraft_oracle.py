@@ -74,7 +74,10 @@ def sine_table(n: int, d: int) -> torch.Tensor:
 
 
 class VoiceCraftOracle:
-    def __init__(self, args: Namespace | dict, state_dict: dict[str, torch.Tensor]):
+    def __init__(self, args: Namespace | dict, state_dict: dict[str, torch.Tensor], dtype: torch.dtype = torch.float32):
+        """dtype: torch.float64 runs the same fp32 model (weights and sine table widened exactly) in double-precision arithmetic,
+        masks and K/V cache included - for tests that measure the fp32 oracle's own rounding.  The default is the reference's fp32."""
+        self.dtype = dtype
         a = dict(vars(args)) if isinstance(args, Namespace) else dict(args)
         self.d = int(a["d_model"]); self.H = int(a["nhead"]); self.L = int(a["num_decoder_layers"])
         self.K = int(a["n_codebooks"])
@@ -88,15 +91,15 @@ class VoiceCraftOracle:
         self.special_first = int(a.get("special_first", 0) or 0)
         self.encodec_sr = int(a["encodec_sr"])
         self.max_n_spans = int(a["max_n_spans"])
-        self.sd = {k: v.detach().to(torch.float32) for k, v in state_dict.items() if v.is_floating_point()}
-        self.pe = sine_table(4000, self.d)
+        self.sd = {k: v.detach().to(torch.float32).to(dtype) for k, v in state_dict.items() if v.is_floating_point()}
+        self.pe = sine_table(4000, self.d).to(dtype)
         self.hd = self.d // self.H
 
     # ---- small pieces
     def _pos(self, emb: torch.Tensor, which: str) -> torch.Tensor:
         n = emb.size(1)
         if n > self.pe.size(1):
-            self.pe = sine_table(n, self.d)
+            self.pe = sine_table(n, self.d).to(self.dtype)
         return emb * 1.0 + self.sd[f"{which}_positional_embedding.alpha"] * self.pe[:, :n]
 
     def _embed_cols(self, cols: torch.Tensor) -> torch.Tensor:
@@ -155,7 +158,7 @@ class VoiceCraftOracle:
     def _causal_rows(self, B: int, S: int, n_last: int) -> torch.Tensor:
         """float mask [B,H,n_last,S]: last n_last rows of the lower-triangular mask (voicecraft.py:419-447)."""
         tri = torch.triu(torch.ones(S, S), diagonal=1).bool()
-        m = torch.zeros(S, S).masked_fill_(tri, float("-inf"))
+        m = torch.zeros(S, S, dtype=self.dtype).masked_fill_(tri, float("-inf"))
         return m[-n_last:].unsqueeze(0).unsqueeze(0).expand(B, self.H, n_last, S).contiguous()
 
     # ---- the shared generation loop
@@ -202,7 +205,7 @@ class VoiceCraftOracle:
                 out, present = self._stack(xy, self._causal_rows(B, S, S), None)
                 out = out[:, Lx:]
                 if kvcache:
-                    past = present.to(torch.float32)
+                    past = present.to(self.dtype)
             logits = self._heads(out[:, -1:])                                        # [B,K,V]
             if trace is not None:
                 trace.append({"logits": logits.clone()})
@@ -526,7 +529,7 @@ class VoiceCraftOracle:
         tri[:Lx, Lx:] = True
         pad = torch.cat([torch.arange(Lx)[None] >= x_lens[:, None], torch.arange(S)[None] >= new_y_lens[:, None]], dim=1)
         m = tri[None] | pad[:, None, :]
-        mask = torch.zeros(B, Lx + S, Lx + S).masked_fill_(m, float("-inf"))[:, None].expand(B, self.H, Lx + S, Lx + S).contiguous()
+        mask = torch.zeros(B, Lx + S, Lx + S, dtype=self.dtype).masked_fill_(m, float("-inf"))[:, None].expand(B, self.H, Lx + S, Lx + S).contiguous()
         out, _ = self._stack(torch.cat([x_input, y_input], dim=1), mask, None)
         y_out = out[:, Lx:]
         logits = torch.stack([F.linear(F.gelu(F.linear(y_out, self.sd[f"predict_layer.{k}.0.weight"], self.sd[f"predict_layer.{k}.0.bias"])),

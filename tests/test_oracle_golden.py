@@ -21,8 +21,12 @@ def test_oracle_matches_reference(name):
     lg = torch.stack([t["logits"][0] for t in trace]).numpy()
     full = MODEL_CASES[name].get("full_steps", FULL_STEPS)
     assert len(g["logits_full"]) == min(full, len(lg))
-    np.testing.assert_allclose(lg[:full], g["logits_full"], rtol=0, atol=2e-6)
-    np.testing.assert_allclose(lg[:, :, ::STRIDE], g["logits_sub"], rtol=0, atol=2e-6)
+    # 2e-6 is the rounding of a residual stream of O(1) values summed in another order (thread count, BLAS blocking).  The
+    # trained-statistics cases carry a common offset of n_codebooks * offset on every audio row: fp32 rounds it, and whatever is
+    # added to it, that many times coarser
+    atol = 2e-6 * max(1.0, lg.shape[1] * MODEL_CASES[name].get("stats_kw", {}).get("offset", 0.0))
+    np.testing.assert_allclose(lg[:full], g["logits_full"], rtol=0, atol=atol)
+    np.testing.assert_allclose(lg[:, :, ::STRIDE], g["logits_sub"], rtol=0, atol=atol)
 
 
 def test_length_identities():

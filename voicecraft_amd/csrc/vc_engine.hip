@@ -36,6 +36,7 @@ struct Layer {
   uint4 *Wqkv16 = nullptr;                                              // Wqkv . gamma in 16-channel tiles (prefill and wide-decode passes, option "qkv16")
   uint4 *Wqkv8 = nullptr;                                               // Wqkv . gamma in 8-channel tiles (one-row paired QKV kernel, option "qkv_p8")
   float *bqkv = nullptr, *bo = nullptr, *b1 = nullptr, *b2 = nullptr;   // bqkv / b1 hold the FOLDED biases (W beta + b)
+  float bo_mean = 0.f, b2_mean = 0.f;   // mean over the d channels of bo / b2: what the update moves a row's mean by whatever its input (GemmArgs.mu_shift)
   float *wg_qkv = nullptr, *wg_1 = nullptr;                             // row sums of the folded weights W . gamma
   void *kc = nullptr, *vc = nullptr;   // KV cache of this layer: WT [max_seqs][H][S_max][hd]
 };
@@ -290,13 +291,20 @@ int pack_folded(vc_engine* e, const std::string& wkey, const std::string& bkey, 
   return VC_OK;
 }
 
-int keep_vec(vc_engine* e, const std::string& key, int n, float** out) {
+int keep_vec(vc_engine* e, const std::string& key, int n, float** out, float* mean = nullptr) {
   const RawTensor* t;
   int rc = need(e, key, {n}, &t);
   if (rc) return rc;
   rc = dalloc(e, out, (size_t)n);
   if (rc) return rc;
   HIPCHK(e, hipMemcpy(*out, t->dev, (size_t)n * 4, hipMemcpyDeviceToDevice));
+  if (mean) {
+    std::vector<float> host((size_t)n);
+    HIPCHK(e, hipMemcpy(host.data(), t->dev, (size_t)n * 4, hipMemcpyDeviceToHost));
+    double sum = 0.0;
+    for (float v : host) sum += v;
+    *mean = (float)(sum / n);
+  }
   return VC_OK;
 }
 
@@ -490,7 +498,8 @@ int site_ln(vc_engine* e, const RowSrc& rs, const Resid& r, hipStream_t s) {
 // The finished-row consumers' `row_mu` ping-pong: QKV reads the means in row_mu[0] and leaves the rows' new means in row_mu[1], which
 // the out-projection centres its copy on; FFN-up reads row_mu[1] and leaves row_mu[0] for the FFN down-projection and the heads.
 // q,k,v = Wqkv LN1(h) + b ; K/V go straight into the cache.  first: layer 0 (no centred copy of its input rows).
-int site_qkv(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly, const Resid& r, bool first, hipStream_t s) {
+int site_qkv(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly, const Resid& r, const Layer* prev, hipStream_t s) {
+  const bool first = prev == nullptr;
   const int d = e->d;
   GemmArgs g = base_args(e, rs, e->p_qkv, 3 * d, d);
   g.Wp = ly.Wqkv; nt_bit(e, g, NT_QKV); g.bias = ly.bqkv; g.wg = ly.wg_qkv;
@@ -499,7 +508,7 @@ int site_qkv(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly,
     g.h_in = r.h_in;
     if (p.hq) g.row_mu_out = e->row_mu[1];
     if (p.hq && !first) {      // the previous layer's FFN down-projection left hqB = WT(hB - row_mu[0])
-      g.x_in = e->hqB; g.x_ld = d; g.row_mu = e->row_mu[0];
+      g.x_in = e->hqB; g.x_ld = d; g.row_mu = e->row_mu[0]; g.mu_shift = prev->b2_mean;
       if (p.qp) { g.Wp = ly.Wqkv8; HIPCHK(e, vc_launch_gemm_qp(g, e->dtype, s)); }
       else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNQ, EPI_QKV, 1, 1, s));
     } else {
@@ -552,7 +561,7 @@ int site_oproj(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& l
   if (p.form == FORM_FR) {
     g.Wp = ly.Wo8; g.bias = ly.bo;
     g.h_in = h; g.h_out = e->hA;
-    if (p.hq) { g.hq_out = e->hqA; g.row_mu = e->row_mu[1]; }      // centred on the mean the QKV consumer found for h
+    if (p.hq) { g.hq_out = e->hqA; g.row_mu = e->row_mu[1]; g.mu_shift = ly.bo_mean; }      // centred on the mean the QKV consumer found for h + the mean of bo
     if (p.att_x) {
       g.x_in = e->xn; g.x_ld = d;
       HIPCHK(e, vc_launch_gemm_fr(g, e->dtype, PRO_PLAIN, s));
@@ -583,7 +592,7 @@ int site_ffn_up(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& 
   if (p.form == FORM_FR) {
     g.h_in = r.h_in;
     if (p.hq) {
-      g.x_in = e->hqA; g.x_ld = d; g.row_mu = e->row_mu[1]; g.row_mu_out = e->row_mu[0];
+      g.x_in = e->hqA; g.x_ld = d; g.row_mu = e->row_mu[1]; g.mu_shift = ly.bo_mean; g.row_mu_out = e->row_mu[0];
       HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNQ, EPI_RELU, 1, 1, s));
     } else {
       HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNW, EPI_RELU, 1, 1, s));
@@ -609,7 +618,7 @@ int site_ffn_down(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer
   if (p.form == FORM_FR || p.fd) {
     g.Wp = ly.W28; g.bias = ly.b2;
     g.h_in = e->hA; g.h_out = e->hB;
-    if (p.hq) { g.hq_out = e->hqB; g.row_mu = e->row_mu[0]; }      // centred on the mean the FFN-up consumer found for h'
+    if (p.hq) { g.hq_out = e->hqB; g.row_mu = e->row_mu[0]; g.mu_shift = ly.b2_mean; }      // centred on the mean the FFN-up consumer found for h' + the mean of b2
     if (p.fd) HIPCHK(e, vc_launch_gemm_fr1(g, e->dtype, PRO_PLAIN, EPI_RES, s));
     else if (p.frp) HIPCHK(e, vc_launch_gemm_frp(g, e->dtype, s));      // 2..8 rows: two k-tiles per fragment
     else HIPCHK(e, vc_launch_gemm_fr(g, e->dtype, PRO_PLAIN, s));
@@ -633,7 +642,7 @@ int run_pass(vc_engine* e, const PassPlan& p, const RowSrc& rs, PassOut* out, hi
     const float* h = prev ? e->hB : rs.h_in;
     const Resid rq = qkv_in(e, p, ly, h, prev), rf = ffn_in(e, p, ly, h);
     int rc;
-    if ((p.ln_launch && (rc = site_ln(e, rs, rq, s))) || (rc = site_qkv(e, p, rs, ly, rq, !prev, s)) || (rc = site_attn(e, p, rs, ly, s)) ||
+    if ((p.ln_launch && (rc = site_ln(e, rs, rq, s))) || (rc = site_qkv(e, p, rs, ly, rq, prev, s)) || (rc = site_attn(e, p, rs, ly, s)) ||
         (rc = site_oproj(e, p, rs, ly, h, s)) || (p.ln_launch && (rc = site_ln(e, rs, rf, s))) || (rc = site_ffn_up(e, p, rs, ly, rf, s)) ||
         (rc = site_ffn_down(e, p, rs, ly, s)))
       return rc;
@@ -1296,7 +1305,7 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
       if ((rc = pack_matrix(e, pre + "self_attn.in_proj_weight", 3 * d, d, &ly.Wqkv16, 16, tg1->dev))) return rc;
     }
     if ((rc = pack_matrix(e, pre + "self_attn.out_proj.weight", d, d, &ly.Wo))) return rc;
-    if ((rc = keep_vec(e, pre + "self_attn.out_proj.bias", d, &ly.bo))) return rc;
+    if ((rc = keep_vec(e, pre + "self_attn.out_proj.bias", d, &ly.bo, &ly.bo_mean))) return rc;
     if ((rc = pack_folded(e, pre + "linear1.weight", pre + "linear1.bias", pre + "norm2.", 4 * d, d,
                           &ly.W1, &ly.wg_1, &ly.b1))) return rc;
     if ((rc = pack_matrix(e, pre + "linear2.weight", d, 4 * d, &ly.W2))) return rc;
@@ -1314,7 +1323,7 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
         if ((rc = pack_matrix(e, pre + "self_attn.in_proj_weight", 3 * d, d, &ly.Wqkv8, VC_TH_RES, tg1->dev))) return rc;
       }
     }
-    if ((rc = keep_vec(e, pre + "linear2.bias", d, &ly.b2))) return rc;
+    if ((rc = keep_vec(e, pre + "linear2.bias", d, &ly.b2, &ly.b2_mean))) return rc;
     const size_t cache_bytes = (size_t)e->B_max * e->H * e->S_max * e->hd * e->esz;
     char* kc; char* vc;
     if ((rc = dalloc(e, &kc, cache_bytes))) return rc;
@@ -2741,7 +2750,7 @@ extern "C" int vc_bench_kernel(vc_engine* e, const char* which, int n_rows, int 
   auto one = [&](int i) -> int {
     const Layer& ly = e->layers[hot ? 0 : i % e->L];   // _hot: the same 8-34 MB every launch (cache-resident)
     const Resid rq = qkv_in(e, p, ly, e->hB, &ly), rf = ffn_in(e, p, ly, e->hB);
-    if (site == "qkv") return site_qkv(e, p, rs, ly, rq, false, s);
+    if (site == "qkv") return site_qkv(e, p, rs, ly, rq, &ly, s);
     if (site == "attn") return site_attn(e, p, rs, ly, s);
     if (site == "oproj") return site_oproj(e, p, rs, ly, e->hB, s);
     if (site == "ln") return site_ln(e, rs, rf, s);         // the per-row LayerNorm launch in front of the FFN up-projection

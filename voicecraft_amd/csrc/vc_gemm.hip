@@ -350,9 +350,9 @@ __global__ __launch_bounds__(256 * NTW) void rows_gemm_k(const GemmArgs a) {
     if constexpr (TWO_ROWS) { VC_LNW_ROW(xb, rowB); }
 #undef VC_LNW_ROW
   } else if constexpr (PRO == PRO_LNQ) {
-    // The same fold on the producer's centred copy q = WT(h - c) of the finished rows (c = a.row_mu[row], the mean the PREVIOUS LayerNorm of
-    // the row found): W LN(h) = rstd (W' q - mean(q) rowsum(W')) + cb holds for any c, and |mean(q)| stays far below sigma because one
-    // residual update moves a row's mean by little - the rounding of q keeps its mantissa for the signal, as with the exact mean.  A wave
+    // The same fold on the producer's centred copy q = WT(h - c) of the finished rows (c = a.row_mu[row] + a.mu_shift: the mean the PREVIOUS LayerNorm of
+    // the row found, plus the mean of the bias the producer's update added): W LN(h) = rstd (W' q - mean(q) rowsum(W')) + cb holds for any c, and
+    // |mean(q)| stays far below sigma because the rest of one residual update moves a row's mean by little - the rounding of q keeps its mantissa for the signal, as with the exact mean.  A wave
     // copies its row(s) from HBM / L2 to LDS as they are (16 bytes per lane and request: HALF the bytes of the fp32 rows in bf16 mode, no
     // conversion) and sums the values and their squares on the way.
     const int d = a.d;
@@ -363,7 +363,7 @@ __global__ __launch_bounds__(256 * NTW) void rows_gemm_k(const GemmArgs a) {
     constexpr bool TWO_ROWS = (NTW == 1) || R2;
     const char* qA = reinterpret_cast<const char*>(a.x_in) + (long)min(rowA, n_rows - 1) * d * (long)sizeof(WT);
     const char* qB = reinterpret_cast<const char*>(a.x_in) + (long)min(rowB, n_rows - 1) * d * (long)sizeof(WT);
-    const float cA = a.row_mu[min(rowA, n_rows - 1)], cB = a.row_mu[min(rowB, n_rows - 1)];
+    const float cA = a.row_mu[min(rowA, n_rows - 1)] + a.mu_shift, cB = a.row_mu[min(rowB, n_rows - 1)] + a.mu_shift;
     uint4 xa[8], xb[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -617,7 +617,7 @@ __global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_fr_k(const GemmArg
   // epilogue operands first (a wave's loads return in order): the residual and the bias of the lane's four channels
   const float4 eres = *reinterpret_cast<const float4*>(a.h_in + (long)((m < n_rows) ? m : 0) * a.d + n);
   const float4 eb = *reinterpret_cast<const float4*>(a.bias + n);
-  const float cmu = a.row_mu[(m < n_rows) ? m : 0];                      // centring constant of the row's copy in the compute dtype (hq_out)
+  const float cmu = a.row_mu[(m < n_rows) ? m : 0] + a.mu_shift;         // centring constant of the row's copy in the compute dtype (hq_out)
   const uint4* wbase = a.Wp + ((long)nt * a.KT + wave * KTW) * SPT;      // wave-uniform
   uint4 wf[KTW];
 #define VC_FR_WEIGHTS(c_)                                                                        \
@@ -819,7 +819,7 @@ __global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_fr2_k(const GemmAr
   const int wslot = kg * TH + min(m, TH - 1);
   const float4 eres = *reinterpret_cast<const float4*>(a.h_in + (long)((m < n_rows) ? m : 0) * a.d + n);
   const float4 eb = *reinterpret_cast<const float4*>(a.bias + n);
-  const float cmu = a.row_mu[(m < n_rows) ? m : 0];
+  const float cmu = a.row_mu[(m < n_rows) ? m : 0] + a.mu_shift;
   const uint4* wbase = a.Wp + ((long)nt * a.KT + wave * KTW) * SPT;      // wave-uniform; the second half is NW * KTW k-tiles further
   uint4 wfa[KTW], wfb[KTW];
   const int upr = Kh * (int)sizeof(WT) / 16;       // 16-byte units per row and half; rows x upr <= 16 x 512 (host contract)
@@ -1254,7 +1254,7 @@ __global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_frp_k(const GemmAr
   const int nfin = nt * TH + 4 * (tid & 1);
   const float4 eres = *reinterpret_cast<const float4*>(a.h_in + (long)frow * a.d + nfin);
   const float4 eb = *reinterpret_cast<const float4*>(a.bias + nfin);
-  const float cmu = a.row_mu[frow];
+  const float cmu = a.row_mu[frow] + a.mu_shift;
   // X rows as 16-byte units, flat index = row * upr + unit; RMAX * NPW / 8 units per thread
   constexpr int NXU = RMAX * ((NPW * 8 + 63) / 64);
   const int ush = a.x_upr_shift;                    // log2(units per row)
@@ -1401,7 +1401,7 @@ __global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_qp_k(const GemmArg
   // wave r < n_rows: row r of the centred copy, NPW requests of 1 KB
   const int xrow = min(wave, n_rows - 1);
   const char* qsrc = reinterpret_cast<const char*>(a.x_in) + (long)xrow * a.x_ld * (long)sizeof(WT);
-  const float cmu = a.row_mu[xrow];
+  const float cmu = a.row_mu[xrow] + a.mu_shift;
   uint4 xq[NPW];
 #pragma unroll
   for (int j = 0; j < NPW; ++j) xq[j] = *reinterpret_cast<const uint4*>(qsrc + (j * 64 + lane) * 16);

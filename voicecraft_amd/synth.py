@@ -27,12 +27,14 @@ PRESETS = {
 
 def make_args(preset: str = "giga830M", *, eos: int = 2051, n_special: int = 4, reduced_eog: int = 1,
               n_codebooks: int = 4, max_n_spans: int = 3, audio_vocab_size: int = 2048,
-              text_vocab_size: int = 100) -> Namespace:
+              text_vocab_size: int = 100, num_decoder_layers: int | None = None) -> Namespace:
     """The `args` Namespace the reference pickles next to a checkpoint (config.py:55-84).
 
     `empty` / `eog` / `pad` follow the audio vocabulary (voicecraft.py:132-134: V, V+1, V+2).  `eos` keeps its default
     of 2051 only with the default vocabulary; with another one it becomes audio_vocab_size + 3 unless the caller set it."""
     d, h, l = PRESETS[preset]
+    if num_decoder_layers is not None:          # a preset's width at another depth (the tiny presets have 2 layers)
+        l = int(num_decoder_layers)
     if audio_vocab_size != 2048 and eos == 2051:
         eos = audio_vocab_size + 3
     return Namespace(
@@ -122,6 +124,46 @@ def make_state_dict(args: Namespace, seed: int = 0, perturb: bool = True, mute_e
                 b[int(tok)] += float(delta)
         sd[p + "2.bias"] = b
     return sd
+
+
+def trained_stats(sd: dict, args: Namespace, *, seed: int = 0, offset: float = 0.0, drift: float = 0.0, qk_gain: float = 1.0,
+                  k_bias: float = 0.0, n_out: int = 0, out_mag: float = 0.0) -> dict[str, torch.Tensor]:
+    """A transformed COPY of a `make_state_dict` checkpoint with the value statistics of a trained pre-LN stack, which the default
+    initialisation never reaches (there every LayerNorm input has |mean| << sigma and the attention softmax is nearly uniform).
+    `make_state_dict` and its frozen stream are untouched; this function draws from a stream of its own, RandomState(1000 + seed).
+
+    offset:   added to every element of every `*word_embeddings.weight` and of `mask_embedding`: the residual stream carries a
+              common offset (text rows have mean `offset`, audio rows K * offset), so |mean| >> sigma at every LayerNorm input.
+    drift:    added to every element of each layer's `out_proj.bias` and `linear2.bias`: every residual update moves the row's mean.
+    n_out, out_mag: `n_out` channels (drawn without replacement) get +-out_mag / (2 L) on the same two biases of every layer, so
+              that after the stack a few "massive activation" channels of magnitude ~out_mag dominate a row's sigma.
+    qk_gain:  multiplies rows [0, 2d) of `in_proj_weight` / `in_proj_bias` (the q and k projections): scores scale by qk_gain^2,
+              the softmax becomes peaked.
+    k_bias:   then +-k_bias (random sign per channel) is added to the k bias: every raw score of a query moves by the same
+              q . b, far past the range of fp32 exp; by shift invariance the softmax itself does not change.
+    """
+    rs = np.random.RandomState(1000 + seed)
+    d, L = args.d_model, args.num_decoder_layers
+    ch = rs.choice(d, n_out, replace=False)
+    sg = rs.choice([-1, 1], n_out)
+    out = {k: v.clone() for k, v in sd.items()}
+    for k in out:
+        if k.endswith("word_embeddings.weight") or k == "mask_embedding":
+            out[k] += float(offset)
+    spike = torch.zeros(d, dtype=torch.float32)
+    spike[torch.from_numpy(ch.astype(np.int64))] = torch.from_numpy((sg * (out_mag / (2.0 * L))).astype(np.float32))
+    for l in range(L):
+        p = f"decoder.layers.{l}."
+        for name in ("self_attn.out_proj.bias", "linear2.bias"):
+            out[p + name] += float(drift)
+            out[p + name] += spike
+        out[p + "self_attn.in_proj_weight"][: 2 * d] *= float(qk_gain)
+        out[p + "self_attn.in_proj_bias"][: 2 * d] *= float(qk_gain)
+    if k_bias:
+        for l in range(L):
+            sign = torch.from_numpy(rs.choice([-1, 1], d).astype(np.float32))
+            out[f"decoder.layers.{l}.self_attn.in_proj_bias"][d: 2 * d] += sign * float(k_bias)
+    return out
 
 
 def random_prompt(args: Namespace, Lx: int, T: int, seed: int = 1):
