@@ -197,40 +197,65 @@ int vc_tts_stream_next(vc_engine* e, int min_frames, int64_t* codes_dev, int cap
                        int* first_frame, int* n_frames, int* done);
 int vc_tts_stream_end(vc_engine* e, int64_t* res_dev, int res_cap, int* gen_len, int* n_steps);
 
-/* ---- decode sessions: continuous batching of TTS requests (inference_tts semantics, one sample each).  A session keeps the decode
- * loop open: requests are submitted at any time, each is prefilled into a free K/V slot between two graph batches and joins the
- * running batch, and each result can be fetched as soon as its own sequence has ended - the batch is refilled instead of idling
- * to its longest member.  The step width follows the live count both ways (the next power of two, captured graphs per width).
- * The sampling controls (top_k, top_p, temperature, stop_repetition, silence_tokens, use_graph) are fixed at open; the seed is per
- * request: a request draws on the Philox stream (its seed, sequence 0, its own step, codebook) - the stream of a lone vc_tts call with
- * that seed - whatever slot it lands in.  Exact mode: every request's tokens are those of its own vc_tts call.  bf16: the tokens are a
- * function of the submissions and of the turn each was made at (the admission schedule is decided from retirements of batches the
- * host has seen end, never from how far the device runs ahead).
- * Not part of a session, because they have no per-request form here: editing, best-of-N, a shared text prefix, logits_out and forced
+/* ---- decode sessions: continuous batching of TTS and speech-editing requests (inference_tts / inference semantics, one sample each).
+ * A session keeps the decode loop open: requests are submitted at any time, each is prefilled into a free K/V slot between two graph
+ * batches and joins the running batch, and each result can be fetched as soon as its own sequence has ended - the batch is refilled
+ * instead of idling to its longest member.  The step width follows the live count both ways (the next power of two, captured graphs
+ * per width).  Both kinds of request share one decode step: an editing request decodes one row per step with its span switches fed
+ * over three steps, as in vc_edit_multi.
+ * Sampling controls: top_k, top_p, temperature and stop_repetition are per REQUEST (vc_request_ctl; NULL = the values given at open);
+ * silence_tokens and use_graph are the session's, fixed at open.  The seed is per request: a request draws on the Philox stream (its
+ * seed, sequence 0, its own step, codebook) - the stream of a lone vc_tts / vc_edit_multi call with that seed - whatever slot it lands
+ * in.  Exact mode: every request's tokens are those of its own blocking call with its controls, whatever it shared a step with.  bf16:
+ * the tokens are a function of the submissions and of the turn each was made at (the admission schedule is decided from retirements of
+ * batches the host has seen end, never from how far the device runs ahead).
+ * Not part of a session, because they have no per-request form here: best-of-N, a shared text prefix, logits_out and forced
  * trajectories - the entry points below simply have no such arguments; use the blocking calls.
  *   open     max_live in [1, max_seqs] slots.  Captures the step graphs of every width the session can pass through (the powers of two
  *            up to the one for max_live), ahead of any timer.  VC_ESTATE while a streaming call or another session is open.  While a
  *            session is open every other decode entry point, vc_set_option and vc_tts_stream_begin return VC_ESTATE.
- *   submit   host-side checks at once, with vc_tts's codes: empty text (VC_EINVAL), a prompt that alone does not fit max_positions
- *            (VC_ECAP).  The request joins a FIFO; *ticket identifies it.  x_dev / y_dev must stay valid until the ticket is fetched
- *            or the session closed.
+ *   submit   a TTS request with the session's controls (submit_ctl with ctl = NULL).  submit_ctl: a TTS request with its own controls.
+ *            Host-side checks at once, with vc_tts's codes: empty text (VC_EINVAL), a prompt that alone does not fit max_positions
+ *            (VC_ECAP); a ctl whose temperature is not a finite positive number or whose top_p is not a number: VC_EINVAL.  The
+ *            request joins a FIFO; *ticket identifies it.  x_dev / y_dev must stay valid until the ticket is fetched or the session
+ *            closed; ctl is copied.
+ *   submit_edit  an editing request: mask_intervals [M][2] and mask_values [2M] are host arrays with vc_edit's meaning, copied at
+ *            submit.  Validated at once with vc_edit's codes and messages (span count; ordered, disjoint intervals; an empty non-masked
+ *            piece; mask value range; eos > 0 without reduced_eog; the rearranged prompt against max_positions and the prefill arena).
+ *            A refused submit of any kind leaves the session running.
  *   advance  one turn: wait for the older of the two batches in flight; note what it (or an earlier one) retired; admit from the FIFO
- *            into the free slots, in order; queue the prefill of the admitted requests, the re-pack to the width now needed, their
- *            first sample and the next batch.  tickets_out[0 .. *n_finished) = the requests found finished this turn, at most cap of
- *            them: one there is no room for is reported by a later turn (and holds its slot until then), so cap >= max_live reports
- *            every request in the turn that finds it.  If the queued work of a turn fails after requests were admitted, the session
- *            is broken: this and every later submit / advance return the error (VC_ESTATE afterwards) until it is closed.
- *            *idle = 1 when nothing is live, pending or in flight: an idle session queues nothing, and a later submit restarts it.
- *   fetch    assembles a finished request exactly as vc_tts does (res_dev [K][res_cap], *gen_len, *n_steps = its own step count) and
- *            frees its slot; res_dev = NULL drops it.  Unknown ticket: VC_EINVAL; unfinished: VC_ESTATE; ran out of positions before
- *            its terminator: VC_ECAP, as vc_tts; an out-of-range token id in its x / y: VC_EINVAL naming the ticket.  A finished
- *            request holds its slot until fetched (the slot's rows of the generated-token log are the result).
+ *            into the free slots, in order; queue the prefill of the admitted requests (both kinds in one pass), the re-pack to the
+ *            width now needed, their first sample and the next batch.  tickets_out[0 .. *n_finished) = the requests found finished this
+ *            turn, at most cap of them: one there is no room for is reported by a later turn (and holds its slot until then), so cap >=
+ *            max_live reports every request in the turn that finds it.  If the queued work of a turn fails after requests were
+ *            admitted, the session is broken: this and every later submit / advance return the error (VC_ESTATE afterwards) until it
+ *            is closed.  *idle = 1 when nothing is live, pending or in flight: an idle session queues nothing, and a later submit
+ *            restarts it.
+ *   fetch    assembles a finished request and frees its slot; res_dev = NULL drops it.  A TTS ticket: exactly as vc_tts does (res_dev
+ *            [K][res_cap], *gen_len = the generated frames Tg, res holds T + Tg columns).  An edit ticket: exactly as vc_edit does
+ *            (nonmask_0, gen_0, ..., nonmask_M) and *gen_len receives the RESULT length T'.  *n_steps = the request's own sampled
+ *            steps (the fed rows of a span switch are not steps).  Unknown ticket: VC_EINVAL; unfinished: VC_ESTATE; ran out of
+ *            positions before its terminator (an edit: before its last span ended): VC_ECAP, as vc_tts / vc_edit_multi; an
+ *            out-of-range token id in its x / y: VC_EINVAL naming the ticket.  A finished request holds its slot until fetched (the
+ *            slot's rows of the generated-token log are the result).
  *   stats    [0] requests admitted, [1] of them admitted while other sequences were live, [2] turns, [3] widenings, [4] narrowings,
- *            [5] sum over launched steps of the rows that were live (counted at retirement), [6] sum over launched steps of the step
- *            width, [7] microseconds of decode-stream time spent on admissions (prefill + re-pack + first sample; HIP events).
+ *            [5] sum over launched steps of the rows that were live, an edit's fed rows included (counted at retirement), [6] sum over
+ *            launched steps of the step width, [7] microseconds of decode-stream time spent on admissions (prefill + re-pack + first
+ *            sample; HIP events).
  *   close    waits for what is queued, drops everything pending and unfetched; the engine is reusable. */
+typedef struct vc_request_ctl {   /* 16 bytes: the per-request part of vc_sample_cfg, same meaning field by field */
+  int32_t top_k;
+  float top_p;
+  float temperature;
+  int32_t stop_repetition;
+} vc_request_ctl;
 int vc_session_open(vc_engine* e, int max_live, const vc_sample_cfg* sc, void* stream);
 int vc_session_submit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T, uint64_t seed, int* ticket);
+int vc_session_submit_ctl(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
+                          const vc_request_ctl* ctl, uint64_t seed, int* ticket);
+int vc_session_submit_edit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
+                           const int32_t* mask_intervals, int M, const int32_t* mask_values,
+                           const vc_request_ctl* ctl, uint64_t seed, int* ticket);
 int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* n_finished, int* idle);
 int vc_session_fetch(vc_engine* e, int ticket, int64_t* res_dev, int res_cap, int* gen_len, int* n_steps);
 int vc_session_stats(vc_engine* e, int64_t out[8]);

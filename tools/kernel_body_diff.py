@@ -1,0 +1,71 @@
+"""Kernel-by-kernel comparison of the gfx950 code of one translation unit at two commits: which kernels kept their code.
+
+usage: python tools/kernel_body_diff.py [--rev HEAD] [--unit vc_tokens] > profiles/<name>.log
+Compiles voicecraft_amd/csrc/<unit>.hip device-only (hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S) from the
+working tree and from `git show <rev>:` copies of csrc/ and include/ in a temporary directory, then compares each kernel's
+instruction lines after dropping comments, directives and the function index inside basic-block labels (.LBB<n>_)."""
+import argparse, os, re, subprocess, sys, tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import isa_store_scan as isa  # noqa: E402
+
+
+def compile_unit(tree, unit, out):
+    src = os.path.join(tree, "voicecraft_amd", "csrc", unit + ".hip")
+    r = subprocess.run([isa.HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-S", src, "-o", out],
+                       cwd=os.path.dirname(src), stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(r.stderr[-2000:])
+    return open(out).read()
+
+
+def checkout(rev, dst):
+    for d in ("voicecraft_amd/csrc", "include"):
+        os.makedirs(os.path.join(dst, d), exist_ok=True)
+        names = subprocess.run(["git", "ls-tree", "--name-only", f"{rev}:{d}"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.split()
+        for n in names:
+            blob = subprocess.run(["git", "show", f"{rev}:{d}/{n}"], cwd=ROOT, capture_output=True, check=True).stdout
+            open(os.path.join(dst, d, n), "wb").write(blob)
+
+
+def instructions(body):
+    out = []
+    for line in body.splitlines():
+        t = line.split(";")[0].strip()
+        if not t or (t.startswith(".") and not t.startswith(".LBB")):
+            continue
+        out.append(re.sub(r"\.LBB\d+_", ".LBB_", t))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rev", default="HEAD")
+    ap.add_argument("--unit", default="vc_tokens")
+    a = ap.parse_args()
+    with tempfile.TemporaryDirectory() as tmp:
+        checkout(a.rev, os.path.join(tmp, "parent"))
+        old = {isa.demangle(n): v for n, v in isa.kernels(compile_unit(os.path.join(tmp, "parent"), a.unit, os.path.join(tmp, "old.s"))).items()}
+        new = {isa.demangle(n): v for n, v in isa.kernels(compile_unit(ROOT, a.unit, os.path.join(tmp, "new.s"))).items()}
+    print(f"# gfx950 disassembly of voicecraft_amd/csrc/{a.unit}.hip (hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S),")
+    print("# parent commit against this build, kernel by kernel: instruction lines after dropping comments and directives and the")
+    print("# function index inside basic-block labels (.LBB<n>_)")
+    for name, (body, scratch, vgpr) in new.items():
+        facts = f"scratch {scratch} bytes, next_free_vgpr {vgpr}, stores waiting for an earlier store: {isa.store_chains(body)[0]}"
+        if name not in old:
+            print(f"{name[:72]:72s} new kernel: {facts}")
+            continue
+        i0, i1 = instructions(old[name][0]), instructions(body)
+        if i0 == i1:
+            print(f"{name[:72]:72s} {len(i1):5d} lines  IDENTICAL")
+        else:
+            print(f"{name[:72]:72s} CHANGED: {len(i0)} -> {len(i1)} lines; {facts} (parent: scratch {old[name][1]}, "
+                  f"next_free_vgpr {old[name][2]}, waiting stores {isa.store_chains(old[name][0])[0]})")
+    for name in old:
+        if name not in new:
+            print(f"{name[:72]:72s} REMOVED")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,5 +1,5 @@
 """Decode sessions (continuous batching) against what the blocking API offers for the same work, on ONE engine, interleaved pairs:
-python tools/session_bench.py [--preset giga830M] [--pairs 5] [--sizes 64:8,256:64]
+python tools/session_bench.py [--preset giga830M] [--pairs 5] [--sizes 64:8,256:64] [--edit-share 0.5]
 
 Workload: the ragged utterances of bench.py's ragged_block (giga830M shape, bf16, top-k 40, 150 prompt frames, the synthetic
 checkpoint's terminator muted, so an utterance of Lx phonemes ends at the reference's length cap: 10 Lx - 150 generated frames).  `N:L`
@@ -10,7 +10,12 @@ every consecutive group of L utterances is exactly that block's batch.
 Per size one JSON line: codec-tokens/s of both arms (median, min, max over the pairs) and the per-pair ratio; the mean number of live
 rows per launched step and the share of launched rows that were live (session: its own counters; baseline: from the utterances' step
 counts, with the launched rows simulated from the blocking loop's re-pack rule); the decode-stream time per admitted request (prefill +
-re-pack + first sample, HIP events).  Both arms produce the same number of frames per utterance (asserted)."""
+re-pack + first sample, HIP events).  Both arms produce the same number of frames per utterance (asserted).
+--edit-share F: that fraction of the requests (evenly spread) are one-span editing requests with the editing front-end's defaults
+(top_k 0, top_p 0.8, stop_repetition -1; the span covers the middle third of the prompt frames), submitted to the SAME session with
+their own controls next to the TTS requests.  The baseline then runs, for every consecutive group of L requests, inference_tts_multi on
+the group's TTS requests and inference_multi on its editing requests - what the blocking API offers when the two kinds cannot share a
+step; the frames compared and counted are the generated ones of either kind."""
 import argparse, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -27,12 +32,17 @@ p.add_argument("--prompt-frames", type=int, default=150)
 p.add_argument("--top-k", type=int, default=40)
 p.add_argument("--pairs", type=int, default=5)
 p.add_argument("--sizes", default="64:8,256:64")
+p.add_argument("--edit-share", type=float, default=0.0)
 args = p.parse_args()
 dev = torch.device("cuda", 0)
 a = synth.make_args(args.preset)
 K = a.n_codebooks
-sd = synth.make_state_dict(a, seed=0, perturb=False, mute_eos=True, fast=True)
+# (with editing requests in the mix every special token is muted, not only the TTS terminator: an edit then ends at the length cap
+# too - its terminator is eog - and both arms generate the same frames whatever their seeds)
+sd = synth.make_state_dict(a, seed=0, perturb=False, mute_eos=True, fast=True, mute_special=args.edit_share > 0)
 kn = dict(top_k=args.top_k, top_p=1.0, temperature=1.0, stop_repetition=3, silence_tokens=[1388, 1898, 131])
+ekn = dict(top_k=0, top_p=0.8, temperature=1.0, stop_repetition=-1)      # the editing front-end's defaults
+span = (args.prompt_frames // 3, 2 * (args.prompt_frames // 3))
 
 
 def stats(v):
@@ -70,6 +80,7 @@ for size in args.sizes.split(","):
     N, L = (int(v) for v in size.split(":"))
     lxs = [args.lx if L == 1 else args.lx_min + (args.lx - args.lx_min) * (u % L) // (L - 1) for u in range(N)]
     prompts = [synth.random_prompt(a, lxs[u], args.prompt_frames, seed=1 + u) for u in range(N)]
+    is_edit = [int((u + 1) * args.edit_share) > int(u * args.edit_share) for u in range(N)]
     xs = [q[0][0].to(dev) for q in prompts]
     ys = [q[2][0].to(dev) for q in prompts]
     eng = VoiceCraftEngine(a, sd, device=dev, dtype=args.dtype, max_seqs=L, max_positions=max(1024, args.lx * 11 + 64))
@@ -80,11 +91,21 @@ for size in args.sizes.split(","):
         t0 = time.perf_counter()
         frames, sim = [], [0, 0, 0]
         for g0 in range(0, N, L):
-            outs = eng.inference_tts_multi(xs[g0: g0 + L], ys[g0: g0 + L], _seed=seed + g0, **kn)
-            f = [int(gen.shape[2]) for res, gen in outs]
-            frames += f
-            for i, v in enumerate(simulate_blocking_rows([x + K for x in f], G)):
-                sim[i] += v
+            grp = list(range(g0, min(N, g0 + L)))
+            tts, edits = [u for u in grp if not is_edit[u]], [u for u in grp if is_edit[u]]
+            f = {}
+            if tts:
+                outs = eng.inference_tts_multi([xs[u] for u in tts], [ys[u] for u in tts], _seed=seed + g0, **kn)
+                f.update({u: int(gen.shape[2]) for u, (res, gen) in zip(tts, outs)})
+            if edits:
+                outs = eng.inference_multi([xs[u] for u in edits], [ys[u] for u in edits], [[span]] * len(edits), _seed=seed + g0,
+                                           silence_tokens=kn["silence_tokens"], **ekn)
+                f.update({u: int(res.shape[2]) - (args.prompt_frames - (span[1] - span[0])) for u, res in zip(edits, outs)})
+            frames += [f[u] for u in grp]
+            for part in (tts, edits):
+                if part:
+                    for i, v in enumerate(simulate_blocking_rows([f[u] + K for u in part], G)):
+                        sim[i] += v
         torch.cuda.synchronize()
         wall = time.perf_counter() - t0
         return dict(tok_s=sum(frames) * K / wall, wall_ms=wall * 1e3, frames=frames, live_rows=sim[0], launched_rows=sim[1], steps=sim[2])
@@ -93,12 +114,16 @@ for size in args.sizes.split(","):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         with eng.open_session(L, **kn) as sess:
-            tickets = [sess.submit(xs[u].reshape(1, -1), torch.tensor([lxs[u]]), ys[u].unsqueeze(0), seed=seed + u) for u in range(N)]
-            done = {t: gen for t, res, gen in sess.drain()}
+            mi = torch.tensor([[span]], dtype=torch.int64)
+            tickets = [sess.submit_edit(xs[u].reshape(1, -1), torch.tensor([lxs[u]]), ys[u].unsqueeze(0), mi, seed=seed + u, **ekn)
+                       if is_edit[u] else
+                       sess.submit(xs[u].reshape(1, -1), torch.tensor([lxs[u]]), ys[u].unsqueeze(0), seed=seed + u) for u in range(N)]
+            done = {t: (res, gen) for t, res, gen in sess.drain()}
             torch.cuda.synchronize()
             wall = time.perf_counter() - t0
             st = sess.stats(timing=True)
-        frames = [int(done[t].shape[2]) for t in tickets]
+        frames = [int(done[t][0].shape[2]) - (args.prompt_frames - (span[1] - span[0])) if is_edit[u] else int(done[t][1].shape[2])
+                  for u, t in enumerate(tickets)]
         return dict(tok_s=sum(frames) * K / wall, wall_ms=wall * 1e3, frames=frames, live_rows=st["live_rows"],
                     launched_rows=st["launched_rows"], steps=(st["turns"] - 1) * G, admitted=st["admitted"],
                     admitted_while_live=st["admitted_while_live"], widenings=st["widenings"], narrowings=st["narrowings"],
@@ -112,7 +137,7 @@ for size in args.sizes.split(","):
             rows[arm].append(baseline(100 + i) if arm == "baseline" else session(100 + i))
     for b, s in zip(rows["baseline"], rows["session"]):
         assert b["frames"] == s["frames"], "both arms generate the same frames per utterance (the length cap ends every sequence)"
-    out = {"workload": f"{args.preset} {args.dtype}, top_k={args.top_k}, {N} utterances through {L} slots, Lx {min(lxs)}..{max(lxs)}, "
+    out = {"workload": f"{args.preset} {args.dtype}, top_k={args.top_k}, {N} utterances ({sum(is_edit)} of them editing requests) through {L} slots, Lx {min(lxs)}..{max(lxs)}, "
                        f"{args.prompt_frames} prompt frames -> {min(rows['session'][0]['frames'])}..{max(rows['session'][0]['frames'])} generated frames",
            "pairs": args.pairs, "graph_steps": G, "options": eng.options()}
     for arm in ("baseline", "session"):

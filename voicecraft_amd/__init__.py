@@ -5,7 +5,8 @@ Public surface (mirrors the reference's model interface):
     pattern_shift / pattern_revert / pattern_unshift   (delayed-codebook pattern, bit-exact)
     AudioTokenizer                                     (EnCodec encode/decode, .decode_stream())
     VoiceCraftEngine.inference_tts_stream, stream_tts  (tokens / audio while the decode loop runs)
-    VoiceCraftEngine.open_session -> DecodeSession, inference_tts_queue   (continuous batching: requests join a running batch)
+    VoiceCraftEngine.open_session -> DecodeSession, inference_tts_queue, inference_queue
+                                                       (continuous batching: TTS and editing requests join a running batch)
 Everything computes in libvcengine.so (HIP, gfx950); importing this package does not need a GPU,
 constructing an engine does.
 """
@@ -13,7 +14,7 @@ from .synth import PRESETS, make_args, make_state_dict, random_prompt  # noqa: F
 
 
 def __getattr__(name):
-    if name in ("VoiceCraftEngine", "DecodeSession", "SessionRequestError", "inference_tts_queue", "pattern_shift", "pattern_revert", "pattern_unshift"):
+    if name in ("VoiceCraftEngine", "DecodeSession", "SessionRequestError", "inference_tts_queue", "inference_queue", "pattern_shift", "pattern_revert", "pattern_unshift"):
         from . import engine
         return getattr(engine, name)
     if name == "stream_tts":

@@ -29,6 +29,11 @@ class SampleCfg(C.Structure):
     ]
 
 
+class RequestCtl(C.Structure):
+    """vc_request_ctl: the per-request sampling controls of a decode session (16 bytes)."""
+    _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float), ("temperature", C.c_float), ("stop_repetition", C.c_int32)]
+
+
 # name -> (restype, argtypes); the single source of truth the symbol test checks against the header
 PROTOTYPES = {
     "vc_create": (C.c_int, [C.POINTER(ModelCfg), C.c_int, C.POINTER(C.c_void_p)]),
@@ -48,6 +53,10 @@ PROTOTYPES = {
     "vc_tts_stream_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vc_session_open": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SampleCfg), C.c_void_p]),
     "vc_session_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_int)]),
+    "vc_session_submit_ctl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(RequestCtl), C.c_uint64,
+                                        C.POINTER(C.c_int)]),
+    "vc_session_submit_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                         C.POINTER(C.c_int32), C.POINTER(RequestCtl), C.c_uint64, C.POINTER(C.c_int)]),
     "vc_session_advance": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vc_session_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vc_session_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

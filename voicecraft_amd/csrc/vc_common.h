@@ -349,6 +349,8 @@ struct SampleDyn {
   const int* batch_id;      // device word: index of the graph batch the step belongs to (set between two batches by session_turn_k)
   const int* row_base;      // device word: first row of the sequences admitted this turn (their first sample touches rows [*row_base, +grid))
   const int* adm_slot;      // [grid] slot of each of them = the logits row its prefill left the first-step logits at
+  const vc_request_ctl* ctl_tab;   // [max_seqs] sampling controls of the request in each slot (written at admission by session_turn_k): a session's
+                            // sampler takes top_k / top_p / temperature / stop_repetition from here, never from the per-call values above
 };
 
 struct SampleArgs {         // engine-constant part (kernel argument)
@@ -380,9 +382,11 @@ struct SampleArgs {         // engine-constant part (kernel argument)
   float alpha_audio;
   int max_positions;
 };
-// retirement record of a slot: [0] batch stamp + 1 (0 = none), [1] total steps, [2] spans finished (0 = ran out of positions),
-// [3] steps of span 0, [4] error bits of the request's prompt (prompt_k; written at admission)
-#define VC_SESS_REC 8
+// retirement record of a slot: [0] batch stamp + 1 (0 = none), [1] total steps, [2] spans finished (fewer than the request's = ran out of
+// positions), [3] steps of span 0, [4] error bits of the request's prompt (prompt_k; written at admission), [5] rows the request fed without
+// sampling (two per span switch of an editing request), [VC_SESS_REC_SPANS + i] steps of span i (what edit_assemble needs of the final state)
+#define VC_SESS_REC_SPANS 8
+#define VC_SESS_REC (VC_SESS_REC_SPANS + VC_MAX_SPANS)
 
 struct AssembleArgs {       // writes res [K][res_cap] from y and the generated spans
   const int64_t* y;         // [T][K]
@@ -456,11 +460,12 @@ struct SessTurnArgs {
   int* row_base;
   int* adm_slot;            // [max_seqs]
   uint64_t* seed_tab;       // [max_seqs] by slot
+  vc_request_ctl* ctl_tab;  // [max_seqs] by slot
+  const SeqState* adm_st;   // [n_new] device staging: the admitted requests' first states, slot set (uploaded on the decode stream in front of this launch)
+  const vc_request_ctl* adm_ctl;   // [n_new] device staging: their sampling controls
   int* prompt_err;          // [max_seqs] by slot: prompt_k's error bits of the request prefilled into the slot (cleared here)
   int* retire_rec;          // pinned host, [max_seqs][VC_SESS_REC]
   int B_old, B_new, d, batch, repack, n_new;
-  int cap_mult, min_gen, term_token, kill_token;   // init_state of a TTS request (vc_engine.hip)
-  int slot[VC_MAX_SEQS], Lx[VC_MAX_SEQS], n_cols[VC_MAX_SEQS];
   uint64_t seed[VC_MAX_SEQS];
 };
 hipError_t vc_launch_session_turn(const SessTurnArgs& a, hipStream_t s);

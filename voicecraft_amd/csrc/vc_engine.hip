@@ -106,6 +106,11 @@ struct vc_engine {
   uint64_t* seed_tab = nullptr;
   int *batch_id = nullptr, *row_base = nullptr, *adm_slot = nullptr, *prompt_err = nullptr, *sess_gather = nullptr;
   int* h_rec = nullptr;
+  // ... the requests' sampling controls by slot (SampleDyn.ctl_tab), and the staging of a turn's admitted requests: their first states
+  // and controls, written by the host into one of VC_ADM_STAGES pinned buffers (rotated by batch index, see vc_session_advance) and
+  // uploaded on the decode stream into adm_st / adm_ctl in front of session_turn_k
+  vc_request_ctl *ctl_tab = nullptr, *adm_ctl = nullptr, *h_adm_ctl = nullptr;
+  SeqState *adm_st = nullptr, *h_adm_st = nullptr;
   // Non-temporal weight loads of the decode kernels, per matrix: bit 0 QKV, 1 out-projection, 2 FFN-up, 3 FFN-down, 4 heads-1, 5 heads-2.
   // Option "nt" (VC_NT).  Until round 4 the compiled QKV / out-projection / heads-2 kernels carried NO such load whatever this said (the
   // compiler merged the kernel's two load arms and dropped the hint): 28 reproduces that mix, 63 = every matrix (default), 0 = none.
@@ -180,6 +185,9 @@ struct vc_engine {
   double *ce_sum = nullptr;
   long long *ce_hits = nullptr, *ce_cnt = nullptr;
 };
+
+#define VC_ADM_STAGES 4
+static_assert(sizeof(vc_request_ctl) == 16, "vc_request_ctl is copied as one 16-byte quad (vc_tokens.hip session_turn_k)");
 
 namespace {
 
@@ -831,6 +839,7 @@ int push_sample_dyn(vc_engine* e, const vc_sample_cfg* sc, const int64_t* forced
   d.n_group = n_group;                                    // samples per best-of-N group (advance_phase's keep decision)
   d.dbg_ts = getenv("VC_SAMPLER_TS") ? e->dbg_ts : nullptr;
   d.seed_tab = e->seed_tab; d.retire_rec = e->h_rec; d.batch_id = e->batch_id; d.row_base = e->row_base; d.adm_slot = e->adm_slot;   // (sessions only)
+  d.ctl_tab = e->ctl_tab;
   HIPCHK(e, hipMemcpyAsync(e->d_dyn, e->h_dyn, sizeof(SampleDyn), hipMemcpyHostToDevice, s));
   return VC_OK;
 }
@@ -1213,6 +1222,8 @@ extern "C" void vc_destroy(vc_engine* e) {
   drop_tts_stream(e);
   drop_session(e);
   if (e->h_rec) (void)hipHostFree(e->h_rec);
+  if (e->h_adm_st) (void)hipHostFree(e->h_adm_st);
+  if (e->h_adm_ctl) (void)hipHostFree(e->h_adm_ctl);
   delete e;
 }
 
@@ -1452,6 +1463,14 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
   if ((rc = dalloc(e, &e->adm_slot, (size_t)e->NS))) return rc;
   if ((rc = dalloc(e, &e->prompt_err, (size_t)e->NS))) return rc;
   if ((rc = dalloc(e, &e->sess_gather, (size_t)e->NS))) return rc;
+  if ((rc = dalloc(e, &e->ctl_tab, (size_t)e->NS))) return rc;
+  if ((rc = dalloc(e, &e->adm_ctl, (size_t)e->NS))) return rc;
+  if ((rc = dalloc(e, &e->adm_st, (size_t)e->NS))) return rc;
+  HIPCHK(e, hipMemset(e->ctl_tab, 0, sizeof(vc_request_ctl) * e->NS));
+  HIPCHK(e, hipMemset(e->adm_ctl, 0, sizeof(vc_request_ctl) * e->NS));
+  HIPCHK(e, hipMemset(e->adm_st, 0, sizeof(SeqState) * e->NS));
+  HIPCHK(e, hipHostMalloc((void**)&e->h_adm_st, sizeof(SeqState) * e->NS * VC_ADM_STAGES));
+  HIPCHK(e, hipHostMalloc((void**)&e->h_adm_ctl, sizeof(vc_request_ctl) * e->NS * VC_ADM_STAGES));
   HIPCHK(e, hipMemset(e->seed_tab, 0, sizeof(uint64_t) * e->NS));
   HIPCHK(e, hipMemset(e->batch_id, 0, 16));
   HIPCHK(e, hipMemset(e->row_base, 0, 16));
@@ -1827,382 +1846,7 @@ extern "C" int vc_tts_stream_end(vc_engine* e, int64_t* res_dev, int res_cap, in
   return rc;
 }
 
-// ------------------------------------------------------------------------------------- decode sessions (continuous batching)
-// A session keeps the decode loop open and takes TTS requests at any time (vc_session_submit).  One TURN (vc_session_advance) is one
-// iteration of DecodeLoop::advance with the way in added:
-//   1. wait for the older of the two graph batches in flight;
-//   2. count the retirements stamped with a batch the host has now seen END (the sampler writes one pinned record per slot, stamped
-//      with the batch index session_turn_k laid down in front of that batch);
-//   3. admit from the FIFO into the free slots, in order, as many as fit;
-//   4. queue, on the decode stream: the prompts and ONE prefill of the admitted requests into their K/V slots, session_turn_k (stamp of the
-//      next batch; re-pack of the live rows onto the width now needed, narrower or wider; the admitted requests' initial states behind
-//      them; fillers; n_active raised), the first sample of the admitted rows alone, and the next batch of graph_steps steps.
-// What the host decides - who is admitted when, every width - depends only on the submissions, the turn each was made at and records
-// of batches that have ended: never on how far the device runs ahead.  The same schedule therefore gives the same tokens in bf16 too.
-// Width in force: the next power of two >= live sequences, capped by `top` (that power for max_live where the per-row buffers hold it,
-// else max_live itself, as a blocking call of max_live sequences starts at its own count).
-struct SessReq {
-  TtsJob job{};
-  uint64_t seed = 0;
-  int slot = -1;
-  int state = 0;            // 0 pending, 1 live, 2 finished
-  int total_steps = 0, span = 0, span_steps0 = 0, prompt_err = 0;
-};
-struct Session {
-  DecodeLoop L{};
-  hipStream_t s = nullptr;
-  vc_sample_cfg sc{};
-  int max_live = 0, top = 0;
-  int B = 0;                // rows of the step in force (0: nothing laid out yet)
-  int live = 0;             // admitted and not yet KNOWN to have retired
-  int batch = 0;            // index of the next graph batch (never reset: the retirement stamps are unique for the session's life)
-  int run_start = 0;        // first batch queued since the session was last idle: only batches from there on can be in flight
-  int next_ticket = 1;
-  std::deque<int> fifo;
-  std::map<int, SessReq> reqs;
-  std::vector<int> slot_ticket;      // [max_live] ticket holding the slot (live, or finished and not yet fetched), -1 = free
-  long long stats[8]{};
-  // decode-stream time of each admission (prefill + session_turn_k + first sample): event pairs, read once their batch has ended
-  hipEvent_t ev_adm[4][2]{};
-  int ev_turn[4]{-1, -1, -1, -1};
-  double adm_ms = 0;
-  // a turn whose queued work failed after requests had been admitted on the host: the device and the tables no longer agree, so every
-  // later submit / advance / fetch returns this error and the caller closes the session
-  bool broken = false;
-  std::string broken_msg;
-};
-namespace {
-int session_broken(vc_engine* e, const Session& t) {
-  return fail(e, VC_ESTATE, "the decode session failed in an earlier turn (%s): close it (vc_session_close)", t.broken_msg.c_str());
-}
-void drop_session(vc_engine* e) {
-  if (!e->sess) return;
-  for (auto& pr : e->sess->ev_adm)
-    for (auto& ev : pr) if (ev) (void)hipEventDestroy(ev);
-  delete e->sess;
-  e->sess = nullptr;
-}
-
-int session_width(const Session& t, int live) { return std::min(DecodeLoop::width_for(std::max(1, live)), t.top); }
-
-// the admission timings whose batch the host has seen end (all of them when `all`: the stream was synchronised)
-void session_read_timers(Session& t, int known, bool all) {
-  for (int i = 0; i < 4; ++i) {
-    if (t.ev_turn[i] < 0 || (!all && t.ev_turn[i] > known)) continue;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, t.ev_adm[i][0], t.ev_adm[i][1]) == hipSuccess) t.adm_ms += ms;
-    t.ev_turn[i] = -1;
-  }
-}
-
-// retirements stamped with a batch <= known (stamps are batch + 1 in the record)
-void session_note_retired(vc_engine* e, Session& t, int known, int* tickets_out, int cap, int* n_fin) {
-  for (int slot = 0; slot < t.max_live; ++slot) {
-    const int ticket = t.slot_ticket[slot];
-    if (ticket < 0) continue;
-    SessReq& r = t.reqs[ticket];
-    if (r.state != 1) continue;
-    volatile int* rec = e->h_rec + slot * VC_SESS_REC;
-    const int stamp = rec[0];
-    if (stamp == 0 || stamp - 1 > known) continue;
-    if (*n_fin >= cap) continue;                        // no room to report it: it stays live on the host and is reported by a later turn
-    r.state = 2;
-    r.total_steps = rec[1]; r.span = rec[2]; r.span_steps0 = rec[3]; r.prompt_err = rec[4];
-    t.live -= 1;
-    t.stats[5] += std::max(0, r.total_steps - 1);      // rows of launched steps that were live: every step of the request but its first sample
-    tickets_out[*n_fin] = ticket;
-    *n_fin += 1;
-  }
-}
-}  // namespace
-
-extern "C" int vc_session_open(vc_engine* e, int max_live, const vc_sample_cfg* sc, void* stream) {
-  int rc = check_idle(e);
-  if (rc) return rc;
-  if (!sc) return fail(e, VC_EINVAL, "null argument to vc_session_open");
-  if (max_live < 1 || max_live > e->B_max) return fail(e, VC_EINVAL, "vc_session_open: max_live %d outside [1, max_seqs = %d]", max_live, e->B_max);
-  hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
-  Session* t = new Session();
-  t->s = s; t->sc = *sc; t->max_live = max_live;
-  t->top = DecodeLoop::width_for(max_live) <= e->NS ? DecodeLoop::width_for(max_live) : max_live;
-  t->slot_ticket.assign(max_live, -1);
-  auto bail = [&](int code) { e->sess = t; drop_session(e); return code; };
-  for (auto& pr : t->ev_adm)
-    for (auto& ev : pr)
-      if (hipEventCreate(&ev) != hipSuccess) return bail(fail(e, VC_EHIP, "hipEventCreate failed"));
-  // the sampling controls are the session's (one SampleDyn, as per call today); the seed is per request (SampleDyn.seed_tab)
-  if ((rc = push_sample_dyn(e, sc, nullptr, 0, nullptr, 0, max_live, s))) return bail(rc);
-  memset(e->h_rec, 0, sizeof(int) * VC_SESS_REC * e->NS);
-  e->h_flag[1] = 0; e->h_flag[8] = 0; e->h_flag[9] = 0; e->h_flag[10] = 0;
-  hipError_t he = hipMemsetAsync(e->n_active, 0, sizeof(int), s);
-  if (he == hipSuccess) he = hipMemsetAsync(e->step_ctr, 0, sizeof(int), s);
-  if (he == hipSuccess) he = hipMemsetAsync(e->batch_id, 0, sizeof(int), s);
-  if (he == hipSuccess) he = hipMemsetAsync(e->prompt_err, 0, sizeof(int) * e->NS, s);
-  if (he == hipSuccess) he = hipStreamSynchronize(s);       // (orders the reuse of the pinned sampler block, as check_err_flag does in a call)
-  if (he != hipSuccess) return bail(fail(e, VC_EHIP, "vc_session_open: %s", hipGetErrorString(he)));
-  e->repack_at.clear();
-  // every graph the session can pass through, ahead of any timer: the powers of two below `top`, and `top`
-  t->L.init(e, make_sample_args(e, t->top, 1), t->top, 1, 0, sc, 0, s);
-  t->L.sess = true;
-  e->host_ms[1] = e->host_ms[2] = 0;
-  if (sc->use_graph) {
-    hipGraphExec_t exec = nullptr;
-    for (int w = t->top; w >= 1 && rc == VC_OK; w = (w == t->top) ? DecodeLoop::width_for(w) / 2 : w / 2) {
-      t->L.B = w; t->L.sa = make_sample_args(e, w, 1);
-      rc = t->L.exec_for(&exec);
-    }
-    if (rc) return bail(rc);
-  }
-  e->sess = t;
-  return VC_OK;
-}
-
-extern "C" int vc_session_submit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T, uint64_t seed, int* ticket) {
-  if (!e) return VC_EINVAL;
-  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
-  if (e->sess->broken) return session_broken(e, *e->sess);
-  if (!x_dev || (!y_dev && T > 0) || !ticket) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_submit");
-  if (Lx < 1 || T < 0) return fail(e, VC_EINVAL, "empty text or negative prompt length");
-  const int n_cols = T + 1;
-  if (e->S_max - (Lx + n_cols) - 1 < e->K + 1)
-    return fail(e, VC_ECAP, "the prompt alone takes %d of max_positions %d", Lx + n_cols, e->S_max);
-  if (((Lx + n_cols + 63) & ~63) > e->emb_cap)
-    return fail(e, VC_ECAP, "a prompt of %d rows does not fit the prefill arena of %d rows", Lx + n_cols, e->emb_cap);
-  Session& t = *e->sess;
-  SessReq r;
-  r.job = TtsJob{x_dev, Lx, y_dev, T};
-  r.seed = seed;
-  const int id = t.next_ticket++;
-  t.reqs[id] = r;
-  t.fifo.push_back(id);
-  *ticket = id;
-  return VC_OK;
-}
-
-extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* n_finished, int* idle) {
-  if (!e) return VC_EINVAL;
-  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
-  if (!n_finished || !idle || cap < 0 || (cap > 0 && !tickets_out)) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_advance");
-  HIPCHK(e, hipSetDevice(e->device));
-  Session& t = *e->sess;
-  if (t.broken) return session_broken(e, t);
-  hipStream_t s = t.s;
-  const int G = t.L.G;
-  *n_finished = 0; *idle = 0;
-  t.stats[2] += 1;
-  // ---- 1, 2: the older batch in flight, and what it (or an earlier one) retired
-  int known = t.run_start - 1;
-  if (t.batch - t.run_start >= 2) {
-    HIPCHK(e, hipEventSynchronize(e->ev_pace[t.batch & 1]));
-    known = t.batch - 2;
-  }
-  session_note_retired(e, t, known, tickets_out, cap, n_finished);
-  session_read_timers(t, known, false);
-  // ---- 3: admission, FIFO, as many as have a free slot
-  SessTurnArgs ta;
-  memset(&ta, 0, sizeof ta);
-  std::vector<PromptArgs> pas;
-  std::vector<int> slots;
-  const int live_before = t.live;
-  for (int slot = 0; slot < t.max_live && !t.fifo.empty(); ++slot) {
-    if (t.slot_ticket[slot] >= 0) continue;
-    const int id = t.fifo.front();
-    t.fifo.pop_front();
-    SessReq& r = t.reqs[id];
-    r.slot = slot; r.state = 1;
-    t.slot_ticket[slot] = id;
-    const int j = ta.n_new++;
-    ta.slot[j] = slot; ta.Lx[j] = r.job.Lx; ta.n_cols[j] = r.job.T + 1; ta.seed[j] = r.seed;
-    PromptArgs pa;
-    fill_prompt_common(e, pa, r.job.x, r.job.Lx, r.job.y, r.job.T);
-    pa.n_seg = 1; pa.n_cols = r.job.T + 1;
-    pa.seg[0] = Segment{0, r.job.T + 1, 0, r.job.T, -1, -1};
-    pas.push_back(pa);
-    slots.push_back(slot);
-    volatile int* rec = e->h_rec + slot * VC_SESS_REC;      // the slot's record: empty until this request retires
-    for (int i = 0; i < VC_SESS_REC; ++i) rec[i] = 0;
-  }
-  const int n_new = ta.n_new;
-  if (t.live + n_new == 0) {
-    // nothing to decode: what is still queued is steps without a live sequence.  Wait for them and queue nothing more; a later
-    // submit (or the fetch that frees a slot for a pending request) restarts the loop.
-    if (t.batch > t.run_start) {
-      HIPCHK(e, hipStreamSynchronize(s));
-      session_note_retired(e, t, t.batch - 1, tickets_out, cap, n_finished);
-      session_read_timers(t, t.batch - 1, true);
-      t.run_start = t.batch;
-      if (int rc = check_err_flag(e, s)) return rc;        // (session_turn_k's row check; the stream is idle, so this costs nothing)
-    }
-    *idle = t.fifo.empty() ? 1 : 0;
-    return VC_OK;
-  }
-  // ---- 4: prefill of the admitted requests, the turn kernel, their first sample, the next batch.  The requests are admitted on the
-  // host already: if anything below fails the session is marked broken (see Session.broken)
-  const int rc4 = [&]() -> int {
-  const int w = session_width(t, t.live + n_new);
-  const int ei = t.batch & 3;
-  if (n_new > 0) {
-    HIPCHK(e, hipEventRecord(t.ev_adm[ei][0], s));
-    int rc = prefill_batch(e, pas, slots, s, true);
-    if (rc) return rc;
-  }
-  ta.st = e->st; ta.dec_h = e->dec_h; ta.row_seq = e->dec_row_seq; ta.row_pos = e->dec_row_pos; ta.logit_row = e->logit_row;
-  ta.err = e->err_flag; ta.n_active = e->n_active; ta.batch_id = e->batch_id; ta.row_base = e->row_base; ta.adm_slot = e->adm_slot;
-  ta.seed_tab = e->seed_tab; ta.prompt_err = e->prompt_err; ta.retire_rec = e->h_rec;
-  ta.B_old = t.B; ta.B_new = w; ta.d = e->d; ta.batch = t.batch; ta.repack = (n_new > 0 || w != t.B) ? 1 : 0;
-  {
-    const SeqState st0 = init_state(e, 1, 0, true, 1);      // (cap_len of Lx = 1 is the multiplier)
-    ta.cap_mult = st0.cap_len; ta.min_gen = st0.min_gen; ta.term_token = st0.term_token; ta.kill_token = st0.kill_token;
-  }
-  HIPCHK(e, vc_launch_session_turn(ta, s));
-  if (t.B > 0 && w > t.B) t.stats[3] += 1;
-  if (w < t.B) t.stats[4] += 1;
-  t.B = w;
-  t.L.B = w; t.L.sa = make_sample_args(e, w, 1);
-  if (n_new > 0) {
-    HIPCHK(e, vc_launch_sample_session(t.L.sa, true, n_new, s));
-    HIPCHK(e, hipEventRecord(t.ev_adm[ei][1], s));
-    t.ev_turn[ei] = t.batch;
-    t.stats[0] += n_new;
-    if (live_before > 0) t.stats[1] += n_new;
-    t.live += n_new;
-  }
-  int rc = VC_OK;
-  if (t.sc.use_graph) {
-    hipGraphExec_t exec = nullptr;
-    if ((rc = t.L.exec_for(&exec))) return rc;
-    HIPCHK(e, hipGraphLaunch(exec, s));
-  } else {
-    for (int i = 0; i < G && rc == VC_OK; ++i) rc = decode_step(e, t.L.sa, w, 1, false, s, true);
-    if (rc) return rc;
-  }
-  HIPCHK(e, hipEventRecord(e->ev_pace[t.batch & 1], s));
-  t.batch += 1;
-  t.stats[6] += (long long)w * G;
-  return VC_OK;
-  }();
-  if (rc4) { t.broken = true; t.broken_msg = e->err; }
-  return rc4;
-}
-
-extern "C" int vc_session_fetch(vc_engine* e, int ticket, int64_t* res_dev, int res_cap, int* gen_len, int* n_steps) {
-  if (!e) return VC_EINVAL;
-  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
-  Session& t = *e->sess;
-  auto it = t.reqs.find(ticket);
-  if (it == t.reqs.end()) return fail(e, VC_EINVAL, "vc_session_fetch: unknown ticket %d (never issued, or fetched already)", ticket);
-  if (it->second.state != 2) {
-    if (t.broken) return session_broken(e, t);
-    return fail(e, VC_ESTATE, "vc_session_fetch: the request of ticket %d has not finished", ticket);
-  }
-  HIPCHK(e, hipSetDevice(e->device));
-  const SessReq r = it->second;
-  // whatever the outcome the ticket is spent: the slot (its K/V rows, its rows of the generated-token log) is free for the next request
-  t.slot_ticket[r.slot] = -1;
-  t.reqs.erase(it);
-  if (!res_dev) return VC_OK;                               // dropped
-  if (!gen_len || res_cap < 0) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_fetch");
-  if (r.prompt_err & 1)
-    return fail(e, VC_EINVAL, "ticket %d: token id out of range in x or y (text rows %d, audio vocab %d)", ticket, e->cfg.text_rows, e->V);
-  SeqState st;
-  memset(&st, 0, sizeof st);
-  st.done = 1; st.span = r.span; st.span_steps[0] = r.span_steps0; st.total_steps = r.total_steps;
-  // on the side stream: the request's rows of the log are final (its batch has ended), and the decode stream's queued batches are not waited for
-  int rc = assemble_tts(e, r.job, r.slot, st, res_dev, res_cap, gen_len, e->side_stream);
-  if (rc) return rc;
-  HIPCHK(e, hipStreamSynchronize(e->side_stream));
-  if (n_steps) *n_steps = r.total_steps;
-  return VC_OK;
-}
-
-extern "C" int vc_session_stats(vc_engine* e, int64_t out[8]) {
-  if (!e) return VC_EINVAL;
-  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
-  if (!out) return fail(e, VC_EINVAL, "null argument to vc_session_stats");
-  const Session& t = *e->sess;
-  for (int i = 0; i < 7; ++i) out[i] = t.stats[i];
-  out[7] = (int64_t)(t.adm_ms * 1000.0);                    // microseconds of decode-stream time spent on admissions whose batch has ended
-  return VC_OK;
-}
-
-extern "C" int vc_session_close(vc_engine* e) {
-  if (!e) return VC_EINVAL;
-  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
-  HIPCHK(e, hipSetDevice(e->device));
-  Session& t = *e->sess;
-  int rc = VC_OK;
-  // wait for what is queued; the next call uploads every state afresh (vc_tts_stream_end with res_dev = NULL is the model)
-  hipError_t he = hipMemsetAsync(e->n_active, 0, sizeof(int), t.s);
-  if (he == hipSuccess) he = hipStreamSynchronize(t.s);
-  if (he != hipSuccess) rc = fail(e, VC_EHIP, "vc_session_close: %s", hipGetErrorString(he));
-  else rc = check_err_flag(e, t.s);                         // (reads and clears the flag word)
-  e->cur_rows = 0;
-  drop_session(e);
-  return rc;
-}
-
-extern "C" int vc_tts(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
-                      const vc_sample_cfg* sc, int n_samples, const int64_t* forced_dev, int n_forced,
-                      int64_t* res_dev, int res_cap, int* gen_len, float* logits_dev, int logit_steps,
-                      int* n_steps, void* stream) {
-  int rc = check_idle(e);
-  if (rc) return rc;
-  if (!x_dev || (!y_dev && T > 0) || !sc || !res_dev || !gen_len || n_samples < 1)
-    return fail(e, VC_EINVAL, "null/invalid argument to vc_tts");
-  hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
-  std::vector<TtsJob> jobs{TtsJob{x_dev, Lx, y_dev, T}};
-  rc = tts_run(e, jobs, n_samples, sc, forced_dev, n_forced, logits_dev, logit_steps, n_steps, s);
-  if (rc) return rc;
-  int slot = 0;
-  if (n_samples > 1) {
-    slot = kept_sample(e, 0, n_samples);
-    if (slot < 0) return fail(e, VC_ECAP, "no sample terminated within the step budget");
-  }
-  rc = assemble_tts(e, jobs[0], slot, res_dev, res_cap, gen_len, s);
-  if (rc) return rc;
-  HIPCHK(e, hipStreamSynchronize(s));
-  return VC_OK;
-}
-
-extern "C" int vc_tts_multi_best_of(vc_engine* e, int B, int n_samples, const int64_t* x_dev, const int32_t* x_off,
-                                    const int64_t* y_dev, const int32_t* y_off, const vc_sample_cfg* sc, int shared_text_prefix,
-                                    const int64_t* forced_dev, int n_forced, int64_t* res_dev, int res_cap, int* gen_len,
-                                    int* kept, float* logits_dev, int logit_steps, int* n_steps, void* stream) {
-  int rc = check_idle(e);
-  if (rc) return rc;
-  if (B < 1 || n_samples < 1 || !x_dev || !x_off || !y_dev || !y_off || !sc || !res_dev || !gen_len)
-    return fail(e, VC_EINVAL, "null/invalid argument to vc_tts_multi (B %d, n_samples %d)", B, n_samples);
-  for (int b = 0; b < B; ++b)
-    if (shared_text_prefix < 0 || shared_text_prefix >= x_off[b + 1] - x_off[b])
-      return fail(e, VC_EINVAL, "shared_text_prefix %d must be shorter than every text (sequence %d has %d tokens)",
-                  shared_text_prefix, b, x_off[b + 1] - x_off[b]);
-  hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
-  std::vector<TtsJob> jobs;
-  for (int b = 0; b < B; ++b)
-    jobs.push_back(TtsJob{x_dev + x_off[b], x_off[b + 1] - x_off[b], y_dev + (size_t)y_off[b] * e->K, y_off[b + 1] - y_off[b]});
-  rc = tts_run(e, jobs, n_samples, sc, forced_dev, n_forced, logits_dev, logit_steps, n_steps, s, B > 1 ? shared_text_prefix : 0);
-  if (rc) return rc;
-  for (int b = 0; b < B; ++b) {
-    const int j = n_samples > 1 ? kept_sample(e, b, n_samples) : 0;
-    if (j < 0) return fail(e, VC_ECAP, "utterance %d: no sample terminated within the step budget", b);
-    if (kept) kept[b] = j;
-    rc = assemble_tts(e, jobs[b], b * n_samples + j, res_dev + (size_t)b * e->K * res_cap, res_cap, &gen_len[b], s);
-    if (rc) return rc;
-  }
-  HIPCHK(e, hipStreamSynchronize(s));
-  return VC_OK;
-}
-
-extern "C" int vc_tts_multi(vc_engine* e, int B, const int64_t* x_dev, const int32_t* x_off,
-                            const int64_t* y_dev, const int32_t* y_off, const vc_sample_cfg* sc,
-                            int shared_text_prefix,
-                            const int64_t* forced_dev, int n_forced, int64_t* res_dev, int res_cap, int* gen_len,
-                            float* logits_dev, int logit_steps, int* n_steps, void* stream) {
-  return vc_tts_multi_best_of(e, B, 1, x_dev, x_off, y_dev, y_off, sc, shared_text_prefix, forced_dev, n_forced, res_dev, res_cap,
-                              gen_len, nullptr, logits_dev, logit_steps, n_steps, stream);
-}
-
-// ------------------------------------------------------------------------------------- editing
+// ------------------------------------------------------------------------------------- editing: the parts shared by vc_edit, vc_edit_multi and the decode sessions
 namespace {
 
 // One editing request: its inputs, the prefill's segment table (PromptArgs) and its budget of sampled steps.
@@ -2304,6 +1948,472 @@ int edit_assemble(vc_engine* e, const EditJob& j, const SeqState& fs, const int*
 
 }  // namespace
 
+// ------------------------------------------------------------------------------------- decode sessions (continuous batching)
+// A session keeps the decode loop open and takes TTS and editing requests at any time (vc_session_submit / _submit_ctl / _submit_edit).
+// One TURN (vc_session_advance) is one iteration of DecodeLoop::advance with the way in added:
+//   1. wait for the older of the two graph batches in flight;
+//   2. count the retirements stamped with a batch the host has now seen END (the sampler writes one pinned record per slot, stamped
+//      with the batch index session_turn_k laid down in front of that batch);
+//   3. admit from the FIFO into the free slots, in order, as many as fit;
+//   4. queue, on the decode stream: the prompts and ONE prefill of the admitted requests into their K/V slots, session_turn_k (stamp of the
+//      next batch; re-pack of the live rows onto the width now needed, narrower or wider; the admitted requests' initial states behind
+//      them; fillers; n_active raised), the first sample of the admitted rows alone, and the next batch of graph_steps steps.
+//      The admitted requests' first states (init_state of a TTS request; edit_state with feed_switch of an editing request - one row
+//      per request, its span switches fed over three steps as in vc_edit_multi) and their sampling controls are written into pinned
+//      staging buffer (batch % VC_ADM_STAGES) and uploaded on the decode stream in front of session_turn_k.  That buffer is written again
+//      VC_ADM_STAGES turns later at the earliest; a turn queues only after the batch two turns back has ENDED (step 1), and a batch ends
+//      behind its turn's upload on the same stream, so no queued upload can still have to read a buffer the host is writing.
+// What the host decides - who is admitted when, every width - depends only on the submissions, the turn each was made at and records
+// of batches that have ended: never on how far the device runs ahead.  The same schedule therefore gives the same tokens in bf16 too.
+// Width in force: the next power of two >= live sequences, capped by `top` (that power for max_live where the per-row buffers hold it,
+// else max_live itself, as a blocking call of max_live sequences starts at its own count).
+struct SessReq {
+  int kind = 0;             // 0 TTS (job), 1 editing (edit)
+  TtsJob job{};
+  EditJob edit{};           // its iv / mv point into iv_own / mv_own (re-pointed wherever a SessReq is copied)
+  std::vector<int32_t> iv_own, mv_own;
+  vc_request_ctl ctl{};     // the request's sampling controls (the session's when it gave none)
+  uint64_t seed = 0;
+  int slot = -1;
+  int state = 0;            // 0 pending, 1 live, 2 finished
+  int total_steps = 0, span = 0, prompt_err = 0, fed = 0;
+  int span_steps[VC_MAX_SPANS]{};
+};
+struct Session {
+  DecodeLoop L{};
+  hipStream_t s = nullptr;
+  vc_sample_cfg sc{};
+  int max_live = 0, top = 0;
+  int B = 0;                // rows of the step in force (0: nothing laid out yet)
+  int live = 0;             // admitted and not yet KNOWN to have retired
+  int batch = 0;            // index of the next graph batch (never reset: the retirement stamps are unique for the session's life)
+  int run_start = 0;        // first batch queued since the session was last idle: only batches from there on can be in flight
+  int next_ticket = 1;
+  std::deque<int> fifo;
+  std::map<int, SessReq> reqs;
+  std::vector<int> slot_ticket;      // [max_live] ticket holding the slot (live, or finished and not yet fetched), -1 = free
+  long long stats[8]{};
+  // decode-stream time of each admission (prefill + session_turn_k + first sample): event pairs, read once their batch has ended
+  hipEvent_t ev_adm[4][2]{};
+  int ev_turn[4]{-1, -1, -1, -1};
+  double adm_ms = 0;
+  // a turn whose queued work failed after requests had been admitted on the host: the device and the tables no longer agree, so every
+  // later submit / advance / fetch returns this error and the caller closes the session
+  bool broken = false;
+  std::string broken_msg;
+};
+namespace {
+int session_broken(vc_engine* e, const Session& t) {
+  return fail(e, VC_ESTATE, "the decode session failed in an earlier turn (%s): close it (vc_session_close)", t.broken_msg.c_str());
+}
+void drop_session(vc_engine* e) {
+  if (!e->sess) return;
+  for (auto& pr : e->sess->ev_adm)
+    for (auto& ev : pr) if (ev) (void)hipEventDestroy(ev);
+  delete e->sess;
+  e->sess = nullptr;
+}
+
+int session_width(const Session& t, int live) { return std::min(DecodeLoop::width_for(std::max(1, live)), t.top); }
+
+// the admission timings whose batch the host has seen end (all of them when `all`: the stream was synchronised)
+void session_read_timers(Session& t, int known, bool all) {
+  for (int i = 0; i < 4; ++i) {
+    if (t.ev_turn[i] < 0 || (!all && t.ev_turn[i] > known)) continue;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, t.ev_adm[i][0], t.ev_adm[i][1]) == hipSuccess) t.adm_ms += ms;
+    t.ev_turn[i] = -1;
+  }
+}
+
+// retirements stamped with a batch <= known (stamps are batch + 1 in the record)
+void session_note_retired(vc_engine* e, Session& t, int known, int* tickets_out, int cap, int* n_fin) {
+  for (int slot = 0; slot < t.max_live; ++slot) {
+    const int ticket = t.slot_ticket[slot];
+    if (ticket < 0) continue;
+    SessReq& r = t.reqs[ticket];
+    if (r.state != 1) continue;
+    volatile int* rec = e->h_rec + slot * VC_SESS_REC;
+    const int stamp = rec[0];
+    if (stamp == 0 || stamp - 1 > known) continue;
+    if (*n_fin >= cap) continue;                        // no room to report it: it stays live on the host and is reported by a later turn
+    r.state = 2;
+    r.total_steps = rec[1]; r.span = rec[2]; r.prompt_err = rec[4]; r.fed = rec[5];
+    for (int i = 0; i < VC_MAX_SPANS; ++i) r.span_steps[i] = rec[VC_SESS_REC_SPANS + i];
+    t.live -= 1;
+    // rows of launched steps that were live: every step of the request but its first sample, and the rows an edit fed at its span switches
+    t.stats[5] += std::max(0, r.total_steps - 1) + std::max(0, r.fed);
+    tickets_out[*n_fin] = ticket;
+    *n_fin += 1;
+  }
+}
+}  // namespace
+
+extern "C" int vc_session_open(vc_engine* e, int max_live, const vc_sample_cfg* sc, void* stream) {
+  int rc = check_idle(e);
+  if (rc) return rc;
+  if (!sc) return fail(e, VC_EINVAL, "null argument to vc_session_open");
+  if (max_live < 1 || max_live > e->B_max) return fail(e, VC_EINVAL, "vc_session_open: max_live %d outside [1, max_seqs = %d]", max_live, e->B_max);
+  hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+  Session* t = new Session();
+  t->s = s; t->sc = *sc; t->max_live = max_live;
+  t->top = DecodeLoop::width_for(max_live) <= e->NS ? DecodeLoop::width_for(max_live) : max_live;
+  t->slot_ticket.assign(max_live, -1);
+  auto bail = [&](int code) { e->sess = t; drop_session(e); return code; };
+  for (auto& pr : t->ev_adm)
+    for (auto& ev : pr)
+      if (hipEventCreate(&ev) != hipSuccess) return bail(fail(e, VC_EHIP, "hipEventCreate failed"));
+  // silence tokens and the graph switch are the session's (one SampleDyn); the seed and the sampling controls are per request
+  // (SampleDyn.seed_tab / ctl_tab by slot), the controls given here being the default of a request that brings none
+  if ((rc = push_sample_dyn(e, sc, nullptr, 0, nullptr, 0, max_live, s))) return bail(rc);
+  memset(e->h_rec, 0, sizeof(int) * VC_SESS_REC * e->NS);
+  e->h_flag[1] = 0; e->h_flag[8] = 0; e->h_flag[9] = 0; e->h_flag[10] = 0;
+  hipError_t he = hipMemsetAsync(e->n_active, 0, sizeof(int), s);
+  if (he == hipSuccess) he = hipMemsetAsync(e->step_ctr, 0, sizeof(int), s);
+  if (he == hipSuccess) he = hipMemsetAsync(e->batch_id, 0, sizeof(int), s);
+  if (he == hipSuccess) he = hipMemsetAsync(e->prompt_err, 0, sizeof(int) * e->NS, s);
+  if (he == hipSuccess) he = hipStreamSynchronize(s);       // (orders the reuse of the pinned sampler block, as check_err_flag does in a call)
+  if (he != hipSuccess) return bail(fail(e, VC_EHIP, "vc_session_open: %s", hipGetErrorString(he)));
+  e->repack_at.clear();
+  // every graph the session can pass through, ahead of any timer: the powers of two below `top`, and `top`
+  t->L.init(e, make_sample_args(e, t->top, 1), t->top, 1, 0, sc, 0, s);
+  t->L.sess = true;
+  e->host_ms[1] = e->host_ms[2] = 0;
+  if (sc->use_graph) {
+    hipGraphExec_t exec = nullptr;
+    for (int w = t->top; w >= 1 && rc == VC_OK; w = (w == t->top) ? DecodeLoop::width_for(w) / 2 : w / 2) {
+      t->L.B = w; t->L.sa = make_sample_args(e, w, 1);
+      rc = t->L.exec_for(&exec);
+    }
+    if (rc) return bail(rc);
+  }
+  e->sess = t;
+  return VC_OK;
+}
+
+namespace {
+// the checks every submit starts with; *t_out = the open, unbroken session
+int session_for_submit(vc_engine* e, Session** t_out) {
+  if (!e) return VC_EINVAL;
+  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
+  if (e->sess->broken) return session_broken(e, *e->sess);
+  *t_out = e->sess;
+  return VC_OK;
+}
+// a request's sampling controls: its own, checked, or the session's
+int session_ctl(vc_engine* e, const Session& t, const vc_request_ctl* ctl, vc_request_ctl* out) {
+  if (!ctl) {
+    *out = vc_request_ctl{t.sc.top_k, t.sc.top_p, t.sc.temperature, t.sc.stop_repetition};
+    return VC_OK;
+  }
+  if (!(ctl->temperature > 0.f && ctl->temperature <= 3.0e38f))
+    return fail(e, VC_EINVAL, "request controls: temperature %g must be a finite positive number", (double)ctl->temperature);
+  if (ctl->top_p != ctl->top_p) return fail(e, VC_EINVAL, "request controls: top_p is not a number");
+  *out = *ctl;
+  return VC_OK;
+}
+int session_enqueue(Session& t, SessReq&& r, int* ticket) {
+  const int id = t.next_ticket++;
+  SessReq& q = t.reqs[id];
+  q = std::move(r);
+  q.edit.iv = q.iv_own.data(); q.edit.mv = q.mv_own.data();
+  t.fifo.push_back(id);
+  *ticket = id;
+  return VC_OK;
+}
+}  // namespace
+
+extern "C" int vc_session_submit_ctl(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
+                                     const vc_request_ctl* ctl, uint64_t seed, int* ticket) {
+  Session* tp = nullptr;
+  if (int rc = session_for_submit(e, &tp)) return rc;
+  if (!x_dev || (!y_dev && T > 0) || !ticket) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_submit");
+  if (Lx < 1 || T < 0) return fail(e, VC_EINVAL, "empty text or negative prompt length");
+  const int n_cols = T + 1;
+  if (e->S_max - (Lx + n_cols) - 1 < e->K + 1)
+    return fail(e, VC_ECAP, "the prompt alone takes %d of max_positions %d", Lx + n_cols, e->S_max);
+  if (((Lx + n_cols + 63) & ~63) > e->emb_cap)
+    return fail(e, VC_ECAP, "a prompt of %d rows does not fit the prefill arena of %d rows", Lx + n_cols, e->emb_cap);
+  SessReq r;
+  if (int rc = session_ctl(e, *tp, ctl, &r.ctl)) return rc;
+  r.kind = 0;
+  r.job = TtsJob{x_dev, Lx, y_dev, T};
+  r.seed = seed;
+  return session_enqueue(*tp, std::move(r), ticket);
+}
+
+extern "C" int vc_session_submit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T, uint64_t seed, int* ticket) {
+  return vc_session_submit_ctl(e, x_dev, Lx, y_dev, T, nullptr, seed, ticket);
+}
+
+extern "C" int vc_session_submit_edit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
+                                      const int32_t* mask_intervals, int M, const int32_t* mask_values,
+                                      const vc_request_ctl* ctl, uint64_t seed, int* ticket) {
+  Session* tp = nullptr;
+  if (int rc = session_for_submit(e, &tp)) return rc;
+  if (!x_dev || !y_dev || !mask_intervals || !mask_values || !ticket) return fail(e, VC_EINVAL, "null argument to vc_session_submit_edit");
+  SessReq r;
+  if (int rc = session_ctl(e, *tp, ctl, &r.ctl)) return rc;
+  r.kind = 1;
+  // (edit_prepare refuses a span count outside [1, max_n_spans] before it reads either array: the copies only have to stay inside them)
+  const int Mc = std::max(0, std::min(M, VC_MAX_SPANS));
+  r.iv_own.assign(mask_intervals, mask_intervals + 2 * (size_t)Mc);
+  r.mv_own.assign(mask_values, mask_values + 2 * (size_t)Mc);
+  r.edit = EditJob{x_dev, Lx, y_dev, T, r.iv_own.data(), M, r.mv_own.data()};
+  if (int rc = edit_prepare(e, r.edit, "")) return rc;
+  const int rows = Lx + r.edit.pa.n_cols;
+  if (((rows + 63) & ~63) > e->emb_cap)
+    return fail(e, VC_ECAP, "a prompt of %d rows does not fit the prefill arena of %d rows", rows, e->emb_cap);
+  r.seed = seed;
+  return session_enqueue(*tp, std::move(r), ticket);
+}
+
+extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* n_finished, int* idle) {
+  if (!e) return VC_EINVAL;
+  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
+  if (!n_finished || !idle || cap < 0 || (cap > 0 && !tickets_out)) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_advance");
+  HIPCHK(e, hipSetDevice(e->device));
+  Session& t = *e->sess;
+  if (t.broken) return session_broken(e, t);
+  hipStream_t s = t.s;
+  const int G = t.L.G;
+  *n_finished = 0; *idle = 0;
+  t.stats[2] += 1;
+  // ---- 1, 2: the older batch in flight, and what it (or an earlier one) retired
+  int known = t.run_start - 1;
+  if (t.batch - t.run_start >= 2) {
+    HIPCHK(e, hipEventSynchronize(e->ev_pace[t.batch & 1]));
+    known = t.batch - 2;
+  }
+  session_note_retired(e, t, known, tickets_out, cap, n_finished);
+  session_read_timers(t, known, false);
+  // ---- 3: admission, FIFO, as many as have a free slot
+  SessTurnArgs ta;
+  memset(&ta, 0, sizeof ta);
+  // this turn's staging buffers (see the comment above Session: the host last wrote them VC_ADM_STAGES turns ago)
+  SeqState* const h_adm_st = e->h_adm_st + (size_t)(t.batch % VC_ADM_STAGES) * e->NS;
+  vc_request_ctl* const h_adm_ctl = e->h_adm_ctl + (size_t)(t.batch % VC_ADM_STAGES) * e->NS;
+  std::vector<PromptArgs> pas;
+  std::vector<int> slots;
+  const int live_before = t.live;
+  for (int slot = 0; slot < t.max_live && !t.fifo.empty(); ++slot) {
+    if (t.slot_ticket[slot] >= 0) continue;
+    const int id = t.fifo.front();
+    t.fifo.pop_front();
+    SessReq& r = t.reqs[id];
+    r.slot = slot; r.state = 1;
+    t.slot_ticket[slot] = id;
+    const int j = ta.n_new++;
+    ta.seed[j] = r.seed;
+    // the request's first state and its prompt, by kind: what tts_prepare / vc_edit_multi lay down for a sequence of a blocking call
+    SeqState& st = h_adm_st[j];
+    PromptArgs pa;
+    if (r.kind == 1) {
+      st = edit_state(e, r.edit);
+      st.feed_switch = 1;
+      pa = r.edit.pa;
+    } else {
+      st = init_state(e, r.job.Lx, r.job.T + 1, true, 1);
+      fill_prompt_common(e, pa, r.job.x, r.job.Lx, r.job.y, r.job.T);
+      pa.n_seg = 1; pa.n_cols = r.job.T + 1;
+      pa.seg[0] = Segment{0, r.job.T + 1, 0, r.job.T, -1, -1};
+    }
+    st.slot = slot;
+    h_adm_ctl[j] = r.ctl;
+    pas.push_back(pa);
+    slots.push_back(slot);
+    volatile int* rec = e->h_rec + slot * VC_SESS_REC;      // the slot's record: empty until this request retires
+    for (int i = 0; i < VC_SESS_REC; ++i) rec[i] = 0;
+  }
+  const int n_new = ta.n_new;
+  if (t.live + n_new == 0) {
+    // nothing to decode: what is still queued is steps without a live sequence.  Wait for them and queue nothing more; a later
+    // submit (or the fetch that frees a slot for a pending request) restarts the loop.
+    if (t.batch > t.run_start) {
+      HIPCHK(e, hipStreamSynchronize(s));
+      session_note_retired(e, t, t.batch - 1, tickets_out, cap, n_finished);
+      session_read_timers(t, t.batch - 1, true);
+      t.run_start = t.batch;
+      if (int rc = check_err_flag(e, s)) return rc;        // (session_turn_k's row check; the stream is idle, so this costs nothing)
+    }
+    *idle = t.fifo.empty() ? 1 : 0;
+    return VC_OK;
+  }
+  // ---- 4: prefill of the admitted requests, the turn kernel, their first sample, the next batch.  The requests are admitted on the
+  // host already: if anything below fails the session is marked broken (see Session.broken)
+  const int rc4 = [&]() -> int {
+  const int w = session_width(t, t.live + n_new);
+  const int ei = t.batch & 3;
+  if (n_new > 0) {
+    HIPCHK(e, hipEventRecord(t.ev_adm[ei][0], s));
+    int rc = prefill_batch(e, pas, slots, s, true);
+    if (rc) return rc;
+    HIPCHK(e, hipMemcpyAsync(e->adm_st, h_adm_st, sizeof(SeqState) * n_new, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->adm_ctl, h_adm_ctl, sizeof(vc_request_ctl) * n_new, hipMemcpyHostToDevice, s));
+  }
+  ta.st = e->st; ta.dec_h = e->dec_h; ta.row_seq = e->dec_row_seq; ta.row_pos = e->dec_row_pos; ta.logit_row = e->logit_row;
+  ta.err = e->err_flag; ta.n_active = e->n_active; ta.batch_id = e->batch_id; ta.row_base = e->row_base; ta.adm_slot = e->adm_slot;
+  ta.seed_tab = e->seed_tab; ta.prompt_err = e->prompt_err; ta.retire_rec = e->h_rec;
+  ta.ctl_tab = e->ctl_tab; ta.adm_st = e->adm_st; ta.adm_ctl = e->adm_ctl;
+  ta.B_old = t.B; ta.B_new = w; ta.d = e->d; ta.batch = t.batch; ta.repack = (n_new > 0 || w != t.B) ? 1 : 0;
+  HIPCHK(e, vc_launch_session_turn(ta, s));
+  if (t.B > 0 && w > t.B) t.stats[3] += 1;
+  if (w < t.B) t.stats[4] += 1;
+  t.B = w;
+  t.L.B = w; t.L.sa = make_sample_args(e, w, 1);
+  if (n_new > 0) {
+    HIPCHK(e, vc_launch_sample_session(t.L.sa, true, n_new, s));
+    HIPCHK(e, hipEventRecord(t.ev_adm[ei][1], s));
+    t.ev_turn[ei] = t.batch;
+    t.stats[0] += n_new;
+    if (live_before > 0) t.stats[1] += n_new;
+    t.live += n_new;
+  }
+  int rc = VC_OK;
+  if (t.sc.use_graph) {
+    hipGraphExec_t exec = nullptr;
+    if ((rc = t.L.exec_for(&exec))) return rc;
+    HIPCHK(e, hipGraphLaunch(exec, s));
+  } else {
+    for (int i = 0; i < G && rc == VC_OK; ++i) rc = decode_step(e, t.L.sa, w, 1, false, s, true);
+    if (rc) return rc;
+  }
+  HIPCHK(e, hipEventRecord(e->ev_pace[t.batch & 1], s));
+  t.batch += 1;
+  t.stats[6] += (long long)w * G;
+  return VC_OK;
+  }();
+  if (rc4) { t.broken = true; t.broken_msg = e->err; }
+  return rc4;
+}
+
+extern "C" int vc_session_fetch(vc_engine* e, int ticket, int64_t* res_dev, int res_cap, int* gen_len, int* n_steps) {
+  if (!e) return VC_EINVAL;
+  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
+  Session& t = *e->sess;
+  auto it = t.reqs.find(ticket);
+  if (it == t.reqs.end()) return fail(e, VC_EINVAL, "vc_session_fetch: unknown ticket %d (never issued, or fetched already)", ticket);
+  if (it->second.state != 2) {
+    if (t.broken) return session_broken(e, t);
+    return fail(e, VC_ESTATE, "vc_session_fetch: the request of ticket %d has not finished", ticket);
+  }
+  HIPCHK(e, hipSetDevice(e->device));
+  SessReq r = std::move(it->second);
+  r.edit.iv = r.iv_own.data(); r.edit.mv = r.mv_own.data();
+  // whatever the outcome the ticket is spent: the slot (its K/V rows, its rows of the generated-token log) is free for the next request
+  t.slot_ticket[r.slot] = -1;
+  t.reqs.erase(it);
+  if (!res_dev) return VC_OK;                               // dropped
+  if (!gen_len || res_cap < 0) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_fetch");
+  if (r.prompt_err & 1)
+    return fail(e, VC_EINVAL, "ticket %d: token id out of range in x or y (text rows %d, audio vocab %d)", ticket, e->cfg.text_rows, e->V);
+  SeqState st;              // what the assembly reads of the request's final state, from the slot's record
+  memset(&st, 0, sizeof st);
+  st.done = 1; st.span = r.span; st.total_steps = r.total_steps;
+  for (int i = 0; i < VC_MAX_SPANS; ++i) st.span_steps[i] = r.span_steps[i];
+  // on the side stream: the request's rows of the log are final (its batch has ended), and the decode stream's queued batches are not waited for
+  int rc;
+  if (r.kind == 1) {
+    char who[32];
+    snprintf(who, sizeof who, "ticket %d: ", ticket);
+    rc = edit_assemble(e, r.edit, st, e->gen + (size_t)r.slot * e->gen_cap * e->K, res_dev, res_cap, gen_len, e->side_stream, who);
+  } else {
+    rc = assemble_tts(e, r.job, r.slot, st, res_dev, res_cap, gen_len, e->side_stream);
+  }
+  if (rc) return rc;
+  HIPCHK(e, hipStreamSynchronize(e->side_stream));
+  if (n_steps) *n_steps = r.total_steps;
+  return VC_OK;
+}
+
+extern "C" int vc_session_stats(vc_engine* e, int64_t out[8]) {
+  if (!e) return VC_EINVAL;
+  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
+  if (!out) return fail(e, VC_EINVAL, "null argument to vc_session_stats");
+  const Session& t = *e->sess;
+  for (int i = 0; i < 7; ++i) out[i] = t.stats[i];
+  out[7] = (int64_t)(t.adm_ms * 1000.0);                    // microseconds of decode-stream time spent on admissions whose batch has ended
+  return VC_OK;
+}
+
+extern "C" int vc_session_close(vc_engine* e) {
+  if (!e) return VC_EINVAL;
+  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
+  HIPCHK(e, hipSetDevice(e->device));
+  Session& t = *e->sess;
+  int rc = VC_OK;
+  // wait for what is queued; the next call uploads every state afresh (vc_tts_stream_end with res_dev = NULL is the model)
+  hipError_t he = hipMemsetAsync(e->n_active, 0, sizeof(int), t.s);
+  if (he == hipSuccess) he = hipStreamSynchronize(t.s);
+  if (he != hipSuccess) rc = fail(e, VC_EHIP, "vc_session_close: %s", hipGetErrorString(he));
+  else rc = check_err_flag(e, t.s);                         // (reads and clears the flag word)
+  e->cur_rows = 0;
+  drop_session(e);
+  return rc;
+}
+
+extern "C" int vc_tts(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
+                      const vc_sample_cfg* sc, int n_samples, const int64_t* forced_dev, int n_forced,
+                      int64_t* res_dev, int res_cap, int* gen_len, float* logits_dev, int logit_steps,
+                      int* n_steps, void* stream) {
+  int rc = check_idle(e);
+  if (rc) return rc;
+  if (!x_dev || (!y_dev && T > 0) || !sc || !res_dev || !gen_len || n_samples < 1)
+    return fail(e, VC_EINVAL, "null/invalid argument to vc_tts");
+  hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+  std::vector<TtsJob> jobs{TtsJob{x_dev, Lx, y_dev, T}};
+  rc = tts_run(e, jobs, n_samples, sc, forced_dev, n_forced, logits_dev, logit_steps, n_steps, s);
+  if (rc) return rc;
+  int slot = 0;
+  if (n_samples > 1) {
+    slot = kept_sample(e, 0, n_samples);
+    if (slot < 0) return fail(e, VC_ECAP, "no sample terminated within the step budget");
+  }
+  rc = assemble_tts(e, jobs[0], slot, res_dev, res_cap, gen_len, s);
+  if (rc) return rc;
+  HIPCHK(e, hipStreamSynchronize(s));
+  return VC_OK;
+}
+
+extern "C" int vc_tts_multi_best_of(vc_engine* e, int B, int n_samples, const int64_t* x_dev, const int32_t* x_off,
+                                    const int64_t* y_dev, const int32_t* y_off, const vc_sample_cfg* sc, int shared_text_prefix,
+                                    const int64_t* forced_dev, int n_forced, int64_t* res_dev, int res_cap, int* gen_len,
+                                    int* kept, float* logits_dev, int logit_steps, int* n_steps, void* stream) {
+  int rc = check_idle(e);
+  if (rc) return rc;
+  if (B < 1 || n_samples < 1 || !x_dev || !x_off || !y_dev || !y_off || !sc || !res_dev || !gen_len)
+    return fail(e, VC_EINVAL, "null/invalid argument to vc_tts_multi (B %d, n_samples %d)", B, n_samples);
+  for (int b = 0; b < B; ++b)
+    if (shared_text_prefix < 0 || shared_text_prefix >= x_off[b + 1] - x_off[b])
+      return fail(e, VC_EINVAL, "shared_text_prefix %d must be shorter than every text (sequence %d has %d tokens)",
+                  shared_text_prefix, b, x_off[b + 1] - x_off[b]);
+  hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+  std::vector<TtsJob> jobs;
+  for (int b = 0; b < B; ++b)
+    jobs.push_back(TtsJob{x_dev + x_off[b], x_off[b + 1] - x_off[b], y_dev + (size_t)y_off[b] * e->K, y_off[b + 1] - y_off[b]});
+  rc = tts_run(e, jobs, n_samples, sc, forced_dev, n_forced, logits_dev, logit_steps, n_steps, s, B > 1 ? shared_text_prefix : 0);
+  if (rc) return rc;
+  for (int b = 0; b < B; ++b) {
+    const int j = n_samples > 1 ? kept_sample(e, b, n_samples) : 0;
+    if (j < 0) return fail(e, VC_ECAP, "utterance %d: no sample terminated within the step budget", b);
+    if (kept) kept[b] = j;
+    rc = assemble_tts(e, jobs[b], b * n_samples + j, res_dev + (size_t)b * e->K * res_cap, res_cap, &gen_len[b], s);
+    if (rc) return rc;
+  }
+  HIPCHK(e, hipStreamSynchronize(s));
+  return VC_OK;
+}
+
+extern "C" int vc_tts_multi(vc_engine* e, int B, const int64_t* x_dev, const int32_t* x_off,
+                            const int64_t* y_dev, const int32_t* y_off, const vc_sample_cfg* sc,
+                            int shared_text_prefix,
+                            const int64_t* forced_dev, int n_forced, int64_t* res_dev, int res_cap, int* gen_len,
+                            float* logits_dev, int logit_steps, int* n_steps, void* stream) {
+  return vc_tts_multi_best_of(e, B, 1, x_dev, x_off, y_dev, y_off, sc, shared_text_prefix, forced_dev, n_forced, res_dev, res_cap,
+                              gen_len, nullptr, logits_dev, logit_steps, n_steps, stream);
+}
+
+// ------------------------------------------------------------------------------------- editing (EditJob, edit_prepare, edit_state, edit_assemble: above the decode sessions)
 extern "C" int vc_edit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
                        const int32_t* mask_intervals, int M, const int32_t* mask_values,
                        const vc_sample_cfg* sc, const int64_t* forced_dev, int n_forced,

@@ -328,6 +328,8 @@ __device__ __forceinline__ int filter_draw(int top_k, float top_p, float tempera
 
 // SESS (decode sessions, sample_session_k): the draw's Philox key is the request's own (SampleArgs.seed_tab by slot, sequence 0);
 // lrow = the row of the logits buffer (the step's row b, or, for the first sample of an admitted request, the row its prefill wrote).
+// The request's own sampling controls too (SampleDyn.ctl_tab by slot): requests with different top_k / top_p / temperature /
+// stop_repetition share a step, and a row's draw depends on its own controls alone.
 // SESS is a literal at every call site and the phases are inlined, so each kernel is compiled for its own value: the one-shot kernels
 // pass false and lrow = b and keep the code they had without the parameter (they carry no branch on it).
 __device__ __forceinline__ void sample_phase(const SampleArgs& a, const SampleDyn& dy, int b, int lrow, const SeqState* sp, int* xs,
@@ -338,6 +340,8 @@ __device__ __forceinline__ void sample_phase(const SampleArgs& a, const SampleDy
   const int min_gen = sp->min_gen, cur_num_gen = sp->cur_num_gen, prev_token = sp->prev_token, consec = sp->consec_silence;
   const int y_len = sp->y_len, cap_len = sp->cap_len, slot = sp->slot, feed = sp->feed;
   if (st_done || feed) return;              // (a feed step of a span switch: the reference does not sample those logits)
+  vc_request_ctl rq = {0, 0.f, 0.f, 0};      // SESS: the request's own controls - one 16-byte load, requested ahead of the row's LDS round trip
+  if (SESS) rq = dy.ctl_tab[slot];
   const int V = a.V;
   const int VP = ((V + 63) >> 6) << 6;
   for (int k = wave; k < a.K; k += 4) {
@@ -366,8 +370,9 @@ __device__ __forceinline__ void sample_phase(const SampleArgs& a, const SampleDy
       if (kill_tl) { sv[term] = -10000.f; sv[a.empty_token] = -10000.f; }
       if (n_eog == 0 && k == 0) {
         if (min_gen >= 0 && cur_num_gen <= min_gen) sv[term] = -10000.f;
-        if (dy.stop_repetition > 0 && prev_token >= 0 && is_silence(dy, prev_token) && consec > dy.stop_repetition) {
-          const float f = (float)(consec - (dy.stop_repetition - 1));
+        const int stop_repetition = SESS ? rq.stop_repetition : dy.stop_repetition;
+        if (stop_repetition > 0 && prev_token >= 0 && is_silence(dy, prev_token) && consec > stop_repetition) {
+          const float f = (float)(consec - (stop_repetition - 1));
           const float x = sv[prev_token];
           sv[prev_token] = (x < 0.f) ? x * f : x / f;
         }
@@ -396,7 +401,7 @@ __device__ __forceinline__ void sample_phase(const SampleArgs& a, const SampleDy
     uint32_t pseq = (uint32_t)slot;
     if (SESS) { seed = dy.seed_tab[slot]; pseq = 0u; }       // the request's own key, whatever slot it landed in
     const float u = philox_uniform(seed, pseq, (uint32_t)step, (uint32_t)k);
-    int tok = filter_draw(dy.top_k, dy.top_p, dy.temperature, v, bv, V, u);
+    int tok = filter_draw(SESS ? rq.top_k : dy.top_k, SESS ? rq.top_p : dy.top_p, SESS ? rq.temperature : dy.temperature, v, bv, V, u);
     if (dy.forced && dy.forced_mode == 1 && step < dy.n_forced)      // replay of recorded reference draws (parity tests)
       tok = (int)dy.forced[((long)step * dy.n_seq + slot) * a.K + k];
     if (lane == 0) {
@@ -542,9 +547,19 @@ __device__ void advance_phase(const SampleArgs& a, const SampleDyn& dy, int b, b
           int* rec = dy.retire_rec + slot * VC_SESS_REC;
           const int s0 = (span >= 1) ? sp->span_steps[0] : 0;
           const int stamp = *dy.batch_id;
+          // the step count of every span (static LDS indices; spans the request never reached hold 0) and the rows it fed without
+          // sampling: two per span switch - every finished span was followed by one, except a span whose end retired the request
+          int ss[VC_MAX_SPANS];
+#pragma unroll
+          for (int i = 0; i < VC_MAX_SPANS; ++i) ss[i] = sp->span_steps[i];
+          const int fed = 2 * max(0, span - (n_eog == 0 && cur == 0 ? 1 : 0));
           __hip_atomic_store(rec + 1, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
           __hip_atomic_store(rec + 2, span, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
           __hip_atomic_store(rec + 3, s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          __hip_atomic_store(rec + 5, fed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#pragma unroll
+          for (int i = 0; i < VC_MAX_SPANS; ++i)
+            __hip_atomic_store(rec + VC_SESS_REC_SPANS + i, ss[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
           __hip_atomic_store(rec + 0, stamp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         if (atomicSub(a.n_active, 1) == 1)     // the last live sequence: tell the host loop without a stream operation
@@ -872,18 +887,20 @@ hipError_t vc_launch_repack(const RepackArgs& a, hipStream_t s) {
 }
 
 // ---- decode sessions: repack_k's compaction for a step that may also get WIDER, plus the admission of new requests.  Queued by the
-// session between two graph batches, behind the prefill of the requests it admits; one workgroup.
+// session between two graph batches, behind the prefill of the requests it admits; one workgroup.  An admitted request's first state
+// is whatever the host built for its kind (a TTS request's init_state, an editing request's edit_state with feed_switch set): the
+// kernel copies it word by word from the staging array, and its sampling controls into the slot's entry of ctl_tab.
 __global__ __launch_bounds__(256) void session_turn_k(const SessTurnArgs a) {
   __shared__ SeqState s_st[VC_MAX_SEQS];
   __shared__ int s_src[VC_MAX_SEQS], s_pos[VC_MAX_SEQS], s_live;
-  __shared__ int s_slot[VC_MAX_SEQS], s_Lx[VC_MAX_SEQS], s_cols[VC_MAX_SEQS];
+  __shared__ SeqState s_adm[VC_MAX_SEQS];     // the admitted requests' first states: parked here with the live ones, so that the layout loop below stores without loading
   const int tid = threadIdx.x;
   constexpr int W = sizeof(SeqState) / 4;
   if (tid == 0) *a.batch_id = a.batch;
   if (!a.repack) return;
   for (int i = tid; i < a.B_old * W; i += blockDim.x) reinterpret_cast<int*>(s_st)[i] = reinterpret_cast<const int*>(a.st)[i];
   if (tid < a.B_old) s_pos[tid] = a.row_pos[tid];
-  if (tid < a.n_new) { s_slot[tid] = a.slot[tid]; s_Lx[tid] = a.Lx[tid]; s_cols[tid] = a.n_cols[tid]; }
+  for (int i = tid; i < a.n_new * W; i += blockDim.x) reinterpret_cast<int*>(s_adm)[i] = reinterpret_cast<const int*>(a.adm_st)[i];
   __syncthreads();
   if (tid == 0) {
     int n = 0;
@@ -905,28 +922,22 @@ __global__ __launch_bounds__(256) void session_turn_k(const SessTurnArgs a) {
     const int r = i / W, w = i - r * W;
     int v;
     if (r < n_live) v = reinterpret_cast<const int*>(s_st + s_src[r])[w];
-    else if (r < n_live + a.n_new) {                   // init_state of a TTS request (vc_engine.hip), slot = its K/V slot
-      const int j = r - n_live;
-      v = (w == (int)(offsetof(SeqState, Lx) / 4)) ? s_Lx[j] :
-          (w == (int)(offsetof(SeqState, y_len) / 4)) ? s_cols[j] :
-          (w == (int)(offsetof(SeqState, prev_token) / 4) || w == (int)(offsetof(SeqState, group) / 4)) ? -1 :
-          (w == (int)(offsetof(SeqState, n_spans) / 4) || w == (int)(offsetof(SeqState, kept) / 4)) ? 1 :
-          (w == (int)(offsetof(SeqState, cap_len) / 4)) ? s_Lx[j] * a.cap_mult :
-          (w == (int)(offsetof(SeqState, min_gen) / 4)) ? a.min_gen :
-          (w == (int)(offsetof(SeqState, term_token) / 4)) ? a.term_token :
-          (w == (int)(offsetof(SeqState, kill_token) / 4)) ? a.kill_token :
-          (w == (int)(offsetof(SeqState, slot) / 4)) ? s_slot[j] : 0;
-    } else {                                           // filler: a finished state that owns no sequence (repack_k)
+    else if (r < n_live + a.n_new) v = reinterpret_cast<const int*>(s_adm + (r - n_live))[w];   // the request's first state, as the host staged it
+    else {                                           // filler: a finished state that owns no sequence (repack_k)
       v = (w == (int)(offsetof(SeqState, done) / 4)) ? 1 :
           (w == (int)(offsetof(SeqState, slot) / 4) || w == (int)(offsetof(SeqState, group) / 4)) ? -1 : 0;
     }
     reinterpret_cast<int*>(a.st + r)[w] = v;
   }
   if (tid < a.n_new) {
-    const int slot = s_slot[tid];
-    a.adm_slot[tid] = slot;
-    a.seed_tab[slot] = a.seed[tid];
+    const int slot = s_adm[tid].slot;
+    // everything loaded before the first store (a store that consumed a load issued behind another store would wait for that store)
+    const uint64_t seed = a.seed[tid];
+    const uint4 ctl = *reinterpret_cast<const uint4*>(a.adm_ctl + tid);       // (16 bytes, as one register quad)
     const int pe = a.prompt_err[slot];
+    a.adm_slot[tid] = slot;
+    a.seed_tab[slot] = seed;
+    *reinterpret_cast<uint4*>(a.ctl_tab + slot) = ctl;
     a.prompt_err[slot] = 0;
     __hip_atomic_store(a.retire_rec + slot * VC_SESS_REC + 4, pe, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }

@@ -344,14 +344,16 @@ class VoiceCraftEngine:
     # ---- decode sessions: continuous batching (include/vc_engine.h vc_session_*)
     def open_session(self, max_live: int | None = None, top_k: int = -100, top_p: float = 1.0, temperature: float = 1.0,
                      stop_repetition: int = 3, silence_tokens: Iterable[int] = (1388, 1898, 131), **unsupported) -> "DecodeSession":
-        """A decode session over `max_live` K/V slots (default max_seqs): TTS requests with inference_tts semantics, one sample each,
-        submitted at any time, each joining the running batch between two graph batches and handed back as soon as it ends.
-        The sampling controls are the session's; the seed is per request (DecodeSession.submit).  Use it as a context manager.
-        Editing, best-of-N, a shared text prefix, logits_out and forced trajectories are not part of a session and are refused."""
+        """A decode session over `max_live` K/V slots (default max_seqs): TTS requests with inference_tts semantics and editing
+        requests with inference semantics, one sample each, submitted at any time, each joining the running batch between two graph
+        batches and handed back as soon as it ends.  top_k / top_p / temperature / stop_repetition given here are the default of a
+        request that brings none of its own (DecodeSession.submit / submit_edit); silence_tokens are the session's; the seed is per
+        request.  Use it as a context manager.
+        Best-of-N, a shared text prefix, logits_out and forced trajectories are not part of a session and are refused."""
         if unsupported:
-            raise AssertionError(f"open_session: {sorted(unsupported)} not supported - a decode session takes plain TTS requests, one "
-                                 "sample each (no editing / mask_interval, no best-of-N batch_size, no _shared_text_prefix, no "
-                                 "_logit_steps, no _forced trajectories): use the blocking calls for those")
+            raise AssertionError(f"open_session: {sorted(unsupported)} not supported - a decode session takes TTS and editing requests, "
+                                 "one sample each (no best-of-N batch_size, no _shared_text_prefix, no _logit_steps, no _forced "
+                                 "trajectories): use the blocking calls for those")
         return DecodeSession(self, self.max_seqs if max_live is None else int(max_live),
                              self._sample_cfg(top_k, top_p, temperature, stop_repetition, silence_tokens, 0))
 
@@ -371,6 +373,29 @@ class VoiceCraftEngine:
                 yv = torch.as_tensor(yv, dtype=torch.int64).reshape(1, -1, K)
                 tickets.append(sess.submit(xv, torch.tensor([xv.shape[1]]), yv, seed=None if seeds is None else seeds[i]))
             done = {t: (res, gen) for t, res, gen in sess.drain()}
+            self.last_session_stats = sess.stats()
+        return [done[t] for t in tickets]
+
+    @torch.no_grad()
+    def inference_queue(self, xs, ys, mask_intervals, max_live: int | None = None, seeds=None, **sampling):
+        """Any number of editing requests through `max_live` slots of one decode session (default max_seqs), each following
+        `inference` exactly.  xs, ys, mask_intervals as inference_multi takes them; seeds: one per request.  Sampling defaults are
+        `inference`'s (stop_repetition -1).  Returns the list of res [1,K,T'_i] in input order - the return type of
+        inference_multi.  self.last_session_stats holds the session's stats()."""
+        assert len(xs) == len(ys) == len(mask_intervals) and len(xs) >= 1, (len(xs), len(ys), len(mask_intervals))
+        assert seeds is None or len(seeds) == len(xs), "one seed per request"
+        K = self.args.n_codebooks
+        sampling.setdefault("stop_repetition", -1)
+        with self.open_session(max_live, **sampling) as sess:
+            tickets = []
+            for i, (xv, yv, mi) in enumerate(zip(xs, ys, mask_intervals)):
+                xv = torch.as_tensor(xv, dtype=torch.int64).reshape(1, -1)
+                yv = torch.as_tensor(yv, dtype=torch.int64).reshape(1, -1, K)
+                mi = torch.as_tensor(mi, dtype=torch.int64)
+                mi = mi.reshape(1, -1, 2) if mi.ndim == 2 else mi
+                tickets.append(sess.submit_edit(xv, torch.tensor([xv.shape[1]]), yv, mi, seed=None if seeds is None else seeds[i],
+                                                _who=f"request {i}: "))
+            done = {t: res for t, res, gen in sess.drain()}
             self.last_session_stats = sess.stats()
         return [done[t] for t in tickets]
 
@@ -678,16 +703,21 @@ class SessionRequestError(EngineError):
 
 
 class DecodeSession:
-    """An open decode session of a VoiceCraftEngine (VoiceCraftEngine.open_session).  submit() queues a request and returns its
-    ticket; poll() runs one turn of the decode loop and returns the requests that finished; drain() polls until the session is
-    idle.  While a session is open the engine's other decode calls and set_option raise (EngineError, VC_ESTATE)."""
+    """An open decode session of a VoiceCraftEngine (VoiceCraftEngine.open_session).  submit() queues a TTS request, submit_edit()
+    an editing request; both return a ticket.  poll() runs one turn of the decode loop and returns the requests that finished;
+    drain() polls until the session is idle.  While a session is open the engine's other decode calls and set_option raise
+    (EngineError, VC_ESTATE)."""
+
+    CONTROLS = ("top_k", "top_p", "temperature", "stop_repetition")
 
     STATS = ("admitted", "admitted_while_live", "turns", "widenings", "narrowings", "live_rows", "launched_rows", "admission_us")
 
     def __init__(self, engine: VoiceCraftEngine, max_live: int, sc: SampleCfg):
         self.engine, self.max_live = engine, int(max_live)
         self._open = False
-        self._reqs: dict[int, tuple] = {}     # ticket -> (x, y, T, Lx): the device tensors stay alive until the ticket is fetched
+        self._reqs: dict[int, tuple] = {}     # ticket -> (x, y, T, Lx, M): the device tensors stay alive until the ticket is fetched
+                                              # (M: spans of an editing request, 0 = TTS)
+        self._sc = sc                         # the session's controls: the default of each field a request does not give
         self._ready: list = []                # (ticket, res, gen) fetched and not yet handed out
         self.idle = True
         # uploads and result arithmetic run on a stream of the session's own: a launch on the null stream would wait for the decode
@@ -709,30 +739,79 @@ class DecodeSession:
         except Exception:  # pragma: no cover
             pass
 
-    def submit(self, x, x_lens, y, seed=None) -> int:
-        """x [1,Lx'], x_lens [1], y [1,T,K] as inference_tts takes them (same checks, same special_first handling)."""
-        assert self._open, "the session is closed"
+    def _ctl(self, who: str, controls: dict):
+        """The request's vc_request_ctl (None when it gives no control of its own: the session's apply)."""
+        bad = sorted(set(controls) - set(self.CONTROLS))
+        assert not bad, (f"{who}: {bad} not supported per request - a request's own controls are {list(self.CONTROLS)}; silence_tokens "
+                         "and everything else are the session's (open_session)")
+        if not controls:
+            return None
+        ctl = _lib.RequestCtl()
+        ctl.top_k = int(controls.get("top_k", self._sc.top_k))
+        ctl.top_p = float(controls.get("top_p", self._sc.top_p))
+        ctl.temperature = float(controls.get("temperature", self._sc.temperature))
+        ctl.stop_repetition = int(controls.get("stop_repetition", self._sc.stop_repetition))
+        return ctl
+
+    def _upload(self, x, x_lens, y):
         eng = self.engine
         Lx = int(x_lens[0])                      # (read on the host before anything is queued)
         with torch.cuda.stream(self._side):
             xd, Lx, yd, T = eng._prep(x, torch.tensor([Lx]), y)
         self._side.synchronize()                 # the prompt is on the device before the prefill that reads it can be queued
+        return xd, Lx, yd, T
+
+    def submit(self, x, x_lens, y, seed=None, **controls) -> int:
+        """A TTS request: x [1,Lx'], x_lens [1], y [1,T,K] as inference_tts takes them (same checks, same special_first handling).
+        controls: any of top_k, top_p, temperature, stop_repetition for this request alone; the others are the session's."""
+        assert self._open, "the session is closed"
+        eng = self.engine
+        ctl = self._ctl("submit", controls)
+        xd, Lx, yd, T = self._upload(x, x_lens, y)
         sd = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
         ticket = C.c_int(0)
-        check(eng.lib.vc_session_submit(eng._h, C.c_void_p(xd.data_ptr()), Lx, C.c_void_p(yd.data_ptr()), T, sd, C.byref(ticket)),
+        check(eng.lib.vc_session_submit_ctl(eng._h, C.c_void_p(xd.data_ptr()), Lx, C.c_void_p(yd.data_ptr()), T,
+                                            C.byref(ctl) if ctl is not None else None, sd, C.byref(ticket)),
               eng._h, "vc_session_submit")
-        self._reqs[ticket.value] = (xd, yd, T, Lx)
+        self._reqs[ticket.value] = (xd, yd, T, Lx, 0)
+        self.idle = False
+        return ticket.value
+
+    def submit_edit(self, x, x_lens, y, mask_interval, seed=None, _who: str = "", **controls) -> int:
+        """An editing request: x, x_lens, y and mask_interval [1,M,2] as `inference` takes them (same checks and messages, the mask
+        values derived as there).  controls: as in submit().  A refused request leaves the session running."""
+        assert self._open, "the session is closed"
+        eng = self.engine
+        ctl = self._ctl("submit_edit", controls)
+        mask_interval = torch.as_tensor(mask_interval)
+        assert mask_interval.ndim == 3 and mask_interval.shape == torch.Size((1, mask_interval.shape[1], 2)), mask_interval
+        ivs = [(int(a), int(b)) for a, b in mask_interval[0].tolist()]
+        M = len(ivs)
+        mask_value = eng._edit_layout(ivs, int(y.shape[1]), who=_who)
+        xd, Lx, yd, T = self._upload(x, x_lens, y)
+        iv_arr = (C.c_int32 * (2 * M))(*[v for iv in ivs for v in iv])
+        mv_arr = (C.c_int32 * (2 * M))(*mask_value)
+        sd = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+        ticket = C.c_int(0)
+        check(eng.lib.vc_session_submit_edit(eng._h, C.c_void_p(xd.data_ptr()), Lx, C.c_void_p(yd.data_ptr()), T, iv_arr, M, mv_arr,
+                                             C.byref(ctl) if ctl is not None else None, sd, C.byref(ticket)),
+              eng._h, f"{_who}vc_session_submit_edit")
+        self._reqs[ticket.value] = (xd, yd, T, Lx, M)
         self.idle = False
         return ticket.value
 
     def fetch(self, ticket: int):
-        """(res [1,K,T+Tg], gen [1,K,Tg]) of a finished request, the values inference_tts returns; frees its slot."""
+        """A finished request's result; frees its slot.  A TTS ticket: (res [1,K,T+Tg], gen [1,K,Tg]), the values inference_tts
+        returns.  An edit ticket: (res [1,K,T'], None), res being what `inference` returns."""
         assert self._open, "the session is closed"
         eng = self.engine
         K = eng.args.n_codebooks
         req = self._reqs.get(int(ticket))
-        xd, yd, T, Lx = req if req is not None else (None, None, 0, 1)
-        cap = T + eng._gen_budget(Lx, T + 1, eng.args.encodec_sr // 5)
+        xd, yd, T, Lx, M = req if req is not None else (None, None, 0, 1, 0)
+        if M:                                    # the buffer of `inference` for this request
+            cap = T + eng._gen_budget(Lx, T + 2 * (M + 1) + (M + 1) * K + 1, 10, spans=M)
+        else:
+            cap = T + eng._gen_budget(Lx, T + 1, eng.args.encodec_sr // 5)
         res = torch.empty((K, cap), dtype=torch.int64, device=eng.device)
         gen_len, n_steps = C.c_int(0), C.c_int(0)
         rc = eng.lib.vc_session_fetch(eng._h, int(ticket), C.c_void_p(res.data_ptr()), cap, C.byref(gen_len), C.byref(n_steps))
@@ -740,6 +819,13 @@ class DecodeSession:
             self._reqs.pop(int(ticket), None)
         check(rc, eng._h, "vc_session_fetch")
         eng.last_steps = n_steps.value
+        if M:                                    # (gen_len is the result length T' of an edit ticket)
+            out = res[:, : gen_len.value].unsqueeze(0)
+            if eng.args.special_first:
+                with torch.cuda.stream(self._side):
+                    out = out - int(eng.args.n_special)
+                self._side.synchronize()
+            return out, None
         Tg = gen_len.value
         out, gen = res[:, : T + Tg].unsqueeze(0), res[:, T: T + Tg].unsqueeze(0)
         if eng.args.special_first:
@@ -811,6 +897,11 @@ class DecodeSession:
 def inference_tts_queue(engine: VoiceCraftEngine, xs, ys, max_live: int | None = None, seeds=None, **sampling):
     """VoiceCraftEngine.inference_tts_queue as a function: any number of utterances through `max_live` slots of one decode session."""
     return engine.inference_tts_queue(xs, ys, max_live=max_live, seeds=seeds, **sampling)
+
+
+def inference_queue(engine: VoiceCraftEngine, xs, ys, mask_intervals, max_live: int | None = None, seeds=None, **sampling):
+    """VoiceCraftEngine.inference_queue as a function: any number of editing requests through `max_live` slots of one decode session."""
+    return engine.inference_queue(xs, ys, mask_intervals, max_live=max_live, seeds=seeds, **sampling)
 
 
 def debug_sample(logits: torch.Tensor, n_draws: int, top_k: int = -100, top_p: float = 1.0, temperature: float = 1.0,
