@@ -86,7 +86,8 @@ int vc_codec_encode_batch(vc_codec* c, const float* wav_dev, int B, int n_sample
                           int codes_cap, int* n_frames, void* stream);
 int vc_codec_decode_batch(vc_codec* c, const int64_t* codes_dev, int B, int T, float* wav_dev, int wav_cap,
                           void* stream);
-/* ---- chunked decode: the waveform of a code sequence that is still being produced (one clip; no batch form).
+/* ---- chunked decode: the waveform of a code sequence that is still being produced (one clip; vc_codec_decode_streams below
+ * advances many).
  * The decoder is an RVQ look-up, one conv over frames, a UNIDIRECTIONAL LSTM and a purely local upsampling stack, so it can
  * run chunk by chunk with the LSTM's (h, c) carried between calls and a few frames of look-ahead - exactly: the
  * concatenation of everything a stream emits is, BIT FOR BIT, what vc_codec_decode gives for the concatenation of
@@ -124,6 +125,39 @@ int vc_codec_stream_geometry(const vc_codec_cfg* cfg, int* lookahead_frames, int
 int vc_codec_decode_stream_begin(vc_codec* c);
 int vc_codec_decode_stream(vc_codec* c, const int64_t* codes_dev, int stride, int n, int last, float* wav_dev,
                            int wav_cap, int* n_samples_out, void* stream);
+/* ---- many decode streams on one handle, advanced together.  Up to max_batch independent streams, each holding what the single
+ * stream above holds ((h, c) of both LSTM layers, kept latents, kept LSTM outputs, counters) in buffers of its own.  The single
+ * stream keeps its own state: it, the streams here and the blocking calls may be interleaved on one handle.
+ *   vc_codec_decode_streams_open   n in [1, max_batch] streams, ids 0 .. n - 1, all at their start (zero LSTM state); a second open
+ *                                  restarts all.  More than 2 LSTM layers: VC_EINVAL, as vc_codec_decode_stream_begin.
+ *   vc_codec_decode_streams_reset  puts stream `id` back at its start (and re-opens it after `last` or a failed call).  Host only,
+ *                                  like open once the buffers exist: no device work, no synchronisation (the stream's first pass
+ *                                  through the LSTM takes zeros for (h, c)), so it may be called while other work is queued.
+ *   vc_codec_decode_streams        host arrays of n entries, no stream twice: entry i feeds stream ids[i] its next n_frames[i] frames
+ *                                  (0 is legal) from codes_dev[i] (device, int64 [K][n_frames[i]], row stride stride[i]); last[i]
+ *                                  flushes and closes that stream; wav_dev[i] (device, wav_cap[i] samples) receives
+ *                                  n_samples_out[i] samples.  Every stream emits, bit for bit and with exactly the per-call sample
+ *                                  counts, what vc_codec_decode_stream emits for the same sequence of feeds, whatever the other
+ *                                  streams of the call do.  The call returns with the samples written.
+ *     Every entry is planned and checked before anything is queued: on a stream id out of range or given twice, a closed stream
+ *     (VC_ESTATE), a chunk over the capacity or a wav_cap too small (VC_ECAP), n_frames < 0, stride < n_frames or a null pointer
+ *     (VC_EINVAL) no stream consumes anything, and the corrected call gives the right result.  A call that fails later (a code
+ *     index out of range, a HIP error) closes the streams it fed.
+ *     Entries whose plans coincide (frames fed and kept, frames through the LSTM, frames handed out, `last`) form a GROUP and run
+ *     as ONE batched launch sequence - window assembly, first conv, LSTM with B carried states, the stack behind it, hand-out - whose
+ *     launch count does not depend on the group's size, where the batched LSTM exists (2 layers, width a multiple of 256 up to
+ *     1024: vc_codec_decode_batch's condition); every other entry is a group of one.  Streams fed in lock-step are one group.
+ *   vc_codec_last_streams_census   of the last vc_codec_decode_streams call: out[0] groups run, out[1] size of the largest,
+ *                                  out[2] kernel launches plus asynchronous copies the call queued, out[3] LSTM form of the largest
+ *                                  group (vc_codec_last_forms' values; -1: nothing went through the LSTM).  out[2] is the host's
+ *                                  own bookkeeping - a tally kept next to each launch site of the decode path - not an observation
+ *                                  of the queue: it shows how the call was grouped and planned, it cannot prove what ran. */
+int vc_codec_decode_streams_open(vc_codec* c, int n);
+int vc_codec_decode_streams_reset(vc_codec* c, int id);
+int vc_codec_decode_streams(vc_codec* c, int n, const int* ids, const int64_t* const* codes_dev, const int* stride,
+                            const int* n_frames, const int* last, float* const* wav_dev, const int* wav_cap,
+                            int* n_samples_out, void* stream);
+int vc_codec_last_streams_census(const vc_codec* c, int out[4]);
 
 /* Test hooks: the latent before quantisation ([T][hidden], channels-last) of the last encode,
  * and its timing (HIP events on the stream). */

@@ -242,6 +242,22 @@ int vc_tts_stream_end(vc_engine* e, int64_t* res_dev, int res_cap, int* gen_len,
  *            [5] sum over launched steps of the rows that were live, an edit's fed rows included (counted at retirement), [6] sum over
  *            launched steps of the step width, [7] microseconds of decode-stream time spent on admissions (prefill + re-pack + first
  *            sample; HIP events).
+ *   frames   the frames of live TTS tickets while they decode (streaming): for each of the n tickets, frames [first_frame[i],
+ *            first_frame[i] + n_frames[i]) un-shifted into block i of codes_dev [n][K][cap] (row stride cap, as vc_tts_stream_next
+ *            lays them out: out[j][t] = the log's row t + j, codebook j).  The call never advances the loop, queues nothing on the
+ *            decode stream and waits for nothing on it: it hands out what the host already knows to be final.  A request admitted by
+ *            the turn that queued batch b has 1 + graph_steps * (known - b + 1) final rows once advance has seen batch known >= b end
+ *            (none before), and its own frame count - the gen_len fetch reports - once its retirement is among the ended batches,
+ *            whether or not advance has reported it yet; frame t needs rows t .. t + K - 1.  What is handed out when is therefore a
+ *            function of the submission schedule, like the admissions.  A ticket gets frames only when at least min_frames are
+ *            ready, or, once it has ended, all the rest however few (never more than cap per call); done[i] = 1 once it has ended
+ *            and every frame has been handed out.  A pending ticket: 0 frames, done 0.  A ticket that ended without a result (ran out
+ *            of positions; an out-of-range token id, of which no frame is ever handed out): done 1 and no further frames - fetch
+ *            still reports the error.  A finished ticket streams until it is fetched.  The gather is one launch for all tickets on
+ *            the side stream of vc_tts_stream_next, and only that stream is synchronised.  Refused as a whole, before any cursor
+ *            moves, with VC_EINVAL: an unknown or fetched ticket, a ticket given twice, an editing ticket ("editing requests do not
+ *            stream": its rows per batch hang on span switches the host learns at retirement, and its result is a splice), n outside
+ *            [1, max_live], cap < 1, min_frames outside [1, cap], null pointers.  No session: VC_ESTATE; a broken session: its error.
  *   close    waits for what is queued, drops everything pending and unfetched; the engine is reusable. */
 typedef struct vc_request_ctl {   /* 16 bytes: the per-request part of vc_sample_cfg, same meaning field by field */
   int32_t top_k;
@@ -258,6 +274,8 @@ int vc_session_submit_edit(vc_engine* e, const int64_t* x_dev, int Lx, const int
                            const vc_request_ctl* ctl, uint64_t seed, int* ticket);
 int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* n_finished, int* idle);
 int vc_session_fetch(vc_engine* e, int ticket, int64_t* res_dev, int res_cap, int* gen_len, int* n_steps);
+int vc_session_frames(vc_engine* e, int n, const int* tickets, int min_frames, int64_t* codes_dev, int cap,
+                      int* first_frame, int* n_frames, int* done);
 int vc_session_stats(vc_engine* e, int64_t out[8]);
 int vc_session_close(vc_engine* e);
 

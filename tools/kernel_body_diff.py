@@ -3,7 +3,8 @@
 usage: python tools/kernel_body_diff.py [--rev HEAD] [--unit vc_tokens] > profiles/<name>.log
 Compiles voicecraft_amd/csrc/<unit>.hip device-only (hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S) from the
 working tree and from `git show <rev>:` copies of csrc/ and include/ in a temporary directory, then compares each kernel's
-instruction lines after dropping comments, directives and the function index inside basic-block labels (.LBB<n>_)."""
+instruction lines (up to the kernel's .Lfunc_end label) after dropping comments, directives and the function index inside basic-block
+labels (.LBB<n>_)."""
 import argparse, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,6 +31,9 @@ def checkout(rev, dst):
 
 
 def instructions(body):
+    # a kernel's code ends at its .Lfunc_end label (basic blocks may follow its last s_endpgm).  What isa.kernels() hands over runs
+    # to the next kernel's head, and for the unit's LAST kernel to the end of the file: the compilation-unit id and the metadata table
+    body = re.split(r"^\.Lfunc_end\d+:", body, maxsplit=1, flags=re.M)[0]
     out = []
     for line in body.splitlines():
         t = line.split(";")[0].strip()

@@ -15,7 +15,15 @@ re-pack + first sample, HIP events).  Both arms produce the same number of frame
 (top_k 0, top_p 0.8, stop_repetition -1; the span covers the middle third of the prompt frames), submitted to the SAME session with
 their own controls next to the TTS requests.  The baseline then runs, for every consecutive group of L requests, inference_tts_multi on
 the group's TTS requests and inference_multi on its editing requests - what the blocking API offers when the two kinds cannot share a
-step; the frames compared and counted are the generated ones of either kind."""
+step; the frames compared and counted are the generated ones of either kind.
+--stream: instead of the above, per size, every request streams (DecodeSession.submit(stream=True)):
+  * streamer: voicecraft_amd.stream.SessionStreamer pumped until the session is idle - frames pulled while the batch decodes, ONE
+    decode_streams feed per pump (--chunk-frames, default 8);
+  * drain:    the same session with drain(), then one blocking tokenizer.decode per result.
+One JSON line: per-request time to first audio (from the moment all requests were submitted; drain arm: to the end of that request's
+decode) and the total time of both arms, interleaved pairs; both arms' audio lengths are asserted equal.  A second line measures the
+codec alone: L streams of --codec-frames frames in chunks of --chunk-frames, all L in one decode_streams call per chunk against the
+same L streams fed one call each.  Every special token is muted so that the generated ids are codec ids."""
 import argparse, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -33,13 +41,16 @@ p.add_argument("--top-k", type=int, default=40)
 p.add_argument("--pairs", type=int, default=5)
 p.add_argument("--sizes", default="64:8,256:64")
 p.add_argument("--edit-share", type=float, default=0.0)
+p.add_argument("--stream", action="store_true")
+p.add_argument("--chunk-frames", type=int, default=8)
+p.add_argument("--codec-frames", type=int, default=200)
 args = p.parse_args()
 dev = torch.device("cuda", 0)
 a = synth.make_args(args.preset)
 K = a.n_codebooks
 # (with editing requests in the mix every special token is muted, not only the TTS terminator: an edit then ends at the length cap
 # too - its terminator is eog - and both arms generate the same frames whatever their seeds)
-sd = synth.make_state_dict(a, seed=0, perturb=False, mute_eos=True, fast=True, mute_special=args.edit_share > 0)
+sd = synth.make_state_dict(a, seed=0, perturb=False, mute_eos=True, fast=True, mute_special=args.edit_share > 0 or args.stream)
 kn = dict(top_k=args.top_k, top_p=1.0, temperature=1.0, stop_repetition=3, silence_tokens=[1388, 1898, 131])
 ekn = dict(top_k=0, top_p=0.8, temperature=1.0, stop_repetition=-1)      # the editing front-end's defaults
 span = (args.prompt_frames // 3, 2 * (args.prompt_frames // 3))
@@ -129,6 +140,98 @@ for size in args.sizes.split(","):
                     admitted_while_live=st["admitted_while_live"], widenings=st["widenings"], narrowings=st["narrowings"],
                     admission_us=st["admission_us"])
 
+    def stream_leg():
+        from voicecraft_amd.codec import AudioTokenizer
+        from voicecraft_amd.stream import SessionStreamer
+        tok = AudioTokenizer(synth.make_codec_state_dict(0), device=dev, max_seconds=(args.lx * 10 + 16) * 320 / 16000.0, max_batch=L)
+
+        def submit_all(sess, seed, stream):
+            return [sess.submit(xs[u].reshape(1, -1), torch.tensor([lxs[u]]), ys[u].unsqueeze(0), seed=seed + u, stream=stream) for u in range(N)]
+
+        def streamer(seed):
+            torch.cuda.synchronize()
+            with eng.open_session(L, **kn) as sess:
+                pump = SessionStreamer(sess, tok, chunk_frames=args.chunk_frames)
+                tickets = submit_all(sess, seed, True)
+                t0 = time.perf_counter()
+                first, samples, done = {}, {t: 0 for t in tickets}, set()
+                while not (sess.idle and len(done) == N):
+                    for t, wav, d in pump.pump():
+                        if wav.shape[2] and t not in first:
+                            torch.cuda.current_stream(dev).synchronize()
+                            first[t] = time.perf_counter() - t0
+                        samples[t] += int(wav.shape[2])
+                        if d:
+                            done.add(t)
+                torch.cuda.synchronize()
+                wall = time.perf_counter() - t0
+            return dict(wall_ms=wall * 1e3, first_ms=[first[t] * 1e3 for t in tickets], samples=[samples[t] for t in tickets])
+
+        def drained(seed):
+            torch.cuda.synchronize()
+            with eng.open_session(L, **kn) as sess:
+                tickets = submit_all(sess, seed, False)
+                t0 = time.perf_counter()
+                res = {t: gen for t, _, gen in sess.drain()}
+                first, samples = {}, {}
+                for t in tickets:
+                    wav = tok.decode([(res[t], None)])
+                    torch.cuda.synchronize()
+                    first[t] = time.perf_counter() - t0
+                    samples[t] = int(wav.shape[2])
+                wall = time.perf_counter() - t0
+            return dict(wall_ms=wall * 1e3, first_ms=[first[t] * 1e3 for t in tickets], samples=[samples[t] for t in tickets])
+
+        streamer(0); drained(0)
+        rows = {"streamer": [], "drain": []}
+        for i in range(args.pairs):
+            for arm in (["streamer", "drain"] if i % 2 == 0 else ["drain", "streamer"]):
+                rows[arm].append(streamer(100 + i) if arm == "streamer" else drained(100 + i))
+        for b_, s_ in zip(rows["drain"], rows["streamer"]):
+            assert b_["samples"] == s_["samples"], "both arms produce the same audio length per request"
+        out = {"workload": f"stream leg: {args.preset} {args.dtype}, top_k={args.top_k}, {N} streaming requests through {L} slots, chunk_frames "
+                           f"{args.chunk_frames}, {min(rows['drain'][0]['samples']) // 320}..{max(rows['drain'][0]['samples']) // 320} generated frames",
+               "pairs": args.pairs, "graph_steps": G}
+        for arm in ("streamer", "drain"):
+            r = rows[arm]
+            out[arm] = {"wall_ms": stats([v["wall_ms"] for v in r]),
+                        "first_audio_ms_median_over_requests": stats([statistics.median(v["first_ms"]) for v in r]),
+                        "first_audio_ms_first_request": stats([v["first_ms"][0] for v in r]),
+                        "first_audio_ms_worst_request": stats([max(v["first_ms"]) for v in r])}
+        out["streamer_vs_drain_wall_pct"] = stats([100.0 * (s_["wall_ms"] / b_["wall_ms"] - 1.0) for b_, s_ in zip(rows["drain"], rows["streamer"])])
+        print(json.dumps(out), flush=True)
+        # the codec alone: L streams in one call per chunk against one call per stream and chunk
+        T, ch = args.codec_frames, args.chunk_frames
+        clips = [torch.randint(0, 2048, (1, 4, T), device=dev) for _ in range(L)]
+
+        def codec(together):
+            st = tok.decode_streams(L)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for f0 in range(0, T, ch):
+                last = tuple(range(L)) if f0 + ch >= T else ()
+                if together:
+                    st.feed({k: clips[k][:, :, f0: f0 + ch] for k in range(L)}, last=last)
+                else:
+                    for k in range(L):
+                        st.feed({k: clips[k][:, :, f0: f0 + ch]}, last=(k,) if last else ())
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3, st.census()
+        codec(True); codec(False)
+        ms = {True: [], False: []}
+        for i in range(args.pairs):
+            for arm in ((True, False) if i % 2 == 0 else (False, True)):
+                ms[arm].append(codec(arm)[0])
+        print(json.dumps({"workload": f"codec alone: {L} streams of {T} frames in chunks of {ch}", "pairs": args.pairs,
+                          "one_call_per_chunk_ms": stats(ms[True]), "one_call_per_stream_and_chunk_ms": stats(ms[False]),
+                          "census_of_a_joint_call": list(codec(True)[1]),
+                          "joint_vs_separate_pct": stats([100.0 * (a_ / b_ - 1.0) for a_, b_ in zip(ms[True], ms[False])])}), flush=True)
+
+    if args.stream:
+        stream_leg()
+        del eng
+        torch.cuda.empty_cache()
+        continue
     baseline(0); session(0)                    # graphs captured, allocator warm
     rows = {"baseline": [], "session": []}
     for i in range(args.pairs):

@@ -51,6 +51,12 @@ PROTOTYPES = {
     "vc_codec_decode_stream_begin": (C.c_int, [C.c_void_p]),
     "vc_codec_decode_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                          C.POINTER(C.c_int), C.c_void_p]),
+    "vc_codec_decode_streams_open": (C.c_int, [C.c_void_p, C.c_int]),
+    "vc_codec_decode_streams_reset": (C.c_int, [C.c_void_p, C.c_int]),
+    "vc_codec_decode_streams": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_int),
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_int),
+                                          C.POINTER(C.c_int), C.c_void_p]),
+    "vc_codec_last_streams_census": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
 }
 
 # the VoiceCraft codec (README.md:198 of the reference; config.py:51; phonemize_encodec_encode_hf.py:11-13)
@@ -136,6 +142,86 @@ class CodecDecodeStream:
         self.emitted += got.value
         self.ms += tok.last_ms()
         return wav[: got.value].reshape(1, 1, -1)
+
+
+class CodecDecodeStreams:
+    """`n` independent decode streams of an AudioTokenizer, ids 0 .. n-1, advanced together (AudioTokenizer.decode_streams;
+    include/vc_codec.h vc_codec_decode_streams).  `feed` takes the next frames of any of them in ONE call and returns each one's
+    samples that have become final: per stream, bit for bit and call for call what a CodecDecodeStream fed the same chunks
+    returns - concatenated, `tokenizer.decode` of everything it was fed.  Streams fed in lock-step run as one batched launch
+    sequence.  The tokenizer's single decode_stream() and its blocking encode / decode may be used in between."""
+
+    def __init__(self, tok: "AudioTokenizer", n: int):
+        self.tok, self.n = tok, int(n)
+        self.lookahead_frames, self.left_context_frames, self.start_frames = stream_geometry(tok.cfg)
+        tok._check(tok.lib.vc_codec_decode_streams_open(tok._h, self.n), "vc_codec_decode_streams_open")
+        self.fed = [0] * self.n
+        self.emitted = [0] * self.n        # samples
+        self.closed = [False] * self.n
+        self.ms = 0.0
+
+    def ready_frames(self, fed: int) -> int:
+        """Frames whose samples have been emitted once `fed` frames were fed to a stream (before its final call)."""
+        return max(0, fed - self.lookahead_frames) if fed >= self.start_frames else 0
+
+    def reset(self, id: int) -> None:
+        """Puts stream `id` back at its start (a new clip on a reused id)."""
+        self.tok._check(self.tok.lib.vc_codec_decode_streams_reset(self.tok._h, int(id)), "vc_codec_decode_streams_reset")
+        self.fed[id], self.emitted[id], self.closed[id] = 0, 0, False
+
+    def census(self) -> tuple[int, int, int, int]:
+        """(groups run, size of the largest, launches + async copies queued, LSTM form of the largest) of the last feed."""
+        v = (C.c_int * 4)()
+        self.tok._check(self.tok.lib.vc_codec_last_streams_census(self.tok._h, v), "vc_codec_last_streams_census")
+        return tuple(v)
+
+    @torch.no_grad()
+    def feed(self, chunks: dict, last=()) -> dict:
+        """chunks {id: codes int64 [1, K, m]} (m may be 0) -> {id: wav fp32 [1, 1, m']}; the ids in `last` are flushed and closed
+        (an id in `last` alone feeds nothing more).  A refused call consumes nothing of any stream."""
+        tok = self.tok
+        last = set(int(i) for i in last)
+        ids = sorted(set(int(i) for i in chunks) | last)
+        if not ids:
+            return {}
+        n = len(ids)
+        keep, wavs = [], []
+        a_ids, a_stride, a_n, a_last, a_cap, a_got = ((C.c_int * n)() for _ in range(6))
+        a_codes, a_wav = (C.c_void_p * n)(), (C.c_void_p * n)()
+        for i, sid in enumerate(ids):
+            cd = chunks.get(sid)
+            m = 0
+            if cd is not None:
+                assert cd.ndim == 3 and cd.shape[0] == 1 and cd.shape[1] == tok.n_q, cd.shape
+                m = int(cd.shape[2])
+                cd = cd[0].to(tok.device, torch.int64).contiguous()
+                keep.append(cd)
+            ok = 0 <= sid < self.n
+            fed = (self.fed[sid] if ok else 0) + m
+            cap = max(0, (fed if sid in last else self.ready_frames(fed)) * tok.hop - (self.emitted[sid] if ok else 0))
+            wav = torch.empty((max(cap, 1),), dtype=torch.float32, device=tok.device)
+            wavs.append(wav)
+            a_ids[i], a_stride[i], a_n[i], a_last[i], a_cap[i] = sid, m, m, int(sid in last), cap
+            a_codes[i] = cd.data_ptr() if m else None
+            a_wav[i] = wav.data_ptr()
+        rc = tok.lib.vc_codec_decode_streams(tok._h, n, a_ids, a_codes, a_stride, a_n, a_last, a_wav, a_cap, a_got, tok._stream())
+        if rc and all(0 <= sid < self.n and not self.closed[sid] for sid in ids):
+            # not one of the refusals this object can see coming (a bad id, a closed stream): either a refusal that consumed nothing
+            # (capacity) or a failure behind the validation (a code index out of range, a HIP error), which closed the streams it fed
+            msg = (tok.lib.vc_codec_last_error(tok._h) or b"").decode()
+            if "capacity" not in msg:
+                for i, sid in enumerate(ids):
+                    if a_n[i] or a_last[i]:
+                        self.closed[sid] = True
+        tok._check(rc, "vc_codec_decode_streams")
+        out = {}
+        for i, sid in enumerate(ids):
+            self.fed[sid] += a_n[i]
+            self.emitted[sid] += a_got[i]
+            self.closed[sid] = sid in last
+            out[sid] = wavs[i][: a_got[i]].reshape(1, 1, -1)
+        self.ms += tok.last_ms()
+        return out
 
 
 def fold_weight_norm(g: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
@@ -348,6 +434,11 @@ class AudioTokenizer:
     def decode_stream(self) -> CodecDecodeStream:
         """Opens the chunked decode: `.feed(codes [1,K,n], last=False) -> wav [1,1,m]`, `.lookahead_frames`."""
         return CodecDecodeStream(self)
+
+    def decode_streams(self, n: int) -> CodecDecodeStreams:
+        """Opens `n` (<= max_batch) decode streams advanced together: `.feed({id: codes [1,K,m]}, last=()) -> {id: wav [1,1,m']}`,
+        `.reset(id)`.  Opening again restarts all of them."""
+        return CodecDecodeStreams(self, n)
 
     def last_latent(self, T: int, hidden: int | None = None) -> torch.Tensor:
         """The latent in front of the quantizer of the last encode, [T, hidden] (first clip of a batch)."""

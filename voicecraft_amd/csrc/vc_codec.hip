@@ -763,6 +763,98 @@ __global__ void add_vec_k(float* __restrict__ a, const float* __restrict__ b, in
   if (i < n) a[i] += b[i];
 }
 
+// ---- many decode streams advanced together (vc_codec_decode_streams): what the single-stream call moves with a chain of copies per
+// chunk, for the B streams of a group at once.  Every stream of a group has the same plan (rows, counts, offsets); what differs is
+// where its codes, its state and its samples live: one table entry per stream, blockIdx.y = the stream's index in the group.
+#define VC_STREAMS_MAX 64       // = the largest max_batch vc_codec_create accepts
+struct StreamsTab {
+  const int64_t* codes[VC_STREAMS_MAX];   // [Q][stride] the stream's new frames
+  int stride[VC_STREAMS_MAX];
+  float* lat[VC_STREAMS_MAX];             // the stream's kept latents [lat_cap][D]
+  float* y[VC_STREAMS_MAX];               // its kept LSTM outputs [y_cap][top]
+  float* h[VC_STREAMS_MAX];               // its carried hidden state [2][top]
+  float* c[VC_STREAMS_MAX];               // its cell state [2][top]
+  float* wav[VC_STREAMS_MAX];             // where its samples go
+  int fresh[VC_STREAMS_MAX];              // 1: the stream is at its start - its (h, c) are zeros, whatever its buffers hold
+};
+// The latent window [B][rows_lat][D] = each stream's n_lat kept rows + the look-up of its n new frames (rvq_decode_stream_k's sum, in
+// its order), and the kept LSTM outputs into rows [0, n_y) of the window [B][rows_y][top].
+__global__ __launch_bounds__(256) void streams_window_k(const StreamsTab tab, const float* __restrict__ E, float* __restrict__ latent,
+                                                         float* __restrict__ ywin, int n_lat, int n, int D, int C, int Q, int n_y,
+                                                         int rows_y, int top, int* err) {
+  const int b = blockIdx.y;
+  const int rows_lat = n_lat + n;
+  const long n_l = (long)rows_lat * D, n_k = (long)n_y * top;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx < n_l) {
+    const int r = (int)(idx / D), i = (int)(idx % D);
+    float v;
+    if (r < n_lat) {
+      v = tab.lat[b][idx];
+    } else {
+      const int64_t* codes = tab.codes[b];
+      const int stride = tab.stride[b], t = r - n_lat;
+      v = 0.f;
+      for (int q = 0; q < Q; ++q) {
+        long cd = codes[(long)q * stride + t];
+        if (cd < 0 || cd >= C) { *err = 1; cd = 0; }
+        v = v + E[((long)q * C + cd) * D + i];
+      }
+    }
+    latent[(long)b * n_l + idx] = v;
+  } else if (idx < n_l + n_k) {
+    const long j = idx - n_l;
+    ywin[(long)b * rows_y * top + j] = tab.y[b][j];
+  }
+}
+// (h, c) of both layers between the streams' own states and the LSTM's carry arrays [2][B][top]: scatter = 0 gathers h and c in front
+// of the recurrence (zeros for a stream at its start: opening or resetting a stream costs no device work), scatter = 1 stores the
+// last step's h and the cell states back.
+__global__ __launch_bounds__(256) void streams_state_k(const StreamsTab tab, float* __restrict__ h_in, const float* __restrict__ h_out,
+                                                        float* __restrict__ cc, int B, int top, int scatter) {
+  const int b = blockIdx.y;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= 2 * top) return;
+  const int l = idx / top, u = idx - l * top;
+  const long g = ((long)l * B + b) * top + u;
+  if (scatter) { tab.h[b][idx] = h_out[g]; tab.c[b][idx] = cc[g]; }
+  else if (tab.fresh[b]) { h_in[g] = 0.f; cc[g] = 0.f; }
+  else { h_in[g] = tab.h[b][idx]; cc[g] = tab.c[b][idx]; }
+}
+// emit = 0, behind the recurrence: the np new LSTM outputs [B][np][top] join the window behind its n_y kept rows, and each stream's
+// next context is stored - latents from window row l_off on, LSTM outputs from window row k_off on (rows below n_y are the ones
+// streams_window_k laid down, the rest are new: no row this launch writes is read by it).
+// emit = 1, behind the back half: each stream's interior samples [e_off, e_off + n_out) of its decoded window go to its own buffer.
+struct StreamsKeepArgs {
+  const float* latent;      // [B][rows_lat][D]
+  float* ywin;              // [B][rows_y][top]
+  const float* ynew;        // [B][np][top]
+  const float* wavwin;      // [B][win_samples]
+  int rows_lat, D, rows_y, top, n_y, np;
+  int l_off, keep_lat, k_off, keep_y;
+  long win_samples, e_off, n_out;
+  int emit;
+};
+__global__ __launch_bounds__(256) void streams_keep_emit_k(const StreamsTab tab, const StreamsKeepArgs a) {
+  const int b = blockIdx.y;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (a.emit) {
+    if (idx < a.n_out) tab.wav[b][idx] = a.wavwin[(long)b * a.win_samples + a.e_off + idx];
+    return;
+  }
+  const long n_new = (long)a.np * a.top, n_l = (long)a.keep_lat * a.D, n_k = (long)a.keep_y * a.top;
+  if (idx < n_new) {
+    a.ywin[((long)b * a.rows_y + a.n_y) * a.top + idx] = a.ynew[(long)b * n_new + idx];
+  } else if (idx < n_new + n_l) {
+    const long j = idx - n_new;
+    tab.lat[b][j] = a.latent[((long)b * a.rows_lat + a.l_off) * a.D + j];
+  } else if (idx < n_new + n_l + n_k) {
+    const long j = idx - n_new - n_l;
+    const int row = a.k_off + (int)(j / a.top), u = (int)(j % a.top);
+    tab.y[b][j] = row < a.n_y ? a.ywin[((long)b * a.rows_y + row) * a.top + u] : a.ynew[((long)b * a.np + (row - a.n_y)) * a.top + u];
+  }
+}
+
 // ============================================================================ host side
 namespace {
 std::string g_codec_create_err;
@@ -837,9 +929,18 @@ struct vc_codec {
     int n_lat = 0, n_y = 0;              // rows kept: latents of frames [fed - n_lat, fed), LSTM outputs of frames [proc - n_y, proc)
     int lat_cap = 0, y_cap = 0;
     int hcur = 0;                        // which half of h holds the carried hidden state
+    bool fresh = false;                  // (vc_codec_decode_streams) nothing has gone through the LSTM yet: (h, c) count as zeros
     float *lat = nullptr, *y = nullptr;  // [lat_cap][hidden], [y_cap][top]
     float *h = nullptr, *c = nullptr;    // [2][layers][top] (ping-pong), [layers][top]
   } ds;
+  // ---- the streams of vc_codec_decode_streams: ms[id] holds what ds holds (its h is [2 layers][top], no ping-pong: the carry arrays
+  // below are the other half), n_ms of them open.  ms_h_in / ms_h_out / ms_c: the carry arrays of a group, [2][B_max][top] each
+  std::vector<DecStream> ms;
+  int n_ms = 0;
+  float *ms_h_in = nullptr, *ms_h_out = nullptr, *ms_c = nullptr;
+  int persist_carry_b_ok[VC_LSTM_BG + 1];   // residency of the carried persistent form by clips per round (-1 not probed)
+  long n_queued = 0;                     // kernel launches and async copies the decode path has queued (vc_codec_last_streams_census)
+  int census[4]{};
 };
 
 namespace {
@@ -968,6 +1069,7 @@ int run_conv(vc_codec* c, const Conv& cv, const float* x, int L_in, const float*
   a.nphase = 1; a.x_bstride = (long)L_in * cv.Ci; a.o_bstride = (long)T * cv.Co;
   hipLaunchKernelGGL(conv_gemm_k, dim3((T + 127) / 128, (cv.Co + 31) / 32, B), dim3(256), 0, s, a);
   CCHK(c, hipGetLastError());
+  c->n_queued += 1;
   *L_out = T;
   return VC_OK;
 }
@@ -988,6 +1090,7 @@ int run_convT(vc_codec* c, const Conv& cv, const float* x, int L_in, float* out_
   a.nphase = st; a.x_bstride = (long)L_in * cv.Ci; a.o_bstride = (long)L_dst * cv.Co;
   hipLaunchKernelGGL(conv_gemm_k, dim3((a.T + 127) / 128, (cv.Co + 31) / 32, st * B), dim3(256), 0, s, a);
   CCHK(c, hipGetLastError());
+  c->n_queued += 1;
   *L_out = L_dst;
   return VC_OK;
 }
@@ -1026,6 +1129,7 @@ int run_conv1x1(vc_codec* c, const Conv& cv, const float* x, int T, float* out_r
   a.nphase = 1; a.x_bstride = (long)T * cv.Ci; a.o_bstride = (long)T * cv.Co;
   hipLaunchKernelGGL(conv_gemm_k, dim3((T + 127) / 128, (cv.Co + 31) / 32, B), dim3(256), 0, s, a);
   CCHK(c, hipGetLastError());
+  c->n_queued += 1;
   return VC_OK;
 }
 
@@ -1043,6 +1147,7 @@ int check_lstm_flag(vc_codec* c) {
 }
 // EncodecLSTM: y = lstm(x) + x over [B][T][H]; x is raw, the block output is written raw and/or ELU'd
 // cy != NULL: the chunk of a stream - the recurrence starts from cy->h_in / cy->c and leaves its last step in cy->h_out / cy->c
+// ([B][H] per layer: B streams advanced together on the two-layer forms, one stream on lstm_step_k)
 struct LstmCarry { const float* h_in[2]; float* h_out[2]; float* c[2]; };
 template <bool CARRY>
 void launch_lstm_wave(int H, const LstmWaveArgs& a, hipStream_t s) {
@@ -1055,7 +1160,7 @@ void launch_lstm_wave(int H, const LstmWaveArgs& a, hipStream_t s) {
 int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, float* out_elu, hipStream_t s, int B = 1,
              const LstmCarry* cy = nullptr) {
   const int H = L.H;
-  if (cy && (B != 1 || L.layers > 2)) return cfail(c, VC_EINVAL, "internal: a carried LSTM state is one sequence of at most two layers");
+  if (cy && L.layers > 2) return cfail(c, VC_EINVAL, "internal: a carried LSTM state has at most two layers");
   const float* in = x;
   float* seq[2] = {c->HS0, c->HS1};
   if (L.layers == 2 && H % 256 == 0 && H <= 1024 && !getenv("VC_LSTM_SEQUENTIAL")) {
@@ -1068,7 +1173,20 @@ int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, 
       const void* kern = cy ? (H == 512 ? (const void*)lstm_persist_k<2, true> : (const void*)lstm_persist_k<4, true>)
                             : (H == 512 ? (const void*)lstm_persist_k<2> : (const void*)lstm_persist_k<4>);
       const long n_wg = 2L * (H / 8);
-      if (cy && c->persist_carry_ok < 0) {   // the carried form is a kernel of its own: its own residency probe (one clip: 16 KB of LDS at most)
+      // the carried form at B > 1 needs 2 * min(B, VC_LSTM_BG) * 2 * H floats of LDS (128 KB at H = 1024, 8 streams): probed with
+      // exactly that, by clips per round, the dynamic-LDS limit raised as for the one-shot form.  Not fully resident: the wavefront
+      const int bgc = std::min(B, VC_LSTM_BG);
+      if (cy && B > 1 && c->persist_carry_b_ok[bgc] < 0) {
+        int per_cu = 0, coop = 0;
+        hipDeviceProp_t prop;
+        CCHK(c, hipGetDeviceProperties(&prop, c->device));
+        CCHK(c, hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device));
+        const size_t lds_max = (size_t)2 * VC_LSTM_BG * 2 * H * sizeof(float), lds_b = (size_t)2 * bgc * 2 * H * sizeof(float);
+        CCHK(c, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+        CCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 512, lds_b));
+        c->persist_carry_b_ok[bgc] = (coop && (long)per_cu * prop.multiProcessorCount >= n_wg) ? 1 : 0;
+      }
+      if (cy && B == 1 && c->persist_carry_ok < 0) {   // the carried form is a kernel of its own: its own residency probe (one clip: 16 KB of LDS at most)
         int per_cu = 0, coop = 0;
         hipDeviceProp_t prop;
         CCHK(c, hipGetDeviceProperties(&prop, c->device));
@@ -1086,11 +1204,12 @@ int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, 
         CCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 512, lds_max));
         c->persist_ok = (coop && (long)per_cu * prop.multiProcessorCount >= n_wg) ? 1 : 0;
       }
-      if (cy ? c->persist_carry_ok : c->persist_ok) {
+      if (cy ? (B > 1 ? c->persist_carry_b_ok[bgc] : c->persist_carry_ok) : c->persist_ok) {
         if (!c->hgran) {
           int rc2 = calloc_dev(c, &c->hgran, (size_t)2 * c->B_max * c->T_max * H);
           if (rc2) return rc2;
           CCHK(c, hipMemsetAsync(c->hgran, 0, (size_t)2 * c->B_max * c->T_max * H * 8, s));
+          c->n_queued += 1;
         }
         if (++c->lstm_epoch == 0) c->lstm_epoch = 1;
         LstmPersistArgs pa;
@@ -1107,6 +1226,7 @@ int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, 
         CCHK(c, hipEventRecord(c->ev_l[0], s));
         CCHK(c, hipLaunchCooperativeKernel(kern, dim3((unsigned)n_wg), dim3(512), kargs, (unsigned)lds, s));
         CCHK(c, hipEventRecord(c->ev_l[1], s));
+        c->n_queued += 1;
         c->persist_used = true;
         c->last_lstm_persist = 1;
         c->last_lstm_form = 2;
@@ -1116,6 +1236,7 @@ int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, 
     c->last_lstm_persist = 0;
     c->last_lstm_form = 1;
     if (!cy) CCHK(c, hipMemsetAsync(c->cstate, 0, (size_t)2 * B * H * 4, s));
+    c->n_queued += (cy ? 0 : 1) + T + 1 + (cy ? 2 : 0);
     LstmWaveArgs a;
     memset(&a, 0, sizeof a);
     a.Whh[0] = L.Whh[0]; a.Whh[1] = L.Whh[1]; a.Wih1 = L.WihP[1]; a.b1 = L.bP[1]; a.G0 = c->G;
@@ -1131,8 +1252,12 @@ int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, 
     }
     CCHK(c, hipGetLastError());
     if (cy)
-      for (int n = 0; n < 2; ++n)
-        CCHK(c, hipMemcpyAsync(cy->h_out[n], a.hs[n] + (size_t)(T - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, s));
+      for (int n = 0; n < 2; ++n) {
+        // the last step's h of every sequence: row T - 1 of each [T][H] block, one (strided) copy per layer whatever B is
+        if (B == 1) CCHK(c, hipMemcpyAsync(cy->h_out[n], a.hs[n] + (size_t)(T - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, s));
+        else CCHK(c, hipMemcpy2DAsync(cy->h_out[n], (size_t)H * 4, a.hs[n] + (size_t)(T - 1) * H, (size_t)T * H * 4, (size_t)H * 4, B,
+                                      hipMemcpyDeviceToDevice, s));
+      }
     CCHK(c, hipEventRecord(c->ev_l[1], s));
     return VC_OK;
   }
@@ -1145,6 +1270,7 @@ int run_lstm(vc_codec* c, const Lstm& L, const float* x, int T, float* out_raw, 
       if (rc) return rc;
     }
     if (!cy) CCHK(c, hipMemsetAsync(c->cstate, 0, (size_t)H * 4, s));
+    c->n_queued += 1 + T;                                  // (the memset or the h_out copy, and T steps)
     float* hs = seq[n & 1];
     const bool last = (n == L.layers - 1);
     for (int t = 0; t < T; ++t) {
@@ -1188,6 +1314,7 @@ int run_dec_back(vc_codec* c, int L, float* wav, hipStream_t s, int B) {
     const int mp = std::max(pad, pt - pad);
     hipLaunchKernelGGL(conv_last_k, dim3((L + 255) / 256, B), dim3(256), (size_t)Kw * Ci * 4, s, elu, c->dec_last.w_raw,
                        c->dec_last.bias, wav, L, Ci, Kw, pad, g.pad_reflect, (g.pad_reflect && L <= mp) ? mp + 1 : L);
+    c->n_queued += 1;
   }
   CCHK(c, hipGetLastError());
   return VC_OK;
@@ -1263,6 +1390,7 @@ extern "C" int vc_codec_create(const vc_codec_cfg* cfg, int hip_device, vc_codec
   if (e != hipSuccess) return cfail(nullptr, VC_EHIP, "hipSetDevice(%d): %s", hip_device, hipGetErrorString(e));
   vc_codec* c = new vc_codec();
   c->cfg = *cfg; c->device = hip_device;
+  for (int& v : c->persist_carry_b_ok) v = -1;
   c->hop = 1;
   for (int i = 0; i < cfg->n_ratios; ++i) c->hop *= cfg->ratios[i];
   *out = c;
@@ -1635,6 +1763,254 @@ extern "C" int vc_codec_decode_stream(vc_codec* c, const int64_t* codes_dev, int
   d.fed = F; d.proc = P; d.emitted = E; d.n_lat = keep_lat; d.n_y = keep_y;
   d.open = !last;
   *n_samples_out = ne * hop;
+  return VC_OK;
+}
+
+// ---- many decode streams on one handle, advanced together
+namespace {
+// the plan of one entry: what vc_codec_decode_stream works out for its one stream (same names, same formulas)
+struct StreamPlan {
+  int id, n, last;
+  long F, P, E;
+  int n_lat, n_y, np, ne, rows_lat, rows_y, lead, at_start, l_off, k_off, keep_lat, keep_y, e_off;
+  bool same(const StreamPlan& o) const {
+    return n == o.n && last == o.last && n_lat == o.n_lat && n_y == o.n_y && np == o.np && ne == o.ne && lead == o.lead &&
+           at_start == o.at_start && l_off == o.l_off && k_off == o.k_off && keep_lat == o.keep_lat && keep_y == o.keep_y &&
+           e_off == o.e_off;
+  }
+};
+void plan_stream(const vc_codec::DecStream& d, int id, int n, int last, StreamPlan* p) {
+  p->id = id; p->n = n; p->last = last;
+  p->F = d.fed + n;
+  p->n_lat = d.n_lat; p->n_y = d.n_y;
+  p->rows_lat = d.n_lat + n;
+  const long w0 = p->F - p->rows_lat;
+  p->P = last ? p->F : (p->F >= d.start ? std::max(d.proc, p->F - d.pr) : d.proc);
+  p->np = (int)(p->P - d.proc);
+  p->E = last ? p->F : std::max(d.emitted, p->P - d.right);
+  p->ne = (int)(p->E - d.emitted);
+  p->rows_y = d.n_y + p->np;
+  const long y0 = p->P - p->rows_y;
+  p->lead = (int)(d.proc - w0);
+  p->at_start = w0 == 0;
+  p->e_off = (int)(d.emitted - y0);
+  p->l_off = p->k_off = p->keep_lat = p->keep_y = 0;
+  if (!last) {
+    const long l0 = std::max(w0, p->P - d.pl), k0 = std::max(y0, p->E - (d.left - 1));
+    p->l_off = (int)(l0 - w0); p->k_off = (int)(k0 - y0);
+    p->keep_lat = (int)(p->F - l0); p->keep_y = (int)(p->P - k0);
+  }
+}
+}  // namespace
+
+extern "C" int vc_codec_decode_streams_open(vc_codec* c, int n) {
+  if (!c) return VC_EINVAL;
+  if (!c->finalized) return cfail(c, VC_ESTATE, "codec not finalized");
+  if (n < 1 || n > c->B_max) return cfail(c, VC_EINVAL, "vc_codec_decode_streams_open: %d streams outside [1, max_batch = %d]", n, c->B_max);
+  if (c->dec_lstm.layers > 2)
+    return cfail(c, VC_EINVAL, "the decode streams carry the state of at most 2 LSTM layers (lstm_layers = %d): use vc_codec_decode", c->dec_lstm.layers);
+  CCHK(c, hipSetDevice(c->device));
+  const int D = c->cfg.hidden, top = c->dec_lstm.H;
+  int rc;
+  if (!c->ms_c) {
+    if ((rc = calloc_dev(c, &c->ms_h_in, (size_t)2 * c->B_max * top))) return rc;
+    if ((rc = calloc_dev(c, &c->ms_h_out, (size_t)2 * c->B_max * top))) return rc;
+    if ((rc = calloc_dev(c, &c->ms_c, (size_t)2 * c->B_max * top))) return rc;
+  }
+  c->n_ms = 0;
+  while ((int)c->ms.size() < n) {
+    vc_codec::DecStream d = c->ds;             // the geometry and the capacities
+    d.lat = d.y = d.h = d.c = nullptr;
+    if ((rc = calloc_dev(c, &d.lat, (size_t)d.lat_cap * D))) return rc;
+    if ((rc = calloc_dev(c, &d.y, (size_t)d.y_cap * top))) return rc;
+    if ((rc = calloc_dev(c, &d.h, (size_t)2 * top))) return rc;
+    if ((rc = calloc_dev(c, &d.c, (size_t)2 * top))) return rc;
+    c->ms.push_back(d);
+  }
+  for (int i = 0; i < n; ++i) {
+    vc_codec::DecStream& d = c->ms[i];
+    // no device work: the first gather of a fresh stream takes zeros for (h, c) (streams_state_k), and nothing else is kept yet
+    d.fed = d.proc = d.emitted = 0;
+    d.n_lat = d.n_y = 0; d.hcur = 0;
+    d.fresh = true;
+    d.open = true;
+  }
+  c->n_ms = n;
+  return VC_OK;
+}
+
+extern "C" int vc_codec_decode_streams_reset(vc_codec* c, int id) {
+  if (!c) return VC_EINVAL;
+  if (!c->finalized) return cfail(c, VC_ESTATE, "codec not finalized");
+  if (c->n_ms < 1) return cfail(c, VC_ESTATE, "no decode streams are open (call vc_codec_decode_streams_open)");
+  if (id < 0 || id >= c->n_ms) return cfail(c, VC_EINVAL, "vc_codec_decode_streams_reset: stream %d outside [0, %d)", id, c->n_ms);
+  // host only - no memset, no synchronisation: inside a running session a wait here would be a wait for the queued decode batches.
+  // (vc_codec_decode_streams returns with nothing of the stream in flight, so its buffers are free to be taken over.)
+  vc_codec::DecStream& d = c->ms[id];
+  d.fed = d.proc = d.emitted = 0;
+  d.n_lat = d.n_y = 0;
+  d.fresh = true;
+  d.open = true;
+  return VC_OK;
+}
+
+extern "C" int vc_codec_decode_streams(vc_codec* c, int n, const int* ids, const int64_t* const* codes_dev, const int* stride,
+                                       const int* n_frames, const int* last, float* const* wav_dev, const int* wav_cap,
+                                       int* n_samples_out, void* stream) {
+  if (!c) return VC_EINVAL;
+  if (!c->finalized) return cfail(c, VC_ESTATE, "codec not finalized");
+  if (!ids || !codes_dev || !stride || !n_frames || !last || !wav_dev || !wav_cap || !n_samples_out)
+    return cfail(c, VC_EINVAL, "null argument to vc_codec_decode_streams");
+  if (c->n_ms < 1) return cfail(c, VC_ESTATE, "no decode streams are open (call vc_codec_decode_streams_open)");
+  if (n < 1 || n > c->n_ms) return cfail(c, VC_EINVAL, "vc_codec_decode_streams: %d entries outside [1, %d open streams]", n, c->n_ms);
+  const vc_codec_cfg& g = c->cfg;
+  const int D = g.hidden, top = c->dec_lstm.H, hop = c->hop;
+  // ---- every entry planned and checked before anything is queued: a refused call consumes nothing
+  std::vector<StreamPlan> plans(n);
+  for (int i = 0; i < n; ++i) {
+    const int id = ids[i];
+    if (id < 0 || id >= c->n_ms) return cfail(c, VC_EINVAL, "vc_codec_decode_streams: entry %d: stream %d outside [0, %d)", i, id, c->n_ms);
+    for (int k = 0; k < i; ++k)
+      if (ids[k] == id) return cfail(c, VC_EINVAL, "vc_codec_decode_streams: stream %d given twice", id);
+    if (n_frames[i] < 0 || (n_frames[i] > 0 && (!codes_dev[i] || stride[i] < n_frames[i])) || !wav_dev[i] || wav_cap[i] < 0)
+      return cfail(c, VC_EINVAL, "vc_codec_decode_streams: entry %d (stream %d): null/invalid codes, stride, n_frames or wav", i, id);
+    const vc_codec::DecStream& d = c->ms[id];
+    if (!d.open) return cfail(c, VC_ESTATE, "vc_codec_decode_streams: stream %d is closed (vc_codec_decode_streams_reset re-opens it)", id);
+    StreamPlan& p = plans[i];
+    plan_stream(d, id, n_frames[i], last[i] ? 1 : 0, &p);
+    if (p.rows_lat > c->T_max - 1 || p.rows_y > c->T_max - 1)
+      return cfail(c, VC_ECAP, "stream %d: chunk of %d frames (+ %d kept) exceeds the codec's capacity of %d frames per call", id, p.n,
+                   std::max(d.n_lat, d.n_y), c->T_max - 1);
+    if ((long)p.ne * hop > wav_cap[i]) return cfail(c, VC_ECAP, "stream %d: wav capacity %d < %ld", id, wav_cap[i], (long)p.ne * hop);
+    if (p.np > 0 && (p.lead > d.pl || (p.lead < d.pl && !p.at_start))) return cfail(c, VC_ESTATE, "internal: stream %d's window lost its left context", id);
+    if (p.keep_lat > d.lat_cap || p.keep_y > d.y_cap)
+      return cfail(c, VC_ESTATE, "internal: stream context %d / %d rows exceeds %d / %d", p.keep_lat, p.keep_y, d.lat_cap, d.y_cap);
+    if (p.ne > 0 && p.P - p.rows_y != 0 && p.e_off < d.left - 1) return cfail(c, VC_ESTATE, "internal: stream %d's window lost its LSTM context", id);
+  }
+  // ---- groups: entries with one plan advance as one batch where the batched LSTM exists (vc_codec_decode_batch's condition); an entry
+  // that feeds nothing and does not end changes nothing (its plan keeps every row it holds) and joins no group
+  const Lstm& L = c->dec_lstm;
+  const bool batched = L.layers == 2 && L.H % 256 == 0 && L.H <= 1024 && !getenv("VC_LSTM_SEQUENTIAL");
+  std::vector<std::vector<int>> groups;
+  for (int i = 0; i < n; ++i) {
+    if (plans[i].n == 0 && !plans[i].last) continue;
+    bool placed = false;
+    for (auto& gr : groups)
+      if (batched && plans[gr[0]].same(plans[i])) { gr.push_back(i); placed = true; break; }
+    if (!placed) groups.push_back({i});
+  }
+  CCHK(c, hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->own_stream;
+  for (int i = 0; i < n; ++i)
+    if (plans[i].n > 0 || plans[i].last) c->ms[ids[i]].open = false;       // an error below leaves them closed; success re-opens them
+  const long q0 = c->n_queued;
+  int big = 0, big_form = -1;
+  CCHK(c, hipEventRecord(c->ev[0], s));
+  int rc;
+  for (const auto& gr : groups) {
+    const int B = (int)gr.size();
+    const StreamPlan& p = plans[gr[0]];
+    const vc_codec::DecStream& d0 = c->ms[p.id];
+    StreamsTab tab;
+    memset(&tab, 0, sizeof tab);
+    for (int b = 0; b < B; ++b) {
+      const int i = gr[b];
+      const vc_codec::DecStream& d = c->ms[ids[i]];
+      tab.codes[b] = codes_dev[i]; tab.stride[b] = stride[i]; tab.wav[b] = wav_dev[i];
+      tab.lat[b] = d.lat; tab.y[b] = d.y; tab.h[b] = d.h; tab.c[b] = d.c; tab.fresh[b] = d.fresh ? 1 : 0;
+    }
+    // front half: the latent windows and the kept LSTM outputs of all B streams
+    {
+      const long tot = (long)p.rows_lat * D + (long)p.n_y * top;
+      if (tot > 0) {
+        hipLaunchKernelGGL(streams_window_k, dim3((unsigned)((tot + 255) / 256), B), dim3(256), 0, s, tab, c->E, c->latent, c->B_elu,
+                           p.n_lat, p.n, D, g.codebook_size, g.n_q, p.n_y, p.rows_y, top, c->err_flag);
+        c->n_queued += 1;
+      }
+    }
+    float* ynew = c->A_elu;                                  // the new LSTM outputs [B][np][top]: free until the back half starts
+    int form = -1;
+    if (p.np > 0) {
+      hipLaunchKernelGGL(streams_state_k, dim3((2 * top + 255) / 256, B), dim3(256), 0, s, tab, c->ms_h_in, c->ms_h_out, c->ms_c, B, top, 0);
+      c->n_queued += 1;
+      // the first conv over frames [proc, P) of every window (vc_codec_decode_stream: pad 0 at an interior left edge, run_conv's padding
+      // at the true start and, at `last`, the true end), the batch as grid.z
+      const Conv& cv = c->dec_first;
+      const int mp = std::max(d0.pl, d0.pr);
+      ConvArgs a;
+      memset(&a, 0, sizeof a);
+      a.x = c->latent; a.Wp = cv.Wp; a.bias = cv.bias; a.out_raw = c->A_raw;
+      a.L_in = p.rows_lat; a.T = p.np; a.Ci = cv.Ci; a.Co = cv.Co; a.Kw = cv.Kw;
+      a.s_in = 1; a.dil = 1; a.pad = d0.pl - p.lead; a.reflect = g.pad_reflect;
+      a.L_ext = (g.pad_reflect && p.at_start && p.rows_lat <= mp) ? mp + 1 : p.rows_lat;
+      a.s_out = 1; a.o_off = 0; a.L_dst = p.np; a.w_phase_stride = cv.phase_stride;
+      a.nphase = 1; a.x_bstride = (long)p.rows_lat * cv.Ci; a.o_bstride = (long)p.np * cv.Co;
+      hipLaunchKernelGGL(conv_gemm_k, dim3((p.np + 127) / 128, (cv.Co + 31) / 32, B), dim3(256), 0, s, a);
+      CCHK(c, hipGetLastError());
+      c->n_queued += 1;
+      LstmCarry cy;
+      for (int l = 0; l < 2; ++l) {
+        cy.h_in[l] = c->ms_h_in + (size_t)l * B * top;
+        cy.h_out[l] = c->ms_h_out + (size_t)l * B * top;
+        cy.c[l] = c->ms_c + (size_t)l * B * top;
+      }
+      if ((rc = run_lstm(c, L, c->A_raw, p.np, nullptr, ynew, s, B, &cy))) return rc;
+      form = c->last_lstm_form;
+      hipLaunchKernelGGL(streams_state_k, dim3((2 * top + 255) / 256, B), dim3(256), 0, s, tab, c->ms_h_in, c->ms_h_out, c->ms_c, B, top, 1);
+      c->n_queued += 1;
+    }
+    StreamsKeepArgs ka;
+    memset(&ka, 0, sizeof ka);
+    ka.latent = c->latent; ka.ywin = c->B_elu; ka.ynew = ynew; ka.wavwin = c->H_elu;
+    ka.rows_lat = p.rows_lat; ka.D = D; ka.rows_y = p.rows_y; ka.top = top; ka.n_y = p.n_y; ka.np = p.np;
+    ka.l_off = p.l_off; ka.keep_lat = p.keep_lat; ka.k_off = p.k_off; ka.keep_y = p.keep_y;
+    ka.win_samples = (long)p.rows_y * hop; ka.e_off = (long)p.e_off * hop; ka.n_out = (long)p.ne * hop;
+    {
+      const long tot = (long)p.np * top + (long)p.keep_lat * D + (long)p.keep_y * top;
+      if (tot > 0) {
+        ka.emit = 0;
+        hipLaunchKernelGGL(streams_keep_emit_k, dim3((unsigned)((tot + 255) / 256), B), dim3(256), 0, s, tab, ka);
+        c->n_queued += 1;
+      }
+    }
+    // back half over the windows of LSTM outputs; only each stream's frames [emitted, E) leave
+    if (p.ne > 0) {
+      if ((rc = run_dec_back(c, p.rows_y, c->H_elu, s, B))) return rc;       // (H_elu: free once the last residual unit has run)
+      ka.emit = 1;
+      hipLaunchKernelGGL(streams_keep_emit_k, dim3((unsigned)((ka.n_out + 255) / 256), B), dim3(256), 0, s, tab, ka);
+      c->n_queued += 1;
+    }
+    CCHK(c, hipGetLastError());
+    if (B > big) { big = B; big_form = form; }
+  }
+  CCHK(c, hipEventRecord(c->ev[1], s));
+  CCHK(c, hipMemcpyAsync(c->h_flag, c->err_flag, 4, hipMemcpyDeviceToHost, s));
+  c->n_queued += 1;
+  // the arenas are shared with the blocking calls: nothing of this call is in flight when it returns
+  CCHK(c, hipStreamSynchronize(s));
+  CCHK(c, hipEventElapsedTime(&c->last_ms, c->ev[0], c->ev[1]));
+  if (*c->h_flag) {
+    (void)hipMemset(c->err_flag, 0, 4);
+    return cfail(c, VC_EINVAL, "code index outside [0, %d)", g.codebook_size);
+  }
+  if ((rc = check_lstm_flag(c))) return rc;
+  for (int i = 0; i < n; ++i) {
+    const StreamPlan& p = plans[i];
+    vc_codec::DecStream& d = c->ms[ids[i]];
+    if (p.n > 0 || p.last) {
+      d.fed = p.F; d.proc = p.P; d.emitted = p.E; d.n_lat = p.keep_lat; d.n_y = p.keep_y;
+      if (p.np > 0) d.fresh = false;                        // its (h, c) are now what the recurrence left
+      d.open = !p.last;
+    }
+    n_samples_out[i] = p.ne * hop;
+  }
+  c->census[0] = (int)groups.size(); c->census[1] = big; c->census[2] = (int)(c->n_queued - q0); c->census[3] = big_form;
+  return VC_OK;
+}
+
+extern "C" int vc_codec_last_streams_census(const vc_codec* c, int out[4]) {
+  if (!c || !out) return VC_EINVAL;
+  for (int i = 0; i < 4; ++i) out[i] = c->census[i];
   return VC_OK;
 }
 

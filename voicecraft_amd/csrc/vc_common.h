@@ -481,6 +481,13 @@ struct StreamGatherArgs {   // vc_tts_stream_next: the frames of sequence 0 that
   int* host_n;              // pinned: receives n
 };
 hipError_t vc_launch_stream_gather(const StreamGatherArgs& a, hipStream_t s);
+struct SessionGatherArgs {  // vc_session_frames: entry i un-shifts frames [first[i], first[i] + count[i]) of slot[i]'s log into block i of out
+  const int* gen;           // [max_seqs][gen_stride][K]
+  int64_t* out;             // [n][K][cap], count[i] <= cap
+  int K, gen_stride, cap, n;
+  int slot[VC_MAX_SEQS], first[VC_MAX_SEQS], count[VC_MAX_SEQS];   // the host has made sure that rows first .. first + count + K - 2 are final
+};
+hipError_t vc_launch_session_gather(const SessionGatherArgs& a, hipStream_t s);
 
 // ---- training objective, teacher-forced (vc_eval_forward; VoiceCraft.forward, models/voicecraft.py:472-559)
 struct CeArgs {            // cross-entropy and top-10 membership of up to VC_ROWS logits rows against their targets

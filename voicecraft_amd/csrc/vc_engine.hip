@@ -1978,6 +1978,8 @@ struct SessReq {
   int state = 0;            // 0 pending, 1 live, 2 finished
   int total_steps = 0, span = 0, prompt_err = 0, fed = 0;
   int span_steps[VC_MAX_SPANS]{};
+  int adm_batch = -1;       // the graph batch queued by the turn that admitted it (vc_session_frames counts its final rows from there)
+  int emitted = 0;          // frames vc_session_frames has handed out
 };
 struct Session {
   DecodeLoop L{};
@@ -1988,6 +1990,7 @@ struct Session {
   int live = 0;             // admitted and not yet KNOWN to have retired
   int batch = 0;            // index of the next graph batch (never reset: the retirement stamps are unique for the session's life)
   int run_start = 0;        // first batch queued since the session was last idle: only batches from there on can be in flight
+  int known = -1;           // the newest batch vc_session_advance has seen END (what vc_session_frames may hand out hangs on this alone)
   int next_ticket = 1;
   std::deque<int> fifo;
   std::map<int, SessReq> reqs;
@@ -2185,6 +2188,7 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
     HIPCHK(e, hipEventSynchronize(e->ev_pace[t.batch & 1]));
     known = t.batch - 2;
   }
+  t.known = std::max(t.known, known);
   session_note_retired(e, t, known, tickets_out, cap, n_finished);
   session_read_timers(t, known, false);
   // ---- 3: admission, FIFO, as many as have a free slot
@@ -2201,7 +2205,7 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
     const int id = t.fifo.front();
     t.fifo.pop_front();
     SessReq& r = t.reqs[id];
-    r.slot = slot; r.state = 1;
+    r.slot = slot; r.state = 1; r.adm_batch = t.batch;
     t.slot_ticket[slot] = id;
     const int j = ta.n_new++;
     ta.seed[j] = r.seed;
@@ -2231,6 +2235,7 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
     // submit (or the fetch that frees a slot for a pending request) restarts the loop.
     if (t.batch > t.run_start) {
       HIPCHK(e, hipStreamSynchronize(s));
+      t.known = t.batch - 1;
       session_note_retired(e, t, t.batch - 1, tickets_out, cap, n_finished);
       session_read_timers(t, t.batch - 1, true);
       t.run_start = t.batch;
@@ -2323,6 +2328,74 @@ extern "C" int vc_session_fetch(vc_engine* e, int ticket, int64_t* res_dev, int 
   if (rc) return rc;
   HIPCHK(e, hipStreamSynchronize(e->side_stream));
   if (n_steps) *n_steps = r.total_steps;
+  return VC_OK;
+}
+
+namespace {
+// Frames of a TTS request the host knows to be final, from the submission schedule alone: the batches vc_session_advance has seen end
+// (t.known) and the slot's retirement record once its batch is among them - whether or not the retirement has been reported yet
+// (session_note_retired leaves a request live when tickets_out is full).  *ended: the count is the request's last.
+int session_final_frames(vc_engine* e, const Session& t, const SessReq& r, bool* ended) {
+  *ended = false;
+  if (r.state == 0 || r.adm_batch < 0 || t.known < r.adm_batch) return 0;
+  int spans = 0, s0 = 0, perr = 0;
+  if (r.state == 2) {
+    *ended = true; spans = r.span; s0 = r.span_steps[0]; perr = r.prompt_err;
+  } else {
+    volatile int* rec = e->h_rec + r.slot * VC_SESS_REC;
+    const int stamp = rec[0];
+    perr = rec[4];                                           // (written by the admitting turn's kernel, in front of batch adm_batch)
+    if (stamp != 0 && stamp - 1 <= t.known) { *ended = true; spans = rec[2]; s0 = rec[3]; }
+  }
+  if (perr & 1) return 0;                                    // an out-of-range token id in the prompt: nothing of it is handed out
+  if (*ended) return spans >= 1 ? std::max(0, s0 - e->K) : 0;      // (ran out of positions: no result, no further frames)
+  const long rows = 1 + (long)t.L.G * (t.known - r.adm_batch + 1);  // its first sample + graph_steps steps per ended batch
+  return (int)std::max(0L, std::min(rows, (long)e->gen_cap) - (e->K - 1));
+}
+}  // namespace
+
+extern "C" int vc_session_frames(vc_engine* e, int n, const int* tickets, int min_frames, int64_t* codes_dev, int cap,
+                                 int* first_frame, int* n_frames, int* done) {
+  if (!e) return VC_EINVAL;
+  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
+  Session& t = *e->sess;
+  if (t.broken) return session_broken(e, t);
+  if (!tickets || !codes_dev || !first_frame || !n_frames || !done) return fail(e, VC_EINVAL, "null argument to vc_session_frames");
+  if (n < 1 || n > t.max_live) return fail(e, VC_EINVAL, "vc_session_frames: %d tickets outside [1, max_live = %d]", n, t.max_live);
+  if (cap < 1 || min_frames < 1 || min_frames > cap)
+    return fail(e, VC_EINVAL, "vc_session_frames: min_frames %d outside [1, cap = %d]", min_frames, cap);
+  // every refusal before any cursor moves
+  for (int i = 0; i < n; ++i) {
+    auto it = t.reqs.find(tickets[i]);
+    if (it == t.reqs.end())
+      return fail(e, VC_EINVAL, "vc_session_frames: unknown ticket %d (never issued, or fetched already)", tickets[i]);
+    if (it->second.kind == 1)
+      return fail(e, VC_EINVAL, "vc_session_frames: ticket %d: editing requests do not stream (their rows per batch hang on span "
+                  "switches known at retirement only, and their result is a splice)", tickets[i]);
+    for (int k = 0; k < i; ++k)
+      if (tickets[k] == tickets[i]) return fail(e, VC_EINVAL, "vc_session_frames: ticket %d given twice", tickets[i]);
+  }
+  SessionGatherArgs a;
+  memset(&a, 0, sizeof a);
+  a.gen = e->gen; a.out = codes_dev; a.K = e->K; a.gen_stride = e->gen_cap; a.cap = cap; a.n = n;
+  int any = 0;
+  for (int i = 0; i < n; ++i) {
+    const SessReq& r = t.reqs[tickets[i]];
+    bool ended = false;
+    const int avail = session_final_frames(e, t, r, &ended) - r.emitted;
+    const int cnt = (avail >= min_frames || (ended && avail > 0)) ? std::min(avail, cap) : 0;
+    a.slot[i] = std::max(0, r.slot); a.first[i] = r.emitted; a.count[i] = cnt;
+    first_frame[i] = r.emitted; n_frames[i] = cnt;
+    done[i] = (ended && avail - cnt <= 0) ? 1 : 0;
+    any += cnt;
+  }
+  if (any > 0) {
+    // on the side stream, and that stream alone is waited for: the rows read are final, the decode stream's queued batches are not touched
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, vc_launch_session_gather(a, e->side_stream));
+    HIPCHK(e, hipStreamSynchronize(e->side_stream));
+  }
+  for (int i = 0; i < n; ++i) t.reqs[tickets[i]].emitted += n_frames[i];
   return VC_OK;
 }
 

@@ -1160,6 +1160,28 @@ hipError_t vc_launch_stream_gather(const StreamGatherArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(stream_gather_k, dim3(1), dim3(256), 0, s, a);
   return hipGetLastError();
 }
+// The frames of up to VC_MAX_SEQS session tickets in one launch, one workgroup per ticket: out[i][j][t] = gen[slot][first + j + t][j].
+// Every count comes from the host (what it knows to be final, vc_engine.hip vc_session_frames): no state is read, nothing is reported
+// back.  Consecutive lanes store consecutive t.
+__global__ __launch_bounds__(256) void session_gather_k(const SessionGatherArgs a) {
+  const int i = blockIdx.x;
+  const int n = a.count[i], first = a.first[i];
+  if (n <= 0) return;
+  const int* gen = a.gen + (long)a.slot[i] * a.gen_stride * a.K;
+  int64_t* out = a.out + (long)i * a.K * a.cap;
+  for (int idx = threadIdx.x; idx < a.K * n; idx += blockDim.x) {
+    const int j = idx / n, t = idx - j * n;
+    out[(long)j * a.cap + t] = (int64_t)gen[(long)(first + j + t) * a.K + j];
+  }
+}
+hipError_t vc_launch_session_gather(const SessionGatherArgs& a, hipStream_t s) {
+  if (a.n < 1 || a.n > VC_MAX_SEQS || a.K < 1 || a.cap < 1) return hipErrorInvalidValue;
+  for (int i = 0; i < a.n; ++i)     // (a logic error of the caller must not become a store outside block i or a load outside the slot's log)
+    if (a.slot[i] < 0 || a.first[i] < 0 || a.count[i] < 0 || a.count[i] > a.cap || a.first[i] + a.count[i] + a.K - 1 > a.gen_stride)
+      return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_gather_k, dim3(a.n), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
 hipError_t vc_launch_assemble(const AssembleArgs& a, hipStream_t s) {
   if (a.n_piece <= 0) return hipSuccess;
   hipLaunchKernelGGL(assemble_k, dim3(8, a.n_piece), dim3(256), 0, s, a);

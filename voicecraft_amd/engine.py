@@ -705,8 +705,9 @@ class SessionRequestError(EngineError):
 class DecodeSession:
     """An open decode session of a VoiceCraftEngine (VoiceCraftEngine.open_session).  submit() queues a TTS request, submit_edit()
     an editing request; both return a ticket.  poll() runs one turn of the decode loop and returns the requests that finished;
-    drain() polls until the session is idle.  While a session is open the engine's other decode calls and set_option raise
-    (EngineError, VC_ESTATE)."""
+    drain() polls until the session is idle.  submit(..., stream=True) marks a TTS request as streaming: poll_frames() hands out its
+    frames while it decodes, without advancing the loop (voicecraft_amd.stream.SessionStreamer turns them into audio).  While a
+    session is open the engine's other decode calls and set_option raise (EngineError, VC_ESTATE)."""
 
     CONTROLS = ("top_k", "top_p", "temperature", "stop_repetition")
 
@@ -719,6 +720,9 @@ class DecodeSession:
                                               # (M: spans of an editing request, 0 = TTS)
         self._sc = sc                         # the session's controls: the default of each field a request does not give
         self._ready: list = []                # (ticket, res, gen) fetched and not yet handed out
+        self._streaming: set[int] = set()     # streaming TTS tickets whose last frame has not been pulled (submit(stream=True))
+        self._tail: list = []                 # (ticket, first_frame, codes, True): what a finished streaming ticket still had, pulled
+                                              # in front of its fetch and handed out by the next poll_frames
         self.idle = True
         # uploads and result arithmetic run on a stream of the session's own: a launch on the null stream would wait for the decode
         # batches queued on the engine's stream (as in _tts_stream)
@@ -761,9 +765,11 @@ class DecodeSession:
         self._side.synchronize()                 # the prompt is on the device before the prefill that reads it can be queued
         return xd, Lx, yd, T
 
-    def submit(self, x, x_lens, y, seed=None, **controls) -> int:
+    def submit(self, x, x_lens, y, seed=None, stream: bool = False, **controls) -> int:
         """A TTS request: x [1,Lx'], x_lens [1], y [1,T,K] as inference_tts takes them (same checks, same special_first handling).
-        controls: any of top_k, top_p, temperature, stop_repetition for this request alone; the others are the session's."""
+        controls: any of top_k, top_p, temperature, stop_repetition for this request alone; the others are the session's.
+        stream=True: the request's frames are handed out by poll_frames() while it decodes (editing requests do not stream:
+        submit_edit has no such argument); poll() / drain() return its (ticket, res, gen) as for any other."""
         assert self._open, "the session is closed"
         eng = self.engine
         ctl = self._ctl("submit", controls)
@@ -774,6 +780,8 @@ class DecodeSession:
                                             C.byref(ctl) if ctl is not None else None, sd, C.byref(ticket)),
               eng._h, "vc_session_submit")
         self._reqs[ticket.value] = (xd, yd, T, Lx, 0)
+        if stream:
+            self._streaming.add(ticket.value)
         self.idle = False
         return ticket.value
 
@@ -848,12 +856,76 @@ class DecodeSession:
         failed = {}
         for i in range(n.value):
             t = int(tickets[i])
+            if t in self._streaming:             # what it still has, in front of the fetch that frees its slot: a slow consumer never holds one
+                self._tail.append(self._pull_rest(t))
             try:
                 self._ready.append((t,) + self.fetch(t))
             except (EngineError, AssertionError) as ex:
                 failed[t] = ex
         if failed:
             raise SessionRequestError(failed)
+
+    FRAMES_CAP = 64      # frames per ticket one vc_session_frames call can hand out (what is left comes with the next call)
+
+    def _frames(self, tickets, min_frames: int):
+        """One vc_session_frames call: [(ticket, first_frame, codes [1,K,m], done)] of the tickets that got frames or are done."""
+        eng = self.engine
+        K, n = eng.args.n_codebooks, len(tickets)
+        cap = max(int(min_frames), self.FRAMES_CAP)
+        buf = torch.empty((n, K, cap), dtype=torch.int64, device=eng.device)
+        arr = (C.c_int * n)(*tickets)
+        first, cnt, done = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        check(eng.lib.vc_session_frames(eng._h, n, arr, int(min_frames), C.c_void_p(buf.data_ptr()), cap, first, cnt, done),
+              eng._h, "vc_session_frames")
+        out = [(int(tickets[i]), int(first[i]), buf[i: i + 1, :, : cnt[i]], bool(done[i])) for i in range(n) if cnt[i] or done[i]]
+        if eng.args.special_first and any(c.shape[2] for _, _, c, _ in out):
+            # not on the null stream: a launch there would wait for the decode batches queued on the engine's stream (as in _tts_stream)
+            with torch.cuda.stream(self._side):
+                out = [(t, f, c - int(eng.args.n_special), d) for t, f, c, d in out]
+            self._side.synchronize()
+        return out
+
+    def _pull_rest(self, ticket: int):
+        """Everything a finished streaming ticket has not handed out yet, as one last chunk."""
+        parts, first = [], None
+        while True:
+            got = self._frames([ticket], 1)
+            assert len(got) <= 1
+            for _, f, c, d in got:
+                first = f if first is None else first
+                parts.append(c)
+            if got and got[0][3]:
+                break
+            assert got, f"ticket {ticket}: reported finished, but its frames are not final"
+        self._streaming.discard(ticket)
+        if len(parts) > 1:
+            with torch.cuda.stream(self._side):
+                codes = torch.cat(parts, dim=2)
+            self._side.synchronize()
+        else:
+            codes = parts[0]
+        return ticket, first, codes, True
+
+    @torch.no_grad()
+    def poll_frames(self, chunk_frames: int = 8):
+        """The new frames of the streaming tickets (submit(stream=True)), without advancing the decode loop: a list of (ticket,
+        first_frame, codes [1,K,m], done).  Per ticket the chunks are contiguous from frame 0, each of at least `chunk_frames` frames
+        except the last, and their concatenation is the `gen` its poll() / drain() entry holds; done comes with the last chunk
+        (possibly of 0 frames; at once for a request that ended without a result).  One vc_session_frames call covers every streaming
+        ticket that can be holding a slot; what a ticket finished by an earlier poll() still had comes first."""
+        assert self._open, "the session is closed"
+        assert int(chunk_frames) >= 1, chunk_frames
+        out, self._tail = self._tail, []
+        # admission is FIFO and a slot is held until its ticket is fetched: only the first max_live unfetched tickets can hold one
+        holders = list(self._reqs)[: self.max_live]
+        tickets = [t for t in holders if t in self._streaming]
+        if tickets:
+            got = self._frames(tickets, int(chunk_frames))
+            for t, f, c, d in got:
+                if d:
+                    self._streaming.discard(t)
+            out += got
+        return out
 
     def _hand_out(self):
         out, self._ready = self._ready, []
@@ -892,6 +964,8 @@ class DecodeSession:
         finally:
             self._reqs.clear()          # the prompts stay valid until the decode stream has been waited for
             self._ready = []
+            self._streaming.clear()
+            self._tail = []
 
 
 def inference_tts_queue(engine: VoiceCraftEngine, xs, ys, max_live: int | None = None, seeds=None, **sampling):
