@@ -130,10 +130,17 @@ const char* vc_version(void);
  *   "shrink"       1 (default) = a multi-utterance call re-packs its live sequences onto the rows of a narrower step (next power of two) as the
  *                  others retire; 0 = the step keeps its starting width until the longest sequence ends (rounds 1-5)
  *   "graph_steps"  decode steps captured per hipGraph;  "prefill_rows"  rows per prefill pass (16: decode kernels only)
+ *   "w13"          mask (default 5): ONE-row steps of a bf16 engine stream the FFN down-projection (1) and the QKV projection (4) as exact
+ *                  13-bit planes of the same bf16 values (low byte, 4-bit exponent code, sign; one base byte per 512-value MFMA fragment:
+ *                  13/16 of the bytes, every result bit-identical); any other bit: VC_EINVAL.  Planes are packed at creation unless
+ *                  VC_W13=0 (+ 0.81 x the two images); a width whose wave shares are not whole groups of four fragments (FFN-down below
+ *                  d = 512, QKV below d = 1024), an fp32 engine, and a matrix of a layer with a fragment whose non-zero exponents span more
+ *                  than 30 binades keep the bf16 launch (vc_debug_read "w13_stats": int32 [layer][FFN-down, QKV][state 0 n/a / 1 packed /
+ *                  2 refused, fragments refused])
  * What an option may change: nothing in the exact fp32 mode's greedy tokens (tests/test_gpu_options.py, test_gpu_one_row.py); in bf16
  * mode the forms that re-order sums or round at another place ("finished_rows", "fr_pair", "att_p16", "hq", "fr_one", "qkv_p8", "attn_fast",
  * "qkv16", "wide_heads", "wide_gemm") move head logits by bf16 rounding (tests allow 0.25 absolute), so top-k SAMPLED tokens can differ between option
- * states; the cache-policy / data-path / host-side options ("nt", "wd_stage", "graph_steps", "shrink") change no value.
+ * states; the cache-policy / data-path / host-side options ("nt", "wd_stage", "graph_steps", "shrink", "w13") change no value.
  * The non-temporal mask "nt" has no bit for the finished-row producers (rows_gemm_fr_k, rows_gemm_fr2_k, row_gemm_fr1_k) and the
  * wide-decode kernels: they always stream with the hint.  Captured decode graphs are kept per option state and step width, so an
  * in-process A/B (bench.py --ab) pays for capture once per state.  Unknown names / malformed values: VC_EINVAL.

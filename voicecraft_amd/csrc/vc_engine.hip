@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "vc_common.h"
+#include "vc_w13.h"
 
 namespace {
 
@@ -39,7 +40,13 @@ struct Layer {
   float bo_mean = 0.f, b2_mean = 0.f;   // mean over the d channels of bo / b2: what the update moves a row's mean by whatever its input (GemmArgs.mu_shift)
   float *wg_qkv = nullptr, *wg_1 = nullptr;                             // row sums of the folded weights W . gamma
   void *kc = nullptr, *vc = nullptr;   // KV cache of this layer: WT [max_seqs][H][S_max][hd]
+  // W28 / Wqkv8 once more as exact 13-bit planes (option "w13", vc_w13.h): index W13_F2 / W13_QKV
+  uint4* w13_planes[2] = {nullptr, nullptr};
+  uint32_t* w13_side[2] = {nullptr, nullptr};               // one byte per fragment
+  int w13_state[2] = {0, 0};                                // 0 not applicable (or not packed), 1 packed, 2 refused: the launch stays on the bf16 image
+  int w13_refused[2] = {0, 0};                              // fragments the packer refused
 };
+enum { W13_F2 = 0, W13_QKV = 1 };
 
 struct Plan { int n_tiles, KT, ksplit, nchunk; };
 
@@ -159,6 +166,13 @@ struct vc_engine {
   int shrink = 1;
   // weight images vc_finalize_weights packed: Layer.Wo8 / W28, Layer.Wqkv8, Layer.Wqkv16 (the forms that read one, plan_pass)
   bool has_fr8 = false, has_qkv8 = false, has_qkv16 = false;
+  // option "w13": one-row steps stream the FFN down-projection (1) and the QKV projection (4) as exact 13-bit planes of the same bf16
+  // values (vc_gemm_w13.hip: 13/16 of the bytes, results bit-identical).  bf16 engines; planes packed at creation unless VC_W13=0
+  // (+ 0.81 x the two images: 0.76 GB at giga830M); a matrix the packer refuses keeps its bf16 launch.  (Bit 2, the FFN up-projection, was
+  // built and measured +0.1 % +- 0.03 per step: it left the tree with its kernel)
+  int w13 = 5;
+  bool has_w13 = false;
+  unsigned int* w13_counts = nullptr;   // two device words of the packer: fragments refused, dwords that did not decode to the image
   int cur_rows = 0;                     // rows per step the last decode loop ended on (tts_run reads the states back accordingly)
   // option "attn_fast": decode attention with the wave's maximum taken before any exponential (no online rescaling inside a wave) and,
   // in bf16 mode, hardware exp2 (v_exp_f32) instead of expf
@@ -296,6 +310,28 @@ int pack_folded(vc_engine* e, const std::string& wkey, const std::string& bkey, 
   if ((rc = dalloc(e, wg, (size_t)N))) return rc;
   if ((rc = dalloc(e, cb, (size_t)N))) return rc;
   HIPCHK(e, vc_launch_fold_vecs(tw->dev, tg->dev, tbe->dev, tb->dev, *wg, *cb, N, Kdim, e->dtype, 0));
+  return VC_OK;
+}
+
+// The 13-bit planes of an already packed bf16 image of `n_frags` 1 KB fragments (vc_w13.h): packed and checked on the device.  A
+// fragment whose non-zero exponents span more than the codes hold, or any dword that does not decode to the image's, refuses the matrix
+// (state 2: the planes are dropped, the launch stays on the image).
+int pack_w13(vc_engine* e, Layer& ly, int which, const uint4* image, long n_frags) {
+  if (!e->w13_counts) { int rc = dalloc(e, &e->w13_counts, (size_t)4); if (rc) return rc; }
+  const size_t mark = e->allocs.size();
+  const double bytes0 = e->bytes_total;
+  int rc;
+  if ((rc = dalloc(e, &ly.w13_planes[which], (size_t)(n_frags / VC_W13_GROUP_FRAGS) * VC_W13_GROUP_U4))) return rc;
+  if ((rc = dalloc(e, &ly.w13_side[which], (size_t)(n_frags / 4)))) return rc;
+  HIPCHK(e, vc_launch_w13_pack(image, n_frags, ly.w13_planes[which], reinterpret_cast<unsigned char*>(ly.w13_side[which]), e->w13_counts, 0));
+  unsigned int cnt[2] = {0, 0};
+  HIPCHK(e, hipMemcpy(cnt, e->w13_counts, sizeof cnt, hipMemcpyDeviceToHost));
+  ly.w13_refused[which] = (int)cnt[0];
+  if (cnt[0] == 0 && cnt[1] == 0) { ly.w13_state[which] = 1; return VC_OK; }
+  ly.w13_state[which] = 2;
+  while (e->allocs.size() > mark) { (void)hipFree(e->allocs.back()); e->allocs.pop_back(); }
+  e->bytes_total = bytes0;
+  ly.w13_planes[which] = nullptr; ly.w13_side[which] = nullptr;
   return VC_OK;
 }
 
@@ -527,7 +563,8 @@ int site_qkv(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly,
   set_resid(e, g, r);
   if (p.qkv_fr1) {         // the row entering the layer is finished (layer 0: the sampler's dec_h row): 8-channel tiles, two k-tiles per fragment
     g.Wp = ly.Wqkv8;
-    HIPCHK(e, vc_launch_gemm_fr1(g, e->dtype, PRO_LN, EPI_QKV, s));
+    if ((e->w13 & 4) && ly.w13_state[W13_QKV] == 1) HIPCHK(e, vc_launch_gemm_fr1_w13(g, ly.w13_planes[W13_QKV], ly.w13_side[W13_QKV], PRO_LN, EPI_QKV, s));
+    else HIPCHK(e, vc_launch_gemm_fr1(g, e->dtype, PRO_LN, EPI_QKV, s));
   } else if (!p.ln_launch) {
     HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LN, EPI_QKV, 1, 1, s));
   } else if (p.qkv16) {    // every A lane a weight: the 16-channel image
@@ -627,7 +664,8 @@ int site_ffn_down(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer
     g.Wp = ly.W28; g.bias = ly.b2;
     g.h_in = e->hA; g.h_out = e->hB;
     if (p.hq) { g.hq_out = e->hqB; g.row_mu = e->row_mu[0]; g.mu_shift = ly.b2_mean; }      // centred on the mean the FFN-up consumer found for h' + the mean of b2
-    if (p.fd) HIPCHK(e, vc_launch_gemm_fr1(g, e->dtype, PRO_PLAIN, EPI_RES, s));
+    if (p.fd && (e->w13 & 1) && ly.w13_state[W13_F2] == 1) HIPCHK(e, vc_launch_gemm_fr1_w13(g, ly.w13_planes[W13_F2], ly.w13_side[W13_F2], PRO_PLAIN, EPI_RES, s));
+    else if (p.fd) HIPCHK(e, vc_launch_gemm_fr1(g, e->dtype, PRO_PLAIN, EPI_RES, s));
     else if (p.frp) HIPCHK(e, vc_launch_gemm_frp(g, e->dtype, s));      // 2..8 rows: two k-tiles per fragment
     else HIPCHK(e, vc_launch_gemm_fr(g, e->dtype, PRO_PLAIN, s));
     return VC_OK;
@@ -1095,6 +1133,9 @@ int apply_option(vc_engine* e, const std::string& name, const char* value) {
     if (v0 && !e->has_qkv16)
       return fail(e, VC_ESTATE, "option 'qkv16': this engine holds no 16-channel image of the QKV matrix (packed for max_seqs > 16, or with VC_QKV16=1 at creation)");
     e->qkv16 = v0 ? 1 : 0;
+  } else if (name == "w13") {      // mask: 1 FFN-down, 4 QKV; a matrix without planes (fp32, narrow, refused, VC_W13=0) keeps its bf16 launch
+    if (v0 < 0 || (v0 & ~5)) return fail(e, VC_EINVAL, "option 'w13': %d is not a mask of 1 (FFN-down) and 4 (QKV)", v0);
+    e->w13 = v0;
   } else if (name == "attn_fast") { e->attn_fast = v0 ? 1 : 0;
   } else if (name == "att_p16") { e->att_p16 = v0 ? 1 : 0;
   } else if (name == "hq") { e->hq = v0 ? 1 : 0;
@@ -1110,9 +1151,9 @@ int apply_option(vc_engine* e, const std::string& name, const char* value) {
 
 void refresh_opt_state(vc_engine* e) {
   char buf[256];
-  snprintf(buf, sizeof buf, "g=%d|nt=%d,%d|fr=%d,%d,%d,%d|ta=%d,%d|r1=%d,%d,%d|q16=%d,%d,%d,%d|sh=%d",
+  snprintf(buf, sizeof buf, "g=%d|nt=%d,%d|fr=%d,%d,%d,%d|ta=%d,%d|r1=%d,%d,%d|q16=%d,%d,%d,%d|sh=%d|w13=%d",
            e->steps_per_graph, e->nt_decode, e->attn_nt, e->fr_rows, e->fr_pair, e->att_p16, e->hq, e->tile_attn, e->tile_attn_min_rows,
-           e->fr_one, e->attn_fast, e->qkv_p8, e->qkv16, e->wide_heads, e->wide_gemm, e->wd_stage, e->shrink);
+           e->fr_one, e->attn_fast, e->qkv_p8, e->qkv16, e->wide_heads, e->wide_gemm, e->wd_stage, e->shrink, e->w13);
   e->opt_state = buf;
 }
 
@@ -1304,6 +1345,8 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
   e->has_fr8 = want_fr8;
   e->has_qkv8 = want_fr8 && want_p8 && vc_gemm_fr1_ok(3 * d, d, e->dtype, 4);
   e->has_qkv16 = want_qkv16;
+  const char* env_w13 = getenv("VC_W13");
+  e->has_w13 = e->dtype == VC_DTYPE_BF16 && !(env_w13 && atoi(env_w13) == 0);
   e->layers.resize(L);
   for (int l = 0; l < L; ++l) {
     const std::string pre = "decoder.layers." + std::to_string(l) + ".";
@@ -1335,6 +1378,12 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
       }
     }
     if ((rc = keep_vec(e, pre + "linear2.bias", d, &ly.b2, &ly.b2_mean))) return rc;
+    // two of the big matrices of a one-row step once more as 13-bit planes, where a wave's share is whole groups of four fragments
+    // (vc_gemm_w13_fr1_ng: FFN-down from d = 512, QKV from d = 1024)
+    if (e->has_w13) {
+      if (ly.W28 && vc_gemm_w13_fr1_ng(d, 4 * d, e->dtype, VC_FR_WAVES) && (rc = pack_w13(e, ly, W13_F2, ly.W28, (long)(d / VC_TH_RES) * (4 * d / 64)))) return rc;
+      if (ly.Wqkv8 && vc_gemm_w13_fr1_ng(3 * d, d, e->dtype, 4) && (rc = pack_w13(e, ly, W13_QKV, ly.Wqkv8, (long)(3 * d / VC_TH_RES) * (d / 64)))) return rc;
+    }
     const size_t cache_bytes = (size_t)e->B_max * e->H * e->S_max * e->hd * e->esz;
     char* kc; char* vc;
     if ((rc = dalloc(e, &kc, cache_bytes))) return rc;
@@ -1488,7 +1537,7 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
                          
                          std::make_pair("VC_FINISHED_ROWS", "finished_rows"),
                          std::make_pair("VC_TILE_ATTN", "tile_attn"),
-                         std::make_pair("VC_FR_ONE", "fr_one"), std::make_pair("VC_QKV_P8", "qkv_p8"), std::make_pair("VC_FR_PAIR", "fr_pair"), std::make_pair("VC_QKV16", "qkv16"), std::make_pair("VC_WIDE_HEADS", "wide_heads"), std::make_pair("VC_WIDE_GEMM", "wide_gemm"), std::make_pair("VC_WD_STAGE", "wd_stage"), std::make_pair("VC_SHRINK", "shrink"), std::make_pair("VC_ATTN_FAST", "attn_fast"), std::make_pair("VC_ATT_P16", "att_p16"), std::make_pair("VC_HQ", "hq")})
+                         std::make_pair("VC_FR_ONE", "fr_one"), std::make_pair("VC_QKV_P8", "qkv_p8"), std::make_pair("VC_FR_PAIR", "fr_pair"), std::make_pair("VC_QKV16", "qkv16"), std::make_pair("VC_WIDE_HEADS", "wide_heads"), std::make_pair("VC_WIDE_GEMM", "wide_gemm"), std::make_pair("VC_WD_STAGE", "wd_stage"), std::make_pair("VC_SHRINK", "shrink"), std::make_pair("VC_ATTN_FAST", "attn_fast"), std::make_pair("VC_ATT_P16", "att_p16"), std::make_pair("VC_HQ", "hq"), std::make_pair("VC_W13", "w13")})
     if (const char* v = getenv(kv.first)) {
       // (VC_NT was a boolean through round 3 - 1 = on, the default; it is a per-matrix bit mask now: the legacy "1" keeps meaning "on")
       if (std::string(kv.first) == "VC_NT" && std::string(v) == "1") v = "63";
@@ -2844,6 +2893,14 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
   else if (n == "options") {        // the option state as text (vc_set_option), NUL-padded
     memset(host_dst, 0, (size_t)nbytes);
     memcpy(host_dst, e->opt_state.c_str(), std::min<size_t>((size_t)nbytes > 0 ? (size_t)nbytes - 1 : 0, e->opt_state.size()));
+    return VC_OK;
+  }
+  else if (n == "w13_stats") {      // int32 [layer][FFN-down, QKV][state (0 not applicable, 1 packed, 2 refused), fragments refused]
+    std::vector<int32_t> v;
+    for (const Layer& ly : e->layers)
+      for (int w = 0; w < 2; ++w) { v.push_back(ly.w13_state[w]); v.push_back(ly.w13_refused[w]); }
+    if (nbytes > (int64_t)(v.size() * 4)) return fail(e, VC_ECAP, "debug buffer 'w13_stats' holds %lld bytes", (long long)(v.size() * 4));
+    memcpy(host_dst, v.data(), (size_t)nbytes);
     return VC_OK;
   }
   else if (n == "launch_counts") { host_src = vc_launch_counts; avail = VC_LC_N * 8; }     // process-wide census of kernel forms (vc_common.h)

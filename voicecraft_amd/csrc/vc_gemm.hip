@@ -1048,6 +1048,8 @@ hipError_t vc_launch_gemm_fr(const GemmArgs& a0, int dtype, int pro, hipStream_t
 // at every cold launch start: its first workgroup had the burst out after 2 000 clk instead of 2 756, and the step came out
 // +0.84 % +- 0.44 at giga830M, +0.21 % +- 0.06 at giga330M in in-process A/Bs, profiles/r05g_ab_*.log.  Not carried: the FFN-up
 // launch is bound by its stream, not by its prologue.)
+// (TWIN: row_gemm_fr1_w13_k in vc_gemm_w13.hip is this kernel's bf16 EXACT form on 13-bit weight planes: a change to the prologue, reduction
+// or epilogue here has to be made there too - tests/test_gpu_w13.py holds the two bit-identical.)
 template <typename WT, int NPW, bool EXACT, int NW, int PRO, int EPI>
 __global__ __launch_bounds__(64 * NW) void row_gemm_fr1_k(const GemmArgs a) {
   using T = WTr<WT>;

@@ -660,8 +660,9 @@ class VoiceCraftEngine:
     def options(self) -> str:
         """The engine's option state as text, `key=v,v,...|key=...`: g = graph_steps, nt = (weight mask, K/V loads), fr = finished-row
         forms (finished_rows, fr_pair, att_p16, hq), ta = tile_attn (kernel, min rows), r1 = one-row and attention forms (fr_one,
-        attn_fast, qkv_p8), q16 = many-row steps (qkv16, wide_heads, wide_gemm, wd_stage), sh = shrink.  bench.py turns it into a JSON
-        object (`config.engine_options`)."""
+        attn_fast, qkv_p8), q16 = many-row steps (qkv16, wide_heads, wide_gemm, wd_stage), sh = shrink, w13 = the one-row launches that
+        stream their weights as exact 13-bit planes (mask: 1 FFN-down, 4 QKV; w13_stats() says which matrices have planes).
+        bench.py turns it into a JSON object (`config.engine_options`)."""
         return bytes(self.debug_read("options", (256,), torch.uint8).tolist()).split(b"\0")[0].decode()
 
     def last_timing_ms(self):
@@ -676,13 +677,25 @@ class VoiceCraftEngine:
         return ms.value, nbytes.value
 
     LAUNCH_FORMS = ("rows_gemm", "mt2", "mt4", "blk64", "blk128_sbs", "blk128_2x2", "blk64_occ2", "ln_rows", "rows_attn",
-                    "tile_attn", "rows_gemm_fr", "big256", "big128", "row_gemm_fr1", "tile_attn64", "rows_gemm_frp", "wd", "rows_gemm_qp")
+                    "tile_attn", "rows_gemm_fr", "big256", "big128", "row_gemm_fr1", "tile_attn64", "rows_gemm_frp", "wd", "rows_gemm_qp", "w13")
 
     def launch_counts(self) -> dict:
         """Process-wide census of the kernel FORMS launched so far (vc_common.h VC_LC_*): the parity tests take the
         difference around a call to assert which form a benchmarked shape really runs on."""
         c = self.debug_read("launch_counts", (len(self.LAUNCH_FORMS),), torch.int64)
         return {n: int(c[i]) for i, n in enumerate(self.LAUNCH_FORMS)}
+
+    W13_MATRICES = ("ffn_down", "qkv")
+    W13_STATES = ("not_applicable", "packed", "refused")
+
+    def w13_stats(self) -> list:
+        """Per layer, for the matrices of option `w13` (mask bits 1 and 4 in this order): {"state": "packed" | "refused" |
+        "not_applicable", "refused_fragments": n}.  A refused matrix holds a 512-value fragment whose non-zero exponents span more than
+        30 binades; its launches stay on the bf16 image.  not_applicable: fp32 engine, a width without the form, or VC_W13=0."""
+        L = int(self.args.num_decoder_layers)
+        v = self.debug_read("w13_stats", (L, 2, 2), torch.int32).tolist()
+        return [{m: {"state": self.W13_STATES[v[l][i][0]], "refused_fragments": v[l][i][1]} for i, m in enumerate(self.W13_MATRICES)}
+                for l in range(L)]
 
     def debug_read(self, name: str, shape, dtype=torch.float32) -> torch.Tensor:
         out = torch.empty(shape, dtype=dtype)
