@@ -67,6 +67,16 @@ def test_editing_prompt_and_a_ragged_batch_with_a_shared_prefix(model):
         assert rel_l2(got[2][0, u][None], tr[0]["logits"][0].numpy()[None]).max() <= 2e-2, u
     pre = torch.arange(10, dtype=torch.int64) % 7
     xs2 = [torch.cat([pre, v]) for v in xs]
+    # a stale call of the same shapes on other text first: every slot's own cache then holds foreign K/V below the prefix, so a
+    # boundary that is one too low reads wrong rows instead of the right ones a call without sharing left there
+    a_text = int(a.text_vocab_size)
+    K = a.n_codebooks
+    ends = np.zeros((1 + K, len(xs2), K), dtype=np.int64)          # forced: one frame, then the staggered terminator - the call is 5 steps long
+    for j in range(K):
+        ends[1 + j, :, :j] = a.empty_token
+        ends[1 + j, :, j] = a.eos
+    eng.inference_tts_multi([(v + 1 + torch.arange(v.numel()) % (a_text - 1)) % a_text for v in xs2], ys, top_k=1, stop_repetition=3,
+                            _forced=ends, _seed=3)
     got = both(eng, lambda: eng.inference_tts_multi(xs2, ys, top_k=1, stop_repetition=3, _logit_steps=1, _seed=3, _shared_text_prefix=10)[1].cpu().numpy())
     assert rel_l2(got[2][0], got[1][0]).max() <= 1e-2, rel_l2(got[2][0], got[1][0])
 
