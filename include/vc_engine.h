@@ -362,7 +362,9 @@ int vc_edit_multi(vc_engine* e, int B, const int64_t* x_dev, const int32_t* x_of
  *   (the utterance's emb_inds_use, :270-273)
  *   out (host): nll_sum double [K] = sum of -log softmax(logits)[target]; hits int64 [K]; n_targets int64 (per codebook)
  *   nll_dev optional device float [nll_cap][K]: the per-row terms in the engine's row order (parity hook), with
- *   tgt_dev int32 [nll_cap][K] (>= 0 index into y_dev, -1 none, <= -2 constant token -(v+2)); n_rows_out = rows written */
+ *   tgt_dev int32 [nll_cap][K] (>= 0 index into y_dev, -1 none, <= -2 constant token -(v+2)); n_rows_out = rows written.
+ *   With the hook the engine also keeps the head logits of every row of the call, fp32 [rows][K][V] in the same row order
+ *   (vc_debug_read "eval_logits"; a device buffer allocated by the first such call).  Without it nothing is allocated or copied. */
 int vc_eval_forward(vc_engine* e, int B, const int64_t* x_dev, const int32_t* x_off,
                     const int64_t* y_dev, const int32_t* y_off,
                     const int32_t* spans, const int32_t* span_off, const int32_t* mask_values,
@@ -409,7 +411,8 @@ int vc_box_probe(long long bytes, int hops, float res[2], void* stream);
  * (1) or falls back to rows_gemm_mt_k (0); out[12] / out[13] its K slices for the out-projection / FFN down-projection; out[14] /
  * out[15] its k-tiles per wave for K = d / K = head_hidden.  tests/test_plan_cpu.py walks every model width with it. */
 int vc_debug_plan(const vc_model_cfg* cfg, int compute_dtype, int rows, int32_t out[16]);
-/* Copies a named internal device buffer to host memory. */
+/* Copies a named internal device buffer to host memory.  "kcache<l>" / "vcache<l>": layer l's K / V cache, [max_seqs][H][max_positions][hd]
+ * in the compute dtype; "eval_logits": see vc_eval_forward. */
 int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int64_t nbytes);
 /* Timing of the last vc_tts/vc_edit call, measured with HIP events on `stream`:
  * ms[0] = prompt build + prefill, ms[1] = decode loop, ms[2] = their sum.  The FIRST call of a shape / option state captures and

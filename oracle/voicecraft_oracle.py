@@ -561,7 +561,8 @@ class VoiceCraftOracle:
                 "_per_token_logits": lg, "_targets": tg,
                 # test hooks: per sample, the concatenated columns [K,S_i], {placeholder column: mask_embedding row} and
                 # the per-piece targets
-                "_cols": cols, "_mask_pos": mask_pos, "_targets_per_sample": targets}
+                "_cols": cols, "_mask_pos": mask_pos, "_targets_per_sample": targets,
+                "_logits_cols": logits}                                      # head logits before the revert, [B,K,S,V]
 
 
 def prompt_columns_tts(y_TK: np.ndarray, empty: int) -> np.ndarray:

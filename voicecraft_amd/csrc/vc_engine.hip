@@ -198,6 +198,10 @@ struct vc_engine {
   float *ce_nll = nullptr;
   double *ce_sum = nullptr;
   long long *ce_hits = nullptr, *ce_cnt = nullptr;
+  // parity hook of vc_eval_forward (nll_dev / tgt_dev given): the head logits of every row of the last such call, [rows][K][V]
+  // (vc_debug_read "eval_logits"); allocated by the first call that asks for it and grown on demand, never otherwise
+  float *eval_logits = nullptr;
+  int64_t eval_logits_cap = 0, eval_logits_rows = 0;      // rows allocated / rows the last call left
 };
 
 #define VC_ADM_STAGES 4
@@ -1251,6 +1255,7 @@ extern "C" void vc_destroy(vc_engine* e) {
   (void)hipDeviceSynchronize();
   for (auto& kv : e->raw) if (kv.second.dev) (void)hipFree(kv.second.dev);
   for (void* p : e->allocs) (void)hipFree(p);
+  if (e->eval_logits) (void)hipFree(e->eval_logits);
   if (e->h_st) (void)hipHostFree(e->h_st);
   if (e->h_st2) (void)hipHostFree(e->h_st2);
   if (e->h_flag) (void)hipHostFree(e->h_flag);
@@ -2769,6 +2774,20 @@ extern "C" int vc_eval_forward(vc_engine* e, int B, const int64_t* x_dev, const 
       return fail(e, VC_EINVAL, "utterance %d: %s", i, why.c_str());
     if (Lx + pa.n_cols > e->S_max) return fail(e, VC_ECAP, "utterance %d: %d positions, max_positions is %d", i, Lx + pa.n_cols, e->S_max);
   }
+  const bool hook = nll_dev && tgt_dev;            // parity hook: per-row terms, targets and head logits of every row
+  if (hook) {
+    int64_t need_rows = 0;
+    for (int i = 0; i < B; ++i) need_rows += ((pas[i].Lx + pas[i].n_cols) + 15) & ~15;
+    if (need_rows > e->eval_logits_cap) {
+      HIPCHK(e, hipStreamSynchronize(s));
+      if (e->eval_logits) { (void)hipFree(e->eval_logits); e->eval_logits = nullptr; e->eval_logits_cap = 0; }
+      void* v = nullptr;
+      const size_t nb = (size_t)need_rows * K * e->V * sizeof(float);
+      if (hipMalloc(&v, nb) != hipSuccess) return fail(e, VC_EHIP, "hipMalloc(%zu bytes) for the per-row logits failed", nb);
+      e->eval_logits = (float*)v; e->eval_logits_cap = need_rows;
+    }
+    e->eval_logits_rows = 0;
+  }
   HIPCHK(e, hipMemsetAsync(e->ce_sum, 0, sizeof(double) * VC_MAX_CODEBOOKS, s));
   HIPCHK(e, hipMemsetAsync(e->ce_hits, 0, sizeof(long long) * VC_MAX_CODEBOOKS, s));
   HIPCHK(e, hipMemsetAsync(e->ce_cnt, 0, sizeof(long long) * VC_MAX_CODEBOOKS, s));
@@ -2819,6 +2838,9 @@ extern "C" int vc_eval_forward(vc_engine* e, int B, const int64_t* x_dev, const 
         ca.nll = e->ce_nll + (size_t)(r0 + g0) * K; ca.hit = e->ce_hit + (size_t)(r0 + g0) * K;
         ca.n_rows = n; ca.K = K; ca.V = e->V; ca.err = e->err_flag;
         HIPCHK(e, vc_launch_ce(ca, s));
+        if (hook)                                    // (rows_out + R <= eval_logits_cap: both are sums of the same padded row counts)
+          HIPCHK(e, hipMemcpyAsync(e->eval_logits + (size_t)(rows_out + r0 + g0) * K * e->V, e->logits, (size_t)n * K * e->V * sizeof(float),
+                                   hipMemcpyDeviceToDevice, s));
       }
     }
     CeReduceArgs ra;
@@ -2826,12 +2848,13 @@ extern "C" int vc_eval_forward(vc_engine* e, int B, const int64_t* x_dev, const 
     ra.nll = e->ce_nll; ra.hit = e->ce_hit; ra.tgt = e->ce_tgt; ra.n_rows = R; ra.K = K;
     ra.nll_sum = e->ce_sum; ra.hits = e->ce_hits; ra.count = e->ce_cnt;
     HIPCHK(e, vc_launch_ce_reduce(ra, s));
-    if (nll_dev && tgt_dev) {                      // parity hook: the per-row terms of this group, appended
+    if (hook) {                                    // parity hook: the per-row terms of this group, appended
       if (rows_out + R > nll_cap) return fail(e, VC_ECAP, "nll capacity %lld < %lld rows", (long long)nll_cap, (long long)(rows_out + R));
       HIPCHK(e, hipMemcpyAsync(nll_dev + rows_out * K, e->ce_nll, (size_t)R * K * sizeof(float), hipMemcpyDeviceToDevice, s));
       HIPCHK(e, hipMemcpyAsync(tgt_dev + rows_out * K, e->ce_tgt, (size_t)R * K * sizeof(int), hipMemcpyDeviceToDevice, s));
     }
     rows_out += R;
+    if (hook) e->eval_logits_rows = rows_out;
     HIPCHK(e, hipStreamSynchronize(s));          // the next group reuses the arena, the target table and the cache slots
     i0 = i1;
   }
@@ -2884,8 +2907,15 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
   else if (n == "dec_h") { src = e->dec_h; avail = (int64_t)e->NS * e->d * 4; }
   else if (n == "gen") { src = e->gen; avail = (int64_t)e->B_max * e->gen_cap * e->K * 4; }
   else if (n == "state") { src = e->st; avail = (int64_t)sizeof(SeqState) * e->NS; }
-  else if (n == "kcache0") { src = e->layers[0].kc; avail = (int64_t)e->B_max * e->H * e->S_max * e->hd * e->esz; }
-  else if (n == "vcache0") { src = e->layers[0].vc; avail = (int64_t)e->B_max * e->H * e->S_max * e->hd * e->esz; }
+  else if ((n.rfind("kcache", 0) == 0 || n.rfind("vcache", 0) == 0) && n.size() > 6 && n.size() <= 9 &&
+           n.find_first_not_of("0123456789", 6) == std::string::npos && atoi(n.c_str() + 6) < e->L) {      // kcache<l> / vcache<l>: [max_seqs][H][max_positions][hd]
+    const Layer& ly = e->layers[atoi(n.c_str() + 6)];
+    src = n[0] == 'k' ? ly.kc : ly.vc; avail = (int64_t)e->B_max * e->H * e->S_max * e->hd * e->esz;
+  }
+  else if (n == "eval_logits") {                    // fp32 [rows][K][V] of the last vc_eval_forward call with the parity hook
+    if (!e->eval_logits) return fail(e, VC_ESTATE, "no vc_eval_forward call with nll_dev / tgt_dev has run");
+    src = e->eval_logits; avail = e->eval_logits_rows * e->K * e->V * 4;
+  }
   else if (n == "pe") { src = e->pe; avail = (int64_t)e->S_max * e->d * 4; }
   else if (n == "sampler_ts") { src = e->dbg_ts; avail = 16 * 8; }
   else if (n == "kernel_ts") { src = e->dbg_ts; avail = 64 * 8; }

@@ -79,6 +79,15 @@ extern "C" int vc_pattern_unshift(const int64_t* span_dev, int N, int K, int64_t
 // in exactly one Segment; a shifted piece of content length n (source frames + optional terminator)
 // contributes columns s = 0..ncols with token(q) = content[s-1-q] or `empty`; a mask placeholder
 // column takes mask_embedding[mask_value] instead of the 4-table sum.  Audio positions restart at 0.
+// emb * 1.0 + alpha * pe as ATen rounds it (embedding.py:94-97): a product and a sum, each rounded - a fused multiply-add leaves rows
+// one ulp off the reference's (tests/test_gpu_prefill_rows.py holds the arena to the oracle's rows bit for bit)
+// (__fmul_rn / __fadd_rn are plain operators in HIP and contract like them: the pragma is what keeps the two roundings)
+__device__ __forceinline__ float add_pos(float e, float alpha, float pe) {
+#pragma clang fp contract(off)
+  const float t = alpha * pe;
+  return e + t;
+}
+
 __global__ __launch_bounds__(256) void prompt_k(const PromptArgs a) {
   const int row = blockIdx.x + a.skip;        // row of the sequence = its cache position
   const int d = a.d;
@@ -99,7 +108,7 @@ __global__ __launch_bounds__(256) void prompt_k(const PromptArgs a) {
     if (tok < 0 || tok >= a.text_rows) { if (threadIdx.x == 0) atomicOr(a.err, 1); tok = 0; }
     const float* e = a.text_emb + tok * d;
     const float* pe = a.pe + (long)row * d;
-    for (int c = threadIdx.x; c < d; c += blockDim.x) dst[c] = e[c] + a.alpha_text * pe[c];
+    for (int c = threadIdx.x; c < d; c += blockDim.x) dst[c] = add_pos(e[c], a.alpha_text, pe[c]);
     return;
   }
   const int col = row - a.Lx;
@@ -110,7 +119,7 @@ __global__ __launch_bounds__(256) void prompt_k(const PromptArgs a) {
   const float* pe = a.pe + (long)col * d;
   if (sg.mask_value >= 0) {
     const float* e = a.mask_emb + (long)sg.mask_value * d;
-    for (int c = threadIdx.x; c < d; c += blockDim.x) dst[c] = e[c] + a.alpha_audio * pe[c];
+    for (int c = threadIdx.x; c < d; c += blockDim.x) dst[c] = add_pos(e[c], a.alpha_audio, pe[c]);
     return;
   }
   const int s = col - sg.col0;
@@ -126,7 +135,7 @@ __global__ __launch_bounds__(256) void prompt_k(const PromptArgs a) {
   for (int c = threadIdx.x; c < d; c += blockDim.x) {
     float v = e[0][c];
     for (int q = 1; q < a.K; ++q) v += e[q][c];       // stack(...).sum(dim=0): k = 0..K-1 in order
-    dst[c] = v + a.alpha_audio * pe[c];
+    dst[c] = add_pos(v, a.alpha_audio, pe[c]);
   }
 }
 hipError_t vc_launch_prompt(const PromptArgs& a, hipStream_t s) {

@@ -409,7 +409,9 @@ class VoiceCraftEngine:
         data augmentation, out of this engine's scope); here they are an argument: `mask_intervals[i]` = the (start, end)
         frame pairs of utterance i.  `mask_values[i]` = the utterance's `emb_inds_use` (default 0..M-1; the reference
         shuffles them when `shuffle_mask_embedding` is set).  `mask_sampler`: a callable `y_lens -> mask_intervals` used when
-        `mask_intervals` is None (the reference's own `prepare_mask_intervals` fits).  No gradients: this engine does not train."""
+        `mask_intervals` is None (the reference's own `prepare_mask_intervals` fits).  No gradients: this engine does not train.
+        `_per_row` (parity hook): also returns, in the engine's row order (utterances back to back, each padded to 16 rows, text rows
+        first), `_nll_rows` / `_tgt_rows` [rows, K] and `_logit_rows` [rows, K, V], the head logits of every row (host, fp32)."""
         import ast
         import random
         if mask_intervals is None and mask_sampler is not None:
@@ -489,6 +491,8 @@ class VoiceCraftEngine:
         if _per_row:
             out["_nll_rows"], out["_tgt_rows"] = nll[: n_rows.value], tgt[: n_rows.value]
             out["_nll_sum"] = [float(nll_sum[k]) for k in range(K)]
+            # the head logits of every row, [rows, K, V] fp32 on the host, in the row order of _nll_rows / _tgt_rows
+            out["_logit_rows"] = self.debug_read("eval_logits", (int(n_rows.value), K, self.args.audio_vocab_size + int(self.args.n_special)))
         return out
 
     @torch.no_grad()
