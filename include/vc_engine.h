@@ -204,7 +204,8 @@ int vc_tts_stream_next(vc_engine* e, int min_frames, int64_t* codes_dev, int cap
                        int* first_frame, int* n_frames, int* done);
 int vc_tts_stream_end(vc_engine* e, int64_t* res_dev, int res_cap, int* gen_len, int* n_steps);
 
-/* ---- decode sessions: continuous batching of TTS and speech-editing requests (inference_tts / inference semantics, one sample each).
+/* ---- decode sessions: continuous batching of TTS and speech-editing requests (inference_tts / inference semantics; a TTS request may
+ * be best-of-N, inference_tts_batch semantics, in a session opened for it).
  * A session keeps the decode loop open: requests are submitted at any time, each is prefilled into a free K/V slot between two graph
  * batches and joins the running batch, and each result can be fetched as soon as its own sequence has ended - the batch is refilled
  * instead of idling to its longest member.  The step width follows the live count both ways (the next power of two, captured graphs
@@ -216,16 +217,30 @@ int vc_tts_stream_end(vc_engine* e, int64_t* res_dev, int res_cap, int* gen_len,
  * in.  Exact mode: every request's tokens are those of its own blocking call with its controls, whatever it shared a step with.  bf16:
  * the tokens are a function of the submissions and of the turn each was made at (the admission schedule is decided from retirements of
  * batches the host has seen end, never from how far the device runs ahead).
- * Not part of a session, because they have no per-request form here: best-of-N, a shared text prefix, logits_out and forced
- * trajectories - the entry points below simply have no such arguments; use the blocking calls.
+ * Best-of-N requests: a session opened with vc_session_open_best_of(max_samples > 1) takes TTS requests of n_samples in [1, max_samples]
+ * samples (vc_session_submit_best_of).  One ticket, N slots and N rows: the prompt is prefilled once and its K/V replicated to the N - 1
+ * sibling slots; sample j draws on (the request's seed, sequence j, its own step, codebook), the stream of a lone vc_tts(n_samples = N)
+ * call; the LAST sample whose first codebook terminates first is kept, the others are dropped at that step and their rows and slots
+ * return to the session.  The steps of such a session end in two sampler launches instead of one (the keep decision reads every
+ * member's terminator flag, which needs a kernel boundary); a session opened with vc_session_open runs the one-launch steps.  Exact
+ * mode: tokens and kept index are those of the request's own vc_tts(n_samples = N) call.  bf16: a function of the submission schedule,
+ * but not bit-equal to the blocking call (the session narrows after a group collapses, the blocking one-group call keeps its N rows).
+ * Not part of a session, because they have no per-request form here: a shared text prefix, logits_out and forced trajectories - the
+ * entry points below simply have no such arguments; use the blocking calls.  Editing and best-of-N tickets do not stream (frames).
  *   open     max_live in [1, max_seqs] slots.  Captures the step graphs of every width the session can pass through (the powers of two
  *            up to the one for max_live), ahead of any timer.  VC_ESTATE while a streaming call or another session is open.  While a
  *            session is open every other decode entry point, vc_set_option and vc_tts_stream_begin return VC_ESTATE.
+ *   open_best_of  the same with max_samples in [1, max_live] (VC_EINVAL outside): the largest n_samples a request may ask for.
+ *            max_samples = 1 is exactly vc_session_open.
  *   submit   a TTS request with the session's controls (submit_ctl with ctl = NULL).  submit_ctl: a TTS request with its own controls.
  *            Host-side checks at once, with vc_tts's codes: empty text (VC_EINVAL), a prompt that alone does not fit max_positions
  *            (VC_ECAP); a ctl whose temperature is not a finite positive number or whose top_p is not a number: VC_EINVAL.  The
  *            request joins a FIFO; *ticket identifies it.  x_dev / y_dev must stay valid until the ticket is fetched or the session
  *            closed; ctl is copied.
+ *   submit_best_of  a TTS request of n_samples samples (n_samples = 1 is submit_ctl).  n_samples outside [1, max_samples] of the session:
+ *            VC_EINVAL naming both numbers, and the session goes on.  The request takes n_samples free slots - the lowest free ones,
+ *            not necessarily consecutive - and is admitted by the first turn that has them; admission stays strictly FIFO, so nothing
+ *            submitted behind it is admitted before it (head-of-line blocking).  Editing requests have no best-of-N form.
  *   submit_edit  an editing request: mask_intervals [M][2] and mask_values [2M] are host arrays with vc_edit's meaning, copied at
  *            submit.  Validated at once with vc_edit's codes and messages (span count; ordered, disjoint intervals; an empty non-masked
  *            piece; mask value range; eos > 0 without reduced_eog; the rearranged prompt against max_positions and the prefill arena).
@@ -244,8 +259,13 @@ int vc_tts_stream_end(vc_engine* e, int64_t* res_dev, int res_cap, int* gen_len,
  *            steps (the fed rows of a span switch are not steps).  Unknown ticket: VC_EINVAL; unfinished: VC_ESTATE; ran out of
  *            positions before its terminator (an edit: before its last span ended): VC_ECAP, as vc_tts / vc_edit_multi; an
  *            out-of-range token id in its x / y: VC_EINVAL naming the ticket.  A finished request holds its slot until fetched (the
- *            slot's rows of the generated-token log are the result).
- *   stats    [0] requests admitted, [1] of them admitted while other sequences were live, [2] turns, [3] widenings, [4] narrowings,
+ *            slot's rows of the generated-token log are the result).  A best-of-N ticket is finished by the turn that has seen all its
+ *            samples retire; a dropped sample's slot is free as soon as the host has seen its batch end, only the kept sample's slot is
+ *            held for the fetch, which assembles from it.  No sample terminated within its room: VC_ECAP "no sample terminated within
+ *            the step budget", as vc_tts_multi_best_of.
+ *   kept     *kept = the kept sample's index of a finished, unfetched best-of-N ticket (-1: none terminated); 0 for any other ticket.
+ *            Unknown ticket: VC_EINVAL; unfinished: VC_ESTATE.
+ *   stats    (requests in [0], [1]; every sample's rows in [5], [6])  [0] requests admitted, [1] of them admitted while other sequences were live, [2] turns, [3] widenings, [4] narrowings,
  *            [5] sum over launched steps of the rows that were live, an edit's fed rows included (counted at retirement), [6] sum over
  *            launched steps of the step width, [7] microseconds of decode-stream time spent on admissions (prefill + re-pack + first
  *            sample; HIP events).
@@ -263,7 +283,8 @@ int vc_tts_stream_end(vc_engine* e, int64_t* res_dev, int res_cap, int* gen_len,
  *            still reports the error.  A finished ticket streams until it is fetched.  The gather is one launch for all tickets on
  *            the side stream of vc_tts_stream_next, and only that stream is synchronised.  Refused as a whole, before any cursor
  *            moves, with VC_EINVAL: an unknown or fetched ticket, a ticket given twice, an editing ticket ("editing requests do not
- *            stream": its rows per batch hang on span switches the host learns at retirement, and its result is a splice), n outside
+ *            stream": its rows per batch hang on span switches the host learns at retirement, and its result is a splice), a best-of-N
+ *            ticket ("best-of-N requests do not stream": the kept sample is unknown until the group decides), n outside
  *            [1, max_live], cap < 1, min_frames outside [1, cap], null pointers.  No session: VC_ESTATE; a broken session: its error.
  *   close    waits for what is queued, drops everything pending and unfetched; the engine is reusable. */
 typedef struct vc_request_ctl {   /* 16 bytes: the per-request part of vc_sample_cfg, same meaning field by field */
@@ -273,14 +294,18 @@ typedef struct vc_request_ctl {   /* 16 bytes: the per-request part of vc_sample
   int32_t stop_repetition;
 } vc_request_ctl;
 int vc_session_open(vc_engine* e, int max_live, const vc_sample_cfg* sc, void* stream);
+int vc_session_open_best_of(vc_engine* e, int max_live, int max_samples, const vc_sample_cfg* sc, void* stream);
 int vc_session_submit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T, uint64_t seed, int* ticket);
 int vc_session_submit_ctl(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
                           const vc_request_ctl* ctl, uint64_t seed, int* ticket);
+int vc_session_submit_best_of(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T, int n_samples,
+                              const vc_request_ctl* ctl, uint64_t seed, int* ticket);
 int vc_session_submit_edit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
                            const int32_t* mask_intervals, int M, const int32_t* mask_values,
                            const vc_request_ctl* ctl, uint64_t seed, int* ticket);
 int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* n_finished, int* idle);
 int vc_session_fetch(vc_engine* e, int ticket, int64_t* res_dev, int res_cap, int* gen_len, int* n_steps);
+int vc_session_kept(vc_engine* e, int ticket, int* kept);
 int vc_session_frames(vc_engine* e, int n, const int* tickets, int min_frames, int64_t* codes_dev, int cap,
                       int* first_frame, int* n_frames, int* done);
 int vc_session_stats(vc_engine* e, int64_t out[8]);

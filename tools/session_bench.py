@@ -1,5 +1,5 @@
 """Decode sessions (continuous batching) against what the blocking API offers for the same work, on ONE engine, interleaved pairs:
-python tools/session_bench.py [--preset giga830M] [--pairs 5] [--sizes 64:8,256:64] [--edit-share 0.5]
+python tools/session_bench.py [--preset giga830M] [--pairs 5] [--sizes 64:8,256:64] [--edit-share 0.5] [--best-of 3 --sizes 48:24]
 
 Workload: the ragged utterances of bench.py's ragged_block (giga830M shape, bf16, top-k 40, 150 prompt frames, the synthetic
 checkpoint's terminator muted, so an utterance of Lx phonemes ends at the reference's length cap: 10 Lx - 150 generated frames).  `N:L`
@@ -16,6 +16,11 @@ re-pack + first sample, HIP events).  Both arms produce the same number of frame
 their own controls next to the TTS requests.  The baseline then runs, for every consecutive group of L requests, inference_tts_multi on
 the group's TTS requests and inference_multi on its editing requests - what the blocking API offers when the two kinds cannot share a
 step; the frames compared and counted are the generated ones of either kind.
+--best-of B (B > 1; TTS only): every utterance is a best-of-B request.  `N:L` = N utterances through L slots, L a multiple of B:
+  * baseline: consecutive inference_tts_multi(batch_size=B) calls of L / B utterances - L rows, each call idling down to its longest group;
+  * session:  open_session(max_live = L, max_samples = B), every utterance submitted with n_samples = B.
+With the terminator muted every sample of a group reaches the length cap on the same step (the last is kept), so both arms generate
+the same frames; admission_stream_ms_per_request then contains the K/V copies to the B - 1 sibling slots.
 --stream: instead of the above, per size, every request streams (DecodeSession.submit(stream=True)):
   * streamer: voicecraft_amd.stream.SessionStreamer pumped until the session is idle - frames pulled while the batch decodes, ONE
     decode_streams feed per pump (--chunk-frames, default 8);
@@ -41,10 +46,13 @@ p.add_argument("--top-k", type=int, default=40)
 p.add_argument("--pairs", type=int, default=5)
 p.add_argument("--sizes", default="64:8,256:64")
 p.add_argument("--edit-share", type=float, default=0.0)
+p.add_argument("--best-of", type=int, default=1)
 p.add_argument("--stream", action="store_true")
 p.add_argument("--chunk-frames", type=int, default=8)
 p.add_argument("--codec-frames", type=int, default=200)
 args = p.parse_args()
+BO = args.best_of
+assert BO >= 1 and (BO == 1 or (args.edit_share == 0 and not args.stream)), "--best-of goes with TTS requests only"
 dev = torch.device("cuda", 0)
 a = synth.make_args(args.preset)
 K = a.n_codebooks
@@ -89,7 +97,9 @@ def simulate_blocking_rows(steps, G):
 
 for size in args.sizes.split(","):
     N, L = (int(v) for v in size.split(":"))
-    lxs = [args.lx if L == 1 else args.lx_min + (args.lx - args.lx_min) * (u % L) // (L - 1) for u in range(N)]
+    assert L % BO == 0, (L, BO)
+    LU = L // BO                  # utterances that fit the slots together
+    lxs = [args.lx if LU == 1 else args.lx_min + (args.lx - args.lx_min) * (u % LU) // (LU - 1) for u in range(N)]
     prompts = [synth.random_prompt(a, lxs[u], args.prompt_frames, seed=1 + u) for u in range(N)]
     is_edit = [int((u + 1) * args.edit_share) > int(u * args.edit_share) for u in range(N)]
     xs = [q[0][0].to(dev) for q in prompts]
@@ -101,12 +111,12 @@ for size in args.sizes.split(","):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         frames, sim = [], [0, 0, 0]
-        for g0 in range(0, N, L):
-            grp = list(range(g0, min(N, g0 + L)))
+        for g0 in range(0, N, LU):
+            grp = list(range(g0, min(N, g0 + LU)))
             tts, edits = [u for u in grp if not is_edit[u]], [u for u in grp if is_edit[u]]
             f = {}
             if tts:
-                outs = eng.inference_tts_multi([xs[u] for u in tts], [ys[u] for u in tts], _seed=seed + g0, **kn)
+                outs = eng.inference_tts_multi([xs[u] for u in tts], [ys[u] for u in tts], _seed=seed + g0, batch_size=BO, **kn)
                 f.update({u: int(gen.shape[2]) for u, (res, gen) in zip(tts, outs)})
             if edits:
                 outs = eng.inference_multi([xs[u] for u in edits], [ys[u] for u in edits], [[span]] * len(edits), _seed=seed + g0,
@@ -115,7 +125,8 @@ for size in args.sizes.split(","):
             frames += [f[u] for u in grp]
             for part in (tts, edits):
                 if part:
-                    for i, v in enumerate(simulate_blocking_rows([f[u] + K for u in part], G)):
+                    # (best-of-B: the kept sample takes f + K steps, a dropped one f + 1 - it is dropped on the deciding step)
+                    for i, v in enumerate(simulate_blocking_rows([f[u] + (K if j == 0 else 1) for u in part for j in range(BO)], G)):
                         sim[i] += v
         torch.cuda.synchronize()
         wall = time.perf_counter() - t0
@@ -124,11 +135,11 @@ for size in args.sizes.split(","):
     def session(seed):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        with eng.open_session(L, **kn) as sess:
+        with eng.open_session(L, max_samples=BO, **kn) as sess:
             mi = torch.tensor([[span]], dtype=torch.int64)
             tickets = [sess.submit_edit(xs[u].reshape(1, -1), torch.tensor([lxs[u]]), ys[u].unsqueeze(0), mi, seed=seed + u, **ekn)
                        if is_edit[u] else
-                       sess.submit(xs[u].reshape(1, -1), torch.tensor([lxs[u]]), ys[u].unsqueeze(0), seed=seed + u) for u in range(N)]
+                       sess.submit(xs[u].reshape(1, -1), torch.tensor([lxs[u]]), ys[u].unsqueeze(0), seed=seed + u, n_samples=BO) for u in range(N)]
             done = {t: (res, gen) for t, res, gen in sess.drain()}
             torch.cuda.synchronize()
             wall = time.perf_counter() - t0
@@ -242,7 +253,7 @@ for size in args.sizes.split(","):
         assert b["frames"] == s["frames"], "both arms generate the same frames per utterance (the length cap ends every sequence)"
     out = {"workload": f"{args.preset} {args.dtype}, top_k={args.top_k}, {N} utterances ({sum(is_edit)} of them editing requests) through {L} slots, Lx {min(lxs)}..{max(lxs)}, "
                        f"{args.prompt_frames} prompt frames -> {min(rows['session'][0]['frames'])}..{max(rows['session'][0]['frames'])} generated frames",
-           "pairs": args.pairs, "graph_steps": G, "options": eng.options()}
+           "pairs": args.pairs, "graph_steps": G, "best_of": BO, "options": eng.options()}
     for arm in ("baseline", "session"):
         r = rows[arm]
         out[arm] = {"codec_tokens_per_s": stats([v["tok_s"] for v in r]), "wall_ms": stats([v["wall_ms"] for v in r]),

@@ -52,6 +52,10 @@ PROTOTYPES = {
                                      C.POINTER(C.c_int)]),
     "vc_tts_stream_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vc_session_open": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SampleCfg), C.c_void_p]),
+    "vc_session_open_best_of": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(SampleCfg), C.c_void_p]),
+    "vc_session_submit_best_of": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(RequestCtl),
+                                            C.c_uint64, C.POINTER(C.c_int)]),
+    "vc_session_kept": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "vc_session_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_int)]),
     "vc_session_submit_ctl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(RequestCtl), C.c_uint64,
                                         C.POINTER(C.c_int)]),

@@ -351,6 +351,10 @@ struct SampleDyn {
   const int* adm_slot;      // [grid] slot of each of them = the logits row its prefill left the first-step logits at
   const vc_request_ctl* ctl_tab;   // [max_seqs] sampling controls of the request in each slot (written at admission by session_turn_k): a session's
                             // sampler takes top_k / top_p / temperature / stop_repetition from here, never from the per-call values above
+  // sessions opened for best-of-N requests only (vc_session_open_best_of): read by the session's sampler PAIR alone
+  const int* samp_tab;      // [max_seqs] by slot: sample index j of the row's request | its sample count N << 16 (written at admission by
+                            // session_groups_k; a plain or editing request is 0 | 1 << 16).  The row draws on (its seed, sequence j, its
+                            // step, codebook); with SeqState.group = the request's ticket this is the group geometry of the keep decision
 };
 
 struct SampleArgs {         // engine-constant part (kernel argument)
@@ -384,7 +388,8 @@ struct SampleArgs {         // engine-constant part (kernel argument)
 };
 // retirement record of a slot: [0] batch stamp + 1 (0 = none), [1] total steps, [2] spans finished (fewer than the request's = ran out of
 // positions), [3] steps of span 0, [4] error bits of the request's prompt (prompt_k; written at admission), [5] rows the request fed without
-// sampling (two per span switch of an editing request), [VC_SESS_REC_SPANS + i] steps of span i (what edit_assemble needs of the final state)
+// sampling (two per span switch of an editing request), [6] SeqState.kept of the row (sessions opened for best-of-N requests only: 0 = a
+// dropped sample), [VC_SESS_REC_SPANS + i] steps of span i (what edit_assemble needs of the final state)
 #define VC_SESS_REC_SPANS 8
 #define VC_SESS_REC (VC_SESS_REC_SPANS + VC_MAX_SPANS)
 
@@ -473,9 +478,21 @@ struct SessTurnArgs {
   uint64_t seed[VC_MAX_SEQS];
 };
 hipError_t vc_launch_session_turn(const SessTurnArgs& a, hipStream_t s);
+// What a turn of a session opened for best-of-N requests adds behind session_turn_k (session_groups_k): a request of N samples is N
+// admitted ROWS, one per sample, each with its own slot.
+struct SessGroupArgs {
+  int* adm_slot;            // [max_seqs] (SampleDyn.adm_slot): entry i becomes lrow[i]
+  int* samp_tab;            // [max_seqs] by slot (SampleDyn.samp_tab): entry slot[i] becomes samp[i]
+  int n_new;
+  int slot[VC_MAX_SEQS];    // admitted row i: its own slot
+  int lrow[VC_MAX_SEQS];    // ... the logits row its first sample reads = the slot its request's prompt was prefilled into
+  int samp[VC_MAX_SEQS];    // ... sample index | sample count << 16
+};
+hipError_t vc_launch_session_groups(const SessGroupArgs& g, int max_seqs, hipStream_t s);
 // The session's sampler launches: first = false, one step of B rows (captured in the session's graphs); first = true, the first sample
-// of the n rows admitted this turn only (the older rows' logits are already consumed).
-hipError_t vc_launch_sample_session(const SampleArgs& a, bool first, int n, hipStream_t s);
+// of the n rows admitted this turn only (the older rows' logits are already consumed).  grouped (a session opened for best-of-N
+// requests): the sample / advance PAIR - the keep decision of a group reads every member's terminator flag, which needs the kernel boundary.
+hipError_t vc_launch_sample_session(const SampleArgs& a, bool first, int n, bool grouped, hipStream_t s);
 hipError_t vc_launch_assemble(const AssembleArgs& a, hipStream_t s);
 struct StreamGatherArgs {   // vc_tts_stream_next: the frames of sequence 0 that `rows` finished rows of its gen buffer make complete
   const SeqState* st;       // sequence 0's state (later steps may be writing it: only what the finished rows fixed is trusted)

@@ -111,6 +111,7 @@ struct vc_engine {
   // whose they are, prompt_k's error bits by slot, the prefill's own gather rows (the decode step's logit_row stays the live rows'), and the
   // pinned retirement records the host reads (vc_common.h VC_SESS_REC)
   uint64_t* seed_tab = nullptr;
+  int* samp_tab = nullptr;  // [NS] by slot: sample index | sample count << 16 of the row's request (sessions opened for best-of-N requests)
   int *batch_id = nullptr, *row_base = nullptr, *adm_slot = nullptr, *prompt_err = nullptr, *sess_gather = nullptr;
   int* h_rec = nullptr;
   // ... the requests' sampling controls by slot (SampleDyn.ctl_tab), and the staging of a turn's admitted requests: their first states
@@ -881,7 +882,7 @@ int push_sample_dyn(vc_engine* e, const vc_sample_cfg* sc, const int64_t* forced
   d.n_group = n_group;                                    // samples per best-of-N group (advance_phase's keep decision)
   d.dbg_ts = getenv("VC_SAMPLER_TS") ? e->dbg_ts : nullptr;
   d.seed_tab = e->seed_tab; d.retire_rec = e->h_rec; d.batch_id = e->batch_id; d.row_base = e->row_base; d.adm_slot = e->adm_slot;   // (sessions only)
-  d.ctl_tab = e->ctl_tab;
+  d.ctl_tab = e->ctl_tab; d.samp_tab = e->samp_tab;
   HIPCHK(e, hipMemcpyAsync(e->d_dyn, e->h_dyn, sizeof(SampleDyn), hipMemcpyHostToDevice, s));
   return VC_OK;
 }
@@ -897,7 +898,7 @@ int decode_step(vc_engine* e, const SampleArgs& sa, int B, int rps, bool grouped
   // rps == 1: logit_row[b] == b (vc_tokens.hip advance_phase); the 3-row span switch is single-sequence
   rc = run_heads(e, p, po, rps == 1 ? nullptr : e->logit_row, B, 0, 0, e->n_active, s);
   if (rc) return rc;
-  if (sess) HIPCHK(e, vc_launch_sample_session(sa, false, B, s));
+  if (sess) HIPCHK(e, vc_launch_sample_session(sa, false, B, grouped, s));     // (grouped: a session opened for best-of-N requests)
   else HIPCHK(e, vc_launch_sample(sa, grouped, s));
   return VC_OK;
 }
@@ -944,7 +945,7 @@ struct DecodeLoop {
   static int width_for(int live) { int p = 1; while (p < live) p *= 2; return p; }
   // One captured graph per (rows per step, option state), kept for the life of the engine.
   int exec_for(hipGraphExec_t* out) {
-    const auto key = std::make_pair(std::make_tuple(B, rps, sess ? 2 : grouped ? 1 : 0), e->opt_state);
+    const auto key = std::make_pair(std::make_tuple(B, rps, sess ? (grouped ? 3 : 2) : grouped ? 1 : 0), e->opt_state);
     auto it = e->graphs.find(key);
     int rc = VC_OK;
     if (it != e->graphs.end()) {
@@ -1512,6 +1513,8 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
   HIPCHK(e, hipHostMalloc((void**)&e->h_rec, sizeof(int) * VC_SESS_REC * e->NS));
   memset(e->h_rec, 0, sizeof(int) * VC_SESS_REC * e->NS);
   if ((rc = dalloc(e, &e->seed_tab, (size_t)e->NS))) return rc;
+  if ((rc = dalloc(e, &e->samp_tab, (size_t)e->NS))) return rc;
+  HIPCHK(e, hipMemset(e->samp_tab, 0, sizeof(int) * e->NS));
   if ((rc = dalloc(e, &e->batch_id, (size_t)4))) return rc;
   if ((rc = dalloc(e, &e->row_base, (size_t)4))) return rc;
   if ((rc = dalloc(e, &e->adm_slot, (size_t)e->NS))) return rc;
@@ -2017,6 +2020,13 @@ int edit_assemble(vc_engine* e, const EditJob& j, const SeqState& fs, const int*
 //      staging buffer (batch % VC_ADM_STAGES) and uploaded on the decode stream in front of session_turn_k.  That buffer is written again
 //      VC_ADM_STAGES turns later at the earliest; a turn queues only after the batch two turns back has ENDED (step 1), and a batch ends
 //      behind its turn's upload on the same stream, so no queued upload can still have to read a buffer the host is writing.
+// A session opened for best-of-N requests (vc_session_open_best_of, max_samples > 1) takes TTS requests of N samples too
+// (vc_session_submit_best_of): one ticket, N rows and N slots.  The prompt is prefilled once, into the first slot, and its K/V copied
+// to the siblings' slots (copy_kv_k); the rows are laid next to each other in sample order, with SeqState.group = the ticket and
+// their sample index in samp_tab (session_groups_k, behind session_turn_k); the steps of such a session end in the sample / advance
+// PAIR (vc_launch_sample_session grouped), whose second launch holds the keep decision.  Every row writes its slot's record, word 6
+// = kept: a dropped sample's slot is free once the host has seen its batch end, the request is finished when all N records are in,
+// and only the kept sample's slot waits for the fetch.
 // What the host decides - who is admitted when, every width - depends only on the submissions, the turn each was made at and records
 // of batches that have ended: never on how far the device runs ahead.  The same schedule therefore gives the same tokens in bf16 too.
 // Width in force: the next power of two >= live sequences, capped by `top` (that power for max_live where the per-row buffers hold it,
@@ -2034,14 +2044,23 @@ struct SessReq {
   int span_steps[VC_MAX_SPANS]{};
   int adm_batch = -1;       // the graph batch queued by the turn that admitted it (vc_session_frames counts its final rows from there)
   int emitted = 0;          // frames vc_session_frames has handed out
+  // a best-of-N request (n_samples > 1): one row and one K/V slot per sample.  `slot` is slots[0] while it decodes and the KEPT sample's
+  // slot once it has finished (-1 when no sample terminated); total_steps / span / span_steps are then the kept sample's
+  int n_samples = 1;
+  std::vector<int> slots;   // [n_samples], increasing
+  std::vector<char> mdone;  // [n_samples] the member's retirement record has been read
+  int members_left = 0;
+  int kept = -1;            // sample index of the member that retired kept with its span finished
 };
 struct Session {
   DecodeLoop L{};
   hipStream_t s = nullptr;
   vc_sample_cfg sc{};
   int max_live = 0, top = 0;
+  int max_samples = 1;      // > 1: opened for best-of-N requests (vc_session_open_best_of) - the steps' sampler is the sample / advance pair
+  bool grouped = false;     // max_samples > 1
   int B = 0;                // rows of the step in force (0: nothing laid out yet)
-  int live = 0;             // admitted and not yet KNOWN to have retired
+  int live = 0;             // rows (one per sample of a request) admitted and not yet KNOWN to have retired
   int batch = 0;            // index of the next graph batch (never reset: the retirement stamps are unique for the session's life)
   int run_start = 0;        // first batch queued since the session was last idle: only batches from there on can be in flight
   int known = -1;           // the newest batch vc_session_advance has seen END (what vc_session_frames may hand out hangs on this alone)
@@ -2093,6 +2112,35 @@ void session_note_retired(vc_engine* e, Session& t, int known, int* tickets_out,
     volatile int* rec = e->h_rec + slot * VC_SESS_REC;
     const int stamp = rec[0];
     if (stamp == 0 || stamp - 1 > known) continue;
+    if (r.n_samples > 1) {
+      // one member of a best-of-N request.  A dropped sample's slot is free from here on; the request is finished - and reported - by
+      // the turn that has read all its members' records, and only the kept sample's slot is held for the fetch
+      int m = -1;
+      for (int i = 0; i < r.n_samples; ++i) if (r.slots[i] == slot) m = i;
+      if (m < 0 || r.mdone[m]) continue;
+      const bool last = r.members_left == 1;
+      if (last && *n_fin >= cap) continue;              // no room to report the request: this member is read again by a later turn
+      r.mdone[m] = 1;
+      r.members_left -= 1;
+      t.live -= 1;
+      t.stats[5] += std::max(0, (int)rec[1] - 1);
+      r.prompt_err |= rec[4];
+      if (rec[6] && rec[2] >= 1 && m >= r.kept) {       // (at most one member ends kept with its span finished: advance_phase)
+        r.kept = m;
+        r.total_steps = rec[1]; r.span = rec[2]; r.fed = rec[5];
+        for (int i = 0; i < VC_MAX_SPANS; ++i) r.span_steps[i] = rec[VC_SESS_REC_SPANS + i];
+      }
+      if (!rec[6]) t.slot_ticket[slot] = -1;
+      if (last) {
+        r.state = 2;
+        for (int i = 0; i < r.n_samples; ++i)
+          if (i != r.kept && t.slot_ticket[r.slots[i]] == ticket) t.slot_ticket[r.slots[i]] = -1;
+        r.slot = r.kept >= 0 ? r.slots[r.kept] : -1;
+        tickets_out[*n_fin] = ticket;
+        *n_fin += 1;
+      }
+      continue;
+    }
     if (*n_fin >= cap) continue;                        // no room to report it: it stays live on the host and is reported by a later turn
     r.state = 2;
     r.total_steps = rec[1]; r.span = rec[2]; r.prompt_err = rec[4]; r.fed = rec[5];
@@ -2106,14 +2154,17 @@ void session_note_retired(vc_engine* e, Session& t, int known, int* tickets_out,
 }
 }  // namespace
 
-extern "C" int vc_session_open(vc_engine* e, int max_live, const vc_sample_cfg* sc, void* stream) {
+extern "C" int vc_session_open_best_of(vc_engine* e, int max_live, int max_samples, const vc_sample_cfg* sc, void* stream) {
   int rc = check_idle(e);
   if (rc) return rc;
   if (!sc) return fail(e, VC_EINVAL, "null argument to vc_session_open");
   if (max_live < 1 || max_live > e->B_max) return fail(e, VC_EINVAL, "vc_session_open: max_live %d outside [1, max_seqs = %d]", max_live, e->B_max);
+  if (max_samples < 1 || max_samples > max_live)
+    return fail(e, VC_EINVAL, "vc_session_open_best_of: max_samples %d outside [1, max_live = %d]", max_samples, max_live);
   hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
   Session* t = new Session();
   t->s = s; t->sc = *sc; t->max_live = max_live;
+  t->max_samples = max_samples; t->grouped = max_samples > 1;
   t->top = DecodeLoop::width_for(max_live) <= e->NS ? DecodeLoop::width_for(max_live) : max_live;
   t->slot_ticket.assign(max_live, -1);
   auto bail = [&](int code) { e->sess = t; drop_session(e); return code; };
@@ -2135,6 +2186,7 @@ extern "C" int vc_session_open(vc_engine* e, int max_live, const vc_sample_cfg* 
   // every graph the session can pass through, ahead of any timer: the powers of two below `top`, and `top`
   t->L.init(e, make_sample_args(e, t->top, 1), t->top, 1, 0, sc, 0, s);
   t->L.sess = true;
+  t->L.grouped = t->grouped;      // graphs of their own: the steps of such a session end in the sample / advance pair
   e->host_ms[1] = e->host_ms[2] = 0;
   if (sc->use_graph) {
     hipGraphExec_t exec = nullptr;
@@ -2146,6 +2198,9 @@ extern "C" int vc_session_open(vc_engine* e, int max_live, const vc_sample_cfg* 
   }
   e->sess = t;
   return VC_OK;
+}
+extern "C" int vc_session_open(vc_engine* e, int max_live, const vc_sample_cfg* sc, void* stream) {
+  return vc_session_open_best_of(e, max_live, 1, sc, stream);
 }
 
 namespace {
@@ -2197,6 +2252,21 @@ extern "C" int vc_session_submit_ctl(vc_engine* e, const int64_t* x_dev, int Lx,
   r.job = TtsJob{x_dev, Lx, y_dev, T};
   r.seed = seed;
   return session_enqueue(*tp, std::move(r), ticket);
+}
+
+extern "C" int vc_session_submit_best_of(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T, int n_samples,
+                                         const vc_request_ctl* ctl, uint64_t seed, int* ticket) {
+  Session* tp = nullptr;
+  if (int rc = session_for_submit(e, &tp)) return rc;
+  if (!ticket) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_submit");
+  if (n_samples < 1 || n_samples > tp->max_samples)
+    return fail(e, VC_EINVAL, "vc_session_submit_best_of: n_samples %d outside [1, max_samples = %d] of this session%s", n_samples,
+                tp->max_samples, tp->max_samples == 1 ? " (vc_session_open_best_of opens one for best-of-N requests)" : "");
+  int id = 0;
+  if (int rc = vc_session_submit_ctl(e, x_dev, Lx, y_dev, T, ctl, seed, &id)) return rc;
+  tp->reqs[id].n_samples = n_samples;
+  *ticket = id;
+  return VC_OK;
 }
 
 extern "C" int vc_session_submit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T, uint64_t seed, int* ticket) {
@@ -2254,36 +2324,60 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
   std::vector<PromptArgs> pas;
   std::vector<int> slots;
   const int live_before = t.live;
-  for (int slot = 0; slot < t.max_live && !t.fifo.empty(); ++slot) {
-    if (t.slot_ticket[slot] >= 0) continue;
+  // strictly FIFO: the head of the queue is admitted by the first turn that has a free slot for EACH of its samples - the lowest free
+  // slots, which need not be consecutive -, and nothing behind it overtakes it (a best-of-N request waiting for slots blocks the line).
+  // A request of one sample takes the lowest free slot, as ever.
+  SessGroupArgs ga;
+  memset(&ga, 0, sizeof ga);
+  CopyKvArgs kv;            // the siblings' prompt K/V: one (source, destination) entry per sibling, every group of the turn in one table
+  memset(&kv, 0, sizeof kv);
+  int n_req = 0;
+  while (!t.fifo.empty()) {
     const int id = t.fifo.front();
-    t.fifo.pop_front();
     SessReq& r = t.reqs[id];
-    r.slot = slot; r.state = 1; r.adm_batch = t.batch;
-    t.slot_ticket[slot] = id;
-    const int j = ta.n_new++;
-    ta.seed[j] = r.seed;
+    const int N = r.n_samples;
+    std::vector<int> mine;
+    for (int slot = 0; slot < t.max_live && (int)mine.size() < N; ++slot)
+      if (t.slot_ticket[slot] < 0) mine.push_back(slot);
+    if ((int)mine.size() < N) break;
+    t.fifo.pop_front();
+    n_req += 1;
+    r.slot = mine[0]; r.state = 1; r.adm_batch = t.batch;
+    r.slots = mine; r.mdone.assign(N, 0); r.members_left = N; r.kept = -1;
     // the request's first state and its prompt, by kind: what tts_prepare / vc_edit_multi lay down for a sequence of a blocking call
-    SeqState& st = h_adm_st[j];
+    SeqState st0;
     PromptArgs pa;
     if (r.kind == 1) {
-      st = edit_state(e, r.edit);
-      st.feed_switch = 1;
+      st0 = edit_state(e, r.edit);
+      st0.feed_switch = 1;
       pa = r.edit.pa;
     } else {
-      st = init_state(e, r.job.Lx, r.job.T + 1, true, 1);
+      st0 = init_state(e, r.job.Lx, r.job.T + 1, true, 1);
       fill_prompt_common(e, pa, r.job.x, r.job.Lx, r.job.y, r.job.T);
       pa.n_seg = 1; pa.n_cols = r.job.T + 1;
       pa.seg[0] = Segment{0, r.job.T + 1, 0, r.job.T, -1, -1};
     }
-    st.slot = slot;
-    h_adm_ctl[j] = r.ctl;
-    pas.push_back(pa);
-    slots.push_back(slot);
-    volatile int* rec = e->h_rec + slot * VC_SESS_REC;      // the slot's record: empty until this request retires
-    for (int i = 0; i < VC_SESS_REC; ++i) rec[i] = 0;
+    if (N > 1) st0.group = id;                              // the group of the keep decision is the request (advance_phase)
+    pas.push_back(pa);                                      // ONE prefill per request, into its first slot
+    slots.push_back(mine[0]);
+    for (int m = 0; m < N; ++m) {                           // one row per sample, consecutive and in sample order
+      const int slot = mine[m];
+      t.slot_ticket[slot] = id;
+      const int j = ta.n_new++;
+      ta.seed[j] = r.seed;
+      h_adm_st[j] = st0;
+      h_adm_st[j].slot = slot;
+      h_adm_ctl[j] = r.ctl;
+      ga.slot[j] = slot; ga.lrow[j] = mine[0]; ga.samp[j] = m | (N << 16);
+      if (m > 0) {
+        const int k = kv.n_ent++;
+        kv.src[k] = mine[0]; kv.dst0[k] = slot; kv.cnt[k] = 1; kv.p0[k] = 0; kv.p1[k] = r.job.Lx + r.job.T + 1;
+      }
+      volatile int* rec = e->h_rec + slot * VC_SESS_REC;    // the slot's record: empty until its row retires
+      for (int i = 0; i < VC_SESS_REC; ++i) rec[i] = 0;
+    }
   }
-  const int n_new = ta.n_new;
+  const int n_new = ta.n_new;                               // ROWS admitted this turn
   if (t.live + n_new == 0) {
     // nothing to decode: what is still queued is steps without a live sequence.  Wait for them and queue nothing more; a later
     // submit (or the fetch that frees a slot for a pending request) restarts the loop.
@@ -2307,6 +2401,21 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
     HIPCHK(e, hipEventRecord(t.ev_adm[ei][0], s));
     int rc = prefill_batch(e, pas, slots, s, true);
     if (rc) return rc;
+    if (kv.n_ent > 0) {
+      // prefill once, replicate: prompt positions [0, Lx + T + 1) of each group's first slot to its siblings' slots, one launch per
+      // cache tensor for every group of the turn.  The first-step logits are not copied: every member's first sample reads the row
+      // of the group's first slot (session_groups_k)
+      kv.n_dst = kv.n_ent;
+      const long esz = e->dtype == VC_DTYPE_BF16 ? 2 : 4;
+      kv.H = e->H; kv.head_stride_b = (long)e->S_max * e->hd * esz; kv.pos_b = (long)e->hd * esz;
+      kv.seq_stride_b = (long)e->H * kv.head_stride_b;
+      for (int l = 0; l < e->L; ++l) {
+        kv.base = (char*)e->layers[l].kc;
+        HIPCHK(e, vc_launch_copy_kv(kv, s));
+        kv.base = (char*)e->layers[l].vc;
+        HIPCHK(e, vc_launch_copy_kv(kv, s));
+      }
+    }
     HIPCHK(e, hipMemcpyAsync(e->adm_st, h_adm_st, sizeof(SeqState) * n_new, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(e->adm_ctl, h_adm_ctl, sizeof(vc_request_ctl) * n_new, hipMemcpyHostToDevice, s));
   }
@@ -2316,16 +2425,20 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
   ta.ctl_tab = e->ctl_tab; ta.adm_st = e->adm_st; ta.adm_ctl = e->adm_ctl;
   ta.B_old = t.B; ta.B_new = w; ta.d = e->d; ta.batch = t.batch; ta.repack = (n_new > 0 || w != t.B) ? 1 : 0;
   HIPCHK(e, vc_launch_session_turn(ta, s));
+  if (t.grouped && n_new > 0) {
+    ga.adm_slot = e->adm_slot; ga.samp_tab = e->samp_tab; ga.n_new = n_new;
+    HIPCHK(e, vc_launch_session_groups(ga, e->NS, s));
+  }
   if (t.B > 0 && w > t.B) t.stats[3] += 1;
   if (w < t.B) t.stats[4] += 1;
   t.B = w;
   t.L.B = w; t.L.sa = make_sample_args(e, w, 1);
   if (n_new > 0) {
-    HIPCHK(e, vc_launch_sample_session(t.L.sa, true, n_new, s));
+    HIPCHK(e, vc_launch_sample_session(t.L.sa, true, n_new, t.grouped, s));
     HIPCHK(e, hipEventRecord(t.ev_adm[ei][1], s));
     t.ev_turn[ei] = t.batch;
-    t.stats[0] += n_new;
-    if (live_before > 0) t.stats[1] += n_new;
+    t.stats[0] += n_req;                                     // requests; the row sums [5], [6] count every sample's rows
+    if (live_before > 0) t.stats[1] += n_req;
     t.live += n_new;
   }
   int rc = VC_OK;
@@ -2334,7 +2447,7 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
     if ((rc = t.L.exec_for(&exec))) return rc;
     HIPCHK(e, hipGraphLaunch(exec, s));
   } else {
-    for (int i = 0; i < G && rc == VC_OK; ++i) rc = decode_step(e, t.L.sa, w, 1, false, s, true);
+    for (int i = 0; i < G && rc == VC_OK; ++i) rc = decode_step(e, t.L.sa, w, 1, t.grouped, s, true);
     if (rc) return rc;
   }
   HIPCHK(e, hipEventRecord(e->ev_pace[t.batch & 1], s));
@@ -2360,12 +2473,15 @@ extern "C" int vc_session_fetch(vc_engine* e, int ticket, int64_t* res_dev, int 
   SessReq r = std::move(it->second);
   r.edit.iv = r.iv_own.data(); r.edit.mv = r.mv_own.data();
   // whatever the outcome the ticket is spent: the slot (its K/V rows, its rows of the generated-token log) is free for the next request
-  t.slot_ticket[r.slot] = -1;
+  // (of a best-of-N request only the kept sample's slot is still held, and none when no sample terminated)
+  if (r.slot >= 0) t.slot_ticket[r.slot] = -1;
   t.reqs.erase(it);
   if (!res_dev) return VC_OK;                               // dropped
   if (!gen_len || res_cap < 0) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_fetch");
   if (r.prompt_err & 1)
     return fail(e, VC_EINVAL, "ticket %d: token id out of range in x or y (text rows %d, audio vocab %d)", ticket, e->cfg.text_rows, e->V);
+  if (r.n_samples > 1 && r.kept < 0)
+    return fail(e, VC_ECAP, "ticket %d: no sample terminated within the step budget", ticket);
   SeqState st;              // what the assembly reads of the request's final state, from the slot's record
   memset(&st, 0, sizeof st);
   st.done = 1; st.span = r.span; st.total_steps = r.total_steps;
@@ -2382,6 +2498,21 @@ extern "C" int vc_session_fetch(vc_engine* e, int ticket, int64_t* res_dev, int 
   if (rc) return rc;
   HIPCHK(e, hipStreamSynchronize(e->side_stream));
   if (n_steps) *n_steps = r.total_steps;
+  return VC_OK;
+}
+
+extern "C" int vc_session_kept(vc_engine* e, int ticket, int* kept) {
+  if (!e) return VC_EINVAL;
+  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
+  if (!kept) return fail(e, VC_EINVAL, "null argument to vc_session_kept");
+  Session& t = *e->sess;
+  auto it = t.reqs.find(ticket);
+  if (it == t.reqs.end()) return fail(e, VC_EINVAL, "vc_session_kept: unknown ticket %d (never issued, or fetched already)", ticket);
+  if (it->second.state != 2) {
+    if (t.broken) return session_broken(e, t);
+    return fail(e, VC_ESTATE, "vc_session_kept: the request of ticket %d has not finished", ticket);
+  }
+  *kept = it->second.n_samples > 1 ? it->second.kept : 0;   // (-1: no sample of the group terminated - the fetch returns VC_ECAP)
   return VC_OK;
 }
 
@@ -2426,6 +2557,9 @@ extern "C" int vc_session_frames(vc_engine* e, int n, const int* tickets, int mi
     if (it->second.kind == 1)
       return fail(e, VC_EINVAL, "vc_session_frames: ticket %d: editing requests do not stream (their rows per batch hang on span "
                   "switches known at retirement only, and their result is a splice)", tickets[i]);
+    if (it->second.n_samples > 1)
+      return fail(e, VC_EINVAL, "vc_session_frames: ticket %d: best-of-N requests do not stream (the kept sample is unknown until the "
+                  "group decides)", tickets[i]);
     for (int k = 0; k < i; ++k)
       if (tickets[k] == tickets[i]) return fail(e, VC_EINVAL, "vc_session_frames: ticket %d given twice", tickets[i]);
   }
@@ -2939,6 +3073,14 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
     if (nbytes != 3 * 4) return fail(e, VC_ECAP, "debug buffer 'stream' holds 12 bytes");
     const int32_t v[3] = {1 + e->ts->L.complete, e->ts->emitted, e->ts->L.over ? 1 : 0};
     memcpy(host_dst, v, sizeof v);
+    return VC_OK;
+  }
+  else if (n == "session_slots") {  // the open decode session's bookkeeping: {rows of the step in force, ticket holding slot 0, 1, ... (-1 = free)}
+    if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
+    std::vector<int32_t> v{e->sess->B};
+    v.insert(v.end(), e->sess->slot_ticket.begin(), e->sess->slot_ticket.end());
+    if (nbytes != (int64_t)(v.size() * 4)) return fail(e, VC_ECAP, "debug buffer 'session_slots' holds %lld bytes", (long long)(v.size() * 4));
+    memcpy(host_dst, v.data(), (size_t)nbytes);
     return VC_OK;
   }
   else return fail(e, VC_EINVAL, "unknown debug buffer '%s'", n.c_str());

@@ -431,6 +431,8 @@ __device__ __forceinline__ void sample_phase(const SampleArgs& a, const SampleDy
 // the next decode rows (embedding sum + position, voicecraft.py:1102-1116; span switch :838-858).
 // SESS (a literal at every call site, as in sample_phase): the block that retires a sequence writes the slot's record for the host
 // (SampleDyn.retire_rec), stamped with the index of the graph batch the step belongs to, next to the n_active update.
+// grouped && SESS (session_advance_only_k): the keep decision of a session opened for best-of-N requests, and the row's `kept` in its
+// retirement record.
 __device__ void advance_phase(const SampleArgs& a, const SampleDyn& dy, int b, bool grouped, SeqState* sp, const int* xs,
                               const bool SESS) {
   __shared__ int s_tok[VC_MAX_CODEBOOKS];
@@ -438,7 +440,37 @@ __device__ void advance_phase(const SampleArgs& a, const SampleDyn& dy, int b, b
   __shared__ int s_ylen, s_mask, s_Lx, s_keep;
   const int tid = threadIdx.x;
   const int K = a.K;
-  if (grouped) {
+  if (grouped && SESS) {
+    // a session opened for best-of-N requests: the ballot below with the group's geometry taken from the REQUEST - group = its ticket
+    // (SeqState.group; -1 = a plain or editing request, which decides nothing), sample index j and count N from samp_tab[slot].  The
+    // members' slots are whatever was free at admission, so a member is recognised by its group and its own sample index; they still
+    // sit on consecutive rows in sample order while the terminator is ahead (laid so at admission, session_turn_k compacts in order)
+    if (tid < 64) {
+      int keep = -1;
+      if (!sp->done && !sp->feed && sp->n_eog == 0 && sp->group >= 0) {        // wave-uniform (LDS)
+        const int group = sp->group, gs = dy.samp_tab[sp->slot];
+        const int j = gs & 0xffff, N = gs >> 16;
+        const int r = b - j + tid;                            // row of sample `tid`
+        bool bad = j >= N || N < 1 || N > 64, flag = false;
+        if (!bad && tid < N) {
+          bad = r < 0 || r >= a.B;
+          if (!bad) {
+            const int rslot = a.st[r].slot;                   // immutable during the step, as is the group
+            bad = a.st[r].group != group || rslot < 0;
+            if (!bad) bad = dy.samp_tab[rslot] != (tid | (N << 16));
+            flag = a.samp[r * (VC_MAX_CODEBOOKS + 2) + K + 1] != 0;
+          }
+        }
+        const uint64_t fb = __ballot(flag && !bad), bb = __ballot(bad);
+        keep = fb ? 63 - __clzll((long long)fb) : -1;
+        if (tid == 0 && bb) atomicOr(a.err, 8);
+        if (tid == 0 && keep >= 0) keep = (keep == j) ? -2 : keep;   // -2: this block is the keeper
+      }
+      if (tid == 0) s_keep = keep;
+    }
+    __syncthreads();
+  }
+  if (grouped && !SESS) {
     // best-of-N (voicecraft.py:1296-1302): the LAST sample whose first codebook terminates is kept.  While the group's terminator is
     // still ahead (n_eog == 0) every member is live and the members sit on consecutive rows in sample order (they start that way and
     // repack_k keeps the live rows in order), so sample m of this block's group is row b - j + m: one lane per member reads that
@@ -566,6 +598,7 @@ __device__ void advance_phase(const SampleArgs& a, const SampleDyn& dy, int b, b
           __hip_atomic_store(rec + 2, span, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
           __hip_atomic_store(rec + 3, s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
           __hip_atomic_store(rec + 5, fed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          if (grouped) __hip_atomic_store(rec + 6, kept, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 #pragma unroll
           for (int i = 0; i < VC_MAX_SPANS; ++i)
             __hip_atomic_store(rec + VC_SESS_REC_SPANS + i, ss[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -819,7 +852,84 @@ __global__ __launch_bounds__(256) void sample_session_k(const SampleArgs a) {
   advance_phase(a, dy, b, false, &s_st, s_xs, true);
   store_state(a, b, &s_st);
 }
-hipError_t vc_launch_sample_session(const SampleArgs& a, bool first, int n, hipStream_t s) {
+// ---- sessions opened for best-of-N requests (vc_session_open_best_of): the same step as a sample / advance PAIR, sample_only_k and
+// advance_only_k in their session forms.  A group's keep decision reads every member's terminator flag (SampleArgs.samp), so it needs
+// the kernel boundary; a group can be decided by its very first sample (arg-max or length-cap rule), so the FIRST forms are a pair
+// too.  Nothing waits for another workgroup inside a launch.
+template <bool FIRST>
+__device__ __forceinline__ void session_sample_only(const SampleArgs& a) {
+  __shared__ SeqState s_st;
+  int b = blockIdx.x, lrow = blockIdx.x;
+  if (FIRST) { b = *a.dyn->row_base + (int)blockIdx.x; lrow = a.dyn->adm_slot[blockIdx.x]; }
+  float v0[VC_VPL];
+  preload_row(a, lrow, v0);
+  const int sw = fetch_state(a, b);
+  const int active = *a.n_active;
+  const SampleDyn dy = *a.dyn;
+  __builtin_amdgcn_sched_barrier(0);
+  if (active == 0) return;
+  if (!FIRST && blockIdx.x == 0 && threadIdx.x == 0) {
+    const int c = *a.step_ctr;
+    *a.step_ctr = c + 1;
+    __hip_atomic_store(a.host_live + ((c / a.graph_steps) & 1), active, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  park_state(&s_st, sw);
+  const int slot = s_st.slot;
+  if (s_st.done || s_st.feed || slot < 0) {      // a row that draws nothing raises no keep flag: its entry may hold a stale one (sample_only_k)
+    if (threadIdx.x == 0) a.samp[b * (VC_MAX_CODEBOOKS + 2) + a.K + 1] = 0;
+    return;
+  }
+  // The row is sample j of a request of N (samp_tab[slot]), and what it draws is what sequence j of the request's own blocking call
+  // vc_tts(n_samples = N) draws: sample_phase in its one-shot form (SESS = false), on a private copy of the sampler values that
+  // holds the REQUEST's seed and controls, and on a parked state whose index in the call is j (the Philox stream is (seed, sequence j,
+  // step, codebook), whatever slots the group landed in).  The parked copy is not stored back: session_advance_only_k reads the
+  // state from memory, with the row's real slot.  (Sessions take no forced draws and no logits_out, the other users of that index.)
+  const vc_request_ctl rq = dy.ctl_tab[slot];
+  SampleDyn dq = dy;
+  dq.seed = dy.seed_tab[slot];
+  dq.top_k = rq.top_k; dq.top_p = rq.top_p; dq.temperature = rq.temperature; dq.stop_repetition = rq.stop_repetition;
+  dq.forced = nullptr; dq.logits_out = nullptr;
+  const int j = dy.samp_tab[slot] & 0xffff;
+  __syncthreads();                               // every thread has read the slot
+  if (threadIdx.x == 0) s_st.slot = j;
+  __syncthreads();
+  sample_phase(a, dq, b, lrow, &s_st, a.samp + b * (VC_MAX_CODEBOOKS + 2), s_dyn, v0, false);
+}
+template <bool FIRST>
+__device__ __forceinline__ void session_advance_only(const SampleArgs& a) {
+  __shared__ SeqState s_st;
+  int b = blockIdx.x;
+  if (FIRST) b = *a.dyn->row_base + (int)blockIdx.x;
+  const int sw = fetch_state(a, b);
+  const int active = *a.n_active;
+  const SampleDyn dy = *a.dyn;
+  __builtin_amdgcn_sched_barrier(0);
+  if (active == 0) return;
+  park_state(&s_st, sw);
+  advance_phase(a, dy, b, true, &s_st, a.samp + b * (VC_MAX_CODEBOOKS + 2), true);
+  store_state(a, b, &s_st);
+}
+// (the kernels: advance_only_k's state-machine tail is theirs too, one thread's few stores behind the keep decision - a cold path)
+__global__ __launch_bounds__(256) void session_sample_only_k(const SampleArgs a) { session_sample_only<false>(a); }
+__global__ __launch_bounds__(256) void session_first_sample_only_k(const SampleArgs a) { session_sample_only<true>(a); }
+__global__ __launch_bounds__(256) void session_advance_only_k(const SampleArgs a) { session_advance_only<false>(a); }
+__global__ __launch_bounds__(256) void session_first_advance_only_k(const SampleArgs a) { session_advance_only<true>(a); }
+hipError_t vc_launch_sample_session(const SampleArgs& a, bool first, int n, bool grouped, hipStream_t s) {
+  if (grouped) {
+    if (a.K < 1 || a.K > VC_MAX_CODEBOOKS || a.V < 1 || a.V > 64 * VC_VPL || n < 1 || n > VC_MAX_SEQS || n > a.B) return hipErrorInvalidValue;
+    const size_t lds = (size_t)a.K * (((a.V + 63) >> 6) << 6) * sizeof(float);
+    static size_t granted_gstep[16] = {0}, granted_gfirst[16] = {0};
+    if (hipError_t e = sample_lds_limit(reinterpret_cast<const void*>(first ? session_first_sample_only_k : session_sample_only_k), lds,
+                                        first ? granted_gfirst : granted_gstep); e != hipSuccess) return e;
+    if (first) {
+      hipLaunchKernelGGL(session_first_sample_only_k, dim3(n), dim3(256), lds, s, a);
+      hipLaunchKernelGGL(session_first_advance_only_k, dim3(n), dim3(256), 0, s, a);
+    } else {
+      hipLaunchKernelGGL(session_sample_only_k, dim3(n), dim3(256), lds, s, a);
+      hipLaunchKernelGGL(session_advance_only_k, dim3(n), dim3(256), 0, s, a);
+    }
+    return hipGetLastError();
+  }
   if (a.K < 1 || a.K > VC_MAX_CODEBOOKS || a.V < 1 || a.V > 64 * VC_VPL || n < 1 || n > VC_MAX_SEQS) return hipErrorInvalidValue;
   const size_t lds = (size_t)a.K * (((a.V + 63) >> 6) << 6) * sizeof(float);
   static size_t granted_step[16] = {0}, granted_first[16] = {0};
@@ -973,6 +1083,23 @@ hipError_t vc_launch_session_turn(const SessTurnArgs& a, hipStream_t s) {
   if (a.B_old < 0 || a.B_old > VC_MAX_SEQS || a.B_new < 1 || a.B_new > VC_MAX_SEQS || a.n_new < 0 || a.n_new > a.B_new || a.d > 2048)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(session_turn_k, dim3(1), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+// ---- sessions opened for best-of-N requests: what a turn that admits adds to session_turn_k, as a launch of its own behind it (so
+// that the turn kernel keeps its code).  A request of N samples is N admitted ROWS, one per sample, each with its own slot: the first
+// sample of row i reads the logits row of the slot the request's prompt was prefilled into (the group's first slot, not its own),
+// and the entry of samp_tab of its slot takes its sample index and count.  One workgroup, once per admitting turn, between batches.
+__global__ __launch_bounds__(64) void session_groups_k(const SessGroupArgs g) {
+  const int i = threadIdx.x;
+  if (i >= g.n_new) return;
+  g.adm_slot[i] = g.lrow[i];
+  g.samp_tab[g.slot[i]] = g.samp[i];
+}
+hipError_t vc_launch_session_groups(const SessGroupArgs& g, int max_seqs, hipStream_t s) {
+  if (g.n_new < 1 || g.n_new > VC_MAX_SEQS || !g.adm_slot || !g.samp_tab) return hipErrorInvalidValue;
+  for (int i = 0; i < g.n_new; ++i)     // (a logic error of the host must not become an access outside the tables or the logits buffer)
+    if (g.lrow[i] < 0 || g.lrow[i] >= max_seqs || g.slot[i] < 0 || g.slot[i] >= max_seqs) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_groups_k, dim3(1), dim3(64), 0, s, g);
   return hipGetLastError();
 }
 

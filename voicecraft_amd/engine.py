@@ -343,37 +343,48 @@ class VoiceCraftEngine:
 
     # ---- decode sessions: continuous batching (include/vc_engine.h vc_session_*)
     def open_session(self, max_live: int | None = None, top_k: int = -100, top_p: float = 1.0, temperature: float = 1.0,
-                     stop_repetition: int = 3, silence_tokens: Iterable[int] = (1388, 1898, 131), **unsupported) -> "DecodeSession":
+                     stop_repetition: int = 3, silence_tokens: Iterable[int] = (1388, 1898, 131), max_samples: int = 1,
+                     **unsupported) -> "DecodeSession":
         """A decode session over `max_live` K/V slots (default max_seqs): TTS requests with inference_tts semantics and editing
-        requests with inference semantics, one sample each, submitted at any time, each joining the running batch between two graph
-        batches and handed back as soon as it ends.  top_k / top_p / temperature / stop_repetition given here are the default of a
+        requests with inference semantics, submitted at any time, each joining the running batch between two graph batches and
+        handed back as soon as it ends.  max_samples > 1 opens it for best-of-N TTS requests as well (DecodeSession.submit(...,
+        n_samples=N), N <= max_samples <= max_live: inference_tts_batch(batch_size=N) semantics, one ticket, N slots); its steps
+        then end in two sampler launches instead of one.  top_k / top_p / temperature / stop_repetition given here are the default of a
         request that brings none of its own (DecodeSession.submit / submit_edit); silence_tokens are the session's; the seed is per
         request.  Use it as a context manager.
-        Best-of-N, a shared text prefix, logits_out and forced trajectories are not part of a session and are refused."""
+        A shared text prefix, logits_out and forced trajectories are not part of a session and are refused."""
         if unsupported:
-            raise AssertionError(f"open_session: {sorted(unsupported)} not supported - a decode session takes TTS and editing requests, "
-                                 "one sample each (no best-of-N batch_size, no _shared_text_prefix, no _logit_steps, no _forced "
-                                 "trajectories): use the blocking calls for those")
-        return DecodeSession(self, self.max_seqs if max_live is None else int(max_live),
-                             self._sample_cfg(top_k, top_p, temperature, stop_repetition, silence_tokens, 0))
+            raise AssertionError(f"open_session: {sorted(unsupported)} not supported - a decode session takes TTS and editing requests "
+                                 "(best-of-N is per request: open_session(max_samples=N), submit(n_samples=N), not batch_size; no "
+                                 "_shared_text_prefix, no _logit_steps, no _forced trajectories): use the blocking calls for those")
+        max_live = self.max_seqs if max_live is None else int(max_live)
+        assert 1 <= int(max_samples) <= max_live, f"open_session: max_samples {max_samples} outside [1, max_live = {max_live}]"
+        return DecodeSession(self, max_live, self._sample_cfg(top_k, top_p, temperature, stop_repetition, silence_tokens, 0),
+                             max_samples=int(max_samples))
 
     @torch.no_grad()
-    def inference_tts_queue(self, xs, ys, max_live: int | None = None, seeds=None, **sampling):
+    def inference_tts_queue(self, xs, ys, max_live: int | None = None, seeds=None, batch_size: int = 1, **sampling):
         """Any number of utterances through `max_live` slots of one decode session (default max_seqs): a freed slot is refilled with
         the next utterance while the others go on decoding.  xs: list of int64 [Lx_i]; ys: list of int64 [T_i,K]; seeds: one per
         utterance (default: drawn from torch's generator, as _sample_cfg does).  Returns the list of (res [1,K,T_i+Tg_i], gen) in
-        input order - the return type of inference_tts_multi.  self.last_session_stats holds the session's stats()."""
+        input order - the return type of inference_tts_multi.  self.last_session_stats holds the session's stats().
+        batch_size N > 1: best-of-N per utterance, as inference_tts_multi(batch_size=N) - every utterance is a request of N samples
+        (N slots), the kept samples' (res, gen) are returned and self.last_kept lists the kept sample index of every utterance."""
         assert len(xs) == len(ys) and len(xs) >= 1, (len(xs), len(ys))
         assert seeds is None or len(seeds) == len(xs), "one seed per utterance"
+        N = int(batch_size)
+        assert N >= 1, f"batch_size must be at least 1, got {batch_size}"
         K = self.args.n_codebooks
-        with self.open_session(max_live, **sampling) as sess:
+        with self.open_session(max_live, max_samples=N, **sampling) as sess:
             tickets = []
             for i, (xv, yv) in enumerate(zip(xs, ys)):
                 xv = torch.as_tensor(xv, dtype=torch.int64).reshape(1, -1)
                 yv = torch.as_tensor(yv, dtype=torch.int64).reshape(1, -1, K)
-                tickets.append(sess.submit(xv, torch.tensor([xv.shape[1]]), yv, seed=None if seeds is None else seeds[i]))
+                tickets.append(sess.submit(xv, torch.tensor([xv.shape[1]]), yv, seed=None if seeds is None else seeds[i], n_samples=N))
             done = {t: (res, gen) for t, res, gen in sess.drain()}
             self.last_session_stats = sess.stats()
+            if N > 1:
+                self.last_kept = [sess.kept[t] for t in tickets]
         return [done[t] for t in tickets]
 
     @torch.no_grad()
@@ -730,8 +741,10 @@ class DecodeSession:
 
     STATS = ("admitted", "admitted_while_live", "turns", "widenings", "narrowings", "live_rows", "launched_rows", "admission_us")
 
-    def __init__(self, engine: VoiceCraftEngine, max_live: int, sc: SampleCfg):
-        self.engine, self.max_live = engine, int(max_live)
+    def __init__(self, engine: VoiceCraftEngine, max_live: int, sc: SampleCfg, max_samples: int = 1):
+        self.engine, self.max_live, self.max_samples = engine, int(max_live), int(max_samples)
+        self.kept: dict[int, int] = {}        # ticket -> kept sample index of every best-of-N request fetched so far (submit(n_samples=N))
+        self._best_of: set[int] = set()       # unfetched best-of-N tickets
         self._open = False
         self._reqs: dict[int, tuple] = {}     # ticket -> (x, y, T, Lx, M): the device tensors stay alive until the ticket is fetched
                                               # (M: spans of an editing request, 0 = TTS)
@@ -744,7 +757,11 @@ class DecodeSession:
         # uploads and result arithmetic run on a stream of the session's own: a launch on the null stream would wait for the decode
         # batches queued on the engine's stream (as in _tts_stream)
         self._side = torch.cuda.Stream(device=engine.device)
-        check(engine.lib.vc_session_open(engine._h, self.max_live, C.byref(sc), engine._stream()), engine._h, "vc_session_open")
+        if self.max_samples > 1:
+            check(engine.lib.vc_session_open_best_of(engine._h, self.max_live, self.max_samples, C.byref(sc), engine._stream()),
+                  engine._h, "vc_session_open_best_of")
+        else:
+            check(engine.lib.vc_session_open(engine._h, self.max_live, C.byref(sc), engine._stream()), engine._h, "vc_session_open")
         self._open = True
 
     def __enter__(self):
@@ -782,20 +799,33 @@ class DecodeSession:
         self._side.synchronize()                 # the prompt is on the device before the prefill that reads it can be queued
         return xd, Lx, yd, T
 
-    def submit(self, x, x_lens, y, seed=None, stream: bool = False, **controls) -> int:
+    def submit(self, x, x_lens, y, seed=None, stream: bool = False, n_samples: int = 1, **controls) -> int:
         """A TTS request: x [1,Lx'], x_lens [1], y [1,T,K] as inference_tts takes them (same checks, same special_first handling).
         controls: any of top_k, top_p, temperature, stop_repetition for this request alone; the others are the session's.
         stream=True: the request's frames are handed out by poll_frames() while it decodes (editing requests do not stream:
-        submit_edit has no such argument); poll() / drain() return its (ticket, res, gen) as for any other."""
+        submit_edit has no such argument); poll() / drain() return its (ticket, res, gen) as for any other.
+        n_samples N > 1 (a session opened with max_samples >= N): a best-of-N request, inference_tts_batch(batch_size=N) on this
+        prompt with this seed - N slots, one ticket; the kept sample's (res, gen) comes back and self.kept[ticket] is its index.
+        Such a request does not stream (the kept sample is unknown until the group decides); editing requests have no such form."""
         assert self._open, "the session is closed"
         eng = self.engine
+        N = int(n_samples)
+        assert 1 <= N <= self.max_samples, (f"submit: n_samples {n_samples} outside [1, max_samples = {self.max_samples}] of this "
+                                            "session (open_session(max_samples=...))")
+        assert not (stream and N > 1), "submit: best-of-N requests do not stream (the kept sample is unknown until the group decides)"
         ctl = self._ctl("submit", controls)
         xd, Lx, yd, T = self._upload(x, x_lens, y)
         sd = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
         ticket = C.c_int(0)
-        check(eng.lib.vc_session_submit_ctl(eng._h, C.c_void_p(xd.data_ptr()), Lx, C.c_void_p(yd.data_ptr()), T,
-                                            C.byref(ctl) if ctl is not None else None, sd, C.byref(ticket)),
-              eng._h, "vc_session_submit")
+        if N > 1:
+            check(eng.lib.vc_session_submit_best_of(eng._h, C.c_void_p(xd.data_ptr()), Lx, C.c_void_p(yd.data_ptr()), T, N,
+                                                    C.byref(ctl) if ctl is not None else None, sd, C.byref(ticket)),
+                  eng._h, "vc_session_submit_best_of")
+            self._best_of.add(ticket.value)
+        else:
+            check(eng.lib.vc_session_submit_ctl(eng._h, C.c_void_p(xd.data_ptr()), Lx, C.c_void_p(yd.data_ptr()), T,
+                                                C.byref(ctl) if ctl is not None else None, sd, C.byref(ticket)),
+                  eng._h, "vc_session_submit")
         self._reqs[ticket.value] = (xd, yd, T, Lx, 0)
         if stream:
             self._streaming.add(ticket.value)
@@ -839,9 +869,14 @@ class DecodeSession:
             cap = T + eng._gen_budget(Lx, T + 1, eng.args.encodec_sr // 5)
         res = torch.empty((K, cap), dtype=torch.int64, device=eng.device)
         gen_len, n_steps = C.c_int(0), C.c_int(0)
+        if int(ticket) in self._best_of:        # the kept sample's index, while the ticket still exists
+            k = C.c_int(-1)
+            if eng.lib.vc_session_kept(eng._h, int(ticket), C.byref(k)) == 0:
+                self.kept[int(ticket)] = int(k.value)
         rc = eng.lib.vc_session_fetch(eng._h, int(ticket), C.c_void_p(res.data_ptr()), cap, C.byref(gen_len), C.byref(n_steps))
         if rc != -2:                           # (an unfinished request keeps its ticket)
             self._reqs.pop(int(ticket), None)
+            self._best_of.discard(int(ticket))
         check(rc, eng._h, "vc_session_fetch")
         eng.last_steps = n_steps.value
         if M:                                    # (gen_len is the result length T' of an edit ticket)
@@ -982,12 +1017,14 @@ class DecodeSession:
             self._reqs.clear()          # the prompts stay valid until the decode stream has been waited for
             self._ready = []
             self._streaming.clear()
+            self._best_of.clear()
             self._tail = []
 
 
-def inference_tts_queue(engine: VoiceCraftEngine, xs, ys, max_live: int | None = None, seeds=None, **sampling):
-    """VoiceCraftEngine.inference_tts_queue as a function: any number of utterances through `max_live` slots of one decode session."""
-    return engine.inference_tts_queue(xs, ys, max_live=max_live, seeds=seeds, **sampling)
+def inference_tts_queue(engine: VoiceCraftEngine, xs, ys, max_live: int | None = None, seeds=None, batch_size: int = 1, **sampling):
+    """VoiceCraftEngine.inference_tts_queue as a function: any number of utterances through `max_live` slots of one decode session
+    (batch_size N > 1: best-of-N per utterance, the kept indices in engine.last_kept)."""
+    return engine.inference_tts_queue(xs, ys, max_live=max_live, seeds=seeds, batch_size=batch_size, **sampling)
 
 
 def inference_queue(engine: VoiceCraftEngine, xs, ys, mask_intervals, max_live: int | None = None, seeds=None, **sampling):
