@@ -286,6 +286,25 @@ int vc_tts_stream_end(vc_engine* e, int64_t* res_dev, int res_cap, int* gen_len,
  *            stream": its rows per batch hang on span switches the host learns at retirement, and its result is a splice), a best-of-N
  *            ticket ("best-of-N requests do not stream": the kept sample is unknown until the group decides), n outside
  *            [1, max_live], cap < 1, min_frames outside [1, cap], null pointers.  No session: VC_ESTATE; a broken session: its error.
+ *   cancel   takes one request out of the session, in whatever state it is; *was (may be NULL) = the state it was in: 0 pending, 1 live,
+ *            2 finished and not yet fetched.  The call never waits for the device and queues nothing.  From it on the ticket is gone:
+ *            advance never reports it, and fetch / kept / frames / cancel refuse it as an unknown ticket.  No partial result comes
+ *            back (stream the request to have its frames; frames already handed out stay valid, a prefix of what it would have made).
+ *            Pending: it leaves the FIFO at once, the order of the others unchanged, and its x_dev / y_dev are never read; if it was
+ *            blocking the head of the line the next advance admits whatever now fits.  Finished: exactly fetch(res_dev = NULL), the
+ *            slot is free at once (so is a request that has retired in a batch advance has seen end but could not report, tickets_out
+ *            being full).  Live: the next advance retires every row of the ticket that has not retired yet (a TTS or editing
+ *            request's one row, an edit in the middle of a span switch included; every remaining member of a best-of-N group) in one
+ *            launch for all cancels made since the last turn, in front of its re-pack.  The slots come back the way any retired row's
+ *            do - when advance has seen the batch end that the retirement is stamped with: a cancel made before the turn that queues
+ *            batch c frees its slots in the turn that queues batch c + 2, that is 2 * graph_steps steps later, so admissions, widths
+ *            and bf16 tokens stay a function of the schedule of submissions AND cancels.  A ticket found finished by the same advance
+ *            that applies its cancel is dropped, not reported.  Cancelling every live request leads to *idle = 1 as usual.  The
+ *            x_dev / y_dev of a cancelled LIVE ticket may still be read by the prefill queued by the turn that admitted it: they must
+ *            stay valid until the second advance after the cancel has returned, or until the session is closed.  A cancelled request
+ *            that had been admitted stays counted in stats [0], and the rows it really ran in [5].  Unknown ticket, or one fetched or
+ *            cancelled already: VC_EINVAL naming the ticket, and the session goes on.  No session: VC_ESTATE; a broken session: its
+ *            error.
  *   close    waits for what is queued, drops everything pending and unfetched; the engine is reusable. */
 typedef struct vc_request_ctl {   /* 16 bytes: the per-request part of vc_sample_cfg, same meaning field by field */
   int32_t top_k;
@@ -308,6 +327,7 @@ int vc_session_fetch(vc_engine* e, int ticket, int64_t* res_dev, int res_cap, in
 int vc_session_kept(vc_engine* e, int ticket, int* kept);
 int vc_session_frames(vc_engine* e, int n, const int* tickets, int min_frames, int64_t* codes_dev, int cap,
                       int* first_frame, int* n_frames, int* done);
+int vc_session_cancel(vc_engine* e, int ticket, int* was);
 int vc_session_stats(vc_engine* e, int64_t out[8]);
 int vc_session_close(vc_engine* e);
 

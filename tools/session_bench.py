@@ -28,7 +28,16 @@ the same frames; admission_stream_ms_per_request then contains the K/V copies to
 One JSON line: per-request time to first audio (from the moment all requests were submitted; drain arm: to the end of that request's
 decode) and the total time of both arms, interleaved pairs; both arms' audio lengths are asserted equal.  A second line measures the
 codec alone: L streams of --codec-frames frames in chunks of --chunk-frames, all L in one decode_streams call per chunk against the
-same L streams fed one call each.  Every special token is muted so that the generated ids are codec ids."""
+same L streams fed one call each.  Every special token is muted so that the generated ids are codec ids.
+--cancel-share F (TTS only): instead of the above, per size, that fraction of the requests (evenly spread) are VICTIMS, in three legs on
+one engine, interleaved (every request is submitted before the first turn):
+  * run:    the victims run to their end - all a caller could do before DecodeSession.cancel existed;
+  * cancel: the victims are cancelled --cancel-after turns after submission (live ones are retired by the next turn, pending ones leave
+            the queue);
+  * absent: the victims are never submitted - the bound.
+One JSON line: the SURVIVORS' codec-tokens/s of each leg (the victims' frames are not counted in any), the per-pair position of the
+cancel leg between the other two, how many victims were live and pending when cancelled, and the turns and milliseconds from the cancels
+to the return of the turn that admits the next request (the one that takes a returned slot)."""
 import argparse, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -50,9 +59,12 @@ p.add_argument("--best-of", type=int, default=1)
 p.add_argument("--stream", action="store_true")
 p.add_argument("--chunk-frames", type=int, default=8)
 p.add_argument("--codec-frames", type=int, default=200)
+p.add_argument("--cancel-share", type=float, default=0.0)
+p.add_argument("--cancel-after", type=int, default=4)
 args = p.parse_args()
 BO = args.best_of
 assert BO >= 1 and (BO == 1 or (args.edit_share == 0 and not args.stream)), "--best-of goes with TTS requests only"
+assert args.cancel_share == 0 or (BO == 1 and args.edit_share == 0 and not args.stream), "--cancel-share goes with plain TTS requests only"
 dev = torch.device("cuda", 0)
 a = synth.make_args(args.preset)
 K = a.n_codebooks
@@ -238,8 +250,63 @@ for size in args.sizes.split(","):
                           "census_of_a_joint_call": list(codec(True)[1]),
                           "joint_vs_separate_pct": stats([100.0 * (a_ / b_ - 1.0) for a_, b_ in zip(ms[True], ms[False])])}), flush=True)
 
-    if args.stream:
-        stream_leg()
+    def cancel_legs():
+        victim = [int((u + 1) * args.cancel_share) > int(u * args.cancel_share) for u in range(N)]
+
+        def leg(mode, seed):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            was, wait, mark = {"pending": 0, "live": 0, "finished": 0}, None, None
+            with eng.open_session(L, **kn) as sess:
+                tickets = {u: sess.submit(xs[u].reshape(1, -1), torch.tensor([lxs[u]]), ys[u].unsqueeze(0), seed=seed + u)
+                           for u in range(N) if not (mode == "absent" and victim[u])}
+                done, turn = {}, 0
+                while not sess.idle:
+                    if mode == "cancel" and turn == args.cancel_after:
+                        for u in range(N):
+                            if victim[u]:
+                                was[sess.cancel(tickets[u])] += 1
+                        if was["live"]:
+                            mark = (turn, time.perf_counter(), sess.stats()["admitted"])
+                    for t, res, gen in sess.poll():
+                        done[t] = int(gen.shape[2])
+                    turn += 1
+                    if mark is not None and sess.stats()["admitted"] > mark[2]:
+                        # (turns: index of the admitting turn minus index of the first turn after the cancel - 2 by the release rule)
+                        wait, mark = (turn - 1 - mark[0], (time.perf_counter() - mark[1]) * 1e3), None
+                torch.cuda.synchronize()
+                wall = time.perf_counter() - t0
+                st = sess.stats()
+            frames = [done[tickets[u]] for u in range(N) if not victim[u]]
+            return dict(tok_s=sum(frames) * K / wall, wall_ms=wall * 1e3, frames=frames, was=was, wait=wait, turns=st["turns"],
+                        live_rows=st["live_rows"], launched_rows=st["launched_rows"])
+
+        modes = ["run", "cancel", "absent"]
+        for m in modes:
+            leg(m, 0)
+        rows = {m: [] for m in modes}
+        for i in range(args.pairs):
+            for m in modes[i % 3:] + modes[: i % 3]:
+                rows[m].append(leg(m, 100 + i))
+        for r_, c_, a_ in zip(rows["run"], rows["cancel"], rows["absent"]):
+            assert r_["frames"] == c_["frames"] == a_["frames"], "the survivors generate the same frames in every leg (the length cap ends them)"
+        c0 = rows["cancel"][0]
+        out = {"workload": f"cancel legs: {args.preset} {args.dtype}, top_k={args.top_k}, {N} requests through {L} slots, {sum(victim)} of them "
+                           f"victims cancelled {args.cancel_after} turns after submission, survivors of {min(c0['frames'])}..{max(c0['frames'])} frames",
+               "pairs": args.pairs, "graph_steps": G, "victims_were": c0["was"]}
+        for m in modes:
+            out[m] = {"survivor_codec_tokens_per_s": stats([v["tok_s"] for v in rows[m]]), "wall_ms": stats([v["wall_ms"] for v in rows[m]]),
+                      "turns": rows[m][0]["turns"], "live_share_of_launched_rows": round(rows[m][0]["live_rows"] / rows[m][0]["launched_rows"], 4)}
+        # 0 = no better than letting the victims run, 1 = as good as never having had them
+        out["cancel_position_between_run_and_absent"] = stats([(c_["tok_s"] - r_["tok_s"]) / (a_["tok_s"] - r_["tok_s"])
+                                                               for r_, c_, a_ in zip(rows["run"], rows["cancel"], rows["absent"])])
+        waits = [v["wait"] for v in rows["cancel"] if v["wait"] is not None]
+        if waits:
+            out["cancel_to_next_admission"] = {"turns": stats([w[0] for w in waits]), "ms": stats([w[1] for w in waits])}
+        print(json.dumps(out), flush=True)
+
+    if args.stream or args.cancel_share > 0:
+        stream_leg() if args.stream else cancel_legs()
         del eng
         torch.cuda.empty_cache()
         continue

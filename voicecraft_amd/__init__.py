@@ -9,6 +9,7 @@ Public surface (mirrors the reference's model interface):
                                                        (continuous batching: TTS and editing requests join a running batch)
     DecodeSession.submit(stream=True) / poll_frames, AudioTokenizer.decode_streams, SessionStreamer
                                                        (frames and audio of every streaming request while the session decodes)
+    DecodeSession.cancel / SessionStreamer.cancel      (a pending, live or finished request leaves the session)
 Everything computes in libvcengine.so (HIP, gfx950); importing this package does not need a GPU,
 constructing an engine does.
 """

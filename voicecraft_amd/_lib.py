@@ -65,6 +65,7 @@ PROTOTYPES = {
     "vc_session_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vc_session_frames": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int),
                                     C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vc_session_cancel": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "vc_session_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "vc_session_close": (C.c_int, [C.c_void_p]),
     "vc_tts_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32),

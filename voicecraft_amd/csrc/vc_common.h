@@ -489,6 +489,19 @@ struct SessGroupArgs {
   int samp[VC_MAX_SEQS];    // ... sample index | sample count << 16
 };
 hipError_t vc_launch_session_groups(const SessGroupArgs& g, int max_seqs, hipStream_t s);
+// The cancels made since the last turn (vc_session_cancel of live tickets), in front of session_turn_k (session_cancel_k): every row
+// of the step in force that is not done and whose slot is in the table retires as a dropped sample does in advance_phase - done = 1,
+// kept = 0, no position, the slot's retirement record stamped with the batch the same turn queues, *n_active lowered once by the rows
+// really retired.  A row that is done already (it may have retired by itself in the batch still in flight) is left alone.
+struct SessCancelArgs {
+  SeqState* st;             // [B]
+  int* row_pos;             // [B] (one row per sequence)
+  int* n_active;
+  int* retire_rec;          // pinned host, [max_seqs][VC_SESS_REC]
+  int B, batch, n;          // rows of the step in force; the batch this turn queues (the records' stamp is batch + 1); table entries
+  int slot[VC_MAX_SEQS];    // [n] slots of the cancelled tickets' rows
+};
+hipError_t vc_launch_session_cancel(const SessCancelArgs& c, int max_seqs, hipStream_t s);
 // The session's sampler launches: first = false, one step of B rows (captured in the session's graphs); first = true, the first sample
 // of the n rows admitted this turn only (the older rows' logits are already consumed).  grouped (a session opened for best-of-N
 // requests): the sample / advance PAIR - the keep decision of a group reads every member's terminator flag, which needs the kernel boundary.

@@ -2051,6 +2051,10 @@ struct SessReq {
   std::vector<char> mdone;  // [n_samples] the member's retirement record has been read
   int members_left = 0;
   int kept = -1;            // sample index of the member that retired kept with its span finished
+  // a live request that was cancelled (vc_session_cancel): gone for every entry point, it stays in the table until the records of
+  // its rows have been read (session_note_retired), which is what frees its slots
+  bool cancelled = false;
+  bool cancel_queued = false;   // its rows are in the table of a session_cancel_k launch already queued
 };
 struct Session {
   DecodeLoop L{};
@@ -2112,6 +2116,24 @@ void session_note_retired(vc_engine* e, Session& t, int known, int* tickets_out,
     volatile int* rec = e->h_rec + slot * VC_SESS_REC;
     const int stamp = rec[0];
     if (stamp == 0 || stamp - 1 > known) continue;
+    if (r.cancelled) {
+      // a row of a cancelled request, retired by session_cancel_k or - in a batch that was still in flight when the cancel was made - by
+      // itself: the slot is free from here on, whatever the record says of `kept`, and nothing is reported (the cancel wins)
+      int m = -1;                                       // (a request of one sample has slots = {slot}, as admission laid them)
+      for (int i = 0; i < r.n_samples; ++i) if (r.slots[i] == slot) m = i;
+      if (m < 0 || r.mdone[m]) continue;
+      r.mdone[m] = 1;
+      r.members_left -= 1;
+      t.live -= 1;
+      t.stats[5] += std::max(0, (int)rec[1] - 1) + std::max(0, (int)rec[5]);
+      t.slot_ticket[slot] = -1;
+      if (r.members_left == 0) {
+        // (a kept member whose record had been read before the cancel was still holding its slot for the fetch)
+        for (int& held : t.slot_ticket) if (held == ticket) held = -1;
+        t.reqs.erase(ticket);
+      }
+      continue;
+    }
     if (r.n_samples > 1) {
       // one member of a best-of-N request.  A dropped sample's slot is free from here on; the request is finished - and reported - by
       // the turn that has read all its members' records, and only the kept sample's slot is held for the fetch
@@ -2315,6 +2337,20 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
   t.known = std::max(t.known, known);
   session_note_retired(e, t, known, tickets_out, cap, n_finished);
   session_read_timers(t, known, false);
+  // ---- the cancels made since the last turn: the slots of the cancelled tickets' rows whose records are still out, one table for
+  // session_cancel_k (queued in step 4, in front of session_turn_k).  Their slots stay taken until those records have been read
+  SessCancelArgs ca;
+  memset(&ca, 0, sizeof ca);
+  for (int slot = 0; slot < t.max_live; ++slot) {
+    const int ticket = t.slot_ticket[slot];
+    if (ticket < 0) continue;
+    const SessReq& r = t.reqs[ticket];
+    if (!r.cancelled || r.cancel_queued) continue;
+    int m = -1;
+    for (int i = 0; i < r.n_samples; ++i) if (r.slots[i] == slot) m = i;
+    if (m >= 0 && !r.mdone[m]) ca.slot[ca.n++] = slot;
+  }
+  for (auto& kv_req : t.reqs) if (kv_req.second.cancelled) kv_req.second.cancel_queued = true;
   // ---- 3: admission, FIFO, as many as have a free slot
   SessTurnArgs ta;
   memset(&ta, 0, sizeof ta);
@@ -2424,6 +2460,11 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
   ta.seed_tab = e->seed_tab; ta.prompt_err = e->prompt_err; ta.retire_rec = e->h_rec;
   ta.ctl_tab = e->ctl_tab; ta.adm_st = e->adm_st; ta.adm_ctl = e->adm_ctl;
   ta.B_old = t.B; ta.B_new = w; ta.d = e->d; ta.batch = t.batch; ta.repack = (n_new > 0 || w != t.B) ? 1 : 0;
+  if (ca.n > 0 && t.B > 0) {
+    // (stamped with the batch queued below, not the one in flight: that batch's pacing event was recorded before this launch)
+    ca.st = e->st; ca.row_pos = e->dec_row_pos; ca.n_active = e->n_active; ca.retire_rec = e->h_rec; ca.B = t.B; ca.batch = t.batch;
+    HIPCHK(e, vc_launch_session_cancel(ca, e->NS, s));
+  }
   HIPCHK(e, vc_launch_session_turn(ta, s));
   if (t.grouped && n_new > 0) {
     ga.adm_slot = e->adm_slot; ga.samp_tab = e->samp_tab; ga.n_new = n_new;
@@ -2464,7 +2505,8 @@ extern "C" int vc_session_fetch(vc_engine* e, int ticket, int64_t* res_dev, int 
   if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
   Session& t = *e->sess;
   auto it = t.reqs.find(ticket);
-  if (it == t.reqs.end()) return fail(e, VC_EINVAL, "vc_session_fetch: unknown ticket %d (never issued, or fetched already)", ticket);
+  if (it == t.reqs.end() || it->second.cancelled)
+    return fail(e, VC_EINVAL, "vc_session_fetch: unknown ticket %d (never issued, or fetched or cancelled already)", ticket);
   if (it->second.state != 2) {
     if (t.broken) return session_broken(e, t);
     return fail(e, VC_ESTATE, "vc_session_fetch: the request of ticket %d has not finished", ticket);
@@ -2507,12 +2549,66 @@ extern "C" int vc_session_kept(vc_engine* e, int ticket, int* kept) {
   if (!kept) return fail(e, VC_EINVAL, "null argument to vc_session_kept");
   Session& t = *e->sess;
   auto it = t.reqs.find(ticket);
-  if (it == t.reqs.end()) return fail(e, VC_EINVAL, "vc_session_kept: unknown ticket %d (never issued, or fetched already)", ticket);
+  if (it == t.reqs.end() || it->second.cancelled)
+    return fail(e, VC_EINVAL, "vc_session_kept: unknown ticket %d (never issued, or fetched or cancelled already)", ticket);
   if (it->second.state != 2) {
     if (t.broken) return session_broken(e, t);
     return fail(e, VC_ESTATE, "vc_session_kept: the request of ticket %d has not finished", ticket);
   }
   *kept = it->second.n_samples > 1 ? it->second.kept : 0;   // (-1: no sample of the group terminated - the fetch returns VC_ECAP)
+  return VC_OK;
+}
+
+// Cancels a request in whatever state it is in (*was: 0 pending, 1 live, 2 finished and not yet fetched).  Host bookkeeping only: the
+// call waits for nothing and queues nothing - the rows of a live ticket are retired by session_cancel_k in the next vc_session_advance.
+extern "C" int vc_session_cancel(vc_engine* e, int ticket, int* was) {
+  if (!e) return VC_EINVAL;
+  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
+  Session& t = *e->sess;
+  if (t.broken) return session_broken(e, t);
+  auto it = t.reqs.find(ticket);
+  if (it == t.reqs.end() || it->second.cancelled)
+    return fail(e, VC_EINVAL, "vc_session_cancel: unknown ticket %d (never issued, or fetched or cancelled already)", ticket);
+  SessReq& r = it->second;
+  int state = r.state;
+  if (state == 1) {
+    // live on the host - but finished as far as the host can know, if the records of all its rows are stamped with batches advance has
+    // seen end (a turn whose tickets_out was full leaves such a request unreported): then it is a finished ticket
+    bool all_in = true;
+    for (int i = 0; i < r.n_samples && all_in; ++i) {
+      if (r.mdone[i]) continue;
+      volatile int* rec = e->h_rec + r.slots[i] * VC_SESS_REC;
+      const int stamp = rec[0];
+      all_in = stamp != 0 && stamp - 1 <= t.known;
+    }
+    if (all_in) {
+      for (int i = 0; i < r.n_samples; ++i) {
+        if (r.mdone[i]) continue;
+        volatile int* rec = e->h_rec + r.slots[i] * VC_SESS_REC;
+        t.live -= 1;
+        t.stats[5] += std::max(0, (int)rec[1] - 1) + std::max(0, (int)rec[5]);
+      }
+      for (int& held : t.slot_ticket) if (held == ticket) held = -1;
+      r.slot = -1;
+      state = 2;
+    }
+  }
+  if (state == 0) {
+    // pending: out of the line, the order of the others unchanged; its prompt is never read
+    for (auto f = t.fifo.begin(); f != t.fifo.end(); ++f)
+      if (*f == ticket) { t.fifo.erase(f); break; }
+    t.reqs.erase(it);
+  } else if (state == 2) {
+    // finished and not fetched: vc_session_fetch(res_dev = NULL)
+    if (r.slot >= 0) t.slot_ticket[r.slot] = -1;
+    t.reqs.erase(it);
+  } else {
+    // live: every row of it that has not retired is retired by the next turn, and the slots come back when the host has read their
+    // records (session_note_retired) - the path of any retirement, so the schedule stays a function of the calls alone
+    r.cancelled = true;
+    r.cancel_queued = false;
+  }
+  if (was) *was = state;
   return VC_OK;
 }
 
@@ -2552,8 +2648,8 @@ extern "C" int vc_session_frames(vc_engine* e, int n, const int* tickets, int mi
   // every refusal before any cursor moves
   for (int i = 0; i < n; ++i) {
     auto it = t.reqs.find(tickets[i]);
-    if (it == t.reqs.end())
-      return fail(e, VC_EINVAL, "vc_session_frames: unknown ticket %d (never issued, or fetched already)", tickets[i]);
+    if (it == t.reqs.end() || it->second.cancelled)
+      return fail(e, VC_EINVAL, "vc_session_frames: unknown ticket %d (never issued, or fetched or cancelled already)", tickets[i]);
     if (it->second.kind == 1)
       return fail(e, VC_EINVAL, "vc_session_frames: ticket %d: editing requests do not stream (their rows per batch hang on span "
                   "switches known at retirement only, and their result is a splice)", tickets[i]);

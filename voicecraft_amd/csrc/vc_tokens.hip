@@ -1102,6 +1102,61 @@ hipError_t vc_launch_session_groups(const SessGroupArgs& g, int max_seqs, hipStr
   hipLaunchKernelGGL(session_groups_k, dim3(1), dim3(64), 0, s, g);
   return hipGetLastError();
 }
+// ---- cancelled requests (vc_session_cancel of a live ticket): what the `drop` branch of advance_phase does for a dropped sample, decided
+// by the host at a turn boundary.  One workgroup of one wave, lane r = row r of the step in force, queued in front of session_turn_k
+// (which then compacts the cancelled rows away like any retired row).  A lane retires its row when the row is not done and its slot is
+// in the table: done = 1, kept = 0, no position (row_seq stays, as a retired row has it), and the slot's retirement record with the
+// stores of advance_phase, the stamp last.  The stamp is the batch this turn queues: the host frees the slot once it has seen THAT batch
+// end (the pacing event of the batch still in flight was recorded before this launch was queued).  A row that is done already - it may
+// have retired by itself in the batch still in flight - keeps its own record, and *n_active falls by the rows really retired.
+__global__ __launch_bounds__(64) void session_cancel_k(const SessCancelArgs c) {
+  const int r = threadIdx.x;
+  // every load before the first store (session_turn_k)
+  bool hit = false;
+  int slot = -1, total = 0, span = 0, feed = 0;
+  int ss[VC_MAX_SPANS];
+#pragma unroll
+  for (int i = 0; i < VC_MAX_SPANS; ++i) ss[i] = 0;
+  if (r < c.B) {
+    const SeqState* sp = c.st + r;
+    const int done = sp->done;
+    slot = sp->slot; total = sp->total_steps; span = sp->span; feed = sp->feed;
+#pragma unroll
+    for (int i = 0; i < VC_MAX_SPANS; ++i) ss[i] = sp->span_steps[i];
+    if (!done && slot >= 0)
+      for (int i = 0; i < c.n; ++i) hit |= c.slot[i] == slot;     // (the table is in the argument block: scalar loads)
+  }
+  const uint64_t m = __ballot(hit);
+#pragma unroll
+  for (int i = 0; i < VC_MAX_SPANS; ++i) asm volatile("" : "+v"(ss[i]));
+  if (hit) {
+    SeqState* sp = c.st + r;
+    sp->done = 1;
+    sp->kept = 0;
+    c.row_pos[r] = -1;
+    int* rec = c.retire_rec + slot * VC_SESS_REC;
+    // the rows it fed without sampling: two per span switch it began, less those of a switch it was still feeding (SeqState.feed)
+    const int fed = max(0, 2 * span - feed);
+    __hip_atomic_store(rec + 1, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(rec + 2, span, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(rec + 3, span >= 1 ? ss[0] : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(rec + 5, fed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(rec + 6, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#pragma unroll
+    for (int i = 0; i < VC_MAX_SPANS; ++i)
+      __hip_atomic_store(rec + VC_SESS_REC_SPANS + i, ss[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(rec + 0, c.batch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  if (r == 0 && m) atomicSub(c.n_active, (int)__popcll(m));
+}
+hipError_t vc_launch_session_cancel(const SessCancelArgs& c, int max_seqs, hipStream_t s) {
+  if (c.n < 1 || c.n > VC_MAX_SEQS || c.B < 1 || c.B > VC_MAX_SEQS || c.batch < 0 || !c.st || !c.row_pos || !c.n_active || !c.retire_rec)
+    return hipErrorInvalidValue;
+  for (int i = 0; i < c.n; ++i)         // (a logic error of the host must not become a store outside the records)
+    if (c.slot[i] < 0 || c.slot[i] >= max_seqs) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(session_cancel_k, dim3(1), dim3(64), 0, s, c);
+  return hipGetLastError();
+}
 
 // =============================================================== sampler test hook
 // n_draws independent draws from ONE logits row through the product filter_draw (the distribution test

@@ -733,7 +733,7 @@ class SessionRequestError(EngineError):
 class DecodeSession:
     """An open decode session of a VoiceCraftEngine (VoiceCraftEngine.open_session).  submit() queues a TTS request, submit_edit()
     an editing request; both return a ticket.  poll() runs one turn of the decode loop and returns the requests that finished;
-    drain() polls until the session is idle.  submit(..., stream=True) marks a TTS request as streaming: poll_frames() hands out its
+    drain() polls until the session is idle.  cancel() takes a request out in whatever state it is.  submit(..., stream=True) marks a TTS request as streaming: poll_frames() hands out its
     frames while it decodes, without advancing the loop (voicecraft_amd.stream.SessionStreamer turns them into audio).  While a
     session is open the engine's other decode calls and set_option raise (EngineError, VC_ESTATE)."""
 
@@ -753,6 +753,9 @@ class DecodeSession:
         self._streaming: set[int] = set()     # streaming TTS tickets whose last frame has not been pulled (submit(stream=True))
         self._tail: list = []                 # (ticket, first_frame, codes, True): what a finished streaming ticket still had, pulled
                                               # in front of its fetch and handed out by the next poll_frames
+        self.cancelled = 0                    # tickets cancelled so far (cancel())
+        self._parked: list = []               # [turns left, tensors] of cancelled live tickets: the prefill queued by the turn that admitted
+                                              # one may still read its prompt, so the tensors outlive two more turns (or close())
         self.idle = True
         # uploads and result arithmetic run on a stream of the session's own: a launch on the null stream would wait for the decode
         # batches queued on the engine's stream (as in _tts_stream)
@@ -894,6 +897,36 @@ class DecodeSession:
             self._side.synchronize()             # final on the device: usable from any stream
         return out, gen
 
+    def cancel(self, ticket: int) -> str:
+        """Takes a request out of the session: "pending" (it leaves the queue, and whatever waited behind a best-of-N head of the
+        line can go in), "live" (its rows are retired by the next turn and its slots come back two turns later, like any
+        retirement's) or "finished" (its slot is free at once) says where it was.  The ticket is gone from here on: poll() / drain()
+        never return it and poll_frames() has no further chunk for it; chunks already handed out are a prefix of what it would
+        have produced.  No partial result comes back.  An unknown, fetched or cancelled ticket raises EngineError; the session
+        goes on."""
+        assert self._open, "the session is closed"
+        eng, t = self.engine, int(ticket)
+        if any(r[0] == t for r in self._ready) or any(c[0] == t for c in self._tail):
+            # a turn has fetched it already (or pulled its last frames): the engine no longer knows it, drop what waits here
+            self._ready = [r for r in self._ready if r[0] != t]
+            self._tail = [c for c in self._tail if c[0] != t]
+            self.kept.pop(t, None)
+            self.cancelled += 1
+            return "finished"
+        was = C.c_int(-1)
+        rc = eng.lib.vc_session_cancel(eng._h, t, C.byref(was))
+        if rc == -1:
+            msg = eng.lib.vc_last_error(eng._h)
+            raise EngineError(f"vc_session_cancel failed (code {rc}): {msg.decode() if msg else ''}")
+        check(rc, eng._h, "vc_session_cancel")
+        req = self._reqs.pop(t, None)           # at once: poll_frames counts on _reqs listing only possible slot holders, in order
+        self._streaming.discard(t)
+        self._best_of.discard(t)
+        if was.value == 1 and req is not None:
+            self._parked.append([2, req])
+        self.cancelled += 1
+        return ("pending", "live", "finished")[was.value]
+
     @torch.no_grad()
     def _turn(self) -> None:
         """One turn of the decode loop.  EVERY request it reports finished is fetched: results go to self._ready; if some finished
@@ -905,6 +938,7 @@ class DecodeSession:
         n, idle = C.c_int(0), C.c_int(0)
         check(eng.lib.vc_session_advance(eng._h, tickets, cap, C.byref(n), C.byref(idle)), eng._h, "vc_session_advance")
         self.idle = bool(idle.value)
+        self._parked = [[n - 1, req] for n, req in self._parked if n > 1]
         failed = {}
         for i in range(n.value):
             t = int(tickets[i])
@@ -1019,6 +1053,7 @@ class DecodeSession:
             self._streaming.clear()
             self._best_of.clear()
             self._tail = []
+            self._parked = []
 
 
 def inference_tts_queue(engine: VoiceCraftEngine, xs, ys, max_live: int | None = None, seeds=None, batch_size: int = 1, **sampling):

@@ -46,8 +46,9 @@ class SessionStreamer:
     `tokenizer.decode` of the request's `gen`.  The finished (ticket, res, gen) of every request, streaming or not, collect in
     `.results` (take them with take_results()).  A ticket holds one of `max_live` codec stream ids from its first chunk until its
     chunk with done = True; ids are reused from a free list and reset on reuse.  poll()'s SessionRequestError passes through pump();
-    the failed tickets' streams are closed by the next pump.  Editing requests do not stream; best-of-N and shared prefixes remain
-    outside sessions."""
+    the failed tickets' streams are closed by the next pump.  cancel(ticket) cancels the request in the session, returns its codec
+    stream id to the free list and drops a result of it waiting in `.results`.  Editing and best-of-N requests do not stream (their
+    results still collect in `.results`); shared prefixes remain outside sessions."""
 
     def __init__(self, sess, tokenizer, chunk_frames: int = 8):
         self.sess, self.tok, self.chunk_frames = sess, tokenizer, int(chunk_frames)
@@ -63,6 +64,20 @@ class SessionStreamer:
     def take_results(self):
         out, self.results = self.results, []
         return out
+
+    def cancel(self, ticket: int) -> str:
+        """DecodeSession.cancel(ticket) for a request of this streamer: the ticket gets no further audio, its codec stream id is free
+        for the next ticket (reset on reuse) and a result of it waiting in `.results` is dropped ("finished")."""
+        ticket = int(ticket)
+        if any(r[0] == ticket for r in self.results):
+            self.results = [r for r in self.results if r[0] != ticket]
+            was = "finished"
+        else:
+            was = self.sess.cancel(ticket)
+        sid = self.ids.pop(ticket, None)
+        if sid is not None:
+            self.free.append(sid)
+        return was
 
     def pump(self):
         self.results += self.sess.poll()
