@@ -137,10 +137,17 @@ const char* vc_version(void);
  *                  d = 512, QKV below d = 1024), an fp32 engine, and a matrix of a layer with a fragment whose non-zero exponents span more
  *                  than 30 binades keep the bf16 launch (vc_debug_read "w13_stats": int32 [layer][FFN-down, QKV][state 0 n/a / 1 packed /
  *                  2 refused, fragments refused])
+ *   "w8"           mask of the same bits, ONLY on an engine that called vc_request_w8 (default: the requested mask; VC_EINVAL on any other
+ *                  engine): those launches stream one OCP E4M3 byte per value + one shift byte per 512-value fragment, half the bytes of the
+ *                  image, decoded to the bit-identical bf16 operands (v_cvt_scalef32_pk_bf16_fp8), for matrices whose every fragment lies on
+ *                  that grid (value = q . 2^s, q E4M3 and not its NaN code, the value a normal bf16 number or +-0; voicecraft_amd/quant.py
+ *                  puts a checkpoint there).  A matrix off the grid is refused and keeps its current launch (vc_debug_read "w8_stats",
+ *                  layout of "w13_stats").  Where a matrix has both kinds of planes the w8 bit wins.  The option text ends in |w8=<mask>
+ *                  on such an engine only.  Resident memory: + 0.5 x the requested images
  * What an option may change: nothing in the exact fp32 mode's greedy tokens (tests/test_gpu_options.py, test_gpu_one_row.py); in bf16
  * mode the forms that re-order sums or round at another place ("finished_rows", "fr_pair", "att_p16", "hq", "fr_one", "qkv_p8", "attn_fast",
  * "qkv16", "wide_heads", "wide_gemm") move head logits by bf16 rounding (tests allow 0.25 absolute), so top-k SAMPLED tokens can differ between option
- * states; the cache-policy / data-path / host-side options ("nt", "wd_stage", "graph_steps", "shrink", "w13") change no value.
+ * states; the cache-policy / data-path / host-side options ("nt", "wd_stage", "graph_steps", "shrink", "w13", "w8") change no value.
  * The non-temporal mask "nt" has no bit for the finished-row producers (rows_gemm_fr_k, rows_gemm_fr2_k, row_gemm_fr1_k) and the
  * wide-decode kernels: they always stream with the hint.  Captured decode graphs are kept per option state and step width, so an
  * in-process A/B (bench.py --ab) pays for capture once per state.  Unknown names / malformed values: VC_EINVAL.
@@ -159,6 +166,10 @@ int vc_load_tensor(vc_engine* e, const char* key, const void* data, int on_devic
  * (VC_DTYPE_BF16, or VC_DTYPE_F32 for the exact mode), builds the sinusoidal
  * position tables (models/modules/embedding.py:69-92) and frees the staging copies. */
 int vc_finalize_weights(vc_engine* e, int compute_dtype);
+/* Before vc_finalize_weights (VC_ESTATE after it): also pack the matrices of `mask` (1 FFN down-projection, 4 QKV projection; any
+ * other bit: VC_EINVAL) of every layer as E4M3 bytes for one-row steps, option "w8" above.  The form is bf16 only: vc_finalize_weights
+ * with VC_DTYPE_F32 after a non-zero request returns VC_EINVAL.  An engine without the request packs nothing more and behaves as before. */
+int vc_request_w8(vc_engine* e, int mask);
 
 /* ---- TTS: VoiceCraft.inference_tts (models/voicecraft.py:908-1153) and, with
  * n_samples > 1, VoiceCraft.inference_tts_batch (:1156-1439, best-of-N: the sample

@@ -43,6 +43,7 @@ PROTOTYPES = {
     "vc_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p]),
     "vc_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "vc_finalize_weights": (C.c_int, [C.c_void_p, C.c_int]),
+    "vc_request_w8": (C.c_int, [C.c_void_p, C.c_int]),
     "vc_tts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(SampleCfg), C.c_int,
                          C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_int,
                          C.POINTER(C.c_int), C.c_void_p]),

@@ -428,12 +428,16 @@ int vc_gemm_qp_ok(int rows, int N, int K, int dtype);
 hipError_t vc_launch_w13_pack(const uint4* img, long n_frags, uint4* planes, unsigned char* side, unsigned int* counts, hipStream_t s);
 int vc_gemm_w13_fr1_ng(int N, int K, int dtype, int nw);   // groups per wave, 0 = the matrix has no planes form
 hipError_t vc_launch_gemm_fr1_w13(const GemmArgs& a, const uint4* planes, const uint32_t* side, int pro, int epi, hipStream_t s);
+// weights on the block-scaled 8-bit grid as E4M3 bytes (vc_gemm_w8.hip, vc_w8.h): the same three entry points, the same contracts
+hipError_t vc_launch_w8_pack(const uint4* img, long n_frags, uint4* planes, unsigned char* side, unsigned int* counts, hipStream_t s);
+int vc_gemm_w8_fr1_ng(int N, int K, int dtype, int nw);    // groups per wave, 0 = the matrix has no w8 form
+hipError_t vc_launch_gemm_fr1_w8(const GemmArgs& a, const uint4* planes, const uint32_t* side, int pro, int epi, hipStream_t s);
 extern int vc_blk_dbg_mask;   // vc_gemm.hip: diagnostic mask of the prefill block GEMM, 0 in production
 // Launch census (process-wide, host side): which kernel FORM each launcher picked.  Read through
 // vc_debug_read("launch_counts") by the parity tests, which assert that the form a benchmarked shape runs on is the one
 // they compared with the oracle.
 enum { VC_LC_ROWS_GEMM = 0, VC_LC_MT2 = 1, VC_LC_MT4 = 2, VC_LC_BLK64 = 3, VC_LC_BLK128_SBS = 4, VC_LC_BLK128_2X2 = 5,
-       VC_LC_BLK64_OCC2 = 6, VC_LC_LN_ROWS = 7, VC_LC_ROWS_ATTN = 8, VC_LC_TILE_ATTN = 9, VC_LC_ROWS_GEMM_FR = 10, VC_LC_BIG256 = 11, VC_LC_BIG128 = 12, VC_LC_ROW_GEMM_FR1 = 13, VC_LC_TILE_ATTN64 = 14, VC_LC_ROWS_GEMM_FRP = 15, VC_LC_WD = 16, VC_LC_ROWS_GEMM_QP = 17, VC_LC_W13 = 18, VC_LC_N = 19 };   // VC_LC_W13: launches on 13-bit planes (also counted in their form's slot)
+       VC_LC_BLK64_OCC2 = 6, VC_LC_LN_ROWS = 7, VC_LC_ROWS_ATTN = 8, VC_LC_TILE_ATTN = 9, VC_LC_ROWS_GEMM_FR = 10, VC_LC_BIG256 = 11, VC_LC_BIG128 = 12, VC_LC_ROW_GEMM_FR1 = 13, VC_LC_TILE_ATTN64 = 14, VC_LC_ROWS_GEMM_FRP = 15, VC_LC_WD = 16, VC_LC_ROWS_GEMM_QP = 17, VC_LC_W13 = 18, VC_LC_W8 = 19, VC_LC_N = 20 };   // VC_LC_W13 / VC_LC_W8: launches on 13-bit planes / on E4M3 bytes (also counted in their form's slot)
 extern long long vc_launch_counts[VC_LC_N];
 hipError_t vc_launch_ln_rows(const GemmArgs& a, int dtype, hipStream_t s);
 hipError_t vc_launch_attn(const AttnArgs& a, int dtype, int rows_cap, hipStream_t s);

@@ -20,6 +20,7 @@
 
 #include "vc_common.h"
 #include "vc_w13.h"
+#include "vc_w8.h"
 
 namespace {
 
@@ -45,8 +46,14 @@ struct Layer {
   uint32_t* w13_side[2] = {nullptr, nullptr};               // one byte per fragment
   int w13_state[2] = {0, 0};                                // 0 not applicable (or not packed), 1 packed, 2 refused: the launch stays on the bf16 image
   int w13_refused[2] = {0, 0};                              // fragments the packer refused
+  // ... and, on request (vc_request_w8), as E4M3 bytes with one shift byte per fragment (option "w8", vc_w8.h): same indices and states
+  uint4* w8_planes[2] = {nullptr, nullptr};
+  uint32_t* w8_side[2] = {nullptr, nullptr};
+  int w8_state[2] = {0, 0};
+  int w8_refused[2] = {0, 0};
 };
 enum { W13_F2 = 0, W13_QKV = 1 };
+constexpr int W8_BITS[2] = {1, 4};        // the mask bits of option "w8" / vc_request_w8 for W13_F2, W13_QKV (the bits of "w13")
 
 struct Plan { int n_tiles, KT, ksplit, nchunk; };
 
@@ -174,6 +181,12 @@ struct vc_engine {
   int w13 = 5;
   bool has_w13 = false;
   unsigned int* w13_counts = nullptr;   // two device words of the packer: fragments refused, dwords that did not decode to the image
+  // option "w8": the same two launches stream E4M3 bytes + one shift byte per fragment (vc_gemm_w8.hip: half the bytes of the image,
+  // results bit-identical) for matrices that lie on that grid (voicecraft_amd/quant.py).  Only on an engine that asked for it before
+  // vc_finalize_weights (vc_request_w8: w8_req); a matrix off the grid is refused and keeps its current launch.  Where a matrix has both
+  // kinds of planes the w8 bit wins.  An engine without the request packs nothing and has no such option.
+  int w8_req = 0;
+  int w8 = 0;
   int cur_rows = 0;                     // rows per step the last decode loop ended on (tts_run reads the states back accordingly)
   // option "attn_fast": decode attention with the wave's maximum taken before any exponential (no online rescaling inside a wave) and,
   // in bf16 mode, hardware exp2 (v_exp_f32) instead of expf
@@ -337,6 +350,27 @@ int pack_w13(vc_engine* e, Layer& ly, int which, const uint4* image, long n_frag
   while (e->allocs.size() > mark) { (void)hipFree(e->allocs.back()); e->allocs.pop_back(); }
   e->bytes_total = bytes0;
   ly.w13_planes[which] = nullptr; ly.w13_side[which] = nullptr;
+  return VC_OK;
+}
+
+// The E4M3 bytes of an already packed bf16 image (vc_w8.h), the way pack_w13 makes its planes: packed and checked on the device with
+// the conversion the kernels use.  A fragment off the 8-bit grid, or any dword that does not decode to the image's, refuses the matrix.
+int pack_w8(vc_engine* e, Layer& ly, int which, const uint4* image, long n_frags) {
+  if (!e->w13_counts) { int rc = dalloc(e, &e->w13_counts, (size_t)4); if (rc) return rc; }
+  const size_t mark = e->allocs.size();
+  const double bytes0 = e->bytes_total;
+  int rc;
+  if ((rc = dalloc(e, &ly.w8_planes[which], (size_t)(n_frags / VC_W8_GROUP_FRAGS) * VC_W8_GROUP_U4))) return rc;
+  if ((rc = dalloc(e, &ly.w8_side[which], (size_t)(n_frags / 4)))) return rc;
+  HIPCHK(e, vc_launch_w8_pack(image, n_frags, ly.w8_planes[which], reinterpret_cast<unsigned char*>(ly.w8_side[which]), e->w13_counts, 0));
+  unsigned int cnt[2] = {0, 0};
+  HIPCHK(e, hipMemcpy(cnt, e->w13_counts, sizeof cnt, hipMemcpyDeviceToHost));
+  ly.w8_refused[which] = (int)cnt[0];
+  if (cnt[0] == 0 && cnt[1] == 0) { ly.w8_state[which] = 1; return VC_OK; }
+  ly.w8_state[which] = 2;
+  while (e->allocs.size() > mark) { (void)hipFree(e->allocs.back()); e->allocs.pop_back(); }
+  e->bytes_total = bytes0;
+  ly.w8_planes[which] = nullptr; ly.w8_side[which] = nullptr;
   return VC_OK;
 }
 
@@ -568,7 +602,8 @@ int site_qkv(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly,
   set_resid(e, g, r);
   if (p.qkv_fr1) {         // the row entering the layer is finished (layer 0: the sampler's dec_h row): 8-channel tiles, two k-tiles per fragment
     g.Wp = ly.Wqkv8;
-    if ((e->w13 & 4) && ly.w13_state[W13_QKV] == 1) HIPCHK(e, vc_launch_gemm_fr1_w13(g, ly.w13_planes[W13_QKV], ly.w13_side[W13_QKV], PRO_LN, EPI_QKV, s));
+    if ((e->w8 & 4) && ly.w8_state[W13_QKV] == 1) HIPCHK(e, vc_launch_gemm_fr1_w8(g, ly.w8_planes[W13_QKV], ly.w8_side[W13_QKV], PRO_LN, EPI_QKV, s));
+    else if ((e->w13 & 4) && ly.w13_state[W13_QKV] == 1) HIPCHK(e, vc_launch_gemm_fr1_w13(g, ly.w13_planes[W13_QKV], ly.w13_side[W13_QKV], PRO_LN, EPI_QKV, s));
     else HIPCHK(e, vc_launch_gemm_fr1(g, e->dtype, PRO_LN, EPI_QKV, s));
   } else if (!p.ln_launch) {
     HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LN, EPI_QKV, 1, 1, s));
@@ -669,7 +704,8 @@ int site_ffn_down(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer
     g.Wp = ly.W28; g.bias = ly.b2;
     g.h_in = e->hA; g.h_out = e->hB;
     if (p.hq) { g.hq_out = e->hqB; g.row_mu = e->row_mu[0]; g.mu_shift = ly.b2_mean; }      // centred on the mean the FFN-up consumer found for h' + the mean of b2
-    if (p.fd && (e->w13 & 1) && ly.w13_state[W13_F2] == 1) HIPCHK(e, vc_launch_gemm_fr1_w13(g, ly.w13_planes[W13_F2], ly.w13_side[W13_F2], PRO_PLAIN, EPI_RES, s));
+    if (p.fd && (e->w8 & 1) && ly.w8_state[W13_F2] == 1) HIPCHK(e, vc_launch_gemm_fr1_w8(g, ly.w8_planes[W13_F2], ly.w8_side[W13_F2], PRO_PLAIN, EPI_RES, s));
+    else if (p.fd && (e->w13 & 1) && ly.w13_state[W13_F2] == 1) HIPCHK(e, vc_launch_gemm_fr1_w13(g, ly.w13_planes[W13_F2], ly.w13_side[W13_F2], PRO_PLAIN, EPI_RES, s));
     else if (p.fd) HIPCHK(e, vc_launch_gemm_fr1(g, e->dtype, PRO_PLAIN, EPI_RES, s));
     else if (p.frp) HIPCHK(e, vc_launch_gemm_frp(g, e->dtype, s));      // 2..8 rows: two k-tiles per fragment
     else HIPCHK(e, vc_launch_gemm_fr(g, e->dtype, PRO_PLAIN, s));
@@ -1141,6 +1177,10 @@ int apply_option(vc_engine* e, const std::string& name, const char* value) {
   } else if (name == "w13") {      // mask: 1 FFN-down, 4 QKV; a matrix without planes (fp32, narrow, refused, VC_W13=0) keeps its bf16 launch
     if (v0 < 0 || (v0 & ~5)) return fail(e, VC_EINVAL, "option 'w13': %d is not a mask of 1 (FFN-down) and 4 (QKV)", v0);
     e->w13 = v0;
+  } else if (name == "w8") {       // mask like "w13", on an engine that requested the w8 form (vc_request_w8); the w8 bit wins over the w13 bit
+    if (!e->w8_req) return fail(e, VC_EINVAL, "option 'w8': this engine was created without vc_request_w8");
+    if (v0 < 0 || (v0 & ~5)) return fail(e, VC_EINVAL, "option 'w8': %d is not a mask of 1 (FFN-down) and 4 (QKV)", v0);
+    e->w8 = v0;
   } else if (name == "attn_fast") { e->attn_fast = v0 ? 1 : 0;
   } else if (name == "att_p16") { e->att_p16 = v0 ? 1 : 0;
   } else if (name == "hq") { e->hq = v0 ? 1 : 0;
@@ -1160,6 +1200,7 @@ void refresh_opt_state(vc_engine* e) {
            e->steps_per_graph, e->nt_decode, e->attn_nt, e->fr_rows, e->fr_pair, e->att_p16, e->hq, e->tile_attn, e->tile_attn_min_rows,
            e->fr_one, e->attn_fast, e->qkv_p8, e->qkv16, e->wide_heads, e->wide_gemm, e->wd_stage, e->shrink, e->w13);
   e->opt_state = buf;
+  if (e->w8_req) e->opt_state += "|w8=" + std::to_string(e->w8);      // only an engine that requested the form has the option
 }
 
 }  // namespace
@@ -1292,10 +1333,22 @@ extern "C" int vc_load_tensor(vc_engine* e, const char* key, const void* data, i
   return VC_OK;
 }
 
+// Asks vc_finalize_weights to pack the matrices of `mask` (1 FFN-down, 4 QKV) as E4M3 bytes too (option "w8").  The compute dtype is
+// chosen at vc_finalize_weights, so that is where a request meets an fp32 engine: VC_EINVAL from there.
+extern "C" int vc_request_w8(vc_engine* e, int mask) {
+  if (!e) return VC_EINVAL;
+  if (e->finalized) return fail(e, VC_ESTATE, "vc_request_w8 comes before vc_finalize_weights");
+  if (mask < 0 || (mask & ~5)) return fail(e, VC_EINVAL, "vc_request_w8: %d is not a mask of 1 (FFN-down) and 4 (QKV)", mask);
+  e->w8_req = mask;
+  e->w8 = mask;
+  return VC_OK;
+}
+
 extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
   if (!e) return VC_EINVAL;
   if (e->finalized) return fail(e, VC_ESTATE, "already finalized");
   if (compute_dtype != VC_DTYPE_BF16 && compute_dtype != VC_DTYPE_F32) return fail(e, VC_EINVAL, "compute dtype must be bf16 or f32");
+  if (e->w8_req && compute_dtype != VC_DTYPE_BF16) return fail(e, VC_EINVAL, "vc_request_w8 was made, and the w8 form exists for bf16 engines only");
   HIPCHK(e, hipSetDevice(e->device));
   e->dtype = compute_dtype;
   e->esz = compute_dtype == VC_DTYPE_BF16 ? 2 : 4;
@@ -1389,6 +1442,13 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
     if (e->has_w13) {
       if (ly.W28 && vc_gemm_w13_fr1_ng(d, 4 * d, e->dtype, VC_FR_WAVES) && (rc = pack_w13(e, ly, W13_F2, ly.W28, (long)(d / VC_TH_RES) * (4 * d / 64)))) return rc;
       if (ly.Wqkv8 && vc_gemm_w13_fr1_ng(3 * d, d, e->dtype, 4) && (rc = pack_w13(e, ly, W13_QKV, ly.Wqkv8, (long)(3 * d / VC_TH_RES) * (d / 64)))) return rc;
+    }
+    // ... and, only for an engine that asked (vc_request_w8), as E4M3 bytes: the same widths, + 0.5 x the requested images
+    if (e->w8_req) {
+      if ((e->w8_req & W8_BITS[W13_F2]) && ly.W28 && vc_gemm_w8_fr1_ng(d, 4 * d, e->dtype, VC_FR_WAVES) &&
+          (rc = pack_w8(e, ly, W13_F2, ly.W28, (long)(d / VC_TH_RES) * (4 * d / 64)))) return rc;
+      if ((e->w8_req & W8_BITS[W13_QKV]) && ly.Wqkv8 && vc_gemm_w8_fr1_ng(3 * d, d, e->dtype, 4) &&
+          (rc = pack_w8(e, ly, W13_QKV, ly.Wqkv8, (long)(3 * d / VC_TH_RES) * (d / 64)))) return rc;
     }
     const size_t cache_bytes = (size_t)e->B_max * e->H * e->S_max * e->hd * e->esz;
     char* kc; char* vc;
@@ -3160,6 +3220,14 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
     for (const Layer& ly : e->layers)
       for (int w = 0; w < 2; ++w) { v.push_back(ly.w13_state[w]); v.push_back(ly.w13_refused[w]); }
     if (nbytes > (int64_t)(v.size() * 4)) return fail(e, VC_ECAP, "debug buffer 'w13_stats' holds %lld bytes", (long long)(v.size() * 4));
+    memcpy(host_dst, v.data(), (size_t)nbytes);
+    return VC_OK;
+  }
+  else if (n == "w8_stats") {       // the same layout for the w8 form (all 0 on an engine without vc_request_w8)
+    std::vector<int32_t> v;
+    for (const Layer& ly : e->layers)
+      for (int w = 0; w < 2; ++w) { v.push_back(ly.w8_state[w]); v.push_back(ly.w8_refused[w]); }
+    if (nbytes > (int64_t)(v.size() * 4)) return fail(e, VC_ECAP, "debug buffer 'w8_stats' holds %lld bytes", (long long)(v.size() * 4));
     memcpy(host_dst, v.data(), (size_t)nbytes);
     return VC_OK;
   }

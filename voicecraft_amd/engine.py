@@ -50,7 +50,12 @@ class VoiceCraftEngine:
     """
 
     def __init__(self, args: Namespace | dict, state_dict: dict[str, torch.Tensor], device="cuda:0",
-                 dtype="bf16", max_seqs: int = 8, max_positions: int = 4096, use_graph: bool = True):
+                 dtype="bf16", max_seqs: int = 8, max_positions: int = 4096, use_graph: bool = True, w8: str | None = None):
+        """w8: None (default: nothing changes) | "quantize" | "as_is" - one-row steps of a bf16 engine stream the matrices of W8_MATRICES
+        as one E4M3 byte per value (option `w8`, csrc/vc_w8.h), bit-identical to the bf16 launches on the same weights.  "quantize" first
+        puts those matrices on the 8-bit grid (quant.quantize_state_dict_w8, on the CPU) and keeps the result as `self.w8_state_dict`,
+        the checkpoint this engine then computes; "as_is" takes the weights as given: a matrix off the grid comes back refused
+        (w8_stats()) and keeps its bf16 launch."""
         self.lib = _lib.load()
         a = Namespace(**args) if isinstance(args, dict) else Namespace(**vars(args))
         # the same normalisation VoiceCraft.__init__ applies (models/voicecraft.py:117-127)
@@ -88,7 +93,14 @@ class VoiceCraftEngine:
         self._h = C.c_void_p()
         index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self.device = torch.device("cuda", index)
+        assert w8 in (None, "quantize", "as_is"), f'w8 = {w8!r}: None, "quantize" or "as_is"'
+        self.w8_state_dict = None
+        if w8 == "quantize":
+            from . import quant
+            state_dict = self.w8_state_dict = quant.quantize_state_dict_w8(a, state_dict, self.W8_MATRICES)
         check(self.lib.vc_create(C.byref(cfg), index, C.byref(self._h)), None, "vc_create")
+        if w8 is not None:
+            check(self.lib.vc_request_w8(self._h, self.W8_MASK), self._h, "vc_request_w8")
         self._load(state_dict)
         self.last_steps = 0
         self.last_kept: list[int] = []       # inference_tts_multi / _long with batch_size > 1: kept sample per utterance
@@ -676,7 +688,8 @@ class VoiceCraftEngine:
         """The engine's option state as text, `key=v,v,...|key=...`: g = graph_steps, nt = (weight mask, K/V loads), fr = finished-row
         forms (finished_rows, fr_pair, att_p16, hq), ta = tile_attn (kernel, min rows), r1 = one-row and attention forms (fr_one,
         attn_fast, qkv_p8), q16 = many-row steps (qkv16, wide_heads, wide_gemm, wd_stage), sh = shrink, w13 = the one-row launches that
-        stream their weights as exact 13-bit planes (mask: 1 FFN-down, 4 QKV; w13_stats() says which matrices have planes).
+        stream their weights as exact 13-bit planes (mask: 1 FFN-down, 4 QKV; w13_stats() says which matrices have planes); an engine
+        created with `w8=` appends w8 = the launches that stream E4M3 bytes instead (same bits, w8_stats()).
         bench.py turns it into a JSON object (`config.engine_options`)."""
         return bytes(self.debug_read("options", (256,), torch.uint8).tolist()).split(b"\0")[0].decode()
 
@@ -692,7 +705,7 @@ class VoiceCraftEngine:
         return ms.value, nbytes.value
 
     LAUNCH_FORMS = ("rows_gemm", "mt2", "mt4", "blk64", "blk128_sbs", "blk128_2x2", "blk64_occ2", "ln_rows", "rows_attn",
-                    "tile_attn", "rows_gemm_fr", "big256", "big128", "row_gemm_fr1", "tile_attn64", "rows_gemm_frp", "wd", "rows_gemm_qp", "w13")
+                    "tile_attn", "rows_gemm_fr", "big256", "big128", "row_gemm_fr1", "tile_attn64", "rows_gemm_frp", "wd", "rows_gemm_qp", "w13", "w8")
 
     def launch_counts(self) -> dict:
         """Process-wide census of the kernel FORMS launched so far (vc_common.h VC_LC_*): the parity tests take the
@@ -710,6 +723,18 @@ class VoiceCraftEngine:
         L = int(self.args.num_decoder_layers)
         v = self.debug_read("w13_stats", (L, 2, 2), torch.int32).tolist()
         return [{m: {"state": self.W13_STATES[v[l][i][0]], "refused_fragments": v[l][i][1]} for i, m in enumerate(self.W13_MATRICES)}
+                for l in range(L)]
+
+    W8_MATRICES = ("ffn_down", "qkv")       # mask bits 1 and 4 of option `w8`, the matrices quant.quantize_state_dict_w8 converts
+    W8_MASK = 5
+
+    def w8_stats(self) -> list:
+        """w13_stats() for option `w8`: per layer {"ffn_down" | "qkv": {"state": "packed" | "refused" | "not_applicable",
+        "refused_fragments": n}}.  A refused matrix holds 512-value fragments off the 8-bit grid; its launches stay where they were.
+        not_applicable: an engine created without `w8=`, or a width without the form (FFN-down below d = 512, QKV below d = 1024)."""
+        L = int(self.args.num_decoder_layers)
+        v = self.debug_read("w8_stats", (L, 2, 2), torch.int32).tolist()
+        return [{m: {"state": self.W13_STATES[v[l][i][0]], "refused_fragments": v[l][i][1]} for i, m in enumerate(self.W8_MATRICES)}
                 for l in range(L)]
 
     def debug_read(self, name: str, shape, dtype=torch.float32) -> torch.Tensor:

@@ -1,0 +1,101 @@
+"""Puts a checkpoint on the engine's 8-bit weight grid ("w8", csrc/vc_w8.h), on the CPU.
+
+The grid's unit is the 512-value MFMA fragment of the engine's 8-channel-tile images: an aligned block of 8 output channels x 64
+inputs of the bf16 image (csrc/vc_gemm.hip pack_k with th = 8: a tile is 8 channels x 32 inputs, a fragment two consecutive
+k-tiles).  A block is on the grid when one shift s exists with every value = q * 2**s, q an OCP E4M3 number (float8_e4m3fn, never its
+NaN code) and the value a normal bf16 number or +-0.  The result is an ordinary fp32 state dict: the oracle and every engine path run
+on it unchanged, and an engine created with `w8="as_is"` on it (or `w8="quantize"` on the original) streams the named matrices of
+one-row steps as one byte per value, with results bit-identical to the bf16 launches on the same state dict.
+
+What lands on the grid is the engine's IMAGE, not the stored matrix: bf16(W) for `linear2.weight`; bf16(W * gamma), the fp32 product
+with gamma = norm1.weight rounded to nearest even, for `self_attn.in_proj_weight` (the LayerNorm fold, csrc/vc_gemm.hip).  The folded
+matrix Q is quantised, Q / gamma is returned, and the fold of the result is asserted to reproduce Q element by element."""
+from __future__ import annotations
+
+import torch
+
+BLOCK = (8, 64)                 # output channels x inputs of one fragment
+SHIFT_MIN, SHIFT_MAX = -117, 119
+MATRICES = {"ffn_down": ("linear2.weight", None), "qkv": ("self_attn.in_proj_weight", "norm1.weight")}
+
+
+def _blocks(x: torch.Tensor) -> torch.Tensor:
+    n, k = x.shape
+    bn, bk = BLOCK
+    assert n % bn == 0 and k % bk == 0, f"matrix [{n}, {k}] is not whole {bn} x {bk} blocks"
+    return x.reshape(n // bn, bn, k // bk, bk).permute(0, 2, 1, 3).reshape(n // bn, k // bk, bn * bk)
+
+
+def _unblocks(b: torch.Tensor, n: int, k: int) -> torch.Tensor:
+    bn, bk = BLOCK
+    return b.reshape(n // bn, k // bk, bn, bk).permute(0, 2, 1, 3).reshape(n, k)
+
+
+def block_shifts(image: torch.Tensor) -> torch.Tensor:
+    """The shift of every block of a bf16-valued fp32 matrix: emax - 8 puts the block's largest value into E4M3's top binade
+    (256 .. 448).  A maximum above 464 * 2**s - past the midpoint between 448 and the NaN code 480 - takes one shift more, where 480 and
+    512 exist (240, 256); clamping it to 448 would cost up to an eighth of the value.  Blocks of zeros take 0."""
+    amax = _blocks(image).abs().amax(dim=-1).double()
+    _, e = torch.frexp(amax)                                  # amax = m * 2**e, m in [0.5, 1)
+    s = (e - 1 - 8).clamp(SHIFT_MIN, SHIFT_MAX)
+    s = torch.where(torch.ldexp(amax, -s) > 464.0, s + 1, s)
+    assert int(s.max()) <= SHIFT_MAX, "a block's largest value does not fit the grid's last shift"
+    return torch.where(amax == 0, torch.zeros_like(s), s)
+
+
+def quantize_image(image: torch.Tensor) -> torch.Tensor:
+    """A bf16-valued fp32 matrix -> the nearest matrix (ties to even) on the grid, block by block.  Values beyond 448 * 2**s are clamped
+    (torch's float8 cast turns them into NaN), values below half the smallest denormal 2**(s - 9) become +-0."""
+    assert image.dtype == torch.float32 and bool(torch.isfinite(image).all())
+    n, k = image.shape
+    b = _blocks(image).double()
+    s = block_shifts(image).unsqueeze(-1)
+    x = torch.ldexp(b, -s).clamp(-448.0, 448.0).float()       # exact: a power-of-two scaling of bf16 values (tiny ones may flush to 0)
+    q = x.to(torch.float8_e4m3fn).float().double()
+    out = _unblocks(torch.ldexp(q, s), n, k).float()
+    assert bool(torch.isfinite(out).all())
+    assert bool((out == out.bfloat16().float()).all()), "grid values are bf16 numbers"
+    return out
+
+
+def fold(w: torch.Tensor, gamma: torch.Tensor | None) -> torch.Tensor:
+    """The engine's bf16 image of a matrix as fp32 values: the fp32 product with the LayerNorm weight, column by column, rounded to nearest
+    even (pack_k: `v *= colscale[k]`, then f32 -> bf16)."""
+    w = w.detach().to(torch.float32)
+    if gamma is not None:
+        w = w * gamma.detach().to(torch.float32)[None, :]
+    return w.bfloat16().float()
+
+
+def quantize_matrix(w: torch.Tensor, gamma: torch.Tensor | None = None) -> torch.Tensor:
+    """The fp32 matrix to store so that the engine's image of it lies on the grid.  Behind a LayerNorm: quantises Q = bf16(W * gamma)
+    and returns Q / gamma; columns with gamma = 0 (image column of zeros, on every grid) are left alone."""
+    img = fold(w, gamma)
+    q = quantize_image(img)
+    if gamma is None:
+        return q
+    g = gamma.detach().to(torch.float32)
+    live = g != 0
+    out = w.detach().to(torch.float32).clone()
+    out[:, live] = (q[:, live].double() / g[live].double()[None, :]).float()
+    # fp32(Q / gamma) * gamma = Q (1 + d) with |d| < 2**-22, and Q is a bf16 number: the rounding to bf16 gives Q back unless the quotient
+    # or the product leaves fp32's normal range
+    again = fold(out, g)
+    assert bool((again == q).all()), f"{int((again != q).sum())} folded values left the grid (a LayerNorm weight outside fp32's normal range?)"
+    return out
+
+
+def quantize_state_dict_w8(args, sd: dict, matrices=("ffn_down", "qkv")) -> dict:
+    """A new fp32 state dict whose named matrices (of every decoder layer) lie on the w8 grid; every other tensor is the input's, cloned.
+    Idempotent: a second pass changes nothing."""
+    unknown = [m for m in matrices if m not in MATRICES]
+    assert not unknown, f"unknown matrices {unknown}: {sorted(MATRICES)} exist"
+    out = {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in sd.items()}
+    n_layers = int(args["num_decoder_layers"] if isinstance(args, dict) else args.num_decoder_layers)
+    for l in range(n_layers):
+        p = f"decoder.layers.{l}."
+        for m in matrices:
+            wkey, gkey = MATRICES[m]
+            gamma = sd[p + gkey] if gkey else None
+            out[p + wkey] = quantize_matrix(sd[p + wkey], gamma).to(torch.float32)
+    return out
