@@ -451,6 +451,32 @@ int vc_pattern_unshift(const int64_t* span_dev, int N, int K, int64_t* out_dev, 
  * Only top_k / top_p / temperature / seed of `sc` are read.  No engine needed. */
 int vc_debug_sample(const float* logits_dev, int V, const vc_sample_cfg* sc, int n_draws,
                     int32_t* out_dev, void* stream);
+/* ONE launch of the decode attention kernel (rows_attn_k, the kernel every decode pass runs) on caller-owned device buffers, through
+ * the launcher the engine itself uses.  No engine needed.  Row r attends to cache positions 0..row_pos[r] of sequence row_seq[r];
+ * positions below *share_len are read from sequence 0; scale = 1/sqrt(hd).
+ *   q fp32 [rows][H*hd]; kcache / vcache [n_seqs][H][S_max][hd] in `dtype` (VC_DTYPE_F32 or VC_DTYPE_BF16), 16-byte aligned like q;
+ *   row_seq, row_pos int32 [rows]; n_active, share_len one int32 each (*n_active == 0: every row leaves an empty partial).
+ *   Split form (x_out null): att_o [rows][H][nsplit][hd] un-normalised partials (fp32; bf16 when part16), att_ml fp32
+ *   [rows][H][nsplit][2] = (running maximum in natural units, sum); an empty split leaves (-inf, 0) and zeros.
+ *   Unsplit form (x_out set, nsplit 1): x_out [rows][H*hd] normalised rows in `dtype` (0 for a row with nothing to attend to);
+ *   att_o / att_ml are not touched and may be null.
+ *   nt / fast / part16: the kernel form, as AttnArgs (non-temporal K/V requests; wave maximum before the exponentials; bf16 partials).
+ * VC_EINVAL for what no decode pass can issue: hd not 32 / 64 / 128, nsplit outside 1..8, x_out with nsplit != 1, part16 without
+ * bf16 or with x_out, a null or misaligned pointer, rows / H / S_max < 1, a dtype other than the two. */
+typedef struct vc_debug_attn_args {
+  const float* q;
+  const void* kcache;
+  const void* vcache;
+  const int32_t* row_seq;
+  const int32_t* row_pos;
+  const int32_t* n_active;
+  const int32_t* share_len;
+  void* att_o;
+  float* att_ml;
+  void* x_out;
+  int32_t dtype, H, hd, S_max, rows, nsplit, nt, fast, part16;
+} vc_debug_attn_args;
+int vc_debug_attn(const vc_debug_attn_args* a, void* stream);
 /* Diagnosis of the BOX, not of the model (no engine needed): ONE thread walks `hops` dependent loads over a ring of `bytes` bytes and
  * stamps the per-XCD shader clock and the chip-wide 100 MHz counter around the walk.  res[0] = ns per dependent load as a lone
  * workgroup on an otherwise idle chip sees it, res[1] = the shader clock (MHz) that workgroup really ran at.  The one-sequence

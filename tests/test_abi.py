@@ -49,6 +49,28 @@ def test_struct_layout_matches_header():
     # 3x int32 (use_graph, poll_every, forced_mode) + tail padding to the 8-byte alignment of the struct
     assert SampleCfg.seed.offset % 8 == 0 and C.sizeof(SampleCfg) == SampleCfg.seed.offset + 8 + 16
     assert SampleCfg.forced_mode.offset == SampleCfg.seed.offset + 16
+    from voicecraft_amd._lib import DebugAttnArgs
+    # ten pointers, nine int32, tail padding to the pointers' alignment
+    assert DebugAttnArgs.dtype.offset == 80 and DebugAttnArgs.part16.offset == 112 and C.sizeof(DebugAttnArgs) == 120
+
+
+def test_debug_attn_refuses_what_no_decode_pass_issues(lib):
+    """vc_debug_attn checks its arguments before it touches the device: the refusals need no GPU (the pointers are never read)."""
+    from voicecraft_amd._lib import DebugAttnArgs
+
+    def args(**kw):
+        base = dict(q=16, kcache=32, vcache=48, row_seq=4, row_pos=8, n_active=12, share_len=20, att_o=64, att_ml=80, x_out=None,
+                    dtype=1, H=2, hd=64, S_max=128, rows=3, nsplit=4, nt=0, fast=1, part16=0)
+        base.update(kw)
+        return DebugAttnArgs(**base)
+
+    bad = [dict(hd=48), dict(hd=256), dict(hd=0), dict(nsplit=0), dict(nsplit=9), dict(x_out=96), dict(x_out=96, nsplit=2),
+           dict(part16=1, dtype=0), dict(part16=1, x_out=96, nsplit=1), dict(dtype=2), dict(rows=0), dict(H=0), dict(S_max=0),
+           dict(q=None), dict(kcache=None), dict(vcache=None), dict(row_seq=None), dict(row_pos=None), dict(n_active=None),
+           dict(share_len=None), dict(att_o=None), dict(att_ml=None), dict(q=20), dict(kcache=40)]
+    for kw in bad:
+        assert lib.vc_debug_attn(C.byref(args(**kw)), None) == -1, kw
+    assert lib.vc_debug_attn(None, None) == -1
 
 
 def test_no_device_fails_loudly(lib):

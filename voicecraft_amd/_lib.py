@@ -34,6 +34,13 @@ class RequestCtl(C.Structure):
     _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float), ("temperature", C.c_float), ("stop_repetition", C.c_int32)]
 
 
+class DebugAttnArgs(C.Structure):
+    """vc_debug_attn_args: ten device pointers, then nine int32 (120 bytes)."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "q", "kcache", "vcache", "row_seq", "row_pos", "n_active", "share_len", "att_o", "att_ml", "x_out")] + [
+        (n, C.c_int32) for n in ("dtype", "H", "hd", "S_max", "rows", "nsplit", "nt", "fast", "part16")]
+
+
 # name -> (restype, argtypes); the single source of truth the symbol test checks against the header
 PROTOTYPES = {
     "vc_create": (C.c_int, [C.POINTER(ModelCfg), C.c_int, C.POINTER(C.c_void_p)]),
@@ -83,6 +90,7 @@ PROTOTYPES = {
     "vc_eval_layout": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int,
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int32), C.c_int64]),
     "vc_debug_sample": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SampleCfg), C.c_int, C.c_void_p, C.c_void_p]),
+    "vc_debug_attn": (C.c_int, [C.POINTER(DebugAttnArgs), C.c_void_p]),
     "vc_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int,
                           C.POINTER(C.c_int32), C.POINTER(SampleCfg), C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                           C.POINTER(C.c_int), C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]),

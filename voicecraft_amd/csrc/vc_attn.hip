@@ -298,6 +298,31 @@ hipError_t vc_launch_attn(const AttnArgs& a, int dtype, int rows_cap, hipStream_
   return hipGetLastError();
 }
 
+// Test hook (include/vc_engine.h): one rows_attn_k launch on caller-owned buffers, with the AttnArgs site_attn would fill.
+extern "C" int vc_debug_attn(const vc_debug_attn_args* p, void* stream) {
+  if (!p) return VC_EINVAL;
+  if (p->dtype != VC_DTYPE_F32 && p->dtype != VC_DTYPE_BF16) return VC_EINVAL;
+  if (p->hd != 32 && p->hd != 64 && p->hd != 128) return VC_EINVAL;
+  if (p->nsplit < 1 || p->nsplit > VC_MAX_NSPLIT) return VC_EINVAL;
+  if (p->H < 1 || p->S_max < 1 || p->rows < 1) return VC_EINVAL;
+  if (!p->q || !p->kcache || !p->vcache || !p->row_seq || !p->row_pos || !p->n_active || !p->share_len) return VC_EINVAL;
+  if (((uintptr_t)p->q | (uintptr_t)p->kcache | (uintptr_t)p->vcache) & 15) return VC_EINVAL;
+  if (p->x_out) {
+    if (p->nsplit != 1 || p->part16) return VC_EINVAL;
+  } else if (!p->att_o || !p->att_ml) return VC_EINVAL;
+  if (p->part16 && p->dtype != VC_DTYPE_BF16) return VC_EINVAL;
+  AttnArgs a = {};
+  a.q = p->q; a.kcache = p->kcache; a.vcache = p->vcache;
+  a.cache_seq_stride = (long)p->H * p->S_max * p->hd;
+  a.S_max = p->S_max; a.H = p->H; a.hd = p->hd; a.hd_shift = p->hd == 32 ? 5 : p->hd == 64 ? 6 : 7; a.d = p->H * p->hd; a.nsplit = p->nsplit;
+  a.scale = 1.0f / sqrtf((float)p->hd);
+  a.row_seq = p->row_seq; a.row_pos = p->row_pos; a.n_rows = p->rows;
+  a.n_active = p->n_active; a.share_len = p->share_len;
+  a.att_o = reinterpret_cast<float*>(p->att_o); a.att_ml = p->att_ml; a.x_out = p->x_out;
+  a.nt = p->nt ? 1 : 0; a.fast = p->fast ? 1 : 0; a.part16 = p->part16 ? 1 : 0;
+  return vc_launch_attn(a, p->dtype, p->rows, (hipStream_t)stream) == hipSuccess ? VC_OK : VC_EHIP;
+}
+
 // ---------------------------------------------------------------- KV replication (best-of-N)
 // inference_tts_batch repeats the prefilled cache batch_size times (voicecraft.py:1329-1343);
 // here each prompt is prefilled once into its group's first slot and positions [p0, p1) are copied to the other

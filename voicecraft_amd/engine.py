@@ -1109,6 +1109,45 @@ def debug_sample(logits: torch.Tensor, n_draws: int, top_k: int = -100, top_p: f
     return out
 
 
+def debug_attn(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, row_seq: torch.Tensor, row_pos: torch.Tensor,
+               n_active: torch.Tensor, share_len: torch.Tensor, nsplit: int, nt: bool = False, fast: bool = True,
+               part16: bool = False, x_out: bool = False, sentinel: float = 0.0) -> dict:
+    """ONE launch of the decode attention kernel on the caller's tensors (vc_debug_attn; tests only).  q fp32 [rows][H*hd];
+    kcache / vcache [n_seqs][H][S_max][hd] fp32 or bf16; row_seq / row_pos int32 [rows]; n_active / share_len int32 [1].
+    Returns {"att_o": [rows][H][nsplit][hd] (fp32, bf16 with part16), "att_ml": fp32 [rows][H][nsplit][2]} or, with x_out,
+    {"x_out": [rows][H*hd] in the cache dtype}; every output buffer is preset to `sentinel`, so what the launch left unwritten shows."""
+    lib = _lib.load()
+    dev = q.device
+    assert q.is_cuda and q.dtype == torch.float32 and q.ndim == 2 and q.is_contiguous()
+    assert kcache.dtype in (torch.float32, torch.bfloat16) and vcache.dtype == kcache.dtype and kcache.shape == vcache.shape
+    assert kcache.ndim == 4 and kcache.is_contiguous() and vcache.is_contiguous() and kcache.device == dev == vcache.device
+    n_seqs, H, S_max, hd = kcache.shape
+    rows = q.shape[0]
+    assert q.shape[1] == H * hd
+    for t, n in ((row_seq, rows), (row_pos, rows), (n_active, 1), (share_len, 1)):
+        assert t.dtype == torch.int32 and t.device == dev and t.numel() == n and t.is_contiguous()
+    assert int(row_seq.max()) < n_seqs and int(row_pos.max()) < S_max and int(share_len) <= S_max      # the kernel trusts its tables
+    a = _lib.DebugAttnArgs()
+    a.q, a.kcache, a.vcache = q.data_ptr(), kcache.data_ptr(), vcache.data_ptr()
+    a.row_seq, a.row_pos, a.n_active, a.share_len = row_seq.data_ptr(), row_pos.data_ptr(), n_active.data_ptr(), share_len.data_ptr()
+    a.dtype = _lib.VC_DTYPE_BF16 if kcache.dtype == torch.bfloat16 else _lib.VC_DTYPE_F32
+    a.H, a.hd, a.S_max, a.rows, a.nsplit = H, hd, S_max, rows, int(nsplit)
+    a.nt, a.fast, a.part16 = int(bool(nt)), int(bool(fast)), int(bool(part16))
+    out = {}
+    if x_out:
+        out["x_out"] = torch.full((rows, H * hd), sentinel, dtype=kcache.dtype, device=dev)
+        a.x_out = out["x_out"].data_ptr()
+    else:
+        n = max(int(nsplit), 1)
+        out["att_o"] = torch.full((rows, H, n, hd), sentinel, dtype=torch.bfloat16 if part16 else torch.float32, device=dev)
+        out["att_ml"] = torch.full((rows, H, n, 2), sentinel, dtype=torch.float32, device=dev)
+        a.att_o, a.att_ml = out["att_o"].data_ptr(), out["att_ml"].data_ptr()
+    rc = lib.vc_debug_attn(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise AssertionError(f"vc_debug_attn rejected its arguments (code {rc})")
+    return out
+
+
 def box_probe(device="cuda:0", hops: int = 256) -> dict:
     """The box's dependent-load latency as ONE workgroup on an idle chip sees it (vc_box_probe): over a 128 KB ring (cache-resident)
     and a 256 MB ring (memory), plus the shader clock that lone workgroup ran at."""
