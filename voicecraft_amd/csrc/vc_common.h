@@ -424,13 +424,23 @@ hipError_t vc_launch_gemm_frp(const GemmArgs& a, int dtype, hipStream_t s);     
 int vc_gemm_frp_ok(int rows, int N, int K, int dtype);
 hipError_t vc_launch_gemm_qp(const GemmArgs& a, int dtype, hipStream_t s);            // paired QKV consumer of 2..8 finished rows (rows_gemm_qp_k)
 int vc_gemm_qp_ok(int rows, int N, int K, int dtype);
-// weights as exact 13-bit planes (vc_gemm_w13.hip, vc_w13.h): packer + check of a bf16 image, and the one-row paired kernel on the planes
+// The packed weight formats of the one-row paired kernel (vc_gemm_fr1.h): exact 13-bit planes (vc_gemm_w13.hip, vc_w13.h) and bytes on the
+// block-scaled 8-bit grid (E4M3, vc_gemm_w8.hip, vc_w8.h).  A matrix is packed in groups of `group_frags` 1 KB image fragments, `group_u4`
+// 16-byte units and one side word each.
+enum { VC_PK_W13 = 0, VC_PK_W8 = 1, VC_PK_N = 2 };
+struct vc_packed_kind {
+  int group_frags, group_u4;
+  int lc;       // the kind's own launch-count slot (its launches count in VC_LC_ROW_GEMM_FR1 too)
+  // packer + check of a bf16 image of n_frags fragments: counts[0] = fragments refused, counts[1] = dwords that do not decode to the image's
+  hipError_t (*pack)(const uint4* img, long n_frags, uint4* planes, unsigned char* side, unsigned int* counts, hipStream_t s);
+  // vc_launch_gemm_fr1 on the packed matrix
+  hipError_t (*row)(const GemmArgs& a, const uint4* planes, const uint32_t* side, int pro, int epi, hipStream_t s);
+};
+const vc_packed_kind& vc_packed(int kind);                  // kind = VC_PK_* (the table is in vc_gemm.hip)
+int vc_gemm_packed_fr1_ng(int kind, int N, int K, int dtype, int nw);   // groups per wave, 0 = the matrix has no such form
 hipError_t vc_launch_w13_pack(const uint4* img, long n_frags, uint4* planes, unsigned char* side, unsigned int* counts, hipStream_t s);
-int vc_gemm_w13_fr1_ng(int N, int K, int dtype, int nw);   // groups per wave, 0 = the matrix has no planes form
 hipError_t vc_launch_gemm_fr1_w13(const GemmArgs& a, const uint4* planes, const uint32_t* side, int pro, int epi, hipStream_t s);
-// weights on the block-scaled 8-bit grid as E4M3 bytes (vc_gemm_w8.hip, vc_w8.h): the same three entry points, the same contracts
 hipError_t vc_launch_w8_pack(const uint4* img, long n_frags, uint4* planes, unsigned char* side, unsigned int* counts, hipStream_t s);
-int vc_gemm_w8_fr1_ng(int N, int K, int dtype, int nw);    // groups per wave, 0 = the matrix has no w8 form
 hipError_t vc_launch_gemm_fr1_w8(const GemmArgs& a, const uint4* planes, const uint32_t* side, int pro, int epi, hipStream_t s);
 extern int vc_blk_dbg_mask;   // vc_gemm.hip: diagnostic mask of the prefill block GEMM, 0 in production
 // Launch census (process-wide, host side): which kernel FORM each launcher picked.  Read through

@@ -19,8 +19,6 @@
 #include <vector>
 
 #include "vc_common.h"
-#include "vc_w13.h"
-#include "vc_w8.h"
 
 namespace {
 
@@ -41,19 +39,17 @@ struct Layer {
   float bo_mean = 0.f, b2_mean = 0.f;   // mean over the d channels of bo / b2: what the update moves a row's mean by whatever its input (GemmArgs.mu_shift)
   float *wg_qkv = nullptr, *wg_1 = nullptr;                             // row sums of the folded weights W . gamma
   void *kc = nullptr, *vc = nullptr;   // KV cache of this layer: WT [max_seqs][H][S_max][hd]
-  // W28 / Wqkv8 once more as exact 13-bit planes (option "w13", vc_w13.h): index W13_F2 / W13_QKV
-  uint4* w13_planes[2] = {nullptr, nullptr};
-  uint32_t* w13_side[2] = {nullptr, nullptr};               // one byte per fragment
-  int w13_state[2] = {0, 0};                                // 0 not applicable (or not packed), 1 packed, 2 refused: the launch stays on the bf16 image
-  int w13_refused[2] = {0, 0};                              // fragments the packer refused
-  // ... and, on request (vc_request_w8), as E4M3 bytes with one shift byte per fragment (option "w8", vc_w8.h): same indices and states
-  uint4* w8_planes[2] = {nullptr, nullptr};
-  uint32_t* w8_side[2] = {nullptr, nullptr};
-  int w8_state[2] = {0, 0};
-  int w8_refused[2] = {0, 0};
+  // W28 / Wqkv8 once more in the packed forms of vc_packed (vc_common.h): [VC_PK_W13] exact 13-bit planes (option "w13", vc_w13.h) and, on request
+  // (vc_request_w8), [VC_PK_W8] E4M3 bytes with one shift byte per fragment (option "w8", vc_w8.h); second index W13_F2 / W13_QKV
+  struct Packed {
+    uint4* planes = nullptr;
+    uint32_t* side = nullptr;      // one byte per fragment
+    int state = 0;                 // 0 not applicable (or not packed), 1 packed, 2 refused: the launch stays on the bf16 image
+    int refused = 0;               // fragments the packer refused
+  } packed[VC_PK_N][2];
 };
 enum { W13_F2 = 0, W13_QKV = 1 };
-constexpr int W8_BITS[2] = {1, 4};        // the mask bits of option "w8" / vc_request_w8 for W13_F2, W13_QKV (the bits of "w13")
+constexpr int W8_BITS[2] = {1, 4};        // the mask bits of options "w13" / "w8" and of vc_request_w8 for W13_F2, W13_QKV
 
 struct Plan { int n_tiles, KT, ksplit, nchunk; };
 
@@ -331,46 +327,28 @@ int pack_folded(vc_engine* e, const std::string& wkey, const std::string& bkey, 
   return VC_OK;
 }
 
-// The 13-bit planes of an already packed bf16 image of `n_frags` 1 KB fragments (vc_w13.h): packed and checked on the device.  A
-// fragment whose non-zero exponents span more than the codes hold, or any dword that does not decode to the image's, refuses the matrix
+// The packed form `kind` (VC_PK_*: 13-bit planes, E4M3 bytes) of an already packed bf16 image of `n_frags` 1 KB fragments: packed
+// and checked on the device, the w8 form with the conversion its kernels use.  A fragment the codes cannot hold (non-zero exponents that
+// span more than the 13-bit codes do, a value off the 8-bit grid), or any dword that does not decode to the image's, refuses the matrix
 // (state 2: the planes are dropped, the launch stays on the image).
-int pack_w13(vc_engine* e, Layer& ly, int which, const uint4* image, long n_frags) {
+int pack_planes(vc_engine* e, Layer& ly, int kind, int which, const uint4* image, long n_frags) {
   if (!e->w13_counts) { int rc = dalloc(e, &e->w13_counts, (size_t)4); if (rc) return rc; }
+  const vc_packed_kind& pk = vc_packed(kind);
+  Layer::Packed& p = ly.packed[kind][which];
   const size_t mark = e->allocs.size();
   const double bytes0 = e->bytes_total;
   int rc;
-  if ((rc = dalloc(e, &ly.w13_planes[which], (size_t)(n_frags / VC_W13_GROUP_FRAGS) * VC_W13_GROUP_U4))) return rc;
-  if ((rc = dalloc(e, &ly.w13_side[which], (size_t)(n_frags / 4)))) return rc;
-  HIPCHK(e, vc_launch_w13_pack(image, n_frags, ly.w13_planes[which], reinterpret_cast<unsigned char*>(ly.w13_side[which]), e->w13_counts, 0));
+  if ((rc = dalloc(e, &p.planes, (size_t)(n_frags / pk.group_frags) * pk.group_u4))) return rc;
+  if ((rc = dalloc(e, &p.side, (size_t)(n_frags / 4)))) return rc;
+  HIPCHK(e, pk.pack(image, n_frags, p.planes, reinterpret_cast<unsigned char*>(p.side), e->w13_counts, 0));
   unsigned int cnt[2] = {0, 0};
   HIPCHK(e, hipMemcpy(cnt, e->w13_counts, sizeof cnt, hipMemcpyDeviceToHost));
-  ly.w13_refused[which] = (int)cnt[0];
-  if (cnt[0] == 0 && cnt[1] == 0) { ly.w13_state[which] = 1; return VC_OK; }
-  ly.w13_state[which] = 2;
+  p.refused = (int)cnt[0];
+  if (cnt[0] == 0 && cnt[1] == 0) { p.state = 1; return VC_OK; }
+  p.state = 2;
   while (e->allocs.size() > mark) { (void)hipFree(e->allocs.back()); e->allocs.pop_back(); }
   e->bytes_total = bytes0;
-  ly.w13_planes[which] = nullptr; ly.w13_side[which] = nullptr;
-  return VC_OK;
-}
-
-// The E4M3 bytes of an already packed bf16 image (vc_w8.h), the way pack_w13 makes its planes: packed and checked on the device with
-// the conversion the kernels use.  A fragment off the 8-bit grid, or any dword that does not decode to the image's, refuses the matrix.
-int pack_w8(vc_engine* e, Layer& ly, int which, const uint4* image, long n_frags) {
-  if (!e->w13_counts) { int rc = dalloc(e, &e->w13_counts, (size_t)4); if (rc) return rc; }
-  const size_t mark = e->allocs.size();
-  const double bytes0 = e->bytes_total;
-  int rc;
-  if ((rc = dalloc(e, &ly.w8_planes[which], (size_t)(n_frags / VC_W8_GROUP_FRAGS) * VC_W8_GROUP_U4))) return rc;
-  if ((rc = dalloc(e, &ly.w8_side[which], (size_t)(n_frags / 4)))) return rc;
-  HIPCHK(e, vc_launch_w8_pack(image, n_frags, ly.w8_planes[which], reinterpret_cast<unsigned char*>(ly.w8_side[which]), e->w13_counts, 0));
-  unsigned int cnt[2] = {0, 0};
-  HIPCHK(e, hipMemcpy(cnt, e->w13_counts, sizeof cnt, hipMemcpyDeviceToHost));
-  ly.w8_refused[which] = (int)cnt[0];
-  if (cnt[0] == 0 && cnt[1] == 0) { ly.w8_state[which] = 1; return VC_OK; }
-  ly.w8_state[which] = 2;
-  while (e->allocs.size() > mark) { (void)hipFree(e->allocs.back()); e->allocs.pop_back(); }
-  e->bytes_total = bytes0;
-  ly.w8_planes[which] = nullptr; ly.w8_side[which] = nullptr;
+  p.planes = nullptr; p.side = nullptr;
   return VC_OK;
 }
 
@@ -578,6 +556,17 @@ int site_ln(vc_engine* e, const RowSrc& rs, const Resid& r, hipStream_t s) {
   return VC_OK;
 }
 
+// The one-row paired launch of matrix `which` of a layer (g.Wp = its image): on the E4M3 bytes where option "w8" has the matrix's bit and
+// the matrix is packed that way, else on the 13-bit planes by the same rule for option "w13", else on the image.
+hipError_t launch_fr1(const vc_engine* e, const Layer& ly, int which, const GemmArgs& g, int pro, int epi, hipStream_t s) {
+  const int mask[VC_PK_N] = {e->w13, e->w8};
+  for (int kind = VC_PK_N - 1; kind >= 0; --kind) {      // the w8 bit wins
+    const Layer::Packed& p = ly.packed[kind][which];
+    if ((mask[kind] & W8_BITS[which]) && p.state == 1) return vc_packed(kind).row(g, p.planes, p.side, pro, epi, s);
+  }
+  return vc_launch_gemm_fr1(g, e->dtype, pro, epi, s);
+}
+
 // The finished-row consumers' `row_mu` ping-pong: QKV reads the means in row_mu[0] and leaves the rows' new means in row_mu[1], which
 // the out-projection centres its copy on; FFN-up reads row_mu[1] and leaves row_mu[0] for the FFN down-projection and the heads.
 // q,k,v = Wqkv LN1(h) + b ; K/V go straight into the cache.  first: layer 0 (no centred copy of its input rows).
@@ -602,9 +591,7 @@ int site_qkv(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly,
   set_resid(e, g, r);
   if (p.qkv_fr1) {         // the row entering the layer is finished (layer 0: the sampler's dec_h row): 8-channel tiles, two k-tiles per fragment
     g.Wp = ly.Wqkv8;
-    if ((e->w8 & 4) && ly.w8_state[W13_QKV] == 1) HIPCHK(e, vc_launch_gemm_fr1_w8(g, ly.w8_planes[W13_QKV], ly.w8_side[W13_QKV], PRO_LN, EPI_QKV, s));
-    else if ((e->w13 & 4) && ly.w13_state[W13_QKV] == 1) HIPCHK(e, vc_launch_gemm_fr1_w13(g, ly.w13_planes[W13_QKV], ly.w13_side[W13_QKV], PRO_LN, EPI_QKV, s));
-    else HIPCHK(e, vc_launch_gemm_fr1(g, e->dtype, PRO_LN, EPI_QKV, s));
+    HIPCHK(e, launch_fr1(e, ly, W13_QKV, g, PRO_LN, EPI_QKV, s));
   } else if (!p.ln_launch) {
     HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LN, EPI_QKV, 1, 1, s));
   } else if (p.qkv16) {    // every A lane a weight: the 16-channel image
@@ -704,9 +691,7 @@ int site_ffn_down(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer
     g.Wp = ly.W28; g.bias = ly.b2;
     g.h_in = e->hA; g.h_out = e->hB;
     if (p.hq) { g.hq_out = e->hqB; g.row_mu = e->row_mu[0]; g.mu_shift = ly.b2_mean; }      // centred on the mean the FFN-up consumer found for h' + the mean of b2
-    if (p.fd && (e->w8 & 1) && ly.w8_state[W13_F2] == 1) HIPCHK(e, vc_launch_gemm_fr1_w8(g, ly.w8_planes[W13_F2], ly.w8_side[W13_F2], PRO_PLAIN, EPI_RES, s));
-    else if (p.fd && (e->w13 & 1) && ly.w13_state[W13_F2] == 1) HIPCHK(e, vc_launch_gemm_fr1_w13(g, ly.w13_planes[W13_F2], ly.w13_side[W13_F2], PRO_PLAIN, EPI_RES, s));
-    else if (p.fd) HIPCHK(e, vc_launch_gemm_fr1(g, e->dtype, PRO_PLAIN, EPI_RES, s));
+    if (p.fd) HIPCHK(e, launch_fr1(e, ly, W13_F2, g, PRO_PLAIN, EPI_RES, s));
     else if (p.frp) HIPCHK(e, vc_launch_gemm_frp(g, e->dtype, s));      // 2..8 rows: two k-tiles per fragment
     else HIPCHK(e, vc_launch_gemm_fr(g, e->dtype, PRO_PLAIN, s));
     return VC_OK;
@@ -1438,17 +1423,14 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
     }
     if ((rc = keep_vec(e, pre + "linear2.bias", d, &ly.b2, &ly.b2_mean))) return rc;
     // two of the big matrices of a one-row step once more as 13-bit planes, where a wave's share is whole groups of four fragments
-    // (vc_gemm_w13_fr1_ng: FFN-down from d = 512, QKV from d = 1024)
-    if (e->has_w13) {
-      if (ly.W28 && vc_gemm_w13_fr1_ng(d, 4 * d, e->dtype, VC_FR_WAVES) && (rc = pack_w13(e, ly, W13_F2, ly.W28, (long)(d / VC_TH_RES) * (4 * d / 64)))) return rc;
-      if (ly.Wqkv8 && vc_gemm_w13_fr1_ng(3 * d, d, e->dtype, 4) && (rc = pack_w13(e, ly, W13_QKV, ly.Wqkv8, (long)(3 * d / VC_TH_RES) * (d / 64)))) return rc;
-    }
-    // ... and, only for an engine that asked (vc_request_w8), as E4M3 bytes: the same widths, + 0.5 x the requested images
-    if (e->w8_req) {
-      if ((e->w8_req & W8_BITS[W13_F2]) && ly.W28 && vc_gemm_w8_fr1_ng(d, 4 * d, e->dtype, VC_FR_WAVES) &&
-          (rc = pack_w8(e, ly, W13_F2, ly.W28, (long)(d / VC_TH_RES) * (4 * d / 64)))) return rc;
-      if ((e->w8_req & W8_BITS[W13_QKV]) && ly.Wqkv8 && vc_gemm_w8_fr1_ng(3 * d, d, e->dtype, 4) &&
-          (rc = pack_w8(e, ly, W13_QKV, ly.Wqkv8, (long)(3 * d / VC_TH_RES) * (d / 64)))) return rc;
+    // (vc_gemm_packed_fr1_ng: FFN-down from d = 512, QKV from d = 1024), and, only for an engine that asked (vc_request_w8), the
+    // requested ones as E4M3 bytes: the same widths, + 0.5 x the requested images
+    const int pack_mask[VC_PK_N] = {e->has_w13 ? 5 : 0, e->w8_req};
+    for (int kind = 0; kind < VC_PK_N; ++kind) {
+      if ((pack_mask[kind] & W8_BITS[W13_F2]) && ly.W28 && vc_gemm_packed_fr1_ng(kind, d, 4 * d, e->dtype, VC_FR_WAVES) &&
+          (rc = pack_planes(e, ly, kind, W13_F2, ly.W28, (long)(d / VC_TH_RES) * (4 * d / 64)))) return rc;
+      if ((pack_mask[kind] & W8_BITS[W13_QKV]) && ly.Wqkv8 && vc_gemm_packed_fr1_ng(kind, 3 * d, d, e->dtype, 4) &&
+          (rc = pack_planes(e, ly, kind, W13_QKV, ly.Wqkv8, (long)(3 * d / VC_TH_RES) * (d / 64)))) return rc;
     }
     const size_t cache_bytes = (size_t)e->B_max * e->H * e->S_max * e->hd * e->esz;
     char* kc; char* vc;
@@ -3215,19 +3197,12 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
     memcpy(host_dst, e->opt_state.c_str(), std::min<size_t>((size_t)nbytes > 0 ? (size_t)nbytes - 1 : 0, e->opt_state.size()));
     return VC_OK;
   }
-  else if (n == "w13_stats") {      // int32 [layer][FFN-down, QKV][state (0 not applicable, 1 packed, 2 refused), fragments refused]
+  else if (n == "w13_stats" || n == "w8_stats") {      // int32 [layer][FFN-down, QKV][state (0 not applicable, 1 packed, 2 refused), fragments refused]
+    const int kind = n == "w13_stats" ? VC_PK_W13 : VC_PK_W8;      // (w8: all 0 on an engine without vc_request_w8)
     std::vector<int32_t> v;
     for (const Layer& ly : e->layers)
-      for (int w = 0; w < 2; ++w) { v.push_back(ly.w13_state[w]); v.push_back(ly.w13_refused[w]); }
-    if (nbytes > (int64_t)(v.size() * 4)) return fail(e, VC_ECAP, "debug buffer 'w13_stats' holds %lld bytes", (long long)(v.size() * 4));
-    memcpy(host_dst, v.data(), (size_t)nbytes);
-    return VC_OK;
-  }
-  else if (n == "w8_stats") {       // the same layout for the w8 form (all 0 on an engine without vc_request_w8)
-    std::vector<int32_t> v;
-    for (const Layer& ly : e->layers)
-      for (int w = 0; w < 2; ++w) { v.push_back(ly.w8_state[w]); v.push_back(ly.w8_refused[w]); }
-    if (nbytes > (int64_t)(v.size() * 4)) return fail(e, VC_ECAP, "debug buffer 'w8_stats' holds %lld bytes", (long long)(v.size() * 4));
+      for (int w = 0; w < 2; ++w) { v.push_back(ly.packed[kind][w].state); v.push_back(ly.packed[kind][w].refused); }
+    if (nbytes > (int64_t)(v.size() * 4)) return fail(e, VC_ECAP, "debug buffer '%s' holds %lld bytes", n.c_str(), (long long)(v.size() * 4));
     memcpy(host_dst, v.data(), (size_t)nbytes);
     return VC_OK;
   }

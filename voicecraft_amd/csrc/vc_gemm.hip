@@ -120,6 +120,8 @@ hipError_t vc_launch_cast(const float* src, void* dst, long n, int dtype, hipStr
 // ------------------------------------------------------------------ rows GEMM
 
 #include "vc_gemm_dev.h"
+#include "vc_w13.h"
+#include "vc_w8.h"
 
 // Decode-step kernel.  The dependency chain of a launch is what the ~80 launches of a step pay for, so
 // the kernel is written around it: (1) everything any later stage needs from HBM - epilogue operands,
@@ -1024,165 +1026,25 @@ hipError_t vc_launch_gemm_fr(const GemmArgs& a0, int dtype, int pro, hipStream_t
 }
 
 // ------------------------------------------------------------------ finished-row producer of ONE-row decode steps (round 5)
-// The one-row step kept split-K slabs through round 4: the FFN down-projection left 4 fp32 slabs and every one of the 512
-// workgroups of the next launch (the following layer's QKV projection) re-summed h + bias + 4 slabs - 40 KB out of L2 per
-// workgroup, requested in front of its own 48 KB weight burst.  rows_gemm_fr_k (above) finishes rows for 2..16-row steps, but
-// its 8-channel tiles fill only half of every MFMA fragment (lanes 8..15 repeat slot 7): twice the vector-memory instructions per
-// weight byte, which a one-row step - nothing but a weight stream - cannot afford.  With ONE row the other 15 columns of the B
-// operand are free, so a fragment carries TWO k-tiles: A rows 0..7 = the tile's 8 channels over k-tile 2p, rows 8..15 = the same
-// channels over k-tile 2p + 1 (the 8-channel image stores consecutive k-tiles of a tile back to back: one contiguous 1 KB
-// burst per wave instruction, every lane's 16 bytes used); B column 0 = x over k-tile 2p, column 1 = x over k-tile 2p + 1.
-// D[c][0] + D[c + 8][1] is channel c's partial sum; every other element of D is a cross term nobody reads.  A workgroup owns
-// 8 channels over the whole K (d/8 workgroups), its 8 waves stream K/8 each in one burst, the row of X is staged once in LDS,
-// and the epilogue adds residual + bias and writes the finished channels: the consumer's LayerNorm prologue reads ONE 8 KB row.
-// NPW = fragment pairs per wave (K / KW / 16, rounded up; pairs beyond the matrix are zeroed).
+// The shared body (vc_gemm_fr1_body.h: the tile and fragment-pair arithmetic, the forms) on the 8-channel-tile image of a bf16 or fp32
+// matrix: pair p of wave w = fragment pair (NPW w + p), one contiguous KB per wave instruction.
 // EXACT: the matrix has exactly NW * NPW fragment pairs per tile (every real model width): no clamped addresses, no zeroed fragments.
-// NW waves per workgroup, each streaming NPW consecutive fragment pairs (KB) in one burst.
-// PRO_PLAIN / EPI_RES (the FFN down-projection): X = a.x_in (WT [K]), h_out = h_in + bias + W x.
-// PRO_LN / EPI_QKV (the QKV projection behind a FINISHED row, option "qkv_p8"): X = the row of h_in, centred and rounded (LayerNorm
-//   fold, rows_gemm_k above), epilogue = rstd / mean correction + folded bias, q to a buffer, K / V into the cache.  The 12-channel
-//   tiles of rows_gemm_k leave a quarter of every fragment's lanes idle: the QKV launch pays the vector-memory instructions of a
-//   33.6 MB stream for 25.2 MB; here every lane's 16 bytes are weights (3d / 8 workgroups: three per CU at d = 2048).
-// (A third form - the FFN up-projection on its ordinary 16-channel tiles with this kernel's lean code, LayerNorm fold of h + bias + two
-// slabs - was built at the end of round 5 on the reading that straight-line code in front of the burst is paid in instruction fetch
-// at every cold launch start: its first workgroup had the burst out after 2 000 clk instead of 2 756, and the step came out
-// +0.84 % +- 0.44 at giga830M, +0.21 % +- 0.06 at giga330M in in-process A/Bs, profiles/r05g_ab_*.log.  Not carried: the FFN-up
-// launch is bound by its stream, not by its prologue.)
-// (TWIN: row_gemm_fr1_w13_k in vc_gemm_w13.hip is this kernel's bf16 EXACT form on 13-bit weight planes: a change to the prologue, reduction
-// or epilogue here has to be made there too - tests/test_gpu_w13.py holds the two bit-identical.)
 template <typename WT, int NPW, bool EXACT, int NW, int PRO, int EPI>
 __global__ __launch_bounds__(64 * NW) void row_gemm_fr1_k(const GemmArgs a) {
-  using T = WTr<WT>;
-  static_assert((PRO == PRO_PLAIN && EPI == EPI_RES) || (PRO == PRO_LN && EPI == EPI_QKV), "one-row paired forms");
-  constexpr int NTHR = 64 * NW, TH = VC_TH_RES, SPT = 4 * TH;   // SPT = 16-byte units per (tile, k-tile) = 32
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  VC_KTS_DECL();
-  VC_KTS(0);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nt = blockIdx.x;
-  const int K = a.K;
-  const int npairs = a.KT >> 1;                    // KT even (host contract)
-  char* xl = smem;                                 // the row: K elements of WT
-  f32x4* red = reinterpret_cast<f32x4*>(smem + (size_t)K * sizeof(WT));     // [NW][4] partial quads
-  float* stat = reinterpret_cast<float*>(red + NW * 4);                     // PRO_LN: [NW] row sums, then [NW][2] statistics of the rounded row
-  const int active = *a.n_active;
-  const int m = lane & 15, kg = lane >> 4;
-  // epilogue operands first (a wave's loads return in order): for the two finishing threads, channels 4 t .. 4 t + 3 of the tile
-  const int nfin = nt * TH + 4 * (tid & 1);
-  float4 eres = make_float4(0.f, 0.f, 0.f, 0.f), ewg = eres;
-  const float4 eb = *reinterpret_cast<const float4*>(a.bias + nfin);
-  int epos = -1, eseq = 0;
-  if constexpr (EPI == EPI_RES) eres = *reinterpret_cast<const float4*>(a.h_in + nfin);
-  else { ewg = *reinterpret_cast<const float4*>(a.wg + nfin); epos = a.row_pos[0]; eseq = a.row_seq[0]; }
-  // the operand row: PLAIN - 16-byte units of X (a fragment pair covers 64 of them); LN - float4 columns of the residual row
-  // (a fragment pair = two k-tiles = 128 bytes of WT = 8 units; K = NW * NPW pairs when EXACT)
-  constexpr int NXU = (NPW * 8 + 63) / 64;                               // 16-byte units of the WT row per thread
-  constexpr int NXQ = ((sizeof(WT) == 2 ? 16 : 8) * NPW + 63) / 64;      // float4 columns of the fp32 row per thread
-  static_assert(NXU <= 4 && (PRO != PRO_LN || NXQ <= 4), "the operand row fits four staging registers per thread");
-  const int units = K * (int)sizeof(WT) / 16, nq = K >> 2;
-  // (explicit scalars: an indexed array is demoted to scratch memory by the compiler)
-  uint4 xu0 = make_uint4(0u, 0u, 0u, 0u), xu1 = xu0, xu2 = xu0, xu3 = xu0;
-  float4 xq0 = make_float4(0.f, 0.f, 0.f, 0.f), xq1 = xq0, xq2 = xq0, xq3 = xq0;
-  if constexpr (PRO == PRO_PLAIN) {
-    const char* src = reinterpret_cast<const char*>(a.x_in);
-#define VC_FR1_XLOAD(j, dst) if constexpr (NXU > (j)) dst = *reinterpret_cast<const uint4*>(src + (size_t)min(tid + (j) * NTHR, units - 1) * 16);
-    VC_FR1_XLOAD(0, xu0) VC_FR1_XLOAD(1, xu1) VC_FR1_XLOAD(2, xu2) VC_FR1_XLOAD(3, xu3)
-#undef VC_FR1_XLOAD
-  } else {
-#define VC_FR1_QLOAD(j, dst) if constexpr (NXQ > (j)) dst = *reinterpret_cast<const float4*>(a.h_in + (size_t)min(tid + (j) * NTHR, nq - 1) * 4);
-    VC_FR1_QLOAD(0, xq0) VC_FR1_QLOAD(1, xq1) VC_FR1_QLOAD(2, xq2) VC_FR1_QLOAD(3, xq3)
-#undef VC_FR1_QLOAD
-  }
-  // the wave's whole share of the weights in one burst: pair p of wave w = fragment pair (NPW w + p)
-  const int wunit = (m >> 3) * SPT + kg * TH + (m & 7);
-  const uint4* wbase = a.Wp + ((long)nt * a.KT + 2 * NPW * wave) * SPT;    // wave-uniform: a wave streams NPW consecutive KB
-  uint4 wf[NPW];
-#pragma unroll
-  for (int p = 0; p < NPW; ++p) {
-    const int gp = EXACT ? p : min(NPW * wave + p, npairs - 1) - NPW * wave;
-    wf[p] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wbase + (long)gp * (2 * SPT) + wunit)));
-  }
+  constexpr int GROUP = 1;
+#define VC_FR1_EARLY
+#define VC_FR1_BURST                                                                                                                     \
+  const uint4* wbase = a.Wp + ((long)nt * a.KT + 2 * NPW * wave) * SPT;    /* wave-uniform: a wave streams NPW consecutive KB */           \
+  uint4 wf[NPW];                                                                                                                         \
+  _Pragma("unroll") for (int p = 0; p < NPW; ++p) {                                                                                      \
+    const int gp = EXACT ? p : min(NPW * wave + p, npairs - 1) - NPW * wave;                                                             \
+    wf[p] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wbase + (long)gp * (2 * SPT) + wunit))); \
+  }                                                                                                                                      \
   __builtin_amdgcn_sched_barrier(0);
-  if (active == 0) return;
-  VC_KTS(1);
-  if constexpr (PRO == PRO_PLAIN) {
-#define VC_FR1_XPARK(j, val) if constexpr (NXU > (j)) { if (tid + (j) * NTHR < units) *reinterpret_cast<uint4*>(xl + (size_t)(tid + (j) * NTHR) * 16) = val; }
-    VC_FR1_XPARK(0, xu0) VC_FR1_XPARK(1, xu1) VC_FR1_XPARK(2, xu2) VC_FR1_XPARK(3, xu3)
-#undef VC_FR1_XPARK
-  } else {
-    // LayerNorm fold of the finished row (see the top of this file): centred BEFORE it is rounded, statistics of the rounded values
-    float t = 0.f;
-#define VC_FR1_QSUM(j, v) if constexpr (NXQ > (j)) { if (tid + (j) * NTHR < nq) t += (v.x + v.y) + (v.z + v.w); }
-    VC_FR1_QSUM(0, xq0) VC_FR1_QSUM(1, xq1) VC_FR1_QSUM(2, xq2) VC_FR1_QSUM(3, xq3)
-#undef VC_FR1_QSUM
-    t = wave_sum(t);
-    if (lane == 0) stat[wave] = t;
-    __syncthreads();
-    float mu = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) mu += stat[w];
-    mu *= 1.0f / (float)K;
-    float s1 = 0.f, s2 = 0.f;
-    WT* xr = reinterpret_cast<WT*>(xl);
-#define VC_FR1_QPARK(j, v)                                                                     \
-    if constexpr (NXQ > (j)) {                                                                 \
-      if (tid + (j) * NTHR < nq) {                                                             \
-        const f32x4 y_ = {v.x - mu, v.y - mu, v.z - mu, v.w - mu};                             \
-        const f32x4 q_ = store4r(xr + (size_t)(tid + (j) * NTHR) * 4, y_);                     \
-        s1 += (q_[0] + q_[1]) + (q_[2] + q_[3]);                                               \
-        s2 += (q_[0] * q_[0] + q_[1] * q_[1]) + (q_[2] * q_[2] + q_[3] * q_[3]);               \
-      }                                                                                        \
-    }
-    VC_FR1_QPARK(0, xq0) VC_FR1_QPARK(1, xq1) VC_FR1_QPARK(2, xq2) VC_FR1_QPARK(3, xq3)
-#undef VC_FR1_QPARK
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    if (lane == 0) { stat[NW + 2 * wave] = s1; stat[NW + 2 * wave + 1] = s2; }
-  }
-  VC_KTS(2);
-  __syncthreads();
-  VC_KTS(3);
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  // B operand: column m = 0 reads x over k-tile 2 gp, column 1 over k-tile 2 gp + 1 (the other columns repeat these: cross terms)
-  const char* xcol = xl + ((size_t)(m & 1) * T::KW + (size_t)kg * T::EPL) * sizeof(WT);
-#pragma unroll
-  for (int p = 0; p < NPW; ++p) {
-    const int gpr = NPW * wave + p;
-    const int gp = EXACT ? gpr : min(gpr, npairs - 1);
-    const uint4 xf = *reinterpret_cast<const uint4*>(xcol + (size_t)gp * (2 * T::KW * sizeof(WT)));
-    uint4 w = wf[p];
-    if constexpr (!EXACT) { if (gpr >= npairs) w = make_uint4(0u, 0u, 0u, 0u); }
-    acc = mfma_frag(w, xf, acc, (WT*)nullptr);
-  }
-  // D[n = 4 kg + r][m]: channels 0..3 / 4..7 over the even k-tiles sit in lanes (m = 0, kg = 0 / 1), over the odd ones in lanes
-  // (m = 1, kg = 2 / 3): four quads per wave
-  VC_KTS(4);
-  if (m == (kg >> 1) && m < 2) red[wave * 4 + kg] = acc;
-  __syncthreads();
-  VC_KTS(5);
-  if (tid < 2) {             // thread t finishes channels 4 t .. 4 t + 3: quads t and t + 2 of every wave, in a fixed order
-    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int w = 0; w < NW; ++w) sum += red[w * 4 + tid] + red[w * 4 + tid + 2];
-    if constexpr (EPI == EPI_RES) {
-      const f32x4 o = {eres.x + eb.x + sum[0], eres.y + eb.y + sum[1], eres.z + eb.z + sum[2], eres.w + eb.w + sum[3]};
-      store4(a.h_out + nfin, o);
-    } else {
-      float q1 = 0.f, q2 = 0.f;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) { q1 += stat[NW + 2 * w]; q2 += stat[NW + 2 * w + 1]; }
-      const float inv_d = 1.0f / (float)K;
-      const float mean = q1 * inv_d;
-      const float var = fmaxf(q2 * inv_d - mean * mean, 0.f);
-      const float rstd = 1.0f / sqrtf(var + 1e-5f);      // eps 1e-5 (transformer.py:30)
-      sum[0] = rstd * (sum[0] - mean * ewg.x); sum[1] = rstd * (sum[1] - mean * ewg.y);
-      sum[2] = rstd * (sum[2] - mean * ewg.z); sum[3] = rstd * (sum[3] - mean * ewg.w);
-      gemm_epilogue<WT, EPI_QKV>(a, sum, 0, nfin, 0, 0, 1, eb, epos, eseq);
-    }
-  }
-  VC_KTS(6);
-  VC_KTS_FLUSH();
+#define VC_FR1_FRAG(F, w)                                                              \
+  uint4 w = wf[g];                                                                     \
+  if constexpr (!EXACT) { if (gpr >= npairs) w = make_uint4(0u, 0u, 0u, 0u); }
+#include "vc_gemm_fr1_body.h"
 }
 template <typename WT, int NPW, int NW, int PRO, int EPI>
 static hipError_t launch_fr1_n(const GemmArgs& a, hipStream_t s) {
@@ -1202,6 +1064,22 @@ int vc_gemm_fr1_ok(int N, int K, int dtype, int nw) {
   while (cap < npw) cap <<= 1;
   if (cap > (nw == 4 ? 16 : 32) || (long)K * esz > 64L * 1024) return 0;      // a wave's fragments fit its registers; the row <= 4 staging registers per thread
   return 1;
+}
+const vc_packed_kind& vc_packed(int kind) {
+  static const vc_packed_kind kinds[VC_PK_N] = {
+    {VC_W13_GROUP_FRAGS, VC_W13_GROUP_U4, VC_LC_W13, vc_launch_w13_pack, vc_launch_gemm_fr1_w13},
+    {VC_W8_GROUP_FRAGS, VC_W8_GROUP_U4, VC_LC_W8, vc_launch_w8_pack, vc_launch_gemm_fr1_w8},
+  };
+  return kinds[kind];
+}
+// Groups per wave of a packed form for an [N x K] matrix on the one-row paired kernel with `nw` waves, 0 = no form: bf16, the kernel's
+// own form (vc_gemm_fr1_ok) with EXACTLY nw x NG groups of fragment pairs per tile.  The engine's packing and the launchers agree on it.
+int vc_gemm_packed_fr1_ng(int kind, int N, int K, int dtype, int nw) {
+  if (kind < 0 || kind >= VC_PK_N || dtype != VC_DTYPE_BF16 || !vc_gemm_fr1_ok(N, K, dtype, nw)) return 0;
+  const int npairs = K / 64, per = nw * vc_packed(kind).group_frags;
+  if (npairs % per != 0) return 0;
+  const int ng = npairs / per;
+  return (ng == 1 || ng == 2 || ng == 4) ? ng : 0;
 }
 // ONE row.  pro / epi = PRO_PLAIN / EPI_RES: h_out[n] = h_in[n] + bias[n] + sum_k W[n][k] x[k] (a.x_in = the row, WT [K]; 8 waves);
 // PRO_LN / EPI_QKV: the QKV projection of the finished row a.h_in (LayerNorm fold; 4 waves).  a.Wp = the 8-channel-tile image.
