@@ -299,3 +299,50 @@ def test_wide_batch_whose_sequences_retire_at_different_steps(preset, B, graph):
         assert eng.last_steps == max(lens) + a.n_codebooks
         repacks = int(eng.debug_read("host_ms", (8,), torch.float64)[6])
         assert (repacks >= 1) if shrink else (repacks == 0), (shrink, repacks)
+
+
+# A legal non-default value for every option of bench.OPTION_STATE, as vc_set_option takes it.
+_NON_DEFAULT = {"graph_steps": "3", "nt": "28,1", "finished_rows": "4", "fr_pair": "0", "att_p16": "0", "hq": "0", "tile_attn": "1,512",
+                "fr_one": "0", "attn_fast": "0", "qkv_p8": "1", "qkv16": "0", "wide_heads": "0", "wide_gemm": "0", "wd_stage": "0", "shrink": "0"}
+# The whole option text of a fresh bf16 engine with max_seqs > 16 and no VC_* preset, as the build of commit 90c5e65 (the last one whose
+# text was one hand-written format string) printed it on an MI355X.
+_DEFAULT_TEXT = "g=8|nt=63,2|fr=16,1,1,1|ta=2,768|r1=1,1,2|q16=1,1,1,1|sh=1|w13=5"
+
+
+def test_option_text_moves_only_in_the_field_of_the_option_set(monkeypatch):
+    """The option text keys the captured decode graphs and is parsed by bench.py, so its format is pinned here: on an engine that holds
+    every weight image (max_seqs > 16, bf16), setting one option changes that option's field(s) of the text and no other character,
+    setting the prior value back restores the text, and the default text equals the recorded literal.  No decode is launched."""
+    import os
+    import bench
+    from voicecraft_amd import synth
+    from voicecraft_amd.engine import VoiceCraftEngine
+    for name in [n for n in os.environ if n.startswith("VC_") and n != "VC_ENGINE_LIB"]:
+        monkeypatch.delenv(name)
+    a = synth.make_args("tiny")
+    eng = VoiceCraftEngine(a, synth.make_state_dict(a, seed=3), device="cuda:0", dtype="bf16", max_seqs=17, max_positions=256)
+    text0 = eng.options()
+    assert text0 == _DEFAULT_TEXT
+    assert set(_NON_DEFAULT) == set(bench.OPTION_STATE)
+
+    def fields(text):
+        return [(key, vals.split(",")) for key, vals in (p.split("=", 1) for p in text.split("|"))]
+
+    def join(fs):
+        return "|".join(f"{key}={','.join(vals)}" for key, vals in fs)
+
+    assert join(fields(text0)) == text0
+    for knob, (key, idx) in bench.OPTION_STATE.items():
+        prior = bench.option_value(text0, knob)
+        new = _NON_DEFAULT[knob]
+        assert prior is not None and prior != new, (knob, prior)
+        want = fields(text0)
+        for k, vals in want:
+            if k == key:
+                for i, v in zip(idx, new.split(",")):
+                    vals[i] = v
+        eng.set_option(knob, new)
+        assert eng.options() == join(want), (knob, eng.options())
+        assert join(want) != text0, knob
+        eng.set_option(knob, prior)
+        assert eng.options() == text0, (knob, eng.options())

@@ -8,6 +8,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <limits.h>
 #include <string.h>
 
 #include <algorithm>
@@ -53,6 +54,15 @@ constexpr int W8_BITS[2] = {1, 4};        // the mask bits of options "w13" / "w
 
 struct Plan { int n_tiles, KT, ksplit, nchunk; };
 
+// Words of the pinned vc_engine::h_flag block.  HF_ACTIVE / HF_LIVE0..1 are written by the device (SampleArgs.host_active / host_live: the
+// sequences still active; the two slots of "sequences still live as the LAST step of a batch found them"), HF_GATHER_N by stream_gather_k.
+enum { HF_ERR = 0, HF_STAGE = 1, HF_SHARE = 2, HF_ACTIVE = 8, HF_LIVE0 = 9, HF_LIVE1 = 10, HF_LIVE_STEPS = 11, HF_GATHER_N = 12 };
+// vc_engine::host_ms (vc_debug_read "host_ms": read by position): graph capture / instantiation of the last call, its decode loop's host
+// time, the decode steps it LAUNCHED (a multiple of steps_per_graph; the tail are no-ops) and the re-packs that moved live sequences.
+enum { HM_CAPTURE = 1, HM_INSTANTIATE = 2, HM_LOOP = 3, HM_SPARE = 4, HM_LAUNCHED = 5, HM_REPACKS = 6 };
+// Session::stats (vc_session_stats: read by position; [7] is the admission time).  The row sums count every sample's rows.
+enum { SS_ADMITTED = 0, SS_ADMITTED_LIVE = 1, SS_TURNS = 2, SS_WIDENINGS = 3, SS_NARROWINGS = 4, SS_LIVE_ROWS = 5, SS_LAUNCHED_ROWS = 6 };
+
 }  // namespace
 
 struct vc_engine {
@@ -95,8 +105,8 @@ struct vc_engine {
   int gen_cap = 0;
   // pinned host staging
   SeqState *h_st = nullptr, *h_st2 = nullptr;
-  int *h_flag = nullptr;                // [0] error/poll word, [1] staging, [8] "sequences still active" written by the device,
-                                        // [9..10] SampleArgs.host_live, [11] the decode loop's live steps (step_ctr, after a re-packed call)
+  int *h_flag = nullptr;                // indexed by HF_*: error/poll word, staging, "sequences still active" written by the device,
+                                        // SampleArgs.host_live, the decode loop's live steps (step_ctr, after a re-packed call)
   SampleDyn *h_dyn = nullptr, *d_dyn = nullptr;   // per-call sampler values (vc_common.h)
   // captured decode steps, kept across calls: key = (sequences, rows per sequence, best-of-N)
   // ... and by the option state they were captured under (vc_set_option): toggling an option back and forth reuses the captures
@@ -201,7 +211,7 @@ struct vc_engine {
   int prefill_rows_per_pass = VC_MAX_ROWS;   // VC_PREFILL_ROWS=16 falls back to the decode kernels for the prompt
   hipEvent_t ev[3]{};
   float ms[3]{0, 0, 0};
-  double host_ms[8]{};                  // host wall clock of the last call's phases (vc_debug_read "host_ms")
+  double host_ms[8]{};                  // host wall clock of the last call's phases, indexed by HM_* (vc_debug_read "host_ms")
   double bytes_total = 0;               // HBM bytes owned by the engine
   // training objective (vc_eval_forward), allocated on first use
   int *ce_tgt = nullptr, *ce_hit = nullptr;
@@ -250,6 +260,13 @@ int dalloc(vc_engine* e, T** p, size_t n) {
   e->bytes_total += (double)(n * sizeof(T));
   *p = reinterpret_cast<T*>(v);
   return VC_OK;
+}
+// the void* fields (buffers in the compute dtype): sized in bytes
+inline int dalloc(vc_engine* e, void** p, size_t bytes) {
+  char* c = nullptr;
+  const int rc = dalloc(e, &c, bytes);
+  *p = c;
+  return rc;
 }
 
 Plan make_plan(int N, int Kdim, int dtype, bool allow_split, const char* env_override, int th = 16) {
@@ -875,7 +892,7 @@ SampleArgs make_sample_args(vc_engine* e, int B, int rps) {
   memset(&a, 0, sizeof a);
   a.logits = e->logits; a.B = B; a.K = e->K; a.V = e->V; a.d = e->d;
   a.empty_token = e->cfg.empty_token; a.gen_stride = e->gen_cap; a.dyn = e->d_dyn;
-  a.st = e->st; a.n_active = e->n_active; a.host_active = e->h_flag + 8; a.host_live = e->h_flag + 9; a.step_ctr = e->step_ctr; a.graph_steps = std::max(1, e->steps_per_graph); a.samp = e->samp;
+  a.st = e->st; a.n_active = e->n_active; a.host_active = e->h_flag + HF_ACTIVE; a.host_live = e->h_flag + HF_LIVE0; a.step_ctr = e->step_ctr; a.graph_steps = std::max(1, e->steps_per_graph); a.samp = e->samp;
   a.err = e->err_flag;
   a.gen = e->gen;
   a.rps = rps; a.dec_h = e->dec_h; a.row_seq = e->dec_row_seq; a.row_pos = e->dec_row_pos;
@@ -931,7 +948,6 @@ int decode_step(vc_engine* e, const SampleArgs& sa, int B, int rps, bool grouped
 // sequence retires, and the host paces itself one graph behind the GPU with events, so a queued graph is
 // always waiting when the running one ends (measured before: ~8 us of idle GPU per graph launch and ~100 us
 // per blocking poll).  Steps replayed after the last sequence retired are no-ops (*n_active == 0).
-void refresh_opt_state(vc_engine* e);
 void drop_tts_stream(vc_engine* e);
 void drop_session(vc_engine* e);
 
@@ -981,13 +997,13 @@ struct DecodeLoop {
         hipError_t ce = hipStreamEndCapture(s, &graph);
         if (rc == VC_OK && ce != hipSuccess) rc = fail(e, VC_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
       }
-      e->host_ms[1] += now_ms() - tc;
+      e->host_ms[HM_CAPTURE] += now_ms() - tc;
       if (rc == VC_OK) {
         const double ti = now_ms();
         hipError_t ie = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
         if (ie != hipSuccess) rc = fail(e, VC_EHIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie));
         else e->graphs[key] = *out;
-        e->host_ms[2] += now_ms() - ti;
+        e->host_ms[HM_INSTANTIATE] += now_ms() - ti;
       }
       if (graph) (void)hipGraphDestroy(graph);
     }
@@ -995,7 +1011,7 @@ struct DecodeLoop {
   }
   // every graph this call can need, captured before the caller starts its decode timer
   int precapture() {
-    e->host_ms[1] = e->host_ms[2] = 0;
+    e->host_ms[HM_CAPTURE] = e->host_ms[HM_INSTANTIATE] = 0;
     if (!sc.use_graph) return VC_OK;
     hipGraphExec_t exec = nullptr;
     int rc0 = exec_for(&exec);
@@ -1014,10 +1030,27 @@ struct DecodeLoop {
     over = launched >= max_steps;
     return VC_OK;
   }
+  // One batch of G steps of the width in force - its captured graph, or G eager steps - and the pacing event `slot` behind it.  The only
+  // place a batch is launched: advance() below and a decode session's turn (vc_session_advance), which keeps its own batch count.
+  int queue_batch(int slot) {
+    int rc = VC_OK;
+    if (sc.use_graph) {
+      hipGraphExec_t exec = nullptr;
+      if ((rc = exec_for(&exec))) return rc;
+      hipError_t le = hipGraphLaunch(exec, s);
+      if (le != hipSuccess) return fail(e, VC_EHIP, "hipGraphLaunch failed: %s", hipGetErrorString(le));
+    } else {
+      for (int i = 0; i < G && rc == VC_OK; ++i) rc = decode_step(e, sa, B, rps, grouped, s, sess);
+      if (rc) return rc;
+    }
+    hipError_t re = hipEventRecord(e->ev_pace[slot], s);
+    if (re != hipSuccess) return fail(e, VC_EHIP, "hipEventRecord: %s", hipGetErrorString(re));
+    return VC_OK;
+  }
   // One turn: wait for the older of the two batches in flight, then queue the next one.  Sets `over` instead when the loop has ended.
   int advance() {
-    volatile int* live = e->h_flag + 8;
-    volatile int* live_n = e->h_flag + 9;                   // two slots: sequences still live as the LAST step of a batch of G steps found them
+    volatile int* live = e->h_flag + HF_ACTIVE;
+    volatile int* live_n = e->h_flag + HF_LIVE0;                   // two slots: sequences still live as the LAST step of a batch of G steps found them
     if (over) return VC_OK;
     if (batch >= 2) {   // pace: at most two batches in flight; the older one must have ended before a third is queued
       hipError_t we = hipEventSynchronize(e->ev_pace[batch & 1]);
@@ -1037,46 +1070,32 @@ struct DecodeLoop {
           hipError_t re = vc_launch_repack(ra, s);
           if (re != hipSuccess) { over = true; return fail(e, VC_EHIP, "re-pack launch: %s", hipGetErrorString(re)); }
           B = w; sa = make_sample_args(e, w, rps);
-          e->repack_at.push_back(batch);                  // counted in host_ms[6] once the call knows its live steps (tts_run)
+          e->repack_at.push_back(batch);                  // counted in host_ms[HM_REPACKS] once the call knows its live steps (tts_run)
         }
       }
     }
-    int rc = VC_OK;
-    if (sc.use_graph) {
-      hipGraphExec_t exec = nullptr;
-      rc = exec_for(&exec);
-      if (rc) { over = true; return rc; }
-      hipError_t le = hipGraphLaunch(exec, s);
-      if (le != hipSuccess) rc = fail(e, VC_EHIP, "hipGraphLaunch failed: %s", hipGetErrorString(le));
-    } else {
-      for (int i = 0; i < G && rc == VC_OK; ++i) rc = decode_step(e, sa, B, rps, grouped, s);
-    }
-    if (rc) { over = true; return rc; }
+    if (const int rc = queue_batch(batch & 1)) { over = true; return rc; }
     launched += G;
-    hipError_t re = hipEventRecord(e->ev_pace[batch & 1], s);
-    if (re != hipSuccess) { over = true; return fail(e, VC_EHIP, "hipEventRecord: %s", hipGetErrorString(re)); }
     ++batch;
     if (launched >= max_steps) over = true;
     return VC_OK;
   }
   void finish(int* steps_run) {
-    e->host_ms[3] = now_ms() - t1;
-    e->host_ms[4] = 0;
-    e->host_ms[5] = launched;                               // decode steps LAUNCHED (a multiple of steps_per_graph; the tail are no-ops)
+    e->host_ms[HM_LOOP] = now_ms() - t1;
+    e->host_ms[HM_SPARE] = 0;
+    e->host_ms[HM_LAUNCHED] = launched;                               // decode steps LAUNCHED (a multiple of steps_per_graph; the tail are no-ops)
     e->cur_rows = B;
     if (steps_run) *steps_run = launched;
   }
 };
 
-int decode_loop(vc_engine* e, const SampleArgs& sa0, int B0, int rps, int groups, const vc_sample_cfg* sc,
-                int max_steps, int* steps_run, hipStream_t s, bool precapture_only = false) {
+int decode_loop(vc_engine* e, const SampleArgs& sa0, int B0, int rps, int groups, const vc_sample_cfg* sc, int max_steps, hipStream_t s) {
   DecodeLoop L;
   L.init(e, sa0, B0, rps, groups, sc, max_steps, s);
-  if (precapture_only) return L.precapture();
   int rc = L.begin();
   if (rc) return rc;
   while (rc == VC_OK && !L.over) rc = L.advance();
-  L.finish(steps_run);
+  L.finish(nullptr);
   return rc;
 }
 
@@ -1132,60 +1151,109 @@ int check_err_flag(vc_engine* e, hipStream_t s) {
   return VC_OK;
 }
 
+// ---- the checks of options that need a weight image or a request: they refuse before anything is set
+int need_fr8(vc_engine* e, const char* name, int v0) {
+  if (v0 <= 0 || e->has_fr8) return VC_OK;
+  return fail(e, VC_ESTATE, "option '%s': this engine was created with VC_FINISHED_ROWS=0 and VC_FR_ONE=0 and holds no 8-channel weight images", name);
+}
+int need_qkv8(vc_engine* e, const char*, int v0) {
+  if (!v0 || e->has_qkv8 || !vc_gemm_fr1_ok(3 * e->d, e->d, e->dtype, 4)) return VC_OK;
+  return fail(e, VC_ESTATE, "option 'qkv_p8': this engine was created with VC_QKV_P8=0 or VC_FR_ONE=0 and holds no 8-channel image of the QKV matrix");
+}
+int need_qkv16(vc_engine* e, const char*, int v0) {
+  if (!v0 || e->has_qkv16) return VC_OK;
+  return fail(e, VC_ESTATE, "option 'qkv16': this engine holds no 16-channel image of the QKV matrix (packed for max_seqs > 16, or with VC_QKV16=1 at creation)");
+}
+// mask: 1 FFN-down, 4 QKV; a matrix without planes (fp32, narrow, refused, VC_W13=0) keeps its bf16 launch
+int need_mask(vc_engine* e, const char* name, int v0) {
+  return v0 < 0 || (v0 & ~5) ? fail(e, VC_EINVAL, "option '%s': %d is not a mask of 1 (FFN-down) and 4 (QKV)", name, v0) : VC_OK;
+}
+// mask like "w13", on an engine that requested the w8 form (vc_request_w8); the w8 bit wins over the w13 bit
+int need_w8(vc_engine* e, const char* name, int v0) {
+  return e->w8_req ? need_mask(e, name, v0) : fail(e, VC_EINVAL, "option 'w8': this engine was created without vc_request_w8");
+}
+
+int nonzero(int v) { return v ? 1 : 0; }
+int two_or_one(int v) { return v == 2 ? 2 : 1; }
+int low6(int v) { return v & 63; }
+int whole_tiles(int v) { return v / VC_ROWS * VC_ROWS; }
+
+// Every option, once: vc_set_option, the VC_* presets at creation and the option text are all driven from this table (the fields' own
+// comments in struct vc_engine say what each option does and why its default is what it is).  A value is "v0[,v1]": `pre` (if any), then
+// the clamp to [lo, hi], give field f0; v1, where the option has a second field, is clamped the same way and optional.
+// The option TEXT lists, in table order, the options that have a group tag - "tag=" in front of the first of a run with the same tag, a
+// comma between its members, '|' between runs -, and keys the captured decode graphs: an option that shapes a decode step carries a tag.
+struct Val { int vc_engine::*f; int lo, hi; };
+struct OptDesc {
+  const char *name, *env, *tag;
+  Val v0;
+  int (*pre)(int);
+  Val v1;                                           // .f null: one value
+  int (*check)(vc_engine*, const char* name, int v0);
+  int vc_engine::*only_if;                          // in the text only on an engine where this field is set (null: always)
+};
+using E = vc_engine;
+const OptDesc OPTIONS[] = {
+    {"graph_steps", "VC_GRAPH_STEPS", "g", {&E::steps_per_graph, 1, 64}},
+    // "mask[,kv]": the weight matrices streamed with the hint, and the decode attention's K/V loads (0 never, 1 always, 2 from two rows up)
+    {"nt", "VC_NT", "nt", {&E::nt_decode, 0, 63}, low6, {&E::attn_nt, 0, 2}},
+    {"finished_rows", "VC_FINISHED_ROWS", "fr", {&E::fr_rows, 0, VC_ROWS}, nullptr, {}, need_fr8},
+    {"fr_pair", "VC_FR_PAIR", "fr", {&E::fr_pair, 0, 1}, nonzero},
+    {"att_p16", "VC_ATT_P16", "fr", {&E::att_p16, 0, 1}, nonzero},
+    {"hq", "VC_HQ", "fr", {&E::hq, 0, 1}, nonzero},
+    {"tile_attn", "VC_TILE_ATTN", "ta", {&E::tile_attn, 1, 2}, two_or_one, {&E::tile_attn_min_rows, 64, INT_MAX}},
+    {"fr_one", "VC_FR_ONE", "r1", {&E::fr_one, 0, 2}, nullptr, {}, need_fr8},
+    {"attn_fast", "VC_ATTN_FAST", "r1", {&E::attn_fast, 0, 1}, nonzero},
+    {"qkv_p8", "VC_QKV_P8", "r1", {&E::qkv_p8, 0, 2}, nullptr, {}, need_qkv8},      // 2: steps of 2..8 finished rows as well (rows_gemm_qp_k)
+    {"qkv16", "VC_QKV16", "q16", {&E::qkv16, 0, 1}, nonzero, {}, need_qkv16},
+    {"wide_heads", "VC_WIDE_HEADS", "q16", {&E::wide_heads, 0, 1}, nonzero},
+    {"wide_gemm", "VC_WIDE_GEMM", "q16", {&E::wide_gemm, 0, 1}, nonzero},
+    {"wd_stage", "VC_WD_STAGE", "q16", {&E::wd_stage, 0, 1}, nonzero},
+    {"shrink", "VC_SHRINK", "sh", {&E::shrink, 0, 1}, nonzero},
+    {"w13", "VC_W13", "w13", {&E::w13, 0, 5}, nullptr, {}, need_mask},
+    {"w8", nullptr, "w8", {&E::w8, 0, 5}, nullptr, {}, need_w8, &E::w8_req},      // only an engine that requested the form has the option
+    {"prefill_rows", "VC_PREFILL_ROWS", nullptr, {&E::prefill_rows_per_pass, VC_ROWS, VC_MAX_ROWS}, whole_tiles},   // 16: decode kernels only
+};
+
 // One option by name (vc_set_option, and the VC_* environment variables at creation).
 int apply_option(vc_engine* e, const std::string& name, const char* value) {
-  int v0 = 0, v1 = 0, v2 = 0;
-  const int n = sscanf(value ? value : "", "%d,%d,%d", &v0, &v1, &v2);
+  int v[3] = {0, 0, 0};
+  const int n = sscanf(value ? value : "", "%d,%d,%d", &v[0], &v[1], &v[2]);
   if (n < 1) return fail(e, VC_EINVAL, "option '%s': '%s' is not a number list", name.c_str(), value ? value : "(null)");
-  if (name == "graph_steps") { e->steps_per_graph = std::max(1, std::min(64, v0));
-  } else if (name == "tile_attn") {
-    e->tile_attn = v0 == 2 ? 2 : 1;
-    if (n >= 2) e->tile_attn_min_rows = std::max(64, v1);
-  } else if (name == "finished_rows" || name == "fr_one") {
-    if (v0 > 0 && !e->has_fr8)
-      return fail(e, VC_ESTATE, "option '%s': this engine was created with VC_FINISHED_ROWS=0 and VC_FR_ONE=0 and holds no 8-channel weight images", name.c_str());
-    if (name == "fr_one") e->fr_one = std::max(0, std::min(v0, 2));
-    else e->fr_rows = std::max(0, std::min(v0, VC_ROWS));
-  } else if (name == "fr_pair") { e->fr_pair = v0 ? 1 : 0;
-  } else if (name == "qkv_p8") {
-    if (v0 && !e->has_qkv8 && vc_gemm_fr1_ok(3 * e->d, e->d, e->dtype, 4))
-      return fail(e, VC_ESTATE, "option 'qkv_p8': this engine was created with VC_QKV_P8=0 or VC_FR_ONE=0 and holds no 8-channel image of the QKV matrix");
-    e->qkv_p8 = std::max(0, std::min(v0, 2));      // 2: steps of 2..8 finished rows as well (rows_gemm_qp_k)
-  } else if (name == "wide_heads") { e->wide_heads = v0 ? 1 : 0;
-  } else if (name == "wide_gemm") { e->wide_gemm = v0 ? 1 : 0;
-  } else if (name == "shrink") { e->shrink = v0 ? 1 : 0;
-  } else if (name == "wd_stage") { e->wd_stage = v0 ? 1 : 0;
-  } else if (name == "qkv16") {
-    if (v0 && !e->has_qkv16)
-      return fail(e, VC_ESTATE, "option 'qkv16': this engine holds no 16-channel image of the QKV matrix (packed for max_seqs > 16, or with VC_QKV16=1 at creation)");
-    e->qkv16 = v0 ? 1 : 0;
-  } else if (name == "w13") {      // mask: 1 FFN-down, 4 QKV; a matrix without planes (fp32, narrow, refused, VC_W13=0) keeps its bf16 launch
-    if (v0 < 0 || (v0 & ~5)) return fail(e, VC_EINVAL, "option 'w13': %d is not a mask of 1 (FFN-down) and 4 (QKV)", v0);
-    e->w13 = v0;
-  } else if (name == "w8") {       // mask like "w13", on an engine that requested the w8 form (vc_request_w8); the w8 bit wins over the w13 bit
-    if (!e->w8_req) return fail(e, VC_EINVAL, "option 'w8': this engine was created without vc_request_w8");
-    if (v0 < 0 || (v0 & ~5)) return fail(e, VC_EINVAL, "option 'w8': %d is not a mask of 1 (FFN-down) and 4 (QKV)", v0);
-    e->w8 = v0;
-  } else if (name == "attn_fast") { e->attn_fast = v0 ? 1 : 0;
-  } else if (name == "att_p16") { e->att_p16 = v0 ? 1 : 0;
-  } else if (name == "hq") { e->hq = v0 ? 1 : 0;
-  } else if (name == "nt") {      // "mask[,kv]": the weight matrices streamed with the hint, and the decode attention's K/V loads (0 never, 1 always, 2 from two rows up)
-    e->nt_decode = v0 & 63;
-    if (n >= 2) e->attn_nt = std::max(0, std::min(v1, 2));
-  } else if (name == "prefill_rows") { e->prefill_rows_per_pass = std::max(VC_ROWS, std::min(VC_MAX_ROWS, v0 / VC_ROWS * VC_ROWS));   // 16: decode kernels only
-  } else {
-    return fail(e, VC_EINVAL, "unknown option '%s'", name.c_str());
+  for (const OptDesc& o : OPTIONS) {
+    if (name != o.name) continue;
+    if (o.check)
+      if (const int rc = o.check(e, o.name, v[0])) return rc;
+    e->*o.v0.f = std::max(o.v0.lo, std::min(o.pre ? o.pre(v[0]) : v[0], o.v0.hi));
+    if (o.v1.f && n >= 2) e->*o.v1.f = std::max(o.v1.lo, std::min(v[1], o.v1.hi));
+    return VC_OK;
   }
-  return VC_OK;
+  return fail(e, VC_EINVAL, "unknown option '%s'", name.c_str());
 }
 
 void refresh_opt_state(vc_engine* e) {
-  char buf[256];
-  snprintf(buf, sizeof buf, "g=%d|nt=%d,%d|fr=%d,%d,%d,%d|ta=%d,%d|r1=%d,%d,%d|q16=%d,%d,%d,%d|sh=%d|w13=%d",
-           e->steps_per_graph, e->nt_decode, e->attn_nt, e->fr_rows, e->fr_pair, e->att_p16, e->hq, e->tile_attn, e->tile_attn_min_rows,
-           e->fr_one, e->attn_fast, e->qkv_p8, e->qkv16, e->wide_heads, e->wide_gemm, e->wd_stage, e->shrink, e->w13);
-  e->opt_state = buf;
-  if (e->w8_req) e->opt_state += "|w8=" + std::to_string(e->w8);      // only an engine that requested the form has the option
+  std::string& t = e->opt_state;
+  t.clear();
+  const char* tag = "";
+  for (const OptDesc& o : OPTIONS) {
+    if (!o.tag || (o.only_if && !(e->*o.only_if))) continue;
+    if (strcmp(tag, o.tag)) t += std::string(t.empty() ? "" : "|") + o.tag + "=";
+    else t += ",";
+    tag = o.tag;
+    t += std::to_string(e->*o.v0.f);
+    if (o.v1.f) t += "," + std::to_string(e->*o.v1.f);
+  }
+}
+
+int apply_env_presets(vc_engine* e) {
+  for (const OptDesc& o : OPTIONS)
+    if (const char* v = o.env ? getenv(o.env) : nullptr) {
+      // (VC_NT was a boolean through round 3 - 1 = on, the default; it is a per-matrix bit mask now: the legacy "1" keeps meaning "on")
+      if (!strcmp(o.env, "VC_NT") && !strcmp(v, "1")) v = "63";
+      if (const int rc = apply_option(e, o.name, v)) return rc;
+    }
+  refresh_opt_state(e);
+  return VC_OK;
 }
 
 }  // namespace
@@ -1433,10 +1501,8 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
           (rc = pack_planes(e, ly, kind, W13_QKV, ly.Wqkv8, (long)(3 * d / VC_TH_RES) * (d / 64)))) return rc;
     }
     const size_t cache_bytes = (size_t)e->B_max * e->H * e->S_max * e->hd * e->esz;
-    char* kc; char* vc;
-    if ((rc = dalloc(e, &kc, cache_bytes))) return rc;
-    if ((rc = dalloc(e, &vc, cache_bytes))) return rc;
-    ly.kc = kc; ly.vc = vc;
+    if ((rc = dalloc(e, &ly.kc, cache_bytes))) return rc;
+    if ((rc = dalloc(e, &ly.vc, cache_bytes))) return rc;
     // free the staging copies of this layer right away (3.3 GB for the 830M shape otherwise)
     for (const char* k2 : {"self_attn.in_proj_weight", "self_attn.out_proj.weight", "linear1.weight", "linear2.weight"}) {
       auto it = e->raw.find(pre + k2);
@@ -1503,13 +1569,9 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
   if ((rc = dalloc(e, &e->parts, (size_t)VC_MAX_KSPLIT * VC_SLAB_ROWS * d))) return rc;
   if ((rc = dalloc(e, &e->att_o, (size_t)VC_ROWS * e->H * VC_MAX_NSPLIT * e->hd))) return rc;     // split partials: decode-size passes only
   if ((rc = dalloc(e, &e->att_ml, (size_t)VC_ROWS * e->H * VC_MAX_NSPLIT * 2))) return rc;
-  char* tmp;
-  if ((rc = dalloc(e, &tmp, (size_t)VC_MAX_ROWS * 4 * d * e->esz))) return rc;
-  e->act = tmp;
-  if ((rc = dalloc(e, &tmp, (size_t)VC_MAX_ROWS * d * e->esz))) return rc;
-  e->xn = tmp;
-  if ((rc = dalloc(e, &tmp, (size_t)e->NS * K * P * e->esz))) return rc;
-  e->hh = tmp;
+  if ((rc = dalloc(e, &e->act, (size_t)VC_MAX_ROWS * 4 * d * e->esz))) return rc;
+  if ((rc = dalloc(e, &e->xn, (size_t)VC_MAX_ROWS * d * e->esz))) return rc;
+  if ((rc = dalloc(e, &e->hh, (size_t)e->NS * K * P * e->esz))) return rc;
   if ((rc = dalloc(e, &e->logits, (size_t)e->NS * K * V))) return rc;
   if ((rc = dalloc(e, &e->dec_h, (size_t)e->NS * d))) return rc;
   if ((rc = dalloc(e, &e->dec_row_seq, (size_t)e->NS))) return rc;
@@ -1518,11 +1580,8 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
   if ((rc = dalloc(e, &e->st, (size_t)e->NS))) return rc;
   if ((rc = dalloc(e, &e->st_fin, (size_t)e->NS))) return rc;
   {
-    char* t2;
-    if ((rc = dalloc(e, &t2, (size_t)VC_ROWS * d * e->esz))) return rc;
-    e->hqA = t2;
-    if ((rc = dalloc(e, &t2, (size_t)VC_ROWS * d * e->esz))) return rc;
-    e->hqB = t2;
+    if ((rc = dalloc(e, &e->hqA, (size_t)VC_ROWS * d * e->esz))) return rc;
+    if ((rc = dalloc(e, &e->hqB, (size_t)VC_ROWS * d * e->esz))) return rc;
     if ((rc = dalloc(e, &e->row_mu[0], (size_t)VC_ROWS))) return rc;
     if ((rc = dalloc(e, &e->row_mu[1], (size_t)VC_ROWS))) return rc;
     if ((rc = dalloc(e, &e->mu_zero, (size_t)VC_ROWS))) return rc;
@@ -1582,18 +1641,7 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
   HIPCHK(e, hipStreamCreate(&e->own_stream));
   HIPCHK(e, hipStreamCreateWithFlags(&e->side_stream, hipStreamNonBlocking));
   // ---- options: the VC_* environment variables preset them, vc_set_option changes them at run time
-  for (const auto& kv : {std::make_pair("VC_NT", "nt"), std::make_pair("VC_PREFILL_ROWS", "prefill_rows"), 
-                         std::make_pair("VC_GRAPH_STEPS", "graph_steps"),
-                         
-                         std::make_pair("VC_FINISHED_ROWS", "finished_rows"),
-                         std::make_pair("VC_TILE_ATTN", "tile_attn"),
-                         std::make_pair("VC_FR_ONE", "fr_one"), std::make_pair("VC_QKV_P8", "qkv_p8"), std::make_pair("VC_FR_PAIR", "fr_pair"), std::make_pair("VC_QKV16", "qkv16"), std::make_pair("VC_WIDE_HEADS", "wide_heads"), std::make_pair("VC_WIDE_GEMM", "wide_gemm"), std::make_pair("VC_WD_STAGE", "wd_stage"), std::make_pair("VC_SHRINK", "shrink"), std::make_pair("VC_ATTN_FAST", "attn_fast"), std::make_pair("VC_ATT_P16", "att_p16"), std::make_pair("VC_HQ", "hq"), std::make_pair("VC_W13", "w13")})
-    if (const char* v = getenv(kv.first)) {
-      // (VC_NT was a boolean through round 3 - 1 = on, the default; it is a per-matrix bit mask now: the legacy "1" keeps meaning "on")
-      if (std::string(kv.first) == "VC_NT" && std::string(v) == "1") v = "63";
-      if ((rc = apply_option(e, kv.second, v))) return rc;
-    }
-  refresh_opt_state(e);
+  if ((rc = apply_env_presets(e))) return rc;
   HIPCHK(e, hipDeviceSynchronize());
   e->finalized = true;
   return VC_OK;
@@ -1604,10 +1652,10 @@ namespace {
 
 struct TtsJob { const int64_t* x; int Lx; const int64_t* y; int T; };
 
-// After a one-row-per-sequence decode loop: the final states by slot into h_st[0, B) and the call's re-pack count (host_ms[6]).
-// Shared by tts_run and vc_edit_multi.
+// After a one-row-per-sequence decode loop: the final states by slot into h_st[0, B) and the call's re-pack count (host_ms[HM_REPACKS]).
+// For one sequence that is the copy of its state.
 int collect_states(vc_engine* e, int B, hipStream_t s) {
-  if (!e->repack_at.empty()) HIPCHK(e, hipMemcpyAsync(e->h_flag + 11, e->step_ctr, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (!e->repack_at.empty()) HIPCHK(e, hipMemcpyAsync(e->h_flag + HF_LIVE_STEPS, e->step_ctr, sizeof(int), hipMemcpyDeviceToHost, s));
   if (e->cur_rows == B) {
     HIPCHK(e, hipMemcpyAsync(e->h_st, e->st, sizeof(SeqState) * B, hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
@@ -1627,7 +1675,87 @@ int collect_states(vc_engine* e, int B, hipStream_t s) {
   // (step_ctr stops at the last one) reach into batch k.  Whether the host queues one more after the last sequence has retired
   // depends on how far it trails the device, so that one is not counted and the figure is the same in every run
   for (int k : e->repack_at)
-    if (e->h_flag[11] > k * std::max(1, e->steps_per_graph)) e->host_ms[6] += 1;
+    if (e->h_flag[HF_LIVE_STEPS] > k * std::max(1, e->steps_per_graph)) e->host_ms[HM_REPACKS] += 1;
+  return VC_OK;
+}
+
+// A TTS request's prompt - one segment: the T prompt frames and the first generated column; `skip` text positions are read from
+// sequence 0's cache, whose text x_shared is - and its first state.  (The blocking calls and a session's admission.)
+SeqState tts_request(vc_engine* e, const TtsJob& j, int skip, const int64_t* x_shared, PromptArgs* pa) {
+  fill_prompt_common(e, *pa, j.x, j.Lx, j.y, j.T);
+  pa->n_seg = 1; pa->n_cols = j.T + 1;
+  pa->seg[0] = Segment{0, j.T + 1, 0, j.T, -1, -1};
+  pa->skip = skip; pa->x_shared = x_shared;
+  return init_state(e, j.Lx, j.T + 1, true, 1);
+}
+
+// Best-of-N prefills once and replicates: the prompt positions of the entries the caller has laid down in `kv` (source and destination
+// slots, position ranges), copied in every layer's K and V cache - one launch per cache tensor, whatever the number of entries.
+int replicate_kv(vc_engine* e, CopyKvArgs kv, hipStream_t s) {
+  const long esz = e->dtype == VC_DTYPE_BF16 ? 2 : 4;
+  kv.H = e->H; kv.head_stride_b = (long)e->S_max * e->hd * esz; kv.pos_b = (long)e->hd * esz;
+  kv.seq_stride_b = (long)e->H * kv.head_stride_b;
+  for (int l = 0; l < e->L; ++l) {
+    kv.base = (char*)e->layers[l].kc;
+    HIPCHK(e, vc_launch_copy_kv(kv, s));
+    kv.base = (char*)e->layers[l].vc;
+    HIPCHK(e, vc_launch_copy_kv(kv, s));
+  }
+  return VC_OK;
+}
+
+// The blocking call's skeleton, shared by the TTS calls (tts_prepare / call_end; the streaming call too), vc_edit and vc_edit_multi:
+//   call_begin - the caller's prompts and prefill, its first states into h_st[0, B) - call_arm - the decode loop - call_end.
+// call_begin: every graph a call of this shape can need, captured ahead of both timers (between ev[0] and ev[1] the host
+// time of capture + instantiation showed up as prefill time of a first call of a shape / option state), then ev[0].
+// groups: as DecodeLoop (0, or the number of best-of-N groups).
+int call_begin(vc_engine* e, int B, int rps, int groups, const vc_sample_cfg* sc, int max_steps, hipStream_t s) {
+  DecodeLoop L;
+  L.init(e, make_sample_args(e, B, rps), B, rps, groups, sc, max_steps, s);
+  if (const int rc = L.precapture()) return rc;
+  HIPCHK(e, hipEventRecord(e->ev[0], s));
+  return VC_OK;
+}
+
+// call_arm: the states up, the live words set, the sampler's per-call values, the prompts' error word, and the first sample - it comes
+// from the prefill logits - ahead of ev[1].  *sa: the sampler arguments the decode loop starts with.  n_group: samples per best-of-N group.
+// parked: the call's loop may re-pack, so the states a re-pack parks (st_fin) are cleared.  vc_edit's one sequence never re-packs and
+// its stream stays without the clear: with it bench.py --mode edit decoded 0.5 % slower (0.5459 against 0.5433 ms per step, parent spread
+// 0.0005; without it 0.5433 against 0.5428, profiles/host_paths_ab.log).
+int call_arm(vc_engine* e, int B, int rps, int n_group, bool parked, const vc_sample_cfg* sc, const int64_t* forced, int n_forced,
+             float* logits_out, int logit_steps, hipStream_t s, SampleArgs* sa) {
+  HIPCHK(e, hipMemcpyAsync(e->st, e->h_st, sizeof(SeqState) * B, hipMemcpyHostToDevice, s));
+  if (parked) HIPCHK(e, hipMemsetAsync(e->st_fin, 0, sizeof(SeqState) * B, s));
+  e->h_flag[HF_STAGE] = B;
+  e->h_flag[HF_ACTIVE] = B;
+  e->h_flag[HF_LIVE0] = B; e->h_flag[HF_LIVE1] = B;        // the two slots of "sequences still live" (SampleArgs.host_live)
+  e->host_ms[HM_REPACKS] = 0;
+  HIPCHK(e, hipMemcpyAsync(e->n_active, e->h_flag + HF_STAGE, sizeof(int), hipMemcpyHostToDevice, s));
+  int rc = push_sample_dyn(e, sc, forced, n_forced, logits_out, logit_steps, B, s, n_group);
+  if (rc) return rc;
+  rc = check_err_flag(e, s);   // also orders the pinned-buffer reuse
+  if (rc) return rc;
+  *sa = make_sample_args(e, B, rps);
+  HIPCHK(e, vc_launch_sample(*sa, n_group > 1, s));
+  HIPCHK(e, hipEventRecord(e->ev[1], s));
+  return VC_OK;
+}
+
+// call_end: ev[2], the final states by slot in h_st[0, B), the timings, and the steps really taken (the longest sequence; feed steps of
+// an edit not counted), not the launched multiple of steps_per_graph.
+int call_end(vc_engine* e, int B, bool grouped, int* steps_out, hipStream_t s) {
+  HIPCHK(e, hipEventRecord(e->ev[2], s));
+  int rc = collect_states(e, B, s);
+  if (rc) return rc;
+  if (grouped && (rc = check_err_flag(e, s))) return rc;      // the keep decisions' row check (advance_phase)
+  HIPCHK(e, hipEventElapsedTime(&e->ms[0], e->ev[0], e->ev[1]));
+  HIPCHK(e, hipEventElapsedTime(&e->ms[1], e->ev[1], e->ev[2]));
+  e->ms[2] = e->ms[0] + e->ms[1];
+  if (steps_out) {
+    int m = 0;
+    for (int b = 0; b < B; ++b) m = std::max(m, e->h_st[b].total_steps);
+    *steps_out = m;
+  }
   return VC_OK;
 }
 
@@ -1635,9 +1763,9 @@ int collect_states(vc_engine* e, int B, hipStream_t s) {
 // sequence of slot u * N + j and, with N > 1, a member of best-of-N group u.  vc_tts is (1, N), vc_tts_multi (U, 1) and
 // vc_tts_multi_best_of (U, N).
 // tts_prepare: everything up to and including the first sample (graphs pre-captured ahead of the timers, prompts, prefill, state
-// upload, sampler values, the sample from the prefill logits); tts_finish: everything behind the decode loop (states, timing).  The
-// blocking calls run prepare - decode_loop - finish back to back (tts_run); the streaming call keeps the loop open in between.
-struct TtsPrep { SampleArgs sa; int B = 0, U = 0, N = 0, max_steps = 0; bool grouped = false; };
+// upload, sampler values, the sample from the prefill logits); call_end: everything behind the decode loop (states, timing).  The
+// blocking calls run prepare - decode_loop - call_end back to back (tts_run); the streaming call keeps the loop open in between.
+struct TtsPrep { SampleArgs sa; int B = 0, U = 0, max_steps = 0; bool grouped = false; };
 int tts_prepare(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const vc_sample_cfg* sc,
                 const int64_t* forced, int n_forced, float* logits_out, int logit_steps,
                 hipStream_t s, int shared_prefix, TtsPrep* prep, bool* share_armed) {
@@ -1669,30 +1797,20 @@ int tts_prepare(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, co
     max_steps = std::max(max_steps, steps);
   }
   max_steps = std::min(max_steps, e->gen_cap);
-  // (a first call of this shape / option state captures its decode graphs HERE, ahead of both timers - ADVICE r05: between ev[0] and
-  // ev[1] the host time of capture + instantiation showed up as prefill time of that first call)
-  {
-    SampleArgs sa0 = make_sample_args(e, B, 1);
-    if (int rc0 = decode_loop(e, sa0, B, 1, grouped ? U : 0, sc, max_steps, nullptr, s, true)) return rc0;
-  }
-  HIPCHK(e, hipEventRecord(e->ev[0], s));
+  if (const int rc0 = call_begin(e, B, 1, grouped ? U : 0, sc, max_steps, s)) return rc0;
   // ---- prompts + ONE prefill over all of them, into the slots of the groups' first samples
   {
     std::vector<PromptArgs> pas(U);
     std::vector<int> slots(U);
     for (int u = 0; u < U; ++u) {
       const TtsJob& j = jobs[u];
-      fill_prompt_common(e, pas[u], j.x, j.Lx, j.y, j.T);
-      pas[u].n_seg = 1; pas[u].n_cols = j.T + 1;
-      pas[u].seg[0] = Segment{0, j.T + 1, 0, j.T, -1, -1};
-      pas[u].skip = (u > 0) ? shared_prefix : 0;          // the shared text prefix is prefilled once, in sequence 0
-      pas[u].x_shared = jobs[0].x;                        // ... and checked on the device to be the same text (prompt_k)
+      // the shared text prefix is prefilled once, in sequence 0, and checked on the device to be the same text (prompt_k)
+      e->h_st[u * N] = tts_request(e, j, (u > 0) ? shared_prefix : 0, jobs[0].x, &pas[u]);
       slots[u] = u * N;
-      e->h_st[u * N] = init_state(e, j.Lx, j.T + 1, true, 1);
       e->h_st[u * N].slot = u * N;
     }
-    e->h_flag[2] = shared_prefix;
-    HIPCHK(e, hipMemcpyAsync(e->share_len, e->h_flag + 2, sizeof(int), hipMemcpyHostToDevice, s));
+    e->h_flag[HF_SHARE] = shared_prefix;
+    HIPCHK(e, hipMemcpyAsync(e->share_len, e->h_flag + HF_SHARE, sizeof(int), hipMemcpyHostToDevice, s));
     *share_armed = shared_prefix > 0;
     int rc = prefill_batch(e, pas, slots, s);
     if (rc) return rc;
@@ -1709,15 +1827,7 @@ int tts_prepare(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, co
       kv.p0[u] = shared_prefix; kv.p1[u] = jobs[u].Lx + jobs[u].T + 1;
     }
     CopyKvArgs lg = kv;
-    const long esz = e->dtype == VC_DTYPE_BF16 ? 2 : 4;
-    kv.H = e->H; kv.head_stride_b = (long)e->S_max * e->hd * esz; kv.pos_b = (long)e->hd * esz;
-    kv.seq_stride_b = (long)e->H * kv.head_stride_b;
-    for (int l = 0; l < e->L; ++l) {
-      kv.base = (char*)e->layers[l].kc;
-      HIPCHK(e, vc_launch_copy_kv(kv, s));
-      kv.base = (char*)e->layers[l].vc;
-      HIPCHK(e, vc_launch_copy_kv(kv, s));
-    }
+    if (const int rc = replicate_kv(e, kv, s)) return rc;
     lg.base = (char*)e->logits; lg.H = 1; lg.seq_stride_b = lg.pos_b = (long)K * e->V * 4;
     for (int u = 0; u < U; ++u) { lg.p0[u] = 0; lg.p1[u] = 1; }
     HIPCHK(e, vc_launch_copy_kv(lg, s));
@@ -1729,40 +1839,8 @@ int tts_prepare(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, co
         st.group = u;
       }
   }
-  HIPCHK(e, hipMemcpyAsync(e->st, e->h_st, sizeof(SeqState) * B, hipMemcpyHostToDevice, s));
-  HIPCHK(e, hipMemsetAsync(e->st_fin, 0, sizeof(SeqState) * B, s));
-  e->h_flag[1] = B;
-  e->h_flag[8] = B;
-  e->h_flag[9] = B; e->h_flag[10] = B;        // the two slots of "sequences still live" (SampleArgs.host_live)
-  e->host_ms[6] = 0;
-  HIPCHK(e, hipMemcpyAsync(e->n_active, e->h_flag + 1, sizeof(int), hipMemcpyHostToDevice, s));
-  int rc = push_sample_dyn(e, sc, forced, n_forced, logits_out, logit_steps, B, s, N);
-  if (rc) return rc;
-  rc = check_err_flag(e, s);   // also orders the pinned-buffer reuse
-  if (rc) return rc;
-  // ---- first sample comes from the prefill logits, then the decode loop
-  SampleArgs sa = make_sample_args(e, B, 1);
-  HIPCHK(e, vc_launch_sample(sa, grouped, s));
-  HIPCHK(e, hipEventRecord(e->ev[1], s));
-  prep->sa = sa; prep->B = B; prep->U = U; prep->N = N; prep->max_steps = max_steps; prep->grouped = grouped;
-  return VC_OK;
-}
-
-int tts_finish(vc_engine* e, const TtsPrep& prep, int* steps_out, hipStream_t s) {
-  const int B = prep.B;
-  const bool grouped = prep.grouped;
-  HIPCHK(e, hipEventRecord(e->ev[2], s));
-  int rc = collect_states(e, B, s);
-  if (rc) return rc;
-  if (grouped && (rc = check_err_flag(e, s))) return rc;      // the keep decisions' row check (advance_phase)
-  HIPCHK(e, hipEventElapsedTime(&e->ms[0], e->ev[0], e->ev[1]));
-  HIPCHK(e, hipEventElapsedTime(&e->ms[1], e->ev[1], e->ev[2]));
-  e->ms[2] = e->ms[0] + e->ms[1];
-  if (steps_out) {   // steps really taken (the longest sequence), not the launched multiple of steps_per_graph
-    int m = 0;
-    for (int b = 0; b < B; ++b) m = std::max(m, e->h_st[b].total_steps);
-    *steps_out = m;
-  }
+  if (const int rc = call_arm(e, B, 1, N, true, sc, forced, n_forced, logits_out, logit_steps, s, &prep->sa)) return rc;
+  prep->B = B; prep->U = U; prep->max_steps = max_steps; prep->grouped = grouped;
   return VC_OK;
 }
 
@@ -1778,10 +1856,9 @@ int tts_run(vc_engine* e, const std::vector<TtsJob>& jobs, int n_samples, const 
   TtsPrep prep;
   int rc = tts_prepare(e, jobs, n_samples, sc, forced, n_forced, logits_out, logit_steps, s, shared_prefix, &prep, &share_guard.armed);
   if (rc) return rc;
-  int steps_run = 0;
-  rc = decode_loop(e, prep.sa, prep.B, 1, prep.grouped ? prep.U : 0, sc, prep.max_steps, &steps_run, s);
+  rc = decode_loop(e, prep.sa, prep.B, 1, prep.grouped ? prep.U : 0, sc, prep.max_steps, s);
   if (rc) return rc;
-  return tts_finish(e, prep, steps_out, s);
+  return call_end(e, prep.B, prep.grouped, steps_out, s);
 }
 
 // The sample utterance u of a tts_run keeps: the member that is kept, done and has its span (-1 if none terminated).
@@ -1812,11 +1889,8 @@ int assemble_tts(vc_engine* e, const TtsJob& j, int slot, const SeqState& st, in
   *gen_len = Tg;
   return VC_OK;
 }
-int assemble_tts(vc_engine* e, const TtsJob& j, int slot, int64_t* res, int res_cap, int* gen_len, hipStream_t s) {
-  return assemble_tts(e, j, slot, e->h_st[slot], res, res_cap, gen_len, s);
-}
 
-// ---- the streaming TTS call: tts_prepare at begin, the DecodeLoop advanced from next, tts_finish + assemble_tts at end
+// ---- the streaming TTS call: tts_prepare at begin, the DecodeLoop advanced from next, call_end + assemble_tts at end
 }  // namespace
 struct TtsStream {
   TtsJob job{};
@@ -1824,7 +1898,7 @@ struct TtsStream {
   DecodeLoop L{};
   hipStream_t s = nullptr;
   int emitted = 0;          // frames handed out so far
-  bool finished = false;    // tts_finish has run: h_st[0] holds the final state
+  bool finished = false;    // call_end has run: h_st[0] holds the final state
   int finish_rc = VC_OK;
   int Tg = -1;              // generated frames, known once finished (-1: the sequence did not terminate)
   int n_steps = 0;
@@ -1840,7 +1914,7 @@ int stream_finalize(vc_engine* e) {
   TtsStream& t = *e->ts;
   if (t.finished) return t.finish_rc;
   t.L.finish(nullptr);
-  t.finish_rc = tts_finish(e, t.prep, &t.n_steps, t.s);
+  t.finish_rc = call_end(e, t.prep.B, t.prep.grouped, &t.n_steps, t.s);
   t.finished = true;
   const SeqState& st = e->h_st[0];
   if (t.finish_rc == VC_OK && st.done && st.span >= 1) t.Tg = std::max(0, st.span_steps[0] - e->K);
@@ -1852,11 +1926,11 @@ int stream_gather(vc_engine* e, int rows, int64_t* codes, int cap, int* n_out) {
   TtsStream& t = *e->ts;
   StreamGatherArgs a;
   memset(&a, 0, sizeof a);
-  a.st = e->st; a.gen = e->gen; a.K = e->K; a.rows = rows; a.first = t.emitted; a.cap = cap; a.out = codes; a.host_n = e->h_flag + 12;
-  e->h_flag[12] = 0;
+  a.st = e->st; a.gen = e->gen; a.K = e->K; a.rows = rows; a.first = t.emitted; a.cap = cap; a.out = codes; a.host_n = e->h_flag + HF_GATHER_N;
+  e->h_flag[HF_GATHER_N] = 0;
   HIPCHK(e, vc_launch_stream_gather(a, e->side_stream));
   HIPCHK(e, hipStreamSynchronize(e->side_stream));       // the side stream only: the decode stream's queued graphs are not waited for
-  *n_out = e->h_flag[12];
+  *n_out = e->h_flag[HF_GATHER_N];
   return VC_OK;
 }
 }  // namespace
@@ -1935,7 +2009,7 @@ extern "C" int vc_tts_stream_end(vc_engine* e, int64_t* res_dev, int res_cap, in
   }
   while (rc == VC_OK && !t.L.over) rc = t.L.advance();
   if (rc == VC_OK) rc = stream_finalize(e);
-  if (rc == VC_OK) rc = assemble_tts(e, t.job, 0, res_dev, res_cap, gen_len, t.s);
+  if (rc == VC_OK) rc = assemble_tts(e, t.job, 0, e->h_st[0], res_dev, res_cap, gen_len, t.s);
   if (rc == VC_OK) {
     hipError_t se = hipStreamSynchronize(t.s);
     if (se != hipSuccess) rc = fail(e, VC_EHIP, "hipStreamSynchronize: %s", hipGetErrorString(se));
@@ -2057,7 +2131,7 @@ int edit_assemble(vc_engine* e, const EditJob& j, const SeqState& fs, const int*
 //   4. queue, on the decode stream: the prompts and ONE prefill of the admitted requests into their K/V slots, session_turn_k (stamp of the
 //      next batch; re-pack of the live rows onto the width now needed, narrower or wider; the admitted requests' initial states behind
 //      them; fillers; n_active raised), the first sample of the admitted rows alone, and the next batch of graph_steps steps.
-//      The admitted requests' first states (init_state of a TTS request; edit_state with feed_switch of an editing request - one row
+//      The admitted requests' first states (tts_request for a TTS request; edit_state with feed_switch of an editing request - one row
 //      per request, its span switches fed over three steps as in vc_edit_multi) and their sampling controls are written into pinned
 //      staging buffer (batch % VC_ADM_STAGES) and uploaded on the decode stream in front of session_turn_k.  That buffer is written again
 //      VC_ADM_STAGES turns later at the earliest; a turn queues only after the batch two turns back has ENDED (step 1), and a batch ends
@@ -2114,7 +2188,7 @@ struct Session {
   std::deque<int> fifo;
   std::map<int, SessReq> reqs;
   std::vector<int> slot_ticket;      // [max_live] ticket holding the slot (live, or finished and not yet fetched), -1 = free
-  long long stats[8]{};
+  long long stats[8]{};     // indexed by SS_*
   // decode-stream time of each admission (prefill + session_turn_k + first sample): event pairs, read once their batch has ended
   hipEvent_t ev_adm[4][2]{};
   int ev_turn[4]{-1, -1, -1, -1};
@@ -2167,7 +2241,7 @@ void session_note_retired(vc_engine* e, Session& t, int known, int* tickets_out,
       r.mdone[m] = 1;
       r.members_left -= 1;
       t.live -= 1;
-      t.stats[5] += std::max(0, (int)rec[1] - 1) + std::max(0, (int)rec[5]);
+      t.stats[SS_LIVE_ROWS] += std::max(0, (int)rec[1] - 1) + std::max(0, (int)rec[5]);
       t.slot_ticket[slot] = -1;
       if (r.members_left == 0) {
         // (a kept member whose record had been read before the cancel was still holding its slot for the fetch)
@@ -2187,7 +2261,7 @@ void session_note_retired(vc_engine* e, Session& t, int known, int* tickets_out,
       r.mdone[m] = 1;
       r.members_left -= 1;
       t.live -= 1;
-      t.stats[5] += std::max(0, (int)rec[1] - 1);
+      t.stats[SS_LIVE_ROWS] += std::max(0, (int)rec[1] - 1);
       r.prompt_err |= rec[4];
       if (rec[6] && rec[2] >= 1 && m >= r.kept) {       // (at most one member ends kept with its span finished: advance_phase)
         r.kept = m;
@@ -2211,7 +2285,7 @@ void session_note_retired(vc_engine* e, Session& t, int known, int* tickets_out,
     for (int i = 0; i < VC_MAX_SPANS; ++i) r.span_steps[i] = rec[VC_SESS_REC_SPANS + i];
     t.live -= 1;
     // rows of launched steps that were live: every step of the request but its first sample, and the rows an edit fed at its span switches
-    t.stats[5] += std::max(0, r.total_steps - 1) + std::max(0, r.fed);
+    t.stats[SS_LIVE_ROWS] += std::max(0, r.total_steps - 1) + std::max(0, r.fed);
     tickets_out[*n_fin] = ticket;
     *n_fin += 1;
   }
@@ -2239,7 +2313,7 @@ extern "C" int vc_session_open_best_of(vc_engine* e, int max_live, int max_sampl
   // (SampleDyn.seed_tab / ctl_tab by slot), the controls given here being the default of a request that brings none
   if ((rc = push_sample_dyn(e, sc, nullptr, 0, nullptr, 0, max_live, s))) return bail(rc);
   memset(e->h_rec, 0, sizeof(int) * VC_SESS_REC * e->NS);
-  e->h_flag[1] = 0; e->h_flag[8] = 0; e->h_flag[9] = 0; e->h_flag[10] = 0;
+  e->h_flag[HF_STAGE] = 0; e->h_flag[HF_ACTIVE] = 0; e->h_flag[HF_LIVE0] = 0; e->h_flag[HF_LIVE1] = 0;
   hipError_t he = hipMemsetAsync(e->n_active, 0, sizeof(int), s);
   if (he == hipSuccess) he = hipMemsetAsync(e->step_ctr, 0, sizeof(int), s);
   if (he == hipSuccess) he = hipMemsetAsync(e->batch_id, 0, sizeof(int), s);
@@ -2251,7 +2325,7 @@ extern "C" int vc_session_open_best_of(vc_engine* e, int max_live, int max_sampl
   t->L.init(e, make_sample_args(e, t->top, 1), t->top, 1, 0, sc, 0, s);
   t->L.sess = true;
   t->L.grouped = t->grouped;      // graphs of their own: the steps of such a session end in the sample / advance pair
-  e->host_ms[1] = e->host_ms[2] = 0;
+  e->host_ms[HM_CAPTURE] = e->host_ms[HM_INSTANTIATE] = 0;
   if (sc->use_graph) {
     hipGraphExec_t exec = nullptr;
     for (int w = t->top; w >= 1 && rc == VC_OK; w = (w == t->top) ? DecodeLoop::width_for(w) / 2 : w / 2) {
@@ -2369,7 +2443,7 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
   hipStream_t s = t.s;
   const int G = t.L.G;
   *n_finished = 0; *idle = 0;
-  t.stats[2] += 1;
+  t.stats[SS_TURNS] += 1;
   // ---- 1, 2: the older batch in flight, and what it (or an earlier one) retired
   int known = t.run_start - 1;
   if (t.batch - t.run_start >= 2) {
@@ -2430,10 +2504,7 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
       st0.feed_switch = 1;
       pa = r.edit.pa;
     } else {
-      st0 = init_state(e, r.job.Lx, r.job.T + 1, true, 1);
-      fill_prompt_common(e, pa, r.job.x, r.job.Lx, r.job.y, r.job.T);
-      pa.n_seg = 1; pa.n_cols = r.job.T + 1;
-      pa.seg[0] = Segment{0, r.job.T + 1, 0, r.job.T, -1, -1};
+      st0 = tts_request(e, r.job, 0, nullptr, &pa);
     }
     if (N > 1) st0.group = id;                              // the group of the keep decision is the request (advance_phase)
     pas.push_back(pa);                                      // ONE prefill per request, into its first slot
@@ -2484,15 +2555,7 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
       // cache tensor for every group of the turn.  The first-step logits are not copied: every member's first sample reads the row
       // of the group's first slot (session_groups_k)
       kv.n_dst = kv.n_ent;
-      const long esz = e->dtype == VC_DTYPE_BF16 ? 2 : 4;
-      kv.H = e->H; kv.head_stride_b = (long)e->S_max * e->hd * esz; kv.pos_b = (long)e->hd * esz;
-      kv.seq_stride_b = (long)e->H * kv.head_stride_b;
-      for (int l = 0; l < e->L; ++l) {
-        kv.base = (char*)e->layers[l].kc;
-        HIPCHK(e, vc_launch_copy_kv(kv, s));
-        kv.base = (char*)e->layers[l].vc;
-        HIPCHK(e, vc_launch_copy_kv(kv, s));
-      }
+      if ((rc = replicate_kv(e, kv, s))) return rc;
     }
     HIPCHK(e, hipMemcpyAsync(e->adm_st, h_adm_st, sizeof(SeqState) * n_new, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(e->adm_ctl, h_adm_ctl, sizeof(vc_request_ctl) * n_new, hipMemcpyHostToDevice, s));
@@ -2512,30 +2575,21 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
     ga.adm_slot = e->adm_slot; ga.samp_tab = e->samp_tab; ga.n_new = n_new;
     HIPCHK(e, vc_launch_session_groups(ga, e->NS, s));
   }
-  if (t.B > 0 && w > t.B) t.stats[3] += 1;
-  if (w < t.B) t.stats[4] += 1;
+  if (t.B > 0 && w > t.B) t.stats[SS_WIDENINGS] += 1;
+  if (w < t.B) t.stats[SS_NARROWINGS] += 1;
   t.B = w;
   t.L.B = w; t.L.sa = make_sample_args(e, w, 1);
   if (n_new > 0) {
     HIPCHK(e, vc_launch_sample_session(t.L.sa, true, n_new, t.grouped, s));
     HIPCHK(e, hipEventRecord(t.ev_adm[ei][1], s));
     t.ev_turn[ei] = t.batch;
-    t.stats[0] += n_req;                                     // requests; the row sums [5], [6] count every sample's rows
-    if (live_before > 0) t.stats[1] += n_req;
+    t.stats[SS_ADMITTED] += n_req;                                     // requests; the row sums SS_LIVE_ROWS, SS_LAUNCHED_ROWS count every sample's rows
+    if (live_before > 0) t.stats[SS_ADMITTED_LIVE] += n_req;
     t.live += n_new;
   }
-  int rc = VC_OK;
-  if (t.sc.use_graph) {
-    hipGraphExec_t exec = nullptr;
-    if ((rc = t.L.exec_for(&exec))) return rc;
-    HIPCHK(e, hipGraphLaunch(exec, s));
-  } else {
-    for (int i = 0; i < G && rc == VC_OK; ++i) rc = decode_step(e, t.L.sa, w, 1, t.grouped, s, true);
-    if (rc) return rc;
-  }
-  HIPCHK(e, hipEventRecord(e->ev_pace[t.batch & 1], s));
+  if (const int rc = t.L.queue_batch(t.batch & 1)) return rc;
   t.batch += 1;
-  t.stats[6] += (long long)w * G;
+  t.stats[SS_LAUNCHED_ROWS] += (long long)w * G;
   return VC_OK;
   }();
   if (rc4) { t.broken = true; t.broken_msg = e->err; }
@@ -2628,7 +2682,7 @@ extern "C" int vc_session_cancel(vc_engine* e, int ticket, int* was) {
         if (r.mdone[i]) continue;
         volatile int* rec = e->h_rec + r.slots[i] * VC_SESS_REC;
         t.live -= 1;
-        t.stats[5] += std::max(0, (int)rec[1] - 1) + std::max(0, (int)rec[5]);
+        t.stats[SS_LIVE_ROWS] += std::max(0, (int)rec[1] - 1) + std::max(0, (int)rec[5]);
       }
       for (int& held : t.slot_ticket) if (held == ticket) held = -1;
       r.slot = -1;
@@ -2768,7 +2822,7 @@ extern "C" int vc_tts(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t*
     slot = kept_sample(e, 0, n_samples);
     if (slot < 0) return fail(e, VC_ECAP, "no sample terminated within the step budget");
   }
-  rc = assemble_tts(e, jobs[0], slot, res_dev, res_cap, gen_len, s);
+  rc = assemble_tts(e, jobs[0], slot, e->h_st[slot], res_dev, res_cap, gen_len, s);
   if (rc) return rc;
   HIPCHK(e, hipStreamSynchronize(s));
   return VC_OK;
@@ -2796,7 +2850,8 @@ extern "C" int vc_tts_multi_best_of(vc_engine* e, int B, int n_samples, const in
     const int j = n_samples > 1 ? kept_sample(e, b, n_samples) : 0;
     if (j < 0) return fail(e, VC_ECAP, "utterance %d: no sample terminated within the step budget", b);
     if (kept) kept[b] = j;
-    rc = assemble_tts(e, jobs[b], b * n_samples + j, res_dev + (size_t)b * e->K * res_cap, res_cap, &gen_len[b], s);
+    const SeqState& st = e->h_st[b * n_samples + j];
+    rc = assemble_tts(e, jobs[b], b * n_samples + j, st, res_dev + (size_t)b * e->K * res_cap, res_cap, &gen_len[b], s);
     if (rc) return rc;
   }
   HIPCHK(e, hipStreamSynchronize(s));
@@ -2825,41 +2880,15 @@ extern "C" int vc_edit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t
   EditJob j{x_dev, Lx, y_dev, T, mask_intervals, M, mask_values};
   if ((rc = edit_prepare(e, j, ""))) return rc;
   hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
-  const int max_steps = j.max_steps;
-  {   // decode graphs of a first call of this shape: captured ahead of both timers (as in tts_run)
-    SampleArgs sa0 = make_sample_args(e, 1, (M > 1) ? 3 : 1);
-    if ((rc = decode_loop(e, sa0, 1, (M > 1) ? 3 : 1, 0, sc, max_steps, nullptr, s, true))) return rc;
-  }
-  HIPCHK(e, hipEventRecord(e->ev[0], s));
-  {
-    std::vector<PromptArgs> pas(1, j.pa);
-    rc = prefill_batch(e, pas, std::vector<int>(1, 0), s);
-    if (rc) return rc;
-  }
+  const int rps = (M > 1) ? 3 : 1;      // a span switch is one 3-row step (vc_edit_multi feeds it over three one-row steps instead)
+  if ((rc = call_begin(e, 1, rps, 0, sc, j.max_steps, s))) return rc;
+  std::vector<PromptArgs> pas(1, j.pa);
+  if ((rc = prefill_batch(e, pas, std::vector<int>(1, 0), s))) return rc;
   e->h_st[0] = edit_state(e, j);
-  HIPCHK(e, hipMemcpyAsync(e->st, e->h_st, sizeof(SeqState), hipMemcpyHostToDevice, s));
-  e->h_flag[1] = 1;
-  e->h_flag[8] = 1;
-  HIPCHK(e, hipMemcpyAsync(e->n_active, e->h_flag + 1, sizeof(int), hipMemcpyHostToDevice, s));
-  rc = push_sample_dyn(e, sc, forced_dev, n_forced, logits_dev, logit_steps, 1, s);
-  if (rc) return rc;
-  rc = check_err_flag(e, s);
-  if (rc) return rc;
-  const int rps = (M > 1) ? 3 : 1;
-  SampleArgs sa = make_sample_args(e, 1, rps);
-  HIPCHK(e, vc_launch_sample(sa, false, s));
-  HIPCHK(e, hipEventRecord(e->ev[1], s));
-  int steps_run = 0;
-  rc = decode_loop(e, sa, 1, rps, 0, sc, max_steps, &steps_run, s);
-  if (rc) return rc;
-  HIPCHK(e, hipEventRecord(e->ev[2], s));
-  HIPCHK(e, hipMemcpyAsync(e->h_st, e->st, sizeof(SeqState), hipMemcpyDeviceToHost, s));
-  HIPCHK(e, hipStreamSynchronize(s));
-  HIPCHK(e, hipEventElapsedTime(&e->ms[0], e->ev[0], e->ev[1]));
-  HIPCHK(e, hipEventElapsedTime(&e->ms[1], e->ev[1], e->ev[2]));
-  e->ms[2] = e->ms[0] + e->ms[1];
-  if (n_steps) *n_steps = e->h_st[0].total_steps;
-  (void)steps_run;
+  SampleArgs sa;
+  if ((rc = call_arm(e, 1, rps, 1, false, sc, forced_dev, n_forced, logits_dev, logit_steps, s, &sa))) return rc;
+  if ((rc = decode_loop(e, sa, 1, rps, 0, sc, j.max_steps, s))) return rc;
+  if ((rc = call_end(e, 1, false, n_steps, s))) return rc;
   rc = edit_assemble(e, j, e->h_st[0], e->gen, res_dev, res_cap, res_len, s, "");
   if (rc) return rc;
   HIPCHK(e, hipStreamSynchronize(s));
@@ -2898,50 +2927,21 @@ extern "C" int vc_edit_multi(vc_engine* e, int B, const int64_t* x_dev, const in
     loop_steps = std::max(loop_steps, j.max_steps + 2 * (j.M - 1));     // + the two feed steps of every span switch
   }
   hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
-  {   // decode graphs (width B and the narrower widths a shrinking batch passes through): ahead of both timers, as in tts_run
-    SampleArgs sa0 = make_sample_args(e, B, 1);
-    if ((rc = decode_loop(e, sa0, B, 1, 0, sc, loop_steps, nullptr, s, true))) return rc;
-  }
-  HIPCHK(e, hipEventRecord(e->ev[0], s));
-  {
-    std::vector<PromptArgs> pas(B);
-    std::vector<int> slots(B);
-    for (int b = 0; b < B; ++b) { pas[b] = jobs[b].pa; slots[b] = b; }
-    rc = prefill_batch(e, pas, slots, s);
-    if (rc) return rc;
-  }
+  // (the graphs of width B and of the narrower widths a shrinking batch passes through)
+  if ((rc = call_begin(e, B, 1, 0, sc, loop_steps, s))) return rc;
+  std::vector<PromptArgs> pas(B);
+  std::vector<int> slots(B);
+  for (int b = 0; b < B; ++b) { pas[b] = jobs[b].pa; slots[b] = b; }
+  if ((rc = prefill_batch(e, pas, slots, s))) return rc;
   for (int b = 0; b < B; ++b) {
     e->h_st[b] = edit_state(e, jobs[b]);
     e->h_st[b].slot = b;
     e->h_st[b].feed_switch = 1;
   }
-  HIPCHK(e, hipMemcpyAsync(e->st, e->h_st, sizeof(SeqState) * B, hipMemcpyHostToDevice, s));
-  HIPCHK(e, hipMemsetAsync(e->st_fin, 0, sizeof(SeqState) * B, s));
-  e->h_flag[1] = B;
-  e->h_flag[8] = B;
-  e->h_flag[9] = B; e->h_flag[10] = B;        // the two slots of "sequences still live" (SampleArgs.host_live)
-  e->host_ms[6] = 0;
-  HIPCHK(e, hipMemcpyAsync(e->n_active, e->h_flag + 1, sizeof(int), hipMemcpyHostToDevice, s));
-  rc = push_sample_dyn(e, sc, forced_dev, n_forced, logits_dev, logit_steps, B, s);
-  if (rc) return rc;
-  rc = check_err_flag(e, s);
-  if (rc) return rc;
-  SampleArgs sa = make_sample_args(e, B, 1);
-  HIPCHK(e, vc_launch_sample(sa, false, s));
-  HIPCHK(e, hipEventRecord(e->ev[1], s));
-  rc = decode_loop(e, sa, B, 1, 0, sc, loop_steps, nullptr, s);
-  if (rc) return rc;
-  HIPCHK(e, hipEventRecord(e->ev[2], s));
-  rc = collect_states(e, B, s);
-  if (rc) return rc;
-  HIPCHK(e, hipEventElapsedTime(&e->ms[0], e->ev[0], e->ev[1]));
-  HIPCHK(e, hipEventElapsedTime(&e->ms[1], e->ev[1], e->ev[2]));
-  e->ms[2] = e->ms[0] + e->ms[1];
-  if (n_steps) {   // sampled steps of the longest request (feed steps not counted)
-    int m = 0;
-    for (int b = 0; b < B; ++b) m = std::max(m, e->h_st[b].total_steps);
-    *n_steps = m;
-  }
+  SampleArgs sa;
+  if ((rc = call_arm(e, B, 1, 1, true, sc, forced_dev, n_forced, logits_dev, logit_steps, s, &sa))) return rc;
+  if ((rc = decode_loop(e, sa, B, 1, 0, sc, loop_steps, s))) return rc;
+  if ((rc = call_end(e, B, false, n_steps, s))) return rc;
   for (int b = 0; b < B; ++b) {
     rc = edit_assemble(e, jobs[b], e->h_st[b], e->gen + (size_t)b * e->gen_cap * K, res_dev + (size_t)b * K * res_cap, res_cap,
                        &res_len[b], s, who[b].c_str());
