@@ -144,10 +144,16 @@ const char* vc_version(void);
  *                  puts a checkpoint there).  A matrix off the grid is refused and keeps its current launch (vc_debug_read "w8_stats",
  *                  layout of "w13_stats").  Where a matrix has both kinds of planes the w8 bit wins.  The option text ends in |w8=<mask>
  *                  on such an engine only.  Resident memory: + 0.5 x the requested images
+ *   "kv8"          0 / 1, ONLY on an engine that called vc_request_kv8 (default 1; VC_EINVAL on any other engine): decode passes read the
+ *                  cached K / V positions older than the pass as one OCP E4M3 byte per value times 2^shift, one shift byte per cached
+ *                  row of a head (csrc/vc_kv8.h; voicecraft_amd/quant.py kv8_quantize_rows states the grid), half the bytes of the bf16
+ *                  rows; the pass's own rows and every prefill pass stay on the bf16 cache.  One more launch per pass (kv8_pack_k)
+ *                  quantises the rows the pass wrote, whatever the option's value.  This CHANGES values: 3 mantissa bits are left of
+ *                  a cached value.  The option text ends in |kv8=<v> on such an engine only.  Resident memory: K/V x 1.5 + 2 / head_dim
  * What an option may change: nothing in the exact fp32 mode's greedy tokens (tests/test_gpu_options.py, test_gpu_one_row.py); in bf16
  * mode the forms that re-order sums or round at another place ("finished_rows", "fr_pair", "att_p16", "hq", "fr_one", "qkv_p8", "attn_fast",
  * "qkv16", "wide_heads", "wide_gemm") move head logits by bf16 rounding (tests allow 0.25 absolute), so top-k SAMPLED tokens can differ between option
- * states; the cache-policy / data-path / host-side options ("nt", "wd_stage", "graph_steps", "shrink", "w13", "w8") change no value.
+ * states; the cache-policy / data-path / host-side options ("nt", "wd_stage", "graph_steps", "shrink", "w13", "w8") change no value; "kv8" rounds cached K / V to its grid.
  * The non-temporal mask "nt" has no bit for the finished-row producers (rows_gemm_fr_k, rows_gemm_fr2_k, row_gemm_fr1_k) and the
  * wide-decode kernels: they always stream with the hint.  Captured decode graphs are kept per option state and step width, so an
  * in-process A/B (bench.py --ab) pays for capture once per state.  Unknown names / malformed values: VC_EINVAL.
@@ -170,6 +176,11 @@ int vc_finalize_weights(vc_engine* e, int compute_dtype);
  * other bit: VC_EINVAL) of every layer as E4M3 bytes for one-row steps, option "w8" above.  The form is bf16 only: vc_finalize_weights
  * with VC_DTYPE_F32 after a non-zero request returns VC_EINVAL.  An engine without the request packs nothing more and behaves as before. */
 int vc_request_w8(vc_engine* e, int mask);
+/* Before vc_finalize_weights (VC_ESTATE after it): keep, next to every layer's bf16 K / V cache, an E4M3 copy (one byte per value) and one
+ * shift byte per cached row of a head, written by one packer launch behind every pass, and let the decode attention read the positions
+ * older than the pass from it (option "kv8" above).  bf16 only: vc_finalize_weights with VC_DTYPE_F32 after the request returns
+ * VC_EINVAL.  An engine without the request allocates and launches nothing more and behaves as before. */
+int vc_request_kv8(vc_engine* e);
 
 /* ---- TTS: VoiceCraft.inference_tts (models/voicecraft.py:908-1153) and, with
  * n_samples > 1, VoiceCraft.inference_tts_batch (:1156-1439, best-of-N: the sample
@@ -477,6 +488,25 @@ typedef struct vc_debug_attn_args {
   int32_t dtype, H, hd, S_max, rows, nsplit, nt, fast, part16;
 } vc_debug_attn_args;
 int vc_debug_attn(const vc_debug_attn_args* a, void* stream);
+/* The same for option "kv8" (bf16 only; no engine needed).  base: as above; kcache8 / vcache8: uint8 [n_seqs][H][S_max][hd], one OCP
+ * E4M3 code byte per value, 16-byte aligned; kvshift8: int8 [n_seqs][H][S_max][2], the shift of the K row and of the V row.
+ *   pack = 1: ONE launch of the packer (kv8_pack_k): the rows (row_seq[r], row_pos[r]) of the bf16 caches are quantised into the three
+ *     arrays (pos < 0: none; *n_active == 0: nothing at all); every other byte stays.  q, share_len, the outputs, nsplit and the form
+ *     flags are not read.
+ *   pack = 0: ONE launch of rows_attn_k in its kv8 form.  The rows are `rps` consecutive rows per sequence at consecutive positions; row r
+ *     reads the positions below lo = row_pos[r - r % rps] from the E4M3 arrays (times 2^shift) and lo..row_pos[r] from the bf16 caches.
+ * VC_EINVAL, before the device is touched: what vc_debug_attn refuses, a dtype other than bf16, rps < 1, a null or misaligned array. */
+typedef struct vc_debug_attn8_args {
+  vc_debug_attn_args base;
+  void* kcache8;
+  void* vcache8;
+  void* kvshift8;
+  int32_t rps, pack;
+} vc_debug_attn8_args;
+int vc_debug_attn8(const vc_debug_attn8_args* a, void* stream);
+/* Host only: the kv8 quantiser (csrc/vc_kv8.h, the code the packer runs) on n_rows rows of hd bf16 values: codes uint8 [n_rows][hd],
+ * shift int8 [n_rows].  The CPU tests hold it against voicecraft_amd/quant.py kv8_quantize_rows. */
+int vc_kv8_quantize_host(const uint16_t* bf16_rows, int n_rows, int hd, uint8_t* codes, int8_t* shift);
 /* Diagnosis of the BOX, not of the model (no engine needed): ONE thread walks `hops` dependent loads over a ring of `bytes` bytes and
  * stamps the per-XCD shader clock and the chip-wide 100 MHz counter around the walk.  res[0] = ns per dependent load as a lone
  * workgroup on an otherwise idle chip sees it, res[1] = the shader clock (MHz) that workgroup really ran at.  The one-sequence

@@ -1,6 +1,9 @@
 """Kernel-by-kernel comparison of the gfx950 code of one translation unit at two commits: which kernels kept their code.
 
-usage: python tools/kernel_body_diff.py [--rev HEAD] [--unit vc_tokens] > profiles/<name>.log
+usage: python tools/kernel_body_diff.py [--rev HEAD] [--unit vc_tokens] [--rename 'REGEX=>TEXT'] > profiles/<name>.log
+--rename rewrites the PARENT's demangled kernel names first (re.sub), for a template that gained a defaulted parameter: with
+--rename '(rows_attn_k<[^>]*)>=>\\1, false>' the parent's rows_attn_k<bf16_t, true, true, true> is held against <..., true, false>;
+a 3-parameter name gets its defaulted 4th first (--rename may be given several times, applied in order).
 Compiles voicecraft_amd/csrc/<unit>.hip device-only (hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S) from the
 working tree and from `git show <rev>:` copies of csrc/ and include/ in a temporary directory, then compares each kernel's
 instruction lines (up to the kernel's .Lfunc_end label) after dropping comments, directives and the function index inside basic-block
@@ -47,11 +50,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rev", default="HEAD")
     ap.add_argument("--unit", default="vc_tokens")
+    ap.add_argument("--rename", action="append", default=[])
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         checkout(a.rev, os.path.join(tmp, "parent"))
         old = {isa.demangle(n): v for n, v in isa.kernels(compile_unit(os.path.join(tmp, "parent"), a.unit, os.path.join(tmp, "old.s"))).items()}
         new = {isa.demangle(n): v for n, v in isa.kernels(compile_unit(ROOT, a.unit, os.path.join(tmp, "new.s"))).items()}
+    for r in a.rename:
+        pat, rep = r.split("=>", 1)
+        old = {re.sub(pat, rep, n): v for n, v in old.items()}
     print(f"# gfx950 disassembly of voicecraft_amd/csrc/{a.unit}.hip (hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S),")
     print("# parent commit against this build, kernel by kernel: instruction lines after dropping comments and directives and the")
     print("# function index inside basic-block labels (.LBB<n>_)")
@@ -64,7 +71,8 @@ def main():
         if i0 == i1:
             print(f"{name[:72]:72s} {len(i1):5d} lines  IDENTICAL")
         else:
-            print(f"{name[:72]:72s} CHANGED: {len(i0)} -> {len(i1)} lines; {facts} (parent: scratch {old[name][1]}, "
+            n_diff = sum(x != y for x, y in zip(i0, i1)) + abs(len(i0) - len(i1))
+            print(f"{name[:72]:72s} CHANGED: {len(i0)} -> {len(i1)} lines, {n_diff} differ; {facts} (parent: scratch {old[name][1]}, "
                   f"next_free_vgpr {old[name][2]}, waiting stores {isa.store_chains(old[name][0])[0]})")
     for name in old:
         if name not in new:

@@ -41,6 +41,12 @@ class DebugAttnArgs(C.Structure):
         (n, C.c_int32) for n in ("dtype", "H", "hd", "S_max", "rows", "nsplit", "nt", "fast", "part16")]
 
 
+class DebugAttn8Args(C.Structure):
+    """vc_debug_attn8_args: vc_debug_attn_args, three device pointers, two int32 (152 bytes)."""
+    _fields_ = [("base", DebugAttnArgs), ("kcache8", C.c_void_p), ("vcache8", C.c_void_p), ("kvshift8", C.c_void_p),
+                ("rps", C.c_int32), ("pack", C.c_int32)]
+
+
 # name -> (restype, argtypes); the single source of truth the symbol test checks against the header
 PROTOTYPES = {
     "vc_create": (C.c_int, [C.POINTER(ModelCfg), C.c_int, C.POINTER(C.c_void_p)]),
@@ -51,6 +57,7 @@ PROTOTYPES = {
     "vc_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "vc_finalize_weights": (C.c_int, [C.c_void_p, C.c_int]),
     "vc_request_w8": (C.c_int, [C.c_void_p, C.c_int]),
+    "vc_request_kv8": (C.c_int, [C.c_void_p]),
     "vc_tts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(SampleCfg), C.c_int,
                          C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_int,
                          C.POINTER(C.c_int), C.c_void_p]),
@@ -91,6 +98,8 @@ PROTOTYPES = {
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int32), C.c_int64]),
     "vc_debug_sample": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SampleCfg), C.c_int, C.c_void_p, C.c_void_p]),
     "vc_debug_attn": (C.c_int, [C.POINTER(DebugAttnArgs), C.c_void_p]),
+    "vc_debug_attn8": (C.c_int, [C.POINTER(DebugAttn8Args), C.c_void_p]),
+    "vc_kv8_quantize_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vc_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int,
                           C.POINTER(C.c_int32), C.POINTER(SampleCfg), C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                           C.POINTER(C.c_int), C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]),

@@ -11,7 +11,9 @@
 // A cached row (hd elements) is spread over LPR = hd*sizeof/16 lanes with 16-byte loads, so a wave
 // reads 64/LPR consecutive positions = one contiguous 1 KiB burst per K (and V) instruction.
 #include <math.h>
+#include <type_traits>
 #include "vc_common.h"
+#include "vc_kv8.h"
 
 template <typename WT>
 __device__ __forceinline__ void unpack16(const uint4& u, float* f);
@@ -27,6 +29,20 @@ __device__ __forceinline__ void unpack16<bf16_t>(const uint4& u, float* f) {
   f[4] = __uint_as_float(u.z << 16); f[5] = __uint_as_float(u.z & 0xffff0000u);
   f[6] = __uint_as_float(u.w << 16); f[7] = __uint_as_float(u.w & 0xffff0000u);
 }
+
+// Sixteen E4M3 code bytes (vc_kv8.h) -> sixteen fp32 values q, the row's shift not applied: it scales the finished score / the weight.
+__device__ __forceinline__ void unpack_e4m3(const uint4& u, float* f) {
+  typedef float vc_f2 __attribute__((ext_vector_type(2)));
+  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const vc_f2 lo = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[i], 1.0f, false);
+    const vc_f2 hi = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[i], 1.0f, true);
+    f[4 * i] = lo.x; f[4 * i + 1] = lo.y; f[4 * i + 2] = hi.x; f[4 * i + 3] = hi.y;
+  }
+}
+// 2^s of a shift byte (int8 s in VC_W8_SHIFT_MIN .. VC_W8_SHIFT_MAX) as fp32: s + 127 is the exponent field.
+__device__ __forceinline__ float kv8_scale(uint32_t b) { return __uint_as_float(((b + 127u) & 0xffu) << 23); }
 
 #ifndef VC_ATT_WAVES
 #define VC_ATT_WAVES 8
@@ -46,10 +62,19 @@ __device__ __forceinline__ void unpack16<bf16_t>(const uint4& u, float* f) {
 // finished-row out-projection re-reads every head's partials in each of its 256 workgroups (rows x heads x splits x hd values: 131 KB
 // per workgroup at 8 rows, four times its weights), and those bytes go through the CU's vector-memory path like any others; the merged
 // row is rounded to bf16 for the MFMA anyway.  (max, sum) stay fp32.
-template <typename WT, bool NT, bool FAST, bool P16 = false>
-__global__ __launch_bounds__(64 * VC_ATT_WAVES) void rows_attn_k(const AttnArgs a) {
+// KV8 (option "kv8", bf16 decode passes of an engine created for it): positions below `lo` - the position of the sequence's first row in
+// this pass - are read from the E4M3 cache, one byte per value: a lane's 16-byte request holds 16 values, so a cached row is spread over
+// hd / 16 lanes and a wave instruction reads twice the positions in the same 1 KiB burst.  The K row's shift 2^s scales the finished
+// score, the V row's the probability weight (one 2-byte request per visit brings both).  Positions lo..pos (at most `rps` of them: this
+// pass's own rows, written by its QKV launch and packed only behind the pass) come from the bf16 cache: the last wave of the split that
+// holds them takes them as one more visit, requested together with the first batch.
+template <typename WT, bool NT, bool FAST, bool P16 = false, bool KV8 = false>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, 64 * VC_ATT_WAVES), amdgpu_waves_per_eu(KV8 ? 4 : 0)))      // KV8: two workgroups per CU
+void rows_attn_k(const AttnArgs a) {
   static_assert(!P16 || sizeof(WT) == 2, "bf16 partials: bf16 mode only");
-  constexpr int EPL = WTr<WT>::EPL;
+  static_assert(!KV8 || sizeof(WT) == 2, "the E4M3 cache stands next to a bf16 cache");
+  constexpr int EPL = KV8 ? 16 : WTr<WT>::EPL;
+  using CT = typename std::conditional<KV8, unsigned char, WT>::type;     // what the main loop's cache holds
   constexpr int NW = VC_ATT_WAVES;
   constexpr bool X2 = sizeof(WT) == 2;        // FAST: base-2 exponentials in bf16 mode
   auto ex = [](float x) -> float {
@@ -65,7 +90,15 @@ __global__ __launch_bounds__(64 * VC_ATT_WAVES) void rows_attn_k(const AttnArgs 
   // compiler cannot prove them invariant) and `share` was sunk behind the branch below - two dependent vector round trips before the
   // first K/V request (seen in the ISA, round 5).  All four are wave-uniform words that earlier launches of the step wrote (the
   // scalar cache is invalidated at every kernel start): one batch of s_load, one wait.
-  int active, pos, seq, share;
+  int active, pos, seq, share, lo = 0;
+  if constexpr (KV8) {      // ... and the position of the sequence's first row in this pass: row r - r % rps
+    const int* lo_at = a.row_pos + ((r * a.rps_magic) >> 16) * a.rps;
+    asm volatile("s_load_dword %0, %5, 0x0\n\ts_load_dword %1, %6, 0x0\n\ts_load_dword %2, %7, 0x0\n\ts_load_dword %3, %8, 0x0\n\ts_load_dword %4, %9, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(active), "=&s"(pos), "=&s"(seq), "=&s"(share), "=&s"(lo)
+                 : "s"(a.n_active), "s"(a.row_pos + r), "s"(a.row_seq + r), "s"(a.share_len), "s"(lo_at)
+                 : "memory");
+    lo = max(lo, 0);
+  } else
   asm volatile("s_load_dword %0, %4, 0x0\n\ts_load_dword %1, %5, 0x0\n\ts_load_dword %2, %6, 0x0\n\ts_load_dword %3, %7, 0x0\n\ts_waitcnt lgkmcnt(0)"
                : "=&s"(active), "=&s"(pos), "=&s"(seq), "=&s"(share)
                : "s"(a.n_active), "s"(a.row_pos + r), "s"(a.row_seq + r), "s"(a.share_len)
@@ -73,7 +106,7 @@ __global__ __launch_bounds__(64 * VC_ATT_WAVES) void rows_attn_k(const AttnArgs 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int hd = a.hd;
-  constexpr int EPL_SH = EPL == 8 ? 3 : 2;
+  constexpr int EPL_SH = EPL == 16 ? 4 : EPL == 8 ? 3 : 2;
   const int lpr_sh = a.hd_shift - EPL_SH;   // (head_dim is a power of two: shifts, not the divisions the compiler would expand)
   const int LPR = 1 << lpr_sh;         // lanes per cached row: 4 (bf16, head_dim 32), 8, 16 or 32
   const int PPW = 64 >> lpr_sh;        // positions per wave per step
@@ -94,7 +127,11 @@ __global__ __launch_bounds__(64 * VC_ATT_WAVES) void rows_attn_k(const AttnArgs 
     int chunk = (int)((float)(S + a.nsplit - 1) * a.inv_nsplit);
     if (chunk * a.nsplit < S) ++chunk;
     const int p0 = sp * chunk;
-    const int p1 = min(S, p0 + chunk);
+    const int p1 = KV8 ? min(min(S, p0 + chunk), lo) : min(S, p0 + chunk);      // KV8: the main loop ends in front of the pass's own rows,
+    const int t0 = max(p0, lo), t1 = min(S, p0 + chunk);                        // ... which are positions [t0, t1) of this split
+    const bool tail = KV8 && wave == NW - 1 && t0 < t1;
+    const void* const kc_main = KV8 ? (const void*)a.kcache8 : a.kcache;
+    const void* const vc_main = KV8 ? (const void*)a.vcache8 : a.vcache;
     const int step = 4 * NW * PPW;
     // q, then K and V of the first 4 visits per wave, are requested together (clamped,
     // unconditional); q is only touched once all of them are on their way.
@@ -105,14 +142,16 @@ __global__ __launch_bounds__(64 * VC_ATT_WAVES) void rows_attn_k(const AttnArgs 
       for (int j = 0; j < EPL / 4; ++j) qv[j] = qp[j];
     }
     uint4 ku[4], vu[4];
+    uint32_t su[4];        // KV8: the visit's shift bytes (K, V)
+    uint4 tk[2], tv[2];    // KV8: the bf16 halves of the tail visit's K and V rows
     int pp[4];
     // (the general form - refills of long chunks, calls with a shared text prefix - computes its per-lane 64-bit bases where it is
     // used: hoisted in front of the first batch they would sit in front of the lean path too)
 #define VC_KV_LOADS(pb_)                                                     \
     const long own = (long)seq * a.cache_seq_stride;      /* positions below `share` live in sequence 0's cache */ \
     const long base = own + (long)h * a.S_max * hd + li * EPL;               \
-    const WT* kb = reinterpret_cast<const WT*>(a.kcache) + base;             \
-    const WT* vb = reinterpret_cast<const WT*>(a.vcache) + base;             \
+    const CT* kb = reinterpret_cast<const CT*>(kc_main) + base;              \
+    const CT* vb = reinterpret_cast<const CT*>(vc_main) + base;              \
     _Pragma("unroll") for (int it = 0; it < 4; ++it) {                       \
       pp[it] = (pb_) + (it * NW + wave) * PPW + sub;                         \
       const long pc = max(min(pp[it], p1 - 1), 0);                           \
@@ -124,20 +163,34 @@ __global__ __launch_bounds__(64 * VC_ATT_WAVES) void rows_attn_k(const AttnArgs 
         ku[it] = *reinterpret_cast<const uint4*>(kb + po);                   \
         vu[it] = *reinterpret_cast<const uint4*>(vb + po);                   \
       }                                                                      \
+      if constexpr (KV8)                                                     \
+        su[it] = *reinterpret_cast<const unsigned short*>(a.kvshift8 + 2 * ((((pc < share) ? 0 : own) >> a.hd_shift) + (long)h * a.S_max + pc)); \
+    }
+    // KV8: positions tb_ + sub of the pass's own rows, bf16: a lane's 16 values are two 16-byte requests
+#define VC_KV_TAIL_LOADS(tb_)                                                \
+    {                                                                        \
+      const long pc = max(min((tb_) + sub, t1 - 1), 0);                      \
+      const long at = ((pc < share) ? 0 : (long)seq * a.cache_seq_stride) + (long)h * a.S_max * hd + pc * hd + li * EPL; \
+      const uint4* kt = reinterpret_cast<const uint4*>(reinterpret_cast<const WT*>(a.kcache) + at); \
+      const uint4* vt = reinterpret_cast<const uint4*>(reinterpret_cast<const WT*>(a.vcache) + at); \
+      tk[0] = kt[0]; tk[1] = kt[1]; tv[0] = vt[0]; tv[1] = vt[1];            \
     }
     // The FIRST batch - the one every launch waits for - from a wave-uniform base and one 32-bit offset per lane when no prefix is
     // shared (every call but the sentence-chained ones): scalar-base addressing, no 64-bit vector arithmetic, no select per visit.
     // (In-kernel stamps of the first round-5 build: 2 956 clk from "position known" to "loads issued" - the address code in front of
     // the requests is paid in instruction fetch at the cold start of the launch, profiles/r05f_kernel_stamps_giga830M.log.)
     if (__builtin_expect(share == 0, 1)) {       // (against the general form, in-process: -0.19 % +- 0.06 per step at giga830M, -0.38 % at giga330M, -0.40 % at 8 rows; profiles/r05g_ab_*.log)
-      const char* kbu = reinterpret_cast<const char*>(reinterpret_cast<const WT*>(a.kcache) + (long)seq * a.cache_seq_stride + (long)h * a.S_max * hd);
-      const char* vbu = reinterpret_cast<const char*>(reinterpret_cast<const WT*>(a.vcache) + (long)seq * a.cache_seq_stride + (long)h * a.S_max * hd);
-      const unsigned lo = (unsigned)(li * EPL) * (unsigned)sizeof(WT);
+      const char* kbu = reinterpret_cast<const char*>(reinterpret_cast<const CT*>(kc_main) + (long)seq * a.cache_seq_stride + (long)h * a.S_max * hd);
+      const char* vbu = reinterpret_cast<const char*>(reinterpret_cast<const CT*>(vc_main) + (long)seq * a.cache_seq_stride + (long)h * a.S_max * hd);
+      const char* sbu = nullptr;
+      if constexpr (KV8) sbu = reinterpret_cast<const char*>(a.kvshift8) + 2 * (((long)seq * a.cache_seq_stride >> a.hd_shift) + (long)h * a.S_max);
+      const unsigned lane_b = (unsigned)(li * EPL) * (unsigned)sizeof(CT);
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         pp[it] = p0 + (it * NW + wave) * PPW + sub;
         const unsigned pc = (unsigned)max(min(pp[it], p1 - 1), 0);
-        const unsigned off = ((pc << a.hd_shift) * (unsigned)sizeof(WT)) + lo;
+        const unsigned off = ((pc << a.hd_shift) * (unsigned)sizeof(CT)) + lane_b;
+        if constexpr (KV8) su[it] = *reinterpret_cast<const unsigned short*>(sbu + 2 * pc);
         if constexpr (NT) {
           ku[it] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kbu + off)));
           vu[it] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vbu + off)));
@@ -149,6 +202,7 @@ __global__ __launch_bounds__(64 * VC_ATT_WAVES) void rows_attn_k(const AttnArgs 
     } else {
       VC_KV_LOADS(p0)
     }
+    if constexpr (KV8) { if (tail) VC_KV_TAIL_LOADS(t0) }
     __builtin_amdgcn_sched_barrier(0);
     VC_KTS(2);
     float q[EPL];
@@ -159,6 +213,103 @@ __global__ __launch_bounds__(64 * VC_ATT_WAVES) void rows_attn_k(const AttnArgs 
       q[4 * j + 2] = qv[j].z * qs; q[4 * j + 3] = qv[j].w * qs;
     }
     VC_KTS(3);
+    if constexpr (KV8) {
+      auto grp_sum = [&](float t) -> float {      // over the LPR = 2, 4 or 8 lanes of a cached row
+        t += dpp_f<VC_DPP_QP_1032>(t);
+        if (LPR >= 4) t += dpp_f<VC_DPP_QP_2301>(t);
+        if (LPR >= 8) t += dpp_f<VC_DPP_ROW_HALF_MIRROR>(t);
+        return t;
+      };
+      // the pass's own rows, bf16, FIRST (their registers are free again before the main loop's arithmetic; the order of positions does not
+      // matter to an online softmax): one position per lane group and visit (a visit holds PPW >= 8 positions, a pass has at most rps)
+      if (tail) for (int tb = t0;;) {
+        float kf[EPL], vf[EPL];
+        unpack16<WT>(tk[0], kf); unpack16<WT>(tk[1], kf + 8);
+        unpack16<WT>(tv[0], vf); unpack16<WT>(tv[1], vf + 8);
+        float t = 0.f;
+#pragma unroll
+        for (int j = 0; j < EPL; ++j) t += q[j] * kf[j];
+        t = grp_sum(t);
+        const bool live = tb + sub < t1;
+        if constexpr (FAST) {
+          const float mn = fmaxf(m, wave_max(live ? t : -INFINITY));
+          const float corr = ex(m - mn);
+          const float pw = live ? ex(t - mn) : 0.f;
+          l = l * corr + pw;
+#pragma unroll
+          for (int j = 0; j < EPL; ++j) o[j] = o[j] * corr + pw * vf[j];
+          m = mn;
+        } else if (live) {
+          const float mn = fmaxf(m, t);
+          const float corr = expf(m - mn);
+          const float pe = expf(t - mn);
+          l = l * corr + pe;
+#pragma unroll
+          for (int j = 0; j < EPL; ++j) o[j] = o[j] * corr + pe * vf[j];
+          m = mn;
+        }
+        tb += PPW;
+        if (tb >= t1) break;
+        VC_KV_TAIL_LOADS(tb)
+      }
+      // (a split that lies behind `lo` has no E4M3 position: what its clamped requests brought never enters the arithmetic)
+      if (p0 < p1) for (int pb = p0;;) {
+        float sc[4], vs[4];
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+          float kf[EPL];
+          unpack_e4m3(ku[it], kf);
+          float t = 0.f;
+#pragma unroll
+          for (int j = 0; j < EPL; ++j) t += q[j] * kf[j];
+          t = grp_sum(t) * kv8_scale(su[it] & 0xffu);          // the K row's shift scales the finished score
+          vs[it] = kv8_scale(su[it] >> 8);
+          sc[it] = (pp[it] < p1) ? t : -INFINITY;
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (FAST) {
+          const float mn = fmaxf(m, wave_max(fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3]))));    // wave-uniform
+          if (mn > -INFINITY) {
+            const float corr = ex(m - mn);
+            float pw[4];
+#pragma unroll
+            for (int it = 0; it < 4; ++it) pw[it] = ex(sc[it] - mn);
+            l = l * corr + ((pw[0] + pw[1]) + (pw[2] + pw[3]));
+#pragma unroll
+            for (int j = 0; j < EPL; ++j) o[j] *= corr;
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+              float vf[EPL];
+              unpack_e4m3(vu[it], vf);
+              const float w = pw[it] * vs[it];                 // ... the V row's the probability weight
+#pragma unroll
+              for (int j = 0; j < EPL; ++j) o[j] += w * vf[j];
+              __builtin_amdgcn_sched_barrier(0);               // one visit's 16 values at a time: hoisted conversions cost 80 VGPRs (two waves per SIMD)
+            }
+            m = mn;
+          }
+        } else {
+#pragma unroll
+          for (int it = 0; it < 4; ++it) {
+            if (pp[it] < p1) {
+              float vf[EPL];
+              unpack_e4m3(vu[it], vf);
+              const float mn = fmaxf(m, sc[it]);
+              const float corr = expf(m - mn);
+              const float pe = expf(sc[it] - mn);
+              l = l * corr + pe;
+              const float w = pe * vs[it];
+#pragma unroll
+              for (int j = 0; j < EPL; ++j) o[j] = o[j] * corr + w * vf[j];
+              m = mn;
+            }
+          }
+        }
+        pb += step;
+        if (pb >= p1) break;
+        { VC_KV_LOADS(pb) }
+      }
+    } else
     for (int pb = p0;;) {
       if constexpr (FAST) {
         float sc[4];
@@ -217,6 +368,7 @@ __global__ __launch_bounds__(64 * VC_ATT_WAVES) void rows_attn_k(const AttnArgs 
       { VC_KV_LOADS(pb) }
     }
 #undef VC_KV_LOADS
+#undef VC_KV_TAIL_LOADS
     VC_KTS(4);
   }
   // merge the PPW position groups of this wave (same li, different sub)
@@ -279,6 +431,19 @@ hipError_t vc_launch_attn(const AttnArgs& a, int dtype, int rows_cap, hipStream_
   ++vc_launch_counts[VC_LC_ROWS_ATTN];
   AttnArgs b = a;
   b.inv_nsplit = nextafterf(1.0f / (float)a.nsplit, 2.0f);
+  if (a.kcache8) {      // option "kv8": the same forms on the E4M3 cache
+    if (dtype != VC_DTYPE_BF16 || !a.vcache8 || !a.kvshift8 || a.rps < 1 || (long)rows_cap * a.rps >= 65536) return hipErrorInvalidValue;
+    b.rps_magic = (65536 + a.rps - 1) / a.rps;
+    ++vc_launch_counts[VC_LC_KV8_ATTN];
+    const dim3 blk(64 * VC_ATT_WAVES);
+#define VC_ATTN8_GO(NT_, F_)                                                                          \
+    if (a.part16 && !a.x_out) hipLaunchKernelGGL((rows_attn_k<bf16_t, NT_, F_, true, true>), grid, blk, 0, s, b); \
+    else hipLaunchKernelGGL((rows_attn_k<bf16_t, NT_, F_, false, true>), grid, blk, 0, s, b);
+    if (a.fast) { if (a.nt) { VC_ATTN8_GO(true, true) } else { VC_ATTN8_GO(false, true) } }
+    else { if (a.nt) { VC_ATTN8_GO(true, false) } else { VC_ATTN8_GO(false, false) } }
+#undef VC_ATTN8_GO
+    return hipGetLastError();
+  }
 #define VC_ATTN_GO(WT_, NT_, F_) hipLaunchKernelGGL((rows_attn_k<WT_, NT_, F_>), grid, dim3(64 * VC_ATT_WAVES), 0, s, b);
   if (dtype == VC_DTYPE_BF16 && a.part16 && !a.x_out) {      // bf16 partials (finished-row passes of 2..8 rows whose attention is split)
     if (a.fast) { if (a.nt) hipLaunchKernelGGL((rows_attn_k<bf16_t, true, true, true>), grid, dim3(64 * VC_ATT_WAVES), 0, s, b);
@@ -321,6 +486,89 @@ extern "C" int vc_debug_attn(const vc_debug_attn_args* p, void* stream) {
   a.att_o = reinterpret_cast<float*>(p->att_o); a.att_ml = p->att_ml; a.x_out = p->x_out;
   a.nt = p->nt ? 1 : 0; a.fast = p->fast ? 1 : 0; a.part16 = p->part16 ? 1 : 0;
   return vc_launch_attn(a, p->dtype, p->rows, (hipStream_t)stream) == hipSuccess ? VC_OK : VC_EHIP;
+}
+
+// ---------------------------------------------------------------- option "kv8": the packer
+// One launch behind every pass of an engine created for the option: the rows the pass wrote (row_seq / row_pos), every layer, K and V,
+// every head.  A lane takes 8 bf16 values (one 16-byte request), the hd / 8 lanes of a head's row agree on its largest magnitude and
+// so on its shift (vc_kv8.h), each stores its 8 code bytes and the first of them the shift byte.  grid = (lanes / 256, 2 L).
+__global__ __launch_bounds__(256) void kv8_pack_k(const Kv8PackArgs a) {
+  if (*a.n_active == 0) return;
+  const int l = blockIdx.y >> 1, kv = blockIdx.y & 1;
+  const Kv8Layer ly = a.layers ? a.layers[l] : a.one;
+  const int lpr_sh = a.hd_shift - 3, LPR = 1 << lpr_sh;      // lanes per cached row: 4, 8 or 16 (groups never straddle a wave)
+  const int lanes_row = a.H << lpr_sh;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const int row = idx / lanes_row, c = idx - row * lanes_row;
+  const int h = c >> lpr_sh, li = c & (LPR - 1);
+  int seq = -1, pos = -1;
+  if (row < a.n_rows) { seq = a.row_seq[row]; pos = a.row_pos[row]; }
+  const bool live = seq >= 0 && pos >= 0 && pos < a.S_max;
+  const long at = live ? ((long)seq * a.H + h) * a.S_max + pos : 0;      // the cached row
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+  if (live) {
+    const uint4 u = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(kv ? ly.vc : ly.kc) + at * a.hd + li * 8);
+    w[0] = u.x; w[1] = u.y; w[2] = u.z; w[3] = u.w;
+  }
+  uint32_t amax = vc_kv8_amax8(w);
+  for (int off = 1; off < LPR; off <<= 1) amax = max(amax, (uint32_t)__shfl_xor((int)amax, off, 64));
+  const int sft = vc_kv8_shift(amax);
+  uint32_t d[2];
+  vc_kv8_encode8(w, sft, d);
+  if (live) {
+    *reinterpret_cast<uint2*>((kv ? ly.v8 : ly.k8) + at * a.hd + li * 8) = uint2{d[0], d[1]};
+    if (li == 0) ly.sh[at * 2 + kv] = (signed char)sft;
+  }
+}
+hipError_t vc_launch_kv8_pack(const Kv8PackArgs& a, hipStream_t s) {
+  if (a.n_rows < 1 || a.L < 1 || a.H < 1 || (a.hd != 32 && a.hd != 64 && a.hd != 128) || !a.n_active) return hipErrorInvalidValue;
+  ++vc_launch_counts[VC_LC_KV8_PACK];
+  const long lanes = (long)a.n_rows * a.H * (a.hd / 8);
+  hipLaunchKernelGGL(kv8_pack_k, dim3((unsigned)((lanes + 255) / 256), 2 * a.L), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// Test hooks of the option (include/vc_engine.h): the packer (pack = 1) or one rows_attn_k launch on the E4M3 cache, through the
+// launchers above; and the header's encode on the CPU.
+extern "C" int vc_debug_attn8(const vc_debug_attn8_args* p8, void* stream) {
+  if (!p8) return VC_EINVAL;
+  const vc_debug_attn_args* p = &p8->base;
+  if (p->dtype != VC_DTYPE_BF16 || p8->rps < 1) return VC_EINVAL;
+  if (p->hd != 32 && p->hd != 64 && p->hd != 128) return VC_EINVAL;
+  if (p->H < 1 || p->S_max < 1 || p->rows < 1 || (long)p->rows * p8->rps >= 65536) return VC_EINVAL;
+  if (!p->kcache || !p->vcache || !p8->kcache8 || !p8->vcache8 || !p8->kvshift8 || !p->row_seq || !p->row_pos || !p->n_active) return VC_EINVAL;
+  if (((uintptr_t)p->kcache | (uintptr_t)p->vcache | (uintptr_t)p8->kcache8 | (uintptr_t)p8->vcache8) & 15) return VC_EINVAL;
+  if ((uintptr_t)p8->kvshift8 & 1) return VC_EINVAL;
+  const int hd_shift = p->hd == 32 ? 5 : p->hd == 64 ? 6 : 7;
+  if (p8->pack) {
+    Kv8PackArgs k = {};
+    k.one = Kv8Layer{p->kcache, p->vcache, (unsigned char*)p8->kcache8, (unsigned char*)p8->vcache8, (signed char*)p8->kvshift8};
+    k.L = 1; k.H = p->H; k.hd = p->hd; k.hd_shift = hd_shift; k.S_max = p->S_max;
+    k.row_seq = p->row_seq; k.row_pos = p->row_pos; k.n_rows = p->rows; k.n_active = p->n_active;
+    return vc_launch_kv8_pack(k, (hipStream_t)stream) == hipSuccess ? VC_OK : VC_EHIP;
+  }
+  if (p->nsplit < 1 || p->nsplit > VC_MAX_NSPLIT) return VC_EINVAL;
+  if (!p->q || !p->share_len || ((uintptr_t)p->q & 15)) return VC_EINVAL;
+  if (p->x_out) {
+    if (p->nsplit != 1 || p->part16) return VC_EINVAL;
+  } else if (!p->att_o || !p->att_ml) return VC_EINVAL;
+  AttnArgs a = {};
+  a.q = p->q; a.kcache = p->kcache; a.vcache = p->vcache;
+  a.kcache8 = (const unsigned char*)p8->kcache8; a.vcache8 = (const unsigned char*)p8->vcache8; a.kvshift8 = (const signed char*)p8->kvshift8;
+  a.rps = p8->rps;
+  a.cache_seq_stride = (long)p->H * p->S_max * p->hd;
+  a.S_max = p->S_max; a.H = p->H; a.hd = p->hd; a.hd_shift = hd_shift; a.d = p->H * p->hd; a.nsplit = p->nsplit;
+  a.scale = 1.0f / sqrtf((float)p->hd);
+  a.row_seq = p->row_seq; a.row_pos = p->row_pos; a.n_rows = p->rows;
+  a.n_active = p->n_active; a.share_len = p->share_len;
+  a.att_o = reinterpret_cast<float*>(p->att_o); a.att_ml = p->att_ml; a.x_out = p->x_out;
+  a.nt = p->nt ? 1 : 0; a.fast = p->fast ? 1 : 0; a.part16 = p->part16 ? 1 : 0;
+  return vc_launch_attn(a, VC_DTYPE_BF16, p->rows, (hipStream_t)stream) == hipSuccess ? VC_OK : VC_EHIP;
+}
+extern "C" int vc_kv8_quantize_host(const uint16_t* bf16_rows, int n_rows, int hd, uint8_t* codes, int8_t* shift) {
+  if (!bf16_rows || !codes || !shift || n_rows < 0 || hd < 1) return VC_EINVAL;
+  for (long r = 0; r < n_rows; ++r) shift[r] = (int8_t)vc_kv8_quantize_row(bf16_rows + r * hd, hd, codes + r * hd);
+  return VC_OK;
 }
 
 // ---------------------------------------------------------------- KV replication (best-of-N)

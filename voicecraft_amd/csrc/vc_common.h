@@ -292,6 +292,27 @@ struct AttnArgs {
   int nt;                   // rows_attn_k: K/V rows requested with the non-temporal hint
   int fast;                 // rows_attn_k: 1 = the round-5 form (wave maximum before any exponential; bf16 mode: hardware exp2)
   int part16;               // rows_attn_k (bf16 mode, split passes): 1 = the partial acc[hd] is written as bf16 (read by rows_gemm_fr_k<.., P16>)
+  // rows_attn_k, option "kv8" (bf16 decode passes of an engine that asked for it; kcache8 null: the plain form).  A row reads the
+  // positions below `lo` = the position of its sequence's FIRST row in this pass (rows r - r % rps .. of `rps` consecutive positions) as
+  // E4M3 bytes times 2^shift, and lo..pos - written by this pass's QKV launch, not packed yet - from the bf16 cache.
+  const unsigned char* kcache8;   // [seq][H][S_max][hd], one code byte per value (vc_kv8.h)
+  const unsigned char* vcache8;
+  const signed char* kvshift8;    // [seq][H][S_max][2]: the shift of the K row, of the V row
+  int rps;                        // rows per sequence of the pass (>= 1)
+  int rps_magic;                  // ceil(2^16 / rps): r / rps = (r * rps_magic) >> 16 for r * (rps - 1) < 2^16 (set by the launcher)
+};
+
+// kv8_pack_k: the rows a pass wrote (row_seq / row_pos; pos < 0: none), every layer, K and V, every head, in one launch: reads the bf16
+// caches, writes the E4M3 caches and the shifts.  Nothing when *n_active == 0.
+struct Kv8Layer { const void *kc, *vc; unsigned char *k8, *v8; signed char* sh; };
+struct Kv8PackArgs {
+  const Kv8Layer* layers;   // device table [L], or null: the one layer in `one`
+  Kv8Layer one;
+  int L, H, hd, hd_shift, S_max;
+  const int* row_seq;
+  const int* row_pos;
+  int n_rows;
+  const int* n_active;      // never null
 };
 
 struct Segment {            // one run of columns of the rearranged audio sequence
@@ -447,10 +468,11 @@ extern int vc_blk_dbg_mask;   // vc_gemm.hip: diagnostic mask of the prefill blo
 // vc_debug_read("launch_counts") by the parity tests, which assert that the form a benchmarked shape runs on is the one
 // they compared with the oracle.
 enum { VC_LC_ROWS_GEMM = 0, VC_LC_MT2 = 1, VC_LC_MT4 = 2, VC_LC_BLK64 = 3, VC_LC_BLK128_SBS = 4, VC_LC_BLK128_2X2 = 5,
-       VC_LC_BLK64_OCC2 = 6, VC_LC_LN_ROWS = 7, VC_LC_ROWS_ATTN = 8, VC_LC_TILE_ATTN = 9, VC_LC_ROWS_GEMM_FR = 10, VC_LC_BIG256 = 11, VC_LC_BIG128 = 12, VC_LC_ROW_GEMM_FR1 = 13, VC_LC_TILE_ATTN64 = 14, VC_LC_ROWS_GEMM_FRP = 15, VC_LC_WD = 16, VC_LC_ROWS_GEMM_QP = 17, VC_LC_W13 = 18, VC_LC_W8 = 19, VC_LC_N = 20 };   // VC_LC_W13 / VC_LC_W8: launches on 13-bit planes / on E4M3 bytes (also counted in their form's slot)
+       VC_LC_BLK64_OCC2 = 6, VC_LC_LN_ROWS = 7, VC_LC_ROWS_ATTN = 8, VC_LC_TILE_ATTN = 9, VC_LC_ROWS_GEMM_FR = 10, VC_LC_BIG256 = 11, VC_LC_BIG128 = 12, VC_LC_ROW_GEMM_FR1 = 13, VC_LC_TILE_ATTN64 = 14, VC_LC_ROWS_GEMM_FRP = 15, VC_LC_WD = 16, VC_LC_ROWS_GEMM_QP = 17, VC_LC_W13 = 18, VC_LC_W8 = 19, VC_LC_KV8_ATTN = 20, VC_LC_KV8_PACK = 21, VC_LC_N = 22 };   // VC_LC_W13 / VC_LC_W8: launches on 13-bit planes / on E4M3 bytes (also counted in their form's slot); VC_LC_KV8_ATTN: rows_attn_k launches on the E4M3 K/V cache (also in VC_LC_ROWS_ATTN), VC_LC_KV8_PACK: kv8_pack_k
 extern long long vc_launch_counts[VC_LC_N];
 hipError_t vc_launch_ln_rows(const GemmArgs& a, int dtype, hipStream_t s);
 hipError_t vc_launch_attn(const AttnArgs& a, int dtype, int rows_cap, hipStream_t s);
+hipError_t vc_launch_kv8_pack(const Kv8PackArgs& a, hipStream_t s);
 hipError_t vc_launch_tile_attn(const AttnArgs& a, int dtype, hipStream_t s);
 hipError_t vc_launch_tile_attn64(const AttnArgs& a, hipStream_t s);   // bf16, head_dim 128, prompts on 64-row boundaries
 hipError_t vc_launch_prompt(const PromptArgs& a, hipStream_t s);

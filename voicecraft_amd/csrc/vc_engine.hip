@@ -40,6 +40,9 @@ struct Layer {
   float bo_mean = 0.f, b2_mean = 0.f;   // mean over the d channels of bo / b2: what the update moves a row's mean by whatever its input (GemmArgs.mu_shift)
   float *wg_qkv = nullptr, *wg_1 = nullptr;                             // row sums of the folded weights W . gamma
   void *kc = nullptr, *vc = nullptr;   // KV cache of this layer: WT [max_seqs][H][S_max][hd]
+  // on request (vc_request_kv8): the same rows as E4M3 bytes, uint8 [max_seqs][H][S_max][hd], and their shifts, int8 [max_seqs][H][S_max][2] (K, V)
+  unsigned char *kc8 = nullptr, *vc8 = nullptr;
+  signed char* sh8 = nullptr;
   // W28 / Wqkv8 once more in the packed forms of vc_packed (vc_common.h): [VC_PK_W13] exact 13-bit planes (option "w13", vc_w13.h) and, on request
   // (vc_request_w8), [VC_PK_W8] E4M3 bytes with one shift byte per fragment (option "w8", vc_w8.h); second index W13_F2 / W13_QKV
   struct Packed {
@@ -193,6 +196,14 @@ struct vc_engine {
   // kinds of planes the w8 bit wins.  An engine without the request packs nothing and has no such option.
   int w8_req = 0;
   int w8 = 0;
+  // option "kv8": decode passes read the cached positions older than the pass from an E4M3 copy of the K / V cache (Layer.kc8 / vc8 / sh8,
+  // vc_kv8.h: one byte per value, one shift per cached row of a head - half the bytes of the launch that grows with the batch), which
+  // one kv8_pack_k launch behind every pass keeps equal to the quantiser of the bf16 rows.  This changes values (3 mantissa bits), so:
+  // only on an engine that asked for it before vc_finalize_weights (vc_request_kv8: kv8_req); 0 = such an engine reads bf16 again (it
+  // goes on packing).  An engine without the request allocates nothing, launches nothing more and has no such option.
+  int kv8_req = 0;
+  int kv8 = 0;
+  Kv8Layer* kv8_tab = nullptr;          // device table [L] of the layers' five arrays (Kv8PackArgs.layers)
   int cur_rows = 0;                     // rows per step the last decode loop ended on (tts_run reads the states back accordingly)
   // option "attn_fast": decode attention with the wave's maximum taken before any exponential (no online rescaling inside a wave) and,
   // in bf16 mode, hardware exp2 (v_exp_f32) instead of expf
@@ -394,6 +405,7 @@ struct RowSrc {
   int n_rows;       // rows carried
   const int* n_active;
   int nt;           // force the streaming-load policy (microbenchmarks)
+  int rps;          // decode passes: rows per sequence (1 or 3: consecutive rows at consecutive positions); 0: a prefill pass (option "kv8")
 };
 
 GemmArgs base_args(vc_engine* e, const RowSrc& rs, const Plan& p, int N, int Kdim) {
@@ -636,6 +648,9 @@ int site_attn(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly
   a.nt = (rs.n_active != nullptr || rs.nt) ? attn_nt_for(e, rs.n_rows) : 0;   // decode passes stream their K/V once, prefill passes re-read it
   a.fast = e->attn_fast;
   a.part16 = p.part16 ? 1 : 0;
+  if (e->kv8 && rs.rps > 0 && p.attn == ATT_ROWS) {      // decode passes of a kv8 engine: positions older than the pass from the E4M3 cache
+    a.kcache8 = ly.kc8; a.vcache8 = ly.vc8; a.kvshift8 = ly.sh8; a.rps = rs.rps;
+  }
   if (p.att_x) a.x_out = e->xn;        // xn is free between the QKV GEMM and the FFN LayerNorm
   if (p.attn == ATT_TILE64) HIPCHK(e, vc_launch_tile_attn64(a, s));
   else if (p.attn == ATT_TILE) HIPCHK(e, vc_launch_tile_attn(a, e->dtype, s));
@@ -738,6 +753,13 @@ int run_pass(vc_engine* e, const PassPlan& p, const RowSrc& rs, PassOut* out, hi
   }
   const bool finished = p.form == FORM_FR || p.fd;
   *out = {finished ? 0 : p.ks_f2, p.hq ? e->hqB : nullptr, e->row_mu[0]};
+  if (e->kv8_req) {      // option "kv8": the rows this pass wrote, every layer, K and V, as E4M3 bytes too - prefill and decode passes alike
+    Kv8PackArgs k;
+    memset(&k, 0, sizeof k);
+    k.layers = e->kv8_tab; k.L = e->L; k.H = e->H; k.hd = e->hd; k.hd_shift = e->hd == 32 ? 5 : e->hd == 64 ? 6 : 7; k.S_max = e->S_max;
+    k.row_seq = rs.row_seq; k.row_pos = rs.row_pos; k.n_rows = rs.n_rows; k.n_active = rs.n_active ? rs.n_active : e->one;
+    HIPCHK(e, vc_launch_kv8_pack(k, s));
+  }
   return VC_OK;
 }
 
@@ -928,7 +950,7 @@ int push_sample_dyn(vc_engine* e, const vc_sample_cfg* sc, const int64_t* forced
 int decode_step(vc_engine* e, const SampleArgs& sa, int B, int rps, bool grouped, hipStream_t s, bool sess = false) {
   RowSrc rs{};
   rs.h_in = e->dec_h; rs.row_seq = e->dec_row_seq; rs.row_pos = e->dec_row_pos;
-  rs.n_rows = B * rps; rs.n_active = e->n_active;
+  rs.n_rows = B * rps; rs.n_active = e->n_active; rs.rps = rps;
   const PassPlan p = plan_pass(e, rs.n_rows, true, 0);
   PassOut po;
   int rc = run_pass(e, p, rs, &po, s);
@@ -1172,6 +1194,9 @@ int need_mask(vc_engine* e, const char* name, int v0) {
 int need_w8(vc_engine* e, const char* name, int v0) {
   return e->w8_req ? need_mask(e, name, v0) : fail(e, VC_EINVAL, "option 'w8': this engine was created without vc_request_w8");
 }
+int need_kv8(vc_engine* e, const char*, int) {
+  return e->kv8_req ? VC_OK : fail(e, VC_EINVAL, "option 'kv8': this engine was created without vc_request_kv8");
+}
 
 int nonzero(int v) { return v ? 1 : 0; }
 int two_or_one(int v) { return v == 2 ? 2 : 1; }
@@ -1212,6 +1237,7 @@ const OptDesc OPTIONS[] = {
     {"shrink", "VC_SHRINK", "sh", {&E::shrink, 0, 1}, nonzero},
     {"w13", "VC_W13", "w13", {&E::w13, 0, 5}, nullptr, {}, need_mask},
     {"w8", nullptr, "w8", {&E::w8, 0, 5}, nullptr, {}, need_w8, &E::w8_req},      // only an engine that requested the form has the option
+    {"kv8", nullptr, "kv8", {&E::kv8, 0, 1}, nonzero, {}, need_kv8, &E::kv8_req},   // likewise
     {"prefill_rows", "VC_PREFILL_ROWS", nullptr, {&E::prefill_rows_per_pass, VC_ROWS, VC_MAX_ROWS}, whole_tiles},   // 16: decode kernels only
 };
 
@@ -1397,11 +1423,22 @@ extern "C" int vc_request_w8(vc_engine* e, int mask) {
   return VC_OK;
 }
 
+// Asks vc_finalize_weights for the E4M3 copy of the K / V cache (option "kv8").  As for vc_request_w8, an fp32 engine meets the request
+// at vc_finalize_weights: VC_EINVAL from there.
+extern "C" int vc_request_kv8(vc_engine* e) {
+  if (!e) return VC_EINVAL;
+  if (e->finalized) return fail(e, VC_ESTATE, "vc_request_kv8 comes before vc_finalize_weights");
+  e->kv8_req = 1;
+  e->kv8 = 1;
+  return VC_OK;
+}
+
 extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
   if (!e) return VC_EINVAL;
   if (e->finalized) return fail(e, VC_ESTATE, "already finalized");
   if (compute_dtype != VC_DTYPE_BF16 && compute_dtype != VC_DTYPE_F32) return fail(e, VC_EINVAL, "compute dtype must be bf16 or f32");
   if (e->w8_req && compute_dtype != VC_DTYPE_BF16) return fail(e, VC_EINVAL, "vc_request_w8 was made, and the w8 form exists for bf16 engines only");
+  if (e->kv8_req && compute_dtype != VC_DTYPE_BF16) return fail(e, VC_EINVAL, "vc_request_kv8 was made, and the kv8 form exists for bf16 engines only");
   HIPCHK(e, hipSetDevice(e->device));
   e->dtype = compute_dtype;
   e->esz = compute_dtype == VC_DTYPE_BF16 ? 2 : 4;
@@ -1503,11 +1540,24 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
     const size_t cache_bytes = (size_t)e->B_max * e->H * e->S_max * e->hd * e->esz;
     if ((rc = dalloc(e, &ly.kc, cache_bytes))) return rc;
     if ((rc = dalloc(e, &ly.vc, cache_bytes))) return rc;
+    if (e->kv8_req) {
+      const size_t vals = (size_t)e->B_max * e->H * e->S_max * e->hd;
+      if ((rc = dalloc(e, &ly.kc8, vals)) || (rc = dalloc(e, &ly.vc8, vals)) || (rc = dalloc(e, &ly.sh8, vals / e->hd * 2))) return rc;
+      HIPCHK(e, hipMemset(ly.kc8, 0, vals));
+      HIPCHK(e, hipMemset(ly.vc8, 0, vals));
+      HIPCHK(e, hipMemset(ly.sh8, 0, vals / e->hd * 2));
+    }
     // free the staging copies of this layer right away (3.3 GB for the 830M shape otherwise)
     for (const char* k2 : {"self_attn.in_proj_weight", "self_attn.out_proj.weight", "linear1.weight", "linear2.weight"}) {
       auto it = e->raw.find(pre + k2);
       if (it != e->raw.end()) { HIPCHK(e, hipDeviceSynchronize()); (void)hipFree(it->second.dev); e->raw.erase(it); }
     }
+  }
+  if (e->kv8_req) {
+    std::vector<Kv8Layer> tab;
+    for (const Layer& ly : e->layers) tab.push_back(Kv8Layer{ly.kc, ly.vc, ly.kc8, ly.vc8, ly.sh8});
+    if ((rc = dalloc(e, &e->kv8_tab, tab.size()))) return rc;
+    HIPCHK(e, hipMemcpy(e->kv8_tab, tab.data(), tab.size() * sizeof(Kv8Layer), hipMemcpyHostToDevice));
   }
   // ---- heads: first linears concatenated to one [K*P][d] matrix, second ones one group each
   {
@@ -1700,6 +1750,19 @@ int replicate_kv(vc_engine* e, CopyKvArgs kv, hipStream_t s) {
     HIPCHK(e, vc_launch_copy_kv(kv, s));
     kv.base = (char*)e->layers[l].vc;
     HIPCHK(e, vc_launch_copy_kv(kv, s));
+  }
+  if (e->kv8_req) {      // the siblings' E4M3 rows and shifts: copies of the source's, which the prefill pass packed
+    CopyKvArgs k8 = kv, sh = kv;
+    k8.head_stride_b = (long)e->S_max * e->hd; k8.pos_b = e->hd; k8.seq_stride_b = (long)e->H * k8.head_stride_b;
+    sh.head_stride_b = (long)e->S_max * 2; sh.pos_b = 2; sh.seq_stride_b = (long)e->H * sh.head_stride_b;
+    for (int l = 0; l < e->L; ++l) {
+      k8.base = (char*)e->layers[l].kc8;
+      HIPCHK(e, vc_launch_copy_kv(k8, s));
+      k8.base = (char*)e->layers[l].vc8;
+      HIPCHK(e, vc_launch_copy_kv(k8, s));
+      sh.base = (char*)e->layers[l].sh8;
+      HIPCHK(e, vc_launch_copy_kv(sh, s));
+    }
   }
   return VC_OK;
 }
@@ -3184,6 +3247,16 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
     const Layer& ly = e->layers[atoi(n.c_str() + 6)];
     src = n[0] == 'k' ? ly.kc : ly.vc; avail = (int64_t)e->B_max * e->H * e->S_max * e->hd * e->esz;
   }
+  else if ((n.rfind("kcache8_", 0) == 0 || n.rfind("vcache8_", 0) == 0 || n.rfind("kvshift8_", 0) == 0) && e->kv8_req) {
+    // kcache8_<l> / vcache8_<l>: uint8 [max_seqs][H][max_positions][hd]; kvshift8_<l>: int8 [max_seqs][H][max_positions][2] (engines with vc_request_kv8)
+    const size_t at = n.find('_') + 1;
+    if (at >= n.size() || n.size() > at + 3 || n.find_first_not_of("0123456789", at) != std::string::npos || atoi(n.c_str() + at) >= e->L)
+      return fail(e, VC_EINVAL, "unknown debug buffer '%s'", n.c_str());
+    const Layer& ly = e->layers[atoi(n.c_str() + at)];
+    const int64_t rows = (int64_t)e->B_max * e->H * e->S_max;
+    if (n[1] == 'v') { src = ly.sh8; avail = rows * 2; }
+    else { src = n[0] == 'k' ? ly.kc8 : ly.vc8; avail = rows * e->hd; }
+  }
   else if (n == "eval_logits") {                    // fp32 [rows][K][V] of the last vc_eval_forward call with the parity hook
     if (!e->eval_logits) return fail(e, VC_ESTATE, "no vc_eval_forward call with nll_dev / tgt_dev has run");
     src = e->eval_logits; avail = e->eval_logits_rows * e->K * e->V * 4;
@@ -3298,6 +3371,7 @@ extern "C" int vc_bench_kernel(vc_engine* e, const char* which, int n_rows, int 
   RowSrc rs{};
   rs.h_in = e->dec_h; rs.row_seq = pf ? e->pre_row_seq : e->dec_row_seq; rs.row_pos = pf ? e->pre_row_pos : e->dec_row_pos;
   rs.n_rows = n_rows; rs.n_active = wide ? e->one : nullptr; rs.nt = 1;
+  rs.rps = pf ? 0 : 1;      // decode sites: a kv8 engine's attention on the E4M3 cache, as its steps launch it
   auto one = [&](int i) -> int {
     const Layer& ly = e->layers[hot ? 0 : i % e->L];   // _hot: the same 8-34 MB every launch (cache-resident)
     const Resid rq = qkv_in(e, p, ly, e->hB, &ly), rf = ffn_in(e, p, ly, e->hB);
@@ -3327,6 +3401,7 @@ extern "C" int vc_bench_kernel(vc_engine* e, const char* which, int n_rows, int 
   *avg_ms = ms / (float)iters;
   if (alg_bytes) {
     const double es = e->esz;
+    const double kvb = e->kv8 ? 1.0 + 2.0 / e->hd : es;      // bytes per cached value the decode attention streams (option "kv8": a code byte + the row's share of two shift bytes)
     const std::string& w = w2;
     double b = 0;
     if (w == "wd_ffn1") b = 4.0 * d * d * es + n_rows * (d * es + 4.0 * d * es);
@@ -3334,12 +3409,12 @@ extern "C" int vc_bench_kernel(vc_engine* e, const char* which, int n_rows, int 
     else if (w == "wd_qkv") b = 3.0 * d * d * es + n_rows * (d * es + d * 4.0 + 2.0 * d * es);
     else if (w == "wd_oproj") b = 1.0 * d * d * es + n_rows * (d * es + d * 4.0 * p.ks_o);
     else if (w == "wd_ln") b = n_rows * (d * 4.0 * (2 + p.ks_o) + d * es);
-    else if (w == "wd_attn") b = n_rows * 2.0 * d * es * (std::min(e->S_max - 1, 883) + 1);
+    else if (w == "wd_attn") b = n_rows * 2.0 * d * kvb * (std::min(e->S_max - 1, 883) + 1);
     else if (w == "ffn1") b = 4.0 * d * d * es + n_rows * (d * 4.0 + 4.0 * d * es);
     else if (w == "ffn2") b = 4.0 * d * d * es + n_rows * (4.0 * d * es + d * 4.0);
     else if (w == "qkv") b = 3.0 * d * d * es + n_rows * (d * 4.0 + 3.0 * d * es);
     else if (w == "oproj") b = 1.0 * d * d * es + n_rows * (d * 4.0 * 2);
-    else if (w == "attn") b = n_rows * 2.0 * d * es * (std::min(e->S_max - 1, 883) + 1);   // K and V of every cached position
+    else if (w == "attn") b = n_rows * 2.0 * d * kvb * (std::min(e->S_max - 1, 883) + 1);   // K and V of every cached position
     else if (w == "pf_qkv") b = 2.0 * n_rows * (double)d * 3.0 * d;                        // FLOPs
     else if (w == "pf_ffn1") b = 2.0 * n_rows * (double)d * 4.0 * d;                       // FLOPs, not bytes (MFMA roofline)
     else if (w == "pf_attn") b = 4.0 * d * ((double)n_rows * (n_rows + 1) / 2.0);          // FLOPs of Q K^T and P V under the causal mask

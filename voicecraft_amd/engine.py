@@ -50,8 +50,12 @@ class VoiceCraftEngine:
     """
 
     def __init__(self, args: Namespace | dict, state_dict: dict[str, torch.Tensor], device="cuda:0",
-                 dtype="bf16", max_seqs: int = 8, max_positions: int = 4096, use_graph: bool = True, w8: str | None = None):
-        """w8: None (default: nothing changes) | "quantize" | "as_is" - one-row steps of a bf16 engine stream the matrices of W8_MATRICES
+                 dtype="bf16", max_seqs: int = 8, max_positions: int = 4096, use_graph: bool = True, w8: str | None = None,
+                 kv8: bool = False):
+        """kv8: False (default: nothing changes) | True - decode passes of a bf16 engine read the cached K / V positions older than the pass
+        as one E4M3 byte per value times a per-row shift (option `kv8`, csrc/vc_kv8.h, quant.kv8_quantize_rows): half the bytes of the
+        launch that grows with the batch, 3 mantissa bits left of a cached value, 1.5 x the K/V memory.  Works with every call and `w8=`.
+        w8: None (default: nothing changes) | "quantize" | "as_is" - one-row steps of a bf16 engine stream the matrices of W8_MATRICES
         as one E4M3 byte per value (option `w8`, csrc/vc_w8.h), bit-identical to the bf16 launches on the same weights.  "quantize" first
         puts those matrices on the 8-bit grid (quant.quantize_state_dict_w8, on the CPU) and keeps the result as `self.w8_state_dict`,
         the checkpoint this engine then computes; "as_is" takes the weights as given: a matrix off the grid comes back refused
@@ -101,6 +105,9 @@ class VoiceCraftEngine:
         check(self.lib.vc_create(C.byref(cfg), index, C.byref(self._h)), None, "vc_create")
         if w8 is not None:
             check(self.lib.vc_request_w8(self._h, self.W8_MASK), self._h, "vc_request_w8")
+        self.kv8 = bool(kv8)
+        if self.kv8:
+            check(self.lib.vc_request_kv8(self._h), self._h, "vc_request_kv8")
         self._load(state_dict)
         self.last_steps = 0
         self.last_kept: list[int] = []       # inference_tts_multi / _long with batch_size > 1: kept sample per utterance
@@ -689,7 +696,8 @@ class VoiceCraftEngine:
         forms (finished_rows, fr_pair, att_p16, hq), ta = tile_attn (kernel, min rows), r1 = one-row and attention forms (fr_one,
         attn_fast, qkv_p8), q16 = many-row steps (qkv16, wide_heads, wide_gemm, wd_stage), sh = shrink, w13 = the one-row launches that
         stream their weights as exact 13-bit planes (mask: 1 FFN-down, 4 QKV; w13_stats() says which matrices have planes); an engine
-        created with `w8=` appends w8 = the launches that stream E4M3 bytes instead (same bits, w8_stats()).
+        created with `w8=` appends w8 = the launches that stream E4M3 bytes instead (same bits, w8_stats()), one created with `kv8=True`
+        appends kv8 = decode attention on the E4M3 copy of the K/V cache (1) or on the bf16 cache (0).
         bench.py turns it into a JSON object (`config.engine_options`)."""
         return bytes(self.debug_read("options", (256,), torch.uint8).tolist()).split(b"\0")[0].decode()
 
@@ -705,7 +713,8 @@ class VoiceCraftEngine:
         return ms.value, nbytes.value
 
     LAUNCH_FORMS = ("rows_gemm", "mt2", "mt4", "blk64", "blk128_sbs", "blk128_2x2", "blk64_occ2", "ln_rows", "rows_attn",
-                    "tile_attn", "rows_gemm_fr", "big256", "big128", "row_gemm_fr1", "tile_attn64", "rows_gemm_frp", "wd", "rows_gemm_qp", "w13", "w8")
+                    "tile_attn", "rows_gemm_fr", "big256", "big128", "row_gemm_fr1", "tile_attn64", "rows_gemm_frp", "wd", "rows_gemm_qp", "w13", "w8",
+                    "kv8_attn", "kv8_pack")
 
     def launch_counts(self) -> dict:
         """Process-wide census of the kernel FORMS launched so far (vc_common.h VC_LC_*): the parity tests take the
@@ -1146,6 +1155,66 @@ def debug_attn(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, row_
     if rc != 0:
         raise AssertionError(f"vc_debug_attn rejected its arguments (code {rc})")
     return out
+
+
+def debug_attn8(q, kcache, vcache, kcache8, vcache8, kvshift8, row_seq, row_pos, n_active, share_len, nsplit: int = 1, rps: int = 1,
+                pack: bool = False, nt: bool = False, fast: bool = True, part16: bool = False, x_out: bool = False,
+                sentinel: float = 0.0) -> dict:
+    """vc_debug_attn8 (tests only): debug_attn for option `kv8`.  kcache / vcache bf16 [n_seqs][H][S_max][hd]; kcache8 / vcache8 uint8 of
+    that shape; kvshift8 int8 [n_seqs][H][S_max][2].  pack=True: ONE launch of the packer over the rows (row_seq, row_pos), which writes
+    the three 8-bit arrays in place ({} comes back).  Else one launch of the decode attention's kv8 form with `rps` rows per sequence;
+    the outputs as debug_attn's."""
+    lib = _lib.load()
+    dev = kcache.device
+    assert kcache.dtype == torch.bfloat16 == vcache.dtype and kcache.shape == vcache.shape and kcache.ndim == 4
+    n_seqs, H, S_max, hd = kcache.shape
+    for t in (kcache8, vcache8):
+        assert t.dtype == torch.uint8 and t.shape == kcache.shape
+    assert kvshift8.dtype == torch.int8 and tuple(kvshift8.shape) == (n_seqs, H, S_max, 2)
+    for t in (kcache, vcache, kcache8, vcache8, kvshift8):
+        assert t.is_cuda and t.device == dev and t.is_contiguous()
+    rows = row_pos.numel()
+    for t, n in ((row_seq, rows), (row_pos, rows), (n_active, 1), (share_len, 1)):
+        assert t.dtype == torch.int32 and t.device == dev and t.numel() == n and t.is_contiguous()
+    assert int(row_seq.max()) < n_seqs and int(row_pos.max()) < S_max and int(share_len) <= S_max      # the kernels trust their tables
+    a8 = _lib.DebugAttn8Args()
+    a = a8.base
+    a.kcache, a.vcache = kcache.data_ptr(), vcache.data_ptr()
+    a8.kcache8, a8.vcache8, a8.kvshift8 = kcache8.data_ptr(), vcache8.data_ptr(), kvshift8.data_ptr()
+    a.row_seq, a.row_pos, a.n_active, a.share_len = row_seq.data_ptr(), row_pos.data_ptr(), n_active.data_ptr(), share_len.data_ptr()
+    a.dtype = _lib.VC_DTYPE_BF16
+    a.H, a.hd, a.S_max, a.rows, a.nsplit = H, hd, S_max, rows, int(nsplit)
+    a.nt, a.fast, a.part16 = int(bool(nt)), int(bool(fast)), int(bool(part16))
+    a8.rps, a8.pack = int(rps), int(bool(pack))
+    out = {}
+    if not pack:
+        assert q.is_cuda and q.dtype == torch.float32 and q.shape == (rows, H * hd) and q.is_contiguous() and rows % int(rps) == 0
+        a.q = q.data_ptr()
+        if x_out:
+            out["x_out"] = torch.full((rows, H * hd), sentinel, dtype=torch.bfloat16, device=dev)
+            a.x_out = out["x_out"].data_ptr()
+        else:
+            n = max(int(nsplit), 1)
+            out["att_o"] = torch.full((rows, H, n, hd), sentinel, dtype=torch.bfloat16 if part16 else torch.float32, device=dev)
+            out["att_ml"] = torch.full((rows, H, n, 2), sentinel, dtype=torch.float32, device=dev)
+            a.att_o, a.att_ml = out["att_o"].data_ptr(), out["att_ml"].data_ptr()
+    rc = lib.vc_debug_attn8(C.byref(a8), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise AssertionError(f"vc_debug_attn8 rejected its arguments (code {rc})")
+    return out
+
+
+def kv8_quantize_host(rows_bf16: torch.Tensor):
+    """csrc/vc_kv8.h's encode on the CPU (vc_kv8_quantize_host): bf16 rows [..., hd] -> (codes uint8 [..., hd], shift int8 [...])."""
+    lib = _lib.load()
+    x = rows_bf16.detach().to("cpu", torch.bfloat16).contiguous()
+    hd = x.shape[-1]
+    n = x.numel() // hd
+    codes = torch.empty(x.shape, dtype=torch.uint8)
+    shift = torch.empty(x.shape[:-1], dtype=torch.int8)
+    rc = lib.vc_kv8_quantize_host(C.c_void_p(x.data_ptr()), n, hd, C.c_void_p(codes.data_ptr()), C.c_void_p(shift.data_ptr()))
+    assert rc == 0, rc
+    return codes, shift
 
 
 def box_probe(device="cuda:0", hops: int = 256) -> dict:

@@ -1,4 +1,5 @@
-"""Puts a checkpoint on the engine's 8-bit weight grid ("w8", csrc/vc_w8.h), on the CPU.
+"""Puts a checkpoint on the engine's 8-bit weight grid ("w8", csrc/vc_w8.h), on the CPU; at the end of the file the CPU statement of the
+same grid for cached K / V rows ("kv8", csrc/vc_kv8.h).
 
 The grid's unit is the 512-value MFMA fragment of the engine's 8-channel-tile images: an aligned block of 8 output channels x 64
 inputs of the bf16 image (csrc/vc_gemm.hip pack_k with th = 8: a tile is 8 channels x 32 inputs, a fragment two consecutive
@@ -99,3 +100,32 @@ def quantize_state_dict_w8(args, sd: dict, matrices=("ffn_down", "qkv")) -> dict
             gamma = sd[p + gkey] if gkey else None
             out[p + wkey] = quantize_matrix(sd[p + wkey], gamma).to(torch.float32)
     return out
+
+
+# ---- "kv8": cached K / V rows on the same grid, the block being one head's row of hd values (csrc/vc_kv8.h) -----------------------------
+def kv8_quantize_rows(x: torch.Tensor):
+    """bf16-valued rows [..., hd] -> (codes uint8 [..., hd], shift int8 [...]): value ~ q * 2**shift, q the float8_e4m3fn number the code
+    byte holds.  The shift is block_shifts' rule with the row as the block (floor(log2 amax) - 8, clamped to the range, one more where
+    amax * 2**-s > 464, 0 for a row of zeros); values are scaled, clamped to +-448 and rounded to nearest even, so the NaN code is never
+    stored.  This is the statement the engine's packer (kv8_pack_k) must match bit for bit."""
+    x = x.detach().to(torch.float32)
+    assert bool(torch.isfinite(x).all()) and bool((x == x.bfloat16().float()).all()), "rows of finite bf16 values"
+    amax = x.abs().amax(dim=-1).double()
+    _, e = torch.frexp(amax)
+    s = (e - 1 - 8).clamp(SHIFT_MIN, SHIFT_MAX)
+    s = torch.where(torch.ldexp(amax, -s) > 464.0, s + 1, s).clamp(max=SHIFT_MAX)
+    s = torch.where(amax == 0, torch.zeros_like(s), s)
+    q = torch.ldexp(x.double(), -s.unsqueeze(-1)).clamp(-448.0, 448.0).float()
+    codes = q.to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes, s.to(torch.int8)
+
+
+def kv8_dequantize(codes: torch.Tensor, shift: torch.Tensor) -> torch.Tensor:
+    """The fp32 values (bf16 numbers, all of them) the codes stand for at their rows' shifts."""
+    q = codes.contiguous().view(torch.float8_e4m3fn).float().double()
+    return torch.ldexp(q, shift.to(torch.int32).unsqueeze(-1)).float()
+
+
+def kv8_roundtrip(x: torch.Tensor) -> torch.Tensor:
+    """What a kv8 engine's decode attention reads in place of the cached rows x [..., hd]."""
+    return kv8_dequantize(*kv8_quantize_rows(x))
