@@ -42,6 +42,15 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
         assert name in decl, f"{name} bound in Python but not declared in include/"
 
 
+def test_build_refuses_a_listed_source_that_is_missing(monkeypatch):
+    """A unit listed in build.SOURCES but absent from csrc/ is an error that names the file: the -shared link accepts undefined
+    symbols, so the library would build without the unit and fail only when it is loaded."""
+    from voicecraft_amd import build
+    monkeypatch.setattr(build, "SOURCES", build.SOURCES + ["vc_engine_misspelt.hip"])
+    with pytest.raises(FileNotFoundError, match="vc_engine_misspelt.hip"):
+        build.build()
+
+
 def test_struct_layout_matches_header():
     from voicecraft_amd._lib import ModelCfg, SampleCfg
     assert C.sizeof(ModelCfg) == 17 * 4

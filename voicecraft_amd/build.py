@@ -35,7 +35,13 @@ def _digest(paths) -> str:
 
 
 def sources() -> list[Path]:
-    return [CSRC / s for s in SOURCES if (CSRC / s).exists()]
+    """Every listed unit.  A listed file that is missing is an error here: the -shared link accepts undefined symbols, so a unit
+    left out would only show when the library is loaded."""
+    srcs = [CSRC / s for s in SOURCES]
+    missing = [p.name for p in srcs if not p.exists()]
+    if missing:
+        raise FileNotFoundError(f"listed in SOURCES but not in {CSRC}: {', '.join(missing)}")
+    return srcs
 
 
 def build(force: bool = False, verbose: bool = False, variant: str = "", extra_flags=()) -> Path:

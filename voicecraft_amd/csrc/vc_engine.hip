@@ -1433,19 +1433,23 @@ extern "C" int vc_request_kv8(vc_engine* e) {
   return VC_OK;
 }
 
-extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
-  if (!e) return VC_EINVAL;
-  if (e->finalized) return fail(e, VC_ESTATE, "already finalized");
-  if (compute_dtype != VC_DTYPE_BF16 && compute_dtype != VC_DTYPE_F32) return fail(e, VC_EINVAL, "compute dtype must be bf16 or f32");
-  if (e->w8_req && compute_dtype != VC_DTYPE_BF16) return fail(e, VC_EINVAL, "vc_request_w8 was made, and the w8 form exists for bf16 engines only");
-  if (e->kv8_req && compute_dtype != VC_DTYPE_BF16) return fail(e, VC_EINVAL, "vc_request_kv8 was made, and the kv8 form exists for bf16 engines only");
-  HIPCHK(e, hipSetDevice(e->device));
-  e->dtype = compute_dtype;
-  e->esz = compute_dtype == VC_DTYPE_BF16 ? 2 : 4;
-  const int d = e->d, L = e->L, K = e->K, V = e->V, P = e->P;
+namespace {
+
+// dalloc, and the first `zero` bytes of the buffer cleared (the device words are four ints each: most are cleared as those 16 bytes)
+template <typename T>
+int dalloc0(vc_engine* e, T** p, size_t n, size_t zero) {
+  if (const int rc = dalloc(e, p, n)) return rc;
+  HIPCHK(e, hipMemset(*p, 0, zero));
+  return VC_OK;
+}
+
+// The steps of vc_finalize_weights, in the order it calls them.  The order and the sizes of the allocations are behaviour: addresses
+// in HBM follow from them, and the decode kernels' timings have been sensitive to placement.
+// ---- embeddings (kept fp32: a handful of row gathers per step)
+int load_embeddings(vc_engine* e) {
+  const int d = e->d, K = e->K, V = e->V;
   int rc;
   const RawTensor* t;
-  // ---- embeddings (kept fp32: a handful of row gathers per step)
   if ((rc = need(e, "text_embedding.word_embeddings.weight", {e->cfg.text_rows, d}, &t))) return rc;
   if ((rc = dalloc(e, &e->text_emb, (size_t)t->numel))) return rc;
   HIPCHK(e, hipMemcpy(e->text_emb, t->dev, (size_t)t->numel * 4, hipMemcpyDeviceToDevice));
@@ -1461,8 +1465,14 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
   HIPCHK(e, hipMemcpy(&e->alpha_text, t->dev, 4, hipMemcpyDeviceToHost));
   if ((rc = need(e, "audio_positional_embedding.alpha", {1}, &t))) return rc;
   HIPCHK(e, hipMemcpy(&e->alpha_audio, t->dev, 4, hipMemcpyDeviceToHost));
-  // ---- sinusoidal table (embedding.py:69-92).  "pe" may be supplied by the loader (torch's own
-  // sin/cos); otherwise it is computed here in fp32 with the same formula.
+  return VC_OK;
+}
+
+// ---- sinusoidal table (embedding.py:69-92).  "pe" may be supplied by the loader (torch's own
+// sin/cos); otherwise it is computed here in fp32 with the same formula.
+int load_position_table(vc_engine* e) {
+  const int d = e->d;
+  int rc;
   if ((rc = dalloc(e, &e->pe, (size_t)e->S_max * d))) return rc;
   if (const RawTensor* pt = find_raw(e, "pe")) {
     if (pt->shape.size() != 2 || pt->shape[0] < e->S_max || pt->shape[1] != d)
@@ -1480,7 +1490,12 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
     }
     HIPCHK(e, hipMemcpy(e->pe, pe.data(), pe.size() * 4, hipMemcpyHostToDevice));
   }
-  // ---- decoder layers
+  return VC_OK;
+}
+
+// ---- which images and planes the decoder layers get: decided at creation, from the VC_* presets
+void decide_images(vc_engine* e) {
+  const int d = e->d;
   const char* env_fr = getenv("VC_FINISHED_ROWS");
   const char* env_f1 = getenv("VC_FR_ONE");
   const bool want_fr8 = !(env_fr && atoi(env_fr) == 0 && env_f1 && atoi(env_f1) == 0);
@@ -1496,111 +1511,124 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
   e->has_qkv16 = want_qkv16;
   const char* env_w13 = getenv("VC_W13");
   e->has_w13 = e->dtype == VC_DTYPE_BF16 && !(env_w13 && atoi(env_w13) == 0);
-  e->layers.resize(L);
-  for (int l = 0; l < L; ++l) {
-    const std::string pre = "decoder.layers." + std::to_string(l) + ".";
-    Layer& ly = e->layers[l];
-    if ((rc = pack_folded(e, pre + "self_attn.in_proj_weight", pre + "self_attn.in_proj_bias", pre + "norm1.", 3 * d, d,
-                          &ly.Wqkv, &ly.wg_qkv, &ly.bqkv, VC_TH_QKV))) return rc;
-    if (want_qkv16) {
+}
+
+// ---- decoder layer l: its images, their 8- and 16-channel twins and packed planes, its K/V cache (and the kv8 copy); frees its staging
+int pack_layer(vc_engine* e, int l) {
+  const int d = e->d;
+  const bool want_fr8 = e->has_fr8, want_qkv16 = e->has_qkv16;
+  int rc;
+  const std::string pre = "decoder.layers." + std::to_string(l) + ".";
+  Layer& ly = e->layers[l];
+  if ((rc = pack_folded(e, pre + "self_attn.in_proj_weight", pre + "self_attn.in_proj_bias", pre + "norm1.", 3 * d, d,
+                        &ly.Wqkv, &ly.wg_qkv, &ly.bqkv, VC_TH_QKV))) return rc;
+  if (want_qkv16) {
+    const RawTensor* tg1;
+    if ((rc = need(e, pre + "norm1.weight", {d}, &tg1))) return rc;
+    if ((rc = pack_matrix(e, pre + "self_attn.in_proj_weight", 3 * d, d, &ly.Wqkv16, 16, tg1->dev))) return rc;
+  }
+  if ((rc = pack_matrix(e, pre + "self_attn.out_proj.weight", d, d, &ly.Wo))) return rc;
+  if ((rc = keep_vec(e, pre + "self_attn.out_proj.bias", d, &ly.bo, &ly.bo_mean))) return rc;
+  if ((rc = pack_folded(e, pre + "linear1.weight", pre + "linear1.bias", pre + "norm2.", 4 * d, d,
+                        &ly.W1, &ly.wg_1, &ly.b1))) return rc;
+  if ((rc = pack_matrix(e, pre + "linear2.weight", d, 4 * d, &ly.W2))) return rc;
+  // the second, 8-channel-tile image of the two row-producing matrices (finished-row forms): + 10 d^2 elements per layer = + 0.67 GB
+  // at giga830M in bf16.  An engine created with BOTH forms preset off (VC_FINISHED_ROWS=0 and VC_FR_ONE=0) does not pack them,
+  // and refuses to switch the forms on later (apply_option).
+  if (want_fr8) {
+    if ((rc = pack_matrix(e, pre + "self_attn.out_proj.weight", d, d, &ly.Wo8, VC_TH_RES))) return rc;
+    if ((rc = pack_matrix(e, pre + "linear2.weight", d, 4 * d, &ly.W28, VC_TH_RES))) return rc;
+    // (the one-row paired QKV kernel reads the folded matrix in 8-channel tiles: only where its form can run, i.e. behind fr_one)
+    // (not packed when either of the two options it serves is preset off - VC_QKV_P8=0 / VC_FR_ONE=0 -: 0.4 GB at giga830M)
+    if (e->has_qkv8) {
       const RawTensor* tg1;
       if ((rc = need(e, pre + "norm1.weight", {d}, &tg1))) return rc;
-      if ((rc = pack_matrix(e, pre + "self_attn.in_proj_weight", 3 * d, d, &ly.Wqkv16, 16, tg1->dev))) return rc;
-    }
-    if ((rc = pack_matrix(e, pre + "self_attn.out_proj.weight", d, d, &ly.Wo))) return rc;
-    if ((rc = keep_vec(e, pre + "self_attn.out_proj.bias", d, &ly.bo, &ly.bo_mean))) return rc;
-    if ((rc = pack_folded(e, pre + "linear1.weight", pre + "linear1.bias", pre + "norm2.", 4 * d, d,
-                          &ly.W1, &ly.wg_1, &ly.b1))) return rc;
-    if ((rc = pack_matrix(e, pre + "linear2.weight", d, 4 * d, &ly.W2))) return rc;
-    // the second, 8-channel-tile image of the two row-producing matrices (finished-row forms): + 10 d^2 elements per layer = + 0.67 GB
-    // at giga830M in bf16.  An engine created with BOTH forms preset off (VC_FINISHED_ROWS=0 and VC_FR_ONE=0) does not pack them,
-    // and refuses to switch the forms on later (apply_option).
-    if (want_fr8) {
-      if ((rc = pack_matrix(e, pre + "self_attn.out_proj.weight", d, d, &ly.Wo8, VC_TH_RES))) return rc;
-      if ((rc = pack_matrix(e, pre + "linear2.weight", d, 4 * d, &ly.W28, VC_TH_RES))) return rc;
-      // (the one-row paired QKV kernel reads the folded matrix in 8-channel tiles: only where its form can run, i.e. behind fr_one)
-      // (not packed when either of the two options it serves is preset off - VC_QKV_P8=0 / VC_FR_ONE=0 -: 0.4 GB at giga830M)
-      if (e->has_qkv8) {
-        const RawTensor* tg1;
-        if ((rc = need(e, pre + "norm1.weight", {d}, &tg1))) return rc;
-        if ((rc = pack_matrix(e, pre + "self_attn.in_proj_weight", 3 * d, d, &ly.Wqkv8, VC_TH_RES, tg1->dev))) return rc;
-      }
-    }
-    if ((rc = keep_vec(e, pre + "linear2.bias", d, &ly.b2, &ly.b2_mean))) return rc;
-    // two of the big matrices of a one-row step once more as 13-bit planes, where a wave's share is whole groups of four fragments
-    // (vc_gemm_packed_fr1_ng: FFN-down from d = 512, QKV from d = 1024), and, only for an engine that asked (vc_request_w8), the
-    // requested ones as E4M3 bytes: the same widths, + 0.5 x the requested images
-    const int pack_mask[VC_PK_N] = {e->has_w13 ? 5 : 0, e->w8_req};
-    for (int kind = 0; kind < VC_PK_N; ++kind) {
-      if ((pack_mask[kind] & W8_BITS[W13_F2]) && ly.W28 && vc_gemm_packed_fr1_ng(kind, d, 4 * d, e->dtype, VC_FR_WAVES) &&
-          (rc = pack_planes(e, ly, kind, W13_F2, ly.W28, (long)(d / VC_TH_RES) * (4 * d / 64)))) return rc;
-      if ((pack_mask[kind] & W8_BITS[W13_QKV]) && ly.Wqkv8 && vc_gemm_packed_fr1_ng(kind, 3 * d, d, e->dtype, 4) &&
-          (rc = pack_planes(e, ly, kind, W13_QKV, ly.Wqkv8, (long)(3 * d / VC_TH_RES) * (d / 64)))) return rc;
-    }
-    const size_t cache_bytes = (size_t)e->B_max * e->H * e->S_max * e->hd * e->esz;
-    if ((rc = dalloc(e, &ly.kc, cache_bytes))) return rc;
-    if ((rc = dalloc(e, &ly.vc, cache_bytes))) return rc;
-    if (e->kv8_req) {
-      const size_t vals = (size_t)e->B_max * e->H * e->S_max * e->hd;
-      if ((rc = dalloc(e, &ly.kc8, vals)) || (rc = dalloc(e, &ly.vc8, vals)) || (rc = dalloc(e, &ly.sh8, vals / e->hd * 2))) return rc;
-      HIPCHK(e, hipMemset(ly.kc8, 0, vals));
-      HIPCHK(e, hipMemset(ly.vc8, 0, vals));
-      HIPCHK(e, hipMemset(ly.sh8, 0, vals / e->hd * 2));
-    }
-    // free the staging copies of this layer right away (3.3 GB for the 830M shape otherwise)
-    for (const char* k2 : {"self_attn.in_proj_weight", "self_attn.out_proj.weight", "linear1.weight", "linear2.weight"}) {
-      auto it = e->raw.find(pre + k2);
-      if (it != e->raw.end()) { HIPCHK(e, hipDeviceSynchronize()); (void)hipFree(it->second.dev); e->raw.erase(it); }
+      if ((rc = pack_matrix(e, pre + "self_attn.in_proj_weight", 3 * d, d, &ly.Wqkv8, VC_TH_RES, tg1->dev))) return rc;
     }
   }
+  if ((rc = keep_vec(e, pre + "linear2.bias", d, &ly.b2, &ly.b2_mean))) return rc;
+  // two of the big matrices of a one-row step once more as 13-bit planes, where a wave's share is whole groups of four fragments
+  // (vc_gemm_packed_fr1_ng: FFN-down from d = 512, QKV from d = 1024), and, only for an engine that asked (vc_request_w8), the
+  // requested ones as E4M3 bytes: the same widths, + 0.5 x the requested images
+  const int pack_mask[VC_PK_N] = {e->has_w13 ? 5 : 0, e->w8_req};
+  for (int kind = 0; kind < VC_PK_N; ++kind) {
+    if ((pack_mask[kind] & W8_BITS[W13_F2]) && ly.W28 && vc_gemm_packed_fr1_ng(kind, d, 4 * d, e->dtype, VC_FR_WAVES) &&
+        (rc = pack_planes(e, ly, kind, W13_F2, ly.W28, (long)(d / VC_TH_RES) * (4 * d / 64)))) return rc;
+    if ((pack_mask[kind] & W8_BITS[W13_QKV]) && ly.Wqkv8 && vc_gemm_packed_fr1_ng(kind, 3 * d, d, e->dtype, 4) &&
+        (rc = pack_planes(e, ly, kind, W13_QKV, ly.Wqkv8, (long)(3 * d / VC_TH_RES) * (d / 64)))) return rc;
+  }
+  const size_t cache_bytes = (size_t)e->B_max * e->H * e->S_max * e->hd * e->esz;
+  if ((rc = dalloc(e, &ly.kc, cache_bytes))) return rc;
+  if ((rc = dalloc(e, &ly.vc, cache_bytes))) return rc;
   if (e->kv8_req) {
-    std::vector<Kv8Layer> tab;
-    for (const Layer& ly : e->layers) tab.push_back(Kv8Layer{ly.kc, ly.vc, ly.kc8, ly.vc8, ly.sh8});
-    if ((rc = dalloc(e, &e->kv8_tab, tab.size()))) return rc;
-    HIPCHK(e, hipMemcpy(e->kv8_tab, tab.data(), tab.size() * sizeof(Kv8Layer), hipMemcpyHostToDevice));
+    const size_t vals = (size_t)e->B_max * e->H * e->S_max * e->hd;
+    if ((rc = dalloc0(e, &ly.kc8, vals, vals)) || (rc = dalloc0(e, &ly.vc8, vals, vals)) ||
+        (rc = dalloc0(e, &ly.sh8, vals / e->hd * 2, vals / e->hd * 2))) return rc;
   }
-  // ---- heads: first linears concatenated to one [K*P][d] matrix, second ones one group each
-  {
-    // (folded with the final LayerNorm decoder.norm, transformer.py:484-485)
-    float *cat, *bcat;
-    const RawTensor *tg, *tbe;
-    if ((rc = need(e, "decoder.norm.weight", {d}, &tg))) return rc;
-    if ((rc = need(e, "decoder.norm.bias", {d}, &tbe))) return rc;
-    HIPCHK(e, hipMalloc((void**)&cat, (size_t)K * P * d * 4));
-    if (hipMalloc((void**)&bcat, (size_t)K * P * 4) != hipSuccess) { (void)hipFree(cat); return fail(e, VC_EHIP, "hipMalloc failed"); }
-    auto drop = [&]() { (void)hipDeviceSynchronize(); (void)hipFree(cat); (void)hipFree(bcat); };
-    if ((rc = dalloc(e, &e->bh1, (size_t)K * P))) { drop(); return rc; }
-    if ((rc = dalloc(e, &e->wg_h1, (size_t)K * P))) { drop(); return rc; }
-    for (int k = 0; k < K; ++k) {
-      const std::string pre = "predict_layer." + std::to_string(k) + ".";
-      if ((rc = need(e, pre + "0.weight", {P, d}, &t))) { drop(); return rc; }
-      if (hipMemcpy(cat + (size_t)k * P * d, t->dev, (size_t)P * d * 4, hipMemcpyDeviceToDevice) != hipSuccess) { drop(); return fail(e, VC_EHIP, "hipMemcpy of %s0.weight failed", pre.c_str()); }
-      if ((rc = need(e, pre + "0.bias", {P}, &t))) { drop(); return rc; }
-      if (hipMemcpy(bcat + (size_t)k * P, t->dev, (size_t)P * 4, hipMemcpyDeviceToDevice) != hipSuccess) { drop(); return fail(e, VC_EHIP, "hipMemcpy of %s0.bias failed", pre.c_str()); }
-    }
-    const int KW = e->dtype == VC_DTYPE_BF16 ? 32 : 16;
-    const long units = (long)(K * P / 16) * (d / KW) * 64;
-    if ((rc = dalloc(e, &e->Wh1, (size_t)units))) { drop(); return rc; }
-    hipError_t pe_ = vc_launch_pack(cat, tg->dev, e->Wh1, K * P, d, e->dtype, 16, 0);
-    if (pe_ == hipSuccess) pe_ = vc_launch_fold_vecs(cat, tg->dev, tbe->dev, bcat, e->wg_h1, e->bh1, K * P, d, e->dtype, 0);
-    drop();
-    HIPCHK(e, pe_);
-    const long gunits = (long)((V + 15) / 16) * (P / KW) * 64;
-    e->wh2_group_stride = gunits;
-    if ((rc = dalloc(e, &e->Wh2, (size_t)gunits * K))) return rc;
-    if ((rc = dalloc(e, &e->bh2, (size_t)K * V))) return rc;
-    for (int k = 0; k < K; ++k) {
-      const std::string pre = "predict_layer." + std::to_string(k) + ".";
-      if ((rc = need(e, pre + "2.weight", {V, P}, &t))) return rc;
-      HIPCHK(e, vc_launch_pack(t->dev, nullptr, e->Wh2 + (size_t)k * gunits, V, P, e->dtype, 16, 0));
-      if ((rc = need(e, pre + "2.bias", {V}, &t))) return rc;
-      HIPCHK(e, hipMemcpy(e->bh2 + (size_t)k * V, t->dev, (size_t)V * 4, hipMemcpyDeviceToDevice));
-    }
+  // free the staging copies of this layer right away (3.3 GB for the 830M shape otherwise)
+  for (const char* k2 : {"self_attn.in_proj_weight", "self_attn.out_proj.weight", "linear1.weight", "linear2.weight"}) {
+    auto it = e->raw.find(pre + k2);
+    if (it != e->raw.end()) { HIPCHK(e, hipDeviceSynchronize()); (void)hipFree(it->second.dev); e->raw.erase(it); }
   }
-  HIPCHK(e, hipDeviceSynchronize());
-  for (auto& kv : e->raw) if (kv.second.dev) (void)hipFree(kv.second.dev);
-  e->raw.clear();
-  // ---- launch plans
+  return VC_OK;
+}
+
+// ---- option "kv8": the device table of the layers' five arrays
+int upload_kv8_table(vc_engine* e) {
+  int rc;
+  std::vector<Kv8Layer> tab;
+  for (const Layer& ly : e->layers) tab.push_back(Kv8Layer{ly.kc, ly.vc, ly.kc8, ly.vc8, ly.sh8});
+  if ((rc = dalloc(e, &e->kv8_tab, tab.size()))) return rc;
+  HIPCHK(e, hipMemcpy(e->kv8_tab, tab.data(), tab.size() * sizeof(Kv8Layer), hipMemcpyHostToDevice));
+  return VC_OK;
+}
+
+// ---- heads: first linears concatenated to one [K*P][d] matrix, second ones one group each
+int pack_heads(vc_engine* e) {
+  const int d = e->d, K = e->K, V = e->V, P = e->P;
+  int rc;
+  const RawTensor* t;
+  // (folded with the final LayerNorm decoder.norm, transformer.py:484-485)
+  float *cat, *bcat;
+  const RawTensor *tg, *tbe;
+  if ((rc = need(e, "decoder.norm.weight", {d}, &tg))) return rc;
+  if ((rc = need(e, "decoder.norm.bias", {d}, &tbe))) return rc;
+  HIPCHK(e, hipMalloc((void**)&cat, (size_t)K * P * d * 4));
+  if (hipMalloc((void**)&bcat, (size_t)K * P * 4) != hipSuccess) { (void)hipFree(cat); return fail(e, VC_EHIP, "hipMalloc failed"); }
+  auto drop = [&]() { (void)hipDeviceSynchronize(); (void)hipFree(cat); (void)hipFree(bcat); };
+  if ((rc = dalloc(e, &e->bh1, (size_t)K * P))) { drop(); return rc; }
+  if ((rc = dalloc(e, &e->wg_h1, (size_t)K * P))) { drop(); return rc; }
+  for (int k = 0; k < K; ++k) {
+    const std::string pre = "predict_layer." + std::to_string(k) + ".";
+    if ((rc = need(e, pre + "0.weight", {P, d}, &t))) { drop(); return rc; }
+    if (hipMemcpy(cat + (size_t)k * P * d, t->dev, (size_t)P * d * 4, hipMemcpyDeviceToDevice) != hipSuccess) { drop(); return fail(e, VC_EHIP, "hipMemcpy of %s0.weight failed", pre.c_str()); }
+    if ((rc = need(e, pre + "0.bias", {P}, &t))) { drop(); return rc; }
+    if (hipMemcpy(bcat + (size_t)k * P, t->dev, (size_t)P * 4, hipMemcpyDeviceToDevice) != hipSuccess) { drop(); return fail(e, VC_EHIP, "hipMemcpy of %s0.bias failed", pre.c_str()); }
+  }
+  const int KW = e->dtype == VC_DTYPE_BF16 ? 32 : 16;
+  const long units = (long)(K * P / 16) * (d / KW) * 64;
+  if ((rc = dalloc(e, &e->Wh1, (size_t)units))) { drop(); return rc; }
+  hipError_t pe_ = vc_launch_pack(cat, tg->dev, e->Wh1, K * P, d, e->dtype, 16, 0);
+  if (pe_ == hipSuccess) pe_ = vc_launch_fold_vecs(cat, tg->dev, tbe->dev, bcat, e->wg_h1, e->bh1, K * P, d, e->dtype, 0);
+  drop();
+  HIPCHK(e, pe_);
+  const long gunits = (long)((V + 15) / 16) * (P / KW) * 64;
+  e->wh2_group_stride = gunits;
+  if ((rc = dalloc(e, &e->Wh2, (size_t)gunits * K))) return rc;
+  if ((rc = dalloc(e, &e->bh2, (size_t)K * V))) return rc;
+  for (int k = 0; k < K; ++k) {
+    const std::string pre = "predict_layer." + std::to_string(k) + ".";
+    if ((rc = need(e, pre + "2.weight", {V, P}, &t))) return rc;
+    HIPCHK(e, vc_launch_pack(t->dev, nullptr, e->Wh2 + (size_t)k * gunits, V, P, e->dtype, 16, 0));
+    if ((rc = need(e, pre + "2.bias", {V}, &t))) return rc;
+    HIPCHK(e, hipMemcpy(e->bh2 + (size_t)k * V, t->dev, (size_t)V * 4, hipMemcpyDeviceToDevice));
+  }
+  return VC_OK;
+}
+
+// ---- launch plans
+void make_plans(vc_engine* e) {
+  const int d = e->d, K = e->K, V = e->V, P = e->P;
   e->p_qkv = make_plan(3 * d, d, e->dtype, false, nullptr, VC_TH_QKV);
   e->p_qkv16 = make_plan(3 * d, d, e->dtype, false, nullptr, 16);
   e->p_o = make_plan(d, d, e->dtype, true, "VC_KSPLIT_O");
@@ -1608,7 +1636,12 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
   e->p_f2 = make_plan(d, 4 * d, e->dtype, true, "VC_KSPLIT_F");
   e->p_h1 = make_plan(K * P, d, e->dtype, false, nullptr);
   e->p_h2 = make_plan(V, P, e->dtype, false, nullptr);
-  // ---- scratch arenas
+}
+
+// ---- scratch arenas of a pass
+int alloc_pass_arenas(vc_engine* e) {
+  const int d = e->d, K = e->K, V = e->V, P = e->P;
+  int rc;
   e->emb_cap = std::max(e->S_max, 8 * VC_MAX_ROWS);
   if ((rc = dalloc(e, &e->emb, (size_t)e->emb_cap * d))) return rc;
   if ((rc = dalloc(e, &e->pre_row_seq, (size_t)e->emb_cap + VC_MAX_ROWS))) return rc;
@@ -1623,39 +1656,43 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
   if ((rc = dalloc(e, &e->xn, (size_t)VC_MAX_ROWS * d * e->esz))) return rc;
   if ((rc = dalloc(e, &e->hh, (size_t)e->NS * K * P * e->esz))) return rc;
   if ((rc = dalloc(e, &e->logits, (size_t)e->NS * K * V))) return rc;
+  return VC_OK;
+}
+
+// ---- the per-sequence tables of a decode step, the sampler's words and tables (and, allocated between them, the finished-row forms'
+// centred copies and row means)
+int alloc_seq_tables(vc_engine* e) {
+  const int d = e->d, K = e->K;
+  int rc;
   if ((rc = dalloc(e, &e->dec_h, (size_t)e->NS * d))) return rc;
   if ((rc = dalloc(e, &e->dec_row_seq, (size_t)e->NS))) return rc;
   if ((rc = dalloc(e, &e->dec_row_pos, (size_t)e->NS))) return rc;
   if ((rc = dalloc(e, &e->logit_row, (size_t)e->NS))) return rc;
   if ((rc = dalloc(e, &e->st, (size_t)e->NS))) return rc;
   if ((rc = dalloc(e, &e->st_fin, (size_t)e->NS))) return rc;
-  {
-    if ((rc = dalloc(e, &e->hqA, (size_t)VC_ROWS * d * e->esz))) return rc;
-    if ((rc = dalloc(e, &e->hqB, (size_t)VC_ROWS * d * e->esz))) return rc;
-    if ((rc = dalloc(e, &e->row_mu[0], (size_t)VC_ROWS))) return rc;
-    if ((rc = dalloc(e, &e->row_mu[1], (size_t)VC_ROWS))) return rc;
-    if ((rc = dalloc(e, &e->mu_zero, (size_t)VC_ROWS))) return rc;
-    HIPCHK(e, hipMemset(e->row_mu[0], 0, VC_ROWS * 4));
-    HIPCHK(e, hipMemset(e->row_mu[1], 0, VC_ROWS * 4));
-    HIPCHK(e, hipMemset(e->mu_zero, 0, VC_ROWS * 4));
-  }
-  if ((rc = dalloc(e, &e->n_active, (size_t)4))) return rc;
-  if ((rc = dalloc(e, &e->step_ctr, (size_t)4))) return rc;
-  HIPCHK(e, hipMemset(e->step_ctr, 0, 4));
-  if ((rc = dalloc(e, &e->err_flag, (size_t)4))) return rc;
-  if ((rc = dalloc(e, &e->one, (size_t)4))) return rc;
-  if ((rc = dalloc(e, &e->share_len, (size_t)4))) return rc;
-  HIPCHK(e, hipMemset(e->share_len, 0, 16));
+  if ((rc = dalloc(e, &e->hqA, (size_t)VC_ROWS * d * e->esz))) return rc;
+  if ((rc = dalloc(e, &e->hqB, (size_t)VC_ROWS * d * e->esz))) return rc;
+  if ((rc = dalloc0(e, &e->row_mu[0], (size_t)VC_ROWS, VC_ROWS * 4))) return rc;
+  if ((rc = dalloc0(e, &e->row_mu[1], (size_t)VC_ROWS, VC_ROWS * 4))) return rc;
+  if ((rc = dalloc0(e, &e->mu_zero, (size_t)VC_ROWS, VC_ROWS * 4))) return rc;
+  if ((rc = dalloc0(e, &e->n_active, (size_t)4, 16))) return rc;
+  if ((rc = dalloc0(e, &e->step_ctr, (size_t)4, 4))) return rc;
+  if ((rc = dalloc0(e, &e->err_flag, (size_t)4, 16))) return rc;
+  if ((rc = dalloc(e, &e->one, (size_t)4))) return rc;             // (set below)
+  if ((rc = dalloc0(e, &e->share_len, (size_t)4, 16))) return rc;
   if ((rc = dalloc(e, &e->samp, (size_t)e->NS * (VC_MAX_CODEBOOKS + 2)))) return rc;
   if ((rc = dalloc(e, &e->cond, (size_t)e->NS))) return rc;
   if ((rc = dalloc(e, &e->amax, (size_t)e->NS))) return rc;
-  if ((rc = dalloc(e, &e->dbg_ts, (size_t)64))) return rc;
-  HIPCHK(e, hipMemset(e->dbg_ts, 0, 64 * 8));
+  if ((rc = dalloc0(e, &e->dbg_ts, (size_t)64, 64 * 8))) return rc;
   e->gen_cap = e->S_max;
   if ((rc = dalloc(e, &e->gen, (size_t)e->B_max * e->gen_cap * K))) return rc;
-  HIPCHK(e, hipMemset(e->err_flag, 0, 16));
-  HIPCHK(e, hipMemset(e->n_active, 0, 16));
   { const int one[4] = {1, 1, 1, 1}; HIPCHK(e, hipMemcpy(e->one, one, 16, hipMemcpyHostToDevice)); }
+  return VC_OK;
+}
+
+// ---- pinned staging of the calls; the decode sessions' tables and staging
+int alloc_session_tables(vc_engine* e) {
+  int rc;
   HIPCHK(e, hipHostMalloc((void**)&e->h_st, sizeof(SeqState) * e->NS));
   HIPCHK(e, hipHostMalloc((void**)&e->h_st2, sizeof(SeqState) * e->NS));
   HIPCHK(e, hipHostMalloc((void**)&e->h_flag, 64));
@@ -1663,33 +1700,57 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
   HIPCHK(e, hipHostMalloc((void**)&e->h_dyn, sizeof(SampleDyn)));
   HIPCHK(e, hipHostMalloc((void**)&e->h_rec, sizeof(int) * VC_SESS_REC * e->NS));
   memset(e->h_rec, 0, sizeof(int) * VC_SESS_REC * e->NS);
-  if ((rc = dalloc(e, &e->seed_tab, (size_t)e->NS))) return rc;
-  if ((rc = dalloc(e, &e->samp_tab, (size_t)e->NS))) return rc;
-  HIPCHK(e, hipMemset(e->samp_tab, 0, sizeof(int) * e->NS));
-  if ((rc = dalloc(e, &e->batch_id, (size_t)4))) return rc;
-  if ((rc = dalloc(e, &e->row_base, (size_t)4))) return rc;
-  if ((rc = dalloc(e, &e->adm_slot, (size_t)e->NS))) return rc;
-  if ((rc = dalloc(e, &e->prompt_err, (size_t)e->NS))) return rc;
-  if ((rc = dalloc(e, &e->sess_gather, (size_t)e->NS))) return rc;
-  if ((rc = dalloc(e, &e->ctl_tab, (size_t)e->NS))) return rc;
-  if ((rc = dalloc(e, &e->adm_ctl, (size_t)e->NS))) return rc;
-  if ((rc = dalloc(e, &e->adm_st, (size_t)e->NS))) return rc;
-  HIPCHK(e, hipMemset(e->ctl_tab, 0, sizeof(vc_request_ctl) * e->NS));
-  HIPCHK(e, hipMemset(e->adm_ctl, 0, sizeof(vc_request_ctl) * e->NS));
-  HIPCHK(e, hipMemset(e->adm_st, 0, sizeof(SeqState) * e->NS));
-  HIPCHK(e, hipHostMalloc((void**)&e->h_adm_st, sizeof(SeqState) * e->NS * VC_ADM_STAGES));
-  HIPCHK(e, hipHostMalloc((void**)&e->h_adm_ctl, sizeof(vc_request_ctl) * e->NS * VC_ADM_STAGES));
-  HIPCHK(e, hipMemset(e->seed_tab, 0, sizeof(uint64_t) * e->NS));
-  HIPCHK(e, hipMemset(e->batch_id, 0, 16));
-  HIPCHK(e, hipMemset(e->row_base, 0, 16));
-  HIPCHK(e, hipMemset(e->adm_slot, 0, sizeof(int) * e->NS));
-  HIPCHK(e, hipMemset(e->prompt_err, 0, sizeof(int) * e->NS));
+  const size_t NS = e->NS;
+  if ((rc = dalloc0(e, &e->seed_tab, NS, sizeof(uint64_t) * NS))) return rc;
+  if ((rc = dalloc0(e, &e->samp_tab, NS, sizeof(int) * NS))) return rc;
+  if ((rc = dalloc0(e, &e->batch_id, (size_t)4, 16))) return rc;
+  if ((rc = dalloc0(e, &e->row_base, (size_t)4, 16))) return rc;
+  if ((rc = dalloc0(e, &e->adm_slot, NS, sizeof(int) * NS))) return rc;
+  if ((rc = dalloc0(e, &e->prompt_err, NS, sizeof(int) * NS))) return rc;
+  if ((rc = dalloc(e, &e->sess_gather, NS))) return rc;
+  if ((rc = dalloc0(e, &e->ctl_tab, NS, sizeof(vc_request_ctl) * NS))) return rc;
+  if ((rc = dalloc0(e, &e->adm_ctl, NS, sizeof(vc_request_ctl) * NS))) return rc;
+  if ((rc = dalloc0(e, &e->adm_st, NS, sizeof(SeqState) * NS))) return rc;
+  HIPCHK(e, hipHostMalloc((void**)&e->h_adm_st, sizeof(SeqState) * NS * VC_ADM_STAGES));
+  HIPCHK(e, hipHostMalloc((void**)&e->h_adm_ctl, sizeof(vc_request_ctl) * NS * VC_ADM_STAGES));
   if ((rc = dalloc(e, &e->d_dyn, (size_t)1))) return rc;
+  return VC_OK;
+}
+
+// ---- events and streams
+int make_events_streams(vc_engine* e) {
   for (auto& ev : e->ev_pace) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   for (auto& ev : e->ev) HIPCHK(e, hipEventCreate(&ev));
   // a blocking stream: implicitly ordered after work the caller queued on the null stream
   HIPCHK(e, hipStreamCreate(&e->own_stream));
   HIPCHK(e, hipStreamCreateWithFlags(&e->side_stream, hipStreamNonBlocking));
+  return VC_OK;
+}
+
+}  // namespace
+
+extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
+  if (!e) return VC_EINVAL;
+  if (e->finalized) return fail(e, VC_ESTATE, "already finalized");
+  if (compute_dtype != VC_DTYPE_BF16 && compute_dtype != VC_DTYPE_F32) return fail(e, VC_EINVAL, "compute dtype must be bf16 or f32");
+  if (e->w8_req && compute_dtype != VC_DTYPE_BF16) return fail(e, VC_EINVAL, "vc_request_w8 was made, and the w8 form exists for bf16 engines only");
+  if (e->kv8_req && compute_dtype != VC_DTYPE_BF16) return fail(e, VC_EINVAL, "vc_request_kv8 was made, and the kv8 form exists for bf16 engines only");
+  HIPCHK(e, hipSetDevice(e->device));
+  e->dtype = compute_dtype;
+  e->esz = compute_dtype == VC_DTYPE_BF16 ? 2 : 4;
+  int rc;
+  if ((rc = load_embeddings(e)) || (rc = load_position_table(e))) return rc;
+  decide_images(e);
+  e->layers.resize(e->L);
+  for (int l = 0; l < e->L; ++l)
+    if ((rc = pack_layer(e, l))) return rc;
+  if (e->kv8_req && (rc = upload_kv8_table(e))) return rc;
+  if ((rc = pack_heads(e))) return rc;
+  HIPCHK(e, hipDeviceSynchronize());
+  for (auto& kv : e->raw) if (kv.second.dev) (void)hipFree(kv.second.dev);
+  e->raw.clear();
+  make_plans(e);
+  if ((rc = alloc_pass_arenas(e)) || (rc = alloc_seq_tables(e)) || (rc = alloc_session_tables(e)) || (rc = make_events_streams(e))) return rc;
   // ---- options: the VC_* environment variables preset them, vc_set_option changes them at run time
   if ((rc = apply_env_presets(e))) return rc;
   HIPCHK(e, hipDeviceSynchronize());
@@ -2496,18 +2557,11 @@ extern "C" int vc_session_submit_edit(vc_engine* e, const int64_t* x_dev, int Lx
   return session_enqueue(*tp, std::move(r), ticket);
 }
 
-extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* n_finished, int* idle) {
-  if (!e) return VC_EINVAL;
-  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
-  if (!n_finished || !idle || cap < 0 || (cap > 0 && !tickets_out)) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_advance");
-  HIPCHK(e, hipSetDevice(e->device));
-  Session& t = *e->sess;
-  if (t.broken) return session_broken(e, t);
-  hipStream_t s = t.s;
-  const int G = t.L.G;
-  *n_finished = 0; *idle = 0;
-  t.stats[SS_TURNS] += 1;
-  // ---- 1, 2: the older batch in flight, and what it (or an earlier one) retired
+namespace {
+
+// The steps of a turn, in the order vc_session_advance takes them (numbered as in the comment above Session).
+// ---- 1, 2: the older batch in flight, and what it (or an earlier one) retired
+int turn_retire(vc_engine* e, Session& t, int* tickets_out, int cap, int* n_finished) {
   int known = t.run_start - 1;
   if (t.batch - t.run_start >= 2) {
     HIPCHK(e, hipEventSynchronize(e->ev_pace[t.batch & 1]));
@@ -2516,9 +2570,12 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
   t.known = std::max(t.known, known);
   session_note_retired(e, t, known, tickets_out, cap, n_finished);
   session_read_timers(t, known, false);
-  // ---- the cancels made since the last turn: the slots of the cancelled tickets' rows whose records are still out, one table for
-  // session_cancel_k (queued in step 4, in front of session_turn_k).  Their slots stay taken until those records have been read
-  SessCancelArgs ca;
+  return VC_OK;
+}
+
+// ---- the cancels made since the last turn: the slots of the cancelled tickets' rows whose records are still out, one table for
+// session_cancel_k (queued in step 4, in front of session_turn_k).  Their slots stay taken until those records have been read
+void turn_cancels(Session& t, SessCancelArgs& ca) {
   memset(&ca, 0, sizeof ca);
   for (int slot = 0; slot < t.max_live; ++slot) {
     const int ticket = t.slot_ticket[slot];
@@ -2530,23 +2587,34 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
     if (m >= 0 && !r.mdone[m]) ca.slot[ca.n++] = slot;
   }
   for (auto& kv_req : t.reqs) if (kv_req.second.cancelled) kv_req.second.cancel_queued = true;
-  // ---- 3: admission, FIFO, as many as have a free slot
+}
+
+// What step 3 admits on the host and step 4 queues on the decode stream.
+struct Admission {
   SessTurnArgs ta;
-  memset(&ta, 0, sizeof ta);
-  // this turn's staging buffers (see the comment above Session: the host last wrote them VC_ADM_STAGES turns ago)
-  SeqState* const h_adm_st = e->h_adm_st + (size_t)(t.batch % VC_ADM_STAGES) * e->NS;
-  vc_request_ctl* const h_adm_ctl = e->h_adm_ctl + (size_t)(t.batch % VC_ADM_STAGES) * e->NS;
+  SessGroupArgs ga;
+  CopyKvArgs kv;            // the siblings' prompt K/V: one (source, destination) entry per sibling, every group of the turn in one table
   std::vector<PromptArgs> pas;
   std::vector<int> slots;
-  const int live_before = t.live;
+  int n_req = 0;
+  SeqState* h_adm_st = nullptr;           // this turn's staging buffers (set by turn_admit)
+  vc_request_ctl* h_adm_ctl = nullptr;
+};
+
+// ---- 3: admission, FIFO, as many as have a free slot
+void turn_admit(vc_engine* e, Session& t, Admission& a) {
+  SessTurnArgs& ta = a.ta;
+  SessGroupArgs& ga = a.ga;
+  CopyKvArgs& kv = a.kv;
+  memset(&ta, 0, sizeof ta);
+  // this turn's staging buffers (see the comment above Session: the host last wrote them VC_ADM_STAGES turns ago)
+  SeqState* const h_adm_st = a.h_adm_st = e->h_adm_st + (size_t)(t.batch % VC_ADM_STAGES) * e->NS;
+  vc_request_ctl* const h_adm_ctl = a.h_adm_ctl = e->h_adm_ctl + (size_t)(t.batch % VC_ADM_STAGES) * e->NS;
   // strictly FIFO: the head of the queue is admitted by the first turn that has a free slot for EACH of its samples - the lowest free
   // slots, which need not be consecutive -, and nothing behind it overtakes it (a best-of-N request waiting for slots blocks the line).
   // A request of one sample takes the lowest free slot, as ever.
-  SessGroupArgs ga;
   memset(&ga, 0, sizeof ga);
-  CopyKvArgs kv;            // the siblings' prompt K/V: one (source, destination) entry per sibling, every group of the turn in one table
   memset(&kv, 0, sizeof kv);
-  int n_req = 0;
   while (!t.fifo.empty()) {
     const int id = t.fifo.front();
     SessReq& r = t.reqs[id];
@@ -2556,7 +2624,7 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
       if (t.slot_ticket[slot] < 0) mine.push_back(slot);
     if ((int)mine.size() < N) break;
     t.fifo.pop_front();
-    n_req += 1;
+    a.n_req += 1;
     r.slot = mine[0]; r.state = 1; r.adm_batch = t.batch;
     r.slots = mine; r.mdone.assign(N, 0); r.members_left = N; r.kept = -1;
     // the request's first state and its prompt, by kind: what tts_prepare / vc_edit_multi lay down for a sequence of a blocking call
@@ -2570,8 +2638,8 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
       st0 = tts_request(e, r.job, 0, nullptr, &pa);
     }
     if (N > 1) st0.group = id;                              // the group of the keep decision is the request (advance_phase)
-    pas.push_back(pa);                                      // ONE prefill per request, into its first slot
-    slots.push_back(mine[0]);
+    a.pas.push_back(pa);                                    // ONE prefill per request, into its first slot
+    a.slots.push_back(mine[0]);
     for (int m = 0; m < N; ++m) {                           // one row per sample, consecutive and in sample order
       const int slot = mine[m];
       t.slot_ticket[slot] = id;
@@ -2589,29 +2657,38 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
       for (int i = 0; i < VC_SESS_REC; ++i) rec[i] = 0;
     }
   }
-  const int n_new = ta.n_new;                               // ROWS admitted this turn
-  if (t.live + n_new == 0) {
-    // nothing to decode: what is still queued is steps without a live sequence.  Wait for them and queue nothing more; a later
-    // submit (or the fetch that frees a slot for a pending request) restarts the loop.
-    if (t.batch > t.run_start) {
-      HIPCHK(e, hipStreamSynchronize(s));
-      t.known = t.batch - 1;
-      session_note_retired(e, t, t.batch - 1, tickets_out, cap, n_finished);
-      session_read_timers(t, t.batch - 1, true);
-      t.run_start = t.batch;
-      if (int rc = check_err_flag(e, s)) return rc;        // (session_turn_k's row check; the stream is idle, so this costs nothing)
-    }
-    *idle = t.fifo.empty() ? 1 : 0;
-    return VC_OK;
+}
+
+// nothing to decode: what is still queued is steps without a live sequence.  Wait for them and queue nothing more; a later
+// submit (or the fetch that frees a slot for a pending request) restarts the loop.
+int turn_idle(vc_engine* e, Session& t, int* tickets_out, int cap, int* n_finished, int* idle) {
+  hipStream_t s = t.s;
+  if (t.batch > t.run_start) {
+    HIPCHK(e, hipStreamSynchronize(s));
+    t.known = t.batch - 1;
+    session_note_retired(e, t, t.batch - 1, tickets_out, cap, n_finished);
+    session_read_timers(t, t.batch - 1, true);
+    t.run_start = t.batch;
+    if (int rc = check_err_flag(e, s)) return rc;        // (session_turn_k's row check; the stream is idle, so this costs nothing)
   }
-  // ---- 4: prefill of the admitted requests, the turn kernel, their first sample, the next batch.  The requests are admitted on the
-  // host already: if anything below fails the session is marked broken (see Session.broken)
-  const int rc4 = [&]() -> int {
+  *idle = t.fifo.empty() ? 1 : 0;
+  return VC_OK;
+}
+
+// ---- 4: prefill of the admitted requests, the turn kernel, their first sample, the next batch
+int turn_queue(vc_engine* e, Session& t, Admission& a, SessCancelArgs& ca) {
+  SessTurnArgs& ta = a.ta;
+  SessGroupArgs& ga = a.ga;
+  CopyKvArgs& kv = a.kv;
+  hipStream_t s = t.s;
+  const int G = t.L.G;
+  const int n_new = ta.n_new;                               // ROWS admitted this turn
+  const int live_before = t.live;
   const int w = session_width(t, t.live + n_new);
   const int ei = t.batch & 3;
   if (n_new > 0) {
     HIPCHK(e, hipEventRecord(t.ev_adm[ei][0], s));
-    int rc = prefill_batch(e, pas, slots, s, true);
+    int rc = prefill_batch(e, a.pas, a.slots, s, true);
     if (rc) return rc;
     if (kv.n_ent > 0) {
       // prefill once, replicate: prompt positions [0, Lx + T + 1) of each group's first slot to its siblings' slots, one launch per
@@ -2620,8 +2697,8 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
       kv.n_dst = kv.n_ent;
       if ((rc = replicate_kv(e, kv, s))) return rc;
     }
-    HIPCHK(e, hipMemcpyAsync(e->adm_st, h_adm_st, sizeof(SeqState) * n_new, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(e->adm_ctl, h_adm_ctl, sizeof(vc_request_ctl) * n_new, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->adm_st, a.h_adm_st, sizeof(SeqState) * n_new, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->adm_ctl, a.h_adm_ctl, sizeof(vc_request_ctl) * n_new, hipMemcpyHostToDevice, s));
   }
   ta.st = e->st; ta.dec_h = e->dec_h; ta.row_seq = e->dec_row_seq; ta.row_pos = e->dec_row_pos; ta.logit_row = e->logit_row;
   ta.err = e->err_flag; ta.n_active = e->n_active; ta.batch_id = e->batch_id; ta.row_base = e->row_base; ta.adm_slot = e->adm_slot;
@@ -2646,15 +2723,35 @@ extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* 
     HIPCHK(e, vc_launch_sample_session(t.L.sa, true, n_new, t.grouped, s));
     HIPCHK(e, hipEventRecord(t.ev_adm[ei][1], s));
     t.ev_turn[ei] = t.batch;
-    t.stats[SS_ADMITTED] += n_req;                                     // requests; the row sums SS_LIVE_ROWS, SS_LAUNCHED_ROWS count every sample's rows
-    if (live_before > 0) t.stats[SS_ADMITTED_LIVE] += n_req;
+    t.stats[SS_ADMITTED] += a.n_req;                                   // requests; the row sums SS_LIVE_ROWS, SS_LAUNCHED_ROWS count every sample's rows
+    if (live_before > 0) t.stats[SS_ADMITTED_LIVE] += a.n_req;
     t.live += n_new;
   }
   if (const int rc = t.L.queue_batch(t.batch & 1)) return rc;
   t.batch += 1;
   t.stats[SS_LAUNCHED_ROWS] += (long long)w * G;
   return VC_OK;
-  }();
+}
+
+}  // namespace
+
+extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* n_finished, int* idle) {
+  if (!e) return VC_EINVAL;
+  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
+  if (!n_finished || !idle || cap < 0 || (cap > 0 && !tickets_out)) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_advance");
+  HIPCHK(e, hipSetDevice(e->device));
+  Session& t = *e->sess;
+  if (t.broken) return session_broken(e, t);
+  *n_finished = 0; *idle = 0;
+  t.stats[SS_TURNS] += 1;
+  if (const int rc = turn_retire(e, t, tickets_out, cap, n_finished)) return rc;
+  SessCancelArgs ca;
+  turn_cancels(t, ca);
+  Admission a;
+  turn_admit(e, t, a);
+  if (t.live + a.ta.n_new == 0) return turn_idle(e, t, tickets_out, cap, n_finished, idle);
+  // the requests are admitted on the host already: if anything of the queued work fails the session is marked broken (see Session.broken)
+  const int rc4 = turn_queue(e, t, a, ca);
   if (rc4) { t.broken = true; t.broken_msg = e->err; }
   return rc4;
 }
