@@ -150,6 +150,7 @@ const char* vc_version(void);
  *                  rows; the pass's own rows and every prefill pass stay on the bf16 cache.  One more launch per pass (kv8_pack_k)
  *                  quantises the rows the pass wrote, whatever the option's value.  This CHANGES values: 3 mantissa bits are left of
  *                  a cached value.  The option text ends in |kv8=<v> on such an engine only.  Resident memory: K/V x 1.5 + 2 / head_dim
+ *                  An engine that called vc_request_kv8c runs the centred forms of the same launches (K codes of k - c, below).
  * What an option may change: nothing in the exact fp32 mode's greedy tokens (tests/test_gpu_options.py, test_gpu_one_row.py); in bf16
  * mode the forms that re-order sums or round at another place ("finished_rows", "fr_pair", "att_p16", "hq", "fr_one", "qkv_p8", "attn_fast",
  * "qkv16", "wide_heads", "wide_gemm") move head logits by bf16 rounding (tests allow 0.25 absolute), so top-k SAMPLED tokens can differ between option
@@ -181,6 +182,14 @@ int vc_request_w8(vc_engine* e, int mask);
  * older than the pass from it (option "kv8" above).  bf16 only: vc_finalize_weights with VC_DTYPE_F32 after the request returns
  * VC_EINVAL.  An engine without the request allocates and launches nothing more and behaves as before. */
 int vc_request_kv8(vc_engine* e);
+/* vc_request_kv8 with CENTRED K (the same call order and dtype rules; implies it).  Next to the E4M3 copy the engine keeps, per layer,
+ * cache slot and head, a bf16 centre c[head_dim] - the mean K row of the prefill pass that wrote the slot's position 0 (csrc/vc_kv8.h
+ * states the contract; voicecraft_amd/quant.py kv8c_* restates it) - found by one more launch in front of the packer on prefill passes
+ * (kv8c_centre_k).  K codes stand for k - c, the decode attention adds q . c to every 8-bit score: softmax does not see the common
+ * offset of the K rows, which is where the plain grid loses its bits on peaked attention.  V is as in the plain mode.
+ * Option "kv8" keeps its 0 / 1 meaning; the option text ends in |kv8c=1 on such an engine only (there is no option "kv8c").  vc_debug_read: "kcentre_<l>" bf16
+ * [max_seqs][H][head_dim], "kcentre_rows" int32 [max_seqs] (n0 per slot).  Resident memory: + max_seqs x d_model x 2 bytes per layer. */
+int vc_request_kv8c(vc_engine* e);
 
 /* ---- TTS: VoiceCraft.inference_tts (models/voicecraft.py:908-1153) and, with
  * n_samples > 1, VoiceCraft.inference_tts_batch (:1156-1439, best-of-N: the sample
@@ -504,9 +513,41 @@ typedef struct vc_debug_attn8_args {
   int32_t rps, pack;
 } vc_debug_attn8_args;
 int vc_debug_attn8(const vc_debug_attn8_args* a, void* stream);
+/* vc_debug_attn8 for the centred mode (vc_request_kv8c; no engine needed).  centre: bf16 [n_seqs][H][hd], 16-byte aligned.
+ *   mode = 0: ONE launch of rows_attn_k in its centred kv8 form: as vc_debug_attn8's pack = 0, and every score of a position read from the E4M3
+ *     arrays gains q . centre[row_seq[r]][h].
+ *   mode = 1: ONE launch of the centred packer: as vc_debug_attn8's pack = 1, the K codes and shifts being those of bf16_rne(k - centre[seq][h]);
+ *     the V half is the plain one.  (base8.pack is not read.)
+ *   mode = 2: ONE launch of the centre kernel over the rows (row_seq, row_pos) as a PREFILL pass's: for every slot < n_seqs whose position 0
+ *     is among the rows, centre[slot] = the mean of its K rows in the pass (bf16 kcache; fp32 sums, rounded to bf16) and n0[slot] = their
+ *     number; while *share_len > 0 every slot with a row in the pass takes sequence 0's.  Everything else stays.  Only kcache, the row
+ *     tables, n_active and share_len of the base are read.
+ * VC_EINVAL, before the device is touched: what vc_debug_attn8 refuses, a mode outside 0..2, a null or misaligned centre; mode 2: a null
+ * n0, n_seqs outside 1..64, more than 2048 rows. */
+typedef struct vc_debug_attn8c_args {
+  vc_debug_attn8_args base8;
+  void* centre;
+  void* n0;          /* int32 [n_seqs], mode 2 */
+  int32_t mode, n_seqs;
+} vc_debug_attn8c_args;
+int vc_debug_attn8c(const vc_debug_attn8c_args* a, void* stream);
+/* Host only: what the kv8 options add to a pass - the function the engine's passes follow.  request: 0 none, 1 vc_request_kv8,
+ * 2 vc_request_kv8c; kv8: the option's value; rps: rows per sequence of a decode pass, 0 = a prefill pass; rows_attn: the pass's
+ * attention is rows_attn_k.  out[0] = the form of the attention launches (VC_KV8_ATTN_*), out[1] = the number of launches queued behind
+ * the last layer, out[2], out[3] = those launches in order (VC_KV8_LAUNCH_*, 0 = none).  VC_EINVAL: a request outside 0..2, rps < 0. */
+#define VC_KV8_ATTN_PLAIN 0
+#define VC_KV8_ATTN_E4M3 1
+#define VC_KV8_ATTN_CENTRED 2
+#define VC_KV8_LAUNCH_CENTRE 1
+#define VC_KV8_LAUNCH_PACK 2
+#define VC_KV8_LAUNCH_PACK_CENTRED 3
+int vc_debug_kv8_plan(int request, int kv8, int rps, int rows_attn, int32_t out[4]);
 /* Host only: the kv8 quantiser (csrc/vc_kv8.h, the code the packer runs) on n_rows rows of hd bf16 values: codes uint8 [n_rows][hd],
  * shift int8 [n_rows].  The CPU tests hold it against voicecraft_amd/quant.py kv8_quantize_rows. */
 int vc_kv8_quantize_host(const uint16_t* bf16_rows, int n_rows, int hd, uint8_t* codes, int8_t* shift);
+/* Host only: the centred quantiser (csrc/vc_kv8.h vc_kv8c_quantize_row) on n_rows K rows of hd bf16 values against ONE centre of hd bf16
+ * values.  The CPU tests hold it against voicecraft_amd/quant.py kv8c_quantize_rows. */
+int vc_kv8c_quantize_host(const uint16_t* bf16_rows, const uint16_t* centre, int n_rows, int hd, uint8_t* codes, int8_t* shift);
 /* Diagnosis of the BOX, not of the model (no engine needed): ONE thread walks `hops` dependent loads over a ring of `bytes` bytes and
  * stamps the per-XCD shader clock and the chip-wide 100 MHz counter around the walk.  res[0] = ns per dependent load as a lone
  * workgroup on an otherwise idle chip sees it, res[1] = the shader clock (MHz) that workgroup really ran at.  The one-sequence

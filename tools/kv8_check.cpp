@@ -1,6 +1,9 @@
 // Host check of the K/V cache's 8-bit grid (voicecraft_amd/csrc/vc_kv8.h): build with the host compiler and
-// -fsanitize=address,undefined, run by tests/test_kv8_cpu.py.  Prints "ok <rows> <values>" and exits 0, or says what broke.
+// -fsanitize=address,undefined, run by tests/test_kv8_cpu.py.  Prints "ok <rows> <values>" (with "centred": "ok <rows> <values> centred
+// <centred rows>") and exits 0, or says what broke.
 // The reference here shares nothing with the header: the 127 E4M3 magnitudes by enumeration, the nearest one by search over doubles.
+// With the argument "centred" the rows also go through vc_kv8c_quantize_row against centres of several sizes: the centred row is
+// restated in doubles (the exact difference, rounded to fp32 by the cast and to bf16 by nearbyint on the scaled mantissa).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -28,7 +31,7 @@ static int nearest_code(double x) {
   return best;
 }
 
-static long n_rows = 0, n_vals = 0;
+static long n_rows = 0, n_vals = 0, n_centred = 0;
 
 static int check_row(const std::vector<uint16_t>& row) {
   const int hd = (int)row.size();
@@ -63,7 +66,39 @@ static int check_row(const std::vector<uint16_t>& row) {
   return 0;
 }
 
-int main() {
+// bf16_rne(float(k) - float(c)), restated: the difference of two bf16 numbers is exact in a double
+static uint16_t centred_value(uint16_t k, uint16_t c) {
+  const float d = (float)(bf16_value(k) - bf16_value(c));      // the cast rounds to nearest even: what the fp32 subtraction gives
+  if (d == 0.0f) { uint32_t u; std::memcpy(&u, &d, 4); return (uint16_t)(u >> 16); }
+  int e;
+  const double m = std::frexp((double)d, &e);                  // |m| in [0.5, 1)
+  double r;
+  if (e < -125) r = std::ldexp(std::nearbyint(std::ldexp((double)d, 133)), -133);      // a bf16 denormal: steps of 2^-133
+  else r = std::ldexp(std::nearbyint(std::ldexp(m, 8)), e - 8);
+  const float f = (float)r;
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  if (u & 0xffffu) { std::printf("centred value not a bf16 number\n"); std::exit(1); }
+  return (uint16_t)(u >> 16);
+}
+
+static int check_centred(const std::vector<uint16_t>& row, const std::vector<uint16_t>& centre) {
+  const int hd = (int)row.size();
+  std::vector<uint16_t> moved(hd);
+  for (int j = 0; j < hd; ++j) {
+    moved[j] = centred_value(row[j], centre[j]);
+    if ((moved[j] & 0x7f80) == 0x7f80) return 0;               // an overflow of the difference: no cached row does that
+  }
+  std::vector<uint8_t> a(hd), b(hd);
+  const int sa = vc_kv8c_quantize_row(row.data(), centre.data(), hd, a.data());
+  const int sb = vc_kv8_quantize_row(moved.data(), hd, b.data());
+  if (sa != sb || a != b) { std::printf("centred row: shift %d / %d or codes differ from the restated row's\n", sa, sb); return 1; }
+  ++n_centred;
+  return check_row(moved);
+}
+
+int main(int argc, char** argv) {
+  const bool centred = argc > 1 && !std::strcmp(argv[1], "centred");
   for (int c = 0; c < 127; ++c) {
     const int E = c >> 3, M = c & 7;
     mags[c] = E == 0 ? std::ldexp((double)M, -9) : std::ldexp((double)(8 + M), E - 10);
@@ -83,6 +118,13 @@ int main() {
         }
         row[hd - 1] = 0x8000;      // -0
         if (check_row(row)) return 1;
+        if (centred)               // centres of nothing, of the rows' own size, of 32 times it, and one equal to the row
+          for (int kind = 0; kind < 4; ++kind) {
+            std::vector<uint16_t> c(hd, 0);
+            for (int j = 0; j < hd && kind; ++j)
+              c[j] = kind == 3 ? row[j] : (uint16_t)(((next() & 1) << 15) | ((base - 2 + (kind == 2 ? 5 : 0) - (int)(next() % 3)) << 7) | (next() & 0x7f));
+            if (check_centred(row, c)) return 1;
+          }
       }
     // rows of zeros, of bf16 denormals, of the smallest and the largest normal numbers, and ties at every binade
     if (check_row(std::vector<uint16_t>(hd, 0))) return 1;
@@ -96,6 +138,7 @@ int main() {
       if (check_row(r)) return 1;
     }
   }
-  std::printf("ok %ld %ld\n", n_rows, n_vals);
+  if (centred) std::printf("ok %ld %ld centred %ld\n", n_rows, n_vals, n_centred);
+  else std::printf("ok %ld %ld\n", n_rows, n_vals);
   return 0;
 }

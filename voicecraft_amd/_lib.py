@@ -47,6 +47,11 @@ class DebugAttn8Args(C.Structure):
                 ("rps", C.c_int32), ("pack", C.c_int32)]
 
 
+class DebugAttn8cArgs(C.Structure):
+    """vc_debug_attn8c_args: vc_debug_attn8_args, two device pointers, two int32 (176 bytes)."""
+    _fields_ = [("base8", DebugAttn8Args), ("centre", C.c_void_p), ("n0", C.c_void_p), ("mode", C.c_int32), ("n_seqs", C.c_int32)]
+
+
 # name -> (restype, argtypes); the single source of truth the symbol test checks against the header
 PROTOTYPES = {
     "vc_create": (C.c_int, [C.POINTER(ModelCfg), C.c_int, C.POINTER(C.c_void_p)]),
@@ -58,6 +63,7 @@ PROTOTYPES = {
     "vc_finalize_weights": (C.c_int, [C.c_void_p, C.c_int]),
     "vc_request_w8": (C.c_int, [C.c_void_p, C.c_int]),
     "vc_request_kv8": (C.c_int, [C.c_void_p]),
+    "vc_request_kv8c": (C.c_int, [C.c_void_p]),
     "vc_tts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(SampleCfg), C.c_int,
                          C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_int,
                          C.POINTER(C.c_int), C.c_void_p]),
@@ -100,6 +106,8 @@ PROTOTYPES = {
     "vc_debug_attn": (C.c_int, [C.POINTER(DebugAttnArgs), C.c_void_p]),
     "vc_debug_attn8": (C.c_int, [C.POINTER(DebugAttn8Args), C.c_void_p]),
     "vc_kv8_quantize_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vc_debug_attn8c": (C.c_int, [C.POINTER(DebugAttn8cArgs), C.c_void_p]),
+    "vc_kv8c_quantize_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vc_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int,
                           C.POINTER(C.c_int32), C.POINTER(SampleCfg), C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                           C.POINTER(C.c_int), C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
@@ -110,6 +118,7 @@ PROTOTYPES = {
     "vc_pattern_shift": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "vc_pattern_revert": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "vc_pattern_unshift": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vc_debug_kv8_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "vc_debug_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "vc_box_probe": (C.c_int, [C.c_longlong, C.c_int, C.POINTER(C.c_float), C.c_void_p]),
     "vc_debug_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),

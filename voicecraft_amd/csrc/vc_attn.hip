@@ -68,11 +68,15 @@ __device__ __forceinline__ float kv8_scale(uint32_t b) { return __uint_as_float(
 // score, the V row's the probability weight (one 2-byte request per visit brings both).  Positions lo..pos (at most `rps` of them: this
 // pass's own rows, written by its QKV launch and packed only behind the pass) come from the bf16 cache: the last wave of the split that
 // holds them takes them as one more visit, requested together with the first batch.
-template <typename WT, bool NT, bool FAST, bool P16 = false, bool KV8 = false>
+// KC ("kv8c", an engine with vc_request_kv8c; the contract is in vc_kv8.h): the K codes stand for k - c, c the bf16 centre of the row's
+// sequence slot and head.  A lane requests the 16 centre values of its slice right behind q's, in q's layout and in front of every
+// K/V request; q . c is one dot product and one group sum per wave, added to every 8-bit score.  The tail visit is the plain one.
+template <typename WT, bool NT, bool FAST, bool P16 = false, bool KV8 = false, bool KC = false>
 __global__ __attribute__((amdgpu_flat_work_group_size(1, 64 * VC_ATT_WAVES), amdgpu_waves_per_eu(KV8 ? 4 : 0)))      // KV8: two workgroups per CU
 void rows_attn_k(const AttnArgs a) {
   static_assert(!P16 || sizeof(WT) == 2, "bf16 partials: bf16 mode only");
   static_assert(!KV8 || sizeof(WT) == 2, "the E4M3 cache stands next to a bf16 cache");
+  static_assert(!KC || KV8, "a centre belongs to the E4M3 cache");
   constexpr int EPL = KV8 ? 16 : WTr<WT>::EPL;
   using CT = typename std::conditional<KV8, unsigned char, WT>::type;     // what the main loop's cache holds
   constexpr int NW = VC_ATT_WAVES;
@@ -140,6 +144,11 @@ void rows_attn_k(const AttnArgs a) {
       const float4* qp = reinterpret_cast<const float4*>(a.q + (long)r * a.d + h * hd + li * EPL);
 #pragma unroll
       for (int j = 0; j < EPL / 4; ++j) qv[j] = qp[j];
+    }
+    uint4 cu[2];           // KC: the lane's 16 centre values, bf16
+    if constexpr (KC) {
+      const uint4* cp = reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(a.centre) + ((long)seq * a.H + h) * hd + li * EPL);
+      cu[0] = cp[0]; cu[1] = cp[1];
     }
     uint4 ku[4], vu[4];
     uint32_t su[4];        // KV8: the visit's shift bytes (K, V)
@@ -220,6 +229,14 @@ void rows_attn_k(const AttnArgs a) {
         if (LPR >= 8) t += dpp_f<VC_DPP_ROW_HALF_MIRROR>(t);
         return t;
       };
+      float qc = 0.f;      // KC: q . c, the same on every lane of a position group
+      if constexpr (KC) {
+        float cf[EPL];
+        unpack16<WT>(cu[0], cf); unpack16<WT>(cu[1], cf + 8);
+#pragma unroll
+        for (int j = 0; j < EPL; ++j) qc += q[j] * cf[j];
+        qc = grp_sum(qc);
+      }
       // the pass's own rows, bf16, FIRST (their registers are free again before the main loop's arithmetic; the order of positions does not
       // matter to an online softmax): one position per lane group and visit (a visit holds PPW >= 8 positions, a pass has at most rps)
       if (tail) for (int tb = t0;;) {
@@ -263,6 +280,7 @@ void rows_attn_k(const AttnArgs a) {
 #pragma unroll
           for (int j = 0; j < EPL; ++j) t += q[j] * kf[j];
           t = grp_sum(t) * kv8_scale(su[it] & 0xffu);          // the K row's shift scales the finished score
+          if constexpr (KC) t += qc;                           // ... of q . (k - c)
           vs[it] = kv8_scale(su[it] >> 8);
           sc[it] = (pp[it] < p1) ? t : -INFINITY;
           __builtin_amdgcn_sched_barrier(0);
@@ -436,6 +454,16 @@ hipError_t vc_launch_attn(const AttnArgs& a, int dtype, int rows_cap, hipStream_
     b.rps_magic = (65536 + a.rps - 1) / a.rps;
     ++vc_launch_counts[VC_LC_KV8_ATTN];
     const dim3 blk(64 * VC_ATT_WAVES);
+    if (a.centre) {     // "kv8c": the centred forms
+      ++vc_launch_counts[VC_LC_KV8C_ATTN];
+#define VC_ATTN8C_GO(NT_, F_)                                                                         \
+      if (a.part16 && !a.x_out) hipLaunchKernelGGL((rows_attn_k<bf16_t, NT_, F_, true, true, true>), grid, blk, 0, s, b); \
+      else hipLaunchKernelGGL((rows_attn_k<bf16_t, NT_, F_, false, true, true>), grid, blk, 0, s, b);
+      if (a.fast) { if (a.nt) { VC_ATTN8C_GO(true, true) } else { VC_ATTN8C_GO(false, true) } }
+      else { if (a.nt) { VC_ATTN8C_GO(true, false) } else { VC_ATTN8C_GO(false, false) } }
+#undef VC_ATTN8C_GO
+      return hipGetLastError();
+    }
 #define VC_ATTN8_GO(NT_, F_)                                                                          \
     if (a.part16 && !a.x_out) hipLaunchKernelGGL((rows_attn_k<bf16_t, NT_, F_, true, true>), grid, blk, 0, s, b); \
     else hipLaunchKernelGGL((rows_attn_k<bf16_t, NT_, F_, false, true>), grid, blk, 0, s, b);
@@ -492,6 +520,8 @@ extern "C" int vc_debug_attn(const vc_debug_attn_args* p, void* stream) {
 // One launch behind every pass of an engine created for the option: the rows the pass wrote (row_seq / row_pos), every layer, K and V,
 // every head.  A lane takes 8 bf16 values (one 16-byte request), the hd / 8 lanes of a head's row agree on its largest magnitude and
 // so on its shift (vc_kv8.h), each stores its 8 code bytes and the first of them the shift byte.  grid = (lanes / 256, 2 L).
+// KC ("kv8c"): the K half meets the grid as bf16_rne(k - c), c the centre of the row's sequence slot and head (vc_kv8c_sub8).
+template <bool KC>
 __global__ __launch_bounds__(256) void kv8_pack_k(const Kv8PackArgs a) {
   if (*a.n_active == 0) return;
   const int l = blockIdx.y >> 1, kv = blockIdx.y & 1;
@@ -509,6 +539,12 @@ __global__ __launch_bounds__(256) void kv8_pack_k(const Kv8PackArgs a) {
   if (live) {
     const uint4 u = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(kv ? ly.vc : ly.kc) + at * a.hd + li * 8);
     w[0] = u.x; w[1] = u.y; w[2] = u.z; w[3] = u.w;
+    if constexpr (KC) if (!kv) {
+      const void* cen = a.centres ? a.centres[l] : a.centre;
+      const uint4 cv = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(cen) + ((long)seq * a.H + h) * a.hd + li * 8);
+      const uint32_t c4[4] = {cv.x, cv.y, cv.z, cv.w};
+      vc_kv8c_sub8(w, c4);
+    }
   }
   uint32_t amax = vc_kv8_amax8(w);
   for (int off = 1; off < LPR; off <<= 1) amax = max(amax, (uint32_t)__shfl_xor((int)amax, off, 64));
@@ -524,7 +560,96 @@ hipError_t vc_launch_kv8_pack(const Kv8PackArgs& a, hipStream_t s) {
   if (a.n_rows < 1 || a.L < 1 || a.H < 1 || (a.hd != 32 && a.hd != 64 && a.hd != 128) || !a.n_active) return hipErrorInvalidValue;
   ++vc_launch_counts[VC_LC_KV8_PACK];
   const long lanes = (long)a.n_rows * a.H * (a.hd / 8);
-  hipLaunchKernelGGL(kv8_pack_k, dim3((unsigned)((lanes + 255) / 256), 2 * a.L), dim3(256), 0, s, a);
+  const dim3 grid((unsigned)((lanes + 255) / 256), 2 * a.L);
+  if (a.centres || a.centre) {
+    ++vc_launch_counts[VC_LC_KV8C_PACK];
+    hipLaunchKernelGGL(kv8_pack_k<true>, grid, dim3(256), 0, s, a);
+  } else hipLaunchKernelGGL(kv8_pack_k<false>, grid, dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- "kv8c": the centre kernel
+// grid = (sequence slots, heads, layers), 256 threads.  First the whole block reads the pass's row table once, coalesced (most blocks
+// belong to a slot without a row in the pass and end there): does the slot have a row, which rows belong to the source slot
+// (Kv8CentreArgs: the slot itself, or sequence 0 while a prefix is shared), is the source's position 0 among them.  Then a lane takes 8
+// channels of the head (one 16-byte request per row) and the 256 / LPR lane groups take every (256 / LPR)-th row between the source's
+// first and last row; the groups' fp32 sums meet in LDS in a fixed order.
+__global__ __launch_bounds__(256) void kv8c_centre_k(const Kv8CentreArgs a) {
+  __shared__ float s_sum[256][8];
+  __shared__ int s_cnt[256];
+  __shared__ int s_first, s_last, s_has0, s_mine;
+  if (*a.n_active == 0) return;
+  const int slot = blockIdx.x, h = blockIdx.y, l = blockIdx.z;
+  const int share = *a.share_len;
+  const int src = share > 0 ? 0 : slot;
+  const int lpr_sh = a.hd_shift - 3, LPR = 1 << lpr_sh, G = 256 >> lpr_sh;
+  const int tid = threadIdx.x, g = tid >> lpr_sh, li = tid & (LPR - 1);
+  if (tid == 0) { s_first = a.n_rows; s_last = -1; s_has0 = 0; s_mine = 0; }
+  __syncthreads();
+  {
+    int first = a.n_rows, last = -1, has0 = 0, mine = 0;
+    for (int r = tid; r < a.n_rows; r += 256) {
+      const int seq = a.row_seq[r], pos = a.row_pos[r];
+      if (pos < 0 || pos >= a.S_max) continue;
+      mine |= seq == slot;
+      if (seq != src) continue;
+      first = min(first, r); last = max(last, r);
+      has0 |= pos == 0;
+    }
+    if (last >= 0) { atomicMin(&s_first, first); atomicMax(&s_last, last); }
+    if (has0) atomicOr(&s_has0, 1);
+    if (mine) atomicOr(&s_mine, 1);
+  }
+  __syncthreads();
+  if (!s_mine) return;         // the slot has no row in this pass (the same answer in every thread)
+  uint16_t* cen = reinterpret_cast<uint16_t*>(a.centres ? a.centres[l] : a.centre);
+  uint16_t* out = cen + ((long)slot * a.H + h) * a.hd + li * 8;
+  if (!s_has0) {               // the source's position 0 is not in this pass: only a shared prefix changes anything
+    if (share > 0 && slot != 0 && tid < LPR) {      // sequence 0's centre, from the pass that held its position 0
+      *reinterpret_cast<uint4*>(out) = *reinterpret_cast<const uint4*>(cen + (long)h * a.hd + li * 8);
+      if (h == 0 && l == 0 && li == 0) a.n0[slot] = a.n0[0];
+    }
+    return;
+  }
+  // the source's rows in this pass are the centre's
+  const uint16_t* kc = reinterpret_cast<const uint16_t*>(a.layers ? a.layers[l].kc : a.one.kc) + ((long)src * a.H + h) * a.S_max * a.hd + li * 8;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  int cnt = 0;
+  const int r_end = s_last;
+  for (int r = s_first + g; r <= r_end; r += G) {
+    const int seq = a.row_seq[r], pos = a.row_pos[r];
+    if (pos < 0 || pos >= a.S_max || seq != src) continue;
+    ++cnt;
+    float f[8];
+    unpack16<bf16_t>(*reinterpret_cast<const uint4*>(kc + (long)pos * a.hd), f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] += f[j];
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) s_sum[tid][j] = acc[j];
+  s_cnt[tid] = cnt;
+  __syncthreads();
+  if (tid >= LPR) return;      // lane group 0 finishes: group g's sums sit at thread g * LPR + li
+  float tot[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  int n0 = 0;
+  for (int k = 0; k < G; ++k) {
+    const int t = (k << lpr_sh) + li;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) tot[j] += s_sum[t][j];
+    n0 += s_cnt[t];
+  }
+  const float inv = 1.0f / (float)n0;
+  uint32_t w[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) w[q] = (uint32_t)f32_to_bf16(tot[2 * q] * inv) | ((uint32_t)f32_to_bf16(tot[2 * q + 1] * inv) << 16);
+  *reinterpret_cast<uint4*>(out) = uint4{w[0], w[1], w[2], w[3]};
+  if (h == 0 && l == 0 && li == 0) a.n0[slot] = n0;
+}
+hipError_t vc_launch_kv8c_centre(const Kv8CentreArgs& a, hipStream_t s) {
+  if (a.n_rows < 1 || a.L < 1 || a.H < 1 || a.n_slots < 1 || (a.hd != 32 && a.hd != 64 && a.hd != 128) || !a.n_active || !a.share_len || !a.n0 ||
+      (!a.centres && !a.centre)) return hipErrorInvalidValue;
+  ++vc_launch_counts[VC_LC_KV8C_CENTRE];
+  hipLaunchKernelGGL(kv8c_centre_k, dim3(a.n_slots, a.H, a.L), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
@@ -568,6 +693,59 @@ extern "C" int vc_debug_attn8(const vc_debug_attn8_args* p8, void* stream) {
 extern "C" int vc_kv8_quantize_host(const uint16_t* bf16_rows, int n_rows, int hd, uint8_t* codes, int8_t* shift) {
   if (!bf16_rows || !codes || !shift || n_rows < 0 || hd < 1) return VC_EINVAL;
   for (long r = 0; r < n_rows; ++r) shift[r] = (int8_t)vc_kv8_quantize_row(bf16_rows + r * hd, hd, codes + r * hd);
+  return VC_OK;
+}
+
+// The same for "kv8c" (include/vc_engine.h): mode 0 the centred attention form, 1 the centred packer, 2 the centre kernel.
+extern "C" int vc_debug_attn8c(const vc_debug_attn8c_args* pc, void* stream) {
+  if (!pc) return VC_EINVAL;
+  const vc_debug_attn8_args* p8 = &pc->base8;
+  const vc_debug_attn_args* p = &p8->base;
+  if (pc->mode < 0 || pc->mode > 2 || !pc->centre || ((uintptr_t)pc->centre & 15)) return VC_EINVAL;
+  if (p->dtype != VC_DTYPE_BF16 || (p->hd != 32 && p->hd != 64 && p->hd != 128)) return VC_EINVAL;
+  if (p->H < 1 || p->S_max < 1 || p->rows < 1 || !p->kcache || ((uintptr_t)p->kcache & 15) || !p->row_seq || !p->row_pos || !p->n_active) return VC_EINVAL;
+  const int hd_shift = p->hd == 32 ? 5 : p->hd == 64 ? 6 : 7;
+  if (pc->mode == 2) {
+    if (!pc->n0 || pc->n_seqs < 1 || pc->n_seqs > VC_MAX_SEQS || !p->share_len || p->rows > VC_MAX_ROWS) return VC_EINVAL;
+    Kv8CentreArgs c = {};
+    c.one.kc = p->kcache; c.centre = pc->centre; c.n0 = (int*)pc->n0;
+    c.L = 1; c.H = p->H; c.hd = p->hd; c.hd_shift = hd_shift; c.S_max = p->S_max; c.n_slots = pc->n_seqs;
+    c.row_seq = p->row_seq; c.row_pos = p->row_pos; c.n_rows = p->rows; c.n_active = p->n_active; c.share_len = p->share_len;
+    return vc_launch_kv8c_centre(c, (hipStream_t)stream) == hipSuccess ? VC_OK : VC_EHIP;
+  }
+  if (p8->rps < 1 || (long)p->rows * p8->rps >= 65536) return VC_EINVAL;
+  if (!p->vcache || !p8->kcache8 || !p8->vcache8 || !p8->kvshift8) return VC_EINVAL;
+  if (((uintptr_t)p->vcache | (uintptr_t)p8->kcache8 | (uintptr_t)p8->vcache8) & 15) return VC_EINVAL;
+  if ((uintptr_t)p8->kvshift8 & 1) return VC_EINVAL;
+  if (pc->mode == 1) {
+    Kv8PackArgs k = {};
+    k.one = Kv8Layer{p->kcache, p->vcache, (unsigned char*)p8->kcache8, (unsigned char*)p8->vcache8, (signed char*)p8->kvshift8};
+    k.L = 1; k.H = p->H; k.hd = p->hd; k.hd_shift = hd_shift; k.S_max = p->S_max;
+    k.row_seq = p->row_seq; k.row_pos = p->row_pos; k.n_rows = p->rows; k.n_active = p->n_active;
+    k.centre = pc->centre;
+    return vc_launch_kv8_pack(k, (hipStream_t)stream) == hipSuccess ? VC_OK : VC_EHIP;
+  }
+  if (p->nsplit < 1 || p->nsplit > VC_MAX_NSPLIT) return VC_EINVAL;
+  if (!p->q || !p->share_len || ((uintptr_t)p->q & 15)) return VC_EINVAL;
+  if (p->x_out) {
+    if (p->nsplit != 1 || p->part16) return VC_EINVAL;
+  } else if (!p->att_o || !p->att_ml) return VC_EINVAL;
+  AttnArgs a = {};
+  a.q = p->q; a.kcache = p->kcache; a.vcache = p->vcache;
+  a.kcache8 = (const unsigned char*)p8->kcache8; a.vcache8 = (const unsigned char*)p8->vcache8; a.kvshift8 = (const signed char*)p8->kvshift8;
+  a.rps = p8->rps; a.centre = pc->centre;
+  a.cache_seq_stride = (long)p->H * p->S_max * p->hd;
+  a.S_max = p->S_max; a.H = p->H; a.hd = p->hd; a.hd_shift = hd_shift; a.d = p->H * p->hd; a.nsplit = p->nsplit;
+  a.scale = 1.0f / sqrtf((float)p->hd);
+  a.row_seq = p->row_seq; a.row_pos = p->row_pos; a.n_rows = p->rows;
+  a.n_active = p->n_active; a.share_len = p->share_len;
+  a.att_o = reinterpret_cast<float*>(p->att_o); a.att_ml = p->att_ml; a.x_out = p->x_out;
+  a.nt = p->nt ? 1 : 0; a.fast = p->fast ? 1 : 0; a.part16 = p->part16 ? 1 : 0;
+  return vc_launch_attn(a, VC_DTYPE_BF16, p->rows, (hipStream_t)stream) == hipSuccess ? VC_OK : VC_EHIP;
+}
+extern "C" int vc_kv8c_quantize_host(const uint16_t* bf16_rows, const uint16_t* centre, int n_rows, int hd, uint8_t* codes, int8_t* shift) {
+  if (!bf16_rows || !centre || !codes || !shift || n_rows < 0 || hd < 1) return VC_EINVAL;
+  for (long r = 0; r < n_rows; ++r) shift[r] = (int8_t)vc_kv8c_quantize_row(bf16_rows + r * hd, centre, hd, codes + r * hd);
   return VC_OK;
 }
 

@@ -300,6 +300,8 @@ struct AttnArgs {
   const signed char* kvshift8;    // [seq][H][S_max][2]: the shift of the K row, of the V row
   int rps;                        // rows per sequence of the pass (>= 1)
   int rps_magic;                  // ceil(2^16 / rps): r / rps = (r * rps_magic) >> 16 for r * (rps - 1) < 2^16 (set by the launcher)
+  // "kv8c" (an engine with vc_request_kv8c; null: the plain kv8 form): the K codes stand for k - c, and q . c joins every 8-bit score
+  const void* centre;             // bf16 [seq][H][hd], the centre of the row's OWN sequence slot (vc_kv8.h)
 };
 
 // kv8_pack_k: the rows a pass wrote (row_seq / row_pos; pos < 0: none), every layer, K and V, every head, in one launch: reads the bf16
@@ -313,6 +315,28 @@ struct Kv8PackArgs {
   const int* row_pos;
   int n_rows;
   const int* n_active;      // never null
+  // "kv8c": the K half packs bf16_rne(k - c) (kv8_pack_k<true>; the V half is the plain one)
+  void* const* centres;     // device table [L] of the layers' centre arrays, or null: `centre`
+  void* centre;             // bf16 [seq][H][hd]; with `centres` null and this null: the plain packer
+};
+
+// kv8c_centre_k, in front of the packer on prefill passes of a centred engine: for every sequence slot whose position 0 is among the
+// pass's rows (row_seq / row_pos, pos < 0: none), every layer and head: c = the mean of the slot's K rows in this pass (fp32 sums,
+// rounded to bf16), n0 = their number.  While *share_len > 0 every slot that has a row in the pass takes sequence 0's centre instead:
+// computed from slot 0's rows where its position 0 is in this pass, else copied from what an earlier pass left.  Other slots, and
+// everything when *n_active == 0, stay untouched.
+struct Kv8CentreArgs {
+  const Kv8Layer* layers;   // device table [L] (only kc is read), or null: `one`
+  Kv8Layer one;
+  void* const* centres;     // device table [L], or null: `centre`
+  void* centre;             // bf16 [n_slots][H][hd]
+  int* n0;                  // [n_slots]
+  int L, H, hd, hd_shift, S_max, n_slots;
+  const int* row_seq;
+  const int* row_pos;
+  int n_rows;
+  const int* n_active;      // never null
+  const int* share_len;     // never null
 };
 
 struct Segment {            // one run of columns of the rearranged audio sequence
@@ -468,11 +492,12 @@ extern int vc_blk_dbg_mask;   // vc_gemm.hip: diagnostic mask of the prefill blo
 // vc_debug_read("launch_counts") by the parity tests, which assert that the form a benchmarked shape runs on is the one
 // they compared with the oracle.
 enum { VC_LC_ROWS_GEMM = 0, VC_LC_MT2 = 1, VC_LC_MT4 = 2, VC_LC_BLK64 = 3, VC_LC_BLK128_SBS = 4, VC_LC_BLK128_2X2 = 5,
-       VC_LC_BLK64_OCC2 = 6, VC_LC_LN_ROWS = 7, VC_LC_ROWS_ATTN = 8, VC_LC_TILE_ATTN = 9, VC_LC_ROWS_GEMM_FR = 10, VC_LC_BIG256 = 11, VC_LC_BIG128 = 12, VC_LC_ROW_GEMM_FR1 = 13, VC_LC_TILE_ATTN64 = 14, VC_LC_ROWS_GEMM_FRP = 15, VC_LC_WD = 16, VC_LC_ROWS_GEMM_QP = 17, VC_LC_W13 = 18, VC_LC_W8 = 19, VC_LC_KV8_ATTN = 20, VC_LC_KV8_PACK = 21, VC_LC_N = 22 };   // VC_LC_W13 / VC_LC_W8: launches on 13-bit planes / on E4M3 bytes (also counted in their form's slot); VC_LC_KV8_ATTN: rows_attn_k launches on the E4M3 K/V cache (also in VC_LC_ROWS_ATTN), VC_LC_KV8_PACK: kv8_pack_k
+       VC_LC_BLK64_OCC2 = 6, VC_LC_LN_ROWS = 7, VC_LC_ROWS_ATTN = 8, VC_LC_TILE_ATTN = 9, VC_LC_ROWS_GEMM_FR = 10, VC_LC_BIG256 = 11, VC_LC_BIG128 = 12, VC_LC_ROW_GEMM_FR1 = 13, VC_LC_TILE_ATTN64 = 14, VC_LC_ROWS_GEMM_FRP = 15, VC_LC_WD = 16, VC_LC_ROWS_GEMM_QP = 17, VC_LC_W13 = 18, VC_LC_W8 = 19, VC_LC_KV8_ATTN = 20, VC_LC_KV8_PACK = 21, VC_LC_KV8C_CENTRE = 22, VC_LC_KV8C_ATTN = 23, VC_LC_KV8C_PACK = 24, VC_LC_N = 25 };   // VC_LC_W13 / VC_LC_W8: launches on 13-bit planes / on E4M3 bytes (also counted in their form's slot); VC_LC_KV8_ATTN: rows_attn_k launches on the E4M3 K/V cache (also in VC_LC_ROWS_ATTN), VC_LC_KV8_PACK: kv8_pack_k; VC_LC_KV8C_*: the centre kernel, and the centred attention / packer launches (also in their kv8 slots)
 extern long long vc_launch_counts[VC_LC_N];
 hipError_t vc_launch_ln_rows(const GemmArgs& a, int dtype, hipStream_t s);
 hipError_t vc_launch_attn(const AttnArgs& a, int dtype, int rows_cap, hipStream_t s);
 hipError_t vc_launch_kv8_pack(const Kv8PackArgs& a, hipStream_t s);
+hipError_t vc_launch_kv8c_centre(const Kv8CentreArgs& a, hipStream_t s);
 hipError_t vc_launch_tile_attn(const AttnArgs& a, int dtype, hipStream_t s);
 hipError_t vc_launch_tile_attn64(const AttnArgs& a, hipStream_t s);   // bf16, head_dim 128, prompts on 64-row boundaries
 hipError_t vc_launch_prompt(const PromptArgs& a, hipStream_t s);

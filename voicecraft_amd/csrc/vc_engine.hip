@@ -43,6 +43,7 @@ struct Layer {
   // on request (vc_request_kv8): the same rows as E4M3 bytes, uint8 [max_seqs][H][S_max][hd], and their shifts, int8 [max_seqs][H][S_max][2] (K, V)
   unsigned char *kc8 = nullptr, *vc8 = nullptr;
   signed char* sh8 = nullptr;
+  void* kcen = nullptr;      // on request (vc_request_kv8c): the K centres of this layer, bf16 [max_seqs][H][hd] (vc_kv8.h)
   // W28 / Wqkv8 once more in the packed forms of vc_packed (vc_common.h): [VC_PK_W13] exact 13-bit planes (option "w13", vc_w13.h) and, on request
   // (vc_request_w8), [VC_PK_W8] E4M3 bytes with one shift byte per fragment (option "w8", vc_w8.h); second index W13_F2 / W13_QKV
   struct Packed {
@@ -204,6 +205,12 @@ struct vc_engine {
   int kv8_req = 0;
   int kv8 = 0;
   Kv8Layer* kv8_tab = nullptr;          // device table [L] of the layers' five arrays (Kv8PackArgs.layers)
+  // "kv8c" (vc_request_kv8c, implies the above; the contract is in vc_kv8.h): K meets the grid as k - c, c the mean K row of the prefill
+  // pass that wrote the slot's position 0, per layer, slot and head (Layer.kcen; kv8c_centre_k in front of the packer on prefill passes);
+  // the decode attention adds q . c to its 8-bit scores.  Fixed at creation: option "kv8" switches between this and the bf16 cache.
+  int kv8c_req = 0;
+  void** kcen_tab = nullptr;            // device table [L] of the layers' centre arrays
+  int* kcen_rows = nullptr;             // device [max_seqs]: n0, the rows each slot's centre is the mean of
   int cur_rows = 0;                     // rows per step the last decode loop ended on (tts_run reads the states back accordingly)
   // option "attn_fast": decode attention with the wave's maximum taken before any exponential (no online rescaling inside a wave) and,
   // in bf16 mode, hardware exp2 (v_exp_f32) instead of expf
@@ -635,6 +642,27 @@ int site_qkv(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly,
   return VC_OK;
 }
 
+// What options "kv8" / "kv8c" add to a pass, decided in ONE place (site_attn and run_pass follow it, vc_debug_kv8_plan reports it):
+// the form of the rows_attn_k launches (VC_KV8_ATTN_*) and the launches queued behind the last layer, in order (VC_KV8_LAUNCH_*).
+// request: 0 no request, 1 vc_request_kv8, 2 vc_request_kv8c; kv8: the option's value; rps: rows per sequence of a decode pass, 0 for a
+// prefill pass; rows_attn: the pass's attention is rows_attn_k (not a tile kernel).
+struct Kv8Plan { int attn; int n_tail; int tail[2]; };
+Kv8Plan kv8_plan(int request, int kv8, int rps, bool rows_attn) {
+  Kv8Plan k = {VC_KV8_ATTN_PLAIN, 0, {0, 0}};
+  if (request <= 0) return k;                                  // nothing more is allocated or launched
+  const bool centred = request >= 2;
+  // decode passes read the positions older than the pass from the E4M3 cache; prefill passes and option 0 stay on the bf16 cache
+  if (kv8 && rps > 0 && rows_attn) k.attn = centred ? VC_KV8_ATTN_CENTRED : VC_KV8_ATTN_E4M3;
+  // a prefill pass of a centred engine leaves the centres of the slots whose position 0 it holds, in front of the packer
+  if (centred && rps == 0) k.tail[k.n_tail++] = VC_KV8_LAUNCH_CENTRE;
+  // the rows the pass wrote, as E4M3 bytes too - prefill and decode passes alike, whatever the option's value
+  k.tail[k.n_tail++] = centred ? VC_KV8_LAUNCH_PACK_CENTRED : VC_KV8_LAUNCH_PACK;
+  return k;
+}
+Kv8Plan kv8_plan(const vc_engine* e, const PassPlan& p, const RowSrc& rs) {
+  return kv8_plan(e->kv8c_req ? 2 : e->kv8_req ? 1 : 0, e->kv8, rs.rps, p.attn == ATT_ROWS);
+}
+
 int site_attn(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly, hipStream_t s) {
   AttnArgs a;
   memset(&a, 0, sizeof a);
@@ -648,8 +676,10 @@ int site_attn(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly
   a.nt = (rs.n_active != nullptr || rs.nt) ? attn_nt_for(e, rs.n_rows) : 0;   // decode passes stream their K/V once, prefill passes re-read it
   a.fast = e->attn_fast;
   a.part16 = p.part16 ? 1 : 0;
-  if (e->kv8 && rs.rps > 0 && p.attn == ATT_ROWS) {      // decode passes of a kv8 engine: positions older than the pass from the E4M3 cache
+  const int form8 = kv8_plan(e, p, rs).attn;
+  if (form8 != VC_KV8_ATTN_PLAIN) {      // decode passes of a kv8 engine: positions older than the pass from the E4M3 cache
     a.kcache8 = ly.kc8; a.vcache8 = ly.vc8; a.kvshift8 = ly.sh8; a.rps = rs.rps;
+    if (form8 == VC_KV8_ATTN_CENTRED) a.centre = ly.kcen;
   }
   if (p.att_x) a.x_out = e->xn;        // xn is free between the QKV GEMM and the FFN LayerNorm
   if (p.attn == ATT_TILE64) HIPCHK(e, vc_launch_tile_attn64(a, s));
@@ -753,11 +783,22 @@ int run_pass(vc_engine* e, const PassPlan& p, const RowSrc& rs, PassOut* out, hi
   }
   const bool finished = p.form == FORM_FR || p.fd;
   *out = {finished ? 0 : p.ks_f2, p.hq ? e->hqB : nullptr, e->row_mu[0]};
-  if (e->kv8_req) {      // option "kv8": the rows this pass wrote, every layer, K and V, as E4M3 bytes too - prefill and decode passes alike
+  const Kv8Plan k8 = kv8_plan(e, p, rs);      // options "kv8" / "kv8c": the launches behind the last layer, in the plan's order
+  for (int i = 0; i < k8.n_tail; ++i) {
     Kv8PackArgs k;
     memset(&k, 0, sizeof k);
     k.layers = e->kv8_tab; k.L = e->L; k.H = e->H; k.hd = e->hd; k.hd_shift = e->hd == 32 ? 5 : e->hd == 64 ? 6 : 7; k.S_max = e->S_max;
     k.row_seq = rs.row_seq; k.row_pos = rs.row_pos; k.n_rows = rs.n_rows; k.n_active = rs.n_active ? rs.n_active : e->one;
+    if (k8.tail[i] == VC_KV8_LAUNCH_CENTRE) {
+      Kv8CentreArgs c;
+      memset(&c, 0, sizeof c);
+      c.layers = e->kv8_tab; c.centres = e->kcen_tab; c.n0 = e->kcen_rows;
+      c.L = k.L; c.H = k.H; c.hd = k.hd; c.hd_shift = k.hd_shift; c.S_max = k.S_max; c.n_slots = e->B_max;
+      c.row_seq = k.row_seq; c.row_pos = k.row_pos; c.n_rows = k.n_rows; c.n_active = k.n_active; c.share_len = e->share_len;
+      HIPCHK(e, vc_launch_kv8c_centre(c, s));
+      continue;
+    }
+    if (k8.tail[i] == VC_KV8_LAUNCH_PACK_CENTRED) k.centres = e->kcen_tab;
     HIPCHK(e, vc_launch_kv8_pack(k, s));
   }
   return VC_OK;
@@ -1269,6 +1310,7 @@ void refresh_opt_state(vc_engine* e) {
     t += std::to_string(e->*o.v0.f);
     if (o.v1.f) t += "," + std::to_string(e->*o.v1.f);
   }
+  if (e->kv8c_req) t += "|kv8c=1";      // no option: an engine with vc_request_kv8c says so (the decode graphs are keyed by "kv8" in front of it)
 }
 
 int apply_env_presets(vc_engine* e) {
@@ -1285,6 +1327,13 @@ int apply_env_presets(vc_engine* e) {
 }  // namespace
 
 // =====================================================================================  C ABI
+// Host-only: what the kv8 options add to a pass (kv8_plan above, the function site_attn and run_pass follow).
+extern "C" int vc_debug_kv8_plan(int request, int kv8, int rps, int rows_attn, int32_t out[4]) {
+  if (!out || request < 0 || request > 2 || rps < 0) return VC_EINVAL;
+  const Kv8Plan k = kv8_plan(request, kv8, rps, rows_attn != 0);
+  out[0] = k.attn; out[1] = k.n_tail; out[2] = k.n_tail > 0 ? k.tail[0] : 0; out[3] = k.n_tail > 1 ? k.tail[1] : 0;
+  return VC_OK;
+}
 // Host-only: how a decode pass of `rows` rows would be launched for this model shape and compute dtype (no engine, no GPU).
 extern "C" int vc_debug_plan(const vc_model_cfg* c, int compute_dtype, int rows, int32_t out[16]) {
   if (!c || !out || rows < 1 || rows > VC_MAX_SEQS || c->d_model <= 0 || c->nhead <= 0 || c->d_model % c->nhead) return VC_EINVAL;
@@ -1430,6 +1479,16 @@ extern "C" int vc_request_kv8(vc_engine* e) {
   if (e->finalized) return fail(e, VC_ESTATE, "vc_request_kv8 comes before vc_finalize_weights");
   e->kv8_req = 1;
   e->kv8 = 1;
+  return VC_OK;
+}
+
+// vc_request_kv8 with centred K (vc_kv8.h): the same rules, and implies it.
+extern "C" int vc_request_kv8c(vc_engine* e) {
+  if (!e) return VC_EINVAL;
+  if (e->finalized) return fail(e, VC_ESTATE, "vc_request_kv8c comes before vc_finalize_weights");
+  e->kv8_req = 1;
+  e->kv8 = 1;
+  e->kv8c_req = 1;
   return VC_OK;
 }
 
@@ -1580,6 +1639,18 @@ int upload_kv8_table(vc_engine* e) {
   for (const Layer& ly : e->layers) tab.push_back(Kv8Layer{ly.kc, ly.vc, ly.kc8, ly.vc8, ly.sh8});
   if ((rc = dalloc(e, &e->kv8_tab, tab.size()))) return rc;
   HIPCHK(e, hipMemcpy(e->kv8_tab, tab.data(), tab.size() * sizeof(Kv8Layer), hipMemcpyHostToDevice));
+  if (!e->kv8c_req) return VC_OK;
+  // centred K: the layers' centres (zero until a prefill pass leaves one), their table, n0 per slot - behind every allocation a plain
+  // kv8 engine makes up to here
+  const size_t cen_bytes = (size_t)e->B_max * e->H * e->hd * 2;
+  std::vector<void*> cen;
+  for (Layer& ly : e->layers) {
+    if ((rc = dalloc(e, &ly.kcen, cen_bytes))) return rc;
+    HIPCHK(e, hipMemset(ly.kcen, 0, cen_bytes));
+    cen.push_back(ly.kcen);
+  }
+  if ((rc = dalloc(e, &e->kcen_tab, cen.size())) || (rc = dalloc0(e, &e->kcen_rows, (size_t)e->B_max, (size_t)e->B_max * sizeof(int)))) return rc;
+  HIPCHK(e, hipMemcpy(e->kcen_tab, cen.data(), cen.size() * sizeof(void*), hipMemcpyHostToDevice));
   return VC_OK;
 }
 
@@ -1824,6 +1895,18 @@ int replicate_kv(vc_engine* e, CopyKvArgs kv, hipStream_t s) {
       sh.base = (char*)e->layers[l].sh8;
       HIPCHK(e, vc_launch_copy_kv(sh, s));
     }
+  }
+  if (e->kv8c_req) {     // ... which stand for k - c: the source's centre (and n0) goes with them, whole, whatever the position range
+    CopyKvArgs cn = kv;
+    cn.head_stride_b = (long)e->hd * 2; cn.pos_b = cn.head_stride_b; cn.seq_stride_b = (long)e->H * cn.head_stride_b;
+    for (int i = 0; i < cn.n_ent; ++i) { cn.p0[i] = 0; cn.p1[i] = 1; }
+    for (int l = 0; l < e->L; ++l) {
+      cn.base = (char*)e->layers[l].kcen;
+      HIPCHK(e, vc_launch_copy_kv(cn, s));
+    }
+    cn.H = 1; cn.head_stride_b = cn.pos_b = cn.seq_stride_b = sizeof(int);
+    cn.base = (char*)e->kcen_rows;
+    HIPCHK(e, vc_launch_copy_kv(cn, s));
   }
   return VC_OK;
 }
@@ -3353,6 +3436,14 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
     const int64_t rows = (int64_t)e->B_max * e->H * e->S_max;
     if (n[1] == 'v') { src = ly.sh8; avail = rows * 2; }
     else { src = n[0] == 'k' ? ly.kc8 : ly.vc8; avail = rows * e->hd; }
+  }
+  else if (n.rfind("kcentre_", 0) == 0 && e->kv8c_req) {      // kcentre_<l>: bf16 [max_seqs][H][hd]; kcentre_rows: int32 [max_seqs] (engines with vc_request_kv8c)
+    if (n == "kcentre_rows") { src = e->kcen_rows; avail = (int64_t)e->B_max * 4; }
+    else {
+      if (n.size() < 9 || n.size() > 11 || n.find_first_not_of("0123456789", 8) != std::string::npos || atoi(n.c_str() + 8) >= e->L)
+        return fail(e, VC_EINVAL, "unknown debug buffer '%s'", n.c_str());
+      src = e->layers[atoi(n.c_str() + 8)].kcen; avail = (int64_t)e->B_max * e->H * e->hd * 2;
+    }
   }
   else if (n == "eval_logits") {                    // fp32 [rows][K][V] of the last vc_eval_forward call with the parity hook
     if (!e->eval_logits) return fail(e, VC_ESTATE, "no vc_eval_forward call with nll_dev / tgt_dev has run");

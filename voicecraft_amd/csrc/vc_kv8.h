@@ -11,6 +11,20 @@
 // 448 and the NaN code 480: at the next shift 480 and 512 exist as 240 and 256); a row of zeros takes 0.  A value is scaled by 2^-s,
 // clamped to +-448 and rounded to the nearest code, ties to the even code.  Everything below is integer arithmetic on the bf16 bits, so
 // the host and the device agree by construction.
+//
+// "kv8c" (vc_request_kv8c, centred K): K rows lose a fixed vector before they meet the grid.  The contract, stated once:
+//   The centre.  For every layer, cache slot and head there is a bf16 vector c[hd]: the mean of the slot's bf16 K rows at positions
+//     0 .. n0-1, accumulated in fp32 and rounded to bf16 (nearest even), n0 = the number of rows of that sequence in the prefill pass
+//     that wrote its position 0.  It is recomputed whenever a slot is prefilled from position 0 (a new call, a session admission) and
+//     never updated by decode passes or by later prefill passes of the same sequence.
+//   Call kinds.  Best-of-N: the copy that gives the siblings the source slot's rows gives them its centre.  A call with a shared text
+//     prefix: every sequence of the call takes SEQUENCE 0's centre (positions below the prefix are read from slot 0's cache, and a row
+//     must meet one c for all its 8-bit positions); slot 0's centre exists before any row of the call is packed.
+//   K codes and shifts: the grid above applied to bf16_rne(float(k) - float(c)) (vc_kv8c_sub; the subtraction in fp32).  V codes and
+//     shifts are the plain ones.
+//   Scores.  A position read from the E4M3 cache scores (q . k8) . 2^s + q . c, q pre-scaled as for the other term: q . (k - c) + q . c
+//     is the true score, so every score of a row is a true score and softmax, the split partials and their merge are as before.
+//     The pass's own positions lo..pos come from the bf16 cache, uncentred.
 #pragma once
 #include <stdint.h>
 #include "vc_w8.h"
@@ -93,11 +107,37 @@ VC_W8_FN uint32_t vc_kv8_decode_value(uint32_t c, int shift) {
   return sign | (field << 7) | m7;
 }
 
+// "kv8c": bf16_rne(float(k) - float(c)) on bf16 bit patterns (finite values; the fp32 difference of two bf16 numbers, rounded to
+// nearest even bf16 - an overflow gives the infinity the encode clamps).
+VC_W8_FN uint32_t vc_kv8c_sub(uint32_t k, uint32_t c) {
+  const uint32_t ku = k << 16, cu = c << 16;
+  float kf, cf;
+  memcpy(&kf, &ku, 4);
+  memcpy(&cf, &cu, 4);
+  const float d = kf - cf;
+  uint32_t u;
+  memcpy(&u, &d, 4);
+  return ((u + 0x7fffu + ((u >> 16) & 1u)) >> 16) & 0xffffu;
+}
+// Eight values (four dwords of bf16 pairs) minus eight centre values, in place.
+VC_W8_FN void vc_kv8c_sub8(uint32_t w[4], const uint32_t c[4]) {
+  for (int q = 0; q < 4; ++q)
+    w[q] = vc_kv8c_sub(w[q] & 0xffffu, c[q] & 0xffffu) | (vc_kv8c_sub(w[q] >> 16, c[q] >> 16) << 16);
+}
+
 // One row of hd bf16 values: its shift and its hd code bytes.
 VC_W8_FN int vc_kv8_quantize_row(const uint16_t* row, int hd, uint8_t* codes) {
   uint32_t amax = 0;
   for (int j = 0; j < hd; ++j) { const uint32_t a = row[j] & 0x7fffu; amax = a > amax ? a : amax; }
   const int s = vc_kv8_shift(amax);
   for (int j = 0; j < hd; ++j) codes[j] = (uint8_t)vc_kv8_encode_value(row[j], s);
+  return s;
+}
+// "kv8c": one K row of hd bf16 values against its head's centre.
+VC_W8_FN int vc_kv8c_quantize_row(const uint16_t* row, const uint16_t* centre, int hd, uint8_t* codes) {
+  uint32_t amax = 0;
+  for (int j = 0; j < hd; ++j) { const uint32_t a = vc_kv8c_sub(row[j], centre[j]) & 0x7fffu; amax = a > amax ? a : amax; }
+  const int s = vc_kv8_shift(amax);
+  for (int j = 0; j < hd; ++j) codes[j] = (uint8_t)vc_kv8_encode_value(vc_kv8c_sub(row[j], centre[j]), s);
   return s;
 }

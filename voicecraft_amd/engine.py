@@ -51,16 +51,21 @@ class VoiceCraftEngine:
 
     def __init__(self, args: Namespace | dict, state_dict: dict[str, torch.Tensor], device="cuda:0",
                  dtype="bf16", max_seqs: int = 8, max_positions: int = 4096, use_graph: bool = True, w8: str | None = None,
-                 kv8: bool = False):
-        """kv8: False (default: nothing changes) | True - decode passes of a bf16 engine read the cached K / V positions older than the pass
+                 kv8: bool | str = False):
+        """kv8: False (default: nothing changes) | True | "centred" - decode passes of a bf16 engine read the cached K / V positions older than the pass
         as one E4M3 byte per value times a per-row shift (option `kv8`, csrc/vc_kv8.h, quant.kv8_quantize_rows): half the bytes of the
         launch that grows with the batch, 3 mantissa bits left of a cached value, 1.5 x the K/V memory.  Works with every call and `w8=`.
+        "centred" (vc_request_kv8c; quant.kv8c_* state the contract): the same, with K stored as k - c, c the mean K row of the slot's
+        prompt per layer and head, and q . c added back to the 8-bit scores - softmax does not see the K rows' common offset, which is
+        where the plain grid loses its bits on peaked attention.  Option `kv8` = 0 / 1 switches either mode off and on.
         w8: None (default: nothing changes) | "quantize" | "as_is" - one-row steps of a bf16 engine stream the matrices of W8_MATRICES
         as one E4M3 byte per value (option `w8`, csrc/vc_w8.h), bit-identical to the bf16 launches on the same weights.  "quantize" first
         puts those matrices on the 8-bit grid (quant.quantize_state_dict_w8, on the CPU) and keeps the result as `self.w8_state_dict`,
         the checkpoint this engine then computes; "as_is" takes the weights as given: a matrix off the grid comes back refused
         (w8_stats()) and keeps its bf16 launch."""
         self.lib = _lib.load()
+        if isinstance(kv8, str) and kv8 != "centred":
+            raise ValueError(f'kv8 = {kv8!r}: False, True or "centred"')
         a = Namespace(**args) if isinstance(args, dict) else Namespace(**vars(args))
         # the same normalisation VoiceCraft.__init__ applies (models/voicecraft.py:117-127)
         if not getattr(a, "special_first", False):
@@ -106,7 +111,10 @@ class VoiceCraftEngine:
         if w8 is not None:
             check(self.lib.vc_request_w8(self._h, self.W8_MASK), self._h, "vc_request_w8")
         self.kv8 = bool(kv8)
-        if self.kv8:
+        self.kv8_centred = kv8 == "centred"
+        if self.kv8_centred:
+            check(self.lib.vc_request_kv8c(self._h), self._h, "vc_request_kv8c")
+        elif self.kv8:
             check(self.lib.vc_request_kv8(self._h), self._h, "vc_request_kv8")
         self._load(state_dict)
         self.last_steps = 0
@@ -697,7 +705,8 @@ class VoiceCraftEngine:
         attn_fast, qkv_p8), q16 = many-row steps (qkv16, wide_heads, wide_gemm, wd_stage), sh = shrink, w13 = the one-row launches that
         stream their weights as exact 13-bit planes (mask: 1 FFN-down, 4 QKV; w13_stats() says which matrices have planes); an engine
         created with `w8=` appends w8 = the launches that stream E4M3 bytes instead (same bits, w8_stats()), one created with `kv8=True`
-        appends kv8 = decode attention on the E4M3 copy of the K/V cache (1) or on the bf16 cache (0).
+        appends kv8 = decode attention on the E4M3 copy of the K/V cache (1) or on the bf16 cache (0), one created with `kv8="centred"`
+        kv8c = 1 behind it.
         bench.py turns it into a JSON object (`config.engine_options`)."""
         return bytes(self.debug_read("options", (256,), torch.uint8).tolist()).split(b"\0")[0].decode()
 
@@ -714,7 +723,7 @@ class VoiceCraftEngine:
 
     LAUNCH_FORMS = ("rows_gemm", "mt2", "mt4", "blk64", "blk128_sbs", "blk128_2x2", "blk64_occ2", "ln_rows", "rows_attn",
                     "tile_attn", "rows_gemm_fr", "big256", "big128", "row_gemm_fr1", "tile_attn64", "rows_gemm_frp", "wd", "rows_gemm_qp", "w13", "w8",
-                    "kv8_attn", "kv8_pack")
+                    "kv8_attn", "kv8_pack", "kv8c_centre", "kv8c_attn", "kv8c_pack")
 
     def launch_counts(self) -> dict:
         """Process-wide census of the kernel FORMS launched so far (vc_common.h VC_LC_*): the parity tests take the
@@ -1202,6 +1211,78 @@ def debug_attn8(q, kcache, vcache, kcache8, vcache8, kvshift8, row_seq, row_pos,
     if rc != 0:
         raise AssertionError(f"vc_debug_attn8 rejected its arguments (code {rc})")
     return out
+
+
+def debug_attn8c(q, kcache, vcache, kcache8, vcache8, kvshift8, centre, row_seq, row_pos, n_active, share_len, nsplit: int = 1,
+                 rps: int = 1, mode: int = 0, n0=None, nt: bool = False, fast: bool = True, part16: bool = False, x_out: bool = False,
+                 sentinel: float = 0.0) -> dict:
+    """vc_debug_attn8c (tests only): debug_attn8 for `kv8="centred"`.  centre bf16 [n_seqs][H][hd].  mode 0: one launch of the centred
+    attention form (outputs as debug_attn's); mode 1: the centred packer, in place; mode 2: the centre kernel over the rows as a prefill
+    pass's, which writes `centre` and n0 (int32 [n_seqs]) in place (the 8-bit arrays, vcache and q may be None)."""
+    lib = _lib.load()
+    dev = kcache.device
+    assert kcache.dtype == torch.bfloat16 and kcache.ndim == 4 and kcache.is_cuda and kcache.is_contiguous()
+    n_seqs, H, S_max, hd = kcache.shape
+    assert centre.dtype == torch.bfloat16 and tuple(centre.shape) == (n_seqs, H, hd) and centre.device == dev and centre.is_contiguous()
+    rows = row_pos.numel()
+    for t, n in ((row_seq, rows), (row_pos, rows), (n_active, 1), (share_len, 1)):
+        assert t.dtype == torch.int32 and t.device == dev and t.numel() == n and t.is_contiguous()
+    assert int(row_seq.max()) < n_seqs and int(row_pos.max()) < S_max and int(share_len) <= S_max      # the kernels trust their tables
+    ac = _lib.DebugAttn8cArgs()
+    a8 = ac.base8
+    a = a8.base
+    a.kcache = kcache.data_ptr()
+    a.row_seq, a.row_pos, a.n_active, a.share_len = row_seq.data_ptr(), row_pos.data_ptr(), n_active.data_ptr(), share_len.data_ptr()
+    a.dtype = _lib.VC_DTYPE_BF16
+    a.H, a.hd, a.S_max, a.rows, a.nsplit = H, hd, S_max, rows, int(nsplit)
+    a.nt, a.fast, a.part16 = int(bool(nt)), int(bool(fast)), int(bool(part16))
+    a8.rps = int(rps)
+    ac.centre, ac.mode, ac.n_seqs = centre.data_ptr(), int(mode), n_seqs
+    out = {}
+    if mode == 2:
+        assert n0.dtype == torch.int32 and n0.numel() == n_seqs and n0.device == dev and n0.is_contiguous()
+        ac.n0 = n0.data_ptr()
+    else:
+        assert vcache.dtype == torch.bfloat16 and vcache.shape == kcache.shape
+        for t in (kcache8, vcache8):
+            assert t.dtype == torch.uint8 and t.shape == kcache.shape
+        assert kvshift8.dtype == torch.int8 and tuple(kvshift8.shape) == (n_seqs, H, S_max, 2)
+        for t in (vcache, kcache8, vcache8, kvshift8):
+            assert t.is_cuda and t.device == dev and t.is_contiguous()
+        a.vcache = vcache.data_ptr()
+        a8.kcache8, a8.vcache8, a8.kvshift8 = kcache8.data_ptr(), vcache8.data_ptr(), kvshift8.data_ptr()
+    if mode == 0:
+        assert q.is_cuda and q.dtype == torch.float32 and q.shape == (rows, H * hd) and q.is_contiguous() and rows % int(rps) == 0
+        a.q = q.data_ptr()
+        if x_out:
+            out["x_out"] = torch.full((rows, H * hd), sentinel, dtype=torch.bfloat16, device=dev)
+            a.x_out = out["x_out"].data_ptr()
+        else:
+            n = max(int(nsplit), 1)
+            out["att_o"] = torch.full((rows, H, n, hd), sentinel, dtype=torch.bfloat16 if part16 else torch.float32, device=dev)
+            out["att_ml"] = torch.full((rows, H, n, 2), sentinel, dtype=torch.float32, device=dev)
+            a.att_o, a.att_ml = out["att_o"].data_ptr(), out["att_ml"].data_ptr()
+    rc = lib.vc_debug_attn8c(C.byref(ac), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise AssertionError(f"vc_debug_attn8c rejected its arguments (code {rc})")
+    return out
+
+
+def kv8c_quantize_host(rows_bf16: torch.Tensor, centre_bf16: torch.Tensor):
+    """csrc/vc_kv8.h's centred encode on the CPU (vc_kv8c_quantize_host): bf16 K rows [..., hd] against ONE centre [hd] ->
+    (codes uint8 [..., hd], shift int8 [...])."""
+    lib = _lib.load()
+    x = rows_bf16.detach().to("cpu", torch.bfloat16).contiguous()
+    c = centre_bf16.detach().to("cpu", torch.bfloat16).contiguous()
+    hd = x.shape[-1]
+    assert tuple(c.shape) == (hd,)
+    n = x.numel() // hd
+    codes = torch.empty(x.shape, dtype=torch.uint8)
+    shift = torch.empty(x.shape[:-1], dtype=torch.int8)
+    rc = lib.vc_kv8c_quantize_host(C.c_void_p(x.data_ptr()), C.c_void_p(c.data_ptr()), n, hd, C.c_void_p(codes.data_ptr()),
+                                   C.c_void_p(shift.data_ptr()))
+    assert rc == 0, rc
+    return codes, shift
 
 
 def kv8_quantize_host(rows_bf16: torch.Tensor):

@@ -129,3 +129,35 @@ def kv8_dequantize(codes: torch.Tensor, shift: torch.Tensor) -> torch.Tensor:
 def kv8_roundtrip(x: torch.Tensor) -> torch.Tensor:
     """What a kv8 engine's decode attention reads in place of the cached rows x [..., hd]."""
     return kv8_dequantize(*kv8_quantize_rows(x))
+
+
+# ---- "kv8c": centred K (csrc/vc_kv8.h states the contract; this is its restatement) ---------------------------------------------------
+# The centre.  For every layer, cache slot and head there is a bf16 vector c[hd]: the mean of the slot's bf16 K rows at positions
+#   0 .. n0-1, accumulated in fp32 and rounded to bf16; n0 = the rows of that sequence in the prefill pass that wrote its position 0.
+#   It is recomputed whenever a slot is prefilled from position 0 (a new call, a session admission), never by decode passes or later
+#   prefill passes of the same sequence.
+# Call kinds.  Best-of-N siblings get the source slot's centre with its rows.  With a shared text prefix every sequence of the call
+#   takes sequence 0's centre, which exists before any row of the call is packed.
+# K codes and shifts: the kv8 grid applied to bf16_rne(float(k) - float(c)).  V is plain kv8.
+# Scores: a position read from the 8-bit cache scores (q . k8) * 2**s + q . c; the pass's own positions come from the bf16 cache, uncentred.
+def kv8c_centre(k_rows: torch.Tensor) -> torch.Tensor:
+    """bf16-valued K rows [..., n0, hd] of one head -> their centre [..., hd]: the fp32 mean, rounded to bf16 (returned as fp32)."""
+    return k_rows.detach().to(torch.float32).mean(dim=-2).bfloat16().float()
+
+
+def _kv8c_centred(k: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    k, c = k.detach().to(torch.float32), c.detach().to(torch.float32)
+    assert bool((c == c.bfloat16().float()).all()), "a bf16 centre"
+    return (k - c.unsqueeze(-2)).bfloat16().float()
+
+
+def kv8c_quantize_rows(k: torch.Tensor, c: torch.Tensor):
+    """K rows [..., n, hd] against their head's centre c [..., hd] -> (codes, shift) of bf16_rne(k - c) on the kv8 grid: what the centred
+    packer must match bit for bit."""
+    return kv8_quantize_rows(_kv8c_centred(k, c))
+
+
+def kv8c_roundtrip(k: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """What the 8-bit cache of a centred engine holds for the rows k: the grid's value of k - c.  The attention's scores are those of
+    c + kv8c_roundtrip(k, c)."""
+    return kv8_roundtrip(_kv8c_centred(k, c))
