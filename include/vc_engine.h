@@ -144,6 +144,12 @@ const char* vc_version(void);
  *                  puts a checkpoint there).  A matrix off the grid is refused and keeps its current launch (vc_debug_read "w8_stats",
  *                  layout of "w13_stats").  Where a matrix has both kinds of planes the w8 bit wins.  The option text ends in |w8=<mask>
  *                  on such an engine only.  Resident memory: + 0.5 x the requested images
+ *   "w8r"          mask of the same bits, ONLY on an engine that called vc_request_w8_rows (default: the requested mask; VC_EINVAL on any
+ *                  other engine): steps of 2..8 finished rows stream the same planes - the FFN down-projection (1: rows_gemm_frp_w8_k, at
+ *                  d = 512, 1024, 2048) and the QKV projection of layers 1.. (4: rows_gemm_qp_w8_k, at d = 2048, up to 6 rows) -, every
+ *                  result bit-identical to the image launch; a refused matrix keeps its image launch for that layer.  "w8" stays the
+ *                  one-row launches.  The option text ends in |w8=<mask>|w8r=<mask> on such an engine only (vc_debug_w8r_plan says which
+ *                  row counts take the form)
  *   "kv8"          0 / 1, ONLY on an engine that called vc_request_kv8 (default 1; VC_EINVAL on any other engine): decode passes read the
  *                  cached K / V positions older than the pass as one OCP E4M3 byte per value times 2^shift, one shift byte per cached
  *                  row of a head (csrc/vc_kv8.h; voicecraft_amd/quant.py kv8_quantize_rows states the grid), half the bytes of the bf16
@@ -177,6 +183,10 @@ int vc_finalize_weights(vc_engine* e, int compute_dtype);
  * other bit: VC_EINVAL) of every layer as E4M3 bytes for one-row steps, option "w8" above.  The form is bf16 only: vc_finalize_weights
  * with VC_DTYPE_F32 after a non-zero request returns VC_EINVAL.  An engine without the request packs nothing more and behaves as before. */
 int vc_request_w8(vc_engine* e, int mask);
+/* After vc_request_w8 on the same engine (VC_ESTATE without it) and before vc_finalize_weights (VC_ESTATE after it): steps of 2..8
+ * finished rows stream the requested planes too, option "w8r" above.  `mask`: bits 1 and 4 as above, a subset of vc_request_w8's (anything
+ * else: VC_EINVAL).  Nothing more is packed.  An engine without this request has no such option and launches what it launched before. */
+int vc_request_w8_rows(vc_engine* e, int mask);
 /* Before vc_finalize_weights (VC_ESTATE after it): keep, next to every layer's bf16 K / V cache, an E4M3 copy (one byte per value) and one
  * shift byte per cached row of a head, written by one packer launch behind every pass, and let the decode attention read the positions
  * older than the pass from it (option "kv8" above).  bf16 only: vc_finalize_weights with VC_DTYPE_F32 after the request returns
@@ -564,6 +574,11 @@ int vc_box_probe(long long bytes, int hops, float res[2], void* stream);
  * (1) or falls back to rows_gemm_mt_k (0); out[12] / out[13] its K slices for the out-projection / FFN down-projection; out[14] /
  * out[15] its k-tiles per wave for K = d / K = head_hidden.  tests/test_plan_cpu.py walks every model width with it. */
 int vc_debug_plan(const vc_model_cfg* cfg, int compute_dtype, int rows, int32_t out[16]);
+/* Host only: what option "w8r" = mask makes of a bf16 decode pass of `rows` rows at this model shape, every matrix taken as packed.
+ * out[0] / out[1] = 1 when the FFN down-projection / the QKV projection of layers 1.. run on the E4M3 bytes (rows_gemm_frp_w8_k /
+ * rows_gemm_qp_w8_k), out[2] / out[3] their groups per wave (0 where the form is not taken).  VC_EINVAL: a null pointer, rows < 1,
+ * a mask with other bits than 1 and 4.  tests/test_w8_rows_cpu.py walks every model width with it. */
+int vc_debug_w8r_plan(const vc_model_cfg* cfg, int mask, int rows, int32_t out[4]);
 /* Copies a named internal device buffer to host memory.  "kcache<l>" / "vcache<l>": layer l's K / V cache, [max_seqs][H][max_positions][hd]
  * in the compute dtype; "eval_logits": see vc_eval_forward. */
 int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int64_t nbytes);

@@ -197,6 +197,12 @@ struct vc_engine {
   // kinds of planes the w8 bit wins.  An engine without the request packs nothing and has no such option.
   int w8_req = 0;
   int w8 = 0;
+  // option "w8r": steps of 2..8 finished rows stream the same planes - the FFN down-projection (1) on rows_gemm_frp_w8_k, the QKV
+  // projection of layers 1.. (4) on rows_gemm_qp_w8_k, results bit-identical -, where plan_pass takes the form.  Only on an engine
+  // that asked for it after vc_request_w8 (vc_request_w8_rows: w8r_req, a subset of w8_req); any other engine has no such option
+  // and launches what it launched before.
+  int w8r_req = 0;
+  int w8r = 0;
   // option "kv8": decode passes read the cached positions older than the pass from an E4M3 copy of the K / V cache (Layer.kc8 / vc8 / sh8,
   // vc_kv8.h: one byte per value, one shift per cached row of a head - half the bytes of the launch that grows with the batch), which
   // one kv8_pack_k launch behind every pass keeps equal to the quantiser of the bf16 rows.  This changes values (3 mantissa bits), so:
@@ -492,12 +498,23 @@ struct PassPlan {
   bool qkv_fr1;     // ... and the QKV projection behind it pairs k-tiles on the 8-channel image (option qkv_p8)
   bool qp;          // 2..8 finished rows: the QKV projection of layers 1.. on rows_gemm_qp_k (qkv_p8 = 2)
   bool frp;         // finished rows: the FFN down-projection on rows_gemm_frp_k (option fr_pair)
+  bool frp_w8;      // ... on the E4M3 bytes of a layer whose W28 is packed that way (rows_gemm_frp_w8_k, option w8r bit 1)
+  bool qp_w8;       // qp on the E4M3 bytes of a layer whose Wqkv8 is packed that way (rows_gemm_qp_w8_k, option w8r bit 4)
   bool qkv16;       // wide and block: the QKV projection on the 16-channel image (option qkv16)
   bool wd;          // wide: the linear layers on rows_gemm_wd_k (option wide_gemm)
   int ks_o, ks_f2;  // split-K slabs the out-projection / FFN down-projection leave (slab, wide and block forms)
   bool heads_wide;  // the heads run once over all rows on the wide-step kernels (option wide_heads)
   bool heads_fold;  // heads-1 folds the finished rows itself (no LayerNorm launch)
 };
+
+// Option "w8r": the row counts at which the w8 form of matrix `which` measured faster than the image over the whole paired range; a
+// row count whose range touches zero would stay on the image.  profiles/w8_rows_ab.log (giga830M, 7 interleaved pairs per line,
+// captured decode loop per step, min..max of the pairs): FFN-down alone -6.3 .. -5.8 % at 2, 3, 4, 6 and 8 rows, QKV alone -4.4 .. -5.0 %
+// at 2, 3, 4 and 6 rows (rows_gemm_qp_k stops at 6 rows at d = 2048), both -10.8 .. -11.0 %: every row count of both bits takes the form.
+bool w8r_rows_win(int which, int rows) {
+  (void)which;
+  return rows >= 2 && rows <= 8;
+}
 
 // decode: a decode step (n_active set).  tiled: a prefill pass whose 16-row tiles (1) or 64-row blocks (2) each hold consecutive
 // positions of ONE sequence (prefill_batch): MFMA attention; 0 for passes of up to VC_ROWS rows.
@@ -544,6 +561,11 @@ PassPlan plan_pass(const vc_engine* e, int rows, bool decode, int tiled) {
     // +0.5 %, giga330M 8 rows -1.3 %): at d >= 2048 the form stops at 6 rows (the 8-row launch itself: 7.42 us against 7.33 us)
     p.qp = e->qkv_p8 >= 2 && p.hq && e->has_qkv8 && rows <= (d >= 2048 ? 6 : 8) && vc_gemm_qp_ok(rows, 3 * d, d, e->dtype) != 0;
     p.frp = e->fr_pair && vc_gemm_frp_ok(rows, d, 4 * d, e->dtype);
+    // option "w8r": the two paired launches on the E4M3 bytes, where the launcher has a form for these rows (a wave's fragments per
+    // tile whole groups: FFN-down at d = 512 / 1024 / 2048, QKV at d = 2048).  The sites take it for the layers whose matrix is packed.
+    const vc_packed_kind& pk8 = vc_packed(VC_PK_W8);
+    p.frp_w8 = p.frp && (e->w8r & W8_BITS[W13_F2]) && w8r_rows_win(W13_F2, rows) && pk8.frp_ng(rows, d, 4 * d, e->dtype) != 0;
+    p.qp_w8 = p.qp && (e->w8r & W8_BITS[W13_QKV]) && w8r_rows_win(W13_QKV, rows) && pk8.qp_ng(rows, 3 * d, d, e->dtype) != 0;
   } else {
     p.nsplit = 1;                      // attention one workgroup per (row, head), no split partials
     p.att_x = true;
@@ -617,7 +639,9 @@ int site_qkv(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly,
     if (p.hq) g.row_mu_out = e->row_mu[1];
     if (p.hq && !first) {      // the previous layer's FFN down-projection left hqB = WT(hB - row_mu[0])
       g.x_in = e->hqB; g.x_ld = d; g.row_mu = e->row_mu[0]; g.mu_shift = prev->b2_mean;
-      if (p.qp) { g.Wp = ly.Wqkv8; HIPCHK(e, vc_launch_gemm_qp(g, e->dtype, s)); }
+      const Layer::Packed& p8 = ly.packed[VC_PK_W8][W13_QKV];
+      if (p.qp_w8 && p8.state == 1) { g.Wp = ly.Wqkv8; HIPCHK(e, vc_packed(VC_PK_W8).qp(g, p8.planes, p8.side, s)); }
+      else if (p.qp) { g.Wp = ly.Wqkv8; HIPCHK(e, vc_launch_gemm_qp(g, e->dtype, s)); }
       else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNQ, EPI_QKV, 1, 1, s));
     } else {
       HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNW, EPI_QKV, 1, 1, s));
@@ -754,6 +778,8 @@ int site_ffn_down(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer
     g.h_in = e->hA; g.h_out = e->hB;
     if (p.hq) { g.hq_out = e->hqB; g.row_mu = e->row_mu[0]; g.mu_shift = ly.b2_mean; }      // centred on the mean the FFN-up consumer found for h' + the mean of b2
     if (p.fd) HIPCHK(e, launch_fr1(e, ly, W13_F2, g, PRO_PLAIN, EPI_RES, s));
+    else if (p.frp_w8 && ly.packed[VC_PK_W8][W13_F2].state == 1)        // ... on the E4M3 bytes (a refused matrix keeps its image)
+      HIPCHK(e, vc_packed(VC_PK_W8).frp(g, ly.packed[VC_PK_W8][W13_F2].planes, ly.packed[VC_PK_W8][W13_F2].side, s));
     else if (p.frp) HIPCHK(e, vc_launch_gemm_frp(g, e->dtype, s));      // 2..8 rows: two k-tiles per fragment
     else HIPCHK(e, vc_launch_gemm_fr(g, e->dtype, PRO_PLAIN, s));
     return VC_OK;
@@ -1235,6 +1261,10 @@ int need_mask(vc_engine* e, const char* name, int v0) {
 int need_w8(vc_engine* e, const char* name, int v0) {
   return e->w8_req ? need_mask(e, name, v0) : fail(e, VC_EINVAL, "option 'w8': this engine was created without vc_request_w8");
 }
+// mask like "w8", on an engine that requested the rows form (vc_request_w8_rows)
+int need_w8r(vc_engine* e, const char* name, int v0) {
+  return e->w8r_req ? need_mask(e, name, v0) : fail(e, VC_EINVAL, "option 'w8r': this engine was created without vc_request_w8_rows");
+}
 int need_kv8(vc_engine* e, const char*, int) {
   return e->kv8_req ? VC_OK : fail(e, VC_EINVAL, "option 'kv8': this engine was created without vc_request_kv8");
 }
@@ -1278,6 +1308,7 @@ const OptDesc OPTIONS[] = {
     {"shrink", "VC_SHRINK", "sh", {&E::shrink, 0, 1}, nonzero},
     {"w13", "VC_W13", "w13", {&E::w13, 0, 5}, nullptr, {}, need_mask},
     {"w8", nullptr, "w8", {&E::w8, 0, 5}, nullptr, {}, need_w8, &E::w8_req},      // only an engine that requested the form has the option
+    {"w8r", nullptr, "w8r", {&E::w8r, 0, 5}, nullptr, {}, need_w8r, &E::w8r_req},   // likewise (vc_request_w8_rows)
     {"kv8", nullptr, "kv8", {&E::kv8, 0, 1}, nonzero, {}, need_kv8, &E::kv8_req},   // likewise
     {"prefill_rows", "VC_PREFILL_ROWS", nullptr, {&E::prefill_rows_per_pass, VC_ROWS, VC_MAX_ROWS}, whole_tiles},   // 16: decode kernels only
 };
@@ -1332,6 +1363,24 @@ extern "C" int vc_debug_kv8_plan(int request, int kv8, int rps, int rows_attn, i
   if (!out || request < 0 || request > 2 || rps < 0) return VC_EINVAL;
   const Kv8Plan k = kv8_plan(request, kv8, rps, rows_attn != 0);
   out[0] = k.attn; out[1] = k.n_tail; out[2] = k.n_tail > 0 ? k.tail[0] : 0; out[3] = k.n_tail > 1 ? k.tail[1] : 0;
+  return VC_OK;
+}
+// Host-only: what option "w8r" = mask makes of a bf16 decode pass of `rows` rows at this model shape, every matrix taken as packed
+// (plan_pass itself, the function the sites follow).
+extern "C" int vc_debug_w8r_plan(const vc_model_cfg* c, int mask, int rows, int32_t out[4]) {
+  if (!c || !out || rows < 1 || rows > VC_MAX_SEQS || mask < 0 || (mask & ~5) || c->d_model <= 0 || c->nhead <= 0 || c->d_model % c->nhead)
+    return VC_EINVAL;
+  vc_engine e;      // default options, the weight images vc_finalize_weights packs, both requests made
+  e.cfg = *c; e.d = c->d_model; e.H = c->nhead; e.hd = c->d_model / c->nhead; e.P = c->head_hidden; e.dtype = VC_DTYPE_BF16;
+  const int d = e.d;
+  e.has_fr8 = e.has_qkv16 = true;
+  e.has_qkv8 = vc_gemm_fr1_ok(3 * d, d, e.dtype, 4) != 0;
+  e.w8_req = e.w8 = 5; e.w8r_req = 5; e.w8r = mask;
+  const PassPlan p = plan_pass(&e, rows, true, 0);
+  out[0] = p.frp_w8 ? 1 : 0;
+  out[1] = p.qp_w8 ? 1 : 0;
+  out[2] = p.frp_w8 ? vc_packed(VC_PK_W8).frp_ng(rows, d, 4 * d, e.dtype) : 0;
+  out[3] = p.qp_w8 ? vc_packed(VC_PK_W8).qp_ng(rows, 3 * d, d, e.dtype) : 0;
   return VC_OK;
 }
 // Host-only: how a decode pass of `rows` rows would be launched for this model shape and compute dtype (no engine, no GPU).
@@ -1469,6 +1518,18 @@ extern "C" int vc_request_w8(vc_engine* e, int mask) {
   if (mask < 0 || (mask & ~5)) return fail(e, VC_EINVAL, "vc_request_w8: %d is not a mask of 1 (FFN-down) and 4 (QKV)", mask);
   e->w8_req = mask;
   e->w8 = mask;
+  return VC_OK;
+}
+
+// Lets steps of 2..8 finished rows stream the planes vc_request_w8 asked for (option "w8r"): `mask` is a subset of that request's.
+extern "C" int vc_request_w8_rows(vc_engine* e, int mask) {
+  if (!e) return VC_EINVAL;
+  if (e->finalized) return fail(e, VC_ESTATE, "vc_request_w8_rows comes before vc_finalize_weights");
+  if (mask < 0 || (mask & ~5)) return fail(e, VC_EINVAL, "vc_request_w8_rows: %d is not a mask of 1 (FFN-down) and 4 (QKV)", mask);
+  if (!e->w8_req) return fail(e, VC_ESTATE, "vc_request_w8_rows comes after vc_request_w8");
+  if (mask & ~e->w8_req) return fail(e, VC_EINVAL, "vc_request_w8_rows: mask %d is no subset of vc_request_w8's %d", mask, e->w8_req);
+  e->w8r_req = mask;
+  e->w8r = mask;
   return VC_OK;
 }
 
@@ -3548,6 +3609,10 @@ extern "C" int vc_bench_kernel(vc_engine* e, const char* which, int n_rows, int 
   bool hot = false;
   std::string w2 = w;
   if (w.size() > 4 && w.substr(w.size() - 4) == "_hot") { hot = true; w2 = w.substr(0, w.size() - 4); }
+  // the paired launches of 2..8 finished rows by their kernels' names: the sites, refused where the plan does not take the form
+  const bool by_frp = w2 == "rows_gemm_frp", by_qp = w2 == "rows_gemm_qp";
+  if (by_frp) w2 = "ffn2";
+  if (by_qp) w2 = "qkv";
   // The launch site a name times, in the form a pass of n_rows rows launches it at a layer > 0 (wd_*: a 17..64-row decode step; pf_*: a
   // prefill pass, the attention kernel a prompt of n_rows rows gets).  The LayerNorm launch in front of a GEMM is a site of its own.
   const std::string site = (wide || pf) ? w2.substr(3) : w2;
@@ -3556,6 +3621,7 @@ extern "C" int vc_bench_kernel(vc_engine* e, const char* which, int n_rows, int 
                           : (site == "ffn1" || site == "ffn2" || site == "oproj" || site == "qkv" || site == "attn" || site == "step");
   if (!known) return fail(e, VC_EINVAL, "unknown kernel '%s'", which);
   const PassPlan p = plan_pass(e, n_rows, wide, pf ? prefill_tiled(e, n_rows) : 0);
+  if ((by_frp && !p.frp) || (by_qp && !p.qp)) return fail(e, VC_EINVAL, "vc_bench_kernel: a step of %d rows does not launch '%s' on this engine", n_rows, which);
   RowSrc rs{};
   rs.h_in = e->dec_h; rs.row_seq = pf ? e->pre_row_seq : e->dec_row_seq; rs.row_pos = pf ? e->pre_row_pos : e->dec_row_pos;
   rs.n_rows = n_rows; rs.n_active = wide ? e->one : nullptr; rs.nt = 1;

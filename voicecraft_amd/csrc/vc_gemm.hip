@@ -1067,8 +1067,9 @@ int vc_gemm_fr1_ok(int N, int K, int dtype, int nw) {
 }
 const vc_packed_kind& vc_packed(int kind) {
   static const vc_packed_kind kinds[VC_PK_N] = {
-    {VC_W13_GROUP_FRAGS, VC_W13_GROUP_U4, VC_LC_W13, vc_launch_w13_pack, vc_launch_gemm_fr1_w13},
-    {VC_W8_GROUP_FRAGS, VC_W8_GROUP_U4, VC_LC_W8, vc_launch_w8_pack, vc_launch_gemm_fr1_w8},
+    {VC_W13_GROUP_FRAGS, VC_W13_GROUP_U4, VC_LC_W13, vc_launch_w13_pack, vc_launch_gemm_fr1_w13, nullptr, nullptr, nullptr, nullptr},
+    {VC_W8_GROUP_FRAGS, VC_W8_GROUP_U4, VC_LC_W8, vc_launch_w8_pack, vc_launch_gemm_fr1_w8, vc_launch_gemm_frp_w8, vc_launch_gemm_qp_w8,
+     vc_gemm_frp_w8_ng, vc_gemm_qp_w8_ng},
   };
   return kinds[kind];
 }
@@ -1117,83 +1118,16 @@ hipError_t vc_launch_gemm_fr1(const GemmArgs& a0, int dtype, int pro, int epi, h
 // RMAX = rows the staging is unrolled for (4 or 8); K x sizeof(WT) / 16 is a power of two (host contract).
 template <typename WT, int NPW, int RMAX>
 __global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_frp_k(const GemmArgs a) {
-  using T = WTr<WT>;
-  constexpr int NW = VC_FR_WAVES, NTHR = 64 * NW, TH = VC_TH_RES, SPT = 4 * TH;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nt = blockIdx.x;
-  const int n_rows = a.n_rows;                      // 2..RMAX (host contract)
-  const int Kb = a.K * (int)sizeof(WT);             // bytes of one X row = NW * NPW * 128
-  char* xl = smem;
-  f32x4* red = reinterpret_cast<f32x4*>(smem + (size_t)RMAX * Kb + 256);      // [NW][RMAX][4]
-  const int active = *a.n_active;
-  const int m = lane & 15, kg = lane >> 4;
-  // epilogue operands first: thread t < 2 RMAX finishes channels 4 (t & 1) .. of row t >> 1
-  const int frow = min(tid >> 1, n_rows - 1);
-  const int nfin = nt * TH + 4 * (tid & 1);
-  const float4 eres = *reinterpret_cast<const float4*>(a.h_in + (long)frow * a.d + nfin);
-  const float4 eb = *reinterpret_cast<const float4*>(a.bias + nfin);
-  const float cmu = a.row_mu[frow] + a.mu_shift;
-  // X rows as 16-byte units, flat index = row * upr + unit; RMAX * NPW / 8 units per thread
-  constexpr int NXU = RMAX * ((NPW * 8 + 63) / 64);
-  const int ush = a.x_upr_shift;                    // log2(units per row)
-  const int upr = 1 << ush, total = n_rows * upr;
-  const char* src = reinterpret_cast<const char*>(a.x_in);
-  const long rstride = (long)a.x_ld * (long)sizeof(WT);
-  // (explicit scalars: an indexed array is demoted to scratch memory by the compiler)
-  uint4 x0, x1, x2, x3, x4, x5, x6, x7, x8, x9, x10, x11, x12, x13, x14, x15;
-  static_assert(NXU <= 16, "staging registers per thread");
-#define VC_FRP_LOAD(j, dst)                                                                      \
-  if constexpr (NXU > (j)) {                                                                     \
-    const int i_ = min(tid + (j) * NTHR, total - 1);                                             \
-    const int r_ = i_ >> ush;                                                                    \
-    dst = *reinterpret_cast<const uint4*>(src + (long)r_ * rstride + (long)(i_ - (r_ << ush)) * 16); \
-  }
-#define VC_FRP_PARK(j, val)                                                                      \
-  if constexpr (NXU > (j)) {                                                                     \
-    const int i_ = tid + (j) * NTHR;                                                             \
-    if (i_ < total) {                                                                            \
-      const int r_ = i_ >> ush;                                                                  \
-      *reinterpret_cast<uint4*>(xl + (size_t)r_ * Kb + 16 * (r_ & 3) + 128 * (r_ >> 2) + (size_t)(i_ - (r_ << ush)) * 16) = val; \
-    }                                                                                            \
-  }
-  VC_FRP_LOAD(0, x0) VC_FRP_LOAD(1, x1) VC_FRP_LOAD(2, x2) VC_FRP_LOAD(3, x3) VC_FRP_LOAD(4, x4) VC_FRP_LOAD(5, x5) VC_FRP_LOAD(6, x6) VC_FRP_LOAD(7, x7)
-  VC_FRP_LOAD(8, x8) VC_FRP_LOAD(9, x9) VC_FRP_LOAD(10, x10) VC_FRP_LOAD(11, x11) VC_FRP_LOAD(12, x12) VC_FRP_LOAD(13, x13) VC_FRP_LOAD(14, x14) VC_FRP_LOAD(15, x15)
-  const int wunit = (m >> 3) * SPT + kg * TH + (m & 7);
-  const uint4* wbase = a.Wp + ((long)nt * a.KT + 2 * NPW * wave) * SPT;
-  uint4 wf[NPW];
-#pragma unroll
-  for (int p = 0; p < NPW; ++p)
-    wf[p] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wbase + (long)p * (2 * SPT) + wunit)));
+  constexpr int GROUP = 1;
+#define VC_FRP_EARLY
+#define VC_FRP_BURST                                                                                                                     \
+  const uint4* wbase = a.Wp + ((long)nt * a.KT + 2 * NPW * wave) * SPT;                                                                  \
+  uint4 wf[NPW];                                                                                                                         \
+  _Pragma("unroll") for (int p = 0; p < NPW; ++p)                                                                                        \
+    wf[p] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wbase + (long)p * (2 * SPT) + wunit)));  \
   __builtin_amdgcn_sched_barrier(0);
-  if (active == 0) return;
-  VC_FRP_PARK(0, x0) VC_FRP_PARK(1, x1) VC_FRP_PARK(2, x2) VC_FRP_PARK(3, x3) VC_FRP_PARK(4, x4) VC_FRP_PARK(5, x5) VC_FRP_PARK(6, x6) VC_FRP_PARK(7, x7)
-  VC_FRP_PARK(8, x8) VC_FRP_PARK(9, x9) VC_FRP_PARK(10, x10) VC_FRP_PARK(11, x11) VC_FRP_PARK(12, x12) VC_FRP_PARK(13, x13) VC_FRP_PARK(14, x14) VC_FRP_PARK(15, x15)
-#undef VC_FRP_LOAD
-#undef VC_FRP_PARK
-  __syncthreads();
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  const int rl = min(m >> 1, n_rows - 1);           // (columns of rows the pass does not have repeat the last row: cross terms)
-  const char* xcol = xl + (size_t)rl * Kb + 16 * (rl & 3) + 128 * (rl >> 2) + ((size_t)(m & 1) * T::KW + (size_t)kg * T::EPL) * sizeof(WT);
-#pragma unroll
-  for (int p = 0; p < NPW; ++p) {
-    const int gp = NPW * wave + p;
-    const uint4 xf = *reinterpret_cast<const uint4*>(xcol + (size_t)gp * (2 * T::KW * sizeof(WT)));
-    acc = mfma_frag(wf[p], xf, acc, (WT*)nullptr);
-  }
-  // D[n = 4 kg + r][m]: row m >> 1; even columns hold the even k-tiles' channels 0..7 (kg 0 / 1), odd columns the odd k-tiles' (kg 2 / 3)
-  if ((m & 1) == (kg >> 1) && (m >> 1) < n_rows) red[(wave * RMAX + (m >> 1)) * 4 + kg] = acc;
-  __syncthreads();
-  if (tid < 2 * n_rows) {
-    const int r = tid >> 1, half = tid & 1;
-    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int w = 0; w < NW; ++w) sum += red[(w * RMAX + r) * 4 + half] + red[(w * RMAX + r) * 4 + half + 2];
-    const f32x4 o = {eres.x + eb.x + sum[0], eres.y + eb.y + sum[1], eres.z + eb.z + sum[2], eres.w + eb.w + sum[3]};
-    store4(a.h_out + (long)r * a.d + nfin, o);
-    if (a.hq_out) { const f32x4 q = {o[0] - cmu, o[1] - cmu, o[2] - cmu, o[3] - cmu}; store4(reinterpret_cast<WT*>(a.hq_out) + (long)r * a.d + nfin, q); }
-  }
+#define VC_FRP_FRAG(F, w) const uint4 w = wf[g];
+#include "vc_gemm_frp_body.h"
 }
 template <typename WT, int NPW, int RMAX>
 static hipError_t launch_frp_n(const GemmArgs& a, hipStream_t s) {
@@ -1258,105 +1192,18 @@ hipError_t vc_launch_gemm_frp(const GemmArgs& a0, int dtype, hipStream_t s) {
 // NPW = fragment pairs per wave and tile = K sizeof(WT) / 1024 = the row's 16-byte units per lane; RMAX = 4 or 8 rows.
 template <typename WT, int NPW, int RMAX>
 __global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_qp_k(const GemmArgs a) {
-  using T = WTr<WT>;
-  constexpr int NW = VC_FR_WAVES, TH = VC_TH_RES, SPT = 4 * TH, NTQ = 3;
-  constexpr int E16 = 16 / (int)sizeof(WT);
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int n_rows = a.n_rows;                      // 2..RMAX (host contract)
-  const int Kb = a.K * (int)sizeof(WT);             // bytes of one row = NPW * 1024
-  char* xl = smem;
-  f32x4* red = reinterpret_cast<f32x4*>(smem + (size_t)RMAX * Kb + 256);      // [NW][RMAX][NTQ][4]
-  float* stat = reinterpret_cast<float*>(red + NW * RMAX * NTQ * 4);         // [RMAX][2]: sum and sum of squares of the row's copy
-  const int active = *a.n_active;
-  const int m = lane & 15, kg = lane >> 4;
-  // epilogue operands first (a wave's loads return in order): thread t < 6 n_rows finishes channels 4 (t & 1) .. of tile (t >> 1) % 3 of row t / 6
-  const int frow = min(tid / (2 * NTQ), n_rows - 1);
-  const int ftile = (tid >> 1) % NTQ;
-  const int nfin = ((int)blockIdx.x * NTQ + ftile) * TH + 4 * (tid & 1);
-  const float4 eb = *reinterpret_cast<const float4*>(a.bias + nfin);
-  const float4 ewg = *reinterpret_cast<const float4*>(a.wg + nfin);
-  const int epos = a.row_pos[frow], eseq = a.row_seq[frow];
-  // wave r < n_rows: row r of the centred copy, NPW requests of 1 KB
-  const int xrow = min(wave, n_rows - 1);
-  const char* qsrc = reinterpret_cast<const char*>(a.x_in) + (long)xrow * a.x_ld * (long)sizeof(WT);
-  const float cmu = a.row_mu[xrow] + a.mu_shift;
-  uint4 xq[NPW];
-#pragma unroll
-  for (int j = 0; j < NPW; ++j) xq[j] = *reinterpret_cast<const uint4*>(qsrc + (j * 64 + lane) * 16);
-  // the wave's share of the three tiles in one burst: pair p of wave w = fragment pair (NPW w + p) of each tile
-  const int wunit = (m >> 3) * SPT + kg * TH + (m & 7);
-  const uint4* wbase = a.Wp + ((long)blockIdx.x * NTQ * a.KT + 2 * NPW * wave) * SPT;
-  uint4 wf[NTQ][NPW];
-#pragma unroll
-  for (int t = 0; t < NTQ; ++t)
-#pragma unroll
-    for (int p = 0; p < NPW; ++p)
-      wf[t][p] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wbase + ((long)t * a.KT + 2 * p) * SPT + wunit)));
+  constexpr int GROUP = 1;
+#define VC_QP_EARLY
+  /* the wave's share of the three tiles in one burst: pair p of wave w = fragment pair (NPW w + p) of each tile */
+#define VC_QP_BURST                                                                                                                      \
+  const uint4* wbase = a.Wp + ((long)blockIdx.x * NTQ * a.KT + 2 * NPW * wave) * SPT;                                                    \
+  uint4 wf[NTQ][NPW];                                                                                                                    \
+  _Pragma("unroll") for (int t = 0; t < NTQ; ++t)                                                                                        \
+    _Pragma("unroll") for (int p = 0; p < NPW; ++p)                                                                                      \
+      wf[t][p] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wbase + ((long)t * a.KT + 2 * p) * SPT + wunit))); \
   __builtin_amdgcn_sched_barrier(0);
-  if (active == 0) return;
-  if (wave < n_rows) {
-    char* xr = xl + (size_t)wave * Kb + 16 * (wave & 3) + 128 * (wave >> 2);
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < NPW; ++j) {
-      *reinterpret_cast<uint4*>(xr + (j * 64 + lane) * 16) = xq[j];
-      float f[E16];
-      if constexpr (sizeof(WT) == 2) {
-        f[0] = __uint_as_float(xq[j].x << 16); f[1] = __uint_as_float(xq[j].x & 0xffff0000u);
-        f[2] = __uint_as_float(xq[j].y << 16); f[3] = __uint_as_float(xq[j].y & 0xffff0000u);
-        f[4] = __uint_as_float(xq[j].z << 16); f[5] = __uint_as_float(xq[j].z & 0xffff0000u);
-        f[6] = __uint_as_float(xq[j].w << 16); f[7] = __uint_as_float(xq[j].w & 0xffff0000u);
-      } else {
-        f[0] = __uint_as_float(xq[j].x); f[1] = __uint_as_float(xq[j].y);
-        f[2] = __uint_as_float(xq[j].z); f[3] = __uint_as_float(xq[j].w);
-      }
-#pragma unroll
-      for (int e = 0; e < E16; e += 4) {
-        s1 += (f[e] + f[e + 1]) + (f[e + 2] + f[e + 3]);
-        s2 += (f[e] * f[e] + f[e + 1] * f[e + 1]) + (f[e + 2] * f[e + 2] + f[e + 3] * f[e + 3]);
-      }
-    }
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    if (lane == 0) {
-      stat[2 * wave] = s1; stat[2 * wave + 1] = s2;
-      if (a.row_mu_out && blockIdx.x == 0) a.row_mu_out[wave] = cmu + s1 * (1.0f / (float)a.K);      // the next producer centres its copy of the row on it
-    }
-  }
-  __syncthreads();
-  f32x4 acc[NTQ];
-#pragma unroll
-  for (int t = 0; t < NTQ; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int rl = min(m >> 1, n_rows - 1);           // (columns of rows the pass does not have repeat the last row: cross terms)
-  const char* xcol = xl + (size_t)rl * Kb + 16 * (rl & 3) + 128 * (rl >> 2) + ((size_t)(m & 1) * T::KW + (size_t)kg * T::EPL) * sizeof(WT);
-#pragma unroll
-  for (int p = 0; p < NPW; ++p) {
-    const int gp = NPW * wave + p;
-    const uint4 xf = *reinterpret_cast<const uint4*>(xcol + (size_t)gp * (2 * T::KW * sizeof(WT)));
-#pragma unroll
-    for (int t = 0; t < NTQ; ++t) acc[t] = mfma_frag(wf[t][p], xf, acc[t], (WT*)nullptr);
-  }
-  // D[n = 4 kg + r][m]: row m >> 1; even columns hold the even k-tiles' channels 0..7 (kg 0 / 1), odd columns the odd k-tiles' (kg 2 / 3)
-  if ((m & 1) == (kg >> 1) && (m >> 1) < n_rows) {
-#pragma unroll
-    for (int t = 0; t < NTQ; ++t) red[((wave * RMAX + (m >> 1)) * NTQ + t) * 4 + kg] = acc[t];
-  }
-  __syncthreads();
-  if (tid < 2 * NTQ * n_rows) {
-    const int half = tid & 1;
-    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int w = 0; w < NW; ++w) sum += red[((w * RMAX + frow) * NTQ + ftile) * 4 + half] + red[((w * RMAX + frow) * NTQ + ftile) * 4 + half + 2];
-    const float inv_d = 1.0f / (float)a.K;
-    const float mean = stat[2 * frow] * inv_d;
-    const float var = fmaxf(stat[2 * frow + 1] * inv_d - mean * mean, 0.f);
-    const float rstd = 1.0f / sqrtf(var + 1e-5f);      // eps 1e-5 (transformer.py:30)
-    sum[0] = rstd * (sum[0] - mean * ewg.x); sum[1] = rstd * (sum[1] - mean * ewg.y);
-    sum[2] = rstd * (sum[2] - mean * ewg.z); sum[3] = rstd * (sum[3] - mean * ewg.w);
-    gemm_epilogue<WT, EPI_QKV>(a, sum, frow, nfin, 0, 0, 1, eb, epos, eseq);
-  }
+#define VC_QP_FRAG(t, F, w) const uint4 w = wf[t][g];
+#include "vc_gemm_qp_body.h"
 }
 template <typename WT, int NPW, int RMAX>
 static hipError_t launch_qp_n(const GemmArgs& a, hipStream_t s) {

@@ -121,3 +121,131 @@ struct W8Kind {
 hipError_t vc_launch_gemm_fr1_w8(const GemmArgs& a, const uint4* planes, const uint32_t* side, int pro, int epi, hipStream_t s) {
   return vc_fr1_launch_packed<W8Kind>(a, planes, side, pro, epi, s);
 }
+
+// ------------------------------------------------------------------ the paired kernels of 2..8-row steps on the code bytes (option "w8r")
+// rows_gemm_frp_k (FFN-down) and rows_gemm_qp_k (QKV of layers 1..) read the images the planes are made from, with the one-row kernel's
+// lane mapping: a wave's NPW consecutive fragments of a tile are NG = NPW / 4 whole groups.  The shared bodies (vc_gemm_frp_body.h,
+// vc_gemm_qp_body.h) with the burst above in place of the image loads: X staging, B columns, reduction order, row statistics and
+// epilogues are the image kernels' text and the MFMA operands are bit-identical, so every result is.  24 / 32 VGPRs of bytes where the
+// image kernels hold 48 / 64 of weights.
+template <int NG, int RMAX>
+__global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_frp_w8_k(const W8Args wa) {
+  using WT = bf16_t;
+  constexpr int NPW = 4 * NG, GROUP = 4;
+  const GemmArgs& a = wa.g;
+#define VC_FRP_EARLY                                                                                                                   \
+  const long G0 = ((long)nt * NW + wave) * NG;                                                                                         \
+  uint32_t sb[NG];                                                                                                                     \
+  _Pragma("unroll") for (int g = 0; g < NG; ++g) sb[g] = wa.side[G0 + g];
+#define VC_FRP_BURST                                                                                                                   \
+  const uint4* gbase = wa.planes + G0 * VC_W8_GROUP_U4;                  /* wave-uniform */                                             \
+  uint4 pa[NG], pb[NG];                                                                                                                \
+  _Pragma("unroll") for (int g = 0; g < NG; ++g) {                                                                                     \
+    const uint4* gp = gbase + g * VC_W8_GROUP_U4;                                                                                      \
+    pa[g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + wunit)));                         \
+    pb[g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + 64 + wunit)));                    \
+    __builtin_amdgcn_sched_barrier(0);                                                                                                 \
+  }                                                                                                                                    \
+  _Pragma("unroll") for (int g = 0; g < NG; ++g) asm volatile("" : "+s"(sb[g]));
+#define VC_FRP_FRAG(F, w) const uint4 w = w8_frag<F>(pa[g], pb[g], sb[g]);
+#include "vc_gemm_frp_body.h"
+}
+// Three tiles per workgroup: group g of tile t of wave w = (((3 blockIdx.x + t) NW + w) NG + g), requested tile by tile as the image is.
+template <int NG, int RMAX>
+__global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_qp_w8_k(const W8Args wa) {
+  using WT = bf16_t;
+  constexpr int NPW = 4 * NG, GROUP = 4;
+  const GemmArgs& a = wa.g;
+#define VC_QP_EARLY                                                                                                                    \
+  const long G0 = ((long)blockIdx.x * NTQ * NW + wave) * NG;             /* tile t: + t * NW * NG */                                    \
+  uint32_t sb[NTQ][NG];                                                                                                                \
+  _Pragma("unroll") for (int t = 0; t < NTQ; ++t)                                                                                      \
+    _Pragma("unroll") for (int g = 0; g < NG; ++g) sb[t][g] = wa.side[G0 + t * (NW * NG) + g];
+#define VC_QP_BURST                                                                                                                    \
+  const uint4* gbase = wa.planes + G0 * VC_W8_GROUP_U4;                  /* wave-uniform */                                             \
+  uint4 pa[NTQ][NG], pb[NTQ][NG];                                                                                                      \
+  _Pragma("unroll") for (int t = 0; t < NTQ; ++t)                                                                                      \
+    _Pragma("unroll") for (int g = 0; g < NG; ++g) {                                                                                   \
+      const uint4* gp = gbase + (t * (NW * NG) + g) * VC_W8_GROUP_U4;                                                                  \
+      pa[t][g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + wunit)));                    \
+      pb[t][g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + 64 + wunit)));               \
+      __builtin_amdgcn_sched_barrier(0);                                                                                               \
+    }                                                                                                                                  \
+  _Pragma("unroll") for (int t = 0; t < NTQ; ++t)                                                                                      \
+    _Pragma("unroll") for (int g = 0; g < NG; ++g) asm volatile("" : "+s"(sb[t][g]));
+#define VC_QP_FRAG(t, F, w) const uint4 w = w8_frag<F>(pa[t][g], pb[t][g], sb[t][g]);
+#include "vc_gemm_qp_body.h"
+}
+
+// Groups per wave of the w8 form of the paired producer / consumer for `rows` rows of an [N x K] matrix, 0 = no form: the image
+// kernel's own form (vc_gemm_frp_ok / vc_gemm_qp_ok), bf16, and a wave's fragments per tile whole groups.  (QKV at d = 1024 has two
+// fragments per wave and tile, half a group: it stays on the image.)
+int vc_gemm_frp_w8_ng(int rows, int N, int K, int dtype) {
+  if (dtype != VC_DTYPE_BF16 || !vc_gemm_frp_ok(rows, N, K, dtype)) return 0;
+  const int npw = K / (64 * VC_FR_WAVES);
+  if (npw % VC_W8_GROUP_FRAGS != 0) return 0;
+  const int ng = npw / VC_W8_GROUP_FRAGS;
+  return (ng == 1 || ng == 2 || ng == 4) ? ng : 0;      // (K = 16384, four rows at the most, stays on the image)
+}
+int vc_gemm_qp_w8_ng(int rows, int N, int K, int dtype) {
+  if (dtype != VC_DTYPE_BF16 || !vc_gemm_qp_ok(rows, N, K, dtype)) return 0;
+  return K * 2 / 1024 == VC_W8_GROUP_FRAGS ? 1 : 0;
+}
+// the launch of one of the two kernels: dynamic LDS beyond 64 KB is granted once per kernel and device
+static hipError_t launch_rows_w8(void (*kern)(const W8Args), size_t* granted, const W8Args& wa, int grid, size_t lds, int lc, hipStream_t s) {
+  if (lds > 64 * 1024) {
+    int dev = 0;
+    if (hipError_t ge = hipGetDevice(&dev); ge != hipSuccess) return ge;
+    if (dev >= 0 && dev < 16 && lds > granted[dev]) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      granted[dev] = lds;
+    }
+  }
+  ++vc_launch_counts[lc];                      // the form the image kernel counts in
+  ++vc_launch_counts[VC_LC_W8_ROWS];
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * VC_FR_WAVES), lds, s, wa);
+  return hipGetLastError();
+}
+// vc_launch_gemm_frp on the E4M3 bytes of a.Wp's image (W28)
+hipError_t vc_launch_gemm_frp_w8(const GemmArgs& a0, const uint4* planes, const uint32_t* side, hipStream_t s) {
+  const int ng = vc_gemm_frp_w8_ng(a0.n_rows, a0.N, a0.K, VC_DTYPE_BF16);
+  if (!ng || !planes || !side) return hipErrorInvalidValue;
+  W8Args wa;
+  wa.g = a0;
+  wa.g.n_tiles = a0.N / VC_TH_RES;
+  wa.g.KT = a0.K / 32;
+  const int upr = a0.K * 2 / 16;
+  wa.g.x_upr_shift = 0;
+  while ((1 << wa.g.x_upr_shift) < upr) ++wa.g.x_upr_shift;
+  wa.planes = planes;
+  wa.side = side;
+  const int rmax = a0.n_rows <= 4 ? 4 : 8;
+  static size_t granted[3][2][16] = {{{0}}};   // per kernel and device
+  void (*kern)(const W8Args) = nullptr;
+  int slot = 0;
+#define VC_FRP_W8_CASE(G_, S_) case G_: kern = rmax == 4 ? rows_gemm_frp_w8_k<G_, 4> : rows_gemm_frp_w8_k<G_, 8>; slot = S_; break;
+  switch (ng) {
+    VC_FRP_W8_CASE(1, 0) VC_FRP_W8_CASE(2, 1) VC_FRP_W8_CASE(4, 2)
+    default: return hipErrorInvalidValue;
+  }
+#undef VC_FRP_W8_CASE
+  const size_t lds = (size_t)rmax * a0.K * sizeof(bf16_t) + 256 + (size_t)VC_FR_WAVES * rmax * 4 * sizeof(f32x4);
+  return launch_rows_w8(kern, granted[slot][rmax == 8], wa, wa.g.n_tiles, lds, VC_LC_ROWS_GEMM_FRP, s);
+}
+// vc_launch_gemm_qp on the E4M3 bytes of a.Wp's image (Wqkv8)
+hipError_t vc_launch_gemm_qp_w8(const GemmArgs& a0, const uint4* planes, const uint32_t* side, hipStream_t s) {
+  const int ng = vc_gemm_qp_w8_ng(a0.n_rows, a0.N, a0.K, VC_DTYPE_BF16);
+  if (ng != 1 || !planes || !side || a0.x_in == nullptr || a0.row_mu == nullptr) return hipErrorInvalidValue;
+  W8Args wa;
+  wa.g = a0;
+  wa.g.n_tiles = a0.N / VC_TH_RES;
+  wa.g.KT = a0.K / 32;
+  wa.planes = planes;
+  wa.side = side;
+  const int rmax = a0.n_rows <= 4 ? 4 : 8;
+  static size_t granted[2][16] = {{0}};        // per kernel and device
+  void (*kern)(const W8Args) = rmax == 4 ? rows_gemm_qp_w8_k<1, 4> : rows_gemm_qp_w8_k<1, 8>;
+  const size_t lds = (size_t)rmax * a0.K * sizeof(bf16_t) + 256 + (size_t)VC_FR_WAVES * rmax * 3 * 4 * sizeof(f32x4) + (size_t)rmax * 2 * sizeof(float);
+  return launch_rows_w8(kern, granted[rmax == 8], wa, wa.g.n_tiles / 3, lds, VC_LC_ROWS_GEMM_QP, s);
+}

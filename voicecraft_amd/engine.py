@@ -51,7 +51,7 @@ class VoiceCraftEngine:
 
     def __init__(self, args: Namespace | dict, state_dict: dict[str, torch.Tensor], device="cuda:0",
                  dtype="bf16", max_seqs: int = 8, max_positions: int = 4096, use_graph: bool = True, w8: str | None = None,
-                 kv8: bool | str = False):
+                 kv8: bool | str = False, w8_rows: bool = False):
         """kv8: False (default: nothing changes) | True | "centred" - decode passes of a bf16 engine read the cached K / V positions older than the pass
         as one E4M3 byte per value times a per-row shift (option `kv8`, csrc/vc_kv8.h, quant.kv8_quantize_rows): half the bytes of the
         launch that grows with the batch, 3 mantissa bits left of a cached value, 1.5 x the K/V memory.  Works with every call and `w8=`.
@@ -62,8 +62,13 @@ class VoiceCraftEngine:
         as one E4M3 byte per value (option `w8`, csrc/vc_w8.h), bit-identical to the bf16 launches on the same weights.  "quantize" first
         puts those matrices on the 8-bit grid (quant.quantize_state_dict_w8, on the CPU) and keeps the result as `self.w8_state_dict`,
         the checkpoint this engine then computes; "as_is" takes the weights as given: a matrix off the grid comes back refused
-        (w8_stats()) and keeps its bf16 launch."""
+        (w8_stats()) and keeps its bf16 launch.
+        w8_rows: False (default: nothing changes) | True, with `w8=` only (ValueError without it) - steps of 2..8 rows stream the same
+        bytes too (option `w8r`, mask W8_ROWS_MASK: the FFN down-projection at d = 512 / 1024 / 2048, the QKV projection of layers 1..
+        at d = 2048 up to 6 rows), bit-identical to the image launches; launch_counts()["w8_rows"] counts them."""
         self.lib = _lib.load()
+        if w8_rows and w8 is None:
+            raise ValueError('w8_rows=True streams the planes of `w8=`: give w8="quantize" or w8="as_is" too')
         if isinstance(kv8, str) and kv8 != "centred":
             raise ValueError(f'kv8 = {kv8!r}: False, True or "centred"')
         a = Namespace(**args) if isinstance(args, dict) else Namespace(**vars(args))
@@ -110,6 +115,8 @@ class VoiceCraftEngine:
         check(self.lib.vc_create(C.byref(cfg), index, C.byref(self._h)), None, "vc_create")
         if w8 is not None:
             check(self.lib.vc_request_w8(self._h, self.W8_MASK), self._h, "vc_request_w8")
+        if w8_rows:
+            check(self.lib.vc_request_w8_rows(self._h, self.W8_ROWS_MASK), self._h, "vc_request_w8_rows")
         self.kv8 = bool(kv8)
         self.kv8_centred = kv8 == "centred"
         if self.kv8_centred:
@@ -704,7 +711,8 @@ class VoiceCraftEngine:
         forms (finished_rows, fr_pair, att_p16, hq), ta = tile_attn (kernel, min rows), r1 = one-row and attention forms (fr_one,
         attn_fast, qkv_p8), q16 = many-row steps (qkv16, wide_heads, wide_gemm, wd_stage), sh = shrink, w13 = the one-row launches that
         stream their weights as exact 13-bit planes (mask: 1 FFN-down, 4 QKV; w13_stats() says which matrices have planes); an engine
-        created with `w8=` appends w8 = the launches that stream E4M3 bytes instead (same bits, w8_stats()), one created with `kv8=True`
+        created with `w8=` appends w8 = the launches that stream E4M3 bytes instead (same bits, w8_stats()), one created with `w8_rows=True`
+        w8r = the launches of 2..8-row steps that do (same bits) behind it, one created with `kv8=True`
         appends kv8 = decode attention on the E4M3 copy of the K/V cache (1) or on the bf16 cache (0), one created with `kv8="centred"`
         kv8c = 1 behind it.
         bench.py turns it into a JSON object (`config.engine_options`)."""
@@ -723,11 +731,12 @@ class VoiceCraftEngine:
 
     LAUNCH_FORMS = ("rows_gemm", "mt2", "mt4", "blk64", "blk128_sbs", "blk128_2x2", "blk64_occ2", "ln_rows", "rows_attn",
                     "tile_attn", "rows_gemm_fr", "big256", "big128", "row_gemm_fr1", "tile_attn64", "rows_gemm_frp", "wd", "rows_gemm_qp", "w13", "w8",
-                    "kv8_attn", "kv8_pack", "kv8c_centre", "kv8c_attn", "kv8c_pack")
+                    "kv8_attn", "kv8_pack", "kv8c_centre", "kv8c_attn", "kv8c_pack", "w8_rows")
 
     def launch_counts(self) -> dict:
         """Process-wide census of the kernel FORMS launched so far (vc_common.h VC_LC_*): the parity tests take the
-        difference around a call to assert which form a benchmarked shape really runs on."""
+        difference around a call to assert which form a benchmarked shape really runs on.  w13 / w8 / w8_rows count launches on packed
+        weights IN ADDITION to their form's slot: w8 the one-row launches, w8_rows those of 2..8-row steps (rows_gemm_frp / rows_gemm_qp)."""
         c = self.debug_read("launch_counts", (len(self.LAUNCH_FORMS),), torch.int64)
         return {n: int(c[i]) for i, n in enumerate(self.LAUNCH_FORMS)}
 
@@ -745,6 +754,7 @@ class VoiceCraftEngine:
 
     W8_MATRICES = ("ffn_down", "qkv")       # mask bits 1 and 4 of option `w8`, the matrices quant.quantize_state_dict_w8 converts
     W8_MASK = 5
+    W8_ROWS_MASK = 5                        # option `w8r` of an engine created with w8_rows=True
 
     def w8_stats(self) -> list:
         """w13_stats() for option `w8`: per layer {"ffn_down" | "qkv": {"state": "packed" | "refused" | "not_applicable",
