@@ -88,7 +88,7 @@ def row_actions(steps):
 
 
 def simulate(actions, schedule, max_live, G, top=None):
-    """The session's host logic replayed on the CPU (vc_engine.hip vc_session_advance; DecodeSession.poll fetches what a turn reports
+    """The session's host logic replayed on the CPU (vc_engine_session.hip vc_session_advance; DecodeSession.poll fetches what a turn reports
     and so frees those slots for the NEXT turn).  A request admitted in front of batch a takes row step 0 (its first sample) there and
     row step j >= 1 in batch a + (j - 1) // G; it retires in the batch of its last row step, and the host counts that once it has seen
     that batch end (two batches may be in flight).  Returns the counters of DecodeSession.stats(), the request indices each poll

@@ -14,7 +14,9 @@ from pathlib import Path
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = HERE / "libvcengine.so"
-SOURCES = ["vc_gemm.hip", "vc_gemm_pf.hip", "vc_gemm_wd.hip", "vc_gemm_w13.hip", "vc_gemm_w8.hip", "vc_attn.hip", "vc_tokens.hip", "vc_engine.hip", "vc_codec.hip"]
+SOURCES = ["vc_gemm.hip", "vc_gemm_pf.hip", "vc_gemm_wd.hip", "vc_gemm_w13.hip", "vc_gemm_w8.hip", "vc_attn.hip", "vc_tokens.hip",
+           "vc_engine.hip", "vc_engine_session.hip", "vc_engine_eval.hip",      # the host units (vc_engine_host.h is what they share)
+           "vc_codec.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -83,7 +85,8 @@ def build(force: bool = False, verbose: bool = False, variant: str = "", extra_f
         tu_stamp.write_text(tu_digest)
         if verbose and out.strip():
             print(out, file=sys.stderr)
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(LIB), *map(str, objs)]
+    # the host units call each other: a prototype without a definition fails here, not when the library is first loaded
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", str(LIB), *map(str, objs)]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"link failed:\n{r.stdout}")

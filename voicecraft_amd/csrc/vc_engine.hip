@@ -4,259 +4,14 @@
 //
 // Control flow restated from VoiceCraft.inference_tts / inference_tts_batch / inference
 // (models/voicecraft.py:908-1153, :1156-1439, :561-906); see DESIGN.md §2 for the mapping.
-#include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <limits.h>
-#include <string.h>
-
-#include <algorithm>
-#include <chrono>
-#include <deque>
-#include <map>
-#include <string>
-#include <tuple>
-#include <vector>
-
-#include "vc_common.h"
+#include "vc_engine_host.h"
 
 namespace {
 
 std::string g_create_err;
 
-struct RawTensor {
-  std::vector<int64_t> shape;
-  float* dev = nullptr;   // fp32 staging copy in HBM
-  long numel = 0;
-};
-
-struct Layer {
-  uint4 *Wqkv = nullptr, *Wo = nullptr, *W1 = nullptr, *W2 = nullptr;
-  uint4 *Wo8 = nullptr, *W28 = nullptr;                                 // Wo / W2 once more in 8-channel tiles (finished-row producers, vc_gemm.hip)
-  uint4 *Wqkv16 = nullptr;                                              // Wqkv . gamma in 16-channel tiles (prefill and wide-decode passes, option "qkv16")
-  uint4 *Wqkv8 = nullptr;                                               // Wqkv . gamma in 8-channel tiles (one-row paired QKV kernel, option "qkv_p8")
-  float *bqkv = nullptr, *bo = nullptr, *b1 = nullptr, *b2 = nullptr;   // bqkv / b1 hold the FOLDED biases (W beta + b)
-  float bo_mean = 0.f, b2_mean = 0.f;   // mean over the d channels of bo / b2: what the update moves a row's mean by whatever its input (GemmArgs.mu_shift)
-  float *wg_qkv = nullptr, *wg_1 = nullptr;                             // row sums of the folded weights W . gamma
-  void *kc = nullptr, *vc = nullptr;   // KV cache of this layer: WT [max_seqs][H][S_max][hd]
-  // on request (vc_request_kv8): the same rows as E4M3 bytes, uint8 [max_seqs][H][S_max][hd], and their shifts, int8 [max_seqs][H][S_max][2] (K, V)
-  unsigned char *kc8 = nullptr, *vc8 = nullptr;
-  signed char* sh8 = nullptr;
-  void* kcen = nullptr;      // on request (vc_request_kv8c): the K centres of this layer, bf16 [max_seqs][H][hd] (vc_kv8.h)
-  // W28 / Wqkv8 once more in the packed forms of vc_packed (vc_common.h): [VC_PK_W13] exact 13-bit planes (option "w13", vc_w13.h) and, on request
-  // (vc_request_w8), [VC_PK_W8] E4M3 bytes with one shift byte per fragment (option "w8", vc_w8.h); second index W13_F2 / W13_QKV
-  struct Packed {
-    uint4* planes = nullptr;
-    uint32_t* side = nullptr;      // one byte per fragment
-    int state = 0;                 // 0 not applicable (or not packed), 1 packed, 2 refused: the launch stays on the bf16 image
-    int refused = 0;               // fragments the packer refused
-  } packed[VC_PK_N][2];
-};
-enum { W13_F2 = 0, W13_QKV = 1 };
-constexpr int W8_BITS[2] = {1, 4};        // the mask bits of options "w13" / "w8" and of vc_request_w8 for W13_F2, W13_QKV
-
-struct Plan { int n_tiles, KT, ksplit, nchunk; };
-
-// Words of the pinned vc_engine::h_flag block.  HF_ACTIVE / HF_LIVE0..1 are written by the device (SampleArgs.host_active / host_live: the
-// sequences still active; the two slots of "sequences still live as the LAST step of a batch found them"), HF_GATHER_N by stream_gather_k.
-enum { HF_ERR = 0, HF_STAGE = 1, HF_SHARE = 2, HF_ACTIVE = 8, HF_LIVE0 = 9, HF_LIVE1 = 10, HF_LIVE_STEPS = 11, HF_GATHER_N = 12 };
-// vc_engine::host_ms (vc_debug_read "host_ms": read by position): graph capture / instantiation of the last call, its decode loop's host
-// time, the decode steps it LAUNCHED (a multiple of steps_per_graph; the tail are no-ops) and the re-packs that moved live sequences.
-enum { HM_CAPTURE = 1, HM_INSTANTIATE = 2, HM_LOOP = 3, HM_SPARE = 4, HM_LAUNCHED = 5, HM_REPACKS = 6 };
-// Session::stats (vc_session_stats: read by position; [7] is the admission time).  The row sums count every sample's rows.
-enum { SS_ADMITTED = 0, SS_ADMITTED_LIVE = 1, SS_TURNS = 2, SS_WIDENINGS = 3, SS_NARROWINGS = 4, SS_LIVE_ROWS = 5, SS_LAUNCHED_ROWS = 6 };
-
 }  // namespace
-
-struct vc_engine {
-  vc_model_cfg cfg{};
-  int device = 0;
-  int dtype = -1;
-  bool finalized = false;
-  std::string err;
-  std::map<std::string, RawTensor> raw;
-  std::vector<void*> allocs;
-
-  int d = 0, H = 0, hd = 0, L = 0, K = 0, V = 0, P = 0, S_max = 0, B_max = 0;
-  int esz = 2;
-
-  std::vector<Layer> layers;
-  uint4 *Wh1 = nullptr, *Wh2 = nullptr;
-  float *bh1 = nullptr, *bh2 = nullptr, *wg_h1 = nullptr;               // bh1: folded with the final LayerNorm
-  long wh2_group_stride = 0;
-  float *text_emb = nullptr, *audio_emb = nullptr, *mask_emb = nullptr, *pe = nullptr;
-  float alpha_text = 1.f, alpha_audio = 1.f;
-  Plan p_qkv{}, p_o{}, p_f1{}, p_f2{}, p_h1{}, p_h2{};
-  Plan p_qkv16;                         // the same matrix on 16-channel tiles (Layer.Wqkv16)
-
-  // activations / scratch
-  float *emb = nullptr;                 // prefill rows [emb_cap][d] (one or several prompts back to back)
-  int emb_cap = 0;
-  int *pre_row_seq = nullptr, *pre_row_pos = nullptr;
-  float *hA = nullptr, *hB = nullptr, *q = nullptr, *parts = nullptr, *att_o = nullptr, *att_ml = nullptr;
-  void *act = nullptr, *hh = nullptr, *xn = nullptr;
-  float *logits = nullptr;              // [B_max][K][V]
-  float *dec_h = nullptr;               // [max(VC_ROWS, max_seqs)][d]
-  int NS = VC_ROWS;                     // rows the per-sequence buffers are sized for
-  int *dec_row_seq = nullptr, *dec_row_pos = nullptr, *logit_row = nullptr;
-  SeqState *st = nullptr, *st_fin = nullptr;      // st_fin: final states by slot of sequences a re-pack moved out of the step (repack_k)
-  long long* dbg_ts = nullptr;
-  int *one = nullptr;                   // device word holding 1: the "always active" flag of prefill launches
-  int *share_len = nullptr;             // device word: text positions shared with sequence 0 (AttnArgs.share_len), 0 outside such calls
-  int *step_ctr = nullptr;              // SampleArgs.step_ctr
-  int *n_active = nullptr, *samp = nullptr, *cond = nullptr, *amax = nullptr, *gen = nullptr, *err_flag = nullptr;
-  int gen_cap = 0;
-  // pinned host staging
-  SeqState *h_st = nullptr, *h_st2 = nullptr;
-  int *h_flag = nullptr;                // indexed by HF_*: error/poll word, staging, "sequences still active" written by the device,
-                                        // SampleArgs.host_live, the decode loop's live steps (step_ctr, after a re-packed call)
-  SampleDyn *h_dyn = nullptr, *d_dyn = nullptr;   // per-call sampler values (vc_common.h)
-  // captured decode steps, kept across calls: key = (sequences, rows per sequence, best-of-N)
-  // ... and by the option state they were captured under (vc_set_option): toggling an option back and forth reuses the captures
-  std::map<std::pair<std::tuple<int, int, int>, std::string>, hipGraphExec_t> graphs;
-  std::string opt_state;                // canonical text of every option that shapes a decode step
-  int steps_per_graph = 8;              // VC_GRAPH_STEPS: decode steps captured into one graph launch
-  hipEvent_t ev_pace[2]{};
-  std::vector<int> repack_at;           // decode_loop: the batch index before which each re-pack of the last call was queued
-
-  hipStream_t own_stream = nullptr;     // used when the caller passes the null stream (not capturable)
-  hipStream_t side_stream = nullptr;    // vc_tts_stream_next gathers finished frames here: never behind the decode stream's queued graphs
-  struct TtsStream* ts = nullptr;       // the open streaming TTS call (vc_tts_stream_begin .. vc_tts_stream_end), else NULL
-  struct Session* sess = nullptr;       // the open decode session (vc_session_open .. vc_session_close), else NULL
-  // decode sessions: per-slot Philox keys, the batch index the sampler stamps retirements with, where this turn's admitted rows start and
-  // whose they are, prompt_k's error bits by slot, the prefill's own gather rows (the decode step's logit_row stays the live rows'), and the
-  // pinned retirement records the host reads (vc_common.h VC_SESS_REC)
-  uint64_t* seed_tab = nullptr;
-  int* samp_tab = nullptr;  // [NS] by slot: sample index | sample count << 16 of the row's request (sessions opened for best-of-N requests)
-  int *batch_id = nullptr, *row_base = nullptr, *adm_slot = nullptr, *prompt_err = nullptr, *sess_gather = nullptr;
-  int* h_rec = nullptr;
-  // ... the requests' sampling controls by slot (SampleDyn.ctl_tab), and the staging of a turn's admitted requests: their first states
-  // and controls, written by the host into one of VC_ADM_STAGES pinned buffers (rotated by batch index, see vc_session_advance) and
-  // uploaded on the decode stream into adm_st / adm_ctl in front of session_turn_k
-  vc_request_ctl *ctl_tab = nullptr, *adm_ctl = nullptr, *h_adm_ctl = nullptr;
-  SeqState *adm_st = nullptr, *h_adm_st = nullptr;
-  // Non-temporal weight loads of the decode kernels, per matrix: bit 0 QKV, 1 out-projection, 2 FFN-up, 3 FFN-down, 4 heads-1, 5 heads-2.
-  // Option "nt" (VC_NT).  Until round 4 the compiled QKV / out-projection / heads-2 kernels carried NO such load whatever this said (the
-  // compiler merged the kernel's two load arms and dropped the hint): 28 reproduces that mix, 63 = every matrix (default), 0 = none.
-  int nt_decode = 63;
-  // option "nt", second value: the decode attention's K/V loads carry the hint too - 0 never, 1 always, 2 (default) from two rows per step up
-  // (in-process A/Bs, profiles/r04d_bench_*attn_nt*: one row +0.3 % +- 0.09 - there the launch is latency-bound and carries the prefetch
-  // role -, 8 rows -4.8 % +- 0.05, 32 rows -6.5 % +- 0.05: several caches stream 58-230 MB per layer through L2 otherwise)
-  int attn_nt = 2;
-  // finished-row form of passes of 2..fr_rows rows (plan_pass): 0 = off.  VC_FINISHED_ROWS / option "finished_rows"
-  int fr_rows = VC_ROWS;
-  // option "tile_attn": prefill attention kernel - 1 = tile_attn_k (16 query rows per wave, keys split over the waves), 2 =
-  // tile_attn64_k (64 query rows per workgroup, transposed score product, P in registers; bf16 / head_dim 128 only, prompts are then
-  // laid out on 64-row boundaries)
-  // Default 2 when the call's longest prompt has at least 768 rows ("tile_attn" = "k[,min_rows]"): measured on one layer of giga830M (profiles/r04o_attn64_probe.log)
-  // 512 / 800 / 2048 causal rows: 14.3 / 24.6 / 86.7 us (first kernel) against 15.5 / 21.0 / 52.5 us (second).
-  int tile_attn = 2, tile_attn_min_rows = 768;
-  // option "fr_one" (round 5): ONE-row steps - the FFN down-projection finishes its row (row_gemm_fr1_k: 8-channel tiles over the whole K,
-  // two k-tiles per MFMA fragment, residual + bias added) instead of leaving 4 split-K slabs, so the next layer's QKV projection (and
-  // heads-1) reads one 8 KB row instead of h + bias + 4 slabs = 40 KB in each of its 512 workgroups; 0 = off
-  int fr_one = 1;
-  // option "fr_pair" (round 5): the FFN down-projection of 2..8-row steps with two k-tiles per MFMA fragment (rows_gemm_frp_k) instead
-  // of half-filled 8-channel fragments (rows_gemm_fr_k)
-  int fr_pair = 1;
-  // option "qkv_p8" (round 5): one-row steps behind a finished row (fr_one) run the QKV projection on 8-channel tiles with two k-tiles
-  // per MFMA fragment (row_gemm_fr1_k<PRO_LN, EPI_QKV>: every lane's 16 bytes are weights) instead of 12-channel tiles; 2 (round 6): steps of
-  // 2..8 finished rows too, behind the producers' centred copy (rows_gemm_qp_k)
-  int qkv_p8 = 2;
-  // option "qkv16" (round 5): prefill passes and wide decode passes (17..64 rows) run the QKV projection on a 16-channel image of the
-  // folded matrix (every A lane of every MFMA a weight) instead of the 12-channel tiles one-row steps were tuned on; + 6 d^2 bytes per
-  // layer in bf16 (0.4 GB at giga830M).  Packed for engines that can take wide steps (max_seqs > 16) or with VC_QKV16=1 at creation;
-  // otherwise the option stays off and prefill passes read the 12-channel tiles.
-  int qkv16 = 1;
-  // option "wide_heads" (round 5): decode steps of 17..64 rows run the prediction heads once on the weight-stationary kernel of those
-  // steps (one LayerNorm launch + two rows_gemm_mt_k launches) instead of once per 16 rows on the rows-GEMM
-  int wide_heads = 1;
-  // option "wide_gemm" (round 6): the linear layers of 17..64-row steps on rows_gemm_wd_k (vc_gemm_wd.hip: every row tile of the step in
-  // flight at once, X fragments straight from L2 into registers, one barrier per launch) instead of the weight-stationary
-  // rows_gemm_mt_k, which walks the row tiles one after the other; 0 = that kernel (two weight tiles per workgroup)
-  int wide_gemm = 1;
-  // option "wd_stage": 1 (default) = that kernel takes X as whole cache lines through a wave-private LDS stage (rows_gemm_wds_k: 64 rows FFN-up
-  // 13.5 -> 9.7 us, the 64-row step -9.5 % +- 0.01, 32 rows -2.7 %; profiles/r06c_*), 0 = MFMA fragments straight from L2 (16 half lines per request)
-  int wd_stage = 1;
-  // option "shrink" (round 6): a multi-utterance call whose sequences retire at different steps re-packs the live ones onto the rows of a
-  // narrower step (the next power of two >= the live count: 64 -> 32 -> 16 -> 8 -> 4 -> 2 -> 1) instead of keeping its launch form until
-  // the longest sequence ends; 0 = the fixed width of rounds 1-5.  Results do not depend on it: everything per sequence is indexed by its slot.
-  int shrink = 1;
-  // weight images vc_finalize_weights packed: Layer.Wo8 / W28, Layer.Wqkv8, Layer.Wqkv16 (the forms that read one, plan_pass)
-  bool has_fr8 = false, has_qkv8 = false, has_qkv16 = false;
-  // option "w13": one-row steps stream the FFN down-projection (1) and the QKV projection (4) as exact 13-bit planes of the same bf16
-  // values (vc_gemm_w13.hip: 13/16 of the bytes, results bit-identical).  bf16 engines; planes packed at creation unless VC_W13=0
-  // (+ 0.81 x the two images: 0.76 GB at giga830M); a matrix the packer refuses keeps its bf16 launch.  (Bit 2, the FFN up-projection, was
-  // built and measured +0.1 % +- 0.03 per step: it left the tree with its kernel)
-  int w13 = 5;
-  bool has_w13 = false;
-  unsigned int* w13_counts = nullptr;   // two device words of the packer: fragments refused, dwords that did not decode to the image
-  // option "w8": the same two launches stream E4M3 bytes + one shift byte per fragment (vc_gemm_w8.hip: half the bytes of the image,
-  // results bit-identical) for matrices that lie on that grid (voicecraft_amd/quant.py).  Only on an engine that asked for it before
-  // vc_finalize_weights (vc_request_w8: w8_req); a matrix off the grid is refused and keeps its current launch.  Where a matrix has both
-  // kinds of planes the w8 bit wins.  An engine without the request packs nothing and has no such option.
-  int w8_req = 0;
-  int w8 = 0;
-  // option "w8r": steps of 2..8 finished rows stream the same planes - the FFN down-projection (1) on rows_gemm_frp_w8_k, the QKV
-  // projection of layers 1.. (4) on rows_gemm_qp_w8_k, results bit-identical -, where plan_pass takes the form.  Only on an engine
-  // that asked for it after vc_request_w8 (vc_request_w8_rows: w8r_req, a subset of w8_req); any other engine has no such option
-  // and launches what it launched before.
-  int w8r_req = 0;
-  int w8r = 0;
-  // option "kv8": decode passes read the cached positions older than the pass from an E4M3 copy of the K / V cache (Layer.kc8 / vc8 / sh8,
-  // vc_kv8.h: one byte per value, one shift per cached row of a head - half the bytes of the launch that grows with the batch), which
-  // one kv8_pack_k launch behind every pass keeps equal to the quantiser of the bf16 rows.  This changes values (3 mantissa bits), so:
-  // only on an engine that asked for it before vc_finalize_weights (vc_request_kv8: kv8_req); 0 = such an engine reads bf16 again (it
-  // goes on packing).  An engine without the request allocates nothing, launches nothing more and has no such option.
-  int kv8_req = 0;
-  int kv8 = 0;
-  Kv8Layer* kv8_tab = nullptr;          // device table [L] of the layers' five arrays (Kv8PackArgs.layers)
-  // "kv8c" (vc_request_kv8c, implies the above; the contract is in vc_kv8.h): K meets the grid as k - c, c the mean K row of the prefill
-  // pass that wrote the slot's position 0, per layer, slot and head (Layer.kcen; kv8c_centre_k in front of the packer on prefill passes);
-  // the decode attention adds q . c to its 8-bit scores.  Fixed at creation: option "kv8" switches between this and the bf16 cache.
-  int kv8c_req = 0;
-  void** kcen_tab = nullptr;            // device table [L] of the layers' centre arrays
-  int* kcen_rows = nullptr;             // device [max_seqs]: n0, the rows each slot's centre is the mean of
-  int cur_rows = 0;                     // rows per step the last decode loop ended on (tts_run reads the states back accordingly)
-  // option "attn_fast": decode attention with the wave's maximum taken before any exponential (no online rescaling inside a wave) and,
-  // in bf16 mode, hardware exp2 (v_exp_f32) instead of expf
-  int attn_fast = 1;
-  // option "hq" (round 6): the finished-row producers of 2..16-row steps also write their rows CENTRED and in the compute dtype (hqA / hqB =
-  // WT(h - c), c = the row's mean as the previous LayerNorm found it: row_mu ping-pong), and the LayerNorm-folding consumers read that copy
-  // (PRO_LNQ: half the bytes of the fp32 row in bf16 mode, no conversion) - the fold is exact for any centring constant
-  int hq = 1;
-  void *hqA = nullptr, *hqB = nullptr;  // centred copies of hA / hB, WT [VC_ROWS][d]
-  float* row_mu[2] = {nullptr, nullptr};       // [VC_ROWS] each: ping-pong of the rows' means
-  float* mu_zero = nullptr;             // [VC_ROWS] zeros: GemmArgs.row_mu of every launch that centres nothing
-  // option "att_p16" (round 6; bf16 mode): finished-row passes of 2..8 rows hand the attention's split partials to the out-projection as
-  // bf16 (131 -> 66 KB per out-projection workgroup at 8 rows; the merged row is rounded to bf16 for the MFMA anyway)
-  int att_p16 = 1;
-  static constexpr int attn_blocks_multi = 512, attn_blocks_one = 256;   // attention workgroups aimed at (several rows / one row); 256 -> 64 at one row measured +1.1..+1.8 % (r05f)
-  int prefill_rows_per_pass = VC_MAX_ROWS;   // VC_PREFILL_ROWS=16 falls back to the decode kernels for the prompt
-  hipEvent_t ev[3]{};
-  float ms[3]{0, 0, 0};
-  double host_ms[8]{};                  // host wall clock of the last call's phases, indexed by HM_* (vc_debug_read "host_ms")
-  double bytes_total = 0;               // HBM bytes owned by the engine
-  // training objective (vc_eval_forward), allocated on first use
-  int *ce_tgt = nullptr, *ce_hit = nullptr;
-  float *ce_nll = nullptr;
-  double *ce_sum = nullptr;
-  long long *ce_hits = nullptr, *ce_cnt = nullptr;
-  // parity hook of vc_eval_forward (nll_dev / tgt_dev given): the head logits of every row of the last such call, [rows][K][V]
-  // (vc_debug_read "eval_logits"); allocated by the first call that asks for it and grown on demand, never otherwise
-  float *eval_logits = nullptr;
-  int64_t eval_logits_cap = 0, eval_logits_rows = 0;      // rows allocated / rows the last call left
-};
-
-#define VC_ADM_STAGES 4
-static_assert(sizeof(vc_request_ctl) == 16, "vc_request_ctl is copied as one 16-byte quad (vc_tokens.hip session_turn_k)");
-
-namespace {
-
-inline double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
+namespace vch __attribute__((visibility("hidden"))) {
 int fail(vc_engine* e, int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
@@ -266,32 +21,8 @@ int fail(vc_engine* e, int code, const char* fmt, ...) {
   if (e) e->err = buf; else g_create_err = buf;
   return code;
 }
-
-#define HIPCHK(e, call)                                                                  \
-  do {                                                                                   \
-    hipError_t _err = (call);                                                            \
-    if (_err != hipSuccess)                                                              \
-      return fail(e, VC_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), \
-                  __FILE__, __LINE__);                                                   \
-  } while (0)
-
-template <typename T>
-int dalloc(vc_engine* e, T** p, size_t n) {
-  void* v = nullptr;
-  hipError_t err = hipMalloc(&v, std::max<size_t>(n * sizeof(T), 16));
-  if (err != hipSuccess) return fail(e, VC_EHIP, "hipMalloc(%zu bytes) failed: %s", n * sizeof(T), hipGetErrorString(err));
-  e->allocs.push_back(v);
-  e->bytes_total += (double)(n * sizeof(T));
-  *p = reinterpret_cast<T*>(v);
-  return VC_OK;
-}
-// the void* fields (buffers in the compute dtype): sized in bytes
-inline int dalloc(vc_engine* e, void** p, size_t bytes) {
-  char* c = nullptr;
-  const int rc = dalloc(e, &c, bytes);
-  *p = c;
-  return rc;
-}
+}  // namespace vch
+namespace {
 
 Plan make_plan(int N, int Kdim, int dtype, bool allow_split, const char* env_override, int th = 16) {
   Plan p;
@@ -411,16 +142,6 @@ int keep_vec(vc_engine* e, const std::string& key, int n, float** out, float* me
 }
 
 // ---------------------------------------------------------------- one forward pass
-struct RowSrc {
-  const float* h_in;
-  const int* row_seq;
-  const int* row_pos;
-  int n_rows;       // rows carried
-  const int* n_active;
-  int nt;           // force the streaming-load policy (microbenchmarks)
-  int rps;          // decode passes: rows per sequence (1 or 3: consecutive rows at consecutive positions); 0: a prefill pass (option "kv8")
-};
-
 GemmArgs base_args(vc_engine* e, const RowSrc& rs, const Plan& p, int N, int Kdim) {
   GemmArgs g;
   memset(&g, 0, sizeof g);
@@ -484,29 +205,6 @@ enum { ATT_ROWS = 0, ATT_TILE = 1, ATT_TILE64 = 2 };                 // rows_att
 // workgroups): from this many rows on, a per-row LayerNorm launch plus the plain prologue is cheaper (8 rows 20 us -> ~12 us per GEMM).
 constexpr int ln_split_rows = 3;
 
-// Every launch decision of a pass of `rows` rows: plan_pass below is the one place they are made.
-struct PassPlan {
-  int form;         // FORM_*
-  int attn;         // ATT_*
-  int nsplit;       // attention splits
-  bool att_x;       // the attention is unsplit and normalises its rows into xn; the out-projection takes them with the plain prologue
-  bool part16;      // the split partials in bf16 (option att_p16)
-  bool ln_launch;   // QKV / FFN-up: LayerNorm as its own per-row launch (ln_rows_k) + the plain prologue, else in the GEMM prologue
-  bool hq;          // finished rows: the consumers fold the producers' centred copy (PRO_LNQ) instead of the fp32 rows (PRO_LNW)
-  int mt;           // GemmArgs.mt of the consumers: 0 / 3 / 4 finished rows, 2 wide, 1 block
-  bool fd;          // one row: the FFN down-projection finishes its row (row_gemm_fr1_k, option fr_one)
-  bool qkv_fr1;     // ... and the QKV projection behind it pairs k-tiles on the 8-channel image (option qkv_p8)
-  bool qp;          // 2..8 finished rows: the QKV projection of layers 1.. on rows_gemm_qp_k (qkv_p8 = 2)
-  bool frp;         // finished rows: the FFN down-projection on rows_gemm_frp_k (option fr_pair)
-  bool frp_w8;      // ... on the E4M3 bytes of a layer whose W28 is packed that way (rows_gemm_frp_w8_k, option w8r bit 1)
-  bool qp_w8;       // qp on the E4M3 bytes of a layer whose Wqkv8 is packed that way (rows_gemm_qp_w8_k, option w8r bit 4)
-  bool qkv16;       // wide and block: the QKV projection on the 16-channel image (option qkv16)
-  bool wd;          // wide: the linear layers on rows_gemm_wd_k (option wide_gemm)
-  int ks_o, ks_f2;  // split-K slabs the out-projection / FFN down-projection leave (slab, wide and block forms)
-  bool heads_wide;  // the heads run once over all rows on the wide-step kernels (option wide_heads)
-  bool heads_fold;  // heads-1 folds the finished rows itself (no LayerNorm launch)
-};
-
 // Option "w8r": the row counts at which the w8 form of matrix `which` measured faster than the image over the whole paired range; a
 // row count whose range touches zero would stay on the image.  profiles/w8_rows_ab.log (giga830M, 7 interleaved pairs per line,
 // captured decode loop per step, min..max of the pairs): FFN-down alone -6.3 .. -5.8 % at 2, 3, 4, 6 and 8 rows, QKV alone -4.4 .. -5.0 %
@@ -516,6 +214,8 @@ bool w8r_rows_win(int which, int rows) {
   return rows >= 2 && rows <= 8;
 }
 
+}  // namespace
+namespace vch __attribute__((visibility("hidden"))) {
 // decode: a decode step (n_active set).  tiled: a prefill pass whose 16-row tiles (1) or 64-row blocks (2) each hold consecutive
 // positions of ONE sequence (prefill_batch): MFMA attention; 0 for passes of up to VC_ROWS rows.
 PassPlan plan_pass(const vc_engine* e, int rows, bool decode, int tiled) {
@@ -588,6 +288,8 @@ PassPlan plan_pass(const vc_engine* e, int rows, bool decode, int tiled) {
   p.heads_fold = p.form == FORM_FR && rows <= VC_FR_MAX_ROWS;
   return p;
 }
+}  // namespace vch
+namespace {
 
 // The rows a LayerNorm reads (a launch, or a GEMM prologue): h_in + prev_bias + n_parts split-K slabs; their sum goes to h_out (may be null).
 struct Resid { const float* h_in; float* h_out; int n_parts; const float* prev_bias; };
@@ -790,10 +492,8 @@ int site_ffn_down(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer
   return VC_OK;
 }
 
-// What a pass leaves for the heads in hB: finished rows (n_parts = 0; hq: their centred copy, on the means in mu) or rows whose
-// n_parts split-K slabs and last FFN-down bias are still to be added.
-struct PassOut { int n_parts; const void* hq; const float* mu; };
-
+}  // namespace
+namespace vch __attribute__((visibility("hidden"))) {
 // One pass of rs.n_rows rows through every layer, in the form `p` plans.
 int run_pass(vc_engine* e, const PassPlan& p, const RowSrc& rs, PassOut* out, hipStream_t s) {
   for (int l = 0; l < e->L; ++l) {
@@ -829,6 +529,8 @@ int run_pass(vc_engine* e, const PassPlan& p, const RowSrc& rs, PassOut* out, hi
   }
   return VC_OK;
 }
+}  // namespace vch
+namespace {
 
 // final LayerNorm + heads-1 for n rows; row r reads hidden row gather[r] (or in_row0 + r) and writes hh row (out_row0 + r).  wide: all
 // rows of a 17..64-row step at once on the weight-stationary kernel of those steps (LayerNorm launch + rows_gemm_wd_k / rows_gemm_mt_k)
@@ -876,6 +578,8 @@ int site_heads2(vc_engine* e, const PassPlan& p, bool wide, int n, int out_row0,
   else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_LOGITS, 1, e->K, s));
   return VC_OK;
 }
+}  // namespace
+namespace vch __attribute__((visibility("hidden"))) {
 // The prediction heads (voicecraft.py:181-185, :1084-1086) behind pass `p`: at 17..64 rows once over the step (option wide_heads: the
 // 16-row passes streamed the 33.6 MB of head weights four times at 64 rows), otherwise 16 rows at a time.
 int run_heads(vc_engine* e, const PassPlan& p, const PassOut& po, const int* gather, int n, int in_row0, int out_row0,
@@ -891,6 +595,8 @@ int run_heads(vc_engine* e, const PassPlan& p, const PassOut& po, const int* gat
   }
   return VC_OK;
 }
+}  // namespace vch
+namespace {
 
 // Prefill attention of a call whose longest prompt has `longest` rows: 2 = tile_attn64_k on 64-row blocks, 1 = tile_attn_k on 16-row tiles.
 // (tile_attn64_k's gain grows with the sequence - 800 rows -15 %, 2048 rows -39 % of the attention launch; 512 rows +8 % -, while the 64-row
@@ -904,6 +610,8 @@ int prefill_tiled(const vc_engine* e, long longest) {
   return attn64 ? 2 : 1;
 }
 
+}  // namespace
+namespace vch __attribute__((visibility("hidden"))) {
 // Prefill of one or several prompts as ONE row stream: the prompts' rows are laid back to back in `emb`
 // (each row carries its own (sequence, position)), pushed through the decoder in passes of up to
 // prefill_rows_per_pass rows - so the weights are streamed once per pass for all sequences together, not
@@ -911,7 +619,7 @@ int prefill_tiled(const vc_engine* e, long longest) {
 // pas[i] describes prompt i (x, y, segments); slots[i] is its sequence slot.
 // sess: a decode session's admission - the prompts' error bits go to prompt_err[slot] (attributable to a request) and the heads gather
 // through sess_gather, so that nothing the live rows of the running batch own is written.
-int prefill_batch(vc_engine* e, std::vector<PromptArgs>& pas, const std::vector<int>& slots, hipStream_t s, bool sess = false) {
+int prefill_batch(vc_engine* e, std::vector<PromptArgs>& pas, const std::vector<int>& slots, hipStream_t s, bool sess) {
   int* const gather = sess ? e->sess_gather : e->logit_row;
   const int chunk = e->prefill_rows_per_pass;
   size_t i0 = 0;
@@ -992,7 +700,7 @@ SampleArgs make_sample_args(vc_engine* e, int B, int rps) {
 }
 
 int push_sample_dyn(vc_engine* e, const vc_sample_cfg* sc, const int64_t* forced, int n_forced, float* logits_out,
-                    int logit_steps, int n_seq, hipStream_t s, int n_group = 1) {
+                    int logit_steps, int n_seq, hipStream_t s, int n_group) {
   SampleDyn& d = *e->h_dyn;
   memset(&d, 0, sizeof d);
   d.top_k = sc->top_k; d.top_p = sc->top_p; d.temperature = sc->temperature;
@@ -1013,6 +721,8 @@ int push_sample_dyn(vc_engine* e, const vc_sample_cfg* sc, const int64_t* forced
   HIPCHK(e, hipMemcpyAsync(e->d_dyn, e->h_dyn, sizeof(SampleDyn), hipMemcpyHostToDevice, s));
   return VC_OK;
 }
+}  // namespace vch
+namespace {
 
 int decode_step(vc_engine* e, const SampleArgs& sa, int B, int rps, bool grouped, hipStream_t s, bool sess = false) {
   RowSrc rs{};
@@ -1038,145 +748,130 @@ int decode_step(vc_engine* e, const SampleArgs& sa, int B, int rps, bool grouped
 // always waiting when the running one ends (measured before: ~8 us of idle GPU per graph launch and ~100 us
 // per blocking poll).  Steps replayed after the last sequence retired are no-ops (*n_active == 0).
 void drop_tts_stream(vc_engine* e);
-void drop_session(vc_engine* e);
 
-// The loop as a resumable object: begin / advance / finish.  The blocking calls drive it to its end in one go (decode_loop); the
-// streaming TTS call (vc_tts_stream_*) keeps it in the engine and advances it from vc_tts_stream_next, reading in between how many
-// steps the pacing has shown to be complete.  One copy of the pacing and of the graph cache.
-// groups: 0 = independent sequences, else the number of best-of-N groups the B0 sequences form (grouped sampler launches).
-struct DecodeLoop {
-  vc_engine* e = nullptr;
-  SampleArgs sa{};
-  vc_sample_cfg sc{};
-  int B0 = 0, B = 0, rps = 1, groups = 0, G = 1, max_steps = 0;
-  bool grouped = false, can_shrink = false;
-  bool sess = false;       // the steps of a decode session (sample_session_k): graphs of their own
-  hipStream_t s = nullptr;
-  int launched = 0, batch = 0;
-  int complete = 0;        // decode steps the host KNOWS to have ended (the pacing event behind them was waited for)
-  bool over = false;       // nothing more will be queued: the last sequence retired, or the step budget is used up
-  double t1 = 0;
-
-  // Rows per step.  A multi-utterance call starts with one row per sequence; when few enough sequences are left (option "shrink") the
-  // live ones are re-packed onto the rows of a narrower step - the next power of two >= the live count - and the loop goes on with
-  // that width's captured graph (graphs are keyed by width).  B / sa = the width in force.  Best-of-N calls of two or more groups shrink
-  // too (a decided group keeps one live row); a call of ONE group does not: its step stays N rows wide, as it always has.
-  void init(vc_engine* e_, const SampleArgs& sa0, int B0_, int rps_, int groups_, const vc_sample_cfg* sc_, int max_steps_, hipStream_t s_) {
-    e = e_; sa = sa0; sc = *sc_; B0 = B = B0_; rps = rps_; groups = groups_; max_steps = max_steps_; s = s_;
-    G = std::max(1, e->steps_per_graph);
-    grouped = groups > 0;
-    can_shrink = e->shrink && groups != 1 && rps == 1 && B0 > 1;
-    launched = batch = complete = 0; over = false;
-  }
-  static int width_for(int live) { int p = 1; while (p < live) p *= 2; return p; }
-  // One captured graph per (rows per step, option state), kept for the life of the engine.
-  int exec_for(hipGraphExec_t* out) {
-    const auto key = std::make_pair(std::make_tuple(B, rps, sess ? (grouped ? 3 : 2) : grouped ? 1 : 0), e->opt_state);
-    auto it = e->graphs.find(key);
-    int rc = VC_OK;
-    if (it != e->graphs.end()) {
-      *out = it->second;
-    } else {
-      const double tc = now_ms();
-      hipGraph_t graph = nullptr;
-      hipError_t be = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-      if (be != hipSuccess) rc = fail(e, VC_EHIP, "hipStreamBeginCapture failed: %s", hipGetErrorString(be));
-      for (int i = 0; i < G && rc == VC_OK; ++i) rc = decode_step(e, sa, B, rps, grouped, s, sess);
-      if (be == hipSuccess) {
-        hipError_t ce = hipStreamEndCapture(s, &graph);
-        if (rc == VC_OK && ce != hipSuccess) rc = fail(e, VC_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-      }
-      e->host_ms[HM_CAPTURE] += now_ms() - tc;
-      if (rc == VC_OK) {
-        const double ti = now_ms();
-        hipError_t ie = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
-        if (ie != hipSuccess) rc = fail(e, VC_EHIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie));
-        else e->graphs[key] = *out;
-        e->host_ms[HM_INSTANTIATE] += now_ms() - ti;
-      }
-      if (graph) (void)hipGraphDestroy(graph);
+}  // namespace
+namespace vch __attribute__((visibility("hidden"))) {
+// Rows per step.  A multi-utterance call starts with one row per sequence; when few enough sequences are left (option "shrink") the
+// live ones are re-packed onto the rows of a narrower step - the next power of two >= the live count - and the loop goes on with
+// that width's captured graph (graphs are keyed by width).  B / sa = the width in force.  Best-of-N calls of two or more groups shrink
+// too (a decided group keeps one live row); a call of ONE group does not: its step stays N rows wide, as it always has.
+void DecodeLoop::init(vc_engine* e_, const SampleArgs& sa0, int B0_, int rps_, int groups_, const vc_sample_cfg* sc_, int max_steps_, hipStream_t s_) {
+  e = e_; sa = sa0; sc = *sc_; B0 = B = B0_; rps = rps_; groups = groups_; max_steps = max_steps_; s = s_;
+  G = std::max(1, e->steps_per_graph);
+  grouped = groups > 0;
+  can_shrink = e->shrink && groups != 1 && rps == 1 && B0 > 1;
+  launched = batch = complete = 0; over = false;
+}
+int DecodeLoop::width_for(int live) { int p = 1; while (p < live) p *= 2; return p; }
+// One captured graph per (rows per step, option state), kept for the life of the engine.
+int DecodeLoop::exec_for(hipGraphExec_t* out) {
+  const auto key = std::make_pair(std::make_tuple(B, rps, sess ? (grouped ? 3 : 2) : grouped ? 1 : 0), e->opt_state);
+  auto it = e->graphs.find(key);
+  int rc = VC_OK;
+  if (it != e->graphs.end()) {
+    *out = it->second;
+  } else {
+    const double tc = now_ms();
+    hipGraph_t graph = nullptr;
+    hipError_t be = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
+    if (be != hipSuccess) rc = fail(e, VC_EHIP, "hipStreamBeginCapture failed: %s", hipGetErrorString(be));
+    for (int i = 0; i < G && rc == VC_OK; ++i) rc = decode_step(e, sa, B, rps, grouped, s, sess);
+    if (be == hipSuccess) {
+      hipError_t ce = hipStreamEndCapture(s, &graph);
+      if (rc == VC_OK && ce != hipSuccess) rc = fail(e, VC_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
     }
-    return rc;
+    e->host_ms[HM_CAPTURE] += now_ms() - tc;
+    if (rc == VC_OK) {
+      const double ti = now_ms();
+      hipError_t ie = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+      if (ie != hipSuccess) rc = fail(e, VC_EHIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie));
+      else e->graphs[key] = *out;
+      e->host_ms[HM_INSTANTIATE] += now_ms() - ti;
+    }
+    if (graph) (void)hipGraphDestroy(graph);
   }
-  // every graph this call can need, captured before the caller starts its decode timer
-  int precapture() {
-    e->host_ms[HM_CAPTURE] = e->host_ms[HM_INSTANTIATE] = 0;
-    if (!sc.use_graph) return VC_OK;
+  return rc;
+}
+// every graph this call can need, captured before the caller starts its decode timer
+int DecodeLoop::precapture() {
+  e->host_ms[HM_CAPTURE] = e->host_ms[HM_INSTANTIATE] = 0;
+  if (!sc.use_graph) return VC_OK;
+  hipGraphExec_t exec = nullptr;
+  int rc0 = exec_for(&exec);
+  if (can_shrink)            // ... and the narrower widths a shrinking batch passes through
+    for (int w = width_for(B0) / 2; w >= 1 && rc0 == VC_OK; w /= 2) {
+      if (w >= B0) continue;
+      B = w; sa = make_sample_args(e, w, rps);
+      rc0 = exec_for(&exec);
+    }
+  return rc0;
+}
+int DecodeLoop::begin() {
+  t1 = now_ms();
+  HIPCHK(e, hipMemsetAsync(e->step_ctr, 0, sizeof(int), s));      // the loop's first step is step 0 of batch 0 (SampleArgs.host_live slots)
+  e->repack_at.clear();
+  over = launched >= max_steps;
+  return VC_OK;
+}
+// One batch of G steps of the width in force - its captured graph, or G eager steps - and the pacing event `slot` behind it.  The only
+// place a batch is launched: advance() below and a decode session's turn (vc_session_advance), which keeps its own batch count.
+int DecodeLoop::queue_batch(int slot) {
+  int rc = VC_OK;
+  if (sc.use_graph) {
     hipGraphExec_t exec = nullptr;
-    int rc0 = exec_for(&exec);
-    if (can_shrink)            // ... and the narrower widths a shrinking batch passes through
-      for (int w = width_for(B0) / 2; w >= 1 && rc0 == VC_OK; w /= 2) {
-        if (w >= B0) continue;
+    if ((rc = exec_for(&exec))) return rc;
+    hipError_t le = hipGraphLaunch(exec, s);
+    if (le != hipSuccess) return fail(e, VC_EHIP, "hipGraphLaunch failed: %s", hipGetErrorString(le));
+  } else {
+    for (int i = 0; i < G && rc == VC_OK; ++i) rc = decode_step(e, sa, B, rps, grouped, s, sess);
+    if (rc) return rc;
+  }
+  hipError_t re = hipEventRecord(e->ev_pace[slot], s);
+  if (re != hipSuccess) return fail(e, VC_EHIP, "hipEventRecord: %s", hipGetErrorString(re));
+  return VC_OK;
+}
+// One turn: wait for the older of the two batches in flight, then queue the next one.  Sets `over` instead when the loop has ended.
+int DecodeLoop::advance() {
+  volatile int* live = e->h_flag + HF_ACTIVE;
+  volatile int* live_n = e->h_flag + HF_LIVE0;                   // two slots: sequences still live as the LAST step of a batch of G steps found them
+  if (over) return VC_OK;
+  if (batch >= 2) {   // pace: at most two batches in flight; the older one must have ended before a third is queued
+    hipError_t we = hipEventSynchronize(e->ev_pace[batch & 1]);
+    if (we != hipSuccess) { over = true; return fail(e, VC_EHIP, "pacing event: %s", hipGetErrorString(we)); }
+    complete = (batch - 1) * G;
+    if (*live <= 0) { over = true; return VC_OK; }
+    if (can_shrink) {
+      // the slot of the batch whose end has just been waited for (launched two iterations ago): the batch still in flight writes
+      // the other one, so the width schedule is the same in every run of the same call - and with it, in bf16, every sampled token
+      const int n_live = live_n[batch & 1];
+      const int w = n_live >= 1 ? width_for(n_live) : B;
+      if (w < B) {
+        RepackArgs ra;
+        memset(&ra, 0, sizeof ra);
+        ra.st = e->st; ra.st_fin = e->st_fin; ra.dec_h = e->dec_h; ra.row_seq = e->dec_row_seq; ra.row_pos = e->dec_row_pos;
+        ra.logit_row = e->logit_row; ra.err = e->err_flag; ra.B_old = B; ra.B_new = w; ra.d = e->d;
+        hipError_t re = vc_launch_repack(ra, s);
+        if (re != hipSuccess) { over = true; return fail(e, VC_EHIP, "re-pack launch: %s", hipGetErrorString(re)); }
         B = w; sa = make_sample_args(e, w, rps);
-        rc0 = exec_for(&exec);
-      }
-    return rc0;
-  }
-  int begin() {
-    t1 = now_ms();
-    HIPCHK(e, hipMemsetAsync(e->step_ctr, 0, sizeof(int), s));      // the loop's first step is step 0 of batch 0 (SampleArgs.host_live slots)
-    e->repack_at.clear();
-    over = launched >= max_steps;
-    return VC_OK;
-  }
-  // One batch of G steps of the width in force - its captured graph, or G eager steps - and the pacing event `slot` behind it.  The only
-  // place a batch is launched: advance() below and a decode session's turn (vc_session_advance), which keeps its own batch count.
-  int queue_batch(int slot) {
-    int rc = VC_OK;
-    if (sc.use_graph) {
-      hipGraphExec_t exec = nullptr;
-      if ((rc = exec_for(&exec))) return rc;
-      hipError_t le = hipGraphLaunch(exec, s);
-      if (le != hipSuccess) return fail(e, VC_EHIP, "hipGraphLaunch failed: %s", hipGetErrorString(le));
-    } else {
-      for (int i = 0; i < G && rc == VC_OK; ++i) rc = decode_step(e, sa, B, rps, grouped, s, sess);
-      if (rc) return rc;
-    }
-    hipError_t re = hipEventRecord(e->ev_pace[slot], s);
-    if (re != hipSuccess) return fail(e, VC_EHIP, "hipEventRecord: %s", hipGetErrorString(re));
-    return VC_OK;
-  }
-  // One turn: wait for the older of the two batches in flight, then queue the next one.  Sets `over` instead when the loop has ended.
-  int advance() {
-    volatile int* live = e->h_flag + HF_ACTIVE;
-    volatile int* live_n = e->h_flag + HF_LIVE0;                   // two slots: sequences still live as the LAST step of a batch of G steps found them
-    if (over) return VC_OK;
-    if (batch >= 2) {   // pace: at most two batches in flight; the older one must have ended before a third is queued
-      hipError_t we = hipEventSynchronize(e->ev_pace[batch & 1]);
-      if (we != hipSuccess) { over = true; return fail(e, VC_EHIP, "pacing event: %s", hipGetErrorString(we)); }
-      complete = (batch - 1) * G;
-      if (*live <= 0) { over = true; return VC_OK; }
-      if (can_shrink) {
-        // the slot of the batch whose end has just been waited for (launched two iterations ago): the batch still in flight writes
-        // the other one, so the width schedule is the same in every run of the same call - and with it, in bf16, every sampled token
-        const int n_live = live_n[batch & 1];
-        const int w = n_live >= 1 ? width_for(n_live) : B;
-        if (w < B) {
-          RepackArgs ra;
-          memset(&ra, 0, sizeof ra);
-          ra.st = e->st; ra.st_fin = e->st_fin; ra.dec_h = e->dec_h; ra.row_seq = e->dec_row_seq; ra.row_pos = e->dec_row_pos;
-          ra.logit_row = e->logit_row; ra.err = e->err_flag; ra.B_old = B; ra.B_new = w; ra.d = e->d;
-          hipError_t re = vc_launch_repack(ra, s);
-          if (re != hipSuccess) { over = true; return fail(e, VC_EHIP, "re-pack launch: %s", hipGetErrorString(re)); }
-          B = w; sa = make_sample_args(e, w, rps);
-          e->repack_at.push_back(batch);                  // counted in host_ms[HM_REPACKS] once the call knows its live steps (tts_run)
-        }
+        e->repack_at.push_back(batch);                  // counted in host_ms[HM_REPACKS] once the call knows its live steps (tts_run)
       }
     }
-    if (const int rc = queue_batch(batch & 1)) { over = true; return rc; }
-    launched += G;
-    ++batch;
-    if (launched >= max_steps) over = true;
-    return VC_OK;
   }
-  void finish(int* steps_run) {
-    e->host_ms[HM_LOOP] = now_ms() - t1;
-    e->host_ms[HM_SPARE] = 0;
-    e->host_ms[HM_LAUNCHED] = launched;                               // decode steps LAUNCHED (a multiple of steps_per_graph; the tail are no-ops)
-    e->cur_rows = B;
-    if (steps_run) *steps_run = launched;
-  }
-};
+  if (const int rc = queue_batch(batch & 1)) { over = true; return rc; }
+  launched += G;
+  ++batch;
+  if (launched >= max_steps) over = true;
+  return VC_OK;
+}
+void DecodeLoop::finish(int* steps_run) {
+  e->host_ms[HM_LOOP] = now_ms() - t1;
+  e->host_ms[HM_SPARE] = 0;
+  e->host_ms[HM_LAUNCHED] = launched;                               // decode steps LAUNCHED (a multiple of steps_per_graph; the tail are no-ops)
+  e->cur_rows = B;
+  if (steps_run) *steps_run = launched;
+}
+}  // namespace vch
+namespace {
 
 int decode_loop(vc_engine* e, const SampleArgs& sa0, int B0, int rps, int groups, const vc_sample_cfg* sc, int max_steps, hipStream_t s) {
   DecodeLoop L;
@@ -1215,6 +910,8 @@ int check_ready(vc_engine* e) {
   return VC_OK;
 }
 
+}  // namespace
+namespace vch __attribute__((visibility("hidden"))) {
 // entry points that decode (or change what a decode step is): not while a streaming TTS call is open
 int check_idle(vc_engine* e) {
   const int rc = check_ready(e);
@@ -1239,6 +936,8 @@ int check_err_flag(vc_engine* e, hipStream_t s) {
   }
   return VC_OK;
 }
+}  // namespace vch
+namespace {
 
 // ---- the checks of options that need a weight image or a request: they refuse before anything is set
 int need_fr8(vc_engine* e, const char* name, int v0) {
@@ -1893,8 +1592,6 @@ extern "C" int vc_finalize_weights(vc_engine* e, int compute_dtype) {
 // ------------------------------------------------------------------------------------- TTS
 namespace {
 
-struct TtsJob { const int64_t* x; int Lx; const int64_t* y; int T; };
-
 // After a one-row-per-sequence decode loop: the final states by slot into h_st[0, B) and the call's re-pack count (host_ms[HM_REPACKS]).
 // For one sequence that is the copy of its state.
 int collect_states(vc_engine* e, int B, hipStream_t s) {
@@ -1922,6 +1619,8 @@ int collect_states(vc_engine* e, int B, hipStream_t s) {
   return VC_OK;
 }
 
+}  // namespace
+namespace vch __attribute__((visibility("hidden"))) {
 // A TTS request's prompt - one segment: the T prompt frames and the first generated column; `skip` text positions are read from
 // sequence 0's cache, whose text x_shared is - and its first state.  (The blocking calls and a session's admission.)
 SeqState tts_request(vc_engine* e, const TtsJob& j, int skip, const int64_t* x_shared, PromptArgs* pa) {
@@ -1971,6 +1670,8 @@ int replicate_kv(vc_engine* e, CopyKvArgs kv, hipStream_t s) {
   }
   return VC_OK;
 }
+}  // namespace vch
+namespace {
 
 // The blocking call's skeleton, shared by the TTS calls (tts_prepare / call_end; the streaming call too), vc_edit and vc_edit_multi:
 //   call_begin - the caller's prompts and prefill, its first states into h_st[0, B) - call_arm - the decode loop - call_end.
@@ -2139,6 +1840,8 @@ int kept_sample(const vc_engine* e, int u, int N) {
   return keep;
 }
 
+}  // namespace
+namespace vch __attribute__((visibility("hidden"))) {
 // (st: the sequence's final state - the blocking calls read it back into h_st, a session rebuilds what is needed from the slot's record)
 int assemble_tts(vc_engine* e, const TtsJob& j, int slot, const SeqState& st, int64_t* res, int res_cap, int* gen_len, hipStream_t s) {
   if (!st.done || st.span < 1)
@@ -2157,9 +1860,9 @@ int assemble_tts(vc_engine* e, const TtsJob& j, int slot, const SeqState& st, in
   *gen_len = Tg;
   return VC_OK;
 }
+}  // namespace vch
 
 // ---- the streaming TTS call: tts_prepare at begin, the DecodeLoop advanced from next, call_end + assemble_tts at end
-}  // namespace
 struct TtsStream {
   TtsJob job{};
   TtsPrep prep{};
@@ -2288,16 +1991,7 @@ extern "C" int vc_tts_stream_end(vc_engine* e, int64_t* res_dev, int res_cap, in
 }
 
 // ------------------------------------------------------------------------------------- editing: the parts shared by vc_edit, vc_edit_multi and the decode sessions
-namespace {
-
-// One editing request: its inputs, the prefill's segment table (PromptArgs) and its budget of sampled steps.
-struct EditJob {
-  const int64_t* x; int Lx; const int64_t* y; int T;
-  const int32_t* iv; int M; const int32_t* mv;     // mask intervals [M][2], mask values [2M]
-  std::vector<int> ns, ne;                          // the M + 1 non-masked pieces
-  PromptArgs pa;
-  int max_steps;
-};
+namespace vch __attribute__((visibility("hidden"))) {
 
 // Validation, segment table and step budget of one request (vc_edit, vc_edit_multi; `who` prefixes every message).
 int edit_prepare(vc_engine* e, EditJob& j, const char* who) {
@@ -2387,727 +2081,7 @@ int edit_assemble(vc_engine* e, const EditJob& j, const SeqState& fs, const int*
   return VC_OK;
 }
 
-}  // namespace
-
-// ------------------------------------------------------------------------------------- decode sessions (continuous batching)
-// A session keeps the decode loop open and takes TTS and editing requests at any time (vc_session_submit / _submit_ctl / _submit_edit).
-// One TURN (vc_session_advance) is one iteration of DecodeLoop::advance with the way in added:
-//   1. wait for the older of the two graph batches in flight;
-//   2. count the retirements stamped with a batch the host has now seen END (the sampler writes one pinned record per slot, stamped
-//      with the batch index session_turn_k laid down in front of that batch);
-//   3. admit from the FIFO into the free slots, in order, as many as fit;
-//   4. queue, on the decode stream: the prompts and ONE prefill of the admitted requests into their K/V slots, session_turn_k (stamp of the
-//      next batch; re-pack of the live rows onto the width now needed, narrower or wider; the admitted requests' initial states behind
-//      them; fillers; n_active raised), the first sample of the admitted rows alone, and the next batch of graph_steps steps.
-//      The admitted requests' first states (tts_request for a TTS request; edit_state with feed_switch of an editing request - one row
-//      per request, its span switches fed over three steps as in vc_edit_multi) and their sampling controls are written into pinned
-//      staging buffer (batch % VC_ADM_STAGES) and uploaded on the decode stream in front of session_turn_k.  That buffer is written again
-//      VC_ADM_STAGES turns later at the earliest; a turn queues only after the batch two turns back has ENDED (step 1), and a batch ends
-//      behind its turn's upload on the same stream, so no queued upload can still have to read a buffer the host is writing.
-// A session opened for best-of-N requests (vc_session_open_best_of, max_samples > 1) takes TTS requests of N samples too
-// (vc_session_submit_best_of): one ticket, N rows and N slots.  The prompt is prefilled once, into the first slot, and its K/V copied
-// to the siblings' slots (copy_kv_k); the rows are laid next to each other in sample order, with SeqState.group = the ticket and
-// their sample index in samp_tab (session_groups_k, behind session_turn_k); the steps of such a session end in the sample / advance
-// PAIR (vc_launch_sample_session grouped), whose second launch holds the keep decision.  Every row writes its slot's record, word 6
-// = kept: a dropped sample's slot is free once the host has seen its batch end, the request is finished when all N records are in,
-// and only the kept sample's slot waits for the fetch.
-// What the host decides - who is admitted when, every width - depends only on the submissions, the turn each was made at and records
-// of batches that have ended: never on how far the device runs ahead.  The same schedule therefore gives the same tokens in bf16 too.
-// Width in force: the next power of two >= live sequences, capped by `top` (that power for max_live where the per-row buffers hold it,
-// else max_live itself, as a blocking call of max_live sequences starts at its own count).
-struct SessReq {
-  int kind = 0;             // 0 TTS (job), 1 editing (edit)
-  TtsJob job{};
-  EditJob edit{};           // its iv / mv point into iv_own / mv_own (re-pointed wherever a SessReq is copied)
-  std::vector<int32_t> iv_own, mv_own;
-  vc_request_ctl ctl{};     // the request's sampling controls (the session's when it gave none)
-  uint64_t seed = 0;
-  int slot = -1;
-  int state = 0;            // 0 pending, 1 live, 2 finished
-  int total_steps = 0, span = 0, prompt_err = 0, fed = 0;
-  int span_steps[VC_MAX_SPANS]{};
-  int adm_batch = -1;       // the graph batch queued by the turn that admitted it (vc_session_frames counts its final rows from there)
-  int emitted = 0;          // frames vc_session_frames has handed out
-  // a best-of-N request (n_samples > 1): one row and one K/V slot per sample.  `slot` is slots[0] while it decodes and the KEPT sample's
-  // slot once it has finished (-1 when no sample terminated); total_steps / span / span_steps are then the kept sample's
-  int n_samples = 1;
-  std::vector<int> slots;   // [n_samples], increasing
-  std::vector<char> mdone;  // [n_samples] the member's retirement record has been read
-  int members_left = 0;
-  int kept = -1;            // sample index of the member that retired kept with its span finished
-  // a live request that was cancelled (vc_session_cancel): gone for every entry point, it stays in the table until the records of
-  // its rows have been read (session_note_retired), which is what frees its slots
-  bool cancelled = false;
-  bool cancel_queued = false;   // its rows are in the table of a session_cancel_k launch already queued
-};
-struct Session {
-  DecodeLoop L{};
-  hipStream_t s = nullptr;
-  vc_sample_cfg sc{};
-  int max_live = 0, top = 0;
-  int max_samples = 1;      // > 1: opened for best-of-N requests (vc_session_open_best_of) - the steps' sampler is the sample / advance pair
-  bool grouped = false;     // max_samples > 1
-  int B = 0;                // rows of the step in force (0: nothing laid out yet)
-  int live = 0;             // rows (one per sample of a request) admitted and not yet KNOWN to have retired
-  int batch = 0;            // index of the next graph batch (never reset: the retirement stamps are unique for the session's life)
-  int run_start = 0;        // first batch queued since the session was last idle: only batches from there on can be in flight
-  int known = -1;           // the newest batch vc_session_advance has seen END (what vc_session_frames may hand out hangs on this alone)
-  int next_ticket = 1;
-  std::deque<int> fifo;
-  std::map<int, SessReq> reqs;
-  std::vector<int> slot_ticket;      // [max_live] ticket holding the slot (live, or finished and not yet fetched), -1 = free
-  long long stats[8]{};     // indexed by SS_*
-  // decode-stream time of each admission (prefill + session_turn_k + first sample): event pairs, read once their batch has ended
-  hipEvent_t ev_adm[4][2]{};
-  int ev_turn[4]{-1, -1, -1, -1};
-  double adm_ms = 0;
-  // a turn whose queued work failed after requests had been admitted on the host: the device and the tables no longer agree, so every
-  // later submit / advance / fetch returns this error and the caller closes the session
-  bool broken = false;
-  std::string broken_msg;
-};
-namespace {
-int session_broken(vc_engine* e, const Session& t) {
-  return fail(e, VC_ESTATE, "the decode session failed in an earlier turn (%s): close it (vc_session_close)", t.broken_msg.c_str());
-}
-void drop_session(vc_engine* e) {
-  if (!e->sess) return;
-  for (auto& pr : e->sess->ev_adm)
-    for (auto& ev : pr) if (ev) (void)hipEventDestroy(ev);
-  delete e->sess;
-  e->sess = nullptr;
-}
-
-int session_width(const Session& t, int live) { return std::min(DecodeLoop::width_for(std::max(1, live)), t.top); }
-
-// the admission timings whose batch the host has seen end (all of them when `all`: the stream was synchronised)
-void session_read_timers(Session& t, int known, bool all) {
-  for (int i = 0; i < 4; ++i) {
-    if (t.ev_turn[i] < 0 || (!all && t.ev_turn[i] > known)) continue;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, t.ev_adm[i][0], t.ev_adm[i][1]) == hipSuccess) t.adm_ms += ms;
-    t.ev_turn[i] = -1;
-  }
-}
-
-// retirements stamped with a batch <= known (stamps are batch + 1 in the record)
-void session_note_retired(vc_engine* e, Session& t, int known, int* tickets_out, int cap, int* n_fin) {
-  for (int slot = 0; slot < t.max_live; ++slot) {
-    const int ticket = t.slot_ticket[slot];
-    if (ticket < 0) continue;
-    SessReq& r = t.reqs[ticket];
-    if (r.state != 1) continue;
-    volatile int* rec = e->h_rec + slot * VC_SESS_REC;
-    const int stamp = rec[0];
-    if (stamp == 0 || stamp - 1 > known) continue;
-    if (r.cancelled) {
-      // a row of a cancelled request, retired by session_cancel_k or - in a batch that was still in flight when the cancel was made - by
-      // itself: the slot is free from here on, whatever the record says of `kept`, and nothing is reported (the cancel wins)
-      int m = -1;                                       // (a request of one sample has slots = {slot}, as admission laid them)
-      for (int i = 0; i < r.n_samples; ++i) if (r.slots[i] == slot) m = i;
-      if (m < 0 || r.mdone[m]) continue;
-      r.mdone[m] = 1;
-      r.members_left -= 1;
-      t.live -= 1;
-      t.stats[SS_LIVE_ROWS] += std::max(0, (int)rec[1] - 1) + std::max(0, (int)rec[5]);
-      t.slot_ticket[slot] = -1;
-      if (r.members_left == 0) {
-        // (a kept member whose record had been read before the cancel was still holding its slot for the fetch)
-        for (int& held : t.slot_ticket) if (held == ticket) held = -1;
-        t.reqs.erase(ticket);
-      }
-      continue;
-    }
-    if (r.n_samples > 1) {
-      // one member of a best-of-N request.  A dropped sample's slot is free from here on; the request is finished - and reported - by
-      // the turn that has read all its members' records, and only the kept sample's slot is held for the fetch
-      int m = -1;
-      for (int i = 0; i < r.n_samples; ++i) if (r.slots[i] == slot) m = i;
-      if (m < 0 || r.mdone[m]) continue;
-      const bool last = r.members_left == 1;
-      if (last && *n_fin >= cap) continue;              // no room to report the request: this member is read again by a later turn
-      r.mdone[m] = 1;
-      r.members_left -= 1;
-      t.live -= 1;
-      t.stats[SS_LIVE_ROWS] += std::max(0, (int)rec[1] - 1);
-      r.prompt_err |= rec[4];
-      if (rec[6] && rec[2] >= 1 && m >= r.kept) {       // (at most one member ends kept with its span finished: advance_phase)
-        r.kept = m;
-        r.total_steps = rec[1]; r.span = rec[2]; r.fed = rec[5];
-        for (int i = 0; i < VC_MAX_SPANS; ++i) r.span_steps[i] = rec[VC_SESS_REC_SPANS + i];
-      }
-      if (!rec[6]) t.slot_ticket[slot] = -1;
-      if (last) {
-        r.state = 2;
-        for (int i = 0; i < r.n_samples; ++i)
-          if (i != r.kept && t.slot_ticket[r.slots[i]] == ticket) t.slot_ticket[r.slots[i]] = -1;
-        r.slot = r.kept >= 0 ? r.slots[r.kept] : -1;
-        tickets_out[*n_fin] = ticket;
-        *n_fin += 1;
-      }
-      continue;
-    }
-    if (*n_fin >= cap) continue;                        // no room to report it: it stays live on the host and is reported by a later turn
-    r.state = 2;
-    r.total_steps = rec[1]; r.span = rec[2]; r.prompt_err = rec[4]; r.fed = rec[5];
-    for (int i = 0; i < VC_MAX_SPANS; ++i) r.span_steps[i] = rec[VC_SESS_REC_SPANS + i];
-    t.live -= 1;
-    // rows of launched steps that were live: every step of the request but its first sample, and the rows an edit fed at its span switches
-    t.stats[SS_LIVE_ROWS] += std::max(0, r.total_steps - 1) + std::max(0, r.fed);
-    tickets_out[*n_fin] = ticket;
-    *n_fin += 1;
-  }
-}
-}  // namespace
-
-extern "C" int vc_session_open_best_of(vc_engine* e, int max_live, int max_samples, const vc_sample_cfg* sc, void* stream) {
-  int rc = check_idle(e);
-  if (rc) return rc;
-  if (!sc) return fail(e, VC_EINVAL, "null argument to vc_session_open");
-  if (max_live < 1 || max_live > e->B_max) return fail(e, VC_EINVAL, "vc_session_open: max_live %d outside [1, max_seqs = %d]", max_live, e->B_max);
-  if (max_samples < 1 || max_samples > max_live)
-    return fail(e, VC_EINVAL, "vc_session_open_best_of: max_samples %d outside [1, max_live = %d]", max_samples, max_live);
-  hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
-  Session* t = new Session();
-  t->s = s; t->sc = *sc; t->max_live = max_live;
-  t->max_samples = max_samples; t->grouped = max_samples > 1;
-  t->top = DecodeLoop::width_for(max_live) <= e->NS ? DecodeLoop::width_for(max_live) : max_live;
-  t->slot_ticket.assign(max_live, -1);
-  auto bail = [&](int code) { e->sess = t; drop_session(e); return code; };
-  for (auto& pr : t->ev_adm)
-    for (auto& ev : pr)
-      if (hipEventCreate(&ev) != hipSuccess) return bail(fail(e, VC_EHIP, "hipEventCreate failed"));
-  // silence tokens and the graph switch are the session's (one SampleDyn); the seed and the sampling controls are per request
-  // (SampleDyn.seed_tab / ctl_tab by slot), the controls given here being the default of a request that brings none
-  if ((rc = push_sample_dyn(e, sc, nullptr, 0, nullptr, 0, max_live, s))) return bail(rc);
-  memset(e->h_rec, 0, sizeof(int) * VC_SESS_REC * e->NS);
-  e->h_flag[HF_STAGE] = 0; e->h_flag[HF_ACTIVE] = 0; e->h_flag[HF_LIVE0] = 0; e->h_flag[HF_LIVE1] = 0;
-  hipError_t he = hipMemsetAsync(e->n_active, 0, sizeof(int), s);
-  if (he == hipSuccess) he = hipMemsetAsync(e->step_ctr, 0, sizeof(int), s);
-  if (he == hipSuccess) he = hipMemsetAsync(e->batch_id, 0, sizeof(int), s);
-  if (he == hipSuccess) he = hipMemsetAsync(e->prompt_err, 0, sizeof(int) * e->NS, s);
-  if (he == hipSuccess) he = hipStreamSynchronize(s);       // (orders the reuse of the pinned sampler block, as check_err_flag does in a call)
-  if (he != hipSuccess) return bail(fail(e, VC_EHIP, "vc_session_open: %s", hipGetErrorString(he)));
-  e->repack_at.clear();
-  // every graph the session can pass through, ahead of any timer: the powers of two below `top`, and `top`
-  t->L.init(e, make_sample_args(e, t->top, 1), t->top, 1, 0, sc, 0, s);
-  t->L.sess = true;
-  t->L.grouped = t->grouped;      // graphs of their own: the steps of such a session end in the sample / advance pair
-  e->host_ms[HM_CAPTURE] = e->host_ms[HM_INSTANTIATE] = 0;
-  if (sc->use_graph) {
-    hipGraphExec_t exec = nullptr;
-    for (int w = t->top; w >= 1 && rc == VC_OK; w = (w == t->top) ? DecodeLoop::width_for(w) / 2 : w / 2) {
-      t->L.B = w; t->L.sa = make_sample_args(e, w, 1);
-      rc = t->L.exec_for(&exec);
-    }
-    if (rc) return bail(rc);
-  }
-  e->sess = t;
-  return VC_OK;
-}
-extern "C" int vc_session_open(vc_engine* e, int max_live, const vc_sample_cfg* sc, void* stream) {
-  return vc_session_open_best_of(e, max_live, 1, sc, stream);
-}
-
-namespace {
-// the checks every submit starts with; *t_out = the open, unbroken session
-int session_for_submit(vc_engine* e, Session** t_out) {
-  if (!e) return VC_EINVAL;
-  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
-  if (e->sess->broken) return session_broken(e, *e->sess);
-  *t_out = e->sess;
-  return VC_OK;
-}
-// a request's sampling controls: its own, checked, or the session's
-int session_ctl(vc_engine* e, const Session& t, const vc_request_ctl* ctl, vc_request_ctl* out) {
-  if (!ctl) {
-    *out = vc_request_ctl{t.sc.top_k, t.sc.top_p, t.sc.temperature, t.sc.stop_repetition};
-    return VC_OK;
-  }
-  if (!(ctl->temperature > 0.f && ctl->temperature <= 3.0e38f))
-    return fail(e, VC_EINVAL, "request controls: temperature %g must be a finite positive number", (double)ctl->temperature);
-  if (ctl->top_p != ctl->top_p) return fail(e, VC_EINVAL, "request controls: top_p is not a number");
-  *out = *ctl;
-  return VC_OK;
-}
-int session_enqueue(Session& t, SessReq&& r, int* ticket) {
-  const int id = t.next_ticket++;
-  SessReq& q = t.reqs[id];
-  q = std::move(r);
-  q.edit.iv = q.iv_own.data(); q.edit.mv = q.mv_own.data();
-  t.fifo.push_back(id);
-  *ticket = id;
-  return VC_OK;
-}
-}  // namespace
-
-extern "C" int vc_session_submit_ctl(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
-                                     const vc_request_ctl* ctl, uint64_t seed, int* ticket) {
-  Session* tp = nullptr;
-  if (int rc = session_for_submit(e, &tp)) return rc;
-  if (!x_dev || (!y_dev && T > 0) || !ticket) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_submit");
-  if (Lx < 1 || T < 0) return fail(e, VC_EINVAL, "empty text or negative prompt length");
-  const int n_cols = T + 1;
-  if (e->S_max - (Lx + n_cols) - 1 < e->K + 1)
-    return fail(e, VC_ECAP, "the prompt alone takes %d of max_positions %d", Lx + n_cols, e->S_max);
-  if (((Lx + n_cols + 63) & ~63) > e->emb_cap)
-    return fail(e, VC_ECAP, "a prompt of %d rows does not fit the prefill arena of %d rows", Lx + n_cols, e->emb_cap);
-  SessReq r;
-  if (int rc = session_ctl(e, *tp, ctl, &r.ctl)) return rc;
-  r.kind = 0;
-  r.job = TtsJob{x_dev, Lx, y_dev, T};
-  r.seed = seed;
-  return session_enqueue(*tp, std::move(r), ticket);
-}
-
-extern "C" int vc_session_submit_best_of(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T, int n_samples,
-                                         const vc_request_ctl* ctl, uint64_t seed, int* ticket) {
-  Session* tp = nullptr;
-  if (int rc = session_for_submit(e, &tp)) return rc;
-  if (!ticket) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_submit");
-  if (n_samples < 1 || n_samples > tp->max_samples)
-    return fail(e, VC_EINVAL, "vc_session_submit_best_of: n_samples %d outside [1, max_samples = %d] of this session%s", n_samples,
-                tp->max_samples, tp->max_samples == 1 ? " (vc_session_open_best_of opens one for best-of-N requests)" : "");
-  int id = 0;
-  if (int rc = vc_session_submit_ctl(e, x_dev, Lx, y_dev, T, ctl, seed, &id)) return rc;
-  tp->reqs[id].n_samples = n_samples;
-  *ticket = id;
-  return VC_OK;
-}
-
-extern "C" int vc_session_submit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T, uint64_t seed, int* ticket) {
-  return vc_session_submit_ctl(e, x_dev, Lx, y_dev, T, nullptr, seed, ticket);
-}
-
-extern "C" int vc_session_submit_edit(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
-                                      const int32_t* mask_intervals, int M, const int32_t* mask_values,
-                                      const vc_request_ctl* ctl, uint64_t seed, int* ticket) {
-  Session* tp = nullptr;
-  if (int rc = session_for_submit(e, &tp)) return rc;
-  if (!x_dev || !y_dev || !mask_intervals || !mask_values || !ticket) return fail(e, VC_EINVAL, "null argument to vc_session_submit_edit");
-  SessReq r;
-  if (int rc = session_ctl(e, *tp, ctl, &r.ctl)) return rc;
-  r.kind = 1;
-  // (edit_prepare refuses a span count outside [1, max_n_spans] before it reads either array: the copies only have to stay inside them)
-  const int Mc = std::max(0, std::min(M, VC_MAX_SPANS));
-  r.iv_own.assign(mask_intervals, mask_intervals + 2 * (size_t)Mc);
-  r.mv_own.assign(mask_values, mask_values + 2 * (size_t)Mc);
-  r.edit = EditJob{x_dev, Lx, y_dev, T, r.iv_own.data(), M, r.mv_own.data()};
-  if (int rc = edit_prepare(e, r.edit, "")) return rc;
-  const int rows = Lx + r.edit.pa.n_cols;
-  if (((rows + 63) & ~63) > e->emb_cap)
-    return fail(e, VC_ECAP, "a prompt of %d rows does not fit the prefill arena of %d rows", rows, e->emb_cap);
-  r.seed = seed;
-  return session_enqueue(*tp, std::move(r), ticket);
-}
-
-namespace {
-
-// The steps of a turn, in the order vc_session_advance takes them (numbered as in the comment above Session).
-// ---- 1, 2: the older batch in flight, and what it (or an earlier one) retired
-int turn_retire(vc_engine* e, Session& t, int* tickets_out, int cap, int* n_finished) {
-  int known = t.run_start - 1;
-  if (t.batch - t.run_start >= 2) {
-    HIPCHK(e, hipEventSynchronize(e->ev_pace[t.batch & 1]));
-    known = t.batch - 2;
-  }
-  t.known = std::max(t.known, known);
-  session_note_retired(e, t, known, tickets_out, cap, n_finished);
-  session_read_timers(t, known, false);
-  return VC_OK;
-}
-
-// ---- the cancels made since the last turn: the slots of the cancelled tickets' rows whose records are still out, one table for
-// session_cancel_k (queued in step 4, in front of session_turn_k).  Their slots stay taken until those records have been read
-void turn_cancels(Session& t, SessCancelArgs& ca) {
-  memset(&ca, 0, sizeof ca);
-  for (int slot = 0; slot < t.max_live; ++slot) {
-    const int ticket = t.slot_ticket[slot];
-    if (ticket < 0) continue;
-    const SessReq& r = t.reqs[ticket];
-    if (!r.cancelled || r.cancel_queued) continue;
-    int m = -1;
-    for (int i = 0; i < r.n_samples; ++i) if (r.slots[i] == slot) m = i;
-    if (m >= 0 && !r.mdone[m]) ca.slot[ca.n++] = slot;
-  }
-  for (auto& kv_req : t.reqs) if (kv_req.second.cancelled) kv_req.second.cancel_queued = true;
-}
-
-// What step 3 admits on the host and step 4 queues on the decode stream.
-struct Admission {
-  SessTurnArgs ta;
-  SessGroupArgs ga;
-  CopyKvArgs kv;            // the siblings' prompt K/V: one (source, destination) entry per sibling, every group of the turn in one table
-  std::vector<PromptArgs> pas;
-  std::vector<int> slots;
-  int n_req = 0;
-  SeqState* h_adm_st = nullptr;           // this turn's staging buffers (set by turn_admit)
-  vc_request_ctl* h_adm_ctl = nullptr;
-};
-
-// ---- 3: admission, FIFO, as many as have a free slot
-void turn_admit(vc_engine* e, Session& t, Admission& a) {
-  SessTurnArgs& ta = a.ta;
-  SessGroupArgs& ga = a.ga;
-  CopyKvArgs& kv = a.kv;
-  memset(&ta, 0, sizeof ta);
-  // this turn's staging buffers (see the comment above Session: the host last wrote them VC_ADM_STAGES turns ago)
-  SeqState* const h_adm_st = a.h_adm_st = e->h_adm_st + (size_t)(t.batch % VC_ADM_STAGES) * e->NS;
-  vc_request_ctl* const h_adm_ctl = a.h_adm_ctl = e->h_adm_ctl + (size_t)(t.batch % VC_ADM_STAGES) * e->NS;
-  // strictly FIFO: the head of the queue is admitted by the first turn that has a free slot for EACH of its samples - the lowest free
-  // slots, which need not be consecutive -, and nothing behind it overtakes it (a best-of-N request waiting for slots blocks the line).
-  // A request of one sample takes the lowest free slot, as ever.
-  memset(&ga, 0, sizeof ga);
-  memset(&kv, 0, sizeof kv);
-  while (!t.fifo.empty()) {
-    const int id = t.fifo.front();
-    SessReq& r = t.reqs[id];
-    const int N = r.n_samples;
-    std::vector<int> mine;
-    for (int slot = 0; slot < t.max_live && (int)mine.size() < N; ++slot)
-      if (t.slot_ticket[slot] < 0) mine.push_back(slot);
-    if ((int)mine.size() < N) break;
-    t.fifo.pop_front();
-    a.n_req += 1;
-    r.slot = mine[0]; r.state = 1; r.adm_batch = t.batch;
-    r.slots = mine; r.mdone.assign(N, 0); r.members_left = N; r.kept = -1;
-    // the request's first state and its prompt, by kind: what tts_prepare / vc_edit_multi lay down for a sequence of a blocking call
-    SeqState st0;
-    PromptArgs pa;
-    if (r.kind == 1) {
-      st0 = edit_state(e, r.edit);
-      st0.feed_switch = 1;
-      pa = r.edit.pa;
-    } else {
-      st0 = tts_request(e, r.job, 0, nullptr, &pa);
-    }
-    if (N > 1) st0.group = id;                              // the group of the keep decision is the request (advance_phase)
-    a.pas.push_back(pa);                                    // ONE prefill per request, into its first slot
-    a.slots.push_back(mine[0]);
-    for (int m = 0; m < N; ++m) {                           // one row per sample, consecutive and in sample order
-      const int slot = mine[m];
-      t.slot_ticket[slot] = id;
-      const int j = ta.n_new++;
-      ta.seed[j] = r.seed;
-      h_adm_st[j] = st0;
-      h_adm_st[j].slot = slot;
-      h_adm_ctl[j] = r.ctl;
-      ga.slot[j] = slot; ga.lrow[j] = mine[0]; ga.samp[j] = m | (N << 16);
-      if (m > 0) {
-        const int k = kv.n_ent++;
-        kv.src[k] = mine[0]; kv.dst0[k] = slot; kv.cnt[k] = 1; kv.p0[k] = 0; kv.p1[k] = r.job.Lx + r.job.T + 1;
-      }
-      volatile int* rec = e->h_rec + slot * VC_SESS_REC;    // the slot's record: empty until its row retires
-      for (int i = 0; i < VC_SESS_REC; ++i) rec[i] = 0;
-    }
-  }
-}
-
-// nothing to decode: what is still queued is steps without a live sequence.  Wait for them and queue nothing more; a later
-// submit (or the fetch that frees a slot for a pending request) restarts the loop.
-int turn_idle(vc_engine* e, Session& t, int* tickets_out, int cap, int* n_finished, int* idle) {
-  hipStream_t s = t.s;
-  if (t.batch > t.run_start) {
-    HIPCHK(e, hipStreamSynchronize(s));
-    t.known = t.batch - 1;
-    session_note_retired(e, t, t.batch - 1, tickets_out, cap, n_finished);
-    session_read_timers(t, t.batch - 1, true);
-    t.run_start = t.batch;
-    if (int rc = check_err_flag(e, s)) return rc;        // (session_turn_k's row check; the stream is idle, so this costs nothing)
-  }
-  *idle = t.fifo.empty() ? 1 : 0;
-  return VC_OK;
-}
-
-// ---- 4: prefill of the admitted requests, the turn kernel, their first sample, the next batch
-int turn_queue(vc_engine* e, Session& t, Admission& a, SessCancelArgs& ca) {
-  SessTurnArgs& ta = a.ta;
-  SessGroupArgs& ga = a.ga;
-  CopyKvArgs& kv = a.kv;
-  hipStream_t s = t.s;
-  const int G = t.L.G;
-  const int n_new = ta.n_new;                               // ROWS admitted this turn
-  const int live_before = t.live;
-  const int w = session_width(t, t.live + n_new);
-  const int ei = t.batch & 3;
-  if (n_new > 0) {
-    HIPCHK(e, hipEventRecord(t.ev_adm[ei][0], s));
-    int rc = prefill_batch(e, a.pas, a.slots, s, true);
-    if (rc) return rc;
-    if (kv.n_ent > 0) {
-      // prefill once, replicate: prompt positions [0, Lx + T + 1) of each group's first slot to its siblings' slots, one launch per
-      // cache tensor for every group of the turn.  The first-step logits are not copied: every member's first sample reads the row
-      // of the group's first slot (session_groups_k)
-      kv.n_dst = kv.n_ent;
-      if ((rc = replicate_kv(e, kv, s))) return rc;
-    }
-    HIPCHK(e, hipMemcpyAsync(e->adm_st, a.h_adm_st, sizeof(SeqState) * n_new, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(e->adm_ctl, a.h_adm_ctl, sizeof(vc_request_ctl) * n_new, hipMemcpyHostToDevice, s));
-  }
-  ta.st = e->st; ta.dec_h = e->dec_h; ta.row_seq = e->dec_row_seq; ta.row_pos = e->dec_row_pos; ta.logit_row = e->logit_row;
-  ta.err = e->err_flag; ta.n_active = e->n_active; ta.batch_id = e->batch_id; ta.row_base = e->row_base; ta.adm_slot = e->adm_slot;
-  ta.seed_tab = e->seed_tab; ta.prompt_err = e->prompt_err; ta.retire_rec = e->h_rec;
-  ta.ctl_tab = e->ctl_tab; ta.adm_st = e->adm_st; ta.adm_ctl = e->adm_ctl;
-  ta.B_old = t.B; ta.B_new = w; ta.d = e->d; ta.batch = t.batch; ta.repack = (n_new > 0 || w != t.B) ? 1 : 0;
-  if (ca.n > 0 && t.B > 0) {
-    // (stamped with the batch queued below, not the one in flight: that batch's pacing event was recorded before this launch)
-    ca.st = e->st; ca.row_pos = e->dec_row_pos; ca.n_active = e->n_active; ca.retire_rec = e->h_rec; ca.B = t.B; ca.batch = t.batch;
-    HIPCHK(e, vc_launch_session_cancel(ca, e->NS, s));
-  }
-  HIPCHK(e, vc_launch_session_turn(ta, s));
-  if (t.grouped && n_new > 0) {
-    ga.adm_slot = e->adm_slot; ga.samp_tab = e->samp_tab; ga.n_new = n_new;
-    HIPCHK(e, vc_launch_session_groups(ga, e->NS, s));
-  }
-  if (t.B > 0 && w > t.B) t.stats[SS_WIDENINGS] += 1;
-  if (w < t.B) t.stats[SS_NARROWINGS] += 1;
-  t.B = w;
-  t.L.B = w; t.L.sa = make_sample_args(e, w, 1);
-  if (n_new > 0) {
-    HIPCHK(e, vc_launch_sample_session(t.L.sa, true, n_new, t.grouped, s));
-    HIPCHK(e, hipEventRecord(t.ev_adm[ei][1], s));
-    t.ev_turn[ei] = t.batch;
-    t.stats[SS_ADMITTED] += a.n_req;                                   // requests; the row sums SS_LIVE_ROWS, SS_LAUNCHED_ROWS count every sample's rows
-    if (live_before > 0) t.stats[SS_ADMITTED_LIVE] += a.n_req;
-    t.live += n_new;
-  }
-  if (const int rc = t.L.queue_batch(t.batch & 1)) return rc;
-  t.batch += 1;
-  t.stats[SS_LAUNCHED_ROWS] += (long long)w * G;
-  return VC_OK;
-}
-
-}  // namespace
-
-extern "C" int vc_session_advance(vc_engine* e, int* tickets_out, int cap, int* n_finished, int* idle) {
-  if (!e) return VC_EINVAL;
-  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
-  if (!n_finished || !idle || cap < 0 || (cap > 0 && !tickets_out)) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_advance");
-  HIPCHK(e, hipSetDevice(e->device));
-  Session& t = *e->sess;
-  if (t.broken) return session_broken(e, t);
-  *n_finished = 0; *idle = 0;
-  t.stats[SS_TURNS] += 1;
-  if (const int rc = turn_retire(e, t, tickets_out, cap, n_finished)) return rc;
-  SessCancelArgs ca;
-  turn_cancels(t, ca);
-  Admission a;
-  turn_admit(e, t, a);
-  if (t.live + a.ta.n_new == 0) return turn_idle(e, t, tickets_out, cap, n_finished, idle);
-  // the requests are admitted on the host already: if anything of the queued work fails the session is marked broken (see Session.broken)
-  const int rc4 = turn_queue(e, t, a, ca);
-  if (rc4) { t.broken = true; t.broken_msg = e->err; }
-  return rc4;
-}
-
-extern "C" int vc_session_fetch(vc_engine* e, int ticket, int64_t* res_dev, int res_cap, int* gen_len, int* n_steps) {
-  if (!e) return VC_EINVAL;
-  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
-  Session& t = *e->sess;
-  auto it = t.reqs.find(ticket);
-  if (it == t.reqs.end() || it->second.cancelled)
-    return fail(e, VC_EINVAL, "vc_session_fetch: unknown ticket %d (never issued, or fetched or cancelled already)", ticket);
-  if (it->second.state != 2) {
-    if (t.broken) return session_broken(e, t);
-    return fail(e, VC_ESTATE, "vc_session_fetch: the request of ticket %d has not finished", ticket);
-  }
-  HIPCHK(e, hipSetDevice(e->device));
-  SessReq r = std::move(it->second);
-  r.edit.iv = r.iv_own.data(); r.edit.mv = r.mv_own.data();
-  // whatever the outcome the ticket is spent: the slot (its K/V rows, its rows of the generated-token log) is free for the next request
-  // (of a best-of-N request only the kept sample's slot is still held, and none when no sample terminated)
-  if (r.slot >= 0) t.slot_ticket[r.slot] = -1;
-  t.reqs.erase(it);
-  if (!res_dev) return VC_OK;                               // dropped
-  if (!gen_len || res_cap < 0) return fail(e, VC_EINVAL, "null/invalid argument to vc_session_fetch");
-  if (r.prompt_err & 1)
-    return fail(e, VC_EINVAL, "ticket %d: token id out of range in x or y (text rows %d, audio vocab %d)", ticket, e->cfg.text_rows, e->V);
-  if (r.n_samples > 1 && r.kept < 0)
-    return fail(e, VC_ECAP, "ticket %d: no sample terminated within the step budget", ticket);
-  SeqState st;              // what the assembly reads of the request's final state, from the slot's record
-  memset(&st, 0, sizeof st);
-  st.done = 1; st.span = r.span; st.total_steps = r.total_steps;
-  for (int i = 0; i < VC_MAX_SPANS; ++i) st.span_steps[i] = r.span_steps[i];
-  // on the side stream: the request's rows of the log are final (its batch has ended), and the decode stream's queued batches are not waited for
-  int rc;
-  if (r.kind == 1) {
-    char who[32];
-    snprintf(who, sizeof who, "ticket %d: ", ticket);
-    rc = edit_assemble(e, r.edit, st, e->gen + (size_t)r.slot * e->gen_cap * e->K, res_dev, res_cap, gen_len, e->side_stream, who);
-  } else {
-    rc = assemble_tts(e, r.job, r.slot, st, res_dev, res_cap, gen_len, e->side_stream);
-  }
-  if (rc) return rc;
-  HIPCHK(e, hipStreamSynchronize(e->side_stream));
-  if (n_steps) *n_steps = r.total_steps;
-  return VC_OK;
-}
-
-extern "C" int vc_session_kept(vc_engine* e, int ticket, int* kept) {
-  if (!e) return VC_EINVAL;
-  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
-  if (!kept) return fail(e, VC_EINVAL, "null argument to vc_session_kept");
-  Session& t = *e->sess;
-  auto it = t.reqs.find(ticket);
-  if (it == t.reqs.end() || it->second.cancelled)
-    return fail(e, VC_EINVAL, "vc_session_kept: unknown ticket %d (never issued, or fetched or cancelled already)", ticket);
-  if (it->second.state != 2) {
-    if (t.broken) return session_broken(e, t);
-    return fail(e, VC_ESTATE, "vc_session_kept: the request of ticket %d has not finished", ticket);
-  }
-  *kept = it->second.n_samples > 1 ? it->second.kept : 0;   // (-1: no sample of the group terminated - the fetch returns VC_ECAP)
-  return VC_OK;
-}
-
-// Cancels a request in whatever state it is in (*was: 0 pending, 1 live, 2 finished and not yet fetched).  Host bookkeeping only: the
-// call waits for nothing and queues nothing - the rows of a live ticket are retired by session_cancel_k in the next vc_session_advance.
-extern "C" int vc_session_cancel(vc_engine* e, int ticket, int* was) {
-  if (!e) return VC_EINVAL;
-  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
-  Session& t = *e->sess;
-  if (t.broken) return session_broken(e, t);
-  auto it = t.reqs.find(ticket);
-  if (it == t.reqs.end() || it->second.cancelled)
-    return fail(e, VC_EINVAL, "vc_session_cancel: unknown ticket %d (never issued, or fetched or cancelled already)", ticket);
-  SessReq& r = it->second;
-  int state = r.state;
-  if (state == 1) {
-    // live on the host - but finished as far as the host can know, if the records of all its rows are stamped with batches advance has
-    // seen end (a turn whose tickets_out was full leaves such a request unreported): then it is a finished ticket
-    bool all_in = true;
-    for (int i = 0; i < r.n_samples && all_in; ++i) {
-      if (r.mdone[i]) continue;
-      volatile int* rec = e->h_rec + r.slots[i] * VC_SESS_REC;
-      const int stamp = rec[0];
-      all_in = stamp != 0 && stamp - 1 <= t.known;
-    }
-    if (all_in) {
-      for (int i = 0; i < r.n_samples; ++i) {
-        if (r.mdone[i]) continue;
-        volatile int* rec = e->h_rec + r.slots[i] * VC_SESS_REC;
-        t.live -= 1;
-        t.stats[SS_LIVE_ROWS] += std::max(0, (int)rec[1] - 1) + std::max(0, (int)rec[5]);
-      }
-      for (int& held : t.slot_ticket) if (held == ticket) held = -1;
-      r.slot = -1;
-      state = 2;
-    }
-  }
-  if (state == 0) {
-    // pending: out of the line, the order of the others unchanged; its prompt is never read
-    for (auto f = t.fifo.begin(); f != t.fifo.end(); ++f)
-      if (*f == ticket) { t.fifo.erase(f); break; }
-    t.reqs.erase(it);
-  } else if (state == 2) {
-    // finished and not fetched: vc_session_fetch(res_dev = NULL)
-    if (r.slot >= 0) t.slot_ticket[r.slot] = -1;
-    t.reqs.erase(it);
-  } else {
-    // live: every row of it that has not retired is retired by the next turn, and the slots come back when the host has read their
-    // records (session_note_retired) - the path of any retirement, so the schedule stays a function of the calls alone
-    r.cancelled = true;
-    r.cancel_queued = false;
-  }
-  if (was) *was = state;
-  return VC_OK;
-}
-
-namespace {
-// Frames of a TTS request the host knows to be final, from the submission schedule alone: the batches vc_session_advance has seen end
-// (t.known) and the slot's retirement record once its batch is among them - whether or not the retirement has been reported yet
-// (session_note_retired leaves a request live when tickets_out is full).  *ended: the count is the request's last.
-int session_final_frames(vc_engine* e, const Session& t, const SessReq& r, bool* ended) {
-  *ended = false;
-  if (r.state == 0 || r.adm_batch < 0 || t.known < r.adm_batch) return 0;
-  int spans = 0, s0 = 0, perr = 0;
-  if (r.state == 2) {
-    *ended = true; spans = r.span; s0 = r.span_steps[0]; perr = r.prompt_err;
-  } else {
-    volatile int* rec = e->h_rec + r.slot * VC_SESS_REC;
-    const int stamp = rec[0];
-    perr = rec[4];                                           // (written by the admitting turn's kernel, in front of batch adm_batch)
-    if (stamp != 0 && stamp - 1 <= t.known) { *ended = true; spans = rec[2]; s0 = rec[3]; }
-  }
-  if (perr & 1) return 0;                                    // an out-of-range token id in the prompt: nothing of it is handed out
-  if (*ended) return spans >= 1 ? std::max(0, s0 - e->K) : 0;      // (ran out of positions: no result, no further frames)
-  const long rows = 1 + (long)t.L.G * (t.known - r.adm_batch + 1);  // its first sample + graph_steps steps per ended batch
-  return (int)std::max(0L, std::min(rows, (long)e->gen_cap) - (e->K - 1));
-}
-}  // namespace
-
-extern "C" int vc_session_frames(vc_engine* e, int n, const int* tickets, int min_frames, int64_t* codes_dev, int cap,
-                                 int* first_frame, int* n_frames, int* done) {
-  if (!e) return VC_EINVAL;
-  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
-  Session& t = *e->sess;
-  if (t.broken) return session_broken(e, t);
-  if (!tickets || !codes_dev || !first_frame || !n_frames || !done) return fail(e, VC_EINVAL, "null argument to vc_session_frames");
-  if (n < 1 || n > t.max_live) return fail(e, VC_EINVAL, "vc_session_frames: %d tickets outside [1, max_live = %d]", n, t.max_live);
-  if (cap < 1 || min_frames < 1 || min_frames > cap)
-    return fail(e, VC_EINVAL, "vc_session_frames: min_frames %d outside [1, cap = %d]", min_frames, cap);
-  // every refusal before any cursor moves
-  for (int i = 0; i < n; ++i) {
-    auto it = t.reqs.find(tickets[i]);
-    if (it == t.reqs.end() || it->second.cancelled)
-      return fail(e, VC_EINVAL, "vc_session_frames: unknown ticket %d (never issued, or fetched or cancelled already)", tickets[i]);
-    if (it->second.kind == 1)
-      return fail(e, VC_EINVAL, "vc_session_frames: ticket %d: editing requests do not stream (their rows per batch hang on span "
-                  "switches known at retirement only, and their result is a splice)", tickets[i]);
-    if (it->second.n_samples > 1)
-      return fail(e, VC_EINVAL, "vc_session_frames: ticket %d: best-of-N requests do not stream (the kept sample is unknown until the "
-                  "group decides)", tickets[i]);
-    for (int k = 0; k < i; ++k)
-      if (tickets[k] == tickets[i]) return fail(e, VC_EINVAL, "vc_session_frames: ticket %d given twice", tickets[i]);
-  }
-  SessionGatherArgs a;
-  memset(&a, 0, sizeof a);
-  a.gen = e->gen; a.out = codes_dev; a.K = e->K; a.gen_stride = e->gen_cap; a.cap = cap; a.n = n;
-  int any = 0;
-  for (int i = 0; i < n; ++i) {
-    const SessReq& r = t.reqs[tickets[i]];
-    bool ended = false;
-    const int avail = session_final_frames(e, t, r, &ended) - r.emitted;
-    const int cnt = (avail >= min_frames || (ended && avail > 0)) ? std::min(avail, cap) : 0;
-    a.slot[i] = std::max(0, r.slot); a.first[i] = r.emitted; a.count[i] = cnt;
-    first_frame[i] = r.emitted; n_frames[i] = cnt;
-    done[i] = (ended && avail - cnt <= 0) ? 1 : 0;
-    any += cnt;
-  }
-  if (any > 0) {
-    // on the side stream, and that stream alone is waited for: the rows read are final, the decode stream's queued batches are not touched
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, vc_launch_session_gather(a, e->side_stream));
-    HIPCHK(e, hipStreamSynchronize(e->side_stream));
-  }
-  for (int i = 0; i < n; ++i) t.reqs[tickets[i]].emitted += n_frames[i];
-  return VC_OK;
-}
-
-extern "C" int vc_session_stats(vc_engine* e, int64_t out[8]) {
-  if (!e) return VC_EINVAL;
-  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
-  if (!out) return fail(e, VC_EINVAL, "null argument to vc_session_stats");
-  const Session& t = *e->sess;
-  for (int i = 0; i < 7; ++i) out[i] = t.stats[i];
-  out[7] = (int64_t)(t.adm_ms * 1000.0);                    // microseconds of decode-stream time spent on admissions whose batch has ended
-  return VC_OK;
-}
-
-extern "C" int vc_session_close(vc_engine* e) {
-  if (!e) return VC_EINVAL;
-  if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
-  HIPCHK(e, hipSetDevice(e->device));
-  Session& t = *e->sess;
-  int rc = VC_OK;
-  // wait for what is queued; the next call uploads every state afresh (vc_tts_stream_end with res_dev = NULL is the model)
-  hipError_t he = hipMemsetAsync(e->n_active, 0, sizeof(int), t.s);
-  if (he == hipSuccess) he = hipStreamSynchronize(t.s);
-  if (he != hipSuccess) rc = fail(e, VC_EHIP, "vc_session_close: %s", hipGetErrorString(he));
-  else rc = check_err_flag(e, t.s);                         // (reads and clears the flag word)
-  e->cur_rows = 0;
-  drop_session(e);
-  return rc;
-}
+}  // namespace vch
 
 extern "C" int vc_tts(vc_engine* e, const int64_t* x_dev, int Lx, const int64_t* y_dev, int T,
                       const vc_sample_cfg* sc, int n_samples, const int64_t* forced_dev, int n_forced,
@@ -3255,217 +2229,6 @@ extern "C" int vc_edit_multi(vc_engine* e, int B, const int64_t* x_dev, const in
   return VC_OK;
 }
 
-// Layout of one utterance's training sequence (host only; also exported as vc_eval_layout so that it can be checked
-// against the oracle without a GPU): the segment table prompt_k consumes (rearrange :239-252, shift :254-262,
-// insert_mask :264-288: every non-masked piece, then every masked piece + eog, a placeholder after each piece but the
-// last) and, per row of [text ; audio columns] and codebook, the target: piece column s, codebook q predicts piece token
-// t = s - q (revert_pattern_logits with is_model_output, codebooks_patterns.py:209-215, :247-266).
-// tgt: >= 0 index into the call's y ([frames][K], y_frame_off = first frame of this utterance); -1 none; <= -2 constant.
-int eval_layout(const vc_model_cfg& c, int K, int Lx, int T, const int32_t* iv, int M, const int32_t* mv, int y_frame_off,
-                Segment* seg, int* n_seg, int* n_cols, std::vector<int>* tgt, std::string* why) {
-  char buf[160];
-  if (Lx < 1 || T < 1) { *why = "empty text or audio"; return 1; }
-  if (M < 1 || M > c.max_n_spans) { snprintf(buf, sizeof buf, "%d spans outside [1,%d]", M, c.max_n_spans); *why = buf; return 1; }
-  for (int j = 0; j < M; ++j) {
-    if (mv[j] < 0 || mv[j] >= c.max_n_spans) { *why = "mask value out of range"; return 1; }
-    const int lo = j ? iv[2 * (j - 1) + 1] : 0;
-    if (iv[2 * j] < lo || iv[2 * j + 1] < iv[2 * j] || iv[2 * j + 1] > T) {
-      snprintf(buf, sizeof buf, "mask intervals must be ordered, disjoint and inside [0,%d]", T); *why = buf; return 1;
-    }
-  }
-  struct Piece { int s, e, term; };
-  std::vector<Piece> pieces;
-  for (int j = 0; j <= M; ++j) {                   // non-masked pieces, the terminator as rearrange() places it
-    const int ps = j ? iv[2 * (j - 1) + 1] : 0, pe = (j == M) ? T : iv[2 * j];
-    int term;
-    if (c.eos > 0) term = (j == M) ? c.eos : -1;
-    else if (c.reduced_eog) term = (j == M) ? c.eog : -1;
-    else term = c.eog;
-    pieces.push_back(Piece{ps, pe, term});
-  }
-  for (int j = 0; j < M; ++j) pieces.push_back(Piece{iv[2 * j], iv[2 * j + 1], c.eog});     // masked pieces, always + eog
-  if ((int)(2 * pieces.size()) > VC_MAX_SEG) { *why = "too many segments"; return 1; }
-  int col = 0, ns = 0;
-  tgt->assign((size_t)Lx * K, -1);                 // text rows carry no target
-  for (size_t j = 0; j < pieces.size(); ++j) {
-    const Piece& p = pieces[j];
-    const int n = (p.e - p.s) + (p.term >= 0 ? 1 : 0);
-    if (n <= 0) { snprintf(buf, sizeof buf, "piece %d is empty (the reference raises inside get_pattern)", (int)j); *why = buf; return 1; }
-    seg[ns++] = Segment{col, n + K, p.s, p.e - p.s, p.term, -1};
-    for (int sidx = 0; sidx < n + K; ++sidx)
-      for (int q = 0; q < K; ++q) {
-        const int t = sidx - q;
-        int v = -1;
-        if (t >= 0 && t < n) v = (t < p.e - p.s) ? (int)(((long)y_frame_off + p.s + t) * K + q) : -(p.term + 2);
-        tgt->push_back(v);
-      }
-    col += n + K;
-    if (j + 1 < pieces.size()) {                   // placeholder: values = emb_inds_use + emb_inds_use (:274)
-      seg[ns++] = Segment{col, 1, 0, 0, -1, mv[j % M]};
-      for (int q = 0; q < K; ++q) tgt->push_back(-1);
-      col += 1;
-    }
-  }
-  *n_seg = ns; *n_cols = col;
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------- training objective
-// VoiceCraft.forward (voicecraft.py:472-559) with given mask intervals (validated on MI355X: tests/test_gpu_forward.py).
-// The decoder pass is the prefill's (row stream over all utterances, block GEMM + tile attention); after every pass the
-// heads run over its rows 16 at a time and ce_rows_k turns each group's logits into per-row terms straight away, so the
-// [rows][K][V] logits of the whole batch never exist.
-extern "C" int vc_eval_forward(vc_engine* e, int B, const int64_t* x_dev, const int32_t* x_off,
-                               const int64_t* y_dev, const int32_t* y_off,
-                               const int32_t* spans, const int32_t* span_off, const int32_t* mask_values,
-                               double* nll_sum, int64_t* hits, int64_t* n_targets,
-                               float* nll_dev, int32_t* tgt_dev, int64_t nll_cap, int64_t* n_rows_out, void* stream) {
-  int rc = check_idle(e);
-  if (rc) return rc;
-  if (B < 1 || !x_dev || !x_off || !y_dev || !y_off || !spans || !span_off || !mask_values || !nll_sum || !hits || !n_targets)
-    return fail(e, VC_EINVAL, "null/invalid argument to vc_eval_forward");
-  if (B > e->B_max) return fail(e, VC_ECAP, "%d utterances, the engine was created for max_seqs %d", B, e->B_max);
-  hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
-  const int K = e->K;
-  const vc_model_cfg& c = e->cfg;
-  if (c.eos > 0 && !c.reduced_eog) return fail(e, VC_EINVAL, "eos > 0 requires reduced_eog (voicecraft.py:244)");
-  if (!e->ce_tgt) {
-    if ((rc = dalloc(e, &e->ce_tgt, (size_t)e->emb_cap * K))) return rc;
-    if ((rc = dalloc(e, &e->ce_hit, (size_t)e->emb_cap * K))) return rc;
-    if ((rc = dalloc(e, &e->ce_nll, (size_t)e->emb_cap * K))) return rc;
-    if ((rc = dalloc(e, &e->ce_sum, (size_t)VC_MAX_CODEBOOKS))) return rc;
-    if ((rc = dalloc(e, &e->ce_hits, (size_t)VC_MAX_CODEBOOKS))) return rc;
-    if ((rc = dalloc(e, &e->ce_cnt, (size_t)VC_MAX_CODEBOOKS))) return rc;
-  }
-  // ---- per utterance: the segment table of its training sequence and the target of every (row, codebook)
-  std::vector<PromptArgs> pas(B);
-  std::vector<std::vector<int>> tgts(B);          // [rows_i][K]
-  for (int i = 0; i < B; ++i) {
-    const int Lx = x_off[i + 1] - x_off[i], T = y_off[i + 1] - y_off[i], M = span_off[i + 1] - span_off[i];
-    PromptArgs& pa = pas[i];
-    fill_prompt_common(e, pa, x_dev + x_off[i], std::max(Lx, 0), y_dev + (size_t)y_off[i] * K, std::max(T, 0));
-    std::string why;
-    if (eval_layout(c, K, Lx, T, spans + 2 * (size_t)span_off[i], M, mask_values + span_off[i], y_off[i], pa.seg, &pa.n_seg,
-                    &pa.n_cols, &tgts[i], &why))
-      return fail(e, VC_EINVAL, "utterance %d: %s", i, why.c_str());
-    if (Lx + pa.n_cols > e->S_max) return fail(e, VC_ECAP, "utterance %d: %d positions, max_positions is %d", i, Lx + pa.n_cols, e->S_max);
-  }
-  const bool hook = nll_dev && tgt_dev;            // parity hook: per-row terms, targets and head logits of every row
-  if (hook) {
-    int64_t need_rows = 0;
-    for (int i = 0; i < B; ++i) need_rows += ((pas[i].Lx + pas[i].n_cols) + 15) & ~15;
-    if (need_rows > e->eval_logits_cap) {
-      HIPCHK(e, hipStreamSynchronize(s));
-      if (e->eval_logits) { (void)hipFree(e->eval_logits); e->eval_logits = nullptr; e->eval_logits_cap = 0; }
-      void* v = nullptr;
-      const size_t nb = (size_t)need_rows * K * e->V * sizeof(float);
-      if (hipMalloc(&v, nb) != hipSuccess) return fail(e, VC_EHIP, "hipMalloc(%zu bytes) for the per-row logits failed", nb);
-      e->eval_logits = (float*)v; e->eval_logits_cap = need_rows;
-    }
-    e->eval_logits_rows = 0;
-  }
-  HIPCHK(e, hipMemsetAsync(e->ce_sum, 0, sizeof(double) * VC_MAX_CODEBOOKS, s));
-  HIPCHK(e, hipMemsetAsync(e->ce_hits, 0, sizeof(long long) * VC_MAX_CODEBOOKS, s));
-  HIPCHK(e, hipMemsetAsync(e->ce_cnt, 0, sizeof(long long) * VC_MAX_CODEBOOKS, s));
-  HIPCHK(e, hipEventRecord(e->ev[0], s));
-  const int chunk = e->prefill_rows_per_pass;
-  int64_t rows_out = 0;
-  size_t i0 = 0;
-  std::vector<int> tg_host;
-  while (i0 < (size_t)B) {                         // groups of utterances that fit the row arena (as prefill_batch)
-    size_t i1 = i0;
-    int R = 0;
-    auto rows_of = [](const PromptArgs& pa) { return ((pa.Lx + pa.n_cols) + 15) & ~15; };
-    while (i1 < (size_t)B && (i1 == i0 || R + rows_of(pas[i1]) <= e->emb_cap)) { R += rows_of(pas[i1]); ++i1; }
-    if (R > e->emb_cap) return fail(e, VC_ECAP, "an utterance of %d rows does not fit the row arena of %d rows", R, e->emb_cap);
-    HIPCHK(e, hipMemsetAsync(e->pre_row_pos, 0xFF, (size_t)R * sizeof(int), s));
-    HIPCHK(e, hipMemsetAsync(e->pre_row_seq, 0, (size_t)R * sizeof(int), s));
-    HIPCHK(e, hipMemsetAsync(e->emb, 0, (size_t)R * e->d * sizeof(float), s));
-    tg_host.assign((size_t)R * K, -1);
-    int row0 = 0;
-    for (size_t i = i0; i < i1; ++i) {
-      PromptArgs& pa = pas[i];
-      const int rows = pa.Lx + pa.n_cols;
-      pa.seq = (int)(i - i0); pa.row0 = row0;     // a cache slot per utterance of the group
-      pa.emb = e->emb; pa.row_seq = e->pre_row_seq; pa.row_pos = e->pre_row_pos; pa.err = e->err_flag;
-      pa.logit_row = nullptr;
-      HIPCHK(e, vc_launch_prompt(pa, s));
-      if ((size_t)rows * K != tgts[i].size()) return fail(e, VC_ESTATE, "internal: target table of utterance %d", (int)i);
-      std::copy(tgts[i].begin(), tgts[i].end(), tg_host.begin() + (size_t)row0 * K);
-      row0 += (rows + 15) & ~15;
-    }
-    // the host table must outlive the copy: synchronous copy (a few hundred KB, once per group)
-    HIPCHK(e, hipStreamSynchronize(s));
-    HIPCHK(e, hipMemcpy(e->ce_tgt, tg_host.data(), (size_t)R * K * sizeof(int), hipMemcpyHostToDevice));
-    for (int r0 = 0; r0 < R; r0 += chunk) {
-      RowSrc rs{};
-      rs.h_in = e->emb + (size_t)r0 * e->d;
-      rs.row_seq = e->pre_row_seq + r0; rs.row_pos = e->pre_row_pos + r0;
-      rs.n_rows = std::min(chunk, R - r0);
-      const PassPlan p = plan_pass(e, rs.n_rows, false, rs.n_rows > VC_ROWS ? 1 : 0);      // 16-row tiles only
-      PassOut po;
-      if ((rc = run_pass(e, p, rs, &po, s))) return rc;
-      for (int g0 = 0; g0 < rs.n_rows; g0 += VC_ROWS) {
-        const int n = std::min(VC_ROWS, rs.n_rows - g0);
-        if ((rc = run_heads(e, p, po, nullptr, n, g0, 0, nullptr, s))) return rc;
-        CeArgs ca;
-        memset(&ca, 0, sizeof ca);
-        ca.logits = e->logits; ca.y = y_dev; ca.tgt = e->ce_tgt + (size_t)(r0 + g0) * K;
-        ca.nll = e->ce_nll + (size_t)(r0 + g0) * K; ca.hit = e->ce_hit + (size_t)(r0 + g0) * K;
-        ca.n_rows = n; ca.K = K; ca.V = e->V; ca.err = e->err_flag;
-        HIPCHK(e, vc_launch_ce(ca, s));
-        if (hook)                                    // (rows_out + R <= eval_logits_cap: both are sums of the same padded row counts)
-          HIPCHK(e, hipMemcpyAsync(e->eval_logits + (size_t)(rows_out + r0 + g0) * K * e->V, e->logits, (size_t)n * K * e->V * sizeof(float),
-                                   hipMemcpyDeviceToDevice, s));
-      }
-    }
-    CeReduceArgs ra;
-    memset(&ra, 0, sizeof ra);
-    ra.nll = e->ce_nll; ra.hit = e->ce_hit; ra.tgt = e->ce_tgt; ra.n_rows = R; ra.K = K;
-    ra.nll_sum = e->ce_sum; ra.hits = e->ce_hits; ra.count = e->ce_cnt;
-    HIPCHK(e, vc_launch_ce_reduce(ra, s));
-    if (hook) {                                    // parity hook: the per-row terms of this group, appended
-      if (rows_out + R > nll_cap) return fail(e, VC_ECAP, "nll capacity %lld < %lld rows", (long long)nll_cap, (long long)(rows_out + R));
-      HIPCHK(e, hipMemcpyAsync(nll_dev + rows_out * K, e->ce_nll, (size_t)R * K * sizeof(float), hipMemcpyDeviceToDevice, s));
-      HIPCHK(e, hipMemcpyAsync(tgt_dev + rows_out * K, e->ce_tgt, (size_t)R * K * sizeof(int), hipMemcpyDeviceToDevice, s));
-    }
-    rows_out += R;
-    if (hook) e->eval_logits_rows = rows_out;
-    HIPCHK(e, hipStreamSynchronize(s));          // the next group reuses the arena, the target table and the cache slots
-    i0 = i1;
-  }
-  HIPCHK(e, hipEventRecord(e->ev[1], s));
-  rc = check_err_flag(e, s);
-  if (rc) return rc;
-  double h_sum[VC_MAX_CODEBOOKS];
-  long long h_hits[VC_MAX_CODEBOOKS], h_cnt[VC_MAX_CODEBOOKS];
-  HIPCHK(e, hipMemcpy(h_sum, e->ce_sum, sizeof h_sum, hipMemcpyDeviceToHost));
-  HIPCHK(e, hipMemcpy(h_hits, e->ce_hits, sizeof h_hits, hipMemcpyDeviceToHost));
-  HIPCHK(e, hipMemcpy(h_cnt, e->ce_cnt, sizeof h_cnt, hipMemcpyDeviceToHost));
-  for (int k = 0; k < K; ++k) { nll_sum[k] = h_sum[k]; hits[k] = h_hits[k]; }
-  *n_targets = h_cnt[0];
-  if (n_rows_out) *n_rows_out = rows_out;
-  HIPCHK(e, hipEventElapsedTime(&e->ms[0], e->ev[0], e->ev[1]));
-  e->ms[1] = 0.f; e->ms[2] = e->ms[0];
-  return VC_OK;
-}
-
-extern "C" int vc_eval_layout(const vc_model_cfg* cfg, int Lx, int T, const int32_t* spans, int M, const int32_t* mask_values,
-                              int y_frame_off, int32_t* seg_out, int* n_seg, int* n_cols, int32_t* tgt_out, int64_t tgt_cap) {
-  if (!cfg || !spans || !mask_values || !seg_out || !n_seg || !n_cols || !tgt_out) return VC_EINVAL;
-  Segment seg[VC_MAX_SEG];
-  std::vector<int> tgt;
-  std::string why;
-  if (eval_layout(*cfg, cfg->n_codebooks, Lx, T, spans, M, mask_values, y_frame_off, seg, n_seg, n_cols, &tgt, &why)) return VC_EINVAL;
-  if ((int64_t)tgt.size() > tgt_cap) return VC_ECAP;
-  for (int i = 0; i < *n_seg; ++i) {
-    int32_t* o = seg_out + 6 * i;
-    o[0] = seg[i].col0; o[1] = seg[i].ncols; o[2] = seg[i].src0; o[3] = seg[i].src_len; o[4] = seg[i].term; o[5] = seg[i].mask_value;
-  }
-  std::copy(tgt.begin(), tgt.end(), tgt_out);
-  return VC_OK;
-}
-
 // ------------------------------------------------------------------------------------- hooks
 extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int64_t nbytes) {
   int rc = check_ready(e);
@@ -3537,9 +2300,8 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
     return VC_OK;
   }
   else if (n == "session_slots") {  // the open decode session's bookkeeping: {rows of the step in force, ticket holding slot 0, 1, ... (-1 = free)}
-    if (!e->sess) return fail(e, VC_ESTATE, "no decode session is open (vc_session_open)");
-    std::vector<int32_t> v{e->sess->B};
-    v.insert(v.end(), e->sess->slot_ticket.begin(), e->sess->slot_ticket.end());
+    std::vector<int32_t> v;
+    if (const int rc = debug_session_slots(e, v)) return rc;
     if (nbytes != (int64_t)(v.size() * 4)) return fail(e, VC_ECAP, "debug buffer 'session_slots' holds %lld bytes", (long long)(v.size() * 4));
     memcpy(host_dst, v.data(), (size_t)nbytes);
     return VC_OK;

@@ -584,7 +584,7 @@ __device__ void advance_phase(const SampleArgs& a, const SampleDyn& dy, int b, b
       }
       if (done) {
         sp->done = 1;
-        if (SESS) {                            // the host counts the retirement once it has waited for batch `stamp` (vc_engine.hip Session)
+        if (SESS) {                            // the host counts the retirement once it has waited for batch `stamp` (vc_engine_session.hip Session)
           int* rec = dy.retire_rec + slot * VC_SESS_REC;
           const int s0 = (span >= 1) ? sp->span_steps[0] : 0;
           const int stamp = *dy.batch_id;
@@ -1352,7 +1352,7 @@ hipError_t vc_launch_stream_gather(const StreamGatherArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 // The frames of up to VC_MAX_SEQS session tickets in one launch, one workgroup per ticket: out[i][j][t] = gen[slot][first + j + t][j].
-// Every count comes from the host (what it knows to be final, vc_engine.hip vc_session_frames): no state is read, nothing is reported
+// Every count comes from the host (what it knows to be final, vc_engine_session.hip vc_session_frames): no state is read, nothing is reported
 // back.  Consecutive lanes store consecutive t.
 __global__ __launch_bounds__(256) void session_gather_k(const SessionGatherArgs a) {
   const int i = blockIdx.x;
