@@ -150,6 +150,16 @@ const char* vc_version(void);
  *                  result bit-identical to the image launch; a refused matrix keeps its image launch for that layer.  "w8" stays the
  *                  one-row launches.  The option text ends in |w8=<mask>|w8r=<mask> on such an engine only (vc_debug_w8r_plan says which
  *                  row counts take the form)
+ *   "w8w"          mask of the same bits plus 8, ONLY on an engine that called vc_request_w8_wide (default: the requested mask; VC_EINVAL
+ *                  on any other engine): steps of 17..64 rows stream the FFN down-projection (1) and the QKV projection of every layer
+ *                  (4) as E4M3 PAIR planes of their 16-channel images (rows_gemm_wds_w8_k: the staged wide kernel, option "wd_stage" = 1,
+ *                  where the K slice a wave owns is 2, 4 or 8 k-tiles) - a pair = two k-tiles of a 16-channel tile = 1 KB of codes +
+ *                  two shift bytes (channels 0..7, channels 8..15: two blocks of the same grid) -, every result bit-identical to the
+ *                  image launch; a refused matrix keeps its image launch for that layer (vc_debug_read "w8w_stats", layout of
+ *                  "w13_stats", pairs refused).  Bit 8: also at the row counts the measured win table leaves out (for the A/B tool and
+ *                  the tests; vc_debug_w8w_plan says which row counts take the form).  The option text gains |w8w=<v> behind |w8=<mask>
+ *                  and, if present, |w8r=<mask> on such an engine only.  Resident memory: + 0.5 x the two images (7 d^2 bytes per
+ *                  layer: + 0.47 GB at giga830M), on engines that can run wide steps (max_seqs > 16)
  *   "kv8"          0 / 1, ONLY on an engine that called vc_request_kv8 (default 1; VC_EINVAL on any other engine): decode passes read the
  *                  cached K / V positions older than the pass as one OCP E4M3 byte per value times 2^shift, one shift byte per cached
  *                  row of a head (csrc/vc_kv8.h; voicecraft_amd/quant.py kv8_quantize_rows states the grid), half the bytes of the bf16
@@ -160,7 +170,7 @@ const char* vc_version(void);
  * What an option may change: nothing in the exact fp32 mode's greedy tokens (tests/test_gpu_options.py, test_gpu_one_row.py); in bf16
  * mode the forms that re-order sums or round at another place ("finished_rows", "fr_pair", "att_p16", "hq", "fr_one", "qkv_p8", "attn_fast",
  * "qkv16", "wide_heads", "wide_gemm") move head logits by bf16 rounding (tests allow 0.25 absolute), so top-k SAMPLED tokens can differ between option
- * states; the cache-policy / data-path / host-side options ("nt", "wd_stage", "graph_steps", "shrink", "w13", "w8") change no value; "kv8" rounds cached K / V to its grid.
+ * states; the cache-policy / data-path / host-side options ("nt", "wd_stage", "graph_steps", "shrink", "w13", "w8", "w8r", "w8w") change no value; "kv8" rounds cached K / V to its grid.
  * The non-temporal mask "nt" has no bit for the finished-row producers (rows_gemm_fr_k, rows_gemm_fr2_k, row_gemm_fr1_k) and the
  * wide-decode kernels: they always stream with the hint.  Captured decode graphs are kept per option state and step width, so an
  * in-process A/B (bench.py --ab) pays for capture once per state.  Unknown names / malformed values: VC_EINVAL.
@@ -187,6 +197,12 @@ int vc_request_w8(vc_engine* e, int mask);
  * finished rows stream the requested planes too, option "w8r" above.  `mask`: bits 1 and 4 as above, a subset of vc_request_w8's (anything
  * else: VC_EINVAL).  Nothing more is packed.  An engine without this request has no such option and launches what it launched before. */
 int vc_request_w8_rows(vc_engine* e, int mask);
+/* After vc_request_w8 on the same engine (VC_ESTATE without it) and before vc_finalize_weights (VC_ESTATE after it): steps of 17..64
+ * rows stream the matrices of `mask` as E4M3 pair planes, option "w8w" above.  `mask`: bits 1 and 4 as above, a subset of
+ * vc_request_w8's (anything else: VC_EINVAL).  vc_finalize_weights then packs the 16-channel images of those matrices once more, for
+ * an engine that can run wide steps (max_seqs > 16): + 0.5 x the two images resident, + 0.47 GB at giga830M.  An engine without this
+ * request packs nothing more, has no such option and launches what it launched before. */
+int vc_request_w8_wide(vc_engine* e, int mask);
 /* Before vc_finalize_weights (VC_ESTATE after it): keep, next to every layer's bf16 K / V cache, an E4M3 copy (one byte per value) and one
  * shift byte per cached row of a head, written by one packer launch behind every pass, and let the decode attention read the positions
  * older than the pass from it (option "kv8" above).  bf16 only: vc_finalize_weights with VC_DTYPE_F32 after the request returns
@@ -579,6 +595,16 @@ int vc_debug_plan(const vc_model_cfg* cfg, int compute_dtype, int rows, int32_t 
  * rows_gemm_qp_w8_k), out[2] / out[3] their groups per wave (0 where the form is not taken).  VC_EINVAL: a null pointer, rows < 1,
  * a mask with other bits than 1 and 4.  tests/test_w8_rows_cpu.py walks every model width with it. */
 int vc_debug_w8r_plan(const vc_model_cfg* cfg, int mask, int rows, int32_t out[4]);
+/* Host only: what option "w8w" = mask (bits 1, 4 and 8) makes of a bf16 decode pass of `rows` rows at this model shape, every matrix
+ * taken as packed.  out[0] / out[1] = 1 when the FFN down-projection / the QKV projection run on the pair planes (rows_gemm_wds_w8_k),
+ * out[2] / out[3] the k-tiles per wave of the FFN-down K slice / of the QKV matrix there (0 where the form is not taken).  All zeros
+ * up to 16 rows.  VC_EINVAL: a null pointer, rows < 1, a mask with other bits.  tests/test_w8_wide_cpu.py walks every model width. */
+int vc_debug_w8w_plan(const vc_model_cfg* cfg, int mask, int rows, int32_t out[4]);
+/* Host only: the packer of the pair planes (csrc/vc_w8.h, the text the device packer runs per lane) on n_pairs pairs of a 16-channel
+ * bf16 image (2 KB each: fragments of k-tiles 2j, 2j + 1 of one tile, lane l = channel l & 15, inputs 8 (l >> 4) .. + 7 of its k-tile):
+ * planes = n_pairs x 1 KB (16 bytes per lane: eight codes of k-tile 2j, eight of 2j + 1), side = n_pairs x 2 bytes (shift + 127 of
+ * channels 0..7, of channels 8..15), *refused_pairs = pairs with a half off the grid.  Returns 0, or -1 on a null pointer. */
+int vc_w8w_pack_host(const uint16_t* image16, long n_pairs, uint8_t* planes, uint8_t* side, int32_t* refused_pairs);
 /* Copies a named internal device buffer to host memory.  "kcache<l>" / "vcache<l>": layer l's K / V cache, [max_seqs][H][max_positions][hd]
  * in the compute dtype; "eval_logits": see vc_eval_forward. */
 int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int64_t nbytes);

@@ -5,6 +5,7 @@
 // Control flow restated from VoiceCraft.inference_tts / inference_tts_batch / inference
 // (models/voicecraft.py:908-1153, :1156-1439, :561-906); see DESIGN.md §2 for the mapping.
 #include "vc_engine_host.h"
+#include "vc_w8.h"      // the pair planes' sizes (pack_pairs)
 
 namespace {
 
@@ -124,6 +125,28 @@ int pack_planes(vc_engine* e, Layer& ly, int kind, int which, const uint4* image
   return VC_OK;
 }
 
+// The pair planes (vc_w8.h "w8w", slot PK_W8W) of a 16-channel bf16 image of `n_pairs` pairs: pack_planes for the wide kernel's images.
+// A pair with a half off the grid, or any dword that does not decode to the image's, refuses the matrix for this layer.
+int pack_pairs(vc_engine* e, Layer& ly, int which, const uint4* image, long n_pairs) {
+  if (!e->w13_counts) { int rc = dalloc(e, &e->w13_counts, (size_t)4); if (rc) return rc; }
+  Layer::Packed& p = ly.packed[PK_W8W][which];
+  const size_t mark = e->allocs.size();
+  const double bytes0 = e->bytes_total;
+  int rc;
+  if ((rc = dalloc(e, &p.planes, (size_t)n_pairs * VC_W8W_PAIR_U4))) return rc;
+  if ((rc = dalloc(e, &p.side, (size_t)(n_pairs + 1) / 2))) return rc;      // two bytes per pair
+  HIPCHK(e, vc_launch_w8w_pack(image, n_pairs, p.planes, reinterpret_cast<unsigned char*>(p.side), e->w13_counts, 0));
+  unsigned int cnt[2] = {0, 0};
+  HIPCHK(e, hipMemcpy(cnt, e->w13_counts, sizeof cnt, hipMemcpyDeviceToHost));
+  p.refused = (int)cnt[0];
+  if (cnt[0] == 0 && cnt[1] == 0) { p.state = 1; return VC_OK; }
+  p.state = 2;
+  while (e->allocs.size() > mark) { (void)hipFree(e->allocs.back()); e->allocs.pop_back(); }
+  e->bytes_total = bytes0;
+  p.planes = nullptr; p.side = nullptr;
+  return VC_OK;
+}
+
 int keep_vec(vc_engine* e, const std::string& key, int n, float** out, float* mean = nullptr) {
   const RawTensor* t;
   int rc = need(e, key, {n}, &t);
@@ -214,6 +237,18 @@ bool w8r_rows_win(int which, int rows) {
   return rows >= 2 && rows <= 8;
 }
 
+
+// Option "w8w": the row counts at which the pair-plane form of matrix `which` measured faster than the image over the whole paired
+// range; row counts between measured ones follow the nearest measured count of the same RT (17..32, 33..64).
+// profiles/w8_wide_ab.log (tools/w8_wide_ab.py: giga830M, 7 interleaved pairs per line, captured decode loop per step, min..max of the
+// pairs) at 17, 24, 32 | 33, 48, 64 rows: FFN-down alone -4.9 .. -3.5 % | -3.6 .. -2.9 %, QKV alone -3.1 .. -2.9 % | -2.3 .. -2.0 %, both
+// -7.9 .. -7.3 % | -5.6 .. -5.2 %: every measured row count of both bits has its whole range below zero, so every wide row count
+// takes the form.
+bool w8w_rows_win(int which, int rows) {
+  (void)which;
+  return rows > VC_ROWS && rows <= VC_MAX_SEQS;
+}
+
 }  // namespace
 namespace vch __attribute__((visibility("hidden"))) {
 // decode: a decode step (n_active set).  tiled: a prefill pass whose 16-row tiles (1) or 64-row blocks (2) each hold consecutive
@@ -282,6 +317,14 @@ PassPlan plan_pass(const vc_engine* e, int rows, bool decode, int tiled) {
       const int ko = wd_ksplit(e, d, d), kf = wd_ksplit(e, d, 4 * d);
       p.wd = vc_gemm_wd_kpw(d, e->dtype, 1) && ko && kf && vc_gemm_wd_kpw(e->P, e->dtype, 1);
       if (p.wd) { p.ks_o = ko; p.ks_f2 = kf; }
+      // option "w8w": FFN-down (on its split-K slices) and QKV on the pair planes, where the staged form runs and the launcher has
+      // a form for the slice.  The sites take it for the layers whose matrix is packed.
+      const vc_packed_kind& pk8 = vc_packed(VC_PK_W8);
+      const bool staged = p.wd && e->wd_stage;
+      p.wd_w8_f2 = staged && (e->w8w & W8_BITS[W13_F2]) && pk8.wd_ok(4 * d, e->dtype, p.ks_f2) != 0 &&
+                   (w8w_rows_win(W13_F2, rows) || (e->w8w & 8));
+      p.wd_w8_qkv = staged && (e->w8w & W8_BITS[W13_QKV]) && pk8.wd_ok(d, e->dtype, 1) != 0 &&
+                    (w8w_rows_win(W13_QKV, rows) || (e->w8w & 8));
     }
   }
   p.heads_wide = p.form == FORM_WIDE && e->wide_heads;
@@ -359,7 +402,10 @@ int site_qkv(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly,
   } else if (p.qkv16) {    // every A lane a weight: the 16-channel image
     g.x_in = e->xn; g.x_ld = d;
     g.Wp = ly.Wqkv16; g.n_tiles = e->p_qkv16.n_tiles; g.KT = e->p_qkv16.KT; g.nchunk = e->p_qkv16.nchunk;
-    if (p.wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_QKV16, 1, 1, s));
+    const Layer::Packed& pw = ly.packed[PK_W8W][W13_QKV];
+    if (p.wd_w8_qkv && pw.state == 1)      // ... on the pair planes (a refused layer keeps its image)
+      HIPCHK(e, vc_packed(VC_PK_W8).wd(g, pw.planes, reinterpret_cast<const uint8_t*>(pw.side), EPI_QKV16, 1, s));
+    else if (p.wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_QKV16, 1, 1, s));
     else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_QKV16, 1, 1, s));
   } else {
     g.x_in = e->xn; g.x_ld = d;
@@ -487,7 +533,10 @@ int site_ffn_down(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer
     return VC_OK;
   }
   g.Wp = ly.W2; nt_bit(e, g, NT_F2); g.part_out = e->parts; g.mt = p.mt;
-  if (p.wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_PART, p.ks_f2, 1, s));
+  const Layer::Packed& pw = ly.packed[PK_W8W][W13_F2];
+  if (p.wd_w8_f2 && pw.state == 1)         // ... on the pair planes (a refused layer keeps its image)
+    HIPCHK(e, vc_packed(VC_PK_W8).wd(g, pw.planes, reinterpret_cast<const uint8_t*>(pw.side), EPI_PART, p.ks_f2, s));
+  else if (p.wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_PART, p.ks_f2, 1, s));
   else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_PART, p.ks_f2, 1, s));
   return VC_OK;
 }
@@ -964,6 +1013,11 @@ int need_w8(vc_engine* e, const char* name, int v0) {
 int need_w8r(vc_engine* e, const char* name, int v0) {
   return e->w8r_req ? need_mask(e, name, v0) : fail(e, VC_EINVAL, "option 'w8r': this engine was created without vc_request_w8_rows");
 }
+// mask like "w8r" plus bit 8, on an engine that requested the wide form (vc_request_w8_wide)
+int need_w8w(vc_engine* e, const char*, int v0) {
+  if (!e->w8w_req) return fail(e, VC_EINVAL, "option 'w8w': this engine was created without vc_request_w8_wide");
+  return v0 < 0 || (v0 & ~13) ? fail(e, VC_EINVAL, "option 'w8w': %d is not a mask of 1 (FFN-down), 4 (QKV) and 8 (every row count)", v0) : VC_OK;
+}
 int need_kv8(vc_engine* e, const char*, int) {
   return e->kv8_req ? VC_OK : fail(e, VC_EINVAL, "option 'kv8': this engine was created without vc_request_kv8");
 }
@@ -1008,6 +1062,7 @@ const OptDesc OPTIONS[] = {
     {"w13", "VC_W13", "w13", {&E::w13, 0, 5}, nullptr, {}, need_mask},
     {"w8", nullptr, "w8", {&E::w8, 0, 5}, nullptr, {}, need_w8, &E::w8_req},      // only an engine that requested the form has the option
     {"w8r", nullptr, "w8r", {&E::w8r, 0, 5}, nullptr, {}, need_w8r, &E::w8r_req},   // likewise (vc_request_w8_rows)
+    {"w8w", nullptr, "w8w", {&E::w8w, 0, 13}, nullptr, {}, need_w8w, &E::w8w_req},  // likewise (vc_request_w8_wide)
     {"kv8", nullptr, "kv8", {&E::kv8, 0, 1}, nonzero, {}, need_kv8, &E::kv8_req},   // likewise
     {"prefill_rows", "VC_PREFILL_ROWS", nullptr, {&E::prefill_rows_per_pass, VC_ROWS, VC_MAX_ROWS}, whole_tiles},   // 16: decode kernels only
 };
@@ -1080,6 +1135,24 @@ extern "C" int vc_debug_w8r_plan(const vc_model_cfg* c, int mask, int rows, int3
   out[1] = p.qp_w8 ? 1 : 0;
   out[2] = p.frp_w8 ? vc_packed(VC_PK_W8).frp_ng(rows, d, 4 * d, e.dtype) : 0;
   out[3] = p.qp_w8 ? vc_packed(VC_PK_W8).qp_ng(rows, 3 * d, d, e.dtype) : 0;
+  return VC_OK;
+}
+// Host-only: what option "w8w" = mask (bits 1, 4, 8) makes of a bf16 decode pass of `rows` rows at this model shape, every matrix taken
+// as packed (plan_pass itself): out = {FFN-down on the pair planes, QKV on them, k-tiles per wave of the FFN-down slice, of the QKV matrix}.
+extern "C" int vc_debug_w8w_plan(const vc_model_cfg* c, int mask, int rows, int32_t out[4]) {
+  if (!c || !out || rows < 1 || rows > VC_MAX_SEQS || mask < 0 || (mask & ~13) || c->d_model <= 0 || c->nhead <= 0 || c->d_model % c->nhead)
+    return VC_EINVAL;
+  vc_engine e;      // default options, the weight images vc_finalize_weights packs for an engine that takes wide steps, both requests made
+  e.cfg = *c; e.d = c->d_model; e.H = c->nhead; e.hd = c->d_model / c->nhead; e.P = c->head_hidden; e.dtype = VC_DTYPE_BF16;
+  const int d = e.d;
+  e.has_fr8 = e.has_qkv16 = true;
+  e.has_qkv8 = vc_gemm_fr1_ok(3 * d, d, e.dtype, 4) != 0;
+  e.w8_req = e.w8 = 5; e.w8w_req = 5; e.w8w = mask;
+  const PassPlan p = plan_pass(&e, rows, true, 0);
+  out[0] = p.wd_w8_f2 ? 1 : 0;
+  out[1] = p.wd_w8_qkv ? 1 : 0;
+  out[2] = p.wd_w8_f2 ? vc_gemm_wd_kpw(4 * d, e.dtype, p.ks_f2) : 0;
+  out[3] = p.wd_w8_qkv ? vc_gemm_wd_kpw(d, e.dtype, 1) : 0;
   return VC_OK;
 }
 // Host-only: how a decode pass of `rows` rows would be launched for this model shape and compute dtype (no engine, no GPU).
@@ -1232,6 +1305,19 @@ extern "C" int vc_request_w8_rows(vc_engine* e, int mask) {
   return VC_OK;
 }
 
+// Lets steps of 17..64 rows stream the matrices of `mask` (a subset of vc_request_w8's) as E4M3 pair planes of their 16-channel images
+// (option "w8w"): packed at vc_finalize_weights, + 0.5 x the two images, on an engine that can run wide steps.
+extern "C" int vc_request_w8_wide(vc_engine* e, int mask) {
+  if (!e) return VC_EINVAL;
+  if (e->finalized) return fail(e, VC_ESTATE, "vc_request_w8_wide comes before vc_finalize_weights");
+  if (mask < 0 || (mask & ~5)) return fail(e, VC_EINVAL, "vc_request_w8_wide: %d is not a mask of 1 (FFN-down) and 4 (QKV)", mask);
+  if (!e->w8_req) return fail(e, VC_ESTATE, "vc_request_w8_wide comes after vc_request_w8");
+  if (mask & ~e->w8_req) return fail(e, VC_EINVAL, "vc_request_w8_wide: mask %d is no subset of vc_request_w8's %d", mask, e->w8_req);
+  e->w8w_req = mask;
+  e->w8w = mask;
+  return VC_OK;
+}
+
 // Asks vc_finalize_weights for the E4M3 copy of the K / V cache (option "kv8").  As for vc_request_w8, an fp32 engine meets the request
 // at vc_finalize_weights: VC_EINVAL from there.
 extern "C" int vc_request_kv8(vc_engine* e) {
@@ -1375,6 +1461,15 @@ int pack_layer(vc_engine* e, int l) {
         (rc = pack_planes(e, ly, kind, W13_F2, ly.W28, (long)(d / VC_TH_RES) * (4 * d / 64)))) return rc;
     if ((pack_mask[kind] & W8_BITS[W13_QKV]) && ly.Wqkv8 && vc_gemm_packed_fr1_ng(kind, 3 * d, d, e->dtype, 4) &&
         (rc = pack_planes(e, ly, kind, W13_QKV, ly.Wqkv8, (long)(3 * d / VC_TH_RES) * (d / 64)))) return rc;
+  }
+  // on request (vc_request_w8_wide), for an engine that can run wide steps: the 16-channel images W2 / Wqkv16 as pair planes, where
+  // the wide kernel has a form on them for the K slice it would use (+ 0.5 x the two images)
+  if (e->w8w_req && want_qkv16 && e->dtype == VC_DTYPE_BF16) {
+    const vc_packed_kind& pk8 = vc_packed(VC_PK_W8);
+    if ((e->w8w_req & W8_BITS[W13_F2]) && pk8.wd_ok(4 * d, e->dtype, std::max(1, wd_ksplit(e, d, 4 * d))) &&
+        (rc = pack_pairs(e, ly, W13_F2, ly.W2, (long)(d / 16) * (4 * d / 64)))) return rc;
+    if ((e->w8w_req & W8_BITS[W13_QKV]) && ly.Wqkv16 && pk8.wd_ok(d, e->dtype, 1) &&
+        (rc = pack_pairs(e, ly, W13_QKV, ly.Wqkv16, (long)(3 * d / 16) * (d / 64)))) return rc;
   }
   const size_t cache_bytes = (size_t)e->B_max * e->H * e->S_max * e->hd * e->esz;
   if ((rc = dalloc(e, &ly.kc, cache_bytes))) return rc;
@@ -2282,8 +2377,8 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
     memcpy(host_dst, e->opt_state.c_str(), std::min<size_t>((size_t)nbytes > 0 ? (size_t)nbytes - 1 : 0, e->opt_state.size()));
     return VC_OK;
   }
-  else if (n == "w13_stats" || n == "w8_stats") {      // int32 [layer][FFN-down, QKV][state (0 not applicable, 1 packed, 2 refused), fragments refused]
-    const int kind = n == "w13_stats" ? VC_PK_W13 : VC_PK_W8;      // (w8: all 0 on an engine without vc_request_w8)
+  else if (n == "w13_stats" || n == "w8_stats" || (n == "w8w_stats" && e->w8w_req)) {      // int32 [layer][FFN-down, QKV][state (0 not applicable, 1 packed, 2 refused), fragments (w8w: pairs) refused]
+    const int kind = n == "w13_stats" ? VC_PK_W13 : n == "w8_stats" ? VC_PK_W8 : PK_W8W;      // (w8: all 0 on an engine without vc_request_w8; w8w: only on an engine with vc_request_w8_wide)
     std::vector<int32_t> v;
     for (const Layer& ly : e->layers)
       for (int w = 0; w < 2; ++w) { v.push_back(ly.packed[kind][w].state); v.push_back(ly.packed[kind][w].refused); }

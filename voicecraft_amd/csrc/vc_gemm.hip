@@ -1067,9 +1067,9 @@ int vc_gemm_fr1_ok(int N, int K, int dtype, int nw) {
 }
 const vc_packed_kind& vc_packed(int kind) {
   static const vc_packed_kind kinds[VC_PK_N] = {
-    {VC_W13_GROUP_FRAGS, VC_W13_GROUP_U4, VC_LC_W13, vc_launch_w13_pack, vc_launch_gemm_fr1_w13, nullptr, nullptr, nullptr, nullptr},
+    {VC_W13_GROUP_FRAGS, VC_W13_GROUP_U4, VC_LC_W13, vc_launch_w13_pack, vc_launch_gemm_fr1_w13, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
     {VC_W8_GROUP_FRAGS, VC_W8_GROUP_U4, VC_LC_W8, vc_launch_w8_pack, vc_launch_gemm_fr1_w8, vc_launch_gemm_frp_w8, vc_launch_gemm_qp_w8,
-     vc_gemm_frp_w8_ng, vc_gemm_qp_w8_ng},
+     vc_gemm_frp_w8_ng, vc_gemm_qp_w8_ng, vc_launch_gemm_wd_w8, vc_gemm_wd_w8_ok},
   };
   return kinds[kind];
 }

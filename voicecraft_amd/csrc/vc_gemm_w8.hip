@@ -249,3 +249,198 @@ hipError_t vc_launch_gemm_qp_w8(const GemmArgs& a0, const uint4* planes, const u
   const size_t lds = (size_t)rmax * a0.K * sizeof(bf16_t) + 256 + (size_t)VC_FR_WAVES * rmax * 3 * 4 * sizeof(f32x4) + (size_t)rmax * 2 * sizeof(float);
   return launch_rows_w8(kern, granted[rmax == 8], wa, wa.g.n_tiles / 3, lds, VC_LC_ROWS_GEMM_QP, s);
 }
+
+// ------------------------------------------------------------------ wide steps (17..64 rows) on the code bytes (option "w8w")
+// rows_gemm_wds_k (vc_gemm_wd.hip) reads 16-channel images: W2 and Wqkv16.  Their planes are PAIRS (vc_w8.h): k-tiles 2j, 2j + 1 of a
+// tile = one X chunk's worth of weights = 1 KB of codes, 16 bytes per lane, and two side bytes (channels 0..7, channels 8..15: the two
+// 8 x 64 blocks of the quantiser's grid the pair consists of).
+// Packer: one wave per pair, image = consecutive 1 KB fragments (pair P = fragments 2 P, 2 P + 1).  counts[0] += pairs refused.
+__global__ __launch_bounds__(64) void w8w_pack_k(const uint4* __restrict__ img, uint4* __restrict__ planes,
+                                                  unsigned char* __restrict__ side, unsigned int* __restrict__ counts) {
+  const long P = blockIdx.x;
+  const int u = threadIdx.x;
+  const int half = vc_w8w_half(u);
+  uint32_t w[2][4];
+  int mn = 256, mx = -1;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const uint4 v = img[(P * 2 + h) * 64 + u];
+    w[h][0] = v.x; w[h][1] = v.y; w[h][2] = v.z; w[h][3] = v.w;
+    int a, b;
+    vc_w8_minmax(w[h], &a, &b);
+    mn = a < mn ? a : mn;
+    mx = b > mx ? b : mx;
+  }
+  int shift[2], refused = 0;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {        // the two halves, each over its 32 lanes
+    const int mnq = wave_min_i(half == q ? mn : 256);
+    const int mxq = -wave_min_i(half == q ? -mx : 1);
+    const int top = wave_sum_i(half == q ? (vc_w8_top111(w[0], mxq) | vc_w8_top111(w[1], mxq)) : 0);
+    int ok;
+    shift[q] = vc_w8_shift(mnq, mxq, top, &ok);
+    refused |= ok ? 0 : 1;
+  }
+  uint32_t c[4];
+  const int bad = vc_w8w_encode_lane(w, half ? shift[1] : shift[0], c);
+  refused |= wave_sum_i(bad) > 0 ? 1 : 0;
+  planes[P * VC_W8W_PAIR_U4 + u] = make_uint4(c[0], c[1], c[2], c[3]);
+  if (u < 2) side[P * 2 + u] = (unsigned char)vc_w8_side(u == 0 ? shift[0] : shift[1]);
+  if (u == 0 && refused) atomicAdd(counts, 1u);
+}
+// counts[1] += dwords that do not decode to the image's (the conversion the GEMM uses)
+__global__ __launch_bounds__(64) void w8w_check_k(const uint4* __restrict__ img, const uint4* __restrict__ planes,
+                                                   const unsigned char* __restrict__ side, unsigned int* __restrict__ counts) {
+  const long P = blockIdx.x;
+  const int u = threadIdx.x;
+  const uint4 pc = planes[P * VC_W8W_PAIR_U4 + u];
+  const uint32_t c[4] = {pc.x, pc.y, pc.z, pc.w};
+  uint32_t w[2][4];
+  vc_w8w_decode_lane(c, side[P * 2 + vc_w8w_half(u)], w);
+  int bad = 0;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const uint4 v = img[(P * 2 + h) * 64 + u];
+    bad += (w[h][0] != v.x) + (w[h][1] != v.y) + (w[h][2] != v.z) + (w[h][3] != v.w);
+  }
+  bad = wave_sum_i(bad);
+  if (u == 0 && bad) atomicAdd(counts + 1, (unsigned int)bad);
+}
+hipError_t vc_launch_w8w_pack(const uint4* img, long n_pairs, uint4* planes, unsigned char* side, unsigned int* counts, hipStream_t s) {
+  if (n_pairs <= 0 || n_pairs > 0x7fffffffL) return hipErrorInvalidValue;
+  hipError_t err = hipMemsetAsync(counts, 0, 2 * sizeof(unsigned int), s);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(w8w_pack_k, dim3((unsigned int)n_pairs), dim3(64), 0, s, img, planes, side, counts);
+  hipLaunchKernelGGL(w8w_check_k, dim3((unsigned int)n_pairs), dim3(64), 0, s, img, (const uint4*)planes, (const unsigned char*)side, counts);
+  return hipGetLastError();
+}
+// The packer's text on a host buffer (no device): image16 = n_pairs x 2 KB of a 16-channel bf16 image, planes = n_pairs x 1 KB, side =
+// n_pairs x 2 bytes; *refused_pairs = pairs with a half off the grid (their bytes decode to something else).
+extern "C" int vc_w8w_pack_host(const uint16_t* image16, long n_pairs, uint8_t* planes, uint8_t* side, int32_t* refused_pairs) {
+  if (!image16 || !planes || !side || !refused_pairs || n_pairs < 0) return -1;
+  int32_t nref = 0;
+  for (long P = 0; P < n_pairs; ++P) {
+    uint32_t img[512], codes[256];
+    memcpy(img, image16 + P * 1024, sizeof img);
+    nref += vc_w8w_encode_pair(img, codes, side + P * 2) ? 1 : 0;
+    memcpy(planes + P * VC_W8W_PAIR_BYTES, codes, sizeof codes);
+  }
+  *refused_pairs = nref;
+  return 0;
+}
+
+// The wave's side bytes, as scalars: KPW bytes at byte offset off = tile * KT + ktb of the side stream (two per pair, KT per tile); KPW
+// = 2 is a halfword: the aligned word, shifted down.  Byte 2 c + q = pair c, channels 8 q .. 8 q + 7.
+template <int KPW>
+struct W8wSide {
+  static constexpr int NSW = KPW <= 4 ? 1 : KPW / 4;
+  uint32_t w[NSW];
+  __device__ __forceinline__ void load(const uint32_t* side, long off) {
+#pragma unroll
+    for (int i = 0; i < NSW; ++i) w[i] = side[(off >> 2) + i];
+    if constexpr (KPW == 2) w[0] >>= 8 * (int)(off & 2);
+  }
+  template <int C> __device__ __forceinline__ uint32_t scale(int hi) const {      // hi: the lane holds channels 8..15
+    const uint32_t sw = w[(2 * C) >> 2] >> (8 * ((2 * C) & 3));
+    const uint32_t s0 = vc_w8_scale_bits(sw), s1 = vc_w8_scale_bits(sw >> 8);      // scalar arithmetic; one select per lane
+    return hi ? s1 : s0;
+  }
+};
+// k-tile 2 c + H of a pair from the lane's 16 bytes
+template <int H>
+__device__ __forceinline__ uint4 w8w_frag(const uint4& pw, uint32_t sc) {
+  const uint32_t d0 = H == 0 ? pw.x : pw.z, d1 = H == 0 ? pw.y : pw.w;
+  uint4 w;
+  w.x = vc_w8_cvt(d0, 0, sc);
+  w.y = vc_w8_cvt(d0, 1, sc);
+  w.z = vc_w8_cvt(d1, 0, sc);
+  w.w = vc_w8_cvt(d1, 1, sc);
+  return w;
+}
+
+// The shared body (vc_gemm_wds_body.h) on the pair planes: KPW / 2 pairs per tile and wave, all requested up front (half the registers
+// of the image's fragments), the side bytes on their way with n_active, each fragment rebuilt right before its MFMAs.  grid.z = 1.
+template <int KPW, int RT, int EPI>
+__global__ __launch_bounds__(512) void rows_gemm_wds_w8_k(const W8Args wa) {
+  using WT = bf16_t;
+  constexpr bool WALL = true;
+  static_assert(KPW == 2 || KPW == 4 || KPW == 8, "pairs per wave and tile: 1, 2 or 4");
+  const GemmArgs& a = wa.g;
+#define VC_WDS_EARLY                                                                                                                   \
+  W8wSide<KPW> sb[2];                                                                                                                  \
+  _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                                        \
+    sb[t].load(wa.side, (long)min(nt0 + t, a.n_tiles - 1) * a.KT + (ks * 8 + wv) * KPW);
+#define VC_WDS_WDECL                                                                                                                   \
+  const uint4* pp[2];                                                                                                                  \
+  _Pragma("unroll") for (int t = 0; t < 2; ++t) {                                                                                      \
+    const int ntc = min(nt0 + t, a.n_tiles - 1);                                                                                       \
+    pp[t] = wa.planes + ((long)ntc * (a.KT >> 1) + (ktb >> 1)) * VC_W8W_PAIR_U4 + lane;                                                \
+  }                                                                                                                                    \
+  const int hi8 = lane & 8;                                                                                                            \
+  uint4 pw[2][KPW / 2];
+#define VC_WDS_WALL_LOADS                                                                                                              \
+  _Pragma("unroll") for (int j = 0; j < KPW / 2; ++j)                                                                                  \
+    _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                                      \
+      pw[t][j] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(pp[t] + (size_t)j * VC_W8W_PAIR_U4))); \
+  /* the pins: the side words are on their way with n_active, not behind the `active == 0` exit */                                    \
+  _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                                        \
+    _Pragma("unroll") for (int i = 0; i < W8wSide<KPW>::NSW; ++i) asm volatile("" : "+s"(sb[t].w[i]));
+#define VC_WDS_STEP_LOADS(c_)
+#define VC_WDS_FRAG(t_, c_, h_) w8w_frag<h_>(pw[t_][c_], sb[t_].template scale<c_>(hi8))
+#include "vc_gemm_wds_body.h"
+}
+
+int vc_gemm_wd_w8_ok(int K, int dtype, int ksplit) {
+  if (dtype != VC_DTYPE_BF16) return 0;
+  const int kpw = vc_gemm_wd_kpw(K, dtype, ksplit);
+  return (kpw == 2 || kpw == 4 || kpw == 8) ? 1 : 0;
+}
+
+template <int KPW, int RT, int EPI>
+static hipError_t launch_wds_w8(const W8Args& wa, int ksplit, hipStream_t s) {
+  auto kern = rows_gemm_wds_w8_k<KPW, RT, EPI>;
+  const size_t lds = (size_t)8 * 2 * RT * 64 * sizeof(f32x4) + (size_t)8 * RT * 16 * 128;      // the image kernel's: reduction + X stages
+  {
+    static bool granted[16] = {false};       // per instantiation and device
+    int dev = 0;
+    if (hipError_t ge = hipGetDevice(&dev); ge != hipSuccess) return ge;
+    if (lds >= 64 * 1024 && dev >= 0 && dev < 16 && !granted[dev]) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      granted[dev] = true;
+    }
+  }
+  ++vc_launch_counts[VC_LC_WD];                // the form the image kernel counts in
+  ++vc_launch_counts[VC_LC_W8_WIDE];
+  hipLaunchKernelGGL(kern, dim3((wa.g.n_tiles + 1) / 2, ksplit, 1), dim3(512), lds, s, wa);
+  return hipGetLastError();
+}
+template <int KPW, int RT>
+static hipError_t launch_wds_w8_epi(const W8Args& wa, int epi, int ksplit, hipStream_t s) {
+  switch (epi) {
+    case EPI_QKV16: return launch_wds_w8<KPW, RT, EPI_QKV16>(wa, ksplit, s);
+    case EPI_PART: return launch_wds_w8<KPW, RT, EPI_PART>(wa, ksplit, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+template <int KPW>
+static hipError_t launch_wds_w8_rt(const W8Args& wa, int epi, int ksplit, hipStream_t s) {
+  if (wa.g.n_rows <= 2 * VC_ROWS) return launch_wds_w8_epi<KPW, 2>(wa, epi, ksplit, s);      // row tiles in flight, as vc_launch_gemm_wd
+  return launch_wds_w8_epi<KPW, 4>(wa, epi, ksplit, s);
+}
+// vc_launch_gemm_wd's staged form on the pair planes of a.Wp's 16-channel image (a.n_tiles tiles x a.KT k-tiles, packed whole by
+// vc_launch_w8w_pack): the same arguments, grid and LDS.
+hipError_t vc_launch_gemm_wd_w8(const GemmArgs& a, const uint4* planes, const uint8_t* side, int epi, int ksplit, hipStream_t s) {
+  if (a.n_rows < 1 || a.n_rows > 4 * VC_ROWS || !planes || !side || !a.wd_stage) return hipErrorInvalidValue;
+  if (!vc_gemm_wd_w8_ok(a.K, VC_DTYPE_BF16, ksplit) || a.KT * 32 != a.K || a.n_tiles < 1) return hipErrorInvalidValue;
+  W8Args wa;
+  wa.g = a;
+  wa.planes = planes;
+  wa.side = reinterpret_cast<const uint32_t*>(side);      // n_tiles x KT bytes, KT a multiple of 16: whole aligned words
+  switch (vc_gemm_wd_kpw(a.K, VC_DTYPE_BF16, ksplit)) {
+    case 2: return launch_wds_w8_rt<2>(wa, epi, ksplit, s);
+    case 4: return launch_wds_w8_rt<4>(wa, epi, ksplit, s);
+    case 8: return launch_wds_w8_rt<8>(wa, epi, ksplit, s);
+    default: return hipErrorInvalidValue;
+  }
+}

@@ -34,6 +34,9 @@
 // (9.7 us for 33.5 MB = 3.5 TB/s = 0.43 of the HBM peak; the weight stream alone - X requests compiled out - takes 7.4 us = 0.57.)
 // In process on one engine: 64-row step 1.830 -> 1.668 -> 1.509 ms (-8.8 %, then -9.5 %), 32-row step 1.245 -> 1.087 -> 1.045 ms.
 //
+// The staged form's text lives in vc_gemm_wds_body.h with the weight source as hooks: rows_gemm_wds_k below supplies the image, and
+// rows_gemm_wds_w8_k (vc_gemm_w8.hip, option "w8w") the E4M3 pair planes of the same image - half the weight bytes, the same operands.
+//
 // HBM-bound (weights read once per step): algorithmic bytes per launch = N K sizeof(WT) (+ rows x (K + N) activations), the same
 // figure as the rows-GEMM's.  gfx950 only.
 #include <algorithm>
@@ -147,118 +150,23 @@ __global__ __launch_bounds__(512) void rows_gemm_wd_k(const GemmArgs a) {
 // what it wrote), two chunks of requests in flight ahead of the weights.
 template <typename WT, int KPW, int RT, int EPI>
 __global__ __launch_bounds__(512) void rows_gemm_wds_k(const GemmArgs a) {
-  using T = WTr<WT>;
-  constexpr int NW = 8, NP = 2 * RT;
-  constexpr int NCH = KPW / 2;               // chunks of 2 k-tiles = 128 B per row (32 x 2 x 2 B = 16 x 2 x 4 B)
-  constexpr int NQ = 2 * RT;                 // requests per chunk: 8 rows x 128 B each
   constexpr bool WALL = 2 * KPW <= 16;       // all of a wave's weight fragments fit its registers (bf16: always; exact mode up to 8 k-tiles)
-  static_assert(KPW % 2 == 0 && T::KW * sizeof(WT) == 64, "a chunk is two k-tiles of 64 B per row");
-  static_assert(EPI != EPI_QKV, "the QKV projection of wide steps reads the 16-channel image (EPI_QKV16)");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  f32x4* red = reinterpret_cast<f32x4*>(smem);                          // [NW][NP][64]
-  const int active = *a.n_active;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  char* stage = smem + (size_t)NW * NP * 64 * sizeof(f32x4) + (size_t)wv * (RT * 16 * 128);      // this wave's [RT x 16 rows][128 B]
-  const int ks = blockIdx.y, grp = blockIdx.z;
-  const int nt0 = blockIdx.x * 2;
-  const int n_rows = a.n_rows;
-  const int m = lane & 15, kg = lane >> 4;
-  const int pt = (wv < NP) ? wv / RT : 0, pr = (wv < NP) ? wv % RT : 0;
-  const int n_fin = (nt0 + pt) * 16 + 4 * kg;
-  const int mg_fin = pr * 16 + m;
-  float4 eb;
-  int epos, eseq;
-  epi_preload<WT, EPI>(a, min(mg_fin, n_rows - 1), n_fin, grp, eb, epos, eseq);
-
-  const int ktb = (ks * NW + wv) * KPW;
-  const uint4* wp[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int ntc = min(nt0 + t, a.n_tiles - 1);
-    wp[t] = a.Wp + (long)grp * a.w_group_stride + ((long)ntc * a.KT + ktb) * 64 + lane;
-  }
-  // request q of a chunk: rows 8 q + (lane >> 3), 16-byte slot lane & 7 of the row's 128 B.
-  // (Everything per request is a NAMED scalar, generated by the list macro below: arrays of fragments that are parked in LDS - xa[q] -
-  // are demoted to scratch memory by the compiler, however constant the index; the one-row kernels of vc_gemm.hip hit the same wall.)
-  const int lr = lane >> 3, lc = lane & 7;
-  const char* xbase = reinterpret_cast<const char*>(a.x_in) + ((long)grp * a.x_group_stride + (long)ktb * T::KW) * (long)sizeof(WT) + lc * 16;
-  const long xrs = (long)a.x_ld * (long)sizeof(WT);
-#define VC_WDS_Q(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7)
-#define VC_WDS_DECL(q) const char* xq##q = xbase + (long)min((q) * 8 + lr, n_rows - 1) * xrs; uint4 xa##q, xb##q;
-  VC_WDS_Q(VC_WDS_DECL)
-  char* st_w = stage + lr * 128 + ((lc ^ lr) << 4);                                   // + q * 1024
-  const char* st_r0 = stage + m * 128 + ((kg ^ (m & 7)) << 4);                          // + r * 2048: slot kg (first k-tile of the chunk)
-  const char* st_r1 = stage + m * 128 + (((kg | 4) ^ (m & 7)) << 4);                    // slot 4 + kg (second k-tile)
-
-  f32x4 acc[2][RT];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < RT; ++r) acc[t][r] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // the weight source: the image itself, one non-temporal 1 KB burst per fragment (the body and its hooks: vc_gemm_wds_body.h)
+#define VC_WDS_EARLY
+#define VC_WDS_WDECL                                                                                               \
+  const uint4* wp[2];                                                                                              \
+  _Pragma("unroll") for (int t = 0; t < 2; ++t) {                                                                  \
+    const int ntc = min(nt0 + t, a.n_tiles - 1);                                                                   \
+    wp[t] = a.Wp + (long)grp * a.w_group_stride + ((long)ntc * a.KT + ktb) * 64 + lane;                            \
+  }                                                                                                                \
   uint4 wf[2][WALL ? KPW : 2];
-#define VC_WDS_LA(q) if constexpr ((q) < NQ) xa##q = *reinterpret_cast<const uint4*>(xq##q + coff);
-#define VC_WDS_LB(q) if constexpr ((q) < NQ) xb##q = *reinterpret_cast<const uint4*>(xq##q + coff);
-#define VC_WDS_PA(q) if constexpr ((q) < NQ) *reinterpret_cast<uint4*>(st_w + (q) * 1024) = xa##q;
-#define VC_WDS_PB(q) if constexpr ((q) < NQ) *reinterpret_cast<uint4*>(st_w + (q) * 1024) = xb##q;
 #define VC_WDS_LW(j_, slot_) _Pragma("unroll") for (int t = 0; t < 2; ++t) \
     wf[t][slot_] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wp[t] + (size_t)(j_) * 64)))
-  { constexpr size_t coff = 0; VC_WDS_Q(VC_WDS_LA) }
-  if constexpr (NCH > 1) { constexpr size_t coff = 128; VC_WDS_Q(VC_WDS_LB) }
-  if constexpr (WALL) {
-#pragma unroll
-    for (int j = 0; j < KPW; ++j) VC_WDS_LW(j, j);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  if (active == 0) return;
-  // one chunk: park it (whole lines -> swizzled slots), re-arm its registers with the chunk after next, read the fragments back, multiply
-#define VC_WDS_STEP(S_, c_)                                                                                        \
-  {                                                                                                                \
-    if constexpr (!WALL) { VC_WDS_LW(2 * (c_), 0); VC_WDS_LW(2 * (c_) + 1, 1); }                                   \
-    VC_WDS_Q(VC_WDS_P##S_)                                                                                         \
-    if constexpr ((c_) + 2 < NCH) { constexpr size_t coff = (size_t)((c_) + 2) * 128; VC_WDS_Q(VC_WDS_L##S_) }     \
-    uint4 f0[RT], f1[RT];                                                                                          \
-    _Pragma("unroll") for (int r = 0; r < RT; ++r) {                                                               \
-      f0[r] = *reinterpret_cast<const uint4*>(st_r0 + r * 2048);                                                   \
-      f1[r] = *reinterpret_cast<const uint4*>(st_r1 + r * 2048);                                                   \
-    }                                                                                                              \
-    _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                  \
-      _Pragma("unroll") for (int r = 0; r < RT; ++r)                                                               \
-        acc[t][r] = mfma_frag(wf[t][WALL ? 2 * (c_) : 0], f0[r], acc[t][r], (WT*)nullptr);                         \
-    _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                  \
-      _Pragma("unroll") for (int r = 0; r < RT; ++r)                                                               \
-        acc[t][r] = mfma_frag(wf[t][WALL ? 2 * (c_) + 1 : 1], f1[r], acc[t][r], (WT*)nullptr);                     \
-  }
-  static_assert(NCH <= 8, "chunks per wave");
-  if constexpr (NCH > 0) VC_WDS_STEP(A, 0)
-  if constexpr (NCH > 1) VC_WDS_STEP(B, 1)
-  if constexpr (NCH > 2) VC_WDS_STEP(A, 2)
-  if constexpr (NCH > 3) VC_WDS_STEP(B, 3)
-  if constexpr (NCH > 4) VC_WDS_STEP(A, 4)
-  if constexpr (NCH > 5) VC_WDS_STEP(B, 5)
-  if constexpr (NCH > 6) VC_WDS_STEP(A, 6)
-  if constexpr (NCH > 7) VC_WDS_STEP(B, 7)
-#undef VC_WDS_STEP
+#define VC_WDS_WALL_LOADS _Pragma("unroll") for (int j = 0; j < KPW; ++j) VC_WDS_LW(j, j);
+#define VC_WDS_STEP_LOADS(c_) VC_WDS_LW(2 * (c_), 0); VC_WDS_LW(2 * (c_) + 1, 1);
+#define VC_WDS_FRAG(t_, c_, h_) wf[t_][WALL ? 2 * (c_) + (h_) : (h_)]
+#include "vc_gemm_wds_body.h"
 #undef VC_WDS_LW
-#undef VC_WDS_PA
-#undef VC_WDS_PB
-#undef VC_WDS_LA
-#undef VC_WDS_LB
-#undef VC_WDS_DECL
-#undef VC_WDS_Q
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < RT; ++r) red[(wv * NP + t * RT + r) * 64 + lane] = acc[t][r];
-  __syncthreads();
-  if (wv < NP) {
-    f32x4 s[NW];
-#pragma unroll
-    for (int w = 0; w < NW; ++w) s[w] = red[(w * NP + wv) * 64 + lane];
-    const f32x4 v = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
-    if (mg_fin < n_rows && nt0 + pt < a.n_tiles)
-      gemm_epilogue<WT, EPI>(a, v, mg_fin, n_fin, ks, grp, (int)gridDim.z, eb, epos, eseq);
-  }
 }
 
 template <typename WT, int KPW, int RT, int EPI>

@@ -1,6 +1,7 @@
 // vc_w8.h - "w8": bf16 weights that lie on a block-scaled 8-bit grid, stored as one OCP E4M3 (e4m3fn) byte per value plus one shift
-// byte per fragment.  Shared by the device packer and its check (vc_gemm_w8.hip), the one-row kernels that stream the planes, and the
-// host round-trip program (tools/w8_check.cpp): plain C++, no HIP type in any signature.
+// byte per fragment.  Shared by the device packers and their checks (vc_gemm_w8.hip), the kernels that stream the planes, and the
+// host round-trip programs (tools/w8_check.cpp, tools/w8_wide_check.cpp): plain C++, no HIP type in any signature.  The second half
+// of the file is the same grid for the 16-channel images of wide steps, stored by PAIRS ("w8w").
 //
 // Unit: the 512-value MFMA fragment one wave instruction loads (64 lanes x 8 bf16 = 64 lanes x four dwords; in matrix terms an aligned
 // block of 8 output channels x 64 inputs of the 8-channel-tile images, vc_gemm.hip pack_k).  A fragment is ON THE GRID when one integer
@@ -152,4 +153,77 @@ VC_W8_FN void vc_w8_decode_dwords(uint32_t d0, uint32_t d1, uint32_t scale_bits,
 VC_W8_FN void vc_w8_decode_frag(const vc_w8_lane* in, int f, uint32_t side, uint32_t w[4]) {
   const uint32_t* piece = f < 2 ? in->a : in->b;
   vc_w8_decode_dwords(piece[2 * (f & 1)], piece[2 * (f & 1) + 1], vc_w8_scale_bits(side), w);
+}
+
+// ------------------------------------------------------------------ "w8w": the 16-channel images of wide steps (17..64 rows), by PAIRS
+// The wide kernel (vc_gemm_wd.hip rows_gemm_wds_k) reads images of 16-channel tiles: lane l of fragment (tile nt, k-tile kt) holds
+// channel 16 nt + (l & 15), inputs 32 kt + 8 (l >> 4) .. + 7.  A PAIR is k-tiles 2j, 2j + 1 of one tile: 16 channels x 64 inputs = 1024
+// values, 2 KB of the image (two consecutive fragments).  Its lanes with (l & 8) == 0 hold channels 0..7 x 64 inputs, the others
+// channels 8..15 x 64 inputs: two aligned 8 x 64 blocks, i.e. two fragments of the grid above in another lane order.  Each HALF is held
+// to the rule above (vc_w8_shift, vc_w8_encode_value, the NaN-code exception) with a shift of its own.  Storage of a pair:
+//   1 KB of codes: 16 bytes per lane = its eight codes of k-tile 2j (two dwords), then its eight of k-tile 2j + 1 - one contiguous,
+//     16-byte-per-lane request of the wave;
+//   2 side bytes: shift + 127 of channels 0..7, then of channels 8..15.
+// Pairs follow the image's order (tile major, then k), so a wave's KPW / 2 pairs of a tile are contiguous and so are their side bytes.
+#define VC_W8W_PAIR_BYTES 1024
+#define VC_W8W_PAIR_U4 64
+
+VC_W8_FN int vc_w8w_half(int lane) { return (lane >> 3) & 1; }
+
+// Encodes a lane's share of a pair: w[h] = its four dwords of k-tile 2j + h, `shift` = its half's.  Returns 1 when a value is off the grid.
+VC_W8_FN int vc_w8w_encode_lane(const uint32_t w[2][4], int shift, uint32_t out[4]) {
+  int bad = 0;
+  for (int h = 0; h < 2; ++h) {
+    uint32_t d[2] = {0u, 0u};
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t v = (w[h][j >> 1] >> (16 * (j & 1))) & 0xffffu;
+      d[j >> 2] |= vc_w8_encode_value(v, shift, &bad) << (8 * (j & 3));
+    }
+    out[2 * h] = d[0];
+    out[2 * h + 1] = d[1];
+  }
+  return bad;
+}
+// A lane's 16 code bytes and its half's side byte back to its four dwords of each of the two k-tiles: eight conversions.
+VC_W8_FN void vc_w8w_decode_lane(const uint32_t in[4], uint32_t side, uint32_t w[2][4]) {
+  vc_w8_decode_dwords(in[0], in[1], vc_w8_scale_bits(side), w[0]);
+  vc_w8_decode_dwords(in[2], in[3], vc_w8_scale_bits(side), w[1]);
+}
+
+// One whole pair in plain C++ (the host export vc_w8w_pack_host and tools/w8_wide_check.cpp; the device packer runs the same per-lane
+// text with wave reductions in place of the loops over the lanes).  img = the pair's 2 x 64 x 4 dwords in image order, codes = 64 x 4
+// dwords, side = 2 bytes.  Returns a mask of the halves refused (no shift of the range, or a value off the grid at the shift).
+VC_W8_FN int vc_w8w_encode_pair(const uint32_t* img, uint32_t* codes, uint8_t side[2]) {
+  int mn[2] = {256, 256}, mx[2] = {-1, -1}, top[2] = {0, 0}, shift[2], refused = 0;
+  for (int l = 0; l < 64; ++l)
+    for (int h = 0; h < 2; ++h) {
+      int a, b;
+      vc_w8_minmax(img + (h * 64 + l) * 4, &a, &b);
+      const int half = vc_w8w_half(l);
+      mn[half] = a < mn[half] ? a : mn[half];
+      mx[half] = b > mx[half] ? b : mx[half];
+    }
+  for (int l = 0; l < 64; ++l)
+    for (int h = 0; h < 2; ++h) top[vc_w8w_half(l)] |= vc_w8_top111(img + (h * 64 + l) * 4, mx[vc_w8w_half(l)]);
+  for (int half = 0; half < 2; ++half) {
+    int ok;
+    shift[half] = vc_w8_shift(mn[half], mx[half], top[half], &ok);
+    refused |= ok ? 0 : 1 << half;
+    side[half] = (uint8_t)vc_w8_side(shift[half]);
+  }
+  for (int l = 0; l < 64; ++l) {
+    uint32_t w[2][4];
+    for (int h = 0; h < 2; ++h)
+      for (int q = 0; q < 4; ++q) w[h][q] = img[(h * 64 + l) * 4 + q];
+    if (vc_w8w_encode_lane(w, shift[vc_w8w_half(l)], codes + l * 4)) refused |= 1 << vc_w8w_half(l);
+  }
+  return refused;
+}
+VC_W8_FN void vc_w8w_decode_pair(const uint32_t* codes, const uint8_t side[2], uint32_t* img) {
+  for (int l = 0; l < 64; ++l) {
+    uint32_t w[2][4];
+    vc_w8w_decode_lane(codes + l * 4, side[vc_w8w_half(l)], w);
+    for (int h = 0; h < 2; ++h)
+      for (int q = 0; q < 4; ++q) img[(h * 64 + l) * 4 + q] = w[h][q];
+  }
 }

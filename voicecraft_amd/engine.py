@@ -51,7 +51,7 @@ class VoiceCraftEngine:
 
     def __init__(self, args: Namespace | dict, state_dict: dict[str, torch.Tensor], device="cuda:0",
                  dtype="bf16", max_seqs: int = 8, max_positions: int = 4096, use_graph: bool = True, w8: str | None = None,
-                 kv8: bool | str = False, w8_rows: bool = False):
+                 kv8: bool | str = False, w8_rows: bool = False, w8_wide: bool = False):
         """kv8: False (default: nothing changes) | True | "centred" - decode passes of a bf16 engine read the cached K / V positions older than the pass
         as one E4M3 byte per value times a per-row shift (option `kv8`, csrc/vc_kv8.h, quant.kv8_quantize_rows): half the bytes of the
         launch that grows with the batch, 3 mantissa bits left of a cached value, 1.5 x the K/V memory.  Works with every call and `w8=`.
@@ -65,8 +65,14 @@ class VoiceCraftEngine:
         (w8_stats()) and keeps its bf16 launch.
         w8_rows: False (default: nothing changes) | True, with `w8=` only (ValueError without it) - steps of 2..8 rows stream the same
         bytes too (option `w8r`, mask W8_ROWS_MASK: the FFN down-projection at d = 512 / 1024 / 2048, the QKV projection of layers 1..
-        at d = 2048 up to 6 rows), bit-identical to the image launches; launch_counts()["w8_rows"] counts them."""
+        at d = 2048 up to 6 rows), bit-identical to the image launches; launch_counts()["w8_rows"] counts them.
+        w8_wide: False (default: nothing changes) | True, with `w8=` only (ValueError without it) - on an engine that runs wide steps
+        (max_seqs > 16) the FFN down-projection and the QKV projection of 17..64-row steps stream E4M3 bytes too (option `w8w`, mask
+        W8_WIDE_MASK; pair planes of the 16-channel images, csrc/vc_w8.h: + 0.5 x the two images resident, + 0.47 GB at giga830M),
+        bit-identical to the image launches; launch_counts()["w8_wide"] counts them, w8_stats() says which layers have the planes."""
         self.lib = _lib.load()
+        if w8_wide and w8 is None:
+            raise ValueError('w8_wide=True streams the planes of `w8=`: give w8="quantize" or w8="as_is" too')
         if w8_rows and w8 is None:
             raise ValueError('w8_rows=True streams the planes of `w8=`: give w8="quantize" or w8="as_is" too')
         if isinstance(kv8, str) and kv8 != "centred":
@@ -117,6 +123,9 @@ class VoiceCraftEngine:
             check(self.lib.vc_request_w8(self._h, self.W8_MASK), self._h, "vc_request_w8")
         if w8_rows:
             check(self.lib.vc_request_w8_rows(self._h, self.W8_ROWS_MASK), self._h, "vc_request_w8_rows")
+        self.w8_wide = bool(w8_wide)
+        if w8_wide:
+            check(self.lib.vc_request_w8_wide(self._h, self.W8_WIDE_MASK), self._h, "vc_request_w8_wide")
         self.kv8 = bool(kv8)
         self.kv8_centred = kv8 == "centred"
         if self.kv8_centred:
@@ -712,7 +721,8 @@ class VoiceCraftEngine:
         attn_fast, qkv_p8), q16 = many-row steps (qkv16, wide_heads, wide_gemm, wd_stage), sh = shrink, w13 = the one-row launches that
         stream their weights as exact 13-bit planes (mask: 1 FFN-down, 4 QKV; w13_stats() says which matrices have planes); an engine
         created with `w8=` appends w8 = the launches that stream E4M3 bytes instead (same bits, w8_stats()), one created with `w8_rows=True`
-        w8r = the launches of 2..8-row steps that do (same bits) behind it, one created with `kv8=True`
+        w8r = the launches of 2..8-row steps that do (same bits) behind it, one created with `w8_wide=True` w8w = those of 17..64-row
+        steps (same bits, + 8 = also at row counts the measured table leaves out) behind that, one created with `kv8=True`
         appends kv8 = decode attention on the E4M3 copy of the K/V cache (1) or on the bf16 cache (0), one created with `kv8="centred"`
         kv8c = 1 behind it.
         bench.py turns it into a JSON object (`config.engine_options`)."""
@@ -731,12 +741,13 @@ class VoiceCraftEngine:
 
     LAUNCH_FORMS = ("rows_gemm", "mt2", "mt4", "blk64", "blk128_sbs", "blk128_2x2", "blk64_occ2", "ln_rows", "rows_attn",
                     "tile_attn", "rows_gemm_fr", "big256", "big128", "row_gemm_fr1", "tile_attn64", "rows_gemm_frp", "wd", "rows_gemm_qp", "w13", "w8",
-                    "kv8_attn", "kv8_pack", "kv8c_centre", "kv8c_attn", "kv8c_pack", "w8_rows")
+                    "kv8_attn", "kv8_pack", "kv8c_centre", "kv8c_attn", "kv8c_pack", "w8_rows", "w8_wide")
 
     def launch_counts(self) -> dict:
         """Process-wide census of the kernel FORMS launched so far (vc_common.h VC_LC_*): the parity tests take the
         difference around a call to assert which form a benchmarked shape really runs on.  w13 / w8 / w8_rows count launches on packed
-        weights IN ADDITION to their form's slot: w8 the one-row launches, w8_rows those of 2..8-row steps (rows_gemm_frp / rows_gemm_qp)."""
+        weights IN ADDITION to their form's slot: w8 the one-row launches, w8_rows those of 2..8-row steps (rows_gemm_frp / rows_gemm_qp),
+        w8_wide those of 17..64-row steps (also in wd)."""
         c = self.debug_read("launch_counts", (len(self.LAUNCH_FORMS),), torch.int64)
         return {n: int(c[i]) for i, n in enumerate(self.LAUNCH_FORMS)}
 
@@ -755,15 +766,24 @@ class VoiceCraftEngine:
     W8_MATRICES = ("ffn_down", "qkv")       # mask bits 1 and 4 of option `w8`, the matrices quant.quantize_state_dict_w8 converts
     W8_MASK = 5
     W8_ROWS_MASK = 5                        # option `w8r` of an engine created with w8_rows=True
+    W8_WIDE_MASK = 5                        # option `w8w` of an engine created with w8_wide=True
 
     def w8_stats(self) -> list:
         """w13_stats() for option `w8`: per layer {"ffn_down" | "qkv": {"state": "packed" | "refused" | "not_applicable",
         "refused_fragments": n}}.  A refused matrix holds 512-value fragments off the 8-bit grid; its launches stay where they were.
-        not_applicable: an engine created without `w8=`, or a width without the form (FFN-down below d = 512, QKV below d = 1024)."""
+        not_applicable: an engine created without `w8=`, or a width without the form (FFN-down below d = 512, QKV below d = 1024).
+        An engine created with `w8_wide=True` adds "ffn_down_wide" / "qkv_wide": the pair planes of the 16-channel images that 17..64-row
+        steps stream, {"state": ..., "refused_pairs": n} (not_applicable: max_seqs <= 16, or a K slice without the form)."""
         L = int(self.args.num_decoder_layers)
         v = self.debug_read("w8_stats", (L, 2, 2), torch.int32).tolist()
-        return [{m: {"state": self.W13_STATES[v[l][i][0]], "refused_fragments": v[l][i][1]} for i, m in enumerate(self.W8_MATRICES)}
-                for l in range(L)]
+        out = [{m: {"state": self.W13_STATES[v[l][i][0]], "refused_fragments": v[l][i][1]} for i, m in enumerate(self.W8_MATRICES)}
+               for l in range(L)]
+        if self.w8_wide:
+            w = self.debug_read("w8w_stats", (L, 2, 2), torch.int32).tolist()
+            for l in range(L):
+                for i, m in enumerate(self.W8_MATRICES):
+                    out[l][m + "_wide"] = {"state": self.W13_STATES[w[l][i][0]], "refused_pairs": w[l][i][1]}
+        return out
 
     def debug_read(self, name: str, shape, dtype=torch.float32) -> torch.Tensor:
         out = torch.empty(shape, dtype=dtype)

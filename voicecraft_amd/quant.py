@@ -102,6 +102,19 @@ def quantize_state_dict_w8(args, sd: dict, matrices=("ffn_down", "qkv")) -> dict
     return out
 
 
+# ---- "w8w": the pair planes of the 16-channel images that 17..64-row steps stream (csrc/vc_w8.h) ----------------------------------------
+def w8w_decode(planes: torch.Tensor, side: torch.Tensor) -> torch.Tensor:
+    """The stated layout of a pair, read back: planes uint8 [n_pairs, 1024] - 16 bytes per lane, lane l's eight codes of k-tile 2j then its
+    eight of k-tile 2j + 1 - and side uint8 [n_pairs, 2] - shift + 127 of channels 0..7 (lanes with l & 8 == 0), of channels 8..15 ->
+    fp32 [n_pairs, 2, 64, 8]: k-tile of the pair, lane, value (lane l = channel l & 15 of the tile, inputs 8 (l >> 4) .. + 7 of the
+    k-tile).  A pair is two BLOCK-shaped blocks of the grid above: channels 0..7 x 64 inputs and channels 8..15 x 64 inputs."""
+    n = planes.shape[0]
+    q = planes.contiguous().view(torch.float8_e4m3fn).float().double().reshape(n, 64, 2, 8).permute(0, 2, 1, 3)
+    half = (torch.arange(64) >> 3) & 1
+    shift = side.to(torch.int32)[:, half] - 127                      # [n_pairs, 64]
+    return torch.ldexp(q, shift[:, None, :, None]).float()
+
+
 # ---- "kv8": cached K / V rows on the same grid, the block being one head's row of hd values (csrc/vc_kv8.h) -----------------------------
 def kv8_quantize_rows(x: torch.Tensor):
     """bf16-valued rows [..., hd] -> (codes uint8 [..., hd], shift int8 [...]): value ~ q * 2**shift, q the float8_e4m3fn number the code
