@@ -150,6 +150,14 @@ const char* vc_version(void);
  *                  result bit-identical to the image launch; a refused matrix keeps its image launch for that layer.  "w8" stays the
  *                  one-row launches.  The option text ends in |w8=<mask>|w8r=<mask> on such an engine only (vc_debug_w8r_plan says which
  *                  row counts take the form)
+ *   "w8m"          1 (FFN-down) plus 8, ONLY on an engine that called vc_request_w8_mid (default: the requested mask; VC_EINVAL on any
+ *                  other engine): passes of 9..16 finished rows stream the FFN down-projection from the same planes (rows_gemm_fr_w8_k
+ *                  at d = 512, 1024: X in LDS in one piece; rows_gemm_fr2_w8_k at d = 2048: K in two halves - the image kernels' text,
+ *                  one decoded fragment feeding two consecutive k-tiles), every result bit-identical to the image launch; a refused
+ *                  matrix keeps its image launch for that layer.  Bit 8: also at the row counts the measured win table leaves out (for
+ *                  the A/B tool and the tests; vc_debug_w8m_plan says which row counts take the form).  The option text gains
+ *                  |w8m=<v> behind |w8=<mask> and, if present, |w8r=<mask>, in front of |w8w=<v>, on such an engine only.  Resident
+ *                  memory does not change: nothing more is packed
  *   "w8w"          mask of the same bits plus 8, ONLY on an engine that called vc_request_w8_wide (default: the requested mask; VC_EINVAL
  *                  on any other engine): steps of 17..64 rows stream the FFN down-projection (1) and the QKV projection of every layer
  *                  (4) as E4M3 PAIR planes of their 16-channel images (rows_gemm_wds_w8_k: the staged wide kernel, option "wd_stage" = 1,
@@ -170,7 +178,7 @@ const char* vc_version(void);
  * What an option may change: nothing in the exact fp32 mode's greedy tokens (tests/test_gpu_options.py, test_gpu_one_row.py); in bf16
  * mode the forms that re-order sums or round at another place ("finished_rows", "fr_pair", "att_p16", "hq", "fr_one", "qkv_p8", "attn_fast",
  * "qkv16", "wide_heads", "wide_gemm") move head logits by bf16 rounding (tests allow 0.25 absolute), so top-k SAMPLED tokens can differ between option
- * states; the cache-policy / data-path / host-side options ("nt", "wd_stage", "graph_steps", "shrink", "w13", "w8", "w8r", "w8w") change no value; "kv8" rounds cached K / V to its grid.
+ * states; the cache-policy / data-path / host-side options ("nt", "wd_stage", "graph_steps", "shrink", "w13", "w8", "w8r", "w8m", "w8w") change no value; "kv8" rounds cached K / V to its grid.
  * The non-temporal mask "nt" has no bit for the finished-row producers (rows_gemm_fr_k, rows_gemm_fr2_k, row_gemm_fr1_k) and the
  * wide-decode kernels: they always stream with the hint.  Captured decode graphs are kept per option state and step width, so an
  * in-process A/B (bench.py --ab) pays for capture once per state.  Unknown names / malformed values: VC_EINVAL.
@@ -197,6 +205,11 @@ int vc_request_w8(vc_engine* e, int mask);
  * finished rows stream the requested planes too, option "w8r" above.  `mask`: bits 1 and 4 as above, a subset of vc_request_w8's (anything
  * else: VC_EINVAL).  Nothing more is packed.  An engine without this request has no such option and launches what it launched before. */
 int vc_request_w8_rows(vc_engine* e, int mask);
+/* After vc_request_w8 on the same engine (VC_ESTATE without it) and before vc_finalize_weights (VC_ESTATE after it): passes of 9..16
+ * finished rows stream the FFN-down planes too, option "w8m" above.  `mask`: 1 (FFN-down), a subset of vc_request_w8's (anything else:
+ * VC_EINVAL; bit 4, QKV, is refused with a message: no kernel reads the 8-channel QKV image at these row counts).  Nothing more is
+ * packed and resident memory does not change.  An engine without this request has no such option and launches what it launched before. */
+int vc_request_w8_mid(vc_engine* e, int mask);
 /* After vc_request_w8 on the same engine (VC_ESTATE without it) and before vc_finalize_weights (VC_ESTATE after it): steps of 17..64
  * rows stream the matrices of `mask` as E4M3 pair planes, option "w8w" above.  `mask`: bits 1 and 4 as above, a subset of
  * vc_request_w8's (anything else: VC_EINVAL).  vc_finalize_weights then packs the 16-channel images of those matrices once more, for
@@ -595,6 +608,12 @@ int vc_debug_plan(const vc_model_cfg* cfg, int compute_dtype, int rows, int32_t 
  * rows_gemm_qp_w8_k), out[2] / out[3] their groups per wave (0 where the form is not taken).  VC_EINVAL: a null pointer, rows < 1,
  * a mask with other bits than 1 and 4.  tests/test_w8_rows_cpu.py walks every model width with it. */
 int vc_debug_w8r_plan(const vc_model_cfg* cfg, int mask, int rows, int32_t out[4]);
+/* Host only: what option "w8m" = mask (bits 1 and 8) makes of a bf16 decode pass of `rows` rows at this model shape, the matrix taken
+ * as packed.  out[0] = 1 when the FFN down-projection runs on the E4M3 bytes, out[1] the kernel (1 = rows_gemm_fr_w8_k, X in one piece;
+ * 2 = rows_gemm_fr2_w8_k, K in two halves), out[2] its groups per wave and piece, out[3] = 0; all zeros where the form is not taken
+ * (always up to 8 and from 17 rows).  VC_EINVAL: a null pointer, rows < 1, a mask with other bits.  tests/test_w8_mid_cpu.py walks
+ * every model width. */
+int vc_debug_w8m_plan(const vc_model_cfg* cfg, int mask, int rows, int32_t out[4]);
 /* Host only: what option "w8w" = mask (bits 1, 4 and 8) makes of a bf16 decode pass of `rows` rows at this model shape, every matrix
  * taken as packed.  out[0] / out[1] = 1 when the FFN down-projection / the QKV projection run on the pair planes (rows_gemm_wds_w8_k),
  * out[2] / out[3] the k-tiles per wave of the FFN-down K slice / of the QKV matrix there (0 where the form is not taken).  All zeros

@@ -249,6 +249,15 @@ bool w8w_rows_win(int which, int rows) {
   return rows > VC_ROWS && rows <= VC_MAX_SEQS;
 }
 
+// Option "w8m": the row counts of 9..16 at which the w8 form of the FFN down-projection measured faster than the image over the whole
+// paired range; a count that was not measured follows the nearest measured one.  profiles/w8_mid_ab.log (tools/w8_mid_ab.py: giga830M,
+// 7 interleaved pairs per line, captured decode loop per step, min..max of the pairs) at 9, 12, 16 rows: -5.3 .. -5.2 %, -5.0 .. -4.9 %,
+// -5.2 .. -5.2 %, and -4.8 .. -4.7 % for 16 utterances at the benchmark's shapes with `w8r` and `w8w` on: every measured row count has
+// its whole range below zero, so every row count 9..16 takes the form.
+bool w8m_rows_win(int rows) {
+  return rows > VC_FR_MAX_ROWS && rows <= VC_ROWS;
+}
+
 }  // namespace
 namespace vch __attribute__((visibility("hidden"))) {
 // decode: a decode step (n_active set).  tiled: a prefill pass whose 16-row tiles (1) or 64-row blocks (2) each hold consecutive
@@ -301,6 +310,11 @@ PassPlan plan_pass(const vc_engine* e, int rows, bool decode, int tiled) {
     const vc_packed_kind& pk8 = vc_packed(VC_PK_W8);
     p.frp_w8 = p.frp && (e->w8r & W8_BITS[W13_F2]) && w8r_rows_win(W13_F2, rows) && pk8.frp_ng(rows, d, 4 * d, e->dtype) != 0;
     p.qp_w8 = p.qp && (e->w8r & W8_BITS[W13_QKV]) && w8r_rows_win(W13_QKV, rows) && pk8.qp_ng(rows, 3 * d, d, e->dtype) != 0;
+    // option "w8m": past 8 rows the paired producer stops (vc_gemm_frp_ok) and FFN-down runs on rows_gemm_fr_k / rows_gemm_fr2_k; their
+    // w8 twins where a wave's k-tiles per piece are whole groups (d = 512 / 1024 / 2048).  The site takes it for the layers whose
+    // matrix is packed.
+    p.fr_w8_f2 = !p.frp && rows > VC_FR_MAX_ROWS && rows <= VC_ROWS && (e->w8m & W8_BITS[W13_F2]) && pk8.fr_ng(rows, d, 4 * d, e->dtype) != 0 &&
+                 (w8m_rows_win(rows) || (e->w8m & 8));
   } else {
     p.nsplit = 1;                      // attention one workgroup per (row, head), no split partials
     p.att_x = true;
@@ -529,6 +543,8 @@ int site_ffn_down(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer
     else if (p.frp_w8 && ly.packed[VC_PK_W8][W13_F2].state == 1)        // ... on the E4M3 bytes (a refused matrix keeps its image)
       HIPCHK(e, vc_packed(VC_PK_W8).frp(g, ly.packed[VC_PK_W8][W13_F2].planes, ly.packed[VC_PK_W8][W13_F2].side, s));
     else if (p.frp) HIPCHK(e, vc_launch_gemm_frp(g, e->dtype, s));      // 2..8 rows: two k-tiles per fragment
+    else if (p.fr_w8_f2 && ly.packed[VC_PK_W8][W13_F2].state == 1)      // 9..16 rows on the E4M3 bytes (a refused matrix keeps its image)
+      HIPCHK(e, vc_packed(VC_PK_W8).fr(g, ly.packed[VC_PK_W8][W13_F2].planes, ly.packed[VC_PK_W8][W13_F2].side, s));
     else HIPCHK(e, vc_launch_gemm_fr(g, e->dtype, PRO_PLAIN, s));
     return VC_OK;
   }
@@ -1018,6 +1034,11 @@ int need_w8w(vc_engine* e, const char*, int v0) {
   if (!e->w8w_req) return fail(e, VC_EINVAL, "option 'w8w': this engine was created without vc_request_w8_wide");
   return v0 < 0 || (v0 & ~13) ? fail(e, VC_EINVAL, "option 'w8w': %d is not a mask of 1 (FFN-down), 4 (QKV) and 8 (every row count)", v0) : VC_OK;
 }
+// mask of bit 1 plus bit 8, on an engine that requested the 9..16-row form (vc_request_w8_mid)
+int need_w8m(vc_engine* e, const char*, int v0) {
+  if (!e->w8m_req) return fail(e, VC_EINVAL, "option 'w8m': this engine was created without vc_request_w8_mid");
+  return v0 < 0 || (v0 & ~9) ? fail(e, VC_EINVAL, "option 'w8m': %d is not a mask of 1 (FFN-down) and 8 (every row count)", v0) : VC_OK;
+}
 int need_kv8(vc_engine* e, const char*, int) {
   return e->kv8_req ? VC_OK : fail(e, VC_EINVAL, "option 'kv8': this engine was created without vc_request_kv8");
 }
@@ -1062,6 +1083,7 @@ const OptDesc OPTIONS[] = {
     {"w13", "VC_W13", "w13", {&E::w13, 0, 5}, nullptr, {}, need_mask},
     {"w8", nullptr, "w8", {&E::w8, 0, 5}, nullptr, {}, need_w8, &E::w8_req},      // only an engine that requested the form has the option
     {"w8r", nullptr, "w8r", {&E::w8r, 0, 5}, nullptr, {}, need_w8r, &E::w8r_req},   // likewise (vc_request_w8_rows)
+    {"w8m", nullptr, "w8m", {&E::w8m, 0, 9}, nullptr, {}, need_w8m, &E::w8m_req},   // likewise (vc_request_w8_mid)
     {"w8w", nullptr, "w8w", {&E::w8w, 0, 13}, nullptr, {}, need_w8w, &E::w8w_req},  // likewise (vc_request_w8_wide)
     {"kv8", nullptr, "kv8", {&E::kv8, 0, 1}, nonzero, {}, need_kv8, &E::kv8_req},   // likewise
     {"prefill_rows", "VC_PREFILL_ROWS", nullptr, {&E::prefill_rows_per_pass, VC_ROWS, VC_MAX_ROWS}, whole_tiles},   // 16: decode kernels only
@@ -1135,6 +1157,24 @@ extern "C" int vc_debug_w8r_plan(const vc_model_cfg* c, int mask, int rows, int3
   out[1] = p.qp_w8 ? 1 : 0;
   out[2] = p.frp_w8 ? vc_packed(VC_PK_W8).frp_ng(rows, d, 4 * d, e.dtype) : 0;
   out[3] = p.qp_w8 ? vc_packed(VC_PK_W8).qp_ng(rows, 3 * d, d, e.dtype) : 0;
+  return VC_OK;
+}
+// Host-only: what option "w8m" = mask (bits 1, 8) makes of a bf16 decode pass of `rows` rows at this model shape, the matrix taken as
+// packed (plan_pass itself): out = {form taken, kernel (1 = X in one piece, 2 = K in two halves), groups per wave and piece, 0}.
+extern "C" int vc_debug_w8m_plan(const vc_model_cfg* c, int mask, int rows, int32_t out[4]) {
+  if (!c || !out || rows < 1 || rows > VC_MAX_SEQS || mask < 0 || (mask & ~9) || c->d_model <= 0 || c->nhead <= 0 || c->d_model % c->nhead)
+    return VC_EINVAL;
+  vc_engine e;      // default options, the weight images vc_finalize_weights packs, both requests made
+  e.cfg = *c; e.d = c->d_model; e.H = c->nhead; e.hd = c->d_model / c->nhead; e.P = c->head_hidden; e.dtype = VC_DTYPE_BF16;
+  const int d = e.d;
+  e.has_fr8 = e.has_qkv16 = true;
+  e.has_qkv8 = vc_gemm_fr1_ok(3 * d, d, e.dtype, 4) != 0;
+  e.w8_req = e.w8 = 5; e.w8m_req = 1; e.w8m = mask;
+  const PassPlan p = plan_pass(&e, rows, true, 0);
+  out[0] = p.fr_w8_f2 ? 1 : 0;
+  out[1] = p.fr_w8_f2 ? vc_gemm_fr_form(rows, d, 4 * d, e.dtype, PRO_PLAIN, 1) : 0;
+  out[2] = p.fr_w8_f2 ? vc_packed(VC_PK_W8).fr_ng(rows, d, 4 * d, e.dtype) : 0;
+  out[3] = 0;
   return VC_OK;
 }
 // Host-only: what option "w8w" = mask (bits 1, 4, 8) makes of a bf16 decode pass of `rows` rows at this model shape, every matrix taken
@@ -1315,6 +1355,20 @@ extern "C" int vc_request_w8_wide(vc_engine* e, int mask) {
   if (mask & ~e->w8_req) return fail(e, VC_EINVAL, "vc_request_w8_wide: mask %d is no subset of vc_request_w8's %d", mask, e->w8_req);
   e->w8w_req = mask;
   e->w8w = mask;
+  return VC_OK;
+}
+
+// Lets passes of 9..16 finished rows stream the FFN-down planes vc_request_w8 asked for (option "w8m"): `mask` is bit 1 of that request.
+// Nothing more is packed and resident memory does not change.
+extern "C" int vc_request_w8_mid(vc_engine* e, int mask) {
+  if (!e) return VC_EINVAL;
+  if (e->finalized) return fail(e, VC_ESTATE, "vc_request_w8_mid comes before vc_finalize_weights");
+  if (mask < 0 || (mask & ~5)) return fail(e, VC_EINVAL, "vc_request_w8_mid: %d is not a mask of 1 (FFN-down)", mask);
+  if (!e->w8_req) return fail(e, VC_ESTATE, "vc_request_w8_mid comes after vc_request_w8");
+  if (mask & ~e->w8_req) return fail(e, VC_EINVAL, "vc_request_w8_mid: mask %d is no subset of vc_request_w8's %d", mask, e->w8_req);
+  if (mask & 4) return fail(e, VC_EINVAL, "vc_request_w8_mid: bit 4 (QKV) has no form - no kernel reads Wqkv8 at 9..16 rows; the mask is 1 (FFN-down)");
+  e->w8m_req = mask;
+  e->w8m = mask;
   return VC_OK;
 }
 

@@ -206,6 +206,13 @@ struct vc_engine {
   // and launches what it launched before.
   int w8r_req = 0;
   int w8r = 0;
+  // option "w8m": passes of 9..16 finished rows stream the FFN down-projection (1) from the same planes (rows_gemm_fr_w8_k /
+  // rows_gemm_fr2_w8_k: the image kernels' text, one decoded fragment feeding two k-tiles, results bit-identical), where plan_pass
+  // takes the form; bit 8 = also at row counts the win table (w8m_rows_win) leaves out, for the A/B tool and the tests.  Only on an
+  // engine that asked for it after vc_request_w8 (vc_request_w8_mid: w8m_req, a subset of w8_req; QKV has no consumer of Wqkv8 at
+  // these row counts).  Nothing more is packed; any other engine has no such option and launches what it launched before.
+  int w8m_req = 0;
+  int w8m = 0;
   // option "w8w": steps of 17..64 rows stream the FFN down-projection (1) and the QKV projection (4) as E4M3 pair planes of their
   // 16-channel images W2 / Wqkv16 (rows_gemm_wds_w8_k: the staged wide kernel's text on half the weight bytes, results bit-identical),
   // where plan_pass takes the form; bit 8 = also at row counts the win table (w8w_rows_win) leaves out, for the A/B tool and the
@@ -323,6 +330,7 @@ struct PassPlan {
   bool frp;         // finished rows: the FFN down-projection on rows_gemm_frp_k (option fr_pair)
   bool frp_w8;      // ... on the E4M3 bytes of a layer whose W28 is packed that way (rows_gemm_frp_w8_k, option w8r bit 1)
   bool qp_w8;       // qp on the E4M3 bytes of a layer whose Wqkv8 is packed that way (rows_gemm_qp_w8_k, option w8r bit 4)
+  bool fr_w8_f2;    // 9..16 finished rows: the FFN down-projection on the E4M3 bytes of a layer whose W28 is packed that way (rows_gemm_fr_w8_k / rows_gemm_fr2_w8_k, option w8m bit 1)
   bool qkv16;       // wide and block: the QKV projection on the 16-channel image (option qkv16)
   bool wd;          // wide: the linear layers on rows_gemm_wd_k (option wide_gemm)
   bool wd_w8_f2;    // ... the FFN down-projection on the pair planes of a layer whose W2 is packed that way (rows_gemm_wds_w8_k, option w8w bit 1)

@@ -599,28 +599,11 @@ __global__ __launch_bounds__(256 * NTW) void rows_gemm_k(const GemmArgs a) {
 // Bounded by rows x K x sizeof(WT) <= 128 KB of LDS: 8 rows in bf16, 4 in the exact fp32 mode.
 template <typename WT, int KTW, int PRO, int NS, bool P16 = false>
 __global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_fr_k(const GemmArgs a) {
-  static_assert(!P16 || (PRO == PRO_ATT && sizeof(WT) == 2), "bf16 attention partials: the merging out-projection in bf16 mode");
-  using T = WTr<WT>;
-  constexpr int NW = VC_FR_WAVES, NTHR = 64 * NW, TH = VC_TH_RES, SPT = 4 * TH;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nt = blockIdx.x;
-  const int n_rows = a.n_rows;                    // 2..16 as far as rows x K fits LDS and 16 staging units per thread (host contract)
-  const int K = a.K;
-  const int xs = K * (int)sizeof(WT) + 16;        // LDS row stride (+16: rotate bank slots)
-  char* xl = smem;
-  f32x4* red = reinterpret_cast<f32x4*>(smem + (size_t)a.r_lds * xs);
-  const int active = *a.n_active;
-  const int m = lane & 15, kg = lane >> 4;
-  const bool nvalid = 4 * kg < TH;
-  const int n = nt * TH + (nvalid ? 4 * kg : 0);
-  const int wslot = kg * TH + min(m, TH - 1);
-  // epilogue operands first (a wave's loads return in order): the residual and the bias of the lane's four channels
-  const float4 eres = *reinterpret_cast<const float4*>(a.h_in + (long)((m < n_rows) ? m : 0) * a.d + n);
-  const float4 eb = *reinterpret_cast<const float4*>(a.bias + n);
-  const float cmu = a.row_mu[(m < n_rows) ? m : 0] + a.mu_shift;         // centring constant of the row's copy in the compute dtype (hq_out)
-  const uint4* wbase = a.Wp + ((long)nt * a.KT + wave * KTW) * SPT;      // wave-uniform
+  constexpr int GROUP = 1;
+  constexpr bool CHUNKS = true;
+#define VC_FR_EARLY
+#define VC_FR_WDECL                                                                                                                      \
+  const uint4* wbase = a.Wp + ((long)nt * a.KT + wave * KTW) * SPT;      /* wave-uniform */                                               \
   uint4 wf[KTW];
 #define VC_FR_WEIGHTS(c_)                                                                        \
   {                                                                                              \
@@ -628,172 +611,8 @@ __global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_fr_k(const GemmArg
     _Pragma("unroll") for (int i = 0; i < KTW; ++i)                                              \
       wf[i] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wb_ + i * SPT + wslot))); \
   }
-  if constexpr (PRO == PRO_PLAIN) {
-    // X rows as 16-byte units, flat index = row * upr + unit; <= 16 units per thread (rows x K x sizeof <= 128 KB)
-    const int upr = K * (int)sizeof(WT) / 16;
-    const int total = n_rows * upr;
-    const char* src = reinterpret_cast<const char*>(a.x_in);
-    const long rstride = (long)a.x_ld * (long)sizeof(WT);
-    const int sh = a.x_upr_shift;
-    // (explicit scalars: an indexed array is demoted to scratch memory by the compiler)
-    uint4 x0, x1, x2, x3, x4, x5, x6, x7, x8, x9, x10, x11, x12, x13, x14, x15;
-#define VC_FRX_LOAD(j, dst)                                                                      \
-    {                                                                                            \
-      const int i_ = min((j) * NTHR + tid, total - 1);                                           \
-      const int r_ = (sh >= 0) ? (i_ >> sh) : (i_ / upr);                                        \
-      dst = *reinterpret_cast<const uint4*>(src + (long)r_ * rstride + (long)(i_ - r_ * upr) * 16); \
-    }
-#define VC_FRX_STORE(j, val)                                                                     \
-    {                                                                                            \
-      const int i_ = (j) * NTHR + tid;                                                           \
-      if (i_ < total) {                                                                          \
-        const int r_ = (sh >= 0) ? (i_ >> sh) : (i_ / upr);                                      \
-        *reinterpret_cast<uint4*>(xl + (size_t)r_ * xs + (size_t)(i_ - r_ * upr) * 16) = val;    \
-      }                                                                                          \
-    }
-    VC_FRX_LOAD(0, x0) VC_FRX_LOAD(1, x1) VC_FRX_LOAD(2, x2) VC_FRX_LOAD(3, x3)
-    VC_FRX_LOAD(4, x4) VC_FRX_LOAD(5, x5) VC_FRX_LOAD(6, x6) VC_FRX_LOAD(7, x7)
-    VC_FRX_LOAD(8, x8) VC_FRX_LOAD(9, x9) VC_FRX_LOAD(10, x10) VC_FRX_LOAD(11, x11)
-    VC_FRX_LOAD(12, x12) VC_FRX_LOAD(13, x13) VC_FRX_LOAD(14, x14) VC_FRX_LOAD(15, x15)
-    VC_FR_WEIGHTS(0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (active == 0) return;
-    VC_FRX_STORE(0, x0) VC_FRX_STORE(1, x1) VC_FRX_STORE(2, x2) VC_FRX_STORE(3, x3)
-    VC_FRX_STORE(4, x4) VC_FRX_STORE(5, x5) VC_FRX_STORE(6, x6) VC_FRX_STORE(7, x7)
-    VC_FRX_STORE(8, x8) VC_FRX_STORE(9, x9) VC_FRX_STORE(10, x10) VC_FRX_STORE(11, x11)
-    VC_FRX_STORE(12, x12) VC_FRX_STORE(13, x13) VC_FRX_STORE(14, x14) VC_FRX_STORE(15, x15)
-#undef VC_FRX_LOAD
-#undef VC_FRX_STORE
-  } else if constexpr (P16) {   // PRO_ATT on bf16 partials (round 6): item = (row, EIGHT columns of one head) - one 16-byte load per partial - NI items per thread
-    constexpr int NI = 8 / NS;
-    const int q8 = K >> 3;
-    const int n_items = n_rows * q8;              // <= NI * NTHR (rows x NS <= 16, K <= 2048: host contract)
-    const int qsh = a.att_q4_shift - 1;           // log2(K / 8) when K / 4 is a power of two, else < 0
-    float2 ml[NI][NS];
-    uint4 os[NI][NS];
-    int ir[NI], ic[NI];
-    bool on[NI];
-#pragma unroll
-    for (int ib = 0; ib < NI; ++ib) {
-      const int idx = ib * NTHR + tid;
-      on[ib] = idx < n_items;
-      const int i_ = on[ib] ? idx : 0;
-      ir[ib] = (a.att_q4_shift >= 1) ? (i_ >> qsh) : (i_ / q8);
-      ic[ib] = (i_ - ir[ib] * q8) * 8;
-      const int h_ = ic[ib] >> a.hd_shift, e_ = ic[ib] & (a.hd - 1);
-      const float2* mp = reinterpret_cast<const float2*>(a.att_ml) + (long)(ir[ib] * a.H + h_) * a.nsplit;
-      const uint16_t* op = reinterpret_cast<const uint16_t*>(a.att_o) + ((long)(ir[ib] * a.H + h_) * a.nsplit) * a.hd + e_;
-#pragma unroll
-      for (int sp = 0; sp < NS; ++sp) {
-        const int se = (sp < a.nsplit) ? sp : 0;
-        ml[ib][sp] = mp[se];
-        os[ib][sp] = *reinterpret_cast<const uint4*>(op + (long)se * a.hd);
-      }
-    }
-    VC_FR_WEIGHTS(0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (active == 0) return;
-#pragma unroll
-    for (int ib = 0; ib < NI; ++ib) {
-      float M = -INFINITY;
-#pragma unroll
-      for (int sp = 0; sp < NS; ++sp) {
-        ml[ib][sp].x = (sp < a.nsplit) ? ml[ib][sp].x : -INFINITY;
-        M = fmaxf(M, ml[ib][sp].x);
-      }
-      float L = 0.f;
-      float o[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = 0.f;
-#pragma unroll
-      for (int sp = 0; sp < NS; ++sp) {
-        const float w = (ml[ib][sp].x == -INFINITY) ? 0.f : expf(ml[ib][sp].x - M);
-        L += w * ml[ib][sp].y;
-        const uint4 u = os[ib][sp];
-        o[0] += w * __uint_as_float(u.x << 16); o[1] += w * __uint_as_float(u.x & 0xffff0000u);
-        o[2] += w * __uint_as_float(u.y << 16); o[3] += w * __uint_as_float(u.y & 0xffff0000u);
-        o[4] += w * __uint_as_float(u.z << 16); o[5] += w * __uint_as_float(u.z & 0xffff0000u);
-        o[6] += w * __uint_as_float(u.w << 16); o[7] += w * __uint_as_float(u.w & 0xffff0000u);
-      }
-      const float inv = (L > 0.f) ? 1.0f / L : 0.f;
-      uint4 pk;
-      pk.x = pack_bf16x2(o[0] * inv, o[1] * inv); pk.y = pack_bf16x2(o[2] * inv, o[3] * inv);
-      pk.z = pack_bf16x2(o[4] * inv, o[5] * inv); pk.w = pack_bf16x2(o[6] * inv, o[7] * inv);
-      if (on[ib]) *reinterpret_cast<uint4*>(reinterpret_cast<WT*>(xl + (size_t)ir[ib] * xs) + ic[ib]) = pk;
-    }
-  } else {   // PRO_ATT: item = (row, 4 columns of one head) with a.nsplit <= NS partials of (max, sum, acc[4]); NI items per thread
-    constexpr int NI = 16 / NS;
-    const int q4 = K >> 2;
-    const int n_items = n_rows * q4;              // <= NI * NTHR (rows x NS <= 16, K <= 2048: host contract)
-    const int qsh = a.att_q4_shift;
-    float2 ml[NI][NS];
-    float4 os[NI][NS];
-    int ir[NI], ic[NI];
-    bool on[NI];
-#pragma unroll
-    for (int ib = 0; ib < NI; ++ib) {
-      const int idx = ib * NTHR + tid;
-      on[ib] = idx < n_items;
-      const int i_ = on[ib] ? idx : 0;
-      ir[ib] = (qsh >= 0) ? (i_ >> qsh) : (i_ / q4);
-      ic[ib] = (i_ - ir[ib] * q4) * 4;
-      const int h_ = ic[ib] >> a.hd_shift, e_ = ic[ib] & (a.hd - 1);
-      const float2* mp = reinterpret_cast<const float2*>(a.att_ml) + (long)(ir[ib] * a.H + h_) * a.nsplit;
-      const float* op = a.att_o + ((long)(ir[ib] * a.H + h_) * a.nsplit) * a.hd + e_;
-#pragma unroll
-      for (int sp = 0; sp < NS; ++sp) {
-        const int se = (sp < a.nsplit) ? sp : 0;
-        ml[ib][sp] = mp[se];
-        os[ib][sp] = *reinterpret_cast<const float4*>(op + (long)se * a.hd);
-      }
-    }
-    VC_FR_WEIGHTS(0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (active == 0) return;
-#pragma unroll
-    for (int ib = 0; ib < NI; ++ib) {
-      float M = -INFINITY;
-#pragma unroll
-      for (int sp = 0; sp < NS; ++sp) {
-        ml[ib][sp].x = (sp < a.nsplit) ? ml[ib][sp].x : -INFINITY;
-        M = fmaxf(M, ml[ib][sp].x);
-      }
-      float L = 0.f;
-      f32x4 o = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int sp = 0; sp < NS; ++sp) {
-        const float w = (ml[ib][sp].x == -INFINITY) ? 0.f : expf(ml[ib][sp].x - M);
-        L += w * ml[ib][sp].y;
-        o[0] += w * os[ib][sp].x; o[1] += w * os[ib][sp].y; o[2] += w * os[ib][sp].z; o[3] += w * os[ib][sp].w;
-      }
-      const float inv = (L > 0.f) ? 1.0f / L : 0.f;
-      o[0] *= inv; o[1] *= inv; o[2] *= inv; o[3] *= inv;
-      if (on[ib]) store4(reinterpret_cast<WT*>(xl + (size_t)ir[ib] * xs) + ic[ib], o);
-    }
-  }
-  __syncthreads();
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  const int mrow = (m < a.r_lds) ? m : 0;
-  const char* xrow = xl + (size_t)mrow * xs + (size_t)kg * 16;
-  for (int c = 0; c < a.nchunk; ++c) {
-    const int ktl = (c * NW + wave) * KTW;
-#pragma unroll
-    for (int i = 0; i < KTW; ++i) {
-      const uint4 xf = *reinterpret_cast<const uint4*>(xrow + (size_t)(ktl + i) * 64);
-      acc = mfma_frag(wf[i], xf, acc, (WT*)nullptr);     // (fragment rows 8..15 repeat slot 7: they only reach D rows nobody reads)
-    }
-    if (c + 1 < a.nchunk) VC_FR_WEIGHTS(c + 1);          // exact fp32 mode at d = 2048: the registers hold half of a wave's share
-  }
-#undef VC_FR_WEIGHTS
-  red[wave * 64 + lane] = acc;
-  __syncthreads();
-  if (wave == 0 && m < n_rows && nvalid) {
-#pragma unroll
-    for (int w = 1; w < NW; ++w) acc += red[w * 64 + lane];
-    const f32x4 o = {eres.x + eb.x + acc[0], eres.y + eb.y + acc[1], eres.z + eb.z + acc[2], eres.w + eb.w + acc[3]};
-    store4(a.h_out + (long)m * a.d + n, o);
-    if (a.hq_out) { const f32x4 q = {o[0] - cmu, o[1] - cmu, o[2] - cmu, o[3] - cmu}; store4(reinterpret_cast<WT*>(a.hq_out) + (long)m * a.d + n, q); }
-  }
+#define VC_FR_FRAG(J, w) const uint4 w = wf[g];      /* (fragment rows 8..15 repeat slot 7) */
+#include "vc_gemm_fr_body.h"
 }
 
 // The FFN down-projection of 9..16 finished rows: X (rows x 4d elements) no longer fits the LDS of one workgroup, so K goes
@@ -803,99 +622,18 @@ __global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_fr_k(const GemmArg
 // once every wave has finished reading the first half.  Same sums in the same order as rows_gemm_fr_k.
 template <typename WT, int KTW>
 __global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_fr2_k(const GemmArgs a) {
-  using T = WTr<WT>;
-  constexpr int NW = VC_FR_WAVES, NTHR = 64 * NW, TH = VC_TH_RES, SPT = 4 * TH;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nt = blockIdx.x;
-  const int n_rows = a.n_rows;                    // <= 16 (host contract)
-  const int Kh = a.K >> 1;                        // K elements per half = NW * KTW k-tiles
-  const int xs = Kh * (int)sizeof(WT) + 16;
-  char* xl = smem;
-  f32x4* red = reinterpret_cast<f32x4*>(smem + (size_t)a.r_lds * xs);
-  const int active = *a.n_active;
-  const int m = lane & 15, kg = lane >> 4;
-  const bool nvalid = 4 * kg < TH;
-  const int n = nt * TH + (nvalid ? 4 * kg : 0);
-  const int wslot = kg * TH + min(m, TH - 1);
-  const float4 eres = *reinterpret_cast<const float4*>(a.h_in + (long)((m < n_rows) ? m : 0) * a.d + n);
-  const float4 eb = *reinterpret_cast<const float4*>(a.bias + n);
-  const float cmu = a.row_mu[(m < n_rows) ? m : 0] + a.mu_shift;
-  const uint4* wbase = a.Wp + ((long)nt * a.KT + wave * KTW) * SPT;      // wave-uniform; the second half is NW * KTW k-tiles further
+  constexpr int GROUP = 1;
+#define VC_FR2_EARLY
+#define VC_FR2_WDECL                                                                                                                     \
+  const uint4* wbase = a.Wp + ((long)nt * a.KT + wave * KTW) * SPT;      /* wave-uniform; the second half is NW * KTW k-tiles further */  \
   uint4 wfa[KTW], wfb[KTW];
-  const int upr = Kh * (int)sizeof(WT) / 16;       // 16-byte units per row and half; rows x upr <= 16 x 512 (host contract)
-  const int total = n_rows * upr;
-  const char* src = reinterpret_cast<const char*>(a.x_in);
-  const long rstride = (long)a.x_ld * (long)sizeof(WT);
-  const long hoff = (long)Kh * (long)sizeof(WT);
-  const int sh = a.x_upr_shift;
-  uint4 x0, x1, x2, x3, x4, x5, x6, x7, x8, x9, x10, x11, x12, x13, x14, x15;
-#define VC_FR2_LOAD(j, dst, off_)                                                                \
-    {                                                                                            \
-      const int i_ = min((j) * NTHR + tid, total - 1);                                           \
-      const int r_ = (sh >= 0) ? (i_ >> sh) : (i_ / upr);                                        \
-      dst = *reinterpret_cast<const uint4*>(src + (off_) + (long)r_ * rstride + (long)(i_ - r_ * upr) * 16); \
-    }
-#define VC_FR2_STORE(j, val)                                                                     \
-    {                                                                                            \
-      const int i_ = (j) * NTHR + tid;                                                           \
-      if (i_ < total) {                                                                          \
-        const int r_ = (sh >= 0) ? (i_ >> sh) : (i_ / upr);                                      \
-        *reinterpret_cast<uint4*>(xl + (size_t)r_ * xs + (size_t)(i_ - r_ * upr) * 16) = val;    \
-      }                                                                                          \
-    }
-#define VC_FR2_LOAD_ALL(off_)                                                                    \
-    VC_FR2_LOAD(0, x0, off_) VC_FR2_LOAD(1, x1, off_) VC_FR2_LOAD(2, x2, off_) VC_FR2_LOAD(3, x3, off_)         \
-    VC_FR2_LOAD(4, x4, off_) VC_FR2_LOAD(5, x5, off_) VC_FR2_LOAD(6, x6, off_) VC_FR2_LOAD(7, x7, off_)         \
-    VC_FR2_LOAD(8, x8, off_) VC_FR2_LOAD(9, x9, off_) VC_FR2_LOAD(10, x10, off_) VC_FR2_LOAD(11, x11, off_)     \
-    VC_FR2_LOAD(12, x12, off_) VC_FR2_LOAD(13, x13, off_) VC_FR2_LOAD(14, x14, off_) VC_FR2_LOAD(15, x15, off_)
-#define VC_FR2_STORE_ALL()                                                                       \
-    VC_FR2_STORE(0, x0) VC_FR2_STORE(1, x1) VC_FR2_STORE(2, x2) VC_FR2_STORE(3, x3)               \
-    VC_FR2_STORE(4, x4) VC_FR2_STORE(5, x5) VC_FR2_STORE(6, x6) VC_FR2_STORE(7, x7)               \
-    VC_FR2_STORE(8, x8) VC_FR2_STORE(9, x9) VC_FR2_STORE(10, x10) VC_FR2_STORE(11, x11)           \
-    VC_FR2_STORE(12, x12) VC_FR2_STORE(13, x13) VC_FR2_STORE(14, x14) VC_FR2_STORE(15, x15)
-  VC_FR2_LOAD_ALL(0L)
-#pragma unroll
-  for (int i = 0; i < KTW; ++i)
-    wfa[i] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wbase + i * SPT + wslot)));
-#pragma unroll
-  for (int i = 0; i < KTW; ++i)
+#define VC_FR2_BURST                                                                                                                     \
+  _Pragma("unroll") for (int i = 0; i < KTW; ++i)                                                                                        \
+    wfa[i] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wbase + i * SPT + wslot)));             \
+  _Pragma("unroll") for (int i = 0; i < KTW; ++i)                                                                                        \
     wfb[i] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wbase + (long)(NW * KTW + i) * SPT + wslot)));
-  __builtin_amdgcn_sched_barrier(0);
-  if (active == 0) return;
-  VC_FR2_STORE_ALL()
-  __syncthreads();
-  VC_FR2_LOAD_ALL(hoff)                           // second half of the rows: on its way during the first half's MFMAs
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  const int mrow = (m < a.r_lds) ? m : 0;
-  const char* xrow = xl + (size_t)mrow * xs + (size_t)kg * 16 + (size_t)(wave * KTW) * 64;
-#pragma unroll
-  for (int i = 0; i < KTW; ++i) {
-    const uint4 xf = *reinterpret_cast<const uint4*>(xrow + (size_t)i * 64);
-    acc = mfma_frag(wfa[i], xf, acc, (WT*)nullptr);
-  }
-  __syncthreads();                                // every wave has read the first half
-  VC_FR2_STORE_ALL()
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < KTW; ++i) {
-    const uint4 xf = *reinterpret_cast<const uint4*>(xrow + (size_t)i * 64);
-    acc = mfma_frag(wfb[i], xf, acc, (WT*)nullptr);
-  }
-#undef VC_FR2_LOAD
-#undef VC_FR2_STORE
-#undef VC_FR2_LOAD_ALL
-#undef VC_FR2_STORE_ALL
-  red[wave * 64 + lane] = acc;
-  __syncthreads();
-  if (wave == 0 && m < n_rows && nvalid) {
-#pragma unroll
-    for (int w = 1; w < NW; ++w) acc += red[w * 64 + lane];
-    const f32x4 o = {eres.x + eb.x + acc[0], eres.y + eb.y + acc[1], eres.z + eb.z + acc[2], eres.w + eb.w + acc[3]};
-    store4(a.h_out + (long)m * a.d + n, o);
-    if (a.hq_out) { const f32x4 q = {o[0] - cmu, o[1] - cmu, o[2] - cmu, o[3] - cmu}; store4(reinterpret_cast<WT*>(a.hq_out) + (long)m * a.d + n, q); }
-  }
+#define VC_FR2_FRAG(h_, J, w) const uint4 w = (h_) ? wfb[g] : wfa[g];
+#include "vc_gemm_fr2_body.h"
 }
 template <typename WT, int KTW>
 static hipError_t launch_fr2(const GemmArgs& a, size_t lds, hipStream_t s) {
@@ -1067,9 +805,9 @@ int vc_gemm_fr1_ok(int N, int K, int dtype, int nw) {
 }
 const vc_packed_kind& vc_packed(int kind) {
   static const vc_packed_kind kinds[VC_PK_N] = {
-    {VC_W13_GROUP_FRAGS, VC_W13_GROUP_U4, VC_LC_W13, vc_launch_w13_pack, vc_launch_gemm_fr1_w13, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
+    {VC_W13_GROUP_FRAGS, VC_W13_GROUP_U4, VC_LC_W13, vc_launch_w13_pack, vc_launch_gemm_fr1_w13, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
     {VC_W8_GROUP_FRAGS, VC_W8_GROUP_U4, VC_LC_W8, vc_launch_w8_pack, vc_launch_gemm_fr1_w8, vc_launch_gemm_frp_w8, vc_launch_gemm_qp_w8,
-     vc_gemm_frp_w8_ng, vc_gemm_qp_w8_ng, vc_launch_gemm_wd_w8, vc_gemm_wd_w8_ok},
+     vc_gemm_frp_w8_ng, vc_gemm_qp_w8_ng, vc_launch_gemm_wd_w8, vc_gemm_wd_w8_ok, vc_launch_gemm_fr_w8, vc_gemm_fr_w8_ng},
   };
   return kinds[kind];
 }

@@ -250,6 +250,142 @@ hipError_t vc_launch_gemm_qp_w8(const GemmArgs& a0, const uint4* planes, const u
   return launch_rows_w8(kern, granted[rmax == 8], wa, wa.g.n_tiles / 3, lds, VC_LC_ROWS_GEMM_QP, s);
 }
 
+// ------------------------------------------------------------------ the finished-row producers of 9..16-row passes on the code bytes (option "w8m")
+// rows_gemm_fr_k<.., PRO_PLAIN, ..> and rows_gemm_fr2_k (vc_gemm.hip) read the same image, W28, one 512-byte k-tile per wave instruction:
+// lane (m, kg) takes unit kg * 8 + min(m, 7), operand rows 0..7 are the real channels and nvalid masks the outputs of rows 8..15.  A
+// decoded w8 fragment is a PAIR in the paired kernels' lane mapping (wunit): lanes m < 8 hold k-tile 2 P, lanes m >= 8 k-tile 2 P + 1,
+// unit kg * 8 + (m & 7) each.  One decoded fragment therefore feeds two consecutive MFMAs of the image kernel's loop: k-tile 2 P takes it
+// as it is (lanes m >= 8 carry the other k-tile's weights, which only reach output channels 8..15: nobody reads those), k-tile 2 P + 1
+// takes the same four dwords with each 16-lane row rotated by eight (one DPP move per dword).  The operand lanes that are read are
+// bit-identical to the image's and so is the order of the sums - k-tile after k-tile in one accumulator per wave, the 8-way reduction,
+// residual + bias, the centred copy -: the shared bodies (vc_gemm_fr_body.h, vc_gemm_fr2_body.h) with the burst above in place of the
+// image loads.  A group is eight k-tiles; the wave's share of a piece is NG whole groups (host contract).
+template <int H>
+__device__ __forceinline__ uint4 w8_ktile(const uint4& w) {
+  if constexpr (H == 0) {
+    return w;
+  } else {      // row_ror:8 - lane (m, kg) takes lane (m ^ 8, kg)'s dword; every lane is active here
+    uint4 r;
+    r.x = (uint32_t)__builtin_amdgcn_update_dpp((int)w.x, (int)w.x, 0x128, 0xf, 0xf, false);
+    r.y = (uint32_t)__builtin_amdgcn_update_dpp((int)w.y, (int)w.y, 0x128, 0xf, 0xf, false);
+    r.z = (uint32_t)__builtin_amdgcn_update_dpp((int)w.z, (int)w.z, 0x128, 0xf, 0xf, false);
+    r.w = (uint32_t)__builtin_amdgcn_update_dpp((int)w.w, (int)w.w, 0x128, 0xf, 0xf, false);
+    return r;
+  }
+}
+// X in LDS in one piece (d = 512: NG = 1, d = 1024: NG = 2): group g of wave w = ((nt NW + w) NG + g), the wave's share one chunk.
+template <int NG>
+__global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_fr_w8_k(const W8Args wa) {
+  using WT = bf16_t;
+  constexpr int KTW = 8 * NG, GROUP = 8, PRO = PRO_PLAIN, NS = 1;
+  constexpr bool P16 = false, CHUNKS = false;
+  const GemmArgs& a = wa.g;
+#define VC_FR_EARLY                                                                                                                    \
+  const long G0 = ((long)nt * NW + wave) * NG;                                                                                         \
+  uint32_t sb[NG];                                                                                                                     \
+  _Pragma("unroll") for (int g = 0; g < NG; ++g) sb[g] = wa.side[G0 + g];
+#define VC_FR_WDECL                                                                                                                    \
+  const int wunit = (m >> 3) * SPT + kg * TH + (m & 7);                                                                                \
+  const uint4* gbase = wa.planes + G0 * VC_W8_GROUP_U4;                  /* wave-uniform */                                             \
+  uint4 pa[NG], pb[NG];
+#define VC_FR_WEIGHTS(c_)                                                                                                              \
+  {                                                                                                                                    \
+    _Pragma("unroll") for (int g = 0; g < NG; ++g) {                                                                                   \
+      const uint4* gp = gbase + g * VC_W8_GROUP_U4;                                                                                    \
+      pa[g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + wunit)));                       \
+      pb[g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + 64 + wunit)));                  \
+      __builtin_amdgcn_sched_barrier(0);                                                                                               \
+    }                                                                                                                                  \
+    _Pragma("unroll") for (int g = 0; g < NG; ++g) asm volatile("" : "+s"(sb[g]));                                                     \
+  }
+#define VC_FR_FRAG(J, w) const uint4 w = w8_ktile<(J) & 1>(w8_frag<((J) >> 1)>(pa[g], pb[g], sb[g]));
+#include "vc_gemm_fr_body.h"
+}
+// K in two halves (d = 2048: NG = 2 per half): a tile has 2 NW NG groups, half h of wave w = groups ((2 nt + h) NW + w) NG + g, both
+// halves requested up front in group order.
+template <int NG>
+__global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_fr2_w8_k(const W8Args wa) {
+  using WT = bf16_t;
+  constexpr int KTW = 8 * NG, GROUP = 8;
+  const GemmArgs& a = wa.g;
+#define VC_FR2_EARLY                                                                                                                   \
+  const long G0 = ((long)nt * 2 * NW + wave) * NG;                       /* half h: + h * NW * NG */                                    \
+  uint32_t sb[2][NG];                                                                                                                  \
+  _Pragma("unroll") for (int h = 0; h < 2; ++h)                                                                                        \
+    _Pragma("unroll") for (int g = 0; g < NG; ++g) sb[h][g] = wa.side[G0 + h * (NW * NG) + g];
+#define VC_FR2_WDECL                                                                                                                   \
+  const int wunit = (m >> 3) * SPT + kg * TH + (m & 7);                                                                                \
+  const uint4* gbase = wa.planes + G0 * VC_W8_GROUP_U4;                  /* wave-uniform */                                             \
+  uint4 pa[2][NG], pb[2][NG];
+#define VC_FR2_BURST                                                                                                                   \
+  _Pragma("unroll") for (int h = 0; h < 2; ++h)                                                                                        \
+    _Pragma("unroll") for (int g = 0; g < NG; ++g) {                                                                                   \
+      const uint4* gp = gbase + (h * (NW * NG) + g) * VC_W8_GROUP_U4;                                                                  \
+      pa[h][g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + wunit)));                    \
+      pb[h][g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + 64 + wunit)));               \
+      __builtin_amdgcn_sched_barrier(0);                                                                                               \
+    }                                                                                                                                  \
+  _Pragma("unroll") for (int h = 0; h < 2; ++h)                                                                                        \
+    _Pragma("unroll") for (int g = 0; g < NG; ++g) asm volatile("" : "+s"(sb[h][g]));
+#define VC_FR2_FRAG(h_, J, w) const uint4 w = w8_ktile<(J) & 1>(w8_frag<((J) >> 1)>(pa[h_][g], pb[h_][g], sb[h_][g]));
+#include "vc_gemm_fr2_body.h"
+}
+
+// Groups per wave and piece of the w8 form of the plain finished-row producer for `rows` rows of an [N x K] matrix, 0 = no form: bf16,
+// 9..16 rows, the image launcher's own form (vc_gemm_fr_form: 1 = one piece, 2 = two halves) and a wave's k-tiles per piece whole
+// groups of eight in ONE chunk - one piece: K = 2048 (1 group) and 4096 (2), two halves: K = 8192 (2 per half).  Other widths keep the image.
+int vc_gemm_fr_w8_ng(int rows, int N, int K, int dtype) {
+  if (dtype != VC_DTYPE_BF16 || rows <= VC_FR_MAX_ROWS || rows > VC_ROWS) return 0;
+  const int form = vc_gemm_fr_form(rows, N, K, dtype, PRO_PLAIN, 1);
+  const int KT = K / 32;
+  if (form == 1) {
+    if (KT % (VC_FR_WAVES * 8) != 0) return 0;
+    const int ng = KT / (VC_FR_WAVES * 8);      // (vc_launch_gemm_fr: k-tiles per wave 8 or 16, one chunk)
+    return (ng == 1 || ng == 2) ? ng : 0;
+  }
+  if (form == 2) return KT == 2 * VC_FR_WAVES * 16 ? 2 : 0;
+  return 0;
+}
+// vc_launch_gemm_fr(.., PRO_PLAIN, ..) on the E4M3 bytes of a.Wp's image (W28): the image launch's grid, LDS and arguments
+hipError_t vc_launch_gemm_fr_w8(const GemmArgs& a0, const uint4* planes, const uint32_t* side, hipStream_t s) {
+  const int ng = vc_gemm_fr_w8_ng(a0.n_rows, a0.N, a0.K, VC_DTYPE_BF16);
+  if (!ng || !planes || !side || a0.x_in == nullptr) return hipErrorInvalidValue;
+  const int form = vc_gemm_fr_form(a0.n_rows, a0.N, a0.K, VC_DTYPE_BF16, PRO_PLAIN, 1);
+  W8Args wa;
+  wa.g = a0;
+  wa.g.n_tiles = a0.N / VC_TH_RES;
+  wa.g.KT = a0.K / 32;
+  wa.g.r_lds = a0.n_rows;
+  wa.g.nchunk = form == 2 ? 2 : 1;
+  const int kp = form == 2 ? a0.K / 2 : a0.K;      // elements of X a piece stages per row
+  const int upr = kp * 2 / 16;
+  wa.g.x_upr_shift = -1; wa.g.att_q4_shift = -1;
+  for (int sft = 0; sft < 20; ++sft) if ((1 << sft) == upr) wa.g.x_upr_shift = sft;
+  wa.planes = planes;
+  wa.side = side;
+  static size_t granted[3][16] = {{0}};        // per kernel and device
+  void (*kern)(const W8Args) = nullptr;
+  int slot = 0;
+  if (form == 2 && ng == 2) { kern = rows_gemm_fr2_w8_k<2>; slot = 2; }
+  else if (form == 1 && ng == 2) { kern = rows_gemm_fr_w8_k<2>; slot = 1; }
+  else if (form == 1 && ng == 1) { kern = rows_gemm_fr_w8_k<1>; slot = 0; }
+  else return hipErrorInvalidValue;
+  const size_t lds = vc_gemm_fr_lds_bytes(a0.n_rows, kp, VC_DTYPE_BF16);
+  if (lds > 64 * 1024) {
+    int dev = 0;
+    if (hipError_t ge = hipGetDevice(&dev); ge != hipSuccess) return ge;
+    if (dev >= 0 && dev < 16 && lds > granted[slot][dev]) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      granted[slot][dev] = lds;
+    }
+  }
+  ++vc_launch_counts[VC_LC_ROWS_GEMM_FR];      // the form the image kernel counts in
+  ++vc_launch_counts[VC_LC_W8_MID];
+  hipLaunchKernelGGL(kern, dim3(wa.g.n_tiles), dim3(64 * VC_FR_WAVES), lds, s, wa);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------ wide steps (17..64 rows) on the code bytes (option "w8w")
 // rows_gemm_wds_k (vc_gemm_wd.hip) reads 16-channel images: W2 and Wqkv16.  Their planes are PAIRS (vc_w8.h): k-tiles 2j, 2j + 1 of a
 // tile = one X chunk's worth of weights = 1 KB of codes, 16 bytes per lane, and two side bytes (channels 0..7, channels 8..15: the two

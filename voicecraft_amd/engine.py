@@ -51,7 +51,8 @@ class VoiceCraftEngine:
 
     def __init__(self, args: Namespace | dict, state_dict: dict[str, torch.Tensor], device="cuda:0",
                  dtype="bf16", max_seqs: int = 8, max_positions: int = 4096, use_graph: bool = True, w8: str | None = None,
-                 kv8: bool | str = False, w8_rows: bool = False, w8_wide: bool = False):
+                 kv8: bool | str = False, w8_rows: bool = False, w8_wide: bool = False,
+                 w8_mid: bool = False):
         """kv8: False (default: nothing changes) | True | "centred" - decode passes of a bf16 engine read the cached K / V positions older than the pass
         as one E4M3 byte per value times a per-row shift (option `kv8`, csrc/vc_kv8.h, quant.kv8_quantize_rows): half the bytes of the
         launch that grows with the batch, 3 mantissa bits left of a cached value, 1.5 x the K/V memory.  Works with every call and `w8=`.
@@ -69,8 +70,13 @@ class VoiceCraftEngine:
         w8_wide: False (default: nothing changes) | True, with `w8=` only (ValueError without it) - on an engine that runs wide steps
         (max_seqs > 16) the FFN down-projection and the QKV projection of 17..64-row steps stream E4M3 bytes too (option `w8w`, mask
         W8_WIDE_MASK; pair planes of the 16-channel images, csrc/vc_w8.h: + 0.5 x the two images resident, + 0.47 GB at giga830M),
-        bit-identical to the image launches; launch_counts()["w8_wide"] counts them, w8_stats() says which layers have the planes."""
+        bit-identical to the image launches; launch_counts()["w8_wide"] counts them, w8_stats() says which layers have the planes.
+        w8_mid: False (default: nothing changes) | True, with `w8=` only (ValueError without it) - passes of 9..16 rows stream the FFN
+        down-projection from the same bytes as the one-row step (option `w8m`, mask W8_MID_MASK; d = 512 / 1024 / 2048; nothing more is
+        packed, resident memory does not change), bit-identical to the image launches; launch_counts()["w8_mid"] counts them."""
         self.lib = _lib.load()
+        if w8_mid and w8 is None:
+            raise ValueError('w8_mid=True streams the planes of `w8=`: give w8="quantize" or w8="as_is" too')
         if w8_wide and w8 is None:
             raise ValueError('w8_wide=True streams the planes of `w8=`: give w8="quantize" or w8="as_is" too')
         if w8_rows and w8 is None:
@@ -123,6 +129,8 @@ class VoiceCraftEngine:
             check(self.lib.vc_request_w8(self._h, self.W8_MASK), self._h, "vc_request_w8")
         if w8_rows:
             check(self.lib.vc_request_w8_rows(self._h, self.W8_ROWS_MASK), self._h, "vc_request_w8_rows")
+        if w8_mid:
+            check(self.lib.vc_request_w8_mid(self._h, self.W8_MID_MASK), self._h, "vc_request_w8_mid")
         self.w8_wide = bool(w8_wide)
         if w8_wide:
             check(self.lib.vc_request_w8_wide(self._h, self.W8_WIDE_MASK), self._h, "vc_request_w8_wide")
@@ -721,7 +729,8 @@ class VoiceCraftEngine:
         attn_fast, qkv_p8), q16 = many-row steps (qkv16, wide_heads, wide_gemm, wd_stage), sh = shrink, w13 = the one-row launches that
         stream their weights as exact 13-bit planes (mask: 1 FFN-down, 4 QKV; w13_stats() says which matrices have planes); an engine
         created with `w8=` appends w8 = the launches that stream E4M3 bytes instead (same bits, w8_stats()), one created with `w8_rows=True`
-        w8r = the launches of 2..8-row steps that do (same bits) behind it, one created with `w8_wide=True` w8w = those of 17..64-row
+        w8r = the launches of 2..8-row steps that do (same bits) behind it, one created with `w8_mid=True` w8m = the FFN-down launches of
+        9..16-row passes (1, + 8 = also at row counts the measured table leaves out) behind that, one created with `w8_wide=True` w8w = those of 17..64-row
         steps (same bits, + 8 = also at row counts the measured table leaves out) behind that, one created with `kv8=True`
         appends kv8 = decode attention on the E4M3 copy of the K/V cache (1) or on the bf16 cache (0), one created with `kv8="centred"`
         kv8c = 1 behind it.
@@ -741,13 +750,13 @@ class VoiceCraftEngine:
 
     LAUNCH_FORMS = ("rows_gemm", "mt2", "mt4", "blk64", "blk128_sbs", "blk128_2x2", "blk64_occ2", "ln_rows", "rows_attn",
                     "tile_attn", "rows_gemm_fr", "big256", "big128", "row_gemm_fr1", "tile_attn64", "rows_gemm_frp", "wd", "rows_gemm_qp", "w13", "w8",
-                    "kv8_attn", "kv8_pack", "kv8c_centre", "kv8c_attn", "kv8c_pack", "w8_rows", "w8_wide")
+                    "kv8_attn", "kv8_pack", "kv8c_centre", "kv8c_attn", "kv8c_pack", "w8_rows", "w8_wide", "w8_mid")
 
     def launch_counts(self) -> dict:
         """Process-wide census of the kernel FORMS launched so far (vc_common.h VC_LC_*): the parity tests take the
         difference around a call to assert which form a benchmarked shape really runs on.  w13 / w8 / w8_rows count launches on packed
         weights IN ADDITION to their form's slot: w8 the one-row launches, w8_rows those of 2..8-row steps (rows_gemm_frp / rows_gemm_qp),
-        w8_wide those of 17..64-row steps (also in wd)."""
+        w8_wide those of 17..64-row steps (also in wd), w8_mid the FFN-down launches of 9..16-row passes (also in rows_gemm_fr)."""
         c = self.debug_read("launch_counts", (len(self.LAUNCH_FORMS),), torch.int64)
         return {n: int(c[i]) for i, n in enumerate(self.LAUNCH_FORMS)}
 
@@ -766,6 +775,7 @@ class VoiceCraftEngine:
     W8_MATRICES = ("ffn_down", "qkv")       # mask bits 1 and 4 of option `w8`, the matrices quant.quantize_state_dict_w8 converts
     W8_MASK = 5
     W8_ROWS_MASK = 5                        # option `w8r` of an engine created with w8_rows=True
+    W8_MID_MASK = 1                         # option `w8m` of an engine created with w8_mid=True (FFN-down)
     W8_WIDE_MASK = 5                        # option `w8w` of an engine created with w8_wide=True
 
     def w8_stats(self) -> list:
