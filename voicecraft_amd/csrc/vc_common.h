@@ -507,7 +507,8 @@ int vc_gemm_frp_w8_ng(int rows, int N, int K, int dtype);
 int vc_gemm_qp_w8_ng(int rows, int N, int K, int dtype);
 // pair planes of a 16-channel bf16 image (n_pairs = tiles x k-tiles / 2): counts[0] = pairs refused, counts[1] = dwords that do not decode to the image's
 hipError_t vc_launch_w8w_pack(const uint4* img, long n_pairs, uint4* planes, unsigned char* side, unsigned int* counts, hipStream_t s);
-// rows_gemm_wds_w8_k: vc_launch_gemm_wd's staged form (a.wd_stage = 1, bf16, EPI_PART or EPI_QKV16, one group) on the pair planes of a.Wp's image
+// rows_gemm_wds_w8_k / rows_gemm_wds_w8u_k: vc_launch_gemm_wd's staged form (a.wd_stage = 1, bf16, EPI_PART, EPI_QKV16 or - the FFN
+// up-projection, option "w8u" - EPI_RELU, one group) on the pair planes of a.Wp's image
 hipError_t vc_launch_gemm_wd_w8(const GemmArgs& a, const uint4* planes, const uint8_t* side, int epi, int ksplit, hipStream_t s);
 int vc_gemm_wd_w8_ok(int K, int dtype, int ksplit);         // bf16 and vc_gemm_wd_kpw in {2, 4, 8}
 // rows_gemm_fr_w8_k / rows_gemm_fr2_w8_k: vc_launch_gemm_fr's plain prologue (bf16, 9..16 rows) on the E4M3 bytes of a.Wp's 8-channel image
@@ -518,7 +519,7 @@ extern int vc_blk_dbg_mask;   // vc_gemm.hip: diagnostic mask of the prefill blo
 // vc_debug_read("launch_counts") by the parity tests, which assert that the form a benchmarked shape runs on is the one
 // they compared with the oracle.
 enum { VC_LC_ROWS_GEMM = 0, VC_LC_MT2 = 1, VC_LC_MT4 = 2, VC_LC_BLK64 = 3, VC_LC_BLK128_SBS = 4, VC_LC_BLK128_2X2 = 5,
-       VC_LC_BLK64_OCC2 = 6, VC_LC_LN_ROWS = 7, VC_LC_ROWS_ATTN = 8, VC_LC_TILE_ATTN = 9, VC_LC_ROWS_GEMM_FR = 10, VC_LC_BIG256 = 11, VC_LC_BIG128 = 12, VC_LC_ROW_GEMM_FR1 = 13, VC_LC_TILE_ATTN64 = 14, VC_LC_ROWS_GEMM_FRP = 15, VC_LC_WD = 16, VC_LC_ROWS_GEMM_QP = 17, VC_LC_W13 = 18, VC_LC_W8 = 19, VC_LC_KV8_ATTN = 20, VC_LC_KV8_PACK = 21, VC_LC_KV8C_CENTRE = 22, VC_LC_KV8C_ATTN = 23, VC_LC_KV8C_PACK = 24, VC_LC_W8_ROWS = 25, VC_LC_W8_WIDE = 26, VC_LC_W8_MID = 27, VC_LC_N = 28 };   // VC_LC_W13 / VC_LC_W8: launches on 13-bit planes / on E4M3 bytes (also counted in their form's slot); VC_LC_KV8_ATTN: rows_attn_k launches on the E4M3 K/V cache (also in VC_LC_ROWS_ATTN), VC_LC_KV8_PACK: kv8_pack_k; VC_LC_KV8C_*: the centre kernel, and the centred attention / packer launches (also in their kv8 slots); VC_LC_W8_ROWS: launches of 2..8-row steps on E4M3 bytes (also in VC_LC_ROWS_GEMM_FRP / VC_LC_ROWS_GEMM_QP; VC_LC_W8 stays the one-row launches); VC_LC_W8_WIDE: launches of 17..64-row steps on E4M3 pair planes (also in VC_LC_WD); VC_LC_W8_MID: launches of 9..16-row passes on E4M3 bytes (also in VC_LC_ROWS_GEMM_FR)
+       VC_LC_BLK64_OCC2 = 6, VC_LC_LN_ROWS = 7, VC_LC_ROWS_ATTN = 8, VC_LC_TILE_ATTN = 9, VC_LC_ROWS_GEMM_FR = 10, VC_LC_BIG256 = 11, VC_LC_BIG128 = 12, VC_LC_ROW_GEMM_FR1 = 13, VC_LC_TILE_ATTN64 = 14, VC_LC_ROWS_GEMM_FRP = 15, VC_LC_WD = 16, VC_LC_ROWS_GEMM_QP = 17, VC_LC_W13 = 18, VC_LC_W8 = 19, VC_LC_KV8_ATTN = 20, VC_LC_KV8_PACK = 21, VC_LC_KV8C_CENTRE = 22, VC_LC_KV8C_ATTN = 23, VC_LC_KV8C_PACK = 24, VC_LC_W8_ROWS = 25, VC_LC_W8_WIDE = 26, VC_LC_W8_MID = 27, VC_LC_W8_UP = 28, VC_LC_N = 29 };   // VC_LC_W13 / VC_LC_W8: launches on 13-bit planes / on E4M3 bytes (also counted in their form's slot); VC_LC_KV8_ATTN: rows_attn_k launches on the E4M3 K/V cache (also in VC_LC_ROWS_ATTN), VC_LC_KV8_PACK: kv8_pack_k; VC_LC_KV8C_*: the centre kernel, and the centred attention / packer launches (also in their kv8 slots); VC_LC_W8_ROWS: launches of 2..8-row steps on E4M3 bytes (also in VC_LC_ROWS_GEMM_FRP / VC_LC_ROWS_GEMM_QP; VC_LC_W8 stays the one-row launches); VC_LC_W8_WIDE: launches of 17..64-row steps on E4M3 pair planes (also in VC_LC_WD); VC_LC_W8_MID: launches of 9..16-row passes on E4M3 bytes (also in VC_LC_ROWS_GEMM_FR); VC_LC_W8_UP: FFN-up launches of 17..64-row steps on E4M3 pair planes (also in VC_LC_WD, not in VC_LC_W8_WIDE)
 extern long long vc_launch_counts[VC_LC_N];
 hipError_t vc_launch_ln_rows(const GemmArgs& a, int dtype, hipStream_t s);
 hipError_t vc_launch_attn(const AttnArgs& a, int dtype, int rows_cap, hipStream_t s);

@@ -249,6 +249,16 @@ bool w8w_rows_win(int which, int rows) {
   return rows > VC_ROWS && rows <= VC_MAX_SEQS;
 }
 
+// Option "w8u": the row counts at which the pair-plane form of the FFN up-projection measured faster than the image over the whole
+// paired range; row counts between measured ones follow the nearest measured count of the same RT (17..32, 33..64).
+// profiles/w8_up_ab.log (tools/w8_up_ab.py: giga830M, 7 interleaved pairs per line, captured decode loop per step, min..max of the
+// pairs) at 17, 24, 32 | 33, 48, 64 rows: FFN-up alone -4.4 .. -4.0 % | -3.1 .. -2.6 %, next to `w8w` = 13 -4.9 .. -4.2 % | -3.3 .. -2.9 %,
+// with kv8 -4.2 .. -4.1 % at 32 rows and -2.9 .. -2.8 % at 64: every measured row count has its whole range below zero, so every wide
+// row count takes the form.
+bool w8u_rows_win(int rows) {
+  return rows > VC_ROWS && rows <= VC_MAX_SEQS;
+}
+
 // Option "w8m": the row counts of 9..16 at which the w8 form of the FFN down-projection measured faster than the image over the whole
 // paired range; a count that was not measured follows the nearest measured one.  profiles/w8_mid_ab.log (tools/w8_mid_ab.py: giga830M,
 // 7 interleaved pairs per line, captured decode loop per step, min..max of the pairs) at 9, 12, 16 rows: -5.3 .. -5.2 %, -5.0 .. -4.9 %,
@@ -339,6 +349,8 @@ PassPlan plan_pass(const vc_engine* e, int rows, bool decode, int tiled) {
                    (w8w_rows_win(W13_F2, rows) || (e->w8w & 8));
       p.wd_w8_qkv = staged && (e->w8w & W8_BITS[W13_QKV]) && pk8.wd_ok(d, e->dtype, 1) != 0 &&
                     (w8w_rows_win(W13_QKV, rows) || (e->w8w & 8));
+      // option "w8u": the FFN up-projection likewise (K = d in one slice, as QKV), for the layers whose W1 is packed
+      p.wd_w8_f1 = staged && (e->w8u & W8_BITS[W13_F1]) && pk8.wd_ok(d, e->dtype, 1) != 0 && (w8u_rows_win(rows) || (e->w8u & 8));
     }
   }
   p.heads_wide = p.form == FORM_WIDE && e->wide_heads;
@@ -525,7 +537,10 @@ int site_ffn_up(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& 
     return VC_OK;
   }
   g.x_in = e->xn; g.x_ld = d;
-  if (p.wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_RELU, 1, 1, s));
+  const Layer::Packed& pw = ly.packed[PK_W8W][W13_F1];
+  if (p.wd_w8_f1 && pw.state == 1)         // ... on the pair planes (a refused layer keeps its image)
+    HIPCHK(e, vc_packed(VC_PK_W8).wd(g, pw.planes, reinterpret_cast<const uint8_t*>(pw.side), EPI_RELU, 1, s));
+  else if (p.wd) HIPCHK(e, vc_launch_gemm_wd(g, e->dtype, EPI_RELU, 1, 1, s));
   else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_PLAIN, EPI_RELU, 1, 1, s));
   return VC_OK;
 }
@@ -1039,6 +1054,11 @@ int need_w8m(vc_engine* e, const char*, int v0) {
   if (!e->w8m_req) return fail(e, VC_EINVAL, "option 'w8m': this engine was created without vc_request_w8_mid");
   return v0 < 0 || (v0 & ~9) ? fail(e, VC_EINVAL, "option 'w8m': %d is not a mask of 1 (FFN-down) and 8 (every row count)", v0) : VC_OK;
 }
+// 2 (FFN-up) plus bit 8, on an engine that requested the form (vc_request_w8_up)
+int need_w8u(vc_engine* e, const char*, int v0) {
+  if (!e->w8u_req) return fail(e, VC_EINVAL, "option 'w8u': this engine was created without vc_request_w8_up");
+  return v0 != 0 && v0 != 2 && v0 != 10 ? fail(e, VC_EINVAL, "option 'w8u': %d is not 0, 2 (FFN-up) or 10 (at every row count)", v0) : VC_OK;
+}
 int need_kv8(vc_engine* e, const char*, int) {
   return e->kv8_req ? VC_OK : fail(e, VC_EINVAL, "option 'kv8': this engine was created without vc_request_kv8");
 }
@@ -1085,6 +1105,7 @@ const OptDesc OPTIONS[] = {
     {"w8r", nullptr, "w8r", {&E::w8r, 0, 5}, nullptr, {}, need_w8r, &E::w8r_req},   // likewise (vc_request_w8_rows)
     {"w8m", nullptr, "w8m", {&E::w8m, 0, 9}, nullptr, {}, need_w8m, &E::w8m_req},   // likewise (vc_request_w8_mid)
     {"w8w", nullptr, "w8w", {&E::w8w, 0, 13}, nullptr, {}, need_w8w, &E::w8w_req},  // likewise (vc_request_w8_wide)
+    {"w8u", nullptr, "w8u", {&E::w8u, 0, 10}, nullptr, {}, need_w8u, &E::w8u_req},  // likewise (vc_request_w8_up)
     {"kv8", nullptr, "kv8", {&E::kv8, 0, 1}, nonzero, {}, need_kv8, &E::kv8_req},   // likewise
     {"prefill_rows", "VC_PREFILL_ROWS", nullptr, {&E::prefill_rows_per_pass, VC_ROWS, VC_MAX_ROWS}, whole_tiles},   // 16: decode kernels only
 };
@@ -1193,6 +1214,23 @@ extern "C" int vc_debug_w8w_plan(const vc_model_cfg* c, int mask, int rows, int3
   out[1] = p.wd_w8_qkv ? 1 : 0;
   out[2] = p.wd_w8_f2 ? vc_gemm_wd_kpw(4 * d, e.dtype, p.ks_f2) : 0;
   out[3] = p.wd_w8_qkv ? vc_gemm_wd_kpw(d, e.dtype, 1) : 0;
+  return VC_OK;
+}
+// Host-only: what option "w8u" = mask (0, 2 or 10) makes of a bf16 decode pass of `rows` rows at this model shape, W1 taken as packed
+// (plan_pass itself): out = {FFN-up on the pair planes, k-tiles per wave there}.
+extern "C" int vc_debug_w8u_plan(const vc_model_cfg* c, int mask, int rows, int32_t out[2]) {
+  if (!c || !out || rows < 1 || rows > VC_MAX_SEQS || (mask != 0 && mask != 2 && mask != 10) || c->d_model <= 0 || c->nhead <= 0 ||
+      c->d_model % c->nhead)
+    return VC_EINVAL;
+  vc_engine e;      // default options, the weight images vc_finalize_weights packs for an engine that takes wide steps, both requests made
+  e.cfg = *c; e.d = c->d_model; e.H = c->nhead; e.hd = c->d_model / c->nhead; e.P = c->head_hidden; e.dtype = VC_DTYPE_BF16;
+  const int d = e.d;
+  e.has_fr8 = e.has_qkv16 = true;
+  e.has_qkv8 = vc_gemm_fr1_ok(3 * d, d, e.dtype, 4) != 0;
+  e.w8_req = e.w8 = 5; e.w8u_req = 2; e.w8u = mask;
+  const PassPlan p = plan_pass(&e, rows, true, 0);
+  out[0] = p.wd_w8_f1 ? 1 : 0;
+  out[1] = p.wd_w8_f1 ? vc_gemm_wd_kpw(d, e.dtype, 1) : 0;
   return VC_OK;
 }
 // Host-only: how a decode pass of `rows` rows would be launched for this model shape and compute dtype (no engine, no GPU).
@@ -1355,6 +1393,19 @@ extern "C" int vc_request_w8_wide(vc_engine* e, int mask) {
   if (mask & ~e->w8_req) return fail(e, VC_EINVAL, "vc_request_w8_wide: mask %d is no subset of vc_request_w8's %d", mask, e->w8_req);
   e->w8w_req = mask;
   e->w8w = mask;
+  return VC_OK;
+}
+
+// Lets steps of 17..64 rows stream the FFN up-projection (mask 2, nothing else) as E4M3 pair planes of its 16-channel image W1 (option
+// "w8u"): packed at vc_finalize_weights, + 0.5 x that image, on an engine that can run wide steps.  Needs vc_request_w8 (the bf16 /
+// fp32 check of that request at vc_finalize_weights covers this one) but none of its bits, and not vc_request_w8_wide.
+extern "C" int vc_request_w8_up(vc_engine* e, int mask) {
+  if (!e) return VC_EINVAL;
+  if (e->finalized) return fail(e, VC_ESTATE, "vc_request_w8_up comes before vc_finalize_weights");
+  if (!e->w8_req) return fail(e, VC_ESTATE, "vc_request_w8_up comes after vc_request_w8");
+  if (mask != W8_BITS[W13_F1]) return fail(e, VC_EINVAL, "vc_request_w8_up: %d is not the mask 2 (FFN-up)", mask);
+  e->w8u_req = mask;
+  e->w8u = mask;
   return VC_OK;
 }
 
@@ -1525,6 +1576,9 @@ int pack_layer(vc_engine* e, int l) {
     if ((e->w8w_req & W8_BITS[W13_QKV]) && ly.Wqkv16 && pk8.wd_ok(d, e->dtype, 1) &&
         (rc = pack_pairs(e, ly, W13_QKV, ly.Wqkv16, (long)(3 * d / 16) * (d / 64)))) return rc;
   }
+  // on request (vc_request_w8_up), likewise: the 16-channel image W1 of the FFN up-projection (K = d in one slice): + 0.5 x the image
+  if (e->w8u_req && want_qkv16 && e->dtype == VC_DTYPE_BF16 && vc_packed(VC_PK_W8).wd_ok(d, e->dtype, 1) &&
+      (rc = pack_pairs(e, ly, W13_F1, ly.W1, (long)(4 * d / 16) * (d / 64)))) return rc;
   const size_t cache_bytes = (size_t)e->B_max * e->H * e->S_max * e->hd * e->esz;
   if ((rc = dalloc(e, &ly.kc, cache_bytes))) return rc;
   if ((rc = dalloc(e, &ly.vc, cache_bytes))) return rc;
@@ -2436,6 +2490,13 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
     std::vector<int32_t> v;
     for (const Layer& ly : e->layers)
       for (int w = 0; w < 2; ++w) { v.push_back(ly.packed[kind][w].state); v.push_back(ly.packed[kind][w].refused); }
+    if (nbytes > (int64_t)(v.size() * 4)) return fail(e, VC_ECAP, "debug buffer '%s' holds %lld bytes", n.c_str(), (long long)(v.size() * 4));
+    memcpy(host_dst, v.data(), (size_t)nbytes);
+    return VC_OK;
+  }
+  else if (n == "w8u_stats" && e->w8u_req) {      // int32 [layer][state, pairs refused] of the FFN up-projection's pair planes (engines with vc_request_w8_up)
+    std::vector<int32_t> v;
+    for (const Layer& ly : e->layers) { v.push_back(ly.packed[PK_W8W][W13_F1].state); v.push_back(ly.packed[PK_W8W][W13_F1].refused); }
     if (nbytes > (int64_t)(v.size() * 4)) return fail(e, VC_ECAP, "debug buffer '%s' holds %lld bytes", n.c_str(), (long long)(v.size() * 4));
     memcpy(host_dst, v.data(), (size_t)nbytes);
     return VC_OK;

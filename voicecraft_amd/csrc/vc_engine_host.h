@@ -46,17 +46,18 @@ struct Layer {
   // W28 / Wqkv8 once more in the packed forms of vc_packed (vc_common.h): [VC_PK_W13] exact 13-bit planes (option "w13", vc_w13.h) and, on request
   // (vc_request_w8), [VC_PK_W8] E4M3 bytes with one shift byte per fragment (option "w8", vc_w8.h); second index W13_F2 / W13_QKV.
   // A third slot, [PK_W8W], on request (vc_request_w8_wide): the 16-channel images W2 / Wqkv16 of wide steps as E4M3 PAIR planes
-  // (option "w8w", vc_w8.h: 1 KB of codes + two side bytes per pair; `refused` counts pairs there)
+  // (option "w8w", vc_w8.h: 1 KB of codes + two side bytes per pair; `refused` counts pairs there).  That slot alone has a third
+  // matrix, W13_F1, on request (vc_request_w8_up): the pair planes of the FFN up-projection's image W1 (option "w8u")
   struct Packed {
     uint4* planes = nullptr;
     uint32_t* side = nullptr;      // one byte per fragment
     int state = 0;                 // 0 not applicable (or not packed), 1 packed, 2 refused: the launch stays on the bf16 image
     int refused = 0;               // fragments the packer refused
-  } packed[VC_PK_N + 1][2];
+  } packed[VC_PK_N + 1][3];
 };
 constexpr int PK_W8W = VC_PK_N;
-enum { W13_F2 = 0, W13_QKV = 1 };
-constexpr int W8_BITS[2] = {1, 4};        // the mask bits of options "w13" / "w8" and of vc_request_w8 for W13_F2, W13_QKV
+enum { W13_F2 = 0, W13_QKV = 1, W13_F1 = 2 };
+constexpr int W8_BITS[3] = {1, 4, 2};     // the mask bits of options "w13" / "w8" and of vc_request_w8 for W13_F2, W13_QKV; of "w8u" / vc_request_w8_up for W13_F1
 
 struct Plan { int n_tiles, KT, ksplit, nchunk; };
 
@@ -221,6 +222,14 @@ struct vc_engine {
   // packs nothing more, has no such option and launches what it launched before.
   int w8w_req = 0;
   int w8w = 0;
+  // option "w8u": steps of 17..64 rows stream the FFN up-projection (2) as E4M3 pair planes of its 16-channel image W1
+  // (rows_gemm_wds_w8u_k: the same text with the bias + ReLU epilogue, results bit-identical), where plan_pass takes the form; bit 8 =
+  // also at row counts the win table (w8u_rows_win) leaves out, for the A/B tool and the tests.  Only on an engine that asked for it
+  // after vc_request_w8 (vc_request_w8_up: w8u_req = 2) and that can run wide steps (has_qkv16): + 0.5 x the W1 image resident
+  // (4 d^2 + d^2 / 128 bytes per layer: + 0.27 GB at giga830M).  Independent of "w8w".  Any other engine packs nothing more, has
+  // no such option and launches what it launched before.
+  int w8u_req = 0;
+  int w8u = 0;
   // option "kv8": decode passes read the cached positions older than the pass from an E4M3 copy of the K / V cache (Layer.kc8 / vc8 / sh8,
   // vc_kv8.h: one byte per value, one shift per cached row of a head - half the bytes of the launch that grows with the batch), which
   // one kv8_pack_k launch behind every pass keeps equal to the quantiser of the bf16 rows.  This changes values (3 mantissa bits), so:
@@ -335,6 +344,7 @@ struct PassPlan {
   bool wd;          // wide: the linear layers on rows_gemm_wd_k (option wide_gemm)
   bool wd_w8_f2;    // ... the FFN down-projection on the pair planes of a layer whose W2 is packed that way (rows_gemm_wds_w8_k, option w8w bit 1)
   bool wd_w8_qkv;   // ... the QKV projection on the pair planes of a layer whose Wqkv16 is packed that way (option w8w bit 4)
+  bool wd_w8_f1;    // ... the FFN up-projection on the pair planes of a layer whose W1 is packed that way (rows_gemm_wds_w8u_k, option w8u bit 2)
   int ks_o, ks_f2;  // split-K slabs the out-projection / FFN down-projection leave (slab, wide and block forms)
   bool heads_wide;  // the heads run once over all rows on the wide-step kernels (option wide_heads)
   bool heads_fold;  // heads-1 folds the finished rows itself (no LayerNorm launch)

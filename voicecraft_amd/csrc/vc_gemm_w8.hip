@@ -496,34 +496,17 @@ __device__ __forceinline__ uint4 w8w_frag(const uint4& pw, uint32_t sc) {
 
 // The shared body (vc_gemm_wds_body.h) on the pair planes: KPW / 2 pairs per tile and wave, all requested up front (half the registers
 // of the image's fragments), the side bytes on their way with n_active, each fragment rebuilt right before its MFMAs.  grid.z = 1.
+// The hooks and the body are text in vc_gemm_wds_w8_body.h, shared with the FFN up-projection's kernel below.
 template <int KPW, int RT, int EPI>
 __global__ __launch_bounds__(512) void rows_gemm_wds_w8_k(const W8Args wa) {
-  using WT = bf16_t;
-  constexpr bool WALL = true;
-  static_assert(KPW == 2 || KPW == 4 || KPW == 8, "pairs per wave and tile: 1, 2 or 4");
-  const GemmArgs& a = wa.g;
-#define VC_WDS_EARLY                                                                                                                   \
-  W8wSide<KPW> sb[2];                                                                                                                  \
-  _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                                        \
-    sb[t].load(wa.side, (long)min(nt0 + t, a.n_tiles - 1) * a.KT + (ks * 8 + wv) * KPW);
-#define VC_WDS_WDECL                                                                                                                   \
-  const uint4* pp[2];                                                                                                                  \
-  _Pragma("unroll") for (int t = 0; t < 2; ++t) {                                                                                      \
-    const int ntc = min(nt0 + t, a.n_tiles - 1);                                                                                       \
-    pp[t] = wa.planes + ((long)ntc * (a.KT >> 1) + (ktb >> 1)) * VC_W8W_PAIR_U4 + lane;                                                \
-  }                                                                                                                                    \
-  const int hi8 = lane & 8;                                                                                                            \
-  uint4 pw[2][KPW / 2];
-#define VC_WDS_WALL_LOADS                                                                                                              \
-  _Pragma("unroll") for (int j = 0; j < KPW / 2; ++j)                                                                                  \
-    _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                                      \
-      pw[t][j] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(pp[t] + (size_t)j * VC_W8W_PAIR_U4))); \
-  /* the pins: the side words are on their way with n_active, not behind the `active == 0` exit */                                    \
-  _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                                        \
-    _Pragma("unroll") for (int i = 0; i < W8wSide<KPW>::NSW; ++i) asm volatile("" : "+s"(sb[t].w[i]));
-#define VC_WDS_STEP_LOADS(c_)
-#define VC_WDS_FRAG(t_, c_, h_) w8w_frag<h_>(pw[t_][c_], sb[t_].template scale<c_>(hi8))
-#include "vc_gemm_wds_body.h"
+#include "vc_gemm_wds_w8_body.h"
+}
+// The same text with the FFN up-projection's epilogue (bias, ReLU, bf16 store into the activation rows): option "w8u", the pair planes
+// of W1.  A kernel of its own name: rows_gemm_wds_w8_k stays the twelve FFN-down / QKV instantiations of option "w8w".
+template <int KPW, int RT>
+__global__ __launch_bounds__(512) void rows_gemm_wds_w8u_k(const W8Args wa) {
+  constexpr int EPI = EPI_RELU;
+#include "vc_gemm_wds_w8_body.h"
 }
 
 int vc_gemm_wd_w8_ok(int K, int dtype, int ksplit) {
@@ -534,7 +517,9 @@ int vc_gemm_wd_w8_ok(int K, int dtype, int ksplit) {
 
 template <int KPW, int RT, int EPI>
 static hipError_t launch_wds_w8(const W8Args& wa, int ksplit, hipStream_t s) {
-  auto kern = rows_gemm_wds_w8_k<KPW, RT, EPI>;
+  void (*kern)(const W8Args);
+  if constexpr (EPI == EPI_RELU) kern = rows_gemm_wds_w8u_k<KPW, RT>;
+  else kern = rows_gemm_wds_w8_k<KPW, RT, EPI>;
   const size_t lds = (size_t)8 * 2 * RT * 64 * sizeof(f32x4) + (size_t)8 * RT * 16 * 128;      // the image kernel's: reduction + X stages
   {
     static bool granted[16] = {false};       // per instantiation and device
@@ -547,7 +532,7 @@ static hipError_t launch_wds_w8(const W8Args& wa, int ksplit, hipStream_t s) {
     }
   }
   ++vc_launch_counts[VC_LC_WD];                // the form the image kernel counts in
-  ++vc_launch_counts[VC_LC_W8_WIDE];
+  ++vc_launch_counts[EPI == EPI_RELU ? VC_LC_W8_UP : VC_LC_W8_WIDE];      // FFN-up (option "w8u") has a slot of its own
   hipLaunchKernelGGL(kern, dim3((wa.g.n_tiles + 1) / 2, ksplit, 1), dim3(512), lds, s, wa);
   return hipGetLastError();
 }
@@ -556,6 +541,7 @@ static hipError_t launch_wds_w8_epi(const W8Args& wa, int epi, int ksplit, hipSt
   switch (epi) {
     case EPI_QKV16: return launch_wds_w8<KPW, RT, EPI_QKV16>(wa, ksplit, s);
     case EPI_PART: return launch_wds_w8<KPW, RT, EPI_PART>(wa, ksplit, s);
+    case EPI_RELU: return ksplit == 1 ? launch_wds_w8<KPW, RT, EPI_RELU>(wa, ksplit, s) : hipErrorInvalidValue;
     default: return hipErrorInvalidValue;
   }
 }

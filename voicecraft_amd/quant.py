@@ -10,7 +10,8 @@ one-row steps as one byte per value, with results bit-identical to the bf16 laun
 
 What lands on the grid is the engine's IMAGE, not the stored matrix: bf16(W) for `linear2.weight`; bf16(W * gamma), the fp32 product
 with gamma = norm1.weight rounded to nearest even, for `self_attn.in_proj_weight` (the LayerNorm fold, csrc/vc_gemm.hip).  The folded
-matrix Q is quantised, Q / gamma is returned, and the fold of the result is asserted to reproduce Q element by element."""
+matrix Q is quantised, Q / gamma is returned, and the fold of the result is asserted to reproduce Q element by element.  On request
+(`ffn_up=True`, engine option `w8u`) the FFN up-projection joins them the same way: bf16(linear1.weight * norm2.weight)."""
 from __future__ import annotations
 
 import torch
@@ -18,6 +19,9 @@ import torch
 BLOCK = (8, 64)                 # output channels x inputs of one fragment
 SHIFT_MIN, SHIFT_MAX = -117, 119
 MATRICES = {"ffn_down": ("linear2.weight", None), "qkv": ("self_attn.in_proj_weight", "norm1.weight")}
+# the third matrix, by the keyword `ffn_up=True` only (`matrices` keeps naming the two the one-row planes exist for): the 16-channel
+# image of wide steps, whose pairs are two blocks of the same grid each (w8w_decode below)
+FFN_UP = ("linear1.weight", "norm2.weight")
 
 
 def _blocks(x: torch.Tensor) -> torch.Tensor:
@@ -86,8 +90,9 @@ def quantize_matrix(w: torch.Tensor, gamma: torch.Tensor | None = None) -> torch
     return out
 
 
-def quantize_state_dict_w8(args, sd: dict, matrices=("ffn_down", "qkv")) -> dict:
+def quantize_state_dict_w8(args, sd: dict, matrices=("ffn_down", "qkv"), ffn_up: bool = False) -> dict:
     """A new fp32 state dict whose named matrices (of every decoder layer) lie on the w8 grid; every other tensor is the input's, cloned.
+    ffn_up: also the FFN up-projection, folded with norm2.weight (what an engine created with `w8_up=True` streams at 17..64 rows).
     Idempotent: a second pass changes nothing."""
     unknown = [m for m in matrices if m not in MATRICES]
     assert not unknown, f"unknown matrices {unknown}: {sorted(MATRICES)} exist"
@@ -99,6 +104,9 @@ def quantize_state_dict_w8(args, sd: dict, matrices=("ffn_down", "qkv")) -> dict
             wkey, gkey = MATRICES[m]
             gamma = sd[p + gkey] if gkey else None
             out[p + wkey] = quantize_matrix(sd[p + wkey], gamma).to(torch.float32)
+        if ffn_up:
+            wkey, gkey = FFN_UP
+            out[p + wkey] = quantize_matrix(sd[p + wkey], sd[p + gkey]).to(torch.float32)
     return out
 
 
