@@ -259,6 +259,16 @@ bool w8u_rows_win(int rows) {
   return rows > VC_ROWS && rows <= VC_MAX_SEQS;
 }
 
+// Option "w8ur": the row counts of 2..16 at which the pair-plane form of the FFN up-projection measured faster than the image over the
+// whole paired range; a count that was not measured follows the nearest measured one of the same kernel form (2..4, 5..8, 9..16 rows).
+// profiles/w8_up_rows_ab.log (tools/w8_up_rows_ab.py: giga830M, 7 interleaved pairs per line, captured decode loop per step, min..max of
+// the pairs) at 2, 4 | 5, 8 | 9, 12, 16 rows: -7.9 .. -7.5 % | -5.6 .. -4.9 % | -4.2 .. -3.7 %, and -5.3 % / -3.7 % for 8 / 16 utterances at
+// the benchmark's shapes with `w8r` and `w8m` on: every measured row count has its whole range below zero, so every row count 2..16
+// takes the form.
+bool w8ur_rows_win(int rows) {
+  return rows >= 2 && rows <= VC_ROWS;
+}
+
 // Option "w8m": the row counts of 9..16 at which the w8 form of the FFN down-projection measured faster than the image over the whole
 // paired range; a count that was not measured follows the nearest measured one.  profiles/w8_mid_ab.log (tools/w8_mid_ab.py: giga830M,
 // 7 interleaved pairs per line, captured decode loop per step, min..max of the pairs) at 9, 12, 16 rows: -5.3 .. -5.2 %, -5.0 .. -4.9 %,
@@ -325,6 +335,9 @@ PassPlan plan_pass(const vc_engine* e, int rows, bool decode, int tiled) {
     // matrix is packed.
     p.fr_w8_f2 = !p.frp && rows > VC_FR_MAX_ROWS && rows <= VC_ROWS && (e->w8m & W8_BITS[W13_F2]) && pk8.fr_ng(rows, d, 4 * d, e->dtype) != 0 &&
                  (w8m_rows_win(rows) || (e->w8m & 8));
+    // option "w8ur": the FFN up-projection behind a centred copy on the pair planes of W1, where the launcher has a form for these rows
+    // (K = d in one chunk of 4, 8 or 16 k-tiles per wave: d = 512 / 1024 / 2048).  The site takes it for the layers whose W1 is packed.
+    p.lnq_w8_f1 = p.hq && (e->w8ur & W8_BITS[W13_F1]) && pk8.lnq_ok(rows, 4 * d, d, e->dtype) != 0 && (w8ur_rows_win(rows) || (e->w8ur & 8));
   } else {
     p.nsplit = 1;                      // attention one workgroup per (row, head), no split partials
     p.att_x = true;
@@ -525,7 +538,10 @@ int site_ffn_up(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& 
     g.h_in = r.h_in;
     if (p.hq) {
       g.x_in = e->hqA; g.x_ld = d; g.row_mu = e->row_mu[1]; g.mu_shift = ly.bo_mean; g.row_mu_out = e->row_mu[0];
-      HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNQ, EPI_RELU, 1, 1, s));
+      const Layer::Packed& pw = ly.packed[PK_W8W][W13_F1];
+      if (p.lnq_w8_f1 && pw.state == 1)      // ... on the pair planes (a refused layer keeps its image)
+        HIPCHK(e, vc_packed(VC_PK_W8).lnq(g, pw.planes, reinterpret_cast<const uint8_t*>(pw.side), s));
+      else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNQ, EPI_RELU, 1, 1, s));
     } else {
       HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNW, EPI_RELU, 1, 1, s));
     }
@@ -1059,6 +1075,11 @@ int need_w8u(vc_engine* e, const char*, int v0) {
   if (!e->w8u_req) return fail(e, VC_EINVAL, "option 'w8u': this engine was created without vc_request_w8_up");
   return v0 != 0 && v0 != 2 && v0 != 10 ? fail(e, VC_EINVAL, "option 'w8u': %d is not 0, 2 (FFN-up) or 10 (at every row count)", v0) : VC_OK;
 }
+// likewise, on an engine that requested the 2..16-row form (vc_request_w8_up_rows)
+int need_w8ur(vc_engine* e, const char*, int v0) {
+  if (!e->w8ur_req) return fail(e, VC_EINVAL, "option 'w8ur': this engine was created without vc_request_w8_up_rows");
+  return v0 != 0 && v0 != 2 && v0 != 10 ? fail(e, VC_EINVAL, "option 'w8ur': %d is not 0, 2 (FFN-up) or 10 (at every row count)", v0) : VC_OK;
+}
 int need_kv8(vc_engine* e, const char*, int) {
   return e->kv8_req ? VC_OK : fail(e, VC_EINVAL, "option 'kv8': this engine was created without vc_request_kv8");
 }
@@ -1106,6 +1127,7 @@ const OptDesc OPTIONS[] = {
     {"w8m", nullptr, "w8m", {&E::w8m, 0, 9}, nullptr, {}, need_w8m, &E::w8m_req},   // likewise (vc_request_w8_mid)
     {"w8w", nullptr, "w8w", {&E::w8w, 0, 13}, nullptr, {}, need_w8w, &E::w8w_req},  // likewise (vc_request_w8_wide)
     {"w8u", nullptr, "w8u", {&E::w8u, 0, 10}, nullptr, {}, need_w8u, &E::w8u_req},  // likewise (vc_request_w8_up)
+    {"w8ur", nullptr, "w8ur", {&E::w8ur, 0, 10}, nullptr, {}, need_w8ur, &E::w8ur_req},   // likewise (vc_request_w8_up_rows)
     {"kv8", nullptr, "kv8", {&E::kv8, 0, 1}, nonzero, {}, need_kv8, &E::kv8_req},   // likewise
     {"prefill_rows", "VC_PREFILL_ROWS", nullptr, {&E::prefill_rows_per_pass, VC_ROWS, VC_MAX_ROWS}, whole_tiles},   // 16: decode kernels only
 };
@@ -1231,6 +1253,23 @@ extern "C" int vc_debug_w8u_plan(const vc_model_cfg* c, int mask, int rows, int3
   const PassPlan p = plan_pass(&e, rows, true, 0);
   out[0] = p.wd_w8_f1 ? 1 : 0;
   out[1] = p.wd_w8_f1 ? vc_gemm_wd_kpw(d, e.dtype, 1) : 0;
+  return VC_OK;
+}
+// Host-only: what option "w8ur" = mask (0, 2 or 10) makes of a bf16 decode pass of `rows` rows at this model shape, W1 taken as packed
+// (plan_pass itself): out = {FFN-up of the finished rows on the pair planes, k-tiles per wave there}.
+extern "C" int vc_debug_w8ur_plan(const vc_model_cfg* c, int mask, int rows, int32_t out[2]) {
+  if (!c || !out || rows < 1 || rows > VC_MAX_SEQS || (mask != 0 && mask != 2 && mask != 10) || c->d_model <= 0 || c->nhead <= 0 ||
+      c->d_model % c->nhead)
+    return VC_EINVAL;
+  vc_engine e;      // default options, the weight images vc_finalize_weights packs, both requests made
+  e.cfg = *c; e.d = c->d_model; e.H = c->nhead; e.hd = c->d_model / c->nhead; e.P = c->head_hidden; e.dtype = VC_DTYPE_BF16;
+  const int d = e.d;
+  e.has_fr8 = e.has_qkv16 = true;
+  e.has_qkv8 = vc_gemm_fr1_ok(3 * d, d, e.dtype, 4) != 0;
+  e.w8_req = e.w8 = 5; e.w8ur_req = 2; e.w8ur = mask;
+  const PassPlan p = plan_pass(&e, rows, true, 0);
+  out[0] = p.lnq_w8_f1 ? 1 : 0;
+  out[1] = p.lnq_w8_f1 ? vc_packed(VC_PK_W8).lnq_ok(rows, 4 * d, d, e.dtype) : 0;
   return VC_OK;
 }
 // Host-only: how a decode pass of `rows` rows would be launched for this model shape and compute dtype (no engine, no GPU).
@@ -1409,6 +1448,19 @@ extern "C" int vc_request_w8_up(vc_engine* e, int mask) {
   return VC_OK;
 }
 
+// Lets passes of 2..16 finished rows stream the FFN up-projection (mask 2, nothing else) from the pair planes of W1 (option "w8ur"):
+// the planes option "w8u" streams at 17..64 rows, packed at vc_finalize_weights whatever max_seqs is - once when both are requested.
+// Needs vc_request_w8 (the bf16 / fp32 check of that request at vc_finalize_weights covers this one) but none of its bits.
+extern "C" int vc_request_w8_up_rows(vc_engine* e, int mask) {
+  if (!e) return VC_EINVAL;
+  if (e->finalized) return fail(e, VC_ESTATE, "vc_request_w8_up_rows comes before vc_finalize_weights");
+  if (!e->w8_req) return fail(e, VC_ESTATE, "vc_request_w8_up_rows comes after vc_request_w8");
+  if (mask != W8_BITS[W13_F1]) return fail(e, VC_EINVAL, "vc_request_w8_up_rows: %d is not the mask 2 (FFN-up)", mask);
+  e->w8ur_req = mask;
+  e->w8ur = mask;
+  return VC_OK;
+}
+
 // Lets passes of 9..16 finished rows stream the FFN-down planes vc_request_w8 asked for (option "w8m"): `mask` is bit 1 of that request.
 // Nothing more is packed and resident memory does not change.
 extern "C" int vc_request_w8_mid(vc_engine* e, int mask) {
@@ -1577,7 +1629,10 @@ int pack_layer(vc_engine* e, int l) {
         (rc = pack_pairs(e, ly, W13_QKV, ly.Wqkv16, (long)(3 * d / 16) * (d / 64)))) return rc;
   }
   // on request (vc_request_w8_up), likewise: the 16-channel image W1 of the FFN up-projection (K = d in one slice): + 0.5 x the image
-  if (e->w8u_req && want_qkv16 && e->dtype == VC_DTYPE_BF16 && vc_packed(VC_PK_W8).wd_ok(d, e->dtype, 1) &&
+  // (vc_request_w8_up_rows: the same planes for passes of 2..16 finished rows, whatever max_seqs is - packed once when both ask)
+  const bool up_wide = e->w8u_req && want_qkv16 && vc_packed(VC_PK_W8).wd_ok(d, e->dtype, 1);
+  const bool up_rows = e->w8ur_req && vc_packed(VC_PK_W8).lnq_ok(2, 4 * d, d, e->dtype);
+  if ((up_wide || up_rows) && e->dtype == VC_DTYPE_BF16 &&
       (rc = pack_pairs(e, ly, W13_F1, ly.W1, (long)(4 * d / 16) * (d / 64)))) return rc;
   const size_t cache_bytes = (size_t)e->B_max * e->H * e->S_max * e->hd * e->esz;
   if ((rc = dalloc(e, &ly.kc, cache_bytes))) return rc;
@@ -2494,6 +2549,13 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
     memcpy(host_dst, v.data(), (size_t)nbytes);
     return VC_OK;
   }
+  else if (n == "w8ur_stats" && e->w8ur_req) {    // the same slot (the planes are shared), on engines with vc_request_w8_up_rows
+    std::vector<int32_t> v;
+    for (const Layer& ly : e->layers) { v.push_back(ly.packed[PK_W8W][W13_F1].state); v.push_back(ly.packed[PK_W8W][W13_F1].refused); }
+    if (nbytes > (int64_t)(v.size() * 4)) return fail(e, VC_ECAP, "debug buffer '%s' holds %lld bytes", n.c_str(), (long long)(v.size() * 4));
+    memcpy(host_dst, v.data(), (size_t)nbytes);
+    return VC_OK;
+  }
   else if (n == "w8u_stats" && e->w8u_req) {      // int32 [layer][state, pairs refused] of the FFN up-projection's pair planes (engines with vc_request_w8_up)
     std::vector<int32_t> v;
     for (const Layer& ly : e->layers) { v.push_back(ly.packed[PK_W8W][W13_F1].state); v.push_back(ly.packed[PK_W8W][W13_F1].refused); }
@@ -2502,6 +2564,7 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
     return VC_OK;
   }
   else if (n == "launch_counts") { host_src = vc_launch_counts; avail = VC_LC_N * 8; }     // process-wide census of kernel forms (vc_common.h)
+  else if (n == "launch_counts_more") { host_src = vc_launch_counts + VC_LC_W8_UP_ROWS; avail = (VC_LC_N - VC_LC_W8_UP_ROWS) * 8; }   // the slots from VC_LC_W8_UP_ROWS on
   else if (n == "stream") {         // the open streaming TTS call: {finished rows the host knows of, frames handed out, loop over}
     if (!e->ts) return fail(e, VC_ESTATE, "no streaming TTS call is open (vc_tts_stream_begin)");
     if (nbytes != 3 * 4) return fail(e, VC_ECAP, "debug buffer 'stream' holds 12 bytes");

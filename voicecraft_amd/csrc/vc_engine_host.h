@@ -47,7 +47,7 @@ struct Layer {
   // (vc_request_w8), [VC_PK_W8] E4M3 bytes with one shift byte per fragment (option "w8", vc_w8.h); second index W13_F2 / W13_QKV.
   // A third slot, [PK_W8W], on request (vc_request_w8_wide): the 16-channel images W2 / Wqkv16 of wide steps as E4M3 PAIR planes
   // (option "w8w", vc_w8.h: 1 KB of codes + two side bytes per pair; `refused` counts pairs there).  That slot alone has a third
-  // matrix, W13_F1, on request (vc_request_w8_up): the pair planes of the FFN up-projection's image W1 (option "w8u")
+  // matrix, W13_F1, on request (vc_request_w8_up / vc_request_w8_up_rows): the pair planes of the FFN up-projection's image W1 (options "w8u", "w8ur")
   struct Packed {
     uint4* planes = nullptr;
     uint32_t* side = nullptr;      // one byte per fragment
@@ -57,7 +57,7 @@ struct Layer {
 };
 constexpr int PK_W8W = VC_PK_N;
 enum { W13_F2 = 0, W13_QKV = 1, W13_F1 = 2 };
-constexpr int W8_BITS[3] = {1, 4, 2};     // the mask bits of options "w13" / "w8" and of vc_request_w8 for W13_F2, W13_QKV; of "w8u" / vc_request_w8_up for W13_F1
+constexpr int W8_BITS[3] = {1, 4, 2};     // the mask bits of options "w13" / "w8" and of vc_request_w8 for W13_F2, W13_QKV; of "w8u" / "w8ur" and their requests for W13_F1
 
 struct Plan { int n_tiles, KT, ksplit, nchunk; };
 
@@ -230,6 +230,14 @@ struct vc_engine {
   // no such option and launches what it launched before.
   int w8u_req = 0;
   int w8u = 0;
+  // option "w8ur": passes of 2..16 finished rows stream the FFN up-projection (2) from the SAME pair planes of W1 (rows_gemm_lnq_w8_k: the
+  // text of rows_gemm_k<bf16_t, KTW, PRO_LNQ, EPI_RELU, ..> with the pairs as the weight source, results bit-identical), where plan_pass
+  // takes the form; bit 8 = also at row counts the win table (w8ur_rows_win) leaves out, for the A/B tool and the tests.  Only on an
+  // engine that asked for it after vc_request_w8 (vc_request_w8_up_rows: w8ur_req = 2), whatever its max_seqs: + 0.5 x the W1 image
+  // resident (4 d^2 + d^2 / 128 bytes per layer: + 0.27 GB at giga830M) unless "w8u" holds the planes already.  Any other engine packs
+  // nothing more, has no such option and launches what it launched before.
+  int w8ur_req = 0;
+  int w8ur = 0;
   // option "kv8": decode passes read the cached positions older than the pass from an E4M3 copy of the K / V cache (Layer.kc8 / vc8 / sh8,
   // vc_kv8.h: one byte per value, one shift per cached row of a head - half the bytes of the launch that grows with the batch), which
   // one kv8_pack_k launch behind every pass keeps equal to the quantiser of the bf16 rows.  This changes values (3 mantissa bits), so:
@@ -344,6 +352,7 @@ struct PassPlan {
   bool wd;          // wide: the linear layers on rows_gemm_wd_k (option wide_gemm)
   bool wd_w8_f2;    // ... the FFN down-projection on the pair planes of a layer whose W2 is packed that way (rows_gemm_wds_w8_k, option w8w bit 1)
   bool wd_w8_qkv;   // ... the QKV projection on the pair planes of a layer whose Wqkv16 is packed that way (option w8w bit 4)
+  bool lnq_w8_f1;   // finished rows behind a centred copy: the FFN up-projection on the pair planes of a layer whose W1 is packed that way (rows_gemm_lnq_w8_k, option w8ur bit 2)
   bool wd_w8_f1;    // ... the FFN up-projection on the pair planes of a layer whose W1 is packed that way (rows_gemm_wds_w8u_k, option w8u bit 2)
   int ks_o, ks_f2;  // split-K slabs the out-projection / FFN down-projection leave (slab, wide and block forms)
   bool heads_wide;  // the heads run once over all rows on the wide-step kernels (option wide_heads)

@@ -481,6 +481,12 @@ struct W8wSide {
     const uint32_t s0 = vc_w8_scale_bits(sw), s1 = vc_w8_scale_bits(sw >> 8);      // scalar arithmetic; one select per lane
     return hi ? s1 : s0;
   }
+  // the same for a pair index that an unrolled loop makes a constant (vc_gemm_rows_body.h walks k-tiles, not pairs)
+  __device__ __forceinline__ uint32_t scale_at(int c, int hi) const {
+    const uint32_t sw = w[(2 * c) >> 2] >> (8 * ((2 * c) & 3));
+    const uint32_t s0 = vc_w8_scale_bits(sw), s1 = vc_w8_scale_bits(sw >> 8);
+    return hi ? s1 : s0;
+  }
 };
 // k-tile 2 c + H of a pair from the lane's 16 bytes
 template <int H>
@@ -563,6 +569,101 @@ hipError_t vc_launch_gemm_wd_w8(const GemmArgs& a, const uint4* planes, const ui
     case 2: return launch_wds_w8_rt<2>(wa, epi, ksplit, s);
     case 4: return launch_wds_w8_rt<4>(wa, epi, ksplit, s);
     case 8: return launch_wds_w8_rt<8>(wa, epi, ksplit, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// ------------------------------------------------------------------ the FFN up-projection of 2..16 finished rows on the pair planes (option "w8ur")
+// At these row counts site_ffn_up launches rows_gemm_k<bf16_t, KTW, PRO_LNQ, EPI_RELU, NTW, NT, R2> (vc_gemm.hip) on W1, the 16-channel image
+// whose pair planes option "w8u" streams at 17..64 rows.  There TH = 16, so a lane's fragment slot is its lane number, and wave w of a tile
+// reads k-tiles kt0 + w KTW .. + KTW - 1, 16 bytes per lane each: KTW / 2 whole, contiguous pairs in this very lane order and KTW contiguous
+// side bytes - half the weight bytes, half the fragment registers.  The shared text (vc_gemm_rows_body.h) with the pairs as the weight
+// source: all requests of the wave in place of the image burst (non-temporal, always), the side bytes as scalar loads on their way with
+// n_active, each fragment rebuilt right in front of its MFMA.  X staging, statistics, row_mu_out, LDS layout, MFMA order, reduction and
+// epilogue are the image kernel's text and the operands are bit-identical, so every result is.  K = d in one chunk (host contract).
+__device__ __forceinline__ uint4 w8w_frag_at(const uint4& pw, int h, uint32_t sc) {      // h: a constant once the k-tile loop is unrolled
+  return h ? w8w_frag<1>(pw, sc) : w8w_frag<0>(pw, sc);
+}
+template <int KTW, int NTW, bool R2>
+__global__ __launch_bounds__(256 * NTW) void rows_gemm_lnq_w8_k(const W8Args wa) {
+  using WT = bf16_t;
+  constexpr int PRO = PRO_LNQ, EPI = EPI_RELU, NP = VC_MAX_KSPLIT;
+  static_assert(KTW == 4 || KTW == 8 || KTW == 16, "pairs per wave and tile: 2, 4 or 8");
+  const GemmArgs& a = wa.g;
+  /* the wave's side bytes: scalar operands, first needed long after the burst is out */
+#define VC_ROWS_EARLY                                                                                                                  \
+  W8wSide<KTW> sd8;                                                                                                                    \
+  sd8.load(wa.side, (long)nt * a.KT + kt0 + wave * KTW);
+#define VC_ROWS_WDECL                                                                                                                  \
+  const uint4* pbase = wa.planes + (((long)nt * a.KT + kt0 + wave * KTW) >> 1) * VC_W8W_PAIR_U4 + lane;      /* wave-uniform + lane */  \
+  const int hi8 = lane & 8;                                                                                                            \
+  uint4 pw[KTW / 2];
+#define VC_ROWS_BURST                                                                                                                  \
+  _Pragma("unroll") for (int j = 0; j < KTW / 2; ++j)                                                                                  \
+    pw[j] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(pbase + (size_t)j * VC_W8W_PAIR_U4))); \
+  /* the pins: the side words are on their way with n_active, not behind the `active == 0` exit */                                    \
+  _Pragma("unroll") for (int i = 0; i < W8wSide<KTW>::NSW; ++i) asm volatile("" : "+s"(sd8.w[i]));
+#define VC_ROWS_FRAG(i_) uint4 wfi = w8w_frag_at(pw[(i_) >> 1], (i_) & 1, sd8.scale_at((i_) >> 1, hi8));
+#define VC_ROWS_W(i_) wfi
+#define VC_ROWS_REFILL(c_)
+#include "vc_gemm_rows_body.h"
+}
+
+// The one statement of "a form exists" for `rows` finished rows of an [N x K] matrix behind a centred copy: bf16, 2..16 rows, make_plan's
+// k-tiles per wave (K / 32 in one slice: the largest of 16, 8, 4, 2 that divides a quarter of them) 4, 8 or 16 in ONE chunk - K = 512,
+// 1024, 2048 -, and an even tile count where a workgroup takes two tiles (5 rows and up).  Returns the k-tiles per wave, 0 = no form.
+int vc_gemm_lnq_w8_ok(int rows, int N, int K, int dtype) {
+  if (dtype != VC_DTYPE_BF16 || rows < 2 || rows > VC_ROWS || N < 16 || N % 16 != 0 || K < 32 || K % 32 != 0) return 0;
+  const int KT = K / 32;
+  int ktw = 16;
+  while (ktw > 2 && KT % (4 * ktw) != 0) ktw >>= 1;
+  if (KT != 4 * ktw || (ktw != 4 && ktw != 8 && ktw != 16)) return 0;
+  if (rows > 4 && (N / 16) % 2 != 0) return 0;
+  return ktw;
+}
+
+template <int KTW, int NTW, bool R2>
+static hipError_t launch_lnq_w8(const W8Args& wa, hipStream_t s) {
+  void (*kern)(const W8Args) = rows_gemm_lnq_w8_k<KTW, NTW, R2>;
+  // the image launch's (launch_dec_nt, vc_gemm.hip): X rows, the reduction area per tile, statistics
+  const size_t lds = vc_gemm_lds_bytes(wa.g, VC_DTYPE_BF16, 1) + (size_t)(NTW - 1) * 4 * 64 * sizeof(f32x4);
+  if (lds > 64 * 1024) {
+    static size_t granted[16] = {0};   // per instantiation and device
+    int dev = 0;
+    if (hipError_t ge = hipGetDevice(&dev); ge != hipSuccess) return ge;
+    if (dev >= 0 && dev < 16 && lds > granted[dev]) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      granted[dev] = lds;
+    }
+  }
+  ++vc_launch_counts[VC_LC_ROWS_GEMM];         // the form the image kernel counts in
+  ++vc_launch_counts[VC_LC_W8_UP_ROWS];
+  hipLaunchKernelGGL(kern, dim3(wa.g.n_tiles / NTW, 1, 1), dim3(256 * NTW), lds, s, wa);
+  return hipGetLastError();
+}
+template <int KTW>
+static hipError_t launch_lnq_w8_form(const W8Args& wa, hipStream_t s) {
+  if (wa.g.mt == 4) return launch_lnq_w8<KTW, 2, true>(wa, s);       // 9..16 rows: two tiles per workgroup, two rows per wave
+  if (wa.g.mt == 3) return launch_lnq_w8<KTW, 2, false>(wa, s);      // 5..8 rows: two tiles per workgroup
+  return launch_lnq_w8<KTW, 1, false>(wa, s);                        // 2..4 rows
+}
+// vc_launch_gemm(a, bf16, PRO_LNQ, EPI_RELU, 1, 1) on the pair planes of a.Wp's 16-channel image (a.n_tiles tiles x a.KT k-tiles, packed
+// whole by vc_launch_w8w_pack): the same arguments, grid and LDS; a.mt picks the form as it does there.
+hipError_t vc_launch_gemm_lnq_w8(const GemmArgs& a, const uint4* planes, const uint8_t* side, hipStream_t s) {
+  const int ktw = vc_gemm_lnq_w8_ok(a.n_rows, a.N, a.K, VC_DTYPE_BF16);
+  if (!ktw || !planes || !side || a.x_in == nullptr || a.row_mu == nullptr) return hipErrorInvalidValue;
+  if (a.KT != 4 * ktw || a.nchunk != 1 || a.n_tiles != a.N / 16 || a.r_lds < a.n_rows || a.r_lds > VC_ROWS) return hipErrorInvalidValue;
+  if (a.mt != (a.n_rows > VC_FR_MAX_ROWS ? 4 : a.n_rows >= 5 ? 3 : 0)) return hipErrorInvalidValue;      // (plan_pass's rule for these rows)
+  W8Args wa;
+  wa.g = a;
+  wa.g.x_upr_shift = -1; wa.g.att_q4_shift = -1;      // (prologues this kernel does not have)
+  wa.planes = planes;
+  wa.side = reinterpret_cast<const uint32_t*>(side);      // n_tiles x KT bytes, a wave's share whole aligned words
+  switch (ktw) {
+    case 4: return launch_lnq_w8_form<4>(wa, s);
+    case 8: return launch_lnq_w8_form<8>(wa, s);
+    case 16: return launch_lnq_w8_form<16>(wa, s);
     default: return hipErrorInvalidValue;
   }
 }

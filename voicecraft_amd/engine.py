@@ -52,7 +52,7 @@ class VoiceCraftEngine:
     def __init__(self, args: Namespace | dict, state_dict: dict[str, torch.Tensor], device="cuda:0",
                  dtype="bf16", max_seqs: int = 8, max_positions: int = 4096, use_graph: bool = True, w8: str | None = None,
                  kv8: bool | str = False, w8_rows: bool = False, w8_wide: bool = False,
-                 w8_mid: bool = False, w8_up: bool = False):
+                 w8_mid: bool = False, w8_up: bool = False, w8_up_rows: bool = False):
         """kv8: False (default: nothing changes) | True | "centred" - decode passes of a bf16 engine read the cached K / V positions older than the pass
         as one E4M3 byte per value times a per-row shift (option `kv8`, csrc/vc_kv8.h, quant.kv8_quantize_rows): half the bytes of the
         launch that grows with the batch, 3 mantissa bits left of a cached value, 1.5 x the K/V memory.  Works with every call and `w8=`.
@@ -80,8 +80,15 @@ class VoiceCraftEngine:
         / 2048), bit-identical to the image launch on the same weights; launch_counts()["w8_up"] counts them, w8_stats() says which
         layers have the planes.  This is a third matrix on the 8-bit grid: `w8="quantize"` then quantises it too (`w8_state_dict` is
         that checkpoint, which steps of every width compute: narrower steps read its bf16 image), `w8="as_is"` takes the weights as
-        given and a layer off the grid keeps its image launch.  Independent of w8_wide, w8_rows, w8_mid and kv8."""
+        given and a layer off the grid keeps its image launch.  Independent of w8_wide, w8_rows, w8_mid and kv8.
+        w8_up_rows: False (default: nothing changes) | True, with `w8=` only (ValueError without it) - the FFN up-projection of passes of
+        2..16 rows streams the same E4M3 pair planes (option `w8ur`, mask W8_UP_ROWS_MASK; d = 512 / 1024 / 2048), packed whatever
+        max_seqs is: + 0.27 GB at giga830M on an engine that does not hold them for `w8_up` already, nothing next to it.  Bit-identical
+        to the image launch on the same weights; launch_counts()["w8_up_rows"] counts them, w8_stats() says which layers have the
+        planes.  `w8="quantize"` quantises the third matrix as for w8_up.  Independent of w8_up, w8_wide, w8_rows, w8_mid and kv8."""
         self.lib = _lib.load()
+        if w8_up_rows and w8 is None:
+            raise ValueError('w8_up_rows=True streams planes on the grid of `w8=`: give w8="quantize" or w8="as_is" too')
         if w8_up and w8 is None:
             raise ValueError('w8_up=True streams planes on the grid of `w8=`: give w8="quantize" or w8="as_is" too')
         if w8_mid and w8 is None:
@@ -132,7 +139,7 @@ class VoiceCraftEngine:
         self.w8_state_dict = None
         if w8 == "quantize":
             from . import quant
-            state_dict = self.w8_state_dict = quant.quantize_state_dict_w8(a, state_dict, self.W8_MATRICES, ffn_up=bool(w8_up))
+            state_dict = self.w8_state_dict = quant.quantize_state_dict_w8(a, state_dict, self.W8_MATRICES, ffn_up=bool(w8_up or w8_up_rows))
         check(self.lib.vc_create(C.byref(cfg), index, C.byref(self._h)), None, "vc_create")
         if w8 is not None:
             check(self.lib.vc_request_w8(self._h, self.W8_MASK), self._h, "vc_request_w8")
@@ -146,6 +153,9 @@ class VoiceCraftEngine:
         self.w8_up = bool(w8_up)
         if w8_up:
             check(self.lib.vc_request_w8_up(self._h, self.W8_UP_MASK), self._h, "vc_request_w8_up")
+        self.w8_up_rows = bool(w8_up_rows)
+        if w8_up_rows:
+            check(self.lib.vc_request_w8_up_rows(self._h, self.W8_UP_ROWS_MASK), self._h, "vc_request_w8_up_rows")
         self.kv8 = bool(kv8)
         self.kv8_centred = kv8 == "centred"
         if self.kv8_centred:
@@ -744,7 +754,8 @@ class VoiceCraftEngine:
         w8r = the launches of 2..8-row steps that do (same bits) behind it, one created with `w8_mid=True` w8m = the FFN-down launches of
         9..16-row passes (1, + 8 = also at row counts the measured table leaves out) behind that, one created with `w8_wide=True` w8w = those of 17..64-row
         steps (same bits, + 8 = also at row counts the measured table leaves out) behind that, one created with `w8_up=True` w8u = the
-        FFN-up launches of 17..64-row steps (2, 10 = also at row counts the measured table leaves out) behind that, one created with `kv8=True`
+        FFN-up launches of 17..64-row steps (2, 10 = also at row counts the measured table leaves out) behind that, one created with
+        `w8_up_rows=True` w8ur = the FFN-up launches of 2..16-row passes (2, 10 likewise) behind that, one created with `kv8=True`
         appends kv8 = decode attention on the E4M3 copy of the K/V cache (1) or on the bf16 cache (0), one created with `kv8="centred"`
         kv8c = 1 behind it.
         bench.py turns it into a JSON object (`config.engine_options`)."""
@@ -765,14 +776,20 @@ class VoiceCraftEngine:
                     "tile_attn", "rows_gemm_fr", "big256", "big128", "row_gemm_fr1", "tile_attn64", "rows_gemm_frp", "wd", "rows_gemm_qp", "w13", "w8",
                     "kv8_attn", "kv8_pack", "kv8c_centre", "kv8c_attn", "kv8c_pack", "w8_rows", "w8_wide", "w8_mid", "w8_up")
 
+    LAUNCH_FORMS_MORE = ("w8_up_rows",)     # the census slots behind LAUNCH_FORMS (vc_debug_read "launch_counts_more")
+
     def launch_counts(self) -> dict:
         """Process-wide census of the kernel FORMS launched so far (vc_common.h VC_LC_*): the parity tests take the
         difference around a call to assert which form a benchmarked shape really runs on.  w13 / w8 / w8_rows count launches on packed
         weights IN ADDITION to their form's slot: w8 the one-row launches, w8_rows those of 2..8-row steps (rows_gemm_frp / rows_gemm_qp),
         w8_wide those of 17..64-row steps (also in wd), w8_mid the FFN-down launches of 9..16-row passes (also in rows_gemm_fr),
-        w8_up the FFN-up launches of 17..64-row steps (also in wd, not in w8_wide)."""
+        w8_up the FFN-up launches of 17..64-row steps (also in wd, not in w8_wide), w8_up_rows the FFN-up launches of 2..16-row passes
+        (also in rows_gemm).  The slots behind LAUNCH_FORMS (LAUNCH_FORMS_MORE) are a second read, merged into the same dict."""
         c = self.debug_read("launch_counts", (len(self.LAUNCH_FORMS),), torch.int64)
-        return {n: int(c[i]) for i, n in enumerate(self.LAUNCH_FORMS)}
+        out = {n: int(c[i]) for i, n in enumerate(self.LAUNCH_FORMS)}
+        m = self.debug_read("launch_counts_more", (len(self.LAUNCH_FORMS_MORE),), torch.int64)
+        out.update({n: int(m[i]) for i, n in enumerate(self.LAUNCH_FORMS_MORE)})
+        return out
 
     W13_MATRICES = ("ffn_down", "qkv")
     W13_STATES = ("not_applicable", "packed", "refused")
@@ -792,6 +809,7 @@ class VoiceCraftEngine:
     W8_MID_MASK = 1                         # option `w8m` of an engine created with w8_mid=True (FFN-down)
     W8_WIDE_MASK = 5                        # option `w8w` of an engine created with w8_wide=True
     W8_UP_MASK = 2                          # option `w8u` of an engine created with w8_up=True (FFN-up)
+    W8_UP_ROWS_MASK = 2                     # option `w8ur` of an engine created with w8_up_rows=True (FFN-up)
 
     def w8_stats(self) -> list:
         """w13_stats() for option `w8`: per layer {"ffn_down" | "qkv": {"state": "packed" | "refused" | "not_applicable",
@@ -799,7 +817,8 @@ class VoiceCraftEngine:
         not_applicable: an engine created without `w8=`, or a width without the form (FFN-down below d = 512, QKV below d = 1024).
         An engine created with `w8_wide=True` adds "ffn_down_wide" / "qkv_wide": the pair planes of the 16-channel images that 17..64-row
         steps stream, {"state": ..., "refused_pairs": n} (not_applicable: max_seqs <= 16, or a K slice without the form); one created
-        with `w8_up=True` adds "ffn_up_wide", the same for the FFN up-projection's image."""
+        with `w8_up=True` adds "ffn_up_wide", the same for the FFN up-projection's image; one created with `w8_up_rows=True` adds
+        "ffn_up_rows", the same planes as passes of 2..16 rows see them (not_applicable: a width without the form)."""
         L = int(self.args.num_decoder_layers)
         v = self.debug_read("w8_stats", (L, 2, 2), torch.int32).tolist()
         out = [{m: {"state": self.W13_STATES[v[l][i][0]], "refused_fragments": v[l][i][1]} for i, m in enumerate(self.W8_MATRICES)}
@@ -813,6 +832,10 @@ class VoiceCraftEngine:
             u = self.debug_read("w8u_stats", (L, 2), torch.int32).tolist()
             for l in range(L):
                 out[l]["ffn_up_wide"] = {"state": self.W13_STATES[u[l][0]], "refused_pairs": u[l][1]}
+        if self.w8_up_rows:
+            u = self.debug_read("w8ur_stats", (L, 2), torch.int32).tolist()
+            for l in range(L):
+                out[l]["ffn_up_rows"] = {"state": self.W13_STATES[u[l][0]], "refused_pairs": u[l][1]}
         return out
 
     def debug_read(self, name: str, shape, dtype=torch.float32) -> torch.Tensor:
