@@ -572,7 +572,30 @@ typedef struct vc_debug_attn_args {
   int32_t dtype, H, hd, S_max, rows, nsplit, nt, fast, part16;
 } vc_debug_attn_args;
 int vc_debug_attn(const vc_debug_attn_args* a, void* stream);
-/* The same for option "kv8" (bf16 only; no engine needed).  base: as above; kcache8 / vcache8: uint8 [n_seqs][H][S_max][hd], one OCP
+/* ONE launch of a prefill attention kernel on caller-owned device buffers, through the launchers the engine itself uses
+ * (form 1: tile_attn_k, 16 query rows per workgroup; form 2: tile_attn64_k, 64 query rows per workgroup, bf16 and hd 128 only).
+ * No engine needed.  The rows are a prefill pass's: prompts back to back, each starting on a multiple of 16 rows (form 2: 64), the
+ * rows of a prompt at consecutive positions of ONE sequence, padding rows (row_pos = -1) only behind a prompt's last row.  Row r
+ * attends to cache positions 0..row_pos[r] of sequence row_seq[r]; positions below *share_len are read from sequence 0;
+ * scale = 1/sqrt(hd).  The kernels trust the tables: row_seq < n_seqs and row_pos < S_max are the caller's to keep.
+ *   q fp32 [rows][H*hd]; kcache / vcache [n_seqs][H][S_max][hd] in `dtype` (VC_DTYPE_F32 or VC_DTYPE_BF16); row_seq, row_pos int32
+ *   [rows]; share_len one int32; x_out [rows][H*hd] normalised rows in `dtype`, exact zeros in padding rows; q, the caches and x_out
+ *   16-byte aligned.
+ * VC_EINVAL, before the device is touched, for what no prefill pass can issue: hd not 32 / 64 / 128, a form other than 1 / 2, form 2
+ * without bf16 and hd 128, rows not a positive multiple of 16 (form 2: 64), a null or misaligned pointer, H / S_max < 1, a dtype
+ * other than the two. */
+typedef struct vc_debug_tile_attn_args {
+  const float* q;
+  const void* kcache;
+  const void* vcache;
+  const int32_t* row_seq;
+  const int32_t* row_pos;
+  const int32_t* share_len;
+  void* x_out;
+  int32_t dtype, H, hd, S_max, rows, form;
+} vc_debug_tile_attn_args;
+int vc_debug_tile_attn(const vc_debug_tile_attn_args* a, void* stream);
+/* vc_debug_attn for option "kv8" (bf16 only; no engine needed).  base: as above; kcache8 / vcache8: uint8 [n_seqs][H][S_max][hd], one OCP
  * E4M3 code byte per value, 16-byte aligned; kvshift8: int8 [n_seqs][H][S_max][2], the shift of the K row and of the V row.
  *   pack = 1: ONE launch of the packer (kv8_pack_k): the rows (row_seq[r], row_pos[r]) of the bf16 caches are quantised into the three
  *     arrays (pos < 0: none; *n_active == 0: nothing at all); every other byte stays.  q, share_len, the outputs, nsplit and the form

@@ -61,6 +61,10 @@ def test_struct_layout_matches_header():
     from voicecraft_amd._lib import DebugAttnArgs
     # ten pointers, nine int32, tail padding to the pointers' alignment
     assert DebugAttnArgs.dtype.offset == 80 and DebugAttnArgs.part16.offset == 112 and C.sizeof(DebugAttnArgs) == 120
+    from voicecraft_amd._lib import DebugTileAttnArgs
+    # seven pointers, six int32
+    assert DebugTileAttnArgs.x_out.offset == 48 and DebugTileAttnArgs.dtype.offset == 56 and DebugTileAttnArgs.form.offset == 76
+    assert C.sizeof(DebugTileAttnArgs) == 80
 
 
 def test_debug_attn_refuses_what_no_decode_pass_issues(lib):
@@ -80,6 +84,24 @@ def test_debug_attn_refuses_what_no_decode_pass_issues(lib):
     for kw in bad:
         assert lib.vc_debug_attn(C.byref(args(**kw)), None) == -1, kw
     assert lib.vc_debug_attn(None, None) == -1
+
+
+def test_debug_tile_attn_refuses_what_no_prefill_pass_issues(lib):
+    """vc_debug_tile_attn checks its arguments before it touches the device: the refusals need no GPU (the pointers are never read)."""
+    from voicecraft_amd._lib import DebugTileAttnArgs
+
+    def args(**kw):
+        base = dict(q=16, kcache=32, vcache=48, row_seq=4, row_pos=8, share_len=20, x_out=64, dtype=1, H=2, hd=128, S_max=128, rows=64, form=1)
+        base.update(kw)
+        return DebugTileAttnArgs(**base)
+
+    bad = [dict(hd=48), dict(hd=256), dict(hd=0), dict(form=0), dict(form=3), dict(form=2, dtype=0), dict(form=2, hd=64), dict(form=2, hd=32),
+           dict(rows=0), dict(rows=-16), dict(rows=8), dict(rows=24), dict(form=2, rows=16), dict(form=2, rows=96), dict(dtype=2), dict(dtype=-1),
+           dict(H=0), dict(S_max=0), dict(q=None), dict(kcache=None), dict(vcache=None), dict(row_seq=None), dict(row_pos=None),
+           dict(share_len=None), dict(x_out=None), dict(q=20), dict(kcache=40), dict(vcache=56), dict(x_out=72)]
+    for kw in bad:
+        assert lib.vc_debug_tile_attn(C.byref(args(**kw)), None) == -1, kw
+    assert lib.vc_debug_tile_attn(None, None) == -1
 
 
 def test_no_device_fails_loudly(lib):

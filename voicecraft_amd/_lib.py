@@ -41,6 +41,12 @@ class DebugAttnArgs(C.Structure):
         (n, C.c_int32) for n in ("dtype", "H", "hd", "S_max", "rows", "nsplit", "nt", "fast", "part16")]
 
 
+class DebugTileAttnArgs(C.Structure):
+    """vc_debug_tile_attn_args: seven device pointers, then six int32 (80 bytes)."""
+    _fields_ = [(n, C.c_void_p) for n in ("q", "kcache", "vcache", "row_seq", "row_pos", "share_len", "x_out")] + [
+        (n, C.c_int32) for n in ("dtype", "H", "hd", "S_max", "rows", "form")]
+
+
 class DebugAttn8Args(C.Structure):
     """vc_debug_attn8_args: vc_debug_attn_args, three device pointers, two int32 (152 bytes)."""
     _fields_ = [("base", DebugAttnArgs), ("kcache8", C.c_void_p), ("vcache8", C.c_void_p), ("kvshift8", C.c_void_p),
@@ -109,6 +115,7 @@ PROTOTYPES = {
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int32), C.c_int64]),
     "vc_debug_sample": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SampleCfg), C.c_int, C.c_void_p, C.c_void_p]),
     "vc_debug_attn": (C.c_int, [C.POINTER(DebugAttnArgs), C.c_void_p]),
+    "vc_debug_tile_attn": (C.c_int, [C.POINTER(DebugTileAttnArgs), C.c_void_p]),
     "vc_debug_attn8": (C.c_int, [C.POINTER(DebugAttn8Args), C.c_void_p]),
     "vc_kv8_quantize_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vc_debug_attn8c": (C.c_int, [C.POINTER(DebugAttn8cArgs), C.c_void_p]),

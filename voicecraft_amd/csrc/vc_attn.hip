@@ -1287,3 +1287,25 @@ hipError_t vc_launch_tile_attn(const AttnArgs& a, int dtype, hipStream_t s) {
   }
   return hipErrorInvalidValue;
 }
+
+// Test hook (include/vc_engine.h): one tile_attn_k / tile_attn64_k launch on caller-owned buffers, with the AttnArgs site_attn would fill.
+extern "C" int vc_debug_tile_attn(const vc_debug_tile_attn_args* p, void* stream) {
+  if (!p) return VC_EINVAL;
+  if (p->dtype != VC_DTYPE_F32 && p->dtype != VC_DTYPE_BF16) return VC_EINVAL;
+  if (p->hd != 32 && p->hd != 64 && p->hd != 128) return VC_EINVAL;
+  if (p->form != 1 && p->form != 2) return VC_EINVAL;
+  if (p->form == 2 && (p->dtype != VC_DTYPE_BF16 || p->hd != 128)) return VC_EINVAL;
+  const int tile = p->form == 2 ? 64 : 16;      // rows of one workgroup: a pass holds whole ones (prefill_batch)
+  if (p->H < 1 || p->S_max < 1 || p->rows < tile || p->rows % tile) return VC_EINVAL;
+  if (!p->q || !p->kcache || !p->vcache || !p->row_seq || !p->row_pos || !p->share_len || !p->x_out) return VC_EINVAL;
+  if (((uintptr_t)p->q | (uintptr_t)p->kcache | (uintptr_t)p->vcache | (uintptr_t)p->x_out) & 15) return VC_EINVAL;
+  AttnArgs a = {};
+  a.q = p->q; a.kcache = p->kcache; a.vcache = p->vcache;
+  a.cache_seq_stride = (long)p->H * p->S_max * p->hd;
+  a.S_max = p->S_max; a.H = p->H; a.hd = p->hd; a.hd_shift = p->hd == 32 ? 5 : p->hd == 64 ? 6 : 7; a.d = p->H * p->hd; a.nsplit = 1;
+  a.scale = 1.0f / sqrtf((float)p->hd);
+  a.row_seq = p->row_seq; a.row_pos = p->row_pos; a.n_rows = p->rows;
+  a.share_len = p->share_len; a.x_out = p->x_out;
+  const hipError_t rc = p->form == 2 ? vc_launch_tile_attn64(a, (hipStream_t)stream) : vc_launch_tile_attn(a, p->dtype, (hipStream_t)stream);
+  return rc == hipSuccess ? VC_OK : VC_EHIP;
+}

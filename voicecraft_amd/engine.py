@@ -1249,6 +1249,37 @@ def debug_attn(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, row_
     return out
 
 
+def debug_tile_attn(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, row_seq: torch.Tensor, row_pos: torch.Tensor,
+                    share_len: torch.Tensor, form: int = 1, sentinel: float = 0.0, guard_rows: int = 0) -> torch.Tensor:
+    """ONE launch of a prefill attention kernel on the caller's tensors (vc_debug_tile_attn; tests only).  form 1: tile_attn_k, form 2:
+    tile_attn64_k.  q fp32 [rows][H*hd]; kcache / vcache [n_seqs][H][S_max][hd] fp32 or bf16; row_seq / row_pos int32 [rows], laid out as
+    a prefill pass's (-1 in padding rows); share_len int32 [1].  Returns x_out [rows + guard_rows][H*hd] in the cache dtype, preset to
+    `sentinel`: what the launch left unwritten shows, and the guard rows behind the launch's must keep it."""
+    lib = _lib.load()
+    dev = q.device
+    assert q.is_cuda and q.dtype == torch.float32 and q.ndim == 2 and q.is_contiguous()
+    assert kcache.dtype in (torch.float32, torch.bfloat16) and vcache.dtype == kcache.dtype and kcache.shape == vcache.shape
+    assert kcache.ndim == 4 and kcache.is_contiguous() and vcache.is_contiguous() and kcache.device == dev == vcache.device
+    n_seqs, H, S_max, hd = kcache.shape
+    rows = q.shape[0]
+    assert q.shape[1] == H * hd
+    for t, n in ((row_seq, rows), (row_pos, rows), (share_len, 1)):
+        assert t.dtype == torch.int32 and t.device == dev and t.numel() == n and t.is_contiguous()
+    assert int(row_seq.max()) < n_seqs and int(row_pos.max()) < S_max and 0 <= int(share_len) <= S_max      # the kernels trust their tables
+    assert bool(((row_seq >= 0) | (row_pos < 0)).all())
+    a = _lib.DebugTileAttnArgs()
+    a.q, a.kcache, a.vcache = q.data_ptr(), kcache.data_ptr(), vcache.data_ptr()
+    a.row_seq, a.row_pos, a.share_len = row_seq.data_ptr(), row_pos.data_ptr(), share_len.data_ptr()
+    a.dtype = _lib.VC_DTYPE_BF16 if kcache.dtype == torch.bfloat16 else _lib.VC_DTYPE_F32
+    a.H, a.hd, a.S_max, a.rows, a.form = H, hd, S_max, rows, int(form)
+    x = torch.full((rows + int(guard_rows), H * hd), sentinel, dtype=kcache.dtype, device=dev)
+    a.x_out = x.data_ptr()
+    rc = lib.vc_debug_tile_attn(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise AssertionError(f"vc_debug_tile_attn rejected its arguments (code {rc})")
+    return x
+
+
 def debug_attn8(q, kcache, vcache, kcache8, vcache8, kvshift8, row_seq, row_pos, n_active, share_len, nsplit: int = 1, rps: int = 1,
                 pack: bool = False, nt: bool = False, fast: bool = True, part16: bool = False, x_out: bool = False,
                 sentinel: float = 0.0) -> dict:
