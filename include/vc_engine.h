@@ -189,6 +189,19 @@ const char* vc_version(void);
  *                  ("hq" = 0) and wide steps keep their launches.  The option text gains |w8ur=<v> right behind |w8u=<v> (or where that
  *                  would stand) on such an engine only.  Resident memory: + 0.5 x the W1 image (4 d^2 + d^2 / 128 bytes per layer:
  *                  + 0.27 GB at giga830M) whatever max_seqs is, nothing where "w8u" already holds the planes
+ *   "w8q"          0 / 4 / 12, ONLY on an engine that called vc_request_w8_qkv_rows (default 4; VC_EINVAL on any other engine and for any
+ *                  other value): the passes of finished rows behind a centred copy (option "hq") whose QKV projection reads the
+ *                  12-channel image - the row counts past the paired consumer's: 9..16 at every width, 7 and 8 at d = 2048, and the
+ *                  lower ones too with "qkv_p8" below 2 - stream the QKV projection of layers 1.. (4) from the E4M3 pairs of that image
+ *                  (csrc/vc_w8.h "w8q": 768 B of codes and two side bytes, one per part, per 12 channels x 64 inputs;
+ *                  rows_gemm_qkvq_w8_k: the text of rows_gemm_k<bf16, KTW, PRO_LNQ, EPI_QKV, ..> with KTW / 2 pairs per wave and tile as
+ *                  the weight source; K = d in one chunk of 4, 8 or 16 k-tiles per wave: d = 512 / 1024 / 2048), every result
+ *                  bit-identical to the image launch; a refused layer keeps its image launch, and so does layer 0, which reads no
+ *                  centred copy (vc_debug_read "w8q_stats": int32 [layer][state, pairs refused]).  12 = 4 + bit 8: also at the row
+ *                  counts the measured win table leaves out (for the A/B tool and the tests; vc_debug_w8q_plan says which row counts
+ *                  take the form).  Independent of "w8r", "w8m", "w8w", "w8u" and "w8ur".  The option text gains |w8q=<v> right behind
+ *                  |w8ur=<v> (or where that would stand) on such an engine only.  Resident memory: + 0.5 x the Wqkv image per packed
+ *                  layer (3 d^2 + d^2 / 128 bytes: + 0.20 GB at giga830M) whatever max_seqs is
  *   "kv8"          0 / 1, ONLY on an engine that called vc_request_kv8 (default 1; VC_EINVAL on any other engine): decode passes read the
  *                  cached K / V positions older than the pass as one OCP E4M3 byte per value times 2^shift, one shift byte per cached
  *                  row of a head (csrc/vc_kv8.h; voicecraft_amd/quant.py kv8_quantize_rows states the grid), half the bytes of the bf16
@@ -199,7 +212,7 @@ const char* vc_version(void);
  * What an option may change: nothing in the exact fp32 mode's greedy tokens (tests/test_gpu_options.py, test_gpu_one_row.py); in bf16
  * mode the forms that re-order sums or round at another place ("finished_rows", "fr_pair", "att_p16", "hq", "fr_one", "qkv_p8", "attn_fast",
  * "qkv16", "wide_heads", "wide_gemm") move head logits by bf16 rounding (tests allow 0.25 absolute), so top-k SAMPLED tokens can differ between option
- * states; the cache-policy / data-path / host-side options ("nt", "wd_stage", "graph_steps", "shrink", "w13", "w8", "w8r", "w8m", "w8w", "w8u", "w8ur") change no value; "kv8" rounds cached K / V to its grid.
+ * states; the cache-policy / data-path / host-side options ("nt", "wd_stage", "graph_steps", "shrink", "w13", "w8", "w8r", "w8m", "w8w", "w8u", "w8ur", "w8q") change no value; "kv8" rounds cached K / V to its grid.
  * The non-temporal mask "nt" has no bit for the finished-row producers (rows_gemm_fr_k, rows_gemm_fr2_k, row_gemm_fr1_k) and the
  * wide-decode kernels: they always stream with the hint.  Captured decode graphs are kept per option state and step width, so an
  * in-process A/B (bench.py --ab) pays for capture once per state.  Unknown names / malformed values: VC_EINVAL.
@@ -252,6 +265,14 @@ int vc_request_w8_up(vc_engine* e, int mask);
  * whatever max_seqs is (once when vc_request_w8_up asked too): + 0.5 x that image resident, + 0.27 GB at giga830M; bf16 only, as
  * vc_request_w8.  An engine without this request packs nothing more, has no such option and launches what it launched before. */
 int vc_request_w8_up_rows(vc_engine* e, int mask);
+/* After vc_request_w8 on the same engine (VC_ESTATE without it) and before vc_finalize_weights (VC_ESTATE after it): the passes of
+ * finished rows whose QKV projection reads the 12-channel image (9..16 rows; 7 and 8 at d = 2048) stream it from E4M3 pairs of that
+ * image, option "w8q" above.  `mask`: 4 (anything else: VC_EINVAL); it needs no bit of vc_request_w8's mask and no other request.  The
+ * weights are taken as given: a layer whose folded in_proj_weight is off the grid is refused and keeps its image launch.
+ * vc_finalize_weights packs the 12-channel image Wqkv of layers 1.. once more, whatever max_seqs is: + 0.5 x that image resident,
+ * + 0.20 GB at giga830M; bf16 only, as vc_request_w8.  An engine without this request packs nothing more, has no such option and launches
+ * what it launched before. */
+int vc_request_w8_qkv_rows(vc_engine* e, int mask);
 /* Before vc_finalize_weights (VC_ESTATE after it): keep, next to every layer's bf16 K / V cache, an E4M3 copy (one byte per value) and one
  * shift byte per cached row of a head, written by one packer launch behind every pass, and let the decode attention read the positions
  * older than the pass from it (option "kv8" above).  bf16 only: vc_finalize_weights with VC_DTYPE_F32 after the request returns
@@ -688,6 +709,17 @@ int vc_debug_w8u_plan(const vc_model_cfg* cfg, int mask, int rows, int32_t out[2
  * form is not taken).  Zeros at 1 row and from 17 rows on.  VC_EINVAL: a null pointer, rows outside 1..64, another mask.
  * tests/test_w8_up_rows_cpu.py walks every model width. */
 int vc_debug_w8ur_plan(const vc_model_cfg* cfg, int mask, int rows, int32_t out[2]);
+/* Host only: what option "w8q" = mask (0, 4 or 12) makes of a bf16 decode pass of `rows` rows at this model shape, Wqkv taken as packed.
+ * out[0] = 1 when the QKV projection of layers 1.. runs on the pairs of the 12-channel image (rows_gemm_qkvq_w8_k), out[1] the k-tiles
+ * per wave there (0 where the form is not taken).  Zeros at 1 row, at the row counts the paired consumer takes and from 17 rows on.
+ * VC_EINVAL: a null pointer, rows outside 1..64, another mask.  tests/test_w8_qkv_rows_cpu.py walks every model width. */
+int vc_debug_w8q_plan(const vc_model_cfg* cfg, int mask, int rows, int32_t out[2]);
+/* Host only: the packer of the "w8q" pairs (csrc/vc_w8.h, the text the device packer runs per lane) on n_pairs pairs of a 12-channel
+ * bf16 image of KT k-tiles per tile (1536 B each: fragments of k-tiles 2j, 2j + 1 of one tile, 48 slots of 16 bytes, slot kg * 12 + m =
+ * channel m, inputs 8 kg .. + 7 of its k-tile; pair P belongs to tile P / (KT / 2), whose parity places the split between the parts):
+ * planes = n_pairs x 768 B, side = n_pairs x 2 bytes (shift + 127 of part 0, of part 1), *refused_pairs = pairs with a part off the
+ * grid.  -1: a null pointer, n_pairs < 0 or no whole tiles, an odd KT. */
+int vc_w8q_pack_host(const uint16_t* image12, long n_pairs, uint8_t* planes, uint8_t* side, int KT, int32_t* refused_pairs);
 /* Host only: the packer of the pair planes (csrc/vc_w8.h, the text the device packer runs per lane) on n_pairs pairs of a 16-channel
  * bf16 image (2 KB each: fragments of k-tiles 2j, 2j + 1 of one tile, lane l = channel l & 15, inputs 8 (l >> 4) .. + 7 of its k-tile):
  * planes = n_pairs x 1 KB (16 bytes per lane: eight codes of k-tile 2j, eight of 2j + 1), side = n_pairs x 2 bytes (shift + 127 of

@@ -73,6 +73,7 @@ PROTOTYPES = {
     "vc_request_w8_wide": (C.c_int, [C.c_void_p, C.c_int]),
     "vc_request_w8_up": (C.c_int, [C.c_void_p, C.c_int]),
     "vc_request_w8_up_rows": (C.c_int, [C.c_void_p, C.c_int]),
+    "vc_request_w8_qkv_rows": (C.c_int, [C.c_void_p, C.c_int]),
     "vc_request_kv8": (C.c_int, [C.c_void_p]),
     "vc_request_kv8c": (C.c_int, [C.c_void_p]),
     "vc_tts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(SampleCfg), C.c_int,
@@ -137,6 +138,8 @@ PROTOTYPES = {
     "vc_debug_w8w_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "vc_debug_w8u_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "vc_debug_w8ur_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "vc_debug_w8q_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "vc_w8q_pack_host": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
     "vc_w8w_pack_host": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "vc_box_probe": (C.c_int, [C.c_longlong, C.c_int, C.POINTER(C.c_float), C.c_void_p]),
     "vc_debug_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),

@@ -498,6 +498,10 @@ struct vc_packed_kind {
   // image, and whether these rows of this matrix have such a form (the k-tiles per wave, 0 = none); null where the kind has none (w13)
   hipError_t (*lnq)(const GemmArgs& a, const uint4* planes, const uint8_t* side, hipStream_t s);
   int (*lnq_ok)(int rows, int N, int K, int dtype);
+  // vc_launch_gemm(.., PRO_LNQ, EPI_QKV, 1, 1) (the QKV projection of 2..16 finished rows) on the pairs of the 12-channel image
+  // (vc_w8.h "w8q"), and whether these rows of this matrix have such a form (the k-tiles per wave, 0 = none); null where the kind has none (w13)
+  hipError_t (*qkvq)(const GemmArgs& a, const uint4* planes, const uint8_t* side, hipStream_t s);
+  int (*qkvq_ok)(int rows, int N, int K, int dtype);
 };
 const vc_packed_kind& vc_packed(int kind);                  // kind = VC_PK_* (the table is in vc_gemm.hip)
 int vc_gemm_packed_fr1_ng(int kind, int N, int K, int dtype, int nw);   // groups per wave, 0 = the matrix has no such form
@@ -521,12 +525,17 @@ int vc_gemm_fr_w8_ng(int rows, int N, int K, int dtype);    // groups per wave a
 // rows_gemm_lnq_w8_k: vc_launch_gemm's PRO_LNQ / EPI_RELU form (bf16, 2..16 finished rows, one K slice, one group) on the pair planes of a.Wp's 16-channel image
 hipError_t vc_launch_gemm_lnq_w8(const GemmArgs& a, const uint4* planes, const uint8_t* side, hipStream_t s);
 int vc_gemm_lnq_w8_ok(int rows, int N, int K, int dtype);   // k-tiles per wave (4, 8, 16: K = 512, 1024, 2048 in one chunk), 0 = no form
+// pairs of a 12-channel bf16 image of KT k-tiles per tile (vc_w8.h "w8q"; n_pairs = tiles x KT / 2): counts as vc_launch_w8w_pack
+hipError_t vc_launch_w8q_pack(const uint4* img, long n_pairs, int KT, uint4* planes, unsigned char* side, unsigned int* counts, hipStream_t s);
+// rows_gemm_qkvq_w8_k: vc_launch_gemm's PRO_LNQ / EPI_QKV form (bf16, 2..16 finished rows, one K slice, one group) on the pairs of a.Wp's 12-channel image
+hipError_t vc_launch_gemm_qkvq_w8(const GemmArgs& a, const uint4* planes, const uint8_t* side, hipStream_t s);
+int vc_gemm_qkvq_w8_ok(int rows, int N, int K, int dtype);  // k-tiles per wave (4, 8, 16: K = 512, 1024, 2048 in one chunk), 0 = no form
 extern int vc_blk_dbg_mask;   // vc_gemm.hip: diagnostic mask of the prefill block GEMM, 0 in production
 // Launch census (process-wide, host side): which kernel FORM each launcher picked.  Read through
 // vc_debug_read("launch_counts") by the parity tests, which assert that the form a benchmarked shape runs on is the one
 // they compared with the oracle.
 enum { VC_LC_ROWS_GEMM = 0, VC_LC_MT2 = 1, VC_LC_MT4 = 2, VC_LC_BLK64 = 3, VC_LC_BLK128_SBS = 4, VC_LC_BLK128_2X2 = 5,
-       VC_LC_BLK64_OCC2 = 6, VC_LC_LN_ROWS = 7, VC_LC_ROWS_ATTN = 8, VC_LC_TILE_ATTN = 9, VC_LC_ROWS_GEMM_FR = 10, VC_LC_BIG256 = 11, VC_LC_BIG128 = 12, VC_LC_ROW_GEMM_FR1 = 13, VC_LC_TILE_ATTN64 = 14, VC_LC_ROWS_GEMM_FRP = 15, VC_LC_WD = 16, VC_LC_ROWS_GEMM_QP = 17, VC_LC_W13 = 18, VC_LC_W8 = 19, VC_LC_KV8_ATTN = 20, VC_LC_KV8_PACK = 21, VC_LC_KV8C_CENTRE = 22, VC_LC_KV8C_ATTN = 23, VC_LC_KV8C_PACK = 24, VC_LC_W8_ROWS = 25, VC_LC_W8_WIDE = 26, VC_LC_W8_MID = 27, VC_LC_W8_UP = 28, VC_LC_W8_UP_ROWS = 29, VC_LC_N = 30 };   // VC_LC_W13 / VC_LC_W8: launches on 13-bit planes / on E4M3 bytes (also counted in their form's slot); VC_LC_KV8_ATTN: rows_attn_k launches on the E4M3 K/V cache (also in VC_LC_ROWS_ATTN), VC_LC_KV8_PACK: kv8_pack_k; VC_LC_KV8C_*: the centre kernel, and the centred attention / packer launches (also in their kv8 slots); VC_LC_W8_ROWS: launches of 2..8-row steps on E4M3 bytes (also in VC_LC_ROWS_GEMM_FRP / VC_LC_ROWS_GEMM_QP; VC_LC_W8 stays the one-row launches); VC_LC_W8_WIDE: launches of 17..64-row steps on E4M3 pair planes (also in VC_LC_WD); VC_LC_W8_MID: launches of 9..16-row passes on E4M3 bytes (also in VC_LC_ROWS_GEMM_FR); VC_LC_W8_UP: FFN-up launches of 17..64-row steps on E4M3 pair planes (also in VC_LC_WD, not in VC_LC_W8_WIDE); VC_LC_W8_UP_ROWS: FFN-up launches of 2..16-row passes on E4M3 pair planes (also in VC_LC_ROWS_GEMM)
+       VC_LC_BLK64_OCC2 = 6, VC_LC_LN_ROWS = 7, VC_LC_ROWS_ATTN = 8, VC_LC_TILE_ATTN = 9, VC_LC_ROWS_GEMM_FR = 10, VC_LC_BIG256 = 11, VC_LC_BIG128 = 12, VC_LC_ROW_GEMM_FR1 = 13, VC_LC_TILE_ATTN64 = 14, VC_LC_ROWS_GEMM_FRP = 15, VC_LC_WD = 16, VC_LC_ROWS_GEMM_QP = 17, VC_LC_W13 = 18, VC_LC_W8 = 19, VC_LC_KV8_ATTN = 20, VC_LC_KV8_PACK = 21, VC_LC_KV8C_CENTRE = 22, VC_LC_KV8C_ATTN = 23, VC_LC_KV8C_PACK = 24, VC_LC_W8_ROWS = 25, VC_LC_W8_WIDE = 26, VC_LC_W8_MID = 27, VC_LC_W8_UP = 28, VC_LC_W8_UP_ROWS = 29, VC_LC_W8_QKV_ROWS = 30, VC_LC_N = 31 };   // VC_LC_W13 / VC_LC_W8: launches on 13-bit planes / on E4M3 bytes (also counted in their form's slot); VC_LC_KV8_ATTN: rows_attn_k launches on the E4M3 K/V cache (also in VC_LC_ROWS_ATTN), VC_LC_KV8_PACK: kv8_pack_k; VC_LC_KV8C_*: the centre kernel, and the centred attention / packer launches (also in their kv8 slots); VC_LC_W8_ROWS: launches of 2..8-row steps on E4M3 bytes (also in VC_LC_ROWS_GEMM_FRP / VC_LC_ROWS_GEMM_QP; VC_LC_W8 stays the one-row launches); VC_LC_W8_WIDE: launches of 17..64-row steps on E4M3 pair planes (also in VC_LC_WD); VC_LC_W8_MID: launches of 9..16-row passes on E4M3 bytes (also in VC_LC_ROWS_GEMM_FR); VC_LC_W8_UP: FFN-up launches of 17..64-row steps on E4M3 pair planes (also in VC_LC_WD, not in VC_LC_W8_WIDE); VC_LC_W8_UP_ROWS: FFN-up launches of 2..16-row passes on E4M3 pair planes (also in VC_LC_ROWS_GEMM); VC_LC_W8_QKV_ROWS: QKV launches of 2..16-row passes on the E4M3 pairs of the 12-channel image (also in VC_LC_ROWS_GEMM)
 extern long long vc_launch_counts[VC_LC_N];
 hipError_t vc_launch_ln_rows(const GemmArgs& a, int dtype, hipStream_t s);
 hipError_t vc_launch_attn(const AttnArgs& a, int dtype, int rows_cap, hipStream_t s);

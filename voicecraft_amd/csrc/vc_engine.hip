@@ -147,6 +147,28 @@ int pack_pairs(vc_engine* e, Layer& ly, int which, const uint4* image, long n_pa
   return VC_OK;
 }
 
+// The pairs (vc_w8.h "w8q", slot Layer::w8q) of the 12-channel image Wqkv of KT k-tiles per tile: pack_pairs for the QKV projection of
+// finished-row passes.  A pair with a part off the grid, or any dword that does not decode to the image's, refuses the layer.
+int pack_pairs12(vc_engine* e, Layer& ly, long n_pairs, int KT) {
+  if (!e->w13_counts) { int rc = dalloc(e, &e->w13_counts, (size_t)4); if (rc) return rc; }
+  Layer::Packed& p = ly.w8q;
+  const size_t mark = e->allocs.size();
+  const double bytes0 = e->bytes_total;
+  int rc;
+  if ((rc = dalloc(e, &p.planes, (size_t)n_pairs * VC_W8Q_PAIR_U4))) return rc;
+  if ((rc = dalloc(e, &p.side, (size_t)(n_pairs + 1) / 2))) return rc;      // two bytes per pair
+  HIPCHK(e, vc_launch_w8q_pack(ly.Wqkv, n_pairs, KT, p.planes, reinterpret_cast<unsigned char*>(p.side), e->w13_counts, 0));
+  unsigned int cnt[2] = {0, 0};
+  HIPCHK(e, hipMemcpy(cnt, e->w13_counts, sizeof cnt, hipMemcpyDeviceToHost));
+  p.refused = (int)cnt[0];
+  if (cnt[0] == 0 && cnt[1] == 0) { p.state = 1; return VC_OK; }
+  p.state = 2;
+  while (e->allocs.size() > mark) { (void)hipFree(e->allocs.back()); e->allocs.pop_back(); }
+  e->bytes_total = bytes0;
+  p.planes = nullptr; p.side = nullptr;
+  return VC_OK;
+}
+
 int keep_vec(vc_engine* e, const std::string& key, int n, float** out, float* mean = nullptr) {
   const RawTensor* t;
   int rc = need(e, key, {n}, &t);
@@ -269,6 +291,17 @@ bool w8ur_rows_win(int rows) {
   return rows >= 2 && rows <= VC_ROWS;
 }
 
+// Option "w8q": the row counts at which the pair form of the QKV projection's 12-channel image measured faster than the image over the
+// whole paired range; a count that was not measured follows the nearest measured one of the same kernel form (2..4, 5..8, 9..16 rows).
+// profiles/w8_qkv_rows_ab.log (tools/w8_qkv_rows_ab.py: giga830M, 7 interleaved pairs per line, captured decode loop per step, min..max of
+// the pairs) at 7, 8 | 9, 12, 16 rows: -2.8 .. -2.6 % | -1.8 .. -1.5 %, and -1.6 .. -1.5 % for 16 utterances at the benchmark's shapes with
+// `w8r`, `w8m` and `w8ur` on: every measured row count has its whole range below zero, so 5..8 rows (two tiles per workgroup) and 9..16
+// rows (two rows per wave as well) take the form where the 12-channel image serves them.  No count of the one-tile form (2..4 rows, which
+// the image serves with `qkv_p8` below 2 only) was measured: those stay out and reach the kernel through bit 8.
+bool w8q_rows_win(int rows) {
+  return rows >= 5 && rows <= VC_ROWS;
+}
+
 // Option "w8m": the row counts of 9..16 at which the w8 form of the FFN down-projection measured faster than the image over the whole
 // paired range; a count that was not measured follows the nearest measured one.  profiles/w8_mid_ab.log (tools/w8_mid_ab.py: giga830M,
 // 7 interleaved pairs per line, captured decode loop per step, min..max of the pairs) at 9, 12, 16 rows: -5.3 .. -5.2 %, -5.0 .. -4.9 %,
@@ -338,6 +371,10 @@ PassPlan plan_pass(const vc_engine* e, int rows, bool decode, int tiled) {
     // option "w8ur": the FFN up-projection behind a centred copy on the pair planes of W1, where the launcher has a form for these rows
     // (K = d in one chunk of 4, 8 or 16 k-tiles per wave: d = 512 / 1024 / 2048).  The site takes it for the layers whose W1 is packed.
     p.lnq_w8_f1 = p.hq && (e->w8ur & W8_BITS[W13_F1]) && pk8.lnq_ok(rows, 4 * d, d, e->dtype) != 0 && (w8ur_rows_win(rows) || (e->w8ur & 8));
+    // option "w8q": the QKV projection behind a centred copy on the pairs of the 12-channel image, at the row counts the paired consumer
+    // leaves to rows_gemm_k (p.qp covers 2..6 rows at d = 2048 and 2..8 at narrower widths; with qkv_p8 < 2 none) and where the launcher
+    // has a form (K = d in one chunk of 4, 8 or 16 k-tiles per wave).  The site takes it for the layers 1.. whose Wqkv is packed.
+    p.qkvq_w8 = p.hq && !p.qp && (e->w8q & W8_BITS[W13_QKV]) && pk8.qkvq_ok(rows, 3 * d, d, e->dtype) != 0 && (w8q_rows_win(rows) || (e->w8q & 8));
   } else {
     p.nsplit = 1;                      // attention one workgroup per (row, head), no split partials
     p.att_x = true;
@@ -426,6 +463,8 @@ int site_qkv(vc_engine* e, const PassPlan& p, const RowSrc& rs, const Layer& ly,
       const Layer::Packed& p8 = ly.packed[VC_PK_W8][W13_QKV];
       if (p.qp_w8 && p8.state == 1) { g.Wp = ly.Wqkv8; HIPCHK(e, vc_packed(VC_PK_W8).qp(g, p8.planes, p8.side, s)); }
       else if (p.qp) { g.Wp = ly.Wqkv8; HIPCHK(e, vc_launch_gemm_qp(g, e->dtype, s)); }
+      else if (p.qkvq_w8 && ly.w8q.state == 1)      // ... on the pairs of the 12-channel image (a refused layer keeps its image)
+        HIPCHK(e, vc_packed(VC_PK_W8).qkvq(g, ly.w8q.planes, reinterpret_cast<const uint8_t*>(ly.w8q.side), s));
       else HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNQ, EPI_QKV, 1, 1, s));
     } else {
       HIPCHK(e, vc_launch_gemm(g, e->dtype, PRO_LNW, EPI_QKV, 1, 1, s));
@@ -1080,6 +1119,11 @@ int need_w8ur(vc_engine* e, const char*, int v0) {
   if (!e->w8ur_req) return fail(e, VC_EINVAL, "option 'w8ur': this engine was created without vc_request_w8_up_rows");
   return v0 != 0 && v0 != 2 && v0 != 10 ? fail(e, VC_EINVAL, "option 'w8ur': %d is not 0, 2 (FFN-up) or 10 (at every row count)", v0) : VC_OK;
 }
+// 4 (QKV) plus bit 8, on an engine that requested the form (vc_request_w8_qkv_rows)
+int need_w8q(vc_engine* e, const char*, int v0) {
+  if (!e->w8q_req) return fail(e, VC_EINVAL, "option 'w8q': this engine was created without vc_request_w8_qkv_rows");
+  return v0 != 0 && v0 != 4 && v0 != 12 ? fail(e, VC_EINVAL, "option 'w8q': %d is not 0, 4 (QKV) or 12 (at every row count)", v0) : VC_OK;
+}
 int need_kv8(vc_engine* e, const char*, int) {
   return e->kv8_req ? VC_OK : fail(e, VC_EINVAL, "option 'kv8': this engine was created without vc_request_kv8");
 }
@@ -1128,6 +1172,7 @@ const OptDesc OPTIONS[] = {
     {"w8w", nullptr, "w8w", {&E::w8w, 0, 13}, nullptr, {}, need_w8w, &E::w8w_req},  // likewise (vc_request_w8_wide)
     {"w8u", nullptr, "w8u", {&E::w8u, 0, 10}, nullptr, {}, need_w8u, &E::w8u_req},  // likewise (vc_request_w8_up)
     {"w8ur", nullptr, "w8ur", {&E::w8ur, 0, 10}, nullptr, {}, need_w8ur, &E::w8ur_req},   // likewise (vc_request_w8_up_rows)
+    {"w8q", nullptr, "w8q", {&E::w8q, 0, 12}, nullptr, {}, need_w8q, &E::w8q_req},   // likewise (vc_request_w8_qkv_rows)
     {"kv8", nullptr, "kv8", {&E::kv8, 0, 1}, nonzero, {}, need_kv8, &E::kv8_req},   // likewise
     {"prefill_rows", "VC_PREFILL_ROWS", nullptr, {&E::prefill_rows_per_pass, VC_ROWS, VC_MAX_ROWS}, whole_tiles},   // 16: decode kernels only
 };
@@ -1270,6 +1315,23 @@ extern "C" int vc_debug_w8ur_plan(const vc_model_cfg* c, int mask, int rows, int
   const PassPlan p = plan_pass(&e, rows, true, 0);
   out[0] = p.lnq_w8_f1 ? 1 : 0;
   out[1] = p.lnq_w8_f1 ? vc_packed(VC_PK_W8).lnq_ok(rows, 4 * d, d, e.dtype) : 0;
+  return VC_OK;
+}
+// Host-only: what option "w8q" = mask (0, 4 or 12) makes of a bf16 decode pass of `rows` rows at this model shape, Wqkv taken as packed
+// (plan_pass itself): out = {QKV of the finished rows of layers 1.. on the pairs of the 12-channel image, k-tiles per wave there}.
+extern "C" int vc_debug_w8q_plan(const vc_model_cfg* c, int mask, int rows, int32_t out[2]) {
+  if (!c || !out || rows < 1 || rows > VC_MAX_SEQS || (mask != 0 && mask != 4 && mask != 12) || c->d_model <= 0 || c->nhead <= 0 ||
+      c->d_model % c->nhead)
+    return VC_EINVAL;
+  vc_engine e;      // default options, the weight images vc_finalize_weights packs, both requests made
+  e.cfg = *c; e.d = c->d_model; e.H = c->nhead; e.hd = c->d_model / c->nhead; e.P = c->head_hidden; e.dtype = VC_DTYPE_BF16;
+  const int d = e.d;
+  e.has_fr8 = e.has_qkv16 = true;
+  e.has_qkv8 = vc_gemm_fr1_ok(3 * d, d, e.dtype, 4) != 0;
+  e.w8_req = e.w8 = 5; e.w8q_req = 4; e.w8q = mask;
+  const PassPlan p = plan_pass(&e, rows, true, 0);
+  out[0] = p.qkvq_w8 ? 1 : 0;
+  out[1] = p.qkvq_w8 ? vc_packed(VC_PK_W8).qkvq_ok(rows, 3 * d, d, e.dtype) : 0;
   return VC_OK;
 }
 // Host-only: how a decode pass of `rows` rows would be launched for this model shape and compute dtype (no engine, no GPU).
@@ -1461,6 +1523,19 @@ extern "C" int vc_request_w8_up_rows(vc_engine* e, int mask) {
   return VC_OK;
 }
 
+// Lets the finished-row passes whose QKV projection still reads the 12-channel image (9..16 rows; 7 and 8 at d = 2048) stream it (mask
+// 4, nothing else) from the pairs of that image (option "w8q"): packed at vc_finalize_weights for layers 1.., + 0.5 x that image, whatever
+// max_seqs is.  Needs vc_request_w8 (the bf16 / fp32 check of that request at vc_finalize_weights covers this one) but none of its bits.
+extern "C" int vc_request_w8_qkv_rows(vc_engine* e, int mask) {
+  if (!e) return VC_EINVAL;
+  if (e->finalized) return fail(e, VC_ESTATE, "vc_request_w8_qkv_rows comes before vc_finalize_weights");
+  if (!e->w8_req) return fail(e, VC_ESTATE, "vc_request_w8_qkv_rows comes after vc_request_w8");
+  if (mask != W8_BITS[W13_QKV]) return fail(e, VC_EINVAL, "vc_request_w8_qkv_rows: %d is not the mask 4 (QKV)", mask);
+  e->w8q_req = mask;
+  e->w8q = mask;
+  return VC_OK;
+}
+
 // Lets passes of 9..16 finished rows stream the FFN-down planes vc_request_w8 asked for (option "w8m"): `mask` is bit 1 of that request.
 // Nothing more is packed and resident memory does not change.
 extern "C" int vc_request_w8_mid(vc_engine* e, int mask) {
@@ -1634,6 +1709,10 @@ int pack_layer(vc_engine* e, int l) {
   const bool up_rows = e->w8ur_req && vc_packed(VC_PK_W8).lnq_ok(2, 4 * d, d, e->dtype);
   if ((up_wide || up_rows) && e->dtype == VC_DTYPE_BF16 &&
       (rc = pack_pairs(e, ly, W13_F1, ly.W1, (long)(4 * d / 16) * (d / 64)))) return rc;
+  // on request (vc_request_w8_qkv_rows): the pairs of the 12-channel image Wqkv, for the layers that read a centred copy (layer 0 has
+  // none and keeps PRO_LNW), whatever max_seqs is: + 0.5 x the image
+  if (e->w8q_req && l > 0 && e->dtype == VC_DTYPE_BF16 && vc_packed(VC_PK_W8).qkvq_ok(2, 3 * d, d, e->dtype) &&
+      (rc = pack_pairs12(e, ly, (long)(3 * d / VC_TH_QKV) * (d / 64), d / 32))) return rc;
   const size_t cache_bytes = (size_t)e->B_max * e->H * e->S_max * e->hd * e->esz;
   if ((rc = dalloc(e, &ly.kc, cache_bytes))) return rc;
   if ((rc = dalloc(e, &ly.vc, cache_bytes))) return rc;
@@ -2527,6 +2606,17 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
       src = e->layers[atoi(n.c_str() + 8)].kcen; avail = (int64_t)e->B_max * e->H * e->hd * 2;
     }
   }
+  else if ((n.rfind("w8q_planes_", 0) == 0 || n.rfind("w8q_side_", 0) == 0) && e->w8q_req) {      // w8q_planes_<l>: uint8 [pairs][768], w8q_side_<l>: uint8 [pairs][2] of a packed layer (engines with vc_request_w8_qkv_rows)
+    const bool planes = n[4] == 'p';
+    const size_t at = planes ? 11 : 9;
+    if (at >= n.size() || n.size() > at + 3 || n.find_first_not_of("0123456789", at) != std::string::npos || atoi(n.c_str() + at) >= e->L)
+      return fail(e, VC_EINVAL, "unknown debug buffer '%s'", n.c_str());
+    const Layer& ly = e->layers[atoi(n.c_str() + at)];
+    if (ly.w8q.state != 1) return fail(e, VC_ESTATE, "debug buffer '%s': the layer holds no pairs of the 12-channel QKV image", n.c_str());
+    const int64_t pairs = (int64_t)(3 * e->d / VC_TH_QKV) * (e->d / 64);
+    if (planes) { src = ly.w8q.planes; avail = pairs * VC_W8Q_PAIR_BYTES; }
+    else { src = ly.w8q.side; avail = pairs * 2; }
+  }
   else if (n == "eval_logits") {                    // fp32 [rows][K][V] of the last vc_eval_forward call with the parity hook
     if (!e->eval_logits) return fail(e, VC_ESTATE, "no vc_eval_forward call with nll_dev / tgt_dev has run");
     src = e->eval_logits; avail = e->eval_logits_rows * e->K * e->V * 4;
@@ -2556,6 +2646,13 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
     memcpy(host_dst, v.data(), (size_t)nbytes);
     return VC_OK;
   }
+  else if (n == "w8q_stats" && e->w8q_req) {      // int32 [layer][state, pairs refused] of the 12-channel QKV image's pairs (engines with vc_request_w8_qkv_rows; layer 0: 0, 0)
+    std::vector<int32_t> v;
+    for (const Layer& ly : e->layers) { v.push_back(ly.w8q.state); v.push_back(ly.w8q.refused); }
+    if (nbytes > (int64_t)(v.size() * 4)) return fail(e, VC_ECAP, "debug buffer '%s' holds %lld bytes", n.c_str(), (long long)(v.size() * 4));
+    memcpy(host_dst, v.data(), (size_t)nbytes);
+    return VC_OK;
+  }
   else if (n == "w8u_stats" && e->w8u_req) {      // int32 [layer][state, pairs refused] of the FFN up-projection's pair planes (engines with vc_request_w8_up)
     std::vector<int32_t> v;
     for (const Layer& ly : e->layers) { v.push_back(ly.packed[PK_W8W][W13_F1].state); v.push_back(ly.packed[PK_W8W][W13_F1].refused); }
@@ -2565,6 +2662,7 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
   }
   else if (n == "launch_counts") { host_src = vc_launch_counts; avail = VC_LC_N * 8; }     // process-wide census of kernel forms (vc_common.h)
   else if (n == "launch_counts_more") { host_src = vc_launch_counts + VC_LC_W8_UP_ROWS; avail = (VC_LC_N - VC_LC_W8_UP_ROWS) * 8; }   // the slots from VC_LC_W8_UP_ROWS on
+  else if (n == "launch_counts_more2") { host_src = vc_launch_counts + VC_LC_W8_QKV_ROWS; avail = (VC_LC_N - VC_LC_W8_QKV_ROWS) * 8; }   // the slots from VC_LC_W8_QKV_ROWS on
   else if (n == "stream") {         // the open streaming TTS call: {finished rows the host knows of, frames handed out, loop over}
     if (!e->ts) return fail(e, VC_ESTATE, "no streaming TTS call is open (vc_tts_stream_begin)");
     if (nbytes != 3 * 4) return fail(e, VC_ECAP, "debug buffer 'stream' holds 12 bytes");

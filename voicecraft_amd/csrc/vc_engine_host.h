@@ -54,6 +54,9 @@ struct Layer {
     int state = 0;                 // 0 not applicable (or not packed), 1 packed, 2 refused: the launch stays on the bf16 image
     int refused = 0;               // fragments the packer refused
   } packed[VC_PK_N + 1][3];
+  // on request (vc_request_w8_qkv_rows), layers 1..: the pairs of the 12-channel image Wqkv (option "w8q", vc_w8.h "w8q": 768 B of codes +
+  // two side bytes per pair, one per part; `refused` counts pairs).  A slot of its own: [PK_W8W][W13_QKV] belongs to the 16-channel planes
+  Packed w8q;
 };
 constexpr int PK_W8W = VC_PK_N;
 enum { W13_F2 = 0, W13_QKV = 1, W13_F1 = 2 };
@@ -238,6 +241,15 @@ struct vc_engine {
   // nothing more, has no such option and launches what it launched before.
   int w8ur_req = 0;
   int w8ur = 0;
+  // option "w8q": passes of finished rows whose QKV projection still launches rows_gemm_k<bf16_t, KTW, PRO_LNQ, EPI_QKV, ..> on the
+  // 12-channel image (the row counts past the paired consumer's, p.qp: 9..16 everywhere, 7 and 8 at d = 2048; with qkv_p8 < 2 also the
+  // lower ones) stream the QKV projection (4) of layers 1.. from the pairs of that image (rows_gemm_qkvq_w8_k: the same text with the
+  // pairs as the weight source, results bit-identical), where plan_pass takes the form; bit 8 = also at row counts the win table
+  // (w8q_rows_win) leaves out, for the A/B tool and the tests.  Only on an engine that asked for it after vc_request_w8
+  // (vc_request_w8_qkv_rows: w8q_req = 4), whatever its max_seqs: + 0.5 x the Wqkv image resident per packed layer (3 d^2 + d^2 / 128
+  // bytes: + 0.20 GB at giga830M).  Any other engine packs nothing more, has no such option and launches what it launched before.
+  int w8q_req = 0;
+  int w8q = 0;
   // option "kv8": decode passes read the cached positions older than the pass from an E4M3 copy of the K / V cache (Layer.kc8 / vc8 / sh8,
   // vc_kv8.h: one byte per value, one shift per cached row of a head - half the bytes of the launch that grows with the batch), which
   // one kv8_pack_k launch behind every pass keeps equal to the quantiser of the bf16 rows.  This changes values (3 mantissa bits), so:
@@ -353,6 +365,7 @@ struct PassPlan {
   bool wd_w8_f2;    // ... the FFN down-projection on the pair planes of a layer whose W2 is packed that way (rows_gemm_wds_w8_k, option w8w bit 1)
   bool wd_w8_qkv;   // ... the QKV projection on the pair planes of a layer whose Wqkv16 is packed that way (option w8w bit 4)
   bool lnq_w8_f1;   // finished rows behind a centred copy: the FFN up-projection on the pair planes of a layer whose W1 is packed that way (rows_gemm_lnq_w8_k, option w8ur bit 2)
+  bool qkvq_w8;     // finished rows behind a centred copy, past the paired consumer's row counts: the QKV projection on the pairs of the 12-channel image of a layer whose Wqkv is packed that way (rows_gemm_qkvq_w8_k, option w8q bit 4)
   bool wd_w8_f1;    // ... the FFN up-projection on the pair planes of a layer whose W1 is packed that way (rows_gemm_wds_w8u_k, option w8u bit 2)
   int ks_o, ks_f2;  // split-K slabs the out-projection / FFN down-projection leave (slab, wide and block forms)
   bool heads_wide;  // the heads run once over all rows on the wide-step kernels (option wide_heads)

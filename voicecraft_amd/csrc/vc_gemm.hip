@@ -145,7 +145,7 @@ hipError_t vc_launch_cast(const float* src, void* dst, long n, int dtype, hipStr
 // pipes per launch, queued IN FRONT of the 25-33 MB weight burst (round 5: in-kernel stamps, profiles/r04b_kernel_stamps_*).
 template <typename WT, int KTW, int PRO, int EPI, int NTW = 1, bool NT = true, bool R2 = false, int NP = VC_MAX_KSPLIT>
 __global__ __launch_bounds__(256 * NTW) void rows_gemm_k(const GemmArgs a) {
-  // The text is vc_gemm_rows_body.h (shared with rows_gemm_lnq_w8_k, vc_gemm_w8.hip); the weight source of this kernel: the image, KTW
+  // The text is vc_gemm_rows_body.h (shared with rows_gemm_lnq_w8_k and rows_gemm_qkvq_w8_k, vc_gemm_w8.hip); the weight source of this kernel: the image, KTW
   // 16-byte fragments per lane from a wave-uniform base, refilled per chunk.
 #define VC_ROWS_EARLY
 #define VC_ROWS_WDECL                                                                            \
@@ -389,10 +389,10 @@ int vc_gemm_fr1_ok(int N, int K, int dtype, int nw) {
 }
 const vc_packed_kind& vc_packed(int kind) {
   static const vc_packed_kind kinds[VC_PK_N] = {
-    {VC_W13_GROUP_FRAGS, VC_W13_GROUP_U4, VC_LC_W13, vc_launch_w13_pack, vc_launch_gemm_fr1_w13, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
+    {VC_W13_GROUP_FRAGS, VC_W13_GROUP_U4, VC_LC_W13, vc_launch_w13_pack, vc_launch_gemm_fr1_w13, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
     {VC_W8_GROUP_FRAGS, VC_W8_GROUP_U4, VC_LC_W8, vc_launch_w8_pack, vc_launch_gemm_fr1_w8, vc_launch_gemm_frp_w8, vc_launch_gemm_qp_w8,
      vc_gemm_frp_w8_ng, vc_gemm_qp_w8_ng, vc_launch_gemm_wd_w8, vc_gemm_wd_w8_ok, vc_launch_gemm_fr_w8, vc_gemm_fr_w8_ng,
-     vc_launch_gemm_lnq_w8, vc_gemm_lnq_w8_ok},
+     vc_launch_gemm_lnq_w8, vc_gemm_lnq_w8_ok, vc_launch_gemm_qkvq_w8, vc_gemm_qkvq_w8_ok},
   };
   return kinds[kind];
 }

@@ -1,6 +1,7 @@
 // vc_gemm_rows_body.h - the body of the decode-step rows GEMM, written once.  NOT a header of declarations: it is the text between the
-// braces of rows_gemm_k (vc_gemm.hip: bf16 / fp32 image) and rows_gemm_lnq_w8_k (vc_gemm_w8.hip: the FFN up-projection of 2..16
-// finished rows on the pair planes of vc_w8.h, block-scaled E4M3 bytes), in the manner of vc_gemm_fr_body.h / vc_gemm_wds_body.h
+// braces of rows_gemm_k (vc_gemm.hip: bf16 / fp32 image), rows_gemm_lnq_w8_k (vc_gemm_w8.hip: the FFN up-projection of 2..16
+// finished rows on the pair planes of vc_w8.h, block-scaled E4M3 bytes) and rows_gemm_qkvq_w8_k (there: the QKV projection of such rows
+// on the pairs of the 12-channel image), in the manner of vc_gemm_fr_body.h / vc_gemm_wds_body.h
 // (vc_gemm_fr1_body.h says why this is text and not a function template).  vc_gemm.hip describes the kernel in front of rows_gemm_k.
 //
 // The kernel supplies, in scope:

@@ -667,3 +667,182 @@ hipError_t vc_launch_gemm_lnq_w8(const GemmArgs& a, const uint4* planes, const u
     default: return hipErrorInvalidValue;
   }
 }
+
+// ------------------------------------------------------------------ the QKV projection of 2..16 finished rows on the pairs of the 12-channel image (option "w8q")
+// Past the row counts the paired consumer takes (rows_gemm_qp_k: 2..8 rows, 2..6 at d = 2048) site_qkv launches
+// rows_gemm_k<bf16_t, KTW, PRO_LNQ, EPI_QKV, NTW, NT, R2> on Wqkv, the 12-channel image: 48 slots of 16 bytes per (tile, k-tile).  Its
+// planes are the "w8q" pairs of vc_w8.h: k-tiles 2j, 2j + 1 of a tile = 768 B of codes, 16 bytes per slot, and two side bytes, one per
+// PART (the tile's channels on either side of the quantiser's 8-channel block boundary).
+// Packer: one wave per pair, lanes 48..63 idle (they take part in the reductions with neutral values and store nothing); image =
+// consecutive 768 B fragments (pair P = fragments 2 P, 2 P + 1), the tile of pair P is P / (KT / 2).  counts[0] += pairs refused.
+__global__ __launch_bounds__(64) void w8q_pack_k(const uint4* __restrict__ img, uint4* __restrict__ planes, unsigned char* __restrict__ side,
+                                                  int pairs_per_tile, unsigned int* __restrict__ counts) {
+  const long P = blockIdx.x;
+  const int u = threadIdx.x;
+  const bool on = u < VC_W8Q_SLOTS;
+  const int odd = (int)((P / pairs_per_tile) & 1);
+  const int part = vc_w8q_part(u % 12, odd);
+  uint32_t w[2][4];
+  int mn = 256, mx = -1;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const uint4 v = on ? img[(P * 2 + h) * VC_W8Q_SLOTS + u] : make_uint4(0u, 0u, 0u, 0u);
+    w[h][0] = v.x; w[h][1] = v.y; w[h][2] = v.z; w[h][3] = v.w;
+    int a, b;
+    vc_w8_minmax(w[h], &a, &b);
+    mn = a < mn ? a : mn;
+    mx = b > mx ? b : mx;
+  }
+  int shift[2], refused = 0;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {        // the two parts, each over its own lanes
+    const bool mine = on && part == q;
+    const int mnq = wave_min_i(mine ? mn : 256);
+    const int mxq = -wave_min_i(mine ? -mx : 1);
+    const int top = wave_sum_i(mine ? (vc_w8_top111(w[0], mxq) | vc_w8_top111(w[1], mxq)) : 0);
+    int ok;
+    shift[q] = vc_w8_shift(mnq, mxq, top, &ok);
+    refused |= ok ? 0 : 1;
+  }
+  uint32_t c[4];
+  const int bad = vc_w8w_encode_lane(w, part ? shift[1] : shift[0], c);
+  refused |= wave_sum_i(on ? bad : 0) > 0 ? 1 : 0;
+  if (on) planes[P * VC_W8Q_PAIR_U4 + u] = make_uint4(c[0], c[1], c[2], c[3]);
+  if (u < 2) side[P * 2 + u] = (unsigned char)vc_w8_side(u == 0 ? shift[0] : shift[1]);
+  if (u == 0 && refused) atomicAdd(counts, 1u);
+}
+// counts[1] += dwords that do not decode to the image's (the conversion the GEMM uses)
+__global__ __launch_bounds__(64) void w8q_check_k(const uint4* __restrict__ img, const uint4* __restrict__ planes,
+                                                   const unsigned char* __restrict__ side, int pairs_per_tile, unsigned int* __restrict__ counts) {
+  const long P = blockIdx.x;
+  const int u = threadIdx.x;
+  const bool on = u < VC_W8Q_SLOTS;
+  const int us = on ? u : 0;      // idle lanes re-read slot 0 and count nothing
+  const int odd = (int)((P / pairs_per_tile) & 1);
+  const uint4 pc = planes[P * VC_W8Q_PAIR_U4 + us];
+  const uint32_t c[4] = {pc.x, pc.y, pc.z, pc.w};
+  uint32_t w[2][4];
+  vc_w8w_decode_lane(c, side[P * 2 + vc_w8q_part(us % 12, odd)], w);
+  int bad = 0;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const uint4 v = img[(P * 2 + h) * VC_W8Q_SLOTS + us];
+    bad += (w[h][0] != v.x) + (w[h][1] != v.y) + (w[h][2] != v.z) + (w[h][3] != v.w);
+  }
+  bad = wave_sum_i(on ? bad : 0);
+  if (u == 0 && bad) atomicAdd(counts + 1, (unsigned int)bad);
+}
+// pair planes of a 12-channel bf16 image of KT k-tiles per tile (n_pairs = tiles x KT / 2)
+hipError_t vc_launch_w8q_pack(const uint4* img, long n_pairs, int KT, uint4* planes, unsigned char* side, unsigned int* counts, hipStream_t s) {
+  if (n_pairs <= 0 || n_pairs > 0x7fffffffL || KT < 2 || KT % 2 != 0 || n_pairs % (KT / 2) != 0) return hipErrorInvalidValue;
+  hipError_t err = hipMemsetAsync(counts, 0, 2 * sizeof(unsigned int), s);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(w8q_pack_k, dim3((unsigned int)n_pairs), dim3(64), 0, s, img, planes, side, KT / 2, counts);
+  hipLaunchKernelGGL(w8q_check_k, dim3((unsigned int)n_pairs), dim3(64), 0, s, img, (const uint4*)planes, (const unsigned char*)side, KT / 2, counts);
+  return hipGetLastError();
+}
+// The packer's text on a host buffer (no device): image12 = n_pairs x 1536 B of a 12-channel bf16 image of KT k-tiles per tile (pair P
+// belongs to tile P / (KT / 2)), planes = n_pairs x 768 B, side = n_pairs x 2 bytes; *refused_pairs = pairs with a part off the grid.
+extern "C" int vc_w8q_pack_host(const uint16_t* image12, long n_pairs, uint8_t* planes, uint8_t* side, int KT, int32_t* refused_pairs) {
+  if (!image12 || !planes || !side || !refused_pairs || n_pairs < 0 || KT < 2 || KT % 2 != 0 || n_pairs % (KT / 2) != 0) return -1;
+  int32_t nref = 0;
+  for (long P = 0; P < n_pairs; ++P) {
+    uint32_t img[2 * VC_W8Q_SLOTS * 4], codes[VC_W8Q_SLOTS * 4];
+    memcpy(img, image12 + P * (2 * VC_W8Q_SLOTS * 8), sizeof img);
+    nref += vc_w8q_encode_pair(img, (int)((P / (KT / 2)) & 1), codes, side + P * 2) ? 1 : 0;
+    memcpy(planes + P * VC_W8Q_PAIR_BYTES, codes, sizeof codes);
+  }
+  *refused_pairs = nref;
+  return 0;
+}
+
+// The kernel: the shared text (vc_gemm_rows_body.h) with TH = 12 and the pairs as the weight source, in the manner of rows_gemm_lnq_w8_k.
+// Wave w of a tile reads k-tiles kt0 + w KTW .. + KTW - 1: KTW / 2 whole, contiguous pairs and KTW contiguous side bytes.  A lane's slot
+// is the body's wslot = kg * 12 + min(m, 11): lanes with m >= 12 re-read slot 11 and the body zeroes their operand.  The lane's part
+// follows from its channel m and the tile's parity (with two tiles per workgroup the parity is the wave's tile, so it is wave-uniform).
+// X staging, statistics, row_mu_out, LDS layout, MFMA order, reduction and gemm_epilogue<EPI_QKV> (q to q_out, K / V straight into the
+// cache) are the image kernel's text and the operands are bit-identical, so every result is.  K = d in one chunk (host contract).
+// A kernel of its own name: rows_gemm_lnq_w8_k stays the nine FFN-up instantiations of option "w8ur".
+template <int KTW, int NTW, bool R2>
+__global__ __launch_bounds__(256 * NTW) void rows_gemm_qkvq_w8_k(const W8Args wa) {
+  using WT = bf16_t;
+  constexpr int PRO = PRO_LNQ, EPI = EPI_QKV, NP = VC_MAX_KSPLIT;
+  static_assert(KTW == 4 || KTW == 8 || KTW == 16, "pairs per wave and tile: 2, 4 or 8");
+  const GemmArgs& a = wa.g;
+  /* the wave's side bytes: scalar operands, first needed long after the burst is out */
+#define VC_ROWS_EARLY                                                                                                                  \
+  W8wSide<KTW> sd8;                                                                                                                    \
+  sd8.load(wa.side, (long)nt * a.KT + kt0 + wave * KTW);
+#define VC_ROWS_WDECL                                                                                                                  \
+  const uint4* pbase = wa.planes + (((long)nt * a.KT + kt0 + wave * KTW) >> 1) * VC_W8Q_PAIR_U4 + wslot;    /* wave-uniform + slot */  \
+  const int hi8 = (nt & 1) ? (m >= 4) : (m >= 8);      /* the lane's part */                                                           \
+  uint4 pw[KTW / 2];
+#define VC_ROWS_BURST                                                                                                                  \
+  _Pragma("unroll") for (int j = 0; j < KTW / 2; ++j)                                                                                  \
+    pw[j] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(pbase + (size_t)j * VC_W8Q_PAIR_U4))); \
+  /* the pins: the side words are on their way with n_active, not behind the `active == 0` exit */                                    \
+  _Pragma("unroll") for (int i = 0; i < W8wSide<KTW>::NSW; ++i) asm volatile("" : "+s"(sd8.w[i]));
+#define VC_ROWS_FRAG(i_) uint4 wfi = w8w_frag_at(pw[(i_) >> 1], (i_) & 1, sd8.scale_at((i_) >> 1, hi8));
+#define VC_ROWS_W(i_) wfi
+#define VC_ROWS_REFILL(c_)
+#include "vc_gemm_rows_body.h"
+}
+
+// The one statement of "a form exists" for the QKV projection of `rows` finished rows of an [N x K] matrix behind a centred copy: bf16,
+// 2..16 rows, whole 12-channel tiles, make_plan's k-tiles per wave 4, 8 or 16 in ONE chunk - K = 512, 1024, 2048 -, and an even tile
+// count where a workgroup takes two tiles (5 rows and up).  Returns the k-tiles per wave, 0 = no form.
+int vc_gemm_qkvq_w8_ok(int rows, int N, int K, int dtype) {
+  if (dtype != VC_DTYPE_BF16 || rows < 2 || rows > VC_ROWS || N < VC_TH_QKV || N % VC_TH_QKV != 0 || K < 32 || K % 32 != 0) return 0;
+  const int KT = K / 32;
+  int ktw = 16;
+  while (ktw > 2 && KT % (4 * ktw) != 0) ktw >>= 1;
+  if (KT != 4 * ktw || (ktw != 4 && ktw != 8 && ktw != 16)) return 0;
+  if (rows > 4 && (N / VC_TH_QKV) % 2 != 0) return 0;
+  return ktw;
+}
+
+template <int KTW, int NTW, bool R2>
+static hipError_t launch_qkvq_w8(const W8Args& wa, hipStream_t s) {
+  void (*kern)(const W8Args) = rows_gemm_qkvq_w8_k<KTW, NTW, R2>;
+  // the image launch's (launch_dec_nt, vc_gemm.hip): X rows, the reduction area per tile, statistics
+  const size_t lds = vc_gemm_lds_bytes(wa.g, VC_DTYPE_BF16, 1) + (size_t)(NTW - 1) * 4 * 64 * sizeof(f32x4);
+  if (lds > 64 * 1024) {
+    static size_t granted[16] = {0};   // per instantiation and device
+    int dev = 0;
+    if (hipError_t ge = hipGetDevice(&dev); ge != hipSuccess) return ge;
+    if (dev >= 0 && dev < 16 && lds > granted[dev]) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      granted[dev] = lds;
+    }
+  }
+  ++vc_launch_counts[VC_LC_ROWS_GEMM];         // the form the image kernel counts in
+  ++vc_launch_counts[VC_LC_W8_QKV_ROWS];
+  hipLaunchKernelGGL(kern, dim3(wa.g.n_tiles / NTW, 1, 1), dim3(256 * NTW), lds, s, wa);
+  return hipGetLastError();
+}
+template <int KTW>
+static hipError_t launch_qkvq_w8_form(const W8Args& wa, hipStream_t s) {
+  if (wa.g.mt == 4) return launch_qkvq_w8<KTW, 2, true>(wa, s);       // 9..16 rows: two tiles per workgroup, two rows per wave
+  if (wa.g.mt == 3) return launch_qkvq_w8<KTW, 2, false>(wa, s);      // 5..8 rows: two tiles per workgroup
+  return launch_qkvq_w8<KTW, 1, false>(wa, s);                        // 2..4 rows
+}
+// vc_launch_gemm(a, bf16, PRO_LNQ, EPI_QKV, 1, 1) on the pairs of a.Wp's 12-channel image (a.n_tiles tiles x a.KT k-tiles, packed whole
+// by vc_launch_w8q_pack): the same arguments, grid and LDS; a.mt picks the form as it does there.
+hipError_t vc_launch_gemm_qkvq_w8(const GemmArgs& a, const uint4* planes, const uint8_t* side, hipStream_t s) {
+  const int ktw = vc_gemm_qkvq_w8_ok(a.n_rows, a.N, a.K, VC_DTYPE_BF16);
+  if (!ktw || !planes || !side || a.x_in == nullptr || a.row_mu == nullptr || !a.q_out || !a.kcache || !a.vcache) return hipErrorInvalidValue;
+  if (a.KT != 4 * ktw || a.nchunk != 1 || a.n_tiles != a.N / VC_TH_QKV || a.r_lds < a.n_rows || a.r_lds > VC_ROWS) return hipErrorInvalidValue;
+  if (a.mt != (a.n_rows > VC_FR_MAX_ROWS ? 4 : a.n_rows >= 5 ? 3 : 0)) return hipErrorInvalidValue;      // (plan_pass's rule for these rows)
+  W8Args wa;
+  wa.g = a;
+  wa.g.x_upr_shift = -1; wa.g.att_q4_shift = -1;      // (prologues this kernel does not have)
+  wa.planes = planes;
+  wa.side = reinterpret_cast<const uint32_t*>(side);      // n_tiles x KT bytes, a wave's share whole aligned words
+  switch (ktw) {
+    case 4: return launch_qkvq_w8_form<4>(wa, s);
+    case 8: return launch_qkvq_w8_form<8>(wa, s);
+    case 16: return launch_qkvq_w8_form<16>(wa, s);
+    default: return hipErrorInvalidValue;
+  }
+}

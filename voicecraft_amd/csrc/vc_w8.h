@@ -1,7 +1,8 @@
 // vc_w8.h - "w8": bf16 weights that lie on a block-scaled 8-bit grid, stored as one OCP E4M3 (e4m3fn) byte per value plus one shift
 // byte per fragment.  Shared by the device packers and their checks (vc_gemm_w8.hip), the kernels that stream the planes, and the
 // host round-trip programs (tools/w8_check.cpp, tools/w8_wide_check.cpp): plain C++, no HIP type in any signature.  The second half
-// of the file is the same grid for the 16-channel images of wide steps, stored by PAIRS ("w8w").
+// of the file is the same grid for the 16-channel images of wide steps, stored by PAIRS ("w8w"), the third section the pairs of the
+// 12-channel QKV image ("w8q": tools/w8_qkv_check.cpp).
 //
 // Unit: the 512-value MFMA fragment one wave instruction loads (64 lanes x 8 bf16 = 64 lanes x four dwords; in matrix terms an aligned
 // block of 8 output channels x 64 inputs of the 8-channel-tile images, vc_gemm.hip pack_k).  A fragment is ON THE GRID when one integer
@@ -225,5 +226,69 @@ VC_W8_FN void vc_w8w_decode_pair(const uint32_t* codes, const uint8_t side[2], u
     vc_w8w_decode_lane(codes + l * 4, side[vc_w8w_half(l)], w);
     for (int h = 0; h < 2; ++h)
       for (int q = 0; q < 4; ++q) img[(h * 64 + l) * 4 + q] = w[h][q];
+  }
+}
+
+// ------------------------------------------------------------------ "w8q": the 12-channel image of the QKV projection, by PAIRS
+// rows_gemm_k's QKV form reads Wqkv in 12-channel tiles (vc_gemm.hip pack_k with th = 12): a (tile nt, k-tile kt) is 48 slots of 16
+// bytes, slot s = kg * 12 + m = channel 12 nt + m, inputs 32 kt + 8 kg .. + 7 - natural channel order, the values of the 8- and 16-channel
+// images.  A PAIR is k-tiles 2j, 2j + 1 of one tile: 12 channels x 64 inputs = 768 values, 1536 B of the image (two consecutive
+// fragments of 768 B).  A 12-channel tile straddles the quantiser's 8-channel blocks, so a pair has two PARTS, split at the block
+// boundary: an even tile's channels are 8 (a whole block) + 4 (the first four of the next block), an odd tile's 4 (the last four of
+// that block) + 8 (a whole block).  Each part is held to the rule at the top of the file (vc_w8_shift, vc_w8_encode_value, the NaN-code
+// exception) with the smallest shift that holds ITS values.  A subset of a block that is on the grid is on the grid at its own shift:
+// that shift is never larger than the block's, normal codes keep their three mantissa bits and denormal codes stay multiples of the
+// smaller step - so every pair of a quantised checkpoint packs.  Storage of a pair:
+//   768 B of codes: 16 bytes per slot = its eight codes of k-tile 2j (two dwords), then its eight of k-tile 2j + 1 (the lane layout
+//     w8w_frag decodes): one contiguous 16-byte-per-lane request of the wave's 48 lanes that carry a weight;
+//   2 side bytes: shift + 127 of part 0, then of part 1.
+// Pairs follow the image's order (tile major, then k), so a wave's KTW / 2 pairs of a tile are contiguous and so are their KTW side
+// bytes (whole aligned words for KTW >= 4).  Lossless, or the pair is refused.
+#define VC_W8Q_SLOTS 48
+#define VC_W8Q_PAIR_BYTES 768
+#define VC_W8Q_PAIR_U4 48
+
+// the part of channel m (0..11) of a tile of parity `odd`
+VC_W8_FN int vc_w8q_part(int m, int odd) { return odd ? (m >= 4 ? 1 : 0) : (m >= 8 ? 1 : 0); }
+
+// One whole pair in plain C++ (the host export vc_w8q_pack_host and tools/w8_qkv_check.cpp; the device packer runs the same per-lane text
+// with wave reductions over a part's lanes in place of the loops).  img = the pair's 2 x 48 x 4 dwords in image order, codes = 48 x 4
+// dwords, side = 2 bytes, odd = the tile's parity.  Returns a mask of the parts refused.
+VC_W8_FN int vc_w8q_encode_pair(const uint32_t* img, int odd, uint32_t* codes, uint8_t side[2]) {
+  int mn[2] = {256, 256}, mx[2] = {-1, -1}, top[2] = {0, 0}, shift[2], refused = 0;
+  for (int s = 0; s < VC_W8Q_SLOTS; ++s)
+    for (int h = 0; h < 2; ++h) {
+      int a, b;
+      vc_w8_minmax(img + (h * VC_W8Q_SLOTS + s) * 4, &a, &b);
+      const int part = vc_w8q_part(s % 12, odd);
+      mn[part] = a < mn[part] ? a : mn[part];
+      mx[part] = b > mx[part] ? b : mx[part];
+    }
+  for (int s = 0; s < VC_W8Q_SLOTS; ++s)
+    for (int h = 0; h < 2; ++h) {
+      const int part = vc_w8q_part(s % 12, odd);
+      top[part] |= vc_w8_top111(img + (h * VC_W8Q_SLOTS + s) * 4, mx[part]);
+    }
+  for (int part = 0; part < 2; ++part) {
+    int ok;
+    shift[part] = vc_w8_shift(mn[part], mx[part], top[part], &ok);
+    refused |= ok ? 0 : 1 << part;
+    side[part] = (uint8_t)vc_w8_side(shift[part]);
+  }
+  for (int s = 0; s < VC_W8Q_SLOTS; ++s) {
+    uint32_t w[2][4];
+    for (int h = 0; h < 2; ++h)
+      for (int q = 0; q < 4; ++q) w[h][q] = img[(h * VC_W8Q_SLOTS + s) * 4 + q];
+    const int part = vc_w8q_part(s % 12, odd);
+    if (vc_w8w_encode_lane(w, shift[part], codes + s * 4)) refused |= 1 << part;
+  }
+  return refused;
+}
+VC_W8_FN void vc_w8q_decode_pair(const uint32_t* codes, const uint8_t side[2], int odd, uint32_t* img) {
+  for (int s = 0; s < VC_W8Q_SLOTS; ++s) {
+    uint32_t w[2][4];
+    vc_w8w_decode_lane(codes + s * 4, side[vc_w8q_part(s % 12, odd)], w);
+    for (int h = 0; h < 2; ++h)
+      for (int q = 0; q < 4; ++q) img[(h * VC_W8Q_SLOTS + s) * 4 + q] = w[h][q];
   }
 }

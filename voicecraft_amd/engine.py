@@ -52,7 +52,7 @@ class VoiceCraftEngine:
     def __init__(self, args: Namespace | dict, state_dict: dict[str, torch.Tensor], device="cuda:0",
                  dtype="bf16", max_seqs: int = 8, max_positions: int = 4096, use_graph: bool = True, w8: str | None = None,
                  kv8: bool | str = False, w8_rows: bool = False, w8_wide: bool = False,
-                 w8_mid: bool = False, w8_up: bool = False, w8_up_rows: bool = False):
+                 w8_mid: bool = False, w8_up: bool = False, w8_up_rows: bool = False, w8_qkv_rows: bool = False):
         """kv8: False (default: nothing changes) | True | "centred" - decode passes of a bf16 engine read the cached K / V positions older than the pass
         as one E4M3 byte per value times a per-row shift (option `kv8`, csrc/vc_kv8.h, quant.kv8_quantize_rows): half the bytes of the
         launch that grows with the batch, 3 mantissa bits left of a cached value, 1.5 x the K/V memory.  Works with every call and `w8=`.
@@ -85,8 +85,15 @@ class VoiceCraftEngine:
         2..16 rows streams the same E4M3 pair planes (option `w8ur`, mask W8_UP_ROWS_MASK; d = 512 / 1024 / 2048), packed whatever
         max_seqs is: + 0.27 GB at giga830M on an engine that does not hold them for `w8_up` already, nothing next to it.  Bit-identical
         to the image launch on the same weights; launch_counts()["w8_up_rows"] counts them, w8_stats() says which layers have the
-        planes.  `w8="quantize"` quantises the third matrix as for w8_up.  Independent of w8_up, w8_wide, w8_rows, w8_mid and kv8."""
+        planes.  `w8="quantize"` quantises the third matrix as for w8_up.  Independent of w8_up, w8_wide, w8_rows, w8_mid and kv8.
+        w8_qkv_rows: False (default: nothing changes) | True, with `w8=` only (ValueError without it) - the QKV projection of the
+        finished-row passes that still read the 12-channel bf16 image (9..16 rows; 7 and 8 at d = 2048) streams E4M3 pairs of that image
+        for layers 1.. (option `w8q`, mask W8_QKV_ROWS_MASK; d = 512 / 1024 / 2048), packed whatever max_seqs is: + 0.20 GB at giga830M.
+        Bit-identical to the image launch on the same weights; launch_counts()["w8_qkv_rows"] counts them, w8_stats() says which
+        layers have the pairs.  No new matrix is quantised (QKV is one of W8_MATRICES).  Independent of the other w8 keywords and kv8."""
         self.lib = _lib.load()
+        if w8_qkv_rows and w8 is None:
+            raise ValueError('w8_qkv_rows=True streams planes on the grid of `w8=`: give w8="quantize" or w8="as_is" too')
         if w8_up_rows and w8 is None:
             raise ValueError('w8_up_rows=True streams planes on the grid of `w8=`: give w8="quantize" or w8="as_is" too')
         if w8_up and w8 is None:
@@ -156,6 +163,9 @@ class VoiceCraftEngine:
         self.w8_up_rows = bool(w8_up_rows)
         if w8_up_rows:
             check(self.lib.vc_request_w8_up_rows(self._h, self.W8_UP_ROWS_MASK), self._h, "vc_request_w8_up_rows")
+        self.w8_qkv_rows = bool(w8_qkv_rows)
+        if w8_qkv_rows:
+            check(self.lib.vc_request_w8_qkv_rows(self._h, self.W8_QKV_ROWS_MASK), self._h, "vc_request_w8_qkv_rows")
         self.kv8 = bool(kv8)
         self.kv8_centred = kv8 == "centred"
         if self.kv8_centred:
@@ -755,7 +765,8 @@ class VoiceCraftEngine:
         9..16-row passes (1, + 8 = also at row counts the measured table leaves out) behind that, one created with `w8_wide=True` w8w = those of 17..64-row
         steps (same bits, + 8 = also at row counts the measured table leaves out) behind that, one created with `w8_up=True` w8u = the
         FFN-up launches of 17..64-row steps (2, 10 = also at row counts the measured table leaves out) behind that, one created with
-        `w8_up_rows=True` w8ur = the FFN-up launches of 2..16-row passes (2, 10 likewise) behind that, one created with `kv8=True`
+        `w8_up_rows=True` w8ur = the FFN-up launches of 2..16-row passes (2, 10 likewise) behind that, one created with
+        `w8_qkv_rows=True` w8q = the QKV launches of finished-row passes on the 12-channel image (4, 12 likewise) behind that, one created with `kv8=True`
         appends kv8 = decode attention on the E4M3 copy of the K/V cache (1) or on the bf16 cache (0), one created with `kv8="centred"`
         kv8c = 1 behind it.
         bench.py turns it into a JSON object (`config.engine_options`)."""
@@ -777,6 +788,7 @@ class VoiceCraftEngine:
                     "kv8_attn", "kv8_pack", "kv8c_centre", "kv8c_attn", "kv8c_pack", "w8_rows", "w8_wide", "w8_mid", "w8_up")
 
     LAUNCH_FORMS_MORE = ("w8_up_rows",)     # the census slots behind LAUNCH_FORMS (vc_debug_read "launch_counts_more")
+    LAUNCH_FORMS_MORE2 = ("w8_qkv_rows",)   # ... and behind those (vc_debug_read "launch_counts_more2"): the tuples above are pinned by tests
 
     def launch_counts(self) -> dict:
         """Process-wide census of the kernel FORMS launched so far (vc_common.h VC_LC_*): the parity tests take the
@@ -784,11 +796,14 @@ class VoiceCraftEngine:
         weights IN ADDITION to their form's slot: w8 the one-row launches, w8_rows those of 2..8-row steps (rows_gemm_frp / rows_gemm_qp),
         w8_wide those of 17..64-row steps (also in wd), w8_mid the FFN-down launches of 9..16-row passes (also in rows_gemm_fr),
         w8_up the FFN-up launches of 17..64-row steps (also in wd, not in w8_wide), w8_up_rows the FFN-up launches of 2..16-row passes
-        (also in rows_gemm).  The slots behind LAUNCH_FORMS (LAUNCH_FORMS_MORE) are a second read, merged into the same dict."""
+        (also in rows_gemm), w8_qkv_rows the QKV launches of finished-row passes on the pairs of the 12-channel image (also in
+        rows_gemm).  The slots behind LAUNCH_FORMS (LAUNCH_FORMS_MORE, LAUNCH_FORMS_MORE2) are further reads, merged into the same dict."""
         c = self.debug_read("launch_counts", (len(self.LAUNCH_FORMS),), torch.int64)
         out = {n: int(c[i]) for i, n in enumerate(self.LAUNCH_FORMS)}
         m = self.debug_read("launch_counts_more", (len(self.LAUNCH_FORMS_MORE),), torch.int64)
         out.update({n: int(m[i]) for i, n in enumerate(self.LAUNCH_FORMS_MORE)})
+        m = self.debug_read("launch_counts_more2", (len(self.LAUNCH_FORMS_MORE2),), torch.int64)
+        out.update({n: int(m[i]) for i, n in enumerate(self.LAUNCH_FORMS_MORE2)})
         return out
 
     W13_MATRICES = ("ffn_down", "qkv")
@@ -810,6 +825,7 @@ class VoiceCraftEngine:
     W8_WIDE_MASK = 5                        # option `w8w` of an engine created with w8_wide=True
     W8_UP_MASK = 2                          # option `w8u` of an engine created with w8_up=True (FFN-up)
     W8_UP_ROWS_MASK = 2                     # option `w8ur` of an engine created with w8_up_rows=True (FFN-up)
+    W8_QKV_ROWS_MASK = 4                    # option `w8q` of an engine created with w8_qkv_rows=True (QKV)
 
     def w8_stats(self) -> list:
         """w13_stats() for option `w8`: per layer {"ffn_down" | "qkv": {"state": "packed" | "refused" | "not_applicable",
@@ -818,7 +834,8 @@ class VoiceCraftEngine:
         An engine created with `w8_wide=True` adds "ffn_down_wide" / "qkv_wide": the pair planes of the 16-channel images that 17..64-row
         steps stream, {"state": ..., "refused_pairs": n} (not_applicable: max_seqs <= 16, or a K slice without the form); one created
         with `w8_up=True` adds "ffn_up_wide", the same for the FFN up-projection's image; one created with `w8_up_rows=True` adds
-        "ffn_up_rows", the same planes as passes of 2..16 rows see them (not_applicable: a width without the form)."""
+        "ffn_up_rows", the same planes as passes of 2..16 rows see them (not_applicable: a width without the form); one created with
+        `w8_qkv_rows=True` adds "qkv_rows", the pairs of the 12-channel QKV image (not_applicable: layer 0, or a width without the form)."""
         L = int(self.args.num_decoder_layers)
         v = self.debug_read("w8_stats", (L, 2, 2), torch.int32).tolist()
         out = [{m: {"state": self.W13_STATES[v[l][i][0]], "refused_fragments": v[l][i][1]} for i, m in enumerate(self.W8_MATRICES)}
@@ -836,6 +853,10 @@ class VoiceCraftEngine:
             u = self.debug_read("w8ur_stats", (L, 2), torch.int32).tolist()
             for l in range(L):
                 out[l]["ffn_up_rows"] = {"state": self.W13_STATES[u[l][0]], "refused_pairs": u[l][1]}
+        if self.w8_qkv_rows:
+            u = self.debug_read("w8q_stats", (L, 2), torch.int32).tolist()
+            for l in range(L):
+                out[l]["qkv_rows"] = {"state": self.W13_STATES[u[l][0]], "refused_pairs": u[l][1]}
         return out
 
     def debug_read(self, name: str, shape, dtype=torch.float32) -> torch.Tensor:

@@ -123,6 +123,22 @@ def w8w_decode(planes: torch.Tensor, side: torch.Tensor) -> torch.Tensor:
     return torch.ldexp(q, shift[:, None, :, None]).float()
 
 
+# ---- "w8q": the pairs of the 12-channel QKV image that finished-row passes stream (csrc/vc_w8.h) ---------------------------------------
+def w8q_decode(planes: torch.Tensor, side: torch.Tensor, kt: int) -> torch.Tensor:
+    """The stated layout of a pair, read back: planes uint8 [n_pairs, 768] - 16 bytes per slot, slot s = kg * 12 + m (channel m of the
+    tile, inputs 8 kg .. + 7 of a k-tile) holding its eight codes of k-tile 2j then its eight of k-tile 2j + 1 - and side uint8
+    [n_pairs, 2] - shift + 127 of part 0, of part 1 -> fp32 [n_pairs, 2, 48, 8]: k-tile of the pair, slot, value.  kt = k-tiles per tile:
+    pair P belongs to tile P // (kt // 2).  The parts split a tile's 12 channels at the quantiser's 8-channel block boundary: an even
+    tile's part 1 is m >= 8, an odd tile's m >= 4."""
+    n = planes.shape[0]
+    q = planes.contiguous().view(torch.float8_e4m3fn).float().double().reshape(n, 48, 2, 8).permute(0, 2, 1, 3)
+    m = torch.arange(48) % 12
+    odd = ((torch.arange(n) // (kt // 2)) & 1).bool()
+    part = torch.where(odd[:, None], m[None, :] >= 4, m[None, :] >= 8).long()          # [n_pairs, 48]
+    shift = torch.gather(side.to(torch.int32), 1, part) - 127
+    return torch.ldexp(q, shift[:, None, :, None]).float()
+
+
 # ---- "kv8": cached K / V rows on the same grid, the block being one head's row of hd values (csrc/vc_kv8.h) -----------------------------
 def kv8_quantize_rows(x: torch.Tensor):
     """bf16-valued rows [..., hd] -> (codes uint8 [..., hd], shift int8 [...]): value ~ q * 2**shift, q the float8_e4m3fn number the code
