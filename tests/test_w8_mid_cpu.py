@@ -12,7 +12,7 @@ from voicecraft_amd import _lib
 from test_w8_rows_cpu import WIDTHS, cfg, image_plan, w8r_plan
 
 MASKS = (0, 1, 8, 9)
-# the row counts at which the form is taken without bit 8 where it exists (csrc/vc_engine.hip w8m_rows_win, from profiles/w8_mid_ab.log)
+# the row counts at which the form is taken without bit 8 where it exists (csrc/vc_engine_host.h W8_FORMS, row `w8m`, from profiles/w8_mid_ab.log)
 ROWS_WIN = range(9, 17)      # measured at 9, 12 and 16 rows, every whole range below zero; the counts between follow the nearest
 # d: (kernel: 1 = X in one piece, 2 = K in two halves; groups per wave and piece)
 FORMS = {512: (1, 1), 1024: (1, 2), 2048: (2, 2)}

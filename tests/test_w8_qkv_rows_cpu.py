@@ -22,7 +22,7 @@ from test_w8_up_rows_cpu import w8ur_plan
 from test_w8_wide_cpu import OFF_GRID, ROOT, WIDTHS, cfg, image_plan, isa, w8w_plan      # (isa: tools/isa_store_scan.py)
 
 MASKS = (0, 4, 12)
-# the row counts at which the form is taken without bit 8 where it exists (csrc/vc_engine.hip w8q_rows_win, from profiles/w8_qkv_rows_ab.log)
+# the row counts at which the form is taken without bit 8 where it exists (csrc/vc_engine_host.h W8_FORMS, row `w8q`, from profiles/w8_qkv_rows_ab.log)
 ROWS_WIN = range(5, 17)       # 5..8: measured at 7 and 8 (two tiles per workgroup); 9..16: at 9, 12, 16; 2..4 (one tile) were not measured
 KTW = {512: 4, 1024: 8, 2048: 16}                 # K = d over the four waves of a tile, in k-tiles of 32 inputs, one chunk
 

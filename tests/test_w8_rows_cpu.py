@@ -12,7 +12,7 @@ from voicecraft_amd._lib import ModelCfg
 
 WIDTHS = [(d, h) for d in range(256, 2049, 256) for h in (d // 32, d // 64, d // 128) if h >= 1 and d % h == 0 and d // h in (32, 64, 128)]
 MASKS = (0, 1, 4, 5)
-# the row counts at which the forms are taken where they exist (csrc/vc_engine.hip w8r_rows_win, from profiles/w8_rows_ab.log)
+# the row counts at which the forms are taken where they exist (csrc/vc_engine_host.h W8_FORMS, row `w8r`, from profiles/w8_rows_ab.log)
 ROWS_FFN_DOWN = range(2, 9)
 ROWS_QKV = range(2, 7)       # rows_gemm_qp_k itself stops at 6 rows at d = 2048
 

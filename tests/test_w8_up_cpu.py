@@ -13,7 +13,7 @@ from voicecraft_amd import _lib, quant, synth
 from test_w8_wide_cpu import OFF_GRID, WIDTHS, cfg, image16, image_plan, pack_host, w8w_plan
 
 MASKS = (0, 2, 10)
-# the row counts at which the form is taken without bit 8 where it exists (csrc/vc_engine.hip w8u_rows_win, from profiles/w8_up_ab.log)
+# the row counts at which the form is taken without bit 8 where it exists (csrc/vc_engine_host.h W8_FORMS, row `w8u`, from profiles/w8_up_ab.log)
 ROWS_FFN_UP = range(17, 65)
 KPW = {512: 2, 1024: 4, 2048: 8}                  # K = d over eight waves, in k-tiles of 32 inputs
 

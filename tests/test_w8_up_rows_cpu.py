@@ -16,7 +16,7 @@ from test_w8_up_cpu import w8u_plan
 from test_w8_wide_cpu import ROOT, WIDTHS, cfg, image_plan, isa, w8w_plan      # (isa: tools/isa_store_scan.py)
 
 MASKS = (0, 2, 10)
-# the row counts at which the form is taken without bit 8 where it exists (csrc/vc_engine.hip w8ur_rows_win, from profiles/w8_up_rows_ab.log)
+# the row counts at which the form is taken without bit 8 where it exists (csrc/vc_engine_host.h W8_FORMS, row `w8ur`, from profiles/w8_up_rows_ab.log)
 ROWS_WIN = range(2, 17)
 KTW = {512: 4, 1024: 8, 2048: 16}                 # K = d over the four waves of a tile, in k-tiles of 32 inputs, one chunk
 

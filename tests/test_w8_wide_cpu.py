@@ -22,7 +22,7 @@ import isa_store_scan as isa  # noqa: E402
 
 MASKS = (0, 1, 4, 5)
 OFF_GRID = (1.0 + 2.0 ** -7) * 2.0 ** -6          # eight significant bits: on no E4M3 grid
-# the row counts at which the forms are taken without bit 8 where they exist (csrc/vc_engine.hip w8w_rows_win, from profiles/w8_wide_ab.log)
+# the row counts at which the forms are taken without bit 8 where they exist (csrc/vc_engine_host.h W8_FORMS, row `w8w`, from profiles/w8_wide_ab.log)
 ROWS_FFN_DOWN = range(17, 65)
 ROWS_QKV = range(17, 65)
 

@@ -6,8 +6,8 @@ says) against `w8m = 0`, whose launches are the parent commit's machine code (pr
   - the decode loop of a 16-utterance inference_tts_multi at bench.py's shapes (650 generated frames per utterance) with `w8r` and
     `w8w` on in both legs (the terminator is muted, so all 16 rows run to the end and neither of the two has a step to take).
 Every line holds the median of the per-pair deltas and their min..max: plan_pass takes the form at a row count only where the whole
-range of that count's decode-loop line is below zero, an unmeasured count following the nearest measured one (csrc/vc_engine.hip
-w8m_rows_win).  JSON lines on stdout.
+range of that count's decode-loop line is below zero, an unmeasured count following the nearest measured one (csrc/vc_engine_host.h W8_FORMS,
+row `w8m`).  JSON lines on stdout.
 usage: python tools/w8_mid_ab.py [pairs = 7] > profiles/w8_mid_ab.log"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -5,7 +5,7 @@ checkpoint of tools/w8_ab.py): interleaved pairs of `w8r = mask` against `w8r = 
   - the captured decode loop per step of inference_tts_multi with 2, 3, 4, 6 and 8 utterances, one line per mask 1 / 4 / 5,
   - the decode loop of inference_tts_batch(batch_size=3) and of an 8-utterance inference_tts_multi at bench.py's shapes.
 Every line holds the median of the per-pair deltas and their min..max: plan_pass takes the form at a row count only where the whole
-range of the bit's decode-loop line is below zero (csrc/vc_engine.hip w8r_rows_win).  JSON lines on stdout.
+range of the bit's decode-loop line is below zero (csrc/vc_engine_host.h W8_FORMS, row `w8r`).  JSON lines on stdout.
 usage: python tools/w8_rows_ab.py [pairs = 7] > profiles/w8_rows_ab.log"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

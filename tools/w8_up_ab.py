@@ -7,7 +7,7 @@ synthetic checkpoint with THREE matrices on the grid: quant.quantize_state_dict_
   - the captured decode loop per step of inference_tts_multi with 17, 24, 32, 33, 48 and 64 utterances, `w8w = 0` in both legs (FFN-up
     alone), then `w8w = 13` in both legs (next to the FFN-down and QKV planes),
   - the same at 32 and 64 utterances on a second engine that has kv8=True (and no w8_wide).
-Every line holds the median of the per-pair deltas and their min..max: a row count stays in w8u_rows_win (csrc/vc_engine.hip) only
+Every line holds the median of the per-pair deltas and their min..max: a row count stays in row `w8u` of W8_FORMS (csrc/vc_engine_host.h) only
 where the whole range of its FFN-up-alone line AND of its next-to-w8w line is below zero; row counts between measured ones follow the
 nearest measured count of the same number of row tiles (17..32, 33..64).  JSON lines on stdout.
 usage: python tools/w8_up_ab.py [pairs = 7] > profiles/w8_up_ab.log"""

@@ -8,7 +8,7 @@ is the baseline.  Logits of forced calls at every measured row count are asserte
     `w8r` and `w8m` on in both legs (the terminator is muted, so all rows run to the end).
 Every line holds the median of the per-pair deltas and their min..max: plan_pass takes the form at a row count only where the whole
 range of that count's decode-loop line is below zero, an unmeasured count following the nearest measured one of the same kernel form
-(2..4, 5..8, 9..16 rows; csrc/vc_engine.hip w8ur_rows_win).  JSON lines on stdout.
+(2..4, 5..8, 9..16 rows; csrc/vc_engine_host.h W8_FORMS, row `w8ur`).  JSON lines on stdout.
 usage: python tools/w8_up_rows_ab.py [pairs = 7] > profiles/w8_up_rows_ab.log"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

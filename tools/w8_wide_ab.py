@@ -4,8 +4,8 @@ says) against `w8w = 0`, whose launches are the parent commit's machine code (pr
 17-, 33- and 64-row calls are asserted equal between the legs first.  Then
   - the captured decode loop per step of inference_tts_multi with 17, 24, 32, 33, 48 and 64 utterances, one line per mask 1 / 4 / 5,
   - the same at 32 and 64 utterances, mask 5, on a second engine that also has kv8=True.
-Every line holds the median of the per-pair deltas and their min..max: a (matrix, row count) stays in w8w_rows_win
-(csrc/vc_engine.hip) only where the whole range of its line is below zero; row counts between measured ones follow the nearest
+Every line holds the median of the per-pair deltas and their min..max: a (matrix, row count) stays in row `w8w` of W8_FORMS
+(csrc/vc_engine_host.h) only where the whole range of its line is below zero; row counts between measured ones follow the nearest
 measured count of the same number of row tiles (17..32, 33..64).  The isolated launches of the two sites (vc_bench_kernel "wd_ffn2",
 "wd_qkv": eager, back to back, iteration i on the weights of layer i % L) at 32 and 64 rows come first.  JSON lines on stdout.
 usage: python tools/w8_wide_ab.py [pairs = 7] > profiles/w8_wide_ab.log"""

@@ -100,64 +100,20 @@ int pack_folded(vc_engine* e, const std::string& wkey, const std::string& bkey, 
   return VC_OK;
 }
 
-// The packed form `kind` (VC_PK_*: 13-bit planes, E4M3 bytes) of an already packed bf16 image of `n_frags` 1 KB fragments: packed
-// and checked on the device, the w8 form with the conversion its kernels use.  A fragment the codes cannot hold (non-zero exponents that
-// span more than the 13-bit codes do, a value off the 8-bit grid), or any dword that does not decode to the image's, refuses the matrix
-// (state 2: the planes are dropped, the launch stays on the image).
-int pack_planes(vc_engine* e, Layer& ly, int kind, int which, const uint4* image, long n_frags) {
+// One packed form of an already packed bf16 image into slot `p`: `planes_u4` 16-byte units of codes and `side_words` words of side
+// bytes, packed and checked on the device by `launch` (the kind's pack and check kernels; the w8 kinds check with the conversion their
+// GEMMs use).  A unit the codes cannot hold (non-zero exponents that span more than the 13-bit codes do, a value off the 8-bit grid:
+// `refused` counts fragments, or pairs), or any dword that does not decode to the image's, refuses the matrix for this layer (state 2:
+// the planes are dropped, the launch stays on the image).
+template <class Launch>
+int pack_checked(vc_engine* e, Layer::Packed& p, size_t planes_u4, size_t side_words, Launch launch) {
   if (!e->w13_counts) { int rc = dalloc(e, &e->w13_counts, (size_t)4); if (rc) return rc; }
-  const vc_packed_kind& pk = vc_packed(kind);
-  Layer::Packed& p = ly.packed[kind][which];
   const size_t mark = e->allocs.size();
   const double bytes0 = e->bytes_total;
   int rc;
-  if ((rc = dalloc(e, &p.planes, (size_t)(n_frags / pk.group_frags) * pk.group_u4))) return rc;
-  if ((rc = dalloc(e, &p.side, (size_t)(n_frags / 4)))) return rc;
-  HIPCHK(e, pk.pack(image, n_frags, p.planes, reinterpret_cast<unsigned char*>(p.side), e->w13_counts, 0));
-  unsigned int cnt[2] = {0, 0};
-  HIPCHK(e, hipMemcpy(cnt, e->w13_counts, sizeof cnt, hipMemcpyDeviceToHost));
-  p.refused = (int)cnt[0];
-  if (cnt[0] == 0 && cnt[1] == 0) { p.state = 1; return VC_OK; }
-  p.state = 2;
-  while (e->allocs.size() > mark) { (void)hipFree(e->allocs.back()); e->allocs.pop_back(); }
-  e->bytes_total = bytes0;
-  p.planes = nullptr; p.side = nullptr;
-  return VC_OK;
-}
-
-// The pair planes (vc_w8.h "w8w", slot PK_W8W) of a 16-channel bf16 image of `n_pairs` pairs: pack_planes for the wide kernel's images.
-// A pair with a half off the grid, or any dword that does not decode to the image's, refuses the matrix for this layer.
-int pack_pairs(vc_engine* e, Layer& ly, int which, const uint4* image, long n_pairs) {
-  if (!e->w13_counts) { int rc = dalloc(e, &e->w13_counts, (size_t)4); if (rc) return rc; }
-  Layer::Packed& p = ly.packed[PK_W8W][which];
-  const size_t mark = e->allocs.size();
-  const double bytes0 = e->bytes_total;
-  int rc;
-  if ((rc = dalloc(e, &p.planes, (size_t)n_pairs * VC_W8W_PAIR_U4))) return rc;
-  if ((rc = dalloc(e, &p.side, (size_t)(n_pairs + 1) / 2))) return rc;      // two bytes per pair
-  HIPCHK(e, vc_launch_w8w_pack(image, n_pairs, p.planes, reinterpret_cast<unsigned char*>(p.side), e->w13_counts, 0));
-  unsigned int cnt[2] = {0, 0};
-  HIPCHK(e, hipMemcpy(cnt, e->w13_counts, sizeof cnt, hipMemcpyDeviceToHost));
-  p.refused = (int)cnt[0];
-  if (cnt[0] == 0 && cnt[1] == 0) { p.state = 1; return VC_OK; }
-  p.state = 2;
-  while (e->allocs.size() > mark) { (void)hipFree(e->allocs.back()); e->allocs.pop_back(); }
-  e->bytes_total = bytes0;
-  p.planes = nullptr; p.side = nullptr;
-  return VC_OK;
-}
-
-// The pairs (vc_w8.h "w8q", slot Layer::w8q) of the 12-channel image Wqkv of KT k-tiles per tile: pack_pairs for the QKV projection of
-// finished-row passes.  A pair with a part off the grid, or any dword that does not decode to the image's, refuses the layer.
-int pack_pairs12(vc_engine* e, Layer& ly, long n_pairs, int KT) {
-  if (!e->w13_counts) { int rc = dalloc(e, &e->w13_counts, (size_t)4); if (rc) return rc; }
-  Layer::Packed& p = ly.w8q;
-  const size_t mark = e->allocs.size();
-  const double bytes0 = e->bytes_total;
-  int rc;
-  if ((rc = dalloc(e, &p.planes, (size_t)n_pairs * VC_W8Q_PAIR_U4))) return rc;
-  if ((rc = dalloc(e, &p.side, (size_t)(n_pairs + 1) / 2))) return rc;      // two bytes per pair
-  HIPCHK(e, vc_launch_w8q_pack(ly.Wqkv, n_pairs, KT, p.planes, reinterpret_cast<unsigned char*>(p.side), e->w13_counts, 0));
+  if ((rc = dalloc(e, &p.planes, planes_u4))) return rc;
+  if ((rc = dalloc(e, &p.side, side_words))) return rc;
+  HIPCHK(e, launch(p.planes, reinterpret_cast<unsigned char*>(p.side), e->w13_counts));
   unsigned int cnt[2] = {0, 0};
   HIPCHK(e, hipMemcpy(cnt, e->w13_counts, sizeof cnt, hipMemcpyDeviceToHost));
   p.refused = (int)cnt[0];
@@ -250,67 +206,6 @@ enum { ATT_ROWS = 0, ATT_TILE = 1, ATT_TILE64 = 2 };                 // rows_att
 // workgroups): from this many rows on, a per-row LayerNorm launch plus the plain prologue is cheaper (8 rows 20 us -> ~12 us per GEMM).
 constexpr int ln_split_rows = 3;
 
-// Option "w8r": the row counts at which the w8 form of matrix `which` measured faster than the image over the whole paired range; a
-// row count whose range touches zero would stay on the image.  profiles/w8_rows_ab.log (giga830M, 7 interleaved pairs per line,
-// captured decode loop per step, min..max of the pairs): FFN-down alone -6.3 .. -5.8 % at 2, 3, 4, 6 and 8 rows, QKV alone -4.4 .. -5.0 %
-// at 2, 3, 4 and 6 rows (rows_gemm_qp_k stops at 6 rows at d = 2048), both -10.8 .. -11.0 %: every row count of both bits takes the form.
-bool w8r_rows_win(int which, int rows) {
-  (void)which;
-  return rows >= 2 && rows <= 8;
-}
-
-
-// Option "w8w": the row counts at which the pair-plane form of matrix `which` measured faster than the image over the whole paired
-// range; row counts between measured ones follow the nearest measured count of the same RT (17..32, 33..64).
-// profiles/w8_wide_ab.log (tools/w8_wide_ab.py: giga830M, 7 interleaved pairs per line, captured decode loop per step, min..max of the
-// pairs) at 17, 24, 32 | 33, 48, 64 rows: FFN-down alone -4.9 .. -3.5 % | -3.6 .. -2.9 %, QKV alone -3.1 .. -2.9 % | -2.3 .. -2.0 %, both
-// -7.9 .. -7.3 % | -5.6 .. -5.2 %: every measured row count of both bits has its whole range below zero, so every wide row count
-// takes the form.
-bool w8w_rows_win(int which, int rows) {
-  (void)which;
-  return rows > VC_ROWS && rows <= VC_MAX_SEQS;
-}
-
-// Option "w8u": the row counts at which the pair-plane form of the FFN up-projection measured faster than the image over the whole
-// paired range; row counts between measured ones follow the nearest measured count of the same RT (17..32, 33..64).
-// profiles/w8_up_ab.log (tools/w8_up_ab.py: giga830M, 7 interleaved pairs per line, captured decode loop per step, min..max of the
-// pairs) at 17, 24, 32 | 33, 48, 64 rows: FFN-up alone -4.4 .. -4.0 % | -3.1 .. -2.6 %, next to `w8w` = 13 -4.9 .. -4.2 % | -3.3 .. -2.9 %,
-// with kv8 -4.2 .. -4.1 % at 32 rows and -2.9 .. -2.8 % at 64: every measured row count has its whole range below zero, so every wide
-// row count takes the form.
-bool w8u_rows_win(int rows) {
-  return rows > VC_ROWS && rows <= VC_MAX_SEQS;
-}
-
-// Option "w8ur": the row counts of 2..16 at which the pair-plane form of the FFN up-projection measured faster than the image over the
-// whole paired range; a count that was not measured follows the nearest measured one of the same kernel form (2..4, 5..8, 9..16 rows).
-// profiles/w8_up_rows_ab.log (tools/w8_up_rows_ab.py: giga830M, 7 interleaved pairs per line, captured decode loop per step, min..max of
-// the pairs) at 2, 4 | 5, 8 | 9, 12, 16 rows: -7.9 .. -7.5 % | -5.6 .. -4.9 % | -4.2 .. -3.7 %, and -5.3 % / -3.7 % for 8 / 16 utterances at
-// the benchmark's shapes with `w8r` and `w8m` on: every measured row count has its whole range below zero, so every row count 2..16
-// takes the form.
-bool w8ur_rows_win(int rows) {
-  return rows >= 2 && rows <= VC_ROWS;
-}
-
-// Option "w8q": the row counts at which the pair form of the QKV projection's 12-channel image measured faster than the image over the
-// whole paired range; a count that was not measured follows the nearest measured one of the same kernel form (2..4, 5..8, 9..16 rows).
-// profiles/w8_qkv_rows_ab.log (tools/w8_qkv_rows_ab.py: giga830M, 7 interleaved pairs per line, captured decode loop per step, min..max of
-// the pairs) at 7, 8 | 9, 12, 16 rows: -2.8 .. -2.6 % | -1.8 .. -1.5 %, and -1.6 .. -1.5 % for 16 utterances at the benchmark's shapes with
-// `w8r`, `w8m` and `w8ur` on: every measured row count has its whole range below zero, so 5..8 rows (two tiles per workgroup) and 9..16
-// rows (two rows per wave as well) take the form where the 12-channel image serves them.  No count of the one-tile form (2..4 rows, which
-// the image serves with `qkv_p8` below 2 only) was measured: those stay out and reach the kernel through bit 8.
-bool w8q_rows_win(int rows) {
-  return rows >= 5 && rows <= VC_ROWS;
-}
-
-// Option "w8m": the row counts of 9..16 at which the w8 form of the FFN down-projection measured faster than the image over the whole
-// paired range; a count that was not measured follows the nearest measured one.  profiles/w8_mid_ab.log (tools/w8_mid_ab.py: giga830M,
-// 7 interleaved pairs per line, captured decode loop per step, min..max of the pairs) at 9, 12, 16 rows: -5.3 .. -5.2 %, -5.0 .. -4.9 %,
-// -5.2 .. -5.2 %, and -4.8 .. -4.7 % for 16 utterances at the benchmark's shapes with `w8r` and `w8w` on: every measured row count has
-// its whole range below zero, so every row count 9..16 takes the form.
-bool w8m_rows_win(int rows) {
-  return rows > VC_FR_MAX_ROWS && rows <= VC_ROWS;
-}
-
 }  // namespace
 namespace vch __attribute__((visibility("hidden"))) {
 // decode: a decode step (n_active set).  tiled: a prefill pass whose 16-row tiles (1) or 64-row blocks (2) each hold consecutive
@@ -361,20 +256,20 @@ PassPlan plan_pass(const vc_engine* e, int rows, bool decode, int tiled) {
     // option "w8r": the two paired launches on the E4M3 bytes, where the launcher has a form for these rows (a wave's fragments per
     // tile whole groups: FFN-down at d = 512 / 1024 / 2048, QKV at d = 2048).  The sites take it for the layers whose matrix is packed.
     const vc_packed_kind& pk8 = vc_packed(VC_PK_W8);
-    p.frp_w8 = p.frp && (e->w8r & W8_BITS[W13_F2]) && w8r_rows_win(W13_F2, rows) && pk8.frp_ng(rows, d, 4 * d, e->dtype) != 0;
-    p.qp_w8 = p.qp && (e->w8r & W8_BITS[W13_QKV]) && w8r_rows_win(W13_QKV, rows) && pk8.qp_ng(rows, 3 * d, d, e->dtype) != 0;
+    p.frp_w8 = p.frp && (e->w8r & W8_BITS[W13_F2]) && w8_rows_win(W8F_ROWS, rows) && pk8.frp_ng(rows, d, 4 * d, e->dtype) != 0;
+    p.qp_w8 = p.qp && (e->w8r & W8_BITS[W13_QKV]) && w8_rows_win(W8F_ROWS, rows) && pk8.qp_ng(rows, 3 * d, d, e->dtype) != 0;
     // option "w8m": past 8 rows the paired producer stops (vc_gemm_frp_ok) and FFN-down runs on rows_gemm_fr_k / rows_gemm_fr2_k; their
     // w8 twins where a wave's k-tiles per piece are whole groups (d = 512 / 1024 / 2048).  The site takes it for the layers whose
     // matrix is packed.
     p.fr_w8_f2 = !p.frp && rows > VC_FR_MAX_ROWS && rows <= VC_ROWS && (e->w8m & W8_BITS[W13_F2]) && pk8.fr_ng(rows, d, 4 * d, e->dtype) != 0 &&
-                 (w8m_rows_win(rows) || (e->w8m & 8));
+                 (w8_rows_win(W8F_MID, rows) || (e->w8m & 8));
     // option "w8ur": the FFN up-projection behind a centred copy on the pair planes of W1, where the launcher has a form for these rows
     // (K = d in one chunk of 4, 8 or 16 k-tiles per wave: d = 512 / 1024 / 2048).  The site takes it for the layers whose W1 is packed.
-    p.lnq_w8_f1 = p.hq && (e->w8ur & W8_BITS[W13_F1]) && pk8.lnq_ok(rows, 4 * d, d, e->dtype) != 0 && (w8ur_rows_win(rows) || (e->w8ur & 8));
+    p.lnq_w8_f1 = p.hq && (e->w8ur & W8_BITS[W13_F1]) && pk8.lnq_ok(rows, 4 * d, d, e->dtype) != 0 && (w8_rows_win(W8F_UP_ROWS, rows) || (e->w8ur & 8));
     // option "w8q": the QKV projection behind a centred copy on the pairs of the 12-channel image, at the row counts the paired consumer
     // leaves to rows_gemm_k (p.qp covers 2..6 rows at d = 2048 and 2..8 at narrower widths; with qkv_p8 < 2 none) and where the launcher
     // has a form (K = d in one chunk of 4, 8 or 16 k-tiles per wave).  The site takes it for the layers 1.. whose Wqkv is packed.
-    p.qkvq_w8 = p.hq && !p.qp && (e->w8q & W8_BITS[W13_QKV]) && pk8.qkvq_ok(rows, 3 * d, d, e->dtype) != 0 && (w8q_rows_win(rows) || (e->w8q & 8));
+    p.qkvq_w8 = p.hq && !p.qp && (e->w8q & W8_BITS[W13_QKV]) && pk8.qkvq_ok(rows, 3 * d, d, e->dtype) != 0 && (w8_rows_win(W8F_QKV_ROWS, rows) || (e->w8q & 8));
   } else {
     p.nsplit = 1;                      // attention one workgroup per (row, head), no split partials
     p.att_x = true;
@@ -396,11 +291,11 @@ PassPlan plan_pass(const vc_engine* e, int rows, bool decode, int tiled) {
       const vc_packed_kind& pk8 = vc_packed(VC_PK_W8);
       const bool staged = p.wd && e->wd_stage;
       p.wd_w8_f2 = staged && (e->w8w & W8_BITS[W13_F2]) && pk8.wd_ok(4 * d, e->dtype, p.ks_f2) != 0 &&
-                   (w8w_rows_win(W13_F2, rows) || (e->w8w & 8));
+                   (w8_rows_win(W8F_WIDE, rows) || (e->w8w & 8));
       p.wd_w8_qkv = staged && (e->w8w & W8_BITS[W13_QKV]) && pk8.wd_ok(d, e->dtype, 1) != 0 &&
-                    (w8w_rows_win(W13_QKV, rows) || (e->w8w & 8));
+                    (w8_rows_win(W8F_WIDE, rows) || (e->w8w & 8));
       // option "w8u": the FFN up-projection likewise (K = d in one slice, as QKV), for the layers whose W1 is packed
-      p.wd_w8_f1 = staged && (e->w8u & W8_BITS[W13_F1]) && pk8.wd_ok(d, e->dtype, 1) != 0 && (w8u_rows_win(rows) || (e->w8u & 8));
+      p.wd_w8_f1 = staged && (e->w8u & W8_BITS[W13_F1]) && pk8.wd_ok(d, e->dtype, 1) != 0 && (w8_rows_win(W8F_UP, rows) || (e->w8u & 8));
     }
   }
   p.heads_wide = p.form == FORM_WIDE && e->wide_heads;
@@ -1091,38 +986,15 @@ int need_qkv16(vc_engine* e, const char*, int v0) {
 int need_mask(vc_engine* e, const char* name, int v0) {
   return v0 < 0 || (v0 & ~5) ? fail(e, VC_EINVAL, "option '%s': %d is not a mask of 1 (FFN-down) and 4 (QKV)", name, v0) : VC_OK;
 }
-// mask like "w13", on an engine that requested the w8 form (vc_request_w8); the w8 bit wins over the w13 bit
-int need_w8(vc_engine* e, const char* name, int v0) {
-  return e->w8_req ? need_mask(e, name, v0) : fail(e, VC_EINVAL, "option 'w8': this engine was created without vc_request_w8");
-}
-// mask like "w8", on an engine that requested the rows form (vc_request_w8_rows)
-int need_w8r(vc_engine* e, const char* name, int v0) {
-  return e->w8r_req ? need_mask(e, name, v0) : fail(e, VC_EINVAL, "option 'w8r': this engine was created without vc_request_w8_rows");
-}
-// mask like "w8r" plus bit 8, on an engine that requested the wide form (vc_request_w8_wide)
-int need_w8w(vc_engine* e, const char*, int v0) {
-  if (!e->w8w_req) return fail(e, VC_EINVAL, "option 'w8w': this engine was created without vc_request_w8_wide");
-  return v0 < 0 || (v0 & ~13) ? fail(e, VC_EINVAL, "option 'w8w': %d is not a mask of 1 (FFN-down), 4 (QKV) and 8 (every row count)", v0) : VC_OK;
-}
-// mask of bit 1 plus bit 8, on an engine that requested the 9..16-row form (vc_request_w8_mid)
-int need_w8m(vc_engine* e, const char*, int v0) {
-  if (!e->w8m_req) return fail(e, VC_EINVAL, "option 'w8m': this engine was created without vc_request_w8_mid");
-  return v0 < 0 || (v0 & ~9) ? fail(e, VC_EINVAL, "option 'w8m': %d is not a mask of 1 (FFN-down) and 8 (every row count)", v0) : VC_OK;
-}
-// 2 (FFN-up) plus bit 8, on an engine that requested the form (vc_request_w8_up)
-int need_w8u(vc_engine* e, const char*, int v0) {
-  if (!e->w8u_req) return fail(e, VC_EINVAL, "option 'w8u': this engine was created without vc_request_w8_up");
-  return v0 != 0 && v0 != 2 && v0 != 10 ? fail(e, VC_EINVAL, "option 'w8u': %d is not 0, 2 (FFN-up) or 10 (at every row count)", v0) : VC_OK;
-}
-// likewise, on an engine that requested the 2..16-row form (vc_request_w8_up_rows)
-int need_w8ur(vc_engine* e, const char*, int v0) {
-  if (!e->w8ur_req) return fail(e, VC_EINVAL, "option 'w8ur': this engine was created without vc_request_w8_up_rows");
-  return v0 != 0 && v0 != 2 && v0 != 10 ? fail(e, VC_EINVAL, "option 'w8ur': %d is not 0, 2 (FFN-up) or 10 (at every row count)", v0) : VC_OK;
-}
-// 4 (QKV) plus bit 8, on an engine that requested the form (vc_request_w8_qkv_rows)
-int need_w8q(vc_engine* e, const char*, int v0) {
-  if (!e->w8q_req) return fail(e, VC_EINVAL, "option 'w8q': this engine was created without vc_request_w8_qkv_rows");
-  return v0 != 0 && v0 != 4 && v0 != 12 ? fail(e, VC_EINVAL, "option 'w8q': %d is not 0, 4 (QKV) or 12 (at every row count)", v0) : VC_OK;
+// the seven w8 options (W8_FORMS, vc_engine_host.h): on an engine that made the form's request, one of the form's values (where a
+// matrix has both kinds of planes the w8 bit wins over the w13 bit)
+int need_w8_form(vc_engine* e, const char* name, int v0) {
+  for (const W8Form& f : W8_FORMS) {
+    if (strcmp(name, f.option)) continue;
+    if (!(e->*f.req)) return fail(e, VC_EINVAL, "option '%s': this engine was created without %s", f.option, f.request);
+    return w8_value_ok(f, v0) ? VC_OK : fail(e, VC_EINVAL, "option '%s': %d is not %s", f.option, v0, f.value_text);
+  }
+  return fail(e, VC_EINVAL, "unknown option '%s'", name);
 }
 int need_kv8(vc_engine* e, const char*, int) {
   return e->kv8_req ? VC_OK : fail(e, VC_EINVAL, "option 'kv8': this engine was created without vc_request_kv8");
@@ -1166,13 +1038,13 @@ const OptDesc OPTIONS[] = {
     {"wd_stage", "VC_WD_STAGE", "q16", {&E::wd_stage, 0, 1}, nonzero},
     {"shrink", "VC_SHRINK", "sh", {&E::shrink, 0, 1}, nonzero},
     {"w13", "VC_W13", "w13", {&E::w13, 0, 5}, nullptr, {}, need_mask},
-    {"w8", nullptr, "w8", {&E::w8, 0, 5}, nullptr, {}, need_w8, &E::w8_req},      // only an engine that requested the form has the option
-    {"w8r", nullptr, "w8r", {&E::w8r, 0, 5}, nullptr, {}, need_w8r, &E::w8r_req},   // likewise (vc_request_w8_rows)
-    {"w8m", nullptr, "w8m", {&E::w8m, 0, 9}, nullptr, {}, need_w8m, &E::w8m_req},   // likewise (vc_request_w8_mid)
-    {"w8w", nullptr, "w8w", {&E::w8w, 0, 13}, nullptr, {}, need_w8w, &E::w8w_req},  // likewise (vc_request_w8_wide)
-    {"w8u", nullptr, "w8u", {&E::w8u, 0, 10}, nullptr, {}, need_w8u, &E::w8u_req},  // likewise (vc_request_w8_up)
-    {"w8ur", nullptr, "w8ur", {&E::w8ur, 0, 10}, nullptr, {}, need_w8ur, &E::w8ur_req},   // likewise (vc_request_w8_up_rows)
-    {"w8q", nullptr, "w8q", {&E::w8q, 0, 12}, nullptr, {}, need_w8q, &E::w8q_req},   // likewise (vc_request_w8_qkv_rows)
+    {"w8", nullptr, "w8", {&E::w8, 0, 5}, nullptr, {}, need_w8_form, &E::w8_req},      // only an engine that requested the form has the option
+    {"w8r", nullptr, "w8r", {&E::w8r, 0, 5}, nullptr, {}, need_w8_form, &E::w8r_req},   // likewise (vc_request_w8_rows)
+    {"w8m", nullptr, "w8m", {&E::w8m, 0, 9}, nullptr, {}, need_w8_form, &E::w8m_req},   // likewise (vc_request_w8_mid)
+    {"w8w", nullptr, "w8w", {&E::w8w, 0, 13}, nullptr, {}, need_w8_form, &E::w8w_req},  // likewise (vc_request_w8_wide)
+    {"w8u", nullptr, "w8u", {&E::w8u, 0, 10}, nullptr, {}, need_w8_form, &E::w8u_req},  // likewise (vc_request_w8_up)
+    {"w8ur", nullptr, "w8ur", {&E::w8ur, 0, 10}, nullptr, {}, need_w8_form, &E::w8ur_req},   // likewise (vc_request_w8_up_rows)
+    {"w8q", nullptr, "w8q", {&E::w8q, 0, 12}, nullptr, {}, need_w8_form, &E::w8q_req},   // likewise (vc_request_w8_qkv_rows)
     {"kv8", nullptr, "kv8", {&E::kv8, 0, 1}, nonzero, {}, need_kv8, &E::kv8_req},   // likewise
     {"prefill_rows", "VC_PREFILL_ROWS", nullptr, {&E::prefill_rows_per_pass, VC_ROWS, VC_MAX_ROWS}, whole_tiles},   // 16: decode kernels only
 };
@@ -1219,6 +1091,46 @@ int apply_env_presets(vc_engine* e) {
   return VC_OK;
 }
 
+// The stand-in engine of the host-only plans (vc_debug_plan, vc_debug_w8*_plan): this model shape and compute dtype, default options,
+// the weight images vc_finalize_weights packs for an engine that takes wide steps.  VC_EINVAL for arguments no such engine has.
+int plan_engine(vc_engine& e, const vc_model_cfg* c, int dtype, int rows, const void* out) {
+  if (!c || !out || rows < 1 || rows > VC_MAX_SEQS || c->d_model <= 0 || c->nhead <= 0 || c->d_model % c->nhead) return VC_EINVAL;
+  e.cfg = *c; e.d = c->d_model; e.H = c->nhead; e.hd = c->d_model / c->nhead; e.P = c->head_hidden; e.dtype = dtype;
+  e.has_fr8 = e.has_qkv16 = true;
+  e.has_qkv8 = vc_gemm_fr1_ok(3 * e.d, e.d, dtype, 4) != 0;
+  return VC_OK;
+}
+// ... in bf16 with vc_request_w8(5) and the form's own request made, every matrix taken as packed, and the form's option = mask
+int plan_engine_w8(vc_engine& e, const vc_model_cfg* c, int form, int mask, int rows, const void* out) {
+  const W8Form& f = W8_FORMS[form];
+  if (!w8_value_ok(f, mask)) return VC_EINVAL;
+  if (const int rc = plan_engine(e, c, VC_DTYPE_BF16, rows, out)) return rc;
+  e.w8_req = e.w8 = 5;
+  e.*f.req = f.bits; e.*f.value = mask;
+  return VC_OK;
+}
+
+// vc_request_w8*: every request comes before vc_finalize_weights; the masks of a form and their order after vc_request_w8 are the
+// table's (W8Form, vc_engine_host.h).  The option starts at the mask that was asked for.
+int request_w8_form(vc_engine* e, int form, int mask) {
+  const W8Form& f = W8_FORMS[form];
+  if (!e) return VC_EINVAL;
+  if (e->finalized) return fail(e, VC_ESTATE, "%s comes before vc_finalize_weights", f.request);
+  const bool after_w8 = form != W8F_ONE;
+  if (f.subset) {
+    if (mask < 0 || (mask & ~5)) return fail(e, VC_EINVAL, "%s: %d is not %s", f.request, mask, f.mask_text);
+    if (after_w8 && !e->w8_req) return fail(e, VC_ESTATE, "%s comes after vc_request_w8", f.request);
+    if (after_w8 && (mask & ~e->w8_req)) return fail(e, VC_EINVAL, "%s: mask %d is no subset of vc_request_w8's %d", f.request, mask, e->w8_req);
+    if (mask & ~f.bits) return fail(e, VC_EINVAL, "%s: %s", f.request, f.no_form);
+  } else {
+    if (!e->w8_req) return fail(e, VC_ESTATE, "%s comes after vc_request_w8", f.request);
+    if (mask != f.bits) return fail(e, VC_EINVAL, "%s: %d is not %s", f.request, mask, f.mask_text);
+  }
+  e->*f.req = mask;
+  e->*f.value = mask;
+  return VC_OK;
+}
+
 }  // namespace
 
 // =====================================================================================  C ABI
@@ -1232,14 +1144,9 @@ extern "C" int vc_debug_kv8_plan(int request, int kv8, int rps, int rows_attn, i
 // Host-only: what option "w8r" = mask makes of a bf16 decode pass of `rows` rows at this model shape, every matrix taken as packed
 // (plan_pass itself, the function the sites follow).
 extern "C" int vc_debug_w8r_plan(const vc_model_cfg* c, int mask, int rows, int32_t out[4]) {
-  if (!c || !out || rows < 1 || rows > VC_MAX_SEQS || mask < 0 || (mask & ~5) || c->d_model <= 0 || c->nhead <= 0 || c->d_model % c->nhead)
-    return VC_EINVAL;
-  vc_engine e;      // default options, the weight images vc_finalize_weights packs, both requests made
-  e.cfg = *c; e.d = c->d_model; e.H = c->nhead; e.hd = c->d_model / c->nhead; e.P = c->head_hidden; e.dtype = VC_DTYPE_BF16;
+  vc_engine e;
+  if (const int rc = plan_engine_w8(e, c, W8F_ROWS, mask, rows, out)) return rc;
   const int d = e.d;
-  e.has_fr8 = e.has_qkv16 = true;
-  e.has_qkv8 = vc_gemm_fr1_ok(3 * d, d, e.dtype, 4) != 0;
-  e.w8_req = e.w8 = 5; e.w8r_req = 5; e.w8r = mask;
   const PassPlan p = plan_pass(&e, rows, true, 0);
   out[0] = p.frp_w8 ? 1 : 0;
   out[1] = p.qp_w8 ? 1 : 0;
@@ -1250,14 +1157,9 @@ extern "C" int vc_debug_w8r_plan(const vc_model_cfg* c, int mask, int rows, int3
 // Host-only: what option "w8m" = mask (bits 1, 8) makes of a bf16 decode pass of `rows` rows at this model shape, the matrix taken as
 // packed (plan_pass itself): out = {form taken, kernel (1 = X in one piece, 2 = K in two halves), groups per wave and piece, 0}.
 extern "C" int vc_debug_w8m_plan(const vc_model_cfg* c, int mask, int rows, int32_t out[4]) {
-  if (!c || !out || rows < 1 || rows > VC_MAX_SEQS || mask < 0 || (mask & ~9) || c->d_model <= 0 || c->nhead <= 0 || c->d_model % c->nhead)
-    return VC_EINVAL;
-  vc_engine e;      // default options, the weight images vc_finalize_weights packs, both requests made
-  e.cfg = *c; e.d = c->d_model; e.H = c->nhead; e.hd = c->d_model / c->nhead; e.P = c->head_hidden; e.dtype = VC_DTYPE_BF16;
+  vc_engine e;
+  if (const int rc = plan_engine_w8(e, c, W8F_MID, mask, rows, out)) return rc;
   const int d = e.d;
-  e.has_fr8 = e.has_qkv16 = true;
-  e.has_qkv8 = vc_gemm_fr1_ok(3 * d, d, e.dtype, 4) != 0;
-  e.w8_req = e.w8 = 5; e.w8m_req = 1; e.w8m = mask;
   const PassPlan p = plan_pass(&e, rows, true, 0);
   out[0] = p.fr_w8_f2 ? 1 : 0;
   out[1] = p.fr_w8_f2 ? vc_gemm_fr_form(rows, d, 4 * d, e.dtype, PRO_PLAIN, 1) : 0;
@@ -1268,14 +1170,9 @@ extern "C" int vc_debug_w8m_plan(const vc_model_cfg* c, int mask, int rows, int3
 // Host-only: what option "w8w" = mask (bits 1, 4, 8) makes of a bf16 decode pass of `rows` rows at this model shape, every matrix taken
 // as packed (plan_pass itself): out = {FFN-down on the pair planes, QKV on them, k-tiles per wave of the FFN-down slice, of the QKV matrix}.
 extern "C" int vc_debug_w8w_plan(const vc_model_cfg* c, int mask, int rows, int32_t out[4]) {
-  if (!c || !out || rows < 1 || rows > VC_MAX_SEQS || mask < 0 || (mask & ~13) || c->d_model <= 0 || c->nhead <= 0 || c->d_model % c->nhead)
-    return VC_EINVAL;
-  vc_engine e;      // default options, the weight images vc_finalize_weights packs for an engine that takes wide steps, both requests made
-  e.cfg = *c; e.d = c->d_model; e.H = c->nhead; e.hd = c->d_model / c->nhead; e.P = c->head_hidden; e.dtype = VC_DTYPE_BF16;
+  vc_engine e;
+  if (const int rc = plan_engine_w8(e, c, W8F_WIDE, mask, rows, out)) return rc;
   const int d = e.d;
-  e.has_fr8 = e.has_qkv16 = true;
-  e.has_qkv8 = vc_gemm_fr1_ok(3 * d, d, e.dtype, 4) != 0;
-  e.w8_req = e.w8 = 5; e.w8w_req = 5; e.w8w = mask;
   const PassPlan p = plan_pass(&e, rows, true, 0);
   out[0] = p.wd_w8_f2 ? 1 : 0;
   out[1] = p.wd_w8_qkv ? 1 : 0;
@@ -1286,15 +1183,9 @@ extern "C" int vc_debug_w8w_plan(const vc_model_cfg* c, int mask, int rows, int3
 // Host-only: what option "w8u" = mask (0, 2 or 10) makes of a bf16 decode pass of `rows` rows at this model shape, W1 taken as packed
 // (plan_pass itself): out = {FFN-up on the pair planes, k-tiles per wave there}.
 extern "C" int vc_debug_w8u_plan(const vc_model_cfg* c, int mask, int rows, int32_t out[2]) {
-  if (!c || !out || rows < 1 || rows > VC_MAX_SEQS || (mask != 0 && mask != 2 && mask != 10) || c->d_model <= 0 || c->nhead <= 0 ||
-      c->d_model % c->nhead)
-    return VC_EINVAL;
-  vc_engine e;      // default options, the weight images vc_finalize_weights packs for an engine that takes wide steps, both requests made
-  e.cfg = *c; e.d = c->d_model; e.H = c->nhead; e.hd = c->d_model / c->nhead; e.P = c->head_hidden; e.dtype = VC_DTYPE_BF16;
+  vc_engine e;
+  if (const int rc = plan_engine_w8(e, c, W8F_UP, mask, rows, out)) return rc;
   const int d = e.d;
-  e.has_fr8 = e.has_qkv16 = true;
-  e.has_qkv8 = vc_gemm_fr1_ok(3 * d, d, e.dtype, 4) != 0;
-  e.w8_req = e.w8 = 5; e.w8u_req = 2; e.w8u = mask;
   const PassPlan p = plan_pass(&e, rows, true, 0);
   out[0] = p.wd_w8_f1 ? 1 : 0;
   out[1] = p.wd_w8_f1 ? vc_gemm_wd_kpw(d, e.dtype, 1) : 0;
@@ -1303,15 +1194,9 @@ extern "C" int vc_debug_w8u_plan(const vc_model_cfg* c, int mask, int rows, int3
 // Host-only: what option "w8ur" = mask (0, 2 or 10) makes of a bf16 decode pass of `rows` rows at this model shape, W1 taken as packed
 // (plan_pass itself): out = {FFN-up of the finished rows on the pair planes, k-tiles per wave there}.
 extern "C" int vc_debug_w8ur_plan(const vc_model_cfg* c, int mask, int rows, int32_t out[2]) {
-  if (!c || !out || rows < 1 || rows > VC_MAX_SEQS || (mask != 0 && mask != 2 && mask != 10) || c->d_model <= 0 || c->nhead <= 0 ||
-      c->d_model % c->nhead)
-    return VC_EINVAL;
-  vc_engine e;      // default options, the weight images vc_finalize_weights packs, both requests made
-  e.cfg = *c; e.d = c->d_model; e.H = c->nhead; e.hd = c->d_model / c->nhead; e.P = c->head_hidden; e.dtype = VC_DTYPE_BF16;
+  vc_engine e;
+  if (const int rc = plan_engine_w8(e, c, W8F_UP_ROWS, mask, rows, out)) return rc;
   const int d = e.d;
-  e.has_fr8 = e.has_qkv16 = true;
-  e.has_qkv8 = vc_gemm_fr1_ok(3 * d, d, e.dtype, 4) != 0;
-  e.w8_req = e.w8 = 5; e.w8ur_req = 2; e.w8ur = mask;
   const PassPlan p = plan_pass(&e, rows, true, 0);
   out[0] = p.lnq_w8_f1 ? 1 : 0;
   out[1] = p.lnq_w8_f1 ? vc_packed(VC_PK_W8).lnq_ok(rows, 4 * d, d, e.dtype) : 0;
@@ -1320,15 +1205,9 @@ extern "C" int vc_debug_w8ur_plan(const vc_model_cfg* c, int mask, int rows, int
 // Host-only: what option "w8q" = mask (0, 4 or 12) makes of a bf16 decode pass of `rows` rows at this model shape, Wqkv taken as packed
 // (plan_pass itself): out = {QKV of the finished rows of layers 1.. on the pairs of the 12-channel image, k-tiles per wave there}.
 extern "C" int vc_debug_w8q_plan(const vc_model_cfg* c, int mask, int rows, int32_t out[2]) {
-  if (!c || !out || rows < 1 || rows > VC_MAX_SEQS || (mask != 0 && mask != 4 && mask != 12) || c->d_model <= 0 || c->nhead <= 0 ||
-      c->d_model % c->nhead)
-    return VC_EINVAL;
-  vc_engine e;      // default options, the weight images vc_finalize_weights packs, both requests made
-  e.cfg = *c; e.d = c->d_model; e.H = c->nhead; e.hd = c->d_model / c->nhead; e.P = c->head_hidden; e.dtype = VC_DTYPE_BF16;
+  vc_engine e;
+  if (const int rc = plan_engine_w8(e, c, W8F_QKV_ROWS, mask, rows, out)) return rc;
   const int d = e.d;
-  e.has_fr8 = e.has_qkv16 = true;
-  e.has_qkv8 = vc_gemm_fr1_ok(3 * d, d, e.dtype, 4) != 0;
-  e.w8_req = e.w8 = 5; e.w8q_req = 4; e.w8q = mask;
   const PassPlan p = plan_pass(&e, rows, true, 0);
   out[0] = p.qkvq_w8 ? 1 : 0;
   out[1] = p.qkvq_w8 ? vc_packed(VC_PK_W8).qkvq_ok(rows, 3 * d, d, e.dtype) : 0;
@@ -1336,13 +1215,10 @@ extern "C" int vc_debug_w8q_plan(const vc_model_cfg* c, int mask, int rows, int3
 }
 // Host-only: how a decode pass of `rows` rows would be launched for this model shape and compute dtype (no engine, no GPU).
 extern "C" int vc_debug_plan(const vc_model_cfg* c, int compute_dtype, int rows, int32_t out[16]) {
-  if (!c || !out || rows < 1 || rows > VC_MAX_SEQS || c->d_model <= 0 || c->nhead <= 0 || c->d_model % c->nhead) return VC_EINVAL;
   if (compute_dtype != VC_DTYPE_BF16 && compute_dtype != VC_DTYPE_F32) return VC_EINVAL;
-  vc_engine e;      // default options, the weight images vc_finalize_weights packs for an engine that takes wide steps
-  e.cfg = *c; e.d = c->d_model; e.H = c->nhead; e.hd = c->d_model / c->nhead; e.P = c->head_hidden; e.dtype = compute_dtype;
+  vc_engine e;
+  if (const int rc = plan_engine(e, c, compute_dtype, rows, out)) return rc;
   const int d = e.d;
-  e.has_fr8 = e.has_qkv16 = true;
-  e.has_qkv8 = vc_gemm_fr1_ok(3 * d, d, compute_dtype, 4) != 0;
   const PassPlan p = plan_pass(&e, rows, true, 0);
   const bool fr = p.form == FORM_FR;
   out[0] = fr_max_rows(&e);
@@ -1463,92 +1339,33 @@ extern "C" int vc_load_tensor(vc_engine* e, const char* key, const void* data, i
 
 // Asks vc_finalize_weights to pack the matrices of `mask` (1 FFN-down, 4 QKV) as E4M3 bytes too (option "w8").  The compute dtype is
 // chosen at vc_finalize_weights, so that is where a request meets an fp32 engine: VC_EINVAL from there.
-extern "C" int vc_request_w8(vc_engine* e, int mask) {
-  if (!e) return VC_EINVAL;
-  if (e->finalized) return fail(e, VC_ESTATE, "vc_request_w8 comes before vc_finalize_weights");
-  if (mask < 0 || (mask & ~5)) return fail(e, VC_EINVAL, "vc_request_w8: %d is not a mask of 1 (FFN-down) and 4 (QKV)", mask);
-  e->w8_req = mask;
-  e->w8 = mask;
-  return VC_OK;
-}
+extern "C" int vc_request_w8(vc_engine* e, int mask) { return request_w8_form(e, W8F_ONE, mask); }
 
 // Lets steps of 2..8 finished rows stream the planes vc_request_w8 asked for (option "w8r"): `mask` is a subset of that request's.
-extern "C" int vc_request_w8_rows(vc_engine* e, int mask) {
-  if (!e) return VC_EINVAL;
-  if (e->finalized) return fail(e, VC_ESTATE, "vc_request_w8_rows comes before vc_finalize_weights");
-  if (mask < 0 || (mask & ~5)) return fail(e, VC_EINVAL, "vc_request_w8_rows: %d is not a mask of 1 (FFN-down) and 4 (QKV)", mask);
-  if (!e->w8_req) return fail(e, VC_ESTATE, "vc_request_w8_rows comes after vc_request_w8");
-  if (mask & ~e->w8_req) return fail(e, VC_EINVAL, "vc_request_w8_rows: mask %d is no subset of vc_request_w8's %d", mask, e->w8_req);
-  e->w8r_req = mask;
-  e->w8r = mask;
-  return VC_OK;
-}
+extern "C" int vc_request_w8_rows(vc_engine* e, int mask) { return request_w8_form(e, W8F_ROWS, mask); }
 
 // Lets steps of 17..64 rows stream the matrices of `mask` (a subset of vc_request_w8's) as E4M3 pair planes of their 16-channel images
 // (option "w8w"): packed at vc_finalize_weights, + 0.5 x the two images, on an engine that can run wide steps.
-extern "C" int vc_request_w8_wide(vc_engine* e, int mask) {
-  if (!e) return VC_EINVAL;
-  if (e->finalized) return fail(e, VC_ESTATE, "vc_request_w8_wide comes before vc_finalize_weights");
-  if (mask < 0 || (mask & ~5)) return fail(e, VC_EINVAL, "vc_request_w8_wide: %d is not a mask of 1 (FFN-down) and 4 (QKV)", mask);
-  if (!e->w8_req) return fail(e, VC_ESTATE, "vc_request_w8_wide comes after vc_request_w8");
-  if (mask & ~e->w8_req) return fail(e, VC_EINVAL, "vc_request_w8_wide: mask %d is no subset of vc_request_w8's %d", mask, e->w8_req);
-  e->w8w_req = mask;
-  e->w8w = mask;
-  return VC_OK;
-}
+extern "C" int vc_request_w8_wide(vc_engine* e, int mask) { return request_w8_form(e, W8F_WIDE, mask); }
 
 // Lets steps of 17..64 rows stream the FFN up-projection (mask 2, nothing else) as E4M3 pair planes of its 16-channel image W1 (option
 // "w8u"): packed at vc_finalize_weights, + 0.5 x that image, on an engine that can run wide steps.  Needs vc_request_w8 (the bf16 /
 // fp32 check of that request at vc_finalize_weights covers this one) but none of its bits, and not vc_request_w8_wide.
-extern "C" int vc_request_w8_up(vc_engine* e, int mask) {
-  if (!e) return VC_EINVAL;
-  if (e->finalized) return fail(e, VC_ESTATE, "vc_request_w8_up comes before vc_finalize_weights");
-  if (!e->w8_req) return fail(e, VC_ESTATE, "vc_request_w8_up comes after vc_request_w8");
-  if (mask != W8_BITS[W13_F1]) return fail(e, VC_EINVAL, "vc_request_w8_up: %d is not the mask 2 (FFN-up)", mask);
-  e->w8u_req = mask;
-  e->w8u = mask;
-  return VC_OK;
-}
+extern "C" int vc_request_w8_up(vc_engine* e, int mask) { return request_w8_form(e, W8F_UP, mask); }
 
 // Lets passes of 2..16 finished rows stream the FFN up-projection (mask 2, nothing else) from the pair planes of W1 (option "w8ur"):
 // the planes option "w8u" streams at 17..64 rows, packed at vc_finalize_weights whatever max_seqs is - once when both are requested.
 // Needs vc_request_w8 (the bf16 / fp32 check of that request at vc_finalize_weights covers this one) but none of its bits.
-extern "C" int vc_request_w8_up_rows(vc_engine* e, int mask) {
-  if (!e) return VC_EINVAL;
-  if (e->finalized) return fail(e, VC_ESTATE, "vc_request_w8_up_rows comes before vc_finalize_weights");
-  if (!e->w8_req) return fail(e, VC_ESTATE, "vc_request_w8_up_rows comes after vc_request_w8");
-  if (mask != W8_BITS[W13_F1]) return fail(e, VC_EINVAL, "vc_request_w8_up_rows: %d is not the mask 2 (FFN-up)", mask);
-  e->w8ur_req = mask;
-  e->w8ur = mask;
-  return VC_OK;
-}
+extern "C" int vc_request_w8_up_rows(vc_engine* e, int mask) { return request_w8_form(e, W8F_UP_ROWS, mask); }
 
 // Lets the finished-row passes whose QKV projection still reads the 12-channel image (9..16 rows; 7 and 8 at d = 2048) stream it (mask
 // 4, nothing else) from the pairs of that image (option "w8q"): packed at vc_finalize_weights for layers 1.., + 0.5 x that image, whatever
 // max_seqs is.  Needs vc_request_w8 (the bf16 / fp32 check of that request at vc_finalize_weights covers this one) but none of its bits.
-extern "C" int vc_request_w8_qkv_rows(vc_engine* e, int mask) {
-  if (!e) return VC_EINVAL;
-  if (e->finalized) return fail(e, VC_ESTATE, "vc_request_w8_qkv_rows comes before vc_finalize_weights");
-  if (!e->w8_req) return fail(e, VC_ESTATE, "vc_request_w8_qkv_rows comes after vc_request_w8");
-  if (mask != W8_BITS[W13_QKV]) return fail(e, VC_EINVAL, "vc_request_w8_qkv_rows: %d is not the mask 4 (QKV)", mask);
-  e->w8q_req = mask;
-  e->w8q = mask;
-  return VC_OK;
-}
+extern "C" int vc_request_w8_qkv_rows(vc_engine* e, int mask) { return request_w8_form(e, W8F_QKV_ROWS, mask); }
 
 // Lets passes of 9..16 finished rows stream the FFN-down planes vc_request_w8 asked for (option "w8m"): `mask` is bit 1 of that request.
 // Nothing more is packed and resident memory does not change.
-extern "C" int vc_request_w8_mid(vc_engine* e, int mask) {
-  if (!e) return VC_EINVAL;
-  if (e->finalized) return fail(e, VC_ESTATE, "vc_request_w8_mid comes before vc_finalize_weights");
-  if (mask < 0 || (mask & ~5)) return fail(e, VC_EINVAL, "vc_request_w8_mid: %d is not a mask of 1 (FFN-down)", mask);
-  if (!e->w8_req) return fail(e, VC_ESTATE, "vc_request_w8_mid comes after vc_request_w8");
-  if (mask & ~e->w8_req) return fail(e, VC_EINVAL, "vc_request_w8_mid: mask %d is no subset of vc_request_w8's %d", mask, e->w8_req);
-  if (mask & 4) return fail(e, VC_EINVAL, "vc_request_w8_mid: bit 4 (QKV) has no form - no kernel reads Wqkv8 at 9..16 rows; the mask is 1 (FFN-down)");
-  e->w8m_req = mask;
-  e->w8m = mask;
-  return VC_OK;
-}
+extern "C" int vc_request_w8_mid(vc_engine* e, int mask) { return request_w8_form(e, W8F_MID, mask); }
 
 // Asks vc_finalize_weights for the E4M3 copy of the K / V cache (option "kv8").  As for vc_request_w8, an fp32 engine meets the request
 // at vc_finalize_weights: VC_EINVAL from there.
@@ -1687,32 +1504,47 @@ int pack_layer(vc_engine* e, int l) {
   // two of the big matrices of a one-row step once more as 13-bit planes, where a wave's share is whole groups of four fragments
   // (vc_gemm_packed_fr1_ng: FFN-down from d = 512, QKV from d = 1024), and, only for an engine that asked (vc_request_w8), the
   // requested ones as E4M3 bytes: the same widths, + 0.5 x the requested images
+  // the group planes of `kind` (VC_PK_*) of an image of `n_frags` 1 KB fragments: one side byte per fragment
+  auto pack_planes = [&](int kind, int which, const uint4* image, long n_frags) {
+    const vc_packed_kind& pk = vc_packed(kind);
+    return pack_checked(e, ly.packed[kind][which], (size_t)(n_frags / pk.group_frags) * pk.group_u4, (size_t)(n_frags / 4),
+                        [&](uint4* planes, unsigned char* side, unsigned int* counts) { return pk.pack(image, n_frags, planes, side, counts, 0); });
+  };
+  // the pair planes (vc_w8.h "w8w", slot PK_W8W) of a 16-channel image of `n_pairs` pairs: two side bytes per pair
+  auto pack_pairs = [&](int which, const uint4* image, long n_pairs) {
+    return pack_checked(e, ly.packed[PK_W8W][which], (size_t)n_pairs * VC_W8W_PAIR_U4, (size_t)(n_pairs + 1) / 2,
+                        [&](uint4* planes, unsigned char* side, unsigned int* counts) { return vc_launch_w8w_pack(image, n_pairs, planes, side, counts, 0); });
+  };
   const int pack_mask[VC_PK_N] = {e->has_w13 ? 5 : 0, e->w8_req};
   for (int kind = 0; kind < VC_PK_N; ++kind) {
     if ((pack_mask[kind] & W8_BITS[W13_F2]) && ly.W28 && vc_gemm_packed_fr1_ng(kind, d, 4 * d, e->dtype, VC_FR_WAVES) &&
-        (rc = pack_planes(e, ly, kind, W13_F2, ly.W28, (long)(d / VC_TH_RES) * (4 * d / 64)))) return rc;
+        (rc = pack_planes(kind, W13_F2, ly.W28, (long)(d / VC_TH_RES) * (4 * d / 64)))) return rc;
     if ((pack_mask[kind] & W8_BITS[W13_QKV]) && ly.Wqkv8 && vc_gemm_packed_fr1_ng(kind, 3 * d, d, e->dtype, 4) &&
-        (rc = pack_planes(e, ly, kind, W13_QKV, ly.Wqkv8, (long)(3 * d / VC_TH_RES) * (d / 64)))) return rc;
+        (rc = pack_planes(kind, W13_QKV, ly.Wqkv8, (long)(3 * d / VC_TH_RES) * (d / 64)))) return rc;
   }
   // on request (vc_request_w8_wide), for an engine that can run wide steps: the 16-channel images W2 / Wqkv16 as pair planes, where
   // the wide kernel has a form on them for the K slice it would use (+ 0.5 x the two images)
   if (e->w8w_req && want_qkv16 && e->dtype == VC_DTYPE_BF16) {
     const vc_packed_kind& pk8 = vc_packed(VC_PK_W8);
     if ((e->w8w_req & W8_BITS[W13_F2]) && pk8.wd_ok(4 * d, e->dtype, std::max(1, wd_ksplit(e, d, 4 * d))) &&
-        (rc = pack_pairs(e, ly, W13_F2, ly.W2, (long)(d / 16) * (4 * d / 64)))) return rc;
+        (rc = pack_pairs(W13_F2, ly.W2, (long)(d / 16) * (4 * d / 64)))) return rc;
     if ((e->w8w_req & W8_BITS[W13_QKV]) && ly.Wqkv16 && pk8.wd_ok(d, e->dtype, 1) &&
-        (rc = pack_pairs(e, ly, W13_QKV, ly.Wqkv16, (long)(3 * d / 16) * (d / 64)))) return rc;
+        (rc = pack_pairs(W13_QKV, ly.Wqkv16, (long)(3 * d / 16) * (d / 64)))) return rc;
   }
   // on request (vc_request_w8_up), likewise: the 16-channel image W1 of the FFN up-projection (K = d in one slice): + 0.5 x the image
   // (vc_request_w8_up_rows: the same planes for passes of 2..16 finished rows, whatever max_seqs is - packed once when both ask)
   const bool up_wide = e->w8u_req && want_qkv16 && vc_packed(VC_PK_W8).wd_ok(d, e->dtype, 1);
   const bool up_rows = e->w8ur_req && vc_packed(VC_PK_W8).lnq_ok(2, 4 * d, d, e->dtype);
   if ((up_wide || up_rows) && e->dtype == VC_DTYPE_BF16 &&
-      (rc = pack_pairs(e, ly, W13_F1, ly.W1, (long)(4 * d / 16) * (d / 64)))) return rc;
+      (rc = pack_pairs(W13_F1, ly.W1, (long)(4 * d / 16) * (d / 64)))) return rc;
   // on request (vc_request_w8_qkv_rows): the pairs of the 12-channel image Wqkv, for the layers that read a centred copy (layer 0 has
   // none and keeps PRO_LNW), whatever max_seqs is: + 0.5 x the image
+  // (vc_w8.h "w8q", slot Layer::w8q: 768 B of codes and two side bytes per pair, d / 32 k-tiles per tile)
+  const long pairs12 = (long)(3 * d / VC_TH_QKV) * (d / 64);
   if (e->w8q_req && l > 0 && e->dtype == VC_DTYPE_BF16 && vc_packed(VC_PK_W8).qkvq_ok(2, 3 * d, d, e->dtype) &&
-      (rc = pack_pairs12(e, ly, (long)(3 * d / VC_TH_QKV) * (d / 64), d / 32))) return rc;
+      (rc = pack_checked(e, ly.w8q, (size_t)pairs12 * VC_W8Q_PAIR_U4, (size_t)(pairs12 + 1) / 2, [&](uint4* planes, unsigned char* side, unsigned int* counts) {
+         return vc_launch_w8q_pack(ly.Wqkv, pairs12, d / 32, planes, side, counts, 0);
+       }))) return rc;
   const size_t cache_bytes = (size_t)e->B_max * e->H * e->S_max * e->hd * e->esz;
   if ((rc = dalloc(e, &ly.kc, cache_bytes))) return rc;
   if ((rc = dalloc(e, &ly.vc, cache_bytes))) return rc;
@@ -2567,6 +2399,25 @@ extern "C" int vc_edit_multi(vc_engine* e, int B, const int64_t* x_dev, const in
 }
 
 // ------------------------------------------------------------------------------------- hooks
+namespace {
+// vc_debug_read "<form>_stats": int32 {state (0 not applicable, 1 packed, 2 refused), fragments or pairs refused} of every slot the
+// name covers, layer by layer.  false: no such buffer on this engine.
+//   w13_stats, w8_stats   [layer][FFN-down, QKV]: the group planes (w8: all 0 on an engine without vc_request_w8)
+//   w8w_stats             [layer][FFN-down, QKV]: the pair planes of the 16-channel images, on engines with vc_request_w8_wide
+//   w8u_stats, w8ur_stats [layer]: the pair planes of W1 - one slot, the planes are shared -, on engines with vc_request_w8_up / _up_rows
+//   w8q_stats             [layer]: the pairs of the 12-channel QKV image, on engines with vc_request_w8_qkv_rows (layer 0: 0, 0)
+bool pack_stats(const vc_engine* e, const std::string& n, std::vector<int32_t>& v) {
+  const int kind = n == "w13_stats" ? VC_PK_W13 : n == "w8_stats" ? VC_PK_W8 : n == "w8w_stats" && e->w8w_req ? PK_W8W : -1;
+  const bool up = (n == "w8u_stats" && e->w8u_req) || (n == "w8ur_stats" && e->w8ur_req), q12 = n == "w8q_stats" && e->w8q_req;
+  if (kind < 0 && !up && !q12) return false;
+  auto put = [&](const Layer::Packed& p) { v.push_back(p.state); v.push_back(p.refused); };
+  for (const Layer& ly : e->layers) {
+    if (kind >= 0) { put(ly.packed[kind][W13_F2]); put(ly.packed[kind][W13_QKV]); }
+    else put(up ? ly.packed[PK_W8W][W13_F1] : ly.w8q);
+  }
+  return true;
+}
+}  // namespace
 extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int64_t nbytes) {
   int rc = check_ready(e);
   if (rc) return rc;
@@ -2630,32 +2481,7 @@ extern "C" int vc_debug_read(vc_engine* e, const char* name, void* host_dst, int
     memcpy(host_dst, e->opt_state.c_str(), std::min<size_t>((size_t)nbytes > 0 ? (size_t)nbytes - 1 : 0, e->opt_state.size()));
     return VC_OK;
   }
-  else if (n == "w13_stats" || n == "w8_stats" || (n == "w8w_stats" && e->w8w_req)) {      // int32 [layer][FFN-down, QKV][state (0 not applicable, 1 packed, 2 refused), fragments (w8w: pairs) refused]
-    const int kind = n == "w13_stats" ? VC_PK_W13 : n == "w8_stats" ? VC_PK_W8 : PK_W8W;      // (w8: all 0 on an engine without vc_request_w8; w8w: only on an engine with vc_request_w8_wide)
-    std::vector<int32_t> v;
-    for (const Layer& ly : e->layers)
-      for (int w = 0; w < 2; ++w) { v.push_back(ly.packed[kind][w].state); v.push_back(ly.packed[kind][w].refused); }
-    if (nbytes > (int64_t)(v.size() * 4)) return fail(e, VC_ECAP, "debug buffer '%s' holds %lld bytes", n.c_str(), (long long)(v.size() * 4));
-    memcpy(host_dst, v.data(), (size_t)nbytes);
-    return VC_OK;
-  }
-  else if (n == "w8ur_stats" && e->w8ur_req) {    // the same slot (the planes are shared), on engines with vc_request_w8_up_rows
-    std::vector<int32_t> v;
-    for (const Layer& ly : e->layers) { v.push_back(ly.packed[PK_W8W][W13_F1].state); v.push_back(ly.packed[PK_W8W][W13_F1].refused); }
-    if (nbytes > (int64_t)(v.size() * 4)) return fail(e, VC_ECAP, "debug buffer '%s' holds %lld bytes", n.c_str(), (long long)(v.size() * 4));
-    memcpy(host_dst, v.data(), (size_t)nbytes);
-    return VC_OK;
-  }
-  else if (n == "w8q_stats" && e->w8q_req) {      // int32 [layer][state, pairs refused] of the 12-channel QKV image's pairs (engines with vc_request_w8_qkv_rows; layer 0: 0, 0)
-    std::vector<int32_t> v;
-    for (const Layer& ly : e->layers) { v.push_back(ly.w8q.state); v.push_back(ly.w8q.refused); }
-    if (nbytes > (int64_t)(v.size() * 4)) return fail(e, VC_ECAP, "debug buffer '%s' holds %lld bytes", n.c_str(), (long long)(v.size() * 4));
-    memcpy(host_dst, v.data(), (size_t)nbytes);
-    return VC_OK;
-  }
-  else if (n == "w8u_stats" && e->w8u_req) {      // int32 [layer][state, pairs refused] of the FFN up-projection's pair planes (engines with vc_request_w8_up)
-    std::vector<int32_t> v;
-    for (const Layer& ly : e->layers) { v.push_back(ly.packed[PK_W8W][W13_F1].state); v.push_back(ly.packed[PK_W8W][W13_F1].refused); }
+  else if (std::vector<int32_t> v; pack_stats(e, n, v)) {      // "w13_stats", "w8_stats", "w8w_stats", "w8u_stats", "w8ur_stats", "w8q_stats"
     if (nbytes > (int64_t)(v.size() * 4)) return fail(e, VC_ECAP, "debug buffer '%s' holds %lld bytes", n.c_str(), (long long)(v.size() * 4));
     memcpy(host_dst, v.data(), (size_t)nbytes);
     return VC_OK;

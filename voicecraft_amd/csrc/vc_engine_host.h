@@ -212,14 +212,14 @@ struct vc_engine {
   int w8r = 0;
   // option "w8m": passes of 9..16 finished rows stream the FFN down-projection (1) from the same planes (rows_gemm_fr_w8_k /
   // rows_gemm_fr2_w8_k: the image kernels' text, one decoded fragment feeding two k-tiles, results bit-identical), where plan_pass
-  // takes the form; bit 8 = also at row counts the win table (w8m_rows_win) leaves out, for the A/B tool and the tests.  Only on an
+  // takes the form; bit 8 = also at row counts the win table (w8_rows_win, W8_FORMS below) leaves out, for the A/B tool and the tests.  Only on an
   // engine that asked for it after vc_request_w8 (vc_request_w8_mid: w8m_req, a subset of w8_req; QKV has no consumer of Wqkv8 at
   // these row counts).  Nothing more is packed; any other engine has no such option and launches what it launched before.
   int w8m_req = 0;
   int w8m = 0;
   // option "w8w": steps of 17..64 rows stream the FFN down-projection (1) and the QKV projection (4) as E4M3 pair planes of their
   // 16-channel images W2 / Wqkv16 (rows_gemm_wds_w8_k: the staged wide kernel's text on half the weight bytes, results bit-identical),
-  // where plan_pass takes the form; bit 8 = also at row counts the win table (w8w_rows_win) leaves out, for the A/B tool and the
+  // where plan_pass takes the form; bit 8 = also at row counts the win table (w8_rows_win, W8_FORMS below) leaves out, for the A/B tool and the
   // tests.  Only on an engine that asked for it after vc_request_w8 (vc_request_w8_wide: w8w_req, a subset of w8_req) and that can
   // run wide steps (has_qkv16): + 0.5 x the two images resident (7 d^2 bytes per layer: + 0.47 GB at giga830M).  Any other engine
   // packs nothing more, has no such option and launches what it launched before.
@@ -227,7 +227,7 @@ struct vc_engine {
   int w8w = 0;
   // option "w8u": steps of 17..64 rows stream the FFN up-projection (2) as E4M3 pair planes of its 16-channel image W1
   // (rows_gemm_wds_w8u_k: the same text with the bias + ReLU epilogue, results bit-identical), where plan_pass takes the form; bit 8 =
-  // also at row counts the win table (w8u_rows_win) leaves out, for the A/B tool and the tests.  Only on an engine that asked for it
+  // also at row counts the win table (w8_rows_win, W8_FORMS below) leaves out, for the A/B tool and the tests.  Only on an engine that asked for it
   // after vc_request_w8 (vc_request_w8_up: w8u_req = 2) and that can run wide steps (has_qkv16): + 0.5 x the W1 image resident
   // (4 d^2 + d^2 / 128 bytes per layer: + 0.27 GB at giga830M).  Independent of "w8w".  Any other engine packs nothing more, has
   // no such option and launches what it launched before.
@@ -235,7 +235,7 @@ struct vc_engine {
   int w8u = 0;
   // option "w8ur": passes of 2..16 finished rows stream the FFN up-projection (2) from the SAME pair planes of W1 (rows_gemm_lnq_w8_k: the
   // text of rows_gemm_k<bf16_t, KTW, PRO_LNQ, EPI_RELU, ..> with the pairs as the weight source, results bit-identical), where plan_pass
-  // takes the form; bit 8 = also at row counts the win table (w8ur_rows_win) leaves out, for the A/B tool and the tests.  Only on an
+  // takes the form; bit 8 = also at row counts the win table (w8_rows_win, W8_FORMS below) leaves out, for the A/B tool and the tests.  Only on an
   // engine that asked for it after vc_request_w8 (vc_request_w8_up_rows: w8ur_req = 2), whatever its max_seqs: + 0.5 x the W1 image
   // resident (4 d^2 + d^2 / 128 bytes per layer: + 0.27 GB at giga830M) unless "w8u" holds the planes already.  Any other engine packs
   // nothing more, has no such option and launches what it launched before.
@@ -245,7 +245,7 @@ struct vc_engine {
   // 12-channel image (the row counts past the paired consumer's, p.qp: 9..16 everywhere, 7 and 8 at d = 2048; with qkv_p8 < 2 also the
   // lower ones) stream the QKV projection (4) of layers 1.. from the pairs of that image (rows_gemm_qkvq_w8_k: the same text with the
   // pairs as the weight source, results bit-identical), where plan_pass takes the form; bit 8 = also at row counts the win table
-  // (w8q_rows_win) leaves out, for the A/B tool and the tests.  Only on an engine that asked for it after vc_request_w8
+  // (w8_rows_win, W8_FORMS below) leaves out, for the A/B tool and the tests.  Only on an engine that asked for it after vc_request_w8
   // (vc_request_w8_qkv_rows: w8q_req = 4), whatever its max_seqs: + 0.5 x the Wqkv image resident per packed layer (3 d^2 + d^2 / 128
   // bytes: + 0.20 GB at giga830M).  Any other engine packs nothing more, has no such option and launches what it launched before.
   int w8q_req = 0;
@@ -371,6 +371,81 @@ struct PassPlan {
   bool heads_wide;  // the heads run once over all rows on the wide-step kernels (option wide_heads)
   bool heads_fold;  // heads-1 folds the finished rows itself (no LayerNorm launch)
 };
+
+// ---------------------------------------------------------------- the w8 forms, one row per option
+// Everything vc_engine.hip knows about an option that streams E4M3 weights, apart from the launch itself: its request (request_w8_form),
+// the values it accepts (w8_value_ok: the option table and the vc_debug_w8*_plan entry points), and the row counts at which plan_pass
+// takes the form without being told to (w8_rows_win).  struct vc_engine says what each option does; DESIGN.md has the table in prose.
+struct W8Form {
+  const char *option, *request;             // the option's name, the C function that asks for it before vc_finalize_weights
+  int vc_engine::*req, vc_engine::*value;   // what the request stored (0: no such option on this engine), the option's value
+  int bits;                                 // the matrices of the form: 1 FFN-down, 4 QKV, 2 FFN-up
+  // subset: the request takes any mask of vc_request_w8's bits 1 and 4 that is a subset of that request's (0 included; a bit outside
+  // `bits` is refused behind that with `no_form`), the option any mask of `bits`.  Otherwise the request needs vc_request_w8 but none of
+  // its bits and takes `bits` alone; the option takes 0 or `bits`.
+  bool subset;
+  bool every_rows;                          // the option's value has bit 8: also at the row counts rows_lo..rows_hi leaves out (the A/B tools, the tests)
+  int rows_lo, rows_hi;                     // the row counts the measured table takes
+  const char *mask_text, *value_text, *no_form;      // for the refusals: the request's masks, the option's values, a bit without a form
+};
+enum { W8F_ONE = 0, W8F_ROWS, W8F_MID, W8F_WIDE, W8F_UP, W8F_UP_ROWS, W8F_QKV_ROWS, W8F_N };
+inline const W8Form W8_FORMS[W8F_N] = {
+    // "w8": one-row steps; the request that packs the planes the next three read
+    {"w8", "vc_request_w8", &vc_engine::w8_req, &vc_engine::w8, 5, true, false, 1, 1,
+     "a mask of 1 (FFN-down) and 4 (QKV)", "a mask of 1 (FFN-down) and 4 (QKV)", nullptr},
+    // "w8r": the row counts at which the w8 form of a matrix measured faster than the image over the whole paired range; a row count
+    // whose range touches zero would stay on the image.  profiles/w8_rows_ab.log (giga830M, 7 interleaved pairs per line, captured
+    // decode loop per step, min..max of the pairs): FFN-down alone -6.3 .. -5.8 % at 2, 3, 4, 6 and 8 rows, QKV alone -4.4 .. -5.0 % at
+    // 2, 3, 4 and 6 rows (rows_gemm_qp_k stops at 6 rows at d = 2048), both -10.8 .. -11.0 %: every row count of both bits takes the form.
+    {"w8r", "vc_request_w8_rows", &vc_engine::w8r_req, &vc_engine::w8r, 5, true, false, 2, 8,
+     "a mask of 1 (FFN-down) and 4 (QKV)", "a mask of 1 (FFN-down) and 4 (QKV)", nullptr},
+    // "w8m": the row counts of 9..16 at which the w8 form of the FFN down-projection measured faster than the image over the whole
+    // paired range; a count that was not measured follows the nearest measured one.  profiles/w8_mid_ab.log (tools/w8_mid_ab.py:
+    // giga830M, 7 interleaved pairs per line, captured decode loop per step, min..max of the pairs) at 9, 12, 16 rows: -5.3 .. -5.2 %,
+    // -5.0 .. -4.9 %, -5.2 .. -5.2 %, and -4.8 .. -4.7 % for 16 utterances at the benchmark's shapes with `w8r` and `w8w` on: every measured
+    // row count has its whole range below zero, so every row count 9..16 takes the form.
+    {"w8m", "vc_request_w8_mid", &vc_engine::w8m_req, &vc_engine::w8m, 1, true, true, VC_FR_MAX_ROWS + 1, VC_ROWS,
+     "a mask of 1 (FFN-down)", "a mask of 1 (FFN-down) and 8 (every row count)",
+     "bit 4 (QKV) has no form - no kernel reads Wqkv8 at 9..16 rows; the mask is 1 (FFN-down)"},
+    // "w8w": the row counts at which the pair-plane form of a matrix measured faster than the image over the whole paired range; row
+    // counts between measured ones follow the nearest measured count of the same RT (17..32, 33..64).  profiles/w8_wide_ab.log
+    // (tools/w8_wide_ab.py: giga830M, 7 interleaved pairs per line, captured decode loop per step, min..max of the pairs) at 17, 24,
+    // 32 | 33, 48, 64 rows: FFN-down alone -4.9 .. -3.5 % | -3.6 .. -2.9 %, QKV alone -3.1 .. -2.9 % | -2.3 .. -2.0 %, both -7.9 .. -7.3 % |
+    // -5.6 .. -5.2 %: every measured row count of both bits has its whole range below zero, so every wide row count takes the form.
+    {"w8w", "vc_request_w8_wide", &vc_engine::w8w_req, &vc_engine::w8w, 5, true, true, VC_ROWS + 1, VC_MAX_SEQS,
+     "a mask of 1 (FFN-down) and 4 (QKV)", "a mask of 1 (FFN-down), 4 (QKV) and 8 (every row count)", nullptr},
+    // "w8u": the row counts at which the pair-plane form of the FFN up-projection measured faster than the image over the whole paired
+    // range; row counts between measured ones follow the nearest measured count of the same RT (17..32, 33..64).  profiles/w8_up_ab.log
+    // (tools/w8_up_ab.py: giga830M, 7 interleaved pairs per line, captured decode loop per step, min..max of the pairs) at 17, 24, 32 |
+    // 33, 48, 64 rows: FFN-up alone -4.4 .. -4.0 % | -3.1 .. -2.6 %, next to `w8w` = 13 -4.9 .. -4.2 % | -3.3 .. -2.9 %, with kv8
+    // -4.2 .. -4.1 % at 32 rows and -2.9 .. -2.8 % at 64: every measured row count has its whole range below zero, so every wide row
+    // count takes the form.
+    {"w8u", "vc_request_w8_up", &vc_engine::w8u_req, &vc_engine::w8u, 2, false, true, VC_ROWS + 1, VC_MAX_SEQS,
+     "the mask 2 (FFN-up)", "0, 2 (FFN-up) or 10 (at every row count)", nullptr},
+    // "w8ur": the row counts of 2..16 at which the pair-plane form of the FFN up-projection measured faster than the image over the
+    // whole paired range; a count that was not measured follows the nearest measured one of the same kernel form (2..4, 5..8, 9..16
+    // rows).  profiles/w8_up_rows_ab.log (tools/w8_up_rows_ab.py: giga830M, 7 interleaved pairs per line, captured decode loop per
+    // step, min..max of the pairs) at 2, 4 | 5, 8 | 9, 12, 16 rows: -7.9 .. -7.5 % | -5.6 .. -4.9 % | -4.2 .. -3.7 %, and -5.3 % / -3.7 % for
+    // 8 / 16 utterances at the benchmark's shapes with `w8r` and `w8m` on: every measured row count has its whole range below zero, so
+    // every row count 2..16 takes the form.
+    {"w8ur", "vc_request_w8_up_rows", &vc_engine::w8ur_req, &vc_engine::w8ur, 2, false, true, 2, VC_ROWS,
+     "the mask 2 (FFN-up)", "0, 2 (FFN-up) or 10 (at every row count)", nullptr},
+    // "w8q": the row counts at which the pair form of the QKV projection's 12-channel image measured faster than the image over the
+    // whole paired range; a count that was not measured follows the nearest measured one of the same kernel form (2..4, 5..8, 9..16
+    // rows).  profiles/w8_qkv_rows_ab.log (tools/w8_qkv_rows_ab.py: giga830M, 7 interleaved pairs per line, captured decode loop per
+    // step, min..max of the pairs) at 7, 8 | 9, 12, 16 rows: -2.8 .. -2.6 % | -1.8 .. -1.5 %, and -1.6 .. -1.5 % for 16 utterances at the
+    // benchmark's shapes with `w8r`, `w8m` and `w8ur` on: every measured row count has its whole range below zero, so 5..8 rows (two
+    // tiles per workgroup) and 9..16 rows (two rows per wave as well) take the form where the 12-channel image serves them.  No count
+    // of the one-tile form (2..4 rows, which the image serves with `qkv_p8` below 2 only) was measured: those stay out and reach the
+    // kernel through bit 8.
+    {"w8q", "vc_request_w8_qkv_rows", &vc_engine::w8q_req, &vc_engine::w8q, 4, false, true, 5, VC_ROWS,
+     "the mask 4 (QKV)", "0, 4 (QKV) or 12 (at every row count)", nullptr},
+};
+inline bool w8_rows_win(int form, int rows) { return rows >= W8_FORMS[form].rows_lo && rows <= W8_FORMS[form].rows_hi; }
+inline bool w8_value_ok(const W8Form& f, int v) {
+  const int every = f.every_rows ? 8 : 0;
+  return f.subset ? v >= 0 && !(v & ~(f.bits | every)) : v == 0 || v == f.bits || v == (f.bits | every);
+}
 
 // What a pass leaves for the heads in hB: finished rows (n_parts = 0; hq: their centred copy, on the means in mu) or rows whose
 // n_parts split-K slabs and last FFN-down bias are still to be added.

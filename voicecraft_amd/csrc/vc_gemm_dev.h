@@ -185,3 +185,17 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& a, f32x4 (&acc)[MT
   }
 }
 
+// Host side of a launch with more than `free_bytes` of dynamic LDS (64 KB come without asking): the size is granted once per kernel
+// and device, and again when a launch needs more.  granted: the kernel's own size_t[16], zero-initialised, one word per device.
+static inline hipError_t grant_lds(const void* kern, size_t* granted, size_t lds, size_t free_bytes = 64 * 1024) {
+  if (lds <= free_bytes) return hipSuccess;
+  int dev = 0;
+  if (hipError_t ge = hipGetDevice(&dev); ge != hipSuccess) return ge;
+  if (dev >= 0 && dev < 16 && lds > granted[dev]) {
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    granted[dev] = lds;
+  }
+  return hipSuccess;
+}
+

@@ -9,7 +9,7 @@
 // No data-dependent branch, no dependent load: the side bytes are wave-uniform and on their way with the burst.
 // Prologue, epilogue and summation order are the bf16 kernels', the MFMA operands are bit-identical, so every result is.
 // Measured at giga830M (one row, 654 steps, in-process A/B of option w13, profiles/w13_ab.log): see DESIGN section 4.6.
-// The packer and its check run once per matrix at creation (vc_engine.hip pack_planes): a matrix with a fragment the codes cannot hold,
+// The packer and its check run once per matrix at creation (vc_engine.hip pack_checked): a matrix with a fragment the codes cannot hold,
 // or whose planes do not decode to the image bit for bit, keeps its bf16 kernel.
 #include "vc_gemm_fr1.h"
 #include "vc_w13.h"

@@ -7,7 +7,7 @@
 // with four v_cvt_scalef32_pk_bf16_fp8 right in front of its MFMA; the scale is the fragment's side byte shifted into an fp32
 // exponent, a wave-uniform scalar.  No data-dependent branch, no dependent load.
 // Prologue, epilogue and summation order are the bf16 kernels', the MFMA operands are bit-identical, so every result is.
-// The packer and its check run once per matrix at creation (vc_engine.hip pack_planes, on request: vc_request_w8): the check decodes with
+// The packer and its check run once per matrix at creation (vc_engine.hip pack_checked, on request: vc_request_w8): the check decodes with
 // the instruction the kernels use, so a matrix off the grid - or a surprise in the instruction - keeps the bf16 kernel.
 #include "vc_gemm_fr1.h"
 #include "vc_w8.h"
@@ -83,6 +83,33 @@ __device__ __forceinline__ uint4 w8_frag(const uint4& pa, const uint4& pb, uint3
   return w;
 }
 
+// The weight source of the five kernels on the group planes, written once: a wave owns NO_ runs of NG consecutive groups, run o
+// starting NW * NG groups behind run o - 1 (NO_ = 1: its share of one tile; NTQ: of the workgroup's tiles; 2: of a tile's two halves of
+// K), the first at group G0 = ((TILE_ NO_) NW + wave) NG.  The macros see the body's wave and wunit, the kernel's NG, NW and wa.
+// VC_W8_SIDE: the wave's side bytes - scalar operands, first needed long after the burst is out.
+#define VC_W8_SIDE(NO_, TILE_)                                                                                                         \
+  const long G0 = ((long)(TILE_) * (NO_) * NW + wave) * NG;                                                                            \
+  uint32_t sb[NO_][NG];                                                                                                                \
+  _Pragma("unroll") for (int o_ = 0; o_ < (NO_); ++o_)                                                                                 \
+    _Pragma("unroll") for (int g = 0; g < NG; ++g) sb[o_][g] = wa.side[G0 + o_ * (NW * NG) + g];
+// VC_W8_PLANES: the lane's two pieces of every group.  VC_W8_BURST: the wave's whole share of the code bytes in one burst, run by run
+// and group by group (loads return in order: group g decodes while g + 1.. land); the sched_barrier keeps the requests in that
+// order: the counted waits of the MFMA steps release a group as it lands; the pins: the side words are on their way with n_active, not
+// behind the prologue.
+#define VC_W8_PLANES(NO_)                                                                                                              \
+  const uint4* gbase = wa.planes + G0 * VC_W8_GROUP_U4;                  /* wave-uniform */                                             \
+  uint4 pa[NO_][NG], pb[NO_][NG];
+#define VC_W8_BURST(NO_)                                                                                                               \
+  _Pragma("unroll") for (int o_ = 0; o_ < (NO_); ++o_)                                                                                 \
+    _Pragma("unroll") for (int g = 0; g < NG; ++g) {                                                                                   \
+      const uint4* gp = gbase + (o_ * (NW * NG) + g) * VC_W8_GROUP_U4;                                                                 \
+      pa[o_][g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + wunit)));                   \
+      pb[o_][g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + 64 + wunit)));              \
+      __builtin_amdgcn_sched_barrier(0);                                                                                               \
+    }                                                                                                                                  \
+  _Pragma("unroll") for (int o_ = 0; o_ < (NO_); ++o_)                                                                                 \
+    _Pragma("unroll") for (int g = 0; g < NG; ++g) asm volatile("" : "+s"(sb[o_][g]));
+
 // The shared body (vc_gemm_fr1_body.h) on the code bytes: the wave's NG groups in place of its 4 NG fragments.  The matrix has exactly
 // NW * NG groups per tile (host contract).
 template <int NG, int NW, int PRO, int EPI>
@@ -91,25 +118,9 @@ __global__ __launch_bounds__(64 * NW) void row_gemm_fr1_w8_k(const W8Args wa) {
   constexpr int NPW = 4 * NG, GROUP = 4;
   constexpr bool EXACT = true;
   const GemmArgs& a = wa.g;
-  /* the wave's side bytes: scalar operands, first needed long after the burst is out */
-#define VC_FR1_EARLY                                                                                                                   \
-  const long G0 = ((long)nt * NW + wave) * NG;                                                                                         \
-  uint32_t sb[NG];                                                                                                                     \
-  _Pragma("unroll") for (int g = 0; g < NG; ++g) sb[g] = wa.side[G0 + g];
-  /* the wave's whole share of the code bytes in one burst, group by group (loads return in order: group g decodes while g + 1.. land); */
-  /* the sched_barrier keeps the requests in group order: the counted waits of the MFMA steps release group g as it lands; */
-  /* the pins: the side words are on their way with n_active, not behind the prologue */
-#define VC_FR1_BURST                                                                                                                   \
-  const uint4* gbase = wa.planes + G0 * VC_W8_GROUP_U4;                  /* wave-uniform */                                             \
-  uint4 pa[NG], pb[NG];                                                                                                                \
-  _Pragma("unroll") for (int g = 0; g < NG; ++g) {                                                                                     \
-    const uint4* gp = gbase + g * VC_W8_GROUP_U4;                                                                                      \
-    pa[g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + wunit)));                         \
-    pb[g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + 64 + wunit)));                    \
-    __builtin_amdgcn_sched_barrier(0);                                                                                                 \
-  }                                                                                                                                    \
-  _Pragma("unroll") for (int g = 0; g < NG; ++g) asm volatile("" : "+s"(sb[g]));
-#define VC_FR1_FRAG(F, w) const uint4 w = w8_frag<F>(pa[g], pb[g], sb[g]);
+#define VC_FR1_EARLY VC_W8_SIDE(1, nt)
+#define VC_FR1_BURST VC_W8_PLANES(1) VC_W8_BURST(1)
+#define VC_FR1_FRAG(F, w) const uint4 w = w8_frag<F>(pa[0][g], pb[0][g], sb[0][g]);
 #include "vc_gemm_fr1_body.h"
 }
 
@@ -133,21 +144,9 @@ __global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_frp_w8_k(const W8A
   using WT = bf16_t;
   constexpr int NPW = 4 * NG, GROUP = 4;
   const GemmArgs& a = wa.g;
-#define VC_FRP_EARLY                                                                                                                   \
-  const long G0 = ((long)nt * NW + wave) * NG;                                                                                         \
-  uint32_t sb[NG];                                                                                                                     \
-  _Pragma("unroll") for (int g = 0; g < NG; ++g) sb[g] = wa.side[G0 + g];
-#define VC_FRP_BURST                                                                                                                   \
-  const uint4* gbase = wa.planes + G0 * VC_W8_GROUP_U4;                  /* wave-uniform */                                             \
-  uint4 pa[NG], pb[NG];                                                                                                                \
-  _Pragma("unroll") for (int g = 0; g < NG; ++g) {                                                                                     \
-    const uint4* gp = gbase + g * VC_W8_GROUP_U4;                                                                                      \
-    pa[g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + wunit)));                         \
-    pb[g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + 64 + wunit)));                    \
-    __builtin_amdgcn_sched_barrier(0);                                                                                                 \
-  }                                                                                                                                    \
-  _Pragma("unroll") for (int g = 0; g < NG; ++g) asm volatile("" : "+s"(sb[g]));
-#define VC_FRP_FRAG(F, w) const uint4 w = w8_frag<F>(pa[g], pb[g], sb[g]);
+#define VC_FRP_EARLY VC_W8_SIDE(1, nt)
+#define VC_FRP_BURST VC_W8_PLANES(1) VC_W8_BURST(1)
+#define VC_FRP_FRAG(F, w) const uint4 w = w8_frag<F>(pa[0][g], pb[0][g], sb[0][g]);
 #include "vc_gemm_frp_body.h"
 }
 // Three tiles per workgroup: group g of tile t of wave w = (((3 blockIdx.x + t) NW + w) NG + g), requested tile by tile as the image is.
@@ -156,23 +155,8 @@ __global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_qp_w8_k(const W8Ar
   using WT = bf16_t;
   constexpr int NPW = 4 * NG, GROUP = 4;
   const GemmArgs& a = wa.g;
-#define VC_QP_EARLY                                                                                                                    \
-  const long G0 = ((long)blockIdx.x * NTQ * NW + wave) * NG;             /* tile t: + t * NW * NG */                                    \
-  uint32_t sb[NTQ][NG];                                                                                                                \
-  _Pragma("unroll") for (int t = 0; t < NTQ; ++t)                                                                                      \
-    _Pragma("unroll") for (int g = 0; g < NG; ++g) sb[t][g] = wa.side[G0 + t * (NW * NG) + g];
-#define VC_QP_BURST                                                                                                                    \
-  const uint4* gbase = wa.planes + G0 * VC_W8_GROUP_U4;                  /* wave-uniform */                                             \
-  uint4 pa[NTQ][NG], pb[NTQ][NG];                                                                                                      \
-  _Pragma("unroll") for (int t = 0; t < NTQ; ++t)                                                                                      \
-    _Pragma("unroll") for (int g = 0; g < NG; ++g) {                                                                                   \
-      const uint4* gp = gbase + (t * (NW * NG) + g) * VC_W8_GROUP_U4;                                                                  \
-      pa[t][g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + wunit)));                    \
-      pb[t][g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + 64 + wunit)));               \
-      __builtin_amdgcn_sched_barrier(0);                                                                                               \
-    }                                                                                                                                  \
-  _Pragma("unroll") for (int t = 0; t < NTQ; ++t)                                                                                      \
-    _Pragma("unroll") for (int g = 0; g < NG; ++g) asm volatile("" : "+s"(sb[t][g]));
+#define VC_QP_EARLY VC_W8_SIDE(NTQ, blockIdx.x)
+#define VC_QP_BURST VC_W8_PLANES(NTQ) VC_W8_BURST(NTQ)
 #define VC_QP_FRAG(t, F, w) const uint4 w = w8_frag<F>(pa[t][g], pb[t][g], sb[t][g]);
 #include "vc_gemm_qp_body.h"
 }
@@ -193,15 +177,7 @@ int vc_gemm_qp_w8_ng(int rows, int N, int K, int dtype) {
 }
 // the launch of one of the two kernels: dynamic LDS beyond 64 KB is granted once per kernel and device
 static hipError_t launch_rows_w8(void (*kern)(const W8Args), size_t* granted, const W8Args& wa, int grid, size_t lds, int lc, hipStream_t s) {
-  if (lds > 64 * 1024) {
-    int dev = 0;
-    if (hipError_t ge = hipGetDevice(&dev); ge != hipSuccess) return ge;
-    if (dev >= 0 && dev < 16 && lds > granted[dev]) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      granted[dev] = lds;
-    }
-  }
+  if (hipError_t e = grant_lds(reinterpret_cast<const void*>(kern), granted, lds); e != hipSuccess) return e;
   ++vc_launch_counts[lc];                      // the form the image kernel counts in
   ++vc_launch_counts[VC_LC_W8_ROWS];
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * VC_FR_WAVES), lds, s, wa);
@@ -280,25 +256,12 @@ __global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_fr_w8_k(const W8Ar
   constexpr int KTW = 8 * NG, GROUP = 8, PRO = PRO_PLAIN, NS = 1;
   constexpr bool P16 = false, CHUNKS = false;
   const GemmArgs& a = wa.g;
-#define VC_FR_EARLY                                                                                                                    \
-  const long G0 = ((long)nt * NW + wave) * NG;                                                                                         \
-  uint32_t sb[NG];                                                                                                                     \
-  _Pragma("unroll") for (int g = 0; g < NG; ++g) sb[g] = wa.side[G0 + g];
+#define VC_FR_EARLY VC_W8_SIDE(1, nt)
 #define VC_FR_WDECL                                                                                                                    \
   const int wunit = (m >> 3) * SPT + kg * TH + (m & 7);                                                                                \
-  const uint4* gbase = wa.planes + G0 * VC_W8_GROUP_U4;                  /* wave-uniform */                                             \
-  uint4 pa[NG], pb[NG];
-#define VC_FR_WEIGHTS(c_)                                                                                                              \
-  {                                                                                                                                    \
-    _Pragma("unroll") for (int g = 0; g < NG; ++g) {                                                                                   \
-      const uint4* gp = gbase + g * VC_W8_GROUP_U4;                                                                                    \
-      pa[g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + wunit)));                       \
-      pb[g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + 64 + wunit)));                  \
-      __builtin_amdgcn_sched_barrier(0);                                                                                               \
-    }                                                                                                                                  \
-    _Pragma("unroll") for (int g = 0; g < NG; ++g) asm volatile("" : "+s"(sb[g]));                                                     \
-  }
-#define VC_FR_FRAG(J, w) const uint4 w = w8_ktile<(J) & 1>(w8_frag<((J) >> 1)>(pa[g], pb[g], sb[g]));
+  VC_W8_PLANES(1)
+#define VC_FR_WEIGHTS(c_) { VC_W8_BURST(1) }
+#define VC_FR_FRAG(J, w) const uint4 w = w8_ktile<(J) & 1>(w8_frag<((J) >> 1)>(pa[0][g], pb[0][g], sb[0][g]));
 #include "vc_gemm_fr_body.h"
 }
 // K in two halves (d = 2048: NG = 2 per half): a tile has 2 NW NG groups, half h of wave w = groups ((2 nt + h) NW + w) NG + g, both
@@ -308,25 +271,11 @@ __global__ __launch_bounds__(64 * VC_FR_WAVES) void rows_gemm_fr2_w8_k(const W8A
   using WT = bf16_t;
   constexpr int KTW = 8 * NG, GROUP = 8;
   const GemmArgs& a = wa.g;
-#define VC_FR2_EARLY                                                                                                                   \
-  const long G0 = ((long)nt * 2 * NW + wave) * NG;                       /* half h: + h * NW * NG */                                    \
-  uint32_t sb[2][NG];                                                                                                                  \
-  _Pragma("unroll") for (int h = 0; h < 2; ++h)                                                                                        \
-    _Pragma("unroll") for (int g = 0; g < NG; ++g) sb[h][g] = wa.side[G0 + h * (NW * NG) + g];
+#define VC_FR2_EARLY VC_W8_SIDE(2, nt)
 #define VC_FR2_WDECL                                                                                                                   \
   const int wunit = (m >> 3) * SPT + kg * TH + (m & 7);                                                                                \
-  const uint4* gbase = wa.planes + G0 * VC_W8_GROUP_U4;                  /* wave-uniform */                                             \
-  uint4 pa[2][NG], pb[2][NG];
-#define VC_FR2_BURST                                                                                                                   \
-  _Pragma("unroll") for (int h = 0; h < 2; ++h)                                                                                        \
-    _Pragma("unroll") for (int g = 0; g < NG; ++g) {                                                                                   \
-      const uint4* gp = gbase + (h * (NW * NG) + g) * VC_W8_GROUP_U4;                                                                  \
-      pa[h][g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + wunit)));                    \
-      pb[h][g] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp + 64 + wunit)));               \
-      __builtin_amdgcn_sched_barrier(0);                                                                                               \
-    }                                                                                                                                  \
-  _Pragma("unroll") for (int h = 0; h < 2; ++h)                                                                                        \
-    _Pragma("unroll") for (int g = 0; g < NG; ++g) asm volatile("" : "+s"(sb[h][g]));
+  VC_W8_PLANES(2)
+#define VC_FR2_BURST VC_W8_BURST(2)
 #define VC_FR2_FRAG(h_, J, w) const uint4 w = w8_ktile<(J) & 1>(w8_frag<((J) >> 1)>(pa[h_][g], pb[h_][g], sb[h_][g]));
 #include "vc_gemm_fr2_body.h"
 }
@@ -371,15 +320,7 @@ hipError_t vc_launch_gemm_fr_w8(const GemmArgs& a0, const uint4* planes, const u
   else if (form == 1 && ng == 1) { kern = rows_gemm_fr_w8_k<1>; slot = 0; }
   else return hipErrorInvalidValue;
   const size_t lds = vc_gemm_fr_lds_bytes(a0.n_rows, kp, VC_DTYPE_BF16);
-  if (lds > 64 * 1024) {
-    int dev = 0;
-    if (hipError_t ge = hipGetDevice(&dev); ge != hipSuccess) return ge;
-    if (dev >= 0 && dev < 16 && lds > granted[slot][dev]) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      granted[slot][dev] = lds;
-    }
-  }
+  if (hipError_t e = grant_lds(reinterpret_cast<const void*>(kern), granted[slot], lds); e != hipSuccess) return e;
   ++vc_launch_counts[VC_LC_ROWS_GEMM_FR];      // the form the image kernel counts in
   ++vc_launch_counts[VC_LC_W8_MID];
   hipLaunchKernelGGL(kern, dim3(wa.g.n_tiles), dim3(64 * VC_FR_WAVES), lds, s, wa);
@@ -526,17 +467,10 @@ static hipError_t launch_wds_w8(const W8Args& wa, int ksplit, hipStream_t s) {
   void (*kern)(const W8Args);
   if constexpr (EPI == EPI_RELU) kern = rows_gemm_wds_w8u_k<KPW, RT>;
   else kern = rows_gemm_wds_w8_k<KPW, RT, EPI>;
-  const size_t lds = (size_t)8 * 2 * RT * 64 * sizeof(f32x4) + (size_t)8 * RT * 16 * 128;      // the image kernel's: reduction + X stages
-  {
-    static bool granted[16] = {false};       // per instantiation and device
-    int dev = 0;
-    if (hipError_t ge = hipGetDevice(&dev); ge != hipSuccess) return ge;
-    if (lds >= 64 * 1024 && dev >= 0 && dev < 16 && !granted[dev]) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      granted[dev] = true;
-    }
-  }
+  constexpr size_t lds = (size_t)8 * 2 * RT * 64 * sizeof(f32x4) + (size_t)8 * RT * 16 * 128;      // the image kernel's: reduction + X stages
+  // (this launcher asks from exactly 64 KB on, as the image launcher does: RT = 2 is 65 536 bytes)
+  static size_t granted[16] = {0};           // per instantiation and device
+  if (hipError_t e = grant_lds(reinterpret_cast<const void*>(kern), granted, lds, 64 * 1024 - 1); e != hipSuccess) return e;
   ++vc_launch_counts[VC_LC_WD];                // the form the image kernel counts in
   ++vc_launch_counts[EPI == EPI_RELU ? VC_LC_W8_UP : VC_LC_W8_WIDE];      // FFN-up (option "w8u") has a slot of its own
   hipLaunchKernelGGL(kern, dim3((wa.g.n_tiles + 1) / 2, ksplit, 1), dim3(512), lds, s, wa);
@@ -586,86 +520,11 @@ __device__ __forceinline__ uint4 w8w_frag_at(const uint4& pw, int h, uint32_t sc
 }
 template <int KTW, int NTW, bool R2>
 __global__ __launch_bounds__(256 * NTW) void rows_gemm_lnq_w8_k(const W8Args wa) {
-  using WT = bf16_t;
-  constexpr int PRO = PRO_LNQ, EPI = EPI_RELU, NP = VC_MAX_KSPLIT;
-  static_assert(KTW == 4 || KTW == 8 || KTW == 16, "pairs per wave and tile: 2, 4 or 8");
-  const GemmArgs& a = wa.g;
-  /* the wave's side bytes: scalar operands, first needed long after the burst is out */
-#define VC_ROWS_EARLY                                                                                                                  \
-  W8wSide<KTW> sd8;                                                                                                                    \
-  sd8.load(wa.side, (long)nt * a.KT + kt0 + wave * KTW);
-#define VC_ROWS_WDECL                                                                                                                  \
-  const uint4* pbase = wa.planes + (((long)nt * a.KT + kt0 + wave * KTW) >> 1) * VC_W8W_PAIR_U4 + lane;      /* wave-uniform + lane */  \
-  const int hi8 = lane & 8;                                                                                                            \
-  uint4 pw[KTW / 2];
-#define VC_ROWS_BURST                                                                                                                  \
-  _Pragma("unroll") for (int j = 0; j < KTW / 2; ++j)                                                                                  \
-    pw[j] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(pbase + (size_t)j * VC_W8W_PAIR_U4))); \
-  /* the pins: the side words are on their way with n_active, not behind the `active == 0` exit */                                    \
-  _Pragma("unroll") for (int i = 0; i < W8wSide<KTW>::NSW; ++i) asm volatile("" : "+s"(sd8.w[i]));
-#define VC_ROWS_FRAG(i_) uint4 wfi = w8w_frag_at(pw[(i_) >> 1], (i_) & 1, sd8.scale_at((i_) >> 1, hi8));
-#define VC_ROWS_W(i_) wfi
-#define VC_ROWS_REFILL(c_)
-#include "vc_gemm_rows_body.h"
-}
-
-// The one statement of "a form exists" for `rows` finished rows of an [N x K] matrix behind a centred copy: bf16, 2..16 rows, make_plan's
-// k-tiles per wave (K / 32 in one slice: the largest of 16, 8, 4, 2 that divides a quarter of them) 4, 8 or 16 in ONE chunk - K = 512,
-// 1024, 2048 -, and an even tile count where a workgroup takes two tiles (5 rows and up).  Returns the k-tiles per wave, 0 = no form.
-int vc_gemm_lnq_w8_ok(int rows, int N, int K, int dtype) {
-  if (dtype != VC_DTYPE_BF16 || rows < 2 || rows > VC_ROWS || N < 16 || N % 16 != 0 || K < 32 || K % 32 != 0) return 0;
-  const int KT = K / 32;
-  int ktw = 16;
-  while (ktw > 2 && KT % (4 * ktw) != 0) ktw >>= 1;
-  if (KT != 4 * ktw || (ktw != 4 && ktw != 8 && ktw != 16)) return 0;
-  if (rows > 4 && (N / 16) % 2 != 0) return 0;
-  return ktw;
-}
-
-template <int KTW, int NTW, bool R2>
-static hipError_t launch_lnq_w8(const W8Args& wa, hipStream_t s) {
-  void (*kern)(const W8Args) = rows_gemm_lnq_w8_k<KTW, NTW, R2>;
-  // the image launch's (launch_dec_nt, vc_gemm.hip): X rows, the reduction area per tile, statistics
-  const size_t lds = vc_gemm_lds_bytes(wa.g, VC_DTYPE_BF16, 1) + (size_t)(NTW - 1) * 4 * 64 * sizeof(f32x4);
-  if (lds > 64 * 1024) {
-    static size_t granted[16] = {0};   // per instantiation and device
-    int dev = 0;
-    if (hipError_t ge = hipGetDevice(&dev); ge != hipSuccess) return ge;
-    if (dev >= 0 && dev < 16 && lds > granted[dev]) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      granted[dev] = lds;
-    }
-  }
-  ++vc_launch_counts[VC_LC_ROWS_GEMM];         // the form the image kernel counts in
-  ++vc_launch_counts[VC_LC_W8_UP_ROWS];
-  hipLaunchKernelGGL(kern, dim3(wa.g.n_tiles / NTW, 1, 1), dim3(256 * NTW), lds, s, wa);
-  return hipGetLastError();
-}
-template <int KTW>
-static hipError_t launch_lnq_w8_form(const W8Args& wa, hipStream_t s) {
-  if (wa.g.mt == 4) return launch_lnq_w8<KTW, 2, true>(wa, s);       // 9..16 rows: two tiles per workgroup, two rows per wave
-  if (wa.g.mt == 3) return launch_lnq_w8<KTW, 2, false>(wa, s);      // 5..8 rows: two tiles per workgroup
-  return launch_lnq_w8<KTW, 1, false>(wa, s);                        // 2..4 rows
-}
-// vc_launch_gemm(a, bf16, PRO_LNQ, EPI_RELU, 1, 1) on the pair planes of a.Wp's 16-channel image (a.n_tiles tiles x a.KT k-tiles, packed
-// whole by vc_launch_w8w_pack): the same arguments, grid and LDS; a.mt picks the form as it does there.
-hipError_t vc_launch_gemm_lnq_w8(const GemmArgs& a, const uint4* planes, const uint8_t* side, hipStream_t s) {
-  const int ktw = vc_gemm_lnq_w8_ok(a.n_rows, a.N, a.K, VC_DTYPE_BF16);
-  if (!ktw || !planes || !side || a.x_in == nullptr || a.row_mu == nullptr) return hipErrorInvalidValue;
-  if (a.KT != 4 * ktw || a.nchunk != 1 || a.n_tiles != a.N / 16 || a.r_lds < a.n_rows || a.r_lds > VC_ROWS) return hipErrorInvalidValue;
-  if (a.mt != (a.n_rows > VC_FR_MAX_ROWS ? 4 : a.n_rows >= 5 ? 3 : 0)) return hipErrorInvalidValue;      // (plan_pass's rule for these rows)
-  W8Args wa;
-  wa.g = a;
-  wa.g.x_upr_shift = -1; wa.g.att_q4_shift = -1;      // (prologues this kernel does not have)
-  wa.planes = planes;
-  wa.side = reinterpret_cast<const uint32_t*>(side);      // n_tiles x KT bytes, a wave's share whole aligned words
-  switch (ktw) {
-    case 4: return launch_lnq_w8_form<4>(wa, s);
-    case 8: return launch_lnq_w8_form<8>(wa, s);
-    case 16: return launch_lnq_w8_form<16>(wa, s);
-    default: return hipErrorInvalidValue;
-  }
+  constexpr int EPI = EPI_RELU;
+#define VC_ROWS_W8_PAIR_U4 VC_W8W_PAIR_U4
+#define VC_ROWS_W8_SLOT lane
+#define VC_ROWS_W8_HI8 (lane & 8)
+#include "vc_gemm_rows_w8_body.h"
 }
 
 // ------------------------------------------------------------------ the QKV projection of 2..16 finished rows on the pairs of the 12-channel image (option "w8q")
@@ -765,84 +624,85 @@ extern "C" int vc_w8q_pack_host(const uint16_t* image12, long n_pairs, uint8_t* 
 // A kernel of its own name: rows_gemm_lnq_w8_k stays the nine FFN-up instantiations of option "w8ur".
 template <int KTW, int NTW, bool R2>
 __global__ __launch_bounds__(256 * NTW) void rows_gemm_qkvq_w8_k(const W8Args wa) {
-  using WT = bf16_t;
-  constexpr int PRO = PRO_LNQ, EPI = EPI_QKV, NP = VC_MAX_KSPLIT;
-  static_assert(KTW == 4 || KTW == 8 || KTW == 16, "pairs per wave and tile: 2, 4 or 8");
-  const GemmArgs& a = wa.g;
-  /* the wave's side bytes: scalar operands, first needed long after the burst is out */
-#define VC_ROWS_EARLY                                                                                                                  \
-  W8wSide<KTW> sd8;                                                                                                                    \
-  sd8.load(wa.side, (long)nt * a.KT + kt0 + wave * KTW);
-#define VC_ROWS_WDECL                                                                                                                  \
-  const uint4* pbase = wa.planes + (((long)nt * a.KT + kt0 + wave * KTW) >> 1) * VC_W8Q_PAIR_U4 + wslot;    /* wave-uniform + slot */  \
-  const int hi8 = (nt & 1) ? (m >= 4) : (m >= 8);      /* the lane's part */                                                           \
-  uint4 pw[KTW / 2];
-#define VC_ROWS_BURST                                                                                                                  \
-  _Pragma("unroll") for (int j = 0; j < KTW / 2; ++j)                                                                                  \
-    pw[j] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(pbase + (size_t)j * VC_W8Q_PAIR_U4))); \
-  /* the pins: the side words are on their way with n_active, not behind the `active == 0` exit */                                    \
-  _Pragma("unroll") for (int i = 0; i < W8wSide<KTW>::NSW; ++i) asm volatile("" : "+s"(sd8.w[i]));
-#define VC_ROWS_FRAG(i_) uint4 wfi = w8w_frag_at(pw[(i_) >> 1], (i_) & 1, sd8.scale_at((i_) >> 1, hi8));
-#define VC_ROWS_W(i_) wfi
-#define VC_ROWS_REFILL(c_)
-#include "vc_gemm_rows_body.h"
+  constexpr int EPI = EPI_QKV;
+#define VC_ROWS_W8_PAIR_U4 VC_W8Q_PAIR_U4
+#define VC_ROWS_W8_SLOT wslot
+#define VC_ROWS_W8_HI8 ((nt & 1) ? (m >= 4) : (m >= 8))      /* the lane's part */
+#include "vc_gemm_rows_w8_body.h"
 }
 
-// The one statement of "a form exists" for the QKV projection of `rows` finished rows of an [N x K] matrix behind a centred copy: bf16,
-// 2..16 rows, whole 12-channel tiles, make_plan's k-tiles per wave 4, 8 or 16 in ONE chunk - K = 512, 1024, 2048 -, and an even tile
-// count where a workgroup takes two tiles (5 rows and up).  Returns the k-tiles per wave, 0 = no form.
-int vc_gemm_qkvq_w8_ok(int rows, int N, int K, int dtype) {
-  if (dtype != VC_DTYPE_BF16 || rows < 2 || rows > VC_ROWS || N < VC_TH_QKV || N % VC_TH_QKV != 0 || K < 32 || K % 32 != 0) return 0;
+// ------------------------------------------------------------------ the host side of the two kernels on pairs ("w8ur", "w8q")
+// The one statement of "a form exists" for `rows` finished rows of an [N x K] matrix in tiles of `th` channels behind a centred copy:
+// bf16, 2..16 rows, whole tiles, make_plan's k-tiles per wave (K / 32 in one slice: the largest of 16, 8, 4, 2 that divides a quarter of
+// them) 4, 8 or 16 in ONE chunk - K = 512, 1024, 2048 -, and an even tile count where a workgroup takes two tiles (5 rows and up).
+// Returns the k-tiles per wave, 0 = no form.
+static int rows_w8_ok(int rows, int N, int K, int dtype, int th) {
+  if (dtype != VC_DTYPE_BF16 || rows < 2 || rows > VC_ROWS || N < th || N % th != 0 || K < 32 || K % 32 != 0) return 0;
   const int KT = K / 32;
   int ktw = 16;
   while (ktw > 2 && KT % (4 * ktw) != 0) ktw >>= 1;
   if (KT != 4 * ktw || (ktw != 4 && ktw != 8 && ktw != 16)) return 0;
-  if (rows > 4 && (N / VC_TH_QKV) % 2 != 0) return 0;
+  if (rows > 4 && (N / th) % 2 != 0) return 0;
   return ktw;
 }
+int vc_gemm_lnq_w8_ok(int rows, int N, int K, int dtype) { return rows_w8_ok(rows, N, K, dtype, 16); }              // FFN-up: the 16-channel image W1
+int vc_gemm_qkvq_w8_ok(int rows, int N, int K, int dtype) { return rows_w8_ok(rows, N, K, dtype, VC_TH_QKV); }      // QKV: the 12-channel image Wqkv
 
-template <int KTW, int NTW, bool R2>
-static hipError_t launch_qkvq_w8(const W8Args& wa, hipStream_t s) {
-  void (*kern)(const W8Args) = rows_gemm_qkvq_w8_k<KTW, NTW, R2>;
+// What differs between the two launches: the kernel, its census slot, the image's tile height, the outputs its epilogue writes.
+struct LnqW8Kind {
+  static constexpr int TH = 16, LC = VC_LC_W8_UP_ROWS;
+  template <int KTW, int NTW, bool R2> static auto kernel() { return &rows_gemm_lnq_w8_k<KTW, NTW, R2>; }
+  static bool outputs_ok(const GemmArgs&) { return true; }      // (a.out: as for the image launch, the site's)
+};
+struct QkvqW8Kind {
+  static constexpr int TH = VC_TH_QKV, LC = VC_LC_W8_QKV_ROWS;
+  template <int KTW, int NTW, bool R2> static auto kernel() { return &rows_gemm_qkvq_w8_k<KTW, NTW, R2>; }
+  static bool outputs_ok(const GemmArgs& a) { return a.q_out && a.kcache && a.vcache; }
+};
+
+template <class Kind, int KTW, int NTW, bool R2>
+static hipError_t launch_rows_pairs(const W8Args& wa, hipStream_t s) {
+  void (*kern)(const W8Args) = Kind::template kernel<KTW, NTW, R2>();
   // the image launch's (launch_dec_nt, vc_gemm.hip): X rows, the reduction area per tile, statistics
   const size_t lds = vc_gemm_lds_bytes(wa.g, VC_DTYPE_BF16, 1) + (size_t)(NTW - 1) * 4 * 64 * sizeof(f32x4);
-  if (lds > 64 * 1024) {
-    static size_t granted[16] = {0};   // per instantiation and device
-    int dev = 0;
-    if (hipError_t ge = hipGetDevice(&dev); ge != hipSuccess) return ge;
-    if (dev >= 0 && dev < 16 && lds > granted[dev]) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      granted[dev] = lds;
-    }
-  }
+  static size_t granted[16] = {0};   // per instantiation and device
+  if (hipError_t e = grant_lds(reinterpret_cast<const void*>(kern), granted, lds); e != hipSuccess) return e;
   ++vc_launch_counts[VC_LC_ROWS_GEMM];         // the form the image kernel counts in
-  ++vc_launch_counts[VC_LC_W8_QKV_ROWS];
+  ++vc_launch_counts[Kind::LC];
   hipLaunchKernelGGL(kern, dim3(wa.g.n_tiles / NTW, 1, 1), dim3(256 * NTW), lds, s, wa);
   return hipGetLastError();
 }
-template <int KTW>
-static hipError_t launch_qkvq_w8_form(const W8Args& wa, hipStream_t s) {
-  if (wa.g.mt == 4) return launch_qkvq_w8<KTW, 2, true>(wa, s);       // 9..16 rows: two tiles per workgroup, two rows per wave
-  if (wa.g.mt == 3) return launch_qkvq_w8<KTW, 2, false>(wa, s);      // 5..8 rows: two tiles per workgroup
-  return launch_qkvq_w8<KTW, 1, false>(wa, s);                        // 2..4 rows
+template <class Kind, int KTW>
+static hipError_t launch_rows_pairs_form(const W8Args& wa, hipStream_t s) {
+  if (wa.g.mt == 4) return launch_rows_pairs<Kind, KTW, 2, true>(wa, s);       // 9..16 rows: two tiles per workgroup, two rows per wave
+  if (wa.g.mt == 3) return launch_rows_pairs<Kind, KTW, 2, false>(wa, s);      // 5..8 rows: two tiles per workgroup
+  return launch_rows_pairs<Kind, KTW, 1, false>(wa, s);                        // 2..4 rows
 }
-// vc_launch_gemm(a, bf16, PRO_LNQ, EPI_QKV, 1, 1) on the pairs of a.Wp's 12-channel image (a.n_tiles tiles x a.KT k-tiles, packed whole
-// by vc_launch_w8q_pack): the same arguments, grid and LDS; a.mt picks the form as it does there.
-hipError_t vc_launch_gemm_qkvq_w8(const GemmArgs& a, const uint4* planes, const uint8_t* side, hipStream_t s) {
-  const int ktw = vc_gemm_qkvq_w8_ok(a.n_rows, a.N, a.K, VC_DTYPE_BF16);
-  if (!ktw || !planes || !side || a.x_in == nullptr || a.row_mu == nullptr || !a.q_out || !a.kcache || !a.vcache) return hipErrorInvalidValue;
-  if (a.KT != 4 * ktw || a.nchunk != 1 || a.n_tiles != a.N / VC_TH_QKV || a.r_lds < a.n_rows || a.r_lds > VC_ROWS) return hipErrorInvalidValue;
+// vc_launch_gemm(a, bf16, PRO_LNQ, the kind's epilogue, 1, 1) on the pairs of a.Wp's image (a.n_tiles tiles x a.KT k-tiles, packed whole
+// by the kind's packer): the same arguments, grid and LDS; a.mt picks the form as it does there.
+template <class Kind>
+static hipError_t launch_gemm_rows_pairs(const GemmArgs& a, const uint4* planes, const uint8_t* side, hipStream_t s) {
+  const int ktw = rows_w8_ok(a.n_rows, a.N, a.K, VC_DTYPE_BF16, Kind::TH);
+  if (!ktw || !planes || !side || a.x_in == nullptr || a.row_mu == nullptr || !Kind::outputs_ok(a)) return hipErrorInvalidValue;
+  if (a.KT != 4 * ktw || a.nchunk != 1 || a.n_tiles != a.N / Kind::TH || a.r_lds < a.n_rows || a.r_lds > VC_ROWS) return hipErrorInvalidValue;
   if (a.mt != (a.n_rows > VC_FR_MAX_ROWS ? 4 : a.n_rows >= 5 ? 3 : 0)) return hipErrorInvalidValue;      // (plan_pass's rule for these rows)
   W8Args wa;
   wa.g = a;
-  wa.g.x_upr_shift = -1; wa.g.att_q4_shift = -1;      // (prologues this kernel does not have)
+  wa.g.x_upr_shift = -1; wa.g.att_q4_shift = -1;      // (prologues these kernels do not have)
   wa.planes = planes;
   wa.side = reinterpret_cast<const uint32_t*>(side);      // n_tiles x KT bytes, a wave's share whole aligned words
   switch (ktw) {
-    case 4: return launch_qkvq_w8_form<4>(wa, s);
-    case 8: return launch_qkvq_w8_form<8>(wa, s);
-    case 16: return launch_qkvq_w8_form<16>(wa, s);
+    case 4: return launch_rows_pairs_form<Kind, 4>(wa, s);
+    case 8: return launch_rows_pairs_form<Kind, 8>(wa, s);
+    case 16: return launch_rows_pairs_form<Kind, 16>(wa, s);
     default: return hipErrorInvalidValue;
   }
+}
+// FFN-up on the pair planes of the 16-channel image W1 (vc_launch_w8w_pack), epilogue EPI_RELU
+hipError_t vc_launch_gemm_lnq_w8(const GemmArgs& a, const uint4* planes, const uint8_t* side, hipStream_t s) {
+  return launch_gemm_rows_pairs<LnqW8Kind>(a, planes, side, s);
+}
+// QKV on the pairs of the 12-channel image Wqkv (vc_launch_w8q_pack), epilogue EPI_QKV
+hipError_t vc_launch_gemm_qkvq_w8(const GemmArgs& a, const uint4* planes, const uint8_t* side, hipStream_t s) {
+  return launch_gemm_rows_pairs<QkvqW8Kind>(a, planes, side, s);
 }

@@ -16,6 +16,7 @@ import logging
 import math
 import random
 from argparse import Namespace
+from collections import namedtuple
 from typing import Iterable
 
 import torch
@@ -92,18 +93,10 @@ class VoiceCraftEngine:
         Bit-identical to the image launch on the same weights; launch_counts()["w8_qkv_rows"] counts them, w8_stats() says which
         layers have the pairs.  No new matrix is quantised (QKV is one of W8_MATRICES).  Independent of the other w8 keywords and kv8."""
         self.lib = _lib.load()
-        if w8_qkv_rows and w8 is None:
-            raise ValueError('w8_qkv_rows=True streams planes on the grid of `w8=`: give w8="quantize" or w8="as_is" too')
-        if w8_up_rows and w8 is None:
-            raise ValueError('w8_up_rows=True streams planes on the grid of `w8=`: give w8="quantize" or w8="as_is" too')
-        if w8_up and w8 is None:
-            raise ValueError('w8_up=True streams planes on the grid of `w8=`: give w8="quantize" or w8="as_is" too')
-        if w8_mid and w8 is None:
-            raise ValueError('w8_mid=True streams the planes of `w8=`: give w8="quantize" or w8="as_is" too')
-        if w8_wide and w8 is None:
-            raise ValueError('w8_wide=True streams the planes of `w8=`: give w8="quantize" or w8="as_is" too')
-        if w8_rows and w8 is None:
-            raise ValueError('w8_rows=True streams the planes of `w8=`: give w8="quantize" or w8="as_is" too')
+        asked = dict(w8_rows=w8_rows, w8_mid=w8_mid, w8_wide=w8_wide, w8_up=w8_up, w8_up_rows=w8_up_rows, w8_qkv_rows=w8_qkv_rows)
+        for form in reversed(self.W8_FORMS):      # (the newest keyword is named first, as it always was)
+            if asked[form.keyword] and w8 is None:
+                raise ValueError(f'{form.keyword}=True streams planes on the grid of `w8=`: give w8="quantize" or w8="as_is" too')
         if isinstance(kv8, str) and kv8 != "centred":
             raise ValueError(f'kv8 = {kv8!r}: False, True or "centred"')
         a = Namespace(**args) if isinstance(args, dict) else Namespace(**vars(args))
@@ -150,22 +143,10 @@ class VoiceCraftEngine:
         check(self.lib.vc_create(C.byref(cfg), index, C.byref(self._h)), None, "vc_create")
         if w8 is not None:
             check(self.lib.vc_request_w8(self._h, self.W8_MASK), self._h, "vc_request_w8")
-        if w8_rows:
-            check(self.lib.vc_request_w8_rows(self._h, self.W8_ROWS_MASK), self._h, "vc_request_w8_rows")
-        if w8_mid:
-            check(self.lib.vc_request_w8_mid(self._h, self.W8_MID_MASK), self._h, "vc_request_w8_mid")
-        self.w8_wide = bool(w8_wide)
-        if w8_wide:
-            check(self.lib.vc_request_w8_wide(self._h, self.W8_WIDE_MASK), self._h, "vc_request_w8_wide")
-        self.w8_up = bool(w8_up)
-        if w8_up:
-            check(self.lib.vc_request_w8_up(self._h, self.W8_UP_MASK), self._h, "vc_request_w8_up")
-        self.w8_up_rows = bool(w8_up_rows)
-        if w8_up_rows:
-            check(self.lib.vc_request_w8_up_rows(self._h, self.W8_UP_ROWS_MASK), self._h, "vc_request_w8_up_rows")
-        self.w8_qkv_rows = bool(w8_qkv_rows)
-        if w8_qkv_rows:
-            check(self.lib.vc_request_w8_qkv_rows(self._h, self.W8_QKV_ROWS_MASK), self._h, "vc_request_w8_qkv_rows")
+        for form in self.W8_FORMS:                # self.w8_rows .. self.w8_qkv_rows: what w8_stats() reports
+            setattr(self, form.keyword, bool(asked[form.keyword]))
+            if asked[form.keyword]:
+                check(getattr(self.lib, form.request)(self._h, getattr(self, form.mask)), self._h, form.request)
         self.kv8 = bool(kv8)
         self.kv8_centred = kv8 == "centred"
         if self.kv8_centred:
@@ -826,6 +807,18 @@ class VoiceCraftEngine:
     W8_UP_MASK = 2                          # option `w8u` of an engine created with w8_up=True (FFN-up)
     W8_UP_ROWS_MASK = 2                     # option `w8ur` of an engine created with w8_up_rows=True (FFN-up)
     W8_QKV_ROWS_MASK = 4                    # option `w8q` of an engine created with w8_qkv_rows=True (QKV)
+    # One entry per keyword behind `w8=` (csrc/vc_engine_host.h W8_FORMS): the option it switches on, the request made at creation in
+    # this order with the mask of the named class attribute, and where the form packs planes of its own the debug buffer of their
+    # per-layer {state, refused pairs} with the w8_stats() key of each matrix in it.
+    W8Form = namedtuple("W8Form", "keyword option request mask stats keys")
+    W8_FORMS = (
+        W8Form("w8_rows", "w8r", "vc_request_w8_rows", "W8_ROWS_MASK", None, ()),
+        W8Form("w8_mid", "w8m", "vc_request_w8_mid", "W8_MID_MASK", None, ()),
+        W8Form("w8_wide", "w8w", "vc_request_w8_wide", "W8_WIDE_MASK", "w8w_stats", ("ffn_down_wide", "qkv_wide")),
+        W8Form("w8_up", "w8u", "vc_request_w8_up", "W8_UP_MASK", "w8u_stats", ("ffn_up_wide",)),
+        W8Form("w8_up_rows", "w8ur", "vc_request_w8_up_rows", "W8_UP_ROWS_MASK", "w8ur_stats", ("ffn_up_rows",)),
+        W8Form("w8_qkv_rows", "w8q", "vc_request_w8_qkv_rows", "W8_QKV_ROWS_MASK", "w8q_stats", ("qkv_rows",)),
+    )
 
     def w8_stats(self) -> list:
         """w13_stats() for option `w8`: per layer {"ffn_down" | "qkv": {"state": "packed" | "refused" | "not_applicable",
@@ -840,23 +833,12 @@ class VoiceCraftEngine:
         v = self.debug_read("w8_stats", (L, 2, 2), torch.int32).tolist()
         out = [{m: {"state": self.W13_STATES[v[l][i][0]], "refused_fragments": v[l][i][1]} for i, m in enumerate(self.W8_MATRICES)}
                for l in range(L)]
-        if self.w8_wide:
-            w = self.debug_read("w8w_stats", (L, 2, 2), torch.int32).tolist()
-            for l in range(L):
-                for i, m in enumerate(self.W8_MATRICES):
-                    out[l][m + "_wide"] = {"state": self.W13_STATES[w[l][i][0]], "refused_pairs": w[l][i][1]}
-        if self.w8_up:
-            u = self.debug_read("w8u_stats", (L, 2), torch.int32).tolist()
-            for l in range(L):
-                out[l]["ffn_up_wide"] = {"state": self.W13_STATES[u[l][0]], "refused_pairs": u[l][1]}
-        if self.w8_up_rows:
-            u = self.debug_read("w8ur_stats", (L, 2), torch.int32).tolist()
-            for l in range(L):
-                out[l]["ffn_up_rows"] = {"state": self.W13_STATES[u[l][0]], "refused_pairs": u[l][1]}
-        if self.w8_qkv_rows:
-            u = self.debug_read("w8q_stats", (L, 2), torch.int32).tolist()
-            for l in range(L):
-                out[l]["qkv_rows"] = {"state": self.W13_STATES[u[l][0]], "refused_pairs": u[l][1]}
+        for form in self.W8_FORMS:
+            if form.stats and getattr(self, form.keyword):
+                w = self.debug_read(form.stats, (L, len(form.keys), 2), torch.int32).tolist()
+                for l in range(L):
+                    for i, key in enumerate(form.keys):
+                        out[l][key] = {"state": self.W13_STATES[w[l][i][0]], "refused_pairs": w[l][i][1]}
         return out
 
     def debug_read(self, name: str, shape, dtype=torch.float32) -> torch.Tensor:
