@@ -87,6 +87,8 @@ SBS = "blk128_sbs"
 BIG = "big256"
 T1808, T2048, T1792 = (14, 9, 17, 12, 20, 11, 16, 14), (14, 18, 12, 20, 17, 15, 13, 19), (14, 9, 17, 12, 20, 11, 15, 14)
 T2304 = (14, 18, 12, 20, 17, 15, 13, 22, 13)          # utterance 7 holds rows 1744 .. 2095: across the pass boundary at 2048 (and 1040 is inside 4)
+T656, T1296 = (17, 13, 11), (14, 18, 12, 20, 17)
+ODD_PRESETS = ("w768_h12", "w768_h24", "w1280_h10", "w1536_h24", "w1792_h14", "w1792_h56")
 T400, T1024, T1040, T1552, T1904 = (9, 7, 9), (17, 13, 20, 14), (17, 12, 19, 14, 3), (17, 13, 20, 14, 18, 15), (14, 18, 12, 20, 17, 15, 13, 10)
 
 
@@ -114,6 +116,16 @@ def _cases():
     add("e-big-1552", "eval", "giga830M", "bf16", _rows(T1552, _slack(6)), (("QKV16", BIG, SBS, BIG, BIG),), max_seqs=17,
         pins="seven blocks: big256 on the 16-channel QKV image")
     add("e-big-2048", "eval", "giga830M", "bf16", _rows(T2048, _slack(8)), (("QKV", BIG, SBS, BIG, BIG),), pins="eight full 256-row blocks")
+    # ---- widths that are no power of two (tests/odd_width_cases.py has their decode steps): 10 .. 56 heads in the QKV epilogue's cache
+    # write and in tile_attn_k's grid, K = 768 .. 1792 and 4 K in the block GEMMs; then each block form beyond blk64 at the smallest stream
+    # at which the launch rules take it, at the width where that stream is cheapest
+    for preset in ODD_PRESETS:
+        for dtype in ("bf16", "fp32") if preset in ("w768_h12", "w1280_h10", "w1792_h56") else ("bf16",):
+            add(f"e-small-{preset}-{dtype}", "eval", preset, dtype, small, (("QKV",) + B64,), pins="blk64 at an odd width, ragged last tile")
+    add("e-sbs-1280-fp32", "eval", "w1280_h10", "fp32", _rows(T656, _slack(3)), (("QKV", SBS, "blk64", SBS, SBS),),
+        pins="blk128_sbs at d = 1280: 40 x 6 blocks of QKV reach 240 workgroups from 641 rows on")
+    add("e-big-1792", "eval", "w1792_h56", "bf16", _rows(T1296, _slack(5)), (("QKV", BIG, "blk64", BIG, BIG),),
+        pins="big256 at d = 1792: 28 x 6 blocks of QKV reach 160 workgroups from 1 281 rows on; the out-projection (7 x 6) stays on blk64")
     # ---- more than one pass: rows of pass 2 attend to cache rows of pass 1; one utterance lies across the boundary
     add("e-pass-tiny128-fp32-2304", "eval", "tiny128", "fp32", _rows(T2304, _slack(9)),
         (("QKV", SBS, "blk64", SBS, SBS), ("QKV",) + B64), pins="default pass size, stream of 2 304 rows: passes of 2 048 + 256")
@@ -338,7 +350,7 @@ class RowsOracle(VoiceCraftOracle):
     `self.defect` = (kind, layer, ...) is a defect model of tests/test_prefill_rows_cpu.py, in oracle coordinates (batch index, row):
       ("swap", l, b, r1, r2)        FFN-down of layer l leaves rows r1 and r2 exchanged
       ("copy", l, b, r, b2, r2)     ... leaves row (b2, r2) in the place of row (b, r)
-      ("chunk", l, b, r, k0)        ... drops the 256-wide K chunk at k0 from row (b, r)
+      ("chunk", l, b, r, k0[, w])   ... drops the w-wide (256 unless given) K chunk at k0 from row (b, r)
       ("slot", l, b, r, b2, r2)     layer l's K/V of row (b, r) are written to slot b2 (row r2: the same position there); slot b keeps zeros"""
 
     def __init__(self, args, state_dict, dtype=torch.float32):
@@ -391,8 +403,9 @@ class RowsOracle(VoiceCraftOracle):
                     _, _, b, r, b2, r2 = self.defect
                     h[b, r] = h[b2, r2]
                 else:
-                    _, _, b, r, k0 = self.defect
-                    h[b, r] = h[b, r] - self.sd[p + "linear2.weight"][:, k0: k0 + 256] @ act[b, r, k0: k0 + 256]
+                    _, _, b, r, k0 = self.defect[:5]
+                    k1 = k0 + (self.defect[5] if len(self.defect) > 5 else 256)
+                    h[b, r] = h[b, r] - self.sd[p + "linear2.weight"][:, k0: k1] @ act[b, r, k0: k1]
             x = x + h
             pres.append(pr)
         x = F.layer_norm(x, (self.d,), self.sd["decoder.norm.weight"], self.sd["decoder.norm.bias"], 1e-5)

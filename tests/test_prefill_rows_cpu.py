@@ -7,6 +7,8 @@
     checker flags exactly the damaged rows at the first layer that shows them and nothing outside their causal cone afterwards, while
     the relative L2 of every utterance's LAST logits row (what every other parity test reads) stays under the 2e-2 bar;
   * the fp32 bar is not met by luck: the oracle in fp64 against itself in fp32 stays inside it on every case of the two tiny widths."""
+import dataclasses
+
 import numpy as np
 import pytest
 import torch
@@ -15,7 +17,7 @@ import prefill_rows_cases as pc
 
 STREAMS = {"e-small": 272, "e-sbs-512": 1808, "e-sbs-512-full": 2048, "e-sbs-512-edge": 1792, "e-sbs-2048": 400, "e-big-1024": 1024,
            "e-big-1040": 1040, "e-big-1552": 1552, "e-big-2048": 2048, "e-pass-tiny128-fp32": 2304, "e-pass-giga-bf16": 1552,
-           "p-tts": 224, "p-tts-bf16-attn64": 256, "p-multi-tiny128": 1808, "p-multi-giga": 1904}
+           "p-tts": 224, "p-tts-bf16-attn64": 256, "p-multi-tiny128": 1808, "p-multi-giga": 1904, "e-sbs-1280": 656, "e-big-1792": 1296}
 
 
 def _stream_of(name):
@@ -39,7 +41,7 @@ def test_the_table_holds_what_it_claims():
         # the forms, as the engine's rules give them
         assert pc.derived_forms(c) == c.forms, (c.name, pc.derived_forms(c))
         assert len(c.forms) == len(c.pass_rows)
-        big = c.dtype == "bf16" and a.d_model == 2048
+        big = c.dtype == "bf16" and a.d_model in (1792, 2048)          # (d = 1792: the odd width at which big256 is cheapest, e-big-1792)
         for f, rows in zip(c.forms, c.pass_rows):
             assert (pc.BIG in f) <= (big and rows > 1024), (c.name, f)
             seen |= {(f[1], f[0]), (f[2], "PART"), (f[3], "RELU"), (f[4], "PART")}
@@ -58,6 +60,12 @@ def test_the_table_holds_what_it_claims():
     for form in ("blk64", pc.SBS, pc.BIG):
         for epi in ("QKV", "QKV16", "PART", "RELU"):
             assert (form, epi) in seen, (form, epi)
+    # the odd widths: every preset on blk64, and each further form at the smallest stream that takes it at its width (one tile less: not yet)
+    assert {c.preset for c in pc.CASES if c.name.startswith("e-small-w")} == set(pc.ODD_PRESETS)
+    for name, form in (("e-sbs-1280-fp32", pc.SBS), ("e-big-1792", pc.BIG)):
+        c = pc.BY_NAME[name]
+        shorter = dataclasses.replace(c, name="shorter", rows=(c.stream - 16,))
+        assert form in c.forms[0] and form not in pc.derived_forms(shorter)[0] and c.preset in pc.ODD_PRESETS, name
     small = pc.layout("e-small-tiny128-fp32")
     assert int(small.valid[256:].sum()) == 3 and small.R - 256 == 16, "the last block: one tile with three valid rows"
     multi = [c for c in pc.CASES if len(c.pass_rows) > 1]

@@ -22,6 +22,14 @@ PRESETS = {
     "tiny_h16": (512, 16, 2),     # 16 heads of 32: batched decode reaches the 4- and 2-split attention merges
     "giga330M": (1024, 16, 24),   # assumed shape: not stated in the reference tree
     "giga830M": (2048, 16, 16),   # z_scripts/e830M.sh:34-37
+    # widths that are no power of two (tests/odd_width_cases.py): the staging prologues divide instead of shifting, a wave of the
+    # finished-row producers owns 3 / 5 / 7 k-chunks, the one-row kernel clamps its pairs, and the head counts are no power of two
+    "w768_h12": (768, 12, 2),     # head_dim 64
+    "w768_h24": (768, 24, 2),     # head_dim 32
+    "w1280_h10": (1280, 10, 2),   # head_dim 128
+    "w1536_h24": (1536, 24, 2),   # head_dim 64
+    "w1792_h14": (1792, 14, 2),   # head_dim 128
+    "w1792_h56": (1792, 56, 2),   # head_dim 32
 }
 
 
